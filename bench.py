@@ -27,9 +27,11 @@ max of seconds).  When launched WITHOUT a launcher (`WORLD_SIZE` unset) and --gp
 process starts the N ranks itself, as child processes, BEFORE anything touches the GPU (torch is not
 even imported in the parent), relays rank 0's JSON line and exits with the worst child status.
 
-Rank 0 prints ONE JSON line.  Besides the headline it carries `roofline`, `cpu_baseline` (N = 1) and
-`also`: the other hot-path kernels (resynth soft / IBM = configs[2] / [3], CompCeps, rfft256), a few
-steps each, timed in the same run.
+Rank 0 prints ONE JSON line.  A plain run measures the headline only: set-up, --warmup steps, the --steps
+timed steps, the `roofline` of those steps, and, with --dump-outputs DIR, the last timed step's results
+written to DIR as .npy files.  With --full the line also carries `cpu_baseline` and `parity_check`
+(N = 1), `end_to_end`, `also`: the other hot-path kernels (resynth soft / IBM = configs[2] / [3],
+CompCeps, rfft256, ...), a few steps each, and the `configs4` object, all timed in the same run.
 """
 import argparse
 import contextlib
@@ -80,7 +82,16 @@ def parse_args(argv=None):
                     help="host threads for the CPU baseline (default 0 = every CPU this process may run on; 16 is reported beside)")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="no GPU work: launcher, gloo rendezvous, shard assignment and the job reduction only (CPU tests)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baseline, end_to_end, the also-array and the configs4 object "
+                         "(each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (rank 0's shard; float32 / float64, "
+                         "a fixed seeded sample of the utterances when the whole output would not fit in 60 MiB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -794,6 +805,36 @@ def end_to_end(batch, steps):
                                        "the reference CPU needs ~12 us per frame (BASELINE.md section 2)"}}
 
 
+DUMP_BYTES = 60 << 20   # --dump-outputs: at most this much in all (under 64 MB)
+
+
+def dump_outputs(dirname, batch, ids, result):
+    """--dump-outputs: what the caller of the timed path receives from its last step, as .npy files in `dirname`.
+    ns_denoise_batch returns the packed int16 output and first_out (int32 per utterance): written are
+      first_out.npy          float64 [n_utt], every utterance of the shard
+      denoised.npy           float32, the full-frame output samples of the chosen utterances, back to back
+      utterance_ids.npy      float64, corpus ids of the chosen utterances (ascending)
+      utterance_lengths.npy  float64, their lengths in denoised.npy
+    The utterances are all of the shard when they fit in DUMP_BYTES, else a fixed seeded sample of them: the same
+    arguments give the same files on every build."""
+    out, _, first = result
+    got = batch.split(out, full_frames_only=True)
+    budget = (DUMP_BYTES - 8 * 3 * len(got) - (1 << 16)) // 4
+    pick, n = [], 0
+    for u in (np.arange(len(got)) if sum(len(g) for g in got) <= budget else np.random.default_rng(80).permutation(len(got))):
+        if n + len(got[u]) <= budget:
+            pick.append(int(u))
+            n += len(got[u])
+    pick.sort()
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"first_out": first.cpu().numpy().astype(np.float64),
+              "denoised": np.concatenate([got[u] for u in pick] or [np.zeros(0, np.int16)]).astype(np.float32),
+              "utterance_ids": np.array([ids[u] for u in pick], dtype=np.float64),
+              "utterance_lengths": np.array([len(got[u]) for u in pick], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def rehearse_cpu(args, world, rank):
     """The N > 1 control path without a GPU: every rank takes its shard of the corpus (ids only), the
     ranks meet at the gloo barrier and reduce (sum of frames, max of seconds) as the real run does."""
@@ -813,7 +854,7 @@ def rehearse_cpu(args, world, rank):
         dist.barrier()
     total, tmax = reduce_job(frames * args.steps, 1.0 + rank, dist if world > 1 else None)
     c4 = None
-    if args.corpus_utts == 0 and not args.no_configs4:   # the `configs4` object: the whole corpus over the ranks of the job
+    if args.full and args.corpus_utts == 0 and not args.no_configs4:   # the `configs4` object: the whole corpus over the ranks
         ids4 = corpus_shard_ids(args.configs4_utts, world, rank)
         fr4 = int(sum(corpus.utterance_length(int(u)) // 80 for u in ids4))
         if world > 1:
@@ -881,14 +922,17 @@ def run_rank(args):
 
     events = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.steps)]
     t0 = time.perf_counter()
+    last = None
     for k in range(args.steps):
         events[k][0].record()
-        sea.ns_denoise_batch(batch, out=out)
+        last = sea.ns_denoise_batch(batch, out=out)
         events[k][1].record()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0   # this rank's timed region; the job's is the max over ranks
     barrier()
     kernel_ms = [a.elapsed_time(b) for a, b in events]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, ids, last)
 
     # whole-job aggregate: frames summed over ranks, time = max over ranks (no data-path collective)
     from speech_enhancement_amd.shard import reduce_job
@@ -953,7 +997,7 @@ def run_rank(args):
                 issue_s = clk / (1024 * 2.4e9)
                 result["roofline"]["valu_issue_ms"] = issue_s * 1e3
                 result["roofline"]["valu_issue_frac"] = issue_s / avg_kernel_s
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1:  # the CPU baseline is reported at N=1 only
             base, outs = cpu_baseline(batch, args.cpu_utts, args.cpu_threads)
             result["cpu_baseline"] = base
             # parity on the sample, exact (the oracle as checker, never as the measured path)
@@ -963,7 +1007,7 @@ def run_rank(args):
             result["gpu_over_cpu"] = value / base["value"]
             if bad:
                 rc = 3
-        if not args.no_also and world == 1:
+        if args.full and not args.no_also and world == 1:
             del out
             if args.corpus_utts == 0 and not args.no_end_to_end:
                 result["end_to_end"] = end_to_end(batch, 5)
@@ -975,7 +1019,7 @@ def run_rank(args):
                 result["also"].insert(0, c4)
                 if bad4:
                     rc = 3
-    if args.corpus_utts == 0 and not args.no_configs4 and not args.no_also:
+    if args.full and args.corpus_utts == 0 and not args.no_configs4 and not args.no_also:
         # every rank takes part (N > 1: the also-array of the other kernels is an N = 1 matter, this line is not)
         batch = out = None   # this rank's configs[1] shard leaves the HBM
         torch.cuda.empty_cache()

@@ -160,3 +160,44 @@ def test_afe_feature_chain_1024_utterances(shard, oracle):
     print(f"AFE chain: {frames} feature frames, {speech} flagged speech, worst |delta| = {worst}")
     assert worst <= 1e-3
     assert 0 < speech < frames
+
+
+def _bench(*args):
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + list(args), env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_dumps_its_last_step(shard, oracle, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run (headline only, exactly --steps timed steps) writes what its last
+    timed step returned -- first_out of every utterance and the denoised samples of the utterances it keeps -- as
+    float .npy files under 64 MB; a small shard is written whole, the 1024-utterance one as a seeded sample.  The
+    samples are the oracle's, bit for bit."""
+    host = shard.data.cpu().numpy()
+    utts = [host[o:o + l] for o, l in zip(shard.host_offsets, shard.host_lengths)]
+    for n_utt, steps, sampled in ((24, 3, False), (1024, 1, True)):
+        d = tmp_path / f"dump{n_utt}"
+        j = _bench("--utts", str(n_utt), "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d))
+        assert j["steps"] == steps and j["ms_per_step"] > 0 and j["unit"] == "frames/s" and j["higher_is_better"] is True
+        assert j["dtype"] == "f32" and j["value"] > 0 and j["metric"].startswith("NoiseSup frames/sec")
+        assert not {"cpu_baseline", "parity_check", "end_to_end", "also", "configs4"} & set(j)
+        files = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert set(files) == {"first_out", "denoised", "utterance_ids", "utterance_lengths"}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(p.stat().st_size for p in d.glob("*.npy")) <= 64_000_000
+        ids = files["utterance_ids"].astype(np.int64)
+        lens = files["utterance_lengths"].astype(np.int64)
+        assert np.array_equal(files["first_out"], [(5 if u % 5 == 0 else 0) + 4 for u in range(n_utt)])
+        assert np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < n_utt
+        assert (len(ids) < n_utt) == sampled and len(ids) > 0
+        assert np.array_equal(lens, [len(utts[u]) // 80 * 80 for u in ids]) and lens.sum() == files["denoised"].size
+        pos = np.concatenate(([0], np.cumsum(lens)))
+        for k, u in enumerate(ids[:24]):
+            want = oracle.etsi_denoise(utts[u])[: lens[k]]
+            assert np.array_equal(files["denoised"][pos[k]:pos[k + 1]], want.astype(np.float32)), f"utt {u}"

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 pass() {
   n=$1; shift
   rm -rf /tmp/pm_$n
-  rocprofv3 --pmc "$@" --output-format csv -d /tmp/pm_$n -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_FLAGS:---no-also} > /tmp/pm_$n.log 2>&1 || { tail -5 /tmp/pm_$n.log; return 1; }
+  rocprofv3 --pmc "$@" --output-format csv -d /tmp/pm_$n -- python3 $R/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_FLAGS:---no-also} > /tmp/pm_$n.log 2>&1 || { tail -5 /tmp/pm_$n.log; return 1; }
   python3 $R/tools/prof_summary.py /tmp/pm_$n $O/${TAG:-r02}_pmc_mix$n.txt --delete-raw | grep -E "SQ" | sed 's/sea::\([a-z0-9_]*\)(.*) /\1 /; s/dispatches=[0-9]* //; s/ min=.*//'
 }
 pass 1 SQ_INSTS_VALU_ADD_F32 SQ_INSTS_VALU_MUL_F32 SQ_INSTS_VALU_FMA_F32 SQ_INSTS_VALU_TRANS_F32 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_TRANS_F64 &&

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python bench.py > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err || { tail -5 $O/${TAG}_bench_n1.err; exit 1; }
+python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err || { tail -5 $O/${TAG}_bench_n1.err; exit 1; }
 python tools/bench_extra.py --what subband,afe,host --steps 5 > $O/${TAG}_bench_extra_1024.jsonl 2> /dev/null
 python tools/ns16k_time.py 1024 400 > $O/${TAG}_ns16k_time.txt 2> /dev/null
 python tools/ns16k_time.py 4096 200 >> $O/${TAG}_ns16k_time.txt 2> /dev/null
@@ -22,11 +22,11 @@ mkdir -p $O/${TAG}_logs
 keep_logs() { cp -f /tmp/p_*.log $O/${TAG}_logs/ 2> /dev/null; }
 trap keep_logs EXIT
 pass() { timeout -k 10 240 "$@" || { echo "profile_round: that pass failed or timed out: stopping" >&2; exit 1; }; }
-echo "profile_round: kernel trace"; pass rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_tr -- python3 $R/bench.py --steps 10 --no-cpu-baseline --no-end-to-end > /tmp/p_tr.log 2>&1
+echo "profile_round: kernel trace"; pass rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_tr -- python3 $R/bench.py --full --steps 10 --no-cpu-baseline --no-end-to-end > /tmp/p_tr.log 2>&1
 python3 $R/tools/prof_summary.py /tmp/p_tr $O/${TAG}_kernel_trace_stats.txt --delete-raw > /dev/null
 for c in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/p_$c
-  echo "profile_round: pmc $c"; pass rocprofv3 --pmc $c --output-format csv -d /tmp/p_$c -- python3 $R/bench.py --steps 3 --warmup 1 --also-steps 2 --no-cpu-baseline --no-end-to-end --no-configs4 > /tmp/p_$c.log 2>&1
+  echo "profile_round: pmc $c"; pass rocprofv3 --pmc $c --output-format csv -d /tmp/p_$c -- python3 $R/bench.py --full --steps 3 --warmup 1 --also-steps 2 --no-cpu-baseline --no-end-to-end --no-configs4 > /tmp/p_$c.log 2>&1
   python3 $R/tools/prof_summary.py /tmp/p_$c $O/${TAG}_pmc_$(echo $c | tr A-Z a-z | sed s/_size//).txt --delete-raw > /dev/null
 done
 i=0
@@ -34,7 +34,7 @@ for set in "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU S
            "SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_ACTIVE_INST_SCA"; do
   i=$((i+1))
   rm -rf /tmp/p_sq$i
-  echo "profile_round: pmc SQ set $i"; pass rocprofv3 --pmc $set --output-format csv -d /tmp/p_sq$i -- python3 $R/bench.py --steps 3 --warmup 1 --also-steps 2 --no-cpu-baseline --no-end-to-end --no-configs4 > /tmp/p_sq$i.log 2>&1
+  echo "profile_round: pmc SQ set $i"; pass rocprofv3 --pmc $set --output-format csv -d /tmp/p_sq$i -- python3 $R/bench.py --full --steps 3 --warmup 1 --also-steps 2 --no-cpu-baseline --no-end-to-end --no-configs4 > /tmp/p_sq$i.log 2>&1
   python3 $R/tools/prof_summary.py /tmp/p_sq$i $O/${TAG}_pmc_sq$i.txt --delete-raw > /dev/null
 done
 # the configs[4] kernel form (sea::ns_denoise_pipe_big_kernel: the form all eight GPUs run) gets counter passes of its own on
@@ -64,5 +64,5 @@ python3 $R/tools/prof_summary.py /tmp/p_mix1 $O/${TAG}_pmc_mix1.txt --delete-raw
 python3 $R/tools/make_pmc_traffic.py $O/${TAG}_pmc_fetch.txt $O/${TAG}_pmc_write.txt $O/pmc_traffic.json $O/${TAG}_pmc_sq1.txt $O/${TAG}_pmc_mix1.txt \
     --big $O/${TAG}_pmc_big_fetch.txt $O/${TAG}_pmc_big_write.txt $O/${TAG}_pmc_big_sq1.txt $O/${TAG}_pmc_big_mix1.txt && cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
 cd $R
-python bench.py --no-cpu-baseline > $O/${TAG}_bench_n1_with_traffic.json 2> /dev/null   # same tree, traffic from the fresh stamp
+python bench.py --full --no-cpu-baseline > $O/${TAG}_bench_n1_with_traffic.json 2> /dev/null   # same tree, traffic from the fresh stamp
 echo "profile_round done -- back home copy gpurun_out/${TAG}_* AND gpurun_out/pmc_traffic.json into profiles/ (the stamp bench.py checks)"
