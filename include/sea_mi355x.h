@@ -101,12 +101,14 @@ int sea_compceps_batch(const float *d_den_f32, const long long *d_offsets, const
 /* sea_ns_denoise_batch picks one of several forms of the same kernel by batch size (all bit-identical):
  * 3 = six waves per utterance (up to 3 utterances per CU: shortest frame period), 6 = the same compiled so that four
  * workgroups co-reside on a CU (up to 4 per CU; round 4), 4 = four waves, lower register use (larger batches), 2 = four waves
- * (the form for up to 4 per CU until round 4; the time-slice launches run on it), 1 = one wave per utterance; 5 = two utterances per
- * workgroup with their lane-sparse phases packed into one wave: 22 % fewer vector instructions per frame and slower; 7 = one wave per
- * utterance running every role in sequence (no workgroup barrier; register-bound at twelve utterances per CU: slower)
- * (5 and 7: experiments kept under the parity tests, never chosen by batch size).
- * sea_ns_kernel_form(f) forces form f for later calls (0 = by batch size again; the SEA_NS_KERNEL
- * environment variable = single | pipe | pipe6 | pipe6d | big | pair | wave sets the initial value); returns the previous one. */
+ * (the form for up to 4 per CU until round 4; the time-slice launches run on it).
+ * Removed after measurement (source at 24082b1; M frames/s on the configs[4] shard, against 465 for form 4 then):
+ *   1 = one wave per utterance, the round-1 kernel: 190-219
+ *   5 = two utterances per workgroup, lane-sparse phases packed: 434 (profiles/r04_ns_pair_form_experiment.txt)
+ *   7 = one wave per utterance running every role in sequence: 363 (profiles/r04_ns_six_wave_dense.txt)
+ * sea_ns_kernel_form(f) forces form f (0, 2, 3, 4 or 6) for later calls (0 = by batch size again; the SEA_NS_KERNEL
+ * environment variable = pipe | pipe6 | pipe6d | big sets the initial value); any other f only reads.  Returns the previous
+ * form. */
 int sea_ns_kernel_form(int form);
 /* The same for one TIME SLICE of every utterance: a batch may be cut along the time axis and run as one launch per
  * slice, so that a caller can upload slice k + 1 and download slice k - 1 while slice k is on the device
@@ -257,13 +259,10 @@ int sea_ns_streams_push_fd(const float *d_in, float *d_out, int *d_produced, uns
 int sea_ns16k_streams_push(const float *d_in, float *d_out, int *d_produced, unsigned char *d_flags, int *d_frame_counter,
                            float *d_wiener, float *d_state, int n_streams, int nframes, int reset, void *stream);
 int sea_ns16k_state_floats(void);
-/* kernel form of sea_ns16k_streams_push for later calls: 0 = four pipelined wavefronts per stream (default), 1 = one
- * wavefront per stream (round 3's form, kept for A/B; SEA_NS16K_KERNEL=single makes it the initial form).  Same arithmetic,
- * same state blob: a stream may change forms between two pushes.  form < 0 only reads; returns the previous form. */
-int sea_ns16k_kernel_form(int form);
 /* its host-side tables as the reference's init code lays them out (for checks against the oracle) */
 int sea_ns16k_tables_host(float *sigWindow480, float *irWindow17, int *gammaStart25, float *gamma25x128, float *idct25x25);
-/* and its table-driven transform schedule (what the kernel walks) run on the host, in place on 512 floats: rfft (x, 512, 8) */
+/* and its table-driven transform schedule (the pipelined kernel's tables are built from it) run on the host, in place on
+ * 512 floats: rfft (x, 512, 8) */
 void sea_ns16k_fft_host(float *x512);
 
 /* The reference's batch plug-in symbols (function/20141106_speech_enhancement/aurora_etsi/NoiseSupExports.h:35-42;

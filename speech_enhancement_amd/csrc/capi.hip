@@ -115,16 +115,13 @@ static std::atomic<int> g_ns6_perm{[] { const char *e = getenv("SEA_NS6_PERM"); 
  *   more         four waves, tables in LDS: six workgroups per CU     SEA_NS_KERNEL=big
  *   (not chosen) four waves, transform address tables in VGPRs: the form for <= 4 per CU until round 4, 4 % behind the
  *                dense six-wave form there; the time-slice launches of the host pipelines run on it   SEA_NS_KERNEL=pipe
- *   (never)      two utterances per workgroup, lane-sparse phases packed   SEA_NS_KERNEL=pair (experiment, slower)
- *   (never)      one wave per utterance, the roles in sequence, no workgroup barrier (ns_wave_kernel.hip): 363 M frames/s on the
- *                configs[4] shard against 465                           SEA_NS_KERNEL=wave (experiment, slower)
- * SEA_NS_KERNEL=single: one wave per utterance (the streaming plug-in's kernel), for A/B. */
+ * Removed after measurement (source at 24082b1; M frames/s on the configs[4] shard, against 465 for the big form then):
+ *   form 1, one wave per utterance, the round-1 kernel: 190-219
+ *   form 5, two utterances per workgroup, lane-sparse phases packed: 434 (profiles/r04_ns_pair_form_experiment.txt)
+ *   form 7, one wave per utterance, the roles in sequence: 363 (profiles/r04_ns_six_wave_dense.txt) */
 int ns_pick_form(int n_inflight, int n_cu)
 {
     const int forced = sea_ns_kernel_form(-1);
-    /* (form 5, two utterances per workgroup with their lane-sparse phases packed into one wave -- ns_pipe2_kernel.hip -- has
-     * 22 % fewer vector instructions per frame and is slower: 434 against 465 M frames/s on the configs[4] shard; never
-     * chosen here, see that file's header) */
     return forced ? forced : (n_inflight <= 3 * n_cu ? 3 : (n_inflight <= 4 * n_cu ? 6 : 4));
 }
 
@@ -132,16 +129,14 @@ int ns_launch(const sea::NsBatchArgs &a, int form, hipStream_t stream)
 {
     if (a.n_utt <= 0) return 0;
     if (a.state) { /* time slices: the four-wave forms only */
-        if (form == 4 || form == 5)
+        if (form == 4)
             hipLaunchKernelGGL(sea::ns_denoise_pipe_big_slice_kernel, dim3(a.n_utt), dim3(256), 0, stream, a);
         else
             hipLaunchKernelGGL(sea::ns_denoise_pipe_slice_kernel, dim3(a.n_utt), dim3(256), 0, stream, a);
         HIP_TRY(hipGetLastError());
         return 0;
     }
-    if (form == 1)
-        hipLaunchKernelGGL(sea::ns_denoise_kernel, dim3(a.n_utt), dim3(64), 0, stream, a);
-    else if (form == 3 || form == 6) {
+    if (form == 3 || form == 6) {
         sea::NsBatchArgs b = a;
         const int perm = g_ns6_perm.load(); /* diagnostic: the wave -> role map of the six-wave form (sea_debug_ns6_perm / SEA_NS6_PERM) */
         if (perm) b.perm6 = perm;
@@ -149,11 +144,6 @@ int ns_launch(const sea::NsBatchArgs &a, int form, hipStream_t stream)
         else hipLaunchKernelGGL(sea::ns_denoise_pipe6_kernel, dim3(a.n_utt), dim3(384), 0, stream, b);
     } else if (form == 4)
         hipLaunchKernelGGL(sea::ns_denoise_pipe_big_kernel, dim3(a.n_utt), dim3(256), 0, stream, a);
-    else if (form == 7) {
-        const int per = sea::ns_wave_utts_per_block();
-        hipLaunchKernelGGL(sea::ns_denoise_wave_kernel, dim3((a.n_utt + per - 1) / per), dim3(64 * per), 0, stream, a);
-    } else if (form == 5)
-        hipLaunchKernelGGL(sea::ns_denoise_pipe_pair_kernel, dim3((a.n_utt + 1) / 2), dim3(sea::ns_pair_threads()), 0, stream, a);
     else
         hipLaunchKernelGGL(sea::ns_denoise_pipe_kernel, dim3(a.n_utt), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
@@ -163,8 +153,6 @@ int ns_launch(const sea::NsBatchArgs &a, int form, hipStream_t stream)
 } // namespace sea_capi
 
 using namespace sea_capi;
-
-extern "C" int sea_ns16k_kernel_form(int form);
 
 extern "C" {
 
@@ -225,13 +213,10 @@ static int ns_form()
     if (f < 0) {
         const char *e = getenv("SEA_NS_KERNEL");
         f = 0;
-        if (e && !strcmp(e, "single")) f = 1;
         if (e && !strcmp(e, "pipe")) f = 2;
         if (e && !strcmp(e, "pipe6")) f = 3;
         if (e && !strcmp(e, "big")) f = 4;
-        if (e && !strcmp(e, "pair")) f = 5;
         if (e && !strcmp(e, "pipe6d")) f = 6;
-        if (e && !strcmp(e, "wave")) f = 7;
         g_ns_form.store(f);
     }
     return f;
@@ -246,7 +231,6 @@ int sea_debug_ns_occupancy(int form)
     if (form == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sea::ns_denoise_pipe6_kernel, 384, 0);
     if (form == 6) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sea::ns_denoise_pipe6_dense_kernel, 384, 0);
     if (form == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sea::ns_denoise_pipe_big_kernel, 256, 0);
-    if (form == 5) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sea::ns_denoise_pipe_pair_kernel, sea::ns_pair_threads(), 0);
     if (form == 16) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, sea::ns16k_pipe_kernel, 512, 0);
     return e == hipSuccess ? n : -1;
 }
@@ -254,7 +238,7 @@ int sea_debug_ns_occupancy(int form)
 int sea_ns_kernel_form(int form)
 {
     const int prev = ns_form();
-    if (form >= 0 && form <= 7) g_ns_form.store(form);
+    if (form == 0 || form == 2 || form == 3 || form == 4 || form == 6) g_ns_form.store(form);
     return prev;
 }
 
@@ -561,20 +545,8 @@ int sea_resynth64_batch(const short *d_in, short *d_out, const long long *d_offs
     a.tables = c->gt;
     a.n_utt = n_utt;
     a.binary = binary;
-    /* default: both passes of an utterance in one workgroup; SEA_RESYNTH=split selects the two-launch form
-     * (analysis pass of the whole batch, then synthesis pass; identical results) */
-    static const bool split = [] {
-        const char *e = getenv("SEA_RESYNTH");
-        return e && !strcmp(e, "split");
-    }();
-
-    if (split) {
-        hipLaunchKernelGGL(sea::resynth_fwd_kernel, dim3(n_utt), dim3(192), 0, (hipStream_t)stream, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(sea::resynth_bwd_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a);
-    } else {
-        hipLaunchKernelGGL(sea::resynth_fused_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a);
-    }
+    /* both passes of an utterance in one workgroup */
+    hipLaunchKernelGGL(sea::resynth_fused_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -660,14 +632,7 @@ int sea_irm_target_batch(const short *d_pure64, const short *d_noise64, const lo
     a.fft = &c->ns->fft;
     a.n_utt = n_utt;
     a.window = window;
-    static const bool dual = [] {
-        const char *e = getenv("SEA_IRM_KERNEL");
-        return e && !strcmp(e, "dual");
-    }();
-    if (dual)
-        hipLaunchKernelGGL(sea::irm_target_dual_kernel, dim3((unsigned)n_utt * 64u), dim3(64), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(sea::irm_target_kernel, dim3((unsigned)n_utt * 64u), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(sea::irm_target_kernel, dim3((unsigned)n_utt * 64u), dim3(256), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -823,7 +788,7 @@ int sea_ns_streams_push_fd(const float *d_in, float *d_out, int *d_produced, uns
 
 int sea_ns_state_floats(void) { return sea::kNsStateFloats; }
 
-/* ---- the 16 k-native variant (ns16k_kernel.hip) ---- */
+/* ---- the 16 k-native variant (ns16k_pipe_kernel.hip) ---- */
 int sea_ns16k_streams_push(const float *d_in, float *d_out, int *d_produced, unsigned char *d_flags, int *d_frame_counter,
                            float *d_wiener, float *d_state, int n_streams, int nframes, int reset, void *stream)
 {
@@ -843,15 +808,10 @@ int sea_ns16k_streams_push(const float *d_in, float *d_out, int *d_produced, uns
     a.nframes = nframes;
     a.reset = reset;
     a.n_streams = n_streams;
-    /* SEA_NS16K_KERNEL=single: round 3's one-wavefront-per-stream form (kept for A/B); default: four pipelined waves per
-     * stream (ns16k_pipe_kernel.hip).  Same arithmetic, same state blob: a stream may change forms between two pushes. */
-    if (sea_ns16k_kernel_form(-1) == 1) {
-        constexpr int G = sea::kNs16StreamsPerGroup;
-        hipLaunchKernelGGL(sea::ns16k_stream_kernel, dim3((n_streams + G - 1) / G), dim3(64 * G), 0, (hipStream_t)stream, a);
-    } else {
-        constexpr int G = sea::kNs16PipeStreamsPerGroup;
-        hipLaunchKernelGGL(sea::ns16k_pipe_kernel, dim3((n_streams + G - 1) / G), dim3(256 * G), 0, (hipStream_t)stream, a);
-    }
+    /* four pipelined waves per stream (round 3's one-wave-per-stream form was removed after measurement, source at 24082b1:
+     * 54 against 181 M frames/s at 1024 x 400, profiles/r03_ns16k_time.txt / r04_ns16k_time.txt) */
+    constexpr int G = sea::kNs16PipeStreamsPerGroup;
+    hipLaunchKernelGGL(sea::ns16k_pipe_kernel, dim3((n_streams + G - 1) / G), dim3(256 * G), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -887,19 +847,6 @@ int sea_selftest_ns16k_pieces(const float *frames512, int nfft, float *fft512_a,
         HIP_TRY(hipMemcpy(idct9, did.p, (size_t)ngain * 9 * sizeof(float), hipMemcpyDeviceToHost));
     }
     return 0;
-}
-
-/* 0: four pipelined waves per stream (default); 1: one wave per stream (round 3's form; SEA_NS16K_KERNEL=single sets it as
- * the initial value).  form < 0 only reads.  Returns the previous form. */
-int sea_ns16k_kernel_form(int form)
-{
-    static std::atomic<int> g_form{[] {
-        const char *e = getenv("SEA_NS16K_KERNEL");
-        return (e && !strcmp(e, "single")) ? 1 : 0;
-    }()};
-    const int prev = g_form.load();
-    if (form == 0 || form == 1) g_form.store(form);
-    return prev;
 }
 
 int sea_ns16k_tables_host(float *sigWindow480, float *irWindow17, int *gammaStart25, float *gamma25x128, float *idct25x25)

@@ -44,7 +44,7 @@ inline long long align8(long long v) { return (v + 7) & ~7LL; }
 void launch_order(const long long *lens, int n, int n_cu, int *order);
 
 /* NoiseSup kernel form for a batch of n_inflight utterances sharing the device (capi.hip::sea_ns_denoise_batch):
- * 3 six-wave, 2 four-wave, 4 four-wave / tables in LDS, 1 single wave; honours sea_ns_kernel_form / SEA_NS_KERNEL */
+ * 3 six-wave, 6 dense six-wave, 4 four-wave / tables in LDS, 2 four-wave; honours sea_ns_kernel_form / SEA_NS_KERNEL */
 int ns_pick_form(int n_inflight, int n_cu);
 /* one launch of that form over a.n_utt utterances; returns 0 or fail() */
 int ns_launch(const sea::NsBatchArgs &a, int form, hipStream_t stream);

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(64, SEA_RFFT_WAVES) void rfft256_kernel(const float
  * the schedule sea_rfft_schedule() unrolled on the host -- digit reversal, the length-two butterflies, then level by
  * level the plain, pi/4 and twiddled butterflies of all blocks, which touch disjoint elements within a level -- with the
  * frame in LDS (n floats, dynamic).  A convenience path behind the drop-in symbol (the hot path's only size, (256, 8),
- * keeps rfft256_kernel; the 16 k-native variant's (512, 8) keeps its own register schedule in ns16k_kernel.hip): written
+ * keeps rfft256_kernel; the 16 k-native variant's (512, 8) keeps its own schedule in ns16k_pipe_kernel.hip): written
  * for exactness -- the reference's operations in the reference's order per butterfly -- not for speed. */
 __global__ __launch_bounds__(256) void rfft_any_kernel(float *x, const unsigned *sched, long long nframes)
 {

@@ -7,7 +7,7 @@
  * SEMANTICS.  By default (sm_glb_res == NULL, which is what the reference's caller passes,
  * resyth_64sub_ori/cpp/aurora_etsi_test.cpp:20) the symbols run what the reference builds behind them: the 16 k-native
  * variant (160-sample frames, window 480, gammatone-shaped windows, rfft (x, 512, 8);
- * aurora_etsi/NoiseSup.cpp:1140-1407 -> csrc/ns16k_kernel.hip), including the line of 25 gains per second-stage frame
+ * aurora_etsi/NoiseSup.cpp:1140-1407 -> csrc/ns16k_pipe_kernel.hip), including the line of 25 gains per second-stage frame
  * printed to the FILE* argument ("%f " each, then a newline; :1319-1328) when that is not NULL.
  * sm_glb_res is ignored, as the reference ignores it (its cast to DENOISEGlobalImpl is commented out, :915, and
  * SamplingFrequency forced to 16000).  Extension, opt-in through the environment only (SEA_MAPPING_8K=1 at global_init):

@@ -6,9 +6,9 @@
  *                                                                               stage buffer, 129 spectral values, rfft (x, 512, 8)
  *     function/20141106_speech_enhancement/aurora_etsi/MelProc.cpp:119-135,556-576   DoGamma, DoGammaIDCT
  *
- * Round 3's form (ns16k_kernel.hip, kept: SEA_NS16K_KERNEL=single) runs a stream on ONE wavefront: 1024 streams are one
- * latency-bound wave per SIMD, 45 k clk per frame, 59 % of its LDS cycles bank conflicts of the un-swizzled transform.  The
- * frame recursion is the same software pipeline as etsi/'s (ns_pipe_kernel.hip), so a stream gets four role waves, one
+ * Round 3's form (removed after measurement, source at 24082b1; profiles/r03_ns16k_time.txt) ran a stream on ONE wavefront:
+ * 1024 streams were one latency-bound wave per SIMD, 45 k clk per frame, 59 % of its LDS cycles bank conflicts of the
+ * un-swizzled transform.  The frame recursion is the same software pipeline as etsi/'s (ns_pipe_kernel.hip), so a stream gets four role waves, one
  * s_barrier per frame (beat), frame f at beat:
  *
  *   f      S  intake: the frame gate's in-order sum of squares (:1160-1171) and the VAD's frame sum (:373-376) ride in two
@@ -25,9 +25,8 @@
  *
  * Two streams (eight waves) share a workgroup and with it the 13.7 KB of DoGamma coefficients in LDS; every stream of a
  * push has the same number of frames, so the lock step costs nothing.  All recursive state lives in the role waves'
- * registers and per-stream LDS; between pushes in the same kNs16StateFloats-float blob the one-wave form uses (linear
- * stage buffers: a stream may change kernels between two pushes).  Arithmetic: ns_core.h's and ns16k_kernel.hip's,
- * operation by operation; bit-identical to the one-wave form and to oracle/ns16k_oracle.c (tests/test_gpu_ns16k.py).
+ * registers and per-stream LDS; between pushes in one kNs16StateFloats-float blob per stream (linear stage buffers).
+ * Arithmetic: ns_core.h's, operation by operation; bit-identical to oracle/ns16k_oracle.c (tests/test_gpu_ns16k.py).
  */
 #include "ns_core.h"
 

@@ -1037,30 +1037,6 @@ __device__ __forceinline__ void ns_idct_tail(const float *rec, const float *idct
     wave_sync();
 }
 
-/* DoMelIDCT rows 0..8 + mirror + Hanning(17) for a wave that did NOT compute the mel gains: mel[0..24] in LDS (28
- * floats, 16-byte aligned), basis idctLds[f][16], irWin = this lane's window weight; taps to fir[0..16].  Same
- * operations in the same order as ns_idct_taps.  Ends with wave_sync(). */
-__device__ __forceinline__ void ns_idct_taps_from(const float *mel, const float *idctLds, float irWin, float *fir, int lane)
-{
-    float m[SEA_NMEL];
-#pragma unroll
-    for (int f4 = 0; f4 < 24; f4 += 4) {
-        const float4 v = *reinterpret_cast<const float4 *>(&mel[f4]);
-        m[f4] = v.x, m[f4 + 1] = v.y, m[f4 + 2] = v.z, m[f4 + 3] = v.w;
-    }
-    m[24] = mel[24];
-    const int l = (lane <= 8) ? lane : 8; /* every lane computes (no divergence), rows 0..8 store */
-    float h = 0.0f;
-#pragma unroll
-    for (int f = 0; f < SEA_NMEL; ++f) h += m[f] * idctLds[f * 16 + l];
-    const float tap = h * irWin;
-    if (lane <= 8) {
-        fir[8 + lane] = tap;
-        fir[8 - lane] = tap;
-    }
-    wave_sync();
-}
-
 /* ApplyWF (NoiseSup.c:324-340): the 17 taps fir[0..16] (wave-uniform: broadcast LDS reads) over
  * buf[80..159] with 8 samples of context either side; lanes 0..39 produce two outputs each into dst.
  * Ends with wave_sync(). */
@@ -1657,7 +1633,7 @@ __device__ __forceinline__ bool dc_step_ok(float d, float yPrev)
 
 /* *unsafe (optional): set when some step of the DC chain fails dc_step_ok -- checked by the sixteen recomputing lanes
  * on the values they hold in registers (start value, five inputs, five outputs); the caller then redoes the frame on
- * the exact path (dc_redo_exact).  nullptr: the caller verifies through LDS (dc_verify). */
+ * the exact path (double multiply-add per sample, as in dc_verify).  nullptr: the caller verifies through LDS (dc_verify). */
 /* FDCH (four-wave fd kernel): three more sums in lanes 48..50, which otherwise repeat the DC chain -- the mean and the
  * sum of squares of the first 64 Wiener gains (SpeechQVar) and the sum of the 25 mel-filtered gains (SpeechQSpec) of
  * the frame whose record fdRec is (kFdRecFloats); returned in fdSums[0..2]. */
@@ -1741,19 +1717,6 @@ __device__ __forceinline__ void helper_chains(const float *sq, const float *den,
         fdSums[0] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 48));
         fdSums[1] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 49));
         fdSums[2] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 50));
-    }
-    wave_sync();
-}
-
-/* the exact path of the DC recurrence over one frame (double multiply-add, rounded to float per sample), for the
- * frames on which the FMA form's exactness condition failed */
-__device__ __forceinline__ void dc_redo_exact(const float *dif, float *out, float y0, float &y)
-{
-    wave_sync();
-    y = y0;
-    for (int n = 0; n < SEA_HOP; ++n) {
-        y = (float)__fma_rn(0.9990234375, (double)y, (double)dif[n]);
-        out[n] = y;
     }
     wave_sync();
 }

@@ -1,18 +1,16 @@
 /*
  * ns_kernel.hip -- two-stage mel-warped Wiener noise suppressor, gfx950 (MI355X).
  *
- * One 64-lane wavefront owns one utterance and walks its 80-sample frames in order (frames of an
- * utterance are serially dependent: SURVEY F6); a launch runs one wavefront per utterance of the
- * batch.  All per-utterance state lives on chip for the whole utterance:
+ * The one-wavefront forms of the ns_core.h arithmetic: one 64-lane wavefront owns one stream and walks
+ * its 80-sample frames in order (frames of a stream are serially dependent: SURVEY F6); a launch runs
+ * one wavefront per stream.  Between frames the state lives on chip:
  *   LDS   : the two 320-sample stage buffers, the 256-point FFT workspace, small exchange areas
  *   VGPRs : per-bin spectra (lane l = PSD bin l; bin 64 rides in lane 0), window / mel / IDCT /
  *           FFT-schedule constants (loaded once, lane-major tables from sea_tables.c)
- * HBM traffic per frame is the algorithmic minimum: 160 B int16 in + 160 B int16 out
- * (+320 B when the float stream for CompCeps is requested).
+ * and between pushes in one HBM blob per stream.  The device self-tests behind sea_selftest_*() live
+ * here too.  The batch entry points run the pipelined forms (ns_pipe_kernel.hip, ns_pipe6_kernel.hip).
  *
  * Reference path reproduced (results bit-identical up to libm log/log10):
- *   etsi/cpp/AdvFrontEnd.c:125-210   etsi_denoise        utterance loop, output placement
- *   etsi/cpp/ParmInterface.c:208-330 DoAdvProcess        int16<->float, zero-frame gate
  *   etsi/cpp/NoiseSup.c:1061-1440    DoNoiseSup          two stages, latency gates, buffers
  *   etsi/cpp/NoiseSup.c:182-669      DCOffsetFil .. DoFilterWindowing
  *   etsi/cpp/MelProc.c:82-104,357-378 DoMelFB, DoMelIDCT
@@ -21,59 +19,6 @@
 #include "ns_core.h"
 
 namespace sea {
-
-/* etsi_denoise over a packed batch: one wavefront per utterance. */
-__global__ __launch_bounds__(64) void ns_denoise_kernel(NsBatchArgs a)
-{
-    __shared__ NsLds L;
-    const int lane = threadIdx.x;
-    const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-    const long long off = a.offsets[u];
-    const long long nfr = a.lengths[u] / SEA_HOP;
-    float *outf = a.out_f32 ? a.out_f32 + off : nullptr;
-
-    NsConst C;
-    load_ns_const(C, a.tables, lane);
-    NsRegs s;
-    regs_init(s, C.eps);
-    for (int i = lane; i < 2 * kRing; i += kLanes) (&L.ring[0][0])[i] = 0.0f;
-    wave_sync();
-
-    int firstOut = -1;
-    /* lanes 0..39 carry two consecutive int16 samples each: 160 B per frame, one dword per lane */
-    const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
-    uint32_t *out32 = reinterpret_cast<uint32_t *>(a.out + off);
-    uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
-
-    for (long long f = 0; f < nfr; ++f) {
-        const uint32_t w = nextw;
-        if (f + 1 < nfr && lane < 40) nextw = in32[(f + 1) * 40 + lane]; /* prefetch next frame */
-
-        /* zero-frame gate: (int)sum(x*x) != 0 <=> some sample != 0 (ParmInterface.c:244-251) */
-        const bool any = __ballot(w != 0u) != 0ull;
-        bool produced = false;
-        if (any || s.onset) {
-            s.onset = 1;
-            const float x0 = (float)(short)(w & 0xFFFFu), x1 = (float)(short)(w >> 16);
-            produced = ns_tick(L, s, C, lane, x0, x1);
-            if (produced && firstOut < 0) firstOut = (int)f;
-        }
-        /* what etsi_denoise copies to p_denoised for this frame (AdvFrontEnd.c:186-190): the
-         * DenoiseBuffer, i.e. zeros until the first NoiseSup output; float -> int16 is the bare
-         * truncating cast of ParmInterface.c:266 */
-        if (lane < 40) {
-            uint32_t packed = 0u;
-            if (produced) {
-                const float2 v = *reinterpret_cast<const float2 *>(&L.outb[2 * lane]);
-                packed = (uint32_t)cast_i16(v.x) | ((uint32_t)cast_i16(v.y) << 16);
-                if (outf) *reinterpret_cast<float2 *>(outf + f * SEA_HOP + 2 * lane) = v;
-            }
-            out32[f * 40 + lane] = packed;
-        }
-        wave_sync();
-    }
-    if (a.first_out && lane == 0) a.first_out[u] = firstOut;
-}
 
 /* DoNoiseSup-shaped streaming: state lives in HBM between calls (one blob per stream), frames are
  * float in / float out, no zero-frame gate (that belongs to DoAdvProcess, not DoNoiseSup). */

@@ -1,7 +1,7 @@
 /*
  * resynth_kernel.hip -- Hu-Wang 64-channel gammatone analysis/synthesis resynthesis, gfx950.
  *
- * One workgroup (three 64-lane wavefronts) owns one utterance; LANE = CHANNEL (64 channels = one
+ * One workgroup (four 64-lane wavefronts) owns one utterance; LANE = CHANNEL (64 channels = one
  * wave), so the 4th-order complex one-pole cascade of every channel advances one sample per step
  * in lock-step.  A wave that is alone on its SIMD issues one vector instruction every 4 cycles, so
  * the ~49 operations of one cascade step bound a one-wave recurrence at ~200 cycles per sample.  The
@@ -14,16 +14,17 @@
  *   wave H   everything per-sample but not recursive: divisions by the middle-ear gain, the
  *            overlap-add weights, channel sums, casts, HBM stores
  *
- *   resynth_fwd_kernel : analysis pass; H writes g1[n][c]/midEar[c] to HBM as rows of 64 floats
- *                        (256 B per step, fully coalesced).  288 GB of HBM is what makes keeping the
- *                        whole [L][64] intermediate of a 1024-utterance batch (~17 GB) resident
- *                        feasible.
- *   resynth_bwd_kernel : R1 reads the rows in reverse time order (8 in flight per lane); H divides
- *                        again, evaluates the mask-weighted raised-cosine overlap-add weight of
- *                        that sample on the fly (at most two overlapping frames per sample),
- *                        multiplies, and sums the 64 channels IN CHANNEL ORDER through a padded LDS
- *                        transpose (lane = sample), then truncates to int16.  No second
- *                        intermediate is written.
+ *   resynth_fwd_body : analysis pass; H writes g1[n][c]/midEar[c] to HBM as rows of 64 floats
+ *                      (256 B per step, fully coalesced).  288 GB of HBM is what makes keeping the
+ *                      whole [L][64] intermediate of a 1024-utterance batch (~17 GB) resident
+ *                      feasible.
+ *   resynth_bwd_body : R1 reads the rows in reverse time order (8 in flight per lane); H divides
+ *                      again, evaluates the mask-weighted raised-cosine overlap-add weight of
+ *                      that sample on the fly (at most two overlapping frames per sample),
+ *                      multiplies, and sums the 64 channels IN CHANNEL ORDER through a padded LDS
+ *                      transpose (lane = sample), then truncates to int16.  No second
+ *                      intermediate is written.
+ *   resynth_fused_kernel runs both passes of an utterance in one workgroup, one after the other.
  *
  * Reference reproduced: resyth_64sub_ori/cpp/extractwav.cpp:55-121 (resynth body; hairCell is dead
  * code there), :167-211 (gammaToneFilter); resyth_64sub_IBM/cpp/extractwav.cpp:97-99
@@ -418,16 +419,6 @@ __device__ __forceinline__ void resynth_fwd_body(const ResynthArgs &a, FwdLds &S
 
 } // namespace
 
-__global__ __launch_bounds__(192, 3) void resynth_fwd_kernel(ResynthArgs a)
-{
-    __shared__ FwdLds S;
-    const int lane = threadIdx.x & 63;
-    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-    TilePrio tp = {0, 0.0f};
-    resynth_fwd_body(a, S, role, lane, u, a.offsets[u], a.lengths[u], tp);
-}
-
 /* gammaToneFilter() for one channel of the bank (HuWang.h:49): a serial recurrence, one lane. */
 __global__ __launch_bounds__(64) void gammatone_kernel(const float *in, float *out, int chan, long long L,
                                                        const sea_gt_tables *t)
@@ -689,18 +680,6 @@ __device__ __forceinline__ void resynth_bwd_body(const ResynthArgs &a, BwdLds &S
 }
 
 } // namespace
-
-__global__ __launch_bounds__(256, 4) void resynth_bwd_kernel(ResynthArgs a)
-{
-    __shared__ BwdLds S;
-    const int lane = threadIdx.x & 63;
-    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-    const long long L = a.lengths[u];
-    if (L < ((a.binary & 2) ? 160 : 320)) return; /* no mask frame fits (wave-uniform exit before any barrier) */
-    TilePrio tp = {0, 0.0f};
-    resynth_bwd_body(a, S, role, lane, u, a.offsets[u], L, tp);
-}
 
 /* Both passes of one utterance in ONE workgroup, back to back: the analysis pass of the long
  * utterances no longer has to drain (and idle most of the chip) before any synthesis pass may

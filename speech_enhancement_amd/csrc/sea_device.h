@@ -554,34 +554,6 @@ __device__ __forceinline__ void fft2_level(float *work, const Fft2Regs &R)
     fft2_store<S>(work, R, in, o);
 }
 
-/* the register-resident start of rfft256 (bit reversal, length-2 and n2=4 butterflies) for one
- * frame; stores the lane's four values at the (swizzled) places of elements 4r..4r+3, r = bitrev6(lane) */
-__device__ __forceinline__ void rfft256_head(float e0, float e1, float e2, float e3, float *work,
-                                             unsigned flags, const unsigned (&head)[2])
-{
-    float g0 = e0, g1 = e2, g2 = e1, g3 = e3;
-    {
-        const float s01 = g0 + g1, d01 = g0 - g1, s23 = g2 + g3, d23 = g2 - g3;
-        const bool f0 = (flags & 1u) != 0, f1 = (flags & 2u) != 0;
-        g0 = f0 ? s01 : g0;
-        g1 = f0 ? d01 : g1;
-        g2 = f1 ? s23 : g2;
-        g3 = f1 ? d23 : g3;
-    }
-    {
-        const float t1 = g3 + g2;
-        const float n3 = g3 - g2, n2 = g0 - t1, n0 = g0 + t1;
-        const bool f = (flags & 4u) != 0;
-        g3 = f ? n3 : g3;
-        g2 = f ? n2 : g2;
-        g0 = f ? n0 : g0;
-    }
-    fft_at(work, head[0] & 0xffffu) = g0;
-    fft_at(work, head[0] >> 16) = g1;
-    fft_at(work, head[1] & 0xffffu) = g2;
-    fft_at(work, head[1] >> 16) = g3;
-}
-
 /* two transforms at once: eA / eB hold the lane's four (windowed) elements of frame A / B.
  * The transform is offered in two halves so that a pipelined kernel can run them in different
  * waves (one frame apart): _lo = register-resident start (up to n2 = 8) + levels n2 = 16, 32; _hi = levels

@@ -54,7 +54,7 @@ struct NsStreamArgs {
     int *frame_counter;        /* optional [B][nframes]: FEParamsX::FrameCounter after the tick */
 };
 
-/* the 16 k-native variant (ns16k_kernel.hip): B independent streams, nframes frames of 160 floats each */
+/* the 16 k-native variant (ns16k_pipe_kernel.hip): B independent streams, nframes frames of 160 floats each */
 constexpr int kNs16StateFloats = 2 * SEA16_BUF + 6 * 132 + 32;
 struct Ns16StreamArgs {
     const float *in;           /* [B][nframes][160] */
@@ -69,10 +69,9 @@ struct Ns16StreamArgs {
     int reset;
     int n_streams;
 };
-constexpr int kNs16StreamsPerGroup = 4; /* wavefronts = streams per workgroup of ns16k_stream_kernel */
 
 struct CepsArgs {
-    const float *den_f32;      /* float NoiseSup stream written by ns_denoise_kernel */
+    const float *den_f32;      /* float NoiseSup stream written by sea_ns_denoise_batch */
     const long long *offsets;  /* as above */
     const long long *lengths;
     const int *first_out;
@@ -139,26 +138,18 @@ struct IrmArgs {
     int n_utt;
     int window;                    /* 0 rectangular, 1 Hamming, 2 Hanning */
 };
-__global__ void irm_target_kernel(IrmArgs a);      /* round 4: per-lane codelet, lane = (polyphase component, frame) */
-__global__ void irm_target_dual_kernel(IrmArgs a); /* rounds 2-3: LDS dual transform per frame (A/B) */
+__global__ void irm_target_kernel(IrmArgs a); /* per-lane codelet, lane = (polyphase component, frame) */
 
 __global__ void subband_kernel(SubbandArgs a);
-__global__ void ns_denoise_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_big_kernel(NsBatchArgs a); /* lower-register form for > 4 utterances per CU */
-__global__ void ns_denoise_pipe_pair_kernel(NsBatchArgs a);
-/* two utterances per workgroup, lane-sparse phases packed (ns_pipe2_kernel.hip: experiment) */
-int ns_pair_threads(); /* threads per workgroup of that kernel */
 __global__ void ns_denoise_pipe_fd_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_slice_kernel(NsBatchArgs a);     /* time slices: state in / out (NsBatchArgs::state) */
 __global__ void ns_denoise_pipe_big_slice_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe6_kernel(NsBatchArgs a);    /* six waves per utterance (ns_pipe6_kernel.hip) */
 __global__ void ns_denoise_pipe6_dense_kernel(NsBatchArgs a);
-__global__ void ns_denoise_wave_kernel(NsBatchArgs a);     /* one wave per utterance, several per workgroup (ns_wave_kernel.hip) */
-int ns_wave_utts_per_block(); /* the same compiled for seven waves per SIMD: four workgroups per CU co-reside */
 __global__ void ns_denoise_pipe6_fd_kernel(NsBatchArgs a); /* + speech flags for the frame-dropping VAD */
 __global__ void ns_stream_kernel(NsStreamArgs a);
-__global__ void ns16k_stream_kernel(Ns16StreamArgs a);
 __global__ void ns16k_pipe_kernel(Ns16StreamArgs a); /* four pipelined waves per stream, two streams per workgroup */
 constexpr int kNs16PipeStreamsPerGroup = 2;
 __global__ void ns16k_selftest_kernel(const sea_ns16k_tables *t, const float *frames, int nfft, float *outA, float *outB, const float *gains,
@@ -179,8 +170,6 @@ __global__ void afe_ceps_kernel(AfeArgs a); /* WaveProc + CompCeps, one wave per
 __global__ void afe_vad_kernel(AfeArgs a);  /* PostProc + frame-dropping VAD + flush, one wave per utterance */
 __global__ void compceps_frames_kernel(const float *data201, float *coef14, long long nframes,
                                        const sea_cc_tables *t);
-__global__ void resynth_fwd_kernel(ResynthArgs a);
-__global__ void resynth_bwd_kernel(ResynthArgs a);
 __global__ void resynth_fused_kernel(ResynthArgs a); /* both passes of an utterance in one workgroup */
 __global__ void gammatone_kernel(const float *in, float *out, int chan, long long L, const sea_gt_tables *t);
 

@@ -858,8 +858,9 @@ void sea_ns16k_plain_tables(float *sigWindow480, float *irWindow17, int *gammaSt
     memcpy(idct25x25, basis, sizeof basis);
 }
 
-/* The table-driven schedule run on the host, item by item as ns16k_kernel.hip's ns16_fft runs it (items of one pass
- * in any order, passes in order): lets a CPU test check rev / fftItem / fftTw against the reference's loop nest. */
+/* The table-driven schedule run on the host, item by item (items of one pass in any order, passes in order): lets a CPU
+ * test check rev / fftItem / fftTw against the reference's loop nest; build_ns16k_pipe derives the pipelined kernel's
+ * tables from the same fields. */
 void sea_ns16k_fft_host(float *x512)
 {
     static sea_ns16k_tables t;

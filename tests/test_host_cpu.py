@@ -47,10 +47,28 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in sea.load().sea_version()
 
 
-def test_library_contains_gfx950_code_object():
+def test_library_contains_gfx950_code_object_with_the_configs1_kernel():
     import speech_enhancement_amd as sea
     blob = open(sea.LIB_PATH, "rb").read()
-    assert b"gfx950" in blob and b"ns_denoise_kernel" in blob
+    assert b"gfx950" in blob and b"ns_denoise_pipe6_dense_kernel" in blob
+
+
+def test_ns_kernel_form_override_accepts_only_the_built_forms():
+    """sea_ns_kernel_form (no HIP call) stores 0 (by batch size) and the forms that exist -- 2, 3, 4, 6 -- and only
+    reads for any other value, the numbers of the removed forms 1, 5 and 7 included."""
+    import speech_enhancement_amd as sea
+    lib = sea.load()
+    prev = lib.sea_ns_kernel_form(-1)
+    try:
+        for f in (2, 3, 4, 6, 0):
+            lib.sea_ns_kernel_form(f)
+            assert lib.sea_ns_kernel_form(-1) == f
+        lib.sea_ns_kernel_form(3)
+        for f in (1, 5, 7, 8):
+            assert lib.sea_ns_kernel_form(f) == 3
+            assert lib.sea_ns_kernel_form(-1) == 3, f"form {f} was stored"
+    finally:
+        lib.sea_ns_kernel_form(prev)
 
 
 def test_host_tables_match_oracle(oracle):
@@ -107,7 +125,7 @@ def test_compceps_mel_lane_map_is_complete_and_conflict_free():
 def test_ns16k_host_tables_and_schedule_match_oracle(oracle):
     """SURVEY 8(f) #4, no GPU needed: the product's tables of the 16 k-native variant (csrc/sea_tables.c) against the
     oracle's, bit for bit, and its table-driven transform schedule (digit-reversal places, butterflies per pass,
-    twiddles: what ns16k_kernel.hip walks) run on the host against the oracle's rfft (x, 512, 8)."""
+    twiddles: what the pipelined kernel's tables are built from) run on the host against the oracle's rfft (x, 512, 8)."""
     import ctypes
     import speech_enhancement_amd as sea
     t, a = sea.ns16k_tables(), oracle.ns16k_tables()

@@ -66,7 +66,7 @@ def main():
                 "value": hops / wall, "unit": "hop-frames/s", "ms_per_step": wall * 1e3, "rtf": wall / audio_s,
                 "config": {"workload": f"BASELINE configs[{3 if binary else 2}]: {args.utts} utterances, 64-band gammatone "
                                        f"analysis/synthesis, {'ideal binary' if binary else 'ratio'} mask", "hop_frames": hops},
-                "roofline": {"bound": "hbm", "kernels": "sea::resynth_fwd_kernel + sea::resynth_bwd_kernel",
+                "roofline": {"bound": "hbm", "kernels": "sea::resynth_fused_kernel",
                              "achieved": alg / ker / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                              "frac": alg / ker / 1e9 / HBM_PEAK_GBPS, "algorithmic_bytes_per_step": alg,
                              "intermediate_bytes_per_step": int(batch.total) * 64 * 4 * 2,

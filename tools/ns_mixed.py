@@ -4,7 +4,7 @@ streams, each with its own kernel form (run on the GPU box).  Prints ms per step
 import ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-FORMS = {"single": 1, "pipe": 2, "pipe6": 3, "big": 4}
+FORMS = {"pipe": 2, "pipe6": 3, "big": 4}
 
 
 def main():
