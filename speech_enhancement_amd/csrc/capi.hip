@@ -105,8 +105,24 @@ void gammatone_host_tables(float *cf64, float *bw64, float *midEar64)
 }
 
 /* diagnostic (tools/ns6_perm_sweep.py): wave -> role map of the six-wave forms, three bits per wave, wave 0 lowest; 0 = the
- * kernel's own.  Initialised from SEA_NS6_PERM (octal). */
-static std::atomic<int> g_ns6_perm{[] { const char *e = getenv("SEA_NS6_PERM"); return e ? (int)strtol(e, nullptr, 8) : 0; }()};
+ * kernel's own.  The kernels take the map as it comes, and a map that leaves a role unstaffed or doubled gives wrong output without
+ * any error, so only 0 and permutations of the roles 0..5 get past this function. */
+static bool ns6_perm_valid(int perm)
+{
+    if (perm == 0) return true;
+    if ((unsigned)perm >> 18) return false;
+    unsigned seen = 0;
+    for (int w = 0; w < 6; ++w) seen |= 1u << ((perm >> (3 * w)) & 7);
+    return seen == 0x3Fu;
+}
+/* initialised from SEA_NS6_PERM (octal); an invalid value is reported once and ignored */
+static std::atomic<int> g_ns6_perm{[] {
+    const char *e = getenv("SEA_NS6_PERM");
+    const int perm = e ? (int)strtol(e, nullptr, 8) : 0;
+    if (ns6_perm_valid(perm)) return perm;
+    fprintf(stderr, "sea: SEA_NS6_PERM=%s is not a permutation of the six roles 0..5 (octal digits); ignored\n", e);
+    return 0;
+}()};
 /* Forms of the same arithmetic (identical results), chosen by how many utterances share a CU:
  *   <= 3 per CU  six waves per utterance: shortest frame period (the run time is one utterance's
  *                chain of frames; 768 utterances: 1.74 ms against 1.85 for the dense form)   SEA_NS_KERNEL=pipe6
@@ -200,9 +216,10 @@ int sea_gammatone_channels(float *cf64, float *bw64, float *midEar64)
 }
 
 /* ------------------------------------------------------------------------------------------- */
+/* stores a valid map (ns6_perm_valid) and returns the one it replaces; any other value only reads, as sea_ns_kernel_form */
 extern "C" int sea_debug_ns6_perm(int perm)
 {
-    return g_ns6_perm.exchange(perm);
+    return ns6_perm_valid(perm) ? g_ns6_perm.exchange(perm) : g_ns6_perm.load();
 }
 
 /* kernel form override: 0 = by batch size; initialised from SEA_NS_KERNEL on first use */
@@ -350,10 +367,8 @@ int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags,
     a.n_utt = n_utt;
     if (total_ceps > 0) {
         const long long nslot = total_ceps / 8 + n_utt; /* tile slots of 8 frames (cc_kernel.hip, kAfeT) */
-#ifndef SEA_AFE_GRID
-#define SEA_AFE_GRID 8192
-#endif
-        const long long want = nslot < SEA_AFE_GRID ? nslot : SEA_AFE_GRID;
+        constexpr long long kAfeGrid = 8192; /* waves of the launch */
+        const long long want = nslot < kAfeGrid ? nslot : kAfeGrid;
         hipLaunchKernelGGL(sea::afe_ceps_kernel, dim3((unsigned)want), dim3(64), 0, (hipStream_t)stream, a);
         HIP_TRY(hipGetLastError());
     }
@@ -406,10 +421,9 @@ int sea_compceps_batch(const float *d_den_f32, const long long *d_offsets, const
     a.tables = c->cc;
     a.n_utt = n_utt;
     const long long nslot = total_frames / 16 + n_utt; /* tile slots of 16 frames (cc_kernel.hip, kCcT) */
-#ifndef SEA_CC_GRID
-#define SEA_CC_GRID 16384 /* waves of the launch (3072 are resident): 8192 0.63 ms, 13312-24576 0.59-0.61, 3072 (every wave its share of the tiles, all in step) 1.0 */
-#endif
-    const long long grid = nslot < SEA_CC_GRID ? nslot : SEA_CC_GRID;
+    /* waves of the launch (3072 are resident): 8192 0.63 ms, 13312-24576 0.59-0.61, 3072 (every wave its share of the tiles, all in step) 1.0 */
+    constexpr long long kCcGrid = 16384;
+    const long long grid = nslot < kCcGrid ? nslot : kCcGrid;
     hipLaunchKernelGGL(sea::compceps_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -19,24 +19,17 @@ namespace sea {
  * HBM rate: ~240 clk per CU, i.e. ~960 SIMD-clk and ~240 LDS-array clk; the dual transform needs ~180 vector
  * issue slots and ~144 LDS clk per frame (the one-frame-per-wave form: ~300 and ~320 -- LDS-bound).  Each lane
  * gathers its eight inputs n0 + 32 bitrev3(j) straight from global memory (per instruction the 32 lanes of a frame
- * read one contiguous 128-byte line), one pair ahead; results leave as one float4 per lane and frame. */
-#ifndef SEA_RFFT_ADDR_LDS
-#define SEA_RFFT_ADDR_LDS 0 /* operand addresses in VGPRs: 4.45 TB/s; in LDS (76 VGPRs, five waves per SIMD): 4.04 */
-#endif
-#ifndef SEA_RFFT_WAVES
-#define SEA_RFFT_WAVES 4
-#endif
-#ifndef SEA_RFFT_NT
-#define SEA_RFFT_NT 1
-#endif
-__global__ __launch_bounds__(64, SEA_RFFT_WAVES) void rfft256_kernel(const float *in, float *out, long long nframes,
+ * read one contiguous 128-byte line), one pair ahead; results leave as one float4 per lane and frame.
+ * The butterflies' operand addresses stay in VGPRs (4.45 TB/s; in LDS -- 76 VGPRs, five waves per SIMD -- 4.04); loads and stores are
+ * non-temporal: every frame is touched once. */
+constexpr int kRfftWaves = 4; /* waves per SIMD the register allocation leaves room for */
+__global__ __launch_bounds__(64, kRfftWaves) void rfft256_kernel(const float *in, float *out, long long nframes,
                                                                      const sea_fft_tables *t)
 {
     __shared__ __attribute__((aligned(16))) float work[512];
-    __shared__ uint4 addrLds[SEA_RFFT_ADDR_LDS ? SEA_FFT_LSTAGES * 64 : 1];
     const int lane = threadIdx.x;
     Fft2Regs R;
-    load_fft2_regs<SEA_RFFT_ADDR_LDS != 0>(R, t, lane, addrLds);
+    load_fft2_regs<false>(R, t, lane, nullptr);
     wave_sync();
     const int n0 = lane & 31, h = lane >> 5;
     unsigned oa[4]; /* where elements 4l..4l+3 of the reference's order sit in a (swizzled) work area */
@@ -49,7 +42,7 @@ __global__ __launch_bounds__(64, SEA_RFFT_WAVES) void rfft256_kernel(const float
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             constexpr int kRev3[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-            const float v = SEA_RFFT_NT ? __builtin_nontemporal_load(x + 32 * kRev3[k]) : x[32 * kRev3[k]];
+            const float v = __builtin_nontemporal_load(x + 32 * kRev3[k]);
             e[k] = (f < nframes) ? v : 0.0f;
         }
     };
@@ -61,7 +54,7 @@ __global__ __launch_bounds__(64, SEA_RFFT_WAVES) void rfft256_kernel(const float
 #pragma unroll
         for (int k = 0; k < 8; ++k) nxt[k] = 0.0f;
         if (pn < npair) load(pn, nxt);
-        rfft256_dual<SEA_RFFT_ADDR_LDS != 0>(cur, work, R);
+        rfft256_dual(cur, work, R);
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
             const long long f = 2 * p + hh;
@@ -73,10 +66,7 @@ __global__ __launch_bounds__(64, SEA_RFFT_WAVES) void rfft256_kernel(const float
                 v.z = fft_at(w, oa[2]);
                 v.w = fft_at(w, oa[3]);
                 typedef float v4f __attribute__((ext_vector_type(4)));
-                if (SEA_RFFT_NT)
-                    __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f *>(out + f * 256 + 4 * lane));
-                else
-                    *reinterpret_cast<float4 *>(out + f * 256 + 4 * lane) = v;
+                __builtin_nontemporal_store(v4f{v.x, v.y, v.z, v.w}, reinterpret_cast<v4f *>(out + f * 256 + 4 * lane));
             }
         }
         wave_sync();
@@ -186,17 +176,7 @@ __global__ __launch_bounds__(256) void rfft_any_kernel(float *x, const unsigned 
  * ================================================================================================ */
 namespace {
 
-#ifndef SEA_CC_TILE
-#define SEA_CC_TILE 16
-#endif
-constexpr int kCcT = SEA_CC_TILE;
-
-#ifndef SEA_CC_FASTLOG
-#define SEA_CC_FASTLOG 1
-#endif
-#ifndef SEA_CC_WAVES
-#define SEA_CC_WAVES 3 /* waves per SIMD the register allocation leaves room for (LDS allows twelve waves per CU) */
-#endif
+constexpr int kCcT = 16; /* frames per tile of compceps_kernel (afe_ceps_kernel: kAfeT) */
 
 /* (float)log((double)v) for a positive normal float v, as CompCeps.c:423 / :511 take it.  The library's double log
  * costs ~150 instructions; the kernels' own table-driven one (ns_core.h, ns_ln: within ~1.1 ulp) gives the same float
@@ -205,13 +185,9 @@ constexpr int kCcT = SEA_CC_TILE;
  * (ns_near_float_boundary; window 4 ulps: ours 1.1 + glibc's 0.52, doubled). */
 __device__ __forceinline__ float cc_logf(float v)
 {
-#if SEA_CC_FASTLOG
     const double l = ns_ln<false>((double)v);
     if (__builtin_expect(ns_near_float_boundary(l, 4), 0)) return (float)ns_ln_cr((double)v);
     return (float)l;
-#else
-    return (float)log((double)v);
-#endif
 }
 
 template <bool SHARED, int T = kCcT>
@@ -432,10 +408,9 @@ __global__ __launch_bounds__(64) void compceps_frames_kernel(const float *data20
     }
 }
 
-#ifndef SEA_CC_MINW
-#define SEA_CC_MINW 3 /* 168 VGPRs, no spilled vector register; left to itself the allocator takes 193 = two waves per SIMD */
-#endif
-__global__ __launch_bounds__(64, SEA_CC_MINW) void compceps_kernel(CepsArgs a)
+/* three waves per SIMD (LDS allows twelve waves per CU): 168 VGPRs, no spilled vector register; left to itself the allocator takes
+ * 193 = two waves per SIMD */
+__global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
 {
     __shared__ CcTileLds<true> L;
     const int lane = threadIdx.x;
@@ -482,20 +457,19 @@ __global__ __launch_bounds__(64, SEA_CC_MINW) void compceps_kernel(CepsArgs a)
             /* all of the tile's words are requested before the first is stored: written as a load-store loop the
              * compiler waits for each of the 22 requests in turn -- ~22 HBM latencies per tile, most of the kernel's time */
             constexpr int kReq = (SEA_HOP * (kCcT - 1) + SEA_WIN + 1 + kLanes - 1) / kLanes; /* 22 */
-#ifndef SEA_CC_STAGE_BATCH
-#define SEA_CC_STAGE_BATCH 11 /* round 3: 22 at once two waves per SIMD 0.77 ms, 8: three waves 0.71; round 4 (three waves per SIMD forced, 168 VGPRs
-                                * either way): 8 0.610 ms, 11 = two equal batches 0.58-0.60, 12 0.60, 22 (32 spilled registers) not run */
-#endif
+            /* round 3: 22 at once two waves per SIMD 0.77 ms, 8: three waves 0.71; round 4 (three waves per SIMD forced, 168 VGPRs
+             * either way): 8 0.610 ms, 11 = two equal batches 0.58-0.60, 12 0.60, 22 (32 spilled registers) not run */
+            constexpr int kCcStageBatch = 11;
 #pragma unroll 1
-            for (int b0 = 0; b0 < kReq; b0 += SEA_CC_STAGE_BATCH) {
-                float sv[SEA_CC_STAGE_BATCH];
+            for (int b0 = 0; b0 < kReq; b0 += kCcStageBatch) {
+                float sv[kCcStageBatch];
 #pragma unroll
-                for (int k = 0; k < SEA_CC_STAGE_BATCH; ++k) {
+                for (int k = 0; k < kCcStageBatch; ++k) {
                     const int x = lane + kLanes * (b0 + k);
                     sv[k] = (x < nword && !(x == 0 && j0 == 0)) ? cur0[x - 1] : 0.0f;
                 }
 #pragma unroll
-                for (int k = 0; k < SEA_CC_STAGE_BATCH; ++k) {
+                for (int k = 0; k < kCcStageBatch; ++k) {
                     const int x = lane + kLanes * (b0 + k);
                     if (x < nword) L.span[x + x / SEA_HOP] = sv[k];
                 }
@@ -523,12 +497,10 @@ __global__ __launch_bounds__(64, SEA_CC_MINW) void compceps_kernel(CepsArgs a)
  * ================================================================================================ */
 namespace {
 
-#ifndef SEA_WP_ROWS
-#define SEA_WP_ROWS 1 /* 1: the peak searches of four frames side by side, one per row of 16 lanes (feature pass 4.19 -> 3.82 ms);
-                         0: one frame at a time, wave-wide.  Dealing the Teager / smoothing / window steps of the four frames
-                         to the lanes as 800 samples as well (13 rounds, one sync per group) measured SLOWER, 4.39 ms: per-lane
-                         frame index, divisions by 200 and a divergent loop over each frame's own peak list */
-#endif
+/* DoWaveProc: the peak searches of four frames run side by side, one per row of 16 lanes (feature pass 4.19 -> 3.82 ms against
+ * one frame at a time, wave-wide).  Dealing the Teager / smoothing / window steps of the four frames to the lanes as 800 samples as
+ * well (13 rounds, one sync per group) measured SLOWER, 4.39 ms: per-lane frame index, divisions by 200 and a divergent loop over
+ * each frame's own peak list */
 
 struct __attribute__((aligned(16))) WpLds { /* scratch of DoWaveProc: four frames in flight */
     float tw[200];
@@ -537,33 +509,6 @@ struct __attribute__((aligned(16))) WpLds { /* scratch of DoWaveProc: four frame
     int pos[4][24];
     int nom[4];
 };
-
-/* wave-wide maximum of a signed 32-bit value in 6 DPP steps (row_shr 1/2/4/8 within rows of 16
- * lanes, then row_bcast 15 / 31 across rows: the total lands in lane 63); a ds_bpermute butterfly
- * costs an LDS round trip per step instead */
-__device__ __forceinline__ int wave_max_i32(int v)
-{
-    constexpr int kMin = -2147483647 - 1;
-    auto mx = [](int a, int b) { return a > b ? a : b; };
-    v = mx(v, __builtin_amdgcn_update_dpp(kMin, v, 0x111, 0xf, 0xf, false)); /* row_shr:1 */
-    v = mx(v, __builtin_amdgcn_update_dpp(kMin, v, 0x112, 0xf, 0xf, false)); /* row_shr:2 */
-    v = mx(v, __builtin_amdgcn_update_dpp(kMin, v, 0x114, 0xf, 0xf, false)); /* row_shr:4 */
-    v = mx(v, __builtin_amdgcn_update_dpp(kMin, v, 0x118, 0xf, 0xf, false)); /* row_shr:8 */
-    v = mx(v, __builtin_amdgcn_update_dpp(kMin, v, 0x142, 0xa, 0xf, false)); /* row_bcast:15 -> rows 1, 3 */
-    v = mx(v, __builtin_amdgcn_update_dpp(kMin, v, 0x143, 0xc, 0xf, false)); /* row_bcast:31 -> rows 2, 3 */
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-/* wave-wide arg-max of (value >= 0, index < 256) pairs; ties go to the LOWER index if lowWins, else
- * the higher.  Entries with valid == false never win.  Returns the winning index, -1 if none. */
-__device__ __forceinline__ int wave_argmax(int value, int index, bool valid, bool lowWins)
-{
-    const int m = wave_max_i32(valid ? value : -1);
-    if (m < 0) return -1;
-    const int code = (valid && value == m) ? (lowWins ? 255 - index : index) : -1;
-    const int c = wave_max_i32(code);
-    return lowWins ? 255 - c : c;
-}
 
 /* maximum over each ROW of 16 lanes, left in every lane of the row: an xor butterfly in four DPP steps
  * (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror) */
@@ -577,7 +522,8 @@ __device__ __forceinline__ int row_max_i32(int v)
     return v;
 }
 
-/* wave_argmax per row of 16 lanes (every lane of a row gets its row's answer) */
+/* arg-max of (value >= 0, index < 256) pairs per row of 16 lanes (every lane of a row gets its row's answer); ties go to the
+ * LOWER index if lowWins, else the higher.  Entries with valid == false never win.  Returns the winning index, -1 if none. */
 __device__ __forceinline__ int row_argmax(int value, int index, bool valid, bool lowWins)
 {
     const int m = row_max_i32(valid ? value : -1);
@@ -589,7 +535,7 @@ __device__ __forceinline__ int row_argmax(int value, int index, bool valid, bool
 /* DoWaveProc (WaveProc.c:397-455) on a frame d[0..199] whose low-energy check (:423-427: in-order sum of squares >= 100,
  * evaluated by the caller lane = frame) has passed, in three steps:
  *   wp_smooth   Teager energy (:216-226) and its 9-point integer smoothing                      -> W.sm[slot]
- *   wp_peaks    maxima 25..79 samples apart (:102-190)                                          -> W.pos[slot], W.nom[slot]
+ *   wp_peaks4   maxima 25..79 samples apart (:102-190), four frames side by side               -> W.pos[slot], W.nom[slot]
  *   wp_window   a two-level window around them (:244-330), applied in place
  * Each ends with wave_sync(). */
 __device__ __forceinline__ void wp_smooth(WpLds &W, int slot, const float *d, int lane)
@@ -624,74 +570,7 @@ __device__ __forceinline__ void wp_smooth(WpLds &W, int slot, const float *d, in
     wave_sync();
 }
 
-/* one frame, wave-wide */
-__device__ __forceinline__ void wp_peaks(WpLds &W, int slot, int lane)
-{
-    constexpr int N = 200;
-    const int *sm = W.sm[slot];
-    /* global maximum: first index of the largest value, which must exceed 0 */
-    int nom = 0;
-    {
-        int bv = 0, bi = -1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int i = lane + 64 * k;
-            if (i < N && sm[i] > bv) { /* ascending i per lane: strict > keeps the first */
-                bv = sm[i];
-                bi = i;
-            }
-        }
-        const int p0 = wave_argmax(bv, bi, bi >= 0, true);
-        if (p0 >= 0) {
-            int R[10], Lf[10], cR = 0, cL = 0;
-            R[0] = Lf[0] = p0;
-            bool found = true;
-#pragma unroll 1
-            while (R[cR] + 25 < N && found) { /* to the right: last of equals = the higher index */
-                const int idx = R[cR] + 25 + lane;
-                const bool in = lane < 55 && idx < N;
-                const int v = in ? sm[idx] : -1;
-                const int nx = wave_argmax(v, idx, in && v >= 0, false);
-                found = nx >= 0;
-                if (found) {
-#pragma unroll
-                    for (int c = 0; c < 9; ++c)
-                        if (c == cR) R[c + 1] = nx;
-                    cR++;
-                }
-            }
-            found = true;
-#pragma unroll 1
-            while (Lf[cL] - 25 > 0 && found) { /* to the left: last of equals in scan order = the lower index */
-                const int idx = Lf[cL] - 25 - lane;
-                const bool in = lane < 55 && idx > -1;
-                const int v = in ? sm[idx] : -1;
-                const int nx = wave_argmax(v, idx, in && v >= 0, true);
-                found = nx >= 0;
-                if (found) {
-#pragma unroll
-                    for (int c = 0; c < 9; ++c)
-                        if (c == cL) Lf[c + 1] = nx;
-                    cL++;
-                }
-            }
-            /* ascending: left ones (farthest first), centre, right ones */
-            if (lane == 0) {
-#pragma unroll
-                for (int c = 9; c >= 1; --c)
-                    if (c <= cL) W.pos[slot][nom++] = Lf[c];
-#pragma unroll
-                for (int c = 0; c < 10; ++c)
-                    if (c <= cR) W.pos[slot][nom++] = R[c];
-            }
-            nom = cL + cR + 1;
-        }
-    }
-    if (lane == 0) W.nom[slot] = nom;
-    wave_sync();
-}
-
-/* the same search for up to four frames at once, frame `slot` = row `slot` of 16 lanes (mask: bit slot = that frame takes
+/* the search for up to four frames at once, frame `slot` = row `slot` of 16 lanes (mask: bit slot = that frame takes
  * part): the searches are short dependent chains of wave-wide reductions, so four of them side by side cost what one does */
 __device__ __forceinline__ void wp_peaks4(WpLds &W, unsigned mask, int lane)
 {
@@ -839,10 +718,7 @@ __device__ __forceinline__ void wp_window(WpLds &W, int slot, float *d, int lane
 /* frames per tile of afe_ceps_kernel: 8 (same-box A/B of the feature pass: 16 frames 3.71 ms, 8 frames 3.05 ms -- half the
  * LDS per wave, 15.6 instead of 25 KB, lets the CU hold the eight waves its registers allow instead of six; compceps_kernel
  * itself is fastest with 16: 0.715 ms against 0.77-0.79 with 8 and 1.42 with 4) */
-#ifndef SEA_AFE_TILE
-#define SEA_AFE_TILE 8
-#endif
-constexpr int kAfeT = SEA_AFE_TILE;
+constexpr int kAfeT = 8;
 
 /* timing-only diagnostic (-DSEA_AFE_TIMING, tools/afe_phases.py): shader clocks workgroup 0 spends per step of a tile */
 #ifdef SEA_AFE_TIMING
@@ -862,10 +738,7 @@ extern "C" int sea_afe_timing(unsigned long long *out8, int reset)
 #define AFE_CK(k)
 #endif
 
-#ifndef SEA_AFE_MINW
-#define SEA_AFE_MINW 1
-#endif
-__global__ __launch_bounds__(64, SEA_AFE_MINW) void afe_ceps_kernel(AfeArgs a)
+__global__ __launch_bounds__(64, 1) void afe_ceps_kernel(AfeArgs a)
 {
     __shared__ CcTileLds<false, kAfeT> L;
     __shared__ WpLds W;
@@ -897,23 +770,21 @@ __global__ __launch_bounds__(64, SEA_AFE_MINW) void afe_ceps_kernel(AfeArgs a)
             /* frameBuf of ParmInterface.c:281 for cepstral frame j: Data[-1..199] = the float NoiseSup stream from
              * sample 80 (f0 + j) - 1 on; Data[-1] of the utterance's first cepstral frame is 0 */
             const float *cur0 = a.den_f32 + a.offsets[u] + (f0 + j0) * SEA_HOP;
-#ifndef SEA_AFE_BATCH
-#define SEA_AFE_BATCH 17 /* 1: 4.03 ms for the feature pass, 6: 3.78, 13-17: 3.66 (outer loop kept rolled) */
-#endif
+            constexpr int kAfeBatch = 17; /* 1: 4.03 ms for the feature pass, 6: 3.78, 13-17: 3.66 (outer loop kept rolled) */
             /* requests in batches before their stores, the outer loop kept rolled (fully unrolled the allocator went to
              * 256 VGPRs + 95 AGPRs, one wave per SIMD: 3.96 -> 5.9 ms) */
             constexpr int kIter = (kAfeT * 201 + kLanes - 1) / kLanes; /* 51 */
 #pragma unroll 1
-            for (int b0 = 0; b0 < kIter; b0 += SEA_AFE_BATCH) {
-                float sv[SEA_AFE_BATCH];
+            for (int b0 = 0; b0 < kIter; b0 += kAfeBatch) {
+                float sv[kAfeBatch];
 #pragma unroll
-                for (int k = 0; k < SEA_AFE_BATCH; ++k) {
+                for (int k = 0; k < kAfeBatch; ++k) {
                     const int i = lane + kLanes * (b0 + k);
                     const int f = i / 201, x = i - f * 201;
                     sv[k] = (i < nv * 201 && !(x == 0 && f == 0 && j0 == 0)) ? cur0[SEA_HOP * f + x - 1] : 0.0f;
                 }
 #pragma unroll
-                for (int k = 0; k < SEA_AFE_BATCH; ++k) {
+                for (int k = 0; k < kAfeBatch; ++k) {
                     const int i = lane + kLanes * (b0 + k);
                     if (i < nv * 201) L.span[i] = sv[k];
                 }
@@ -931,7 +802,6 @@ __global__ __launch_bounds__(64, SEA_AFE_MINW) void afe_ceps_kernel(AfeArgs a)
             }
             const unsigned long long pass = __ballot(lane < nv && (double)energy >= 100.0);
             AFE_CK(1);
-#if SEA_WP_ROWS
             for (int g = 0; g < nv; g += 4) { /* four frames at a time: their peak searches run side by side */
                 const unsigned m4 = (unsigned)(pass >> g) & 0xfu;
                 if (m4 == 0) continue;
@@ -944,14 +814,6 @@ __global__ __launch_bounds__(64, SEA_AFE_MINW) void afe_ceps_kernel(AfeArgs a)
                     if ((m4 >> r) & 1u) wp_window(W, r, L.span + 201 * (g + r) + 1, lane);
                 AFE_CK(4);
             }
-#else
-            for (int f = 0; f < nv; ++f)
-                if ((pass >> f) & 1ull) {
-                    wp_smooth(W, 0, L.span + 201 * f + 1, lane);
-                    wp_peaks(W, 0, lane);
-                    wp_window(W, 0, L.span + 201 * f + 1, lane);
-                }
-#endif
             wave_sync();
             cc_tile<false, kAfeT>(L, C, nv, dst, lane);
             AFE_CK(5);

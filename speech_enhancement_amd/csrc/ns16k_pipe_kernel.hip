@@ -30,10 +30,6 @@
  */
 #include "ns_core.h"
 
-#ifndef SEA16P_LOG_IN_S
-#define SEA16P_LOG_IN_S 1
-#endif
-
 namespace sea {
 
 namespace p16 {
@@ -349,9 +345,9 @@ __device__ __forceinline__ void back16(StreamLds &L, const Tab &T, const float *
         if (nb < 2147483647) nb++;
         s.nbFrame[ST] = nb;
     }
-    /* _VAD_ (:350-421).  SEA16P_LOG_IN_S (round 4): the helper wave S, which idles ~3500 clk of a beat, took the log-energy of the
+    /* _VAD_ (:350-421).  The helper wave S, which idles ~3500 clk of a beat, took the log-energy of the
      * sum it left at intake; this wave -- the longest role -- only updates the VAD with it */
-    if (ST == 0) vad_update(s, SEA16P_LOG_IN_S ? frameSum : vad_frame_energy(frameSum));
+    if (ST == 0) vad_update(s, frameSum);
     const int nb16 = (int)(short)s.nbFrame[ST];
     float nSigv[3], Pv[3], noisev[3], denv[3], Wv[3];
     bool inDomain = true;
@@ -368,7 +364,7 @@ __device__ __forceinline__ void back16(StreamLds &L, const Tab &T, const float *
     }
     /* the guarded fast-division domain of ns_core.h (ns_back), established per frame, wave-uniformly */
     const bool domainNow = __ballot(!inDomain) == 0ull;
-    const bool fast = SEA_NS_FAST_DIV && domainNow && (s.psdOk[ST] != 0);
+    const bool fast = domainNow && (s.psdOk[ST] != 0);
     s.psdOk[ST] = domainNow ? 1 : 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k)
@@ -797,7 +793,7 @@ __global__ void __launch_bounds__(256 * p16::kStreams, 4) ns16k_pipe_kernel(Ns16
                 const float *fr = L.circ[0] + (tk & (kSlots - 1)) * kHop;
                 float acc = 64.0f;
                 for (int n = 0; n < kHop; ++n) acc += fr[n] * fr[n];
-                const float accEn = SEA16P_LOG_IN_S ? vad_frame_energy(acc) : acc;
+                const float accEn = vad_frame_energy(acc);
                 if (lane == 0) L.frameEn[tk & (kSlots - 1)] = accEn;
             }
             wave_sync();
@@ -880,7 +876,7 @@ __global__ void __launch_bounds__(256 * p16::kStreams, 4) ns16k_pipe_kernel(Ns16
                         valid = 1;
                         tick++;
                         slot_store3(L.circ[0], tick, lane, x);
-                        const float vadEn = SEA16P_LOG_IN_S ? vad_frame_energy(vadSum) : vadSum;
+                        const float vadEn = vad_frame_energy(vadSum);
                         if (lane == 0) L.frameEn[tick & (kSlots - 1)] = vadEn;
                     }
                     if (lane == 0) {

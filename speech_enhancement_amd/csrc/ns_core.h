@@ -49,31 +49,10 @@ struct NsConst {
     float eps;
 };
 
-/* per-utterance recursive state that is not in LDS */
-#ifndef SEA_NS_FAST_SQRT
-#define SEA_NS_FAST_SQRT 1
-#endif
-#if SEA_NS_FAST_SQRT
+/* the square root inside the fast-division domain (ns_sqrt_fast below); outside it the code calls sqrtf */
 #define SEA_SQRT(x) ns_sqrt_fast(x)
-#else
-#define SEA_SQRT(x) sqrtf(x)
-#endif
-#ifndef SEA_NS_PAIR_BINS
-#define SEA_NS_PAIR_BINS 1
-#endif
-#ifndef SEA_NS_FAST_DIV
-#define SEA_NS_FAST_DIV 1
-#endif
-#ifndef SEA_NOISE_SAFE
-#define SEA_NOISE_SAFE 1 /* skip the noise range test after a frame that ran inside the fast-division domain (ns_back) */
-#endif
-#ifndef SEA_P6_G1_PK
-#define SEA_P6_G1_PK 1 /* six-wave forms' gain wave: lean square roots and packed gains inside the fast-division domain, as the four-wave forms */
-#endif
-#ifndef SEA_NS_STEADY
-#define SEA_NS_STEADY 1 /* branch-free FilterCalc of (bin lane, bin 64) side by side in the forms without register pairs */
-#endif
 
+/* per-utterance recursive state that is not in LDS */
 struct NsRegs {
     /* per bin: [stage]; "Lo" = bin lane (0..63), "Hi" = bin 64 (meaningful in lane 0) */
     float noiseLo[2], noiseHi[2];   /* noiseSE1/2 */
@@ -123,50 +102,9 @@ __device__ __forceinline__ float uniform_f(float v)
  * (< 1 ulp) at two scalar sites per frame and immediately rounds the result of a short double
  * expression to float; any double log accurate to a few ulp yields the same float except when the
  * exact value sits within ~1e-16 (relative) of a float rounding boundary (probability ~1e-8 per
- * call) -- the same caveat the device library's own log carries against glibc.  This one is
- * ~3x shorter than the general-purpose library routine, which matters because both sites sit on
- * lane-redundant critical chains:  x = m 2^e, m in [sqrt(1/2), sqrt 2), f = (m-1)/(m+1),
- * ln m = 2 f (1 + f^2/3 + f^4/5 + ... + f^22/23), ln x = e ln2_hi + (e ln2_lo + ln m).
- * Measured against 40-digit references by tests/test_gpu_parity.py::test_selftest_log. */
-__device__ __forceinline__ double ns_ln_series(double x)
-{
-    const long long bits = __double_as_longlong(x);
-    int e = (int)((bits >> 52) & 0x7ff) - 1023;
-    double m = __longlong_as_double((bits & 0x000fffffffffffffLL) | 0x3ff0000000000000LL); /* [1,2) */
-    const bool big = m > 1.4142135623730951;
-    m = big ? m * 0.5 : m;
-    e = big ? e + 1 : e;
-    /* f = (m-1)/(m+1) by reciprocal refinement (m+1 in [1.7, 2.42]: no scaling needed) */
-    const double d = m + 1.0, n = m - 1.0;
-    double r = __builtin_amdgcn_rcp(d);
-    r = __fma_rn(__fma_rn(-d, r, 1.0), r, r);
-    r = __fma_rn(__fma_rn(-d, r, 1.0), r, r);
-    double f = n * r;
-    f = __fma_rn(__fma_rn(-d, f, n), r, f);
-    const double f2 = f * f;
-    double p = 1.0 / 23.0;
-    p = __fma_rn(p, f2, 1.0 / 21.0);
-    p = __fma_rn(p, f2, 1.0 / 19.0);
-    p = __fma_rn(p, f2, 1.0 / 17.0);
-    p = __fma_rn(p, f2, 1.0 / 15.0);
-    p = __fma_rn(p, f2, 1.0 / 13.0);
-    p = __fma_rn(p, f2, 1.0 / 11.0);
-    p = __fma_rn(p, f2, 1.0 / 9.0);
-    p = __fma_rn(p, f2, 1.0 / 7.0);
-    p = __fma_rn(p, f2, 1.0 / 5.0);
-    p = __fma_rn(p, f2, 1.0 / 3.0);
-    /* ln m = 2f + 2f * f2 * p  (the leading term kept separate: it carries almost all the value) */
-    const double two_f = f + f;
-    const double lnm = __fma_rn(two_f * f2, p, two_f);
-    const double de = (double)e;
-    /* ln2 split so that e * ln2_hi is exact for |e| < 2^10 */
-    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
-    return __fma_rn(de, ln2_hi, __fma_rn(de, ln2_lo, lnm));
-}
-
-
-/* The same logarithm, table-driven (round 3): both call sites sit on the two longest role waves of the pipelined
- * kernel and the series above is a chain of ~30 dependent double-precision instructions.  Here
+ * call) -- the same caveat the device library's own log carries against glibc.  Both sites sit on
+ * lane-redundant critical chains of the two longest role waves of the pipelined kernel, so the log is
+ * table-driven (a series in (m-1)/(m+1) was a chain of ~30 dependent double-precision instructions):
  *     x = m 2^e, m in [sqrt 1/2, sqrt 2);   i = interval of m (256 intervals of 2^15 float patterns, ns_logtab.inc)
  *     r = m c_i - 1      exact: m is a float (both sites pass floats), c_i has 26 significant bits, |r| <= 2^-9
  *     ln x = e ln2 + (th_i + tl_i) + (r - r^2/2 + r^3/3 - r^4/4 + r^5/5 - r^6/6)
@@ -181,9 +119,6 @@ static __device__ const double kNsLogTab[256][3] = {
 template <bool UNI = false> /* UNI: the argument is wave-uniform -> the table row comes through a scalar load */
 __device__ __forceinline__ double ns_ln(double x)
 {
-#ifdef SEA_LN_SERIES
-    return ns_ln_series(x);
-#else
     const unsigned fb = __float_as_uint((float)x); /* exact: x is a float */
     int e = (int)(fb >> 23) - 127;
     unsigned mb = (fb & 0x007fffffu) | 0x3f800000u; /* m in [1, 2) */
@@ -207,7 +142,6 @@ __device__ __forceinline__ double ns_ln(double x)
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
     const double small = __fma_rn(r2, p, r) + __fma_rn(de, ln2_lo, tl);
     return __fma_rn(de, ln2_hi, th) + small;
-#endif
 }
 
 /* ---- the guard of the lean log --------------------------------------------------------------------------
@@ -605,11 +539,7 @@ __device__ __forceinline__ float filter_steady(float P, float nSig, float &noise
  * the raw frame only, so the pipelined kernel computes it in its helper wave */
 __device__ __forceinline__ float vad_frame_energy(float frameSum)
 {
-#ifdef SEA_LIBM_LOG
-    return uniform_f((float)(0.5 + (log((double)frameSum / 64.0) / kLn2) * 16.0));
-#else
     return uniform_f(ns_vad_energy_expr<true>(uniform_f(frameSum)));
-#endif
 }
 
 /* squares of the raw frame frame[0..79] -> sq[0..79], then the in-order sum (all lanes) */
@@ -622,11 +552,7 @@ __device__ __forceinline__ float vad_frame_sum(const float *frame, float *sq, in
         sq[64 + lane] = y * y;
     }
     wave_sync();
-#ifdef SEA_ABLATE_VADSUM
-    return 64.0f + sq[0] + sq[79];
-#else
     return serial_sum<80>(sq, 64.0f);
-#endif
 }
 
 /* VAD for noise suppression, NoiseSup.c:359-430 (first stage only does work) */
@@ -663,12 +589,8 @@ __device__ __forceinline__ void vad_update(NsRegs &s, float frameEn)
 __device__ __forceinline__ void gain_fact_update(NsRegs &s, float noiseEn)
 {
     float averSNR = (s.denEn0 * s.denEn1 * s.denEn2) / (noiseEn * noiseEn * noiseEn);
-    if ((double)averSNR > 0.00001)
-#ifdef SEA_LIBM_LOG
-        averSNR = (float)((20 * log10((double)averSNR)) / 3.0);
-#else /* log10(y) = ln(y) * log10(e), guarded (ns_aversnr_expr) */
+    if ((double)averSNR > 0.00001) /* log10(y) = ln(y) * log10(e), guarded (ns_aversnr_expr) */
         averSNR = ns_aversnr_expr<true>(uniform_f(averSNR));
-#endif
     else
         averSNR = (float)(-100.0 / 3.0);
     averSNR = uniform_f(averSNR);
@@ -799,43 +721,12 @@ __device__ __forceinline__ void ns_front(const float *buf, float *work, float *p
     wave_sync();
 }
 
-/* FFTtoPSD (NoiseSup.c:249-270) of one transformed frame of the dual transform -> psd[0..64]
- * (addresses from the tables: the work area is swizzled).  All five operands are fetched unconditionally (lane 0's
- * unused Im(0) address is element 0, the Nyquist bin is a broadcast read) and made opaque before the arithmetic:
- * written with conditional loads the compiler builds a branch -- and an LDS latency -- per operand. */
-struct PsdOps {
-    float re0, re1, im1, im0, ny;
-};
-__device__ __forceinline__ void psd_load(const float *work, const Fft2Regs &R, PsdOps &o)
-{
-    o.re0 = fft_at(work, R.psdA[0] & 0xffffu), o.re1 = fft_at(work, R.psdA[0] >> 16);
-    o.im1 = fft_at(work, R.psdA[1] & 0xffffu), o.im0 = fft_at(work, R.psdA[1] >> 16);
-    o.ny = fft_at(work, R.nyq);
-}
-__device__ __forceinline__ void psd_store(const PsdOps &o, float *psd, int lane)
-{
-    const float p0 = (lane > 0) ? (o.re0 * o.re0 + o.im0 * o.im0) : (o.re0 * o.re0);
-    const float p1 = o.re1 * o.re1 + o.im1 * o.im1;
-    psd[lane] = (p0 + p1) * 0.5f;
-    if (lane == 0) psd[64] = o.ny * o.ny;
-}
-__device__ __forceinline__ void psd_from_fft2(const float *work, float *psd, const Fft2Regs &R, int lane)
-{
-    PsdOps o;
-    psd_load(work, R, o);
-    asm volatile("" : "+v"(o.re0), "+v"(o.re1), "+v"(o.im1), "+v"(o.im0), "+v"(o.ny));
-    psd_store(o, psd, lane);
-}
-
 /* FFTtoPSD of BOTH transforms of a dual transform straight from the registers of its last level (sea_device.h,
  * rfft256_dual_keep_last): slot s = lane & 31 of a transform holds both parts of the bins s + 1, 65 + s, 63 - s, 127 - s (slot 31: 0, 64,
  * 32, 96 and 128), so a PSD value (P(2l) + P(2l+1)) / 2 is the sum of one kind of power of two NEIGHBOURING slots: the even slots take
  * them -- from the slot below (cyclic within the transform's 32 lanes: wave_shr:1, slots 0 repaired from lanes 31 / 63) for the bins
- * below 32 and from 64 to 95, from the slot above (the same quad) for the others.  Same products, same sums as psd_store; no store of
+ * below 32 and from 64 to 95, from the slot above (the same quad) for the others.  Same products, same sums as FFTtoPSD takes them; no store of
  * the level's results, no reads of the spectrum.  (NoiseSup.c:249-270) */
-#ifndef SEA_PSD_REGS
-#define SEA_PSD_REGS 1
-#endif
 __device__ __forceinline__ void psd_from_last_level(const float (&o)[8], const Fft2Regs &R, float *psdA, bool actA, float *psdB,
                                                     bool actB, int lane)
 {
@@ -905,38 +796,17 @@ __device__ __forceinline__ void ns_front_dual(const float *bufA, bool actA, floa
 {
     float e[8];
     ns_window8(bufA, actA, bufB, actB, win8, lane, e);
-#ifndef SEA_BIG_LAT
-#define SEA_BIG_LAT 0 /* the table-in-LDS (large-batch, issue-bound) form keeps the throughput transform: 484 vs 468 M frames/s on the configs[4] shard */
-#endif
-    if (SEA_PSD_REGS) { /* the last level feeds the PSDs from registers */
-        float o[8];
-        if (!ADDR_LDS || SEA_BIG_LAT) { /* the latency form: levels chained */
-            if (SEA_FFT_HEAD16 && ADDR_LDS) {
-                rfft256_head16(e, work, fft);
-                wave_sync();
-                fft2_levels_keep_last<2, 5, ADDR_LDS>(work, fft, e, o);
-            } else {
-                rfft256_head8(e, work, fft);
-                wave_sync();
-                fft2_levels_keep_last<1, 5, ADDR_LDS>(work, fft, e, o);
-            }
-        } else {
-            rfft256_dual_lo<ADDR_LDS>(e, work, fft);
-            rfft256_dual_hi_keep_last<ADDR_LDS>(work, fft, o);
-        }
-        psd_from_last_level(o, fft, psdA, actA, psdB, actB, lane);
+    float o[8]; /* the last level stays in registers and feeds the PSDs */
+    if (!ADDR_LDS) { /* the latency form: levels chained */
+        rfft256_head8(e, work, fft);
         wave_sync();
-        return;
+        fft2_levels_keep_last<1, 5, ADDR_LDS>(work, fft, e, o);
+    } else { /* the table-in-LDS (large-batch, issue-bound) form keeps the throughput transform: 484 vs 468 M frames/s on the
+              * configs[4] shard */
+        rfft256_dual_lo<ADDR_LDS>(e, work, fft);
+        rfft256_dual_hi_keep_last<ADDR_LDS>(work, fft, o);
     }
-    rfft256_dual<ADDR_LDS, (!ADDR_LDS || SEA_BIG_LAT)>(e, work, fft);
-    /* both PSDs' operands in one batch of reads */
-    PsdOps a, b;
-    psd_load(work, fft, a);
-    psd_load(work + 256, fft, b);
-    asm volatile("" : "+v"(a.re0), "+v"(a.re1), "+v"(a.im1), "+v"(a.im0), "+v"(a.ny), "+v"(b.re0), "+v"(b.re1), "+v"(b.im1),
-                 "+v"(b.im0), "+v"(b.ny));
-    if (actA) psd_store(a, psdA, lane);
-    if (actB) psd_store(b, psdB, lane);
+    psd_from_last_level(o, fft, psdA, actA, psdB, actB, lane);
     wave_sync();
 }
 
@@ -961,10 +831,8 @@ __device__ __forceinline__ float ns_mel_fb(const BackLds &B, const NsConst &C, i
  * lanes 0..39 produce two outputs each into dst.  Ends with wave_sync().
  * LDSBASIS: the 9x25 basis sits in LDS ([f][16], lane = row) instead of 25 VGPRs per lane. */
 template <bool LDSBASIS, bool RL = false>
-__device__ __forceinline__ void ns_idct_taps(float melOut, BackLds &B, const NsConst &C, int lane, const float *idctLds,
-                                             float *firOut = nullptr /* where the 17 taps go; default B.fir */)
+__device__ __forceinline__ void ns_idct_taps(float melOut, BackLds &B, const NsConst &C, int lane, const float *idctLds)
 {
-    float *fir = firOut ? firOut : B.fir;
     /* RL (the latency-bound kernel forms): band f's gain sits in lane f and reaches the nine row lanes through
      * v_readlane (a scalar operand of the multiply) instead of an LDS store, a fence and seven broadcast reads.
      * The issue-bound forms keep the LDS route: 25 lane reads are 25 more vector instructions. */
@@ -993,8 +861,8 @@ __device__ __forceinline__ void ns_idct_taps(float melOut, BackLds &B, const NsC
             h += B.mel[24] * (LDSBASIS ? idctLds[24 * 16 + lane] : C.idct[24]);
         }
         const float tap = h * C.irWin;
-        fir[8 + lane] = tap;
-        fir[8 - lane] = tap;
+        B.fir[8 + lane] = tap;
+        B.fir[8 - lane] = tap;
     }
     wave_sync();
 }
@@ -1242,16 +1110,15 @@ __device__ unsigned long long g_back_ck[16];
  *   ST 0: the VAD frame log-energy arrives in frameEnExt; the 65 denSigSE1 values go to spectOut
  *         (summed later by the helper), the denEn registers are not touched.
  *   ST 1: the caller has loaded s.denEn0..2.
- * DEFER_FIR: stop after the IDCT and deposit the 17 filter taps in dst[0..16]; the FIR itself is then
- *   run by the consumer wave (ns_fir_apply), which has cycles to spare.
- * IDCT_HEAD = K >= 0 (with DEFER_FIR): add only the first K terms of the IDCT's sums and deposit the partial sums and
- *   the remaining mel gains in dst (ns_idct_head); another wave finishes them into the taps (ns_idct_tail). */
-template <int ST, bool PIPE, bool FD = false, bool DEFER_FIR = false, bool RL = false, int IDCT_HEAD = -1>
+ * IDCT_HEAD = K >= 0: stop inside the IDCT -- add only the first K terms of its sums and deposit the partial sums and the
+ *   remaining mel gains in dst (ns_idct_head); the consumer wave, which has cycles to spare, finishes them into the taps
+ *   (ns_idct_tail, ns_idct_tail_rl) and runs the FIR itself. */
+template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1>
 __device__ __forceinline__ void ns_back(const float *psd, const float *buf, BackLds &B, NsRegs &s,
                                         const NsConst &C, float *dst, int lane, float frameEnExt = 0.0f,
                                         float *spectOut = nullptr, const float *idctLds = nullptr,
                                         NsFd *fd = nullptr, int *fdFlags = nullptr, float *fdRec = nullptr,
-                                        float *yRegs = nullptr /* RL, !DEFER_FIR: the filter's two outputs of this lane stay in
+                                        float *yRegs = nullptr /* RL, IDCT_HEAD < 0: the filter's two outputs of this lane stay in
                                                                 * yRegs[0..1] (ns_fir_regs), dst is not written */,
                                         const float *bregs = nullptr /* RL: the IDCT basis column in registers (ns_idct_head) */)
 {
@@ -1289,15 +1156,14 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
      * n2 >= P and n2 * upd < 1.1 P otherwise, :492-508), so after a fast frame the test is skipped (~10 vector instructions per stage
      * and frame); after anything else -- initial state, a reloaded state, a frame outside the domain -- it is made. */
     bool noiseOk = true;
-    if (!SEA_NOISE_SAFE || !s.noiseSafe[ST])
+    if (!s.noiseSafe[ST])
         noiseOk = __ballot(!(s.noiseLo[ST] <= 0x1p28f && s.noiseHi[ST] <= 0x1p28f && s.noiseLo[ST] >= 0x1p-15f && s.noiseHi[ST] >= 0x1p-15f)) == 0ull;
-    const bool fast = SEA_NS_FAST_DIV && psdOk && noiseOk && (s.psdOk[ST] != 0);
+    const bool fast = psdOk && noiseOk && (s.psdOk[ST] != 0);
     s.noiseSafe[ST] = fast ? 1 : 0;
     s.psdOk[ST] = psdOk ? 1 : 0;
     float WLo, WHi;
     auto lane_sum = [&](float vLo, float vHi) { return ns_lane_sum65(vLo, vHi); };
-#ifndef SEA_NS_NO_OVERLAP
-    if constexpr (ST == 1 && PIPE && RL && DEFER_FIR && !FD) {
+    if constexpr (ST == 1 && PIPE && RL && IDCT_HEAD >= 0 && !FD) {
         /* The second stage of the four-wave form, fast-division domain: two chains that do not depend on each other
          * until the gain factor is applied --
          *   A  gains of the 65 bins -> LDS -> mel filter bank              (FilterCalc :522-560, DoMelFB)
@@ -1325,19 +1191,15 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
             gain_fact_update(s, total);
             float melOut = ns_mel_fb(B, C, lane);
             melOut = (float)((double)(s.alfaGF * melOut) + (1.0 - (double)s.alfaGF) * 1.0);
-            if (IDCT_HEAD >= 0)
-                ns_idct_head<(IDCT_HEAD >= 0 ? IDCT_HEAD : 0)>(melOut, dst, lane, idctLds, bregs);
-            else
-                ns_idct_taps<PIPE, RL>(melOut, B, C, lane, idctLds, dst); /* the 17 taps straight into the consumer's record */
+            ns_idct_head<IDCT_HEAD>(melOut, dst, lane, idctLds, bregs);
             return;
         }
     }
-#endif
     if (fast) {
-        if (SEA_NS_PAIR_BINS && RL) { /* not in the 80-VGPR form: the pairs cost registers there (9 spills, -4 %) */
+        if (RL) { /* not in the 80-VGPR form: the pairs cost registers there (9 spills, -4 %) */
             filter_bins_fast<ST>(PLo, PHi, nSigLo, nSigHi, s.noiseLo[ST], s.noiseHi[ST], s.denLo[ST], s.denHi[ST],
                                  nb16, s.flagVAD, C.eps, WLo, WHi);
-        } else if (SEA_NS_STEADY && (ST == 0 || nb16 >= 11)) { /* the two chains in one basic block (filter_steady) */
+        } else if (ST == 0 || nb16 >= 11) { /* the two chains in one basic block (filter_steady) */
             WLo = filter_steady<ST>(PLo, nSigLo, s.noiseLo[ST], s.denLo[ST], nb16, s.flagVAD, C.eps);
             WHi = filter_steady<ST>(PHi, nSigHi, s.noiseHi[ST], s.denHi[ST], nb16, s.flagVAD, C.eps);
         } else {
@@ -1403,12 +1265,8 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
         }
     }
     NS_BACK_CK(3); /* in-order sum, gain factor */
-    if (DEFER_FIR && IDCT_HEAD >= 0) {
-        ns_idct_head<(IDCT_HEAD >= 0 ? IDCT_HEAD : 0)>(melOut, dst, lane, idctLds, bregs);
-    } else if (DEFER_FIR) { /* the consumer wave applies the filter (ns_fir_apply): hand over the 17 taps */
-        ns_idct_taps<PIPE, RL>(melOut, B, C, lane, idctLds);
-        if (lane < SEA_NTAP) dst[lane] = B.fir[lane];
-        wave_sync();
+    if constexpr (IDCT_HEAD >= 0) {
+        ns_idct_head<IDCT_HEAD>(melOut, dst, lane, idctLds, bregs);
     } else if (RL && PIPE && yRegs) {
         ns_fir_regs(fir_taps_rl(ns_idct_tap_rl(melOut, C.irWin, lane, idctLds, bregs)), buf, lane, yRegs[0], yRegs[1]);
     } else {
@@ -1441,7 +1299,7 @@ __device__ __forceinline__ float ns_noise1(const float *psd, float *Pout, float 
     /* the fast-division domain exactly as in ns_back (this wave sees every frame's PSD and owns the noise) */
     const bool psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
     const bool noiseOk = __ballot(!(s.noiseLo[1] <= 0x1p28f && s.noiseHi[1] <= 0x1p28f)) == 0ull;
-    const bool fast = SEA_NS_FAST_DIV && psdOk && noiseOk && (s.psdOk[1] != 0);
+    const bool fast = psdOk && noiseOk && (s.psdOk[1] != 0);
     s.psdOk[1] = psdOk ? 1 : 0;
     if (fast) {
         noise_track1<true>(PLo, s.noiseLo[1], nb16, eps);
@@ -1471,10 +1329,10 @@ __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const
     const float nSigLo = psd[lane], nSigHi = psd[64], nzLo = noise[lane], nzHi = noise[64];
     const bool psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
     const bool noiseOk = __ballot(!(nzLo <= 0x1p29f && nzHi <= 0x1p29f)) == 0ull;
-    const bool fast = SEA_NS_FAST_DIV && psdOk && noiseOk && (s.psdOk[1] != 0);
+    const bool fast = psdOk && noiseOk && (s.psdOk[1] != 0);
     s.psdOk[1] = psdOk ? 1 : 0;
     float WLo, WHi;
-    if (fast && SEA_P6_G1_PK) { /* as filter_bins_fast: the lean square root (valid on the domain), the pair (lane, 64) through the packed form */
+    if (fast) { /* as filter_bins_fast: the lean square root (valid on the domain), the pair (lane, 64) through the packed form */
         const ns_v2f nSig = {SEA_SQRT(nSigLo), SEA_SQRT(nSigHi)};
         const ns_v2f Pq = {SEA_SQRT(P[lane]), SEA_SQRT(P[64])};
         ns_v2f den = {s.denLo[1], s.denHi[1]};
@@ -1483,9 +1341,6 @@ __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const
         s.denHi[1] = den.y;
         WLo = W.x;
         WHi = W.y;
-    } else if (fast) {
-        WLo = gain_bin<true>(sqrtf(P[lane]), sqrtf(nSigLo), nzLo, s.denLo[1]);
-        WHi = gain_bin<true>(sqrtf(P[64]), sqrtf(nSigHi), nzHi, s.denHi[1]);
     } else {
         WLo = gain_bin<false>(sqrtf(P[lane]), sqrtf(nSigLo), nzLo, s.denLo[1]);
         WHi = gain_bin<false>(sqrtf(P[64]), sqrtf(nSigHi), nzHi, s.denHi[1]);
@@ -1509,10 +1364,10 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
     const float nSigLo = psd[lane], nSigHi = psd[64], nzLo = noise[lane], nzHi = noise[64];
     const bool psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
     const bool noiseOk = __ballot(!(nzLo <= 0x1p29f && nzHi <= 0x1p29f)) == 0ull;
-    const bool fast = SEA_NS_FAST_DIV && psdOk && noiseOk && (s.psdOk[1] != 0);
+    const bool fast = psdOk && noiseOk && (s.psdOk[1] != 0);
     s.psdOk[1] = psdOk ? 1 : 0;
     float WLo, WHi;
-    if (fast && SEA_P6_G1_PK) { /* as filter_bins_fast: the lean square root (valid on the domain), the pair (lane, 64) through the packed form */
+    if (fast) { /* as filter_bins_fast: the lean square root (valid on the domain), the pair (lane, 64) through the packed form */
         const ns_v2f nSig = {SEA_SQRT(nSigLo), SEA_SQRT(nSigHi)};
         const ns_v2f Pq = {SEA_SQRT(P[lane]), SEA_SQRT(P[64])};
         ns_v2f den = {s.denLo[1], s.denHi[1]};
@@ -1521,9 +1376,6 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
         s.denHi[1] = den.y;
         WLo = W.x;
         WHi = W.y;
-    } else if (fast) {
-        WLo = gain_bin<true>(sqrtf(P[lane]), sqrtf(nSigLo), nzLo, s.denLo[1]);
-        WHi = gain_bin<true>(sqrtf(P[64]), sqrtf(nSigHi), nzHi, s.denHi[1]);
     } else {
         WLo = gain_bin<false>(sqrtf(P[lane]), sqrtf(nSigLo), nzLo, s.denLo[1]);
         WHi = gain_bin<false>(sqrtf(P[64]), sqrtf(nSigHi), nzHi, s.denHi[1]);
@@ -1564,12 +1416,8 @@ __device__ __forceinline__ bool dc_filter(const float *dif, float *out, float &y
 {
     const float y0 = yState;
     float y = y0;
-#ifdef SEA_ABLATE_DC
-    for (int n = 0; n < 4; n += 4) {
-#else
 #pragma unroll 5
     for (int n = 0; n < SEA_HOP; n += 4) {
-#endif
         const float4 d = *reinterpret_cast<const float4 *>(&dif[n]);
         float4 o;
         y = __fmaf_rn(0.9990234375f, y, d.x);

@@ -20,11 +20,11 @@
  * iteration, read at the next); the two transform work areas alternate between FA and FB.
  *
  * Round 4: this is the form for up to FOUR utterances per CU, configs[1] included (capi.hip::ns_pick_form).  Up to three per CU
- * ns_denoise_pipe6_kernel (80 VGPRs, the lighter helper wave: SEA_P6_LIGHT_S); for the fourth ns_denoise_pipe6_dense_kernel, the same
+ * ns_denoise_pipe6_kernel (80 VGPRs, the lighter helper wave: LIGHT / DIFG1 of ns_pipe6_body); for the fourth ns_denoise_pipe6_dense_kernel, the same
  * body compiled for seven waves per SIMD -- with six, the dispatcher never found room for the fourth six-wave workgroup of a CU, which is
  * what rounds 1-3 measured as "the six-wave form loses at four per CU" (see the comment at the kernels below).  With more than one
  * utterance per CU the waves set their issue priority by the frames their utterance has left (prio_by_remaining, the rule of
- * ns_pipe_kernel.hip), and the wave -> role map (SEA_NS6_PERM) puts B0 and S on the two oldest waves: among equal priorities a SIMD
+ * ns_pipe_kernel.hip), and the wave -> role map (kDefaultPerm) puts B0 and S on the two oldest waves: among equal priorities a SIMD
  * issues its oldest wave first.  configs[1]: 1.91-1.95 ms = 420-427 M frames/s (four-wave form 2.08-2.13);
  * profiles/r04_ns_six_wave_dense.txt.
  */
@@ -63,6 +63,14 @@ constexpr int kCirc = kSlots * kSlotLen;
 constexpr int kMirror = 3 * kSlotLen;
 constexpr int kWaves = 6;
 constexpr int kDepth = 7; /* S stores frame i - kDepth */
+constexpr int kSChunks = 10; /* helper_chains: the helper wave's 20 quads are requested in ten chunks (2 x 8 VGPRs in flight) */
+/* issue priority by remaining frames: evaluated every kPrioStep frames, kPrioLevels levels dithered into the four hardware ones
+ * (the rule and its measurements: ns_pipe_kernel.hip) */
+constexpr int kPrioStep = 16;
+constexpr int kPrioLevels = 32;
+/* wave -> role (octal digits, wave 0 rightmost; roles 0 FA, 1 FB, 2 B0, 3 N1, 4 G1, 5 S): B0 and S on the two oldest waves.
+ * NsBatchArgs::perm6 != 0 replaces it (sea_debug_ns6_perm, which accepts permutations of 0..5 only). */
+constexpr int kDefaultPerm = 0014352;
 
 struct __attribute__((aligned(16))) RecA { /* FA -> FB, S: what was pushed at this iteration */
     int valid, tick;      /* stage 0, frame i */
@@ -92,8 +100,8 @@ struct __attribute__((aligned(16))) Pipe6Lds {
     BackLds back[2];                /* scratch of B0 and G1 */
     float ssq[80], sdif[80], sout[80], szero[4]; /* scratch of S */
     float frameEn[kSlots], denSum[kSlots];
-    int vadTodo[2];                 /* SEA_P6_LOG_IN = 3: the ring entry whose log N1 takes at beat i + 1, by i & 1 (-1: none) */
-    float frameEnLog[kSlots];       /* SEA_P6_LIGHT_S: frameEn = 64 + sum of squares (S), frameEnLog = its log-energy (FA, one beat later) */
+    int vadTodo[2];                 /* unused (initialised only), kept for the layout */
+    float frameEnLog[kSlots];       /* LIGHT: frameEn = 64 + sum of squares (S), frameEnLog = its log-energy (FA, one beat later) */
     int fdFlags[kSlots];
     float idctT[SEA_NMEL * 16];
     RecA ra[2];
@@ -130,69 +138,34 @@ __device__ __forceinline__ void load_back_const(NsConst &C, const sea_ns_tables 
     C.eps = t->eps;
 }
 
-template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 = LIGHT /* G1 hands over the DC differences */>
+template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands over the DC differences */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 {
     const int lane = threadIdx.x & 63;
-    /* wave -> role (octal digits, wave 0 rightmost; roles 0 FA, 1 FB, 2 B0, 3 N1, 4 G1, 5 S).  This form is for up to two
-     * utterances per CU.  At four per CU (configs[1], where the four-wave form runs at 2.20 ms) the placement of the roles on
-     * the SIMDs decides: identity 3.19 ms, 0104352 (B0, S, N1, G1, FA, FB) 2.78 ms, the ten even / odd splits in wave order
-     * 2.97-3.26 ms (round 3, tools/build_variant.sh -DSEA_NS6_PERM=...): none reaches the four-wave form. */
-#ifndef SEA_P6_TAPS_RL
-#define SEA_P6_TAPS_RL 1
-#endif
-/* 1 (round 4; the forms for up to two utterances per CU, where the run time is one utterance's chain of frames): the helper
- * wave S was this form's longest role (3397 clk per frame alone, B0 3089, G1 2985, N1 2623, FB 2608, FA 2268): (a) the VAD's
- * log-energy (NoiseSup.c:391) is taken by the first transform wave FA one beat after S left the frame's sum of squares -- FA has
- * ~1000 clk of slack, the value is consumed by B0 two beats later still (SEA_P6_LOG_IN = 3: by N1 instead); (b) G1 hands over the
- * DC filter's input differences instead of the filtered frame (ns_gain1_dif), S's own pass over the frame goes.  S 3397 -> 2836,
- * G1 2985 -> 3134, FA 2268 -> 2694: 256 utterances 1.777 -> 1.664 ms.  NOT in the dense form: at four workgroups per CU the step is
- * a throughput limit and the same change costs 2 % there (1.99 against 1.95 ms). */
-#ifndef SEA_P6_LIGHT_S
-#define SEA_P6_LIGHT_S 1
-#endif
-#ifndef SEA_P6D_LOGMOVE /* the same two changes in the dense form, separately */
-#define SEA_P6D_LOGMOVE 0
-#endif
-#ifndef SEA_P6D_DIFG1
-#define SEA_P6D_DIFG1 0
-#endif
-#ifndef SEA_P6_LOG_IN /* which wave takes the VAD log with LIGHT: 0 FA itself, 3 N1 (FA only leaves the ring index) */
-#define SEA_P6_LOG_IN 0
-#endif
-#ifndef SEA_P6_S_CHUNKS
-#define SEA_P6_S_CHUNKS 10
-#endif
-#ifndef SEA_P6_LRPT
-#define SEA_P6_LRPT 1
-#endif
-#ifndef SEA_P6_PRIO_LEVELS
-#define SEA_P6_PRIO_LEVELS 32
-#endif
-#ifndef SEA_P6_PRIO_STEP
-#define SEA_P6_PRIO_STEP 16
-#endif
-#ifndef SEA_P6_PRIO_ROWBIAS
-#define SEA_P6_PRIO_ROWBIAS 1
-#endif
-#ifndef SEA_NS6_PERM
-#define SEA_NS6_PERM 0014352
-#endif
-    const int role = ((a.perm6 ? a.perm6 : SEA_NS6_PERM) >> (3 * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6))) & 7;
+    /* LIGHT / DIFG1 (the forms for up to two utterances per CU, where the run time is one utterance's chain of frames): the helper
+     * wave S was this form's longest role (3397 clk per frame alone, B0 3089, G1 2985, N1 2623, FB 2608, FA 2268): (LIGHT) the VAD's
+     * log-energy (NoiseSup.c:391) is taken by the first transform wave FA one beat after S left the frame's sum of squares -- FA has
+     * ~1000 clk of slack, the value is consumed by B0 two beats later still; (DIFG1) G1 hands over the DC filter's input differences
+     * instead of the filtered frame (ns_gain1_dif), S's own pass over the frame goes.  S 3397 -> 2836, G1 2985 -> 3134,
+     * FA 2268 -> 2694: 256 utterances 1.777 -> 1.664 ms.  NOT in the dense form: at four workgroups per CU the step is a throughput
+     * limit and the same change costs 2 % there (1.99 against 1.95 ms).
+     * The placement of the roles on the SIMDs decides at four utterances per CU (round 3, before the dense form: identity
+     * 3.19 ms, 0104352 (B0, S, N1, G1, FA, FB) 2.78 ms, the ten even / odd splits in wave order 2.97-3.26 ms). */
+    const int role = ((a.perm6 ? a.perm6 : kDefaultPerm) >> (3 * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6))) & 7;
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
     const long long off = a.offsets[u];
     const long long nfr = a.lengths[u] / SEA_HOP;
     const long long niter = nfr + kDepth;
-    /* issue priority by remaining frames, the rule of the four-wave form (ns_pipe_kernel.hip, SEA_PRIO_LRPT): on whenever the
+    /* issue priority by remaining frames, the rule of the four-wave form (ns_pipe_kernel.hip): on whenever the
      * launch has more utterances than CUs to put them on and an order whose first entry is the longest */
-    const bool lrpt = SEA_P6_LRPT && a.prio_row > 0 && a.order;
+    const bool lrpt = a.prio_row > 0 && a.order;
     const long long longestFr = lrpt ? a.lengths[a.order[0]] / SEA_HOP : 0;
-    const float lrptScale = (float)SEA_P6_PRIO_LEVELS / (float)(longestFr > 0 ? longestFr : 1);
-    const int lrptBias = lrpt ? SEA_P6_PRIO_ROWBIAS * ((int)blockIdx.x / a.prio_row) : 0;
+    const float lrptScale = (float)kPrioLevels / (float)(longestFr > 0 ? longestFr : 1);
+    const int lrptBias = lrpt ? (int)blockIdx.x / a.prio_row : 0; /* equal levels: the hardware prefers the oldest wave */
     auto prio_by_remaining = [&](long long i) {
-        if (SEA_P6_LRPT && lrpt && (i & (SEA_P6_PRIO_STEP - 1)) == 0) {
+        if (lrpt && (i & (kPrioStep - 1)) == 0) {
             const int L = __builtin_amdgcn_readfirstlane((int)((float)(nfr - i) * lrptScale)) + lrptBias;
-            const int pr = (L + (int)((i / SEA_P6_PRIO_STEP) & (SEA_P6_PRIO_LEVELS / 4 - 1))) / (SEA_P6_PRIO_LEVELS / 4);
+            const int pr = (L + (int)((i / kPrioStep) & (kPrioLevels / 4 - 1))) / (kPrioLevels / 4);
             if (pr >= 3) __builtin_amdgcn_s_setprio(3);
             else if (pr == 2) __builtin_amdgcn_s_setprio(2);
             else if (pr == 1) __builtin_amdgcn_s_setprio(1);
@@ -236,12 +209,11 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         for (long long i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            if (LIGHT && SEA_P6_LOG_IN == 0 && vH2) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is tick tH2 + 2's "current frame") */
+            if (LIGHT && vH2) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is tick tH2 + 2's "current frame") */
                 const int e = (tH2 + 2) & (kSlots - 1);
                 const float en = vad_frame_energy(L.frameEn[e]);
                 if (lane == 0) L.frameEnLog[e] = en;
             }
-            if (LIGHT && SEA_P6_LOG_IN == 3 && lane == 0) L.vadTodo[i & 1] = vH2 ? ((tH2 + 2) & (kSlots - 1)) : -1;
             RecA &r = L.ra[i & 1];
             int valid = 0;
             bool actA = false;
@@ -303,15 +275,9 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 const bool actB = (f1 >= 0 && f1 < nfr) && valid1 && t1 >= 5;
                 float *work = L.work[g & 1];
                 if (actA || actB) {
-                    if (SEA_PSD_REGS) { /* the last level stays in registers and feeds both PSDs (ns_core.h, psd_from_last_level) */
-                        float o[8];
-                        rfft256_dual_hi_keep_last<false>(work, fft, o);
-                        psd_from_last_level(o, fft, L.p0[f0 & 1].psd, actA, L.p1[(f1 < 0 ? 0 : f1) & 1].psd, actB, lane);
-                    } else {
-                        rfft256_dual_hi<false>(work, fft);
-                        if (actA) psd_from_fft2(work, L.p0[f0 & 1].psd, fft, lane);
-                        if (actB) psd_from_fft2(work + 256, L.p1[f1 & 1].psd, fft, lane);
-                    }
+                    float o[8]; /* the last level stays in registers and feeds both PSDs (ns_core.h, psd_from_last_level) */
+                    rfft256_dual_hi_keep_last<false>(work, fft, o);
+                    psd_from_last_level(o, fft, L.p0[f0 & 1].psd, actA, L.p1[(f1 < 0 ? 0 : f1) & 1].psd, actB, lane);
                     wave_sync();
                 }
                 if (lane == 0) {
@@ -347,23 +313,15 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 RecDen &o = L.rd[f & 1];
                 const int valid = r.valid, t = r.tick;
                 if (valid && t >= 3) {
-                    float *tmp = L.back[0].sq;
                     int bits = 0;
-                    /* SEA_P6_TAPS_RL: the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
+                    /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
                      * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
                     float y01[2] = {0.0f, 0.0f};
-                    ns_back<0, true, FD, false, true>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, tmp, lane,
+                    ns_back<0, true, FD, true>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, nullptr, lane,
                                          (LIGHT ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)], o.den, L.idctT, &fd, &bits, nullptr,
-                                         SEA_P6_TAPS_RL ? y01 : nullptr);
+                                         y01);
                     if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
-                    if (lane < 40) {
-                        if (SEA_P6_TAPS_RL) {
-                            slot_store(L.circ[1], t, lane, y01[0], y01[1]);
-                        } else {
-                            const float2 v = *reinterpret_cast<const float2 *>(tmp + 2 * lane);
-                            slot_store(L.circ[1], t, lane, v.x, v.y);
-                        }
-                    }
+                    if (lane < 40) slot_store(L.circ[1], t, lane, y01[0], y01[1]);
                 }
                 if (lane == 0) {
                     o.valid = valid;
@@ -383,13 +341,6 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         for (long long i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            if (LIGHT && SEA_P6_LOG_IN == 3 && i > 0) { /* the VAD log of the entry FA named one beat ago; B0 reads it one beat from now */
-                const int e = L.vadTodo[(i - 1) & 1];
-                if (e >= 0) {
-                    const float en = vad_frame_energy(L.frameEn[e]);
-                    if (lane == 0) L.frameEnLog[e] = en;
-                }
-            }
             const long long f = i - 5;
             if (f >= 0 && f < nfr) {
                 const RecPsd &r = L.p1[f & 1];
@@ -496,15 +447,14 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             if (doVad || doDen || produced) {
                 wave_sync();
                 float vadSum, denTotal, y = dcY;
-                helper_chains<SEA_P6_S_CHUNKS>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane);
+                helper_chains<kSChunks>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane);
                 if (doVad) {
-                    const float en = LIGHT ? vadSum : vad_frame_energy(vadSum); /* LIGHT_S: FA takes the log one beat later */
+                    const float en = LIGHT ? vadSum : vad_frame_energy(vadSum); /* LIGHT: FA takes the log one beat later */
                     if (lane == 0) L.frameEn[(tp + 2) & (kSlots - 1)] = en;
                 }
                 if (doDen && lane == 0) L.denSum[td & (kSlots - 1)] = denTotal;
                 if (produced) {
-                    if (SEA_P6_TAPS_RL) vOut = dc_verify_take(difS, L.sout, dcY, y, lane); /* check + output in one batch of reads */
-                    else dc_verify(difS, L.sout, dcY, y, lane);
+                    vOut = dc_verify_take(difS, L.sout, dcY, y, lane); /* check + output in one batch of reads */
                     dcY = y;
                     if (firstOut < 0) firstOut = (int)fo;
                 }
@@ -513,9 +463,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 if (lane < 40) {
                     uint32_t packed = 0u;
                     if (produced) {
-                        const float2 v = SEA_P6_TAPS_RL ? vOut : *reinterpret_cast<const float2 *>(&L.sout[2 * lane]);
-                        packed = (uint32_t)cast_i16(v.x) | ((uint32_t)cast_i16(v.y) << 16);
-                        if (outf) *reinterpret_cast<float2 *>(outf + fo * SEA_HOP + 2 * lane) = v;
+                        packed = (uint32_t)cast_i16(vOut.x) | ((uint32_t)cast_i16(vOut.y) << 16);
+                        if (outf) *reinterpret_cast<float2 *>(outf + fo * SEA_HOP + 2 * lane) = vOut;
                     }
                     out32[fo * 40 + lane] = packed;
                 }
@@ -534,18 +483,14 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 
 } // namespace p6
 
-#ifndef SEA_NS_BODY_ONLY
 /* launched for at most two utterances per CU (capi.hip::ns_pick_form): twelve waves per CU, three per SIMD, so the
  * register allocation could use up to 168 VGPRs.  The plain form stays compiled for 80 (measured: 1644 against 1679 ns
  * per frame with the looser bound, which only changes the schedule); the _fd form takes the looser bound, which
  * removes its 7 spilled registers (91 VGPRs). */
-#ifndef SEA_NS6_BLOCKS
-#define SEA_NS6_BLOCKS 6
-#endif
-__global__ __launch_bounds__(384, SEA_NS6_BLOCKS) void ns_denoise_pipe6_kernel(NsBatchArgs a)
+__global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
-    p6::ns_pipe6_body<false, SEA_P6_LIGHT_S != 0>(a, L);
+    p6::ns_pipe6_body<false, true, true>(a, L);
 }
 /* The same body compiled for SEVEN waves per SIMD (72 VGPRs, 8 spilled): the form for three or four utterances per CU
  * (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
@@ -567,7 +512,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, SEA_P6D_LOGMOVE != 0, SEA_P6D_DIFG1 != 0>(a, L);
+    p6::ns_pipe6_body<false, false, false>(a, L);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
@@ -575,13 +520,12 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
 __global__ __launch_bounds__(384, 2) void ns_denoise_pipe6_fd_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
-    p6::ns_pipe6_body<true, SEA_P6_LIGHT_S != 0>(a, L);
+    p6::ns_pipe6_body<true, true, true>(a, L);
 }
-#endif
 
 } // namespace sea
 
-#if defined(SEA_NS6_TIMING) && !defined(SEA_NS_BODY_ONLY)
+#ifdef SEA_NS6_TIMING
 extern "C" int sea_debug_ns6_timing(unsigned long long *out16)
 {
     return (int)hipMemcpyFromSymbol(out16, HIP_SYMBOL(sea::p6::g_ns6_timing), 16 * sizeof(unsigned long long));

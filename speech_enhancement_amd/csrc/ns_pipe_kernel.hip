@@ -38,95 +38,39 @@ constexpr int kCirc = kSlots * kSlotLen;   /* 640 */
 constexpr int kMirror = 3 * kSlotLen;      /* slots 0..2 repeated behind the end */
 constexpr int kPipeWaves = 4;
 
-/* timing-only diagnostic: bit set = that piece of work is done (default all) */
-/* 1: the second-stage FIR runs in the helper wave S instead of B1 (shorter lone-workgroup frame period,
- * slightly more instructions) */
-#ifndef SEA_FIR_IN_S
-#define SEA_FIR_IN_S 1
-#endif
-/* 1 (experiment, off): the second-stage mel IDCT (DoMelIDCT: nine in-order sums of 25 terms) SPLIT between B1, the
- * longest role, and the transform wave F, which has ~1000 clk of slack per frame: B1 adds the first SEA_IDCT_SPLIT
- * terms, F the rest one beat later, then windows and mirrors the taps (one more beat of pipeline depth).  Bit-identical
- * and measured: the role timers of the top-priority workgroup balance (whole IDCT in B1: F 3140 / B1 4100 clk per frame;
- * 17 terms in B1: F 3650 / B1 3825, frame period 4310 -> 4060), but the bench step gets SLOWER for every split
- * (2.27-2.35 ms against 2.19-2.23): the extra beat and LDS traffic cost the lower launch rows more than the top row
- * gains (profiles/r03_ns_idct_split_experiment.txt). */
-#ifndef SEA_IDCT_IN_F
-#define SEA_IDCT_IN_F 0
-#endif
-#ifndef SEA_IDCT_SPLIT
-#define SEA_IDCT_SPLIT 13
-#endif
-/* > 0: the same split with the TAIL in the helper wave S, which applies the taps anyway one beat after B1 (no extra
- * beat, no extra record): B1 adds the first 25 - SEA_IDCT_TAIL_S terms, S the last SEA_IDCT_TAIL_S, windows and mirrors */
-#ifndef SEA_IDCT_TAIL_S
-#define SEA_IDCT_TAIL_S 8 /* round 4 (LDS-free taps, LRPT priorities): 4: 2.14 ms, 8: 2.11, 12: 2.11, 16: 2.13; round 3, measured on configs[1], alternating A/B (tools/ns_ab.sh): 0: 2.19-2.24 ms, 4: 2.14-2.19, 7: 2.16-2.19, 10: 2.17-2.18 */
-#endif
-/* 1 (experiment, off): the int16 cast and the output store (ParmInterface.c:266) of a frame run in the transform wave F one
- * beat after the helper wave finished it (F has ~900 clk of slack per frame, S none): double-buffered output frame in
- * LDS.  Bit-identical; measured on configs[1], alternating A/B: 2.29-2.31 ms against 2.20-2.22 (also with 6 or 8 IDCT
- * terms moved to S on top): the extra beat costs the lower launch rows more than the top row gains, as with the
- * IDCT split in F. */
-#ifndef SEA_STORE_IN_F
-#define SEA_STORE_IN_F 0
-#endif
-constexpr bool kIdctSplit = (SEA_IDCT_IN_F || SEA_IDCT_TAIL_S > 0) && SEA_FIR_IN_S;
-constexpr int kIdctHead = SEA_IDCT_IN_F ? SEA_IDCT_SPLIT : 25 - SEA_IDCT_TAIL_S;
-constexpr int kLagS = (SEA_IDCT_IN_F && SEA_FIR_IN_S) ? 5 : 4; /* beats between a frame's intake and its output store */
-constexpr int kRec34 = (SEA_IDCT_IN_F && SEA_FIR_IN_S) ? 4 : 2;    /* with the split: B1 writes at beat i, F at i + 1, S reads at i + 2 */
-/* 1 (four-wave forms with the address tables in VGPRs): the filter taps reach the 17-tap filters as scalar operands through
- * v_readlane and the filters' outputs stay in registers (B0: straight into the stage-1 buffer; S: straight into the DC filter's
- * differences), the helper wave fetches the operands of its exactness check and of the output store in one batch -- two LDS
- * round trips (~200 clk each) less on B0's chain, two less on S's */
-#ifndef SEA_TAPS_RL
-#define SEA_TAPS_RL 1
-#endif
-/* 1 (four-wave forms with the address tables in VGPRs): the two BACK waves keep their column of the 9 x 25 IDCT basis in
- * registers (the kernel's register budget is set by the transform wave's address tables, these roles have room) instead
- * of 25 + 21 LDS reads of constants per frame */
-#ifndef SEA_BASIS_REGS
-#define SEA_BASIS_REGS 1
-#endif
-/* 1: issue priority by REMAINING frames instead of by launch row (longest-remaining-processing-time first, the makespan
- * rule).  Every SEA_PRIO_STEP frames each wave of a workgroup sets s_setprio from
- *     L = SEA_PRIO_LEVELS * (frames its utterance has left) / (frames of the batch's longest utterance) + SEA_PRIO_ROWBIAS * launch row
- * dithered over SEA_PRIO_LEVELS / 4 consecutive evaluations into the four hardware levels: level (L + d) / (LEVELS / 4) with
- * d = 0 .. LEVELS / 4 - 1 in turn.  An utterance keeps the top level only while more of it is left than of its neighbours, so the
+constexpr int kPipeDepth = 4; /* beats between a frame's intake and its output store */
+/* The second-stage mel IDCT (DoMelIDCT: nine in-order sums of 25 terms) is split between B1, the longest role, and the helper
+ * wave S: B1 adds the first kIdctHead terms; S, which applies the taps anyway one beat after B1 (the second-stage FIR runs in S:
+ * shorter lone-workgroup frame period, slightly more instructions), adds the last eight, windows and mirrors.  No extra beat, no
+ * extra record.  (Giving the tail, or the int16 cast and the output store, to the transform wave F balanced the role timers of
+ * the top-priority workgroup but made the bench step slower: the extra beat costs the lower launch rows more than the top row
+ * gains, profiles/r03_ns_idct_split_experiment.txt.) */
+constexpr int kIdctHead = 17;
+/* In the four-wave forms with the address tables in VGPRs (!ADDR_LDS):
+ *  - the filter taps reach the 17-tap filters as scalar operands through v_readlane and the filters' outputs stay in registers
+ *    (B0: straight into the stage-1 buffer; S: straight into the DC filter's differences), and the helper wave fetches the
+ *    operands of its exactness check and of the output store in one batch -- two LDS round trips (~200 clk each) less on B0's
+ *    chain, two less on S's;
+ *  - the two BACK waves keep their column of the 9 x 25 IDCT basis in registers (the kernel's register budget is set by the
+ *    transform wave's address tables, these roles have room) instead of 25 + 21 LDS reads of constants per frame.
+ * The table-in-LDS form gains nothing from either (464 M frames/s on the configs[4] shard either way). */
+/* Issue priority by REMAINING frames instead of by launch row (longest-remaining-processing-time first, the makespan rule).
+ * Every kPrioStep frames each wave of a workgroup sets s_setprio from
+ *     L = kPrioLevels * (frames its utterance has left) / (frames of the batch's longest utterance) + launch row
+ * dithered over kPrioLevels / 4 consecutive evaluations into the four hardware levels: level (L + d) / (kPrioLevels / 4) with
+ * d = 0 .. kPrioLevels / 4 - 1 in turn.  An utterance keeps the top level only while more of it is left than of its neighbours, so the
  * utterances of a CU converge on a common finishing time whatever their lengths.  (The static rows gave the longest utterance of
  * a CU its lone frame period from start to end and starved the third row: rows 0 / 1 finished at 2.09 / 2.15 ms, row 2 at 2.39,
  * tools/ns_finish_order.py; 2.24 -> 2.15 ms per configs[1] step, profiles/r04_ns_priority_and_lone_period.txt.)  The launch row
  * enters because among equal levels the hardware prefers the oldest wave.  Whole utterances in the four-wave form only. */
-#ifndef SEA_PRIO_LRPT
-#define SEA_PRIO_LRPT 1
-#endif
-#ifndef SEA_PRIO_STEP
-#define SEA_PRIO_STEP 16
-#endif
-#ifndef SEA_PRIO_LEVELS
-#define SEA_PRIO_LEVELS 32 /* 4 (no dither to speak of): 2.21 ms; 16: 2.17; 32: 2.15; 64 with step 8: 2.16 */
-#endif
-#ifndef SEA_PRIO_ROWBIAS
-#define SEA_PRIO_ROWBIAS 1
-#endif
-#ifndef SEA_PRIO_DITHER
-#define SEA_PRIO_DITHER 1
-#endif
-/* waves per SIMD the register allocation must leave room for (= workgroups per CU of this 4-wave kernel) */
-#ifndef SEA_NS_MIN_WAVES
-#define SEA_NS_MIN_WAVES 4
-#endif
+constexpr int kPrioStep = 16;
+constexpr int kPrioLevels = 32;
+/* waves per SIMD the register allocation must leave room for (= workgroups per CU): the four-wave form, and its table-in-LDS form */
+constexpr int kMinWaves = 4;
+constexpr int kBigWaves = 6;
+/* timing-only diagnostic (tools/pmc_roles.sh, tools/ns_role_periods.sh): bit set = that piece of work is done (default all) */
 #ifndef SEA_ROLE_MASK
 #define SEA_ROLE_MASK 127
-#endif
-/* timing-only ablations of the helper wave (results wrong by construction): 1 no second-stage FIR, 2 no VAD log,
- * 4 no output store, 8 no chains */
-#ifndef SEA_ABL_S
-#define SEA_ABL_S 0
-#endif
-/* timing-only ablation (results wrong by construction): the frame barrier on every second beat only -- no gain on configs[1]
- * or on the configs[4] shard: synchronising less often than once per frame is not what this pipeline lacks */
-#ifndef SEA_ABL_HALFSYNC
-#define SEA_ABL_HALFSYNC 0
 #endif
 
 
@@ -189,11 +133,11 @@ struct __attribute__((aligned(16))) RecFd { /* S -> F, same variant: the measure
     float mean, var, tempEn, m1, m2, m3;
     int nb16, vadns, tick, pad0, pad1, pad2; /* tick 0: the first stage did not run */
 };
-struct __attribute__((aligned(16))) Rec34 { /* B1 -> F -> S */
-    float mel[kIdctSplit ? 40 : 4]; /* split IDCT: [k..24] second-stage mel gains (gain factor applied) whose IDCT terms F still has to
-                    * add, [28..36] B1's partial sums of rows 0..8 (ns_idct_head / ns_idct_tail) */
-    float fir[20]; /* SEA_FIR_IN_S: the 17 taps of the second-stage filter, S applies them */
-    float out[80]; /* otherwise: second-stage filter output before the DC-offset filter */
+struct __attribute__((aligned(16))) Rec34 { /* B1 -> S */
+    float mel[40]; /* split IDCT: [k..24] second-stage mel gains (gain factor applied) whose IDCT terms S still has to
+                    * add, [28..36] B1's partial sums of rows 0..8 (ns_idct_head / ns_idct_tail_rl) */
+    float fir[20]; /* table-in-LDS form: the 17 taps of the second-stage filter, finished and applied by S */
+    float out[80]; /* unused, kept for the layout */
     int produced, tick, pad1, pad2;
 };
 
@@ -203,8 +147,8 @@ struct __attribute__((aligned(16))) PipeLds {
     float work[512];                /* the two FFT frames of F */
     uint4 fftAddr[ADDR_LDS ? SEA_FFT_LSTAGES * 64 : 1]; /* F's butterfly operand addresses (Fft2Regs) */
     BackLds back[2];                /* scratch of B0 and B1 */
-    float ssq[80], sdif[80], sout[SEA_STORE_IN_F ? 2 : 1][80]; /* scratch of S (sout: the DC-filtered output frame) */
-    int outProd[2];                 /* SEA_STORE_IN_F: frame fo & 1 holds an output (1) / is a latency frame to be zero-filled (0) */
+    float ssq[80], sdif[80], sout[1][80]; /* scratch of S (sout: the DC-filtered output frame) */
+    int outProd[2];                 /* unused, kept for the layout */
     float szero[4];                 /* zeros: what the shorter chain reads past its end */
     float sfir[80];                 /* second-stage filter output before the DC-offset filter */
     float frameEn[kSlots];          /* 64 + in-order sum of squares of the VAD's frame for tick t at [t & 7] */
@@ -214,7 +158,7 @@ struct __attribute__((aligned(16))) PipeLds {
     RecPsd r01[2];
     Rec12 r12[2];
     RecPsd r23[2];
-    Rec34 r34[kRec34];
+    Rec34 r34[2];
     /* frame-dropping VAD variant only, BEHIND everything else (the other forms keep their layout): what B0 leaves of frame f
      * (by parity) for the speech measures (ns_core.h, kFdRecFloats), and their sums on the way from S to F */
     float fdRec[2][FD ? kFdRecFloats : 4];
@@ -268,10 +212,10 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     const int lane = threadIdx.x & 63;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
-    /* Issue priority.  Whole utterances in the four-wave form: by remaining frames (SEA_PRIO_LRPT above, prio_by_remaining below).
+    /* Issue priority.  Whole utterances in the four-wave form: by remaining frames (kPrioStep above, prio_by_remaining below).
      * Otherwise (time slices, which hold the same frame range of every utterance) by launch row: the launch order puts the longest
      * utterances first, in rows of one workgroup per CU; row 0 gets s_setprio 3, row 1 -> 2, row 2 -> 1.  prio_row = 0: off. */
-    constexpr bool kLrptForm = SEA_PRIO_LRPT && !ADDR_LDS && !SLICES; /* whole utterances in the four-wave form */
+    constexpr bool kLrptForm = !ADDR_LDS && !SLICES; /* whole utterances in the four-wave form */
     const bool lrpt = kLrptForm && a.prio_row > 0 && a.order && !a.state;
     if (a.prio_row > 0 && !lrpt) {
         const int row = a.prio_base + (int)blockIdx.x / a.prio_row;
@@ -283,20 +227,20 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     const long long nfr = a.lengths[u] / SEA_HOP;
     /* the batch's longest utterance is block 0's (the launch order is longest first; any other order only makes the rule less sharp) */
     const long long longestFr = lrpt ? a.lengths[a.order[0]] / SEA_HOP : 0;
-    const float lrptScale = (float)SEA_PRIO_LEVELS / (float)(longestFr > 0 ? longestFr : 1);
-    const int lrptBias = lrpt ? SEA_PRIO_ROWBIAS * ((int)blockIdx.x / a.prio_row) : 0; /* equal levels: the hardware prefers the oldest wave */
+    const float lrptScale = (float)kPrioLevels / (float)(longestFr > 0 ? longestFr : 1);
+    const int lrptBias = lrpt ? (int)blockIdx.x / a.prio_row : 0; /* equal levels: the hardware prefers the oldest wave */
     auto prio_by_remaining = [&](long long i) {
-        if (kLrptForm && lrpt && (i & (SEA_PRIO_STEP - 1)) == 0) {
+        if (kLrptForm && lrpt && (i & (kPrioStep - 1)) == 0) {
             const int L = __builtin_amdgcn_readfirstlane((int)((float)(nfr - i) * lrptScale)) + lrptBias;
-            const int d = SEA_PRIO_DITHER ? (int)((i / SEA_PRIO_STEP) & (SEA_PRIO_LEVELS / 4 - 1)) : 0;
-            const int pr = (L + d) / (SEA_PRIO_LEVELS / 4);
+            const int d = (int)((i / kPrioStep) & (kPrioLevels / 4 - 1));
+            const int pr = (L + d) / (kPrioLevels / 4);
             if (pr >= 3) __builtin_amdgcn_s_setprio(3);
             else if (pr == 2) __builtin_amdgcn_s_setprio(2);
             else if (pr == 1) __builtin_amdgcn_s_setprio(1);
             else __builtin_amdgcn_s_setprio(0);
         }
     };
-    const long long niter = nfr + kLagS + (SEA_STORE_IN_F ? 1 : 0);
+    const long long niter = nfr + kPipeDepth;
 
     /* time slices (NsBatchArgs::state): the recursion of utterance u between two launches */
     float *const blob = (SLICES && !FD && a.state) ? a.state + (size_t)u * kNsPipeStateFloats : nullptr;
@@ -322,7 +266,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         L.r12[threadIdx.x].den[65] = L.r12[threadIdx.x].den[66] = L.r12[threadIdx.x].den[67] = 0.0f; /* read as zeros by S */
         L.r23[threadIdx.x].valid = 0;
     }
-    if (threadIdx.x < kRec34) L.r34[threadIdx.x].produced = 0;
+    if (threadIdx.x < 2) L.r34[threadIdx.x].produced = 0;
     if (FD && threadIdx.x < 2) {
         L.rfd[threadIdx.x].tick = 0;
         L.fdRec[threadIdx.x][153] = L.fdRec[threadIdx.x][154] = L.fdRec[threadIdx.x][155] = 0.0f; /* the mel chain's zeros */
@@ -342,7 +286,6 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         float win8[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) win8[k] = a.tables->win8[k][lane];
-        const float irWin = a.tables->irWin[lane];
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
         uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
         int tick = resume ? __float_as_int(blob[kBlobScal + 0]) : 0; /* frames seen since (and including) the first non-zero one */
@@ -378,29 +321,10 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
 #ifdef SEA_NS_TIMING
         const unsigned long long clk0_ = clock64(), wall0_ = wall_clock64();
 #endif
-        uint32_t *out32F = reinterpret_cast<uint32_t *>(a.out + off);
-        float *outfF = a.out_f32 ? a.out_f32 + off : nullptr;
         for (long long i = 0; i < niter; ++i) {
             NS_T_BEGIN;
             prio_by_remaining(i);
             NS_T_CK_START;
-            if (SEA_STORE_IN_F) { /* cast + store of the frame the helper wave finished one beat ago */
-                const long long fs = i - kLagS - 1;
-                if (fs >= 0 && fs < nfr) {
-                    int ln = lane;
-                    if (ADDR_LDS) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-                    const int prod = L.outProd[fs & 1];
-                    if (ln < 40) {
-                        uint32_t packed = 0u;
-                        if (prod) {
-                            const float2 v = *reinterpret_cast<const float2 *>(&L.sout[fs & 1][2 * ln]);
-                            packed = (uint32_t)cast_i16(v.x) | ((uint32_t)cast_i16(v.y) << 16);
-                            if (outfF) *reinterpret_cast<float2 *>(outfF + fs * SEA_HOP + 2 * ln) = v;
-                        }
-                        out32F[fs * 40 + ln] = packed;
-                    }
-                }
-            }
             /* stage 0, frame i */
             bool actA = false;
             auto &rA = L.r01[i & 1];
@@ -431,13 +355,6 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                               L.work, fft, win8, lane);
             }
             NS_T_CK(6);
-            if (SEA_IDCT_IN_F && SEA_FIR_IN_S) { /* the taps of the frame B1 finished one beat ago */
-                const long long fg = i - 4;
-                if (fg >= 0 && fg < nfr) {
-                    Rec34 &g = L.r34[fg & (kRec34 - 1)];
-                    if (g.produced) ns_idct_tail<SEA_IDCT_SPLIT>(g.mel, L.idctT, irWin, g.fir, lane);
-                }
-            }
             if (FD) { /* the scalar logic of the speech measures of the frame whose sums S finished one beat ago */
                 const long long ff = i - 3;
                 if (ff >= 0 && ff < nfr) {
@@ -455,7 +372,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             vCur = 0;
             if (i + 1 < nfr) intake(i + 1);
             NS_T_MID;
-            if (!SEA_ABL_HALFSYNC || (i & 1)) block_sync();
+            block_sync();
             NS_T_END;
         }
         if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset;
@@ -479,8 +396,8 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     } else if (role == 1) {
         /* ---- B0: BACK of stage 0; its 80 outputs enter the stage-1 buffer ---- */
         NsConst C;
-        constexpr bool kBregs = SEA_BASIS_REGS && !ADDR_LDS && SEA_TAPS_RL;
-        load_back_const<kBregs>(C, a.tables, lane);
+        constexpr bool kRegs = !ADDR_LDS; /* taps as scalar operands, filter outputs and the IDCT basis column in registers */
+        load_back_const<kRegs>(C, a.tables, lane);
         NsRegs s;
         regs_init(s, C.eps);
         NsFd fd;
@@ -507,11 +424,10 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                      * here, by its consumer: this wave has ~1000 clk of slack per frame, the helper wave none */
                     /* FD: the speech measures' inputs go into o.fd; S sums them in free lanes of its chain one beat later, F
                      * runs their scalar logic the beat after (this wave has no slack left for ~1300 clk of them) */
-                    constexpr bool kRegs = SEA_TAPS_RL && !ADDR_LDS; /* (the table-in-LDS form gains nothing from any of it: 464 M frames/s on the configs[4] shard either way) */
                     float y01[2] = {0.0f, 0.0f};
-                    ns_back<0, true, FD, false, !ADDR_LDS>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, tmp, lane,
+                    ns_back<0, true, FD, kRegs>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, tmp, lane,
                                          vad_frame_energy(L.frameEn[t & (kSlots - 1)]), o.den, L.idctT, &fd, &bits,
-                                         FD ? L.fdRec[f & 1] : nullptr, kRegs ? y01 : nullptr, kBregs ? C.idct : nullptr);
+                                         FD ? L.fdRec[f & 1] : nullptr, kRegs ? y01 : nullptr, kRegs ? C.idct : nullptr);
                     if (lane < 40) {
                         if (kRegs) {
                             slot_store(L.circ[1], t, lane, y01[0], y01[1]);
@@ -527,7 +443,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                 }
             }
             NS_T_MID;
-            if (!SEA_ABL_HALFSYNC || (i & 1)) block_sync();
+            block_sync();
             NS_T_END;
         }
         if (blob) {
@@ -543,8 +459,8 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     } else if (role == 2) {
         /* ---- B1: BACK of stage 1 ---- */
         NsConst C;
-        constexpr bool kBregs = SEA_BASIS_REGS && !ADDR_LDS && kIdctSplit;
-        load_back_const<kBregs>(C, a.tables, lane);
+        constexpr bool kRegs = !ADDR_LDS; /* in-order sums through lane reads, the IDCT basis column in registers */
+        load_back_const<kRegs>(C, a.tables, lane);
         NsRegs s;
         regs_init(s, C.eps);
         if (resume) {
@@ -559,7 +475,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             const long long f = i - 3;
             if (f >= 0 && f < nfr) {
                 const auto &r = L.r23[f & 1];
-                Rec34 &o = L.r34[f & (kRec34 - 1)];
+                Rec34 &o = L.r34[f & 1];
                 const int valid = r.valid, t = r.tick;
                 int produced = 0;
                 if ((SEA_ROLE_MASK & 8) && valid && t >= 5) {
@@ -567,10 +483,9 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                     s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
                     s.denEn1 = L.denSum[(t - 1) & (kSlots - 1)];
                     s.denEn2 = L.denSum[t & (kSlots - 1)];
-                    ns_back<1, true, false, SEA_FIR_IN_S != 0, !ADDR_LDS, kIdctSplit ? kIdctHead : -1>(
-                        r.psd, L.circ[1] + window_base(t), L.back[1], s, C,
-                        SEA_FIR_IN_S ? (kIdctSplit ? o.mel : o.fir) : o.out, lane, 0.0f, nullptr, L.idctT, nullptr, nullptr, nullptr,
-                        nullptr, kBregs ? C.idct : nullptr);
+                    ns_back<1, true, false, kRegs, kIdctHead>(
+                        r.psd, L.circ[1] + window_base(t), L.back[1], s, C, o.mel, lane, 0.0f, nullptr, L.idctT, nullptr, nullptr, nullptr,
+                        nullptr, kRegs ? C.idct : nullptr);
                     produced = 1;
                 }
                 if (lane == 0) {
@@ -579,7 +494,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                 }
             }
             NS_T_MID;
-            if (!SEA_ABL_HALFSYNC || (i & 1)) block_sync();
+            block_sync();
             NS_T_END;
         }
         if (blob) {
@@ -597,7 +512,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         float *outf = a.out_f32 ? a.out_f32 + off : nullptr;
         float dcX = resume ? blob[kBlobScal + 11] : 0.0f, dcY = resume ? blob[kBlobScal + 12] : 0.0f; /* prevSamples, NoiseSup.c:908-909 */
         int firstOut = resume ? __float_as_int(blob[kBlobScal + 13]) : -1;
-        const float irWinS = (SEA_IDCT_TAIL_S > 0) ? a.tables->irWin[lane] : 0.0f;
+        const float irWinS = a.tables->irWin[lane];
         NS_T_CK_DECL;
         for (long long i = 0; i < niter; ++i) {
             NS_T_BEGIN;
@@ -610,7 +525,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
              *     the frame B1 finished at i-1.  etsi_denoise copies zeros until the first NoiseSup
              *     output (AdvFrontEnd.c:186-190).
              * The three serial chains are independent of each other and run interleaved. */
-            const long long fp = i - 1, fd = i - 2, fo = i - kLagS;
+            const long long fp = i - 1, fd = i - 2, fo = i - kPipeDepth;
             bool doVad = false, doDen = false, produced = false;
             int tp = 0, td = 0;
             const float *denSrc = L.r12[0].den;
@@ -629,10 +544,10 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                 fdSrc = L.fdRec[fd & 1];
             }
             const bool haveOut = fo >= 0 && fo < nfr;
-            float *soutS = L.sout[SEA_STORE_IN_F ? (fo & 1) : 0];
-            constexpr bool kTake = SEA_TAPS_RL && !ADDR_LDS && !SEA_STORE_IN_F; /* dc_verify_take: check + output in one batch */
+            float *soutS = L.sout[0];
+            constexpr bool kRegs = !ADDR_LDS; /* taps as scalar operands; dc_verify_take: check + output in one batch */
             float2 vOut = make_float2(0.0f, 0.0f);
-            if (haveOut) produced = (SEA_ROLE_MASK & 64) && L.r34[fo & (kRec34 - 1)].produced != 0;
+            if (haveOut) produced = (SEA_ROLE_MASK & 64) && L.r34[fo & 1].produced != 0;
             /* everything the chains need goes into LDS in one batch: the squares of the VAD frame and the DC filter's
              * input differences, straight from the second-stage FIR's registers (stage-1 17-tap FIR, NoiseSup.c:324-340) */
             {
@@ -643,41 +558,28 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                     if (lane < 16) yv = frame[64 + lane];
                 }
                 if (produced) {
-                    Rec34 &r = L.r34[fo & (kRec34 - 1)];
-                    constexpr bool kTapsRl = SEA_TAPS_RL && !ADDR_LDS && SEA_IDCT_TAIL_S > 0 && !SEA_IDCT_IN_F && SEA_FIR_IN_S;
-                    if (!kTapsRl && SEA_IDCT_TAIL_S > 0 && !SEA_IDCT_IN_F && SEA_FIR_IN_S) /* finish the taps B1 started */
-                        ns_idct_tail<kIdctHead>(r.mel, L.idctT, irWinS, r.fir, lane);
-                    if (SEA_ABL_S & 1) {
-                        d0 = d1 = dcX;
-                    } else if (kTapsRl) { /* the taps B1 started, finished in lanes 0..8 and read as scalars; no trip through LDS */
+                    Rec34 &r = L.r34[fo & 1];
+                    if (kRegs) { /* the taps B1 started, finished in lanes 0..8 and read as scalars; no trip through LDS */
                         dcX = ns_fir_dif_rl(fir_taps_rl(ns_idct_tail_rl<kIdctHead>(r.mel, L.idctT, irWinS, lane)),
                                             L.circ[1] + window_base(r.tick), lane, dcX, d0, d1);
-                    } else if (SEA_FIR_IN_S) {
+                    } else { /* finish the taps B1 started */
+                        ns_idct_tail<kIdctHead>(r.mel, L.idctT, irWinS, r.fir, lane);
                         dcX = ns_fir_dif(r.fir, L.circ[1] + window_base(r.tick), lane, dcX, d0, d1);
-                    } else {
-                        const float *y2 = r.out;
-                        const float xm1 = (lane == 0) ? dcX : y2[lane - 1];
-                        L.sdif[lane] = y2[lane] - xm1;
-                        if (lane < 16) L.sdif[64 + lane] = y2[64 + lane] - y2[63 + lane];
-                        dcX = y2[79];
                     }
                 }
                 if (doVad) {
                     L.ssq[lane] = x * x;
                     if (lane < 16) L.ssq[64 + lane] = yv * yv;
                 }
-                if (produced && SEA_FIR_IN_S && lane < 40) *reinterpret_cast<float2 *>(&L.sdif[2 * lane]) = make_float2(d0, d1);
+                if (produced && lane < 40) *reinterpret_cast<float2 *>(&L.sdif[2 * lane]) = make_float2(d0, d1);
             }
             NS_T_CK(0);
             if (FD && fd >= 0 && fd < nfr && !doDen && lane == 0) L.rfd[fd & 1].tick = 0;
             if (doVad || doDen || produced) {
                 wave_sync();
                 float vadSum, denTotal, y = dcY;
-                if (SEA_ABL_S & 8) {
-                    vadSum = L.ssq[3] + 64.0f, denTotal = denSrc[5], y = L.sdif[7];
-                } else
-                    helper_chains<ADDR_LDS ? 10 : 4, FD>(L.ssq, denSrc, L.sdif, soutS, L.szero, vadSum, denTotal, y, lane, nullptr,
-                                                         FD ? fdSrc : nullptr, FD ? fdSums : nullptr);
+                helper_chains<ADDR_LDS ? 10 : 4, FD>(L.ssq, denSrc, L.sdif, soutS, L.szero, vadSum, denTotal, y, lane, nullptr,
+                                                     FD ? fdSrc : nullptr, FD ? fdSums : nullptr);
                 NS_T_CK(1);
                 if (doVad && lane == 0) L.frameEn[(tp + 2) & (kSlots - 1)] = vadSum; /* 64 + sum of squares; B0 takes the log */
                 NS_T_CK(2);
@@ -697,36 +599,32 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                 if (produced) {
                     /* (checking the recurrence's exactness condition on the sixteen recomputing lanes' registers instead
                      * was measured slower: five checks in a row per lane against two per lane here) */
-                    if (kTake) vOut = dc_verify_take(L.sdif, soutS, dcY, y, lane);
+                    if (kRegs) vOut = dc_verify_take(L.sdif, soutS, dcY, y, lane);
                     else dc_verify(L.sdif, soutS, dcY, y, lane);
                     dcY = y;
                     if (firstOut < 0) firstOut = (int)fo + (blob ? a.frame_base : 0);
                 }
                 NS_T_CK(3);
             }
-            if (haveOut && SEA_STORE_IN_F) {
-                if (lane == 0) L.outProd[fo & 1] = produced ? 1 : 0;
-                if (FD && produced && lane == 0 && a.flags_out)
-                    a.flags_out[off / 8 + 10 * fo] = (unsigned char)L.fdFlags[L.r34[fo & (kRec34 - 1)].tick & (kSlots - 1)];
-            } else if (haveOut) {
+            if (haveOut) {
                 int ln = lane; /* 80-VGPR form: recomputed, or the per-lane store address lives in scratch (see F's intake) */
                 if (ADDR_LDS) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
-                if (ln < 40 && !(SEA_ABL_S & 4)) {
+                if (ln < 40) {
                     uint32_t packed = 0u;
                     if (produced) {
-                        const float2 v = kTake ? vOut : *reinterpret_cast<const float2 *>(&soutS[2 * ln]);
+                        const float2 v = kRegs ? vOut : *reinterpret_cast<const float2 *>(&soutS[2 * ln]);
                         packed = (uint32_t)cast_i16(v.x) | ((uint32_t)cast_i16(v.y) << 16);
                         if (outf) *reinterpret_cast<float2 *>(outf + fo * SEA_HOP + 2 * ln) = v;
                     }
                     out32[fo * 40 + ln] = packed;
                 }
                 if (FD && produced && lane == 0 && a.flags_out)
-                    a.flags_out[off / 8 + 10 * fo] = (unsigned char)L.fdFlags[L.r34[fo & (kRec34 - 1)].tick & (kSlots - 1)];
+                    a.flags_out[off / 8 + 10 * fo] = (unsigned char)L.fdFlags[L.r34[fo & 1].tick & (kSlots - 1)];
                 wave_sync();
             }
             NS_T_CK(4);
             NS_T_MID;
-            if (!SEA_ABL_HALFSYNC || (i & 1)) block_sync();
+            block_sync();
             NS_T_END;
         }
         if (a.first_out && lane == 0) a.first_out[u] = firstOut;
@@ -749,8 +647,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
 
 } // namespace p4
 
-#ifndef SEA_NS_BODY_ONLY
-__global__ __launch_bounds__(256, SEA_NS_MIN_WAVES) void ns_denoise_pipe_kernel(NsBatchArgs a)
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_kernel(NsBatchArgs a)
 {
     __shared__ p4::PipeLds<false> L;
     p4::ns_pipe_body<false, false>(a, L);
@@ -759,10 +656,7 @@ __global__ __launch_bounds__(256, SEA_NS_MIN_WAVES) void ns_denoise_pipe_kernel(
 /* the same arithmetic with the transform's address tables in LDS instead of VGPRs: 80 instead of 110
  * VGPRs, six workgroups per CU instead of four -- the form to launch when the batch has more than four
  * utterances per CU (373 vs 331 M frames/s at 4096 utterances; 267 vs 298 M at 1024) */
-#ifndef SEA_NS_BIG_WAVES
-#define SEA_NS_BIG_WAVES 6
-#endif
-__global__ __launch_bounds__(256, SEA_NS_BIG_WAVES) void ns_denoise_pipe_big_kernel(NsBatchArgs a)
+__global__ __launch_bounds__(256, p4::kBigWaves) void ns_denoise_pipe_big_kernel(NsBatchArgs a)
 {
     __shared__ p4::PipeLds<true> L;
     p4::ns_pipe_body<false, true>(a, L);
@@ -770,12 +664,12 @@ __global__ __launch_bounds__(256, SEA_NS_BIG_WAVES) void ns_denoise_pipe_big_ker
 
 /* both forms for utterances processed in time slices (NsBatchArgs::state): the recursion is loaded at the start and
  * stored at the end of the launch; kernels of their own so that the whole-utterance forms keep their register budgets */
-__global__ __launch_bounds__(256, SEA_NS_MIN_WAVES) void ns_denoise_pipe_slice_kernel(NsBatchArgs a)
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_slice_kernel(NsBatchArgs a)
 {
     __shared__ p4::PipeLds<false> L;
     p4::ns_pipe_body<false, false, true>(a, L);
 }
-__global__ __launch_bounds__(256, SEA_NS_BIG_WAVES) void ns_denoise_pipe_big_slice_kernel(NsBatchArgs a)
+__global__ __launch_bounds__(256, p4::kBigWaves) void ns_denoise_pipe_big_slice_kernel(NsBatchArgs a)
 {
     __shared__ p4::PipeLds<true> L;
     p4::ns_pipe_body<false, true, true>(a, L);
@@ -783,16 +677,15 @@ __global__ __launch_bounds__(256, SEA_NS_BIG_WAVES) void ns_denoise_pipe_big_sli
 
 /* the same pipeline with the first stage's speech measures (SpeechQVar/Spec/Mel, VADNS) evaluated in
  * B0 and their four bits stored per output frame: input of the frame-dropping VAD */
-__global__ __launch_bounds__(256, SEA_NS_MIN_WAVES) void ns_denoise_pipe_fd_kernel(NsBatchArgs a)
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_fd_kernel(NsBatchArgs a)
 {
     __shared__ p4::PipeLds<false, true> L;
     p4::ns_pipe_body<true, false>(a, L);
 }
-#endif
 
 } // namespace sea
 
-#if defined(SEA_NS_TIMING) && !defined(SEA_NS_BODY_ONLY)
+#ifdef SEA_NS_TIMING
 extern "C" int sea_debug_ns_back_ck(unsigned long long *out16, int reset)
 {
     if (reset) {

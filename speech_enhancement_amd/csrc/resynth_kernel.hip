@@ -138,22 +138,16 @@ __device__ __forceinline__ void tile_sync()
 }
 
 /* Issue priority by REMAINING tiles (longest-remaining-processing-time first, as the four-wave NoiseSup kernel has it,
- * ns_pipe_kernel.hip: SEA_PRIO_LRPT): every wave counts its tile barriers down and, every 64 tiles, sets s_setprio from
+ * ns_pipe_kernel.hip): every wave counts its tile barriers down and, every 64 tiles, sets s_setprio from
  * 32 * remaining / (the batch's longest utterance) dithered over eight consecutive evaluations into the four hardware
  * levels, so that the utterances sharing a CU converge on a common finishing time.  scale = 0: off. */
-#ifndef SEA_RS_FEED_W3
-#define SEA_RS_FEED_W3 1
-#endif
-#ifndef SEA_RS_LRPT
-#define SEA_RS_LRPT 1
-#endif
 struct TilePrio {
     long long left; /* tile barriers this wave still has to pass */
     float scale;    /* 32 / (tile barriers of the batch's longest utterance); 0: off */
     __device__ __forceinline__ void tick()
     {
         --left;
-        if (SEA_RS_LRPT && scale > 0.0f && (left & 63) == 0) {
+        if (scale > 0.0f && (left & 63) == 0) {
             const int lv = __builtin_amdgcn_readfirstlane((int)((float)left * scale)) + (int)((left >> 6) & 7);
             if (lv >= 24) __builtin_amdgcn_s_setprio(3);
             else if (lv >= 16) __builtin_amdgcn_s_setprio(2);
@@ -318,7 +312,7 @@ namespace {
 struct __attribute__((aligned(16))) FwdLds {
     v2f pq[2][kTile][64]; /* R1 -> R2: new (p1,q1) */
     v2f pa[2][kTile][64]; /* R2 -> R3: partial sums A */
-    float xs[2][kTile]; /* SEA_RS_FEED_W3: the input samples of tile j at [j & 1], deposited one tile ahead by the fourth wave */
+    float xs[2][kTile]; /* the input samples of tile j at [j & 1], deposited one tile ahead by the fourth wave */
 };
 
 /* roles 0..2 work; any further wave of the workgroup only keeps the barrier count (fused kernel) */
@@ -331,14 +325,14 @@ __device__ __forceinline__ void resynth_fwd_body(const ResynthArgs &a, FwdLds &S
     const int nwaves = (int)(blockDim.x >> 6);
     RS_T_DECL;
     if (role > 2) {
-        /* SEA_RS_FEED_W3 (round 4): the fused kernel's fourth wave, idle during this pass, converts and deposits the input samples of
+        /* the fused kernel's fourth wave, idle during this pass, converts and deposits the input samples of
          * tile j + 1 while the cascade works on tile j: the first cascade wave R1 -- the longest role of the pass -- no longer pays a
          * store / fence / load round trip per tile for them */
         const int16_t *in = a.in + off;
         InFeed feed;
-        if (SEA_RS_FEED_W3 && role == 3) feed.start(in, L, lane);
+        if (role == 3) feed.start(in, L, lane);
         for (long long j = 0; j < niter; ++j) {
-            if (SEA_RS_FEED_W3 && role == 3 && j + 1 < ntile) feed.tile(in, L, j + 1, lane, S.xs[(j + 1) & 1]);
+            if (role == 3 && j + 1 < ntile) feed.tile(in, L, j + 1, lane, S.xs[(j + 1) & 1]);
             tile_sync(tp);
         }
     } else if (role == 0) {
@@ -347,7 +341,7 @@ __device__ __forceinline__ void resynth_fwd_body(const ResynthArgs &a, FwdLds &S
         GtLo s = {};
         InFeed feed;
         feed.start(in, L, lane); /* extractwav.cpp:55-58 */
-        const bool ownFeed = !(SEA_RS_FEED_W3 && nwaves > 3); /* the three-wave kernel of the split form feeds itself */
+        const bool ownFeed = nwaves <= 3; /* the three-wave kernel of the split form feeds itself */
         for (long long j = 0; j < niter; ++j) {
             RS_T_BEGIN;
             if (j < ntile) {
@@ -766,29 +760,14 @@ __device__ __forceinline__ float haircell_kt(const HairCell &h, float in)
     return (s > 0.0) ? (float)((double)h.gdt * s / (s + 300.0)) : 0.0f;
 }
 
-/* the recurrence (extractwav.cpp:239-255); returns output[n] = hdt * c */
-__device__ __forceinline__ float haircell_step(HairCell &h, float kt)
-{
-    const float replenish = ((double)h.q < 1.0) ? (h.ymdt - h.ydt * h.q) : 0.0f;
-    const float eject = kt * h.q;
-    const float reuptakeandloss = h.lplusrdt * h.c;
-    const float reuptake = h.rdt * h.c;
-    const float reprocess = h.xdt * h.w;
-    h.q = h.q + replenish - eject + reprocess;
-    if (h.q < 0.0f) h.q = 0.0f;
-    h.c = h.c + eject - reuptakeandloss;
-    if (h.c < 0.0f) h.c = 0.0f;
-    h.w = h.w + reuptake - reprocess;
-    if (h.w < 0.0f) h.w = 0.0f;
-    return h.hdt * h.c;
-}
-
-/* the same step with fewer vector instructions on the recurrence's wave (round 4): the pair (c, w) through packed operations --
- * each half rounded like the scalar instruction -- and the three clamps as v_max_f32 against +0 instead of compare + select.
- * The clamp differs from `if (x < 0) x = 0` only for NaN and for -0.0, neither of which the recurrence can produce: every input is
- * finite (int16 audio through the gammatone cascade, kt in [0, gdt)), the state stays >= +0, and a sum or difference of finite
- * values that is zero is +0 in round-to-nearest unless both operands are -0.  15 instead of 21 instructions per sample. */
-__device__ __forceinline__ void haircell_step_lean(HairCell &h, float kt)
+/* the recurrence (extractwav.cpp:239-255): q += replenish - eject + reprocess, c += eject - reuptakeandloss,
+ * w += reuptake - reprocess, each clamped at 0; output[n] = hdt * c is taken from the state by the caller.  The pair (c, w) goes
+ * through packed operations -- each half rounded like the scalar instruction -- and the three clamps are v_max_f32 against +0
+ * instead of compare + select.  The clamp differs from the reference's `if (x < 0) x = 0` only for NaN and for -0.0, neither of
+ * which the recurrence can produce: every input is finite (int16 audio through the gammatone cascade, kt in [0, gdt)), the state
+ * stays >= +0, and a sum or difference of finite values that is zero is +0 in round-to-nearest unless both operands are -0.
+ * 15 instead of 21 instructions per sample. */
+__device__ __forceinline__ void haircell_step(HairCell &h, float kt)
 {
     typedef float v2 __attribute__((ext_vector_type(2)));
     const float replenish = (h.q < 1.0f) ? (h.ymdt - h.ydt * h.q) : 0.0f; /* (double)q < 1.0 <=> q < 1.0f: the conversion is exact */
@@ -803,19 +782,12 @@ __device__ __forceinline__ void haircell_step_lean(HairCell &h, float kt)
     h.c = __builtin_fmaxf(cw.x, 0.0f);
     h.w = __builtin_fmaxf(cw.y, 0.0f);
 }
-#ifndef SEA_SB_HC_LEAN
-#define SEA_SB_HC_LEAN 1
-#endif
 
-constexpr int kSbStride = 66; /* int16 per tile row: 64 channels + 2 pad (33 words: conflict-free) */
-/* SEA_SB_CAST_IN_W (round 4): the hair cell's wave -- the longest role of subbband() by half (2850 clk per 16-sample tile against
+/* The hair cell's wave -- the longest role of subbband() by half (2850 clk per 16-sample tile against
  * 1900 for the next) -- leaves its state c of every step where its input kt stood (the permeability tile, now a ring of three
  * float tiles of row stride 66) and the transposing wave W, idle four fifths of a tile, takes hdt * c, the truncating cast and the
  * store: four of the 29 vector instructions per sample leave the recurrence's wave.  Same operations on the same values. */
-#ifndef SEA_SB_CAST_IN_W
-#define SEA_SB_CAST_IN_W 1
-#endif
-constexpr int kKtStride = SEA_SB_CAST_IN_W ? 66 : 64, kKtBufs = SEA_SB_CAST_IN_W ? 3 : 2;
+constexpr int kKtStride = 66, kKtBufs = 3;
 
 } // namespace
 
@@ -824,7 +796,6 @@ __global__ __launch_bounds__(384) void subband_kernel(SubbandArgs a)
     __shared__ RsLds S;
     __shared__ __attribute__((aligned(16))) float xs[kTile];
     __shared__ __attribute__((aligned(16))) float ktile[kKtBufs][kTile][kKtStride];
-    __shared__ __attribute__((aligned(16))) short otile[SEA_SB_CAST_IN_W ? 1 : 2][SEA_SB_CAST_IN_W ? 8 : kTile * kSbStride];
     const int lane = threadIdx.x & 63;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
@@ -905,17 +876,10 @@ __global__ __launch_bounds__(384) void subband_kernel(SubbandArgs a)
             const long long jt = j - 3;
             if (jt >= 0 && jt < ntile) {
                 float(*k)[kKtStride] = ktile[jt % kKtBufs];
-                short *o = otile[SEA_SB_CAST_IN_W ? 0 : (jt & 1)];
 #pragma unroll
                 for (int t = 0; t < kTile; ++t) {
-                    if (SEA_SB_CAST_IN_W && SEA_SB_HC_LEAN) {
-                        haircell_step_lean(h, k[t][lane]);
-                        k[t][lane] = h.c;
-                    } else {
-                        const float v = haircell_step(h, k[t][lane]);
-                        if (SEA_SB_CAST_IN_W) k[t][lane] = h.c; /* W takes hdt * c and the cast */
-                        else o[t * kSbStride + lane] = (short)cast_i16(v);
-                    }
+                    haircell_step(h, k[t][lane]);
+                    k[t][lane] = h.c; /* W takes hdt * c and the cast */
                 }
             }
             RS_T_MID;
@@ -936,14 +900,12 @@ __global__ __launch_bounds__(384) void subband_kernel(SubbandArgs a)
             const long long jt = j - 4;
             if (jt >= 0 && jt < ntile) {
                 const long long n = jt * kTile + t;
-                const short *o = otile[SEA_SB_CAST_IN_W ? 0 : (jt & 1)] + (SEA_SB_CAST_IN_W ? 0 : t * kSbStride);
                 const float *cf = &ktile[jt % kKtBufs][t][0];
                 if (n < L) {
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
                         const int c = 4 * k + cg;
-                        if (SEA_SB_CAST_IN_W) out[c * Lp + n] = (short)cast_i16(hdtW * cf[c]); /* extractwav.cpp:255, :85-88 */
-                        else out[c * Lp + n] = o[c];
+                        out[c * Lp + n] = (short)cast_i16(hdtW * cf[c]); /* extractwav.cpp:255, :85-88 */
                     }
                 }
             }

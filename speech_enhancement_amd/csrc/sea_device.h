@@ -256,7 +256,6 @@ __device__ __forceinline__ void rfft256(float e0, float e1, float e2, float e3, 
     const int r = (int)(__brev((unsigned)lane) >> 26);
     *reinterpret_cast<float4 *>(work + 4 * r) = make_float4(g0, g1, g2, g3);
     wave_sync();
-#ifndef SEA_ABLATE_FFT
     fft_level<0>(work, R);
     wave_sync();
     fft_level<1>(work, R);
@@ -269,7 +268,6 @@ __device__ __forceinline__ void rfft256(float e0, float e1, float e2, float e3, 
     wave_sync();
     fft_level<5>(work, R);
     wave_sync();
-#endif
 }
 
 /* Swizzled form of rfft256: 256-point real split-radix FFT of one frame held 4 elements per lane: lane l passes elements
@@ -302,7 +300,6 @@ __device__ __forceinline__ void rfft256(float e0, float e1, float e2, float e3, 
     fft_at(work, R.head[1] & 0xffffu) = g2;
     fft_at(work, R.head[1] >> 16) = g3;
     wave_sync();
-#ifndef SEA_ABLATE_FFT
     fft_level<0>(work, R);
     wave_sync();
     fft_level<1>(work, R);
@@ -315,7 +312,6 @@ __device__ __forceinline__ void rfft256(float e0, float e1, float e2, float e3, 
     wave_sync();
     fft_level<5>(work, R);
     wave_sync();
-#endif
 }
 
 /* ---- two independent 256-point transforms side by side in one wave (lanes 0..31 / 32..63) ----
@@ -326,16 +322,10 @@ __device__ __forceinline__ void rfft256(float e0, float e1, float e2, float e3, 
  * then bound by the longest utterance's chain of frames, which is what matters up to four workgroups
  * per CU) or in LDS (one ds_read_b128 per level, 30 VGPRs fewer: six workgroups per CU, which is what
  * matters for large batches). */
-#ifndef SEA_FFT_PACKED
-#define SEA_FFT_PACKED 1
-#endif
-
-#ifndef SEA_FFT_HEAD16
-#define SEA_FFT_HEAD16 1 /* the n2 = 16 level of the dual transform on registers (rfft256_head16): one LDS round trip less per transform.
-                          * Only in the table-in-LDS forms (ADDR_LDS: the large-batch NoiseSup kernels, where the LDS array is the busier
-                          * pipe: configs[4] shard 477 -> 481 M frames/s); everywhere else the ~25 extra vector instructions cost what the
-                          * sixteen LDS instructions save (configs[1] 1.966 -> 1.981 ms, CompCeps unchanged) */
-#endif
+/* The table-in-LDS forms also run the n2 = 16 level of the dual transform on registers (rfft256_head16): one LDS round trip less per
+ * transform.  Only there (the large-batch NoiseSup kernels, where the LDS array is the busier pipe: configs[4] shard 477 -> 481 M
+ * frames/s); everywhere else the ~25 extra vector instructions cost what the sixteen LDS instructions save (configs[1] 1.966 ->
+ * 1.981 ms, CompCeps unchanged). */
 struct Fft2Regs {
     unsigned kind[SEA_FFT_LSTAGES];
     unsigned addr[SEA_FFT_LSTAGES][4]; /* byte offsets of the eight operands, two per word, already moved
@@ -345,7 +335,7 @@ struct Fft2Regs {
     unsigned headA[2], psdA[2];        /* frame A: where this lane stores its head values / finds its PSD inputs */
     unsigned nyq;
     unsigned head8Flags, head8[4];     /* the eight-positions-per-lane start (sea_tables.h fft8*), this lane's transform */
-    unsigned head16[4];                /* SEA_FFT_HEAD16: where the lane's results of the register-resident n2 = 16 level go (fft16*) */
+    unsigned head16[4];                /* ADDR_LDS: where the lane's results of the register-resident n2 = 16 level go (fft16*) */
     float tw16[4];                     /* the one twiddle set of that level (j = 1) */
 };
 
@@ -375,7 +365,7 @@ __device__ __forceinline__ void load_fft2_regs(Fft2Regs &R, const sea_fft_tables
     R.psdA[0] = t->fft2Psd[0][lane];
     R.psdA[1] = t->fft2Psd[1][lane];
     R.nyq = t->fft2Nyq;
-    R.head8Flags = (SEA_FFT_HEAD16 && ADDR_LDS) ? t->fft16Flags[lane] : t->fft8Flags[lane];
+    R.head8Flags = ADDR_LDS ? t->fft16Flags[lane] : t->fft8Flags[lane];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         R.head8[q] = t->fft8Addr[q][lane] + both;
@@ -428,8 +418,7 @@ __device__ __forceinline__ void fft2_butterfly(const Fft2Regs &R, const Fft2Ops 
     float o1, o2, o3, o4, o5, o6, o7, o8;
     { /* SEA_BF_TWIDDLE, rfft.c:145-174 */
         const float cc1 = R.tw[S][0], ss1 = R.tw[S][1], cc3 = R.tw[S][2], ss3 = R.tw[S][3];
-#if SEA_FFT_PACKED
-        /* the same 24 operations on register pairs (v_pk_mul_f32 / v_pk_add_f32: each half rounded like the
+        /* the 24 operations of rfft.c:145-174 on register pairs (v_pk_mul_f32 / v_pk_add_f32: each half rounded like the
          * scalar instruction; a - b == a + (-b) and the operand swaps / sign flips are instruction modifiers):
          *   (t1,t2) = (x3,x7)*(cc1,cc1) + (x7,x3)*(ss1,-ss1)      (t3,t4) likewise from (x4,x8), cc3, ss3 */
         typedef float v2f __attribute__((ext_vector_type(2)));
@@ -448,23 +437,6 @@ __device__ __forceinline__ void fft2_butterfly(const Fft2Regs &R, const Fft2Ops 
         const v2f o83 = v2f{T56.y, T56.y} + v2f{x6, -x6}; /* x6 + t6, t6 - x6 */
         const v2f o47 = v2f{x2, -x2} - v2f{D34.x, D34.x}; /* x2 - t3, -x2 - t3 */
         o1 = o16.x, o6 = o16.y, o2 = o25.x, o5 = o25.y, o8 = o83.x, o3 = o83.y, o4 = o47.x, o7 = o47.y;
-#else
-        float t1 = x3 * cc1 + x7 * ss1;
-        float t2 = x7 * cc1 - x3 * ss1;
-        float t3 = x4 * cc3 + x8 * ss3;
-        float t4 = x8 * cc3 - x4 * ss3;
-        const float t5 = t1 + t3, t6 = t2 + t4;
-        t3 = t1 - t3;
-        t4 = t2 - t4;
-        o3 = t6 - x6;
-        o8 = x6 + t6;
-        o7 = -x2 - t3;
-        o4 = x2 - t3;
-        o6 = x1 - t5;
-        o1 = x1 + t5;
-        o5 = x5 - t4;
-        o2 = x5 + t4;
-#endif
     }
     float p1, p3, p4, p5, p6, p7, p8;
     { /* SEA_BF_PAIR: plain butterfly on the a-quadruple (rfft.c:110-113), pi/4 butterfly on
@@ -602,7 +574,7 @@ __device__ __forceinline__ void rfft256_head8_regs(float (&e)[8], const unsigned
         e[7] = f ? o8 : x8;
     }
 }
-/* SEA_FFT_HEAD16: ... and the n2 = 16 level (rfft.c:100-174 at n2 = 16; sea_tables.h fft16*).  Lane and lane ^ 16 hold the two halves
+/* ... and the n2 = 16 level (rfft.c:100-174 at n2 = 16; sea_tables.h fft16*).  Lane and lane ^ 16 hold the two halves
  * of a 16-block; the lower one gives its four odd positions and takes the upper one's four even ones (v_permlane16_swap), then runs the
  * block's PAIR item on the eight even positions while the upper one runs the twiddled item (j = 1) on the eight odd ones -- the
  * butterflies of fft2_bf_kind on registers.  A block outside the level's schedule passes through.  One LDS round trip (eight stores,
@@ -640,21 +612,8 @@ __device__ __forceinline__ void rfft256_head8(float (&e)[8], float *work, const 
     }
 }
 
-/* levels S0 .. S1 chained: level k+1's operand reads go out right behind level k's stores (see Fft2Ops) */
-template <int S0, int S1, bool ADDR_LDS>
-__device__ __forceinline__ void fft2_levels(float *work, const Fft2Regs &R, float (&prev)[8])
-{
-    Fft2Ops in;
-    fft2_load<S0, ADDR_LDS>(work, R, in);
-    fft2_keep(prev);
-    float o[8];
-    fft2_butterfly<S0>(R, in, o);
-    fft2_store<S0>(work, R, in, o);
-    wave_sync();
-    if constexpr (S0 < S1) fft2_levels<S0 + 1, S1, ADDR_LDS>(work, R, o);
-    else fft2_keep(o);
-}
-/* the same chain with level S1's results left in `last` instead of stored (rfft256_dual_keep_last) */
+/* levels S0 .. S1 chained: level k+1's operand reads go out right behind level k's stores (see Fft2Ops); level S1's results are
+ * left in `last` instead of stored (rfft256_dual_keep_last) */
 template <int S0, int S1, bool ADDR_LDS>
 __device__ __forceinline__ void fft2_levels_keep_last(float *work, const Fft2Regs &R, float (&prev)[8], float (&last)[8])
 {
@@ -675,7 +634,7 @@ __device__ __forceinline__ void fft2_levels_keep_last(float *work, const Fft2Reg
 template <bool ADDR_LDS>
 __device__ __forceinline__ void rfft256_dual_lo(float (&e)[8], float *work, const Fft2Regs &R)
 {
-    if (SEA_FFT_HEAD16 && ADDR_LDS) {
+    if (ADDR_LDS) {
         rfft256_head16(e, work, R);
         wave_sync();
     } else {
@@ -699,25 +658,11 @@ __device__ __forceinline__ void rfft256_dual_hi(float *work, const Fft2Regs &R)
     wave_sync();
 }
 
-/* LAT = true: the latency form (levels chained, branch-free butterflies) for a wave whose run time is its own chain of
- * dependent instructions -- the transform wave of the pipelined NoiseSup kernels; LAT = false: the throughput form */
-template <bool ADDR_LDS, bool LAT = false>
+/* the throughput form with the address words in VGPRs (cc_kernel.hip: rfft256_kernel) */
 __device__ __forceinline__ void rfft256_dual(float (&e)[8], float *work, const Fft2Regs &R)
 {
-    if (LAT) {
-        if (SEA_FFT_HEAD16 && ADDR_LDS) {
-            rfft256_head16(e, work, R);
-            wave_sync();
-            fft2_levels<2, 5, ADDR_LDS>(work, R, e);
-        } else {
-            rfft256_head8(e, work, R);
-            wave_sync();
-            fft2_levels<1, 5, ADDR_LDS>(work, R, e);
-        }
-    } else {
-        rfft256_dual_lo<ADDR_LDS>(e, work, R);
-        rfft256_dual_hi<ADDR_LDS>(work, R);
-    }
+    rfft256_dual_lo<false>(e, work, R);
+    rfft256_dual_hi<false>(work, R);
 }
 
 /* second half of the dual transform with the last level's results left in registers (see rfft256_dual_keep_last) */

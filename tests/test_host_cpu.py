@@ -71,6 +71,45 @@ def test_ns_kernel_form_override_accepts_only_the_built_forms():
         lib.sea_ns_kernel_form(prev)
 
 
+def test_ns6_perm_override_accepts_only_permutations_of_the_six_roles():
+    """sea_debug_ns6_perm (no HIP call) stores 0 (the kernel's own map) and wave -> role maps whose six octal digits are a
+    permutation of the roles 0..5, and returns the map it replaced; any other value -- a role twice, a digit above 5, a bit
+    above the six digits, fewer than six digits -- only reads: the six-wave kernels take the map unchecked, and such a map
+    leaves a role unstaffed."""
+    import speech_enhancement_amd as sea
+    lib = sea.load()
+    prev = lib.sea_debug_ns6_perm(0)
+    try:
+        for good in (0o104352, 0o543210, 0o014352, 0):
+            lib.sea_debug_ns6_perm(good)
+            assert lib.sea_debug_ns6_perm(good) == good, f"{good:o} was not stored"
+        lib.sea_debug_ns6_perm(0o104352)
+        for bad in (0o014355, 0o014372, 0o14352 | 1 << 18, 0o352, -1):
+            assert lib.sea_debug_ns6_perm(bad) == 0o104352, f"{bad:o} replaced the stored map"
+            assert lib.sea_debug_ns6_perm(0o104352) == 0o104352, f"{bad:o} was stored"
+    finally:
+        lib.sea_debug_ns6_perm(prev)
+
+
+def test_ns6_perm_environment_variable_is_validated():
+    """SEA_NS6_PERM initialises the same map in a fresh process: a permutation is taken, anything else is ignored (0 = the
+    kernel's own map stays) with one line on stderr that names the variable and the value."""
+    code = ("import sys; sys.path.insert(0, sys.argv[1]); import speech_enhancement_amd as sea; "
+            "print('perm', oct(sea.load().sea_debug_ns6_perm(0)))")
+
+    def child(value):
+        r = subprocess.run([sys.executable, "-c", code, ROOT], env=dict(os.environ, SEA_NS6_PERM=value), capture_output=True,
+                           text=True, timeout=120)
+        assert r.returncode == 0, r.stderr
+        return r.stdout.strip().splitlines()[-1], r.stderr
+
+    out, err = child("0104352")
+    assert out == "perm 0o104352" and "SEA_NS6_PERM" not in err, (out, err)
+    out, err = child("0014355")
+    assert out == "perm 0o0", out
+    assert "SEA_NS6_PERM" in err and "0014355" in err, err
+
+
 def test_host_tables_match_oracle(oracle):
     """sea_tables_host needs no GPU: the product's own table builder (csrc/sea_tables.c) against the
     oracle's, entry by entry, bit for bit."""

@@ -3,7 +3,7 @@
 compiler's own -Rpass-analysis=kernel-resource-usage remarks (cross-compiles, no GPU needed).
 
     python tools/kernel_resources.py                      # every .hip under speech_enhancement_amd/csrc
-    python tools/kernel_resources.py ns_pipe_kernel.hip -DSEA_NS_MIN_WAVES=4
+    python tools/kernel_resources.py ns_pipe_kernel.hip -DSEA_NS_TIMING
 """
 import os
 import re

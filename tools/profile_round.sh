@@ -8,10 +8,12 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out
 mkdir -p $O
 cd $R
-python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err || { tail -5 $O/${TAG}_bench_n1.err; exit 1; }
-python tools/bench_extra.py --what subband,afe,host --steps 5 > $O/${TAG}_bench_extra_1024.jsonl 2> /dev/null
-python tools/ns16k_time.py 1024 400 > $O/${TAG}_ns16k_time.txt 2> /dev/null
-python tools/ns16k_time.py 4096 200 >> $O/${TAG}_ns16k_time.txt 2> /dev/null
+# every GPU step runs under a limit of its own, and one that fails or times out ends the script: nothing is started after it
+step() { timeout -k 10 "$@" || { echo "profile_round: that step failed or timed out: stopping" >&2; exit 1; }; }
+echo "profile_round: bench"; timeout -k 10 600 python bench.py --full > $O/${TAG}_bench_n1.json 2> $O/${TAG}_bench_n1.err || { tail -5 $O/${TAG}_bench_n1.err; exit 1; }
+echo "profile_round: bench_extra"; step 300 python tools/bench_extra.py --what subband,afe,host --steps 5 > $O/${TAG}_bench_extra_1024.jsonl 2> /dev/null
+echo "profile_round: ns16k_time"; step 120 python tools/ns16k_time.py 1024 400 > $O/${TAG}_ns16k_time.txt 2> /dev/null
+step 120 python tools/ns16k_time.py 4096 200 >> $O/${TAG}_ns16k_time.txt 2> /dev/null
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/p_tr
 # every profiler pass prints a line first (a silent call is taken to be hung after 7 minutes) and runs under its own limit:
@@ -64,5 +66,5 @@ python3 $R/tools/prof_summary.py /tmp/p_mix1 $O/${TAG}_pmc_mix1.txt --delete-raw
 python3 $R/tools/make_pmc_traffic.py $O/${TAG}_pmc_fetch.txt $O/${TAG}_pmc_write.txt $O/pmc_traffic.json $O/${TAG}_pmc_sq1.txt $O/${TAG}_pmc_mix1.txt \
     --big $O/${TAG}_pmc_big_fetch.txt $O/${TAG}_pmc_big_write.txt $O/${TAG}_pmc_big_sq1.txt $O/${TAG}_pmc_big_mix1.txt && cp $O/pmc_traffic.json $R/profiles/pmc_traffic.json
 cd $R
-python bench.py --full --no-cpu-baseline > $O/${TAG}_bench_n1_with_traffic.json 2> /dev/null   # same tree, traffic from the fresh stamp
+step 600 python bench.py --full --no-cpu-baseline > $O/${TAG}_bench_n1_with_traffic.json 2> /dev/null   # same tree, traffic from the fresh stamp
 echo "profile_round done -- back home copy gpurun_out/${TAG}_* AND gpurun_out/pmc_traffic.json into profiles/ (the stamp bench.py checks)"
