@@ -144,6 +144,48 @@ int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags,
                            const long long *d_ceps_cum, long long total_ceps, float *d_feat_cc, float *d_feat_pp,
                            const long long *d_feat_cum, float *d_feat15, int *d_n_feat, int *d_n_ceps, int n_utt,
                            void *stream);
+/* The ETSI WIDEBAND (16 kHz) mode -- what AdvProcessAlloc (16000) switches on (etsi/cpp/ParmInterface.c:100-108), not the
+ * defective wrapper etsi_denoise_16k: frames of 160 samples at 16 kHz, each split by the standard's 118-tap QMF pair into a
+ * 0-4 kHz and a 4-8 kHz half (Do16kProcessing, etsi/cpp/16kHzProcessing.c:711-774).  The low half runs through the
+ * two-stage Wiener filter exactly as an 8 kHz signal would; the high half becomes, per NoiseSup output frame, three
+ * spectrally subtracted mel band energies and a 3 x 3 code against the low band's upper bands (NoiseSup.c:1216-1235,
+ * :1307-1327), which sea_wb_compceps_batch merges into a 26-band cepstrum.
+ *   d_in             packed int16 at 16 kHz, utterance u at [d_offsets[u], d_offsets[u] + d_lengths[u]) as above; the trailing
+ *                    d_lengths[u] % 160 samples are ignored
+ *   everything at the 8 kHz rate is indexed by HALF the offset: frame f (80 samples) of utterance u sits at
+ *                    d_offsets[u] / 2 + 80 f, in buffers of total_padded_samples / 2 elements
+ *   per-frame ROWS   frame f of utterance u owns row ceil (d_offsets[u] / 160) + f of buffers with
+ *                    sea_wb_rows (total_padded_samples) rows; only frames with a NoiseSup output have their rows written
+ *   d_out_lp         int16 low-band output, (short) truncation of the float one; zeros for every frame before the first
+ *                    NoiseSup output (4 frames after the first non-zero input frame), as etsi_denoise writes them
+ *   d_out_f32        optional: the float NoiseSup output, written where produced
+ *   d_first_out      optional: per utterance, index of the first frame with an output, -1 if none
+ *   d_onset          optional: per utterance, index of the first frame whose 160 raw samples are not all zero (the zero-frame
+ *                    gate of ParmInterface.c:244-251 acts on the raw input; frames before it advance nothing), the frame
+ *                    count if there is none
+ *   d_hp_rows        optional, with d_code_rows: rows of 3 floats, the high-band energies after DoSpecSub16k (what
+ *                    NoiseSup.c:1421-1422 appends to hpBands)
+ *   d_code_rows      rows of 9 floats, CodeForBands16k (NoiseSup.c:1325)
+ *   d_scratch        sea_wb_scratch_bytes (total_padded_samples, n_utt) bytes, 16-byte aligned.  After the call its first
+ *                    total_padded_samples / 2 floats (rounded up to 8) hold the QMF low band and the next as many the high
+ *                    band (shifted down to 0-4 kHz), indexed like the other 8 kHz-rate buffers, for every whole frame
+ *   total_padded_samples  size of d_in in samples (the sum of the utterances' lengths, each rounded up to 8) */
+int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                         const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset, float *d_hp_rows,
+                         float *d_code_rows, void *d_scratch, long long total_padded_samples, int n_utt, void *stream);
+long long sea_wb_scratch_bytes(long long total_padded_samples, int n_utt);
+long long sea_wb_rows(long long total_padded_samples);
+/* The wideband CompCeps (CompCeps.c:392-402, :464-479, :488-530) on those outputs: 14 floats per cepstral frame (c1..c12, c0,
+ * logE; 26-band DCT, logE after the high-band correction), the first after the third NoiseSup output.  d_ceps_cum /
+ * d_ceps / d_n_ceps as for sea_compceps_batch, capacities >= d_lengths[u] / 160 - 6. */
+int sea_wb_compceps_batch(const float *d_out_f32, const long long *d_offsets, const long long *d_lengths, const int *d_first_out,
+                          const float *d_hp_rows, const float *d_code_rows, const long long *d_ceps_cum, long long total_frames,
+                          float *d_ceps, int *d_n_ceps, int n_utt, void *stream);
+/* one utterance from host memory, in the style of etsi_denoise: out_lp[0 .. 80 * (n / 160)) is written */
+int sea_wb_denoise(const short *in, long n, short *out_lp);
+/* the mode's tables as the library computed them (tests): the QMF pair, bands 1..3 of the high band's mel filter
+ * (InitMelFBwindows (.., 80.0, 8000, 128, 5, 0)) and the 26-channel DCT (InitDCTMatrix (13, 26)) */
+int sea_wb_tables_host(float *qmfLp118, float *qmfHp118, int *hpMelStart3, int *hpMelLen3, float *hpMelW3x64, float *dct12x26);
 /* 64-band gammatone resynthesis over a batch.  mask rows (64 floats) of utterance u start at row
  * d_mask_offsets[u] and number (lengths[u]-320)/160+1.  d_inter is scratch of
  * sea_resynth_scratch_bytes(total padded samples of the batch, n_utt) bytes (the [time][64]

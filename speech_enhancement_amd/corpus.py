@@ -49,6 +49,23 @@ def synth_utterance(u, length=None):
     return x
 
 
+def synth_wideband(u, length):
+    """A signal that reaches the upper half of a 16 kHz band, for the wideband (QMF) mode: the corpus utterances stop at
+    1.65 kHz plus flat noise and leave its high-band noise tracker idle.  Harmonics h = 1 .. floor(7600 / f0) - 1 of
+    f0 = 140 + 7 u Hz with amplitudes h^-1/2, gated on/off every 0.4 s (A = 2500 * [(i mod 12800) < 6400]), scaled by
+    A / 3, plus uniform noise in [-200, 200] from the LCG seeded 777 + u; truncated to int16."""
+    L = int(length)
+    i = np.arange(L, dtype=np.float64)
+    f0 = 140 + 7 * u
+    speech = np.zeros(L, np.float64)
+    for h in range(1, int(7600 // f0)):
+        speech += np.sin(2 * np.pi * h * f0 * i / 16000.0) / np.sqrt(h)
+    speech *= (2500.0 / 3.0) * ((np.arange(L) % 12800) < 6400)
+    s = lcg_stream(777 + u, L)
+    noise = ((s >> np.uint32(16)) % np.uint32(401)).astype(np.int64) - 200
+    return np.clip(np.trunc(speech + noise), -32768, 32767).astype(np.int16)
+
+
 def synth_mask(u, length):
     F = (int(length) - 320) // 160 + 1
     s = lcg_stream(777 + u, F * 64)

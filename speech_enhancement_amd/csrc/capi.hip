@@ -40,6 +40,7 @@ sea_ns_tables g_ns_host;
 sea_cc_tables g_cc_host;
 sea_gt_tables g_gt_host;
 sea_ns16k_tables g_ns16_host;
+sea_wb_tables g_wb_host;
 bool g_host_ready = false;
 
 void host_tables()
@@ -49,6 +50,7 @@ void host_tables()
     sea_build_cc_tables(&g_cc_host);
     sea_build_gt_tables(&g_gt_host);
     sea_build_ns16k_tables(&g_ns16_host);
+    sea_build_wb_tables(&g_wb_host);
     g_host_ready = true;
 }
 } // namespace
@@ -71,10 +73,12 @@ int ctx(DeviceCtx **out)
         HIP_TRY(hipMalloc(&c.cc, sizeof(sea_cc_tables)));
         HIP_TRY(hipMalloc(&c.gt, sizeof(sea_gt_tables)));
         HIP_TRY(hipMalloc(&c.ns16, sizeof(sea_ns16k_tables)));
+        HIP_TRY(hipMalloc(&c.wb, sizeof(sea_wb_tables)));
         HIP_TRY(hipMemcpy(c.ns, &g_ns_host, sizeof g_ns_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.cc, &g_cc_host, sizeof g_cc_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.gt, &g_gt_host, sizeof g_gt_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.ns16, &g_ns16_host, sizeof g_ns16_host, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.wb, &g_wb_host, sizeof g_wb_host, hipMemcpyHostToDevice));
         c.ready = true;
     }
     *out = &c;
@@ -374,6 +378,142 @@ int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags,
     }
     hipLaunchKernelGGL(sea::afe_vad_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, a);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+/* ---- the ETSI wideband (16 kHz) mode: QMF split + NoiseSup on the low band (wb_kernel.hip, ns_pipe_kernel.hip) ---- */
+int sea_wb_tables_host(float *qmfLp118, float *qmfHp118, int *hpMelStart3, int *hpMelLen3, float *hpMelW3x64, float *dct12x26)
+{
+    sea_wb_plain_tables(qmfLp118, qmfHp118, hpMelStart3, hpMelLen3, hpMelW3x64, dct12x26);
+    return 0;
+}
+
+long long sea_wb_rows(long long total_padded_samples) { return total_padded_samples > 0 ? total_padded_samples / SEA_WB_HOP + 1 : 1; }
+
+/* scratch layout: [low band: total / 2 floats][high band: total / 2 floats][raw onset: n_utt ints] */
+long long sea_wb_scratch_bytes(long long total_padded_samples, int n_utt)
+{
+    if (total_padded_samples < 0 || n_utt < 0) return 0;
+    return align8(total_padded_samples / 2) * 2 * (long long)sizeof(float) + align8(n_utt) * (long long)sizeof(int);
+}
+
+int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                         const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset, float *d_hp_rows,
+                         float *d_code_rows, void *d_scratch, long long total_padded_samples, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_in || !d_out_lp || !d_offsets || !d_lengths || !d_scratch)
+        return fail("sea_wb_denoise_batch: input, low-band output, offsets, lengths and scratch are required");
+    if ((d_hp_rows == nullptr) != (d_code_rows == nullptr)) return fail("sea_wb_denoise_batch: the high-band rows and the code rows come together");
+    if (total_padded_samples < 0 || (total_padded_samples & 7)) return fail("sea_wb_denoise_batch: total_padded_samples must be a multiple of 8");
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    const long long half = align8(total_padded_samples / 2);
+    float *lp = static_cast<float *>(d_scratch), *hp = lp + half;
+    int *onset = reinterpret_cast<int *>(hp + half);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(onset, 0x7f, (size_t)n_utt * sizeof(int), st)); /* 0x7f7f7f7f: beyond any frame count */
+    sea::WbQmfArgs q = {};
+    q.in = d_in;
+    q.offsets = d_offsets;
+    q.lengths = d_lengths;
+    q.lp = lp;
+    q.hp = hp;
+    q.onset = onset;
+    q.tables = c->wb;
+    q.n_utt = n_utt;
+    /* blockIdx.y strides over an utterance's frames: about two frames per workgroup for an utterance of average length */
+    long long rows = total_padded_samples / SEA_WB_HOP / n_utt / 2 + 1;
+    if (rows > 1024) rows = 1024;
+    hipLaunchKernelGGL(sea::wb_qmf_kernel, dim3((unsigned)n_utt, (unsigned)rows), dim3(sea::kWbQmfThreads), 0, st, q);
+    HIP_TRY(hipGetLastError());
+    sea::NsWbArgs a = {};
+    a.b.out = d_out_lp;
+    a.b.out_f32 = d_out_f32;
+    a.b.offsets = d_offsets;
+    a.b.lengths = d_lengths;
+    a.b.order = d_order;
+    a.b.first_out = d_first_out;
+    a.b.onset_out = d_onset;
+    a.b.tables = c->ns;
+    a.b.n_utt = n_utt;
+    a.in_f32 = lp;
+    a.onset = onset;
+    hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_kernel, dim3(n_utt), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (d_hp_rows) { /* the high band: needs the two QMF streams and the onset only */
+        sea::WbHbArgs h = {};
+        h.lp = lp;
+        h.hp = hp;
+        h.offsets = d_offsets;
+        h.lengths = d_lengths;
+        h.onset = onset;
+        h.hp_rows = d_hp_rows;
+        h.code_rows = d_code_rows;
+        h.ns = c->ns;
+        h.wb = c->wb;
+        h.n_utt = n_utt;
+        /* one wave per workgroup, about two output frames each (eight each: 2.53 ms against 2.43 on the 2048-utterance workload) */
+        hipLaunchKernelGGL(sea::wb_hb_kernel, dim3((unsigned)n_utt, (unsigned)rows), dim3(64), 0, st, h);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(sea::wb_specsub_kernel, dim3((unsigned)((n_utt + 63) / 64)), dim3(64), 0, st, h);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+int sea_wb_compceps_batch(const float *d_out_f32, const long long *d_offsets, const long long *d_lengths, const int *d_first_out,
+                          const float *d_hp_rows, const float *d_code_rows, const long long *d_ceps_cum, long long total_frames,
+                          float *d_ceps, int *d_n_ceps, int n_utt, void *stream)
+{
+    if (n_utt <= 0 || total_frames <= 0) return 0;
+    if (!d_out_f32 || !d_first_out || !d_hp_rows || !d_code_rows)
+        return fail("sea_wb_compceps_batch: the float stream, first_out, the high-band rows and the code rows are required");
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::WbCepsArgs a = {};
+    a.c.den_f32 = d_out_f32;
+    a.c.offsets = d_offsets;
+    a.c.lengths = d_lengths;
+    a.c.first_out = d_first_out;
+    a.c.ceps_cum = d_ceps_cum;
+    a.c.ceps = d_ceps;
+    a.c.n_ceps = d_n_ceps;
+    a.c.tables = c->cc;
+    a.c.n_utt = n_utt;
+    a.hp_rows = d_hp_rows;
+    a.code_rows = d_code_rows;
+    a.wb = c->wb;
+    const long long nslot = total_frames / 16 + n_utt; /* tile slots of 16 frames, as sea_compceps_batch */
+    const long long grid = nslot < 16384 ? nslot : 16384;
+    hipLaunchKernelGGL(sea::compceps_wb_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_wb_denoise(const short *in, long n, short *out_lp)
+{
+    const long nfr = n > 0 ? n / SEA_WB_HOP : 0;
+    if (nfr <= 0) return 0;
+    if (!in || !out_lp) return fail("sea_wb_denoise: null buffer");
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    const long long total = align8(n);
+    const long long meta[2] = {0, (long long)n};
+    DevBuf<short> d_in, d_out;
+    DevBuf<long long> d_meta;
+    DevBuf<char> d_scr;
+    HIP_TRY(d_in.alloc((size_t)total));
+    HIP_TRY(d_out.alloc((size_t)total / 2));
+    HIP_TRY(d_meta.alloc(2));
+    HIP_TRY(d_scr.alloc((size_t)sea_wb_scratch_bytes(total, 1)));
+    HIP_TRY(hipMemcpy(d_in.p, in, (size_t)n * sizeof(short), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_meta.p, meta, sizeof meta, hipMemcpyHostToDevice));
+    if (sea_wb_denoise_batch(d_in.p, d_out.p, nullptr, d_meta.p, d_meta.p + 1, nullptr, nullptr, nullptr, nullptr, nullptr, d_scr.p, total, 1,
+                             nullptr))
+        return 1;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out_lp, d_out.p, (size_t)nfr * SEA_HOP * sizeof(short), hipMemcpyDeviceToHost));
     return 0;
 }
 

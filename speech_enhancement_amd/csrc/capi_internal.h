@@ -25,6 +25,7 @@ struct DeviceCtx {
     sea_cc_tables *cc = nullptr;
     sea_gt_tables *gt = nullptr;
     sea_ns16k_tables *ns16 = nullptr;
+    sea_wb_tables *wb = nullptr;
     int n_cu = 256;
 };
 

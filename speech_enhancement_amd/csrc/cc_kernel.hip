@@ -179,16 +179,8 @@ namespace {
 constexpr int kCcT = 16; /* frames per tile of compceps_kernel (afe_ceps_kernel: kAfeT) */
 
 /* (float)log((double)v) for a positive normal float v, as CompCeps.c:423 / :511 take it.  The library's double log
- * costs ~150 instructions; the kernels' own table-driven one (ns_core.h, ns_ln: within ~1.1 ulp) gives the same float
- * unless the double lands within a few ulps of a float ROUNDING BOUNDARY -- there (probability ~2^-27 per call) the
- * logarithm is redone in double-double arithmetic and rounded once, exactly like the two NoiseSup sites
- * (ns_near_float_boundary; window 4 ulps: ours 1.1 + glibc's 0.52, doubled). */
-__device__ __forceinline__ float cc_logf(float v)
-{
-    const double l = ns_ln<false>((double)v);
-    if (__builtin_expect(ns_near_float_boundary(l, 4), 0)) return (float)ns_ln_cr((double)v);
-    return (float)l;
-}
+ * costs ~150 instructions; the kernels' own table-driven one with its rounding-boundary guard (ns_core.h, ns_logf) */
+__device__ __forceinline__ float cc_logf(float v) { return ns_logf(v); }
 
 template <bool SHARED, int T = kCcT>
 struct CcGeom {
@@ -275,9 +267,22 @@ extern "C" int sea_cc_waves(unsigned *out, int n) { return hipMemcpyFromSymbol(o
 #define CC_CK(k)
 #endif
 
-/* the staged tile -> nv rows of 14 coefficients at dst */
-template <bool SHARED, int T = kCcT>
-__device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileConst &C, int nv, float *dst, int lane)
+/* the wideband mode's additions to a tile (cc_tile<.., WB = true>) */
+struct __attribute__((aligned(16))) CcWbLds {
+    float dec[kCcT][4];               /* GetBandsForDecoding16k's three sums per frame */
+    float fbx[kCcT][4];               /* log band energies 23..25 (the frame's row of fb has 24 columns) */
+    float dct26T[SEA_WB_NCHAN * 16];
+};
+
+/* the staged tile -> nv rows of 14 coefficients at dst.
+ * WB: the wideband mode (CompCeps.c:392-402, :464-479, :488-530).  X = the additions' LDS; hpRows / codeRows = the tile's first
+ * frame's rows of high-band energies (after the spectral subtraction) and code values: cepstral frame j of an utterance is
+ * computed after NoiseSup output j + 2 and reads the heads of the three-deep queues hpBands / bufferCodeForBands16k, the
+ * entries of output j (NoiseSup.c:1418-1428).  logE is taken after CorrectEnergy, not before. */
+template <bool SHARED, int T = kCcT, bool WB = false>
+__device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileConst &C, int nv, float *dst, int lane,
+                                        CcWbLds *X = nullptr, const float *hpRows = nullptr, const float *codeRows = nullptr,
+                                        const sea_wb_tables *wbt = nullptr)
 {
     constexpr int FS = CcGeom<SHARED, T>::FS;
     /* logE (CompCeps.c:413-423): lane f sums the squares of frame f in sample order */
@@ -299,7 +304,8 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
                 for (int x = 1; x < 201; ++x) { const float v = p[x]; acc += v * v; }
             }
         }
-        logE = (acc < C.floorE) ? (float)-50.0 : cc_logf(acc);
+        if (WB) logE = acc;
+        else logE = (acc < C.floorE) ? (float)-50.0 : cc_logf(acc);
     }
     CC_CK(1);
     const int npair = (nv + 1) >> 1;
@@ -335,6 +341,16 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
             if (pl) rowAB[128] = power(o[2], 0.0f); /* bin 128 */
         }
         wave_sync();
+        if (WB && lane < 6) { /* GetBandsForDecoding16k (16kHzProcessing.c:317-336) from the power spectrum, before the mel pass */
+            const int hh = lane / 3, b = lane - 3 * hh;
+            if (2 * pr + hh < nv) {
+                const float *row = &L.pw[hh][0];
+                const int b0 = b == 0 ? 66 : (b == 1 ? 78 : 98), b1 = b == 0 ? 77 : (b == 1 ? 97 : 129);
+                float sum = 0.0f;
+                for (int i = b0; i < b1; ++i) sum += row[i];
+                X->dec[2 * pr + hh][b] = sum * 0.5f; /* /= 2.0 */
+            }
+        }
         /* 23 mel triangles (DoMelFB, MelProc.c:82-104): lane = one (frame, band) of the pair, dealt so that the aligned
          * pairs the lanes of a group read lie on different banks (round 4: 3-way conflicts on every tap before) */
         if (C.melFb >= 0 && 2 * pr + (C.melFb >= 24 ? 1 : 0) < nv) {
@@ -359,12 +375,55 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
     }
     wave_sync();
     CC_CK(3);
+    if (WB) { /* lane = frame: the high bands join (the promotions are the reference's: float unless a double constant enters) */
+        if (lane < nv) {
+            const int f = lane;
+            const float *code = codeRows + f * 9, *hpr = hpRows + f * 3;
+            const float cw[3] = {(float)0.1, (float)0.2, (float)0.7}; /* codeWeights, CompCeps.c:475-477 */
+            float aux[3], hb[3], fbv[3];
+            for (int j = 0; j < 3; ++j) { /* :468-473 */
+                const float v = X->dec[f][j];
+                aux[j] = (v > C.floorFB) ? cc_logf(v) : (float)-10.0;
+            }
+            for (int i = 0; i < 3; ++i) { /* DecodeBands16k, then the coded bands' pre-emphasis correction (:503-504) */
+                float sum = 0.0f;
+                for (int j = 0; j < 3; ++j) sum += cw[j] * (aux[j] - code[3 * i + j]);
+                hb[i] = sum + wbt->preemLog;
+            }
+            for (int i = 0; i < 3; ++i) { /* the subtracted bands (:497-498), log with floor (:509-513) */
+                const float v = (float)((1.0 + 0.90) * (double)hpr[i]);
+                fbv[i] = (v < C.floorFB) ? (float)-10.0 : cc_logf(v);
+            }
+            const float percCoded = (float)0.7; /* MergeSSandCoded, 16kHzProcessing.c:106-125 */
+            for (int i = 0; i < 3; ++i) fbv[i] = (float)((double)(percCoded * hb[i]) + (1.0 - (double)percCoded) * (double)fbv[i]);
+            float f22 = L.fb[f][SEA_CC_NCHAN - 1];
+            const float avg = (float)(0.5 * (double)f22 + 0.5 * (double)fbv[0]);
+            f22 = (float)(0.6 * (double)f22 + 0.4 * (double)avg);
+            fbv[0] = (float)(0.6 * (double)fbv[0] + 0.4 * (double)avg);
+            L.fb[f][SEA_CC_NCHAN - 1] = f22;
+            float energyHP = 0.0f; /* CorrectEnergy, :145-158 */
+            for (int i = 0; i < 3; ++i) {
+                X->fbx[f][i] = fbv[i];
+                energyHP = (float)((double)energyHP + exp((double)(fbv[i] - wbt->preemLogF)));
+            }
+            logE += energyHP;
+            logE = (logE < C.floorE) ? (float)-50.0 : cc_logf(logE); /* CompCeps.c:526-529 */
+        }
+        wave_sync();
+    }
     /* DCT (:203-227): lane = (frame, coefficient) flattened; c = 12 is c0, logE goes to c = 13 */
     for (int idx = lane; idx < nv * 13; idx += kLanes) {
         const int f = idx / 13, c = idx - f * 13;
         float acc = 0.0f;
+        if (WB) {
 #pragma unroll
-        for (int j = 0; j < SEA_CC_NCHAN; ++j) acc += L.fb[f][j] * L.dctT[j * 16 + c];
+            for (int j = 0; j < SEA_CC_NCHAN; ++j) acc += L.fb[f][j] * X->dct26T[j * 16 + c];
+#pragma unroll
+            for (int j = 0; j < SEA_WB_NHP; ++j) acc += X->fbx[f][j] * X->dct26T[(SEA_CC_NCHAN + j) * 16 + c];
+        } else {
+#pragma unroll
+            for (int j = 0; j < SEA_CC_NCHAN; ++j) acc += L.fb[f][j] * L.dctT[j * 16 + c];
+        }
         L.work[f * SEA_CC_NCEP + c] = acc;
     }
     if (lane < nv) L.work[lane * SEA_CC_NCEP + 13] = logE;
@@ -408,11 +467,12 @@ __global__ __launch_bounds__(64) void compceps_frames_kernel(const float *data20
     }
 }
 
-/* three waves per SIMD (LDS allows twelve waves per CU): 168 VGPRs, no spilled vector register; left to itself the allocator takes
- * 193 = two waves per SIMD */
-__global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
+namespace {
+/* WB: the wideband mode -- the float stream and first_out are at the 8 kHz rate (offsets[u] / 2, frames of 160 input samples) */
+template <bool WB>
+__device__ __forceinline__ void compceps_body(const CepsArgs &a, CcTileLds<true> &L, CcWbLds *X = nullptr, const float *hpRows = nullptr,
+                                              const float *codeRows = nullptr, const sea_wb_tables *wbt = nullptr)
 {
-    __shared__ CcTileLds<true> L;
     const int lane = threadIdx.x;
 #ifdef SEA_CC_TIMING
     if (lane == 0 && blockIdx.x < 16384) {
@@ -423,6 +483,10 @@ __global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
 #endif
     CcTileConst C;
     load_cc_tile_const<true>(C, L, a.tables, lane);
+    if (WB) {
+        for (int i = lane; i < SEA_WB_NCHAN * 16; i += kLanes) X->dct26T[i] = wbt->dct26T[i >> 4][i & 15];
+        wave_sync();
+    }
     /* tile slots: utterance u owns slots [ceps_cum[u] / T + u, ceps_cum[u+1] / T + u + 1), at least
      * ceil(capacity / T) of them; slot k of an utterance covers its cepstral frames kT .. kT + T - 1 */
     const long long nslot = a.ceps_cum[a.n_utt] / kCcT + a.n_utt;
@@ -437,7 +501,7 @@ __global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
         const long long j0 = (s - (c0 / kCcT + u)) * kCcT;
         if (j0 >= cap) continue; /* spare slot */
         const int f0 = a.first_out[u];
-        const long long nfr = a.lengths[u] / SEA_HOP;
+        const long long nfr = a.lengths[u] / (WB ? SEA_WB_HOP : SEA_HOP);
         const long long nout = (f0 >= 0) ? nfr - f0 : 0;
         const long long nceps = (nout >= 3) ? nout - 2 : 0;
         if (j0 == 0 && lane == 0 && a.n_ceps) a.n_ceps[u] = (int)nceps;
@@ -452,7 +516,7 @@ __global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
             CC_CK_START;
             /* span word x = Data[x-1] of frame j0: the float NoiseSup stream from sample 80 (f0 + j0) - 1 on;
              * Data[-1] of the utterance's very first cepstral frame is the zero before the first output */
-            const float *cur0 = a.den_f32 + a.offsets[u] + (f0 + j0) * SEA_HOP;
+            const float *cur0 = a.den_f32 + (WB ? a.offsets[u] / 2 : a.offsets[u]) + (f0 + j0) * SEA_HOP;
             const int nword = SEA_HOP * (nv - 1) + SEA_WIN + 1;
             /* all of the tile's words are requested before the first is stored: written as a load-store loop the
              * compiler waits for each of the 22 requests in turn -- ~22 HBM latencies per tile, most of the kernel's time */
@@ -479,13 +543,34 @@ __global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
 #ifdef SEA_CC_TIMING
             if (blockIdx.x == 0 && lane == 0) g_cc_ck[7] += 1;
 #endif
-            cc_tile<true>(L, C, nv, dst, lane);
+            if (WB) {
+                const long long row = (a.offsets[u] + SEA_WB_HOP - 1) / SEA_WB_HOP + f0 + j0; /* sea_kernels.h, WbHbArgs */
+                cc_tile<true, kCcT, true>(L, C, nv, dst, lane, X, hpRows + row * 3, codeRows + row * 9, wbt);
+            } else
+                cc_tile<true>(L, C, nv, dst, lane);
         }
         for (int idx = nv * SEA_CC_NCEP + lane; idx < nrow * SEA_CC_NCEP; idx += kLanes) dst[idx] = 0.0f;
     }
 #ifdef SEA_CC_TIMING
     if (lane == 0 && blockIdx.x < 16384) g_cc_wave[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
+}
+} // namespace
+
+/* three waves per SIMD (LDS allows twelve waves per CU): 168 VGPRs, no spilled vector register; left to itself the allocator takes
+ * 193 = two waves per SIMD */
+__global__ __launch_bounds__(64, 3) void compceps_kernel(CepsArgs a)
+{
+    __shared__ CcTileLds<true> L;
+    compceps_body<false>(a, L);
+}
+
+/* the wideband mode's CompCeps on the outputs of sea_wb_denoise_batch */
+__global__ __launch_bounds__(64, 2) void compceps_wb_kernel(WbCepsArgs a)
+{
+    __shared__ CcTileLds<true> L;
+    __shared__ CcWbLds X;
+    compceps_body<true>(a.c, L, &X, a.hp_rows, a.code_rows, a.wb);
 }
 
 /* ==================================================================================================

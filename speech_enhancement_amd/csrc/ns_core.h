@@ -252,6 +252,17 @@ __device__ __forceinline__ double ns_ln_cr(double x)
     const NsDD l = ns_ln_dd(x);
     return l.hi + l.lo;
 }
+/* (float)log((double)v) for a positive normal float v, as the reference takes it wherever it rounds a bare log to float
+ * (CompCeps.c:423, :511; the wideband mode's NoiseSup.c:1231, :1321 and 16kHzProcessing.c:422).  The lean log gives the same
+ * float unless the double lands within a few ulps of a float ROUNDING BOUNDARY -- there (probability ~2^-27 per call) the
+ * logarithm is redone in double-double arithmetic and rounded once, exactly like the two NoiseSup sites below
+ * (window 4 ulps: ours 1.1 + glibc's 0.52, doubled). */
+__device__ __forceinline__ float ns_logf(float v)
+{
+    const double l = ns_ln<false>((double)v);
+    if (__builtin_expect(ns_near_float_boundary(l, 4), 0)) return (float)ns_ln_cr((double)v);
+    return (float)l;
+}
 /* log10 x as glibc computes it (sysdeps/ieee754/dbl-64/e_log10.c, the fdlibm formula) with the correctly
  * rounded log inside; x positive and normal */
 __device__ __forceinline__ double ns_log10_slow(double x)

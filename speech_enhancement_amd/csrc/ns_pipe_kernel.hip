@@ -206,8 +206,12 @@ __device__ __forceinline__ void load_back_const(NsConst &C, const sea_ns_tables 
     C.eps = t->eps;
 }
 
-template <bool FD, bool ADDR_LDS, bool SLICES = false>
-__device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_LDS, FD> &L)
+/* WB: the wideband mode's low-band frame loop -- frames of 80 FLOATS (the QMF low band, wbIn, at offsets[u] / 2) instead of
+ * int16 ones, lengths counted in 16 kHz samples, and instead of the zero-frame gate the onset the QMF kernel found on the
+ * raw input (wbOnset): DoAdvProcess gates on the 160 raw samples, before the split (ParmInterface.c:244-262). */
+template <bool FD, bool ADDR_LDS, bool SLICES = false, bool WB = false>
+__device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_LDS, FD> &L, const float *wbIn = nullptr,
+                                             const int *wbOnset = nullptr)
 {
     const int lane = threadIdx.x & 63;
     const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -223,8 +227,8 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         else if (row == 1) __builtin_amdgcn_s_setprio(2);
         else if (row == 2) __builtin_amdgcn_s_setprio(1);
     }
-    const long long off = a.offsets[u];
-    const long long nfr = a.lengths[u] / SEA_HOP;
+    const long long off = WB ? a.offsets[u] / 2 : a.offsets[u];
+    const long long nfr = a.lengths[u] / (WB ? SEA_WB_HOP : SEA_HOP);
     /* the batch's longest utterance is block 0's (the launch order is longest first; any other order only makes the rule less sharp) */
     const long long longestFr = lrpt ? a.lengths[a.order[0]] / SEA_HOP : 0;
     const float lrptScale = (float)kPrioLevels / (float)(longestFr > 0 ? longestFr : 1);
@@ -287,7 +291,15 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
 #pragma unroll
         for (int k = 0; k < 8; ++k) win8[k] = a.tables->win8[k][lane];
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
-        uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
+        const float2 *inf2 = reinterpret_cast<const float2 *>(wbIn + off);
+        uint32_t nextw = (!WB && lane < 40 && nfr > 0) ? in32[lane] : 0u;
+        float2 nextv = make_float2(0.0f, 0.0f);
+        long long wbFirst = nfr; /* first frame that runs */
+        if (WB) {
+            const int o = wbOnset[u];
+            if ((long long)o < nfr) wbFirst = o;
+            if (lane < 40 && nfr > 0) nextv = inf2[lane];
+        }
         int tick = resume ? __float_as_int(blob[kBlobScal + 0]) : 0; /* frames seen since (and including) the first non-zero one */
         int onset = (int)nfr;
         /* The intake of a frame (zero-frame gate, int16 -> float, store into its slot of the stage-0 buffer)
@@ -304,14 +316,19 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             int ln = lane;
             if (ADDR_LDS) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
             const uint32_t w = nextw;
-            if (f + 1 < nfr && ln < 40) nextw = in32[(f + 1) * 40 + ln];
-            const bool any = __ballot(w != 0u) != 0ull;
+            const float2 v = nextv;
+            if (WB) {
+                if (f + 1 < nfr && ln < 40) nextv = inf2[(f + 1) * 40 + ln];
+            } else {
+                if (f + 1 < nfr && ln < 40) nextw = in32[(f + 1) * 40 + ln];
+            }
+            const bool any = WB ? f >= wbFirst : __ballot(w != 0u) != 0ull;
             vCur = 0;
             if (any || tick > 0) {
                 vCur = 1;
                 if (FD && tick == 0) onset = (int)f;
                 tick++;
-                const float x0 = (float)(short)(w & 0xFFFFu), x1 = (float)(short)(w >> 16);
+                const float x0 = WB ? v.x : (float)(short)(w & 0xFFFFu), x1 = WB ? v.y : (float)(short)(w >> 16);
                 if (ln < 40) slot_store(L.circ[0], tick, ln, x0, x1);
             }
             tCur = tick;
@@ -376,6 +393,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             NS_T_END;
         }
         if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset;
+        if (WB && a.onset_out && lane == 0) a.onset_out[u] = (int)wbFirst;
         if (blob && lane == 0) blob[kBlobScal + 0] = __int_as_float(tick);
         NS_T_FLUSH(0);
 #ifdef SEA_NS_TIMING
@@ -681,6 +699,14 @@ __global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_fd_kernel(
 {
     __shared__ p4::PipeLds<false, true> L;
     p4::ns_pipe_body<true, false>(a, L);
+}
+
+/* the wideband mode's low-band frame loop (float intake, onset instead of the gate): a kernel of its own so that the int16
+ * forms come out of the compiler as they were.  The form with the address tables in VGPRs: it needs no scratch. */
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_kernel(NsWbArgs a)
+{
+    __shared__ p4::PipeLds<false> L;
+    p4::ns_pipe_body<false, false, false, true>(a.b, L, a.in_f32, a.onset);
 }
 
 } // namespace sea

@@ -40,6 +40,44 @@ struct NsBatchArgs {
  * [8 frame energies][8 denSigSE1 sums][8 speech-flag words][40 scalars] */
 constexpr int kNsPipeStateFloats = 2 * 640 + 12 * 64 + 3 * 8 + 40;
 
+/* The ETSI wideband (16 kHz) mode (wb_kernel.hip; include/sea_mi355x.h, sea_wb_denoise_batch).  Utterance u occupies
+ * samples [offsets[u], offsets[u] + lengths[u]) of `in` at 16 kHz; everything at the 8 kHz rate (the two QMF streams,
+ * the low-band outputs) sits at offsets[u] / 2, frame f of 80 samples at offsets[u] / 2 + 80 f. */
+struct WbQmfArgs {
+    const int16_t *in;
+    const long long *offsets;
+    const long long *lengths;
+    float *lp, *hp;            /* QMF low band / high band shifted down to 0-4 kHz */
+    int *onset;                /* per utterance, preset to INT_MAX: atomicMin of the indices of the non-zero frames */
+    const sea_wb_tables *tables;
+    int n_utt;
+};
+__global__ void wb_qmf_kernel(WbQmfArgs a); /* blockIdx.x = utterance, blockIdx.y strides over its frames */
+constexpr int kWbQmfThreads = 128;
+/* the low-band frame loop: a pipelined NoiseSup form with a FLOAT intake (the QMF low band) and no zero-frame gate --
+ * frames before onset[u] advance nothing, every later one runs (ns_pipe_kernel.hip) */
+struct NsWbArgs {
+    NsBatchArgs b;             /* in unused; out / out_f32 / first_out / onset_out as for the int16 forms, at the 8 kHz rate */
+    const float *in_f32;       /* WbQmfArgs::lp */
+    const int *onset;          /* WbQmfArgs::onset (values beyond the frame count: no non-zero frame) */
+};
+__global__ void ns_denoise_pipe_wb_kernel(NsWbArgs a);     /* transform address tables in VGPRs, four workgroups per CU */
+/* the high band's features per output frame: rows of 3 band energies and of 9 code values; the row of frame f of utterance
+ * u is ceil(offsets[u] / 160) + f */
+struct WbHbArgs {
+    const float *lp, *hp;      /* the QMF streams */
+    const long long *offsets;
+    const long long *lengths;
+    const int *onset;          /* WbQmfArgs::onset */
+    float *hp_rows;            /* [rows][3] */
+    float *code_rows;          /* [rows][9] */
+    const sea_ns_tables *ns;   /* transform schedule and Hanning window */
+    const sea_wb_tables *wb;
+    int n_utt;
+};
+__global__ void wb_hb_kernel(WbHbArgs a);      /* blockIdx.x = utterance, blockIdx.y strides over its output frames; one wave */
+__global__ void wb_specsub_kernel(WbHbArgs a); /* one lane per utterance */
+
 /* B independent streams, nframes frames of 80 floats each, state blobs of kNsStateFloats floats */
 constexpr int kNsStateFloats = 2 * 320 + 12 * 64 + 32;
 struct NsStreamArgs {
@@ -81,6 +119,14 @@ struct CepsArgs {
     const sea_cc_tables *tables;
     int n_utt;
 };
+
+/* the wideband CompCeps: the 8 kHz one on the low band's float stream + the decoded / subtracted high bands, 26-band DCT */
+struct WbCepsArgs {
+    CepsArgs c;                /* den_f32 at offsets[u] / 2; lengths in 16 kHz samples; first_out in frames of 160 */
+    const float *hp_rows, *code_rows;
+    const sea_wb_tables *wb;
+};
+__global__ void compceps_wb_kernel(WbCepsArgs a);
 
 /* WaveProc -> CompCeps -> PostProc -> VAD (+ flush) on the float NoiseSup stream */
 struct AfeArgs {

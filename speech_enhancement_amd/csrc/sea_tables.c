@@ -485,6 +485,73 @@ static float phons_at(float hz)
     return (float)(4.2 + a * (60.0 - t) / (1.0 + b * (60.0 - t)));
 }
 
+/* ---- wideband mode: the QMF taps (16kHzProcessing.c:559-605).  ES 202 050 gives the low-pass filter as 118 integers over
+ * 2^23, symmetric about its middle; kept here as the 59 distinct numerators, taps 0..58.  Every quotient is exact in a
+ * float (|numerator| < 2^24).  The high-pass filter is the low-pass one reversed with alternating sign (:595-599). */
+static const int kQmfNum[SEA_WB_QMF / 2] = {
+    1584, 805, -4192, -8985, -5987, 2583, 4657, -3035, -7004, 1542, 8969, 567, -10924, -3757, 12320,
+    7951, -12793, -13048, 11923, 18793, -9331, -24802, 4694, 30570, 2233, -35439, -11526, 38680, 23114, -39474,
+    -36701, 36999, 51797, -30419, -67658, 18962, 83318, -1927, -97566, -21284, 108971, 51215, -115837, -88430, 116130,
+    133716, -107253, -188497, 85497, 255795, -44643, -342699, -28185, 468096, 167799, -696809, -519818, 1446093, 3562497};
+
+void sea_build_wb_tables(sea_wb_tables *t)
+{
+    int i, aux = 1;
+    memset(t, 0, sizeof *t);
+    for (i = 0; i < SEA_WB_QMF; i++) {
+        const int n = kQmfNum[i < SEA_WB_QMF / 2 ? i : SEA_WB_QMF - 1 - i];
+        t->qmfLp[i] = (float)((double)n / (double)(float)0x00800000);
+    }
+    for (i = 0; i < SEA_WB_QMF; i++) { /* :596-599 */
+        t->qmfHp[SEA_WB_QMF - 1 - i] = (float)aux * t->qmfLp[i];
+        aux *= -1;
+    }
+    { /* InitMelFBwindows (.., 80.0, 8000, 128, 5, 0), MelProc.c:128-230: inner triangles i = 1..3 */
+        const float fs = 8000.0f;
+        const float lo = hz_to_mel(80.0f), hi = hz_to_mel(fs / 2);
+        int c[5], j, n;
+        for (i = 0; i < 5; i++) c[i] = mel_bin(lo, hi, i, 4, 128, fs);
+        for (i = 1; i <= SEA_WB_NHP; i++) {
+            const int rise = c[i] - c[i - 1], fall = c[i + 1] - c[i];
+            float *w = t->hpMelW[i - 1];
+            if (rise + fall - 1 > SEA_WB_MELTAPS || c[i + 1] > SEA_NSPEC - 1) abort();
+            n = 0;
+            for (j = 0; j < rise; j++) w[n++] = (float)(j + 1) / (float)rise;
+            for (j = 0; j < fall - 1; j++) w[n++] = (float)(1.0 - (j + 1) / (float)fall);
+            t->hpMelStart[i - 1] = c[i - 1] + 1;
+            t->hpMelLen[i - 1] = n;
+        }
+    }
+    { /* InitDCTMatrix (13, 26): CompCeps.c:153-173 */
+        int j;
+        for (j = 0; j < SEA_WB_NCHAN; j++) {
+            for (i = 1; i <= 12; i++) t->dct26T[j][i - 1] = (float)cos(kPi * (float)i / (float)SEA_WB_NCHAN * ((float)j + 0.5));
+            t->dct26T[j][12] = 1.0f;
+        }
+    }
+    t->floorSpec = (float)exp((double)-10.0);
+    t->floorE = (float)exp((double)-50.0);
+    t->logMin16k = (float)log((double)0.001);
+    t->preemLog = (float)log(1.0 + 0.90);
+    t->preemLogF = (float)log(1.0 + (float)0.90);
+}
+
+void sea_wb_plain_tables(float *qmfLp118, float *qmfHp118, int *hpMelStart3, int *hpMelLen3, float *hpMelW3x64, float *dct12x26)
+{
+    static sea_wb_tables t; /* too large for some callers' stacks */
+    int i, j;
+    sea_build_wb_tables(&t);
+    memcpy(qmfLp118, t.qmfLp, sizeof t.qmfLp);
+    memcpy(qmfHp118, t.qmfHp, sizeof t.qmfHp);
+    for (i = 0; i < SEA_WB_NHP; i++) {
+        hpMelStart3[i] = t.hpMelStart[i];
+        hpMelLen3[i] = t.hpMelLen[i];
+    }
+    memcpy(hpMelW3x64, t.hpMelW, sizeof t.hpMelW);
+    for (i = 0; i < 12; i++)
+        for (j = 0; j < SEA_WB_NCHAN; j++) dct12x26[i * SEA_WB_NCHAN + j] = t.dct26T[j][i];
+}
+
 void sea_build_gt_tables(sea_gt_tables *t)
 {
     const double kPiHW = 3.1415926535897932384626433832795; /* HuWang.h:7 */

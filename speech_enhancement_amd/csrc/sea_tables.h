@@ -197,6 +197,35 @@ void sea_ns16k_fft_host(float *x512); /* the table-driven transform on the host 
 void sea_ns16k_pipe_fft_host(float *x512); /* the same through the pipelined kernel's tables (tests) */
 void sea_ns16k_plain_tables(float *sigWindow480, float *irWindow17, int *gammaStart25, float *gamma25x128, float *idct25x25);
 
+/* ---- the ETSI wideband (16 kHz) mode: the QMF pair that splits a frame of 160 samples into a 0-4 kHz and a 4-8 kHz
+ * half (etsi/cpp/16kHzProcessing.c:559-605, :711-774) -------------------------------------------------------------- */
+enum {
+    SEA_WB_HOP = 160,      /* input samples per frame: 2 * NS_FRAME_SHIFT  etsi/cpp/ParmInterface.c:188-189 */
+    SEA_WB_QMF = 118,      /* LENGTH_QMF                                   etsi/cpp/16kHzProcessing.c:557 */
+    SEA_WB_NHP = 3,        /* HP16k_MEL_USED                               etsi/cpp/16kHzProcExports.h:20 */
+    SEA_WB_MELTAPS = 64,   /* room for the widest high-band triangle (asserted at build) */
+    SEA_WB_NCHAN = 26      /* CC_NUM_CHANNELS_WI8 + HP16k_MEL_USED         etsi/cpp/CompCeps.c:280 */
+};
+typedef struct {
+    float qmfLp[SEA_WB_QMF];                      /* the standard's integer numerators over 2^23, symmetric */
+    float qmfHp[SEA_WB_QMF];                      /* qmfHp[117 - i] = (-1)^i qmfLp[i], i.e. qmfHp[j] = (-1)^(j+1) qmfLp[j] */
+    /* the high band's mel filter: bands 1..3 of the five un-normalised triangles InitMelFBwindows (.., 80.0, 8000, 128, 5, 0)
+     * lays over the 65-bin PSD (16kHzProcessing.c:242-247; the two half bands at the ends are not used, NoiseSup.c:1314-1316) */
+    int hpMelStart[4], hpMelLen[4];
+    float hpMelW[SEA_WB_NHP][SEA_WB_MELTAPS];
+    /* InitDCTMatrix (13, 23 + 3) (CompCeps.c:280) as [j][c]: c = 0..11 the rows of c1..c12, c = 12 all ones (c0), 13..15 zero */
+    float dct26T[SEA_WB_NCHAN][16];
+    float floorSpec;                              /* NS_SPEC_FLOOR = NS_EPS_16K = EnergyFloor_FB = (float)exp(-10.0) */
+    float floorE;                                 /* (float)exp(-50.0) */
+    float logMin16k;                              /* (float)log(0.001): the high-band VAD's frame energy floor, 16kHzProcessing.c:424 */
+    float preemLog;                               /* (float)log(1.0 + 0.90), CompCeps.c:489 */
+    float preemLogF;                              /* (float)log(1.0 + (float)0.90), CorrectEnergy's (16kHzProcessing.c:150) */
+    float pad[3];
+} sea_wb_tables;
+void sea_build_wb_tables(sea_wb_tables *t);
+/* plain tables for host-side checks */
+void sea_wb_plain_tables(float *qmfLp118, float *qmfHp118, int *hpMelStart3, int *hpMelLen3, float *hpMelW3x64, float *dct12x26);
+
 void sea_build_ns_tables(sea_ns_tables *t);
 void sea_build_cc_tables(sea_cc_tables *t);
 void sea_build_gt_tables(sea_gt_tables *t);

@@ -261,6 +261,87 @@ def ns_denoise_batch(batch, out=None, want_f32=False, use_order=True):
     return out, f32, first
 
 
+def wb_denoise_batch(batch, want_f32=False, want_hb=False, use_order=True):
+    """The ETSI wideband (16 kHz) mode for every utterance of the batch (frames of 160 samples): QMF split, NoiseSup on
+    the low band and (want_hb) the high band's features per output frame.  Everything returned is at the 8 kHz rate and
+    indexed by HALF the batch's offsets (frame f of utterance u at offsets[u] / 2 + 80 f; ``wb_split`` cuts it up); the
+    per-frame rows are indexed by ceil(offsets[u] / 160) + f (``wb_rows``).  Returns a dict: out (int16 low band), f32
+    (float low band or None), first_out / onset (int32 [n], in frames of 160), hp_rows [rows, 3] / code_rows [rows, 9] (or
+    None), qmf_lp / qmf_hp (the float QMF streams, views of the scratch buffer).  Asynchronous on the current stream."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = batch.data.device
+    half = (batch.total // 2 + 7) // 8 * 8
+    out = torch.zeros(half, dtype=torch.int16, device=dev)
+    f32 = torch.zeros(half, dtype=torch.float32, device=dev) if want_f32 else None
+    first = torch.full((batch.n_utt,), -1, dtype=torch.int32, device=dev)
+    onset = torch.zeros(batch.n_utt, dtype=torch.int32, device=dev)
+    rows = int(lib.sea_wb_rows(batch.total))
+    hp_rows = torch.zeros((rows, 3), dtype=torch.float32, device=dev) if want_hb else None
+    code_rows = torch.zeros((rows, 9), dtype=torch.float32, device=dev) if want_hb else None
+    nbytes = int(lib.sea_wb_scratch_bytes(batch.total, batch.n_utt))
+    assert nbytes >= 2 * half * 4
+    scratch = torch.zeros(nbytes // 4 + 4, dtype=torch.float32, device=dev)
+    rc = lib.sea_wb_denoise_batch(_dptr(batch.data), _dptr(out), _dptr(f32), _dptr(batch.offsets), _dptr(batch.lengths),
+                                  _dptr(batch.order) if use_order else None, _dptr(first), _dptr(onset), _dptr(hp_rows),
+                                  _dptr(code_rows), _dptr(scratch), batch.total, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_wb_denoise_batch")
+    return dict(out=out, f32=f32, first_out=first, onset=onset, hp_rows=hp_rows, code_rows=code_rows,
+                qmf_lp=scratch[:half], qmf_hp=scratch[half:2 * half])
+
+
+def wb_compceps_batch(batch, res):
+    """The wideband CompCeps on a wb_denoise_batch(.., want_f32=True, want_hb=True) result.  Returns (ceps float32
+    [total, 14], ceps_cum int64 [n+1] on host, n_ceps int32 [n] tensor)."""
+    torch = _torch()
+    lib = _lib.load()
+    cap = np.maximum(np.asarray(batch.host_lengths) // 160 - 6, 0).astype(np.int64)
+    cum = np.concatenate(([0], np.cumsum(cap))).astype(np.int64)
+    total = int(cum[-1])
+    dev = batch.data.device
+    ceps = torch.zeros((max(total, 1), 14), dtype=torch.float32, device=dev)
+    n_ceps = torch.zeros(batch.n_utt, dtype=torch.int32, device=dev)
+    d_cum = torch.from_numpy(cum).to(dev)
+    rc = lib.sea_wb_compceps_batch(_dptr(res["f32"]), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(res["first_out"]),
+                                   _dptr(res["hp_rows"]), _dptr(res["code_rows"]), _dptr(d_cum), total, _dptr(ceps),
+                                   _dptr(n_ceps), batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_wb_compceps_batch")
+    return ceps, cum, n_ceps
+
+
+def wb_split(batch, tensor):
+    """Cut an 8 kHz-rate result of wb_denoise_batch into per-utterance numpy arrays of 80 * (length // 160) samples."""
+    host = tensor.detach().cpu().numpy()
+    return [host[int(off) // 2:int(off) // 2 + int(L) // 160 * 80].copy()
+            for off, L in zip(batch.host_offsets, batch.host_lengths)]
+
+
+def wb_rows(batch, tensor):
+    """Cut a per-frame row result of wb_denoise_batch into per-utterance numpy arrays of length // 160 rows."""
+    host = tensor.detach().cpu().numpy()
+    return [host[(int(off) + 159) // 160:(int(off) + 159) // 160 + int(L) // 160].copy()
+            for off, L in zip(batch.host_offsets, batch.host_lengths)]
+
+
+def wb_denoise(x):
+    """One utterance at 16 kHz from host memory through the wideband mode: int16 low band, 80 * (len // 160) samples."""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.int16)
+    out = np.zeros(x.size // 160 * 80, np.int16)
+    _lib.check(lib.sea_wb_denoise(_np_ptr(x), x.size, _np_ptr(out)), "sea_wb_denoise")
+    return out
+
+
+def wb_tables():
+    """The wideband mode's tables as the library computed them (no GPU needed)."""
+    lib = _lib.load()
+    t = dict(qmfLp=np.zeros(118, np.float32), qmfHp=np.zeros(118, np.float32), hpMelStart=np.zeros(3, np.int32),
+             hpMelLen=np.zeros(3, np.int32), hpMelW=np.zeros((3, 64), np.float32), dct=np.zeros((12, 26), np.float32))
+    keys = ("qmfLp", "qmfHp", "hpMelStart", "hpMelLen", "hpMelW", "dct")
+    _lib.check(lib.sea_wb_tables_host(*[_np_ptr(t[k]) for k in keys]), "sea_wb_tables_host")
+    return t
+
+
 def compceps_batch(batch, den_f32, first_out):
     """CompCeps on the float NoiseSup stream.  Returns (ceps float32 [total,14], ceps_cum int64
     [n+1] on host, n_ceps int32[n] tensor)."""

@@ -4,6 +4,7 @@ the CompCeps front-end) on one MI355X.  bench.py stays the headline (NoiseSup, c
 script prints one JSON line per workload with the same roofline convention.
 
     python tools/bench_extra.py [--utts 1024] [--steps 5] [--what resynth,ibm,ceps,rfft]
+    python tools/bench_extra.py --what wb --steps 7      # the ETSI wideband (16 kHz) mode, opt-in
 """
 import argparse
 import json
@@ -225,6 +226,69 @@ def main():
             print(json.dumps({"metric": f"resynth hop-frames/sec through the HOST-buffer entry point (PCIe inclusive), {'IBM' if binary else 'ratio mask'}",
                               "value": hops / wall, "unit": "hop-frames/s", "ms_per_step": wall * 1e3,
                               "config": {"workload": f"sea_resynth_utterances on {n} host utterances, {hops} mask rows"}}), flush=True)
+
+    if "wb" in what:
+        # the ETSI wideband (16 kHz) mode: the corpus plus as many wideband signals of the same lengths (the corpus alone
+        # never moves the high band's VAD), QMF + low-band NoiseSup + high band, then the 26-band CompCeps; device events,
+        # warm-up discarded, MEDIAN of the steps
+        lib = sea.load()
+        lens = [int(L) for L in batch.host_lengths]
+        host = batch.data.cpu().numpy()
+        utts = [host[o:o + l] for o, l in zip(batch.host_offsets, lens)] + [corpus.synth_wideband(u, L) for u, L in enumerate(lens)]
+        wb = sea.PackedBatch.from_arrays(utts, dev)
+        n, total = wb.n_utt, wb.total
+        half = (total // 2 + 7) // 8 * 8
+        out = torch.zeros(half, dtype=torch.int16, device=dev)
+        f32 = torch.zeros(half, dtype=torch.float32, device=dev)
+        first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        onset = torch.zeros(n, dtype=torch.int32, device=dev)
+        rows = int(lib.sea_wb_rows(total))
+        hpr = torch.zeros((rows, 3), dtype=torch.float32, device=dev)
+        code = torch.zeros((rows, 9), dtype=torch.float32, device=dev)
+        scratch = torch.zeros(int(lib.sea_wb_scratch_bytes(total, n)) // 4 + 4, dtype=torch.float32, device=dev)
+        cap = np.maximum(np.asarray(wb.host_lengths) // 160 - 6, 0).astype(np.int64)
+        cum = np.concatenate(([0], np.cumsum(cap))).astype(np.int64)
+        tc = int(cum[-1])
+        ceps = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
+        ncep = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_cum = torch.from_numpy(cum).to(dev)
+        P = lambda t: t.data_ptr()
+        st = torch.cuda.current_stream().cuda_stream
+
+        def denoise():
+            assert lib.sea_wb_denoise_batch(P(wb.data), P(out), P(f32), P(wb.offsets), P(wb.lengths), P(wb.order), P(first),
+                                            P(onset), P(hpr), P(code), P(scratch), total, n, st) == 0, lib.sea_last_error()
+
+        def cepstra():
+            assert lib.sea_wb_compceps_batch(P(f32), P(wb.offsets), P(wb.lengths), P(first), P(hpr), P(code), P(d_cum), tc,
+                                             P(ceps), P(ncep), n, st) == 0, lib.sea_last_error()
+
+        def median_ms(fn, steps):
+            fn()
+            torch.cuda.synchronize()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+            for a, b in ev:
+                a.record()
+                fn()
+                b.record()
+            torch.cuda.synchronize()
+            t = sorted(a.elapsed_time(b) for a, b in ev)
+            return t[len(t) // 2], t
+        steps = max(args.steps, 5)
+        m1, t1 = median_ms(denoise, steps)
+        m2, t2 = median_ms(cepstra, steps)
+        frames = int(np.sum(np.asarray(wb.host_lengths) // 160))
+        print(json.dumps({"metric": "ETSI wideband mode frames/sec (160-sample frames: QMF + low-band NoiseSup + high band + 26-band CompCeps)",
+                          "value": frames / ((m1 + m2) / 1e3), "unit": "frames/s", "ms_per_step": m1 + m2,
+                          "config": {"workload": f"{n} utterances at 16 kHz: the {args.utts}-utterance corpus + as many wideband signals of "
+                                                 f"the same lengths, {frames} frames, {int(ncep.sum().item())} cepstral frames; median of {steps}",
+                                     "wb_denoise_batch_ms": m1, "wb_compceps_batch_ms": m2,
+                                     "wb_denoise_batch_ms_sorted": [round(v, 3) for v in t1],
+                                     "wb_compceps_batch_ms_sorted": [round(v, 3) for v in t2]},
+                          "kernels": "sea::wb_qmf_kernel + sea::ns_denoise_pipe_wb_kernel + sea::wb_hb_kernel + sea::wb_specsub_kernel + "
+                                     "sea::compceps_wb_kernel",
+                          "algorithmic_bytes_per_frame": {"wb_qmf_kernel": 160 * 2 + 2 * 80 * 4, "wb_hb_kernel": 2 * 80 * 4 + 12 * 4}}),
+              flush=True)
 
     if "rfft" in what:
         n = 1 << 18
