@@ -17,16 +17,20 @@
  *            denSigSE1 of frame i-3, DC-offset recurrence + cast + store of frame i-7
  *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
- * iteration, read at the next); the two transform work areas alternate between FA and FB.
+ * iteration, read at the next; the stage-1 PSD, which N1 and then G1 read in place, in a ring of four); the two
+ * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
+ * and whether they produce output follow from ONE number per utterance, the index of its first non-zero frame, which
+ * FA publishes once (kNoOnset / onset_poll below).
  *
  * Round 4: this is the form for up to FOUR utterances per CU, configs[1] included (capi.hip::ns_pick_form).  Up to three per CU
- * ns_denoise_pipe6_kernel (80 VGPRs, the lighter helper wave: LIGHT / DIFG1 of ns_pipe6_body); for the fourth ns_denoise_pipe6_dense_kernel, the same
+ * ns_denoise_pipe6_kernel (bound of 80 VGPRs, the lighter helper wave: LIGHT / DIFG1 of ns_pipe6_body); for the fourth ns_denoise_pipe6_dense_kernel, the same
  * body compiled for seven waves per SIMD -- with six, the dispatcher never found room for the fourth six-wave workgroup of a CU, which is
  * what rounds 1-3 measured as "the six-wave form loses at four per CU" (see the comment at the kernels below).  With more than one
  * utterance per CU the waves set their issue priority by the frames their utterance has left (prio_by_remaining, the rule of
  * ns_pipe_kernel.hip), and the wave -> role map (kDefaultPerm) puts B0 and S on the two oldest waves: among equal priorities a SIMD
  * issues its oldest wave first.  configs[1]: 1.91-1.95 ms = 420-427 M frames/s (four-wave form 2.08-2.13);
- * profiles/r04_ns_six_wave_dense.txt.
+ * profiles/r04_ns_six_wave_dense.txt.  With the bookkeeping taken off the per-frame stream: 1.85 ms = 442 M frames/s
+ * (profiles/r05_ns6_bookkeeping.txt).
  */
 #include "ns_core.h"
 
@@ -72,26 +76,45 @@ constexpr int kPrioLevels = 32;
  * NsBatchArgs::perm6 != 0 replaces it (sea_debug_ns6_perm, which accepts permutations of 0..5 only). */
 constexpr int kDefaultPerm = 0014352;
 
-struct __attribute__((aligned(16))) RecA { /* FA -> FB, S: what was pushed at this iteration */
-    int valid, tick;      /* stage 0, frame i */
-    int valid1, tick1;    /* stage 1, frame i-3 */
-};
-struct __attribute__((aligned(16))) RecPsd { /* FB -> B0 (stage 0) / N1 (stage 1) */
+/* Frame bookkeeping (valid / tick / produced of every frame) is a pure function of the frame index: the zero-frame gate
+ * (ParmInterface.c:244-251) has one degree of freedom per utterance, the index `onset` of the first non-zero frame.  From it on every
+ * frame f < nfr is valid with tick(f) = f - onset + 1, stage 0 runs from tick 3 (NoiseSup.c:1152) and stage 1 / the output from tick 5
+ * (NoiseSup.c:1178).  So the records between the roles carry data only; FA publishes the onset ONCE (Pipe6Lds::onset) and every role
+ * derives the flags of the frame it handles with scalar arithmetic on (f, onset, nfr).
+ *
+ * A reader keeps the onset in an SGPR.  While that is still kNoOnset it reads the LDS word once per beat (onset_poll); from the beat
+ * it sees a value on it never reads it again.  Why "not yet" may be taken for "invalid": a role at iteration i only handles frames
+ * f < i.  FA decides frame g at its own iteration g and writes the word there, before the barrier that ends iteration g; a reader at
+ * iteration i has passed the barriers of iterations 0 .. i-1, so it sees FA's write of every iteration g <= i-1.  Reading kNoOnset at
+ * beat i therefore means onset >= i > f: the frame is before the onset, i.e. invalid -- exactly what f >= onset gives with
+ * kNoOnset = INT_MAX.  (FA's write of iteration i itself may or may not be seen; both readings give the same flags for f < i.) */
+constexpr int kNoOnset = 0x7fffffff;
+constexpr long long kMaxFrames = 0x7fffffffLL - 16; /* frame indices, iteration counts and ticks stay below kNoOnset */
+__device__ __forceinline__ void onset_poll(int &onset, const int *word)
+{
+    if (onset == kNoOnset)
+        onset = __builtin_amdgcn_readfirstlane(__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+}
+/* tick of frame f (meaningful for f >= onset; unsigned so that kNoOnset wraps instead of overflowing -- callers only mask such a value) */
+__device__ __forceinline__ int tick_of(int f, int onset) { return (int)((unsigned)f - (unsigned)onset + 1u); }
+/* frame f exists and has tick >= k (k >= 1; f may be negative: onset >= 0) */
+__device__ __forceinline__ bool tick_ge(int f, int k, int onset, int nfr) { return f < nfr && f - (k - 1) >= onset; }
+
+constexpr int kP1Ring = 4; /* stage-1 PSD of frame f: written by FB at iteration f+4, read by N1 at f+5 and by G1 at f+6; slot f is
+                            * written again at iteration f+kP1Ring+4, which has to be >= f+7: three would do; four, for 272 B more LDS, makes the
+                            * slot index a mask (& 3) instead of a division by three */
+struct __attribute__((aligned(16))) RecPsd { /* FB -> B0 (stage 0) / N1, G1 (stage 1) */
     float psd[68];
-    int valid, tick, pad0, pad1;
 };
-struct __attribute__((aligned(16))) RecDen { /* B0 -> FA (valid / tick of the stage-1 frame), S (den) */
+struct __attribute__((aligned(16))) RecDen { /* B0 -> S */
     float den[68];
-    int valid, tick, pad0, pad1;
 };
 struct __attribute__((aligned(16))) RecN { /* N1 -> G1 */
-    float psd[68], P[68], noise[68];
+    float P[68], noise[68];
     float alfa;
-    int produced, tick, pad0;
 };
 struct __attribute__((aligned(16))) RecOut { /* G1 -> S */
     float out[80]; /* second-stage filter output before the DC-offset filter */
-    int produced, tick, pad0, pad1;
 };
 
 struct __attribute__((aligned(16))) Pipe6Lds {
@@ -100,12 +123,11 @@ struct __attribute__((aligned(16))) Pipe6Lds {
     BackLds back[2];                /* scratch of B0 and G1 */
     float ssq[80], sdif[80], sout[80], szero[4]; /* scratch of S */
     float frameEn[kSlots], denSum[kSlots];
-    int vadTodo[2];                 /* unused (initialised only), kept for the layout */
+    int onset;                      /* index of the first non-zero frame, kNoOnset until FA has met it */
     float frameEnLog[kSlots];       /* LIGHT: frameEn = 64 + sum of squares (S), frameEnLog = its log-energy (FA, one beat later) */
     int fdFlags[kSlots];
     float idctT[SEA_NMEL * 16];
-    RecA ra[2];
-    RecPsd p0[2], p1[2];
+    RecPsd p0[2], p1[kP1Ring];
     RecDen rd[2];
     RecN rn[2];
     RecOut ro[2];
@@ -154,18 +176,24 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
     const int role = ((a.perm6 ? a.perm6 : kDefaultPerm) >> (3 * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6))) & 7;
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
     const long long off = a.offsets[u];
-    const long long nfr = a.lengths[u] / SEA_HOP;
-    const long long niter = nfr + kDepth;
+    /* frame counts and counters are 32-bit and scalar: 2^31 frames would be 172 G samples, in and out 687 GB, more than the device's
+     * memory holds (a longer length is SILENTLY cut to kMaxFrames frames rather than wrapping: the lengths live in
+     * device memory, so the C entry points cannot refuse one without a synchronising copy; PackedBatch.layout, which has them on the
+     * host, refuses it).  Byte and sample offsets into the streams are still
+     * formed in 64 bits (a single utterance may exceed 2^31 samples). */
+    const long long nfr64 = a.lengths[u] / SEA_HOP;
+    const int nfr = __builtin_amdgcn_readfirstlane((int)(nfr64 < kMaxFrames ? nfr64 : kMaxFrames));
+    const int niter = nfr + kDepth;
     /* issue priority by remaining frames, the rule of the four-wave form (ns_pipe_kernel.hip): on whenever the
      * launch has more utterances than CUs to put them on and an order whose first entry is the longest */
     const bool lrpt = a.prio_row > 0 && a.order;
     const long long longestFr = lrpt ? a.lengths[a.order[0]] / SEA_HOP : 0;
     const float lrptScale = (float)kPrioLevels / (float)(longestFr > 0 ? longestFr : 1);
     const int lrptBias = lrpt ? (int)blockIdx.x / a.prio_row : 0; /* equal levels: the hardware prefers the oldest wave */
-    auto prio_by_remaining = [&](long long i) {
+    auto prio_by_remaining = [&](int i) {
         if (lrpt && (i & (kPrioStep - 1)) == 0) {
             const int L = __builtin_amdgcn_readfirstlane((int)((float)(nfr - i) * lrptScale)) + lrptBias;
-            const int pr = (L + (int)((i / kPrioStep) & (kPrioLevels / 4 - 1))) / (kPrioLevels / 4);
+            const int pr = (L + (int)(((unsigned)i / kPrioStep) & (kPrioLevels / 4 - 1))) / (kPrioLevels / 4);
             if (pr >= 3) __builtin_amdgcn_s_setprio(3);
             else if (pr == 2) __builtin_amdgcn_s_setprio(2);
             else if (pr == 1) __builtin_amdgcn_s_setprio(1);
@@ -183,14 +211,9 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
     }
     if (threadIdx.x < 2) {
         const int k = threadIdx.x;
-        L.vadTodo[k] = -1;
-        L.ra[k].valid = L.ra[k].valid1 = 0;
-        L.p0[k].valid = L.p1[k].valid = 0;
-        L.rd[k].valid = 0;
         L.rd[k].den[65] = L.rd[k].den[66] = L.rd[k].den[67] = 0.0f; /* read as zeros by S */
-        L.rn[k].produced = 0;
-        L.ro[k].produced = 0;
     }
+    if (threadIdx.x == 0) L.onset = kNoOnset;
     block_sync();
     NS6_T_DECL;
 
@@ -203,50 +226,34 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         for (int k = 0; k < 8; ++k) win8[k] = a.tables->win8[k][lane];
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
         uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
-        int tick = 0; /* frames seen since (and including) the first non-zero one */
-        int onset = (int)nfr;
-        int vH1 = 0, tH1 = 0, vH2 = 0, tH2 = 0; /* (valid, tick) of frames i-1 and i-2 */
-        for (long long i = 0; i < niter; ++i) {
+        int onset = kNoOnset; /* index of the first non-zero frame */
+        for (int i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            if (LIGHT && vH2) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is tick tH2 + 2's "current frame") */
-                const int e = (tH2 + 2) & (kSlots - 1);
+            if (LIGHT && tick_ge(i - 2, 1, onset, nfr)) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is its tick + 2's "current frame") */
+                const int e = (tick_of(i - 2, onset) + 2) & (kSlots - 1);
                 const float en = vad_frame_energy(L.frameEn[e]);
                 if (lane == 0) L.frameEnLog[e] = en;
             }
-            RecA &r = L.ra[i & 1];
-            int valid = 0;
+            int tick = 0; /* frames seen since (and including) the first non-zero one */
             bool actA = false;
             if (i < nfr) {
                 const uint32_t w = nextw;
-                if (i + 1 < nfr && lane < 40) nextw = in32[(i + 1) * 40 + lane];
-                const bool any = __ballot(w != 0u) != 0ull;
-                if (any || tick > 0) {
-                    valid = 1;
-                    if (FD && tick == 0) onset = (int)i;
-                    tick++;
+                if (i + 1 < nfr && lane < 40) nextw = (in32 + (long long)(i + 1) * 40)[lane];
+                if (onset == kNoOnset && __ballot(w != 0u) != 0ull) {
+                    onset = i;
+                    if (lane == 0) __hip_atomic_store(&L.onset, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+                if (i >= onset) {
+                    tick = tick_of(i, onset);
                     const float x0 = (float)(short)(w & 0xFFFFu), x1 = (float)(short)(w >> 16);
                     if (lane < 40) slot_store(L.circ[0], tick, lane, x0, x1);
                     actA = tick >= 3; /* NoiseSup.c:1152 */
                 }
             }
             /* stage 1, frame i-3 (B0 finished it at the previous iteration): NoiseSup.c:1178 <=> tick >= 5 */
-            const long long f1 = i - 3;
-            int valid1 = 0, t1 = 0;
-            bool actB = false;
-            if (f1 >= 0 && f1 < nfr) {
-                const RecDen &d = L.rd[f1 & 1];
-                valid1 = d.valid;
-                t1 = d.tick;
-                actB = valid1 && t1 >= 5;
-            }
-            if (lane == 0) {
-                r.valid = valid;
-                r.tick = tick;
-                r.valid1 = valid1;
-                r.tick1 = t1;
-            }
-            vH2 = vH1, tH2 = tH1, vH1 = valid, tH1 = tick;
+            const int t1 = tick_of(i - 3, onset);
+            const bool actB = tick_ge(i - 3, 5, onset, nfr);
             if (actA || actB) {
                 wave_sync();
                 float e[8];
@@ -258,37 +265,27 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_END;
         }
         NS6_T_FLUSH(role, niter);
-        if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset;
+        if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset == kNoOnset ? nfr : onset;
     } else if (role == 1) {
         /* ---- FB: second half of both transforms, FFTtoPSD ---- */
         Fft2Regs fft;
         load_fft2_regs<false>(fft, &a.tables->fft, lane, nullptr);
-        for (long long i = 0; i < niter; ++i) {
+        int onset = kNoOnset;
+        for (int i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            const long long g = i - 1; /* FA's iteration */
+            onset_poll(onset, &L.onset);
+            const int g = i - 1; /* FA's iteration */
             if (g >= 0) {
-                const RecA &r = L.ra[g & 1];
-                const long long f0 = g, f1 = g - 3;
-                const int valid = r.valid, t0 = r.tick, valid1 = r.valid1, t1 = r.tick1;
-                const bool actA = (f0 < nfr) && valid && t0 >= 3;
-                const bool actB = (f1 >= 0 && f1 < nfr) && valid1 && t1 >= 5;
+                const int f0 = g, f1 = g - 3;
+                const bool actA = tick_ge(f0, 3, onset, nfr);
+                const bool actB = tick_ge(f1, 5, onset, nfr);
                 float *work = L.work[g & 1];
                 if (actA || actB) {
                     float o[8]; /* the last level stays in registers and feeds both PSDs (ns_core.h, psd_from_last_level) */
                     rfft256_dual_hi_keep_last<false>(work, fft, o);
-                    psd_from_last_level(o, fft, L.p0[f0 & 1].psd, actA, L.p1[(f1 < 0 ? 0 : f1) & 1].psd, actB, lane);
+                    psd_from_last_level(o, fft, L.p0[f0 & 1].psd, actA, L.p1[f1 & (kP1Ring - 1)].psd, actB, lane);
                     wave_sync();
-                }
-                if (lane == 0) {
-                    if (f0 < nfr) {
-                        L.p0[f0 & 1].valid = valid;
-                        L.p0[f0 & 1].tick = t0;
-                    }
-                    if (f1 >= 0 && f1 < nfr) {
-                        L.p1[f1 & 1].valid = valid1;
-                        L.p1[f1 & 1].tick = t1;
-                    }
                 }
             }
             NS6_T_MID;
@@ -304,29 +301,25 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         regs_init(s, C.eps);
         NsFd fd;
         fd_init(fd);
-        for (long long i = 0; i < niter; ++i) {
+        int onset = kNoOnset;
+        for (int i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            const long long f = i - 2;
-            if (f >= 0 && f < nfr) {
+            onset_poll(onset, &L.onset);
+            const int f = i - 2;
+            if (tick_ge(f, 3, onset, nfr)) {
                 const RecPsd &r = L.p0[f & 1];
                 RecDen &o = L.rd[f & 1];
-                const int valid = r.valid, t = r.tick;
-                if (valid && t >= 3) {
-                    int bits = 0;
-                    /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
-                     * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
-                    float y01[2] = {0.0f, 0.0f};
-                    ns_back<0, true, FD, true>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, nullptr, lane,
-                                         (LIGHT ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)], o.den, L.idctT, &fd, &bits, nullptr,
-                                         y01);
-                    if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
-                    if (lane < 40) slot_store(L.circ[1], t, lane, y01[0], y01[1]);
-                }
-                if (lane == 0) {
-                    o.valid = valid;
-                    o.tick = t;
-                }
+                const int t = tick_of(f, onset);
+                int bits = 0;
+                /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
+                 * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
+                float y01[2] = {0.0f, 0.0f};
+                ns_back<0, true, FD, true>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, nullptr, lane,
+                                     (LIGHT ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)], o.den, L.idctT, &fd, &bits, nullptr,
+                                     y01);
+                if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
+                if (lane < 40) slot_store(L.circ[1], t, lane, y01[0], y01[1]);
             }
             NS6_T_MID;
             block_sync();
@@ -338,30 +331,22 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         const float eps = a.tables->eps;
         NsRegs s;
         regs_init(s, eps);
-        for (long long i = 0; i < niter; ++i) {
+        int onset = kNoOnset;
+        for (int i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            const long long f = i - 5;
-            if (f >= 0 && f < nfr) {
-                const RecPsd &r = L.p1[f & 1];
+            onset_poll(onset, &L.onset);
+            const int f = i - 5;
+            if (tick_ge(f, 5, onset, nfr)) {
+                const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place one beat later (kP1Ring) */
                 RecN &o = L.rn[f & 1];
-                const int valid = r.valid, t = r.tick;
-                int produced = 0;
-                if (valid && t >= 5) {
-                    /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
-                    s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
-                    s.denEn1 = L.denSum[(t - 1) & (kSlots - 1)];
-                    s.denEn2 = L.denSum[t & (kSlots - 1)];
-                    o.psd[lane] = r.psd[lane];
-                    if (lane == 0) o.psd[64] = r.psd[64];
-                    const float alfa = ns_noise1(r.psd, o.P, o.noise, s, eps, lane);
-                    if (lane == 0) o.alfa = alfa;
-                    produced = 1;
-                }
-                if (lane == 0) {
-                    o.produced = produced;
-                    o.tick = t;
-                }
+                const int t = tick_of(f, onset);
+                /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
+                s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
+                s.denEn1 = L.denSum[(t - 1) & (kSlots - 1)];
+                s.denEn2 = L.denSum[t & (kSlots - 1)];
+                const float alfa = ns_noise1(r.psd, o.P, o.noise, s, eps, lane);
+                if (lane == 0) o.alfa = alfa;
             }
             NS6_T_MID;
             block_sync();
@@ -375,22 +360,21 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         NsRegs s;
         regs_init(s, C.eps);
         float lastIn = 0.0f; /* LIGHT: y[79] of the previous filtered frame (prevSamples, NoiseSup.c:908) */
-        for (long long i = 0; i < niter; ++i) {
+        int onset = kNoOnset;
+        for (int i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            const long long f = i - 6;
-            if (f >= 0 && f < nfr) {
+            onset_poll(onset, &L.onset);
+            const int f = i - 6;
+            if (tick_ge(f, 5, onset, nfr)) {
+                const float *psd = L.p1[f & (kP1Ring - 1)].psd;
                 const RecN &r = L.rn[f & 1];
                 RecOut &o = L.ro[f & 1];
-                const int produced = r.produced, t = r.tick;
-                if (produced && DIFG1)
-                    ns_gain1_dif(r.psd, r.P, r.noise, r.alfa, L.circ[1] + window_base(t), L.back[1], s, C, o.out, lane, L.idctT, lastIn);
-                else if (produced)
-                    ns_gain1(r.psd, r.P, r.noise, r.alfa, L.circ[1] + window_base(t), L.back[1], s, C, o.out, lane, L.idctT);
-                if (lane == 0) {
-                    o.produced = produced;
-                    o.tick = t;
-                }
+                const int t = tick_of(f, onset);
+                if (DIFG1)
+                    ns_gain1_dif(psd, r.P, r.noise, r.alfa, L.circ[1] + window_base(t), L.back[1], s, C, o.out, lane, L.idctT, lastIn);
+                else
+                    ns_gain1(psd, r.P, r.noise, r.alfa, L.circ[1] + window_base(t), L.back[1], s, C, o.out, lane, L.idctT);
             }
             NS6_T_MID;
             block_sync();
@@ -403,30 +387,20 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         float *outf = a.out_f32 ? a.out_f32 + off : nullptr;
         float dcX = 0.0f, dcY = 0.0f; /* prevSamples, NoiseSup.c:908-909 */
         int firstOut = -1;
-        for (long long i = 0; i < niter; ++i) {
+        int onset = kNoOnset;
+        for (int i = 0; i < niter; ++i) {
             NS6_T_BEGIN;
             prio_by_remaining(i);
+            onset_poll(onset, &L.onset);
             /* (1) VAD log-energy (NoiseSup.c:386-391) of the frame pushed at i-1 = tick tp ("current frame" of
              *     tick tp+2); (2) in-order sum of denSigSE1 of the frame B0 finished at i-1; (3) DC-offset
              *     filter, int16 cast, store of the frame G1 finished at i-1 */
-            const long long fp = i - 1, fd = i - 3, fo = i - kDepth;
-            bool doVad = false, doDen = false, produced = false;
-            int tp = 0, td = 0;
-            const float *denSrc = L.rd[0].den;
-            if (fp >= 0 && fp < nfr) {
-                const RecA &r = L.ra[fp & 1];
-                doVad = r.valid != 0;
-                tp = r.tick;
-            }
-            if (fd >= 0 && fd < nfr) {
-                const RecDen &r = L.rd[fd & 1];
-                doDen = r.valid && r.tick >= 3;
-                td = r.tick;
-                denSrc = r.den;
-            }
+            const int fp = i - 1, fd = i - 3, fo = i - kDepth;
+            const bool doVad = tick_ge(fp, 1, onset, nfr), doDen = tick_ge(fd, 3, onset, nfr), produced = tick_ge(fo, 5, onset, nfr);
+            const int tp = tick_of(fp, onset), td = tick_of(fd, onset);
+            const float *denSrc = L.rd[(fd >= 0 && fd < nfr) ? (fd & 1) : 0].den;
             const bool haveOut = fo >= 0 && fo < nfr;
             float2 vOut = make_float2(0.0f, 0.0f);
-            if (haveOut) produced = L.ro[fo & 1].produced != 0;
             if (doVad) {
                 const float *frame = L.circ[0] + (tp & (kSlots - 1)) * kSlotLen;
                 const float x = frame[lane];
@@ -456,7 +430,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 if (produced) {
                     vOut = dc_verify_take(difS, L.sout, dcY, y, lane); /* check + output in one batch of reads */
                     dcY = y;
-                    if (firstOut < 0) firstOut = (int)fo;
+                    if (firstOut < 0) firstOut = fo;
                 }
             }
             if (haveOut) {
@@ -464,12 +438,12 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                     uint32_t packed = 0u;
                     if (produced) {
                         packed = (uint32_t)cast_i16(vOut.x) | ((uint32_t)cast_i16(vOut.y) << 16);
-                        if (outf) *reinterpret_cast<float2 *>(outf + fo * SEA_HOP + 2 * lane) = vOut;
+                        if (outf) *reinterpret_cast<float2 *>(outf + (long long)fo * SEA_HOP + 2 * lane) = vOut;
                     }
-                    out32[fo * 40 + lane] = packed;
+                    (out32 + (long long)fo * 40)[lane] = packed;
                 }
                 if (FD && produced && lane == 0 && a.flags_out)
-                    a.flags_out[off / 8 + 10 * fo] = (unsigned char)L.fdFlags[L.ro[fo & 1].tick & (kSlots - 1)];
+                    a.flags_out[off / 8 + 10 * (long long)fo] = (unsigned char)L.fdFlags[tick_of(fo, onset) & (kSlots - 1)];
                 wave_sync();
             }
             NS6_T_MID;
@@ -486,13 +460,13 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 /* launched for at most two utterances per CU (capi.hip::ns_pick_form): twelve waves per CU, three per SIMD, so the
  * register allocation could use up to 168 VGPRs.  The plain form stays compiled for 80 (measured: 1644 against 1679 ns
  * per frame with the looser bound, which only changes the schedule); the _fd form takes the looser bound, which
- * removes its 7 spilled registers (91 VGPRs). */
+ * removes its 7 spilled registers (91 VGPRs).  Today the plain form takes 68 VGPRs and the _fd form 80, nothing spilled. */
 __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
     p6::ns_pipe6_body<false, true, true>(a, L);
 }
-/* The same body compiled for SEVEN waves per SIMD (72 VGPRs, 8 spilled): the form for three or four utterances per CU
+/* The same body compiled for SEVEN waves per SIMD (69 VGPRs, four SGPRs spilled, no scratch): the form for three or four utterances per CU
  * (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
  * dispatcher, which deals the six waves of a workgroup 2 / 2 / 1 / 1 over the SIMDs, does not find room for the fourth: it
  * waited for one of the first three to end (configs[1]: 3.20 ms, which rounds 1-3 read as "the six-wave form loses at four

@@ -171,6 +171,11 @@ def _dptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+# the six-wave NoiseSup kernels keep frame indices in 32 bits and would silently cut a longer utterance (ns_pipe6_kernel.hip,
+# kMaxFrames); 2^31 frames are 172 G samples, more than the device's memory holds in and out
+MAX_FRAMES_PER_UTTERANCE = 2 ** 31 - 17
+
+
 def launch_order(lengths, n_cu=256):
     """Launch order of the utterance-per-workgroup kernels: longest first (the dispatcher serves the
     oldest waves first, so the critical path -- the longest utterance -- starts at once and keeps
@@ -215,6 +220,9 @@ class PackedBatch:
     @staticmethod
     def layout(lengths):
         lengths = np.asarray(lengths, dtype=np.int64)
+        if len(lengths) and int(lengths.max()) // 80 >= MAX_FRAMES_PER_UTTERANCE:
+            raise ValueError(f"an utterance of {int(lengths.max())} samples has {MAX_FRAMES_PER_UTTERANCE} frames or more: "
+                             "the NoiseSup kernels count frames in 32 bits")
         padded = (lengths + 7) // 8 * 8
         offsets = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64) if len(lengths) else np.zeros(0, np.int64)
         total = int(padded.sum())
