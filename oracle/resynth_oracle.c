@@ -20,6 +20,14 @@
  * The binary (IBM) branch, ora_haircell / ora_subband64 and the L/160 frame-count mode have no recorded
  * reference output at all.  Everything the GPU tests claim for the resynthesis half is "bit-identical to this
  * restatement", checked line by line against extractwav.cpp:9-211, not "to the reference".
+ *
+ * CROSS-CHECKED, STILL UNPINNED.  tests/gammatone_model.py is an independent float64 model of the same formulas (the filter
+ * in closed form, gain * sum_k k^3 e^(-2 pi bw k/fs) cos(2 pi cf k/fs) in[n-k], as an FIR convolution; closed-form overlap-add
+ * weights; interpolated BS3383 rows; the hair cell in float64) that shares nothing with this file.  tests/test_resynth_model_cpu.py
+ * holds ora_resynth_channels, ora_gammatone (all 64 channels, 1.25e-5 of peak), ora_haircell, ora_subband64 and ora_resynth64
+ * (soft, IBM, L/160: 1 LSB) to it and shows that seven misreadings of extractwav.cpp -- output after the update, x[2] not
+ * doubled, no /3, no frame > 0 guard, >= 0.5, one middle-ear division, nearest table row -- would not pass.  That guards
+ * against a misreading shared with the kernels; it is no pin to the reference.
  */
 #include <math.h>
 #include <stdlib.h>
