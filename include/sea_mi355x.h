@@ -181,6 +181,30 @@ long long sea_wb_rows(long long total_padded_samples);
 int sea_wb_compceps_batch(const float *d_out_f32, const long long *d_offsets, const long long *d_lengths, const int *d_first_out,
                           const float *d_hp_rows, const float *d_code_rows, const long long *d_ceps_cum, long long total_frames,
                           float *d_ceps, int *d_n_ceps, int n_utt, void *stream);
+/* The wideband FEATURE CHAIN -- what DoAdvProcess / FlushAdvProcess hand to a recogniser in the AdvProcessAlloc (16000) mode
+ * once the block the reference keeps commented out runs (etsi/cpp/ParmInterface.c:274-311, :348-354): NoiseSup -> WaveProc ->
+ * CompCeps -> PostProc -> frame-dropping VAD, as sea_ns_denoise_batch_fd + sea_afe_features_batch are for 8 kHz.
+ * Step 1: sea_wb_denoise_batch that also stores what the frame-dropping VAD votes over.  d_flag_rows: ONE BYTE PER PER-FRAME
+ * ROW (buffer of sea_wb_rows (total_padded_samples) bytes, the row convention of d_hp_rows): for a frame with a NoiseSup output,
+ * bit 0 SpeechFoundVar, 1 SpeechFoundSpec, 2 SpeechFoundMel, 3 SpeechFoundVADNS as the first stage left them at that frame
+ * (NoiseSup.c:1255-1281, :1359-1365); rows of other frames are not written.  d_out_f32, d_first_out, d_onset and d_flag_rows
+ * are required here; every other output is bit for bit sea_wb_denoise_batch's. */
+int sea_wb_denoise_batch_fd(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                            const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                            unsigned char *d_flag_rows, float *d_hp_rows, float *d_code_rows, void *d_scratch,
+                            long long total_padded_samples, int n_utt, void *stream);
+/* Step 2: features, with the meaning and the emission order of sea_afe_features_batch.  DoWaveProc (WaveProc.c:397-455) on the
+ * low band's 200-sample frame, then the wideband DoCompCeps (CompCeps.c:392-402, :464-479, :488-530) with the frame's rows of
+ * d_hp_rows / d_code_rows -> d_feat_cc; DoPostProc (PostProc.c:123-149) -> d_feat_pp (optional); DoVADProc (VAD.c:219-317) and
+ * DoVADFlush (:342-433) -> d_feat15 = c1..c12, c0, logE and the VAD flag per emitted frame, the null vectors of the all-zero
+ * lead first (ParmInterface.c:314-329: d_onset of them, the gate acts on the 160 raw samples, :244-251); d_n_feat[u] their
+ * number, d_n_ceps[u] (optional) the cepstral frames.  d_ceps_cum / d_feat_cum: n_utt + 1 prefix sums of per-utterance
+ * capacities >= d_lengths[u] / 160 - 6 cepstral and >= d_lengths[u] / 160 + 6 emitted frames; total_ceps = d_ceps_cum[n_utt]. */
+int sea_wb_afe_features_batch(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
+                              const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,
+                              const int *d_first_out, const int *d_onset, const long long *d_ceps_cum, long long total_ceps,
+                              float *d_feat_cc, float *d_feat_pp, const long long *d_feat_cum, float *d_feat15, int *d_n_feat,
+                              int *d_n_ceps, int n_utt, void *stream);
 /* one utterance from host memory, in the style of etsi_denoise: out_lp[0 .. 80 * (n / 160)) is written */
 int sea_wb_denoise(const short *in, long n, short *out_lp);
 /* the mode's tables as the library computed them (tests): the QMF pair, bands 1..3 of the high band's mel filter

@@ -39,6 +39,8 @@ PROTOTYPES = {
     "sea_wb_scratch_bytes": (_ll, [_ll, _i]),
     "sea_wb_rows": (_ll, [_ll]),
     "sea_wb_compceps_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _vp]),
+    "sea_wb_denoise_batch_fd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp]),
+    "sea_wb_afe_features_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sea_wb_denoise": (_i, [_vp, _l, _vp]),
     "sea_wb_tables_host": (_i, [_vp] * 6),
     "sea_resynth64_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

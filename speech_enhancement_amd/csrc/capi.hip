@@ -397,15 +397,16 @@ long long sea_wb_scratch_bytes(long long total_padded_samples, int n_utt)
     return align8(total_padded_samples / 2) * 2 * (long long)sizeof(float) + align8(n_utt) * (long long)sizeof(int);
 }
 
-int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
-                         const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset, float *d_hp_rows,
-                         float *d_code_rows, void *d_scratch, long long total_padded_samples, int n_utt, void *stream)
+/* both wideband NoiseSup entry points: d_flag_rows != nullptr selects the frame loop that records the speech flags */
+static int wb_denoise_launch(const char *who, const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                             const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                             unsigned char *d_flag_rows, float *d_hp_rows, float *d_code_rows, void *d_scratch,
+                             long long total_padded_samples, int n_utt, void *stream)
 {
-    if (n_utt <= 0) return 0;
     if (!d_in || !d_out_lp || !d_offsets || !d_lengths || !d_scratch)
-        return fail("sea_wb_denoise_batch: input, low-band output, offsets, lengths and scratch are required");
-    if ((d_hp_rows == nullptr) != (d_code_rows == nullptr)) return fail("sea_wb_denoise_batch: the high-band rows and the code rows come together");
-    if (total_padded_samples < 0 || (total_padded_samples & 7)) return fail("sea_wb_denoise_batch: total_padded_samples must be a multiple of 8");
+        return fail("%s: input, low-band output, offsets, lengths and scratch are required", who);
+    if ((d_hp_rows == nullptr) != (d_code_rows == nullptr)) return fail("%s: the high-band rows and the code rows come together", who);
+    if (total_padded_samples < 0 || (total_padded_samples & 7)) return fail("%s: total_padded_samples must be a multiple of 8", who);
     DeviceCtx *c;
     if (ctx(&c)) return 1;
     const long long half = align8(total_padded_samples / 2);
@@ -439,7 +440,11 @@ int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, c
     a.b.n_utt = n_utt;
     a.in_f32 = lp;
     a.onset = onset;
-    hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_kernel, dim3(n_utt), dim3(256), 0, st, a);
+    a.b.flags_out = d_flag_rows;
+    if (d_flag_rows)
+        hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_fd_kernel, dim3(n_utt), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_kernel, dim3(n_utt), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (d_hp_rows) { /* the high band: needs the two QMF streams and the onset only */
         sea::WbHbArgs h = {};
@@ -459,6 +464,73 @@ int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, c
         hipLaunchKernelGGL(sea::wb_specsub_kernel, dim3((unsigned)((n_utt + 63) / 64)), dim3(64), 0, st, h);
         HIP_TRY(hipGetLastError());
     }
+    return 0;
+}
+
+int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                         const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset, float *d_hp_rows,
+                         float *d_code_rows, void *d_scratch, long long total_padded_samples, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    return wb_denoise_launch("sea_wb_denoise_batch", d_in, d_out_lp, d_out_f32, d_offsets, d_lengths, d_order, d_first_out, d_onset,
+                             nullptr, d_hp_rows, d_code_rows, d_scratch, total_padded_samples, n_utt, stream);
+}
+
+int sea_wb_denoise_batch_fd(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                            const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                            unsigned char *d_flag_rows, float *d_hp_rows, float *d_code_rows, void *d_scratch,
+                            long long total_padded_samples, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_out_f32 || !d_first_out || !d_onset || !d_flag_rows)
+        return fail("sea_wb_denoise_batch_fd: the float stream, first_out, onset and the flag rows are all required");
+    return wb_denoise_launch("sea_wb_denoise_batch_fd", d_in, d_out_lp, d_out_f32, d_offsets, d_lengths, d_order, d_first_out, d_onset,
+                             d_flag_rows, d_hp_rows, d_code_rows, d_scratch, total_padded_samples, n_utt, stream);
+}
+
+int sea_wb_afe_features_batch(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
+                              const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,
+                              const int *d_first_out, const int *d_onset, const long long *d_ceps_cum, long long total_ceps,
+                              float *d_feat_cc, float *d_feat_pp, const long long *d_feat_cum, float *d_feat15, int *d_n_feat,
+                              int *d_n_ceps, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_out_f32 || !d_flag_rows || !d_hp_rows || !d_code_rows || !d_first_out || !d_onset)
+        return fail("sea_wb_afe_features_batch: the float stream, the flag rows, the high-band rows, the code rows, first_out and onset are required");
+    if (!d_offsets || !d_lengths || !d_ceps_cum || !d_feat_cc || !d_feat_cum || !d_feat15 || !d_n_feat)
+        return fail("sea_wb_afe_features_batch: offsets, lengths, both prefix sums, feat_cc, feat15 and n_feat are required");
+    if (total_ceps < 0) return fail("sea_wb_afe_features_batch: total_ceps must not be negative");
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::WbAfeArgs w = {};
+    sea::AfeArgs &a = w.a;
+    a.den_f32 = d_out_f32;
+    a.flags = d_flag_rows;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.first_out = d_first_out;
+    a.onset = d_onset;
+    a.ceps_cum = d_ceps_cum;
+    a.feat_cc = d_feat_cc;
+    a.feat_pp = d_feat_pp;
+    a.feat_cum = d_feat_cum;
+    a.feat15 = d_feat15;
+    a.n_feat = d_n_feat;
+    a.n_ceps = d_n_ceps;
+    a.tables = c->cc;
+    a.n_utt = n_utt;
+    w.hp_rows = d_hp_rows;
+    w.code_rows = d_code_rows;
+    w.wb = c->wb;
+    if (total_ceps > 0) {
+        const long long nslot = total_ceps / 8 + n_utt; /* tile slots of 8 frames, as sea_afe_features_batch */
+        constexpr long long kAfeGrid = 8192;
+        const long long want = nslot < kAfeGrid ? nslot : kAfeGrid;
+        hipLaunchKernelGGL(sea::afe_wb_ceps_kernel, dim3((unsigned)want), dim3(64), 0, (hipStream_t)stream, w);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sea::afe_wb_vad_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -9,8 +9,10 @@
  *                            frame j of an utterance = denoised[80j-1 .. 80j+199], available once 3
  *                            NoiseSup outputs exist (the commented-out driver block
  *                            etsi/cpp/ParmInterface.c:275-293)
+ * The tile (cc_tile.h) and DoWaveProc (cc_waveproc.h) are shared with afe_wb_kernel.hip.
  */
-#include "ns_core.h" /* the kernels' own double log and its guard (ns_ln, ns_near_float_boundary, ns_ln_cr) */
+#include "cc_tile.h"
+#include "cc_waveproc.h"
 
 namespace sea {
 
@@ -156,286 +158,6 @@ __global__ __launch_bounds__(256) void rfft_any_kernel(float *x, const unsigned 
     }
 }
 
-/* ==================================================================================================
- * Tiled CompCeps: one wave owns a TILE of kCcT consecutive frames.
- *
- * A one-frame-per-wave form (round 1: 2.5 ms for 810 511 frames) spends most of its time on work that every one of
- * its 64 lanes repeats: the frame's 200-term in-order energy sum (CompCeps.c:413-423) and its double-precision log.
- * Here the tile's samples are staged in LDS once and
- *   * the energy sums run LANE = FRAME (lane f adds the 200 squares of frame f in order; the hop
- *     blocks sit 81 words apart -- one pad word per 80 samples -- so the 16 lanes hit 16 banks),
- *     and the log of the sum is evaluated once per frame, again lane = frame;
- *   * two frames at a time go through the dual transform (lanes 0..31 / 32..63, swizzled work area,
- *     five LDS round trips instead of six), their power spectra and the 23 mel triangles (lane =
- *     (frame, band));
- *   * the 23 log energies of all frames are taken lane = (frame, band) flattened (6 evaluations of the
- *     double log per tile instead of 16), the DCT lane = (frame, coefficient) flattened (4 passes).
- * Arithmetic per value is WI8CompCeps' (CompCeps.c:368-549), operation by operation: pre-emphasis in double
- * (:427-429), power spectrum products and sum in double (:451-459), taps / DCT terms in their order.  Zero-weight taps stand in for the band length test (acc + p * 0 == acc: p is a
- * finite power, acc >= +0) and c0's plain sum is a DCT row of ones (x * 1.0f == x).
- * ================================================================================================ */
-namespace {
-
-constexpr int kCcT = 16; /* frames per tile of compceps_kernel (afe_ceps_kernel: kAfeT) */
-
-/* (float)log((double)v) for a positive normal float v, as CompCeps.c:423 / :511 take it.  The library's double log
- * costs ~150 instructions; the kernels' own table-driven one with its rounding-boundary guard (ns_core.h, ns_logf) */
-__device__ __forceinline__ float cc_logf(float v) { return ns_logf(v); }
-
-template <bool SHARED, int T = kCcT>
-struct CcGeom {
-    /* SHARED: frames of one utterance, 80 samples apart, share their samples; word x of the span (x = 0 is
-     * Data[-1] of the tile's first frame) sits at x + x / 80.  Otherwise: kCcT separate frames of 201 floats. */
-    static constexpr int FS = SHARED ? 81 : 201;
-    static constexpr int SPAN = SHARED ? 81 * (T - 1) + 204 : 201 * T;
-};
-
-template <bool SHARED, int T = kCcT>
-struct __attribute__((aligned(16))) CcTileLds {
-    float span[(CcGeom<SHARED, T>::SPAN + 3) & ~3];
-    float work[512];                  /* the dual transform's work area; after the tile's last pair, its T x 14 output rows */
-    float pw[2][SEA_CC_PWROW];        /* 129 power bins per frame, zeros behind (the mel taps read past 128) */
-    float fb[T][24];
-    float dctT[SEA_CC_NCHAN * 16];
-};
-
-struct CcTileConst {
-    Fft2Regs fft;
-    float win8[8];
-    int qd[8], qm[8];                 /* word offsets of Data[idx], Data[idx-1] from the frame's base; qd < 0: idx >= 200 */
-    int pwAB, pwCD;                   /* words from the pair's first power row: bins j (+ 64) and 64 - j (+ 64) of this lane's
-                                         last-level item (rfft256_dual_keep_last), row of its transform */
-    bool pairLane;                    /* the item with bins 0, 64, 128 | 32, 96 */
-    int melBase, melFb;               /* this lane's (frame, band) of the mel pass: sea_tables.h, melLaneBase */
-    float melW[SEA_CC_TAPS2];
-    float floorFB, floorE;
-};
-
-template <bool SHARED>
-__device__ __forceinline__ int cc_q(int x) /* word offset of Data[x-1] within its frame, x = 0..200 */
-{
-    return SHARED ? x + (x >= 80 ? 1 : 0) + (x >= 160 ? 1 : 0) : x;
-}
-
-template <bool SHARED, int T = kCcT>
-__device__ __forceinline__ void load_cc_tile_const(CcTileConst &C, CcTileLds<SHARED, T> &L, const sea_cc_tables *t, int lane)
-{
-    load_fft2_regs<false>(C.fft, &t->fft, lane, nullptr);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        constexpr int kRev3[8] = {0, 4, 2, 6, 1, 5, 3, 7};
-        const int idx = (lane & 31) + 32 * kRev3[k];
-        C.win8[k] = t->win8[k][lane];
-        C.qd[k] = (idx < SEA_WIN) ? cc_q<SHARED>(idx + 1) : -1;
-        C.qm[k] = (idx < SEA_WIN) ? cc_q<SHARED>(idx) : 0;
-    }
-    {
-        const unsigned item = t->fft.fft2Item[SEA_FFT_LSTAGES - 1][lane & 31];
-        C.pairLane = (item >> 16) == SEA_BF_PAIR;
-        const int ja = (int)(item & 255u), jc = C.pairLane ? (int)((item >> 8) & 255u) : ja; /* j, j | 0, 32 */
-        C.pwAB = SEA_CC_PWROW * (lane >> 5) + ja;
-        C.pwCD = SEA_CC_PWROW * (lane >> 5) + 64 - jc;
-    }
-    C.melBase = t->melLaneBase[lane];
-    C.melFb = t->melLaneFb[lane];
-#pragma unroll
-    for (int i = 0; i < SEA_CC_TAPS2; ++i) C.melW[i] = t->melLaneW[i][lane];
-    C.floorFB = t->floorFB;
-    C.floorE = t->floorE;
-    for (int i = lane; i < SEA_CC_NCHAN * 16; i += kLanes) L.dctT[i] = t->dctT[i >> 4][i & 15];
-    for (int i = lane; i < 2 * SEA_CC_PWROW; i += kLanes) (&L.pw[0][0])[i] = 0.0f;
-    wave_sync();
-}
-
-/* timing-only diagnostic (-DSEA_CC_TIMING, tools/cc_phases.py): shader clocks workgroup 0 of compceps_kernel spends per step of a tile */
-#ifdef SEA_CC_TIMING
-__device__ unsigned long long g_cc_ck[8];
-extern "C" int sea_cc_timing(unsigned long long *out8, int reset)
-{
-    if (reset) {
-        unsigned long long z[8] = {};
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_cc_ck), z, sizeof z) != hipSuccess;
-    }
-    return hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_cc_ck), 8 * sizeof(unsigned long long)) != hipSuccess;
-}
-__device__ unsigned g_cc_wave[16384 * 4]; /* per wave of compceps_kernel: start, end (constant 100 MHz counter), HW_ID, XCC_ID */
-extern "C" int sea_cc_waves(unsigned *out, int n) { return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_cc_wave), (size_t)n * 4 * sizeof(unsigned)) != hipSuccess; }
-#define CC_CK_START unsigned long long cck_ = clock64()
-#define CC_CK(k) do { const unsigned long long c_ = clock64(); if (SHARED && blockIdx.x == 0 && threadIdx.x == 0) g_cc_ck[k] += c_ - cck_; cck_ = c_; } while (0)
-#else
-#define CC_CK_START
-#define CC_CK(k)
-#endif
-
-/* the wideband mode's additions to a tile (cc_tile<.., WB = true>) */
-struct __attribute__((aligned(16))) CcWbLds {
-    float dec[kCcT][4];               /* GetBandsForDecoding16k's three sums per frame */
-    float fbx[kCcT][4];               /* log band energies 23..25 (the frame's row of fb has 24 columns) */
-    float dct26T[SEA_WB_NCHAN * 16];
-};
-
-/* the staged tile -> nv rows of 14 coefficients at dst.
- * WB: the wideband mode (CompCeps.c:392-402, :464-479, :488-530).  X = the additions' LDS; hpRows / codeRows = the tile's first
- * frame's rows of high-band energies (after the spectral subtraction) and code values: cepstral frame j of an utterance is
- * computed after NoiseSup output j + 2 and reads the heads of the three-deep queues hpBands / bufferCodeForBands16k, the
- * entries of output j (NoiseSup.c:1418-1428).  logE is taken after CorrectEnergy, not before. */
-template <bool SHARED, int T = kCcT, bool WB = false>
-__device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileConst &C, int nv, float *dst, int lane,
-                                        CcWbLds *X = nullptr, const float *hpRows = nullptr, const float *codeRows = nullptr,
-                                        const sea_wb_tables *wbt = nullptr)
-{
-    constexpr int FS = CcGeom<SHARED, T>::FS;
-    /* logE (CompCeps.c:413-423): lane f sums the squares of frame f in sample order */
-    float logE; /* three ranges of the walk, each with a constant pad */
-    CC_CK_START;
-    {
-        const float *p = L.span + FS * (lane & (T - 1));
-        float acc = 0.0f;
-        if (lane < T) {
-            if (SHARED) {
-#pragma unroll 8
-                for (int x = 1; x < 80; ++x) { const float v = p[x]; acc += v * v; }
-#pragma unroll 8
-                for (int x = 80; x < 160; ++x) { const float v = p[x + 1]; acc += v * v; }
-#pragma unroll 8
-                for (int x = 160; x < 201; ++x) { const float v = p[x + 2]; acc += v * v; }
-            } else {
-#pragma unroll 8
-                for (int x = 1; x < 201; ++x) { const float v = p[x]; acc += v * v; }
-            }
-        }
-        if (WB) logE = acc;
-        else logE = (acc < C.floorE) ? (float)-50.0 : cc_logf(acc);
-    }
-    CC_CK(1);
-    const int npair = (nv + 1) >> 1;
-    for (int pr = 0; pr < npair; ++pr) {
-        const int h = lane >> 5;
-        const int f = 2 * pr + h;
-        const bool act = f < nv;
-        const float *p = L.span + FS * f;
-        /* pre-emphasis in double (:427-429), symmetric Hamming (:115-125), zero padding (:439-440) */
-        float e[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float v = 0.0f;
-            if (act && C.qd[k] >= 0) {
-                const float d = p[C.qd[k]], dm1 = p[C.qm[k]];
-                v = (float)((double)d - 0.90 * (double)dm1) * C.win8[k];
-            }
-            e[k] = v;
-        }
-        /* the transform's last level stays in registers: every lane holds four complete bins of its frame (one lane per frame
-         * five), whose power -- products and sum in double (:451-459) -- goes straight to the frame's row */
-        float o[8];
-        rfft256_dual_keep_last<false>(e, L.work, C.fft, o);
-        {
-            const bool pl = C.pairLane;
-            const float ia = pl ? 0.0f : o[7], ib = pl ? o[3] : o[6], ic = pl ? o[7] : o[3], id = pl ? o[6] : o[2];
-            auto power = [](float re, float im) { return (float)((double)re * (double)re + (double)im * (double)im); };
-            float *rowAB = &L.pw[0][0] + C.pwAB, *rowCD = &L.pw[0][0] + C.pwCD;
-            rowAB[0] = power(o[0], ia);   /* bin j | 0: (float)(re * re + 0.0) == (float)(re * re) */
-            rowAB[64] = power(o[1], ib);  /* bin 64 + j | 64 */
-            rowCD[0] = power(o[4], ic);   /* bin 64 - j | 32 */
-            rowCD[64] = power(o[5], id);  /* bin 128 - j | 96 */
-            if (pl) rowAB[128] = power(o[2], 0.0f); /* bin 128 */
-        }
-        wave_sync();
-        if (WB && lane < 6) { /* GetBandsForDecoding16k (16kHzProcessing.c:317-336) from the power spectrum, before the mel pass */
-            const int hh = lane / 3, b = lane - 3 * hh;
-            if (2 * pr + hh < nv) {
-                const float *row = &L.pw[hh][0];
-                const int b0 = b == 0 ? 66 : (b == 1 ? 78 : 98), b1 = b == 0 ? 77 : (b == 1 ? 97 : 129);
-                float sum = 0.0f;
-                for (int i = b0; i < b1; ++i) sum += row[i];
-                X->dec[2 * pr + hh][b] = sum * 0.5f; /* /= 2.0 */
-            }
-        }
-        /* 23 mel triangles (DoMelFB, MelProc.c:82-104): lane = one (frame, band) of the pair, dealt so that the aligned
-         * pairs the lanes of a group read lie on different banks (round 4: 3-way conflicts on every tap before) */
-        if (C.melFb >= 0 && 2 * pr + (C.melFb >= 24 ? 1 : 0) < nv) {
-            const float2 *q = reinterpret_cast<const float2 *>(&L.pw[0][0] + C.melBase);
-            float acc = 0.0f;
-#pragma unroll
-            for (int i = 0; i < SEA_CC_TAPS2 / 2; ++i) {
-                const float2 v = q[i];
-                acc = acc + v.x * C.melW[2 * i];
-                acc = acc + v.y * C.melW[2 * i + 1];
-            }
-            (&L.fb[2 * pr][0])[C.melFb] = acc;
-        }
-        wave_sync();
-    }
-    CC_CK(2);
-    /* natural log with floor (:509-513): lane = (frame, band) flattened */
-    for (int idx = lane; idx < nv * SEA_CC_NCHAN; idx += kLanes) {
-        const int f = idx / SEA_CC_NCHAN, b = idx - f * SEA_CC_NCHAN;
-        const float v = L.fb[f][b];
-        L.fb[f][b] = (v < C.floorFB) ? (float)-10.0 : cc_logf(v);
-    }
-    wave_sync();
-    CC_CK(3);
-    if (WB) { /* lane = frame: the high bands join (the promotions are the reference's: float unless a double constant enters) */
-        if (lane < nv) {
-            const int f = lane;
-            const float *code = codeRows + f * 9, *hpr = hpRows + f * 3;
-            const float cw[3] = {(float)0.1, (float)0.2, (float)0.7}; /* codeWeights, CompCeps.c:475-477 */
-            float aux[3], hb[3], fbv[3];
-            for (int j = 0; j < 3; ++j) { /* :468-473 */
-                const float v = X->dec[f][j];
-                aux[j] = (v > C.floorFB) ? cc_logf(v) : (float)-10.0;
-            }
-            for (int i = 0; i < 3; ++i) { /* DecodeBands16k, then the coded bands' pre-emphasis correction (:503-504) */
-                float sum = 0.0f;
-                for (int j = 0; j < 3; ++j) sum += cw[j] * (aux[j] - code[3 * i + j]);
-                hb[i] = sum + wbt->preemLog;
-            }
-            for (int i = 0; i < 3; ++i) { /* the subtracted bands (:497-498), log with floor (:509-513) */
-                const float v = (float)((1.0 + 0.90) * (double)hpr[i]);
-                fbv[i] = (v < C.floorFB) ? (float)-10.0 : cc_logf(v);
-            }
-            const float percCoded = (float)0.7; /* MergeSSandCoded, 16kHzProcessing.c:106-125 */
-            for (int i = 0; i < 3; ++i) fbv[i] = (float)((double)(percCoded * hb[i]) + (1.0 - (double)percCoded) * (double)fbv[i]);
-            float f22 = L.fb[f][SEA_CC_NCHAN - 1];
-            const float avg = (float)(0.5 * (double)f22 + 0.5 * (double)fbv[0]);
-            f22 = (float)(0.6 * (double)f22 + 0.4 * (double)avg);
-            fbv[0] = (float)(0.6 * (double)fbv[0] + 0.4 * (double)avg);
-            L.fb[f][SEA_CC_NCHAN - 1] = f22;
-            float energyHP = 0.0f; /* CorrectEnergy, :145-158 */
-            for (int i = 0; i < 3; ++i) {
-                X->fbx[f][i] = fbv[i];
-                energyHP = (float)((double)energyHP + exp((double)(fbv[i] - wbt->preemLogF)));
-            }
-            logE += energyHP;
-            logE = (logE < C.floorE) ? (float)-50.0 : cc_logf(logE); /* CompCeps.c:526-529 */
-        }
-        wave_sync();
-    }
-    /* DCT (:203-227): lane = (frame, coefficient) flattened; c = 12 is c0, logE goes to c = 13 */
-    for (int idx = lane; idx < nv * 13; idx += kLanes) {
-        const int f = idx / 13, c = idx - f * 13;
-        float acc = 0.0f;
-        if (WB) {
-#pragma unroll
-            for (int j = 0; j < SEA_CC_NCHAN; ++j) acc += L.fb[f][j] * X->dct26T[j * 16 + c];
-#pragma unroll
-            for (int j = 0; j < SEA_WB_NHP; ++j) acc += X->fbx[f][j] * X->dct26T[(SEA_CC_NCHAN + j) * 16 + c];
-        } else {
-#pragma unroll
-            for (int j = 0; j < SEA_CC_NCHAN; ++j) acc += L.fb[f][j] * L.dctT[j * 16 + c];
-        }
-        L.work[f * SEA_CC_NCEP + c] = acc;
-    }
-    if (lane < nv) L.work[lane * SEA_CC_NCEP + 13] = logE;
-    wave_sync();
-    CC_CK(4);
-    for (int idx = lane; idx < nv * SEA_CC_NCEP; idx += kLanes) dst[idx] = L.work[idx];
-    wave_sync();
-    CC_CK(5);
-}
-
-} // namespace
-
 __global__ __launch_bounds__(64) void compceps_frames_kernel(const float *data201, float *coef14,
                                                              long long nframes, const sea_cc_tables *t)
 {
@@ -580,230 +302,11 @@ __global__ __launch_bounds__(64, 2) void compceps_wb_kernel(WbCepsArgs a)
  * PostProc (an LMS recurrence over frames) and the frame-dropping VAD (a 7-frame ring and two
  * hangover counters) are serial per utterance and tiny -> one wave per utterance (afe_vad_kernel).
  * ================================================================================================ */
-namespace {
-
-/* DoWaveProc: the peak searches of four frames run side by side, one per row of 16 lanes (feature pass 4.19 -> 3.82 ms against
- * one frame at a time, wave-wide).  Dealing the Teager / smoothing / window steps of the four frames to the lanes as 800 samples as
- * well (13 rounds, one sync per group) measured SLOWER, 4.39 ms: per-lane frame index, divisions by 200 and a divergent loop over
- * each frame's own peak list */
-
-struct __attribute__((aligned(16))) WpLds { /* scratch of DoWaveProc: four frames in flight */
-    float tw[200];
-    int q[200];
-    int sm[4][200];
-    int pos[4][24];
-    int nom[4];
-};
-
-/* maximum over each ROW of 16 lanes, left in every lane of the row: an xor butterfly in four DPP steps
- * (quad_perm [1,0,3,2], quad_perm [2,3,0,1], row_half_mirror, row_mirror) */
-__device__ __forceinline__ int row_max_i32(int v)
-{
-    auto mx = [](int a, int b) { return a > b ? a : b; };
-    v = mx(v, __builtin_amdgcn_update_dpp(v, v, 0xB1, 0xf, 0xf, false));
-    v = mx(v, __builtin_amdgcn_update_dpp(v, v, 0x4E, 0xf, 0xf, false));
-    v = mx(v, __builtin_amdgcn_update_dpp(v, v, 0x141, 0xf, 0xf, false));
-    v = mx(v, __builtin_amdgcn_update_dpp(v, v, 0x140, 0xf, 0xf, false));
-    return v;
-}
-
-/* arg-max of (value >= 0, index < 256) pairs per row of 16 lanes (every lane of a row gets its row's answer); ties go to the
- * LOWER index if lowWins, else the higher.  Entries with valid == false never win.  Returns the winning index, -1 if none. */
-__device__ __forceinline__ int row_argmax(int value, int index, bool valid, bool lowWins)
-{
-    const int m = row_max_i32(valid ? value : -1);
-    const int code = (valid && value == m) ? (lowWins ? 255 - index : index) : -1;
-    const int c = row_max_i32(code);
-    return (m < 0) ? -1 : (lowWins ? 255 - c : c);
-}
-
-/* DoWaveProc (WaveProc.c:397-455) on a frame d[0..199] whose low-energy check (:423-427: in-order sum of squares >= 100,
- * evaluated by the caller lane = frame) has passed, in three steps:
- *   wp_smooth   Teager energy (:216-226) and its 9-point integer smoothing                      -> W.sm[slot]
- *   wp_peaks4   maxima 25..79 samples apart (:102-190), four frames side by side               -> W.pos[slot], W.nom[slot]
- *   wp_window   a two-level window around them (:244-330), applied in place
- * Each ends with wave_sync(). */
-__device__ __forceinline__ void wp_smooth(WpLds &W, int slot, const float *d, int lane)
-{
-    constexpr int N = 200;
-    /* Teager energy and its integer quarter, (int)floor(T * 0.25 + 0.5) in double */
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = lane + 64 * k;
-        if (i < N) {
-            const float a = d[i], l = d[i > 0 ? i - 1 : 0], r = d[i < N - 1 ? i + 1 : N - 1];
-            /* ends: |d0*d0 - d0*d1| and |dN-1*dN-1 - dN-2*dN-1| (the missing neighbour is the sample itself) */
-            const float t = (i == 0) ? fabsf(a * a - a * r) : ((i == N - 1) ? fabsf(a * a - l * a) : fabsf(a * a - l * r));
-            W.q[i] = (int)floor((double)t * 0.25 + 0.5);
-        }
-    }
-    wave_sync();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = lane + 64 * k;
-        if (i < N) {
-            unsigned acc = 0;
-#pragma unroll
-            for (int j = -4; j <= 4; ++j) {
-                int idx = i + j;
-                idx = idx < 0 ? 0 : (idx > N - 1 ? N - 1 : idx);
-                acc += (unsigned)W.q[idx];
-            }
-            W.sm[slot][i] = (int)acc;
-        }
-    }
-    wave_sync();
-}
-
-/* the search for up to four frames at once, frame `slot` = row `slot` of 16 lanes (mask: bit slot = that frame takes
- * part): the searches are short dependent chains of wave-wide reductions, so four of them side by side cost what one does */
-__device__ __forceinline__ void wp_peaks4(WpLds &W, unsigned mask, int lane)
-{
-    constexpr int N = 200;
-    const int row = lane >> 4, l = lane & 15;
-    const int *sm = W.sm[row];
-    const bool on = (mask >> row) & 1u;
-    int bv = 0, bi = -1;
-#pragma unroll
-    for (int k = 0; k < 13; ++k) {
-        const int i = l + 16 * k;
-        if (i < N) {
-            const int v = sm[i];
-            if (v > bv) { /* ascending i per lane: strict > keeps the first */
-                bv = v;
-                bi = i;
-            }
-        }
-    }
-    const int p0 = row_argmax(bv, bi, on && bi >= 0, true);
-    int nom = 0;
-    int R[10], Lf[10], cR = 0, cL = 0;
-    R[0] = Lf[0] = p0;
-    int cur = p0;
-    bool go = p0 >= 0 && cur + 25 < N;
-#pragma unroll 1
-    while (__ballot(go) != 0ull) { /* to the right: last of equals = the higher index */
-        int v = -1, vi = -1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int off = l + 16 * k, idx = cur + 25 + off;
-            if (go && off < 55 && idx < N) {
-                const int x = sm[idx];
-                if (x >= v) { /* ascending idx per lane: >= keeps the last */
-                    v = x;
-                    vi = idx;
-                }
-            }
-        }
-        const int nx = row_argmax(v, vi, go && v >= 0, false);
-        if (go) {
-            if (nx >= 0) {
-#pragma unroll
-                for (int c = 0; c < 9; ++c)
-                    if (c == cR) R[c + 1] = nx;
-                cR++;
-                cur = nx;
-                go = cur + 25 < N;
-            } else
-                go = false;
-        }
-    }
-    cur = p0;
-    go = p0 >= 0 && cur - 25 > 0;
-#pragma unroll 1
-    while (__ballot(go) != 0ull) { /* to the left: last of equals in scan order = the lower index */
-        int v = -1, vi = -1;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int off = l + 16 * k, idx = cur - 25 - off;
-            if (go && off < 55 && idx > -1) {
-                const int x = sm[idx];
-                if (x >= v) { /* descending idx per lane: >= keeps the lowest */
-                    v = x;
-                    vi = idx;
-                }
-            }
-        }
-        const int nx = row_argmax(v, vi, go && v >= 0, true);
-        if (go) {
-            if (nx >= 0) {
-#pragma unroll
-                for (int c = 0; c < 9; ++c)
-                    if (c == cL) Lf[c + 1] = nx;
-                cL++;
-                cur = nx;
-                go = cur - 25 > 0;
-            } else
-                go = false;
-        }
-    }
-    if (p0 >= 0) {
-        if (l == 0) { /* ascending: left ones (farthest first), centre, right ones */
-#pragma unroll
-            for (int c = 9; c >= 1; --c)
-                if (c <= cL) W.pos[row][nom++] = Lf[c];
-#pragma unroll
-            for (int c = 0; c < 10; ++c)
-                if (c <= cR) W.pos[row][nom++] = R[c];
-        }
-        nom = cL + cR + 1;
-    }
-    if (l == 0) W.nom[row] = nom;
-    wave_sync();
-}
-
-__device__ __forceinline__ void wp_window(WpLds &W, int slot, float *d, int lane)
-{
-    constexpr int N = 200;
-    constexpr int kMaxPeaks = 12; /* maxima are at least 25 samples apart: at most 8 in 200 samples */
-    const int nom = W.nom[slot];
-    const int *pos = W.pos[slot];
-    const float eps = (float)0.2;
-    const float lowVal = (float)((double)(1 - eps) / 2.0), highVal = (float)((double)(1 + eps) / 2.0);
-    /* the peak list once into registers (one LDS round trip instead of one per peak and round); entries beyond the
-     * list sit past every sample */
-    int pk[kMaxPeaks];
-#pragma unroll
-    for (int c = 0; c < kMaxPeaks; ++c) pk[c] = (c < nom) ? pos[c] : (1 << 20);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int j = lane + 64 * k;
-        if (j < N) {
-            /* the raised segments [pos_i - 4, pos_i - 4 + ceil(0.8 gap_i)) are ordered and disjoint: the only
-             * one that can hold j is the last one starting at or before j */
-            bool high = false;
-            if (nom > 1) {
-                int cnt = 0;
-#pragma unroll
-                for (int c = 0; c < kMaxPeaks; ++c) cnt += (pk[c] - 4 <= j) ? 1 : 0;
-                if (cnt > 0) {
-                    const int i = cnt - 1;
-                    const int gap = (i < nom - 1) ? (pos[i + 1] - pos[i]) : (pos[nom - 1] - pos[nom - 2]);
-                    high = j < pos[i] - 4 + (80 * gap + 99) / 100;
-                }
-            }
-            W.tw[j] = high ? highVal : lowVal;
-        }
-    }
-    wave_sync();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = lane + 64 * k;
-        if (i < N) d[i] *= (W.tw[i] + W.tw[i < N - 1 ? i + 1 : N - 1]);
-    }
-    wave_sync();
-}
-
-} // namespace
 
 /* WaveProc + CompCeps of the restored feature chain, tiled like compceps_kernel: a wave owns 16 consecutive
  * cepstral frames of one utterance as SEPARATE 201-float frames in LDS (WaveProc reshapes each frame in place, so
  * they cannot share samples).  The low-energy check's in-order sum of squares runs lane = frame; the frames that
  * pass go through DoWaveProc one after the other (wave-wide peak search), then the tile through cc_tile(). */
-/* frames per tile of afe_ceps_kernel: 8 (same-box A/B of the feature pass: 16 frames 3.71 ms, 8 frames 3.05 ms -- half the
- * LDS per wave, 15.6 instead of 25 KB, lets the CU hold the eight waves its registers allow instead of six; compceps_kernel
- * itself is fastest with 16: 0.715 ms against 0.77-0.79 with 8 and 1.42 with 4) */
-constexpr int kAfeT = 8;
 
 /* timing-only diagnostic (-DSEA_AFE_TIMING, tools/afe_phases.py): shader clocks workgroup 0 spends per step of a tile */
 #ifdef SEA_AFE_TIMING
@@ -913,13 +416,17 @@ __global__ __launch_bounds__(64, 1) void afe_ceps_kernel(AfeArgs a)
 /* DoPostProc (PostProc.c:123-149), DoVADProc (VAD.c:219-317), DoVADFlush (:342-433) and the null
  * feature frames of the all-zero lead (ParmInterface.c:314-329), in emission order.  lane = feature
  * index (0..13 cepstra/energies, 14 the VAD flag). */
-__global__ __launch_bounds__(64) void afe_vad_kernel(AfeArgs a)
+namespace {
+/* WB: frames of 160 input samples, the speech flags one byte per per-frame row (ns_denoise_pipe_wb_fd_kernel); the null vectors
+ * follow the wideband gate, which works on the 160 raw samples (ParmInterface.c:244-251): a.onset is that gate's.  The
+ * arithmetic is the same: PostProc.c and VAD.c read no wideband state. */
+template <bool WB>
+__device__ __forceinline__ void afe_vad_body(const AfeArgs &a, float (&ring)[7][16])
 {
-    __shared__ float ring[7][16];
     const int lane = threadIdx.x;
     const int u = blockIdx.x;
     const int f0 = a.first_out[u];
-    const long long nfr = a.lengths[u] / SEA_HOP;
+    const long long nfr = a.lengths[u] / (WB ? SEA_WB_HOP : SEA_HOP);
     const long long nout = (f0 >= 0) ? nfr - f0 : 0;
     const long long nceps = (nout >= 3) ? nout - 2 : 0;
     long long nnull = a.onset[u];
@@ -927,7 +434,8 @@ __global__ __launch_bounds__(64) void afe_vad_kernel(AfeArgs a)
     float *out = a.feat15 + a.feat_cum[u] * 15;
     const float *cc = a.feat_cc + a.ceps_cum[u] * SEA_CC_NCEP;
     float *pp = a.feat_pp ? a.feat_pp + a.ceps_cum[u] * SEA_CC_NCEP : nullptr;
-    const unsigned char *flg = a.flags + a.offsets[u] / 8;
+    const unsigned char *flg = a.flags + (WB ? (a.offsets[u] + SEA_WB_HOP - 1) / SEA_WB_HOP : a.offsets[u] / 8);
+    constexpr int kFlagStep = WB ? 1 : 10; /* bytes between the flags of two frames */
     long long nemit = 0;
 
     for (long long k = 0; k < nnull; ++k) { /* null MFCC vectors, VAD = NON_SPEECH */
@@ -984,7 +492,7 @@ __global__ __launch_bounds__(64) void afe_vad_kernel(AfeArgs a)
     auto fetch = [&](long long j, float &row, int &bits) {
         const long long jj = j < nceps ? j : (nceps > 0 ? nceps - 1 : 0);
         row = (lane < 14 && nceps > 0) ? cc[jj * SEA_CC_NCEP + lane] : 0.0f;
-        bits = (nceps > 0) ? (int)flg[10 * (f0 + jj + 2)] : 0;
+        bits = (nceps > 0) ? (int)flg[kFlagStep * (f0 + jj + 2)] : 0;
     };
 #pragma unroll
     for (int q = 0; q < kAhead; ++q) fetch(q, rowQ[q], bitQ[q]);
@@ -1038,6 +546,19 @@ __global__ __launch_bounds__(64) void afe_vad_kernel(AfeArgs a)
     }
     if (lane == 0) a.n_feat[u] = (int)nemit;
 }
+} // namespace
+
+__global__ __launch_bounds__(64) void afe_vad_kernel(AfeArgs a)
+{
+    __shared__ float ring[7][16];
+    afe_vad_body<false>(a, ring);
+}
+
+/* the same pass over the wideband chain's cepstra (afe_wb_kernel.hip) */
+__global__ __launch_bounds__(64) void afe_wb_vad_kernel(AfeArgs a)
+{
+    __shared__ float ring[7][16];
+    afe_vad_body<true>(a, ring);
+}
 
 } // namespace sea
-

@@ -392,7 +392,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             block_sync();
             NS_T_END;
         }
-        if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset;
+        if (FD && !WB && a.onset_out && lane == 0) a.onset_out[u] = onset; /* WB: the QMF kernel's, below */
         if (WB && a.onset_out && lane == 0) a.onset_out[u] = (int)wbFirst;
         if (blob && lane == 0) blob[kBlobScal + 0] = __int_as_float(tick);
         NS_T_FLUSH(0);
@@ -636,8 +636,10 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
                     }
                     out32[fo * 40 + ln] = packed;
                 }
+                /* WB: one byte per per-frame row, the rows of the high band's features (sea_kernels.h, WbHbArgs) */
                 if (FD && produced && lane == 0 && a.flags_out)
-                    a.flags_out[off / 8 + 10 * fo] = (unsigned char)L.fdFlags[L.r34[fo & 1].tick & (kSlots - 1)];
+                    a.flags_out[WB ? (a.offsets[u] + SEA_WB_HOP - 1) / SEA_WB_HOP + fo : off / 8 + 10 * fo] =
+                        (unsigned char)L.fdFlags[L.r34[fo & 1].tick & (kSlots - 1)];
                 wave_sync();
             }
             NS_T_CK(4);
@@ -707,6 +709,15 @@ __global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_kernel(
 {
     __shared__ p4::PipeLds<false> L;
     p4::ns_pipe_body<false, false, false, true>(a.b, L, a.in_f32, a.onset);
+}
+
+/* the wideband frame loop + the first stage's speech measures, as ns_denoise_pipe_fd_kernel keeps them: their four bits go to
+ * the output frame's ROW of a.b.flags_out (one byte per row), input of the wideband frame-dropping VAD (afe_wb_vad_kernel).
+ * Everything else it writes is the plain wideband form's. */
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_fd_kernel(NsWbArgs a)
+{
+    __shared__ p4::PipeLds<false, true> L;
+    p4::ns_pipe_body<true, false, false, true>(a.b, L, a.in_f32, a.onset);
 }
 
 } // namespace sea

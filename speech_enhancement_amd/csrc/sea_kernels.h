@@ -62,6 +62,9 @@ struct NsWbArgs {
     const int *onset;          /* WbQmfArgs::onset (values beyond the frame count: no non-zero frame) */
 };
 __global__ void ns_denoise_pipe_wb_kernel(NsWbArgs a);     /* transform address tables in VGPRs, four workgroups per CU */
+/* + the speech flags of the frame-dropping VAD: b.flags_out holds ONE BYTE PER PER-FRAME ROW (row ceil(offsets[u] / 160) + f,
+ * as WbHbArgs below), bits as NsBatchArgs::flags_out; b.onset_out is the plain form's */
+__global__ void ns_denoise_pipe_wb_fd_kernel(NsWbArgs a);
 /* the high band's features per output frame: rows of 3 band energies and of 9 code values; the row of frame f of utterance
  * u is ceil(offsets[u] / 160) + f */
 struct WbHbArgs {
@@ -146,6 +149,16 @@ struct AfeArgs {
     const sea_cc_tables *tables;
     int n_utt;
 };
+
+/* the same chain in the wideband mode: a.den_f32 at offsets[u] / 2, a.lengths in 16 kHz samples, a.first_out / a.onset in frames
+ * of 160 (capacities >= lengths/160 - 6 and >= lengths/160 + 6), a.flags one byte per per-frame row (NsWbArgs above) */
+struct WbAfeArgs {
+    AfeArgs a;
+    const float *hp_rows, *code_rows; /* WbHbArgs: read by afe_wb_ceps_kernel as compceps_wb_kernel reads them */
+    const sea_wb_tables *wb;
+};
+__global__ void afe_wb_ceps_kernel(WbAfeArgs a); /* WaveProc + the 26-band CompCeps */
+__global__ void afe_wb_vad_kernel(AfeArgs a);    /* PostProc + frame-dropping VAD + flush on frames of 160 samples */
 
 struct ResynthArgs {
     const int16_t *in;

@@ -317,6 +317,58 @@ def wb_compceps_batch(batch, res):
     return ceps, cum, n_ceps
 
 
+def wb_afe_features_batch(batch, want_intermediates=False, use_order=True):
+    """The wideband (16 kHz) mode's full feature chain -- DoAdvProcess with AdvProcessAlloc (16000) as it was before the author
+    commented the chain out (etsi/cpp/ParmInterface.c:274-311): QMF split, NoiseSup on the low band, WaveProc -> the 26-band
+    CompCeps -> PostProc -> frame-dropping VAD, with FlushAdvProcess at the end.  Mirrors ``afe_features_batch``.
+
+    Returns a dict: feats (list of float32 [n_u, 15] host arrays: c1..c12, c0, logE, VAD flag per emitted frame), out (int16
+    low band, as wb_denoise_batch), and with want_intermediates also flag_rows (uint8, one speech-flag byte per per-frame
+    row; ``wb_rows`` cuts it up), feat_cc / feat_pp (per cepstral frame, after CompCeps / PostProc), ceps_cum, n_ceps,
+    first_out, onset, f32, hp_rows, code_rows."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = batch.data.device
+    n = batch.n_utt
+    half = (batch.total // 2 + 7) // 8 * 8
+    out = torch.zeros(half, dtype=torch.int16, device=dev)
+    f32 = torch.zeros(half, dtype=torch.float32, device=dev)
+    first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    onset = torch.zeros(n, dtype=torch.int32, device=dev)
+    rows = int(lib.sea_wb_rows(batch.total))
+    flag_rows = torch.zeros(rows, dtype=torch.uint8, device=dev)
+    hp_rows = torch.zeros((rows, 3), dtype=torch.float32, device=dev)
+    code_rows = torch.zeros((rows, 9), dtype=torch.float32, device=dev)
+    scratch = torch.zeros(int(lib.sea_wb_scratch_bytes(batch.total, n)) // 4 + 4, dtype=torch.float32, device=dev)
+    _lib.check(lib.sea_wb_denoise_batch_fd(_dptr(batch.data), _dptr(out), _dptr(f32), _dptr(batch.offsets), _dptr(batch.lengths),
+                                           _dptr(batch.order) if use_order else None, _dptr(first), _dptr(onset),
+                                           _dptr(flag_rows), _dptr(hp_rows), _dptr(code_rows), _dptr(scratch), batch.total, n,
+                                           _stream_ptr()), "sea_wb_denoise_batch_fd")
+    nfr = np.asarray(batch.host_lengths) // 160
+    ccap = np.maximum(nfr - 6, 0).astype(np.int64)
+    ccum = np.concatenate(([0], np.cumsum(ccap))).astype(np.int64)
+    fcap = (nfr + 6).astype(np.int64)
+    fcum = np.concatenate(([0], np.cumsum(fcap))).astype(np.int64)
+    tc, tf = int(ccum[-1]), int(fcum[-1])
+    feat_cc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
+    feat_pp = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev) if want_intermediates else None
+    feat15 = torch.zeros((max(tf, 1), 15), dtype=torch.float32, device=dev)
+    n_feat = torch.zeros(n, dtype=torch.int32, device=dev)
+    n_ceps = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_ccum, d_fcum = torch.from_numpy(ccum).to(dev), torch.from_numpy(fcum).to(dev)
+    _lib.check(lib.sea_wb_afe_features_batch(_dptr(f32), _dptr(flag_rows), _dptr(hp_rows), _dptr(code_rows), _dptr(batch.offsets),
+                                             _dptr(batch.lengths), _dptr(first), _dptr(onset), _dptr(d_ccum), tc, _dptr(feat_cc),
+                                             _dptr(feat_pp), _dptr(d_fcum), _dptr(feat15), _dptr(n_feat), _dptr(n_ceps), n,
+                                             _stream_ptr()), "sea_wb_afe_features_batch")
+    torch.cuda.synchronize()
+    host15, nf = feat15.cpu().numpy(), n_feat.cpu().numpy()
+    res = dict(feats=[host15[fcum[u]:fcum[u] + int(nf[u])] for u in range(n)], out=out)
+    if want_intermediates:
+        res.update(flag_rows=flag_rows, feat_cc=feat_cc, feat_pp=feat_pp, ceps_cum=ccum, n_ceps=n_ceps, first_out=first,
+                   onset=onset, f32=f32, hp_rows=hp_rows, code_rows=code_rows)
+    return res
+
+
 def wb_split(batch, tensor):
     """Cut an 8 kHz-rate result of wb_denoise_batch into per-utterance numpy arrays of 80 * (length // 160) samples."""
     host = tensor.detach().cpu().numpy()

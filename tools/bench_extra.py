@@ -5,6 +5,7 @@ script prints one JSON line per workload with the same roofline convention.
 
     python tools/bench_extra.py [--utts 1024] [--steps 5] [--what resynth,ibm,ceps,rfft]
     python tools/bench_extra.py --what wb --steps 7      # the ETSI wideband (16 kHz) mode, opt-in
+    python tools/bench_extra.py --what wbafe --steps 7   # its feature chain (WaveProc, PostProc, VAD), opt-in
 """
 import argparse
 import json
@@ -35,6 +36,31 @@ def timed(fn, steps, warmup=1):
     torch.cuda.synchronize()
     wall = (time.perf_counter() - t0) / steps
     return wall, float(np.mean([a.elapsed_time(b) for a, b in ev])) / 1e3
+
+
+def median_ms(fn, steps):
+    """device events around every step after one discarded warm-up call: (median, sorted list), in ms"""
+    import torch
+    fn()
+    torch.cuda.synchronize()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    t = sorted(a.elapsed_time(b) for a, b in ev)
+    return t[len(t) // 2], t
+
+
+def wb_batch(batch, dev):
+    """the batch of --what wb and --what wbafe: the corpus plus as many wideband signals of the same lengths"""
+    import speech_enhancement_amd as sea
+    from speech_enhancement_amd import corpus
+    lens = [int(L) for L in batch.host_lengths]
+    host = batch.data.cpu().numpy()
+    utts = [host[o:o + l] for o, l in zip(batch.host_offsets, lens)] + [corpus.synth_wideband(u, L) for u, L in enumerate(lens)]
+    return sea.PackedBatch.from_arrays(utts, dev)
 
 
 def main():
@@ -232,10 +258,7 @@ def main():
         # never moves the high band's VAD), QMF + low-band NoiseSup + high band, then the 26-band CompCeps; device events,
         # warm-up discarded, MEDIAN of the steps
         lib = sea.load()
-        lens = [int(L) for L in batch.host_lengths]
-        host = batch.data.cpu().numpy()
-        utts = [host[o:o + l] for o, l in zip(batch.host_offsets, lens)] + [corpus.synth_wideband(u, L) for u, L in enumerate(lens)]
-        wb = sea.PackedBatch.from_arrays(utts, dev)
+        wb = wb_batch(batch, dev)
         n, total = wb.n_utt, wb.total
         half = (total // 2 + 7) // 8 * 8
         out = torch.zeros(half, dtype=torch.int16, device=dev)
@@ -262,18 +285,6 @@ def main():
         def cepstra():
             assert lib.sea_wb_compceps_batch(P(f32), P(wb.offsets), P(wb.lengths), P(first), P(hpr), P(code), P(d_cum), tc,
                                              P(ceps), P(ncep), n, st) == 0, lib.sea_last_error()
-
-        def median_ms(fn, steps):
-            fn()
-            torch.cuda.synchronize()
-            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-            for a, b in ev:
-                a.record()
-                fn()
-                b.record()
-            torch.cuda.synchronize()
-            t = sorted(a.elapsed_time(b) for a, b in ev)
-            return t[len(t) // 2], t
         steps = max(args.steps, 5)
         m1, t1 = median_ms(denoise, steps)
         m2, t2 = median_ms(cepstra, steps)
@@ -289,6 +300,70 @@ def main():
                                      "sea::compceps_wb_kernel",
                           "algorithmic_bytes_per_frame": {"wb_qmf_kernel": 160 * 2 + 2 * 80 * 4, "wb_hb_kernel": 2 * 80 * 4 + 12 * 4}}),
               flush=True)
+
+    if "wbafe" in what:
+        # the wideband mode's FEATURE CHAIN on the batch of --what wb, one line per launch group and one for the whole path:
+        # QMF + low-band NoiseSup with speech flags + high band | WaveProc + 26-band CompCeps | PostProc + VAD + flush; device
+        # events, warm-up discarded, MEDIAN of the steps.  The library launches the last two groups from one call: the third is
+        # timed alone (total_ceps = 0 skips the second, the cepstra of the run before stay in place), the second is the whole
+        # call's median minus the third's
+        lib = sea.load()
+        wb = wb_batch(batch, dev)
+        n, total = wb.n_utt, wb.total
+        half = (total // 2 + 7) // 8 * 8
+        out = torch.zeros(half, dtype=torch.int16, device=dev)
+        f32 = torch.zeros(half, dtype=torch.float32, device=dev)
+        first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        onset = torch.zeros(n, dtype=torch.int32, device=dev)
+        rows = int(lib.sea_wb_rows(total))
+        flg = torch.zeros(rows, dtype=torch.uint8, device=dev)
+        hpr = torch.zeros((rows, 3), dtype=torch.float32, device=dev)
+        code = torch.zeros((rows, 9), dtype=torch.float32, device=dev)
+        scratch = torch.zeros(int(lib.sea_wb_scratch_bytes(total, n)) // 4 + 4, dtype=torch.float32, device=dev)
+        nfr = np.asarray(wb.host_lengths) // 160
+        ccum = np.concatenate(([0], np.cumsum(np.maximum(nfr - 6, 0)))).astype(np.int64)
+        fcum = np.concatenate(([0], np.cumsum(nfr + 6))).astype(np.int64)
+        tc, tf = int(ccum[-1]), int(fcum[-1])
+        fcc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
+        f15 = torch.zeros((max(tf, 1), 15), dtype=torch.float32, device=dev)
+        nfe = torch.zeros(n, dtype=torch.int32, device=dev)
+        ncep = torch.zeros(n, dtype=torch.int32, device=dev)
+        d_ccum, d_fcum = torch.from_numpy(ccum).to(dev), torch.from_numpy(fcum).to(dev)
+        P = lambda t: t.data_ptr()
+        st = torch.cuda.current_stream().cuda_stream
+
+        def denoise_fd():
+            assert lib.sea_wb_denoise_batch_fd(P(wb.data), P(out), P(f32), P(wb.offsets), P(wb.lengths), P(wb.order), P(first),
+                                               P(onset), P(flg), P(hpr), P(code), P(scratch), total, n, st) == 0, lib.sea_last_error()
+
+        def features(total_ceps):
+            assert lib.sea_wb_afe_features_batch(P(f32), P(flg), P(hpr), P(code), P(wb.offsets), P(wb.lengths), P(first), P(onset),
+                                                 P(d_ccum), total_ceps, P(fcc), None, P(d_fcum), P(f15), P(nfe), P(ncep), n,
+                                                 st) == 0, lib.sea_last_error()
+        steps = max(args.steps, 5)
+        m1, t1 = median_ms(denoise_fd, steps)
+        m23, t23 = median_ms(lambda: features(tc), steps)
+        m3, t3 = median_ms(lambda: features(0), steps)
+        m2 = m23 - m3
+        frames, emitted = int(nfr.sum()), int(nfe.sum().item())
+        workload = (f"{n} utterances at 16 kHz: the {args.utts}-utterance corpus + as many wideband signals of the same lengths, "
+                    f"{frames} frames, {int(ncep.sum().item())} cepstral frames, {emitted} emitted feature frames; median of {steps}")
+        for group, ms, kernels, extra in (
+                ("QMF + low-band NoiseSup with speech flags + high band", m1,
+                 "sea::wb_qmf_kernel + sea::ns_denoise_pipe_wb_fd_kernel + sea::wb_hb_kernel + sea::wb_specsub_kernel",
+                 {"ms_sorted": [round(v, 3) for v in t1]}),
+                ("WaveProc + 26-band CompCeps", m2, "sea::afe_wb_ceps_kernel",
+                 {"derived": "median of the features call minus the median of its PostProc + VAD launch alone",
+                  "features_call_ms_sorted": [round(v, 3) for v in t23]}),
+                ("PostProc + VAD + flush", m3, "sea::afe_wb_vad_kernel", {"ms_sorted": [round(v, 3) for v in t3]})):
+            print(json.dumps({"metric": f"ETSI wideband feature chain, launch group: {group} (frames of 160 samples/sec)",
+                              "value": frames / (ms / 1e3), "unit": "frames/s", "ms_per_step": ms,
+                              "config": dict(workload=workload, **extra), "kernels": kernels}), flush=True)
+        print(json.dumps({"metric": "ETSI wideband feature chain frames/sec (160-sample frames: QMF + NoiseSup with flags + high band "
+                                    "+ WaveProc + 26-band CompCeps + PostProc + VAD)",
+                          "value": frames / ((m1 + m23) / 1e3), "unit": "frames/s", "ms_per_step": m1 + m23,
+                          "config": {"workload": workload, "wb_denoise_batch_fd_ms": m1, "waveproc_compceps_ms": m2,
+                                     "postproc_vad_ms": m3, "wb_afe_features_batch_ms": m23}}), flush=True)
 
     if "rfft" in what:
         n = 1 << 18
