@@ -175,6 +175,25 @@ int sea_wb_denoise_batch(const short *d_in, short *d_out_lp, float *d_out_f32, c
                          float *d_code_rows, void *d_scratch, long long total_padded_samples, int n_utt, void *stream);
 long long sea_wb_scratch_bytes(long long total_padded_samples, int n_utt);
 long long sea_wb_rows(long long total_padded_samples);
+/* The same for one TIME SLICE of every utterance, as sea_ns_denoise_batch_slice is for 8 kHz: a wideband batch may be cut
+ * along the time axis and run slice by slice (sea_wb_denoise_utterances does), for audio that does not fit or has not all
+ * arrived.  Every buffer, d_offsets, d_lengths, the rows, d_scratch and total_padded_samples describe THIS slice, packed like
+ * a batch of its own with the conventions above; utterance u of every slice is the same utterance.  Every slice of an
+ * utterance is a multiple of 160 samples except its last, which may carry the ragged tail and may hold no whole frame at all;
+ * frame_base = the utterance's frames of 160 samples before this slice; resume = 0 for the first slice, whose state is not
+ * read.  d_state (required) holds sea_wb_slice_state_floats () floats per utterance and carries everything from launch to
+ * launch: the QMF delay line (the last 117 raw samples), the first non-zero frame, the frame loop's recursion as in
+ * sea_ns_denoise_batch_slice, the last five frames of both QMF streams for the high band's windows, and DoSpecSub16k's
+ * tracker.  d_first_out and d_onset (optional) are ABSOLUTE frame indices and have their one-launch meaning once all slices
+ * of the utterance have run (until then d_onset is the frames so far while all were zero).  Every whole frame of the slice
+ * gets its 80 d_out_lp samples, zeros where it has no output; rows and d_out_f32 are written for frames with an output only.
+ * Results are bit for bit those of the one launch: tests/test_gpu_wb_slices.py.  Not carried: sea_wb_compceps_batch and the
+ * feature chain, whose windows cross slice boundaries -- keep the float stream and the rows and run them once at the end. */
+int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                               const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                               float *d_hp_rows, float *d_code_rows, void *d_scratch, long long total_padded_samples,
+                               float *d_state, int n_utt, int frame_base, int resume, void *stream);
+int sea_wb_slice_state_floats(void);
 /* The wideband CompCeps (CompCeps.c:392-402, :464-479, :488-530) on those outputs: 14 floats per cepstral frame (c1..c12, c0,
  * logE; 26-band DCT, logE after the high-band correction), the first after the third NoiseSup output.  d_ceps_cum /
  * d_ceps / d_n_ceps as for sea_compceps_batch, capacities >= d_lengths[u] / 160 - 6. */
@@ -237,6 +256,15 @@ long long sea_resynth_scratch_bytes(long long total_padded_samples, int n_utt);
  * etsi_denoise does; results do not depend on either cut. */
 int sea_denoise_utterances(const short *const *in, short *const *out, const long *lengths, int n_utt);
 int sea_host_threads(void); /* size of that pool */
+int sea_host_last_slices(void); /* launches (time slices) the calling thread's last sea_denoise_utterances call in the
+                                 * time-slice mode, or its last sea_wb_denoise_utterances call, was cut into; 0 before any */
+/* The same pipeline for the ETSI wideband (16 kHz) mode (sea_wb_denoise_batch_slice per slice): in[u] holds lengths[u] int16
+ * samples at 16 kHz; out_lp[u] receives the 80 * (lengths[u] / 160) low-band samples sea_wb_denoise_batch writes.  hp_rows and
+ * code_rows are optional, both or neither; each non-NULL hp_rows[u] (with code_rows[u]) receives 3 (9) floats per frame of
+ * 160 samples, the rows of sea_wb_denoise_batch, zeros for frames without an output.  A single long utterance is cut into
+ * several launches like any list; results do not depend on the cut (tests/test_gpu_wb_slices.py). */
+int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
+                              const long *lengths, int n_utt);
 /* NoiseSup from PINNED staging the caller fills and reads -- no pack / unpack copies (csrc/hostpipe.hip).  For a caller that
  * produces its samples itself (a file reader) and consumes the results itself (a file writer):
  *   p = sea_packed_create();                          a reusable staging set (pinned, portable across devices)

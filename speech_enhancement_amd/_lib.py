@@ -41,6 +41,10 @@ PROTOTYPES = {
     "sea_wb_compceps_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _i, _vp]),
     "sea_wb_denoise_batch_fd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp]),
     "sea_wb_afe_features_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sea_wb_denoise_batch_slice": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _vp]),
+    "sea_wb_slice_state_floats": (_i, []),
+    "sea_wb_denoise_utterances": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "sea_host_last_slices": (_i, []),
     "sea_wb_denoise": (_i, [_vp, _l, _vp]),
     "sea_wb_tables_host": (_i, [_vp] * 6),
     "sea_resynth64_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),

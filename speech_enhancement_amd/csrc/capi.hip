@@ -488,6 +488,76 @@ int sea_wb_denoise_batch_fd(const short *d_in, short *d_out_lp, float *d_out_f32
                              d_flag_rows, d_hp_rows, d_code_rows, d_scratch, total_padded_samples, n_utt, stream);
 }
 
+/* One TIME SLICE of a wideband batch: see include/sea_mi355x.h.  Four launches as in wb_denoise_launch, each the slice form of
+ * its kernel; the last one also stores what the next slice starts from. */
+int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                               const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                               float *d_hp_rows, float *d_code_rows, void *d_scratch, long long total_padded_samples,
+                               float *d_state, int n_utt, int frame_base, int resume, void *stream)
+{
+    const char *who = "sea_wb_denoise_batch_slice";
+    if (n_utt <= 0) return 0;
+    if (!d_state) return fail("%s: d_state is required", who);
+    if (!d_in || !d_out_lp || !d_offsets || !d_lengths || !d_scratch)
+        return fail("%s: input, low-band output, offsets, lengths and scratch are required", who);
+    if ((d_hp_rows == nullptr) != (d_code_rows == nullptr)) return fail("%s: the high-band rows and the code rows come together", who);
+    if (total_padded_samples < 0 || (total_padded_samples & 7)) return fail("%s: total_padded_samples must be a multiple of 8", who);
+    if (frame_base < 0) return fail("%s: frame_base must not be negative", who);
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    const long long half = align8(total_padded_samples / 2);
+    float *lp = static_cast<float *>(d_scratch), *hp = lp + half;
+    int *onset = reinterpret_cast<int *>(hp + half);
+    hipStream_t st = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(onset, 0x7f, (size_t)n_utt * sizeof(int), st)); /* sea::kWbNoOnset */
+    sea::WbSliceArgs w = {};
+    w.q.in = d_in;
+    w.q.offsets = d_offsets;
+    w.q.lengths = d_lengths;
+    w.q.lp = lp;
+    w.q.hp = hp;
+    w.q.onset = onset;
+    w.q.tables = c->wb;
+    w.q.n_utt = n_utt;
+    w.hp_rows = d_hp_rows;
+    w.code_rows = d_code_rows;
+    w.ns = c->ns;
+    w.state = d_state;
+    w.frame_base = frame_base;
+    w.resume = resume != 0;
+    long long rows = total_padded_samples / SEA_WB_HOP / n_utt / 2 + 1; /* as wb_denoise_launch */
+    if (rows > 1024) rows = 1024;
+    hipLaunchKernelGGL(sea::wb_qmf_slice_kernel, dim3((unsigned)n_utt, (unsigned)rows), dim3(sea::kWbQmfThreads), 0, st, w);
+    HIP_TRY(hipGetLastError());
+    sea::NsWbArgs a = {};
+    a.b.out = d_out_lp;
+    a.b.out_f32 = d_out_f32;
+    a.b.offsets = d_offsets;
+    a.b.lengths = d_lengths;
+    a.b.order = d_order;
+    a.b.first_out = d_first_out;
+    a.b.onset_out = d_onset;
+    a.b.tables = c->ns;
+    a.b.n_utt = n_utt;
+    a.b.state = d_state;
+    a.b.resume = resume != 0;
+    a.b.frame_base = frame_base;
+    a.b.prio_row = (d_order && n_utt > c->n_cu) ? c->n_cu : 0; /* by launch row, as the 8 kHz slices */
+    a.in_f32 = lp;
+    a.onset = onset;
+    hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_slice_kernel, dim3(n_utt), dim3(256), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (d_hp_rows) {
+        hipLaunchKernelGGL(sea::wb_hb_slice_kernel, dim3((unsigned)n_utt, (unsigned)rows), dim3(64), 0, st, w);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sea::wb_slice_end_kernel, dim3((unsigned)n_utt), dim3(128), 0, st, w);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_wb_slice_state_floats(void) { return sea::kWbSliceStateFloats; }
+
 int sea_wb_afe_features_batch(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
                               const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,
                               const int *d_first_out, const int *d_onset, const long long *d_ceps_cum, long long total_ceps,

@@ -268,6 +268,7 @@ struct PipeWs {
     Grow<long long> meta;  /* offsets | lengths | mask offsets, in launch order */
     Grow<float> f32, ceps; /* sea_denoise_ceps_utterances: the float NoiseSup stream (device side used only), the cepstra */
     Grow<int> ints;        /* the same: first_out | n_ceps | order */
+    Grow<float> wb_rows;   /* sea_wb_denoise_utterances: per frame 3 high-band energies, then per frame 9 code values */
     float *d_inter = nullptr; /* resynth scratch */
     size_t inter_bytes = 0;
     float *d_state = nullptr; /* NoiseSup in time slices: the recursion per utterance between two launches */
@@ -288,6 +289,7 @@ struct PipeWs {
         f32.release();
         ceps.release();
         ints.release();
+        wb_rows.release();
         if (d_inter) (void)hipFree(d_inter);
         d_inter = nullptr;
         inter_bytes = 0;
@@ -363,6 +365,7 @@ struct PipeWs {
     }
 };
 thread_local PipeWs t_ws;
+thread_local int t_last_slices = 0; /* launches the calling thread's last time-slice pipeline call was cut into */
 
 /* On every exit path: no pool task may outlive the buffers it copies from / to, no stream may still be copying. */
 struct Scope {
@@ -699,6 +702,7 @@ static int denoise_utterances_slices(const short *const *in, short *const *out, 
     }
     B.push_back(max_fr);
     const int K = (int)B.size() - 1;
+    t_last_slices = K;
 
     /* per slice: the active prefix of the sorted list, packed offsets (absolute, in samples) and lengths */
     std::vector<int> nact(K);
@@ -822,6 +826,204 @@ static int denoise_utterances_slices(const short *const *in, short *const *out, 
     scope.ok = true;
     return 0;
 }
+
+/* ---------------------------------------------------------------------------------------------------- */
+/* The wideband (16 kHz) mode from host buffers: denoise_utterances_slices above for sea_wb_denoise_batch_slice.  The same cut
+ * (frames of 160 input samples here), the same three streams and event-driven loop; what differs is what travels: 160 int16
+ * up and 80 int16 down per frame, and, where the caller asks for them, 3 + 9 floats of high-band rows down.  Slice k is a
+ * batch of its own on the device: its offsets count from the slice's start, so the QMF scratch (two floats per input sample)
+ * is one slice's, reused by the next -- the slices' kernels run in order on one stream.  Rows of frames without an output are
+ * not written by the kernels and reach the caller as zeros: the slice's rows are cleared on the kernels' stream first.
+ * The state is used even for a list that is not cut: there is one wideband path here, the slice kernels'. */
+static int wb_denoise_utterances_slices(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
+                                        const long *lengths, int n_utt)
+{
+    if (n_utt <= 0) return 0;
+    if (!in || !out_lp || !lengths) return fail("sea_wb_denoise_utterances: in, out_lp and lengths are required");
+    if ((hp_rows == nullptr) != (code_rows == nullptr)) return fail("sea_wb_denoise_utterances: hp_rows and code_rows come together");
+    for (int u = 0; u < n_utt; ++u) {
+        if (lengths[u] < 0) return fail("negative length for utterance %d", u);
+        if (hp_rows && (hp_rows[u] == nullptr) != (code_rows[u] == nullptr))
+            return fail("sea_wb_denoise_utterances: hp_rows[%d] and code_rows[%d] come together", u, u);
+    }
+    DeviceCtx *dc;
+    if (ctx(&dc)) return 1;
+    const bool rows = hp_rows != nullptr;
+    constexpr long long kIn = SEA_WB_HOP, kOut = SEA_HOP; /* samples per frame up / down */
+    std::vector<int> idx(n_utt);
+    for (int i = 0; i < n_utt; ++i) idx[i] = i;
+    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return lengths[a] > lengths[b]; });
+    std::vector<long long> nfr(n_utt);
+    long long total_fr = 0;
+    for (int j = 0; j < n_utt; ++j) total_fr += (nfr[j] = lengths[idx[j]] / kIn);
+    t_last_slices = 0;
+    if (total_fr == 0) return 0;
+    const long long max_fr = nfr[0];
+    if (max_fr > 0x7fffffffLL - 8) return fail("sea_wb_denoise_utterances: utterance %d is too long", idx[0]);
+    const long long total = total_fr * kIn;
+    PipeWs &w = t_ws;
+    HIP_TRY(w.bind());
+    Pool &pool = Pool::get(w.device);
+
+    /* slice boundaries in frames: equal shares of the samples */
+    const bool small = total * 2 < (2 << 20) || pool.size() <= 1;
+    int want = small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8);
+    want = (int)std::min<long long>(std::min(want, kMaxChunks), std::max<long long>(1, max_fr / 8));
+    auto frames_below = [&](long long f) {
+        long long s = 0;
+        for (int j = 0; j < n_utt; ++j) s += std::min(nfr[j], f);
+        return s;
+    };
+    std::vector<long long> B(1, 0);
+    for (int k = 1; k < want; ++k) {
+        long long lo = B.back() + 1, hi = max_fr; /* smallest f with frames_below(f) >= share */
+        const long long share = total_fr * k / want;
+        while (lo < hi) {
+            const long long mid = (lo + hi) / 2;
+            if (frames_below(mid) >= share) hi = mid; else lo = mid + 1;
+        }
+        if (lo >= max_fr) break;
+        B.push_back(lo);
+    }
+    B.push_back(max_fr);
+    const int K = (int)B.size() - 1;
+    t_last_slices = K;
+
+    /* per slice: the active prefix of the sorted list; where the slice starts in the staging (in FRAMES: x 160 in the input,
+     * x 80 in the output, x 3 and x 9 in the rows); offsets (from the slice's start, in input samples) and lengths */
+    std::vector<int> nact(K);
+    std::vector<long long> foff(K + 1, 0);
+    std::vector<size_t> mbase(K + 1, 0);
+    long long max_slice_fr = 0;
+    for (int k = 0; k < K; ++k) {
+        int n = 0;
+        while (n < n_utt && nfr[n] > B[k]) ++n;
+        nact[k] = n;
+        long long fr = 0;
+        for (int j = 0; j < n; ++j) fr += std::min(nfr[j], B[k + 1]) - B[k];
+        foff[k + 1] = foff[k] + fr;
+        max_slice_fr = std::max(max_slice_fr, fr);
+        mbase[k + 1] = mbase[k] + 2 * (size_t)n;
+    }
+    const size_t n_rows = (size_t)total_fr + 1; /* a slice writes rows [0, its frames): sea_wb_rows' spare row is never touched */
+    HIP_TRY(w.in.ensure((size_t)total));
+    HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
+    HIP_TRY(w.meta.ensure(mbase[K]));
+    if (rows) HIP_TRY(w.wb_rows.ensure(12 * n_rows));
+    HIP_TRY(w.ensure_state((size_t)n_utt * sea::kWbSliceStateFloats));
+    HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
+    std::vector<std::vector<long long>> bpre(K); /* byte prefix per slice: task sizing */
+    for (int k = 0; k < K; ++k) {
+        long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
+        bpre[k].assign(nact[k] + 1, 0);
+        long long o = 0;
+        for (int j = 0; j < nact[k]; ++j) {
+            const long long L = kIn * (std::min(nfr[j], B[k + 1]) - B[k]);
+            offs[j] = o;
+            lens[j] = L;
+            o += L;
+            bpre[k][j + 1] = bpre[k][j] + 2 * L;
+        }
+    }
+
+    std::vector<Latch> packed(K), unpacked(K);
+    Scope scope(&w);
+    short *h_in = w.in.h, *h_out = w.out.h;
+    float *h_hp = rows ? w.wb_rows.h : nullptr, *h_code = rows ? w.wb_rows.h + 3 * n_rows : nullptr;
+    float *d_hp = rows ? w.wb_rows.d : nullptr, *d_code = rows ? w.wb_rows.d + 3 * n_rows : nullptr;
+    const int *ix = idx.data();
+    for (int k = 0; k < K; ++k) {
+        const long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
+        const long long b0 = kIn * B[k], s0 = kIn * foff[k];
+        run_copies(pool, 0, nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
+    }
+    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
+
+    const char *tr = getenv("SEA_HOST_TRACE");
+    const bool trace = tr && atoi(tr) <= 0;
+    const double t0 = now_ms();
+    enum { kWaitPack, kComputing, kDownloading, kUnpacking };
+    std::vector<char> state(K, kWaitPack);
+    int next = 0, finished = 0;
+    while (finished < K) {
+        bool progressed = false;
+        int r = 0;
+        if (next < K && packed[next].ready() && (next == 0 || (r = evq(w.ev_h2d[next - 1], "hostpipe: upload event")) != 0)) {
+            if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
+            const int k = next++;
+            const long long fr = foff[k + 1] - foff[k];
+            if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  wideband slice %d packed (frames %lld..%lld of %d utterances, %.1f MB), issuing\n",
+                               now_ms() - t0, k, B[k], B[k + 1], nact[k], fr * kIn * 2 / 1048576.0);
+            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * foff[k], h_in + kIn * foff[k], (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
+            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
+            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
+            if (rows) {
+                HIP_TRY(hipMemsetAsync(d_hp + 3 * foff[k], 0, (size_t)fr * 3 * sizeof(float), sKern));
+                HIP_TRY(hipMemsetAsync(d_code + 9 * foff[k], 0, (size_t)fr * 9 * sizeof(float), sKern));
+            }
+            if (sea_wb_denoise_batch_slice(w.in.d + kIn * foff[k], w.out.d + kOut * foff[k], nullptr, w.meta.d + mbase[k],
+                                           w.meta.d + mbase[k] + nact[k], nullptr, nullptr, nullptr, rows ? d_hp + 3 * foff[k] : nullptr,
+                                           rows ? d_code + 9 * foff[k] : nullptr, w.d_inter, fr * kIn, w.d_state, nact[k], (int)B[k],
+                                           k > 0, sKern))
+                return 1;
+            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            state[k] = kComputing;
+            progressed = true;
+        }
+        for (int k = 0; k < next; ++k) {
+            if (state[k] == kComputing && (r = evq(w.ev_kernel[k], "hostpipe: kernel event")) != 0) {
+                if (r < 0) return 1;
+                const long long fr = foff[k + 1] - foff[k];
+                HIP_TRY(hipMemcpyAsync(h_out + kOut * foff[k], w.out.d + kOut * foff[k], (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
+                if (rows) {
+                    HIP_TRY(hipMemcpyAsync(h_hp + 3 * foff[k], d_hp + 3 * foff[k], (size_t)fr * 3 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+                    HIP_TRY(hipMemcpyAsync(h_code + 9 * foff[k], d_code + 9 * foff[k], (size_t)fr * 9 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+                }
+                HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+                state[k] = kDownloading;
+                progressed = true;
+                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  wideband slice %d computed, downloading\n", now_ms() - t0, k);
+            }
+            if (state[k] == kDownloading && (r = evq(w.ev_done[k], "hostpipe: download event")) != 0) {
+                if (r < 0) return 1;
+                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  wideband slice %d on the host, unpacking\n", now_ms() - t0, k);
+                const long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
+                const long long bk = B[k], fk = foff[k];
+                run_copies(pool, 0, nact[k], bpre[k].data(), &unpacked[k], &scope.all, small, [=](int j) {
+                    const long long f0 = fk + offs[j] / kIn, n = lens[j] / kIn; /* the piece's first frame in the staging, its frames */
+                    const int u = ix[j];
+                    copy_stream(out_lp[u] + kOut * bk, h_out + kOut * f0, (size_t)(n * kOut) * sizeof(short));
+                    if (rows && hp_rows[u]) {
+                        copy_stream(hp_rows[u] + 3 * bk, h_hp + 3 * f0, (size_t)n * 3 * sizeof(float));
+                        copy_stream(code_rows[u] + 9 * bk, h_code + 9 * f0, (size_t)n * 9 * sizeof(float));
+                    }
+                });
+                state[k] = kUnpacking;
+                finished++;
+                progressed = true;
+            }
+        }
+        if (!progressed) {
+            if (next < K && !packed[next].ready()) packed[next].wait_for(std::chrono::microseconds(30));
+            else std::this_thread::sleep_for(std::chrono::microseconds(20));
+        }
+    }
+    scope.all.wait();
+    if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  all unpacked (%d wideband slices)\n", now_ms() - t0, K);
+    scope.ok = true;
+    return 0;
+}
+
+int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
+                              const long *lengths, int n_utt)
+{
+    return wb_denoise_utterances_slices(in, out_lp, hp_rows, code_rows, lengths, n_utt);
+}
+
+/* launches the calling thread's last sea_denoise_utterances (time-slice mode) or sea_wb_denoise_utterances call was cut into */
+int sea_host_last_slices(void) { return t_last_slices; }
 
 /* ---------------------------------------------------------------------------------------------------- */
 /* sea_packed_*: NoiseSup from PINNED staging the CALLER fills and reads (VERDICT r03 #5 ii).

@@ -247,7 +247,9 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     const long long niter = nfr + kPipeDepth;
 
     /* time slices (NsBatchArgs::state): the recursion of utterance u between two launches */
-    float *const blob = (SLICES && !FD && a.state) ? a.state + (size_t)u * kNsPipeStateFloats : nullptr;
+    /* (the wideband slices keep more per utterance behind the blob: sea_kernels.h, kWbSliceStateFloats) */
+    constexpr int kStateStride = (SLICES && WB) ? kWbSliceStateFloats : kNsPipeStateFloats;
+    float *const blob = (SLICES && !FD && a.state) ? a.state + (size_t)u * kStateStride : nullptr;
     const bool resume = blob && a.resume;
     constexpr int kBlobLane = 2 * kCirc, kBlobRing = kBlobLane + 12 * 64, kBlobScal = kBlobRing + 3 * kSlots;
     if (resume) { /* the two stage buffers with their mirrors, the tick-indexed rings */
@@ -295,7 +297,19 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         uint32_t nextw = (!WB && lane < 40 && nfr > 0) ? in32[lane] : 0u;
         float2 nextv = make_float2(0.0f, 0.0f);
         long long wbFirst = nfr; /* first frame that runs */
-        if (WB) {
+        int wbAbs = kWbNoOnset; /* WB time slices: the onset as an absolute frame index */
+        if (WB && SLICES) {
+            /* wbOnset[u] is absolute and covers this slice's frames, the state has what the earlier slices found: the intake
+             * starts at the slice's frame of the smaller one, frame 0 when the onset lies in an earlier slice */
+            wbAbs = wbOnset[u];
+            if (resume) {
+                const int before = __float_as_int(blob[kWbStOnset]);
+                if (before < wbAbs) wbAbs = before;
+            }
+            const long long o = wbAbs > a.frame_base ? (long long)wbAbs - a.frame_base : 0;
+            if (o < nfr) wbFirst = o;
+            if (lane < 40 && nfr > 0) nextv = inf2[lane];
+        } else if (WB) {
             const int o = wbOnset[u];
             if ((long long)o < nfr) wbFirst = o;
             if (lane < 40 && nfr > 0) nextv = inf2[lane];
@@ -393,7 +407,9 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             NS_T_END;
         }
         if (FD && !WB && a.onset_out && lane == 0) a.onset_out[u] = onset; /* WB: the QMF kernel's, below */
-        if (WB && a.onset_out && lane == 0) a.onset_out[u] = (int)wbFirst;
+        if (WB && !SLICES && a.onset_out && lane == 0) a.onset_out[u] = (int)wbFirst;
+        if (WB && SLICES && a.onset_out && lane == 0) /* absolute; the frames so far while there is none */
+            a.onset_out[u] = (long long)wbAbs < a.frame_base + nfr ? wbAbs : (int)(a.frame_base + nfr);
         if (blob && lane == 0) blob[kBlobScal + 0] = __int_as_float(tick);
         NS_T_FLUSH(0);
 #ifdef SEA_NS_TIMING
@@ -718,6 +734,14 @@ __global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_fd_kern
 {
     __shared__ p4::PipeLds<false, true> L;
     p4::ns_pipe_body<true, false, false, true>(a.b, L, a.in_f32, a.onset);
+}
+
+/* the wideband frame loop over one TIME SLICE: ns_denoise_pipe_slice_kernel's carried recursion with the wideband intake.  The
+ * blob of utterance u sits at a.b.state + u * kWbSliceStateFloats; a.onset holds absolute frame indices. */
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_slice_kernel(NsWbArgs a)
+{
+    __shared__ p4::PipeLds<false> L;
+    p4::ns_pipe_body<false, false, true, true>(a.b, L, a.in_f32, a.onset);
 }
 
 } // namespace sea

@@ -81,6 +81,44 @@ struct WbHbArgs {
 __global__ void wb_hb_kernel(WbHbArgs a);      /* blockIdx.x = utterance, blockIdx.y strides over its output frames; one wave */
 __global__ void wb_specsub_kernel(WbHbArgs a); /* one lane per utterance */
 
+/* The wideband mode in TIME SLICES (include/sea_mi355x.h, sea_wb_denoise_batch_slice): what one utterance carries from the
+ * launches of one slice to those of the next, kWbSliceStateFloats floats at state + u * that, integers as their bit patterns:
+ *   [0, kNsPipeStateFloats)   the low-band frame loop's blob, laid out and carried as NsBatchArgs::state
+ *   kWbStQmf   117 floats     the QMF delay line: the last 117 raw input samples before the next slice's first frame
+ *   kWbStOnset   1 int        ABSOLUTE index of the first non-zero frame (kWbNoOnset while there has been none); once found,
+ *                             no later slice replaces it
+ *   kWbStLp    400 floats     the last five frames of the QMF low band (the high band's window of output frame F starts at
+ *                             sample 60 of low-band frame F - 5) ...
+ *   kWbStHp    400 floats     ... and of the QMF high band (read from frame F - 4 on); both are SHIFTED by the slice's frames,
+ *                             so a slice of a single frame keeps the four before it
+ *   kWbStSub     8 floats     DoSpecSub16k's tracker: noise[3], meanEn, nbSpeech (int), hangOver (int), the count of
+ *                             second-stage frames so far (int), one unused
+ * A slice's launches only READ the parts beyond the frame loop's blob (with resume != 0; nothing is read of a first slice's
+ * state); its last launch, wb_slice_end_kernel, writes them all, so the workgroups that stride over a slice's frames never
+ * race with a store.  Each slice's kernels find the onset among the slice's own frames in the scratch, as absolute indices,
+ * and every reader takes the smaller of that and the carried one. */
+constexpr int kWbStQmf = kNsPipeStateFloats;
+constexpr int kWbStOnset = kWbStQmf + 117;
+constexpr int kWbStLp = kWbStOnset + 3; /* 16-byte aligned */
+constexpr int kWbStHp = kWbStLp + 5 * 80;
+constexpr int kWbStSub = kWbStHp + 5 * 80;
+constexpr int kWbSliceStateFloats = kWbStSub + 8;
+constexpr int kWbNoOnset = 0x7f7f7f7f; /* what the scratch's onset is preset to: beyond any frame count */
+struct WbSliceArgs {
+    WbQmfArgs q;               /* the slice's input, packed like a batch of its own; q.onset: the scratch's, ABSOLUTE indices */
+    float *hp_rows;            /* optional, with code_rows: the slice's rows */
+    float *code_rows;
+    const sea_ns_tables *ns;
+    float *state;              /* [n_utt][kWbSliceStateFloats] */
+    int frame_base;            /* frames of 160 samples of every utterance before this slice */
+    int resume;                /* 0: first slice, the state is not read */
+};
+__global__ void wb_qmf_slice_kernel(WbSliceArgs a);   /* as wb_qmf_kernel; the delay line of frame 0 comes from the state */
+__global__ void ns_denoise_pipe_wb_slice_kernel(NsWbArgs a); /* b.state with the stride kWbSliceStateFloats; onset absolute */
+__global__ void wb_hb_slice_kernel(WbSliceArgs a);    /* as wb_hb_kernel; frames before the slice come from the state */
+__global__ void wb_slice_end_kernel(WbSliceArgs a);   /* one workgroup of 128 per utterance: DoSpecSub16k over the slice's rows, then
+                                                       * the state's wideband parts for the next slice */
+
 /* B independent streams, nframes frames of 80 floats each, state blobs of kNsStateFloats floats */
 constexpr int kNsStateFloats = 2 * 320 + 12 * 64 + 32;
 struct NsStreamArgs {

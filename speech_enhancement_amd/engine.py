@@ -298,6 +298,69 @@ def wb_denoise_batch(batch, want_f32=False, want_hb=False, use_order=True):
                 qmf_lp=scratch[:half], qmf_hp=scratch[half:2 * half])
 
 
+def wb_slice_state(n_utt, device="cuda"):
+    """The per-utterance state wb_denoise_batch_slice carries from slice to slice: float32 [n_utt, floats per utterance].
+    Its contents do not matter before the first slice (resume = 0 reads none of it)."""
+    return _torch().zeros((n_utt, int(_lib.load().sea_wb_slice_state_floats())), dtype=_torch().float32, device=device)
+
+
+def wb_denoise_batch_slice(batch, state, frame_base, resume, want_f32=False, want_hb=False, first_out=None, onset=None,
+                           use_order=True):
+    """One TIME SLICE of a wideband batch (sea_wb_denoise_batch_slice): ``batch`` packs THIS slice's samples of every utterance
+    that has some (utterance u of every slice is the same utterance; every slice of an utterance is a multiple of 160 samples
+    except its last), ``state`` is a ``wb_slice_state`` tensor with a row per utterance, ``frame_base`` the frames of 160
+    samples before this slice, ``resume`` false for the first slice.  Returns wb_denoise_batch's dict for the slice, indexed by
+    the slice's own offsets; first_out / onset are ABSOLUTE frame indices -- pass the previous slice's tensors back in as
+    ``first_out`` / ``onset`` and utterances that have ended keep theirs.  Rows and f32 of frames without an output stay zero.
+    Concatenated over the slices, everything is bit for bit wb_denoise_batch's.  Asynchronous on the current stream."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = batch.data.device
+    n = batch.n_utt
+    if state is None or state.dtype != torch.float32 or not state.is_contiguous() \
+            or state.numel() < n * int(lib.sea_wb_slice_state_floats()):
+        raise ValueError("state must be a contiguous float32 tensor of sea_wb_slice_state_floats() floats per utterance")
+    half = (batch.total // 2 + 7) // 8 * 8
+    out = torch.zeros(half, dtype=torch.int16, device=dev)
+    f32 = torch.zeros(half, dtype=torch.float32, device=dev) if want_f32 else None
+    if first_out is None:
+        first_out = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    if onset is None:
+        onset = torch.zeros(n, dtype=torch.int32, device=dev)
+    rows = int(lib.sea_wb_rows(batch.total))
+    hp_rows = torch.zeros((rows, 3), dtype=torch.float32, device=dev) if want_hb else None
+    code_rows = torch.zeros((rows, 9), dtype=torch.float32, device=dev) if want_hb else None
+    scratch = torch.zeros(int(lib.sea_wb_scratch_bytes(batch.total, n)) // 4 + 4, dtype=torch.float32, device=dev)
+    rc = lib.sea_wb_denoise_batch_slice(_dptr(batch.data), _dptr(out), _dptr(f32), _dptr(batch.offsets), _dptr(batch.lengths),
+                                        _dptr(batch.order) if use_order else None, _dptr(first_out), _dptr(onset),
+                                        _dptr(hp_rows), _dptr(code_rows), _dptr(scratch), batch.total, _dptr(state), n,
+                                        int(frame_base), 1 if resume else 0, _stream_ptr())
+    _lib.check(rc, "sea_wb_denoise_batch_slice")
+    return dict(out=out, f32=f32, first_out=first_out, onset=onset, hp_rows=hp_rows, code_rows=code_rows,
+                qmf_lp=scratch[:half], qmf_hp=scratch[half:2 * half], state=state)
+
+
+def wb_denoise_utterances(utterances, want_hb=False):
+    """A list of 16 kHz int16 utterances in host memory through the wideband mode's copy / compute pipeline
+    (sea_wb_denoise_utterances: time slices, uploads, launches and downloads overlapped).  Returns a dict: out (list of int16
+    low-band arrays, 80 * (len // 160) samples each), hp_rows / code_rows (lists of float32 [len // 160, 3] / [.., 9], zeros
+    for frames without an output; None without want_hb), slices (launches the list was cut into)."""
+    lib = _lib.load()
+    xs = [np.ascontiguousarray(x, dtype=np.int16) for x in utterances]
+    n = len(xs)
+    outs = [np.zeros(x.size // 160 * 80, np.int16) for x in xs]
+    hps = [np.zeros((x.size // 160, 3), np.float32) for x in xs] if want_hb else None
+    codes = [np.zeros((x.size // 160, 9), np.float32) for x in xs] if want_hb else None
+    if n == 0:
+        return dict(out=outs, hp_rows=hps, code_rows=codes, slices=0)
+    ptrs = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_long * n)(*[x.size for x in xs])
+    rc = lib.sea_wb_denoise_utterances(ptrs(xs), ptrs(outs), ptrs(hps) if want_hb else None, ptrs(codes) if want_hb else None,
+                                       lens, n)
+    _lib.check(rc, "sea_wb_denoise_utterances")
+    return dict(out=outs, hp_rows=hps, code_rows=codes, slices=int(lib.sea_host_last_slices()))
+
+
 def wb_compceps_batch(batch, res):
     """The wideband CompCeps on a wb_denoise_batch(.., want_f32=True, want_hb=True) result.  Returns (ceps float32
     [total, 14], ceps_cum int64 [n+1] on host, n_ceps int32 [n] tensor)."""

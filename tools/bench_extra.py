@@ -6,6 +6,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py [--utts 1024] [--steps 5] [--what resynth,ibm,ceps,rfft]
     python tools/bench_extra.py --what wb --steps 7      # the ETSI wideband (16 kHz) mode, opt-in
     python tools/bench_extra.py --what wbafe --steps 7   # its feature chain (WaveProc, PostProc, VAD), opt-in
+    python tools/bench_extra.py --what wbslices --steps 7  # the wideband mode in time slices and its host pipeline, opt-in
 """
 import argparse
 import json
@@ -364,6 +365,125 @@ def main():
                           "value": frames / ((m1 + m23) / 1e3), "unit": "frames/s", "ms_per_step": m1 + m23,
                           "config": {"workload": workload, "wb_denoise_batch_fd_ms": m1, "waveproc_compceps_ms": m2,
                                      "postproc_vad_ms": m3, "wb_afe_features_batch_ms": m23}}), flush=True)
+
+    if "wbslices" in what:
+        # The wideband mode cut along the TIME axis, on the batch of --what wb.  Three lines:
+        #   (i)   sea_wb_denoise_batch, the one launch: the yardstick
+        #   (ii)  the same batch as 4 and as 8 slices of equal frame shares, one sea_wb_denoise_batch_slice per slice, device only
+        #         (every slice's packed input is resident before the clock starts)
+        #   (iii) sea_wb_denoise_utterances from pageable host arrays, wall clock around calls that return with the results
+        #         on the host: PCIe inclusive
+        # (i) and (ii): device events around every step, one warm-up step of every shape discarded, the steps of the three
+        # forms ALTERNATING in one loop, median and the sorted list of each.  All in frames of 160 samples per second.
+        import ctypes
+        lib = sea.load()
+        wb = wb_batch(batch, dev)
+        n, total = wb.n_utt, wb.total
+        lens = np.asarray(wb.host_lengths)
+        nfr = lens // 160
+        frames = int(nfr.sum())
+        host = wb.data.cpu().numpy()
+        utts = [host[o:o + l] for o, l in zip(wb.host_offsets, lens)]
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        class Bufs:  # the outputs and the scratch of one launch over a PackedBatch
+            def __init__(self, b):
+                half = (b.total // 2 + 7) // 8 * 8
+                rows = int(lib.sea_wb_rows(b.total))
+                self.b = b
+                self.out = torch.zeros(half, dtype=torch.int16, device=dev)
+                self.hpr = torch.zeros((rows, 3), dtype=torch.float32, device=dev)
+                self.code = torch.zeros((rows, 9), dtype=torch.float32, device=dev)
+                self.scratch = torch.zeros(int(lib.sea_wb_scratch_bytes(b.total, b.n_utt)) // 4 + 4, dtype=torch.float32, device=dev)
+        whole = Bufs(wb)
+        first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        onset = torch.zeros(n, dtype=torch.int32, device=dev)
+
+        def one_launch():
+            assert lib.sea_wb_denoise_batch(P(wb.data), P(whole.out), None, P(wb.offsets), P(wb.lengths), P(wb.order), P(first),
+                                            P(onset), P(whole.hpr), P(whole.code), P(whole.scratch), total, n, st) == 0, lib.sea_last_error()
+        idx = np.argsort(-nfr, kind="stable")
+        snfr = nfr[idx]
+        state = torch.zeros((n, int(lib.sea_wb_slice_state_floats())), dtype=torch.float32, device=dev)
+        sfirst, sonset = torch.full_like(first, -1), torch.zeros_like(onset)
+
+        def cut(nslices):  # boundaries with equal shares of the frames, as the host pipeline cuts
+            bounds = [0]
+            for k in range(1, nslices):
+                share = frames * k // nslices
+                f = next(f for f in range(bounds[-1] + 1, int(snfr[0]) + 1) if int(np.minimum(snfr, f).sum()) >= share)
+                if f >= snfr[0]:
+                    break
+                bounds.append(f)
+            bounds.append(int(snfr[0]))
+            pieces = []
+            for b0, b1 in zip(bounds[:-1], bounds[1:]):
+                act = [int(u) for u in idx[snfr > b0]]
+                pieces.append((b0, Bufs(sea.PackedBatch.from_arrays([utts[u][160 * b0:160 * min(b1, int(nfr[u]))] for u in act], dev))))
+            return pieces
+
+        def run_slices(pieces):
+            for k, (b0, B) in enumerate(pieces):
+                b = B.b
+                assert lib.sea_wb_denoise_batch_slice(P(b.data), P(B.out), None, P(b.offsets), P(b.lengths), P(b.order), P(sfirst),
+                                                      P(sonset), P(B.hpr), P(B.code), P(B.scratch), b.total, P(state), b.n_utt, b0,
+                                                      1 if k else 0, st) == 0, lib.sea_last_error()
+        forms = [("one launch", one_launch)] + [(f"{len(p)} slices", (lambda p=p: run_slices(p))) for p in (cut(4), cut(8))]
+        steps = max(args.steps, 5)
+        for _, fn in forms:
+            fn()
+        torch.cuda.synchronize()
+        ev = {name: [] for name, _ in forms}
+        for _ in range(steps):
+            for name, fn in forms:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                ev[name].append((a, b))
+        torch.cuda.synchronize()
+        # the sliced runs saw the utterances longest first: the same indices, permuted
+        assert torch.equal(sfirst.cpu(), first.cpu()[torch.from_numpy(idx)]) and torch.equal(sonset.cpu(), onset.cpu()[torch.from_numpy(idx)])
+        med = {}
+        for name, _ in forms:
+            t = sorted(a.elapsed_time(b) for a, b in ev[name])
+            med[name] = t[len(t) // 2]
+            print(json.dumps({"metric": f"ETSI wideband mode, QMF + low-band NoiseSup + high band, {name}, device only (frames of 160 samples/sec)",
+                              "value": frames / (med[name] / 1e3), "unit": "frames/s", "ms_per_step": med[name],
+                              "config": {"workload": f"{n} utterances at 16 kHz: the {args.utts}-utterance corpus + as many wideband signals of "
+                                                     f"the same lengths, {frames} frames; median of {steps} alternating steps",
+                                         "ms_sorted": [round(v, 3) for v in t],
+                                         "ratio_to_one_launch": round(med[name] / med["one launch"], 3)},
+                              "kernels": "sea::wb_qmf_kernel + sea::ns_denoise_pipe_wb_kernel + sea::wb_hb_kernel + sea::wb_specsub_kernel"
+                                         if name == "one launch" else
+                                         "per slice: sea::wb_qmf_slice_kernel + sea::ns_denoise_pipe_wb_slice_kernel + sea::wb_hb_slice_kernel + "
+                                         "sea::wb_slice_end_kernel"}), flush=True)
+        del forms, whole
+        outs = [np.zeros(int(f) * 80, np.int16) for f in nfr]
+        hps = [np.zeros((int(f), 3), np.float32) for f in nfr]
+        codes = [np.zeros((int(f), 9), np.float32) for f in nfr]
+        ptr = lambda arrs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs])
+        pin, pout, php, pcode = ptr(utts), ptr(outs), ptr(hps), ptr(codes)
+        plen = (ctypes.c_long * n)(*[int(l) for l in lens])
+        res = {}
+        for name, a, b in (("low band only", None, None), ("low band + high-band rows", php, pcode)):
+            assert lib.sea_wb_denoise_utterances(pin, pout, a, b, plen, n) == 0, lib.sea_last_error()
+            t = []
+            for _ in range(steps):
+                t0 = time.perf_counter()
+                assert lib.sea_wb_denoise_utterances(pin, pout, a, b, plen, n) == 0, lib.sea_last_error()
+                t.append((time.perf_counter() - t0) * 1e3)
+            t.sort()
+            res[name] = (t[len(t) // 2], [round(v, 3) for v in t])
+        m = res["low band only"][0]
+        print(json.dumps({"metric": "ETSI wideband mode through the HOST-buffer pipeline sea_wb_denoise_utterances (PCIe inclusive, frames of 160 samples/sec)",
+                          "value": frames / (m / 1e3), "unit": "frames/s", "ms_per_step": m,
+                          "config": {"workload": f"{n} host utterances at 16 kHz, {frames} frames, {int(lib.sea_host_last_slices())} slices, "
+                                                 f"{lib.sea_host_threads()} packing threads; wall clock, median of {steps} calls after one warm-up",
+                                     "ms_sorted": res["low band only"][1],
+                                     "with_high_band_rows_ms": res["low band + high-band rows"][0],
+                                     "with_high_band_rows_ms_sorted": res["low band + high-band rows"][1]}}), flush=True)
 
     if "rfft" in what:
         n = 1 << 18
