@@ -13,12 +13,16 @@
  *   copy engines   H2D piece k+1                                 | D2H piece k-1
  *   device         kernel over piece k
  *
- * NoiseSup (sea_denoise_utterances): the pieces are TIME SLICES of the whole list -- frames [B_k, B_k+1) of every
- * utterance, one launch per slice, the recursion carried in a state blob per utterance (denoise_utterances_slices).
- * A launch over whole utterances lasts as long as its longest utterance's chain of frames whatever its size; a slice lasts
- * as long as its own frames.  Resynthesis (sea_resynth_utterances; its second pass runs backwards over the utterance) and
- * SEA_HOST_MODE=chunks: the pieces are chunks of whole utterances, sorted longest first, one launch per chunk on its own
- * part of ONE device buffer.  Results do not depend on either cut.
+ * NoiseSup (sea_denoise_utterances) and the wideband mode (sea_wb_denoise_utterances): the pieces are TIME SLICES of the
+ * whole list -- frames [B_k, B_k+1) of every utterance, one launch per slice, the recursion carried in a state blob per
+ * utterance.  A launch over whole utterances lasts as long as its longest utterance's chain of frames whatever its size; a
+ * slice lasts as long as its own frames.  Resynthesis (sea_resynth_utterances; its second pass runs backwards over the
+ * utterance) and SEA_HOST_MODE=chunks: the pieces are chunks of whole utterances, sorted longest first, one launch per chunk
+ * on its own part of ONE device buffer.  Results do not depend on either cut.
+ *
+ * What the entry points share lives once: the cut along the time axis in slice_plan.h (also sea_packed_plan's), the
+ * event-driven loop in run_pipeline, the NoiseSup launch over a slice in ns_launch_slice.  An entry point is its set-up and
+ * three callables: issue (upload + launch), download, unpack.
  * Staging, device buffers, streams and events are grow-only and belong to the calling host thread (the reference's
  * batch tool calls etsi_denoise from N threads); the packing threads are one pool per device.
  */
@@ -39,6 +43,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "slice_plan.h"
 
 using namespace sea_capi;
 
@@ -194,9 +199,10 @@ struct Latch {
     }
 };
 
-/* copies [j0, j1) of a job list on the pool (or inline when the job is small), cut into ~1 MB tasks */
+/* copies [j0, j1) of a job list on the pool (or inline when the job is small), cut into ~1 MB tasks; `piece` (may be null)
+ * and `all` count the tasks */
 template <class Copy>
-void run_copies(Pool &pool, int j0, int j1, const long long *bytes_prefix, Latch *chunk, Latch *all, bool inline_, Copy copy)
+void run_copies(Pool &pool, int j0, int j1, const long long *bytes_prefix, Latch *piece, Latch *all, bool inline_, Copy copy)
 {
     if (j0 >= j1) return;
     if (inline_) {
@@ -209,12 +215,12 @@ void run_copies(Pool &pool, int j0, int j1, const long long *bytes_prefix, Latch
     while (a < j1) {
         int b = a + 1;
         while (b < j1 && bytes_prefix[b] - bytes_prefix[a] < kTask) ++b;
-        chunk->add(1);
+        if (piece) piece->add(1);
         all->add(1);
         pool.submit([=] {
             for (int j = a; j < b; ++j) copy(j);
             copy_fence(); /* non-temporal stores are visible to the copy engine / the caller before the task counts as done */
-            chunk->done();
+            if (piece) piece->done();
             all->done();
         });
         a = b;
@@ -233,32 +239,50 @@ int n_streams()
     return n;
 }
 #define kStreams n_streams()
-constexpr int kMaxChunks = 64;
+constexpr int kMaxChunks = 64; /* pieces of one call: the workspace has that many events of each kind */
+static_assert(kMaxSlices <= kMaxChunks, "a time slice is a piece");
 
 template <class T>
-struct Grow { /* one pinned + one device buffer of the same size, grow-only */
+struct Grow { /* a pinned and a device buffer, grow-only, each with a capacity of its own: a user may need only one half */
     T *h = nullptr, *d = nullptr;
-    size_t cap = 0;
+    size_t hcap = 0, dcap = 0;
+    Grow() = default;
+    Grow(const Grow &) = delete;
+    Grow &operator=(const Grow &) = delete;
+    ~Grow() { release(); }
     void release()
     {
         if (h) (void)hipHostFree(h);
         if (d) (void)hipFree(d);
         h = d = nullptr;
-        cap = 0;
+        hcap = dcap = 0;
+    }
+    static size_t roomy(size_t n) { return n + n / 4 + 4096; }
+    hipError_t ensure_host(size_t n, unsigned flags = hipHostMallocDefault) /* (write-combined staging: no gain) */
+    {
+        if (n <= hcap) return hipSuccess;
+        if (h) (void)hipHostFree(h);
+        h = nullptr;
+        hcap = 0;
+        const hipError_t e = hipHostMalloc((void **)&h, roomy(n) * sizeof(T), flags);
+        if (e == hipSuccess) hcap = roomy(n);
+        return e;
+    }
+    hipError_t ensure_device(size_t n) { return ensure_device(n, roomy(n)); }
+    hipError_t ensure_device(size_t n, size_t alloc) /* alloc >= n: what to allocate when n no longer fits */
+    {
+        if (n <= dcap) return hipSuccess;
+        if (d) (void)hipFree(d);
+        d = nullptr;
+        dcap = 0;
+        const hipError_t e = hipMalloc((void **)&d, alloc * sizeof(T) + 16);
+        if (e == hipSuccess) dcap = alloc;
+        return e;
     }
     hipError_t ensure(size_t n)
     {
-        if (n <= cap) return hipSuccess;
-        release();
-        const size_t want = n + n / 4 + 4096;
-        hipError_t e = hipHostMalloc((void **)&h, want * sizeof(T), hipHostMallocDefault); /* (write-combined staging: no gain) */
-        if (e == hipSuccess) e = hipMalloc((void **)&d, want * sizeof(T) + 16);
-        if (e != hipSuccess) {
-            release();
-            return e;
-        }
-        cap = want;
-        return hipSuccess;
+        const hipError_t e = ensure_host(n);
+        return e == hipSuccess ? ensure_device(n) : e;
     }
 };
 
@@ -269,10 +293,8 @@ struct PipeWs {
     Grow<float> f32, ceps; /* sea_denoise_ceps_utterances: the float NoiseSup stream (device side used only), the cepstra */
     Grow<int> ints;        /* the same: first_out | n_ceps | order */
     Grow<float> wb_rows;   /* sea_wb_denoise_utterances: per frame 3 high-band energies, then per frame 9 code values */
-    float *d_inter = nullptr; /* resynth scratch */
-    size_t inter_bytes = 0;
-    float *d_state = nullptr; /* NoiseSup in time slices: the recursion per utterance between two launches */
-    size_t state_floats = 0;
+    Grow<char> inter;      /* device only: resynth / wideband QMF scratch, allocated as asked for */
+    Grow<float> state;     /* device only: the recursion per utterance between two launches of a time-slice pipeline */
     hipStream_t stream[kMaxStreams] = {};
     hipEvent_t ev_meta = nullptr, ev_done[kMaxChunks] = {}, ev_kernel[kMaxChunks] = {}, ev_h2d[kMaxChunks] = {};
     int device = -1;
@@ -290,12 +312,8 @@ struct PipeWs {
         ceps.release();
         ints.release();
         wb_rows.release();
-        if (d_inter) (void)hipFree(d_inter);
-        d_inter = nullptr;
-        inter_bytes = 0;
-        if (d_state) (void)hipFree(d_state);
-        d_state = nullptr;
-        state_floats = 0;
+        inter.release();
+        state.release();
         for (auto &s : stream) {
             if (s) (void)hipStreamDestroy(s);
             s = nullptr;
@@ -337,27 +355,8 @@ struct PipeWs {
             if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
         return hipSuccess;
     }
-    hipError_t ensure_inter(size_t bytes)
-    {
-        if (bytes <= inter_bytes) return hipSuccess;
-        if (d_inter) (void)hipFree(d_inter);
-        d_inter = nullptr;
-        inter_bytes = 0;
-        hipError_t e = hipMalloc((void **)&d_inter, bytes + 16);
-        if (e == hipSuccess) inter_bytes = bytes;
-        return e;
-    }
-    hipError_t ensure_state(size_t floats)
-    {
-        if (floats <= state_floats) return hipSuccess;
-        if (d_state) (void)hipFree(d_state);
-        d_state = nullptr;
-        state_floats = 0;
-        const size_t want = floats + floats / 4;
-        hipError_t e = hipMalloc((void **)&d_state, want * sizeof(float));
-        if (e == hipSuccess) state_floats = want;
-        return e;
-    }
+    hipError_t ensure_inter(size_t bytes) { return inter.ensure_device(bytes, bytes); }
+    hipError_t ensure_state(size_t floats) { return state.ensure_device(floats, floats + floats / 4); }
     void drain()
     {
         for (auto &s : stream)
@@ -380,26 +379,20 @@ struct Scope {
     }
 };
 
-/* hipEventQuery as a three-way answer: 0 and *done set when the event has completed, 0 and *done clear while the work
- * before it is still running (hipErrorNotReady), 1 after fail() for ANYTHING else -- a failed kernel or copy, an invalid
- * event.  The pipelines below poll events; treating every non-success as "not yet" would spin for ever on a fault instead
- * of returning the reference's fault code.  `query` is hipEventQuery except in the state-machine unit test. */
+/* hipEventQuery as a three-way answer: 1 when the event has completed, 0 while the work before it is still running
+ * (hipErrorNotReady), -1 after fail() for ANYTHING else -- a failed kernel or copy, an invalid event.  The pipelines below
+ * poll events; treating every non-success as "not yet" would spin for ever on a fault instead of returning the reference's
+ * fault code.  g_event_query is hipEventQuery except under sea_selftest_hostpipe_fault. */
 typedef hipError_t (*EventQueryFn)(hipEvent_t);
 EventQueryFn g_event_query = hipEventQuery;
-int ev_ready(hipEvent_t e, bool *done, const char *what)
-{
-    const hipError_t r = g_event_query(e);
-    *done = (r == hipSuccess);
-    if (r == hipSuccess || r == hipErrorNotReady) return 0;
-    (void)hipGetLastError(); /* the sticky copy of an asynchronous fault must not fail the caller's next, unrelated call */
-    return fail("%s: %s", what, hipGetErrorString(r));
-}
-/* 1 done, 0 still running, -1 failed (fail() has the message) */
 int evq(hipEvent_t e, const char *what)
 {
-    bool done = false;
-    if (ev_ready(e, &done, what)) return -1;
-    return done ? 1 : 0;
+    const hipError_t r = g_event_query(e);
+    if (r == hipSuccess) return 1;
+    if (r == hipErrorNotReady) return 0;
+    (void)hipGetLastError(); /* the sticky copy of an asynchronous fault must not fail the caller's next, unrelated call */
+    fail("%s: %s", what, hipGetErrorString(r));
+    return -1;
 }
 
 double now_ms()
@@ -432,6 +425,115 @@ std::vector<int> cut_chunks(const std::vector<long long> &weight_prefix, int n, 
     }
     cuts.push_back(n);
     return cuts;
+}
+
+/* SEA_HOST_TRACE=n: from the process's n-th pipeline call of more than one piece on (calls of one piece: with n <= 0) */
+bool trace_this_call(int n_pieces)
+{
+    static std::atomic<int> n_cut{0};
+    const char *tr = getenv("SEA_HOST_TRACE");
+    return tr && (n_pieces == 1 ? atoi(tr) <= 0 : n_cut++ >= atoi(tr));
+}
+
+/* The event-driven loop of every pipeline here.  Piece k of packed.size() goes through
+ *     packed[k] (the latch of its packing tasks)
+ *     issue(k)      upload + launch on the caller's streams; records ev_h2d[k] after the upload, ev_kernel[k] after the launch
+ *     download(k)   once ev_kernel[k] has completed; records ev_done[k]
+ *     unpack(k)     once ev_done[k] has completed: pool tasks into the caller's buffers, counted in scope.all
+ * in that order, pieces in turn.  A copy is only handed to the runtime when everything it depends on has finished: the copy
+ * engines' queues are in order, so a D2H copy queued behind its still-running kernel would hold up the H2D copies of later
+ * pieces (measured: piece k+2's upload waited for piece k's kernel).  uploads_in_turn: piece k is issued when piece k - 1's
+ * upload has completed -- concurrent uploads share the link, and the first kernel should start as early as it can.
+ * issue and download return 0 or fail().  An event that answers anything but "done" / "not ready" ends the call with 1 as well,
+ * at once: the caller's Scope then waits for the pool and drains the streams.  Returns 0 with everything unpacked and
+ * scope.ok set.
+ * SEA_HOST_TRACE: the host-clock timeline of the call on stderr. */
+template <class Issue, class Download, class Unpack>
+int run_pipeline(PipeWs &w, Scope &scope, std::vector<Latch> &packed, const char *piece, bool uploads_in_turn, Issue issue,
+                 Download download, Unpack unpack)
+{
+    const int n = (int)packed.size();
+    const bool trace = trace_this_call(n);
+    const double t0 = now_ms();
+    enum { kWaitPack, kComputing, kDownloading, kUnpacking };
+    std::vector<char> state(n, kWaitPack);
+    int next = 0, finished = 0;
+    while (finished < n) {
+        bool progressed = false;
+        int r = 0;
+        if (next < n && packed[next].ready() &&
+            (!uploads_in_turn || next == 0 || (r = evq(w.ev_h2d[next - 1], "hostpipe: upload event")) != 0)) {
+            if (r < 0) return 1;
+            const int k = next++;
+            if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  %s %d of %d packed, issuing\n", now_ms() - t0, piece, k, n);
+            if (issue(k)) return 1;
+            state[k] = kComputing;
+            progressed = true;
+        }
+        for (int k = 0; k < next; ++k) {
+            if (state[k] == kComputing && (r = evq(w.ev_kernel[k], "hostpipe: kernel event")) != 0) {
+                if (r < 0) return 1;
+                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  %s %d computed, downloading\n", now_ms() - t0, piece, k);
+                if (download(k)) return 1;
+                state[k] = kDownloading;
+                progressed = true;
+            }
+            if (state[k] == kDownloading && (r = evq(w.ev_done[k], "hostpipe: download event")) != 0) {
+                if (r < 0) return 1;
+                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  %s %d on the host, unpacking\n", now_ms() - t0, piece, k);
+                unpack(k);
+                state[k] = kUnpacking;
+                finished++;
+                progressed = true;
+            }
+        }
+        if (!progressed) {
+            if (next < n && !packed[next].ready()) packed[next].wait_for(std::chrono::microseconds(30));
+            else std::this_thread::sleep_for(std::chrono::microseconds(20));
+        }
+    }
+    scope.all.wait();
+    if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  all unpacked (%d %ss)\n", now_ms() - t0, n, piece);
+    scope.ok = true;
+    return 0;
+}
+
+/* The rows of every slice of a plan into the meta staging (slice k's at p.mbase[k]); returns per slice the byte prefix of its
+ * pieces, for task sizing. */
+std::vector<std::vector<long long>> fill_slice_rows(const SlicePlan &p, long long hop, bool absolute, long long *meta_h)
+{
+    std::vector<std::vector<long long>> bpre(p.K);
+    for (int k = 0; k < p.K; ++k) {
+        bpre[k].resize(p.nact[k] + 1);
+        slice_rows(p, k, hop, absolute, meta_h + p.mbase[k], bpre[k].data());
+    }
+    return bpre;
+}
+
+/* One NoiseSup launch over slice k of K on the workspace's in / out buffers: d_rows = the slice's offsets | lengths rows on
+ * the device, nact utterances.  A list that is cut carries the recursion in w.state and runs on the four-wave forms, which
+ * load and store it (2; 4, the tables in LDS, above four utterances per CU); a list in one piece runs as
+ * sea_ns_denoise_batch would.  The list is sorted longest first, so form 2's issue priority goes by rows of n_cu without an
+ * order array. */
+int ns_launch_slice(PipeWs &w, DeviceCtx *dc, const long long *d_rows, int nact, int K, int k, int frame_base, hipStream_t s)
+{
+    sea::NsBatchArgs a = {};
+    a.in = w.in.d;
+    a.out = w.out.d;
+    a.offsets = d_rows;
+    a.lengths = d_rows + nact;
+    a.tables = dc->ns;
+    a.n_utt = nact;
+    int form;
+    if (K > 1) {
+        a.state = w.state.d;
+        a.resume = k > 0;
+        a.frame_base = frame_base;
+        form = (nact <= 4 * dc->n_cu) ? 2 : 4;
+    } else
+        form = ns_pick_form(nact, dc->n_cu);
+    if (form == 2 && nact > dc->n_cu) a.prio_row = dc->n_cu;
+    return ns_launch(a, form, s);
 }
 
 } // namespace
@@ -495,91 +597,50 @@ static int denoise_utterances_chunks(const short *const *in, short *const *out, 
         offs[j] = pre[j];
         lens[j] = lengths[idx[j]];
     }
-    /* Chunks (small lists: one chunk, packed by the calling thread).  Default: a third of the list each -- measured on
-     * the 1024-utterance bench corpus (tools/host_sweep.sh): kernels launched on different streams do overlap, but a
-     * launch runs as long as its longest utterance's chain of frames whatever its size and several small launches side
-     * by side fill the chip worse than one large one, so few large chunks win (3 chunks 6.3 ms, 6 chunks 7.4 ms,
-     * 16 chunks 16.5 ms; one chunk = no overlap 10.4 ms).  SEA_HOST_CHUNK_MB sets the chunk size in MB of int16. */
+    /* Chunks (small lists: one chunk, packed by the calling thread), issued longest first.  Default: a third of the list
+     * each -- measured on the 1024-utterance bench corpus: kernels launched on different streams do overlap, but a launch
+     * runs as long as its longest utterance's chain of frames whatever its size and several small launches side by side
+     * fill the chip worse than one large one, so few large chunks win (3 chunks 6.3 ms, 6 chunks 7.4 ms, 16 chunks 16.5 ms;
+     * one chunk = no overlap 10.4 ms).  SEA_HOST_CHUNK_MB sets the chunk size in MB of int16.
+     * Measured with switches that were removed afterwards: issuing the shortest chunk first, or long and short
+     * in turn, is within 5 % of longest first and no better; kernel stores straight to the pinned output staging instead of
+     * a D2H copy reach ~24 GB/s against the copy's 52 GB/s and slow the kernel down by as much as the copy they save. */
     const long long chunk_samples = getenv("SEA_HOST_CHUNK_MB") ? env_mb("SEA_HOST_CHUNK_MB", 24) * (1 << 20) / 2
                                                                 : std::max<long long>((total + 2) / 3, 1 << 20);
     const bool small = total * 2 < (2 << 20) || n_utt == 1 || pool.size() <= 1;
     const std::vector<int> cuts = small ? std::vector<int>{0, n_utt} : cut_chunks(pre, n_utt, chunk_samples, kMaxChunks);
     const int nchunk = (int)cuts.size() - 1;
     const int form = ns_pick_form(n_utt, dc->n_cu);
-    /* SEA_HOST_ZEROCOPY=o (experiment kept for other hosts): the kernel's stores go straight to the pinned output
-     * staging over PCIe (160 B per frame and utterance), no D2H phase.  Measured here: such stores reach ~24 GB/s
-     * against 52 GB/s of a D2H copy and slow the kernel down by as much as the copy phase they save. */
-    const char *zc = getenv("SEA_HOST_ZEROCOPY");
-    const bool zc_out = zc ? (strchr(zc, 'o') != nullptr) : false;
-    short *d_out = w.out.d;
-    if (zc_out) HIP_TRY(hipHostGetDevicePointer((void **)&d_out, w.out.h, 0));
-    /* issue order of the chunks (chunk 0 holds the longest utterances; SEA_HOST_ORDER=desc|asc|mix, measured within
-     * 5 % of each other, longest first best) */
-    std::vector<int> seq(nchunk);
-    {
-        const char *o = getenv("SEA_HOST_ORDER");
-        const int mode = (o && !strcmp(o, "mix")) ? 2 : ((o && !strcmp(o, "asc")) ? 1 : 0); /* default: longest first */
-        for (int i = 0, lo = 0, hi = nchunk - 1; i < nchunk; ++i)
-            seq[i] = mode == 0 ? i : (mode == 1 ? nchunk - 1 - i : ((i & 1) ? hi-- : lo++));
-    }
 
-    std::vector<Latch> packed(nchunk), unpacked(nchunk);
+    std::vector<Latch> packed(nchunk);
     Scope scope(&w);
     short *h_in = w.in.h, *h_out = w.out.h;
     std::vector<long long> bytes_pre(pre); /* task sizing */
     for (auto &b : bytes_pre) b *= 2;
     const long long *bp = bytes_pre.data();
     const int *ix = idx.data();
-    for (int i = 0; i < nchunk; ++i) {
-        const int k = seq[i];
+    for (int k = 0; k < nchunk; ++k)
         run_copies(pool, cuts[k], cuts[k + 1], bp, &packed[k], &scope.all, small, [=](int j) {
             const long long L = lens[j];
             copy_stream(h_in + offs[j], in[ix[j]], (size_t)L * sizeof(short));
             const long long pad = align8(L) - L;
             if (pad) memset(h_in + offs[j] + L, 0, (size_t)pad * sizeof(short));
         });
-    }
     HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, 2 * (size_t)n_utt * sizeof(long long), hipMemcpyHostToDevice, w.stream[0]));
     HIP_TRY(hipEventRecord(w.ev_meta, w.stream[0]));
 
-    const bool trace = getenv("SEA_HOST_TRACE") != nullptr;
-    /* timing experiments only: from the second call on skip the PCIe copies (the device works on the first call's input) */
-    static std::atomic<int> n_calls{0};
-    const bool nocopy = getenv("SEA_HOST_DEBUG_NOCOPY") != nullptr && n_calls++ > 0;
-    const double t0 = now_ms();
-    std::vector<hipEvent_t> tev; /* trace only: base, then (start, h2d, kernel, d2h) per chunk */
-    if (trace) {
-        tev.resize(1 + 4 * nchunk);
-        for (auto &e : tev) HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(tev[0], w.stream[0]));
-    }
-    /* Event-driven: a copy is only handed to the runtime when everything it depends on has finished.  The copy
-     * engines' queues are in order, so a D2H copy queued behind its still-running kernel would hold up the H2D copies
-     * of later chunks (measured: chunk k+2's upload waited for chunk k's kernel). */
-    enum { kWaitPack, kComputing, kDownloading, kUnpacking };
-    std::vector<char> state(nchunk, kWaitPack);
-    int next = 0, finished = 0;
-    while (finished < nchunk) {
-        bool progressed = false;
-        int r = 0;
-        /* one upload at a time: concurrent uploads share the link, and the first kernel should start as early as it can */
-        if (next < nchunk && packed[seq[next]].ready() &&
-            (next == 0 || (r = evq(w.ev_h2d[seq[next - 1]], "hostpipe: upload event")) != 0)) {
-            if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-            const int k = seq[next], i = next++;
-            hipStream_t s = w.stream[i % kStreams];
+    return run_pipeline(
+        w, scope, packed, "chunk", true,
+        [&](int k) {
+            hipStream_t s = w.stream[k % kStreams];
             const int u0 = cuts[k], n = cuts[k + 1] - cuts[k];
             const long long o0 = pre[u0], cnt = pre[cuts[k + 1]] - o0;
-            if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  chunk %d packed (%d utterances, %.1f MB), issuing\n", now_ms() - t0, k, n, cnt * 2 / 1048576.0);
-            if (i > 0 && i < kStreams) HIP_TRY(hipStreamWaitEvent(s, w.ev_meta, 0));
-            if (trace) HIP_TRY(hipEventRecord(tev[1 + 4 * k], s));
-            if (!nocopy)
-                HIP_TRY(hipMemcpyAsync(w.in.d + o0, h_in + o0, (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, s));
+            if (k > 0 && k < kStreams) HIP_TRY(hipStreamWaitEvent(s, w.ev_meta, 0));
+            HIP_TRY(hipMemcpyAsync(w.in.d + o0, h_in + o0, (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, s));
             HIP_TRY(hipEventRecord(w.ev_h2d[k], s));
-            if (trace) HIP_TRY(hipEventRecord(tev[2 + 4 * k], s));
             sea::NsBatchArgs a = {};
             a.in = w.in.d;
-            a.out = d_out;
+            a.out = w.out.d;
             a.offsets = w.meta.d + u0;
             a.lengths = w.meta.d + n_utt + u0;
             a.tables = dc->ns;
@@ -589,53 +650,22 @@ static int denoise_utterances_chunks(const short *const *in, short *const *out, 
                 a.prio_base = u0 / dc->n_cu;
             }
             if (ns_launch(a, form, s)) return 1;
-            if (trace) HIP_TRY(hipEventRecord(tev[3 + 4 * k], s));
             HIP_TRY(hipEventRecord(w.ev_kernel[k], s));
-            state[k] = kComputing;
-            progressed = true;
-        }
-        for (int i = 0; i < next; ++i) {
-            const int k = seq[i];
-            if (state[k] == kComputing && (r = evq(w.ev_kernel[k], "hostpipe: kernel event")) != 0) {
-                if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-                hipStream_t s = w.stream[i % kStreams];
-                const long long o0 = pre[cuts[k]], cnt = pre[cuts[k + 1]] - o0;
-                if (!zc_out && !nocopy) HIP_TRY(hipMemcpyAsync(h_out + o0, w.out.d + o0, (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, s));
-                if (trace) HIP_TRY(hipEventRecord(tev[4 + 4 * k], s));
-                HIP_TRY(hipEventRecord(w.ev_done[k], s));
-                state[k] = kDownloading;
-                progressed = true;
-            }
-            if (state[k] == kDownloading && (r = evq(w.ev_done[k], "hostpipe: download event")) != 0) {
-                if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  chunk %d done on the device, unpacking\n", now_ms() - t0, k);
-                run_copies(pool, cuts[k], cuts[k + 1], bp, &unpacked[k], &scope.all, small, [=](int j) {
-                    /* the trailing partial frame stays untouched */
-                    copy_stream(out[ix[j]], h_out + offs[j], (size_t)(lens[j] / 80 * 80) * sizeof(short));
-                });
-                state[k] = kUnpacking;
-                finished++;
-                progressed = true;
-            }
-        }
-        if (!progressed) {
-            if (next < nchunk && !packed[seq[next]].ready()) packed[seq[next]].wait_for(std::chrono::microseconds(30));
-            else std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
-    scope.all.wait();
-    if (trace) {
-        fprintf(stderr, "[hostpipe] %7.3f ms  all unpacked\n", now_ms() - t0);
-        for (int k = 0; k < nchunk; ++k) {
-            float t[4];
-            for (int q = 0; q < 4; ++q) (void)hipEventElapsedTime(&t[q], tev[0], tev[1 + 4 * k + q]);
-            fprintf(stderr, "[hostpipe] device clock, chunk %d: start %.3f  h2d done %.3f  kernel done %.3f  d2h done %.3f ms\n", k,
-                    t[0], t[1], t[2], t[3]);
-        }
-        for (auto &e : tev) (void)hipEventDestroy(e);
-    }
-    scope.ok = true;
-    return 0;
+            return 0;
+        },
+        [&](int k) {
+            hipStream_t s = w.stream[k % kStreams];
+            const long long o0 = pre[cuts[k]], cnt = pre[cuts[k + 1]] - o0;
+            HIP_TRY(hipMemcpyAsync(h_out + o0, w.out.d + o0, (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipEventRecord(w.ev_done[k], s));
+            return 0;
+        },
+        [&](int k) {
+            run_copies(pool, cuts[k], cuts[k + 1], bp, nullptr, &scope.all, small, [=](int j) {
+                /* the trailing partial frame stays untouched */
+                copy_stream(out[ix[j]], h_out + offs[j], (size_t)(lens[j] / 80 * 80) * sizeof(short));
+            });
+        });
 }
 
 int sea_denoise_utterances(const short *const *in, short *const *out, const long *lengths, int n_utt)
@@ -653,7 +683,7 @@ int sea_denoise_utterances(const short *const *in, short *const *out, const long
  *     copy engines  H2D slice k+1             | D2H slice k-1
  *     device        kernel over slice k
  * has short fill and drain phases: the first kernel starts after 1/K of the upload, the last download carries 1/K of the
- * output.  Slice boundaries equalise the slices' sample counts (SEA_HOST_SLICES of them, default 8: measured on the
+ * output.  Slice boundaries (slice_plan.h) equalise the slices' sample counts (SEA_HOST_SLICES of them, default 8: measured on the
  * 1024-utterance bench corpus, tools/host_slices_sweep.sh, alternating on one box -- chunks of whole utterances 7.4 ms,
  * 4 slices 6.2-6.5, 6: 5.9-6.0, 8: 4.8-5.7, 10: 5.6-5.7, 12: 5.3-5.8, 16: 5.8 ms; what is left is the pool's memcpy
  * rate: 2 x 131 MB packed and unpacked in that time).
@@ -667,176 +697,74 @@ static int denoise_utterances_slices(const short *const *in, short *const *out, 
     if (ctx(&dc)) return 1;
     for (int u = 0; u < n_utt; ++u)
         if (lengths[u] < 0) return fail("negative length for utterance %d", u);
-    std::vector<int> idx(n_utt);
-    for (int i = 0; i < n_utt; ++i) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return lengths[a] > lengths[b]; });
-    std::vector<long long> nfr(n_utt);
-    long long total_fr = 0;
-    for (int j = 0; j < n_utt; ++j) total_fr += (nfr[j] = lengths[idx[j]] / 80);
-    if (total_fr == 0) return 0;
-    const long long max_fr = nfr[0];
-    const long long total = total_fr * 80;
+    constexpr long long kHop = SEA_HOP;
+    const long long total = slice_total_frames(lengths, n_utt, kHop) * kHop;
+    if (total == 0) return 0;
     PipeWs &w = t_ws;
     HIP_TRY(w.bind());
     Pool &pool = Pool::get(w.device);
-
-    /* slice boundaries in frames: equal shares of the samples */
     const bool small = total * 2 < (2 << 20) || pool.size() <= 1;
-    int want = small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8);
-    want = (int)std::min<long long>(std::min(want, kMaxChunks), std::max<long long>(1, max_fr / 8));
-    auto frames_below = [&](long long f) {
-        long long s = 0;
-        for (int j = 0; j < n_utt; ++j) s += std::min(nfr[j], f);
-        return s;
-    };
-    std::vector<long long> B(1, 0);
-    for (int k = 1; k < want; ++k) {
-        long long lo = B.back() + 1, hi = max_fr; /* smallest f with frames_below(f) >= share */
-        const long long share = total_fr * k / want;
-        while (lo < hi) {
-            const long long mid = (lo + hi) / 2;
-            if (frames_below(mid) >= share) hi = mid; else lo = mid + 1;
-        }
-        if (lo >= max_fr) break;
-        B.push_back(lo);
-    }
-    B.push_back(max_fr);
-    const int K = (int)B.size() - 1;
-    t_last_slices = K;
+    SlicePlan p;
+    slice_plan(p, lengths, n_utt, kHop, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    const int K = t_last_slices = p.K;
 
-    /* per slice: the active prefix of the sorted list, packed offsets (absolute, in samples) and lengths */
-    std::vector<int> nact(K);
-    std::vector<long long> soff(K + 1, 0);
-    std::vector<size_t> mbase(K + 1, 0); /* where slice k's offsets | lengths sit in the meta array */
-    for (int k = 0; k < K; ++k) {
-        int n = 0;
-        while (n < n_utt && nfr[n] > B[k]) ++n;
-        nact[k] = n;
-        long long smp = 0;
-        for (int j = 0; j < n; ++j) smp += 80 * (std::min(nfr[j], B[k + 1]) - B[k]);
-        soff[k + 1] = soff[k] + smp;
-        mbase[k + 1] = mbase[k] + 2 * (size_t)n;
-    }
+    /* the slices one after the other in the staging, offsets absolute: the device sees ONE in and ONE out buffer */
     HIP_TRY(w.in.ensure((size_t)total));
     HIP_TRY(w.out.ensure((size_t)total));
-    HIP_TRY(w.meta.ensure(mbase[K]));
+    HIP_TRY(w.meta.ensure(p.mbase[K]));
     if (K > 1) HIP_TRY(w.ensure_state((size_t)n_utt * sea::kNsPipeStateFloats));
-    std::vector<std::vector<long long>> bpre(K); /* byte prefix per slice: task sizing */
-    for (int k = 0; k < K; ++k) {
-        long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
-        bpre[k].assign(nact[k] + 1, 0);
-        long long o = soff[k];
-        for (int j = 0; j < nact[k]; ++j) {
-            const long long L = 80 * (std::min(nfr[j], B[k + 1]) - B[k]);
-            offs[j] = o;
-            lens[j] = L;
-            o += L;
-            bpre[k][j + 1] = bpre[k][j] + 2 * L;
-        }
-    }
+    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kHop, true, w.meta.h);
 
-    std::vector<Latch> packed(K), unpacked(K);
+    std::vector<Latch> packed(K);
     Scope scope(&w);
     short *h_in = w.in.h, *h_out = w.out.h;
-    const int *ix = idx.data();
+    const int *ix = p.idx.data();
     for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
-        const long long b0 = 80 * B[k];
-        run_copies(pool, 0, nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long b0 = kHop * p.B[k];
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
                    [=](int j) { copy_stream(h_in + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
     }
+    /* one stream per job: uploads (after the meta arrays, same stream), kernels (in order: the recursion needs slice k after
+     * slice k - 1), downloads -- a slice's download is never queued behind a later slice's work */
     hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, p.mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
 
-    /* SEA_HOST_TRACE=n: print the timeline of this thread's calls from the n-th list of more than one slice on */
-    static std::atomic<int> n_sliced{0};
-    const char *tr = getenv("SEA_HOST_TRACE");
-    const bool trace = tr && (K == 1 ? atoi(tr) <= 0 : n_sliced++ >= atoi(tr));
-    const double t0 = now_ms();
-    /* Event-driven, as the chunk pipeline: a copy is only handed to the runtime when what it depends on has finished (the
-     * copy engines' queues are in order: a D2H copy queued behind its still-running kernel would hold up the next H2D). */
-    enum { kWaitPack, kComputing, kDownloading, kUnpacking };
-    std::vector<char> state(K, kWaitPack);
-    int next = 0, finished = 0;
-    while (finished < K) {
-        bool progressed = false;
-        int r = 0;
-        if (next < K && packed[next].ready() && (next == 0 || (r = evq(w.ev_h2d[next - 1], "hostpipe: upload event")) != 0)) {
-            if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-            const int k = next++;
-            const long long cnt = soff[k + 1] - soff[k];
-            if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  slice %d packed (frames %lld..%lld of %d utterances, %.1f MB), issuing\n",
-                               now_ms() - t0, k, B[k], B[k + 1], nact[k], cnt * 2 / 1048576.0);
-            /* one stream per job: uploads (after the meta arrays, same stream), kernels (in order: the recursion needs
-             * slice k after slice k - 1), downloads -- a slice's download is never queued behind a later slice's work */
-            HIP_TRY(hipMemcpyAsync(w.in.d + soff[k], h_in + soff[k], (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, sUp));
+    return run_pipeline(
+        w, scope, packed, "slice", true,
+        [&](int k) {
+            const long long o0 = kHop * p.foff[k], cnt = kHop * (p.foff[k + 1] - p.foff[k]);
+            HIP_TRY(hipMemcpyAsync(w.in.d + o0, h_in + o0, (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, sUp));
             HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
             HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
-            hipStream_t s = sKern;
-            sea::NsBatchArgs a = {};
-            a.in = w.in.d;
-            a.out = w.out.d;
-            a.offsets = w.meta.d + mbase[k];
-            a.lengths = w.meta.d + mbase[k] + nact[k];
-            a.tables = dc->ns;
-            a.n_utt = nact[k];
-            int form;
-            if (K > 1) {
-                a.state = w.d_state;
-                a.resume = k > 0;
-                a.frame_base = (int)B[k];
-                form = (nact[k] <= 4 * dc->n_cu) ? 2 : 4;
-            } else
-                form = ns_pick_form(nact[k], dc->n_cu);
-            if (form == 2 && nact[k] > dc->n_cu) a.prio_row = dc->n_cu;
-            if (ns_launch(a, form, s)) return 1;
-            HIP_TRY(hipEventRecord(w.ev_kernel[k], s));
-            state[k] = kComputing;
-            progressed = true;
-        }
-        for (int k = 0; k < next; ++k) {
-            if (state[k] == kComputing && (r = evq(w.ev_kernel[k], "hostpipe: kernel event")) != 0) {
-                if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-                const long long cnt = soff[k + 1] - soff[k];
-                HIP_TRY(hipMemcpyAsync(h_out + soff[k], w.out.d + soff[k], (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, sDown));
-                HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-                state[k] = kDownloading;
-                progressed = true;
-                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  slice %d computed, downloading\n", now_ms() - t0, k);
-            }
-            if (state[k] == kDownloading && (r = evq(w.ev_done[k], "hostpipe: download event")) != 0) {
-                if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  slice %d on the host, unpacking\n", now_ms() - t0, k);
-                const long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
-                const long long b0 = 80 * B[k];
-                run_copies(pool, 0, nact[k], bpre[k].data(), &unpacked[k], &scope.all, small,
-                           [=](int j) { copy_stream(out[ix[j]] + b0, h_out + offs[j], (size_t)lens[j] * sizeof(short)); });
-                state[k] = kUnpacking;
-                finished++;
-                progressed = true;
-            }
-        }
-        if (!progressed) {
-            if (next < K && !packed[next].ready()) packed[next].wait_for(std::chrono::microseconds(30));
-            else std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
-    scope.all.wait();
-    if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  all unpacked (%d slices)\n", now_ms() - t0, K);
-    scope.ok = true;
-    return 0;
+            if (ns_launch_slice(w, dc, w.meta.d + p.mbase[k], p.nact[k], K, k, (int)p.B[k], sKern)) return 1;
+            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            return 0;
+        },
+        [&](int k) {
+            const long long o0 = kHop * p.foff[k], cnt = kHop * (p.foff[k + 1] - p.foff[k]);
+            HIP_TRY(hipMemcpyAsync(h_out + o0, w.out.d + o0, (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+            return 0;
+        },
+        [&](int k) {
+            const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+            const long long b0 = kHop * p.B[k];
+            run_copies(pool, 0, p.nact[k], bpre[k].data(), nullptr, &scope.all, small,
+                       [=](int j) { copy_stream(out[ix[j]] + b0, h_out + offs[j], (size_t)lens[j] * sizeof(short)); });
+        });
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
-/* The wideband (16 kHz) mode from host buffers: denoise_utterances_slices above for sea_wb_denoise_batch_slice.  The same cut
- * (frames of 160 input samples here), the same three streams and event-driven loop; what differs is what travels: 160 int16
- * up and 80 int16 down per frame, and, where the caller asks for them, 3 + 9 floats of high-band rows down.  Slice k is a
- * batch of its own on the device: its offsets count from the slice's start, so the QMF scratch (two floats per input sample)
- * is one slice's, reused by the next -- the slices' kernels run in order on one stream.  Rows of frames without an output are
- * not written by the kernels and reach the caller as zeros: the slice's rows are cleared on the kernels' stream first.
+/* The wideband (16 kHz) mode from host buffers: the same cut (frames of 160 input samples here), streams and loop as
+ * sea_denoise_utterances, for sea_wb_denoise_batch_slice.  What differs is what travels: 160 int16 up and 80 int16 down per
+ * frame, and, where the caller asks for them, 3 + 9 floats of high-band rows down.  Slice k is a batch of its own on the
+ * device: its offsets count from the slice's start, so the QMF scratch (two floats per input sample) is one slice's, reused by
+ * the next -- the slices' kernels run in order on one stream.  Rows of frames without an output are not written by the
+ * kernels and reach the caller as zeros: the slice's rows are cleared on the kernels' stream first.
  * The state is used even for a list that is not cut: there is one wideband path here, the slice kernels'. */
-static int wb_denoise_utterances_slices(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
-                                        const long *lengths, int n_utt)
+int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
+                              const long *lengths, int n_utt)
 {
     if (n_utt <= 0) return 0;
     if (!in || !out_lp || !lengths) return fail("sea_wb_denoise_utterances: in, out_lp and lengths are required");
@@ -850,176 +778,88 @@ static int wb_denoise_utterances_slices(const short *const *in, short *const *ou
     if (ctx(&dc)) return 1;
     const bool rows = hp_rows != nullptr;
     constexpr long long kIn = SEA_WB_HOP, kOut = SEA_HOP; /* samples per frame up / down */
-    std::vector<int> idx(n_utt);
-    for (int i = 0; i < n_utt; ++i) idx[i] = i;
-    std::stable_sort(idx.begin(), idx.end(), [&](int a, int b) { return lengths[a] > lengths[b]; });
-    std::vector<long long> nfr(n_utt);
-    long long total_fr = 0;
-    for (int j = 0; j < n_utt; ++j) total_fr += (nfr[j] = lengths[idx[j]] / kIn);
+    const long long total_fr = slice_total_frames(lengths, n_utt, kIn);
     t_last_slices = 0;
     if (total_fr == 0) return 0;
-    const long long max_fr = nfr[0];
-    if (max_fr > 0x7fffffffLL - 8) return fail("sea_wb_denoise_utterances: utterance %d is too long", idx[0]);
-    const long long total = total_fr * kIn;
     PipeWs &w = t_ws;
     HIP_TRY(w.bind());
     Pool &pool = Pool::get(w.device);
+    const bool small = total_fr * kIn * 2 < (2 << 20) || pool.size() <= 1;
+    SlicePlan p;
+    slice_plan(p, lengths, n_utt, kIn, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    if (p.max_fr > 0x7fffffffLL - 8) return fail("sea_wb_denoise_utterances: utterance %d is too long", p.idx[0]);
+    const int K = t_last_slices = p.K;
 
-    /* slice boundaries in frames: equal shares of the samples */
-    const bool small = total * 2 < (2 << 20) || pool.size() <= 1;
-    int want = small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8);
-    want = (int)std::min<long long>(std::min(want, kMaxChunks), std::max<long long>(1, max_fr / 8));
-    auto frames_below = [&](long long f) {
-        long long s = 0;
-        for (int j = 0; j < n_utt; ++j) s += std::min(nfr[j], f);
-        return s;
-    };
-    std::vector<long long> B(1, 0);
-    for (int k = 1; k < want; ++k) {
-        long long lo = B.back() + 1, hi = max_fr; /* smallest f with frames_below(f) >= share */
-        const long long share = total_fr * k / want;
-        while (lo < hi) {
-            const long long mid = (lo + hi) / 2;
-            if (frames_below(mid) >= share) hi = mid; else lo = mid + 1;
-        }
-        if (lo >= max_fr) break;
-        B.push_back(lo);
-    }
-    B.push_back(max_fr);
-    const int K = (int)B.size() - 1;
-    t_last_slices = K;
-
-    /* per slice: the active prefix of the sorted list; where the slice starts in the staging (in FRAMES: x 160 in the input,
-     * x 80 in the output, x 3 and x 9 in the rows); offsets (from the slice's start, in input samples) and lengths */
-    std::vector<int> nact(K);
-    std::vector<long long> foff(K + 1, 0);
-    std::vector<size_t> mbase(K + 1, 0);
+    /* slice k starts at frame foff[k] of every staging buffer: x 160 in the input, x 80 in the output, x 3 and x 9 in the rows */
+    const std::vector<long long> &foff = p.foff;
     long long max_slice_fr = 0;
-    for (int k = 0; k < K; ++k) {
-        int n = 0;
-        while (n < n_utt && nfr[n] > B[k]) ++n;
-        nact[k] = n;
-        long long fr = 0;
-        for (int j = 0; j < n; ++j) fr += std::min(nfr[j], B[k + 1]) - B[k];
-        foff[k + 1] = foff[k] + fr;
-        max_slice_fr = std::max(max_slice_fr, fr);
-        mbase[k + 1] = mbase[k] + 2 * (size_t)n;
-    }
+    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
     const size_t n_rows = (size_t)total_fr + 1; /* a slice writes rows [0, its frames): sea_wb_rows' spare row is never touched */
-    HIP_TRY(w.in.ensure((size_t)total));
+    HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
     HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
-    HIP_TRY(w.meta.ensure(mbase[K]));
+    HIP_TRY(w.meta.ensure(p.mbase[K]));
     if (rows) HIP_TRY(w.wb_rows.ensure(12 * n_rows));
     HIP_TRY(w.ensure_state((size_t)n_utt * sea::kWbSliceStateFloats));
     HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
-    std::vector<std::vector<long long>> bpre(K); /* byte prefix per slice: task sizing */
-    for (int k = 0; k < K; ++k) {
-        long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
-        bpre[k].assign(nact[k] + 1, 0);
-        long long o = 0;
-        for (int j = 0; j < nact[k]; ++j) {
-            const long long L = kIn * (std::min(nfr[j], B[k + 1]) - B[k]);
-            offs[j] = o;
-            lens[j] = L;
-            o += L;
-            bpre[k][j + 1] = bpre[k][j] + 2 * L;
-        }
-    }
+    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kIn, false, w.meta.h);
 
-    std::vector<Latch> packed(K), unpacked(K);
+    std::vector<Latch> packed(K);
     Scope scope(&w);
     short *h_in = w.in.h, *h_out = w.out.h;
     float *h_hp = rows ? w.wb_rows.h : nullptr, *h_code = rows ? w.wb_rows.h + 3 * n_rows : nullptr;
     float *d_hp = rows ? w.wb_rows.d : nullptr, *d_code = rows ? w.wb_rows.d + 3 * n_rows : nullptr;
-    const int *ix = idx.data();
+    const int *ix = p.idx.data();
     for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
-        const long long b0 = kIn * B[k], s0 = kIn * foff[k];
-        run_copies(pool, 0, nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long b0 = kIn * p.B[k], s0 = kIn * foff[k];
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
                    [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
     }
     hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, p.mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
 
-    const char *tr = getenv("SEA_HOST_TRACE");
-    const bool trace = tr && atoi(tr) <= 0;
-    const double t0 = now_ms();
-    enum { kWaitPack, kComputing, kDownloading, kUnpacking };
-    std::vector<char> state(K, kWaitPack);
-    int next = 0, finished = 0;
-    while (finished < K) {
-        bool progressed = false;
-        int r = 0;
-        if (next < K && packed[next].ready() && (next == 0 || (r = evq(w.ev_h2d[next - 1], "hostpipe: upload event")) != 0)) {
-            if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-            const int k = next++;
-            const long long fr = foff[k + 1] - foff[k];
-            if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  wideband slice %d packed (frames %lld..%lld of %d utterances, %.1f MB), issuing\n",
-                               now_ms() - t0, k, B[k], B[k + 1], nact[k], fr * kIn * 2 / 1048576.0);
-            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * foff[k], h_in + kIn * foff[k], (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
+    return run_pipeline(
+        w, scope, packed, "wideband slice", true,
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * f0, h_in + kIn * f0, (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
             HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
             HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
             if (rows) {
-                HIP_TRY(hipMemsetAsync(d_hp + 3 * foff[k], 0, (size_t)fr * 3 * sizeof(float), sKern));
-                HIP_TRY(hipMemsetAsync(d_code + 9 * foff[k], 0, (size_t)fr * 9 * sizeof(float), sKern));
+                HIP_TRY(hipMemsetAsync(d_hp + 3 * f0, 0, (size_t)fr * 3 * sizeof(float), sKern));
+                HIP_TRY(hipMemsetAsync(d_code + 9 * f0, 0, (size_t)fr * 9 * sizeof(float), sKern));
             }
-            if (sea_wb_denoise_batch_slice(w.in.d + kIn * foff[k], w.out.d + kOut * foff[k], nullptr, w.meta.d + mbase[k],
-                                           w.meta.d + mbase[k] + nact[k], nullptr, nullptr, nullptr, rows ? d_hp + 3 * foff[k] : nullptr,
-                                           rows ? d_code + 9 * foff[k] : nullptr, w.d_inter, fr * kIn, w.d_state, nact[k], (int)B[k],
-                                           k > 0, sKern))
+            const long long *d_rows = w.meta.d + p.mbase[k];
+            if (sea_wb_denoise_batch_slice(w.in.d + kIn * f0, w.out.d + kOut * f0, nullptr, d_rows, d_rows + p.nact[k], nullptr, nullptr,
+                                           nullptr, rows ? d_hp + 3 * f0 : nullptr, rows ? d_code + 9 * f0 : nullptr,
+                                           (float *)w.inter.d, fr * kIn, w.state.d, p.nact[k], (int)p.B[k], k > 0, sKern))
                 return 1;
             HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
-            state[k] = kComputing;
-            progressed = true;
-        }
-        for (int k = 0; k < next; ++k) {
-            if (state[k] == kComputing && (r = evq(w.ev_kernel[k], "hostpipe: kernel event")) != 0) {
-                if (r < 0) return 1;
-                const long long fr = foff[k + 1] - foff[k];
-                HIP_TRY(hipMemcpyAsync(h_out + kOut * foff[k], w.out.d + kOut * foff[k], (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
-                if (rows) {
-                    HIP_TRY(hipMemcpyAsync(h_hp + 3 * foff[k], d_hp + 3 * foff[k], (size_t)fr * 3 * sizeof(float), hipMemcpyDeviceToHost, sDown));
-                    HIP_TRY(hipMemcpyAsync(h_code + 9 * foff[k], d_code + 9 * foff[k], (size_t)fr * 9 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+            return 0;
+        },
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            HIP_TRY(hipMemcpyAsync(h_out + kOut * f0, w.out.d + kOut * f0, (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
+            if (rows) {
+                HIP_TRY(hipMemcpyAsync(h_hp + 3 * f0, d_hp + 3 * f0, (size_t)fr * 3 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+                HIP_TRY(hipMemcpyAsync(h_code + 9 * f0, d_code + 9 * f0, (size_t)fr * 9 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+            }
+            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+            return 0;
+        },
+        [&](int k) {
+            const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+            const long long bk = p.B[k], fk = foff[k];
+            run_copies(pool, 0, p.nact[k], bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
+                const long long f0 = fk + offs[j] / kIn, n = lens[j] / kIn; /* the piece's first frame in the staging, its frames */
+                const int u = ix[j];
+                copy_stream(out_lp[u] + kOut * bk, h_out + kOut * f0, (size_t)(n * kOut) * sizeof(short));
+                if (rows && hp_rows[u]) {
+                    copy_stream(hp_rows[u] + 3 * bk, h_hp + 3 * f0, (size_t)n * 3 * sizeof(float));
+                    copy_stream(code_rows[u] + 9 * bk, h_code + 9 * f0, (size_t)n * 9 * sizeof(float));
                 }
-                HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-                state[k] = kDownloading;
-                progressed = true;
-                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  wideband slice %d computed, downloading\n", now_ms() - t0, k);
-            }
-            if (state[k] == kDownloading && (r = evq(w.ev_done[k], "hostpipe: download event")) != 0) {
-                if (r < 0) return 1;
-                if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  wideband slice %d on the host, unpacking\n", now_ms() - t0, k);
-                const long long *offs = w.meta.h + mbase[k], *lens = offs + nact[k];
-                const long long bk = B[k], fk = foff[k];
-                run_copies(pool, 0, nact[k], bpre[k].data(), &unpacked[k], &scope.all, small, [=](int j) {
-                    const long long f0 = fk + offs[j] / kIn, n = lens[j] / kIn; /* the piece's first frame in the staging, its frames */
-                    const int u = ix[j];
-                    copy_stream(out_lp[u] + kOut * bk, h_out + kOut * f0, (size_t)(n * kOut) * sizeof(short));
-                    if (rows && hp_rows[u]) {
-                        copy_stream(hp_rows[u] + 3 * bk, h_hp + 3 * f0, (size_t)n * 3 * sizeof(float));
-                        copy_stream(code_rows[u] + 9 * bk, h_code + 9 * f0, (size_t)n * 9 * sizeof(float));
-                    }
-                });
-                state[k] = kUnpacking;
-                finished++;
-                progressed = true;
-            }
-        }
-        if (!progressed) {
-            if (next < K && !packed[next].ready()) packed[next].wait_for(std::chrono::microseconds(30));
-            else std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
-    scope.all.wait();
-    if (trace) fprintf(stderr, "[hostpipe] %7.3f ms  all unpacked (%d wideband slices)\n", now_ms() - t0, K);
-    scope.ok = true;
-    return 0;
-}
-
-int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
-                              const long *lengths, int n_utt)
-{
-    return wb_denoise_utterances_slices(in, out_lp, hp_rows, code_rows, lengths, n_utt);
+            });
+        });
 }
 
 /* launches the calling thread's last sea_denoise_utterances (time-slice mode) or sea_wb_denoise_utterances call was cut into */
@@ -1035,7 +875,7 @@ int sea_host_last_slices(void) { return t_last_slices; }
  * its samples (a file reader) can write them where the copy engine reads them, and read the results where it writes them:
  *
  *   p = sea_packed_create();                       once per reusable staging set (any thread)
- *   sea_packed_plan(p, lengths, n);                lays the list out: time slices as in denoise_utterances_slices
+ *   sea_packed_plan(p, lengths, n);                lays the list out: the time slices of slice_plan.h, one after the other
  *   k = sea_packed_segments(p, u, in, out, cnt, max);   utterance u = k pieces in time order: fill in[i][0 .. cnt[i])
  *   sea_packed_denoise(p);                         on a device thread: uploads, launches, downloads, pipelined over the slices
  *   ... read out[i][0 .. cnt[i]) ...               etsi_denoise's result for every whole frame (the trailing lengths[u] % 80
@@ -1044,124 +884,50 @@ int sea_host_last_slices(void) { return t_last_slices; }
  * per-utterance state blob) is the calling thread's workspace, as for sea_denoise_utterances. */
 } /* extern "C": the staging set's type and its allocator are C++ */
 struct sea_packed {
-    Grow<short> in, out;      /* only .h is used: pinned, portable */
-    Grow<long long> meta;     /* per slice: offsets | lengths (as the kernel reads them); .d filled at run */
-    std::vector<int> idx, inv, nact;
-    std::vector<long long> nfr, B, soff;
-    std::vector<size_t> mbase;
-    int n_utt = 0, K = 0;
-    long long total = 0;
+    Grow<short> in, out;  /* the pinned halves only: portable, the slices one after the other */
+    Grow<long long> meta; /* the same: per slice the offsets | lengths rows, offsets absolute, as the kernel reads them */
+    SlicePlan plan;       /* frames of 80 samples */
+    int n_utt = 0;
 };
-
-template <class T>
-static hipError_t grow_pinned(Grow<T> &g, size_t n)
-{ /* host side only, portable across devices */
-    if (n <= g.cap) return hipSuccess;
-    if (g.h) (void)hipHostFree(g.h);
-    g.h = nullptr;
-    g.cap = 0;
-    const size_t want = n + n / 4 + 4096;
-    hipError_t e = hipHostMalloc((void **)&g.h, want * sizeof(T), hipHostMallocPortable);
-    if (e == hipSuccess) g.cap = want;
-    return e;
-}
 
 extern "C" {
 
 sea_packed *sea_packed_create(void) { return new (std::nothrow) sea_packed(); }
 
-void sea_packed_destroy(sea_packed *p)
-{
-    if (!p) return;
-    if (p->in.h) (void)hipHostFree(p->in.h);
-    if (p->out.h) (void)hipHostFree(p->out.h);
-    if (p->meta.h) (void)hipHostFree(p->meta.h);
-    p->in.h = p->out.h = nullptr;
-    p->meta.h = nullptr;
-    delete p;
-}
+void sea_packed_destroy(sea_packed *p) { delete p; }
 
 int sea_packed_plan(sea_packed *p, const long *lengths, int n_utt)
 {
     if (!p || n_utt < 0) return fail("sea_packed_plan: bad argument");
     p->n_utt = n_utt;
-    p->K = 0;
-    p->total = 0;
-    if (n_utt == 0) return 0;
+    p->plan.K = 0;
     for (int u = 0; u < n_utt; ++u)
         if (lengths[u] < 0) return fail("negative length for utterance %d", u);
-    p->idx.resize(n_utt);
-    p->inv.resize(n_utt);
-    for (int i = 0; i < n_utt; ++i) p->idx[i] = i;
-    std::stable_sort(p->idx.begin(), p->idx.end(), [&](int a, int b) { return lengths[a] > lengths[b]; });
-    for (int j = 0; j < n_utt; ++j) p->inv[p->idx[j]] = j;
-    p->nfr.resize(n_utt);
-    long long total_fr = 0;
-    for (int j = 0; j < n_utt; ++j) total_fr += (p->nfr[j] = lengths[p->idx[j]] / 80);
-    p->total = total_fr * 80;
-    if (total_fr == 0) return 0;
-    const long long max_fr = p->nfr[0];
+    const long long total = slice_total_frames(lengths, n_utt, SEA_HOP) * SEA_HOP;
     /* slices: SEA_HOST_SLICES, default 10 (tools/host_packed.py on the configs[1] corpus, one box: 4: 4.22 ms, 6: 3.98, 8: 3.84,
      * 10: 3.74, 12: 3.73, 16: 3.82, 24: 3.94 -- without packing to overlap, the optimum is a little finer than the pointer-array
      * entry point's eight) */
-    int want = (p->total * 2 < (2 << 20)) ? 1 : (int)env_mb("SEA_HOST_SLICES", 10);
-    want = (int)std::min<long long>(std::min(want, kMaxChunks), std::max<long long>(1, max_fr / 8));
-    auto frames_below = [&](long long f) {
-        long long s = 0;
-        for (int j = 0; j < n_utt; ++j) s += std::min(p->nfr[j], f);
-        return s;
-    };
-    p->B.assign(1, 0);
-    for (int k = 1; k < want; ++k) {
-        long long lo = p->B.back() + 1, hi = max_fr;
-        const long long share = total_fr * k / want;
-        while (lo < hi) {
-            const long long mid = (lo + hi) / 2;
-            if (frames_below(mid) >= share) hi = mid; else lo = mid + 1;
-        }
-        if (lo >= max_fr) break;
-        p->B.push_back(lo);
-    }
-    p->B.push_back(max_fr);
-    const int K = p->K = (int)p->B.size() - 1;
-    p->nact.assign(K, 0);
-    p->soff.assign(K + 1, 0);
-    p->mbase.assign(K + 1, 0);
-    for (int k = 0; k < K; ++k) {
-        int n = 0;
-        while (n < n_utt && p->nfr[n] > p->B[k]) ++n;
-        p->nact[k] = n;
-        long long smp = 0;
-        for (int j = 0; j < n; ++j) smp += 80 * (std::min(p->nfr[j], p->B[k + 1]) - p->B[k]);
-        p->soff[k + 1] = p->soff[k] + smp;
-        p->mbase[k + 1] = p->mbase[k] + 2 * (size_t)n;
-    }
-    HIP_TRY(grow_pinned(p->in, (size_t)p->total));
-    HIP_TRY(grow_pinned(p->out, (size_t)p->total));
-    HIP_TRY(grow_pinned(p->meta, p->mbase[K]));
-    for (int k = 0; k < K; ++k) {
-        long long *offs = p->meta.h + p->mbase[k], *lens = offs + p->nact[k];
-        long long o = p->soff[k];
-        for (int j = 0; j < p->nact[k]; ++j) {
-            const long long L = 80 * (std::min(p->nfr[j], p->B[k + 1]) - p->B[k]);
-            offs[j] = o;
-            lens[j] = L;
-            o += L;
-        }
-    }
+    SlicePlan &plan = p->plan;
+    slice_plan(plan, lengths, n_utt, SEA_HOP, (total * 2 < (2 << 20)) ? 1 : (int)env_mb("SEA_HOST_SLICES", 10));
+    if (plan.K == 0) return 0;
+    HIP_TRY(p->in.ensure_host((size_t)total, hipHostMallocPortable));
+    HIP_TRY(p->out.ensure_host((size_t)total, hipHostMallocPortable));
+    HIP_TRY(p->meta.ensure_host(plan.mbase[plan.K], hipHostMallocPortable));
+    for (int k = 0; k < plan.K; ++k) slice_rows(plan, k, SEA_HOP, true, p->meta.h + plan.mbase[k], nullptr);
     return 0;
 }
 
-int sea_packed_slices(const sea_packed *p) { return p ? p->K : 0; }
+int sea_packed_slices(const sea_packed *p) { return p ? p->plan.K : 0; }
 
 int sea_packed_segments(const sea_packed *p, int u, short **in_seg, short **out_seg, long *count, int max_seg)
 {
     if (!p || u < 0 || u >= p->n_utt) return 0;
-    const int j = p->inv[u];
+    const SlicePlan &plan = p->plan;
+    const int j = plan.inv[u];
     int n = 0;
-    for (int k = 0; k < p->K && n < max_seg; ++k) {
-        if (j >= p->nact[k]) break; /* the list is sorted by length: no later slice holds this utterance either */
-        const long long *offs = p->meta.h + p->mbase[k], *lens = offs + p->nact[k];
+    for (int k = 0; k < plan.K && n < max_seg; ++k) {
+        if (j >= plan.nact[k]) break; /* the list is sorted by length: no later slice holds this utterance either */
+        const long long *offs = p->meta.h + plan.mbase[k], *lens = offs + plan.nact[k];
         if (in_seg) in_seg[n] = p->in.h + offs[j];
         if (out_seg) out_seg[n] = p->out.h + offs[j];
         if (count) count[n] = (long)lens[j];
@@ -1173,44 +939,30 @@ int sea_packed_segments(const sea_packed *p, int u, short **in_seg, short **out_
 int sea_packed_denoise(sea_packed *p)
 {
     if (!p) return fail("sea_packed_denoise: NULL");
-    if (p->n_utt == 0 || p->K == 0) return 0;
+    const SlicePlan &plan = p->plan;
+    const int K = plan.K;
+    if (p->n_utt == 0 || K == 0) return 0;
     DeviceCtx *dc;
     if (ctx(&dc)) return 1;
     PipeWs &w = t_ws;
     HIP_TRY(w.bind());
-    const int K = p->K, n_utt = p->n_utt;
-    HIP_TRY(w.in.ensure((size_t)p->total)); /* (the workspace's own pinned halves stay unused here) */
-    HIP_TRY(w.out.ensure((size_t)p->total));
-    HIP_TRY(w.meta.ensure(p->mbase[K]));
-    if (K > 1) HIP_TRY(w.ensure_state((size_t)n_utt * sea::kNsPipeStateFloats));
+    HIP_TRY(w.in.ensure_device((size_t)(plan.total_fr * SEA_HOP))); /* the pinned halves are the handle's */
+    HIP_TRY(w.out.ensure_device((size_t)(plan.total_fr * SEA_HOP)));
+    HIP_TRY(w.meta.ensure_device(plan.mbase[K]));
+    if (K > 1) HIP_TRY(w.ensure_state((size_t)p->n_utt * sea::kNsPipeStateFloats));
     Scope scope(&w);
     hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, p->meta.h, p->mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
-    /* uploads in order on one stream, kernels in order on another (slice k needs slice k - 1's state), each download handed
-     * to the runtime when its kernel HAS finished (the copy engines' queues are in order: a download queued behind its
-     * still-running kernel would hold up the next upload) */
+    HIP_TRY(hipMemcpyAsync(w.meta.d, p->meta.h, plan.mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
+    /* Nothing to pack or unpack, so everything is issued up front: uploads in order on one stream, kernels in order on
+     * another (slice k needs slice k - 1's state).  What is left of the pipelines' loop is its rule for downloads: each is
+     * handed to the runtime when its kernel HAS finished (the copy engines' queues are in order: a download queued behind
+     * its still-running kernel would hold up the next upload). */
+    auto soff = [&](int k) { return (long long)SEA_HOP * plan.foff[k]; };
     for (int k = 0; k < K; ++k) {
-        const long long cnt = p->soff[k + 1] - p->soff[k];
-        HIP_TRY(hipMemcpyAsync(w.in.d + p->soff[k], p->in.h + p->soff[k], (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, sUp));
+        HIP_TRY(hipMemcpyAsync(w.in.d + soff(k), p->in.h + soff(k), (size_t)(soff(k + 1) - soff(k)) * sizeof(short), hipMemcpyHostToDevice, sUp));
         HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
         HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
-        sea::NsBatchArgs a = {};
-        a.in = w.in.d;
-        a.out = w.out.d;
-        a.offsets = w.meta.d + p->mbase[k];
-        a.lengths = w.meta.d + p->mbase[k] + p->nact[k];
-        a.tables = dc->ns;
-        a.n_utt = p->nact[k];
-        int form;
-        if (K > 1) {
-            a.state = w.d_state;
-            a.resume = k > 0;
-            a.frame_base = (int)p->B[k];
-            form = (p->nact[k] <= 4 * dc->n_cu) ? 2 : 4;
-        } else
-            form = ns_pick_form(p->nact[k], dc->n_cu);
-        if (form == 2 && p->nact[k] > dc->n_cu) a.prio_row = dc->n_cu;
-        if (ns_launch(a, form, sKern)) return 1;
+        if (ns_launch_slice(w, dc, w.meta.d + plan.mbase[k], plan.nact[k], K, k, (int)plan.B[k], sKern)) return 1;
         HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
     }
     int next = 0;
@@ -1221,8 +973,8 @@ int sea_packed_denoise(sea_packed *p)
             std::this_thread::sleep_for(std::chrono::microseconds(20));
             continue;
         }
-        const long long cnt = p->soff[next + 1] - p->soff[next];
-        HIP_TRY(hipMemcpyAsync(p->out.h + p->soff[next], w.out.d + p->soff[next], (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, sDown));
+        HIP_TRY(hipMemcpyAsync(p->out.h + soff(next), w.out.d + soff(next), (size_t)(soff(next + 1) - soff(next)) * sizeof(short),
+                               hipMemcpyDeviceToHost, sDown));
         ++next;
     }
     HIP_TRY(hipStreamSynchronize(sDown));
@@ -1334,7 +1086,7 @@ int sea_resynth_utterances(const short *const *in, const long *lengths, const fl
     Pool &pool = Pool::get(w.device);
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    long long budget = (long long)((free_b + w.inter_bytes) / 10 * 6);
+    long long budget = (long long)((free_b + w.inter.dcap) / 10 * 6);
     if (const char *e = getenv("SEA_RESYNTH_SCRATCH_MB")) budget = atoll(e) * (1LL << 20);
     /* regions: as many streams as there will be chunks, each at least one utterance */
     long long region = std::max(largest, budget / kStreams);
@@ -1384,7 +1136,7 @@ int sea_resynth_utterances(const short *const *in, const long *lengths, const fl
         }
     const bool small = (total * 4 + rows * 256) < (2 << 20) || n_utt == 1 || pool.size() <= 1;
 
-    std::vector<Latch> packed(nchunk), unpacked(nchunk);
+    std::vector<Latch> packed(nchunk);
     Scope scope(&w);
     short *h_in = w.in.h, *h_out = w.out.h;
     float *h_mask = w.mask.h;
@@ -1403,16 +1155,12 @@ int sea_resynth_utterances(const short *const *in, const long *lengths, const fl
     HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, 3 * (size_t)n_utt * sizeof(long long), hipMemcpyHostToDevice, w.stream[0]));
     HIP_TRY(hipEventRecord(w.ev_meta, w.stream[0]));
 
-    /* event-driven, as in sea_denoise_utterances: the D2H copy of a chunk is issued when its kernel has finished */
-    enum { kWaitPack, kComputing, kDownloading, kUnpacking };
-    std::vector<char> state(nchunk, kWaitPack);
-    int next = 0, finished = 0;
-    while (finished < nchunk) {
-        bool progressed = false;
-        int r = 0;
-        /* a chunk reuses the scratch region and the stream of chunk k - nregion: stream order protects the region */
-        if (next < nchunk && packed[next].ready()) {
-            const int k = next++, r = k % nregion;
+    /* a chunk reuses the scratch region and the stream of chunk k - nregion: stream order protects the region.  Uploads do
+     * not wait for each other: the kernel is six times the copies */
+    return run_pipeline(
+        w, scope, packed, "resynthesis chunk", false,
+        [&](int k) {
+            const int r = k % nregion;
             hipStream_t s = w.stream[r];
             const int u0 = cuts[k], n = cuts[k + 1] - cuts[k];
             const long long o0 = pre[u0], cnt = pre[cuts[k + 1]] - o0, r0 = rpre[u0], rcnt = rpre[cuts[k + 1]] - r0;
@@ -1420,40 +1168,22 @@ int sea_resynth_utterances(const short *const *in, const long *lengths, const fl
             HIP_TRY(hipMemcpyAsync(w.in.d + o0, h_in + o0, (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, s));
             HIP_TRY(hipMemcpyAsync(w.mask.d + r0 * 64, h_mask + r0 * 64, (size_t)rcnt * 64 * sizeof(float), hipMemcpyHostToDevice, s));
             if (sea_resynth64_batch(w.in.d + o0, w.out.d + o0, w.meta.d + u0, w.meta.d + n_utt + u0, w.mask.d + r0 * 64,
-                                    w.meta.d + 2 * n_utt + u0, (float *)((char *)w.d_inter + (size_t)r * region), nullptr, n,
-                                    binary, s))
+                                    w.meta.d + 2 * n_utt + u0, (float *)(w.inter.d + (size_t)r * region), nullptr, n, binary, s))
                 return 1;
             HIP_TRY(hipEventRecord(w.ev_kernel[k], s));
-            state[k] = kComputing;
-            progressed = true;
-        }
-        for (int k = 0; k < next; ++k) {
-            if (state[k] == kComputing && (r = evq(w.ev_kernel[k], "hostpipe: kernel event")) != 0) {
-                if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-                const long long o0 = pre[cuts[k]], cnt = pre[cuts[k + 1]] - o0;
-                hipStream_t s = w.stream[k % nregion];
-                HIP_TRY(hipMemcpyAsync(h_out + o0, w.out.d + o0, (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, s));
-                HIP_TRY(hipEventRecord(w.ev_done[k], s));
-                state[k] = kDownloading;
-                progressed = true;
-            }
-            if (state[k] == kDownloading && (r = evq(w.ev_done[k], "hostpipe: download event")) != 0) {
-                if (r < 0) return 1; /* Scope waits for the pool and drains the streams */
-                run_copies(pool, cuts[k], cuts[k + 1], bp, &unpacked[k], &scope.all, small,
-                           [=](int j) { copy_stream(out[ix[j]], h_out + prep[j], (size_t)lens[j] * sizeof(short)); });
-                state[k] = kUnpacking;
-                finished++;
-                progressed = true;
-            }
-        }
-        if (!progressed) {
-            if (next < nchunk) packed[next].wait_for(std::chrono::microseconds(30));
-            else std::this_thread::sleep_for(std::chrono::microseconds(20));
-        }
-    }
-    scope.all.wait();
-    scope.ok = true;
-    return 0;
+            return 0;
+        },
+        [&](int k) {
+            const long long o0 = pre[cuts[k]], cnt = pre[cuts[k + 1]] - o0;
+            hipStream_t s = w.stream[k % nregion];
+            HIP_TRY(hipMemcpyAsync(h_out + o0, w.out.d + o0, (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipEventRecord(w.ev_done[k], s));
+            return 0;
+        },
+        [&](int k) {
+            run_copies(pool, cuts[k], cuts[k + 1], bp, nullptr, &scope.all, small,
+                       [=](int j) { copy_stream(out[ix[j]], h_out + prep[j], (size_t)lens[j] * sizeof(short)); });
+        });
 }
 
 } // extern "C"

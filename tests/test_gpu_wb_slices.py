@@ -266,8 +266,9 @@ def _batch_rows(sea, utts):
 
 def test_host_pipeline_equals_one_launch(gold):
     """sea_wb_denoise_utterances on (i) the six fixtures plus 31 short synthetic utterances of 0 .. 40 frames, some ragged,
-    one empty, one all-zero, and (ii) a list of ONE utterance of 120 s, which the pipeline must cut into several launches:
-    low band and rows are sea_wb_denoise_batch's bit for bit, and the long utterance run twice gives the same bits twice."""
+    one empty, one all-zero, (ii) a list of ONE utterance of 120 s, and (iii) twelve utterances of 2000 .. 0 frames, some ragged
+    -- a list that is both cut and ragged, so the slices' active prefix shrinks.  The pipeline must cut (ii) and (iii) into
+    several launches: low band and rows are sea_wb_denoise_batch's bit for bit, and a cut list run twice gives the same bits twice."""
     import speech_enhancement_amd as sea
     from speech_enhancement_amd import corpus
     _torch()
@@ -280,11 +281,16 @@ def test_host_pipeline_equals_one_launch(gold):
     assert len(utts) == 37 and sum(len(x) % 160 != 0 for x in utts) >= 10
     long_one = np.tile(corpus.synth_wideband(3, 16000 * 4), 30)
     assert len(long_one) == 16000 * 120
-    for name, lst in (("short list", utts), ("one long utterance", [long_one])):
+    ragged = []
+    for i, n in enumerate((2000, 1500, 1200, 900, 700, 500, 300, 200, 100, 40, 9, 0)):
+        L = 160 * n + (0 if i % 3 else 17 + i)
+        ragged.append(corpus.synth_wideband(100 + i, L) if i % 2 else corpus.synth_utterance(100 + i, L))
+    assert sum(len(x) // 160 for x in ragged) == 7449 and sum(len(x) % 160 != 0 for x in ragged) == 4
+    for name, lst, cut in (("short list", utts, False), ("one long utterance", [long_one], True), ("cut and ragged list", ragged, True)):
         want = _batch_rows(sea, lst)
         got = sea.wb_denoise_utterances(lst, want_hb=True)
         plain = sea.wb_denoise_utterances(lst)
-        if len(lst) == 1:
+        if cut:
             assert got["slices"] > 1 and plain["slices"] > 1, f"{name}: run as {got['slices']} launch(es)"
             again = sea.wb_denoise_utterances(lst, want_hb=True)
         else:
