@@ -187,8 +187,10 @@ long long sea_wb_rows(long long total_padded_samples);
  * tracker.  d_first_out and d_onset (optional) are ABSOLUTE frame indices and have their one-launch meaning once all slices
  * of the utterance have run (until then d_onset is the frames so far while all were zero).  Every whole frame of the slice
  * gets its 80 d_out_lp samples, zeros where it has no output; rows and d_out_f32 are written for frames with an output only.
- * Results are bit for bit those of the one launch: tests/test_gpu_wb_slices.py.  Not carried: sea_wb_compceps_batch and the
- * feature chain, whose windows cross slice boundaries -- keep the float stream and the rows and run them once at the end. */
+ * Results are bit for bit those of the one launch: tests/test_gpu_wb_slices.py.  The feature chain has a slice form of its own
+ * with a state of its own (sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice below).  Not carried:
+ * sea_wb_compceps_batch, the plain cepstrum without WaveProc, whose windows cross slice boundaries -- keep the float stream and
+ * the rows and run it once at the end. */
 int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
                                const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
                                float *d_hp_rows, float *d_code_rows, void *d_scratch, long long total_padded_samples,
@@ -224,6 +226,36 @@ int sea_wb_afe_features_batch(const float *d_out_f32, const unsigned char *d_fla
                               const int *d_first_out, const int *d_onset, const long long *d_ceps_cum, long long total_ceps,
                               float *d_feat_cc, float *d_feat_pp, const long long *d_feat_cum, float *d_feat15, int *d_n_feat,
                               int *d_n_ceps, int n_utt, void *stream);
+/* The feature chain in TIME SLICES: both steps over one slice of every utterance, cut as for sea_wb_denoise_batch_slice.
+ * Step 1: sea_wb_denoise_batch_slice that also stores the speech flags.  d_flag_rows: one byte per per-frame row of THIS
+ * slice, in the row convention of d_hp_rows, written for frames with an output only.  d_out_f32, d_first_out, d_onset,
+ * d_flag_rows, d_hp_rows and d_code_rows are required; everything else it writes is sea_wb_denoise_batch_slice's, bit for bit.
+ * The state is that call's, sea_wb_slice_state_floats () floats per utterance (the speech measures ride in words of the frame
+ * loop's blob that the plain slice call leaves alone: run an utterance through one of the two calls, not a mixture). */
+int sea_wb_denoise_batch_slice_fd(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                                  const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                                  unsigned char *d_flag_rows, float *d_hp_rows, float *d_code_rows, void *d_scratch,
+                                  long long total_padded_samples, float *d_state, int n_utt, int frame_base, int resume,
+                                  void *stream);
+/* Step 2: sea_wb_afe_features_batch over what step 1 left of THIS slice (buffers, d_offsets, d_lengths, frame_base and resume as
+ * there; d_first_out / d_onset absolute, as that call leaves them).  Every output describes the slice: d_feat_cc / d_feat_pp
+ * receive the cepstral frames that COMPLETE in it (frame j of an utterance with first output f0 completes with output frame
+ * f0 + j + 2), capacity per utterance >= the slice's frames; d_feat15 the frames EMITTED during it, in emission order, capacity
+ * >= the slice's frames + 6 (a frame before the onset gives one null vector, a later one completes at most one cepstral frame,
+ * the flush adds six); d_n_feat[u] / d_n_ceps[u] the slice's counts.  Concatenated over an utterance's slices all three are
+ * sea_wb_afe_features_batch's for the whole utterance, bit for bit, and the counts sum to its counts
+ * (tests/test_gpu_wb_afe_slices.py).  DoVADFlush runs only where d_final[u] (optional, one byte per utterance of the slice) is
+ * non-zero: the utterance ends with this slice, which may hold just the ragged tail or nothing at all -- a stream whose end is
+ * learnt late is flushed by an empty slice.  d_afe_state (required) holds sea_wb_afe_slice_state_floats () floats per utterance,
+ * separate from step 1's state and not read when resume == 0: the last three frames of the float stream, the last two
+ * high-band and code rows, PostProc's weights, the VAD's feature buffer, ring of seven and counters. */
+int sea_wb_afe_features_batch_slice(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
+                                    const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,
+                                    const int *d_first_out, const int *d_onset, const unsigned char *d_final,
+                                    const long long *d_ceps_cum, long long total_ceps, float *d_feat_cc, float *d_feat_pp,
+                                    const long long *d_feat_cum, float *d_feat15, int *d_n_feat, int *d_n_ceps, float *d_afe_state,
+                                    int n_utt, int frame_base, int resume, void *stream);
+int sea_wb_afe_slice_state_floats(void);
 /* one utterance from host memory, in the style of etsi_denoise: out_lp[0 .. 80 * (n / 160)) is written */
 int sea_wb_denoise(const short *in, long n, short *out_lp);
 /* the mode's tables as the library computed them (tests): the QMF pair, bands 1..3 of the high band's mel filter
@@ -257,7 +289,8 @@ long long sea_resynth_scratch_bytes(long long total_padded_samples, int n_utt);
 int sea_denoise_utterances(const short *const *in, short *const *out, const long *lengths, int n_utt);
 int sea_host_threads(void); /* size of that pool */
 int sea_host_last_slices(void); /* launches (time slices) the calling thread's last sea_denoise_utterances call in the
-                                 * time-slice mode, or its last sea_wb_denoise_utterances call, was cut into; 0 before any */
+                                 * time-slice mode, or its last sea_wb_denoise_utterances / sea_wb_features_utterances call, was
+                                 * cut into; 0 before any */
 /* The same pipeline for the ETSI wideband (16 kHz) mode (sea_wb_denoise_batch_slice per slice): in[u] holds lengths[u] int16
  * samples at 16 kHz; out_lp[u] receives the 80 * (lengths[u] / 160) low-band samples sea_wb_denoise_batch writes.  hp_rows and
  * code_rows are optional, both or neither; each non-NULL hp_rows[u] (with code_rows[u]) receives 3 (9) floats per frame of
@@ -265,6 +298,13 @@ int sea_host_last_slices(void); /* launches (time slices) the calling thread's l
  * several launches like any list; results do not depend on the cut (tests/test_gpu_wb_slices.py). */
 int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, float *const *hp_rows, float *const *code_rows,
                               const long *lengths, int n_utt);
+/* The wideband FEATURES from host buffers, as sea_denoise_ceps_utterances is for 8 kHz: the same cut and pipeline, per slice
+ * sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice.  feats[u] has room for lengths[u] / 160 + 6 rows of 15 floats
+ * (c1..c12, c0, logE, the VAD flag) and receives sea_wb_afe_features_batch's rows for the utterance, n_feat[u] their number;
+ * out_lp (optional, as a whole) as above.  Only the emitted rows and their counts travel back; the float stream, the flag bytes
+ * and the high-band rows never leave the device.  Results do not depend on the cut (tests/test_gpu_wb_afe_slices.py). */
+int sea_wb_features_utterances(const short *const *in, short *const *out_lp, float *const *feats, int *n_feat,
+                               const long *lengths, int n_utt);
 /* NoiseSup from PINNED staging the caller fills and reads -- no pack / unpack copies (csrc/hostpipe.hip).  For a caller that
  * produces its samples itself (a file reader) and consumes the results itself (a file writer):
  *   p = sea_packed_create();                          a reusable staging set (pinned, portable across devices)

@@ -16,5 +16,6 @@ from ._lib import LIB_PATH, SeaError, load  # noqa: F401
 from .engine import (DoCompCeps, MaskBatch, NoiseSup, PackedBatch, afe_features_batch, compceps_batch,  # noqa: F401
                      compceps_frames, etsi_denoise, gammaToneFilter, irm_target, irm_target_batch, ns_denoise_batch,
                      ns16k_streams_push, ns16k_tables, ns_streams_push, resynth, resynth_batch, resynth_scratch_elems, rfft, rfft_any_batch, rfft_batch, subband_batch, subbband,
-                     tables, wb_afe_features_batch, wb_compceps_batch, wb_denoise, wb_denoise_batch,
-                     wb_denoise_batch_slice, wb_denoise_utterances, wb_rows, wb_slice_state, wb_split, wb_tables)
+                     tables, wb_afe_features_batch, wb_afe_features_batch_slice, wb_afe_slice_state, wb_compceps_batch,
+                     wb_denoise, wb_denoise_batch, wb_denoise_batch_slice, wb_denoise_utterances, wb_features_utterances,
+                     wb_rows, wb_slice_state, wb_split, wb_tables)

@@ -43,6 +43,11 @@ PROTOTYPES = {
     "sea_wb_afe_features_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sea_wb_denoise_batch_slice": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _vp]),
     "sea_wb_slice_state_floats": (_i, []),
+    "sea_wb_denoise_batch_slice_fd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _i, _i, _i, _vp]),
+    "sea_wb_afe_features_batch_slice": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _vp, _i, _i, _i, _vp]),
+    "sea_wb_afe_slice_state_floats": (_i, []),
+    "sea_wb_features_utterances": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
     "sea_wb_denoise_utterances": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
     "sea_host_last_slices": (_i, []),
     "sea_wb_denoise": (_i, [_vp, _l, _vp]),

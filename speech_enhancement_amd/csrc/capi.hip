@@ -490,13 +490,11 @@ int sea_wb_denoise_batch_fd(const short *d_in, short *d_out_lp, float *d_out_f32
 
 /* One TIME SLICE of a wideband batch: see include/sea_mi355x.h.  Four launches as in wb_denoise_launch, each the slice form of
  * its kernel; the last one also stores what the next slice starts from. */
-int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
-                               const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
-                               float *d_hp_rows, float *d_code_rows, void *d_scratch, long long total_padded_samples,
-                               float *d_state, int n_utt, int frame_base, int resume, void *stream)
+static int wb_slice_launch(const char *who, const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                           const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                           unsigned char *d_flag_rows, float *d_hp_rows, float *d_code_rows, void *d_scratch,
+                           long long total_padded_samples, float *d_state, int n_utt, int frame_base, int resume, void *stream)
 {
-    const char *who = "sea_wb_denoise_batch_slice";
-    if (n_utt <= 0) return 0;
     if (!d_state) return fail("%s: d_state is required", who);
     if (!d_in || !d_out_lp || !d_offsets || !d_lengths || !d_scratch)
         return fail("%s: input, low-band output, offsets, lengths and scratch are required", who);
@@ -545,7 +543,11 @@ int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_
     a.b.prio_row = (d_order && n_utt > c->n_cu) ? c->n_cu : 0; /* by launch row, as the 8 kHz slices */
     a.in_f32 = lp;
     a.onset = onset;
-    hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_slice_kernel, dim3(n_utt), dim3(256), 0, st, a);
+    a.b.flags_out = d_flag_rows;
+    if (d_flag_rows)
+        hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_fd_slice_kernel, dim3(n_utt), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(sea::ns_denoise_pipe_wb_slice_kernel, dim3(n_utt), dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     if (d_hp_rows) {
         hipLaunchKernelGGL(sea::wb_hb_slice_kernel, dim3((unsigned)n_utt, (unsigned)rows), dim3(64), 0, st, w);
@@ -556,7 +558,92 @@ int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_
     return 0;
 }
 
+int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                               const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                               float *d_hp_rows, float *d_code_rows, void *d_scratch, long long total_padded_samples,
+                               float *d_state, int n_utt, int frame_base, int resume, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    return wb_slice_launch("sea_wb_denoise_batch_slice", d_in, d_out_lp, d_out_f32, d_offsets, d_lengths, d_order, d_first_out,
+                           d_onset, nullptr, d_hp_rows, d_code_rows, d_scratch, total_padded_samples, d_state, n_utt, frame_base,
+                           resume, stream);
+}
+
+/* the same slice + the speech flags of its output frames: what sea_wb_afe_features_batch_slice reads */
+int sea_wb_denoise_batch_slice_fd(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
+                                  const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
+                                  unsigned char *d_flag_rows, float *d_hp_rows, float *d_code_rows, void *d_scratch,
+                                  long long total_padded_samples, float *d_state, int n_utt, int frame_base, int resume,
+                                  void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_out_f32 || !d_first_out || !d_onset || !d_flag_rows || !d_hp_rows || !d_code_rows)
+        return fail("sea_wb_denoise_batch_slice_fd: the float stream, first_out, onset, the flag rows, the high-band rows and the "
+                    "code rows are all required");
+    return wb_slice_launch("sea_wb_denoise_batch_slice_fd", d_in, d_out_lp, d_out_f32, d_offsets, d_lengths, d_order, d_first_out,
+                           d_onset, d_flag_rows, d_hp_rows, d_code_rows, d_scratch, total_padded_samples, d_state, n_utt,
+                           frame_base, resume, stream);
+}
+
 int sea_wb_slice_state_floats(void) { return sea::kWbSliceStateFloats; }
+
+int sea_wb_afe_slice_state_floats(void) { return sea::kWbAfeStateFloats; }
+
+/* The feature chain over one TIME SLICE: see include/sea_mi355x.h.  Two launches as in sea_wb_afe_features_batch, each the slice
+ * form of its kernel (afe_wb_slice_kernel.hip); the second one also stores what the next slice starts from. */
+int sea_wb_afe_features_batch_slice(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
+                                    const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,
+                                    const int *d_first_out, const int *d_onset, const unsigned char *d_final,
+                                    const long long *d_ceps_cum, long long total_ceps, float *d_feat_cc, float *d_feat_pp,
+                                    const long long *d_feat_cum, float *d_feat15, int *d_n_feat, int *d_n_ceps, float *d_afe_state,
+                                    int n_utt, int frame_base, int resume, void *stream)
+{
+    const char *who = "sea_wb_afe_features_batch_slice";
+    if (n_utt <= 0) return 0;
+    if (!d_afe_state) return fail("%s: d_afe_state is required", who);
+    if (!d_out_f32 || !d_flag_rows || !d_hp_rows || !d_code_rows || !d_first_out || !d_onset)
+        return fail("%s: the float stream, the flag rows, the high-band rows, the code rows, first_out and onset are required", who);
+    if (!d_offsets || !d_lengths || !d_ceps_cum || !d_feat_cc || !d_feat_cum || !d_feat15 || !d_n_feat)
+        return fail("%s: offsets, lengths, both prefix sums, feat_cc, feat15 and n_feat are required", who);
+    if (total_ceps < 0) return fail("%s: total_ceps must not be negative", who);
+    if (frame_base < 0) return fail("%s: frame_base must not be negative", who);
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::WbAfeSliceArgs s = {};
+    sea::AfeArgs &a = s.w.a;
+    a.den_f32 = d_out_f32;
+    a.flags = d_flag_rows;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.first_out = d_first_out;
+    a.onset = d_onset;
+    a.ceps_cum = d_ceps_cum;
+    a.feat_cc = d_feat_cc;
+    a.feat_pp = d_feat_pp;
+    a.feat_cum = d_feat_cum;
+    a.feat15 = d_feat15;
+    a.n_feat = d_n_feat;
+    a.n_ceps = d_n_ceps;
+    a.tables = c->cc;
+    a.n_utt = n_utt;
+    s.w.hp_rows = d_hp_rows;
+    s.w.code_rows = d_code_rows;
+    s.w.wb = c->wb;
+    s.final = d_final;
+    s.state = d_afe_state;
+    s.frame_base = frame_base;
+    s.resume = resume != 0;
+    if (total_ceps > 0) {
+        const long long nslot = total_ceps / 8 + n_utt; /* tile slots of 8 frames, as sea_wb_afe_features_batch */
+        constexpr long long kAfeGrid = 8192;
+        const long long want = nslot < kAfeGrid ? nslot : kAfeGrid;
+        hipLaunchKernelGGL(sea::afe_wb_ceps_slice_kernel, dim3((unsigned)want), dim3(64), 0, (hipStream_t)stream, s);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sea::afe_wb_vad_slice_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 
 int sea_wb_afe_features_batch(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
                               const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,

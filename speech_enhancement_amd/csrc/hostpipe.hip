@@ -295,6 +295,8 @@ struct PipeWs {
     Grow<float> wb_rows;   /* sea_wb_denoise_utterances: per frame 3 high-band energies, then per frame 9 code values */
     Grow<char> inter;      /* device only: resynth / wideband QMF scratch, allocated as asked for */
     Grow<float> state;     /* device only: the recursion per utterance between two launches of a time-slice pipeline */
+    Grow<float> feat, afe_state;      /* sea_wb_features_utterances: the emitted rows of every slice; device only: the chain's state */
+    Grow<unsigned char> flag_rows, fin; /* the same: device only, a slice's speech flags; per slice the utterances that end with it */
     hipStream_t stream[kMaxStreams] = {};
     hipEvent_t ev_meta = nullptr, ev_done[kMaxChunks] = {}, ev_kernel[kMaxChunks] = {}, ev_h2d[kMaxChunks] = {};
     int device = -1;
@@ -314,6 +316,10 @@ struct PipeWs {
         wb_rows.release();
         inter.release();
         state.release();
+        feat.release();
+        afe_state.release();
+        flag_rows.release();
+        fin.release();
         for (auto &s : stream) {
             if (s) (void)hipStreamDestroy(s);
             s = nullptr;
@@ -862,7 +868,174 @@ int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, floa
         });
 }
 
-/* launches the calling thread's last sea_denoise_utterances (time-slice mode) or sea_wb_denoise_utterances call was cut into */
+/* ---------------------------------------------------------------------------------------------------- */
+/* The wideband FEATURES from host buffers: sea_wb_denoise_utterances' cut, streams and loop, per slice
+ * sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice on the kernel stream.  What the chain reads of a slice -- the
+ * float stream, the flag bytes, the high-band and code rows, the cepstra before PostProc -- lives in device buffers of one
+ * slice's size, reused by the next slice (the kernels run in order on one stream) and never downloaded.  What travels back is a
+ * slice's block of emitted rows (its frames + 6 per utterance) and the counts.  An utterance's rows of slice k go behind those
+ * of its earlier slices, so where they go is known once the counts of slices 0 .. k - 1 are on the host.  run_pipeline promises
+ * no order here: one pass of its loop may find slice k's kernel or download event "not ready" and slice k + 1's done, so both
+ * download (k + 1) and unpack (k + 1) may come before slice k's.  unpack (k) therefore only notes that slice k has arrived; the
+ * slices' copy tasks are cut strictly in slice order, each as soon as it and every slice before it have arrived, from a running
+ * sum that by then holds exactly the earlier slices' counts.  The tasks need no order among themselves.
+ * d_final is set where an utterance's last planned slice is this one.  An utterance without a whole frame is in no slice: its
+ * result is DoVADFlush on the initial state, six zero rows, written here. */
+int sea_wb_features_utterances(const short *const *in, short *const *out_lp, float *const *feats, int *n_feat,
+                               const long *lengths, int n_utt)
+{
+    const char *who = "sea_wb_features_utterances";
+    if (n_utt <= 0) return 0;
+    if (!in || !feats || !n_feat || !lengths) return fail("%s: in, feats, n_feat and lengths are required", who);
+    for (int u = 0; u < n_utt; ++u) {
+        if (lengths[u] < 0) return fail("%s: negative length for utterance %d", who, u);
+        if (!feats[u]) return fail("%s: feats[%d] is NULL", who, u);
+    }
+    DeviceCtx *dc;
+    if (ctx(&dc)) return 1;
+    constexpr long long kIn = SEA_WB_HOP, kOut = SEA_HOP;
+    const long long total_fr = slice_total_frames(lengths, n_utt, kIn);
+    t_last_slices = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        n_feat[u] = 0;
+        if (lengths[u] / kIn == 0) {
+            memset(feats[u], 0, 6 * 15 * sizeof(float));
+            n_feat[u] = 6;
+        }
+    }
+    if (total_fr == 0) return 0;
+    PipeWs &w = t_ws;
+    HIP_TRY(w.bind());
+    Pool &pool = Pool::get(w.device);
+    const bool small = total_fr * kIn * 2 < (2 << 20) || pool.size() <= 1;
+    SlicePlan p;
+    slice_plan(p, lengths, n_utt, kIn, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
+    const int K = t_last_slices = p.K;
+
+    const std::vector<long long> &foff = p.foff;
+    long long max_slice_fr = 0;
+    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
+    /* meta: the slices' offsets | lengths rows, then per slice the two prefix sums (nact + 1 each); ints: per slice the counts,
+     * then first_out and onset per utterance; feat: slice k's block starts at row foff[k] + 6 * (utterances of the slices before) */
+    const size_t n_act = p.mbase[K] / 2;
+    auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] + 2 * (size_t)k; };
+    auto feat_row = [&](int k) { return foff[k] + 3 * (long long)p.mbase[k]; };
+    const size_t n_feat_rows = (size_t)feat_row(K);
+    HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
+    HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
+    HIP_TRY(w.meta.ensure(cum_base(K)));
+    HIP_TRY(w.ints.ensure(n_act + 2 * (size_t)n_utt));
+    HIP_TRY(w.fin.ensure(n_act));
+    HIP_TRY(w.feat.ensure(n_feat_rows * 15));
+    HIP_TRY(w.f32.ensure_device((size_t)(max_slice_fr * kOut)));
+    HIP_TRY(w.flag_rows.ensure_device((size_t)max_slice_fr + 1));
+    HIP_TRY(w.wb_rows.ensure_device(12 * ((size_t)max_slice_fr + 1)));
+    HIP_TRY(w.ceps.ensure_device((size_t)max_slice_fr * SEA_CC_NCEP));
+    HIP_TRY(w.ensure_state((size_t)n_utt * sea::kWbSliceStateFloats));
+    HIP_TRY(w.afe_state.ensure_device((size_t)n_utt * sea::kWbAfeStateFloats));
+    HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
+    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kIn, false, w.meta.h);
+    for (int k = 0; k < K; ++k) {
+        const int n = p.nact[k];
+        const long long *offs = w.meta.h + p.mbase[k];
+        long long *cc = w.meta.h + cum_base(k), *fc = cc + n + 1;
+        unsigned char *fin = w.fin.h + p.mbase[k] / 2;
+        for (int j = 0; j < n; ++j) {
+            cc[j] = offs[j] / kIn;
+            fc[j] = cc[j] + 6 * (long long)j;
+            fin[j] = p.nfr[j] <= p.B[k + 1];
+        }
+        cc[n] = foff[k + 1] - foff[k];
+        fc[n] = cc[n] + 6 * (long long)n;
+    }
+
+    std::vector<Latch> packed(K);
+    std::vector<long long> pos(n_utt, 0);             /* rows of sorted position j in the slices before next_cut */
+    std::vector<std::vector<long long>> start(K);     /* per slice: where each of its utterances' rows go */
+    std::vector<char> arrived(K, 0);                  /* slice k's rows and counts are on the host */
+    int next_cut = 0;                                 /* the first slice whose copy tasks are not cut yet */
+    Scope scope(&w);
+    short *h_in = w.in.h, *h_out = w.out.h;
+    float *h_feat = w.feat.h;
+    const int *h_cnt = w.ints.h;
+    int *d_first = w.ints.d + n_act, *d_onset = d_first + n_utt;
+    float *d_hp = w.wb_rows.d, *d_code = w.wb_rows.d + 3 * ((size_t)max_slice_fr + 1);
+    const int *ix = p.idx.data();
+    for (int k = 0; k < K; ++k) {
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long b0 = kIn * p.B[k], s0 = kIn * foff[k];
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
+    }
+    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, cum_base(K) * sizeof(long long), hipMemcpyHostToDevice, sUp));
+    HIP_TRY(hipMemcpyAsync(w.fin.d, w.fin.h, n_act, hipMemcpyHostToDevice, sUp));
+
+    const int rc = run_pipeline(
+        w, scope, packed, "wideband feature slice", true,
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            const int n = p.nact[k];
+            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * f0, h_in + kIn * f0, (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
+            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
+            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
+            const long long *d_rows = w.meta.d + p.mbase[k], *d_cc = w.meta.d + cum_base(k);
+            if (sea_wb_denoise_batch_slice_fd(w.in.d + kIn * f0, w.out.d + kOut * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
+                                              d_onset, w.flag_rows.d, d_hp, d_code, (float *)w.inter.d, fr * kIn, w.state.d, n,
+                                              (int)p.B[k], k > 0, sKern))
+                return 1;
+            if (sea_wb_afe_features_batch_slice(w.f32.d, w.flag_rows.d, d_hp, d_code, d_rows, d_rows + n, d_first, d_onset,
+                                                w.fin.d + p.mbase[k] / 2, d_cc, fr, w.ceps.d, nullptr, d_cc + n + 1,
+                                                w.feat.d + 15 * feat_row(k), w.ints.d + p.mbase[k] / 2, nullptr, w.afe_state.d, n,
+                                                (int)p.B[k], k > 0, sKern))
+                return 1;
+            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            return 0;
+        },
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            const long long r0 = feat_row(k), nr = feat_row(k + 1) - r0;
+            if (out_lp)
+                HIP_TRY(hipMemcpyAsync(h_out + kOut * f0, w.out.d + kOut * f0, (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipMemcpyAsync(h_feat + 15 * r0, w.feat.d + 15 * r0, (size_t)nr * 15 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipMemcpyAsync(w.ints.h + p.mbase[k] / 2, w.ints.d + p.mbase[k] / 2, (size_t)p.nact[k] * sizeof(int),
+                                   hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+            return 0;
+        },
+        [&](int arrived_k) {
+            arrived[arrived_k] = 1;
+            for (; next_cut < K && arrived[next_cut]; ++next_cut) { /* in slice order, whatever order the slices arrive in */
+                const int k = next_cut, n = p.nact[k];
+                const long long *offs = w.meta.h + p.mbase[k], *lens = offs + n;
+                const int *cnt = h_cnt + p.mbase[k] / 2;
+                start[k].resize(n);
+                for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
+                    start[k][j] = pos[j];
+                    pos[j] += cnt[j];
+                }
+                const long long *st = start[k].data();
+                const long long bk = p.B[k], fk = foff[k], rk = feat_row(k);
+                run_copies(pool, 0, n, bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
+                    const long long f0 = offs[j] / kIn, nfr = lens[j] / kIn; /* the piece's first frame in the slice, its frames */
+                    const int u = ix[j];
+                    if (out_lp && out_lp[u])
+                        copy_stream(out_lp[u] + kOut * bk, h_out + kOut * (fk + f0), (size_t)(nfr * kOut) * sizeof(short));
+                    if (cnt[j] > 0)
+                        copy_stream(feats[u] + 15 * st[j], h_feat + 15 * (rk + f0 + 6 * (long long)j),
+                                    (size_t)cnt[j] * 15 * sizeof(float));
+                });
+            }
+        });
+    if (rc) return rc;
+    for (int j = 0; j < n_utt; ++j) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
+        if (p.nfr[j] > 0) n_feat[ix[j]] = (int)pos[j];
+    return 0;
+}
+
+/* launches the calling thread's last time-slice pipeline call (sea_denoise_utterances in the time-slice mode,
+ * sea_wb_denoise_utterances, sea_wb_features_utterances) was cut into */
 int sea_host_last_slices(void) { return t_last_slices; }
 
 /* ---------------------------------------------------------------------------------------------------- */

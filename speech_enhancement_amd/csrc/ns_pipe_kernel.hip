@@ -249,7 +249,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     /* time slices (NsBatchArgs::state): the recursion of utterance u between two launches */
     /* (the wideband slices keep more per utterance behind the blob: sea_kernels.h, kWbSliceStateFloats) */
     constexpr int kStateStride = (SLICES && WB) ? kWbSliceStateFloats : kNsPipeStateFloats;
-    float *const blob = (SLICES && !FD && a.state) ? a.state + (size_t)u * kStateStride : nullptr;
+    float *const blob = (SLICES && (!FD || WB) && a.state) ? a.state + (size_t)u * kStateStride : nullptr;
     const bool resume = blob && a.resume;
     constexpr int kBlobLane = 2 * kCirc, kBlobRing = kBlobLane + 12 * 64, kBlobScal = kBlobRing + 3 * kSlots;
     if (resume) { /* the two stage buffers with their mirrors, the tick-indexed rings */
@@ -324,6 +324,11 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         int vCur = 0, tCur = 0, v1 = 0, t1 = 0, v2 = 0, t2 = 0;
         NsFd fdF; /* FD: the frame-dropping VAD's measures (SpeechQVar / Spec / Mel) live here */
         fd_init(fdF);
+        if (FD && resume) { /* the measures between two slices: the blob's scalars 14..20 */
+            const float *q = blob + kBlobScal + 14;
+            fdF.melMean = q[0]; fdF.varMean = q[1]; fdF.accTest = q[2]; fdF.specMean = q[3];
+            fdF.mel0 = q[4]; fdF.specValues = q[5]; fdF.speechInVADQ = q[6];
+        }
         auto intake = [&](long long f) {
             /* the 80-VGPR form has no register left for the lane id across the transform: the allocator would park it
              * (and 8 * lane) in scratch and reload both every frame; two v_mbcnt recompute it instead */
@@ -411,6 +416,11 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         if (WB && SLICES && a.onset_out && lane == 0) /* absolute; the frames so far while there is none */
             a.onset_out[u] = (long long)wbAbs < a.frame_base + nfr ? wbAbs : (int)(a.frame_base + nfr);
         if (blob && lane == 0) blob[kBlobScal + 0] = __int_as_float(tick);
+        if (FD && blob && lane == 0) {
+            float *q = blob + kBlobScal + 14;
+            q[0] = fdF.melMean; q[1] = fdF.varMean; q[2] = fdF.accTest; q[3] = fdF.specMean;
+            q[4] = fdF.mel0; q[5] = fdF.specValues; q[6] = fdF.speechInVADQ;
+        }
         NS_T_FLUSH(0);
 #ifdef SEA_NS_TIMING
         if (blockIdx.x < 4096 && lane == 0) {
@@ -742,6 +752,14 @@ __global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_slice_k
 {
     __shared__ p4::PipeLds<false> L;
     p4::ns_pipe_body<false, false, true, true>(a.b, L, a.in_f32, a.onset);
+}
+
+/* ... and the same slice with the speech flags: one byte per per-frame row of the slice, for the frames with an output.  The
+ * pipeline drains within a launch, so of the frame-dropping VAD's side only the measures' seven floats cross a slice boundary. */
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_fd_slice_kernel(NsWbArgs a)
+{
+    __shared__ p4::PipeLds<false, true> L;
+    p4::ns_pipe_body<true, false, true, true>(a.b, L, a.in_f32, a.onset);
 }
 
 } // namespace sea

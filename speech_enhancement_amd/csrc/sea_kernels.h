@@ -27,7 +27,7 @@ struct NsBatchArgs {
     int *onset_out;            /* per utterance: index of the first non-zero frame (number of frames if none) */
     int prio_row;              /* > 0: workgroups [k * prio_row, (k+1) * prio_row) get issue priority 3 - k - prio_base (four-wave form only) */
     int prio_base;             /* rows to skip: a later chunk of a batch launched in pieces (hostpipe.hip) starts below the first */
-    /* An utterance processed in TIME SLICES, one launch per slice (four-wave forms without speech flags only): state != nullptr
+    /* An utterance processed in TIME SLICES, one launch per slice (four-wave forms; with speech flags the wideband one only): state != nullptr
      * makes every workgroup store its recursion at the end of the launch -- kNsPipeStateFloats floats at state + u * that --
      * and, with resume != 0, start from what the previous slice stored instead of DoNoiseSupInit's state.  in / out /
      * offsets / lengths describe the slice; frame_base = frames of the utterance before this slice (first_out is absolute). */
@@ -115,6 +115,9 @@ struct WbSliceArgs {
 };
 __global__ void wb_qmf_slice_kernel(WbSliceArgs a);   /* as wb_qmf_kernel; the delay line of frame 0 comes from the state */
 __global__ void ns_denoise_pipe_wb_slice_kernel(NsWbArgs a); /* b.state with the stride kWbSliceStateFloats; onset absolute */
+/* + the speech flags, one byte per per-frame row of the SLICE (b.flags_out); the measures' seven floats ride in the blob's
+ * scalars 14..20, which the plain slice form leaves alone */
+__global__ void ns_denoise_pipe_wb_fd_slice_kernel(NsWbArgs a);
 __global__ void wb_hb_slice_kernel(WbSliceArgs a);    /* as wb_hb_kernel; frames before the slice come from the state */
 __global__ void wb_slice_end_kernel(WbSliceArgs a);   /* one workgroup of 128 per utterance: DoSpecSub16k over the slice's rows, then
                                                        * the state's wideband parts for the next slice */
@@ -197,6 +200,41 @@ struct WbAfeArgs {
 };
 __global__ void afe_wb_ceps_kernel(WbAfeArgs a); /* WaveProc + the 26-band CompCeps */
 __global__ void afe_wb_vad_kernel(AfeArgs a);    /* PostProc + frame-dropping VAD + flush on frames of 160 samples */
+
+/* The wideband feature chain over one TIME SLICE (afe_wb_slice_kernel.hip; include/sea_mi355x.h,
+ * sea_wb_afe_features_batch_slice).  Every buffer of w describes the slice as sea_wb_denoise_batch_slice_fd leaves it; first_out
+ * and onset are absolute.  Cepstral frame j of an utterance with first output f0 completes with output frame f0 + j + 2, so the
+ * frames that complete in a slice [fb, fb + n) are j in [max(0, fb - f0 - 2), fb + n - f0 - 2).  What one utterance carries,
+ * kWbAfeStateFloats floats at state + u * that, integers as their bit patterns:
+ *   kAfStF32   240 floats   the last three frames of the low band's float stream (a frame reads from sample 80 (f0 + j) - 1 on:
+ *                           two frames and one sample before the slice), SHIFTED by the slice's frames as kWbStLp is
+ *   kAfStHp    2 x 3        the high-band rows of the last two frames ...
+ *   kAfStCode  2 x 9        ... and their code rows (frame j reads the rows of frame f0 + j, not f0 + j + 2)
+ *   kAfStRing  7 x 16       DoVADProc's ring of feature frames, column 14 the speech flag
+ *   kAfStLane  2 x 16       weightLMS[12] | FeatureBuffer[15]
+ *   kAfStScal  8 ints       focus, hangOver, hCount, vCount, frameCounter, cepstral frames so far, null vectors so far, flushed
+ *                           The last three are DIAGNOSTIC ONLY, kept for whoever inspects a state: no kernel decides anything by
+ *                           them.  Where a slice starts follows from frame_base, first_out and onset alone, and a caller that
+ *                           sets d_final twice for an utterance gets DoVADFlush's six rows twice.
+ * afe_wb_ceps_slice_kernel strides over the slice's tiles and only READS the state; afe_wb_vad_slice_kernel, one wave per
+ * utterance, writes all of it after its reads. */
+constexpr int kAfStF32 = 0;
+constexpr int kAfStKeep = 3 * 80;
+constexpr int kAfStHp = kAfStF32 + kAfStKeep;
+constexpr int kAfStCode = kAfStHp + 8;
+constexpr int kAfStRing = kAfStCode + 24;
+constexpr int kAfStLane = kAfStRing + 7 * 16;
+constexpr int kAfStScal = kAfStLane + 2 * 16;
+constexpr int kWbAfeStateFloats = kAfStScal + 8;
+struct WbAfeSliceArgs {
+    WbAfeArgs w;                /* w.a.flags / w.hp_rows / w.code_rows: the slice's rows; w.a.n_feat / n_ceps: the slice's counts */
+    const unsigned char *final; /* optional, per utterance: non-zero = DoVADFlush after this slice */
+    float *state;               /* [n_utt][kWbAfeStateFloats] */
+    int frame_base;
+    int resume;
+};
+__global__ void afe_wb_ceps_slice_kernel(WbAfeSliceArgs s); /* WaveProc + the 26-band CompCeps of the frames completing in the slice */
+__global__ void afe_wb_vad_slice_kernel(WbAfeSliceArgs s);  /* nulls, PostProc + VAD, flush where final; then the state */
 
 struct ResynthArgs {
     const int16_t *in;

@@ -7,6 +7,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what wb --steps 7      # the ETSI wideband (16 kHz) mode, opt-in
     python tools/bench_extra.py --what wbafe --steps 7   # its feature chain (WaveProc, PostProc, VAD), opt-in
     python tools/bench_extra.py --what wbslices --steps 7  # the wideband mode in time slices and its host pipeline, opt-in
+    python tools/bench_extra.py --what wbafeslices --steps 7  # its feature chain in time slices and from host buffers, opt-in
 """
 import argparse
 import json
@@ -484,6 +485,169 @@ def main():
                                      "ms_sorted": res["low band only"][1],
                                      "with_high_band_rows_ms": res["low band + high-band rows"][0],
                                      "with_high_band_rows_ms_sorted": res["low band + high-band rows"][1]}}), flush=True)
+
+    if "wbafeslices" in what:
+        # The wideband FEATURE CHAIN cut along the TIME axis, on the batch of --what wbafe.  Side by side:
+        #   (i)   sea_wb_denoise_batch_fd + sea_wb_afe_features_batch, the one launch group: the yardstick
+        #   (ii)  the same batch as 8 slices of equal frame shares, sea_wb_denoise_batch_slice_fd +
+        #         sea_wb_afe_features_batch_slice per slice, device only (every slice's packed input is resident)
+        #   (iii) the same chain on ONE slice of one frame per utterance: the fixed cost of a slice's launches
+        #   (iv)  sea_wb_features_utterances from pageable host arrays, wall clock, PCIe inclusive
+        # (i)-(iii): device events around every step, one warm-up step of every form discarded, the steps of the forms
+        # ALTERNATING in one loop, median and the sorted list of each.
+        import ctypes
+        lib = sea.load()
+        wb = wb_batch(batch, dev)
+        n = wb.n_utt
+        lens = np.asarray(wb.host_lengths)
+        nfr = lens // 160
+        frames = int(nfr.sum())
+        host = wb.data.cpu().numpy()
+        utts = [host[o:o + l] for o, l in zip(wb.host_offsets, lens)]
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        class Chain:  # everything one launch group over a PackedBatch reads and writes; ccap / fcap: rows per utterance of feat_cc / feat15
+            def __init__(self, b, ccap, fcap, final=None):
+                half = (b.total // 2 + 7) // 8 * 8
+                rows = int(lib.sea_wb_rows(b.total))
+                z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+                self.b = b
+                self.out, self.f32 = z(half, torch.int16), z(half, torch.float32)
+                self.flg, self.hpr, self.code = z(rows, torch.uint8), z((rows, 3), torch.float32), z((rows, 9), torch.float32)
+                self.scratch = z(int(lib.sea_wb_scratch_bytes(b.total, b.n_utt)) // 4 + 4, torch.float32)
+                ccum = np.concatenate(([0], np.cumsum(ccap))).astype(np.int64)
+                fcum = np.concatenate(([0], np.cumsum(fcap))).astype(np.int64)
+                self.tc = int(ccum[-1])
+                self.fcc, self.f15 = z((max(self.tc, 1), 14), torch.float32), z((max(int(fcum[-1]), 1), 15), torch.float32)
+                self.nfe, self.ncep = z(b.n_utt, torch.int32), z(b.n_utt, torch.int32)
+                self.ccum, self.fcum = torch.from_numpy(ccum).to(dev), torch.from_numpy(fcum).to(dev)
+                self.final = torch.from_numpy(np.asarray(final, np.uint8)).to(dev) if final is not None else None
+        whole = Chain(wb, np.maximum(nfr - 6, 0), nfr + 6)
+        first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        onset = torch.zeros(n, dtype=torch.int32, device=dev)
+
+        def one_launch(denoise=True, features=True):
+            C, b = whole, wb
+            if denoise:
+                rc = lib.sea_wb_denoise_batch_fd(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order), P(first), P(onset),
+                                                 P(C.flg), P(C.hpr), P(C.code), P(C.scratch), b.total, n, st)
+                assert rc == 0, lib.sea_last_error()
+            if features:
+                rc = lib.sea_wb_afe_features_batch(P(C.f32), P(C.flg), P(C.hpr), P(C.code), P(b.offsets), P(b.lengths), P(first), P(onset),
+                                                   P(C.ccum), C.tc, P(C.fcc), None, P(C.fcum), P(C.f15), P(C.nfe), P(C.ncep), n, st)
+                assert rc == 0, lib.sea_last_error()
+        idx = np.argsort(-nfr, kind="stable")
+        snfr = nfr[idx]
+        state = torch.zeros((n, int(lib.sea_wb_slice_state_floats())), dtype=torch.float32, device=dev)
+        afe = torch.zeros((n, int(lib.sea_wb_afe_slice_state_floats())), dtype=torch.float32, device=dev)
+        sfirst, sonset = torch.full_like(first, -1), torch.zeros_like(onset)
+
+        def cut(bounds):
+            pieces = []
+            for b0, b1 in zip(bounds[:-1], bounds[1:]):
+                act = [int(u) for u in idx[snfr > b0]]
+                fr = np.array([min(b1, int(nfr[u])) - b0 for u in act], np.int64)
+                pb = sea.PackedBatch.from_arrays([utts[u][160 * b0:160 * min(b1, int(nfr[u]))] for u in act], dev)
+                pieces.append((b0, Chain(pb, fr, fr + 6, [int(nfr[u]) <= b1 for u in act])))
+            return pieces
+
+        def equal_shares(nslices):  # boundaries with equal shares of the frames, as the host pipeline cuts
+            bounds = [0]
+            for k in range(1, nslices):
+                share = frames * k // nslices
+                f = next(f for f in range(bounds[-1] + 1, int(snfr[0]) + 1) if int(np.minimum(snfr, f).sum()) >= share)
+                if f >= snfr[0]:
+                    break
+                bounds.append(f)
+            return bounds + [int(snfr[0])]
+
+        def run_slices(pieces, denoise=True, features=True):
+            for k, (b0, C) in enumerate(pieces):
+                b = C.b
+                if denoise:
+                    rc = lib.sea_wb_denoise_batch_slice_fd(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order),
+                                                           P(sfirst), P(sonset), P(C.flg), P(C.hpr), P(C.code), P(C.scratch), b.total,
+                                                           P(state), b.n_utt, b0, 1 if k else 0, st)
+                    assert rc == 0, lib.sea_last_error()
+                if features:
+                    rc = lib.sea_wb_afe_features_batch_slice(P(C.f32), P(C.flg), P(C.hpr), P(C.code), P(b.offsets), P(b.lengths),
+                                                             P(sfirst), P(sonset), P(C.final), P(C.ccum), C.tc, P(C.fcc), None,
+                                                             P(C.fcum), P(C.f15), P(C.nfe), P(C.ncep), P(afe), b.n_utt, b0,
+                                                             1 if k else 0, st)
+                    assert rc == 0, lib.sea_last_error()
+        p8 = cut(equal_shares(8))
+        p1 = cut([0, 1])[:1]
+        for _, C in p1:
+            C.final = None  # one frame of every utterance, nothing ends: the launches' fixed cost
+        forms = [("one launch group", one_launch), (f"{len(p8)} slices", lambda: run_slices(p8)),
+                 ("one slice of one frame per utterance", lambda: run_slices(p1)),
+                 # each step alone, on what the whole chain left in place: which of the two accounts for the slices' cost
+                 ("one launch group, step 1 alone", lambda: one_launch(features=False)),
+                 ("one launch group, step 2 alone", lambda: one_launch(denoise=False)),
+                 ("slices, step 1 alone", lambda: run_slices(p8, features=False)),
+                 ("slices, step 2 alone", lambda: run_slices(p8, denoise=False))]
+        steps = max(args.steps, 7)
+        for _, fn in forms:
+            fn()
+        torch.cuda.synchronize()
+        ev = {name: [] for name, _ in forms}
+        for _ in range(steps):
+            for name, fn in forms:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                ev[name].append((a, b))
+        torch.cuda.synchronize()
+        run_slices(p8)  # once more after the one-frame form, for the comparison of the counts below
+        torch.cuda.synchronize()
+        emitted = int(whole.nfe.sum().item())
+        assert sum(int(C.nfe.sum().item()) for _, C in p8) == emitted, "the slices' emitted frames do not sum to the one launch's"
+        med, srt = {}, {}
+        for name, _ in forms:
+            t = sorted(a.elapsed_time(b) for a, b in ev[name])
+            med[name], srt[name] = t[len(t) // 2], [round(v, 3) for v in t]
+        outs = [np.zeros(int(f) * 80, np.int16) for f in nfr]
+        feats = [np.zeros((int(f) + 6, 15), np.float32) for f in nfr]
+        ptr = lambda arrs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs])
+        pin, pout, pfeat = ptr(utts), ptr(outs), ptr(feats)
+        plen = (ctypes.c_long * n)(*[int(l) for l in lens])
+        pnf = (ctypes.c_int * n)()
+        hostres = {}
+        for name, po in (("features only", None), ("features + low band", pout)):
+            rc = lib.sea_wb_features_utterances(pin, po, pfeat, pnf, plen, n)
+            assert rc == 0, lib.sea_last_error()
+            t = []
+            for _ in range(steps):
+                t0 = time.perf_counter()
+                rc = lib.sea_wb_features_utterances(pin, po, pfeat, pnf, plen, n)
+                t.append((time.perf_counter() - t0) * 1e3)
+                assert rc == 0, lib.sea_last_error()
+            t.sort()
+            hostres[name] = (t[len(t) // 2], [round(v, 3) for v in t])
+        assert sum(pnf) == emitted, "the host pipeline's emitted frames are not the one launch's"
+        k8, one, fix = f"{len(p8)} slices", med["one launch group"], med["one slice of one frame per utterance"]
+        print(json.dumps({
+            "metric": "ETSI wideband feature chain in time slices: one launch group | slices | host pipeline (frames of 160 samples/sec)",
+            "value": frames / (med[k8] / 1e3), "unit": "frames/s", "ms_per_step": med[k8],
+            "config": {"workload": f"{n} utterances at 16 kHz: the {args.utts}-utterance corpus + as many wideband signals of the same "
+                                   f"lengths, {frames} frames, {emitted} emitted feature frames; device forms: median of {steps} "
+                                   f"alternating steps after one warm-up; host pipeline: wall clock, median of {steps} calls",
+                       "slices": len(p8), "one_launch_group_ms": one, "one_launch_group_ms_sorted": srt["one launch group"],
+                       "slices_ms": med[k8], "slices_ms_sorted": srt[k8], "ratio_to_one_launch_group": round(med[k8] / one, 3),
+                       "one_frame_slice_ms": fix, "one_frame_slice_ms_sorted": srt["one slice of one frame per utterance"],
+                       "slices_minus_one_launch_ms": round(med[k8] - one, 3), "fixed_cost_of_the_slices_ms": round(len(p8) * fix, 3),
+                       "step1_alone_ms": {"one_launch_group": med["one launch group, step 1 alone"], "slices": med["slices, step 1 alone"],
+                                          "one_launch_group_sorted": srt["one launch group, step 1 alone"], "slices_sorted": srt["slices, step 1 alone"]},
+                       "step2_alone_ms": {"one_launch_group": med["one launch group, step 2 alone"], "slices": med["slices, step 2 alone"],
+                                          "one_launch_group_sorted": srt["one launch group, step 2 alone"], "slices_sorted": srt["slices, step 2 alone"]},
+                       "host_pipeline_ms": hostres["features only"][0], "host_pipeline_ms_sorted": hostres["features only"][1],
+                       "host_pipeline_slices": int(lib.sea_host_last_slices()), "host_threads": lib.sea_host_threads(),
+                       "host_pipeline_with_low_band_ms": hostres["features + low band"][0],
+                       "host_pipeline_with_low_band_ms_sorted": hostres["features + low band"][1]},
+            "kernels": "per slice: sea::wb_qmf_slice_kernel + sea::ns_denoise_pipe_wb_fd_slice_kernel + sea::wb_hb_slice_kernel + "
+                       "sea::wb_slice_end_kernel + sea::afe_wb_ceps_slice_kernel + sea::afe_wb_vad_slice_kernel"}), flush=True)
 
     if "rfft" in what:
         n = 1 << 18
