@@ -60,6 +60,13 @@ def _mixed_corpus():
     return utts
 
 
+def _short_utterances():
+    """1000 seeded utterances of 6 .. 59 frames plus a partial one (test_ns_four_per_cu_any_launch_order)"""
+    from speech_enhancement_amd import corpus
+    rng = np.random.default_rng(7)
+    return [corpus.synth_utterance(300 + k, 80 * int(n) + int(r)) for k, (n, r) in enumerate(zip(rng.integers(6, 60, 1000), rng.integers(0, 80, 1000)))]
+
+
 def test_library_reports_gfx950():
     import speech_enhancement_amd as sea
     _torch()
@@ -160,10 +167,8 @@ def test_ns_four_per_cu_any_launch_order(oracle):
     launch order; a caller may pass any permutation (then the rule is only less sharp): with the library's order, with a shuffled
     one and with none the outputs are the same words, and a spread of utterances equals the oracle."""
     import speech_enhancement_amd as sea
-    from speech_enhancement_amd import corpus
     torch = _torch()
-    rng = np.random.default_rng(7)
-    utts = [corpus.synth_utterance(300 + k, 80 * int(n) + int(r)) for k, (n, r) in enumerate(zip(rng.integers(6, 60, 1000), rng.integers(0, 80, 1000)))]
+    utts = _short_utterances()
     batch = sea.PackedBatch.from_arrays(utts)
     a, _, fa = sea.ns_denoise_batch(batch, use_order=True)
     keep = batch.order.clone()
