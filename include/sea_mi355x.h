@@ -144,6 +144,43 @@ int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags,
                            const long long *d_ceps_cum, long long total_ceps, float *d_feat_cc, float *d_feat_pp,
                            const long long *d_feat_cum, float *d_feat15, int *d_n_feat, int *d_n_ceps, int n_utt,
                            void *stream);
+/* The 8 kHz feature chain in TIME SLICES: both steps over one slice of every utterance, cut as for sea_ns_denoise_batch_slice
+ * (every buffer, d_offsets and d_lengths describe THIS slice, packed like a batch of its own; every slice of an utterance is a
+ * multiple of 80 samples except its last, which may carry the ragged tail and may hold no whole frame at all; frame_base = the
+ * utterance's frames before this slice; resume = 0 for the first slice, whose state is not read).
+ * Step 1: sea_ns_denoise_batch_slice + what sea_ns_denoise_batch_fd stores.  d_flags: one byte per frame of THIS slice with an
+ * output, at [d_offsets[u]/8 + 10*f], f the frame within the slice (buffer of the slice's total_padded_samples/8 bytes), bits as
+ * sea_ns_denoise_batch_fd's; bytes of frames without an output are not written.  d_first_out and d_onset are ABSOLUTE frame
+ * indices and, like d_out_f32, d_flags and d_state, required; d_onset is the first non-zero frame of 80 samples (the gate of
+ * ParmInterface.c:244-251), while every frame so far was zero the frames so far (frame_base + the slice's frames), and after
+ * all slices the one launch's value.  The state is sea_ns_denoise_batch_slice's, sea_ns_slice_state_floats () floats per
+ * utterance: the seven speech measures and the onset ride in words of the frame loop's blob that the plain slice call leaves
+ * alone -- run an utterance through one of the two calls, not a mixture.  Every other output is sea_ns_denoise_batch_slice's,
+ * bit for bit.  One kernel form, the four-wave one, at every batch size. */
+int sea_ns_denoise_batch_slice_fd(const short *d_in, short *d_out, float *d_out_f32, const long long *d_offsets,
+                                  const long long *d_lengths, const int *d_order, int *d_first_out,
+                                  unsigned char *d_flags, int *d_onset, float *d_state, int n_utt,
+                                  int frame_base, int resume, void *stream);
+/* Step 2: sea_afe_features_batch over what step 1 left of THIS slice (d_first_out / d_onset absolute, as that call leaves
+ * them).  Every output describes the slice: d_feat_cc / d_feat_pp receive the cepstral frames that COMPLETE in it (frame j of
+ * an utterance with first output f0 reads the float stream from sample 80 (f0 + j) - 1 and the flag of frame f0 + j + 2: it
+ * completes with output frame f0 + j + 2), capacity per utterance >= the slice's frames; d_feat15 the frames EMITTED during it,
+ * in emission order (a null vector per frame of the slice below the onset, then one row per completed cepstral frame once the
+ * VAD's frame counter passes 10, then the flush), capacity >= the slice's frames + 6; d_n_feat[u] / d_n_ceps[u] the slice's
+ * counts; rows behind the counts are left alone.  Concatenated over an utterance's slices all three are
+ * sea_afe_features_batch's for the whole utterance, bit for bit, and the counts sum to its counts
+ * (tests/test_gpu_afe_slices.py).  DoVADFlush runs only where d_final[u] (optional, one byte per utterance of the slice) is
+ * non-zero: the utterance ends with this slice, which may hold just the ragged tail or nothing at all -- a stream whose end is
+ * learnt late is flushed by an empty slice.  d_afe_state (required) holds sea_afe_slice_state_floats () floats per utterance,
+ * separate from step 1's state and not read when resume == 0: the last three frames of the float stream, PostProc's weights,
+ * the VAD's feature buffer, ring of seven and counters. */
+int sea_afe_features_batch_slice(const float *d_den_f32, const unsigned char *d_flags, const long long *d_offsets,
+                                 const long long *d_lengths, const int *d_first_out, const int *d_onset,
+                                 const unsigned char *d_final, const long long *d_ceps_cum, long long total_ceps,
+                                 float *d_feat_cc, float *d_feat_pp, const long long *d_feat_cum, float *d_feat15,
+                                 int *d_n_feat, int *d_n_ceps, float *d_afe_state, int n_utt, int frame_base,
+                                 int resume, void *stream);
+int sea_afe_slice_state_floats(void);
 /* The ETSI WIDEBAND (16 kHz) mode -- what AdvProcessAlloc (16000) switches on (etsi/cpp/ParmInterface.c:100-108), not the
  * defective wrapper etsi_denoise_16k: frames of 160 samples at 16 kHz, each split by the standard's 118-tap QMF pair into a
  * 0-4 kHz and a 4-8 kHz half (Do16kProcessing, etsi/cpp/16kHzProcessing.c:711-774).  The low half runs through the
@@ -289,8 +326,8 @@ long long sea_resynth_scratch_bytes(long long total_padded_samples, int n_utt);
 int sea_denoise_utterances(const short *const *in, short *const *out, const long *lengths, int n_utt);
 int sea_host_threads(void); /* size of that pool */
 int sea_host_last_slices(void); /* launches (time slices) the calling thread's last sea_denoise_utterances call in the
-                                 * time-slice mode, or its last sea_wb_denoise_utterances / sea_wb_features_utterances call, was
-                                 * cut into; 0 before any */
+                                 * time-slice mode, or its last sea_wb_denoise_utterances / sea_wb_features_utterances /
+                                 * sea_features_utterances call, was cut into; 0 before any */
 /* The same pipeline for the ETSI wideband (16 kHz) mode (sea_wb_denoise_batch_slice per slice): in[u] holds lengths[u] int16
  * samples at 16 kHz; out_lp[u] receives the 80 * (lengths[u] / 160) low-band samples sea_wb_denoise_batch writes.  hp_rows and
  * code_rows are optional, both or neither; each non-NULL hp_rows[u] (with code_rows[u]) receives 3 (9) floats per frame of
@@ -305,6 +342,14 @@ int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, floa
  * and the high-band rows never leave the device.  Results do not depend on the cut (tests/test_gpu_wb_afe_slices.py). */
 int sea_wb_features_utterances(const short *const *in, short *const *out_lp, float *const *feats, int *n_feat,
                                const long *lengths, int n_utt);
+/* The 8 kHz FEATURES from host buffers -- the rows a recogniser consumes: the same cut and pipeline, per slice
+ * sea_ns_denoise_batch_slice_fd + sea_afe_features_batch_slice.  feats[u] has room for lengths[u] / 80 + 6 rows of 15 floats
+ * (c1..c12, c0, logE, the VAD flag) and receives sea_afe_features_batch's rows for the utterance, n_feat[u] their number (an
+ * utterance shorter than 80 samples gives DoVADFlush's six zero rows); out (optional, as a whole) as sea_denoise_utterances
+ * writes it.  Only the emitted rows, their counts and out travel back; the float stream, the flag bytes and the cepstra before
+ * PostProc never leave the device.  Results do not depend on the cut (tests/test_gpu_afe_slices.py). */
+int sea_features_utterances(const short *const *in, short *const *out, float *const *feats, int *n_feat,
+                            const long *lengths, int n_utt);
 /* NoiseSup from PINNED staging the caller fills and reads -- no pack / unpack copies (csrc/hostpipe.hip).  For a caller that
  * produces its samples itself (a file reader) and consumes the results itself (a file writer):
  *   p = sea_packed_create();                          a reusable staging set (pinned, portable across devices)

@@ -35,6 +35,11 @@ PROTOTYPES = {
     "sea_ns_kernel_form": (_i, [_i]),
     "sea_ns_denoise_batch_fd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sea_afe_features_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sea_ns_denoise_batch_slice_fd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sea_afe_features_batch_slice": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i,
+                                          _vp]),
+    "sea_afe_slice_state_floats": (_i, []),
+    "sea_features_utterances": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
     "sea_wb_denoise_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _i, _vp]),
     "sea_wb_scratch_bytes": (_ll, [_ll, _i]),
     "sea_wb_rows": (_ll, [_ll]),

@@ -381,6 +381,98 @@ int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags,
     return 0;
 }
 
+/* The 8 kHz feature chain in TIME SLICES: see include/sea_mi355x.h.  Step 1: sea_ns_denoise_batch_slice + what
+ * sea_ns_denoise_batch_fd stores.  One kernel form, the four-wave one, at every batch size. */
+int sea_ns_denoise_batch_slice_fd(const short *d_in, short *d_out, float *d_out_f32, const long long *d_offsets,
+                                  const long long *d_lengths, const int *d_order, int *d_first_out,
+                                  unsigned char *d_flags, int *d_onset, float *d_state, int n_utt,
+                                  int frame_base, int resume, void *stream)
+{
+    const char *who = "sea_ns_denoise_batch_slice_fd";
+    if (n_utt <= 0) return 0;
+    if (!d_state) return fail("%s: d_state is required", who);
+    if (!d_in || !d_out || !d_offsets || !d_lengths) return fail("%s: input, output, offsets and lengths are required", who);
+    if (!d_out_f32 || !d_first_out || !d_flags || !d_onset)
+        return fail("%s: the float stream, first_out, flags and onset outputs are all required", who);
+    if (frame_base < 0) return fail("%s: frame_base must not be negative", who);
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::NsBatchArgs a = {};
+    a.in = d_in;
+    a.out = d_out;
+    a.out_f32 = d_out_f32;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.order = d_order;
+    a.first_out = d_first_out;
+    a.tables = c->ns;
+    a.n_utt = n_utt;
+    a.flags_out = d_flags;
+    a.onset_out = d_onset;
+    a.state = d_state;
+    a.resume = resume != 0;
+    a.frame_base = frame_base;
+    a.prio_row = (d_order && n_utt > c->n_cu) ? c->n_cu : 0; /* by launch row, as sea_ns_denoise_batch_slice's form 2 */
+    hipLaunchKernelGGL(sea::ns_denoise_pipe_fd_slice_kernel, dim3(n_utt), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_afe_slice_state_floats(void) { return sea::kAfeStateFloats; }
+
+/* Step 2 over one TIME SLICE: two launches as in sea_afe_features_batch, each the slice form of its kernel
+ * (afe_slice_kernel.hip); the second one also stores what the next slice starts from. */
+int sea_afe_features_batch_slice(const float *d_den_f32, const unsigned char *d_flags, const long long *d_offsets,
+                                 const long long *d_lengths, const int *d_first_out, const int *d_onset,
+                                 const unsigned char *d_final, const long long *d_ceps_cum, long long total_ceps,
+                                 float *d_feat_cc, float *d_feat_pp, const long long *d_feat_cum, float *d_feat15,
+                                 int *d_n_feat, int *d_n_ceps, float *d_afe_state, int n_utt, int frame_base,
+                                 int resume, void *stream)
+{
+    const char *who = "sea_afe_features_batch_slice";
+    if (n_utt <= 0) return 0;
+    if (!d_afe_state) return fail("%s: d_afe_state is required", who);
+    if (!d_den_f32 || !d_flags || !d_first_out || !d_onset)
+        return fail("%s: the float stream, the flags, first_out and onset are required", who);
+    if (!d_offsets || !d_lengths || !d_ceps_cum || !d_feat_cc || !d_feat_cum || !d_feat15 || !d_n_feat)
+        return fail("%s: offsets, lengths, both prefix sums, feat_cc, feat15 and n_feat are required", who);
+    if (total_ceps < 0) return fail("%s: total_ceps must not be negative", who);
+    if (frame_base < 0) return fail("%s: frame_base must not be negative", who);
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::AfeSliceArgs s = {};
+    sea::AfeArgs &a = s.a;
+    a.den_f32 = d_den_f32;
+    a.flags = d_flags;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.first_out = d_first_out;
+    a.onset = d_onset;
+    a.ceps_cum = d_ceps_cum;
+    a.feat_cc = d_feat_cc;
+    a.feat_pp = d_feat_pp;
+    a.feat_cum = d_feat_cum;
+    a.feat15 = d_feat15;
+    a.n_feat = d_n_feat;
+    a.n_ceps = d_n_ceps;
+    a.tables = c->cc;
+    a.n_utt = n_utt;
+    s.final = d_final;
+    s.state = d_afe_state;
+    s.frame_base = frame_base;
+    s.resume = resume != 0;
+    if (total_ceps > 0) {
+        const long long nslot = total_ceps / 8 + n_utt; /* tile slots of 8 frames, as sea_afe_features_batch */
+        constexpr long long kAfeGrid = 8192;
+        const long long want = nslot < kAfeGrid ? nslot : kAfeGrid;
+        hipLaunchKernelGGL(sea::afe_ceps_slice_kernel, dim3((unsigned)want), dim3(64), 0, (hipStream_t)stream, s);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sea::afe_vad_slice_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 /* ---- the ETSI wideband (16 kHz) mode: QMF split + NoiseSup on the low band (wb_kernel.hip, ns_pipe_kernel.hip) ---- */
 int sea_wb_tables_host(float *qmfLp118, float *qmfHp118, int *hpMelStart3, int *hpMelLen3, float *hpMelW3x64, float *dct12x26)
 {

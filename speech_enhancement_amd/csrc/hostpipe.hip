@@ -295,7 +295,7 @@ struct PipeWs {
     Grow<float> wb_rows;   /* sea_wb_denoise_utterances: per frame 3 high-band energies, then per frame 9 code values */
     Grow<char> inter;      /* device only: resynth / wideband QMF scratch, allocated as asked for */
     Grow<float> state;     /* device only: the recursion per utterance between two launches of a time-slice pipeline */
-    Grow<float> feat, afe_state;      /* sea_wb_features_utterances: the emitted rows of every slice; device only: the chain's state */
+    Grow<float> feat, afe_state;      /* sea_wb_features_utterances, sea_features_utterances: the emitted rows of every slice; device only: the chain's state */
     Grow<unsigned char> flag_rows, fin; /* the same: device only, a slice's speech flags; per slice the utterances that end with it */
     hipStream_t stream[kMaxStreams] = {};
     hipEvent_t ev_meta = nullptr, ev_done[kMaxChunks] = {}, ev_kernel[kMaxChunks] = {}, ev_h2d[kMaxChunks] = {};
@@ -1034,8 +1034,166 @@ int sea_wb_features_utterances(const short *const *in, short *const *out_lp, flo
     return 0;
 }
 
+/* ---------------------------------------------------------------------------------------------------- */
+/* The 8 kHz FEATURES from host buffers: sea_wb_features_utterances' cut, streams and loop on frames of 80 samples, per slice
+ * sea_ns_denoise_batch_slice_fd + sea_afe_features_batch_slice on the kernel stream.  Slice k is a batch of its own on the
+ * device (offsets from the slice's start), so the float stream, the flag bytes (one per 8 samples) and the cepstra before
+ * PostProc live in device buffers of one slice's size, reused by the next slice and never downloaded.  What travels back is a
+ * slice's block of emitted rows (its frames + 6 per utterance), the counts, and the int16 audio where the caller asks for it.
+ * Where an utterance's rows of slice k go, and why unpack only notes arrivals: as in sea_wb_features_utterances above.
+ * The state is used even for a list that is not cut: there is one path here, the slice kernels'. */
+int sea_features_utterances(const short *const *in, short *const *out, float *const *feats, int *n_feat, const long *lengths,
+                            int n_utt)
+{
+    const char *who = "sea_features_utterances";
+    if (n_utt <= 0) return 0;
+    if (!in || !feats || !n_feat || !lengths) return fail("%s: in, feats, n_feat and lengths are required", who);
+    for (int u = 0; u < n_utt; ++u) {
+        if (lengths[u] < 0) return fail("%s: negative length for utterance %d", who, u);
+        if (!feats[u]) return fail("%s: feats[%d] is NULL", who, u);
+    }
+    DeviceCtx *dc;
+    if (ctx(&dc)) return 1;
+    constexpr long long kHop = SEA_HOP;
+    const long long total_fr = slice_total_frames(lengths, n_utt, kHop);
+    t_last_slices = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        n_feat[u] = 0;
+        if (lengths[u] / kHop == 0) { /* in no slice: DoVADFlush on the initial state */
+            memset(feats[u], 0, 6 * 15 * sizeof(float));
+            n_feat[u] = 6;
+        }
+    }
+    if (total_fr == 0) return 0;
+    PipeWs &w = t_ws;
+    HIP_TRY(w.bind());
+    Pool &pool = Pool::get(w.device);
+    /* "small list -> one slice" is sea_wb_features_utterances' rule, in FRAMES: a frame costs this chain what it costs the
+     * wideband one (the frame loop and the tile are the same), so the list too small to cut is one of 2 MB / 320 B = 6553 frames */
+    const bool small = total_fr * SEA_WB_HOP * 2 < (2 << 20) || pool.size() <= 1;
+    SlicePlan p;
+    slice_plan(p, lengths, n_utt, kHop, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
+    const int K = t_last_slices = p.K;
+
+    const std::vector<long long> &foff = p.foff;
+    long long max_slice_fr = 0;
+    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
+    /* meta: the slices' offsets | lengths rows, then per slice the two prefix sums (nact + 1 each); ints: per slice the counts,
+     * then first_out and onset per utterance; feat: slice k's block starts at row foff[k] + 6 * (utterances of the slices before) */
+    const size_t n_act = p.mbase[K] / 2;
+    auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] + 2 * (size_t)k; };
+    auto feat_row = [&](int k) { return foff[k] + 3 * (long long)p.mbase[k]; };
+    const size_t n_feat_rows = (size_t)feat_row(K);
+    HIP_TRY(w.in.ensure((size_t)(total_fr * kHop)));
+    HIP_TRY(w.out.ensure((size_t)(total_fr * kHop)));
+    HIP_TRY(w.meta.ensure(cum_base(K)));
+    HIP_TRY(w.ints.ensure(n_act + 2 * (size_t)n_utt));
+    HIP_TRY(w.fin.ensure(n_act));
+    HIP_TRY(w.feat.ensure(n_feat_rows * 15));
+    HIP_TRY(w.f32.ensure_device((size_t)(max_slice_fr * kHop)));
+    HIP_TRY(w.flag_rows.ensure_device((size_t)max_slice_fr * 10 + 1)); /* one byte per 8 samples of the slice */
+    HIP_TRY(w.ceps.ensure_device((size_t)max_slice_fr * SEA_CC_NCEP));
+    HIP_TRY(w.ensure_state((size_t)n_utt * sea::kNsPipeStateFloats));
+    HIP_TRY(w.afe_state.ensure_device((size_t)n_utt * sea::kAfeStateFloats));
+    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kHop, false, w.meta.h);
+    for (int k = 0; k < K; ++k) {
+        const int n = p.nact[k];
+        const long long *offs = w.meta.h + p.mbase[k];
+        long long *cc = w.meta.h + cum_base(k), *fc = cc + n + 1;
+        unsigned char *fin = w.fin.h + p.mbase[k] / 2;
+        for (int j = 0; j < n; ++j) {
+            cc[j] = offs[j] / kHop;
+            fc[j] = cc[j] + 6 * (long long)j;
+            fin[j] = p.nfr[j] <= p.B[k + 1];
+        }
+        cc[n] = foff[k + 1] - foff[k];
+        fc[n] = cc[n] + 6 * (long long)n;
+    }
+
+    std::vector<Latch> packed(K);
+    std::vector<long long> pos(n_utt, 0);             /* rows of sorted position j in the slices before next_cut */
+    std::vector<std::vector<long long>> start(K);     /* per slice: where each of its utterances' rows go */
+    std::vector<char> arrived(K, 0);                  /* slice k's rows and counts are on the host */
+    int next_cut = 0;                                 /* the first slice whose copy tasks are not cut yet */
+    Scope scope(&w);
+    short *h_in = w.in.h, *h_out = w.out.h;
+    float *h_feat = w.feat.h;
+    const int *h_cnt = w.ints.h;
+    int *d_first = w.ints.d + n_act, *d_onset = d_first + n_utt;
+    const int *ix = p.idx.data();
+    for (int k = 0; k < K; ++k) {
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long b0 = kHop * p.B[k], s0 = kHop * foff[k];
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
+    }
+    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, cum_base(K) * sizeof(long long), hipMemcpyHostToDevice, sUp));
+    HIP_TRY(hipMemcpyAsync(w.fin.d, w.fin.h, n_act, hipMemcpyHostToDevice, sUp));
+
+    const int rc = run_pipeline(
+        w, scope, packed, "feature slice", true,
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            const int n = p.nact[k];
+            HIP_TRY(hipMemcpyAsync(w.in.d + kHop * f0, h_in + kHop * f0, (size_t)(fr * kHop) * sizeof(short), hipMemcpyHostToDevice, sUp));
+            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
+            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
+            const long long *d_rows = w.meta.d + p.mbase[k], *d_cc = w.meta.d + cum_base(k);
+            if (sea_ns_denoise_batch_slice_fd(w.in.d + kHop * f0, w.out.d + kHop * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
+                                              w.flag_rows.d, d_onset, w.state.d, n, (int)p.B[k], k > 0, sKern))
+                return 1;
+            if (sea_afe_features_batch_slice(w.f32.d, w.flag_rows.d, d_rows, d_rows + n, d_first, d_onset, w.fin.d + p.mbase[k] / 2,
+                                             d_cc, fr, w.ceps.d, nullptr, d_cc + n + 1, w.feat.d + 15 * feat_row(k),
+                                             w.ints.d + p.mbase[k] / 2, nullptr, w.afe_state.d, n, (int)p.B[k], k > 0, sKern))
+                return 1;
+            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            return 0;
+        },
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            const long long r0 = feat_row(k), nr = feat_row(k + 1) - r0;
+            if (out)
+                HIP_TRY(hipMemcpyAsync(h_out + kHop * f0, w.out.d + kHop * f0, (size_t)(fr * kHop) * sizeof(short), hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipMemcpyAsync(h_feat + 15 * r0, w.feat.d + 15 * r0, (size_t)nr * 15 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipMemcpyAsync(w.ints.h + p.mbase[k] / 2, w.ints.d + p.mbase[k] / 2, (size_t)p.nact[k] * sizeof(int),
+                                   hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+            return 0;
+        },
+        [&](int arrived_k) {
+            arrived[arrived_k] = 1;
+            for (; next_cut < K && arrived[next_cut]; ++next_cut) { /* in slice order, whatever order the slices arrive in */
+                const int k = next_cut, n = p.nact[k];
+                const long long *offs = w.meta.h + p.mbase[k], *lens = offs + n;
+                const int *cnt = h_cnt + p.mbase[k] / 2;
+                start[k].resize(n);
+                for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
+                    start[k][j] = pos[j];
+                    pos[j] += cnt[j];
+                }
+                const long long *st = start[k].data();
+                const long long bk = p.B[k], fk = foff[k], rk = feat_row(k);
+                run_copies(pool, 0, n, bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
+                    const long long f0 = offs[j] / kHop; /* the piece's first frame in the slice */
+                    const int u = ix[j];
+                    if (out && out[u]) /* whole frames only: the trailing partial frame stays untouched, as with etsi_denoise */
+                        copy_stream(out[u] + kHop * bk, h_out + kHop * (fk + f0), (size_t)lens[j] * sizeof(short));
+                    if (cnt[j] > 0)
+                        copy_stream(feats[u] + 15 * st[j], h_feat + 15 * (rk + f0 + 6 * (long long)j),
+                                    (size_t)cnt[j] * 15 * sizeof(float));
+                });
+            }
+        });
+    if (rc) return rc;
+    for (int j = 0; j < n_utt; ++j) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
+        if (p.nfr[j] > 0) n_feat[ix[j]] = (int)pos[j];
+    return 0;
+}
+
 /* launches the calling thread's last time-slice pipeline call (sea_denoise_utterances in the time-slice mode,
- * sea_wb_denoise_utterances, sea_wb_features_utterances) was cut into */
+ * sea_wb_denoise_utterances, sea_wb_features_utterances, sea_features_utterances) was cut into */
 int sea_host_last_slices(void) { return t_last_slices; }
 
 /* ---------------------------------------------------------------------------------------------------- */

@@ -249,9 +249,13 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
     /* time slices (NsBatchArgs::state): the recursion of utterance u between two launches */
     /* (the wideband slices keep more per utterance behind the blob: sea_kernels.h, kWbSliceStateFloats) */
     constexpr int kStateStride = (SLICES && WB) ? kWbSliceStateFloats : kNsPipeStateFloats;
-    float *const blob = (SLICES && (!FD || WB) && a.state) ? a.state + (size_t)u * kStateStride : nullptr;
+    float *const blob = (SLICES && a.state) ? a.state + (size_t)u * kStateStride : nullptr;
     const bool resume = blob && a.resume;
     constexpr int kBlobLane = 2 * kCirc, kBlobRing = kBlobLane + 12 * 64, kBlobScal = kBlobRing + 3 * kSlots;
+    /* the 8 kHz slices with speech flags (ns_denoise_pipe_fd_slice_kernel): the gate's onset crosses slices as an ABSOLUTE
+     * frame index in scalar 21 of the blob; the plain slice forms leave that word, like scalars 14..20, alone */
+    constexpr bool kFdSlice = FD && SLICES && !WB;
+    constexpr int kBlobOnset = kBlobScal + 21;
     if (resume) { /* the two stage buffers with their mirrors, the tick-indexed rings */
         for (int i = threadIdx.x; i < 2 * (kCirc + kMirror); i += 64 * kPipeWaves) {
             const int st = i / (kCirc + kMirror), x = i - st * (kCirc + kMirror);
@@ -316,6 +320,8 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
         }
         int tick = resume ? __float_as_int(blob[kBlobScal + 0]) : 0; /* frames seen since (and including) the first non-zero one */
         int onset = (int)nfr;
+        if (kFdSlice) /* absolute: the carried one once the gate has opened, else the frames so far until it opens below */
+            onset = (resume && tick > 0) ? __float_as_int(blob[kBlobOnset]) : (int)(a.frame_base + nfr);
         /* The intake of a frame (zero-frame gate, int16 -> float, store into its slot of the stage-0 buffer)
          * runs at the BOTTOM of the previous iteration, when its words (requested one iteration earlier still)
          * have long arrived: the new slot is outside every window read during that iteration, and the
@@ -345,7 +351,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             vCur = 0;
             if (any || tick > 0) {
                 vCur = 1;
-                if (FD && tick == 0) onset = (int)f;
+                if (FD && tick == 0) onset = (int)f + (kFdSlice ? a.frame_base : 0);
                 tick++;
                 const float x0 = WB ? v.x : (float)(short)(w & 0xFFFFu), x1 = WB ? v.y : (float)(short)(w >> 16);
                 if (ln < 40) slot_store(L.circ[0], tick, ln, x0, x1);
@@ -421,6 +427,7 @@ __device__ __forceinline__ void ns_pipe_body(const NsBatchArgs &a, PipeLds<ADDR_
             q[0] = fdF.melMean; q[1] = fdF.varMean; q[2] = fdF.accTest; q[3] = fdF.specMean;
             q[4] = fdF.mel0; q[5] = fdF.specValues; q[6] = fdF.speechInVADQ;
         }
+        if (kFdSlice && blob && lane == 0) blob[kBlobOnset] = __int_as_float(onset);
         NS_T_FLUSH(0);
 #ifdef SEA_NS_TIMING
         if (blockIdx.x < 4096 && lane == 0) {
@@ -760,6 +767,16 @@ __global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_wb_fd_slic
 {
     __shared__ p4::PipeLds<false, true> L;
     p4::ns_pipe_body<true, false, true, true>(a.b, L, a.in_f32, a.onset);
+}
+
+/* ns_denoise_pipe_fd_kernel over one TIME SLICE (sea_ns_denoise_batch_slice_fd): ns_denoise_pipe_slice_kernel's carried
+ * recursion + the speech flags, one byte per output frame of the slice at [offsets[u]/8 + 10*fo], fo within the slice.  The
+ * pipeline drains within a launch, so of the frame-dropping VAD's side only the measures' seven floats (scalars 14..20) and
+ * the gate's onset (scalar 21, absolute) cross a slice boundary; first_out and onset_out are absolute. */
+__global__ __launch_bounds__(256, p4::kMinWaves) void ns_denoise_pipe_fd_slice_kernel(NsBatchArgs a)
+{
+    __shared__ p4::PipeLds<false, true> L;
+    p4::ns_pipe_body<true, false, true>(a, L);
 }
 
 } // namespace sea

@@ -27,7 +27,7 @@ struct NsBatchArgs {
     int *onset_out;            /* per utterance: index of the first non-zero frame (number of frames if none) */
     int prio_row;              /* > 0: workgroups [k * prio_row, (k+1) * prio_row) get issue priority 3 - k - prio_base (four-wave form only) */
     int prio_base;             /* rows to skip: a later chunk of a batch launched in pieces (hostpipe.hip) starts below the first */
-    /* An utterance processed in TIME SLICES, one launch per slice (four-wave forms; with speech flags the wideband one only): state != nullptr
+    /* An utterance processed in TIME SLICES, one launch per slice (four-wave forms): state != nullptr
      * makes every workgroup store its recursion at the end of the launch -- kNsPipeStateFloats floats at state + u * that --
      * and, with resume != 0, start from what the previous slice stored instead of DoNoiseSupInit's state.  in / out /
      * offsets / lengths describe the slice; frame_base = frames of the utterance before this slice (first_out is absolute). */
@@ -236,6 +236,33 @@ struct WbAfeSliceArgs {
 __global__ void afe_wb_ceps_slice_kernel(WbAfeSliceArgs s); /* WaveProc + the 26-band CompCeps of the frames completing in the slice */
 __global__ void afe_wb_vad_slice_kernel(WbAfeSliceArgs s);  /* nulls, PostProc + VAD, flush where final; then the state */
 
+/* The 8 kHz feature chain over one TIME SLICE (afe_slice_kernel.hip; include/sea_mi355x.h, sea_afe_features_batch_slice): the
+ * wideband slice form above without the high-band and code rows.  Every buffer of a describes the slice as
+ * sea_ns_denoise_batch_slice_fd leaves it (den_f32 at offsets[u], the flag byte of the slice's frame f at offsets[u]/8 + 10 f);
+ * first_out and onset are absolute.  What one utterance carries, kAfeStateFloats floats at state + u * that, integers as their
+ * bit patterns:
+ *   kAf8StF32   240 floats  the last three frames of the float stream, SHIFTED by the slice's frames (kAfStKeep of them)
+ *   kAf8StRing  7 x 16      DoVADProc's ring of feature frames, column 14 the speech flag
+ *   kAf8StLane  2 x 16      weightLMS[12] | FeatureBuffer[15]
+ *   kAf8StScal  8 ints      focus, hangOver, hCount, vCount, frameCounter, then cepstral frames so far, null vectors so far,
+ *                           flushed: the last three DIAGNOSTIC ONLY, as in the wideband state
+ * afe_ceps_slice_kernel strides over the slice's tiles and only READS the state; afe_vad_slice_kernel, one wave per utterance
+ * and the slice's last launch, writes all of it after its reads. */
+constexpr int kAf8StF32 = 0;
+constexpr int kAf8StRing = kAf8StF32 + kAfStKeep;
+constexpr int kAf8StLane = kAf8StRing + 7 * 16;
+constexpr int kAf8StScal = kAf8StLane + 2 * 16;
+constexpr int kAfeStateFloats = kAf8StScal + 8;
+struct AfeSliceArgs {
+    AfeArgs a;                  /* a.flags: the slice's bytes; a.n_feat / a.n_ceps: the slice's counts */
+    const unsigned char *final; /* optional, per utterance: non-zero = DoVADFlush after this slice */
+    float *state;               /* [n_utt][kAfeStateFloats] */
+    int frame_base;
+    int resume;
+};
+__global__ void afe_ceps_slice_kernel(AfeSliceArgs s); /* WaveProc + CompCeps of the frames completing in the slice */
+__global__ void afe_vad_slice_kernel(AfeSliceArgs s);  /* nulls, PostProc + VAD, flush where final; then the state */
+
 struct ResynthArgs {
     const int16_t *in;
     int16_t *out;
@@ -281,6 +308,9 @@ __global__ void ns_denoise_pipe_big_kernel(NsBatchArgs a); /* lower-register for
 __global__ void ns_denoise_pipe_fd_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_slice_kernel(NsBatchArgs a);     /* time slices: state in / out (NsBatchArgs::state) */
 __global__ void ns_denoise_pipe_big_slice_kernel(NsBatchArgs a);
+/* + the speech flags of the slice's output frames and the gate's onset as an absolute index: the measures' seven floats ride
+ * in the blob's scalars 14..20 and the onset in scalar 21, which the plain slice forms leave alone */
+__global__ void ns_denoise_pipe_fd_slice_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe6_kernel(NsBatchArgs a);    /* six waves per utterance (ns_pipe6_kernel.hip) */
 __global__ void ns_denoise_pipe6_dense_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe6_fd_kernel(NsBatchArgs a); /* + speech flags for the frame-dropping VAD */

@@ -618,6 +618,127 @@ def afe_features_batch(batch, want_intermediates=False):
     return res
 
 
+def ns_slice_state(n_utt, device="cuda"):
+    """The per-utterance state ns_denoise_batch_slice carries from slice to slice: float32 [n_utt, floats per utterance].
+    Its contents do not matter before the first slice (resume = 0 reads none of it)."""
+    return _torch().zeros((n_utt, int(_lib.load().sea_ns_slice_state_floats())), dtype=_torch().float32, device=device)
+
+
+def afe_slice_state(n_utt, device="cuda"):
+    """The per-utterance state afe_features_batch_slice carries from slice to slice, separate from ``ns_slice_state``:
+    float32 [n_utt, floats per utterance].  Its contents do not matter before the first slice."""
+    return _torch().zeros((n_utt, int(_lib.load().sea_afe_slice_state_floats())), dtype=_torch().float32, device=device)
+
+
+def ns_denoise_batch_slice(batch, state, frame_base, resume, want_f32=False, want_flags=False, first_out=None, onset=None,
+                           use_order=True):
+    """One TIME SLICE of an 8 kHz batch (sea_ns_denoise_batch_slice): ``batch`` packs THIS slice's samples of every utterance
+    that has some (utterance u of every slice is the same utterance; every slice of an utterance is a multiple of 80 samples
+    except its last), ``state`` is an ``ns_slice_state`` tensor with a row per utterance, ``frame_base`` the frames of 80
+    samples before this slice, ``resume`` false for the first slice.  Returns a dict for the slice, indexed by the slice's own
+    offsets: out (int16), f32 (float stream or None), first_out (int32 [n], ABSOLUTE frame indices -- pass the previous
+    slice's tensor back in as ``first_out`` and utterances that have ended keep theirs), state.  f32 of frames without an
+    output stays zero.  Concatenated over the slices, everything is bit for bit ns_denoise_batch's.  Asynchronous on the
+    current stream.
+
+    ``want_flags`` runs sea_ns_denoise_batch_slice_fd instead (f32 comes with it): the dict also holds flags, one speech-flag
+    byte per frame with an output at [offsets[u]/8 + 10*f], f within the slice (zero elsewhere), and onset (int32 [n],
+    absolute; pass it on like first_out) -- the input of ``afe_features_batch_slice``."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = batch.data.device
+    n = batch.n_utt
+    if state is None or state.dtype != torch.float32 or not state.is_contiguous() \
+            or state.numel() < n * int(lib.sea_ns_slice_state_floats()):
+        raise ValueError("state must be a contiguous float32 tensor of sea_ns_slice_state_floats() floats per utterance")
+    if want_flags:
+        want_f32 = True
+    out = torch.zeros_like(batch.data)
+    f32 = torch.zeros(batch.total, dtype=torch.float32, device=dev) if want_f32 else None
+    if first_out is None:
+        first_out = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    order = _dptr(batch.order) if use_order else None
+    if want_flags:
+        if onset is None:
+            onset = torch.zeros(n, dtype=torch.int32, device=dev)
+        flags = torch.zeros(max(batch.total // 8, 1), dtype=torch.uint8, device=dev)
+        rc = lib.sea_ns_denoise_batch_slice_fd(_dptr(batch.data), _dptr(out), _dptr(f32), _dptr(batch.offsets),
+                                               _dptr(batch.lengths), order, _dptr(first_out), _dptr(flags), _dptr(onset),
+                                               _dptr(state), n, int(frame_base), 1 if resume else 0, _stream_ptr())
+        _lib.check(rc, "sea_ns_denoise_batch_slice_fd")
+        return dict(out=out, f32=f32, first_out=first_out, onset=onset, flags=flags, state=state)
+    rc = lib.sea_ns_denoise_batch_slice(_dptr(batch.data), _dptr(out), _dptr(f32), _dptr(batch.offsets), _dptr(batch.lengths),
+                                        order, _dptr(first_out), _dptr(state), n, int(frame_base), 1 if resume else 0,
+                                        _stream_ptr())
+    _lib.check(rc, "sea_ns_denoise_batch_slice")
+    return dict(out=out, f32=f32, first_out=first_out, onset=None, flags=None, state=state)
+
+
+def afe_features_batch_slice(batch, den, afe_state, frame_base, resume, final=None, want_pp=False):
+    """The 8 kHz feature chain over one TIME SLICE (sea_afe_features_batch_slice): ``batch`` and ``den`` are the slice's batch
+    and the dict ``ns_denoise_batch_slice(.., want_flags=True)`` returned for it, ``afe_state`` an ``afe_slice_state`` tensor
+    with a row per utterance, ``frame_base`` / ``resume`` as there.  ``final``: per utterance, true where the utterance ends
+    with this slice -- DoVADFlush runs after it (a slice may be empty: a stream whose end is learnt late); None flushes nothing.
+    Returns a dict for THIS slice: feats (list of float32 [n_u, 15] host arrays, the frames emitted during the slice), n_feat /
+    n_ceps (int32 host arrays), feat_cc / feat_pp (device tensors [frames of the slice, 14], the cepstral frames that complete
+    in it; feat_pp None without want_pp), ceps_cum / feat_cum (host prefix sums of the capacities: the slice's frames and the
+    slice's frames + 6), feat15 (the device tensor behind feats); rows behind the counts are zero.
+    Concatenated over the slices of an utterance, everything is bit for bit afe_features_batch's."""
+    torch = _torch()
+    lib = _lib.load()
+    n = batch.n_utt
+    if afe_state is None or afe_state.dtype != torch.float32 or not afe_state.is_contiguous() \
+            or afe_state.numel() < n * int(lib.sea_afe_slice_state_floats()):
+        raise ValueError("afe_state must be a contiguous float32 tensor of sea_afe_slice_state_floats() floats per utterance")
+    dev = batch.data.device
+    nfr = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+    ccum = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
+    fcum = np.concatenate(([0], np.cumsum(nfr + 6))).astype(np.int64)
+    tc, tf = int(ccum[-1]), int(fcum[-1])
+    feat_cc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
+    feat_pp = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev) if want_pp else None
+    feat15 = torch.zeros((max(tf, 1), 15), dtype=torch.float32, device=dev)
+    n_feat = torch.zeros(n, dtype=torch.int32, device=dev)
+    n_ceps = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_ccum, d_fcum = torch.from_numpy(ccum).to(dev), torch.from_numpy(fcum).to(dev)
+    d_final = None
+    if final is not None:
+        d_final = torch.from_numpy(np.asarray(final, dtype=bool).astype(np.uint8)).to(dev)
+        if d_final.numel() != n:
+            raise ValueError("final must hold one entry per utterance of the slice")
+    rc = lib.sea_afe_features_batch_slice(_dptr(den["f32"]), _dptr(den["flags"]), _dptr(batch.offsets), _dptr(batch.lengths),
+                                          _dptr(den["first_out"]), _dptr(den["onset"]), _dptr(d_final), _dptr(d_ccum), tc,
+                                          _dptr(feat_cc), _dptr(feat_pp), _dptr(d_fcum), _dptr(feat15), _dptr(n_feat),
+                                          _dptr(n_ceps), _dptr(afe_state), n, int(frame_base), 1 if resume else 0,
+                                          _stream_ptr())
+    _lib.check(rc, "sea_afe_features_batch_slice")
+    torch.cuda.synchronize()
+    host15, nf, nc = feat15.cpu().numpy(), n_feat.cpu().numpy(), n_ceps.cpu().numpy()
+    return dict(feats=[host15[fcum[u]:fcum[u] + int(nf[u])] for u in range(n)], n_feat=nf, n_ceps=nc, feat_cc=feat_cc,
+                feat_pp=feat_pp, feat15=feat15, ceps_cum=ccum, feat_cum=fcum, afe_state=afe_state)
+
+
+def features_utterances(utterances, want_out=False):
+    """A list of 8 kHz int16 utterances in host memory -> the feature frames a recogniser reads (sea_features_utterances:
+    the host pipeline's time slices with the feature chain run slice by slice on the device).  Returns a dict: feats (list of
+    float32 [n_u, 15] arrays: c1..c12, c0, logE, VAD flag per emitted frame -- what afe_features_batch returns, however the
+    list is cut), out (list of int16 arrays as etsi_denoise writes them with want_out -- the trailing partial frame stays
+    zero -- else None), slices (launches the list was cut into)."""
+    lib = _lib.load()
+    xs = [np.ascontiguousarray(x, dtype=np.int16) for x in utterances]
+    n = len(xs)
+    feats = [np.zeros((x.size // 80 + 6, 15), np.float32) for x in xs]
+    outs = [np.zeros(x.size, np.int16) for x in xs] if want_out else None
+    if n == 0:
+        return dict(feats=feats, out=outs, slices=0)
+    ptrs = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_long * n)(*[x.size for x in xs])
+    n_feat = (ctypes.c_int * n)()
+    rc = lib.sea_features_utterances(ptrs(xs), ptrs(outs) if want_out else None, ptrs(feats), n_feat, lens, n)
+    _lib.check(rc, "sea_features_utterances")
+    return dict(feats=[f[:int(k)] for f, k in zip(feats, n_feat)], out=outs, slices=int(lib.sea_host_last_slices()))
+
+
 def rfft_batch(frames):
     """frames: float32 tensor [n,256] on the GPU -> rfft of every row."""
     torch = _torch()

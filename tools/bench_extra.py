@@ -8,6 +8,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what wbafe --steps 7   # its feature chain (WaveProc, PostProc, VAD), opt-in
     python tools/bench_extra.py --what wbslices --steps 7  # the wideband mode in time slices and its host pipeline, opt-in
     python tools/bench_extra.py --what wbafeslices --steps 7  # its feature chain in time slices and from host buffers, opt-in
+    python tools/bench_extra.py --what afeslices --steps 7  # the 8 kHz feature chain in time slices and from host buffers, opt-in
 """
 import argparse
 import json
@@ -648,6 +649,146 @@ def main():
                        "host_pipeline_with_low_band_ms_sorted": hostres["features + low band"][1]},
             "kernels": "per slice: sea::wb_qmf_slice_kernel + sea::ns_denoise_pipe_wb_fd_slice_kernel + sea::wb_hb_slice_kernel + "
                        "sea::wb_slice_end_kernel + sea::afe_wb_ceps_slice_kernel + sea::afe_wb_vad_slice_kernel"}), flush=True)
+
+    if "afeslices" in what:
+        # The 8 kHz FEATURE CHAIN cut along the TIME axis, on the --utts corpus batch.  Side by side in one process:
+        #   (i)   sea_ns_denoise_batch_fd + sea_afe_features_batch, the one launch group: the baseline to quote against
+        #   (ii)  the same batch as 8 slices of equal frame shares, sea_ns_denoise_batch_slice_fd + sea_afe_features_batch_slice
+        #         per slice, device only (every slice's packed input is resident)
+        #   (iii) sea_features_utterances from pageable host arrays, wall clock, PCIe inclusive
+        # (i), (ii): device events around every step, one warm-up step of either form discarded, the steps of the forms
+        # ALTERNATING in one loop, median and the sorted list of each.
+        import ctypes
+        lib = sea.load()
+        n = batch.n_utt
+        lens = np.asarray(batch.host_lengths)
+        nfr = lens // 80
+        frames = int(nfr.sum())
+        host = batch.data.cpu().numpy()
+        utts = [host[o:o + l] for o, l in zip(batch.host_offsets, lens)]
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        class Chain:  # everything one launch group over a PackedBatch reads and writes; ccap / fcap: rows per utterance of feat_cc / feat15
+            def __init__(self, b, ccap, fcap, final=None):
+                z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+                self.b = b
+                self.out, self.f32 = torch.zeros_like(b.data), z(b.data.numel(), torch.float32)
+                self.flg = z(max(b.total // 8, 1), torch.uint8)
+                ccum = np.concatenate(([0], np.cumsum(ccap))).astype(np.int64)
+                fcum = np.concatenate(([0], np.cumsum(fcap))).astype(np.int64)
+                self.tc = int(ccum[-1])
+                self.fcc, self.f15 = z((max(self.tc, 1), 14), torch.float32), z((max(int(fcum[-1]), 1), 15), torch.float32)
+                self.nfe, self.ncep = z(b.n_utt, torch.int32), z(b.n_utt, torch.int32)
+                self.ccum, self.fcum = torch.from_numpy(ccum).to(dev), torch.from_numpy(fcum).to(dev)
+                self.final = torch.from_numpy(np.asarray(final, np.uint8)).to(dev) if final is not None else None
+        whole = Chain(batch, np.maximum(nfr - 6, 0), nfr + 6)
+        first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+        onset = torch.zeros(n, dtype=torch.int32, device=dev)
+
+        def one_launch(denoise=True, features=True):
+            C, b = whole, batch
+            if denoise:
+                rc = lib.sea_ns_denoise_batch_fd(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order), P(first),
+                                                 P(C.flg), P(onset), n, st)
+                assert rc == 0, lib.sea_last_error()
+            if features:
+                rc = lib.sea_afe_features_batch(P(C.f32), P(C.flg), P(b.offsets), P(b.lengths), P(first), P(onset), P(C.ccum), C.tc,
+                                                P(C.fcc), None, P(C.fcum), P(C.f15), P(C.nfe), P(C.ncep), n, st)
+                assert rc == 0, lib.sea_last_error()
+        idx = np.argsort(-nfr, kind="stable")
+        snfr = nfr[idx]
+        state = torch.zeros((n, int(lib.sea_ns_slice_state_floats())), dtype=torch.float32, device=dev)
+        afe = torch.zeros((n, int(lib.sea_afe_slice_state_floats())), dtype=torch.float32, device=dev)
+        sfirst, sonset = torch.full_like(first, -1), torch.zeros_like(onset)
+        bounds = [0]
+        for k in range(1, 8):  # boundaries with equal shares of the frames, as the host pipeline cuts
+            share = frames * k // 8
+            f = next(f for f in range(bounds[-1] + 1, int(snfr[0]) + 1) if int(np.minimum(snfr, f).sum()) >= share)
+            if f >= snfr[0]:
+                break
+            bounds.append(f)
+        bounds.append(int(snfr[0]))
+        pieces = []
+        for b0, b1 in zip(bounds[:-1], bounds[1:]):
+            act = [int(u) for u in idx[snfr > b0]]
+            fr = np.array([min(b1, int(nfr[u])) - b0 for u in act], np.int64)
+            pb = sea.PackedBatch.from_arrays([utts[u][80 * b0:80 * min(b1, int(nfr[u]))] for u in act], dev)
+            pieces.append((b0, Chain(pb, fr, fr + 6, [int(nfr[u]) <= b1 for u in act])))
+
+        def run_slices(denoise=True, features=True):
+            for k, (b0, C) in enumerate(pieces):
+                b = C.b
+                if denoise:
+                    rc = lib.sea_ns_denoise_batch_slice_fd(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order),
+                                                           P(sfirst), P(C.flg), P(sonset), P(state), b.n_utt, b0, 1 if k else 0, st)
+                    assert rc == 0, lib.sea_last_error()
+                if features:
+                    rc = lib.sea_afe_features_batch_slice(P(C.f32), P(C.flg), P(b.offsets), P(b.lengths), P(sfirst), P(sonset),
+                                                          P(C.final), P(C.ccum), C.tc, P(C.fcc), None, P(C.fcum), P(C.f15), P(C.nfe),
+                                                          P(C.ncep), P(afe), b.n_utt, b0, 1 if k else 0, st)
+                    assert rc == 0, lib.sea_last_error()
+        k8 = f"{len(pieces)} slices"
+        forms = [("one launch group", one_launch), (k8, run_slices),
+                 # each step alone, on what the whole chain left in place: which of the two accounts for the slices' cost
+                 ("one launch group, step 1 alone", lambda: one_launch(features=False)),
+                 ("one launch group, step 2 alone", lambda: one_launch(denoise=False)),
+                 ("slices, step 1 alone", lambda: run_slices(features=False)),
+                 ("slices, step 2 alone", lambda: run_slices(denoise=False))]
+        steps = max(args.steps, 7)
+        for _, fn in forms:
+            fn()
+        torch.cuda.synchronize()
+        ev = {name: [] for name, _ in forms}
+        for _ in range(steps):
+            for name, fn in forms:
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                ev[name].append((a, b))
+        torch.cuda.synchronize()
+        run_slices()  # the whole chain once more after the steps alone, for the comparison of the counts below
+        torch.cuda.synchronize()
+        emitted = int(whole.nfe.sum().item())
+        assert sum(int(C.nfe.sum().item()) for _, C in pieces) == emitted, "the slices' emitted frames do not sum to the one launch's"
+        med, srt = {}, {}
+        for name, _ in forms:
+            t = sorted(a.elapsed_time(b) for a, b in ev[name])
+            med[name], srt[name] = t[len(t) // 2], [round(v, 3) for v in t]
+        feats = [np.zeros((int(f) + 6, 15), np.float32) for f in nfr]
+        ptr = lambda arrs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs])
+        pin, pfeat = ptr(utts), ptr(feats)
+        plen = (ctypes.c_long * n)(*[int(l) for l in lens])
+        pnf = (ctypes.c_int * n)()
+        rc = lib.sea_features_utterances(pin, None, pfeat, pnf, plen, n)
+        assert rc == 0, lib.sea_last_error()
+        t = []
+        for _ in range(steps):
+            t0 = time.perf_counter()
+            rc = lib.sea_features_utterances(pin, None, pfeat, pnf, plen, n)
+            t.append((time.perf_counter() - t0) * 1e3)
+            assert rc == 0, lib.sea_last_error()
+        t.sort()
+        assert sum(pnf) == emitted, "the host pipeline's emitted frames are not the one launch's"
+        one = med["one launch group"]
+        print(json.dumps({
+            "metric": "8 kHz feature chain in time slices: one launch group | slices | host pipeline (frames of 80 samples/sec)",
+            "value": frames / (med[k8] / 1e3), "unit": "frames/s", "ms_per_step": med[k8],
+            "config": {"workload": f"the {args.utts}-utterance corpus at 8 kHz, {frames} frames, {emitted} emitted feature frames; device "
+                                   f"forms: median of {steps} alternating steps after one warm-up; host pipeline: wall clock, median "
+                                   f"of {steps} calls",
+                       "slices": len(pieces), "one_launch_group_ms": one, "one_launch_group_ms_sorted": srt["one launch group"],
+                       "slices_ms": med[k8], "slices_ms_sorted": srt[k8], "ratio_to_one_launch_group": round(med[k8] / one, 3),
+                       "step1_alone_ms": {"one_launch_group": med["one launch group, step 1 alone"], "slices": med["slices, step 1 alone"],
+                                          "one_launch_group_sorted": srt["one launch group, step 1 alone"], "slices_sorted": srt["slices, step 1 alone"]},
+                       "step2_alone_ms": {"one_launch_group": med["one launch group, step 2 alone"], "slices": med["slices, step 2 alone"],
+                                          "one_launch_group_sorted": srt["one launch group, step 2 alone"], "slices_sorted": srt["slices, step 2 alone"]},
+                       "host_pipeline_ms": t[len(t) // 2], "host_pipeline_ms_sorted": [round(v, 3) for v in t],
+                       "host_pipeline_slices": int(lib.sea_host_last_slices()), "host_threads": lib.sea_host_threads()},
+            "kernels": "one launch group: sea::ns_denoise_pipe6_fd_kernel or sea::ns_denoise_pipe_fd_kernel + sea::afe_ceps_kernel + "
+                       "sea::afe_vad_kernel; per slice: sea::ns_denoise_pipe_fd_slice_kernel + sea::afe_ceps_slice_kernel + "
+                       "sea::afe_vad_slice_kernel"}), flush=True)
 
     if "rfft" in what:
         n = 1 << 18
