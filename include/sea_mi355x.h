@@ -181,6 +181,23 @@ int sea_afe_features_batch_slice(const float *d_den_f32, const unsigned char *d_
                                  int *d_n_feat, int *d_n_ceps, float *d_afe_state, int n_utt, int frame_base,
                                  int resume, void *stream);
 int sea_afe_slice_state_floats(void);
+/* The plain CompCeps (sea_compceps_batch: no WaveProc, 14 floats per frame) over one TIME SLICE of every utterance, after
+ * sea_ns_denoise_batch_slice or sea_ns_denoise_batch_slice_fd on the same slice: d_den_f32, d_offsets, d_lengths, frame_base and
+ * resume describe the slice exactly as that call left it; d_first_out is absolute.  Only the float stream and first_out are read
+ * of the producer's outputs.  d_ceps receives the cepstral frames that COMPLETE in the slice (frame j of an utterance with first
+ * output f0 reads the float stream from sample 80 (f0 + j) - 1 for 201 values: it completes with output frame f0 + j + 2), frame
+ * jLo + r of the utterance in row d_ceps_cum[u] + r; d_ceps_cum holds n_utt + 1 prefix sums of per-utterance capacities >= the
+ * slice's frames, total_frames = d_ceps_cum[n_utt]; d_n_ceps[u] is the slice's count, written for every utterance of every
+ * slice, also one that holds only a ragged tail; rows behind the count are left alone.  d_cc_state (required) holds
+ * sea_cc_slice_state_floats () floats per utterance, a blob of its own next to the producer's and not read when resume == 0: the
+ * last three frames of the float stream.  Concatenated over an utterance's slices the rows are sea_compceps_batch's, bit for
+ * bit, and the counts sum to its count (tests/test_gpu_ceps_slices.py).  Two launches on the stream: the tiles, which only read
+ * the state, then one wave per utterance that writes the counts and the state. */
+int sea_compceps_batch_slice(const float *d_den_f32, const long long *d_offsets, const long long *d_lengths,
+                             const int *d_first_out, const long long *d_ceps_cum, long long total_frames,
+                             float *d_ceps, int *d_n_ceps, float *d_cc_state, int n_utt, int frame_base,
+                             int resume, void *stream);
+int sea_cc_slice_state_floats(void);
 /* The ETSI WIDEBAND (16 kHz) mode -- what AdvProcessAlloc (16000) switches on (etsi/cpp/ParmInterface.c:100-108), not the
  * defective wrapper etsi_denoise_16k: frames of 160 samples at 16 kHz, each split by the standard's 118-tap QMF pair into a
  * 0-4 kHz and a 4-8 kHz half (Do16kProcessing, etsi/cpp/16kHzProcessing.c:711-774).  The low half runs through the
@@ -225,9 +242,10 @@ long long sea_wb_rows(long long total_padded_samples);
  * of the utterance have run (until then d_onset is the frames so far while all were zero).  Every whole frame of the slice
  * gets its 80 d_out_lp samples, zeros where it has no output; rows and d_out_f32 are written for frames with an output only.
  * Results are bit for bit those of the one launch: tests/test_gpu_wb_slices.py.  The feature chain has a slice form of its own
- * with a state of its own (sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice below).  Not carried:
- * sea_wb_compceps_batch, the plain cepstrum without WaveProc, whose windows cross slice boundaries -- keep the float stream and
- * the rows and run it once at the end. */
+ * with a state of its own (sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice below).  So has the plain cepstrum
+ * without WaveProc, whose windows cross slice boundaries: sea_wb_compceps_batch_slice below carries the last three frames of the
+ * float stream and the last two rows of either kind from slice to slice.  Neither the float stream nor the rows of earlier
+ * slices need to be kept. */
 int sea_wb_denoise_batch_slice(const short *d_in, short *d_out_lp, float *d_out_f32, const long long *d_offsets,
                                const long long *d_lengths, const int *d_order, int *d_first_out, int *d_onset,
                                float *d_hp_rows, float *d_code_rows, void *d_scratch, long long total_padded_samples,
@@ -239,6 +257,18 @@ int sea_wb_slice_state_floats(void);
 int sea_wb_compceps_batch(const float *d_out_f32, const long long *d_offsets, const long long *d_lengths, const int *d_first_out,
                           const float *d_hp_rows, const float *d_code_rows, const long long *d_ceps_cum, long long total_frames,
                           float *d_ceps, int *d_n_ceps, int n_utt, void *stream);
+/* The wideband CompCeps over one TIME SLICE, as sea_compceps_batch_slice is for 8 kHz (see there): d_out_f32, d_offsets, d_lengths,
+ * d_hp_rows, d_code_rows, frame_base and resume describe the slice exactly as sea_wb_denoise_batch_slice (or _fd) left it, with
+ * the wideband conventions above (the float stream at d_offsets[u] / 2, the rows at ceil (d_offsets[u] / 160) + f, frames of 160
+ * input samples); d_first_out is absolute.  d_cc_state (required) holds sea_wb_cc_slice_state_floats () floats per utterance: the
+ * last three frames of the float stream, the last two high-band rows and the last two code rows.  Concatenated over an
+ * utterance's slices the rows are sea_wb_compceps_batch's, bit for bit, and the counts sum to its count
+ * (tests/test_gpu_ceps_slices.py). */
+int sea_wb_compceps_batch_slice(const float *d_out_f32, const long long *d_offsets, const long long *d_lengths,
+                                const int *d_first_out, const float *d_hp_rows, const float *d_code_rows,
+                                const long long *d_ceps_cum, long long total_frames, float *d_ceps, int *d_n_ceps,
+                                float *d_cc_state, int n_utt, int frame_base, int resume, void *stream);
+int sea_wb_cc_slice_state_floats(void);
 /* The wideband FEATURE CHAIN -- what DoAdvProcess / FlushAdvProcess hand to a recogniser in the AdvProcessAlloc (16000) mode
  * once the block the reference keeps commented out runs (etsi/cpp/ParmInterface.c:274-311, :348-354): NoiseSup -> WaveProc ->
  * CompCeps -> PostProc -> frame-dropping VAD, as sea_ns_denoise_batch_fd + sea_afe_features_batch are for 8 kHz.
@@ -327,7 +357,8 @@ int sea_denoise_utterances(const short *const *in, short *const *out, const long
 int sea_host_threads(void); /* size of that pool */
 int sea_host_last_slices(void); /* launches (time slices) the calling thread's last sea_denoise_utterances call in the
                                  * time-slice mode, or its last sea_wb_denoise_utterances / sea_wb_features_utterances /
-                                 * sea_features_utterances call, was cut into; 0 before any */
+                                 * sea_features_utterances / sea_denoise_ceps_utterances / sea_wb_denoise_ceps_utterances call,
+                                 * was cut into; 0 before any */
 /* The same pipeline for the ETSI wideband (16 kHz) mode (sea_wb_denoise_batch_slice per slice): in[u] holds lengths[u] int16
  * samples at 16 kHz; out_lp[u] receives the 80 * (lengths[u] / 160) low-band samples sea_wb_denoise_batch writes.  hp_rows and
  * code_rows are optional, both or neither; each non-NULL hp_rows[u] (with code_rows[u]) receives 3 (9) floats per frame of
@@ -368,9 +399,19 @@ int sea_packed_segments(const sea_packed *p, int u, short **in_seg, short **out_
 int sea_packed_denoise(sea_packed *p);
 /* NoiseSup + CompCeps from host buffers, the chain ParmInterface.c:275-293 ran before its author commented it out
  * (SURVEY 8(d) Config 1: a 4-s utterance gives 800 NoiseSup frames, 796 outputs, 794 cepstral frames): out as above;
- * ceps[u] receives n_ceps[u] rows of 14 floats (c1..c12, c0, logE), capacity max(lengths[u]/80 - 6, 0) rows. */
+ * ceps[u] receives n_ceps[u] rows of 14 floats (c1..c12, c0, logE), capacity max(lengths[u]/80 - 6, 0) rows.  A list the slice
+ * plan cuts (SEA_HOST_SLICES, default 8; small lists stay in one piece) runs sea_denoise_utterances' pipeline with
+ * sea_ns_denoise_batch_slice + sea_compceps_batch_slice per slice, the float stream sized for one slice; a list in one piece
+ * runs one launch each.  SEA_HOST_CEPS_PIPELINE=0 keeps the one launch for every list.  Results do not depend on the cut
+ * (tests/test_gpu_ceps_slices.py); sea_host_last_slices () reports it. */
 int sea_denoise_ceps_utterances(const short *const *in, short *const *out, float *const *ceps, int *n_ceps,
                                 const long *lengths, int n_utt);
+/* The same for the wideband (16 kHz) mode: sea_wb_denoise_utterances' cut and pipeline, per slice sea_wb_denoise_batch_slice +
+ * sea_wb_compceps_batch_slice.  out_lp (optional, as a whole) as there; ceps[u] receives n_ceps[u] rows of 14 floats,
+ * sea_wb_compceps_batch's, capacity max(lengths[u]/160 - 6, 0) rows.  Only out_lp, the cepstral rows and their counts travel
+ * back: the float stream and the high-band and code rows are sized for one slice and never leave the device. */
+int sea_wb_denoise_ceps_utterances(const short *const *in, short *const *out_lp, float *const *ceps, int *n_ceps,
+                                   const long *lengths, int n_utt);
 
 /* DoCompCeps(Data, Coef, This): Data[-1] must be valid (host pointers) */
 int sea_compceps_frame(const float *Data, float *Coef14);

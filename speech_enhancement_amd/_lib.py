@@ -68,6 +68,11 @@ PROTOTYPES = {
     "sea_packed_segments": (_i, [_vp, _i, _vp, _vp, _vp, _i]),
     "sea_packed_denoise": (_i, [_vp]),
     "sea_denoise_ceps_utterances": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "sea_wb_denoise_ceps_utterances": (_i, [_vp, _vp, _vp, _vp, _vp, _i]),
+    "sea_compceps_batch_slice": (_i, [_vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sea_cc_slice_state_floats": (_i, []),
+    "sea_wb_compceps_batch_slice": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ll, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "sea_wb_cc_slice_state_floats": (_i, []),
     "sea_compceps_frame": (_i, [_vp, _vp]),
     "sea_resynth64": (_i, [_vp, _l, _vp, _i, _i, _vp]),
     "sea_resynth_utterances": (_i, [_vp, _vp, _vp, _i, _vp, _i]),

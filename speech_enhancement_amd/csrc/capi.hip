@@ -890,6 +890,78 @@ int sea_compceps_batch(const float *d_den_f32, const long long *d_offsets, const
     return 0;
 }
 
+/* The plain CompCeps over one TIME SLICE, both rates: see include/sea_mi355x.h.  Two launches: the tiles of the cepstral frames
+ * that complete in the slice (cc_slice_kernel.hip; none where the slice holds no whole frame), then one wave per utterance that
+ * writes the slice's counts and the state for the next slice.  The second one always runs: sea_compceps_batch's early return
+ * on total_frames <= 0 would leave the counts and the state of a ragged tail's slice unwritten. */
+static int cc_slice_launch(const char *who, bool wb, const float *d_f32, const long long *d_offsets, const long long *d_lengths,
+                           const int *d_first_out, const float *d_hp_rows, const float *d_code_rows, const long long *d_ceps_cum,
+                           long long total_frames, float *d_ceps, int *d_n_ceps, float *d_cc_state, int n_utt, int frame_base,
+                           int resume, void *stream)
+{
+    if (!d_cc_state) return fail("%s: d_cc_state is required", who);
+    if (!d_f32 || !d_first_out) return fail("%s: the float stream and first_out are required", who);
+    if (wb && (!d_hp_rows || !d_code_rows)) return fail("%s: the high-band rows and the code rows are required", who);
+    if (!d_offsets || !d_lengths || !d_ceps_cum || !d_ceps || !d_n_ceps)
+        return fail("%s: offsets, lengths, the prefix sums, ceps and n_ceps are required", who);
+    if (total_frames < 0) return fail("%s: total_frames must not be negative", who);
+    if (frame_base < 0) return fail("%s: frame_base must not be negative", who);
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::CcSliceArgs s = {};
+    s.c.den_f32 = d_f32;
+    s.c.offsets = d_offsets;
+    s.c.lengths = d_lengths;
+    s.c.first_out = d_first_out;
+    s.c.ceps_cum = d_ceps_cum;
+    s.c.ceps = d_ceps;
+    s.c.n_ceps = d_n_ceps;
+    s.c.tables = c->cc;
+    s.c.n_utt = n_utt;
+    s.hp_rows = wb ? d_hp_rows : nullptr;
+    s.code_rows = wb ? d_code_rows : nullptr;
+    s.wb = c->wb;
+    s.state = d_cc_state;
+    s.stride = wb ? sea::kWbCcStateFloats : sea::kCcStateFloats;
+    s.frame_base = frame_base;
+    s.resume = resume != 0;
+    if (total_frames > 0) {
+        const long long nslot = total_frames / 16 + n_utt; /* tile slots of 16 frames, as sea_compceps_batch */
+        const long long grid = nslot < 16384 ? nslot : 16384;
+        if (wb)
+            hipLaunchKernelGGL(sea::compceps_wb_slice_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, s);
+        else
+            hipLaunchKernelGGL(sea::compceps_slice_kernel, dim3((unsigned)grid), dim3(64), 0, (hipStream_t)stream, s);
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(sea::compceps_carry_slice_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, s);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_compceps_batch_slice(const float *d_den_f32, const long long *d_offsets, const long long *d_lengths,
+                             const int *d_first_out, const long long *d_ceps_cum, long long total_frames, float *d_ceps,
+                             int *d_n_ceps, float *d_cc_state, int n_utt, int frame_base, int resume, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    return cc_slice_launch("sea_compceps_batch_slice", false, d_den_f32, d_offsets, d_lengths, d_first_out, nullptr, nullptr,
+                           d_ceps_cum, total_frames, d_ceps, d_n_ceps, d_cc_state, n_utt, frame_base, resume, stream);
+}
+
+int sea_cc_slice_state_floats(void) { return sea::kCcStateFloats; }
+
+int sea_wb_compceps_batch_slice(const float *d_out_f32, const long long *d_offsets, const long long *d_lengths,
+                                const int *d_first_out, const float *d_hp_rows, const float *d_code_rows,
+                                const long long *d_ceps_cum, long long total_frames, float *d_ceps, int *d_n_ceps,
+                                float *d_cc_state, int n_utt, int frame_base, int resume, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    return cc_slice_launch("sea_wb_compceps_batch_slice", true, d_out_f32, d_offsets, d_lengths, d_first_out, d_hp_rows,
+                           d_code_rows, d_ceps_cum, total_frames, d_ceps, d_n_ceps, d_cc_state, n_utt, frame_base, resume, stream);
+}
+
+int sea_wb_cc_slice_state_floats(void) { return sea::kWbCcStateFloats; }
+
 int etsi_denoise(short *p_data, short *p_denoised, long i_frame)
 {
     const short *in[1] = {p_data};

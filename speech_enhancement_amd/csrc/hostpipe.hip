@@ -20,6 +20,10 @@
  * utterance) and SEA_HOST_MODE=chunks: the pieces are chunks of whole utterances, sorted longest first, one launch per chunk
  * on its own part of ONE device buffer.  Results do not depend on either cut.
  *
+ * NoiseSup + the plain CompCeps (sea_denoise_ceps_utterances where the plan cuts the list, sea_wb_denoise_ceps_utterances) and the
+ * feature chains (sea_features_utterances, sea_wb_features_utterances) ride the same slices: per slice the denoiser's slice call
+ * and the cepstrum's or the chain's on the kernel stream, the float stream on the device sized for one slice.
+ *
  * What the entry points share lives once: the cut along the time axis in slice_plan.h (also sea_packed_plan's), the
  * event-driven loop in run_pipeline, the NoiseSup launch over a slice in ns_launch_slice.  An entry point is its set-up and
  * three callables: issue (upload + launch), download, unpack.
@@ -295,7 +299,8 @@ struct PipeWs {
     Grow<float> wb_rows;   /* sea_wb_denoise_utterances: per frame 3 high-band energies, then per frame 9 code values */
     Grow<char> inter;      /* device only: resynth / wideband QMF scratch, allocated as asked for */
     Grow<float> state;     /* device only: the recursion per utterance between two launches of a time-slice pipeline */
-    Grow<float> feat, afe_state;      /* sea_wb_features_utterances, sea_features_utterances: the emitted rows of every slice; device only: the chain's state */
+    Grow<float> feat, afe_state;      /* sea_wb_features_utterances, sea_features_utterances: the emitted rows of every slice; device only: the chain's
+                                       * state (the cepstrum pipelines: sea_compceps_batch_slice's) */
     Grow<unsigned char> flag_rows, fin; /* the same: device only, a slice's speech flags; per slice the utterances that end with it */
     hipStream_t stream[kMaxStreams] = {};
     hipEvent_t ev_meta = nullptr, ev_done[kMaxChunks] = {}, ev_kernel[kMaxChunks] = {}, ev_h2d[kMaxChunks] = {};
@@ -1193,7 +1198,8 @@ int sea_features_utterances(const short *const *in, short *const *out, float *co
 }
 
 /* launches the calling thread's last time-slice pipeline call (sea_denoise_utterances in the time-slice mode,
- * sea_wb_denoise_utterances, sea_wb_features_utterances, sea_features_utterances) was cut into */
+ * sea_wb_denoise_utterances, sea_wb_features_utterances, sea_features_utterances, sea_denoise_ceps_utterances,
+ * sea_wb_denoise_ceps_utterances) was cut into */
 int sea_host_last_slices(void) { return t_last_slices; }
 
 /* ---------------------------------------------------------------------------------------------------- */
@@ -1314,12 +1320,166 @@ int sea_packed_denoise(sea_packed *p)
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
+/* ---------------------------------------------------------------------------------------------------- */
+/* NoiseSup + the plain CompCeps from host buffers as a pipeline over TIME SLICES, both rates: sea_features_utterances' cut,
+ * streams and loop, per slice sea_ns_denoise_batch_slice + sea_compceps_batch_slice (WB: sea_wb_denoise_batch_slice +
+ * sea_wb_compceps_batch_slice) on the kernel stream.  Slice k is a batch of its own on the device (offsets from the slice's
+ * start), so the float stream -- and the wideband mode's QMF scratch, high-band rows and code rows -- live in device buffers of
+ * one slice's size, reused by the next slice and never downloaded.  What travels back is the int16 audio, a slice's block of
+ * cepstral rows (its frames) and the counts.  An utterance's rows of slice k go behind those of its earlier slices: unpack only
+ * notes arrivals and the copy tasks are cut in slice order, as in sea_wb_features_utterances.
+ * one_piece_elsewhere: return -1 before any work where the plan gives one slice (the 8 kHz call keeps its one launch there). */
+} /* extern "C": a template */
+template <bool WB>
+static int denoise_ceps_slices(const char *who, const short *const *in, short *const *out, float *const *ceps, int *n_ceps,
+                               const long *lengths, int n_utt, bool one_piece_elsewhere)
+{
+    DeviceCtx *dc;
+    if (ctx(&dc)) return 1;
+    constexpr long long kIn = WB ? SEA_WB_HOP : SEA_HOP, kOut = SEA_HOP; /* samples per frame up / down */
+    const long long total_fr = slice_total_frames(lengths, n_utt, kIn);
+    PipeWs &w = t_ws;
+    HIP_TRY(w.bind());
+    Pool &pool = Pool::get(w.device);
+    /* "small list -> one slice" is sea_features_utterances' rule, in FRAMES: the frame loop and the tile cost the same at both rates */
+    const bool small = total_fr * SEA_WB_HOP * 2 < (2 << 20) || pool.size() <= 1;
+    SlicePlan p;
+    slice_plan(p, lengths, n_utt, kIn, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    if (one_piece_elsewhere && p.K <= 1) return -1;
+    for (int u = 0; u < n_utt; ++u) n_ceps[u] = 0;
+    t_last_slices = 0;
+    if (total_fr == 0) return 0;
+    if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
+    const int K = t_last_slices = p.K;
+
+    const std::vector<long long> &foff = p.foff;
+    long long max_slice_fr = 0;
+    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
+    /* meta: the slices' offsets | lengths rows, then per slice the prefix sums of the capacities (nact + 1); ints: per slice the
+     * counts, then first_out per utterance; ceps: slice k's block starts at row foff[k] */
+    const size_t n_act = p.mbase[K] / 2;
+    auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] / 2 + (size_t)k; };
+    HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
+    HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
+    HIP_TRY(w.meta.ensure(cum_base(K)));
+    HIP_TRY(w.ints.ensure(n_act + (size_t)n_utt));
+    HIP_TRY(w.ceps.ensure((size_t)total_fr * SEA_CC_NCEP));
+    HIP_TRY(w.f32.ensure_device((size_t)(max_slice_fr * kOut)));
+    HIP_TRY(w.ensure_state((size_t)n_utt * (WB ? sea::kWbSliceStateFloats : sea::kNsPipeStateFloats)));
+    HIP_TRY(w.afe_state.ensure_device((size_t)n_utt * (WB ? sea::kWbCcStateFloats : sea::kCcStateFloats)));
+    if (WB) {
+        HIP_TRY(w.wb_rows.ensure_device(12 * ((size_t)max_slice_fr + 1)));
+        HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
+    }
+    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kIn, false, w.meta.h);
+    for (int k = 0; k < K; ++k) {
+        const int n = p.nact[k];
+        const long long *offs = w.meta.h + p.mbase[k];
+        long long *cc = w.meta.h + cum_base(k);
+        for (int j = 0; j < n; ++j) cc[j] = offs[j] / kIn;
+        cc[n] = foff[k + 1] - foff[k];
+    }
+
+    std::vector<Latch> packed(K);
+    std::vector<long long> pos(n_utt, 0);             /* rows of sorted position j in the slices before next_cut */
+    std::vector<std::vector<long long>> start(K);     /* per slice: where each of its utterances' rows go */
+    std::vector<char> arrived(K, 0);                  /* slice k's rows and counts are on the host */
+    int next_cut = 0;                                 /* the first slice whose copy tasks are not cut yet */
+    Scope scope(&w);
+    short *h_in = w.in.h, *h_out = w.out.h;
+    float *h_ceps = w.ceps.h;
+    const int *h_cnt = w.ints.h;
+    int *d_first = w.ints.d + n_act;
+    float *d_hp = WB ? w.wb_rows.d : nullptr, *d_code = WB ? w.wb_rows.d + 3 * ((size_t)max_slice_fr + 1) : nullptr;
+    const int *ix = p.idx.data();
+    for (int k = 0; k < K; ++k) {
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long b0 = kIn * p.B[k], s0 = kIn * foff[k];
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
+    }
+    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, cum_base(K) * sizeof(long long), hipMemcpyHostToDevice, sUp));
+
+    const int rc = run_pipeline(
+        w, scope, packed, WB ? "wideband cepstrum slice" : "cepstrum slice", true,
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            const int n = p.nact[k];
+            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * f0, h_in + kIn * f0, (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
+            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
+            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
+            const long long *d_rows = w.meta.d + p.mbase[k], *d_cc = w.meta.d + cum_base(k);
+            float *d_blk = w.ceps.d + SEA_CC_NCEP * f0;
+            int *d_cnt = w.ints.d + p.mbase[k] / 2;
+            if (WB) {
+                if (sea_wb_denoise_batch_slice(w.in.d + kIn * f0, w.out.d + kOut * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
+                                               nullptr, d_hp, d_code, (float *)w.inter.d, fr * kIn, w.state.d, n, (int)p.B[k], k > 0,
+                                               sKern))
+                    return 1;
+                if (sea_wb_compceps_batch_slice(w.f32.d, d_rows, d_rows + n, d_first, d_hp, d_code, d_cc, fr, d_blk, d_cnt,
+                                                w.afe_state.d, n, (int)p.B[k], k > 0, sKern))
+                    return 1;
+            } else {
+                if (sea_ns_denoise_batch_slice(w.in.d + kIn * f0, w.out.d + kOut * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
+                                               w.state.d, n, (int)p.B[k], k > 0, sKern))
+                    return 1;
+                if (sea_compceps_batch_slice(w.f32.d, d_rows, d_rows + n, d_first, d_cc, fr, d_blk, d_cnt, w.afe_state.d, n,
+                                             (int)p.B[k], k > 0, sKern))
+                    return 1;
+            }
+            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            return 0;
+        },
+        [&](int k) {
+            const long long f0 = foff[k], fr = foff[k + 1] - f0;
+            if (out)
+                HIP_TRY(hipMemcpyAsync(h_out + kOut * f0, w.out.d + kOut * f0, (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipMemcpyAsync(h_ceps + SEA_CC_NCEP * f0, w.ceps.d + SEA_CC_NCEP * f0, (size_t)fr * SEA_CC_NCEP * sizeof(float),
+                                   hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipMemcpyAsync(w.ints.h + p.mbase[k] / 2, w.ints.d + p.mbase[k] / 2, (size_t)p.nact[k] * sizeof(int),
+                                   hipMemcpyDeviceToHost, sDown));
+            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+            return 0;
+        },
+        [&](int arrived_k) {
+            arrived[arrived_k] = 1;
+            for (; next_cut < K && arrived[next_cut]; ++next_cut) { /* in slice order, whatever order the slices arrive in */
+                const int k = next_cut, n = p.nact[k];
+                const long long *offs = w.meta.h + p.mbase[k], *lens = offs + n;
+                const int *cnt = h_cnt + p.mbase[k] / 2;
+                start[k].resize(n);
+                for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
+                    start[k][j] = pos[j];
+                    pos[j] += cnt[j];
+                }
+                const long long *st = start[k].data();
+                const long long bk = p.B[k], fk = foff[k];
+                run_copies(pool, 0, n, bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
+                    const long long f0 = offs[j] / kIn, nfr = lens[j] / kIn; /* the piece's first frame in the slice, its frames */
+                    const int u = ix[j];
+                    if (out && out[u]) /* whole frames only: the trailing partial frame stays untouched, as with etsi_denoise */
+                        copy_stream(out[u] + kOut * bk, h_out + kOut * (fk + f0), (size_t)(nfr * kOut) * sizeof(short));
+                    if (cnt[j] > 0)
+                        copy_stream(ceps[u] + SEA_CC_NCEP * st[j], h_ceps + SEA_CC_NCEP * (fk + f0),
+                                    (size_t)cnt[j] * SEA_CC_NCEP * sizeof(float));
+                });
+            }
+        });
+    if (rc) return rc;
+    for (int j = 0; j < n_utt; ++j) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
+        n_ceps[ix[j]] = (int)pos[j];
+    return 0;
+}
+extern "C" {
+
 /* NoiseSup + CompCeps from host buffers: the explicit chain SURVEY 8(c) describes for the reference (DoNoiseSup into
  * the denoised-sample shift register, DoCompCeps on its last 201 samples from the third output on,
  * etsi/cpp/ParmInterface.c:275-293).  ceps[u] receives n_ceps[u] rows of 14 floats (c1..c12, c0, logE); its capacity
- * must be max(lengths[u]/80 - 6, 0) rows.  One launch each, no chunking (the feature path of the file driver). */
-int sea_denoise_ceps_utterances(const short *const *in, short *const *out, float *const *ceps, int *n_ceps,
-                                const long *lengths, int n_utt)
+ * must be max(lengths[u]/80 - 6, 0) rows.  One launch each, no chunking: the path of a list the slice plan leaves in one piece
+ * (sea_denoise_ceps_utterances below). */
+static int denoise_ceps_one_launch(const short *const *in, short *const *out, float *const *ceps, int *n_ceps,
+                                   const long *lengths, int n_utt)
 {
     if (n_utt <= 0) return 0;
     DeviceCtx *dc;
@@ -1381,6 +1541,53 @@ int sea_denoise_ceps_utterances(const short *const *in, short *const *out, float
         if (n_ceps[u] > 0) memcpy(ceps[u], w.ceps.h + (size_t)cum[u] * 14, (size_t)n_ceps[u] * 14 * sizeof(float));
     }
     return 0;
+}
+
+/* the lists the slice plan cuts go through the pipeline unless SEA_HOST_CEPS_PIPELINE=0 */
+static bool ceps_pipeline_on()
+{
+    const char *e = getenv("SEA_HOST_CEPS_PIPELINE");
+    return !(e && e[0] == '0');
+}
+
+static int ceps_args_ok(const char *who, const void *in, const void *out, bool out_required, float *const *ceps, const int *n_ceps,
+                        const long *lengths, int n_utt)
+{
+    if (!in || (out_required && !out) || !ceps || !n_ceps || !lengths)
+        return fail(out_required ? "%s: in, out, ceps, n_ceps and lengths are required" : "%s: in, ceps, n_ceps and lengths are required", who);
+    for (int u = 0; u < n_utt; ++u) {
+        if (lengths[u] < 0) return fail("%s: negative length for utterance %d", who, u);
+        if (!ceps[u]) return fail("%s: ceps[%d] is NULL", who, u);
+    }
+    return 0;
+}
+
+/* NoiseSup + CompCeps from host buffers (include/sea_mi355x.h).  A list the slice plan cuts runs the pipeline above; a list in
+ * one piece -- small lists -- keeps the one launch each. */
+int sea_denoise_ceps_utterances(const short *const *in, short *const *out, float *const *ceps, int *n_ceps,
+                                const long *lengths, int n_utt)
+{
+    const char *who = "sea_denoise_ceps_utterances";
+    if (n_utt <= 0) return 0;
+    if (ceps_args_ok(who, in, out, true, ceps, n_ceps, lengths, n_utt)) return 1;
+    if (ceps_pipeline_on()) {
+        const int rc = denoise_ceps_slices<false>(who, in, out, ceps, n_ceps, lengths, n_utt, true);
+        if (rc >= 0) return rc;
+    }
+    t_last_slices = 0;
+    const int rc = denoise_ceps_one_launch(in, out, ceps, n_ceps, lengths, n_utt);
+    if (!rc && slice_total_frames(lengths, n_utt, SEA_HOP) > 0) t_last_slices = 1;
+    return rc;
+}
+
+/* The wideband mode's: one path, the slice kernels', also for a list that is not cut (as sea_wb_features_utterances). */
+int sea_wb_denoise_ceps_utterances(const short *const *in, short *const *out_lp, float *const *ceps, int *n_ceps,
+                                   const long *lengths, int n_utt)
+{
+    const char *who = "sea_wb_denoise_ceps_utterances";
+    if (n_utt <= 0) return 0;
+    if (ceps_args_ok(who, in, out_lp, false, ceps, n_ceps, lengths, n_utt)) return 1;
+    return denoise_ceps_slices<true>(who, in, out_lp, ceps, n_ceps, lengths, n_utt, false);
 }
 
 /* ---------------------------------------------------------------------------------------------------- */

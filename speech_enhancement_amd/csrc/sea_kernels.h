@@ -263,6 +263,35 @@ struct AfeSliceArgs {
 __global__ void afe_ceps_slice_kernel(AfeSliceArgs s); /* WaveProc + CompCeps of the frames completing in the slice */
 __global__ void afe_vad_slice_kernel(AfeSliceArgs s);  /* nulls, PostProc + VAD, flush where final; then the state */
 
+/* The plain CompCeps (no WaveProc) over one TIME SLICE, both rates (cc_slice_kernel.hip; include/sea_mi355x.h,
+ * sea_compceps_batch_slice / sea_wb_compceps_batch_slice).  c.den_f32 / c.offsets / c.lengths (and the rows) describe the slice as
+ * the matching *_denoise_batch_slice call leaves it; c.first_out is absolute; c.ceps_cum / c.ceps / c.n_ceps are the slice's
+ * (capacity per utterance >= the slice's frames).  The frames that complete in a slice are afe_slice_span's.  What one utterance
+ * carries, kCcStateFloats (8 kHz) or kWbCcStateFloats (wideband) floats at state + u * that:
+ *   kCcStF32   240 floats   the last three frames of the float stream, SHIFTED by the slice's frames (kAfStKeep of them; a tile
+ *                           reads at most two frames and one sample before the slice)
+ *   kCcStHp    2 x 3        wideband: the high-band rows of the last two frames ...
+ *   kCcStCode  2 x 9        ... and their code rows
+ * The tile kernels stride over the slice's tiles with many workgroups per utterance and only READ the state;
+ * compceps_carry_slice_kernel, one wave per utterance and the slice's last launch, writes the counts and the state. */
+constexpr int kCcStF32 = 0;
+constexpr int kCcStateFloats = kCcStF32 + kAfStKeep;
+constexpr int kCcStHp = kCcStateFloats;
+constexpr int kCcStCode = kCcStHp + 8;
+constexpr int kWbCcStateFloats = kCcStCode + 24;
+struct CcSliceArgs {
+    CepsArgs c;
+    const float *hp_rows, *code_rows; /* wideband: the slice's rows (WbHbArgs); nullptr at 8 kHz */
+    const sea_wb_tables *wb;
+    float *state;               /* [n_utt][stride] */
+    int stride;                 /* kCcStateFloats or kWbCcStateFloats */
+    int frame_base;
+    int resume;
+};
+__global__ void compceps_slice_kernel(CcSliceArgs s);       /* the 8 kHz tiles of the frames completing in the slice */
+__global__ void compceps_wb_slice_kernel(CcSliceArgs s);    /* the wideband ones */
+__global__ void compceps_carry_slice_kernel(CcSliceArgs s); /* counts, then the state; hp_rows != nullptr: the wideband state */
+
 struct ResynthArgs {
     const int16_t *in;
     int16_t *out;

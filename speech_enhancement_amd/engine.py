@@ -739,6 +739,102 @@ def features_utterances(utterances, want_out=False):
     return dict(feats=[f[:int(k)] for f, k in zip(feats, n_feat)], out=outs, slices=int(lib.sea_host_last_slices()))
 
 
+def cc_slice_state(n_utt, device="cuda"):
+    """The per-utterance state compceps_batch_slice carries from slice to slice, separate from ``ns_slice_state``: float32
+    [n_utt, floats per utterance].  Its contents do not matter before the first slice."""
+    return _torch().zeros((n_utt, int(_lib.load().sea_cc_slice_state_floats())), dtype=_torch().float32, device=device)
+
+
+def wb_cc_slice_state(n_utt, device="cuda"):
+    """The same for wb_compceps_batch_slice, separate from ``wb_slice_state``."""
+    return _torch().zeros((n_utt, int(_lib.load().sea_wb_cc_slice_state_floats())), dtype=_torch().float32, device=device)
+
+
+def _cc_slice(batch, den, cc_state, frame_base, resume, wb):
+    torch = _torch()
+    lib = _lib.load()
+    n = batch.n_utt
+    name = "sea_wb_cc_slice_state_floats" if wb else "sea_cc_slice_state_floats"
+    if cc_state is None or cc_state.dtype != torch.float32 or not cc_state.is_contiguous() \
+            or cc_state.numel() < n * int(getattr(lib, name)()):
+        raise ValueError(f"cc_state must be a contiguous float32 tensor of {name}() floats per utterance")
+    dev = batch.data.device
+    nfr = np.asarray(batch.host_lengths, dtype=np.int64) // (160 if wb else 80)
+    cum = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
+    total = int(cum[-1])
+    ceps = torch.zeros((max(total, 1), 14), dtype=torch.float32, device=dev)
+    n_ceps = torch.zeros(n, dtype=torch.int32, device=dev)
+    d_cum = torch.from_numpy(cum).to(dev)
+    if wb:
+        rc = lib.sea_wb_compceps_batch_slice(_dptr(den["f32"]), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(den["first_out"]),
+                                             _dptr(den["hp_rows"]), _dptr(den["code_rows"]), _dptr(d_cum), total, _dptr(ceps),
+                                             _dptr(n_ceps), _dptr(cc_state), n, int(frame_base), 1 if resume else 0, _stream_ptr())
+        _lib.check(rc, "sea_wb_compceps_batch_slice")
+    else:
+        rc = lib.sea_compceps_batch_slice(_dptr(den["f32"]), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(den["first_out"]),
+                                          _dptr(d_cum), total, _dptr(ceps), _dptr(n_ceps), _dptr(cc_state), n, int(frame_base),
+                                          1 if resume else 0, _stream_ptr())
+        _lib.check(rc, "sea_compceps_batch_slice")
+    torch.cuda.synchronize()
+    host, nc = ceps.cpu().numpy(), n_ceps.cpu().numpy()
+    return dict(ceps=[host[cum[u]:cum[u] + int(nc[u])] for u in range(n)], n_ceps=nc, ceps_dev=ceps, ceps_cum=cum,
+                cc_state=cc_state)
+
+
+def compceps_batch_slice(batch, den, cc_state, frame_base, resume):
+    """The plain CompCeps over one TIME SLICE (sea_compceps_batch_slice): ``batch`` and ``den`` are the slice's batch and the
+    dict ``ns_denoise_batch_slice(.., want_f32=True)`` (or ``want_flags=True``) returned for it, ``cc_state`` a
+    ``cc_slice_state`` tensor with a row per utterance, ``frame_base`` / ``resume`` as there.  Returns a dict for THIS slice:
+    ceps (list of float32 [n_u, 14] host arrays, the cepstral frames that complete in the slice), n_ceps (int32 host array),
+    ceps_dev (the device tensor behind ceps, capacity = the slice's frames per utterance; rows behind the counts are zero),
+    ceps_cum (host prefix sums of the capacities).  Concatenated over the slices of an utterance the rows are bit for bit
+    compceps_batch's."""
+    return _cc_slice(batch, den, cc_state, frame_base, resume, False)
+
+
+def wb_compceps_batch_slice(batch, den, cc_state, frame_base, resume):
+    """The wideband CompCeps over one TIME SLICE (sea_wb_compceps_batch_slice): as ``compceps_batch_slice`` with the dict of
+    ``wb_denoise_batch_slice(.., want_f32=True, want_hb=True)`` (or ``want_flags=True``) and a ``wb_cc_slice_state`` tensor.
+    Concatenated over the slices of an utterance the rows are bit for bit wb_compceps_batch's."""
+    return _cc_slice(batch, den, cc_state, frame_base, resume, True)
+
+
+def _denoise_ceps_utterances(utterances, want_audio, wb):
+    lib = _lib.load()
+    hop = 160 if wb else 80
+    xs = [np.ascontiguousarray(x, dtype=np.int16) for x in utterances]
+    n = len(xs)
+    ceps = [np.zeros((max(x.size // hop - 6, 0) or 1, 14), np.float32) for x in xs]
+    # the 8 kHz call always writes its audio: out has the input's length, the trailing partial frame stays zero
+    outs = [np.zeros(x.size // 160 * 80 if wb else x.size, np.int16) for x in xs] if (want_audio or not wb) else None
+    if n == 0:
+        return dict(ceps=[], n_ceps=np.zeros(0, np.int32), out=[] if want_audio else None, slices=0)
+    ptrs = lambda arrs: (ctypes.c_void_p * n)(*[a.ctypes.data for a in arrs])
+    lens = (ctypes.c_long * n)(*[x.size for x in xs])
+    n_ceps = (ctypes.c_int * n)()
+    name = "sea_wb_denoise_ceps_utterances" if wb else "sea_denoise_ceps_utterances"
+    rc = getattr(lib, name)(ptrs(xs), ptrs(outs) if outs is not None else None, ptrs(ceps), n_ceps, lens, n)
+    _lib.check(rc, name)
+    nc = np.array(list(n_ceps), dtype=np.int32)
+    return dict(ceps=[c[:int(k)] for c, k in zip(ceps, nc)], n_ceps=nc, out=outs if want_audio else None,
+                slices=int(lib.sea_host_last_slices()))
+
+
+def denoise_ceps_utterances(utterances, want_out=True):
+    """A list of 8 kHz int16 utterances in host memory -> denoised audio and the plain cepstra (sea_denoise_ceps_utterances: a
+    list the slice plan cuts runs the host pipeline's time slices, a small one one launch each).  Returns a dict: ceps (list of
+    float32 [n_u, 14] arrays: c1..c12, c0, logE -- compceps_batch's rows, however the list is cut), n_ceps (int32 array), out
+    (list of int16 arrays as etsi_denoise writes them -- the trailing partial frame stays zero -- or None without want_out),
+    slices (launches the list was cut into)."""
+    return _denoise_ceps_utterances(utterances, want_out, False)
+
+
+def wb_denoise_ceps_utterances(utterances, want_lp=False):
+    """The same for 16 kHz utterances through the wideband mode (sea_wb_denoise_ceps_utterances): ceps are wb_compceps_batch's
+    rows, out the int16 low band (80 * (len // 160) samples each) with want_lp, else None."""
+    return _denoise_ceps_utterances(utterances, want_lp, True)
+
+
 def rfft_batch(frames):
     """frames: float32 tensor [n,256] on the GPU -> rfft of every row."""
     torch = _torch()

@@ -9,6 +9,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what wbslices --steps 7  # the wideband mode in time slices and its host pipeline, opt-in
     python tools/bench_extra.py --what wbafeslices --steps 7  # its feature chain in time slices and from host buffers, opt-in
     python tools/bench_extra.py --what afeslices --steps 7  # the 8 kHz feature chain in time slices and from host buffers, opt-in
+    python tools/bench_extra.py --what cepsslices --steps 7  # NoiseSup + the plain CompCeps in time slices and from host buffers, both rates, opt-in
 """
 import argparse
 import json
@@ -789,6 +790,188 @@ def main():
             "kernels": "one launch group: sea::ns_denoise_pipe6_fd_kernel or sea::ns_denoise_pipe_fd_kernel + sea::afe_ceps_kernel + "
                        "sea::afe_vad_kernel; per slice: sea::ns_denoise_pipe_fd_slice_kernel + sea::afe_ceps_slice_kernel + "
                        "sea::afe_vad_slice_kernel"}), flush=True)
+
+    if "cepsslices" in what:
+        # NoiseSup + the plain CompCeps (no WaveProc) cut along the TIME axis, at 8 kHz on the --utts corpus batch (--what afeslices')
+        # and in the wideband mode on the batch of --what wbafeslices.  Side by side in one process, per rate:
+        #   (i)   the one launch group: sea_ns_denoise_batch + sea_compceps_batch (sea_wb_denoise_batch + sea_wb_compceps_batch)
+        #   (ii)  the same batch as 8 slices of equal frame shares, the denoiser's slice call + sea_compceps_batch_slice
+        #         (sea_wb_compceps_batch_slice) per slice, device only (every slice's packed input is resident)
+        #   (iii) the host call from pageable host arrays, wall clock, PCIe inclusive: sea_denoise_ceps_utterances with
+        #         SEA_HOST_CEPS_PIPELINE=0 (one launch each, the code as it was before the pipeline) and as the pipeline,
+        #         ALTERNATING call by call; sea_wb_denoise_ceps_utterances (there is no one-launch host call to set it against)
+        # (i), (ii): device events around every step, one warm-up step of either form discarded, the steps of the forms
+        # ALTERNATING in one loop, median and the sorted list of each.
+        import ctypes
+        lib = sea.load()
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+        steps = max(args.steps, 7)
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        for wide in (False, True):
+            b_all = wb_batch(batch, dev) if wide else batch
+            hop = 160 if wide else 80
+            n = b_all.n_utt
+            lens = np.asarray(b_all.host_lengths)
+            nfr = lens // hop
+            frames = int(nfr.sum())
+            host = b_all.data.cpu().numpy()
+            utts = [host[o:o + l] for o, l in zip(b_all.host_offsets, lens)]
+
+            class Chain:  # everything one launch group over a PackedBatch reads and writes; cap: rows of ceps per utterance
+                def __init__(self, b, cap):
+                    self.b = b
+                    if wide:
+                        half, rows = (b.total // 2 + 7) // 8 * 8, int(lib.sea_wb_rows(b.total))
+                        self.out, self.f32 = z(half, torch.int16), z(half, torch.float32)
+                        self.hpr, self.code = z((rows, 3), torch.float32), z((rows, 9), torch.float32)
+                        self.scratch = z(int(lib.sea_wb_scratch_bytes(b.total, b.n_utt)) // 4 + 4, torch.float32)
+                    else:
+                        self.out, self.f32 = torch.zeros_like(b.data), z(b.data.numel(), torch.float32)
+                    cum = np.concatenate(([0], np.cumsum(cap))).astype(np.int64)
+                    self.tc = int(cum[-1])
+                    self.ceps, self.ncep = z((max(self.tc, 1), 14), torch.float32), z(b.n_utt, torch.int32)
+                    self.cum = torch.from_numpy(cum).to(dev)
+            whole = Chain(b_all, np.maximum(nfr - 6, 0))
+            first = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            onset = torch.zeros(n, dtype=torch.int32, device=dev)
+
+            def one_launch(denoise=True, ceps=True):
+                C, b = whole, b_all
+                if denoise and wide:
+                    rc = lib.sea_wb_denoise_batch(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order), P(first), P(onset),
+                                                  P(C.hpr), P(C.code), P(C.scratch), b.total, n, st)
+                    assert rc == 0, lib.sea_last_error()
+                elif denoise:
+                    rc = lib.sea_ns_denoise_batch(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order), P(first), n, st)
+                    assert rc == 0, lib.sea_last_error()
+                if ceps and wide:
+                    rc = lib.sea_wb_compceps_batch(P(C.f32), P(b.offsets), P(b.lengths), P(first), P(C.hpr), P(C.code), P(C.cum), C.tc,
+                                                   P(C.ceps), P(C.ncep), n, st)
+                    assert rc == 0, lib.sea_last_error()
+                elif ceps:
+                    rc = lib.sea_compceps_batch(P(C.f32), P(b.offsets), P(b.lengths), P(first), P(C.cum), C.tc, P(C.ceps), P(C.ncep), n, st)
+                    assert rc == 0, lib.sea_last_error()
+            idx = np.argsort(-nfr, kind="stable")
+            snfr = nfr[idx]
+            state = z((n, int(lib.sea_wb_slice_state_floats() if wide else lib.sea_ns_slice_state_floats())), torch.float32)
+            ccst = z((n, int(lib.sea_wb_cc_slice_state_floats() if wide else lib.sea_cc_slice_state_floats())), torch.float32)
+            sfirst, sonset = torch.full_like(first, -1), torch.zeros_like(onset)
+            bounds = [0]
+            for k in range(1, 8):  # boundaries with equal shares of the frames, as the host pipeline cuts
+                share = frames * k // 8
+                f = next(f for f in range(bounds[-1] + 1, int(snfr[0]) + 1) if int(np.minimum(snfr, f).sum()) >= share)
+                if f >= snfr[0]:
+                    break
+                bounds.append(f)
+            bounds.append(int(snfr[0]))
+            pieces = []
+            for b0, b1 in zip(bounds[:-1], bounds[1:]):
+                act = [int(u) for u in idx[snfr > b0]]
+                fr = np.array([min(b1, int(nfr[u])) - b0 for u in act], np.int64)
+                pb = sea.PackedBatch.from_arrays([utts[u][hop * b0:hop * min(b1, int(nfr[u]))] for u in act], dev)
+                pieces.append((b0, Chain(pb, fr)))
+
+            def run_slices(denoise=True, ceps=True):
+                for k, (b0, C) in enumerate(pieces):
+                    b = C.b
+                    if denoise and wide:
+                        rc = lib.sea_wb_denoise_batch_slice(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order), P(sfirst),
+                                                            P(sonset), P(C.hpr), P(C.code), P(C.scratch), b.total, P(state), b.n_utt, b0,
+                                                            1 if k else 0, st)
+                        assert rc == 0, lib.sea_last_error()
+                    elif denoise:
+                        rc = lib.sea_ns_denoise_batch_slice(P(b.data), P(C.out), P(C.f32), P(b.offsets), P(b.lengths), P(b.order), P(sfirst),
+                                                            P(state), b.n_utt, b0, 1 if k else 0, st)
+                        assert rc == 0, lib.sea_last_error()
+                    if ceps and wide:
+                        rc = lib.sea_wb_compceps_batch_slice(P(C.f32), P(b.offsets), P(b.lengths), P(sfirst), P(C.hpr), P(C.code), P(C.cum),
+                                                             C.tc, P(C.ceps), P(C.ncep), P(ccst), b.n_utt, b0, 1 if k else 0, st)
+                        assert rc == 0, lib.sea_last_error()
+                    elif ceps:
+                        rc = lib.sea_compceps_batch_slice(P(C.f32), P(b.offsets), P(b.lengths), P(sfirst), P(C.cum), C.tc, P(C.ceps),
+                                                          P(C.ncep), P(ccst), b.n_utt, b0, 1 if k else 0, st)
+                        assert rc == 0, lib.sea_last_error()
+            k8 = f"{len(pieces)} slices"
+            forms = [("one launch group", one_launch), (k8, run_slices),
+                     ("one launch group, denoise alone", lambda: one_launch(ceps=False)),
+                     ("one launch group, compceps alone", lambda: one_launch(denoise=False)),
+                     ("slices, denoise alone", lambda: run_slices(ceps=False)),
+                     ("slices, compceps alone", lambda: run_slices(denoise=False))]
+            for _, fn in forms:
+                fn()
+            torch.cuda.synchronize()
+            ev = {name: [] for name, _ in forms}
+            for _ in range(steps):
+                for name, fn in forms:
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    fn()
+                    b.record()
+                    ev[name].append((a, b))
+            torch.cuda.synchronize()
+            run_slices()  # the whole chain once more after the steps alone, for the comparison of the counts below
+            torch.cuda.synchronize()
+            rows = int(whole.ncep.sum().item())
+            assert sum(int(C.ncep.sum().item()) for _, C in pieces) == rows, "the slices' cepstral frames do not sum to the one launch's"
+            med, srt = {}, {}
+            for name, _ in forms:
+                t = sorted(a.elapsed_time(b) for a, b in ev[name])
+                med[name], srt[name] = t[len(t) // 2], [round(v, 3) for v in t]
+            outs = [np.zeros(int(f) * 80 if wide else int(l), np.int16) for f, l in zip(nfr, lens)]
+            cepss = [np.zeros((max(int(f) - 6, 1), 14), np.float32) for f in nfr]
+            ptr = lambda arrs: (ctypes.c_void_p * n)(*[x.ctypes.data for x in arrs])
+            pin, pout, pceps = ptr(utts), ptr(outs), ptr(cepss)
+            plen = (ctypes.c_long * n)(*[int(l) for l in lens])
+            pnc = (ctypes.c_int * n)()
+            call = lib.sea_wb_denoise_ceps_utterances if wide else lib.sea_denoise_ceps_utterances
+            modes = [("pipeline", None)] if wide else [("one launch each", "0"), ("pipeline", None)]
+            saved = os.environ.pop("SEA_HOST_CEPS_PIPELINE", None)
+            hostt, hostk = {m: [] for m, _ in modes}, {}
+            for rep in range(steps + 1):  # the first call of either mode is the warm-up
+                for m, env in modes:
+                    if env is not None:
+                        os.environ["SEA_HOST_CEPS_PIPELINE"] = env
+                    t0 = time.perf_counter()
+                    rc = call(pin, pout, pceps, pnc, plen, n)
+                    dt = (time.perf_counter() - t0) * 1e3
+                    os.environ.pop("SEA_HOST_CEPS_PIPELINE", None)
+                    assert rc == 0, lib.sea_last_error()
+                    assert sum(pnc) == rows, f"the host call's cepstral frames ({m}) are not the one launch's"
+                    hostk[m] = int(lib.sea_host_last_slices())
+                    if rep:
+                        hostt[m].append(dt)
+            if saved is not None:
+                os.environ["SEA_HOST_CEPS_PIPELINE"] = saved
+            hostres = {m: (sorted(t)[len(t) // 2], [round(v, 3) for v in sorted(t)]) for m, t in hostt.items()}
+            one = med["one launch group"]
+            cfg = {"slices": len(pieces), "one_launch_group_ms": one, "one_launch_group_ms_sorted": srt["one launch group"],
+                   "slices_ms": med[k8], "slices_ms_sorted": srt[k8], "ratio_to_one_launch_group": round(med[k8] / one, 3),
+                   "denoise_alone_ms": {"one_launch_group": med["one launch group, denoise alone"], "slices": med["slices, denoise alone"],
+                                        "one_launch_group_sorted": srt["one launch group, denoise alone"],
+                                        "slices_sorted": srt["slices, denoise alone"]},
+                   "compceps_alone_ms": {"one_launch_group": med["one launch group, compceps alone"], "slices": med["slices, compceps alone"],
+                                         "one_launch_group_sorted": srt["one launch group, compceps alone"],
+                                         "slices_sorted": srt["slices, compceps alone"]},
+                   "host_pipeline_ms": hostres["pipeline"][0], "host_pipeline_ms_sorted": hostres["pipeline"][1],
+                   "host_pipeline_slices": hostk["pipeline"], "host_threads": lib.sea_host_threads()}
+            if not wide:
+                cfg.update({"host_one_launch_each_ms": hostres["one launch each"][0],
+                            "host_one_launch_each_ms_sorted": hostres["one launch each"][1],
+                            "host_one_launch_each_slices": hostk["one launch each"]})
+            cfg["workload"] = (f"{n} utterances at 16 kHz: the {args.utts}-utterance corpus + as many wideband signals of the same lengths"
+                               if wide else f"the {args.utts}-utterance corpus at 8 kHz") + \
+                f", {frames} frames, {rows} cepstral frames; device forms: median of {steps} alternating steps after one warm-up; " \
+                f"host calls: wall clock, median of {steps} alternating calls after one warm-up each"
+            print(json.dumps({
+                "metric": ("ETSI wideband" if wide else "8 kHz") + " NoiseSup + plain CompCeps in time slices: one launch group | slices | "
+                          f"host pipeline (frames of {hop} samples/sec)",
+                "value": frames / (med[k8] / 1e3), "unit": "frames/s", "ms_per_step": med[k8], "config": cfg,
+                "kernels": ("per slice: sea::wb_qmf_slice_kernel + sea::ns_denoise_pipe_wb_slice_kernel + sea::wb_hb_slice_kernel + "
+                            "sea::wb_slice_end_kernel + sea::compceps_wb_slice_kernel + sea::compceps_carry_slice_kernel" if wide else
+                            "per slice: sea::ns_denoise_pipe_slice_kernel or sea::ns_denoise_pipe_big_slice_kernel + "
+                            "sea::compceps_slice_kernel + sea::compceps_carry_slice_kernel")}), flush=True)
+            del whole, pieces
 
     if "rfft" in what:
         n = 1 << 18
