@@ -442,6 +442,48 @@ int sea_irm_target(const short *pure64, const short *noise64, long L, int window
 int sea_irm_target_batch(const short *d_pure64, const short *d_noise64, const long long *d_offsets,
                          const long long *d_lengths, const long long *d_row_offsets, float *d_irm, int window,
                          int n_utt, void *stream);
+/* The training-set builder (enhancement_extract_subband_linux/cpp/main.cpp:91-274; csrc/mix_kernel.hip).
+ * addnoise() (extractwav.cpp:6-35) per utterance, as g++ on x86-64 compiles it: two float sums of x * x over the clean signal
+ * and the noise stretch, every step one correctly rounded float addition IN ORDER (sum = (float)((double)sum + (double)(x * x)));
+ * gain = sqrt ((pure / noise) / snr_lin) in float; scaled[i] = (short)((float)noise[i] * gain), where the conversion is DEFINED
+ * as int32 truncating toward zero with the low 16 bits kept and 0 for a NaN or a product of magnitude >= 2^31; noisy[i] = low 16
+ * bits of clean[i] + scaled[i].  Silent noise gives gain inf, scaled noise 0 and noisy = clean; silent clean gives gain 0.
+ * The reference cannot be compiled (its file includes the absent Wave.h): parity unpinned, semantics pinned to a restatement.
+ * Batch form (device pointers): d_clean / d_offsets / d_lengths a packed batch (offsets multiples of 8); d_noise_src all noise
+ * recordings back to back, utterance u's stretch starting at sample d_noise_start[u] (gathered on the device); d_snr_lin[u] =
+ * (float)pow (10.0, db / 10.0) with db an int; d_noise_scaled / d_noisy laid out like d_clean (the pad samples become 0);
+ * d_sums [n_utt][2] = (pure, noise) and d_gain [n_utt], either may be NULL.  The second launch reads the sums the first wrote:
+ * without d_sums they live in a buffer of the calling host thread that only grows (allocated at the first such call and when a
+ * larger batch comes), so calls WITHOUT d_sums from one thread must not overlap on the device -- keep them on one stream, or
+ * pass d_sums, which also keeps the call free of any allocation.  Host form: one utterance, host pointers, the
+ * outputs optional. */
+int sea_addnoise_batch(const short *d_clean, const long long *d_offsets, const long long *d_lengths, const short *d_noise_src,
+                       const long long *d_noise_start, const float *d_snr_lin, short *d_noise_scaled, short *d_noisy,
+                       float *d_sums, float *d_gain, int n_utt, void *stream);
+int sea_addnoise(const short *clean, const short *noise, long L, int db, short *noise_scaled, short *noisy, float *sums2,
+                 float *gain);
+/* The mix, then sea_subband64_batch of the clean and of the SCALED noise (and of the noisy signal when d_sub_noisy is given),
+ * then sea_irm_target_batch (clean, scaled noise), all on `stream`.  The subband buffers are the caller's, 64x the packed size
+ * each; with d_sums given nothing is allocated inside (without it: the per-thread buffer and its rule above).  Every utterance
+ * needs 320 samples: the lengths are read back first (one stream synchronisation) and a shorter one makes the call return
+ * non-zero before anything is launched. */
+int sea_trainset_batch(const short *d_clean, const long long *d_offsets, const long long *d_lengths, const short *d_noise_src,
+                       const long long *d_noise_start, const float *d_snr_lin, short *d_noise_scaled, short *d_noisy,
+                       float *d_sums, float *d_gain, short *d_sub_clean, short *d_sub_noise, short *d_sub_noisy,
+                       const long long *d_row_offsets, float *d_irm, int window, const int *d_order, int n_utt, void *stream);
+/* The same from host memory: utterance u is mixed with noises[rec[u]][off[u] .. off[u] + lengths[u]) at db[u] dB.  Outputs:
+ * noisy[u] (lengths[u] samples) and irm[u] ([(L-320)/160+1][64]) are required; noise_scaled, sub_clean, sub_noise and
+ * sub_noisy are optional as a whole (NULL) and per utterance, the subband blocks [64][L] as sea_subband64 writes them; the
+ * noisy subbands are computed only when sub_noisy is given.  L < 320, a recording index out of range, off < 0 or
+ * off + L > noise_lengths[rec] return non-zero before the device is touched.  The recordings go up once per call; the list
+ * runs in chunks of whole utterances whose device footprint (per sample 6 B of audio and 128 B per subband set, two
+ * sets or three; 256 B per mask row) stays within 60 % of the free HBM (SEA_TRAINSET_SCRATCH_MB overrides); results do not depend on the cut.
+ * sea_trainset_last_chunks () reports the calling thread's last cut. */
+int sea_trainset_utterances(const short *const *clean, const long *lengths, int n_utt, const short *const *noises,
+                            const long *noise_lengths, int n_noise, const int *rec, const long *off, const int *db, int window,
+                            short *const *noisy, float *const *irm, short *const *noise_scaled, short *const *sub_clean,
+                            short *const *sub_noise, short *const *sub_noisy);
+int sea_trainset_last_chunks(void);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

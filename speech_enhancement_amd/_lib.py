@@ -80,6 +80,11 @@ PROTOTYPES = {
     "sea_subband64_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "sea_irm_target": (_i, [_vp, _vp, _l, _i, _vp]),
     "sea_irm_target_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "sea_addnoise_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sea_addnoise": (_i, [_vp, _vp, _l, _i, _vp, _vp, _vp, _vp]),
+    "sea_trainset_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
+    "sea_trainset_utterances": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sea_trainset_last_chunks": (_i, []),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

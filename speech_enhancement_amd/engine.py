@@ -940,6 +940,131 @@ def irm_target_batch(batch, pure_sub, noise_sub, window=1):
     return MaskBatch(irm, d_offs, offs, rows)
 
 
+# ------------------------------------------------------------------------------------------------
+# the training-set builder (enhancement_extract_subband_linux/cpp/main.cpp:91-274): mix at an SNR, subbands, IRM target
+# ------------------------------------------------------------------------------------------------
+def snr_lin(db):
+    """addnoise's `float dB = pow (10.0, db / 10.0)` with db an int: the C library's double pow, rounded to float."""
+    import math
+    db = np.asarray(db)
+    if not np.issubdtype(db.dtype, np.integer):
+        raise ValueError("addnoise takes whole dB values (the reference's addnoisedB is an int)")
+    return np.array([math.pow(10.0, int(v) / 10.0) for v in db.ravel()], dtype=np.float64).astype(np.float32).reshape(db.shape)
+
+
+def _mix_inputs(batch, noise_src, noise_start, db):
+    torch = _torch()
+    dev = batch.data.device
+    if not (torch.is_tensor(noise_src) and noise_src.dtype == torch.int16 and noise_src.device == dev):
+        noise_src = torch.as_tensor(np.ascontiguousarray(noise_src, dtype=np.int16)).to(dev)
+    noise_src = noise_src.contiguous()
+    start = np.ascontiguousarray(noise_start, dtype=np.int64)
+    db = np.ascontiguousarray(db)
+    if start.shape != (batch.n_utt,) or db.shape != (batch.n_utt,):
+        raise ValueError("one noise start and one dB value per utterance")
+    if np.any(start < 0) or np.any(start + np.asarray(batch.host_lengths) > int(noise_src.numel())):
+        raise ValueError("a noise stretch does not lie inside noise_src")
+    return noise_src, torch.from_numpy(start).to(dev), torch.from_numpy(snr_lin(db)).to(dev)
+
+
+def addnoise_batch(batch, noise_src, noise_start, db):
+    """addnoise() (enhancement_extract_subband_linux/cpp/extractwav.cpp:6-35) for every utterance of the batch: utterance u
+    is mixed with noise_src[noise_start[u] : noise_start[u] + L_u] (an int16 tensor or array holding all noise recordings back
+    to back) scaled to db[u] dB (ints).  Returns a dict: noise_scaled and noisy (int16 tensors laid out like batch.data),
+    sums (float32 [n, 2]: the in-order float sums of squares of clean and noise) and gain (float32 [n]).  Asynchronous on the
+    current stream."""
+    torch = _torch()
+    lib = _lib.load()
+    noise_src, d_start, d_snr = _mix_inputs(batch, noise_src, noise_start, db)
+    dev = batch.data.device
+    scaled, noisy = torch.zeros_like(batch.data), torch.zeros_like(batch.data)
+    sums = torch.zeros((batch.n_utt, 2), dtype=torch.float32, device=dev)
+    gain = torch.zeros(batch.n_utt, dtype=torch.float32, device=dev)
+    _lib.check(lib.sea_addnoise_batch(_dptr(batch.data), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(noise_src),
+                                      _dptr(d_start), _dptr(d_snr), _dptr(scaled), _dptr(noisy), _dptr(sums), _dptr(gain),
+                                      batch.n_utt, _stream_ptr()), "sea_addnoise_batch")
+    return dict(noise_scaled=scaled, noisy=noisy, sums=sums, gain=gain)
+
+
+def addnoise(clean, noise, db):
+    """addnoise() on host arrays, one utterance (sea_addnoise): returns (noise_scaled, noisy, sums float32[2], gain)."""
+    lib = _lib.load()
+    clean = np.ascontiguousarray(clean, dtype=np.int16)
+    noise = np.ascontiguousarray(noise, dtype=np.int16)
+    if clean.shape != noise.shape or clean.ndim != 1:
+        raise ValueError("addnoise needs a clean signal and a noise stretch of the same length")
+    scaled, noisy = np.zeros_like(clean), np.zeros_like(clean)
+    sums, gain = np.zeros(2, np.float32), np.zeros(1, np.float32)
+    _lib.check(lib.sea_addnoise(_np_ptr(clean), _np_ptr(noise), clean.size, int(db), _np_ptr(scaled), _np_ptr(noisy),
+                                _np_ptr(sums), _np_ptr(gain)), "sea_addnoise")
+    return scaled, noisy, sums, gain[0]
+
+
+def trainset_batch(batch, noise_src, noise_start, db, window=1, noisy_subband=False, use_order=True):
+    """The training-set pipeline on the current stream (sea_trainset_batch): addnoise_batch, subband_batch of the clean and of
+    the SCALED noise (and of the noisy signal with noisy_subband), irm_target_batch (clean, scaled noise).  Returns
+    addnoise_batch's dict plus sub_clean, sub_noise, sub_noisy (int16 tensors as subband_batch returns them; sub_noisy None
+    without noisy_subband) and irm (a MaskBatch)."""
+    torch = _torch()
+    lib = _lib.load()
+    if np.any(np.asarray(batch.host_lengths) < 320):
+        raise ValueError("trainset needs utterances of at least one 320-sample frame")
+    noise_src, d_start, d_snr = _mix_inputs(batch, noise_src, noise_start, db)
+    dev = batch.data.device
+    scaled, noisy = torch.zeros_like(batch.data), torch.zeros_like(batch.data)
+    sums = torch.zeros((batch.n_utt, 2), dtype=torch.float32, device=dev)
+    gain = torch.zeros(batch.n_utt, dtype=torch.float32, device=dev)
+    subs = [torch.zeros(batch.total * 64, dtype=torch.int16, device=dev) for _ in range(3 if noisy_subband else 2)]
+    rows = (np.asarray(batch.host_lengths) - 320) // 160 + 1
+    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    irm = torch.zeros((int(rows.sum()), 64), dtype=torch.float32, device=dev)
+    d_offs = torch.from_numpy(offs).to(dev)
+    _lib.check(lib.sea_trainset_batch(_dptr(batch.data), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(noise_src),
+                                      _dptr(d_start), _dptr(d_snr), _dptr(scaled), _dptr(noisy), _dptr(sums), _dptr(gain),
+                                      _dptr(subs[0]), _dptr(subs[1]), _dptr(subs[2]) if noisy_subband else None, _dptr(d_offs),
+                                      _dptr(irm), int(window), _dptr(batch.order) if use_order else None, batch.n_utt,
+                                      _stream_ptr()), "sea_trainset_batch")
+    return dict(noise_scaled=scaled, noisy=noisy, sums=sums, gain=gain, sub_clean=subs[0], sub_noise=subs[1],
+                sub_noisy=subs[2] if noisy_subband else None, irm=MaskBatch(irm, d_offs, offs, rows))
+
+
+def make_trainset(clean_list, noises, rec, off, db, window=1, want_noise_scaled=False, want_subbands=False,
+                  noisy_subband=False):
+    """The reference's training-set loop from host memory (sea_trainset_utterances): clean_list[u] is mixed with
+    noises[rec[u]][off[u] : off[u] + L_u] at db[u] dB; the list runs in chunks that fit the free HBM.  Returns a dict: noisy
+    (list of int16 arrays), irm (list of float32 [(L-320)//160+1, 64]), noise_scaled (list or None), sub_clean / sub_noise
+    (lists of int16 [64, L] or None), sub_noisy (the same, only with noisy_subband), chunks (how many the list was cut into)."""
+    lib = _lib.load()
+    xs = [np.ascontiguousarray(x, dtype=np.int16) for x in clean_list]
+    ns = [np.ascontiguousarray(x, dtype=np.int16) for x in noises]
+    n, m = len(xs), len(ns)
+    rec = np.ascontiguousarray(rec, dtype=np.int32)
+    db = np.ascontiguousarray(db)
+    if not np.issubdtype(db.dtype, np.integer):
+        raise ValueError("addnoise takes whole dB values")
+    db = db.astype(np.int32)
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    if not (rec.shape == db.shape == off.shape == (n,)):
+        raise ValueError("one recording index, offset and dB value per utterance")
+    noisy = [np.zeros(x.size, np.int16) for x in xs]
+    irm = [np.zeros((max((x.size - 320) // 160 + 1, 1), 64), np.float32) for x in xs]
+    scaled = [np.zeros(x.size, np.int16) for x in xs] if want_noise_scaled else None
+    blocks = lambda: [np.zeros((64, x.size), np.int16) for x in xs]
+    sub_c, sub_n = (blocks(), blocks()) if want_subbands else (None, None)
+    sub_y = blocks() if noisy_subband else None
+    if n == 0:
+        return dict(noisy=[], irm=[], noise_scaled=scaled, sub_clean=sub_c, sub_noise=sub_n, sub_noisy=sub_y, chunks=0)
+    ptrs = lambda arrs: (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs]) if arrs is not None else None
+    lens = (ctypes.c_long * n)(*[x.size for x in xs])
+    nlens = (ctypes.c_long * max(m, 1))(*[x.size for x in ns])
+    offs = (ctypes.c_long * n)(*[int(v) for v in off])
+    rc = lib.sea_trainset_utterances(ptrs(xs), lens, n, ptrs(ns), nlens, m, _np_ptr(rec), offs, _np_ptr(db), int(window),
+                                     ptrs(noisy), ptrs(irm), ptrs(scaled), ptrs(sub_c), ptrs(sub_n), ptrs(sub_y))
+    _lib.check(rc, "sea_trainset_utterances")
+    return dict(noisy=noisy, irm=irm, noise_scaled=scaled, sub_clean=sub_c, sub_noise=sub_n, sub_noisy=sub_y,
+                chunks=int(lib.sea_trainset_last_chunks()))
+
+
 def ns16k_streams_push(frames, state=None, reset=None):
     """The 16 k-native NoiseSup variant behind the reference's batch plug-in symbols (aurora_etsi/NoiseSup.cpp:1140-1407;
     SURVEY 8(f) #4): frames float32 [B, nframes, 160] on the GPU, func_Wiener's frame gate applied inside.  Returns

@@ -386,3 +386,125 @@ void sea_queue_destroy(sea_queue *q)
     pthread_cond_destroy(&q->can_put);
     pthread_cond_destroy(&q->can_get);
 }
+
+/* ---- the training-set tool: cfg of Read_CFG (enhancement_extract_subband_linux/cpp/main.cpp:280-397), the plan ---- */
+int sea_read_extract_cfg(const char *path, sea_extract_cfg *c)
+{
+    FILE *fp = fopen(path, "r");
+    int bad = 0, k;
+    memset(c, 0, sizeof *c);
+    if (!fp) {
+        printf("Open %s file error!\n", path);
+        return 1;
+    }
+    bad |= cfg_line(fp, c->func, NULL);
+    bad |= cfg_line(fp, c->purewavDictionary, NULL);
+    bad |= cfg_line(fp, c->purewavlist, NULL);
+    for (k = 0; k < 4; k++) bad |= cfg_line(fp, c->noisepath[k], NULL);
+    bad |= cfg_line(fp, NULL, &c->addnoisedB);
+    bad |= cfg_line(fp, c->outputDictionary, NULL);
+    bad |= cfg_line(fp, c->save_noisy_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_pure_wav_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_noise_wav_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_wav_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_IBM_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_IRM_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_single_IRM_dir, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_MFCC, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_ACF, NULL);
+    bad |= cfg_line(fp, c->save_subband_noisy_Wiener, NULL);
+    bad |= cfg_line(fp, c->Log, NULL);
+    fclose(fp);
+    return bad;
+}
+
+void sea_plan_draw(const long *noise_len4, long clean_len, sea_plan *p)
+{
+    static const int db_of_case[8] = {0, -5, 0, -5, -5, 0, -5, 0};
+    float first = rand() % 20 / 20.0, second = rand() % 20 / 20.0;
+    int which = (int)(first * 8);
+    p->rec = which / 2;
+    p->db = db_of_case[which];
+    p->off = (int)(second * (noise_len4[p->rec] - clean_len));
+}
+
+int sea_plan_check(const sea_plan *p, const long *noise_len, int n_noise, long clean_len)
+{
+    if (clean_len < 320) return 1;
+    if (p->rec < 0 || p->rec >= n_noise) return 2;
+    if (p->off < 0 || p->off > noise_len[p->rec] - clean_len) return 3;
+    return 0;
+}
+
+int sea_plan_write(FILE *fp, const char *id, const sea_plan *p)
+{
+    if (!fp) return 1;
+    fprintf(fp, "%s %d %ld %d\n", id, p->rec, p->off, p->db);
+    return ferror(fp) ? 1 : 0;
+}
+
+typedef struct {
+    char *id;
+    long line;
+    sea_plan plan;
+} plan_row;
+struct sea_plan_table {
+    plan_row *row;
+    long n;
+};
+
+static int plan_row_cmp(const void *a, const void *b)
+{
+    const plan_row *x = (const plan_row *)a, *y = (const plan_row *)b;
+    int c = strcmp(x->id, y->id);
+    return c ? c : (x->line > y->line) - (x->line < y->line);
+}
+
+sea_plan_table *sea_plan_load(const char *path)
+{
+    FILE *fp = fopen(path, "r");
+    char line[2 * SEA_FILE_LEN], name[SEA_FILE_LEN], rest[8];
+    long cap = 0, ln = 0;
+    sea_plan_table *t;
+    if (!fp) return NULL;
+    t = (sea_plan_table *)calloc(1, sizeof *t);
+    while (t && fgets(line, sizeof line, fp)) {
+        sea_plan q;
+        ln++;
+        if (sscanf(line, "%1023s %d %ld %d %7s", name, &q.rec, &q.off, &q.db, rest) != 4) continue;
+        if (t->n == cap) {
+            plan_row *grown = (plan_row *)realloc(t->row, (size_t)(cap = cap ? 2 * cap : 256) * sizeof *grown);
+            if (!grown) break;
+            t->row = grown;
+        }
+        t->row[t->n].id = strdup(name);
+        t->row[t->n].line = ln;
+        t->row[t->n].plan = q;
+        t->n++;
+    }
+    fclose(fp);
+    if (t) qsort(t->row, (size_t)t->n, sizeof *t->row, plan_row_cmp);
+    return t;
+}
+
+int sea_plan_find(const sea_plan_table *t, const char *id, sea_plan *p)
+{
+    long lo = 0, hi = t ? t->n : 0; /* first row whose id is greater than `id`; the one before it is the id's last line */
+    while (lo < hi) {
+        long mid = lo + (hi - lo) / 2;
+        if (strcmp(t->row[mid].id, id) <= 0) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0 || strcmp(t->row[lo - 1].id, id)) return 1;
+    *p = t->row[lo - 1].plan;
+    return 0;
+}
+
+void sea_plan_free(sea_plan_table *t)
+{
+    long k;
+    if (!t) return;
+    for (k = 0; k < t->n; k++) free(t->row[k].id);
+    free(t->row);
+    free(t);
+}

@@ -53,6 +53,52 @@ int sea_mask_text_write(FILE *fp, const char *id, const float *mask64, long rows
 long sea_mask_text_read(FILE *fp, char *id_out /* SEA_FILE_LEN, may be NULL */, float *mask64, long max_rows);
 
 
+/* ---- the training-set tool (enhancement_extract_subband_linux/cpp/main.cpp) ----------------------------------------
+ * Its cfg: 20 positional "key value" lines in Read_CFG's order (main.cpp:280-397). */
+typedef struct {
+    char func[SEA_FILE_LEN];
+    char purewavDictionary[SEA_FILE_LEN];
+    char purewavlist[SEA_FILE_LEN];
+    char noisepath[4][SEA_FILE_LEN];
+    int addnoisedB;
+    char outputDictionary[SEA_FILE_LEN];
+    char save_noisy_dir[SEA_FILE_LEN];
+    char save_subband_pure_wav_dir[SEA_FILE_LEN];
+    char save_subband_noise_wav_dir[SEA_FILE_LEN];
+    char save_subband_noisy_wav_dir[SEA_FILE_LEN];
+    char save_subband_noisy_IBM_dir[SEA_FILE_LEN];
+    char save_subband_noisy_IRM_dir[SEA_FILE_LEN];
+    char save_subband_noisy_single_IRM_dir[SEA_FILE_LEN];
+    char save_subband_noisy_MFCC[SEA_FILE_LEN];
+    char save_subband_noisy_ACF[SEA_FILE_LEN];
+    char save_subband_noisy_Wiener[SEA_FILE_LEN];
+    char Log[SEA_FILE_LEN];
+} sea_extract_cfg;
+int sea_read_extract_cfg(const char *path, sea_extract_cfg *cfg);
+
+/* The plan of one utterance: which noise recording (0..3), the offset of its stretch in it, the dB value. */
+typedef struct {
+    int rec;
+    long off;
+    int db;
+} sea_plan;
+/* The reference's draw (main.cpp:105-122) from the C library's rand (): two draws of `rand () % 20 / 20.0` held in a float;
+ * the first picks case (int)(key * 8) -- recording case / 2, dB from the table 0, -5, 0, -5, -5, 0, -5, 0 --, the second
+ * the offset (int)(key * (noise_len - clean_len)) with the product in float.  Seed with srand () first.  noise_len4 are the
+ * lengths of the four recordings. */
+void sea_plan_draw(const long *noise_len4, long clean_len, sea_plan *p);
+/* 0 if the plan can run, else 1 (the utterance has fewer than 320 samples), 2 (recording index out of range) or 3 (the stretch
+ * does not lie inside the recording: the reference reads out of bounds there) */
+int sea_plan_check(const sea_plan *p, const long *noise_len, int n_noise, long clean_len);
+/* One line "<id> <rec> <off> <db>\n", the format of a plan file and of the plan lines of the Log.  sea_plan_load reads a file
+ * ONCE into a table (lines of another shape -- the Log's other entries -- are passed over; NULL when it cannot be opened);
+ * sea_plan_find returns 0 and the LAST such line of `id` (a Log is appended to), or 1 when there is none: a binary search. */
+int sea_plan_write(FILE *fp, const char *id, const sea_plan *p);
+typedef struct sea_plan_table sea_plan_table;
+sea_plan_table *sea_plan_load(const char *path);
+int sea_plan_find(const sea_plan_table *t, const char *id, sea_plan *p);
+void sea_plan_free(sea_plan_table *t);
+
 /* ---- the drivers' pipeline: reader thread(s) -> device thread(s) -> writer thread(s) ------------------------------
  * A chunk of the utterance list travels through two bounded queues, so that chunk k+1's WAVs are read and chunk
  * k-1's written while chunk k is on a GPU (the reference reads, processes and writes one file at a time,

@@ -10,6 +10,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what wbafeslices --steps 7  # its feature chain in time slices and from host buffers, opt-in
     python tools/bench_extra.py --what afeslices --steps 7  # the 8 kHz feature chain in time slices and from host buffers, opt-in
     python tools/bench_extra.py --what cepsslices --steps 7  # NoiseSup + the plain CompCeps in time slices and from host buffers, both rates, opt-in
+    python tools/bench_extra.py --what trainset --steps 7  # the training-set builder: mix, subbands, IRM, pipeline and host entry point, opt-in
 """
 import argparse
 import json
@@ -972,6 +973,91 @@ def main():
                             "per slice: sea::ns_denoise_pipe_slice_kernel or sea::ns_denoise_pipe_big_slice_kernel + "
                             "sea::compceps_slice_kernel + sea::compceps_carry_slice_kernel")}), flush=True)
             del whole, pieces
+
+    if "trainset" in what:
+        # The training-set builder on the --utts corpus, noise stretches from four synthetic recordings, side by side in one
+        # process (median of --steps alternating steps after one warm-up, device events): (a) the mix alone, (b) subband_batch x2
+        # + irm_target_batch as three calls -- taken twice per round, b and b_again, whose difference is the run-to-run spread --,
+        # (c) sea_trainset_batch without and with the noisy subbands, (d) make_trainset from host buffers (wall clock, PCIe
+        # inclusive, noisy + IRM only).  The yardstick for (c) is (a) + (b).
+        import ctypes
+        from speech_enhancement_amd import _lib
+        lib = sea.load()
+        n = batch.n_utt
+        lens = np.asarray(batch.host_lengths)
+        recs = [(corpus.synth_utterance(900 + k, 16000 * 8).astype(np.int32) // 3).astype(np.int16) for k in range(4)]
+        rec = (np.arange(n) % 4).astype(np.int32)
+        off = ((np.arange(n) * 7919) % (16000 * 8 - lens + 1)).astype(np.int64)
+        db = np.where(np.arange(n) % 2 == 0, 0, -5).astype(np.int32)
+        base = np.arange(4, dtype=np.int64) * (16000 * 8)
+        src = torch.from_numpy(np.concatenate(recs)).to(dev)
+        d_start = torch.from_numpy(base[rec] + off).to(dev)
+        d_snr = torch.from_numpy(sea.snr_lin(db)).to(dev)
+        scaled, noisy = torch.zeros_like(batch.data), torch.zeros_like(batch.data)
+        sums = torch.zeros((n, 2), dtype=torch.float32, device=dev)
+        gain = torch.zeros(n, dtype=torch.float32, device=dev)
+        subs = [torch.zeros(batch.total * 64, dtype=torch.int16, device=dev) for _ in range(3)]
+        rows = (lens - 320) // 160 + 1
+        d_rows = torch.from_numpy(np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)).to(dev)
+        irm = torch.zeros((int(rows.sum()), 64), dtype=torch.float32, device=dev)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        sp = lambda: ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        nb = sea.PackedBatch(scaled, batch.offsets, batch.lengths, batch.order, batch.host_offsets, batch.host_lengths)
+
+        def mix():
+            _lib.check(lib.sea_addnoise_batch(p(batch.data), p(batch.offsets), p(batch.lengths), p(src), p(d_start), p(d_snr),
+                                              p(scaled), p(noisy), p(sums), p(gain), n, sp()), "sea_addnoise_batch")
+
+        def parts():
+            sea.subband_batch(batch, out=subs[0])
+            sea.subband_batch(nb, out=subs[1])
+            _lib.check(lib.sea_irm_target_batch(p(subs[0]), p(subs[1]), p(batch.offsets), p(batch.lengths), p(d_rows), p(irm), 1,
+                                                n, sp()), "sea_irm_target_batch")
+
+        def pipeline(with_noisy):
+            _lib.check(lib.sea_trainset_batch(p(batch.data), p(batch.offsets), p(batch.lengths), p(src), p(d_start), p(d_snr),
+                                              p(scaled), p(noisy), p(sums), p(gain), p(subs[0]), p(subs[1]),
+                                              p(subs[2]) if with_noisy else None, p(d_rows), p(irm), 1, p(batch.order), n, sp()),
+                       "sea_trainset_batch")
+        forms = {"a_mix": mix, "b_parts": parts, "b_parts_again": parts, "c_pipeline": lambda: pipeline(False),
+                 "c_pipeline_noisy_subbands": lambda: pipeline(True)}
+        for fn in forms.values():
+            fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in forms}
+        for _ in range(args.steps):
+            for k, fn in forms.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                torch.cuda.synchronize()
+                times[k].append(a.elapsed_time(b))
+        med = {k: sorted(v)[len(v) // 2] for k, v in times.items()}
+        host = batch.data.cpu().numpy()
+        clean = [host[o:o + l] for o, l in zip(batch.host_offsets, lens)]
+        del subs, irm, scaled, noisy
+        torch.cuda.empty_cache()
+        sea.make_trainset(clean, recs, rec, off, db)
+        hs = []
+        for _ in range(args.steps):
+            t0 = time.perf_counter()
+            r = sea.make_trainset(clean, recs, rec, off, db)
+            hs.append((time.perf_counter() - t0) * 1e3)
+        samples = int(lens.sum())
+        print(json.dumps({
+            "metric": "training-set builder: mix | subband x2 + IRM as separate calls | sea_trainset_batch | make_trainset from host "
+                      "buffers (samples/sec of the pipeline without the noisy subbands)",
+            "value": samples / (med["c_pipeline"] / 1e3), "unit": "samples/s", "ms_per_step": med["c_pipeline"],
+            "config": {"workload": f"the {args.utts}-utterance corpus, {samples} samples, stretches of four 8-s synthetic noise "
+                                   f"recordings at 0 / -5 dB; device forms: device events, median of {args.steps} alternating steps "
+                                   "after one warm-up; host call: wall clock, noisy + IRM returned",
+                       "median_ms": med, "sorted_ms": {k: sorted(v) for k, v in times.items()},
+                       "a_plus_b_ms": med["a_mix"] + med["b_parts"], "spread_b_ms": abs(med["b_parts"] - med["b_parts_again"]),
+                       "mix_share_of_pipeline": med["a_mix"] / med["c_pipeline"],
+                       "host_make_trainset_ms": sorted(hs)[len(hs) // 2], "host_make_trainset_ms_sorted": sorted(hs),
+                       "host_chunks": r["chunks"]},
+            "kernels": "mix_sums_kernel + mix_scale_kernel + sea::subband_kernel x2 (x3) + sea::irm_target_kernel"}), flush=True)
 
     if "rfft" in what:
         n = 1 << 18
