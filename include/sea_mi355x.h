@@ -484,6 +484,38 @@ int sea_trainset_utterances(const short *const *clean, const long *lengths, int 
                             short *const *noisy, float *const *irm, short *const *noise_scaled, short *const *sub_clean,
                             short *const *sub_noise, short *const *sub_noisy);
 int sea_trainset_last_chunks(void);
+/* The front half of the Hu-Wang mask estimator createIBM() (function/20141106_speech_enhancement/aurora_etsi_test/
+ * HuWang.cpp:41-76) on its 25-channel 8 kHz gammatone bank: AudiPeriph (gammatone + Meddis hair cell, hOut in float), lowPass
+ * (hEv), computeACF, crossCorr, globalPitch, timeCrn (corrHc) and the initial labelling of Grp (csrc/hw25_kernel.hip,
+ * DESIGN.md section 5.11).  Parity: bit for bit against the reference's own functions compiled on a CPU
+ * (tests/golden/hw25_golden.npz).  The back half (initGroup, pitchDtm, computeAM, finalSeg) is not built; it consumes exactly
+ * these arrays.
+ * Samples are floats on the int16 scale, as createIBM takes them.  Batch forms (device pointers): d_in_f32 holds the packed
+ * batch, utterance u at d_offsets[u] (multiples of 8; the stretch up to the next multiple of 8 past its length must be
+ * readable); d_hout / d_hev hold 25x the packed size, utterance u's [25][pitch] block at d_offsets[u] * 25, pitch =
+ * lengths[u] rounded up to 8 (the padding is not written).  Utterance u has sea_hw25_frames (lengths[u]) = lengths[u] / 80
+ * rows starting at d_row_offsets[u]: d_cross_hc / d_cross_ev / d_pratio / d_mark [rows][25] floats (mark is 0 or 1),
+ * d_pitch [rows] ints (16..100), d_acf_hc / d_acf_ev [rows][25][101] floats -- large (2 x 10100 B per row), so optional:
+ * a null pointer is not written.  d_order (launch order, optional) as elsewhere.  sea_hw25_scratch_bytes is what d_scratch
+ * must hold; the present form keeps a frame's ACFs in LDS and needs none (0 bytes, d_scratch may be null).
+ * sea_hw25_frontend_batch is the two batch calls as one launch group on `stream`.  sea_hw25_frontend: one utterance from
+ * host memory; hout / hev [25][L], the frame outputs as above with rows = L / 80; every output pointer may be null. */
+int sea_hw25_tables_host(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
+                         float *lp91, float *hair10 /* ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0 */);
+long long sea_hw25_frames(long long length);
+long long sea_hw25_scratch_bytes(long long total_padded_samples, int n_utt);
+int sea_hw25_periphery_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
+                             const long long *d_lengths, const int *d_order, int n_utt, void *stream);
+int sea_hw25_correlogram_batch(const float *d_hout, const float *d_hev, const long long *d_offsets, const long long *d_lengths,
+                               const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev, float *d_cross_hc,
+                               float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
+                               const int *d_order, int n_utt, void *stream);
+int sea_hw25_frontend_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
+                            const long long *d_lengths, const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev,
+                            float *d_cross_hc, float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
+                            const int *d_order, int n_utt, void *stream);
+int sea_hw25_frontend(const float *in, long L, float *hout, float *hev, float *acf_hc, float *acf_ev, float *cross_hc,
+                      float *cross_ev, int *pitch, float *pratio, float *mark);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

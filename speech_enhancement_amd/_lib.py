@@ -85,6 +85,13 @@ PROTOTYPES = {
     "sea_trainset_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "sea_trainset_utterances": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sea_trainset_last_chunks": (_i, []),
+    "sea_hw25_tables_host": (_i, [_vp] * 9),
+    "sea_hw25_frames": (_ll, [_ll]),
+    "sea_hw25_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw25_periphery_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sea_hw25_correlogram_batch": (_i, [_vp] * 14 + [_i, _vp]),
+    "sea_hw25_frontend_batch": (_i, [_vp] * 15 + [_i, _vp]),
+    "sea_hw25_frontend": (_i, [_vp, _l] + [_vp] * 9),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -41,6 +41,7 @@ sea_cc_tables g_cc_host;
 sea_gt_tables g_gt_host;
 sea_ns16k_tables g_ns16_host;
 sea_wb_tables g_wb_host;
+sea_hw25_tables g_hw25_host;
 bool g_host_ready = false;
 
 void host_tables()
@@ -51,6 +52,7 @@ void host_tables()
     sea_build_gt_tables(&g_gt_host);
     sea_build_ns16k_tables(&g_ns16_host);
     sea_build_wb_tables(&g_wb_host);
+    sea_build_hw25_tables(&g_hw25_host);
     g_host_ready = true;
 }
 } // namespace
@@ -74,11 +76,13 @@ int ctx(DeviceCtx **out)
         HIP_TRY(hipMalloc(&c.gt, sizeof(sea_gt_tables)));
         HIP_TRY(hipMalloc(&c.ns16, sizeof(sea_ns16k_tables)));
         HIP_TRY(hipMalloc(&c.wb, sizeof(sea_wb_tables)));
+        HIP_TRY(hipMalloc(&c.hw25, sizeof(sea_hw25_tables)));
         HIP_TRY(hipMemcpy(c.ns, &g_ns_host, sizeof g_ns_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.cc, &g_cc_host, sizeof g_cc_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.gt, &g_gt_host, sizeof g_gt_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.ns16, &g_ns16_host, sizeof g_ns16_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.wb, &g_wb_host, sizeof g_wb_host, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.hw25, &g_hw25_host, sizeof g_hw25_host, hipMemcpyHostToDevice));
         c.ready = true;
     }
     *out = &c;
@@ -1204,6 +1208,140 @@ int sea_irm_target(const short *pure64, const short *noise64, long L, int window
     if (sea_irm_target_batch(dp.p, dn.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dirm.p, window, 1, nullptr)) return 1;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(irm, dirm.p, (size_t)F * 64 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+/* ---- the Hu-Wang estimator's front half on the 25-channel 8 kHz bank (hw25_kernel.hip) ------------------------------ */
+int sea_hw25_tables_host(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
+                         float *lp91, float *hair10)
+{
+    sea_hw25_plain_tables(cf25, bw25, midEar25, gain25, f1_25, f2_25, winsize25, lp91, hair10);
+    return 0;
+}
+
+long long sea_hw25_frames(long long length) { return length > 0 ? length / SEA_HW25_HOP : 0; }
+
+/* the correlogram keeps a frame's ACFs in LDS: this form needs no scratch */
+long long sea_hw25_scratch_bytes(long long total_padded_samples, int n_utt)
+{
+    (void)total_padded_samples;
+    (void)n_utt;
+    return 0;
+}
+
+static int hw25_args(sea::Hw25Args &a, int n_utt)
+{
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    a = sea::Hw25Args{};
+    a.tables = c->hw25;
+    a.n_utt = n_utt;
+    return 0;
+}
+
+int sea_hw25_periphery_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
+                             const long long *d_lengths, const int *d_order, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_in_f32 || !d_hout || !d_hev || !d_offsets || !d_lengths) return fail("hw25_periphery: null pointer");
+    sea::Hw25Args a;
+    if (hw25_args(a, n_utt)) return 1;
+    a.in = d_in_f32;
+    a.hout = d_hout;
+    a.hev = d_hev;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.order = d_order;
+    hipLaunchKernelGGL(sea::hw25_periphery_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sea::hw25_lowpass_kernel, dim3(n_utt, SEA_HW25_NCHAN), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_hw25_correlogram_batch(const float *d_hout, const float *d_hev, const long long *d_offsets, const long long *d_lengths,
+                               const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev, float *d_cross_hc,
+                               float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
+                               const int *d_order, int n_utt, void *stream)
+{
+    (void)d_scratch; /* sea_hw25_scratch_bytes is 0 for this form */
+    if (n_utt <= 0) return 0;
+    if (!d_hout || !d_hev || !d_offsets || !d_lengths || !d_row_offsets || !d_cross_hc || !d_cross_ev || !d_pitch || !d_pratio ||
+        !d_mark)
+        return fail("hw25_correlogram: null pointer (only d_acf_hc, d_acf_ev, d_scratch and d_order may be null)");
+    DeviceCtx *c;
+    sea::Hw25Args a;
+    if (ctx(&c) || hw25_args(a, n_utt)) return 1;
+    a.hout = const_cast<float *>(d_hout);
+    a.hev = const_cast<float *>(d_hev);
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.row_offsets = d_row_offsets;
+    a.acf_hc = d_acf_hc;
+    a.acf_ev = d_acf_ev;
+    a.cross_hc = d_cross_hc;
+    a.cross_ev = d_cross_ev;
+    a.pitch = d_pitch;
+    a.pratio = d_pratio;
+    a.mark = d_mark;
+    a.order = d_order;
+    /* the lengths stay on the device: a fixed number of workgroups per utterance walks its frames, about eight workgroups
+     * per CU over the batch; the utterances go on grid x (y ends at 65535) */
+    int per_utt = (8 * c->n_cu + n_utt - 1) / n_utt;
+    per_utt = per_utt < 1 ? 1 : (per_utt > 1024 ? 1024 : per_utt);
+    hipLaunchKernelGGL(sea::hw25_correlogram_kernel, dim3(n_utt, per_utt), dim3(256), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_hw25_frontend_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
+                            const long long *d_lengths, const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev,
+                            float *d_cross_hc, float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
+                            const int *d_order, int n_utt, void *stream)
+{
+    if (sea_hw25_periphery_batch(d_in_f32, d_hout, d_hev, d_offsets, d_lengths, d_order, n_utt, stream)) return 1;
+    return sea_hw25_correlogram_batch(d_hout, d_hev, d_offsets, d_lengths, d_row_offsets, d_acf_hc, d_acf_ev, d_cross_hc,
+                                      d_cross_ev, d_pitch, d_pratio, d_mark, d_scratch, d_order, n_utt, stream);
+}
+
+int sea_hw25_frontend(const float *in, long L, float *hout, float *hev, float *acf_hc, float *acf_ev, float *cross_hc,
+                      float *cross_ev, int *pitch, float *pratio, float *mark)
+{
+    if (L <= 0) return fail("hw25_frontend: L=%ld", L);
+    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
+    DevBuf<float> din, dho, dhe, dah, dae, dfr;
+    DevBuf<int> dp;
+    DevBuf<long long> dmeta;
+    HIP_TRY(din.alloc((size_t)Lp));
+    HIP_TRY(dho.alloc((size_t)Lp * SEA_HW25_NCHAN));
+    HIP_TRY(dhe.alloc((size_t)Lp * SEA_HW25_NCHAN));
+    if (acf_hc) HIP_TRY(dah.alloc((size_t)rows * SEA_HW25_NCHAN * SEA_HW25_DELAYS));
+    if (acf_ev) HIP_TRY(dae.alloc((size_t)rows * SEA_HW25_NCHAN * SEA_HW25_DELAYS));
+    HIP_TRY(dfr.alloc((size_t)rows * SEA_HW25_NCHAN * 4)); /* cross_hc | cross_ev | pratio | mark */
+    HIP_TRY(dp.alloc((size_t)rows));
+    HIP_TRY(dmeta.alloc(3));
+    const long long meta[3] = {0, L, 0};
+    const size_t fr = (size_t)rows * SEA_HW25_NCHAN;
+    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
+    HIP_TRY(hipMemcpy(din.p, in, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
+    if (sea_hw25_frontend_batch(din.p, dho.p, dhe.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dah.p, dae.p, dfr.p, dfr.p + fr, dp.p,
+                                dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
+        return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t rowb = (size_t)L * sizeof(float);
+    if (hout) HIP_TRY(hipMemcpy2D(hout, rowb, dho.p, (size_t)Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
+    if (hev) HIP_TRY(hipMemcpy2D(hev, rowb, dhe.p, (size_t)Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
+    if (F > 0) {
+        const size_t nf = (size_t)F * SEA_HW25_NCHAN * sizeof(float);
+        if (acf_hc) HIP_TRY(hipMemcpy(acf_hc, dah.p, nf * SEA_HW25_DELAYS, hipMemcpyDeviceToHost));
+        if (acf_ev) HIP_TRY(hipMemcpy(acf_ev, dae.p, nf * SEA_HW25_DELAYS, hipMemcpyDeviceToHost));
+        if (cross_hc) HIP_TRY(hipMemcpy(cross_hc, dfr.p, nf, hipMemcpyDeviceToHost));
+        if (cross_ev) HIP_TRY(hipMemcpy(cross_ev, dfr.p + fr, nf, hipMemcpyDeviceToHost));
+        if (pratio) HIP_TRY(hipMemcpy(pratio, dfr.p + 2 * fr, nf, hipMemcpyDeviceToHost));
+        if (mark) HIP_TRY(hipMemcpy(mark, dfr.p + 3 * fr, nf, hipMemcpyDeviceToHost));
+        if (pitch) HIP_TRY(hipMemcpy(pitch, dp.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+    }
     return 0;
 }
 

@@ -26,6 +26,7 @@ struct DeviceCtx {
     sea_gt_tables *gt = nullptr;
     sea_ns16k_tables *ns16 = nullptr;
     sea_wb_tables *wb = nullptr;
+    sea_hw25_tables *hw25 = nullptr;
     int n_cu = 256;
 };
 

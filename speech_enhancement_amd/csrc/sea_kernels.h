@@ -331,6 +331,29 @@ struct IrmArgs {
 };
 __global__ void irm_target_kernel(IrmArgs a); /* per-lane codelet, lane = (polyphase component, frame) */
 
+/* The Hu-Wang estimator's front half on the 25-channel 8 kHz bank (hw25_kernel.hip).  in: packed float samples on the int16
+ * scale, utterance u at in + offsets[u] (offsets multiples of 8, `pitch` floats readable); hout / hev: utterance u's
+ * [25][pitch] block at offsets[u] * 25, pitch = lengths[u] rounded up to 8; the frame outputs are rows, utterance u's
+ * lengths[u] / 80 rows starting at row_offsets[u]: acf_* [rows][25][101] (either may be null: not written), cross_*, pratio,
+ * mark [rows][25], pitch [rows]. */
+struct Hw25Args {
+    const float *in;
+    float *hout, *hev;
+    const long long *offsets;
+    const long long *lengths;
+    const long long *row_offsets;
+    float *acf_hc, *acf_ev;
+    float *cross_hc, *cross_ev;
+    int *pitch;
+    float *pratio, *mark;
+    const int *order;
+    const sea_hw25_tables *tables;
+    int n_utt;
+};
+__global__ void hw25_periphery_kernel(Hw25Args a);   /* grid n_utt x 64 threads */
+__global__ void hw25_lowpass_kernel(Hw25Args a);     /* grid (n_utt, 25) x 256 */
+__global__ void hw25_correlogram_kernel(Hw25Args a); /* grid (n_utt, G) x 256: workgroup (u, g) takes frames g, g + G, ... */
+
 __global__ void subband_kernel(SubbandArgs a);
 __global__ void ns_denoise_pipe_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_big_kernel(NsBatchArgs a); /* lower-register form for > 4 utterances per CU */

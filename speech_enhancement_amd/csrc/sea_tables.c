@@ -582,6 +582,111 @@ void sea_build_gt_tables(sea_gt_tables *t)
 }
 
 /* ------------------------------------------------------------------------------------------
+ * The Hu-Wang estimator's 25-channel front end at 8 kHz (aurora_etsi_test/HuWang.cpp).  The file is C++: a math function
+ * of a float argument is the float overload there (expf, cosf, sinf, sqrtf, log10f, powf, fabsf below); pow (int, x) and
+ * pow (float, int) promote to double.
+ * ---------------------------------------------------------------------------------------- */
+static float hw_bessi0(float x)
+{ /* :1603-1621 */
+    float ax = fabsf(x), ans, y;
+    if (ax < 3.75) {
+        y = (float)(x / 3.75);
+        y *= y;
+        ans = (float)(1.0 + y * (3.5156229 + y * (3.0899424 + y * (1.2067492 + y * (0.2659732 + y * (0.360768e-1 + y * 0.45813e-2))))));
+    } else {
+        y = (float)(3.75 / ax);
+        ans = (float)((expf(ax) / sqrtf(ax)) *
+                      (0.39894228 +
+                       y * (0.1328592e-1 +
+                            y * (0.225319e-2 +
+                                 y * (-0.157565e-2 +
+                                      y * (0.916281e-2 + y * (-0.2057706e-1 + y * (0.2635537e-1 + y * (-0.1647633e-1 + y * 0.392377e-2)))))))));
+    }
+    return ans;
+}
+
+void sea_build_hw25_tables(sea_hw25_tables *t)
+{
+    const double kPiHW = 3.1415926535897932384626433832795; /* HuWang.h:7 */
+    const double Y = 5.05, G = 2000.0, Lc = 2500.0, R = 6580.0, X = 66.31, A = 3.0, B = 300.0, H = 48000.0, M = 1.0; /* HuWang.h:36-44 */
+    float erbLo = (float)(21.4 * log10(80 * 0.00437 + 1.0));
+    float erbHi = (float)(21.4 * log10(4000 * 0.00437 + 1.0));
+    float erbStep = (erbHi - erbLo) / (SEA_HW25_NCHAN - 1);
+    float dt = 1 / (float)8000;
+    float twoPiT = (float)(2 * kPiHW * dt);
+    int c;
+    memset(t, 0, sizeof *t);
+    for (c = 0; c < SEA_HW25_NCHAN; c++) { /* AudiPeriph:132-140, gammaToneFilter:216-223, computeACF:345-346 */
+        float cf = (float)((pow(10, (erbLo + c * erbStep) / 21.4) - 1) / 0.00437);
+        float bw = (float)(24.7 * (cf * 0.00437 + 1.0) * 1.019);
+        float phon = (float)(phons_at(cf) - 60.0);
+        float ear = (float)pow(10, (double)(phon / 20));
+        float z = expf(-twoPiT * bw);
+        int win = (int)(4 * 8000 / cf);
+        t->cf[c] = cf;
+        t->bw[c] = bw;
+        t->midEar[c] = ear;
+        t->gain[c] = (float)(ear * pow((double)(twoPiT * bw), 4.0) / 3.0);
+        t->f1[c] = cosf(cf * twoPiT) * z;
+        t->f2[c] = sinf(cf * twoPiT) * z;
+        t->winsize[c] = win < SEA_HW25_WINDOW ? SEA_HW25_WINDOW : win;
+        if (t->winsize[c] > SEA_HW25_MAXWIN) abort();
+    }
+    { /* kaiserPara (RIPPLE, float (STOPBAND - PASSBAND) / SAMPLING_FREQUENCY, ..), :1553-1569 */
+        const float delta = (float)0.01, transBw = (float)((float)(1200 - 1000) / 8000);
+        const float wn = (float)(1000 + 1200) / 8000; /* :311 */
+        float a = -20 * log10f(delta), beta, len;
+        int fLength, tim;
+        if (a <= 21) beta = 0;
+        else if (a <= 50) beta = (float)(0.5842 * powf(a - 21, (float)0.4) + 0.07889 * (a - 21));
+        else beta = (float)(0.1102 * (a - 8.7));
+        len = (float)((a - 7.95) / 14.36 / transBw);
+        fLength = (int)len;
+        if ((len - fLength) < 0.5) fLength++;
+        else fLength += 2;
+        if (fLength % 2 != 0) fLength++;
+        if (fLength != SEA_HW25_TAPS - 1) abort();
+        for (tim = 0; tim <= fLength; tim++) { /* kaiserLowPass, :1576-1590 */
+            float k = 2 * tim / (float)fLength - 1;
+            float f = hw_bessi0(beta * sqrtf(1 - k * k)) / hw_bessi0(beta);
+            int step = tim - fLength / 2;
+            if (step != 0) f = (float)(f * (sin(wn * kPiHW * step) / kPiHW / step));
+            else f *= wn;
+            t->lp[tim] = f;
+        }
+    }
+    { /* hairCell:261-274 */
+        float kt = (float)(G * A / (A + B));
+        t->ymdt = (float)(Y * M * dt);
+        t->xdt = (float)(X * dt);
+        t->ydt = (float)(Y * dt);
+        t->lplusrdt = (float)((Lc + R) * dt);
+        t->rdt = (float)(R * dt);
+        t->gdt = (float)(G * dt);
+        t->hdt = (float)H;
+        t->c0 = (float)(M * Y * kt / (Lc * kt + Y * (Lc + R)));
+        t->q0 = (float)(t->c0 * (Lc + R) / kt);
+        t->w0 = (float)(t->c0 * R / X);
+    }
+}
+
+void sea_hw25_plain_tables(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
+                           float *lp91, float *hair10)
+{
+    sea_hw25_tables t;
+    sea_build_hw25_tables(&t);
+    memcpy(cf25, t.cf, SEA_HW25_NCHAN * sizeof(float));
+    memcpy(bw25, t.bw, SEA_HW25_NCHAN * sizeof(float));
+    memcpy(midEar25, t.midEar, SEA_HW25_NCHAN * sizeof(float));
+    memcpy(gain25, t.gain, SEA_HW25_NCHAN * sizeof(float));
+    memcpy(f1_25, t.f1, SEA_HW25_NCHAN * sizeof(float));
+    memcpy(f2_25, t.f2, SEA_HW25_NCHAN * sizeof(float));
+    memcpy(winsize25, t.winsize, SEA_HW25_NCHAN * sizeof(int));
+    memcpy(lp91, t.lp, SEA_HW25_TAPS * sizeof(float));
+    memcpy(hair10, &t.ymdt, 10 * sizeof(float));
+}
+
+/* ------------------------------------------------------------------------------------------
  * The 16 k-native NoiseSup variant: function/20141106_speech_enhancement/aurora_etsi/
  * NoiseSup.cpp:1034-1079 (windows), MelProc.cpp:269-341 (InitGammawindows), :464-503 (InitGammaIDCTbasis),
  * :505-513 (ERB scale), rfft.cpp:46-181 called with (512, 8).  These files are C++: cos / sin of a float there are

@@ -226,6 +226,34 @@ void sea_build_wb_tables(sea_wb_tables *t);
 /* plain tables for host-side checks */
 void sea_wb_plain_tables(float *qmfLp118, float *qmfHp118, int *hpMelStart3, int *hpMelLen3, float *hpMelW3x64, float *dct12x26);
 
+/* ---- the Hu-Wang estimator's 25-channel 8 kHz front end (function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp,
+ * HuWang.h): the bank of AudiPeriph:121-140 + gammaToneFilter:216-223 at dt = 1/8000, computeACF's window sizes (:345-346),
+ * lowPass's Kaiser filter (:309-311, :1553-1621) and hairCell's constants (:261-274).  Every value is evaluated in the type
+ * the reference's C++ expression has (float variables, double literals, the float overloads of exp / cos / sin / sqrt /
+ * log10 / pow where the argument is a float). */
+enum {
+    SEA_HW25_NCHAN = 25,   /* NUMBER_CHANNEL */
+    SEA_HW25_DELAYS = 101, /* MAX_DELAY = 8000 / 80 + 1 */
+    SEA_HW25_MINDELAY = 16, /* MIN_DELAY = 8000 / 500 */
+    SEA_HW25_WINDOW = 200, /* WINDOW = 8000 / 40 */
+    SEA_HW25_HOP = 80,     /* OFFSET = 8000 / 100 */
+    SEA_HW25_TAPS = 91,    /* fLength + 1, fLength = 90 from kaiserPara (0.01, 200 / 8000.) */
+    SEA_HW25_MAXWIN = 400  /* the widest window: channel 0, int (4 * 8000 / cf) */
+};
+typedef struct {
+    float cf[32], bw[32], midEar[32];             /* entries 0..24 */
+    float gain[32], f1[32], f2[32];
+    int winsize[32];
+    float lp[96];                                 /* the 91 taps of kaiserLowPass */
+    float ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt; /* hairCell:261-268 */
+    float q0, c0, w0;                             /* its initial state, :271-274 */
+    float pad[2];
+} sea_hw25_tables;
+void sea_build_hw25_tables(sea_hw25_tables *t);
+/* plain tables for host-side checks; hair10 = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0 */
+void sea_hw25_plain_tables(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
+                           float *lp91, float *hair10);
+
 void sea_build_ns_tables(sea_ns_tables *t);
 void sea_build_cc_tables(sea_cc_tables *t);
 void sea_build_gt_tables(sea_gt_tables *t);

@@ -229,11 +229,12 @@ class PackedBatch:
         return offsets, total, launch_order(lengths)
 
     @classmethod
-    def from_arrays(cls, utterances, device="cuda"):
+    def from_arrays(cls, utterances, device="cuda", dtype=np.int16):
+        """dtype: int16 audio everywhere; float32 only for the hw25_* calls, which take float samples on the int16 scale."""
         torch = _torch()
         lengths = np.array([len(u) for u in utterances], dtype=np.int64)
         offsets, total, order = cls.layout(lengths)
-        host = np.zeros(max(total, 8), np.int16)
+        host = np.zeros(max(total, 8), dtype)
         for u, off in zip(utterances, offsets):
             host[off:off + len(u)] = u
         return cls(torch.from_numpy(host).to(device), torch.from_numpy(offsets).to(device),
@@ -938,6 +939,147 @@ def irm_target_batch(batch, pure_sub, noise_sub, window=1):
                                         _dptr(d_offs), _dptr(irm), int(window), batch.n_utt, _stream_ptr()),
                "sea_irm_target_batch")
     return MaskBatch(irm, d_offs, offs, rows)
+
+
+# ------------------------------------------------------------------------------------------------
+# the Hu-Wang estimator's front half on the 25-channel 8 kHz bank (aurora_etsi_test/HuWang.cpp:41-76; csrc/hw25_kernel.hip)
+# ------------------------------------------------------------------------------------------------
+HW25_NCHAN, HW25_DELAYS, HW25_HOP = 25, 101, 80
+
+
+def hw25_tables():
+    """The bank's host tables: cf, bw, midEarCoeff, gain, f1, f2 [25], winsize int32 [25], lp [91] (lowPass's Kaiser taps) and
+    hair [10] = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0."""
+    lib = _lib.load()
+    t = {k: np.zeros(HW25_NCHAN, np.float32) for k in ("cf", "bw", "midEarCoeff", "gain", "f1", "f2")}
+    t.update(winsize=np.zeros(HW25_NCHAN, np.int32), lp=np.zeros(91, np.float32), hair=np.zeros(10, np.float32))
+    keys = ("cf", "bw", "midEarCoeff", "gain", "f1", "f2", "winsize", "lp", "hair")
+    _lib.check(lib.sea_hw25_tables_host(*[_np_ptr(t[k]) for k in keys]), "sea_hw25_tables_host")
+    return t
+
+
+def _hw25_input(batch):
+    """createIBM takes float samples on the int16 scale: an int16 batch converts exactly, a float32 one is used as it is"""
+    torch = _torch()
+    if batch.data.dtype == torch.float32:
+        return batch.data
+    if batch.data.dtype != torch.int16:
+        raise ValueError("hw25: the batch must hold int16 or float32 samples")
+    return batch.data.to(torch.float32)
+
+
+def hw25_periphery_batch(batch, use_order=True):
+    """AudiPeriph + lowPass for every utterance of the batch: (hOut, hEv), two float32 tensors of 25x the packed size;
+    utterance u's [25][pitch] block starts at offsets[u]*25, pitch = length rounded up to 8 (hw25_split cuts them)."""
+    torch = _torch()
+    lib = _lib.load()
+    x = _hw25_input(batch)
+    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=x.device)
+    hev = torch.zeros_like(hout)
+    rc = lib.sea_hw25_periphery_batch(_dptr(x), _dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths),
+                                      _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_periphery_batch")
+    return hout, hev
+
+
+def hw25_split(batch, tensor):
+    """A hw25_periphery_batch() tensor -> per-utterance numpy arrays [25][L]."""
+    host = tensor.detach().cpu().numpy()
+    out = []
+    for off, L in zip(batch.host_offsets, batch.host_lengths):
+        pitch = (int(L) + 7) // 8 * 8
+        out.append(host[off * HW25_NCHAN:off * HW25_NCHAN + HW25_NCHAN * pitch].reshape(HW25_NCHAN, pitch)[:, :int(L)].copy())
+    return out
+
+
+class Hw25Result:
+    """What hw25_frontend_batch() computed, device tensors: hout, hev (25x the packed size), cross_hc, cross_ev, pratio, mark
+    [rows][25], pitch int32 [rows], acf_hc, acf_ev [rows][25][101] or None; row_offsets / host_row_offsets / host_rows say
+    where utterance u's length // 80 rows are.  utterance(u) returns numpy views of one utterance under the reference's names."""
+
+    def __init__(self, batch, **kw):
+        self.batch = batch
+        self.__dict__.update(kw)
+
+    def utterance(self, u):
+        r0, n = int(self.host_row_offsets[u]), int(self.host_rows[u])
+        off, L = int(self.batch.host_offsets[u]), int(self.batch.host_lengths[u])
+        pitch = (L + 7) // 8 * 8
+
+        def rows(t):
+            return None if t is None else t[r0:r0 + n].cpu().numpy()
+
+        def block(t):
+            return t[off * HW25_NCHAN:off * HW25_NCHAN + HW25_NCHAN * pitch].cpu().numpy().reshape(HW25_NCHAN, pitch)[:, :L]
+
+        return dict(hOut=block(self.hout), hEv=block(self.hev), acf_hc=rows(self.acf_hc), acf_ev=rows(self.acf_ev),
+                    cross_hc=rows(self.cross_hc), cross_ev=rows(self.cross_ev), pitch=rows(self.pitch), pRatio=rows(self.pratio),
+                    mark=rows(self.mark))
+
+
+def _hw25_outputs(batch, dev, want_acf):
+    """the frame outputs of a batch (at least one row, so that no tensor is empty), the row offsets and the scratch"""
+    torch = _torch()
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
+    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
+    n = max(int(rows.sum()), 1)
+    fr = {k: torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev) for k in ("cross_hc", "cross_ev", "pratio", "mark")}
+    acf = [torch.zeros((n, HW25_NCHAN, HW25_DELAYS), dtype=torch.float32, device=dev) if want_acf else None for _ in range(2)]
+    nbytes = int(_lib.load().sea_hw25_scratch_bytes(int(batch.total), int(batch.n_utt)))
+    return dict(rows=rows, offs=offs, d_offs=torch.from_numpy(offs).to(dev), fr=fr, acf=acf,
+                pitch=torch.zeros(n, dtype=torch.int32, device=dev),
+                scratch=torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None)
+
+
+def hw25_correlogram_batch(batch, hout, hev, want_acf=False, use_order=True):
+    """computeACF, crossCorr, globalPitch, timeCrn and the initial labelling from hw25_periphery_batch()'s tensors."""
+    lib = _lib.load()
+    o = _hw25_outputs(batch, hout.device, want_acf)
+    fr, acf, pitch, d_offs, scratch = o["fr"], o["acf"], o["pitch"], o["d_offs"], o["scratch"]
+    rc = lib.sea_hw25_correlogram_batch(_dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs),
+                                        _dptr(acf[0]), _dptr(acf[1]), _dptr(fr["cross_hc"]), _dptr(fr["cross_ev"]), _dptr(pitch),
+                                        _dptr(fr["pratio"]), _dptr(fr["mark"]), _dptr(scratch),
+                                        _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_correlogram_batch")
+    return Hw25Result(batch, hout=hout, hev=hev, acf_hc=acf[0], acf_ev=acf[1], pitch=pitch, row_offsets=d_offs,
+                      host_row_offsets=o["offs"], host_rows=o["rows"], **fr)
+
+
+def hw25_frontend_batch(batch, want_acf=False, use_order=True):
+    """The front half of createIBM() for every utterance of the batch, one launch group on the current stream -> Hw25Result.
+    The ACFs are [rows][25][101] floats per stream (about 8 MB per 4 s utterance): computed always, written only on request."""
+    torch = _torch()
+    lib = _lib.load()
+    x = _hw25_input(batch)
+    dev = x.device
+    o = _hw25_outputs(batch, dev, want_acf)
+    fr, acf, pitch, d_offs, scratch = o["fr"], o["acf"], o["pitch"], o["d_offs"], o["scratch"]
+    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=dev)
+    hev = torch.zeros_like(hout)
+    rc = lib.sea_hw25_frontend_batch(_dptr(x), _dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs),
+                                     _dptr(acf[0]), _dptr(acf[1]), _dptr(fr["cross_hc"]), _dptr(fr["cross_ev"]), _dptr(pitch),
+                                     _dptr(fr["pratio"]), _dptr(fr["mark"]), _dptr(scratch),
+                                     _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_frontend_batch")
+    return Hw25Result(batch, hout=hout, hev=hev, acf_hc=acf[0], acf_ev=acf[1], pitch=pitch, row_offsets=d_offs,
+                      host_row_offsets=o["offs"], host_rows=o["rows"], **fr)
+
+
+def hw25_frontend(x, want_acf=True):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict under the reference's names:
+    hOut, hEv [25][L]; acf_hc, acf_ev [F][25][101] (None without want_acf); cross_hc, cross_ev, pRatio, mark [F][25]; pitch [F]."""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    L, F = x.size, x.size // HW25_HOP
+    r = dict(hOut=np.zeros((HW25_NCHAN, L), np.float32), hEv=np.zeros((HW25_NCHAN, L), np.float32),
+             acf_hc=np.zeros((F, HW25_NCHAN, HW25_DELAYS), np.float32) if want_acf else None,
+             acf_ev=np.zeros((F, HW25_NCHAN, HW25_DELAYS), np.float32) if want_acf else None,
+             cross_hc=np.zeros((F, HW25_NCHAN), np.float32), cross_ev=np.zeros((F, HW25_NCHAN), np.float32),
+             pitch=np.zeros(F, np.int32), pRatio=np.zeros((F, HW25_NCHAN), np.float32), mark=np.zeros((F, HW25_NCHAN), np.float32))
+    keys = ("hOut", "hEv", "acf_hc", "acf_ev", "cross_hc", "cross_ev", "pitch", "pRatio", "mark")
+    rc = lib.sea_hw25_frontend(_np_ptr(x), L, *[_np_ptr(r[k]) if r[k] is not None else None for k in keys])
+    _lib.check(rc, "sea_hw25_frontend")
+    return r
 
 
 # ------------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what afeslices --steps 7  # the 8 kHz feature chain in time slices and from host buffers, opt-in
     python tools/bench_extra.py --what cepsslices --steps 7  # NoiseSup + the plain CompCeps in time slices and from host buffers, both rates, opt-in
     python tools/bench_extra.py --what trainset --steps 7  # the training-set builder: mix, subbands, IRM, pipeline and host entry point, opt-in
+    python tools/bench_extra.py --what hw25 --steps 5  # the Hu-Wang front half on the 25-channel bank: periphery, correlogram, launch group, opt-in
 """
 import argparse
 import json
@@ -1058,6 +1059,55 @@ def main():
                        "host_make_trainset_ms": sorted(hs)[len(hs) // 2], "host_make_trainset_ms_sorted": sorted(hs),
                        "host_chunks": r["chunks"]},
             "kernels": "mix_sums_kernel + mix_scale_kernel + sea::subband_kernel x2 (x3) + sea::irm_target_kernel"}), flush=True)
+
+    if "hw25" in what:
+        # The Hu-Wang estimator's front half on the 25-channel 8 kHz bank, on the --utts corpus batch taken as float samples:
+        # the periphery (gammatone + hair cell + low-pass), the correlogram without and with the two ACF outputs, and the launch
+        # group (periphery + correlogram without ACFs).  Device events around every step, one warm-up discarded, median.  The
+        # correlogram's arithmetic is 2 x 101 x 5282 multiply-adds per frame (the window sizes sum to 5282).
+        lib = sea.load()
+        n = batch.n_utt
+        x = batch.data.to(torch.float32)
+        rows = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames = int(rows.sum())
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev = z(batch.total * 25), z(batch.total * 25)
+        cross_hc, cross_ev, pratio, mark, pitch = z((frames, 25)), z((frames, 25)), z((frames, 25)), z((frames, 25)), z(frames, torch.int32)
+        acf_hc, acf_ev = z((frames, 25, 101)), z((frames, 25, 101))
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def periphery():
+            assert lib.sea_hw25_periphery_batch(P(x), P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def correlogram(a0=None, a1=None):
+            assert lib.sea_hw25_correlogram_batch(P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(a0), P(a1), P(cross_hc),
+                                                  P(cross_ev), P(pitch), P(pratio), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def group():
+            assert lib.sea_hw25_frontend_batch(P(x), P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), None, None, P(cross_hc),
+                                               P(cross_ev), P(pitch), P(pratio), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+        macs = frames * 2 * 101 * 5282
+        samples = int(np.sum(batch.host_lengths))
+        workload = f"the {args.utts}-utterance corpus as 8 kHz float samples: {samples} samples, {frames} frames of 80; median of {args.steps} steps after one warm-up"
+        for name, fn, kernels in (("periphery (25-channel gammatone + hair cell + 91-tap low-pass)", periphery, "sea::hw25_periphery_kernel + sea::hw25_lowpass_kernel"),
+                                  ("correlogram without ACF outputs", correlogram, "sea::hw25_correlogram_kernel"),
+                                  ("correlogram with both ACF outputs", lambda: correlogram(acf_hc, acf_ev), "sea::hw25_correlogram_kernel"),
+                                  ("launch group: periphery + correlogram without ACF outputs", group,
+                                   "sea::hw25_periphery_kernel + sea::hw25_lowpass_kernel + sea::hw25_correlogram_kernel")):
+            med, t = median_ms(fn, args.steps)
+            line = {"metric": f"Hu-Wang front half, 25-channel 8 kHz bank: {name} (frames of 80 samples/sec); a first form, not tuned",
+                    "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
+                    "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}
+            if "correlogram" in name:
+                line["multiply_adds_per_step"] = macs
+                line["multiply_adds_per_sec"] = macs / (med / 1e3)
+            else:
+                line["samples_per_sec"] = samples / (med / 1e3)
+            print(json.dumps(line), flush=True)
+        del hout, hev, acf_hc, acf_ev
 
     if "rfft" in what:
         n = 1 << 18
