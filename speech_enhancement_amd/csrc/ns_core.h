@@ -1287,14 +1287,15 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
 }
 
 /* ---- the second-stage BACK half cut in two (six-wave kernel, ns_pipe6_kernel.hip) -------------------
- * ns_noise1 (wave N1): PSDMean, the non-VAD noise tracking of all 65 bins, the in-order sum of the
- *   noise spectrum and the gain-factor scalars (NoiseSup.c:289-303, :486-517, :600-637).  None of it
- *   depends on the Wiener gains, so it runs one frame ahead of ns_gain1.  Writes P[0..64] (mean PSD),
- *   noise[0..64] and returns alfaGF; the caller has loaded s.denEn0..2.
+ * ns_noise1 (wave N1): PSDMean and the non-VAD noise tracking of all 65 bins (NoiseSup.c:289-303,
+ *   :486-517).  None of it depends on the Wiener gains, so it runs ahead of ns_gain1.  Writes P[0..64]
+ *   (mean PSD) and noise[0..64].  The in-order sum of the noise spectrum is taken by the helper wave
+ *   (helper_chains<.., .., true>), the gain-factor scalars (:600-637) follow from it in N1 again
+ *   (gain_fact_update; ns_pipe6_kernel.hip has the schedule).
  * ns_gain1 (wave G1): the gains of all bins from (P, PSD, noise), mel filter bank, gain
  *   factorisation of the 25 mel gains, IDCT, FIR (:522-560, MelProc.c, :639-640, :324-340). */
-__device__ __forceinline__ float ns_noise1(const float *psd, float *Pout, float *noiseOut, NsRegs &s, float eps,
-                                           int lane)
+__device__ __forceinline__ void ns_noise1(const float *psd, float *Pout, float *noiseOut, NsRegs &s, float eps,
+                                          int lane)
 {
     const float nSigLo = psd[lane], nSigHi = psd[64];
     const float PLo = (s.prevLo[1] + nSigLo) * 0.5f;
@@ -1326,9 +1327,6 @@ __device__ __forceinline__ float ns_noise1(const float *psd, float *Pout, float 
         noiseOut[64] = s.noiseHi[1];
     }
     wave_sync();
-    const float total = ns_lane_sum65(s.noiseLo[1], s.noiseHi[1]); /* in-order sum of the noise spectrum */
-    gain_fact_update(s, total);
-    return s.alfaGF;
 }
 
 __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const float *noise, float alfaGF,
@@ -1496,20 +1494,32 @@ __device__ __forceinline__ bool dc_step_ok(float d, float yPrev)
 /* FDCH (four-wave fd kernel): three more sums in lanes 48..50, which otherwise repeat the DC chain -- the mean and the
  * sum of squares of the first 64 Wiener gains (SpeechQVar) and the sum of the 25 mel-filtered gains (SpeechQSpec) of
  * the frame whose record fdRec is (kFdRecFloats); returned in fdSums[0..2]. */
-template <int CHUNKS, bool FDCH = false>
+/* NZ (six-wave forms): a fourth in-order sum in lanes 48..63, which otherwise repeat the DC chain -- the 65 second-stage
+ * noise magnitudes nz[0..64] (NoiseSup.c:600-604), the same arithmetic as the den sum: RN(1 * acc + x) from acc = 0,
+ * nz[65..67] must be zero, x = 0 from n = 68 on; returned in *nzSum.  Its zero tail is folded into the
+ * per-lane offsets before the stream as the den chain's is, so the stream keeps its instruction count (113 instructions between
+ * the 80 FMAs of the dense six-wave kernel's listing, with and without NZ). */
+template <int CHUNKS, bool FDCH = false, bool NZ = false>
 __device__ __forceinline__ void helper_chains(const float *sq, const float *den, const float *dif, float *out,
                                               const float *zero4, float &vadSum, float &denSum,
                                               float &y, int lane, bool *unsafe = nullptr, const float *fdRec = nullptr,
-                                              float *fdSums = nullptr)
+                                              float *fdSums = nullptr, const float *nz = nullptr, float *nzSum = nullptr)
 {
+    static_assert(!(FDCH && NZ), "lanes 48..63 carry either the fd sums or the noise sum");
     const int g = lane >> 4;
     const bool fdLane = FDCH && lane >= 48 && lane <= 50;
     const float *src = (g == 0) ? sq : ((g == 1) ? den : dif);
     if (FDCH && fdLane) src = fdRec + 64 * (lane - 48);
+    if (NZ && g == 3) src = nz;
     const float *tail = (g == 1) ? zero4 : src; /* the den chain runs out after 65 terms: x = 0 from n = 68 on */
+    if (NZ && g == 3) tail = zero4;             /* and so does the noise chain */
     const int fdLim = FDCH ? ((lane == 50) ? 28 : (fdLane ? 64 : SEA_HOP)) : SEA_HOP; /* an fd chain's first quad of zeros */
-    const float m = (g >= 2 && !fdLane) ? 0.9990234375f : 1.0f;
+    float m = (g >= 2 && !fdLane) ? 0.9990234375f : 1.0f;
     float acc = (g == 0) ? 64.0f : ((g == 1 || fdLane) ? 0.0f : y);
+    if (NZ && g == 3) {
+        m = 1.0f;
+        acc = 0.0f;
+    }
     /* the 20 quads are requested in CHUNKS chunks (4: 2 x 20 VGPRs in flight; 10: 2 x 8, for the 80-VGPR kernel
      * forms), chunk c + 1 before the chain of chunk c starts (an LDS round trip is ~60 clk) */
     constexpr int kQ = SEA_HOP / 4 / CHUNKS;
@@ -1519,7 +1529,7 @@ __device__ __forceinline__ void helper_chains(const float *sq, const float *den,
 #pragma unroll
         for (int k = 0; k < kQ; ++k) {
             const int n = 4 * (c * kQ + k);
-            const float *p = (n >= 68) ? tail + ((g == 1) ? 0 : n) : src + n;
+            const float *p = (n >= 68) ? tail + (NZ ? ((g == 1 || g == 3) ? 0 : n) : ((g == 1) ? 0 : n)) : src + n;
             if (FDCH && n >= 28) p = (n >= fdLim) ? zero4 : p;
             dstq[k] = *reinterpret_cast<const float4 *>(p);
         }
@@ -1577,6 +1587,7 @@ __device__ __forceinline__ void helper_chains(const float *sq, const float *den,
         fdSums[1] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 49));
         fdSums[2] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 50));
     }
+    if (NZ) *nzSum = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 48));
     wave_sync();
 }
 

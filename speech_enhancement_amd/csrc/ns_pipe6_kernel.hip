@@ -11,13 +11,21 @@
  *            + levels n2 = 8, 16, 32 of BOTH transforms (stage 0 of frame i, stage 1 of frame i-3)
  *   wave FB  i+1 / i+4:   levels n2 = 64, 128, 256 and the two 65-bin PSDs
  *   wave B0  frame i-2:   stage-0 FilterCalc, VAD, mel, IDCT, FIR -> stage-1 buffer
- *   wave N1  frame i-5:   stage-1 PSD mean, noise tracking, in-order noise sum, gain-factor scalars
- *   wave G1  frame i-6:   stage-1 Wiener gains, mel, gain factorisation, IDCT, FIR
+ *   wave N1  frame i-5:   stage-1 PSD mean, noise tracking -> P, noise
+ *            frame i-7:   gain-factor scalars from S's noise sum and the denSigSE1 sums -> alfa
+ *   wave G1  frame i-8:   stage-1 Wiener gains, mel, gain factorisation, IDCT, FIR
  *   wave S   the lane-grouped scalar chains: VAD log-energy of the frame pushed at i-1, in-order sum of
- *            denSigSE1 of frame i-3, DC-offset recurrence + cast + store of frame i-7
+ *            denSigSE1 of frame i-3, in-order sum of the noise spectrum of frame i-6, DC-offset recurrence
+ *            + cast + store of frame i-9 (kDepth)
+ *
+ * Round 6: the in-order sum of the 65 second-stage noise magnitudes (64 v_readlane + v_add in N1, ~129 vector instructions
+ * for one scalar) rides the helper wave's serial stream in lanes 48..63, which only repeated the DC chain: no instruction
+ * more there.  N1's frame is thereby cut in two jobs two beats apart, and G1 and S's output follow two beats later than
+ * before; the lifetimes and ring depths are derived beside kP1Ring below.  configs[1]: 1.84 -> 1.76 ms = 465 M frames/s
+ * (profiles/ns6_noise_sum_in_helper.txt).
  *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
- * iteration, read at the next; the stage-1 PSD, which N1 and then G1 read in place, in a ring of four); the two
+ * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
  * and whether they produce output follow from ONE number per utterance, the index of its first non-zero frame, which
  * FA publishes once (kNoOnset / onset_poll below).
@@ -61,12 +69,14 @@ struct RoleTimer6 {
 #define NS6_T_FLUSH(r, n)
 #endif
 
-constexpr int kSlots = 8;
+constexpr int kSlots = 8;   /* stage-0 buffer, and the per-tick rings frameEn, frameEnLog, denSum, fdFlags */
+constexpr int kSlots1 = 16; /* stage-1 buffer (derivation at kP1Ring) */
 constexpr int kSlotLen = SEA_HOP;
 constexpr int kCirc = kSlots * kSlotLen;
+constexpr int kCirc1 = kSlots1 * kSlotLen;
 constexpr int kMirror = 3 * kSlotLen;
 constexpr int kWaves = 6;
-constexpr int kDepth = 7; /* S stores frame i - kDepth */
+constexpr int kDepth = 9; /* S stores frame i - kDepth */
 constexpr int kSChunks = 10; /* helper_chains: the helper wave's 20 quads are requested in ten chunks (2 x 8 VGPRs in flight) */
 /* issue priority by remaining frames: evaluated every kPrioStep frames, kPrioLevels levels dithered into the four hardware ones
  * (the rule and its measurements: ns_pipe_kernel.hip) */
@@ -100,25 +110,45 @@ __device__ __forceinline__ int tick_of(int f, int onset) { return (int)((unsigne
 /* frame f exists and has tick >= k (k >= 1; f may be negative: onset >= 0) */
 __device__ __forceinline__ bool tick_ge(int f, int k, int onset, int nfr) { return f < nfr && f - (k - 1) >= onset; }
 
-constexpr int kP1Ring = 4; /* stage-1 PSD of frame f: written by FB at iteration f+4, read by N1 at f+5 and by G1 at f+6; slot f is
-                            * written again at iteration f+kP1Ring+4, which has to be >= f+7: three would do; four, for 272 B more LDS, makes the
-                            * slot index a mask (& 3) instead of a division by three */
+/* The second-stage schedule and its ring depths.  Everything written at iteration w is visible from iteration w+1 on (the frame
+ * barrier); a slot may be written again at the iteration of its last read at the earliest when writer and reader touch different
+ * slots there, i.e. a ring of depth D written at f+w and last read at f+r needs f+D+w > f+r: D > r - w.
+ *   frame f is        transformed (stage 1) by FA at f+3, FB at f+4       (unchanged)
+ *                     noise-tracked by N1 at f+5      -> rn[f].P, rn[f].noise
+ *                     noise-summed by S at f+6        -> nzSum[f]          (the 65 addends are rn[f].noise)
+ *                     gain-factored by N1 at f+7      -> alfa[f]           (nzSum[f], denSum of ticks t-2 .. t)
+ *                     filtered by G1 at f+8           -> ro[f]             (p1[f], rn[f], alfa[f], stage-1 buffer)
+ *                     DC-filtered and stored by S at f+9 = f+kDepth
+ *   p1 (stage-1 PSD)  written by FB at f+4, read by N1 at f+5 and by G1 at f+8: D > 4, five would do; eight makes the slot a mask
+ *   rn (P, noise)     written at f+5, read by S at f+6 and by G1 at f+8: D > 3, kRnRing = 4
+ *   nzSum, alfa, ro   written at one iteration, read at the next: D > 1, by frame parity
+ *   denSum[tick & 7]  tick t (frame f) written by S at f+3; N1 reads ticks t-2 .. t for the frames f .. f+2, the last at f+9: D > 6
+ *   fdFlags[tick & 7] written by B0 at f+2, read by S at f+9: D > 7 -- eight still hold, by one
+ *   frameEn, frameEnLog, rd, p0: between FA, B0 and S's first two chains, whose frame offsets did not move
+ *   stage-1 buffer    B0 writes the slot of tick t+6 (frame f+6, at iteration f+8) while G1 reads the window of tick t, slots
+ *                     t-3 .. t, and FA that of tick t+5 (frame f+5 at f+8), slots t+2 .. t+5: ten live slots, eight collide
+ *                     (t+6 = t-2 mod 8), so kSlots1 = 16, with the same three mirrored slots behind the last one
+ * nbFrame of the gain-factor job: N1's counter has by then counted the two frames tracked since; the job takes the frame's own
+ * count, tick - 4 (the first second-stage frame has tick 5).
+ * LDS: 24 624 B per workgroup (was 19 904); four workgroups per CU take 98.5 KB of the 160. */
+constexpr int kP1Ring = 8;
+constexpr int kRnRing = 4;
 struct __attribute__((aligned(16))) RecPsd { /* FB -> B0 (stage 0) / N1, G1 (stage 1) */
     float psd[68];
 };
 struct __attribute__((aligned(16))) RecDen { /* B0 -> S */
     float den[68];
 };
-struct __attribute__((aligned(16))) RecN { /* N1 -> G1 */
+struct __attribute__((aligned(16))) RecN { /* N1 -> S (noise[0..67], [65..67] stay zero), G1 */
     float P[68], noise[68];
-    float alfa;
 };
 struct __attribute__((aligned(16))) RecOut { /* G1 -> S */
     float out[80]; /* second-stage filter output before the DC-offset filter */
 };
 
 struct __attribute__((aligned(16))) Pipe6Lds {
-    float circ[2][kCirc + kMirror];
+    float circ0[kCirc + kMirror];   /* stage-0 buffer: kSlots slots and three mirrored ones */
+    float circ1[kCirc1 + kMirror];  /* stage-1 buffer: kSlots1 slots and three mirrored ones */
     float work[2][512];             /* transform work areas: FA fills [i & 1], FB finishes [(i-1) & 1] */
     BackLds back[2];                /* scratch of B0 and G1 */
     float ssq[80], sdif[80], sout[80], szero[4]; /* scratch of S */
@@ -129,18 +159,44 @@ struct __attribute__((aligned(16))) Pipe6Lds {
     float idctT[SEA_NMEL * 16];
     RecPsd p0[2], p1[kP1Ring];
     RecDen rd[2];
-    RecN rn[2];
+    RecN rn[kRnRing];
     RecOut ro[2];
+    float nzSum[2], alfa[2];        /* S -> N1: in-order sum of rn[f].noise; N1 -> G1: alfaGF of frame f; both by frame parity */
 };
+/* The helper wave reads its four sources with one ds_read_b128 per quad; lanes of different chains share a lane group
+ * ({ssq, den} in two of the four groups, {dif, noise} in the other two; past term 68 the sums read szero), so two sources that sit a
+ * multiple of 256 B apart would cost an LDS cycle more per quad (both are 16-byte aligned: equal slot or disjoint banks).  That is the
+ * bank rule of ds_read_b128 applied to this layout, NOT a measurement: no layout that breaks one of these conditions was run.  What was
+ * measured is this layout's SQ_LDS_BANK_CONFLICT as a whole (profiles/ns6_noise_sum_in_helper.txt). */
+constexpr bool lds_slots_differ(size_t a, size_t b) { return (a % 256) != (b % 256); }
+#define NS6_OFF(m) offsetof(Pipe6Lds, m)
+static_assert(lds_slots_differ(NS6_OFF(ssq), NS6_OFF(rd[0].den)) && lds_slots_differ(NS6_OFF(ssq), NS6_OFF(rd[1].den)), "ssq | den");
+static_assert(lds_slots_differ(NS6_OFF(sdif), NS6_OFF(rn[0].noise)) && lds_slots_differ(NS6_OFF(sdif), NS6_OFF(rn[1].noise)) &&
+              lds_slots_differ(NS6_OFF(sdif), NS6_OFF(rn[2].noise)) && lds_slots_differ(NS6_OFF(sdif), NS6_OFF(rn[3].noise)), "sdif | noise");
+/* DIFG1: dif = ro[fo & 1].out with fo = i - 9, noise = rn[(i - 6) & 3]: opposite parities */
+static_assert(lds_slots_differ(NS6_OFF(ro[0].out), NS6_OFF(rn[1].noise)) && lds_slots_differ(NS6_OFF(ro[0].out), NS6_OFF(rn[3].noise)) &&
+              lds_slots_differ(NS6_OFF(ro[1].out), NS6_OFF(rn[0].noise)) && lds_slots_differ(NS6_OFF(ro[1].out), NS6_OFF(rn[2].noise)), "ro | noise");
+static_assert(lds_slots_differ(NS6_OFF(ssq[68]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ssq[72]), NS6_OFF(szero)) &&
+              lds_slots_differ(NS6_OFF(ssq[76]), NS6_OFF(szero)), "ssq tail | szero");
+static_assert(lds_slots_differ(NS6_OFF(sdif[68]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(sdif[72]), NS6_OFF(szero)) &&
+              lds_slots_differ(NS6_OFF(sdif[76]), NS6_OFF(szero)), "sdif tail | szero");
+static_assert(lds_slots_differ(NS6_OFF(ro[0].out[68]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[0].out[72]), NS6_OFF(szero)) &&
+              lds_slots_differ(NS6_OFF(ro[0].out[76]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[1].out[68]), NS6_OFF(szero)) &&
+              lds_slots_differ(NS6_OFF(ro[1].out[72]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[1].out[76]), NS6_OFF(szero)), "ro tail | szero");
+#undef NS6_OFF
+static_assert(sizeof(Pipe6Lds) == 24624, "the figure in the comment at kP1Ring");
 
-__device__ __forceinline__ int window_base(int tick) { return ((tick - 3) & (kSlots - 1)) * kSlotLen; }
+/* SLOTS: kSlots for the stage-0 buffer, kSlots1 for the stage-1 buffer */
+template <int SLOTS>
+__device__ __forceinline__ int window_base(int tick) { return ((tick - 3) & (SLOTS - 1)) * kSlotLen; }
 
+template <int SLOTS>
 __device__ __forceinline__ void slot_store(float *circ, int tick, int lane, float a, float b)
 {
-    const int slot = tick & (kSlots - 1);
+    const int slot = tick & (SLOTS - 1);
     float *p = circ + slot * kSlotLen + 2 * lane;
     *reinterpret_cast<float2 *>(p) = make_float2(a, b);
-    if (slot < 3) *reinterpret_cast<float2 *>(p + kCirc) = make_float2(a, b);
+    if (slot < 3) *reinterpret_cast<float2 *>(p + SLOTS * kSlotLen) = make_float2(a, b);
 }
 
 __device__ __forceinline__ void block_sync()
@@ -201,7 +257,11 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         }
     };
 
-    for (int i = threadIdx.x; i < 2 * (kCirc + kMirror); i += 64 * kWaves) (&L.circ[0][0])[i] = 0.0f;
+    { /* both buffers, the first members of the record, cleared in one loop */
+        static_assert(offsetof(Pipe6Lds, circ0) == 0 && offsetof(Pipe6Lds, circ1) == sizeof(float) * (kCirc + kMirror), "circ0 | circ1 lead the record");
+        float *z = reinterpret_cast<float *>(&L);
+        for (int i = threadIdx.x; i < kCirc + kCirc1 + 2 * kMirror; i += 64 * kWaves) z[i] = 0.0f;
+    }
     for (int i = threadIdx.x; i < SEA_NMEL * 16; i += 64 * kWaves) L.idctT[i] = a.tables->idct[i >> 4][i & 15];
     if (threadIdx.x < 4) L.szero[threadIdx.x] = 0.0f;
     if (threadIdx.x < kSlots) {
@@ -212,6 +272,11 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
     if (threadIdx.x < 2) {
         const int k = threadIdx.x;
         L.rd[k].den[65] = L.rd[k].den[66] = L.rd[k].den[67] = 0.0f; /* read as zeros by S */
+        L.nzSum[k] = L.alfa[k] = 0.0f;
+    }
+    if (threadIdx.x < kRnRing) {
+        const int k = threadIdx.x;
+        L.rn[k].noise[65] = L.rn[k].noise[66] = L.rn[k].noise[67] = 0.0f; /* likewise */
     }
     if (threadIdx.x == 0) L.onset = kNoOnset;
     block_sync();
@@ -247,7 +312,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 if (i >= onset) {
                     tick = tick_of(i, onset);
                     const float x0 = (float)(short)(w & 0xFFFFu), x1 = (float)(short)(w >> 16);
-                    if (lane < 40) slot_store(L.circ[0], tick, lane, x0, x1);
+                    if (lane < 40) slot_store<kSlots>(L.circ0, tick, lane, x0, x1);
                     actA = tick >= 3; /* NoiseSup.c:1152 */
                 }
             }
@@ -257,7 +322,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             if (actA || actB) {
                 wave_sync();
                 float e[8];
-                ns_window8(L.circ[0] + window_base(tick), actA, L.circ[1] + window_base(t1), actB, win8, lane, e);
+                ns_window8(L.circ0 + window_base<kSlots>(tick), actA, L.circ1 + window_base<kSlots1>(t1), actB, win8, lane, e);
                 rfft256_dual_lo<false>(e, L.work[i & 1], fft);
             }
             NS6_T_MID;
@@ -315,11 +380,11 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
                  * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
                 float y01[2] = {0.0f, 0.0f};
-                ns_back<0, true, FD, true>(r.psd, L.circ[0] + window_base(t), L.back[0], s, C, nullptr, lane,
+                ns_back<0, true, FD, true>(r.psd, L.circ0 + window_base<kSlots>(t), L.back[0], s, C, nullptr, lane,
                                      (LIGHT ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)], o.den, L.idctT, &fd, &bits, nullptr,
                                      y01);
                 if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
-                if (lane < 40) slot_store(L.circ[1], t, lane, y01[0], y01[1]);
+                if (lane < 40) slot_store<kSlots1>(L.circ1, t, lane, y01[0], y01[1]);
             }
             NS6_T_MID;
             block_sync();
@@ -327,7 +392,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         }
         NS6_T_FLUSH(role, niter);
     } else if (role == 3) {
-        /* ---- N1: stage-1 noise tracking, noise-spectrum sum, gain-factor scalars ---- */
+        /* ---- N1: stage-1 noise tracking of frame i-5; gain-factor scalars of frame i-7, whose noise sum S took in between ---- */
         const float eps = a.tables->eps;
         NsRegs s;
         regs_init(s, eps);
@@ -336,17 +401,23 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_BEGIN;
             prio_by_remaining(i);
             onset_poll(onset, &L.onset);
-            const int f = i - 5;
-            if (tick_ge(f, 5, onset, nfr)) {
-                const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place one beat later (kP1Ring) */
-                RecN &o = L.rn[f & 1];
-                const int t = tick_of(f, onset);
+            const int f = i - 5, fg = i - 7;
+            if (tick_ge(fg, 5, onset, nfr)) {
+                const int t = tick_of(fg, onset);
                 /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
                 s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
                 s.denEn1 = L.denSum[(t - 1) & (kSlots - 1)];
                 s.denEn2 = L.denSum[t & (kSlots - 1)];
-                const float alfa = ns_noise1(r.psd, o.P, o.noise, s, eps, lane);
-                if (lane == 0) o.alfa = alfa;
+                const int nbNow = s.nbFrame[1]; /* has counted the frames tracked since; this frame's count is t - 4 */
+                s.nbFrame[1] = t - 4;
+                gain_fact_update(s, L.nzSum[fg & 1]);
+                s.nbFrame[1] = nbNow;
+                if (lane == 0) L.alfa[fg & 1] = s.alfaGF;
+            }
+            if (tick_ge(f, 5, onset, nfr)) {
+                const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place three beats later (kP1Ring) */
+                RecN &o = L.rn[f & (kRnRing - 1)];
+                ns_noise1(r.psd, o.P, o.noise, s, eps, lane);
             }
             NS6_T_MID;
             block_sync();
@@ -365,16 +436,17 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_BEGIN;
             prio_by_remaining(i);
             onset_poll(onset, &L.onset);
-            const int f = i - 6;
+            const int f = i - 8;
             if (tick_ge(f, 5, onset, nfr)) {
                 const float *psd = L.p1[f & (kP1Ring - 1)].psd;
-                const RecN &r = L.rn[f & 1];
+                const RecN &r = L.rn[f & (kRnRing - 1)];
                 RecOut &o = L.ro[f & 1];
                 const int t = tick_of(f, onset);
+                const float alfa = L.alfa[f & 1];
                 if (DIFG1)
-                    ns_gain1_dif(psd, r.P, r.noise, r.alfa, L.circ[1] + window_base(t), L.back[1], s, C, o.out, lane, L.idctT, lastIn);
+                    ns_gain1_dif(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT, lastIn);
                 else
-                    ns_gain1(psd, r.P, r.noise, r.alfa, L.circ[1] + window_base(t), L.back[1], s, C, o.out, lane, L.idctT);
+                    ns_gain1(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT);
             }
             NS6_T_MID;
             block_sync();
@@ -394,15 +466,18 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             onset_poll(onset, &L.onset);
             /* (1) VAD log-energy (NoiseSup.c:386-391) of the frame pushed at i-1 = tick tp ("current frame" of
              *     tick tp+2); (2) in-order sum of denSigSE1 of the frame B0 finished at i-1; (3) DC-offset
-             *     filter, int16 cast, store of the frame G1 finished at i-1 */
-            const int fp = i - 1, fd = i - 3, fo = i - kDepth;
-            const bool doVad = tick_ge(fp, 1, onset, nfr), doDen = tick_ge(fd, 3, onset, nfr), produced = tick_ge(fo, 5, onset, nfr);
+             *     filter, int16 cast, store of the frame G1 finished at i-1; (4) in-order sum of the noise
+             *     spectrum N1 left at i-1 */
+            const int fp = i - 1, fd = i - 3, fn = i - 6, fo = i - kDepth;
+            const bool doVad = tick_ge(fp, 1, onset, nfr), doDen = tick_ge(fd, 3, onset, nfr), doNz = tick_ge(fn, 5, onset, nfr),
+                       produced = tick_ge(fo, 5, onset, nfr);
             const int tp = tick_of(fp, onset), td = tick_of(fd, onset);
             const float *denSrc = L.rd[(fd >= 0 && fd < nfr) ? (fd & 1) : 0].den;
+            const float *nzSrc = L.rn[fn & (kRnRing - 1)].noise;
             const bool haveOut = fo >= 0 && fo < nfr;
             float2 vOut = make_float2(0.0f, 0.0f);
             if (doVad) {
-                const float *frame = L.circ[0] + (tp & (kSlots - 1)) * kSlotLen;
+                const float *frame = L.circ0 + (tp & (kSlots - 1)) * kSlotLen;
                 const float x = frame[lane];
                 L.ssq[lane] = x * x;
                 if (lane < 16) {
@@ -418,15 +493,17 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 if (lane < 16) L.sdif[64 + lane] = y2[64 + lane] - y2[63 + lane];
                 dcX = y2[79];
             }
-            if (doVad || doDen || produced) {
+            if (doVad || doDen || doNz || produced) {
                 wave_sync();
-                float vadSum, denTotal, y = dcY;
-                helper_chains<kSChunks>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane);
+                float vadSum, denTotal, nzTotal, y = dcY;
+                helper_chains<kSChunks, false, true>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane, nullptr, nullptr,
+                                                     nullptr, nzSrc, &nzTotal);
                 if (doVad) {
                     const float en = LIGHT ? vadSum : vad_frame_energy(vadSum); /* LIGHT: FA takes the log one beat later */
                     if (lane == 0) L.frameEn[(tp + 2) & (kSlots - 1)] = en;
                 }
                 if (doDen && lane == 0) L.denSum[td & (kSlots - 1)] = denTotal;
+                if (doNz && lane == 0) L.nzSum[fn & 1] = nzTotal;
                 if (produced) {
                     vOut = dc_verify_take(difS, L.sout, dcY, y, lane); /* check + output in one batch of reads */
                     dcY = y;
@@ -466,7 +543,7 @@ __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
     __shared__ p6::Pipe6Lds L;
     p6::ns_pipe6_body<false, true, true>(a, L);
 }
-/* The same body compiled for SEVEN waves per SIMD (69 VGPRs, four SGPRs spilled, no scratch): the form for three or four utterances per CU
+/* The same body compiled for SEVEN waves per SIMD (70 VGPRs, ten SGPRs spilled to lanes, no scratch): the form for three or four utterances per CU
  * (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
  * dispatcher, which deals the six waves of a workgroup 2 / 2 / 1 / 1 over the SIMDs, does not find room for the fourth: it
  * waited for one of the first three to end (configs[1]: 3.20 ms, which rounds 1-3 read as "the six-wave form loses at four

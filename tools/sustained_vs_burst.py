@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """tools/sustained_vs_burst.py -- (GPU box) the dense six-wave NoiseSup form on 1024 EQUAL utterances (four per CU, in lock step) of
-300 / 3000 / 12000 frames: ns per frame beat as a function of how long the launch lasts."""
+300 / 3000 / 12000 frames: ns per frame beat (a launch is nfr + 9 beats, kDepth of ns_pipe6_kernel.hip) as a function of how long the
+launch lasts."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.getcwd())
@@ -21,6 +22,6 @@ for nfr in (300, 3000, 12000):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / 3
-    print(os.environ.get("SEA_NS_KERNEL", "auto"), nfr, "frames x 1024:", round(ms, 3), "ms,", round(ms * 1e6 / (nfr + 7), 1), "ns per beat,",
+    print(os.environ.get("SEA_NS_KERNEL", "auto"), nfr, "frames x 1024:", round(ms, 3), "ms,", round(ms * 1e6 / (nfr + 9), 1), "ns per beat,",
           round(1024 * nfr / ms / 1e3, 1), "M frames/s")
     del batch, out
