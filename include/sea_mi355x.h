@@ -94,7 +94,9 @@ int sea_rfft_batch(float *d_x, int n, int m, long long nframes, void *stream);
 int sea_compceps_frames(const float *d_data201, float *d_coef14, long long nframes, void *stream);
 /* CompCeps straight from the float NoiseSup stream of sea_ns_denoise_batch.  d_ceps_cum holds
  * n_utt+1 prefix sums of per-utterance capacities (>= lengths/80 - 6 each); cepstral frame j of
- * utterance u lands at d_ceps[(d_ceps_cum[u] + j) * 14]; d_n_ceps[u] receives the valid count. */
+ * utterance u lands at d_ceps[(d_ceps_cum[u] + j) * 14]; d_n_ceps[u] receives the valid count and the rows behind
+ * it up to the capacity are zeroed.  An utterance whose capacity is 0 owns no tile: its count is NOT written (zero-fill
+ * d_n_ceps, as the Python layer does). */
 int sea_compceps_batch(const float *d_den_f32, const long long *d_offsets, const long long *d_lengths,
                        const int *d_first_out, const long long *d_ceps_cum, long long total_frames,
                        float *d_ceps, int *d_n_ceps, int n_utt, void *stream);

@@ -150,15 +150,17 @@ def test_afe_feature_chain_1024_utterances(shard, oracle):
     ref(utts[0][:1600])
     with ThreadPoolExecutor(_threads()) as ex:
         want = list(ex.map(ref, utts))
-    worst, frames, speech = 0.0, 0, 0
+    worst, frames, speech, nbits = 0.0, 0, 0, 0
     for u, (g, w) in enumerate(zip(res["feats"], want)):
         assert g.shape == w.shape, f"utt {u}: {g.shape} vs {w.shape}"
         assert np.array_equal(g[:, 14], w[:, 14]), f"utt {u}: VAD decisions differ"
         worst = max(worst, float(np.abs(g[:, :14] - w[:, :14]).max()))
+        nbits += int(np.count_nonzero(np.ascontiguousarray(g[:, :14]).view(np.uint32) != np.ascontiguousarray(w[:, :14]).view(np.uint32)))
         frames += len(g)
         speech += int(g[:, 14].sum())
-    print(f"AFE chain: {frames} feature frames, {speech} flagged speech, worst |delta| = {worst}")
+    print(f"AFE chain: {frames} feature frames, {speech} flagged speech, worst |delta| = {worst}, {nbits} words differ in bits")
     assert worst <= 1e-3
+    assert nbits == 0, f"{nbits} of {14 * frames} feature words differ in bits from the oracle"
     assert 0 < speech < frames
 
 

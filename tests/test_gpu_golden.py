@@ -22,6 +22,13 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NAMES = ("plain_1s", "leading_zeros", "ragged", "loud", "gap", "kat_head")
 
 
+def _bits_differ(got, want):
+    """how many float32 words of two arrays of one shape differ in bits"""
+    got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
+    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
+    return int(np.count_nonzero(got.view(np.uint32) != want.view(np.uint32)))
+
+
 def _torch():
     import torch
     if not torch.cuda.is_available():
@@ -71,7 +78,9 @@ def test_golden_noisesup_batch_int16_float_stream_and_cepstra():
         d = float(np.abs(cepsh[cum[u]:cum[u] + len(wantc)] - wantc).max())
         worst = max(worst, d)
         assert d <= 1e-3, f"{name}: cepstra off by {d}"
-    print("golden cepstra worst |delta| =", worst)
+        nb = _bits_differ(cepsh[cum[u]:cum[u] + len(wantc)], wantc)
+        assert nb == 0, f"{name}: {nb} of {wantc.size} cepstral words differ in bits from the reference's"
+    print("golden cepstra worst |delta| =", worst, "-- 0 words differ in bits")
 
 
 def test_golden_rfft():
@@ -117,10 +126,12 @@ def test_golden_compceps_frames():
     g = np.load(os.path.join(GOLD, "compceps_golden.npz"))
     got = sea.compceps_frames(torch.from_numpy(g["data201"]).cuda()).cpu().numpy()
     d = float(np.abs(got - g["coef"]).max())
-    print("golden DoCompCeps worst |delta| =", d)
+    print("golden DoCompCeps worst |delta| =", d, "--", _bits_differ(got, g["coef"]), "of", got.size, "words differ in bits")
     assert d <= 1e-3
+    assert _bits_differ(got, g["coef"]) == 0
     one = sea.DoCompCeps(g["data201"][3])                # the plug-in slot's host form
     assert float(np.abs(one - g["coef"][3]).max()) <= 1e-3
+    assert _bits_differ(one, g["coef"][3]) == 0
 
 
 def test_golden_afe_feature_chain():
@@ -153,10 +164,14 @@ def test_golden_afe_feature_chain():
             d = float(np.abs(gg[c0:c0 + len(ww)] - ww).max()) if len(ww) else 0.0
             worst = max(worst, d)
             assert d <= 1e-3, f"{name} {what}: off by {d}"
+            nb = _bits_differ(gg[c0:c0 + len(ww)], ww)
+            assert nb == 0, f"{name} {what}: {nb} of {ww.size} words differ in bits from the reference's"
         got15 = res["feats"][u]
         assert got15.shape == w15.shape, f"{name}: {got15.shape} emitted frames, the reference has {w15.shape}"
         assert np.array_equal(got15[:, 14], w15[:, 14]), f"{name}: VAD decisions differ"
         d = float(np.abs(got15[:, :14] - w15[:, :14]).max())
         worst = max(worst, d)
         assert d <= 1e-3, f"{name}: emitted features off by {d}"
-    print("golden AFE chain worst |delta| =", worst)
+        nb = _bits_differ(got15[:, :14], w15[:, :14])
+        assert nb == 0, f"{name}: {nb} of {w15[:, :14].size} emitted feature words differ in bits from the reference's"
+    print("golden AFE chain worst |delta| =", worst, "-- 0 words differ in bits")

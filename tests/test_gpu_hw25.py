@@ -28,11 +28,9 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-@pytest.fixture(scope="module")
-def case():
-    """the batch and, computed once, what every utterance must give"""
-    import torch
-    import speech_enhancement_amd as sea
+def seven_inputs():
+    """the seven utterances of the batch, what each must give (the fixture's arrays or the model's) and the tables; also the
+    building blocks of tests/test_gpu_launch_caps.py"""
     g = M.load_golden()
     t = M.tables()
     rng = np.random.default_rng(25)
@@ -49,6 +47,15 @@ def case():
             utts.append(extra[u])
             want.append(M.frontend(extra[u], t))
     assert [len(x) for x in utts] == [1210, 1210, 1210, 79, 80, 163, 647]
+    return utts, want, t
+
+
+@pytest.fixture(scope="module")
+def case():
+    """the batch and, computed once, what every utterance must give"""
+    import torch
+    import speech_enhancement_amd as sea
+    utts, want, t = seven_inputs()
     batch = sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32)
     rows = np.array([len(x) // 80 for x in utts], np.int64)
     offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)

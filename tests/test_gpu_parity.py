@@ -45,6 +45,13 @@ def _assert_int16_close(got, want, what):
     assert not np.any(got[:lead]), f"{what}: output before the reference's first output frame"
 
 
+def _bits_differ(got, want):
+    """how many float32 words of two arrays of one shape differ in bits"""
+    got, want = np.ascontiguousarray(got, dtype=np.float32), np.ascontiguousarray(want, dtype=np.float32)
+    assert got.shape == want.shape, f"shape {got.shape} vs {want.shape}"
+    return int(np.count_nonzero(got.view(np.uint32) != want.view(np.uint32)))
+
+
 def _mixed_corpus():
     """Seeded utterances covering the edge cases: leading zeros (every 5th), ragged lengths (not a
     multiple of 80), shorter than one frame, empty, all-zero, loud (clipping-range) input."""
@@ -193,7 +200,7 @@ def test_compceps_vs_oracle(oracle):
     ceps, cum, n_ceps = sea.compceps_batch(batch, f32, first)
     torch.cuda.synchronize()
     ceps, n_ceps = ceps.cpu().numpy(), n_ceps.cpu().numpy()
-    worst = 0.0
+    worst, nbits, nwords = 0.0, 0, 0
     for u, x in enumerate(utts):
         tr = oracle.ns_trace(x, want_state=False)
         assert int(n_ceps[u]) == tr["nceps"], f"utt {u}: {n_ceps[u]} cepstral frames vs {tr['nceps']}"
@@ -202,16 +209,21 @@ def test_compceps_vs_oracle(oracle):
             d = np.abs(got - tr["ceps"]).max()
             worst = max(worst, float(d))
             assert d <= 1e-3, f"utt {u}: cepstra off by {d}"
-    print("CompCeps worst |delta| =", worst)
+            nbits += _bits_differ(got, tr["ceps"])
+            nwords += got.size
+    print(f"CompCeps worst |delta| = {worst}, {nbits} of {nwords} words differ in bits")
+    assert nbits == 0, f"{nbits} of {nwords} cepstral words differ in bits from the oracle"
     # DoCompCeps-shaped single-frame call, on an arbitrary frame (not from NoiseSup)
     rng = np.random.default_rng(2)
     data = (rng.standard_normal(201) * 500).astype(np.float32)
     got = sea.DoCompCeps(data)
     want = oracle.compceps_frame(data)
     assert np.abs(got - want).max() <= 1e-3
+    assert _bits_differ(got, want) == 0
     # silent frame hits both floors (e^-50 and e^-10)
     z = np.zeros(201, np.float32)
     assert np.abs(sea.DoCompCeps(z) - oracle.compceps_frame(z)).max() <= 1e-3
+    assert _bits_differ(sea.DoCompCeps(z), oracle.compceps_frame(z)) == 0
 
 
 def test_compceps_frames_amplitudes_and_ragged_tiles(oracle):
@@ -831,7 +843,7 @@ def test_afe_feature_chain_vs_oracle(oracle):
     flags = res["flags"].cpu().numpy()
     fcc, fpp = res["feat_cc"].cpu().numpy(), res["feat_pp"].cpu().numpy()
     n_ceps, first = res["n_ceps"].cpu().numpy(), res["first_out"].cpu().numpy()
-    worst = 0.0
+    worst, nbits, nwords = 0.0, 0, 0
     for u, x in enumerate(utts):
         tr = oracle.afe_trace(x)
         assert int(n_ceps[u]) == tr["nceps"], f"utt {u}"
@@ -848,6 +860,8 @@ def test_afe_feature_chain_vs_oracle(oracle):
                 d = float(np.abs(g[c0:c0 + tr["nceps"]] - w).max())
                 worst = max(worst, d)
                 assert d <= 1e-3, f"utt {u} {name}: off by {d}"
+                nbits += _bits_differ(g[c0:c0 + tr["nceps"]], w)
+                nwords += w.size
         got15 = res["feats"][u]
         assert got15.shape == tr["vad_out"].shape, f"utt {u}: {got15.shape} vs {tr['vad_out'].shape}"
         if len(got15):
@@ -855,7 +869,10 @@ def test_afe_feature_chain_vs_oracle(oracle):
             d = float(np.abs(got15[:, :14] - tr["vad_out"][:, :14]).max())
             worst = max(worst, d)
             assert d <= 1e-3, f"utt {u} emitted features: off by {d}"
-    print("AFE chain worst |delta| =", worst)
+            nbits += _bits_differ(got15[:, :14], tr["vad_out"][:, :14])
+            nwords += got15[:, :14].size
+    print(f"AFE chain worst |delta| = {worst}, {nbits} of {nwords} words differ in bits")
+    assert nbits == 0, f"{nbits} of {nwords} feature words differ in bits from the oracle"
     # the audio is the same as the plain NoiseSup kernel's
     plain, _, _ = sea.ns_denoise_batch(batch)
     assert _torch().equal(plain, res["out"])

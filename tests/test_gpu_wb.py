@@ -92,6 +92,7 @@ class _Stats:
         assert self.i16_diff <= 1e-3 * max(self.i16_n, 1), f"{self.i16_diff} of {self.i16_n} int16 samples differ"
         for k, (m, n, nb) in self.f.items():
             assert m <= (1e-3 if k == "ceps" else 1e-4), f"{k}: max error {m}"
+            assert nb == 0, f"{k}: {nb} of {n} values differ in bits"
 
 
 def _compare(st, got, want, nfr, what, f32=True):

@@ -93,6 +93,7 @@ class _Stats:
     def check(self):
         for k, (m, n, nb) in self.f.items():
             assert m <= 1e-3, f"{k}: max |delta| {m}"
+            assert nb == 0, f"{k}: {nb} of {n} values differ in bits"
 
 
 def _compare(st, got, want, nfr, what):
