@@ -490,8 +490,8 @@ int sea_trainset_last_chunks(void);
  * HuWang.cpp:41-76) on its 25-channel 8 kHz gammatone bank: AudiPeriph (gammatone + Meddis hair cell, hOut in float), lowPass
  * (hEv), computeACF, crossCorr, globalPitch, timeCrn (corrHc) and the initial labelling of Grp (csrc/hw25_kernel.hip,
  * DESIGN.md section 5.11).  Parity: bit for bit against the reference's own functions compiled on a CPU
- * (tests/golden/hw25_golden.npz).  The back half (initGroup, pitchDtm, computeAM, finalSeg) is not built; it consumes exactly
- * these arrays.
+ * (tests/golden/hw25_golden.npz).  initGroup and pitchDtm follow below (sea_hw25_pitch_*); computeAM, finalSeg and resynthesis
+ * are not built.
  * Samples are floats on the int16 scale, as createIBM takes them.  Batch forms (device pointers): d_in_f32 holds the packed
  * batch, utterance u at d_offsets[u] (multiples of 8; the stretch up to the next multiple of 8 past its length must be
  * readable); d_hout / d_hev hold 25x the packed size, utterance u's [25][pitch] block at d_offsets[u] * 25, pitch =
@@ -518,6 +518,48 @@ int sea_hw25_frontend_batch(const float *d_in_f32, float *d_hout, float *d_hev, 
                             const int *d_order, int n_utt, void *stream);
 int sea_hw25_frontend(const float *in, long L, float *hout, float *hev, float *acf_hc, float *acf_ev, float *cross_hc,
                       float *cross_ev, int *pitch, float *pratio, float *mark);
+/* createIBM():79-87 on the same bank: initGroup (HuWang.cpp:639-702, with segmentation / search / relationship:466-637) and
+ * pitchDtm (:795-824: findPitch, sumAuto, pitchCrn, checkPitch, leftDevelope, rightDevelope, linearEstimate, timeCrn, reGroup,
+ * relationship2) -- the pitch contour of the dominant voiced source and the units grouped with it (csrc/hw25_pitch_kernel.hip,
+ * DESIGN.md section 5.12).  Parity: bit for bit, every stage, against the reference's own functions compiled on a CPU
+ * (tests/golden/hw25_pitch_golden.npz).
+ * Inputs are rows as sea_hw25_correlogram_batch writes them and are not modified: d_acf_hc [rows][25][101], d_cross_hc,
+ * d_pratio_in, d_mark_in [rows][25]; utterance u has lengths[u] / 80 rows from d_row_offsets[u].  (d_cross_hc is read because
+ * the reference's leftDevelope / rightDevelope count `number2` over forty channels on this bank of 25: channels 25..39 of a
+ * frame are, by the layout of its arrays, the frame's cross and pRatio and the next frame's acf and marks.  That is
+ * reproduced, see below for the last frame.)  Outputs: d_pitch [rows] ints, Pitch after linearEstimate (0 = unvoiced, else
+ * 16..100); d_grp [rows][25] floats in {-1, 0, +1}, Grp after reGroup (THETAT); d_pratio [rows][25], pRatio after the last
+ * timeCrn (finalSeg reads it); d_status [n_utt] ints, bits 0..15 the segment count, flags above.  d_stages (optional, null:
+ * not written): utterance u's block of SEA_HW25_STAGE_WORDS words per row starts at word d_row_offsets[u] *
+ * SEA_HW25_STAGE_WORDS: [5][rows_u] ints, Pitch after findPitch #1, findPitch #2, checkPitch, leftDevelope, rightDevelope; then
+ * [2][rows_u][25] floats, Grp after initGroup and after reGroup (THETAP).  d_scratch must hold sea_hw25_pitch_scratch_bytes
+ * (total_rows, n_utt) bytes, total_rows being the extent of the row space (the largest d_row_offsets[u] + rows_u); d_order as
+ * elsewhere.  The lengths stay on the device, nothing synchronises with the host, every launch is on `stream`.
+ * No output buffer may overlap an input or another output (the inputs are read after the first outputs are written); equal
+ * pointers are rejected.
+ * Where the reference is undefined, this is defined:
+ *  - no segment (always so with fewer than 3 rows): relationship writes Seg[0] of an empty array.  Here: segment count 0,
+ *    pitch, grp, pratio (and the stages) all 0;
+ *  - more than 400 segments: segMark[MAX_NUMBER_SEGMENT] overflows.  Here: SEA_HW25_TOO_MANY_SEGMENTS is set, bits 0..15 hold
+ *    the count (at most 65535), pitch, grp, pratio (and the stages) all 0;
+ *  - leftDevelope / rightDevelope read chan_mark uninitialised on their first step when the neighbouring frame has no pitch
+ *    (no streak of three consistent frames).  Here chan_mark starts at zeros, and SEA_HW25_CHANMARK_UNSET is set when it was
+ *    read before it was computed;
+ *  - on the LAST frame of an utterance the fifteen channels 25..39 of `number2` lie past the reference's arrays.  Here they
+ *    are not counted.
+ * sea_hw25_pitch: one utterance from host memory; runs the front half itself with the ACF in a device buffer of its own;
+ * pitch [L / 80], grp and pratio [L / 80][25], status [1]; pitch, grp and pratio may be null. */
+enum {
+    SEA_HW25_MAX_SEGMENTS = 400, /* MAX_NUMBER_SEGMENT */
+    SEA_HW25_STAGE_WORDS = 55,   /* per row: 5 ints and 2 x 25 floats */
+    SEA_HW25_TOO_MANY_SEGMENTS = 1 << 16,
+    SEA_HW25_CHANMARK_UNSET = 1 << 17
+};
+long long sea_hw25_pitch_scratch_bytes(long long total_rows, int n_utt);
+int sea_hw25_pitch_batch(const float *d_acf_hc, const float *d_cross_hc, const float *d_pratio_in, const float *d_mark_in,
+                         const long long *d_lengths, const long long *d_row_offsets, int *d_pitch, float *d_grp, float *d_pratio,
+                         int *d_status, void *d_stages, void *d_scratch, const int *d_order, int n_utt, void *stream);
+int sea_hw25_pitch(const float *x, long L, int *pitch, float *grp, float *pratio, int *status);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

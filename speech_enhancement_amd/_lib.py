@@ -92,6 +92,9 @@ PROTOTYPES = {
     "sea_hw25_correlogram_batch": (_i, [_vp] * 14 + [_i, _vp]),
     "sea_hw25_frontend_batch": (_i, [_vp] * 15 + [_i, _vp]),
     "sea_hw25_frontend": (_i, [_vp, _l] + [_vp] * 9),
+    "sea_hw25_pitch_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw25_pitch_batch": (_i, [_vp] * 13 + [_i, _vp]),
+    "sea_hw25_pitch": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

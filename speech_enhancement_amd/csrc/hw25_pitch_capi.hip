@@ -1,0 +1,127 @@
+/*
+ * hw25_pitch_capi.hip -- the C ABI of the Hu-Wang estimator's initial grouping and pitch tracking (hw25_pitch_kernel.hip):
+ * sea_hw25_pitch_scratch_bytes, sea_hw25_pitch_batch, sea_hw25_pitch.  The batch call is eight launches on one stream and
+ * nothing else: the lengths stay on the device.
+ */
+#include <initializer_list>
+
+#include "capi_internal.h"
+
+using namespace sea_capi;
+
+/* the scratch: segse [n_utt][2][400] ints first (its size needs n_utt alone), then SEA_HW25_SCRATCH_WORDS words per row;
+ * utterance u's block starts at its first row, so the batch call needs no row total */
+static long long segse_words(int n_utt) { return (long long)(n_utt > 0 ? n_utt : 0) * 2 * SEA_HW25_MAX_SEGMENTS; }
+
+long long sea_hw25_pitch_scratch_bytes(long long total_rows, int n_utt)
+{
+    return 4 * (segse_words(n_utt) + (total_rows > 0 ? total_rows : 0) * SEA_HW25_SCRATCH_WORDS);
+}
+
+static int pitch_launch(sea::Hw25PitchArgs a, int n_utt, hipStream_t stream)
+{
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    /* the frame kernels: a fixed number of waves per utterance walks its frames, about eight waves per CU over the batch
+     * (the utterances go on grid x) */
+    int waves = (8 * c->n_cu + n_utt - 1) / n_utt;
+    waves = waves < 1 ? 1 : (waves > 1024 ? 1024 : waves);
+    const dim3 per_frame(n_utt, waves), per_utt(n_utt), block(64);
+    hipLaunchKernelGGL(sea::hw25_pitch_max_kernel, per_frame, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sea::hw25_pitch_segment_kernel, per_utt, block, 0, stream, a); /* initGroup */
+    HIP_TRY(hipGetLastError());
+    a.mode = SEA_HW25_FRAME_FIND | SEA_HW25_FRAME_TIMECRN; /* findPitch, timeCrn */
+    a.stage = 0;
+    hipLaunchKernelGGL(sea::hw25_pitch_frame_kernel, per_frame, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    a.theta = 0.95f; /* reGroup (THETAP): the double constant converted to the float parameter */
+    a.stage = 1;
+    hipLaunchKernelGGL(sea::hw25_pitch_regroup_kernel, per_utt, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    a.mode = SEA_HW25_FRAME_FIND; /* findPitch */
+    hipLaunchKernelGGL(sea::hw25_pitch_frame_kernel, per_frame, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(sea::hw25_pitch_track_kernel, per_utt, block, 0, stream, a); /* checkPitch .. linearEstimate */
+    HIP_TRY(hipGetLastError());
+    a.mode = SEA_HW25_FRAME_TIMECRN; /* timeCrn */
+    hipLaunchKernelGGL(sea::hw25_pitch_frame_kernel, per_frame, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    a.theta = 0.85f; /* reGroup (THETAT) */
+    a.stage = -1;
+    hipLaunchKernelGGL(sea::hw25_pitch_regroup_kernel, per_utt, block, 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_hw25_pitch_batch(const float *d_acf_hc, const float *d_cross_hc, const float *d_pratio_in, const float *d_mark_in,
+                         const long long *d_lengths, const long long *d_row_offsets, int *d_pitch, float *d_grp, float *d_pratio,
+                         int *d_status, void *d_stages, void *d_scratch, const int *d_order, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_acf_hc || !d_cross_hc || !d_pratio_in || !d_mark_in || !d_lengths || !d_row_offsets || !d_pitch || !d_grp ||
+        !d_pratio || !d_status || !d_scratch)
+        return fail("hw25_pitch: null pointer (only d_stages and d_order may be null)");
+    /* the kernels read the inputs after they have begun to write the outputs: no output may be an input */
+    for (const float *out : {(const float *)d_grp, (const float *)d_pratio})
+        for (const float *in : {d_acf_hc, d_cross_hc, d_pratio_in, d_mark_in})
+            if (out == in) return fail("hw25_pitch: an output (d_grp, d_pratio) must not be one of the inputs");
+    if (d_grp == d_pratio) return fail("hw25_pitch: d_grp and d_pratio must be different buffers");
+    sea::Hw25PitchArgs a{};
+    a.acf = d_acf_hc;
+    a.cross = d_cross_hc;
+    a.pratio_in = d_pratio_in;
+    a.mark_in = d_mark_in;
+    a.lengths = d_lengths;
+    a.row_offsets = d_row_offsets;
+    a.pitch = d_pitch;
+    a.grp = d_grp;
+    a.pratio = d_pratio;
+    a.status = d_status;
+    a.stages = static_cast<int *>(d_stages);
+    a.segse = static_cast<int *>(d_scratch);
+    a.rowscr = a.segse + segse_words(n_utt);
+    a.order = d_order;
+    a.n_utt = n_utt;
+    return pitch_launch(a, n_utt, (hipStream_t)stream);
+}
+
+int sea_hw25_pitch(const float *x, long L, int *pitch, float *grp, float *pratio, int *status)
+{
+    if (L <= 0) return fail("hw25_pitch: L=%ld", L);
+    if (!x || !status) return fail("hw25_pitch: null pointer");
+    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
+    const size_t fr = (size_t)rows * SEA_HW25_NCHAN;
+    DevBuf<float> din, dho, dhe, dah, dfr;
+    DevBuf<int> dp, dint;
+    DevBuf<long long> dmeta;
+    DevBuf<char> dscr;
+    HIP_TRY(din.alloc((size_t)Lp));
+    HIP_TRY(dho.alloc((size_t)Lp * SEA_HW25_NCHAN));
+    HIP_TRY(dhe.alloc((size_t)Lp * SEA_HW25_NCHAN));
+    HIP_TRY(dah.alloc(fr * SEA_HW25_DELAYS));
+    HIP_TRY(dfr.alloc(fr * 6)); /* cross_hc | cross_ev | pratio_in | mark | grp | pratio */
+    HIP_TRY(dp.alloc((size_t)rows));
+    HIP_TRY(dint.alloc((size_t)rows + 1)); /* pitch | status */
+    HIP_TRY(dmeta.alloc(3));
+    HIP_TRY(dscr.alloc((size_t)sea_hw25_pitch_scratch_bytes(rows, 1)));
+    const long long meta[3] = {0, L, 0};
+    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
+    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
+    if (sea_hw25_frontend_batch(din.p, dho.p, dhe.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dah.p, nullptr, dfr.p, dfr.p + fr, dp.p,
+                                dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
+        return 1;
+    if (sea_hw25_pitch_batch(dah.p, dfr.p, dfr.p + 2 * fr, dfr.p + 3 * fr, dmeta.p + 1, dmeta.p + 2, dint.p, dfr.p + 4 * fr,
+                             dfr.p + 5 * fr, dint.p + rows, nullptr, dscr.p, nullptr, 1, nullptr))
+        return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(status, dint.p + rows, sizeof(int), hipMemcpyDeviceToHost));
+    if (F > 0) {
+        const size_t nf = (size_t)F * SEA_HW25_NCHAN * sizeof(float);
+        if (pitch) HIP_TRY(hipMemcpy(pitch, dint.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+        if (grp) HIP_TRY(hipMemcpy(grp, dfr.p + 4 * fr, nf, hipMemcpyDeviceToHost));
+        if (pratio) HIP_TRY(hipMemcpy(pratio, dfr.p + 5 * fr, nf, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}

@@ -354,6 +354,35 @@ __global__ void hw25_periphery_kernel(Hw25Args a);   /* grid n_utt x 64 threads 
 __global__ void hw25_lowpass_kernel(Hw25Args a);     /* grid (n_utt, 25) x 256 */
 __global__ void hw25_correlogram_kernel(Hw25Args a); /* grid (n_utt, G) x 256: workgroup (u, g) takes frames g, g + G, ... */
 
+/* The Hu-Wang estimator's initial grouping and pitch tracking (hw25_pitch_kernel.hip).  Rows as Hw25Args has them: acf
+ * [rows][25][101], cross, pratio_in, mark_in [rows][25] are the front half's and only read; pitch [rows], grp and pratio
+ * [rows][25], status [n_utt] are written.  stages (or null): utterance u's block of SEA_HW25_STAGE_WORDS words per row at
+ * row_offsets[u] * SEA_HW25_STAGE_WORDS, [5][F] ints then [2][F][25] floats.  Scratch: rowscr, utterance u's block of
+ * SEA_HW25_SCRATCH_WORDS words per row at row_offsets[u] * SEA_HW25_SCRATCH_WORDS; segse [n_utt][2][400] ints. */
+struct Hw25PitchArgs {
+    const float *acf, *cross, *pratio_in, *mark_in;
+    const long long *lengths;
+    const long long *row_offsets;
+    int *pitch;
+    float *grp, *pratio;
+    int *status;
+    int *stages;
+    int *rowscr, *segse;
+    const int *order;
+    int n_utt;
+    int mode;    /* frame kernel: SEA_HW25_FRAME_FIND | SEA_HW25_FRAME_TIMECRN */
+    int stage;   /* the stage slot the launch fills (frame kernel: Pitch 0 / 1; regroup kernel: Grp 1, or -1 for none) */
+    float theta; /* regroup kernel */
+};
+#define SEA_HW25_SCRATCH_WORDS 76 /* per row: lab, key, mraw [25] and buf */
+#define SEA_HW25_FRAME_FIND 1
+#define SEA_HW25_FRAME_TIMECRN 2
+__global__ void hw25_pitch_max_kernel(Hw25PitchArgs a);     /* grid (n_utt, G) x 64: wave (u, g) takes frames g, g + G, ... */
+__global__ void hw25_pitch_segment_kernel(Hw25PitchArgs a); /* grid n_utt x 64 */
+__global__ void hw25_pitch_frame_kernel(Hw25PitchArgs a);   /* grid (n_utt, G) x 64 */
+__global__ void hw25_pitch_regroup_kernel(Hw25PitchArgs a); /* grid n_utt x 64 */
+__global__ void hw25_pitch_track_kernel(Hw25PitchArgs a);   /* grid n_utt x 64 */
+
 __global__ void subband_kernel(SubbandArgs a);
 __global__ void ns_denoise_pipe_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_big_kernel(NsBatchArgs a); /* lower-register form for > 4 utterances per CU */

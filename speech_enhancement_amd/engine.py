@@ -1083,6 +1083,76 @@ def hw25_frontend(x, want_acf=True):
 
 
 # ------------------------------------------------------------------------------------------------
+# the Hu-Wang estimator's initial grouping and pitch tracking (HuWang.cpp:79-87: initGroup, pitchDtm; csrc/hw25_pitch_kernel.hip)
+# ------------------------------------------------------------------------------------------------
+HW25_STAGE_WORDS, HW25_TOO_MANY_SEGMENTS, HW25_CHANMARK_UNSET = 55, 1 << 16, 1 << 17
+HW25_PITCH_STAGES = ("pitch_find1", "pitch_find2", "pitch_check", "pitch_left", "pitch_right")
+HW25_GRP_STAGES = ("grp_init", "grp_thetap")
+
+
+class Hw25PitchResult:
+    """What hw25_pitch_batch() computed, device tensors: pitch int32 [rows] (0 = unvoiced, else the delay 16..100 in samples
+    at 8 kHz), grp [rows][25] in {-1, 0, +1} (+1: grouped with the dominant voiced source), pratio [rows][25], status int32
+    [n_utt] (bits 0..15 the segment count, HW25_TOO_MANY_SEGMENTS, HW25_CHANMARK_UNSET), stages (int32 words, or None) and
+    front, the Hw25Result they were computed from.  utterance(u) returns numpy arrays of one utterance, the stage arrays
+    under HW25_PITCH_STAGES / HW25_GRP_STAGES when they were asked for."""
+
+    def __init__(self, front, **kw):
+        self.front = front
+        self.__dict__.update(kw)
+
+    def utterance(self, u):
+        r0, n = int(self.front.host_row_offsets[u]), int(self.front.host_rows[u])
+        out = dict(pitch=self.pitch[r0:r0 + n].cpu().numpy(), grp=self.grp[r0:r0 + n].cpu().numpy(),
+                   pratio=self.pratio[r0:r0 + n].cpu().numpy(), status=int(self.status[u]))
+        if self.stages is not None:
+            block = self.stages[r0 * HW25_STAGE_WORDS:(r0 + n) * HW25_STAGE_WORDS].cpu().numpy()
+            for k, name in enumerate(HW25_PITCH_STAGES):
+                out[name] = block[k * n:(k + 1) * n].copy()
+            grp = block[5 * n:].view(np.float32).reshape(2, n, HW25_NCHAN)
+            for k, name in enumerate(HW25_GRP_STAGES):
+                out[name] = grp[k].copy()
+        return out
+
+
+def hw25_pitch_batch(batch, stages=False, use_order=True):
+    """createIBM():41-87 for every utterance of the batch: the front half with its ACF output, then initGroup and pitchDtm, one
+    launch group on the current stream -> Hw25PitchResult.  stages: also keep Pitch / Grp after every step of pitchDtm."""
+    torch = _torch()
+    lib = _lib.load()
+    front = hw25_frontend_batch(batch, want_acf=True, use_order=use_order)
+    dev = front.pitch.device
+    n = front.pitch.shape[0]
+    pitch = torch.zeros(n, dtype=torch.int32, device=dev)
+    grp = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
+    pratio = torch.zeros_like(grp)
+    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
+    st = torch.zeros(n * HW25_STAGE_WORDS, dtype=torch.int32, device=dev) if stages else None
+    nbytes = int(lib.sea_hw25_pitch_scratch_bytes(n, int(batch.n_utt)))
+    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+    rc = lib.sea_hw25_pitch_batch(_dptr(front.acf_hc), _dptr(front.cross_hc), _dptr(front.pratio), _dptr(front.mark),
+                                  _dptr(batch.lengths), _dptr(front.row_offsets), _dptr(pitch), _dptr(grp), _dptr(pratio),
+                                  _dptr(status), _dptr(st), _dptr(scratch), _dptr(batch.order) if use_order else None,
+                                  batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_pitch_batch")
+    return Hw25PitchResult(front, pitch=pitch, grp=grp, pratio=pratio, status=status, stages=st)
+
+
+def hw25_pitch(x):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict: pitch int32 [F], grp and pratio
+    [F][25], status."""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    F = x.size // HW25_HOP
+    r = dict(pitch=np.zeros(F, np.int32), grp=np.zeros((F, HW25_NCHAN), np.float32), pratio=np.zeros((F, HW25_NCHAN), np.float32))
+    status = np.zeros(1, np.int32)
+    rc = lib.sea_hw25_pitch(_np_ptr(x), x.size, _np_ptr(r["pitch"]), _np_ptr(r["grp"]), _np_ptr(r["pratio"]), _np_ptr(status))
+    _lib.check(rc, "sea_hw25_pitch")
+    r["status"] = int(status[0])
+    return r
+
+
+# ------------------------------------------------------------------------------------------------
 # the training-set builder (enhancement_extract_subband_linux/cpp/main.cpp:91-274): mix at an SNR, subbands, IRM target
 # ------------------------------------------------------------------------------------------------
 def snr_lin(db):

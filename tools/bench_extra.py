@@ -12,6 +12,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what cepsslices --steps 7  # NoiseSup + the plain CompCeps in time slices and from host buffers, both rates, opt-in
     python tools/bench_extra.py --what trainset --steps 7  # the training-set builder: mix, subbands, IRM, pipeline and host entry point, opt-in
     python tools/bench_extra.py --what hw25 --steps 5  # the Hu-Wang front half on the 25-channel bank: periphery, correlogram, launch group, opt-in
+    python tools/bench_extra.py --what hw25pitch --steps 3  # its initial grouping and pitch tracking beside the correlogram, opt-in
 """
 import argparse
 import json
@@ -1108,6 +1109,62 @@ def main():
                 line["samples_per_sec"] = samples / (med / 1e3)
             print(json.dumps(line), flush=True)
         del hout, hev, acf_hc, acf_ev
+
+    if "hw25pitch" in what:
+        # The Hu-Wang estimator's initial grouping and pitch tracking (initGroup, pitchDtm) on the --utts corpus batch taken as
+        # float samples, beside the front half that feeds it, in one process: the front half with the corrHc ACF output, the
+        # correlogram alone with that output, and sea_hw25_pitch_batch without and with the stage block.  Device events around
+        # every step, one warm-up discarded, median.
+        lib = sea.load()
+        n = batch.n_utt
+        x = batch.data.to(torch.float32)
+        rows = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames = int(rows.sum())
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev = z(batch.total * 25), z(batch.total * 25)
+        cross_hc, cross_ev, pratio_in, mark, gpitch = z((frames, 25)), z((frames, 25)), z((frames, 25)), z((frames, 25)), z(frames, torch.int32)
+        acf_hc = z((frames, 25, 101))
+        pitch, grp, pratio, status = z(frames, torch.int32), z((frames, 25)), z((frames, 25)), z(n, torch.int32)
+        stages = z(frames * 55, torch.int32)
+        scratch = torch.empty(int(lib.sea_hw25_pitch_scratch_bytes(frames, n)), dtype=torch.uint8, device=dev)
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def front():
+            assert lib.sea_hw25_frontend_batch(P(x), P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(acf_hc), None, P(cross_hc),
+                                               P(cross_ev), P(gpitch), P(pratio_in), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def correlogram():
+            assert lib.sea_hw25_correlogram_batch(P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(acf_hc), None, P(cross_hc),
+                                                  P(cross_ev), P(gpitch), P(pratio_in), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def stage(with_stages=False):
+            assert lib.sea_hw25_pitch_batch(P(acf_hc), P(cross_hc), P(pratio_in), P(mark), P(batch.lengths), P(d_offs), P(pitch), P(grp), P(pratio),
+                                            P(status), P(stages) if with_stages else None, P(scratch), P(batch.order), n, st) == 0, lib.sea_last_error()
+        samples = int(np.sum(batch.host_lengths))
+        workload = f"the {args.utts}-utterance corpus as 8 kHz float samples: {samples} samples, {frames} frames of 80; median of {args.steps} steps after one warm-up"
+        results = []
+        for name, fn, kernels in (("front half with the corrHc ACF output", front, "sea::hw25_periphery_kernel + sea::hw25_lowpass_kernel + sea::hw25_correlogram_kernel"),
+                                  ("correlogram with the corrHc ACF output", correlogram, "sea::hw25_correlogram_kernel"),
+                                  ("initial grouping and pitch tracking", stage,
+                                   "sea::hw25_pitch_max_kernel + _segment_kernel + _frame_kernel x3 + _regroup_kernel x2 + _track_kernel"),
+                                  ("initial grouping and pitch tracking with the stage block", lambda: stage(True), "the same")):
+            med, t = median_ms(fn, args.steps)
+            results.append(med)
+            print(json.dumps({"metric": f"Hu-Wang estimator, 25-channel 8 kHz bank: {name} (frames of 80 samples/sec); a first form, not tuned",
+                              "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
+                              "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}), flush=True)
+        s_host = status.cpu().numpy()
+        p_host = pitch.cpu().numpy()
+        print(json.dumps({"metric": "Hu-Wang estimator: initial grouping and pitch tracking relative to the correlogram of the same run",
+                          "value": results[2] / results[1], "unit": "ratio", "config": {"workload": workload},
+                          "segments_per_utterance": {"min": int((s_host & 0xFFFF).min()), "median": float(np.median(s_host & 0xFFFF)),
+                                                     "max": int((s_host & 0xFFFF).max())},
+                          "utterances_flagged": {"too_many_segments": int((s_host >> 16 & 1).sum()), "chanmark_unset": int((s_host >> 17 & 1).sum())},
+                          "voiced_frames": int((p_host > 0).sum())}), flush=True)
+        del hout, hev, acf_hc, stages, scratch
 
     if "rfft" in what:
         n = 1 << 18
