@@ -1,0 +1,116 @@
+/*
+ * ns6_beat_plan.h -- which beats of a six-wave NoiseSup role need no frame bookkeeping (ns_pipe6_kernel.hip).
+ *
+ * Every role of the six-wave form runs niter = nfr + kDepth beats; at beat i it handles a few frames i - d, and what it does with
+ * each hangs on one flag, "frame i - d exists and has tick >= k":
+ *
+ *      flag(i; d, k)  =  i - d < nfr  &&  i - d - (k - 1) >= onset          (tick_ge of the kernel; onset = first non-zero frame)
+ *
+ * which is true exactly for  onset + d + k - 1 <= i < nfr + d.  The flags of a role are therefore ALL true on one interval of beats,
+ * from the largest lower end to the smallest upper end: the role's steady range.  Inside it the kernel runs a copy of the role's beat
+ * in which every flag is the literal `true`; before and after it the general copy, which evaluates them.  This header holds the table
+ * of (d, k) per role and the two ends of the range; the kernel's flags are checked against the table at compile time (beat_flag
+ * there), tests/test_ns6_beat_plan_cpu.py sweeps the ends on the host.
+ *
+ * Plain C++: no HIP types, includable from a host program.
+ */
+#ifndef SEA_NS6_BEAT_PLAN_H
+#define SEA_NS6_BEAT_PLAN_H
+
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define SEA_NS6_HD __host__ __device__
+#else
+#define SEA_NS6_HD
+#endif
+
+namespace sea {
+namespace ns6plan {
+
+constexpr int kNoOnset = 0x7fffffff; /* the gate never opened (or: not yet seen) */
+constexpr int kDepth = 9;            /* a role runs nfr + kDepth beats; S stores frame i - kDepth */
+
+enum Role { FA = 0, FB = 1, B0 = 2, N1 = 3, G1 = 4, S = 5, kRoles = 6 };
+
+/* the compile-time variants of the body: a flag of the table belongs to all of them (kAlways) or to those with one of these */
+constexpr unsigned kAlways = 0u, kFd = 1u, kLight = 2u, kDifg1 = 4u;
+/* the three kernels */
+constexpr unsigned kVariantPlain = kLight | kDifg1, kVariantDense = 0u, kVariantFd = kFd | kLight | kDifg1;
+
+struct Flag {
+    int d;         /* the flag is about frame i - d ... */
+    int k;         /* ... having tick >= k */
+    unsigned when; /* kAlways, or the variant bit that adds it */
+};
+constexpr int kMaxFlags = 5;
+struct RolePlan {
+    int n;
+    Flag f[kMaxFlags];
+    int ahead;  /* frames BEYOND frame i that a steady beat touches: FA prefetches frame i + 1, so i + 1 < nfr must hold */
+    int settle; /* beats the general copy must have run with all flags true before the steady copy may take over: S notes the
+                 * index of its first output frame (firstOut) at the first beat whose `produced` is true, the steady copy does not */
+};
+
+constexpr RolePlan kPlan[kRoles] = {
+    /* FA: frame i itself enters stage 0 from tick 3; stage 1 of frame i-3 from tick 5; LIGHT: the VAD log-energy of frame i-2 */
+    {3, {{0, 3, kAlways}, {3, 5, kAlways}, {2, 1, kLight}, {0, 0, 0}, {0, 0, 0}}, 1, 0},
+    /* FB: one beat behind FA on both transforms */
+    {2, {{1, 3, kAlways}, {4, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* B0: stage-0 back half of frame i-2 */
+    {1, {{2, 3, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* N1: noise tracking of frame i-5, gain-factor scalars of frame i-7 */
+    {2, {{5, 5, kAlways}, {7, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* G1: gains of frame i-8 */
+    {1, {{8, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* S: VAD sum of frame i-1, denSigSE1 sum of i-3, noise sum of i-6, output of i-9; FD: the speech flags of frame i-9 */
+    {5, {{1, 1, kAlways}, {3, 3, kAlways}, {6, 5, kAlways}, {kDepth, 5, kAlways}, {kDepth, 5, kFd}}, 0, 1},
+};
+
+SEA_NS6_HD constexpr bool flag_applies(const Flag &f, unsigned variant) { return f.when == kAlways || (f.when & variant) != 0u; }
+
+/* (d, k) is a flag of the role in that variant: what the kernel asserts of every flag it evaluates */
+SEA_NS6_HD constexpr bool has_flag(unsigned variant, int role, int d, int k)
+{
+    for (int j = 0; j < kPlan[role].n; ++j)
+        if (kPlan[role].f[j].d == d && kPlan[role].f[j].k == k && flag_applies(kPlan[role].f[j], variant)) return true;
+    return false;
+}
+
+/* beats after the onset from which all flags hold: max over the flags of d + k - 1, plus the settle beats */
+SEA_NS6_HD constexpr int steady_lead(unsigned variant, int role)
+{
+    int lead = 0;
+    for (int j = 0; j < kPlan[role].n; ++j) {
+        const Flag &f = kPlan[role].f[j];
+        if (flag_applies(f, variant) && f.d + f.k - 1 > lead) lead = f.d + f.k - 1;
+    }
+    return lead + kPlan[role].settle;
+}
+/* beats past nfr at which the first flag falls: min over the flags of d, less the frames a steady beat touches ahead (may be < 0) */
+SEA_NS6_HD constexpr int steady_tail(unsigned variant, int role)
+{
+    int tail = kDepth;
+    for (int j = 0; j < kPlan[role].n; ++j) {
+        const Flag &f = kPlan[role].f[j];
+        if (flag_applies(f, variant) && f.d < tail) tail = f.d;
+    }
+    return tail - kPlan[role].ahead;
+}
+
+/* first beat at which every flag of the role is true; kNoOnset while there is no onset (no beat is >= it: frame counts stay below) */
+SEA_NS6_HD constexpr int steady_begin(unsigned variant, int role, int onset)
+{
+    return onset == kNoOnset ? kNoOnset : onset + steady_lead(variant, role);
+}
+/* first beat from steady_begin on at which one of them is false again (never above nfr + kDepth - 1; the range is empty when this
+ * is not above steady_begin) */
+SEA_NS6_HD constexpr int steady_end(unsigned variant, int role, int nfr)
+{
+    const int e = nfr + steady_tail(variant, role);
+    return e > 0 ? e : 0;
+}
+
+} // namespace ns6plan
+} // namespace sea
+
+#undef SEA_NS6_HD
+#endif

@@ -24,6 +24,11 @@
  * before; the lifetimes and ring depths are derived beside kP1Ring below.  configs[1]: 1.84 -> 1.76 ms = 465 M frames/s
  * (profiles/ns6_noise_sum_in_helper.txt).
  *
+ * Round 7: every role's beat exists in a general copy, which derives the frame's flags, and a steady copy without them for the beats on
+ * which all are true (run_beats below, ns6_beat_plan.h); the dense and the _fd kernel take it, the plain kernel lost with it and stays on
+ * the general copy (template parameter STEADY_LOOP).  configs[1]: 1.76 -> 1.71 ms = 479 M frames/s, 489 -> 356 scalar instructions per
+ * frame (profiles/ns6_steady_loop.txt).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -41,6 +46,7 @@
  * (profiles/r05_ns6_bookkeeping.txt).
  */
 #include "ns_core.h"
+#include "ns6_beat_plan.h"
 
 namespace sea {
 
@@ -76,7 +82,7 @@ constexpr int kCirc = kSlots * kSlotLen;
 constexpr int kCirc1 = kSlots1 * kSlotLen;
 constexpr int kMirror = 3 * kSlotLen;
 constexpr int kWaves = 6;
-constexpr int kDepth = 9; /* S stores frame i - kDepth */
+constexpr int kDepth = ns6plan::kDepth; /* 9: S stores frame i - kDepth */
 constexpr int kSChunks = 10; /* helper_chains: the helper wave's 20 quads are requested in ten chunks (2 x 8 VGPRs in flight) */
 /* issue priority by remaining frames: evaluated every kPrioStep frames, kPrioLevels levels dithered into the four hardware ones
  * (the rule and its measurements: ns_pipe_kernel.hip) */
@@ -98,7 +104,7 @@ constexpr int kDefaultPerm = 0014352;
  * iteration i has passed the barriers of iterations 0 .. i-1, so it sees FA's write of every iteration g <= i-1.  Reading kNoOnset at
  * beat i therefore means onset >= i > f: the frame is before the onset, i.e. invalid -- exactly what f >= onset gives with
  * kNoOnset = INT_MAX.  (FA's write of iteration i itself may or may not be seen; both readings give the same flags for f < i.) */
-constexpr int kNoOnset = 0x7fffffff;
+constexpr int kNoOnset = ns6plan::kNoOnset; /* 0x7fffffff */
 constexpr long long kMaxFrames = 0x7fffffffLL - 16; /* frame indices, iteration counts and ticks stay below kNoOnset */
 __device__ __forceinline__ void onset_poll(int &onset, const int *word)
 {
@@ -109,6 +115,55 @@ __device__ __forceinline__ void onset_poll(int &onset, const int *word)
 __device__ __forceinline__ int tick_of(int f, int onset) { return (int)((unsigned)f - (unsigned)onset + 1u); }
 /* frame f exists and has tick >= k (k >= 1; f may be negative: onset >= 0) */
 __device__ __forceinline__ bool tick_ge(int f, int k, int onset, int nfr) { return f < nfr && f - (k - 1) >= onset; }
+
+/* Round 7: one general and one steady copy of every role's beat.  Once the onset is known and the pipeline is full, every flag a role
+ * derives from (f, onset, nfr) is true until the utterance runs out (ns6_beat_plan.h: all of them hold exactly on the beats
+ * steady_begin <= i < steady_end).  A role's beat is ONE body, a lambda taking the compile-time STEADY; with STEADY every flag is the
+ * literal `true` (beat_flag), the onset is not polled, and what only the fill and the drain need (FA's gate, S's firstOut and its
+ * zero-filled output frames) folds away.  Ticks, ring slots and the arithmetic are the same expressions in both copies.
+ *
+ * run_beats is the loop of every role.  Invariants:
+ *   Barriers.  Each call of beat(.., i), general or steady, executes exactly one block_sync(), and i goes up by one after each call
+ *     and by nothing else: the inner loop runs beat<true>(i) for i .. e-1 and leaves i = e, the statement after it runs
+ *     beat<false>(i) and ++i only while i < niter.  i starts at 0 and the outer loop ends at i == niter, so every wave executes exactly
+ *     niter barriers whatever its role, its variant and its switch points are; roles switch at different beats, which no barrier sees.
+ *   The switch is decided in the general loop only, once per beat: `onset` is the role's own register copy, which only the general
+ *     copy updates (onset_poll, FA's gate), so "not yet" may still be read for "invalid" exactly as before (comment at kNoOnset), and
+ *     steady_begin(kNoOnset) = kNoOnset is above every beat.
+ *   After the steady loop i = min(steady_end, niter) and control is back in the same general copy for the drain; the test is then true
+ *     again on every drain beat and the inner loop runs zero times (e <= i).
+ *   Frames after the onset: the flags hold for EVERY frame onset <= f < nfr, zero or not (the gate has one degree of freedom), so the
+ *     steady copy never looks at the samples' being zero.
+ *   FA: steady_end(FA) = nfr - 1 (RolePlan::ahead), so a steady beat's prefetch of frame i + 1 stays inside the utterance -- for the
+ *     last utterance of the batch that is the end of the packed buffer.
+ *   S: steady_begin(S) = onset + 14 (RolePlan::settle): the first produced frame is onset + 4 at beat onset + 13, in the general
+ *     copy, which sets firstOut; the steady copy never touches it. */
+template <bool B>
+struct BoolC {
+    static constexpr bool value = B;
+};
+/* the flag "frame i - D exists and has tick >= K" of role ROLE; it must be in the role's beat plan, from which the steady range follows */
+template <unsigned VARIANT, int ROLE, int D, int K, bool STEADY>
+__device__ __forceinline__ bool beat_flag(int i, int onset, int nfr)
+{
+    static_assert(ns6plan::has_flag(VARIANT, ROLE, D, K), "a flag the beat plan of ns6_beat_plan.h does not know");
+    return STEADY || tick_ge(i - D, K, onset, nfr);
+}
+template <bool STEADY_LOOP, unsigned VARIANT, int ROLE, class Beat>
+__device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, Beat &&beat)
+{
+    int i = 0;
+    while (i < niter) {
+        if (STEADY_LOOP && i >= ns6plan::steady_begin(VARIANT, ROLE, onset)) {
+            const int e0 = ns6plan::steady_end(VARIANT, ROLE, nfr), e = e0 < niter ? e0 : niter;
+            for (; i < e; ++i) beat(BoolC<true>{}, i);
+        }
+        if (i < niter) {
+            beat(BoolC<false>{}, i);
+            ++i;
+        }
+    }
+}
 
 /* The second-stage schedule and its ring depths.  Everything written at iteration w is visible from iteration w+1 on (the frame
  * barrier); a slot may be written again at the iteration of its last read at the earliest when writer and reader touch different
@@ -216,9 +271,11 @@ __device__ __forceinline__ void load_back_const(NsConst &C, const sea_ns_tables 
     C.eps = t->eps;
 }
 
-template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands over the DC differences */>
+template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands over the DC differences */,
+          bool STEADY_LOOP /* the flag-free copy of every role's beat on its steady range (run_beats) */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 {
+    constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u);
     const int lane = threadIdx.x & 63;
     /* LIGHT / DIFG1 (the forms for up to two utterances per CU, where the run time is one utterance's chain of frames): the helper
      * wave S was this form's longest role (3397 clk per frame alone, B0 3089, G1 2985, N1 2623, FB 2608, FA 2268): (LIGHT) the VAD's
@@ -292,33 +349,37 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
         uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
         int onset = kNoOnset; /* index of the first non-zero frame */
-        for (int i = 0; i < niter; ++i) {
+        auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            if (LIGHT && tick_ge(i - 2, 1, onset, nfr)) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is its tick + 2's "current frame") */
-                const int e = (tick_of(i - 2, onset) + 2) & (kSlots - 1);
-                const float en = vad_frame_energy(L.frameEn[e]);
-                if (lane == 0) L.frameEnLog[e] = en;
+            if constexpr (LIGHT) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is its tick + 2's "current frame") */
+                if (beat_flag<V, ns6plan::FA, 2, 1, STEADY>(i, onset, nfr)) {
+                    const int e = (tick_of(i - 2, onset) + 2) & (kSlots - 1);
+                    const float en = vad_frame_energy(L.frameEn[e]);
+                    if (lane == 0) L.frameEnLog[e] = en;
+                }
             }
             int tick = 0; /* frames seen since (and including) the first non-zero one */
             bool actA = false;
-            if (i < nfr) {
+            if (STEADY || i < nfr) {
                 const uint32_t w = nextw;
-                if (i + 1 < nfr && lane < 40) nextw = (in32 + (long long)(i + 1) * 40)[lane];
-                if (onset == kNoOnset && __ballot(w != 0u) != 0ull) {
+                if ((STEADY || i + 1 < nfr) && lane < 40) nextw = (in32 + (long long)(i + 1) * 40)[lane];
+                if (!STEADY && onset == kNoOnset && __ballot(w != 0u) != 0ull) {
                     onset = i;
                     if (lane == 0) __hip_atomic_store(&L.onset, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
-                if (i >= onset) {
+                if (STEADY || i >= onset) {
                     tick = tick_of(i, onset);
                     const float x0 = (float)(short)(w & 0xFFFFu), x1 = (float)(short)(w >> 16);
                     if (lane < 40) slot_store<kSlots>(L.circ0, tick, lane, x0, x1);
-                    actA = tick >= 3; /* NoiseSup.c:1152 */
+                    static_assert(ns6plan::has_flag(V, ns6plan::FA, 0, 3), "frame i exists here: its flag is the tick alone");
+                    actA = STEADY || tick >= 3; /* NoiseSup.c:1152 */
                 }
             }
             /* stage 1, frame i-3 (B0 finished it at the previous iteration): NoiseSup.c:1178 <=> tick >= 5 */
             const int t1 = tick_of(i - 3, onset);
-            const bool actB = tick_ge(i - 3, 5, onset, nfr);
+            const bool actB = beat_flag<V, ns6plan::FA, 3, 5, STEADY>(i, onset, nfr);
             if (actA || actB) {
                 wave_sync();
                 float e[8];
@@ -328,7 +389,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_MID;
             block_sync();
             NS6_T_END;
-        }
+        };
+        run_beats<STEADY_LOOP, V, ns6plan::FA>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
         if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset == kNoOnset ? nfr : onset;
     } else if (role == 1) {
@@ -336,15 +398,16 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         Fft2Regs fft;
         load_fft2_regs<false>(fft, &a.tables->fft, lane, nullptr);
         int onset = kNoOnset;
-        for (int i = 0; i < niter; ++i) {
+        auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            onset_poll(onset, &L.onset);
+            if (!STEADY) onset_poll(onset, &L.onset);
             const int g = i - 1; /* FA's iteration */
-            if (g >= 0) {
+            if (STEADY || g >= 0) {
                 const int f0 = g, f1 = g - 3;
-                const bool actA = tick_ge(f0, 3, onset, nfr);
-                const bool actB = tick_ge(f1, 5, onset, nfr);
+                const bool actA = beat_flag<V, ns6plan::FB, 1, 3, STEADY>(i, onset, nfr);
+                const bool actB = beat_flag<V, ns6plan::FB, 4, 5, STEADY>(i, onset, nfr);
                 float *work = L.work[g & 1];
                 if (actA || actB) {
                     float o[8]; /* the last level stays in registers and feeds both PSDs (ns_core.h, psd_from_last_level) */
@@ -356,7 +419,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_MID;
             block_sync();
             NS6_T_END;
-        }
+        };
+        run_beats<STEADY_LOOP, V, ns6plan::FB>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else if (role == 2) {
         /* ---- B0: BACK of stage 0; its 80 outputs enter the stage-1 buffer ---- */
@@ -367,12 +431,13 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         NsFd fd;
         fd_init(fd);
         int onset = kNoOnset;
-        for (int i = 0; i < niter; ++i) {
+        auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            onset_poll(onset, &L.onset);
+            if (!STEADY) onset_poll(onset, &L.onset);
             const int f = i - 2;
-            if (tick_ge(f, 3, onset, nfr)) {
+            if (beat_flag<V, ns6plan::B0, 2, 3, STEADY>(i, onset, nfr)) {
                 const RecPsd &r = L.p0[f & 1];
                 RecDen &o = L.rd[f & 1];
                 const int t = tick_of(f, onset);
@@ -389,7 +454,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_MID;
             block_sync();
             NS6_T_END;
-        }
+        };
+        run_beats<STEADY_LOOP, V, ns6plan::B0>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else if (role == 3) {
         /* ---- N1: stage-1 noise tracking of frame i-5; gain-factor scalars of frame i-7, whose noise sum S took in between ---- */
@@ -397,12 +463,13 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         NsRegs s;
         regs_init(s, eps);
         int onset = kNoOnset;
-        for (int i = 0; i < niter; ++i) {
+        auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            onset_poll(onset, &L.onset);
+            if (!STEADY) onset_poll(onset, &L.onset);
             const int f = i - 5, fg = i - 7;
-            if (tick_ge(fg, 5, onset, nfr)) {
+            if (beat_flag<V, ns6plan::N1, 7, 5, STEADY>(i, onset, nfr)) {
                 const int t = tick_of(fg, onset);
                 /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
                 s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
@@ -414,7 +481,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 s.nbFrame[1] = nbNow;
                 if (lane == 0) L.alfa[fg & 1] = s.alfaGF;
             }
-            if (tick_ge(f, 5, onset, nfr)) {
+            if (beat_flag<V, ns6plan::N1, 5, 5, STEADY>(i, onset, nfr)) {
                 const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place three beats later (kP1Ring) */
                 RecN &o = L.rn[f & (kRnRing - 1)];
                 ns_noise1(r.psd, o.P, o.noise, s, eps, lane);
@@ -422,7 +489,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_MID;
             block_sync();
             NS6_T_END;
-        }
+        };
+        run_beats<STEADY_LOOP, V, ns6plan::N1>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else if (role == 4) {
         /* ---- G1: stage-1 Wiener gains, mel, gain factorisation, IDCT, FIR ---- */
@@ -432,12 +500,13 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         regs_init(s, C.eps);
         float lastIn = 0.0f; /* LIGHT: y[79] of the previous filtered frame (prevSamples, NoiseSup.c:908) */
         int onset = kNoOnset;
-        for (int i = 0; i < niter; ++i) {
+        auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            onset_poll(onset, &L.onset);
+            if (!STEADY) onset_poll(onset, &L.onset);
             const int f = i - 8;
-            if (tick_ge(f, 5, onset, nfr)) {
+            if (beat_flag<V, ns6plan::G1, 8, 5, STEADY>(i, onset, nfr)) {
                 const float *psd = L.p1[f & (kP1Ring - 1)].psd;
                 const RecN &r = L.rn[f & (kRnRing - 1)];
                 RecOut &o = L.ro[f & 1];
@@ -451,7 +520,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_MID;
             block_sync();
             NS6_T_END;
-        }
+        };
+        run_beats<STEADY_LOOP, V, ns6plan::G1>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else {
         /* ---- S: the lane-grouped scalar chains (helper_chains) ---- */
@@ -460,21 +530,22 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         float dcX = 0.0f, dcY = 0.0f; /* prevSamples, NoiseSup.c:908-909 */
         int firstOut = -1;
         int onset = kNoOnset;
-        for (int i = 0; i < niter; ++i) {
+        auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
-            onset_poll(onset, &L.onset);
+            if (!STEADY) onset_poll(onset, &L.onset);
             /* (1) VAD log-energy (NoiseSup.c:386-391) of the frame pushed at i-1 = tick tp ("current frame" of
              *     tick tp+2); (2) in-order sum of denSigSE1 of the frame B0 finished at i-1; (3) DC-offset
              *     filter, int16 cast, store of the frame G1 finished at i-1; (4) in-order sum of the noise
              *     spectrum N1 left at i-1 */
             const int fp = i - 1, fd = i - 3, fn = i - 6, fo = i - kDepth;
-            const bool doVad = tick_ge(fp, 1, onset, nfr), doDen = tick_ge(fd, 3, onset, nfr), doNz = tick_ge(fn, 5, onset, nfr),
-                       produced = tick_ge(fo, 5, onset, nfr);
+            const bool doVad = beat_flag<V, ns6plan::S, 1, 1, STEADY>(i, onset, nfr), doDen = beat_flag<V, ns6plan::S, 3, 3, STEADY>(i, onset, nfr),
+                       doNz = beat_flag<V, ns6plan::S, 6, 5, STEADY>(i, onset, nfr), produced = beat_flag<V, ns6plan::S, kDepth, 5, STEADY>(i, onset, nfr);
             const int tp = tick_of(fp, onset), td = tick_of(fd, onset);
-            const float *denSrc = L.rd[(fd >= 0 && fd < nfr) ? (fd & 1) : 0].den;
+            const float *denSrc = L.rd[(STEADY || (fd >= 0 && fd < nfr)) ? (fd & 1) : 0].den;
             const float *nzSrc = L.rn[fn & (kRnRing - 1)].noise;
-            const bool haveOut = fo >= 0 && fo < nfr;
+            const bool haveOut = STEADY || (fo >= 0 && fo < nfr);
             float2 vOut = make_float2(0.0f, 0.0f);
             if (doVad) {
                 const float *frame = L.circ0 + (tp & (kSlots - 1)) * kSlotLen;
@@ -507,7 +578,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 if (produced) {
                     vOut = dc_verify_take(difS, L.sout, dcY, y, lane); /* check + output in one batch of reads */
                     dcY = y;
-                    if (firstOut < 0) firstOut = fo;
+                    if (!STEADY && firstOut < 0) firstOut = fo; /* set before S goes steady (RolePlan::settle) */
                 }
             }
             if (haveOut) {
@@ -519,14 +590,17 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                     }
                     (out32 + (long long)fo * 40)[lane] = packed;
                 }
-                if (FD && produced && lane == 0 && a.flags_out)
-                    a.flags_out[off / 8 + 10 * (long long)fo] = (unsigned char)L.fdFlags[tick_of(fo, onset) & (kSlots - 1)];
+                if constexpr (FD) { /* the speech flags B0 left for this frame seven beats ago: the plan's fifth flag of S */
+                    if (beat_flag<V, ns6plan::S, kDepth, 5, STEADY>(i, onset, nfr) && lane == 0 && a.flags_out)
+                        a.flags_out[off / 8 + 10 * (long long)fo] = (unsigned char)L.fdFlags[tick_of(fo, onset) & (kSlots - 1)];
+                }
                 wave_sync();
             }
             NS6_T_MID;
             block_sync();
             NS6_T_END;
-        }
+        };
+        run_beats<STEADY_LOOP, V, ns6plan::S>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
         if (a.first_out && lane == 0) a.first_out[u] = firstOut;
     }
@@ -537,13 +611,15 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 /* launched for at most two utterances per CU (capi.hip::ns_pick_form): twelve waves per CU, three per SIMD, so the
  * register allocation could use up to 168 VGPRs.  The plain form stays compiled for 80 (measured: 1644 against 1679 ns
  * per frame with the looser bound, which only changes the schedule); the _fd form takes the looser bound, which
- * removes its 7 spilled registers (91 VGPRs).  Today the plain form takes 68 VGPRs and the _fd form 80, nothing spilled. */
+ * removes its 7 spilled registers (91 VGPRs).  Today the plain form takes 68 VGPRs and the _fd form 82, nothing spilled.
+ * STEADY_LOOP: off here -- with the steady copies this form ran 2.1 % (256 utterances) and 2.6 % (768) slower, its period is B0's beat,
+ * the one role they did not shorten; on in the dense form (-2.9 %) and in the _fd form (-1.9 %).  profiles/ns6_steady_loop.txt */
 __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
-    p6::ns_pipe6_body<false, true, true>(a, L);
+    p6::ns_pipe6_body<false, true, true, false>(a, L);
 }
-/* The same body compiled for SEVEN waves per SIMD (70 VGPRs, ten SGPRs spilled to lanes, no scratch): the form for three or four utterances per CU
+/* The same body compiled for SEVEN waves per SIMD (71 VGPRs, thirty SGPRs spilled to lanes, no scratch): the form for three or four utterances per CU
  * (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
  * dispatcher, which deals the six waves of a workgroup 2 / 2 / 1 / 1 over the SIMDs, does not find room for the fourth: it
  * waited for one of the first three to end (configs[1]: 3.20 ms, which rounds 1-3 read as "the six-wave form loses at four
@@ -563,7 +639,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false>(a, L);
+    p6::ns_pipe6_body<false, false, false, true>(a, L);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
@@ -571,7 +647,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
 __global__ __launch_bounds__(384, 2) void ns_denoise_pipe6_fd_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
-    p6::ns_pipe6_body<true, true, true>(a, L);
+    p6::ns_pipe6_body<true, true, true, true>(a, L);
 }
 
 } // namespace sea

@@ -1,15 +1,19 @@
 #!/usr/bin/env python3
-"""tools/isa_loop_counts.py <file.s> <kernel-substring> -- static instruction counts per loop of one kernel
+"""tools/isa_loop_counts.py [--inner] <file.s> <kernel-substring> -- static instruction counts per loop of one kernel
 (VALU / SALU / LDS / VMEM / branch / waitcnt), from hipcc -S output.  Every basic block is attributed to the
 outermost loop named in its '; in Loop: Header=' comment; blocks outside any loop go to 'straight'.  Static
-counts: blocks under a rarely-taken branch (slow paths) count like any other."""
+counts: blocks under a rarely-taken branch (slow paths) count like any other.
+
+--inner: every block (labelled or '; %bb.N:') goes to the loop its own comment names, a loop header to itself, so a
+loop nested in another (the steady copy of a six-wave role inside its general loop) is counted apart from it."""
 import re
 import sys
 from collections import defaultdict, OrderedDict
 
 
 def main():
-    path, key = sys.argv[1], sys.argv[2]
+    inner = "--inner" in sys.argv
+    path, key = [a for a in sys.argv[1:] if a != "--inner"][:2]
     lines = open(path).read().splitlines()
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*" + re.escape(key) + r"\w*:", l))
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])
@@ -17,6 +21,17 @@ def main():
     counts = OrderedDict()
     depth_of = {}
     for l in lines[start:end + 1]:
+        if inner:
+            m = re.match(r"^(?:\.L(BB\d+_\d+)|; %bb\.\d+):(.*)", l)
+            if m:
+                h = re.search(r"in Loop: Header=(BB\d+_\d+)", m.group(2))
+                if h:
+                    cur = h.group(1)
+                elif m.group(1) and ("Loop Header" in m.group(2) or "Parent Loop" in m.group(2)):
+                    cur = m.group(1)
+                else:
+                    cur = "straight"
+                continue
         m = re.match(r"^(\.LBB\d+_\d+):(.*)", l)
         if m:
             label, rest = m.group(1), m.group(2)
