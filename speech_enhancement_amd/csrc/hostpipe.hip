@@ -24,9 +24,13 @@
  * feature chains (sea_features_utterances, sea_wb_features_utterances) ride the same slices: per slice the denoiser's slice call
  * and the cepstrum's or the chain's on the kernel stream, the float stream on the device sized for one slice.
  *
- * What the entry points share lives once: the cut along the time axis in slice_plan.h (also sea_packed_plan's), the
- * event-driven loop in run_pipeline, the NoiseSup launch over a slice in ns_launch_slice.  An entry point is its set-up and
- * three callables: issue (upload + launch), download, unpack.
+ * What the entry points share lives once: the cut along the time axis and the in-order placement of emitted rows in
+ * slice_plan.h (the cut is also sea_packed_plan's), the event-driven loop in run_pipeline, the NoiseSup launch over a slice in
+ * ns_launch_slice, and for the six calls over time slices everything but the kernels in run_slices: staging layout, packing,
+ * the three streams, upload / record / wait, the audio download, the unpacking tasks and the lifetime of what those tasks
+ * read.  Such an entry point is its argument checks, its "too small to cut" rule, its buffer sizes and three callables: launch,
+ * extra_download, unpack_piece.  The feature chains are features_slices<WB>, the cepstrum pipelines denoise_ceps_slices<WB>.
+ * The chunk pipelines (SEA_HOST_MODE=chunks, resynthesis) and sea_packed_denoise sit on run_pipeline / the events directly.
  * Staging, device buffers, streams and events are grow-only and belong to the calling host thread (the reference's
  * batch tool calls etsi_denoise from N threads); the packing threads are one pool per device.
  */
@@ -306,43 +310,31 @@ struct PipeWs {
     hipEvent_t ev_meta = nullptr, ev_done[kMaxChunks] = {}, ev_kernel[kMaxChunks] = {}, ev_h2d[kMaxChunks] = {};
     int device = -1;
     ~PipeWs() { release(); }
+    template <class... G>
+    static void release_all(G &...g) { (g.release(), ...); }
+    template <class F>
+    hipError_t each_event(F f) /* f on every event until one call fails */
+    {
+        hipError_t e = f(ev_meta);
+        for (hipEvent_t *evs : {ev_done, ev_kernel, ev_h2d})
+            for (int i = 0; i < kMaxChunks && e == hipSuccess; ++i) e = f(evs[i]);
+        return e;
+    }
     void release()
     {
         int cur = -1;
         const bool sw = device >= 0 && hipGetDevice(&cur) == hipSuccess && cur != device;
         if (sw) (void)hipSetDevice(device); /* the buffers belong to `device`, whatever the thread uses now */
-        in.release();
-        out.release();
-        mask.release();
-        meta.release();
-        f32.release();
-        ceps.release();
-        ints.release();
-        wb_rows.release();
-        inter.release();
-        state.release();
-        feat.release();
-        afe_state.release();
-        flag_rows.release();
-        fin.release();
+        release_all(in, out, mask, meta, f32, ceps, ints, wb_rows, inter, state, feat, afe_state, flag_rows, fin);
         for (auto &s : stream) {
             if (s) (void)hipStreamDestroy(s);
             s = nullptr;
         }
-        if (ev_meta) (void)hipEventDestroy(ev_meta);
-        ev_meta = nullptr;
-        for (auto &e : ev_done) {
+        (void)each_event([](hipEvent_t &e) {
             if (e) (void)hipEventDestroy(e);
             e = nullptr;
-        }
-        for (auto &e : ev_kernel) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        for (auto &e : ev_h2d) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
+            return hipSuccess;
+        });
         if (sw) (void)hipSetDevice(cur);
         device = -1;
     }
@@ -357,14 +349,7 @@ struct PipeWs {
         }
         for (int i = 0; i < kStreams; ++i)
             if (!stream[i] && (e = hipStreamCreateWithFlags(&stream[i], hipStreamNonBlocking)) != hipSuccess) return e;
-        if (!ev_meta && (e = hipEventCreateWithFlags(&ev_meta, hipEventDisableTiming)) != hipSuccess) return e;
-        for (auto &ev : ev_done)
-            if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-        for (auto &ev : ev_kernel)
-            if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-        for (auto &ev : ev_h2d)
-            if (!ev && (e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e;
-        return hipSuccess;
+        return each_event([](hipEvent_t &ev) { return ev ? hipSuccess : hipEventCreateWithFlags(&ev, hipEventDisableTiming); });
     }
     hipError_t ensure_inter(size_t bytes) { return inter.ensure_device(bytes, bytes); }
     hipError_t ensure_state(size_t floats) { return state.ensure_device(floats, floats + floats / 4); }
@@ -547,13 +532,259 @@ int ns_launch_slice(PipeWs &w, DeviceCtx *dc, const long long *d_rows, int nact,
     return ns_launch(a, form, s);
 }
 
+/* ---- the time-slice pipelines ------------------------------------------------------------------------ */
+/* The list cut along the TIME axis: slice k holds the frames [B_k, B_k+1) of every utterance that has them, packed like a
+ * batch of its own, and is one launch (or launch group) over all those utterances, the recursion travelling in a state blob
+ * per utterance.  A launch then lasts as long as ITS frames take -- a chunk of whole utterances lasts as long as its longest
+ * utterance, whatever its size -- so the pipeline
+ *     pool threads  pack slice k+1            | unpack slice k-1
+ *     copy engines  H2D slice k+1             | D2H slice k-1
+ *     device        kernel over slice k
+ * has short fill and drain phases: the first kernel starts after 1/K of the upload, the last download carries 1/K of the
+ * output.  Slice boundaries (slice_plan.h) equalise the slices' sample counts (SEA_HOST_SLICES of them, default 8: measured on the
+ * 1024-utterance bench corpus, tools/host_slices_sweep.sh, alternating on one box -- chunks of whole utterances 7.4 ms,
+ * 4 slices 6.2-6.5, 6: 5.9-6.0, 8: 4.8-5.7, 10: 5.6-5.7, 12: 5.3-5.8, 16: 5.8 ms; what is left is the pool's memcpy
+ * rate: 2 x 131 MB packed and unpacked in that time).
+ * Three streams, one per job -- uploads (after the meta rows, same stream), kernels (in order: slice k needs slice k - 1's
+ * state), downloads: with one stream per slice, reused round robin, a slice's download ended up queued behind a later slice's
+ * kernel (calls of 13-20 ms among the 6 ms ones). */
+
+/* slice k as the callables launch and extra_download of run_slices see it */
+struct SliceView {
+    int k, n;                /* the slice, its utterances (nact[k]) */
+    long long f0, fr;        /* its first frame in the staging buffers (foff[k]), its frames */
+    size_t i0;               /* the number of its first piece among the pieces of all slices in plan order (mbase[k] / 2) */
+    const long long *d_rows; /* its offsets | lengths rows on the device */
+    int frame_base;          /* its first frame in every utterance (B[k]) */
+    bool resume;             /* k > 0: the recursion continues from the state blob */
+    hipStream_t sKern, sDown;
+};
+
+/* one utterance's piece of a slice as the callable unpack_piece sees it */
+struct SlicePiece {
+    int u;           /* the utterance */
+    size_t i;        /* the piece's number among the pieces of all slices in plan order (mbase[k] / 2 + j) */
+    long long b;     /* its first frame in the utterance (B[k]) */
+    long long f0, n; /* its first frame in the staging buffers, its frames */
+    long long start; /* rows the utterance's earlier slices emitted: where this piece's rows go (0 without row counts) */
+};
+
+/* One call of a time-slice pipeline on plan p (p.K > 0) of the list `in`, frames of hop_in samples up.  The caller has sized
+ * the workspace's buffers and written what it keeps in w.meta.h behind the slices' offsets | lengths rows (meta_n long longs
+ * are uploaded in all); the rows themselves are written here, offsets absolute (the device sees ONE in and ONE out buffer) or
+ * from each slice's start (a slice is a batch of its own).  Per slice:
+ *     upload of its input, then on the kernel stream   launch(view)          returns 0 or fail()
+ *     download of its int16 audio (frames of hop_out samples, where want_out), then on the download stream
+ *                                                      extra_download(view)  returns 0 or fail()
+ *     per utterance, in a pool task                    unpack_piece(piece)   copied into the tasks: it holds pointers only
+ * h_cnt, where given: the pinned array extra_download brings the pieces' emitted row counts to (piece i's at h_cnt[i]); the
+ * slices are then unpacked in slice order (RowOrder, slice_plan.h), piece.start says where the rows go, and after the run
+ * n_rows[u] is the total of every utterance with a whole frame.  Returns run_pipeline's result. */
+template <class Launch, class ExtraDownload, class UnpackPiece>
+int run_slices(PipeWs &w, Pool &pool, const SlicePlan &p, const char *piece, const short *const *in, long long hop_in,
+               long long hop_out, bool want_out, bool absolute, bool small, size_t meta_n, const int *h_cnt, int *n_rows,
+               Launch launch, ExtraDownload extra_download, UnpackPiece unpack_piece)
+{
+    const int K = p.K;
+    /* The lifetime rule of every pipeline here: what a pool task dereferences -- bpre, order.start, packed -- is declared
+     * BEFORE scope, whose destructor waits for the pool on every exit path.  (p is the caller's and outlives this call.) */
+    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, hop_in, absolute, w.meta.h);
+    RowOrder order(h_cnt ? K : 0, h_cnt ? (int)p.idx.size() : 0);
+    std::vector<Latch> packed(K);
+    Scope scope(&w);
+    short *h_in = w.in.h;
+    const int *ix = p.idx.data();
+    for (int k = 0; k < K; ++k) {
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long b0 = hop_in * p.B[k], s0 = absolute ? 0 : hop_in * p.foff[k];
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
+                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
+    }
+    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
+    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, meta_n * sizeof(long long), hipMemcpyHostToDevice, sUp));
+    auto view = [&](int k) {
+        return SliceView{k, p.nact[k], p.foff[k], p.foff[k + 1] - p.foff[k], p.mbase[k] / 2, w.meta.d + p.mbase[k], (int)p.B[k], k > 0,
+                         sKern, sDown};
+    };
+    auto cut = [&](int k, const long long *st) { /* the copy tasks of slice k */
+        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
+        const long long bk = p.B[k], s0 = absolute ? 0 : p.foff[k];
+        const size_t i0 = p.mbase[k] / 2;
+        run_copies(pool, 0, p.nact[k], bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
+            unpack_piece(SlicePiece{ix[j], i0 + (size_t)j, bk, s0 + offs[j] / hop_in, lens[j] / hop_in, st ? st[j] : 0});
+        });
+    };
+
+    const int rc = run_pipeline(
+        w, scope, packed, piece, true,
+        [&](int k) {
+            const SliceView v = view(k);
+            HIP_TRY(hipMemcpyAsync(w.in.d + hop_in * v.f0, h_in + hop_in * v.f0, (size_t)(v.fr * hop_in) * sizeof(short),
+                                   hipMemcpyHostToDevice, sUp));
+            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
+            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
+            if (launch(v)) return 1;
+            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            return 0;
+        },
+        [&](int k) {
+            const SliceView v = view(k);
+            if (want_out)
+                HIP_TRY(hipMemcpyAsync(w.out.h + hop_out * v.f0, w.out.d + hop_out * v.f0, (size_t)(v.fr * hop_out) * sizeof(short),
+                                       hipMemcpyDeviceToHost, sDown));
+            if (extra_download(v)) return 1;
+            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
+            return 0;
+        },
+        [&](int k) {
+            if (h_cnt) order.arrive(p, k, h_cnt, cut);
+            else cut(k, nullptr);
+        });
+    if (rc) return rc;
+    if (n_rows) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
+        for (size_t j = 0; j < p.idx.size(); ++j)
+            if (p.nfr[j] > 0) n_rows[ix[j]] = (int)order.pos[j];
+    return 0;
+}
+
+/* the plan of a call: one slice for a list too small to cut, SEA_HOST_SLICES (default 8) otherwise */
+void plan_call(SlicePlan &p, const long *lengths, int n_utt, long long hop, bool small)
+{
+    slice_plan(p, lengths, n_utt, hop, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+}
+
+/* The FEATURES from host buffers, both rates: per slice sea_ns_denoise_batch_slice_fd + sea_afe_features_batch_slice (WB:
+ * sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice) on the kernel stream.  Slice k is a batch of its own on the
+ * device (offsets from the slice's start), so what the chain reads of a slice -- the float stream, the flag bytes (8 kHz: one
+ * per 8 samples), the cepstra before PostProc, and the wideband mode's QMF scratch, high-band and code rows -- lives in device
+ * buffers of one slice's size, reused by the next slice (the kernels run in order on one stream) and never downloaded.  What
+ * travels back is a slice's block of emitted rows (its frames + 6 per utterance), the counts, and the int16 audio where the
+ * caller asks for it.  d_final is set where an utterance's last planned slice is this one.  An utterance without a whole frame
+ * is in no slice: its result is DoVADFlush on the initial state, six zero rows, written here.
+ * The state is used even for a list that is not cut: there is one path here, the slice kernels'. */
+template <bool WB>
+int features_slices(const char *who, const short *const *in, short *const *out, float *const *feats, int *n_feat,
+                    const long *lengths, int n_utt)
+{
+    if (n_utt <= 0) return 0;
+    if (!in || !feats || !n_feat || !lengths) return fail("%s: in, feats, n_feat and lengths are required", who);
+    for (int u = 0; u < n_utt; ++u) {
+        if (lengths[u] < 0) return fail("%s: negative length for utterance %d", who, u);
+        if (!feats[u]) return fail("%s: feats[%d] is NULL", who, u);
+    }
+    DeviceCtx *dc;
+    if (ctx(&dc)) return 1;
+    constexpr long long kIn = WB ? SEA_WB_HOP : SEA_HOP, kOut = SEA_HOP; /* samples per frame up / down */
+    const long long total_fr = slice_total_frames(lengths, n_utt, kIn);
+    t_last_slices = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        n_feat[u] = 0;
+        if (lengths[u] / kIn == 0) { /* in no slice: DoVADFlush on the initial state */
+            memset(feats[u], 0, 6 * 15 * sizeof(float));
+            n_feat[u] = 6;
+        }
+    }
+    if (total_fr == 0) return 0;
+    PipeWs &w = t_ws;
+    HIP_TRY(w.bind());
+    Pool &pool = Pool::get(w.device);
+    /* "small list -> one slice" in FRAMES at both rates: a frame costs the 8 kHz chain what it costs the wideband one (the frame
+     * loop and the tile are the same), so the list too small to cut is one of 2 MB / 320 B = 6553 frames */
+    const bool small = total_fr * SEA_WB_HOP * 2 < (2 << 20) || pool.size() <= 1;
+    SlicePlan p;
+    plan_call(p, lengths, n_utt, kIn, small);
+    if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
+    const int K = t_last_slices = p.K;
+
+    /* meta: the slices' offsets | lengths rows, then per slice the two prefix sums (nact + 1 each); ints: per piece the count,
+     * then first_out and onset per utterance; feat: the block of the slice whose first piece is number i0 starts at row
+     * foff[k] + 6 * i0 */
+    const long long max_slice_fr = slice_max_frames(p);
+    const size_t n_act = p.mbase[K] / 2;
+    auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] + 2 * (size_t)k; };
+    HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
+    HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
+    HIP_TRY(w.meta.ensure(cum_base(K)));
+    HIP_TRY(w.ints.ensure(n_act + 2 * (size_t)n_utt));
+    HIP_TRY(w.fin.ensure(n_act));
+    HIP_TRY(w.feat.ensure(((size_t)total_fr + 6 * n_act) * 15));
+    HIP_TRY(w.f32.ensure_device((size_t)(max_slice_fr * kOut)));
+    HIP_TRY(w.flag_rows.ensure_device(WB ? (size_t)max_slice_fr + 1 : (size_t)max_slice_fr * 10 + 1));
+    HIP_TRY(w.ceps.ensure_device((size_t)max_slice_fr * SEA_CC_NCEP));
+    HIP_TRY(w.ensure_state((size_t)n_utt * (WB ? sea::kWbSliceStateFloats : sea::kNsPipeStateFloats)));
+    HIP_TRY(w.afe_state.ensure_device((size_t)n_utt * (WB ? sea::kWbAfeStateFloats : sea::kAfeStateFloats)));
+    if (WB) {
+        HIP_TRY(w.wb_rows.ensure_device(12 * ((size_t)max_slice_fr + 1)));
+        HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
+    }
+    for (int k = 0; k < K; ++k) {
+        const int n = p.nact[k];
+        long long *cc = w.meta.h + cum_base(k), *fc = cc + n + 1, c = 0;
+        unsigned char *fin = w.fin.h + p.mbase[k] / 2;
+        for (int j = 0; j < n; ++j) {
+            cc[j] = c;
+            fc[j] = c + 6 * (long long)j;
+            fin[j] = p.nfr[j] <= p.B[k + 1];
+            c += slice_piece_frames(p, k, j);
+        }
+        cc[n] = c;
+        fc[n] = c + 6 * (long long)n;
+    }
+    short *h_out = w.out.h;
+    float *h_feat = w.feat.h;
+    const int *h_cnt = w.ints.h;
+    int *d_first = w.ints.d + n_act, *d_onset = d_first + n_utt;
+    float *d_hp = WB ? w.wb_rows.d : nullptr, *d_code = WB ? w.wb_rows.d + 3 * ((size_t)max_slice_fr + 1) : nullptr;
+    HIP_TRY(hipMemcpyAsync(w.fin.d, w.fin.h, n_act, hipMemcpyHostToDevice, w.stream[0])); /* the upload stream, before every slice */
+
+    return run_slices(
+        w, pool, p, WB ? "wideband feature slice" : "feature slice", in, kIn, kOut, out != nullptr, false, small, cum_base(K), h_cnt,
+        n_feat,
+        [&](const SliceView &v) {
+            const long long *d_rows = v.d_rows, *d_cc = w.meta.d + cum_base(v.k);
+            const int n = v.n;
+            const short *d_in = w.in.d + kIn * v.f0;
+            short *d_out = w.out.d + kOut * v.f0;
+            float *d_blk = w.feat.d + 15 * (v.f0 + 6 * (long long)v.i0);
+            if constexpr (WB) {
+                if (sea_wb_denoise_batch_slice_fd(d_in, d_out, w.f32.d, d_rows, d_rows + n, nullptr, d_first, d_onset, w.flag_rows.d,
+                                                  d_hp, d_code, (float *)w.inter.d, v.fr * kIn, w.state.d, n, v.frame_base, v.resume,
+                                                  v.sKern))
+                    return 1;
+                return sea_wb_afe_features_batch_slice(w.f32.d, w.flag_rows.d, d_hp, d_code, d_rows, d_rows + n, d_first, d_onset,
+                                                       w.fin.d + v.i0, d_cc, v.fr, w.ceps.d, nullptr, d_cc + n + 1, d_blk,
+                                                       w.ints.d + v.i0, nullptr, w.afe_state.d, n, v.frame_base, v.resume, v.sKern);
+            } else {
+                if (sea_ns_denoise_batch_slice_fd(d_in, d_out, w.f32.d, d_rows, d_rows + n, nullptr, d_first, w.flag_rows.d, d_onset,
+                                                  w.state.d, n, v.frame_base, v.resume, v.sKern))
+                    return 1;
+                return sea_afe_features_batch_slice(w.f32.d, w.flag_rows.d, d_rows, d_rows + n, d_first, d_onset, w.fin.d + v.i0, d_cc,
+                                                    v.fr, w.ceps.d, nullptr, d_cc + n + 1, d_blk, w.ints.d + v.i0, nullptr,
+                                                    w.afe_state.d, n, v.frame_base, v.resume, v.sKern);
+            }
+        },
+        [&](const SliceView &v) {
+            const long long r0 = v.f0 + 6 * (long long)v.i0, nr = v.fr + 6 * (long long)v.n;
+            HIP_TRY(hipMemcpyAsync(h_feat + 15 * r0, w.feat.d + 15 * r0, (size_t)nr * 15 * sizeof(float), hipMemcpyDeviceToHost, v.sDown));
+            HIP_TRY(hipMemcpyAsync(w.ints.h + v.i0, w.ints.d + v.i0, (size_t)v.n * sizeof(int), hipMemcpyDeviceToHost, v.sDown));
+            return 0;
+        },
+        [=](const SlicePiece &c) {
+            if (out && out[c.u]) /* whole frames only: the trailing partial frame stays untouched, as with etsi_denoise */
+                copy_stream(out[c.u] + kOut * c.b, h_out + kOut * c.f0, (size_t)(c.n * kOut) * sizeof(short));
+            if (h_cnt[c.i] > 0)
+                copy_stream(feats[c.u] + 15 * c.start, h_feat + 15 * (c.f0 + 6 * (long long)c.i), (size_t)h_cnt[c.i] * 15 * sizeof(float));
+        });
+}
+
 } // namespace
 
 extern "C" {
 
 /* Test hook: from the nth event query of this process on (1-based; 0 switches the hook off) every query reports a device
  * fault instead of asking the runtime.  tests/test_gpu_parity.py::test_host_pipeline_returns_fault_on_event_error checks
- * that all three pipelines then return 1 with their streams drained and work again afterwards. */
+ * that the time-slice driver (through three of its entry points) and both chunk pipelines then return 1 with their streams
+ * drained and work again afterwards. */
 static std::atomic<long long> g_fault_after{0}, g_queries{0};
 static hipError_t faulty_query(hipEvent_t e)
 {
@@ -686,21 +917,9 @@ int sea_denoise_utterances(const short *const *in, short *const *out, const long
     return denoise_utterances_slices(in, out, lengths, n_utt);
 }
 
-/* The list cut along the TIME axis: slice k holds the frames [B_k, B_k+1) of every utterance that has them, packed like a
- * batch of its own, and is one launch over all those utterances (sea_ns_denoise_batch_slice: the recursion travels in a
- * state blob per utterance).  A launch then lasts as long as ITS frames take -- a chunk of whole utterances lasts as long
- * as its longest utterance, whatever its size -- so the pipeline
- *     pool threads  pack slice k+1            | unpack slice k-1
- *     copy engines  H2D slice k+1             | D2H slice k-1
- *     device        kernel over slice k
- * has short fill and drain phases: the first kernel starts after 1/K of the upload, the last download carries 1/K of the
- * output.  Slice boundaries (slice_plan.h) equalise the slices' sample counts (SEA_HOST_SLICES of them, default 8: measured on the
- * 1024-utterance bench corpus, tools/host_slices_sweep.sh, alternating on one box -- chunks of whole utterances 7.4 ms,
- * 4 slices 6.2-6.5, 6: 5.9-6.0, 8: 4.8-5.7, 10: 5.6-5.7, 12: 5.3-5.8, 16: 5.8 ms; what is left is the pool's memcpy
- * rate: 2 x 131 MB packed and unpacked in that time).
- * Three streams, one per job -- uploads, kernels (in order: slice k needs slice k - 1's state), downloads: with one
- * stream per slice, reused round robin, a slice's download ended up queued behind a later slice's kernel (calls of
- * 13-20 ms among the 6 ms ones). */
+/* NoiseSup in time slices (run_slices above), sea_ns_denoise_batch_slice per slice.  The slices lie one after the other in the
+ * staging, offsets absolute: the device sees ONE in and ONE out buffer.  A list that is not cut needs no state blob and runs
+ * as sea_ns_denoise_batch would (ns_launch_slice). */
 static int denoise_utterances_slices(const short *const *in, short *const *out, const long *lengths, int n_utt)
 {
     if (n_utt <= 0) return 0;
@@ -716,54 +935,18 @@ static int denoise_utterances_slices(const short *const *in, short *const *out, 
     Pool &pool = Pool::get(w.device);
     const bool small = total * 2 < (2 << 20) || pool.size() <= 1;
     SlicePlan p;
-    slice_plan(p, lengths, n_utt, kHop, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    plan_call(p, lengths, n_utt, kHop, small);
     const int K = t_last_slices = p.K;
-
-    /* the slices one after the other in the staging, offsets absolute: the device sees ONE in and ONE out buffer */
     HIP_TRY(w.in.ensure((size_t)total));
     HIP_TRY(w.out.ensure((size_t)total));
     HIP_TRY(w.meta.ensure(p.mbase[K]));
     if (K > 1) HIP_TRY(w.ensure_state((size_t)n_utt * sea::kNsPipeStateFloats));
-    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kHop, true, w.meta.h);
-
-    std::vector<Latch> packed(K);
-    Scope scope(&w);
-    short *h_in = w.in.h, *h_out = w.out.h;
-    const int *ix = p.idx.data();
-    for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-        const long long b0 = kHop * p.B[k];
-        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
-                   [=](int j) { copy_stream(h_in + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
-    }
-    /* one stream per job: uploads (after the meta arrays, same stream), kernels (in order: the recursion needs slice k after
-     * slice k - 1), downloads -- a slice's download is never queued behind a later slice's work */
-    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, p.mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
-
-    return run_pipeline(
-        w, scope, packed, "slice", true,
-        [&](int k) {
-            const long long o0 = kHop * p.foff[k], cnt = kHop * (p.foff[k + 1] - p.foff[k]);
-            HIP_TRY(hipMemcpyAsync(w.in.d + o0, h_in + o0, (size_t)cnt * sizeof(short), hipMemcpyHostToDevice, sUp));
-            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
-            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
-            if (ns_launch_slice(w, dc, w.meta.d + p.mbase[k], p.nact[k], K, k, (int)p.B[k], sKern)) return 1;
-            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
-            return 0;
-        },
-        [&](int k) {
-            const long long o0 = kHop * p.foff[k], cnt = kHop * (p.foff[k + 1] - p.foff[k]);
-            HIP_TRY(hipMemcpyAsync(h_out + o0, w.out.d + o0, (size_t)cnt * sizeof(short), hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-            return 0;
-        },
-        [&](int k) {
-            const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-            const long long b0 = kHop * p.B[k];
-            run_copies(pool, 0, p.nact[k], bpre[k].data(), nullptr, &scope.all, small,
-                       [=](int j) { copy_stream(out[ix[j]] + b0, h_out + offs[j], (size_t)lens[j] * sizeof(short)); });
-        });
+    short *h_out = w.out.h;
+    return run_slices(
+        w, pool, p, "slice", in, kHop, kHop, true, true, small, p.mbase[K], nullptr, nullptr,
+        [&](const SliceView &v) { return ns_launch_slice(w, dc, v.d_rows, v.n, K, v.k, v.frame_base, v.sKern); },
+        [](const SliceView &) { return 0; },
+        [=](const SlicePiece &c) { copy_stream(out[c.u] + kHop * c.b, h_out + kHop * c.f0, (size_t)(c.n * kHop) * sizeof(short)); });
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
@@ -797,404 +980,61 @@ int sea_wb_denoise_utterances(const short *const *in, short *const *out_lp, floa
     Pool &pool = Pool::get(w.device);
     const bool small = total_fr * kIn * 2 < (2 << 20) || pool.size() <= 1;
     SlicePlan p;
-    slice_plan(p, lengths, n_utt, kIn, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    plan_call(p, lengths, n_utt, kIn, small);
     if (p.max_fr > 0x7fffffffLL - 8) return fail("sea_wb_denoise_utterances: utterance %d is too long", p.idx[0]);
     const int K = t_last_slices = p.K;
 
     /* slice k starts at frame foff[k] of every staging buffer: x 160 in the input, x 80 in the output, x 3 and x 9 in the rows */
-    const std::vector<long long> &foff = p.foff;
-    long long max_slice_fr = 0;
-    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
     const size_t n_rows = (size_t)total_fr + 1; /* a slice writes rows [0, its frames): sea_wb_rows' spare row is never touched */
     HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
     HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
     HIP_TRY(w.meta.ensure(p.mbase[K]));
     if (rows) HIP_TRY(w.wb_rows.ensure(12 * n_rows));
     HIP_TRY(w.ensure_state((size_t)n_utt * sea::kWbSliceStateFloats));
-    HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
-    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kIn, false, w.meta.h);
-
-    std::vector<Latch> packed(K);
-    Scope scope(&w);
-    short *h_in = w.in.h, *h_out = w.out.h;
+    HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(slice_max_frames(p) * kIn, n_utt)));
+    short *h_out = w.out.h;
     float *h_hp = rows ? w.wb_rows.h : nullptr, *h_code = rows ? w.wb_rows.h + 3 * n_rows : nullptr;
     float *d_hp = rows ? w.wb_rows.d : nullptr, *d_code = rows ? w.wb_rows.d + 3 * n_rows : nullptr;
-    const int *ix = p.idx.data();
-    for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-        const long long b0 = kIn * p.B[k], s0 = kIn * foff[k];
-        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
-                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
-    }
-    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, p.mbase[K] * sizeof(long long), hipMemcpyHostToDevice, sUp));
 
-    return run_pipeline(
-        w, scope, packed, "wideband slice", true,
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * f0, h_in + kIn * f0, (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
-            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
-            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
+    return run_slices(
+        w, pool, p, "wideband slice", in, kIn, kOut, true, false, small, p.mbase[K], nullptr, nullptr,
+        [&](const SliceView &v) {
             if (rows) {
-                HIP_TRY(hipMemsetAsync(d_hp + 3 * f0, 0, (size_t)fr * 3 * sizeof(float), sKern));
-                HIP_TRY(hipMemsetAsync(d_code + 9 * f0, 0, (size_t)fr * 9 * sizeof(float), sKern));
+                HIP_TRY(hipMemsetAsync(d_hp + 3 * v.f0, 0, (size_t)v.fr * 3 * sizeof(float), v.sKern));
+                HIP_TRY(hipMemsetAsync(d_code + 9 * v.f0, 0, (size_t)v.fr * 9 * sizeof(float), v.sKern));
             }
-            const long long *d_rows = w.meta.d + p.mbase[k];
-            if (sea_wb_denoise_batch_slice(w.in.d + kIn * f0, w.out.d + kOut * f0, nullptr, d_rows, d_rows + p.nact[k], nullptr, nullptr,
-                                           nullptr, rows ? d_hp + 3 * f0 : nullptr, rows ? d_code + 9 * f0 : nullptr,
-                                           (float *)w.inter.d, fr * kIn, w.state.d, p.nact[k], (int)p.B[k], k > 0, sKern))
-                return 1;
-            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+            return sea_wb_denoise_batch_slice(w.in.d + kIn * v.f0, w.out.d + kOut * v.f0, nullptr, v.d_rows, v.d_rows + v.n, nullptr,
+                                              nullptr, nullptr, rows ? d_hp + 3 * v.f0 : nullptr, rows ? d_code + 9 * v.f0 : nullptr,
+                                              (float *)w.inter.d, v.fr * kIn, w.state.d, v.n, v.frame_base, v.resume, v.sKern);
+        },
+        [&](const SliceView &v) {
+            if (rows) {
+                HIP_TRY(hipMemcpyAsync(h_hp + 3 * v.f0, d_hp + 3 * v.f0, (size_t)v.fr * 3 * sizeof(float), hipMemcpyDeviceToHost, v.sDown));
+                HIP_TRY(hipMemcpyAsync(h_code + 9 * v.f0, d_code + 9 * v.f0, (size_t)v.fr * 9 * sizeof(float), hipMemcpyDeviceToHost, v.sDown));
+            }
             return 0;
         },
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            HIP_TRY(hipMemcpyAsync(h_out + kOut * f0, w.out.d + kOut * f0, (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
-            if (rows) {
-                HIP_TRY(hipMemcpyAsync(h_hp + 3 * f0, d_hp + 3 * f0, (size_t)fr * 3 * sizeof(float), hipMemcpyDeviceToHost, sDown));
-                HIP_TRY(hipMemcpyAsync(h_code + 9 * f0, d_code + 9 * f0, (size_t)fr * 9 * sizeof(float), hipMemcpyDeviceToHost, sDown));
+        [=](const SlicePiece &c) {
+            copy_stream(out_lp[c.u] + kOut * c.b, h_out + kOut * c.f0, (size_t)(c.n * kOut) * sizeof(short));
+            if (rows && hp_rows[c.u]) {
+                copy_stream(hp_rows[c.u] + 3 * c.b, h_hp + 3 * c.f0, (size_t)c.n * 3 * sizeof(float));
+                copy_stream(code_rows[c.u] + 9 * c.b, h_code + 9 * c.f0, (size_t)c.n * 9 * sizeof(float));
             }
-            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-            return 0;
-        },
-        [&](int k) {
-            const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-            const long long bk = p.B[k], fk = foff[k];
-            run_copies(pool, 0, p.nact[k], bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
-                const long long f0 = fk + offs[j] / kIn, n = lens[j] / kIn; /* the piece's first frame in the staging, its frames */
-                const int u = ix[j];
-                copy_stream(out_lp[u] + kOut * bk, h_out + kOut * f0, (size_t)(n * kOut) * sizeof(short));
-                if (rows && hp_rows[u]) {
-                    copy_stream(hp_rows[u] + 3 * bk, h_hp + 3 * f0, (size_t)n * 3 * sizeof(float));
-                    copy_stream(code_rows[u] + 9 * bk, h_code + 9 * f0, (size_t)n * 9 * sizeof(float));
-                }
-            });
         });
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
-/* The wideband FEATURES from host buffers: sea_wb_denoise_utterances' cut, streams and loop, per slice
- * sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice on the kernel stream.  What the chain reads of a slice -- the
- * float stream, the flag bytes, the high-band and code rows, the cepstra before PostProc -- lives in device buffers of one
- * slice's size, reused by the next slice (the kernels run in order on one stream) and never downloaded.  What travels back is a
- * slice's block of emitted rows (its frames + 6 per utterance) and the counts.  An utterance's rows of slice k go behind those
- * of its earlier slices, so where they go is known once the counts of slices 0 .. k - 1 are on the host.  run_pipeline promises
- * no order here: one pass of its loop may find slice k's kernel or download event "not ready" and slice k + 1's done, so both
- * download (k + 1) and unpack (k + 1) may come before slice k's.  unpack (k) therefore only notes that slice k has arrived; the
- * slices' copy tasks are cut strictly in slice order, each as soon as it and every slice before it have arrived, from a running
- * sum that by then holds exactly the earlier slices' counts.  The tasks need no order among themselves.
- * d_final is set where an utterance's last planned slice is this one.  An utterance without a whole frame is in no slice: its
- * result is DoVADFlush on the initial state, six zero rows, written here. */
+/* The feature chains from host buffers (features_slices above): rows of 15 floats, n_feat[u] of them. */
 int sea_wb_features_utterances(const short *const *in, short *const *out_lp, float *const *feats, int *n_feat,
                                const long *lengths, int n_utt)
 {
-    const char *who = "sea_wb_features_utterances";
-    if (n_utt <= 0) return 0;
-    if (!in || !feats || !n_feat || !lengths) return fail("%s: in, feats, n_feat and lengths are required", who);
-    for (int u = 0; u < n_utt; ++u) {
-        if (lengths[u] < 0) return fail("%s: negative length for utterance %d", who, u);
-        if (!feats[u]) return fail("%s: feats[%d] is NULL", who, u);
-    }
-    DeviceCtx *dc;
-    if (ctx(&dc)) return 1;
-    constexpr long long kIn = SEA_WB_HOP, kOut = SEA_HOP;
-    const long long total_fr = slice_total_frames(lengths, n_utt, kIn);
-    t_last_slices = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        n_feat[u] = 0;
-        if (lengths[u] / kIn == 0) {
-            memset(feats[u], 0, 6 * 15 * sizeof(float));
-            n_feat[u] = 6;
-        }
-    }
-    if (total_fr == 0) return 0;
-    PipeWs &w = t_ws;
-    HIP_TRY(w.bind());
-    Pool &pool = Pool::get(w.device);
-    const bool small = total_fr * kIn * 2 < (2 << 20) || pool.size() <= 1;
-    SlicePlan p;
-    slice_plan(p, lengths, n_utt, kIn, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
-    if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
-    const int K = t_last_slices = p.K;
-
-    const std::vector<long long> &foff = p.foff;
-    long long max_slice_fr = 0;
-    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
-    /* meta: the slices' offsets | lengths rows, then per slice the two prefix sums (nact + 1 each); ints: per slice the counts,
-     * then first_out and onset per utterance; feat: slice k's block starts at row foff[k] + 6 * (utterances of the slices before) */
-    const size_t n_act = p.mbase[K] / 2;
-    auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] + 2 * (size_t)k; };
-    auto feat_row = [&](int k) { return foff[k] + 3 * (long long)p.mbase[k]; };
-    const size_t n_feat_rows = (size_t)feat_row(K);
-    HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
-    HIP_TRY(w.out.ensure((size_t)(total_fr * kOut)));
-    HIP_TRY(w.meta.ensure(cum_base(K)));
-    HIP_TRY(w.ints.ensure(n_act + 2 * (size_t)n_utt));
-    HIP_TRY(w.fin.ensure(n_act));
-    HIP_TRY(w.feat.ensure(n_feat_rows * 15));
-    HIP_TRY(w.f32.ensure_device((size_t)(max_slice_fr * kOut)));
-    HIP_TRY(w.flag_rows.ensure_device((size_t)max_slice_fr + 1));
-    HIP_TRY(w.wb_rows.ensure_device(12 * ((size_t)max_slice_fr + 1)));
-    HIP_TRY(w.ceps.ensure_device((size_t)max_slice_fr * SEA_CC_NCEP));
-    HIP_TRY(w.ensure_state((size_t)n_utt * sea::kWbSliceStateFloats));
-    HIP_TRY(w.afe_state.ensure_device((size_t)n_utt * sea::kWbAfeStateFloats));
-    HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
-    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kIn, false, w.meta.h);
-    for (int k = 0; k < K; ++k) {
-        const int n = p.nact[k];
-        const long long *offs = w.meta.h + p.mbase[k];
-        long long *cc = w.meta.h + cum_base(k), *fc = cc + n + 1;
-        unsigned char *fin = w.fin.h + p.mbase[k] / 2;
-        for (int j = 0; j < n; ++j) {
-            cc[j] = offs[j] / kIn;
-            fc[j] = cc[j] + 6 * (long long)j;
-            fin[j] = p.nfr[j] <= p.B[k + 1];
-        }
-        cc[n] = foff[k + 1] - foff[k];
-        fc[n] = cc[n] + 6 * (long long)n;
-    }
-
-    std::vector<Latch> packed(K);
-    std::vector<long long> pos(n_utt, 0);             /* rows of sorted position j in the slices before next_cut */
-    std::vector<std::vector<long long>> start(K);     /* per slice: where each of its utterances' rows go */
-    std::vector<char> arrived(K, 0);                  /* slice k's rows and counts are on the host */
-    int next_cut = 0;                                 /* the first slice whose copy tasks are not cut yet */
-    Scope scope(&w);
-    short *h_in = w.in.h, *h_out = w.out.h;
-    float *h_feat = w.feat.h;
-    const int *h_cnt = w.ints.h;
-    int *d_first = w.ints.d + n_act, *d_onset = d_first + n_utt;
-    float *d_hp = w.wb_rows.d, *d_code = w.wb_rows.d + 3 * ((size_t)max_slice_fr + 1);
-    const int *ix = p.idx.data();
-    for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-        const long long b0 = kIn * p.B[k], s0 = kIn * foff[k];
-        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
-                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
-    }
-    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, cum_base(K) * sizeof(long long), hipMemcpyHostToDevice, sUp));
-    HIP_TRY(hipMemcpyAsync(w.fin.d, w.fin.h, n_act, hipMemcpyHostToDevice, sUp));
-
-    const int rc = run_pipeline(
-        w, scope, packed, "wideband feature slice", true,
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            const int n = p.nact[k];
-            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * f0, h_in + kIn * f0, (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
-            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
-            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
-            const long long *d_rows = w.meta.d + p.mbase[k], *d_cc = w.meta.d + cum_base(k);
-            if (sea_wb_denoise_batch_slice_fd(w.in.d + kIn * f0, w.out.d + kOut * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
-                                              d_onset, w.flag_rows.d, d_hp, d_code, (float *)w.inter.d, fr * kIn, w.state.d, n,
-                                              (int)p.B[k], k > 0, sKern))
-                return 1;
-            if (sea_wb_afe_features_batch_slice(w.f32.d, w.flag_rows.d, d_hp, d_code, d_rows, d_rows + n, d_first, d_onset,
-                                                w.fin.d + p.mbase[k] / 2, d_cc, fr, w.ceps.d, nullptr, d_cc + n + 1,
-                                                w.feat.d + 15 * feat_row(k), w.ints.d + p.mbase[k] / 2, nullptr, w.afe_state.d, n,
-                                                (int)p.B[k], k > 0, sKern))
-                return 1;
-            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
-            return 0;
-        },
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            const long long r0 = feat_row(k), nr = feat_row(k + 1) - r0;
-            if (out_lp)
-                HIP_TRY(hipMemcpyAsync(h_out + kOut * f0, w.out.d + kOut * f0, (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipMemcpyAsync(h_feat + 15 * r0, w.feat.d + 15 * r0, (size_t)nr * 15 * sizeof(float), hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipMemcpyAsync(w.ints.h + p.mbase[k] / 2, w.ints.d + p.mbase[k] / 2, (size_t)p.nact[k] * sizeof(int),
-                                   hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-            return 0;
-        },
-        [&](int arrived_k) {
-            arrived[arrived_k] = 1;
-            for (; next_cut < K && arrived[next_cut]; ++next_cut) { /* in slice order, whatever order the slices arrive in */
-                const int k = next_cut, n = p.nact[k];
-                const long long *offs = w.meta.h + p.mbase[k], *lens = offs + n;
-                const int *cnt = h_cnt + p.mbase[k] / 2;
-                start[k].resize(n);
-                for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
-                    start[k][j] = pos[j];
-                    pos[j] += cnt[j];
-                }
-                const long long *st = start[k].data();
-                const long long bk = p.B[k], fk = foff[k], rk = feat_row(k);
-                run_copies(pool, 0, n, bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
-                    const long long f0 = offs[j] / kIn, nfr = lens[j] / kIn; /* the piece's first frame in the slice, its frames */
-                    const int u = ix[j];
-                    if (out_lp && out_lp[u])
-                        copy_stream(out_lp[u] + kOut * bk, h_out + kOut * (fk + f0), (size_t)(nfr * kOut) * sizeof(short));
-                    if (cnt[j] > 0)
-                        copy_stream(feats[u] + 15 * st[j], h_feat + 15 * (rk + f0 + 6 * (long long)j),
-                                    (size_t)cnt[j] * 15 * sizeof(float));
-                });
-            }
-        });
-    if (rc) return rc;
-    for (int j = 0; j < n_utt; ++j) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
-        if (p.nfr[j] > 0) n_feat[ix[j]] = (int)pos[j];
-    return 0;
+    return features_slices<true>("sea_wb_features_utterances", in, out_lp, feats, n_feat, lengths, n_utt);
 }
 
-/* ---------------------------------------------------------------------------------------------------- */
-/* The 8 kHz FEATURES from host buffers: sea_wb_features_utterances' cut, streams and loop on frames of 80 samples, per slice
- * sea_ns_denoise_batch_slice_fd + sea_afe_features_batch_slice on the kernel stream.  Slice k is a batch of its own on the
- * device (offsets from the slice's start), so the float stream, the flag bytes (one per 8 samples) and the cepstra before
- * PostProc live in device buffers of one slice's size, reused by the next slice and never downloaded.  What travels back is a
- * slice's block of emitted rows (its frames + 6 per utterance), the counts, and the int16 audio where the caller asks for it.
- * Where an utterance's rows of slice k go, and why unpack only notes arrivals: as in sea_wb_features_utterances above.
- * The state is used even for a list that is not cut: there is one path here, the slice kernels'. */
 int sea_features_utterances(const short *const *in, short *const *out, float *const *feats, int *n_feat, const long *lengths,
                             int n_utt)
 {
-    const char *who = "sea_features_utterances";
-    if (n_utt <= 0) return 0;
-    if (!in || !feats || !n_feat || !lengths) return fail("%s: in, feats, n_feat and lengths are required", who);
-    for (int u = 0; u < n_utt; ++u) {
-        if (lengths[u] < 0) return fail("%s: negative length for utterance %d", who, u);
-        if (!feats[u]) return fail("%s: feats[%d] is NULL", who, u);
-    }
-    DeviceCtx *dc;
-    if (ctx(&dc)) return 1;
-    constexpr long long kHop = SEA_HOP;
-    const long long total_fr = slice_total_frames(lengths, n_utt, kHop);
-    t_last_slices = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        n_feat[u] = 0;
-        if (lengths[u] / kHop == 0) { /* in no slice: DoVADFlush on the initial state */
-            memset(feats[u], 0, 6 * 15 * sizeof(float));
-            n_feat[u] = 6;
-        }
-    }
-    if (total_fr == 0) return 0;
-    PipeWs &w = t_ws;
-    HIP_TRY(w.bind());
-    Pool &pool = Pool::get(w.device);
-    /* "small list -> one slice" is sea_wb_features_utterances' rule, in FRAMES: a frame costs this chain what it costs the
-     * wideband one (the frame loop and the tile are the same), so the list too small to cut is one of 2 MB / 320 B = 6553 frames */
-    const bool small = total_fr * SEA_WB_HOP * 2 < (2 << 20) || pool.size() <= 1;
-    SlicePlan p;
-    slice_plan(p, lengths, n_utt, kHop, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
-    if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
-    const int K = t_last_slices = p.K;
-
-    const std::vector<long long> &foff = p.foff;
-    long long max_slice_fr = 0;
-    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
-    /* meta: the slices' offsets | lengths rows, then per slice the two prefix sums (nact + 1 each); ints: per slice the counts,
-     * then first_out and onset per utterance; feat: slice k's block starts at row foff[k] + 6 * (utterances of the slices before) */
-    const size_t n_act = p.mbase[K] / 2;
-    auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] + 2 * (size_t)k; };
-    auto feat_row = [&](int k) { return foff[k] + 3 * (long long)p.mbase[k]; };
-    const size_t n_feat_rows = (size_t)feat_row(K);
-    HIP_TRY(w.in.ensure((size_t)(total_fr * kHop)));
-    HIP_TRY(w.out.ensure((size_t)(total_fr * kHop)));
-    HIP_TRY(w.meta.ensure(cum_base(K)));
-    HIP_TRY(w.ints.ensure(n_act + 2 * (size_t)n_utt));
-    HIP_TRY(w.fin.ensure(n_act));
-    HIP_TRY(w.feat.ensure(n_feat_rows * 15));
-    HIP_TRY(w.f32.ensure_device((size_t)(max_slice_fr * kHop)));
-    HIP_TRY(w.flag_rows.ensure_device((size_t)max_slice_fr * 10 + 1)); /* one byte per 8 samples of the slice */
-    HIP_TRY(w.ceps.ensure_device((size_t)max_slice_fr * SEA_CC_NCEP));
-    HIP_TRY(w.ensure_state((size_t)n_utt * sea::kNsPipeStateFloats));
-    HIP_TRY(w.afe_state.ensure_device((size_t)n_utt * sea::kAfeStateFloats));
-    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kHop, false, w.meta.h);
-    for (int k = 0; k < K; ++k) {
-        const int n = p.nact[k];
-        const long long *offs = w.meta.h + p.mbase[k];
-        long long *cc = w.meta.h + cum_base(k), *fc = cc + n + 1;
-        unsigned char *fin = w.fin.h + p.mbase[k] / 2;
-        for (int j = 0; j < n; ++j) {
-            cc[j] = offs[j] / kHop;
-            fc[j] = cc[j] + 6 * (long long)j;
-            fin[j] = p.nfr[j] <= p.B[k + 1];
-        }
-        cc[n] = foff[k + 1] - foff[k];
-        fc[n] = cc[n] + 6 * (long long)n;
-    }
-
-    std::vector<Latch> packed(K);
-    std::vector<long long> pos(n_utt, 0);             /* rows of sorted position j in the slices before next_cut */
-    std::vector<std::vector<long long>> start(K);     /* per slice: where each of its utterances' rows go */
-    std::vector<char> arrived(K, 0);                  /* slice k's rows and counts are on the host */
-    int next_cut = 0;                                 /* the first slice whose copy tasks are not cut yet */
-    Scope scope(&w);
-    short *h_in = w.in.h, *h_out = w.out.h;
-    float *h_feat = w.feat.h;
-    const int *h_cnt = w.ints.h;
-    int *d_first = w.ints.d + n_act, *d_onset = d_first + n_utt;
-    const int *ix = p.idx.data();
-    for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-        const long long b0 = kHop * p.B[k], s0 = kHop * foff[k];
-        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
-                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
-    }
-    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, cum_base(K) * sizeof(long long), hipMemcpyHostToDevice, sUp));
-    HIP_TRY(hipMemcpyAsync(w.fin.d, w.fin.h, n_act, hipMemcpyHostToDevice, sUp));
-
-    const int rc = run_pipeline(
-        w, scope, packed, "feature slice", true,
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            const int n = p.nact[k];
-            HIP_TRY(hipMemcpyAsync(w.in.d + kHop * f0, h_in + kHop * f0, (size_t)(fr * kHop) * sizeof(short), hipMemcpyHostToDevice, sUp));
-            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
-            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
-            const long long *d_rows = w.meta.d + p.mbase[k], *d_cc = w.meta.d + cum_base(k);
-            if (sea_ns_denoise_batch_slice_fd(w.in.d + kHop * f0, w.out.d + kHop * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
-                                              w.flag_rows.d, d_onset, w.state.d, n, (int)p.B[k], k > 0, sKern))
-                return 1;
-            if (sea_afe_features_batch_slice(w.f32.d, w.flag_rows.d, d_rows, d_rows + n, d_first, d_onset, w.fin.d + p.mbase[k] / 2,
-                                             d_cc, fr, w.ceps.d, nullptr, d_cc + n + 1, w.feat.d + 15 * feat_row(k),
-                                             w.ints.d + p.mbase[k] / 2, nullptr, w.afe_state.d, n, (int)p.B[k], k > 0, sKern))
-                return 1;
-            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
-            return 0;
-        },
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            const long long r0 = feat_row(k), nr = feat_row(k + 1) - r0;
-            if (out)
-                HIP_TRY(hipMemcpyAsync(h_out + kHop * f0, w.out.d + kHop * f0, (size_t)(fr * kHop) * sizeof(short), hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipMemcpyAsync(h_feat + 15 * r0, w.feat.d + 15 * r0, (size_t)nr * 15 * sizeof(float), hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipMemcpyAsync(w.ints.h + p.mbase[k] / 2, w.ints.d + p.mbase[k] / 2, (size_t)p.nact[k] * sizeof(int),
-                                   hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-            return 0;
-        },
-        [&](int arrived_k) {
-            arrived[arrived_k] = 1;
-            for (; next_cut < K && arrived[next_cut]; ++next_cut) { /* in slice order, whatever order the slices arrive in */
-                const int k = next_cut, n = p.nact[k];
-                const long long *offs = w.meta.h + p.mbase[k], *lens = offs + n;
-                const int *cnt = h_cnt + p.mbase[k] / 2;
-                start[k].resize(n);
-                for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
-                    start[k][j] = pos[j];
-                    pos[j] += cnt[j];
-                }
-                const long long *st = start[k].data();
-                const long long bk = p.B[k], fk = foff[k], rk = feat_row(k);
-                run_copies(pool, 0, n, bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
-                    const long long f0 = offs[j] / kHop; /* the piece's first frame in the slice */
-                    const int u = ix[j];
-                    if (out && out[u]) /* whole frames only: the trailing partial frame stays untouched, as with etsi_denoise */
-                        copy_stream(out[u] + kHop * bk, h_out + kHop * (fk + f0), (size_t)lens[j] * sizeof(short));
-                    if (cnt[j] > 0)
-                        copy_stream(feats[u] + 15 * st[j], h_feat + 15 * (rk + f0 + 6 * (long long)j),
-                                    (size_t)cnt[j] * 15 * sizeof(float));
-                });
-            }
-        });
-    if (rc) return rc;
-    for (int j = 0; j < n_utt; ++j) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
-        if (p.nfr[j] > 0) n_feat[ix[j]] = (int)pos[j];
-    return 0;
+    return features_slices<false>("sea_features_utterances", in, out, feats, n_feat, lengths, n_utt);
 }
 
 /* launches the calling thread's last time-slice pipeline call (sea_denoise_utterances in the time-slice mode,
@@ -1320,14 +1160,12 @@ int sea_packed_denoise(sea_packed *p)
 }
 
 /* ---------------------------------------------------------------------------------------------------- */
-/* ---------------------------------------------------------------------------------------------------- */
-/* NoiseSup + the plain CompCeps from host buffers as a pipeline over TIME SLICES, both rates: sea_features_utterances' cut,
- * streams and loop, per slice sea_ns_denoise_batch_slice + sea_compceps_batch_slice (WB: sea_wb_denoise_batch_slice +
+/* NoiseSup + the plain CompCeps from host buffers as a pipeline over TIME SLICES, both rates: features_slices' cut, streams
+ * and loop (run_slices), per slice sea_ns_denoise_batch_slice + sea_compceps_batch_slice (WB: sea_wb_denoise_batch_slice +
  * sea_wb_compceps_batch_slice) on the kernel stream.  Slice k is a batch of its own on the device (offsets from the slice's
  * start), so the float stream -- and the wideband mode's QMF scratch, high-band rows and code rows -- live in device buffers of
  * one slice's size, reused by the next slice and never downloaded.  What travels back is the int16 audio, a slice's block of
- * cepstral rows (its frames) and the counts.  An utterance's rows of slice k go behind those of its earlier slices: unpack only
- * notes arrivals and the copy tasks are cut in slice order, as in sea_wb_features_utterances.
+ * cepstral rows (its frames) and the counts.
  * one_piece_elsewhere: return -1 before any work where the plan gives one slice (the 8 kHz call keeps its one launch there). */
 } /* extern "C": a template */
 template <bool WB>
@@ -1341,10 +1179,10 @@ static int denoise_ceps_slices(const char *who, const short *const *in, short *c
     PipeWs &w = t_ws;
     HIP_TRY(w.bind());
     Pool &pool = Pool::get(w.device);
-    /* "small list -> one slice" is sea_features_utterances' rule, in FRAMES: the frame loop and the tile cost the same at both rates */
+    /* "small list -> one slice" is features_slices' rule, in FRAMES: the frame loop and the tile cost the same at both rates */
     const bool small = total_fr * SEA_WB_HOP * 2 < (2 << 20) || pool.size() <= 1;
     SlicePlan p;
-    slice_plan(p, lengths, n_utt, kIn, small ? 1 : (int)env_mb("SEA_HOST_SLICES", 8));
+    plan_call(p, lengths, n_utt, kIn, small);
     if (one_piece_elsewhere && p.K <= 1) return -1;
     for (int u = 0; u < n_utt; ++u) n_ceps[u] = 0;
     t_last_slices = 0;
@@ -1352,11 +1190,9 @@ static int denoise_ceps_slices(const char *who, const short *const *in, short *c
     if (p.max_fr > 0x7fffffffLL - 8) return fail("%s: utterance %d is too long", who, p.idx[0]);
     const int K = t_last_slices = p.K;
 
-    const std::vector<long long> &foff = p.foff;
-    long long max_slice_fr = 0;
-    for (int k = 0; k < K; ++k) max_slice_fr = std::max(max_slice_fr, foff[k + 1] - foff[k]);
-    /* meta: the slices' offsets | lengths rows, then per slice the prefix sums of the capacities (nact + 1); ints: per slice the
-     * counts, then first_out per utterance; ceps: slice k's block starts at row foff[k] */
+    /* meta: the slices' offsets | lengths rows, then per slice the prefix sums of the capacities (nact + 1); ints: per piece the
+     * count, then first_out per utterance; ceps: slice k's block starts at row foff[k] */
+    const long long max_slice_fr = slice_max_frames(p);
     const size_t n_act = p.mbase[K] / 2;
     auto cum_base = [&](int k) { return p.mbase[K] + p.mbase[k] / 2 + (size_t)k; };
     HIP_TRY(w.in.ensure((size_t)(total_fr * kIn)));
@@ -1371,105 +1207,53 @@ static int denoise_ceps_slices(const char *who, const short *const *in, short *c
         HIP_TRY(w.wb_rows.ensure_device(12 * ((size_t)max_slice_fr + 1)));
         HIP_TRY(w.ensure_inter((size_t)sea_wb_scratch_bytes(max_slice_fr * kIn, n_utt)));
     }
-    const std::vector<std::vector<long long>> bpre = fill_slice_rows(p, kIn, false, w.meta.h);
     for (int k = 0; k < K; ++k) {
-        const int n = p.nact[k];
-        const long long *offs = w.meta.h + p.mbase[k];
         long long *cc = w.meta.h + cum_base(k);
-        for (int j = 0; j < n; ++j) cc[j] = offs[j] / kIn;
-        cc[n] = foff[k + 1] - foff[k];
+        cc[0] = 0;
+        for (int j = 0; j < p.nact[k]; ++j) cc[j + 1] = cc[j] + slice_piece_frames(p, k, j);
     }
-
-    std::vector<Latch> packed(K);
-    std::vector<long long> pos(n_utt, 0);             /* rows of sorted position j in the slices before next_cut */
-    std::vector<std::vector<long long>> start(K);     /* per slice: where each of its utterances' rows go */
-    std::vector<char> arrived(K, 0);                  /* slice k's rows and counts are on the host */
-    int next_cut = 0;                                 /* the first slice whose copy tasks are not cut yet */
-    Scope scope(&w);
-    short *h_in = w.in.h, *h_out = w.out.h;
+    short *h_out = w.out.h;
     float *h_ceps = w.ceps.h;
     const int *h_cnt = w.ints.h;
     int *d_first = w.ints.d + n_act;
     float *d_hp = WB ? w.wb_rows.d : nullptr, *d_code = WB ? w.wb_rows.d + 3 * ((size_t)max_slice_fr + 1) : nullptr;
-    const int *ix = p.idx.data();
-    for (int k = 0; k < K; ++k) {
-        const long long *offs = w.meta.h + p.mbase[k], *lens = offs + p.nact[k];
-        const long long b0 = kIn * p.B[k], s0 = kIn * foff[k];
-        run_copies(pool, 0, p.nact[k], bpre[k].data(), &packed[k], &scope.all, small,
-                   [=](int j) { copy_stream(h_in + s0 + offs[j], in[ix[j]] + b0, (size_t)lens[j] * sizeof(short)); });
-    }
-    hipStream_t sUp = w.stream[0], sKern = w.stream[1], sDown = w.stream[2];
-    HIP_TRY(hipMemcpyAsync(w.meta.d, w.meta.h, cum_base(K) * sizeof(long long), hipMemcpyHostToDevice, sUp));
 
-    const int rc = run_pipeline(
-        w, scope, packed, WB ? "wideband cepstrum slice" : "cepstrum slice", true,
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            const int n = p.nact[k];
-            HIP_TRY(hipMemcpyAsync(w.in.d + kIn * f0, h_in + kIn * f0, (size_t)(fr * kIn) * sizeof(short), hipMemcpyHostToDevice, sUp));
-            HIP_TRY(hipEventRecord(w.ev_h2d[k], sUp));
-            HIP_TRY(hipStreamWaitEvent(sKern, w.ev_h2d[k], 0));
-            const long long *d_rows = w.meta.d + p.mbase[k], *d_cc = w.meta.d + cum_base(k);
-            float *d_blk = w.ceps.d + SEA_CC_NCEP * f0;
-            int *d_cnt = w.ints.d + p.mbase[k] / 2;
-            if (WB) {
-                if (sea_wb_denoise_batch_slice(w.in.d + kIn * f0, w.out.d + kOut * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
-                                               nullptr, d_hp, d_code, (float *)w.inter.d, fr * kIn, w.state.d, n, (int)p.B[k], k > 0,
-                                               sKern))
+    return run_slices(
+        w, pool, p, WB ? "wideband cepstrum slice" : "cepstrum slice", in, kIn, kOut, out != nullptr, false, small, cum_base(K), h_cnt,
+        n_ceps,
+        [&](const SliceView &v) {
+            const long long *d_rows = v.d_rows, *d_cc = w.meta.d + cum_base(v.k);
+            const int n = v.n;
+            const short *d_in = w.in.d + kIn * v.f0;
+            short *d_out = w.out.d + kOut * v.f0;
+            float *d_blk = w.ceps.d + SEA_CC_NCEP * v.f0;
+            int *d_cnt = w.ints.d + v.i0;
+            if constexpr (WB) {
+                if (sea_wb_denoise_batch_slice(d_in, d_out, w.f32.d, d_rows, d_rows + n, nullptr, d_first, nullptr, d_hp, d_code,
+                                               (float *)w.inter.d, v.fr * kIn, w.state.d, n, v.frame_base, v.resume, v.sKern))
                     return 1;
-                if (sea_wb_compceps_batch_slice(w.f32.d, d_rows, d_rows + n, d_first, d_hp, d_code, d_cc, fr, d_blk, d_cnt,
-                                                w.afe_state.d, n, (int)p.B[k], k > 0, sKern))
-                    return 1;
+                return sea_wb_compceps_batch_slice(w.f32.d, d_rows, d_rows + n, d_first, d_hp, d_code, d_cc, v.fr, d_blk, d_cnt,
+                                                   w.afe_state.d, n, v.frame_base, v.resume, v.sKern);
             } else {
-                if (sea_ns_denoise_batch_slice(w.in.d + kIn * f0, w.out.d + kOut * f0, w.f32.d, d_rows, d_rows + n, nullptr, d_first,
-                                               w.state.d, n, (int)p.B[k], k > 0, sKern))
+                if (sea_ns_denoise_batch_slice(d_in, d_out, w.f32.d, d_rows, d_rows + n, nullptr, d_first, w.state.d, n, v.frame_base,
+                                               v.resume, v.sKern))
                     return 1;
-                if (sea_compceps_batch_slice(w.f32.d, d_rows, d_rows + n, d_first, d_cc, fr, d_blk, d_cnt, w.afe_state.d, n,
-                                             (int)p.B[k], k > 0, sKern))
-                    return 1;
+                return sea_compceps_batch_slice(w.f32.d, d_rows, d_rows + n, d_first, d_cc, v.fr, d_blk, d_cnt, w.afe_state.d, n,
+                                                v.frame_base, v.resume, v.sKern);
             }
-            HIP_TRY(hipEventRecord(w.ev_kernel[k], sKern));
+        },
+        [&](const SliceView &v) {
+            HIP_TRY(hipMemcpyAsync(h_ceps + SEA_CC_NCEP * v.f0, w.ceps.d + SEA_CC_NCEP * v.f0, (size_t)v.fr * SEA_CC_NCEP * sizeof(float),
+                                   hipMemcpyDeviceToHost, v.sDown));
+            HIP_TRY(hipMemcpyAsync(w.ints.h + v.i0, w.ints.d + v.i0, (size_t)v.n * sizeof(int), hipMemcpyDeviceToHost, v.sDown));
             return 0;
         },
-        [&](int k) {
-            const long long f0 = foff[k], fr = foff[k + 1] - f0;
-            if (out)
-                HIP_TRY(hipMemcpyAsync(h_out + kOut * f0, w.out.d + kOut * f0, (size_t)(fr * kOut) * sizeof(short), hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipMemcpyAsync(h_ceps + SEA_CC_NCEP * f0, w.ceps.d + SEA_CC_NCEP * f0, (size_t)fr * SEA_CC_NCEP * sizeof(float),
-                                   hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipMemcpyAsync(w.ints.h + p.mbase[k] / 2, w.ints.d + p.mbase[k] / 2, (size_t)p.nact[k] * sizeof(int),
-                                   hipMemcpyDeviceToHost, sDown));
-            HIP_TRY(hipEventRecord(w.ev_done[k], sDown));
-            return 0;
-        },
-        [&](int arrived_k) {
-            arrived[arrived_k] = 1;
-            for (; next_cut < K && arrived[next_cut]; ++next_cut) { /* in slice order, whatever order the slices arrive in */
-                const int k = next_cut, n = p.nact[k];
-                const long long *offs = w.meta.h + p.mbase[k], *lens = offs + n;
-                const int *cnt = h_cnt + p.mbase[k] / 2;
-                start[k].resize(n);
-                for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
-                    start[k][j] = pos[j];
-                    pos[j] += cnt[j];
-                }
-                const long long *st = start[k].data();
-                const long long bk = p.B[k], fk = foff[k];
-                run_copies(pool, 0, n, bpre[k].data(), nullptr, &scope.all, small, [=](int j) {
-                    const long long f0 = offs[j] / kIn, nfr = lens[j] / kIn; /* the piece's first frame in the slice, its frames */
-                    const int u = ix[j];
-                    if (out && out[u]) /* whole frames only: the trailing partial frame stays untouched, as with etsi_denoise */
-                        copy_stream(out[u] + kOut * bk, h_out + kOut * (fk + f0), (size_t)(nfr * kOut) * sizeof(short));
-                    if (cnt[j] > 0)
-                        copy_stream(ceps[u] + SEA_CC_NCEP * st[j], h_ceps + SEA_CC_NCEP * (fk + f0),
-                                    (size_t)cnt[j] * SEA_CC_NCEP * sizeof(float));
-                });
-            }
+        [=](const SlicePiece &c) {
+            if (out && out[c.u]) /* whole frames only: the trailing partial frame stays untouched, as with etsi_denoise */
+                copy_stream(out[c.u] + kOut * c.b, h_out + kOut * c.f0, (size_t)(c.n * kOut) * sizeof(short));
+            if (h_cnt[c.i] > 0)
+                copy_stream(ceps[c.u] + SEA_CC_NCEP * c.start, h_ceps + SEA_CC_NCEP * c.f0, (size_t)h_cnt[c.i] * SEA_CC_NCEP * sizeof(float));
         });
-    if (rc) return rc;
-    for (int j = 0; j < n_utt; ++j) /* every slice has arrived, so every slice is cut: pos is the utterance's total */
-        n_ceps[ix[j]] = (int)pos[j];
-    return 0;
 }
 extern "C" {
 

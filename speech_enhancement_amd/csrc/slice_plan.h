@@ -1,6 +1,7 @@
 /*
- * slice_plan.h -- how the host pipelines cut a list of utterances along the TIME axis (hostpipe.hip: sea_denoise_utterances,
- * sea_wb_denoise_utterances, sea_packed_plan).  Integer arithmetic only, no HIP: tests/slice_plan_driver.cpp runs it on a CPU.
+ * slice_plan.h -- how the host pipelines cut a list of utterances along the TIME axis (hostpipe.hip: run_slices and
+ * sea_packed_plan), and where the rows a slice emits go in the caller's arrays (RowOrder).  Integer arithmetic only, no HIP:
+ * tests/slice_plan_driver.cpp runs it on a CPU.
  *
  * The utterances are sorted longest first (stable), utterance idx[j] at position j with nfr[j] = length / hop whole frames.
  * Slice k holds the frames [B[k], B[k+1]) of every utterance that has them: the first nact[k] positions.  The boundaries give
@@ -82,6 +83,17 @@ inline void slice_plan(SlicePlan &p, const long *lengths, int n_utt, long long h
     }
 }
 
+/* frames of sorted position j in slice k (j < nact[k]) */
+inline long long slice_piece_frames(const SlicePlan &p, int k, int j) { return std::min(p.nfr[j], p.B[k + 1]) - p.B[k]; }
+
+/* frames of the largest slice: what a device buffer that holds one slice at a time is sized for */
+inline long long slice_max_frames(const SlicePlan &p)
+{
+    long long m = 0;
+    for (int k = 0; k < p.K; ++k) m = std::max(m, p.foff[k + 1] - p.foff[k]);
+    return m;
+}
+
 /* Slice k as the kernels read it: rows[0 .. nact) the pieces' offsets, rows[nact .. 2 nact) their lengths, both in samples of
  * `hop` per frame.  Offsets count from the start of the staging (absolute: one batch, launched slice by slice) or from the
  * start of the slice (a batch of its own).  bytes_prefix, where given, receives nact + 1 running sums of the pieces' int16
@@ -92,12 +104,49 @@ inline void slice_rows(const SlicePlan &p, int k, long long hop, bool absolute, 
     long long o = absolute ? hop * p.foff[k] : 0;
     if (bytes_prefix) bytes_prefix[0] = 0;
     for (int j = 0; j < n; ++j) {
-        const long long L = hop * (std::min(p.nfr[j], p.B[k + 1]) - p.B[k]);
+        const long long L = hop * slice_piece_frames(p, k, j);
         rows[j] = o;
         rows[n + j] = L;
         o += L;
         if (bytes_prefix) bytes_prefix[j + 1] = bytes_prefix[j] + 2 * L;
     }
 }
+
+/* Where the rows that the slices emit go in the caller's per-utterance arrays.  A pipeline whose slices emit a number of rows
+ * per utterance that only the device knows (feature rows, cepstral rows) places an utterance's rows of slice k behind those of
+ * its earlier slices, so where they go is known once the counts of slices 0 .. k - 1 are on the host.  The event loop that
+ * brings them there (hostpipe.hip: run_pipeline) promises no order among the slices: one pass of it may find slice k's kernel
+ * or download event "not ready" and slice k + 1's done, so both the download and the unpacking of slice k + 1 may come before
+ * slice k's.  arrive (k) therefore only notes that slice k is on the host; the slices are CUT -- their start rows fixed, their
+ * copy tasks handed out -- strictly in slice order, each as soon as it and every slice before it have arrived, from a running
+ * sum that by then holds exactly the earlier slices' counts.  The copy tasks need no order among themselves.
+ * start[k] is what those tasks read: it is written once, when slice k is cut, and must outlive them. */
+struct RowOrder {
+    std::vector<long long> pos;                /* rows of sorted position j in the slices before next_cut */
+    std::vector<std::vector<long long>> start; /* per cut slice: where each of its utterances' rows go */
+    std::vector<char> arrived;                 /* slice k's rows and counts are on the host */
+    int next_cut = 0;                          /* the first slice that is not cut yet */
+
+    RowOrder(int K, int n_utt) : pos(n_utt, 0), start(K), arrived(K, 0) {}
+
+    /* Slice arrived_k is on the host; counts holds the rows every piece emitted, slice k's nact[k] at counts + mbase[k] / 2.
+     * Calls cut(k, start[k].data()) for every slice that can be cut now, in slice order.  Once every slice has arrived, pos[j]
+     * is the total of sorted position j. */
+    template <class Cut>
+    void arrive(const SlicePlan &p, int arrived_k, const int *counts, Cut cut)
+    {
+        arrived[arrived_k] = 1;
+        for (; next_cut < p.K && arrived[next_cut]; ++next_cut) {
+            const int k = next_cut, n = p.nact[k];
+            const int *cnt = counts + p.mbase[k] / 2;
+            start[k].resize(n);
+            for (int j = 0; j < n; ++j) { /* pos: the counts of slices 0 .. k - 1, all arrived */
+                start[k][j] = pos[j];
+                pos[j] += cnt[j];
+            }
+            cut(k, start[k].data());
+        }
+    }
+};
 
 } // namespace sea_capi

@@ -444,10 +444,14 @@ def test_packed_pinned_entry_points(oracle, monkeypatch):
 
 
 def test_host_pipeline_returns_fault_on_event_error(oracle, monkeypatch):
-    """The three event-driven pipelines of csrc/hostpipe.hip poll hipEventQuery; any answer other than "done" / "not
-    ready" must end the call with the reference's fault code 1 (etsi/cpp/AdvFrontEnd.c:205-209) -- not be polled for
-    ever -- with the pool idle and the streams drained, and the next call must work.  sea_selftest_hostpipe_fault makes
-    the nth query of the process report a device fault."""
+    """The event-driven pipelines of csrc/hostpipe.hip -- the time-slice driver behind sea_denoise_utterances, the feature
+    chains and the cepstrum pipelines, and the two chunk pipelines (SEA_HOST_MODE=chunks, sea_resynth_utterances) -- poll
+    hipEventQuery; any answer other than "done" / "not ready" must end the call with the reference's fault code 1
+    (etsi/cpp/AdvFrontEnd.c:205-209) -- not be polled for ever -- with the pool idle and the streams drained, and the next
+    call must work.  sea_selftest_hostpipe_fault makes the nth query of the process report a device fault.  The time-slice
+    driver is entered through three of its entry points: plain audio, rows of a feature chain with the audio requested, and
+    wideband cepstral rows; the latter two place rows through pool tasks that read the driver's own arrays, so their early
+    exit is the one that must wait for the pool."""
     import ctypes
     import speech_enhancement_amd as sea
     from speech_enhancement_amd import corpus
@@ -471,10 +475,33 @@ def test_host_pipeline_returns_fault_on_event_error(oracle, monkeypatch):
         po = (ctypes.c_void_p * n)(*[y.ctypes.data for y in outs])
         return lib.sea_resynth_utterances(pin, pl, pm, 0, po, n), outs
 
+    def features():                                        # sea_features_utterances with the audio requested
+        outs = [np.zeros_like(x) for x in utts]
+        rows = [np.zeros((L // 80 + 6, 15), np.float32) for L in lens]
+        po, pr = (ctypes.c_void_p * n)(*[y.ctypes.data for y in outs]), (ctypes.c_void_p * n)(*[r.ctypes.data for r in rows])
+        cnt = (ctypes.c_int * n)()
+        return lib.sea_features_utterances(pin, po, pr, cnt, pl, n), (outs, rows, list(cnt))
+
+    def wb_ceps():                                         # sea_wb_denoise_ceps_utterances: the same samples read as 16 kHz
+        outs = [np.zeros(L // 160 * 80, np.int16) for L in lens]
+        rows = [np.zeros((L // 160 - 6, 14), np.float32) for L in lens]
+        po, pr = (ctypes.c_void_p * n)(*[y.ctypes.data for y in outs]), (ctypes.c_void_p * n)(*[r.ctypes.data for r in rows])
+        cnt = (ctypes.c_int * n)()
+        return lib.sea_wb_denoise_ceps_utterances(pin, po, pr, cnt, pl, n), (outs, rows, list(cnt))
+
+    def same(a, b):                                        # audio, emitted rows (bits) and counts of two calls
+        return (a[2] == b[2] and all(np.array_equal(x, y) for x, y in zip(a[0], b[0]))
+                and all(np.array_equal(x[:k].view(np.uint32), y[:k].view(np.uint32)) for x, y, k in zip(a[1], b[1], a[2])))
+
     rc, good = denoise()
     assert rc == 0, lib.sea_last_error()
     rc, good_rs = resynth()
     assert rc == 0, lib.sea_last_error()
+    good_rows = {}
+    for call in (features, wb_ceps):                       # 16.7k frames of 80 samples, 8.3k of 160: both lists are cut
+        rc, good_rows[call] = call()
+        assert rc == 0, lib.sea_last_error()
+        assert lib.sea_host_last_slices() > 1 and sum(good_rows[call][2]) > 0
     try:
         for mode in (None, "chunks"):
             if mode:
@@ -496,6 +523,17 @@ def test_host_pipeline_returns_fault_on_event_error(oracle, monkeypatch):
         rc, outs = resynth()
         assert rc == 0, lib.sea_last_error()
         assert all(np.array_equal(a, b) for a, b in zip(outs, good_rs))
+        for call in (features, wb_ceps):
+            for nth in (1, 3, 9):
+                lib.sea_selftest_hostpipe_fault(nth)
+                rc, _ = call()
+                assert rc == 1, f"{call.__name__}: fault at query {nth} was not reported"
+                assert b"event" in lib.sea_last_error()
+                lib.sea_selftest_hostpipe_fault(0)
+                rc, res = call()
+                assert rc == 0, lib.sea_last_error()
+                assert lib.sea_host_last_slices() > 1, f"{call.__name__}: the list was not cut"
+                assert same(res, good_rows[call]), f"{call.__name__}: the call after a fault differs"
     finally:
         lib.sea_selftest_hostpipe_fault(0)
 

@@ -6,7 +6,10 @@ restatement of the rule (a linear scan for each boundary where the header bisect
 The rule: utterances sorted longest first (stable), nfr = length // hop; want = min(want, 64, max(1, max_fr // 8)); B[k] is
 the smallest f > B[k-1] with sum_j min(nfr[j], f) >= total_fr * k // want, boundaries stop at the first such f >= max_fr,
 and the last one is max_fr; slice k holds frames [B[k], B[k+1]) of the first nact[k] sorted utterances, those with
-nfr > B[k]."""
+nfr > B[k].
+
+The driver's second command runs RowOrder, the in-order placement of the rows the slices of a pipeline emit: whatever order the
+slices arrive in, slice k is cut once it and every slice before it have arrived, its rows start behind the earlier slices'."""
 import os
 import shutil
 import subprocess
@@ -158,3 +161,71 @@ def test_slice_plan_named_cases(driver):
     assert seven["K"] == [1] and seven["B"] == [0, 7]
     assert capped["K"] == [64] and len(capped["B"]) == 65
     assert equal["K"] == [10] and equal["nact"] == [50] * 10
+
+
+def _order_lists(hop):
+    """name -> (lengths in samples, slice count asked for, K the plan must come to)"""
+    r5 = np.random.default_rng(5)
+    return {
+        "one slice": ([50 * hop, 20 * hop + 3, 0, 9 * hop], 1, 1),
+        "two slices": ([50 * hop, 20 * hop + 3, 0, 9 * hop, hop - 1, 50 * hop], 2, 2),
+        "five slices": ([int(v) for v in r5.integers(0, 400 * hop, 30)] + [0, hop, 400 * hop], 5, 5),
+        "64 slices": ([1000 * hop, 900 * hop + 1, 600 * hop, 40 * hop, 0, 3 * hop], 100, 64),
+    }
+
+
+def _arrival_orders(K, rng):
+    ident = list(range(K))
+    pairs = [k ^ 1 if (k ^ 1) < K else k for k in ident]                      # k + 1 before k, for every even k
+    return [ident, ident[::-1], pairs] + [[int(v) for v in rng.permutation(K)] for _ in range(3)]
+
+
+def test_row_order_cuts_in_slice_order_whatever_arrives_first(driver):
+    rng = np.random.default_rng(31)
+    cases = []
+    for hop in (80, 160):
+        for name, (lengths, want, K) in _order_lists(hop).items():
+            plan = _restate(lengths, hop, want)
+            assert plan["K"] == [K], f"{name}: the list was meant to give {K} slices"
+            nact, B, nfr = plan["nact"], plan["B"], plan["nfr"]
+            for arrival in _arrival_orders(K, rng):
+                # rows emitted per slice and sorted position: anything from none to the piece's frames + the 6 rows of a flush
+                cnt = np.zeros((K, len(lengths)), np.int64)
+                for k in range(K):
+                    frames = np.array([min(nfr[j], B[k + 1]) - B[k] for j in range(nact[k])])
+                    c = rng.integers(0, frames + 7)
+                    c[rng.random(nact[k]) < 0.2] = 0
+                    top = rng.random(nact[k]) < 0.2
+                    c[top] = frames[top] + 6
+                    cnt[k, :nact[k]] = c
+                cases.append((f"{name}, hop {hop}, arrival {arrival[:8]}", lengths, hop, want, nact, arrival, cnt))
+    stdin = "".join(f"{hop} {want} {len(lengths)} {' '.join(map(str, lengths))} {' '.join(map(str, arrival))} "
+                    f"{' '.join(str(int(v)) for k in range(len(nact)) for v in cnt[k, :nact[k]])}\n"
+                    for _, lengths, hop, want, nact, arrival, cnt in cases)
+    run = subprocess.run([driver, "order"], input=stdin, capture_output=True, text=True, timeout=120)
+    assert run.returncode == 0 and not run.stderr, f"driver (sanitizers on) exited with {run.returncode}:\n{run.stderr[-2000:]}"
+    blocks = [b.split("\n") for b in run.stdout.split("case\n")[1:]]
+    assert len(blocks) == len(cases)
+    for (what, lengths, hop, want, nact, arrival, cnt), lines in zip(cases, blocks):
+        K = len(nact)
+        want_start = np.cumsum(cnt, axis=0) - cnt                             # the sum of cnt[k'][j] over k' < k
+        want_pos = cnt.sum(axis=0)                                            # ... over all k
+        arrived, cut, start, pos = [], [], {}, None
+        for tok in (ln.split() for ln in lines if ln):
+            if tok[0] == "arrive":
+                arrived.append(int(tok[1]))
+            elif tok[0] == "cut":
+                k = int(tok[1])
+                assert set(range(k + 1)) <= set(arrived), f"{what}: slice {k} was cut with only {arrived} on the host"
+                assert not set(range(k + 1)) <= set(arrived[:-1]), f"{what}: slice {k} could have been cut an arrival earlier"
+                cut.append(k)
+            elif tok[0] == "start":
+                start[int(tok[1])] = [int(v) for v in tok[2:]]
+            elif tok[0] == "pos":
+                pos = [int(v) for v in tok[1:]]
+        assert arrived == arrival
+        assert cut == list(range(K)), f"{what}: cut in the order {cut}"
+        assert list(start) == cut
+        for k in range(K):
+            assert start[k] == [int(v) for v in want_start[k, :nact[k]]], f"{what}: start rows of slice {k}"
+        assert pos == [int(v) for v in want_pos], f"{what}: totals"
