@@ -658,6 +658,11 @@ int sea_selftest_log(const float *x, double *ln_out, int n);
 int sea_selftest_log_dd(const double *x, double *hi, double *lo, int n);
 int sea_selftest_log_sites(const float *x, float *site1, float *site2, int n);
 int sea_selftest_log_guard(int site, unsigned long long *stats8, float *hits3, int cap);
+/* the same three logarithm forms as the kernels that take the caller's floats instantiate them (sea_ns_stream_push, sea_ns_streams_push,
+ * sea_ns_streams_push_fd, sea_ns16k_streams_push, sea_compceps_frames): the exponent field is tested first, +Inf gives +Inf, a NaN
+ * (and -Inf) gives NaN, as libm's log does; every other argument goes the way of sea_selftest_log_sites.  n floats of any bit
+ * pattern (host pointers): site1 / site2 as in sea_selftest_log_sites without its range selection, logf = (float)log((double)x) */
+int sea_selftest_log_nonfinite(const float *x, float *site1, float *site2, float *logf, int n);
 /* host pipelines (csrc/hostpipe.hip): from the nth hipEventQuery of the process on, every query reports a device fault
  * (0: off).  The pipelines must then return 1 -- the reference's fault code -- instead of polling for ever. */
 int sea_selftest_hostpipe_fault(long long nth_query);

@@ -22,6 +22,40 @@
 
 enum { HOP = 80, WIN = 200, NFFT = 256, NSPEC = 65, NMEL = 25, NBUF = 320, NTAP = 17, HALF = 8 };
 
+/* The four logarithms that see values derived from the input floats (NoiseSup.c:391, :607, CompCeps.c:423, :511).
+ * ORA_LOG / ORA_LOG10 are libm's.  -DORA_BITPATTERN_LOG builds a MUTANT of this restatement (libsea_oracle_bitlog.so,
+ * tests/test_nonfinite_cpu.py only): for an argument that is not finite they decompose the bit pattern of the argument
+ * rounded to float into exponent and mantissa and return e ln 2 + ln m, which is what a table-driven logarithm without
+ * a test of the exponent field does (csrc/ns_core.h, ns_ln, before it got one): 128 ln 2 = 88.72 for +Inf, 89.13 for
+ * the quiet NaN 0x7FC00000 the device generates.  Every finite argument takes the true function.  The tests use the
+ * mutant to show that their inputs tell the two apart. */
+#ifdef ORA_BITPATTERN_LOG
+static double ora_bitpattern_ln(double x)
+{
+    float f = (float)x;
+    unsigned b;
+    int e;
+    double m;
+    if (isfinite(x)) return log(x);
+    memcpy(&b, &f, sizeof b);
+    b &= 0x7fffffffu; /* the device's own NaNs are positive */
+    e = (int)(b >> 23) - 127;
+    b = (b & 0x007fffffu) | 0x3f800000u;
+    memcpy(&f, &b, sizeof f);
+    m = (double)f;
+    if (b > 0x3FB504F2u) { /* m >= sqrt 2: halve it */
+        m *= 0.5;
+        e += 1;
+    }
+    return (double)e * 0.69314718055994530942 + log(m);
+}
+#define ORA_LOG(x) ora_bitpattern_ln(x)
+#define ORA_LOG10(x) (isfinite(x) ? log10(x) : ora_bitpattern_ln(x) * 0.43429448190325182765)
+#else
+#define ORA_LOG(x) log(x)
+#define ORA_LOG10(x) log10(x)
+#endif
+
 /* ------------------------------------------------------------------------------------------
  * rfft: etsi/cpp/rfft.c:45-180.  Restated as an explicit butterfly schedule: a bit-reversal
  * permutation, the length-2 pass, then per split-radix level three kinds of independent
@@ -352,7 +386,7 @@ static void ns_vad(ns_state *s, int st, const float *frame)
     lambdaLTE = (nb < 10) ? 1 - 1 / (float)nb : (float)0.97;
     frameEn = 64.0f;
     for (i = 0; i < HOP; i++) frameEn += frame[i] * frame[i];
-    frameEn = (float)(0.5 + (log(frameEn / 64.0) / log(2.0)) * 16.0);
+    frameEn = (float)(0.5 + (ORA_LOG(frameEn / 64.0) / log(2.0)) * 16.0);
 
     if (((frameEn - meanEn) < (short)20) || (nb < (short)10)) {
         if ((frameEn < meanEn) || (nb < (short)10))
@@ -444,7 +478,7 @@ static void ns_gain_fact(ns_state *s, int st, float *W)
         for (i = 0; i < NSPEC; i++) noiseEn += noise[i];
         averSNR = (s->denEn[0] * s->denEn[1] * s->denEn[2]) / (noiseEn * noiseEn * noiseEn);
         if (averSNR > 0.00001)
-            averSNR = (float)((20 * log10((double)averSNR)) / 3.0);
+            averSNR = (float)((20 * ORA_LOG10((double)averSNR)) / 3.0);
         else
             averSNR = (float)(-100.0 / 3.0);
 
@@ -630,7 +664,7 @@ static void compceps(const float *cur /* cur[-1] valid */, float *coef14)
     if (logE < floorE)
         logE = (float)-50.0;
     else
-        logE = (float)log((double)logE);
+        logE = (float)ORA_LOG((double)logE);
 
     for (i = 0; i < WIN; i++) fb[i] = (float)(cur[i] - 0.90 * cur[i - 1]);
     for (i = 0; i < WIN / 2; i++) fb[i] *= T.hamming[i];
@@ -644,7 +678,7 @@ static void compceps(const float *cur /* cur[-1] valid */, float *coef14)
     fb[NFFT / 2] = (float)((double)fb[NFFT / 2] * fb[NFFT / 2]);
 
     mel_fb(fb, T.ccmel, 23);
-    for (i = 0; i < 23; i++) fb[i] = (fb[i] < floorFB) ? (float)-10.0 : (float)log((double)fb[i]);
+    for (i = 0; i < 23; i++) fb[i] = (fb[i] < floorFB) ? (float)-10.0 : (float)ORA_LOG((double)fb[i]);
 
     /* DCT: CompCeps.c:203-227 */
     for (i = 1; i <= 12; i++) {
@@ -678,6 +712,29 @@ long ora_ns_stream_f32(const float *in, long nframes, float *out, int *produced)
         float y[HOP];
         int ok = ns_step(s, in + f * HOP, y);
         produced[f] = ok ? 1 : 0;
+        if (ok) {
+            memcpy(out + nout * HOP, y, sizeof y);
+            nout++;
+        }
+    }
+    free(s);
+    return nout;
+}
+
+/* the same with the per-frame outputs of the batch plug-in shape (NoiseSupExports.h:19-27) as they stand after each
+ * call: flags[f] = SpeechFoundVar | Spec << 1 | Mel << 2 | VADNS << 3, counter[f] = FrameCounter (ParmInterface.h:85-89) */
+long ora_ns_stream_f32_fd(const float *in, long nframes, float *out, int *produced, int *flags, int *counter)
+{
+    ns_state *s = (ns_state *)malloc(sizeof *s);
+    long f, nout = 0;
+    tables_init();
+    ns_init(s);
+    for (f = 0; f < nframes; f++) {
+        float y[HOP];
+        int ok = ns_step(s, in + f * HOP, y);
+        produced[f] = ok ? 1 : 0;
+        flags[f] = s->speechFoundVar | (s->speechFoundSpec << 1) | (s->speechFoundMel << 2) | (s->speechFoundVADNS << 3);
+        counter[f] = s->frameCounter;
         if (ok) {
             memcpy(out + nout * HOP, y, sizeof y);
             nout++;

@@ -3,6 +3,8 @@
 ctypes front-end for the two checker libraries:
 
   * ``libsea_oracle.so``       the CPU restatement (oracle/ns_oracle.c, oracle/resynth_oracle.c)
+  * ``libsea_oracle_bitlog.so``  a deliberately wrong build of ns_oracle.c (-DORA_BITPATTERN_LOG) that
+                               tests/test_nonfinite_cpu.py must tell apart from the restatement
   * ``_ref/libetsi_ref.so``    the reference's own C (etsi/cpp/*.c) compiled where it lies under
                                /root/reference, plus oracle/ref_driver*.c (only where it was built)
   * ``_ref/libaurora_ref.so``  the two files of the 16 k-native variant that compile on their own
@@ -19,6 +21,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 ORACLE_SO = os.path.join(_HERE, "libsea_oracle.so")
+BITLOG_SO = os.path.join(_HERE, "libsea_oracle_bitlog.so")
 REF_SO = os.path.join(_HERE, "_ref", "libetsi_ref.so")
 AURORA_SO = os.path.join(_HERE, "_ref", "libaurora_ref.so")
 NSCAL = 16
@@ -90,6 +93,17 @@ class _Lib:
         fn.restype = ctypes.c_long
         nout = fn(_ptr(x), ctypes.c_long(x.shape[0]), _ptr(out), _ptr(prod))
         return out[: nout * 80], prod
+
+    def ns_stream_f32_fd(self, frames):
+        """ns_stream_f32 plus, per frame, the flags SpeechFoundVar | Spec << 1 | Mel << 2 | VADNS << 3 and FrameCounter as
+        they stand after the call: (out[nout*80] float32, produced[n], flags[n], counter[n])."""
+        x = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, 80)
+        out = np.zeros(x.size, np.float32)
+        prod, flags, counter = (np.zeros(x.shape[0], np.int32) for _ in range(3))
+        fn = self._f("ns_stream_f32_fd")
+        fn.restype = ctypes.c_long
+        nout = fn(_ptr(x), ctypes.c_long(x.shape[0]), _ptr(out), _ptr(prod), _ptr(flags), _ptr(counter))
+        return out[: nout * 80], prod, flags, counter
 
     def afe_trace(self, x):
         """The full per-frame chain: WaveProc -> CompCeps -> PostProc -> VAD + flush.
@@ -218,6 +232,16 @@ class Oracle(_Lib):
         assert y.size >= 25
         self.lib.ora16_idct(_ptr(y))
         return y[:25]
+
+
+class BitPatternLogMutant(_Lib):
+    """The restatement built with -DORA_BITPATTERN_LOG (oracle/Makefile): a deliberately WRONG build whose logarithms take
+    a non-finite argument apart by its bit pattern.  tests/test_nonfinite_cpu.py only."""
+
+    def __init__(self):
+        if not os.path.exists(BITLOG_SO):
+            build(ref=False)
+        super().__init__(BITLOG_SO, "ora_")
 
 
 class Ns16k:

@@ -130,6 +130,31 @@ long ref_ns_stream_f32(const float *in, long nframes, float *out, int *produced)
     return nout;
 }
 
+/* the same with the flags the frame-dropping VAD reads, as they stand after each call (same contract as ora_ns_stream_f32_fd) */
+long ref_ns_stream_f32_fd(const float *in, long nframes, float *out, int *produced, int *flags, int *counter)
+{
+    FEParamsX *fe = AdvProcessAlloc(8000);
+    long f, nout = 0;
+    int i;
+    AdvProcessInit(fe);
+    for (f = 0; f < nframes; f++) {
+        float cur[80], y[80];
+        int ok;
+        for (i = 0; i < 80; i++) cur[i] = in[f * 80 + i];
+        ok = fe->DoNoiseSup(cur, y, fe);
+        produced[f] = ok ? 1 : 0;
+        flags[f] = (fe->SpeechFoundVar ? 1 : 0) | (fe->SpeechFoundSpec ? 2 : 0) | (fe->SpeechFoundMel ? 4 : 0) |
+                   (fe->SpeechFoundVADNS ? 8 : 0);
+        counter[f] = (int)fe->FrameCounter;
+        if (ok) {
+            for (i = 0; i < 80; i++) out[nout * 80 + i] = y[i];
+            nout++;
+        }
+    }
+    AdvProcessDelete(&fe);
+    return nout;
+}
+
 /*
  * ref_afe_trace -- the per-frame chain the reference author commented out
  * (etsi/cpp/ParmInterface.c:274-311): WaveProc -> CompCeps -> PostProc -> VAD on every NoiseSup

@@ -30,6 +30,8 @@ int ora_etsi_denoise(const short *in, short *out, long n);
 void ora_rfft(float *x, int n, int m);
 /* same contract as ref_ns_trace() in ref_driver.c */
 long ora_ns_stream_f32(const float *in, long nframes, float *out, int *produced);
+/* + per frame: SpeechFoundVar | Spec << 1 | Mel << 2 | VADNS << 3 and FrameCounter as they stand after the call */
+long ora_ns_stream_f32_fd(const float *in, long nframes, float *out, int *produced, int *flags, int *counter);
 long ora_afe_trace(const short *in, long n, int *flags, float *feat_cc, float *feat_pp, float *vad_out,
                    long *counts);
 long ora_ns_trace(const short *in, long n, short *out_i16, float *den_f32, float *ceps,

@@ -1658,6 +1658,26 @@ int sea_selftest_log_sites(const float *x, float *site1, float *site2, int n)
     return 0;
 }
 
+int sea_selftest_log_nonfinite(const float *x, float *site1, float *site2, float *logf, int n)
+{
+    if (n <= 0) return 0;
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    DevBuf<float> dx, d1, d2, d3;
+    HIP_TRY(dx.alloc(n));
+    HIP_TRY(d1.alloc(n));
+    HIP_TRY(d2.alloc(n));
+    HIP_TRY(d3.alloc(n));
+    HIP_TRY(hipMemcpy(dx.p, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(sea::selftest_log_nonfinite_kernel, dim3((n + 255) / 256), dim3(256), 0, nullptr, dx.p, d1.p, d2.p, d3.p, n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(site1, d1.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(site2, d2.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(logf, d3.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 int sea_selftest_log_guard(int site, unsigned long long *stats8, float *hits3, int cap)
 {
     if (site != 1 && site != 2) return fail("selftest_log_guard: site must be 1 or 2");

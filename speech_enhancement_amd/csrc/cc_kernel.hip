@@ -185,7 +185,7 @@ __global__ __launch_bounds__(64) void compceps_frames_kernel(const float *data20
             }
         }
         wave_sync();
-        cc_tile<false>(L, C, nv, coef14 + f0 * SEA_CC_NCEP, lane);
+        cc_tile<false, kCcT, false, true>(L, C, nv, coef14 + f0 * SEA_CC_NCEP, lane); /* the caller's floats: NF */
     }
 }
 

@@ -31,7 +31,8 @@ constexpr int kCcT = 16; /* frames per tile of compceps_kernel (afe_ceps_kernel:
 
 /* (float)log((double)v) for a positive normal float v, as CompCeps.c:423 / :511 take it.  The library's double log
  * costs ~150 instructions; the kernels' own table-driven one with its rounding-boundary guard (ns_core.h, ns_logf) */
-__device__ __forceinline__ float cc_logf(float v) { return ns_logf(v); }
+template <bool NF = false> /* NF: the frames are the caller's floats (compceps_frames_kernel): Inf and NaN as libm gives them */
+__device__ __forceinline__ float cc_logf(float v) { return ns_logf<NF>(v); }
 
 template <bool SHARED, int T = kCcT>
 struct CcGeom {
@@ -130,7 +131,7 @@ struct __attribute__((aligned(16))) CcWbLds {
  * frame's rows of high-band energies (after the spectral subtraction) and code values: cepstral frame j of an utterance is
  * computed after NoiseSup output j + 2 and reads the heads of the three-deep queues hpBands / bufferCodeForBands16k, the
  * entries of output j (NoiseSup.c:1418-1428).  logE is taken after CorrectEnergy, not before. */
-template <bool SHARED, int T = kCcT, bool WB = false>
+template <bool SHARED, int T = kCcT, bool WB = false, bool NF = false /* see cc_logf */>
 __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileConst &C, int nv, float *dst, int lane,
                                         CcWbLds *X = nullptr, const float *hpRows = nullptr, const float *codeRows = nullptr,
                                         const sea_wb_tables *wbt = nullptr)
@@ -156,7 +157,7 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
             }
         }
         if (WB) logE = acc;
-        else logE = (acc < C.floorE) ? (float)-50.0 : cc_logf(acc);
+        else logE = (acc < C.floorE) ? (float)-50.0 : cc_logf<NF>(acc); /* a NaN goes INTO the log, as in the reference */
     }
     CC_CK(1);
     const int npair = (nv + 1) >> 1;
@@ -179,6 +180,7 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
         /* the transform's last level stays in registers: every lane holds four complete bins of its frame (one lane per frame
          * five), whose power -- products and sum in double (:451-459) -- goes straight to the frame's row */
         float o[8];
+        bool nfPower = false;
         rfft256_dual_keep_last<false>(e, L.work, C.fft, o);
         {
             const bool pl = C.pairLane;
@@ -190,7 +192,12 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
             rowCD[0] = power(o[4], ic);   /* bin 64 - j | 32 */
             rowCD[64] = power(o[5], id);  /* bin 128 - j | 96 */
             if (pl) rowAB[128] = power(o[2], 0.0f); /* bin 128 */
+            if constexpr (NF) /* (a separate statement: the lines above compile as they did without it) */
+                nfPower = ns_nonfinite(power(o[0], ia)) || ns_nonfinite(power(o[1], ib)) || ns_nonfinite(power(o[4], ic)) ||
+                          ns_nonfinite(power(o[5], id)) || (pl && ns_nonfinite(power(o[2], 0.0f)));
         }
+        /* NF (the caller's floats): a power of this pair of frames is Inf or NaN (wave-uniform) */
+        const bool skipZeroTaps = NF && __ballot(nfPower) != 0ull;
         wave_sync();
         if (WB && lane < 6) { /* GetBandsForDecoding16k (16kHzProcessing.c:317-336) from the power spectrum, before the mel pass */
             const int hh = lane / 3, b = lane - 3 * hh;
@@ -207,11 +214,23 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
         if (C.melFb >= 0 && 2 * pr + (C.melFb >= 24 ? 1 : 0) < nv) {
             const float2 *q = reinterpret_cast<const float2 *>(&L.pw[0][0] + C.melBase);
             float acc = 0.0f;
+            if (NF && skipZeroTaps) {
+                /* Inf * 0 must not reach a band from a tap in front of or behind it, as it does not in the reference's loop over
+                 * the band's own length: zero-weight taps are skipped (none lies INSIDE a band: sea_tables.c refuses such a table) */
 #pragma unroll
-            for (int i = 0; i < SEA_CC_TAPS2 / 2; ++i) {
-                const float2 v = q[i];
-                acc = acc + v.x * C.melW[2 * i];
-                acc = acc + v.y * C.melW[2 * i + 1];
+                for (int i = 0; i < SEA_CC_TAPS2 / 2; ++i) {
+                    const float2 v = q[i];
+                    const float w0 = C.melW[2 * i], w1 = C.melW[2 * i + 1];
+                    acc = (w0 == 0.0f) ? acc : acc + v.x * w0;
+                    acc = (w1 == 0.0f) ? acc : acc + v.y * w1;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < SEA_CC_TAPS2 / 2; ++i) {
+                    const float2 v = q[i];
+                    acc = acc + v.x * C.melW[2 * i];
+                    acc = acc + v.y * C.melW[2 * i + 1];
+                }
             }
             (&L.fb[2 * pr][0])[C.melFb] = acc;
         }
@@ -222,7 +241,7 @@ __device__ __forceinline__ void cc_tile(CcTileLds<SHARED, T> &L, const CcTileCon
     for (int idx = lane; idx < nv * SEA_CC_NCHAN; idx += kLanes) {
         const int f = idx / SEA_CC_NCHAN, b = idx - f * SEA_CC_NCHAN;
         const float v = L.fb[f][b];
-        L.fb[f][b] = (v < C.floorFB) ? (float)-10.0 : cc_logf(v);
+        L.fb[f][b] = (v < C.floorFB) ? (float)-10.0 : cc_logf<NF>(v);
     }
     wave_sync();
     CC_CK(3);

@@ -405,7 +405,7 @@ __device__ __forceinline__ void back16(StreamLds &L, const Tab &T, const float *
     /* DoGainFact_IBM (:634-698) */
     float g = L.gam[ST][(lane < SEA16_NGAM) ? lane : 0];
     if (ST == 1) {
-        gain_fact_update(s, total); /* the caller has loaded s.denEn0..2 */
+        gain_fact_update<true>(s, total); /* the caller has loaded s.denEn0..2; <true>: the caller's floats (ns_core.h, ns_ln) */
         g = (float)((double)(s.alfaGF * g) + (1.0 - (double)s.alfaGF) * 1.0);
         gainOut = g;
         wave_sync();
@@ -793,7 +793,7 @@ __global__ void __launch_bounds__(256 * p16::kStreams, 4) ns16k_pipe_kernel(Ns16
                 const float *fr = L.circ[0] + (tk & (kSlots - 1)) * kHop;
                 float acc = 64.0f;
                 for (int n = 0; n < kHop; ++n) acc += fr[n] * fr[n];
-                const float accEn = vad_frame_energy(acc);
+                const float accEn = vad_frame_energy<true>(acc);
                 if (lane == 0) L.frameEn[tk & (kSlots - 1)] = accEn;
             }
             wave_sync();
@@ -876,7 +876,7 @@ __global__ void __launch_bounds__(256 * p16::kStreams, 4) ns16k_pipe_kernel(Ns16
                         valid = 1;
                         tick++;
                         slot_store3(L.circ[0], tick, lane, x);
-                        const float vadEn = vad_frame_energy(vadSum);
+                        const float vadEn = vad_frame_energy<true>(vadSum); /* the sum may be Inf or NaN: the exponent field is tested */
                         if (lane == 0) L.frameEn[tick & (kSlots - 1)] = vadEn;
                     }
                     if (lane == 0) {

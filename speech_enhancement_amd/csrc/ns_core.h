@@ -112,7 +112,21 @@ __device__ __forceinline__ float uniform_f(float v)
  * around 1 has c = 1, th = tl = 0, so ln x keeps its relative accuracy where it vanishes.  Truncation r^7/7 is below
  * 2^-56 of r; measured against 40-digit references by test_selftest_log_accuracy, and both complete call sites are
  * swept over every float argument against the double-double slow path by sea_selftest_log_guard.
- * The argument must be a positive normal FLOAT (as a double). */
+ * The argument must be a positive normal FLOAT (as a double).
+ *
+ * Outside that domain ns_ln still returns a finite number: it reads exponent and mantissa from the bit pattern, so +Inf
+ * gives 128 ln 2 = 88.72 and the quiet NaN 0x7FC00000 gives 89.13 where libm gives Inf and NaN.  idx itself is 0..255
+ * for all 2^32 patterns (mb is forced into [0x3F800000, 0x3FFFFFFF], halved above 0x3FB504F2 into [0x3F3504F3, 0x3F7FFFFF]:
+ * mb - 0x3F3504F3 is in [0, 0x7FFFFF], >> 15 in [0, 255]), so no argument reads outside the table.  Kernels that take
+ * floats from the caller (ns_stream_kernel, ns_stream_fd_kernel, ns16k_pipe_kernel, compceps_frames_kernel) can be handed
+ * Inf, NaN, or finite floats whose energy overflows: they instantiate the three entry forms below (ns_vad_energy_expr,
+ * ns_aversnr_expr, ns_logf) with NF = true, which test the exponent field -- one integer compare per logarithm, beside the
+ * chain, and one select behind it -- and return what the reference's literal expression gives (ns_log_nonfinite).  The int16-intake kernels cannot produce
+ * such an argument (64 + 80 * 32768^2 = 2^36.3) and keep NF = false: their code is unchanged. */
+__device__ __forceinline__ bool ns_nonfinite(float v) { return (__float_as_uint(v) & 0x7f800000u) == 0x7f800000u; }
+/* for a float whose exponent field is all ones: (float) of libm's log / log10 of it, and of the expressions
+ * 0.5 + (L / ln 2) * 16 and (20 L) / 3 the two NoiseSup sites round to float: +Inf -> +Inf, NaN -> NaN, -Inf -> NaN */
+__device__ __forceinline__ float ns_log_nonfinite(float v) { return (v > 0.0f) ? v : __uint_as_float(0x7fc00000u); }
 static __device__ const double kNsLogTab[256][3] = {
 #include "ns_logtab.inc"
 };
@@ -257,9 +271,15 @@ __device__ __forceinline__ double ns_ln_cr(double x)
  * float unless the double lands within a few ulps of a float ROUNDING BOUNDARY -- there (probability ~2^-27 per call) the
  * logarithm is redone in double-double arithmetic and rounded once, exactly like the two NoiseSup sites below
  * (window 4 ulps: ours 1.1 + glibc's 0.52, doubled). */
+template <bool NF = false>
 __device__ __forceinline__ float ns_logf(float v)
 {
     const double l = ns_ln<false>((double)v);
+    if constexpr (NF) { /* the exponent-field test runs beside the chain; one select behind it */
+        float r = (float)l;
+        if (__builtin_expect(ns_near_float_boundary(l, 4), 0)) r = (float)ns_ln_cr((double)v);
+        return ns_nonfinite(v) ? ns_log_nonfinite(v) : r;
+    }
     if (__builtin_expect(ns_near_float_boundary(l, 4), 0)) return (float)ns_ln_cr((double)v);
     return (float)l;
 }
@@ -289,12 +309,20 @@ __device__ __forceinline__ float ns_vad_energy_slow(float frameSum)
 {
     return (float)(0.5 + (ns_ln_cr((double)frameSum / 64.0) / kLn2) * 16.0);
 }
-template <bool UNI = false>
+template <bool UNI = false, bool NF = false>
 __device__ __forceinline__ float ns_vad_energy_expr(float frameSum, bool *hit = nullptr)
 { /* NoiseSup.c:391 */
     const double v = __fma_rn(ns_ln<UNI>((double)frameSum * 0.015625), 23.083120654223414 /* 16 / ln 2 */, 0.5);
     const bool near = ns_near_float_boundary(v, 10);
-    if (hit) *hit = near;
+    if (hit) *hit = near && !(NF && ns_nonfinite(frameSum));
+    if constexpr (NF) { /* (float)(0.5 + (log (Inf / 64.0) / log (2.0)) * 16.0) = Inf, NaN stays NaN: the exponent-field test
+                         * runs beside the chain (which only reads bit patterns: no trap, no index outside the table), one select
+                         * behind it.  Measured on the one-wave streaming kernel against a test in front of the chain and against
+                         * the test OR-ed into the guard's branch: this form is the cheapest */
+        float r = (float)v;
+        if (__builtin_expect(near, 0)) r = ns_vad_energy_slow(frameSum);
+        return ns_nonfinite(frameSum) ? ns_log_nonfinite(frameSum) : r;
+    }
     if (__builtin_expect(near, 0)) return ns_vad_energy_slow(frameSum);
     return (float)v;
 }
@@ -302,12 +330,17 @@ __device__ __forceinline__ float ns_aversnr_slow(float averSNR)
 {
     return (float)((20 * ns_log10_slow((double)averSNR)) / 3.0);
 }
-template <bool UNI = false>
+template <bool UNI = false, bool NF = false>
 __device__ __forceinline__ float ns_aversnr_expr(float averSNR, bool *hit = nullptr)
-{ /* NoiseSup.c:607; the caller has established (double)averSNR > 0.00001 */
+{ /* NoiseSup.c:607; the caller has established (double)averSNR > 0.00001 (which keeps a NaN out: only +Inf gets here) */
     const double v = ns_ln<UNI>((double)averSNR) * 2.8952965460216789 /* 20 log10(e) / 3 */;
     const bool near = ns_near_float_boundary(v, 20);
-    if (hit) *hit = near;
+    if (hit) *hit = near && !(NF && ns_nonfinite(averSNR));
+    if constexpr (NF) { /* (float)((20 * log10 (Inf)) / 3.0) = Inf: tested beside the chain, selected behind it */
+        float r = (float)v;
+        if (__builtin_expect(near, 0)) r = ns_aversnr_slow(averSNR);
+        return ns_nonfinite(averSNR) ? ns_log_nonfinite(averSNR) : r;
+    }
     if (__builtin_expect(near, 0)) return ns_aversnr_slow(averSNR);
     return (float)v;
 }
@@ -548,9 +581,10 @@ __device__ __forceinline__ float filter_steady(float P, float nSig, float &noise
 
 /* VAD frame log-energy (NoiseSup.c:386-391) from 64 + sum of the 80 squared samples: depends on
  * the raw frame only, so the pipelined kernel computes it in its helper wave */
+template <bool NF = false> /* NF: the frame is the caller's floats: the sum may be Inf or NaN (see ns_ln) */
 __device__ __forceinline__ float vad_frame_energy(float frameSum)
 {
-    return uniform_f(ns_vad_energy_expr<true>(uniform_f(frameSum)));
+    return uniform_f(ns_vad_energy_expr<true, NF>(uniform_f(frameSum)));
 }
 
 /* squares of the raw frame frame[0..79] -> sq[0..79], then the in-order sum (all lanes) */
@@ -597,11 +631,12 @@ __device__ __forceinline__ void vad_update(NsRegs &s, float frameEn)
 }
 
 /* second-stage gain factorisation scalars, NoiseSup.c:600-637; returns alfaGF */
+template <bool NF = false>
 __device__ __forceinline__ void gain_fact_update(NsRegs &s, float noiseEn)
 {
     float averSNR = (s.denEn0 * s.denEn1 * s.denEn2) / (noiseEn * noiseEn * noiseEn);
-    if ((double)averSNR > 0.00001) /* log10(y) = ln(y) * log10(e), guarded (ns_aversnr_expr) */
-        averSNR = ns_aversnr_expr<true>(uniform_f(averSNR));
+    if ((double)averSNR > 0.00001) /* log10(y) = ln(y) * log10(e), guarded (ns_aversnr_expr); a NaN takes the else, as in the reference */
+        averSNR = ns_aversnr_expr<true, NF>(uniform_f(averSNR));
     else
         averSNR = (float)(-100.0 / 3.0);
     averSNR = uniform_f(averSNR);
@@ -829,7 +864,9 @@ __device__ __forceinline__ float ns_mel_fb(const BackLds &B, const NsConst &C, i
 #pragma unroll
         for (int i = 0; i < SEA_MEL_TAPS; ++i) {
             /* taps past the band's length carry weight 0 in the table: melOut + W * 0 == melOut exactly (W is
-             * a finite gain, melOut >= +0), which keeps a select out of the dependent chain */
+             * a finite gain, melOut >= +0), which keeps a select out of the dependent chain.  W is finite for EVERY input,
+             * Inf and NaN included: gain_bin's `prio > rsbMin ? prio : rsbMin` turns a NaN into rsbMin, and prio = +Inf there
+             * would need a first gain that is not NaN together with P / noise = Inf, which makes that first gain Inf / Inf */
             const int idx = C.melStart + i;
             melOut = melOut + B.wbuf[idx < 65 ? idx : 64] * C.melW[i];
         }
@@ -1124,7 +1161,7 @@ __device__ unsigned long long g_back_ck[16];
  * IDCT_HEAD = K >= 0: stop inside the IDCT -- add only the first K terms of its sums and deposit the partial sums and the
  *   remaining mel gains in dst (ns_idct_head); the consumer wave, which has cycles to spare, finishes them into the taps
  *   (ns_idct_tail, ns_idct_tail_rl) and runs the FIR itself. */
-template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1>
+template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1, bool NF = false /* see ns_ln */>
 __device__ __forceinline__ void ns_back(const float *psd, const float *buf, BackLds &B, NsRegs &s,
                                         const NsConst &C, float *dst, int lane, float frameEnExt = 0.0f,
                                         float *spectOut = nullptr, const float *idctLds = nullptr,
@@ -1149,7 +1186,7 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
         s.nbFrame[ST] = nb;
     }
     if (ST == 0) {
-        const float frameEn = PIPE ? frameEnExt : vad_frame_energy(vad_frame_sum(buf + 80, B.sq, lane));
+        const float frameEn = PIPE ? frameEnExt : vad_frame_energy<NF>(vad_frame_sum(buf + 80, B.sq, lane));
         vad_update(s, frameEn);
     }
 
@@ -1271,7 +1308,7 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
             s.denEn1 = s.denEn2;
             s.denEn2 = total;
         } else {
-            gain_fact_update(s, total);
+            gain_fact_update<NF>(s, total);
             melOut = (float)((double)(s.alfaGF * melOut) + (1.0 - (double)s.alfaGF) * 1.0);
         }
     }
@@ -1401,13 +1438,13 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
 }
 
 /* One whole stage on the single-wave form: stage 0 deposits its 80 output samples in
- * ring[1][240..319], stage 1 in outb[0..79]. */
+ * ring[1][240..319], stage 1 in outb[0..79].  Only the streaming kernels (ns_tick) run it, on the caller's floats: NF. */
 template <int ST, bool FD = false>
 __device__ __forceinline__ void ns_stage(NsLds &L, NsRegs &s, const NsConst &C, int lane, NsFd *fd = nullptr,
                                          int *fdFlags = nullptr)
 {
     ns_front(L.ring[ST], L.work, L.psd, C.fft, C.win, lane);
-    ns_back<ST, false, FD>(L.psd, L.ring[ST], L.back, s, C, (ST == 0) ? (L.ring[1] + 240) : L.outb, lane, 0.0f, nullptr,
+    ns_back<ST, false, FD, false, -1, true>(L.psd, L.ring[ST], L.back, s, C, (ST == 0) ? (L.ring[1] + 240) : L.outb, lane, 0.0f, nullptr,
                            nullptr, fd, fdFlags);
 }
 

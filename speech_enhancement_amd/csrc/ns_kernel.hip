@@ -130,6 +130,19 @@ __global__ __launch_bounds__(256) void selftest_log_sites_kernel(const float *x,
     }
 }
 
+/* the three entry forms as the float-intake kernels instantiate them (NF = true: the exponent field is tested first) on n
+ * floats of ANY bit pattern: site1 / site2 as above without the range selection, lg = ns_logf */
+__global__ __launch_bounds__(256) void selftest_log_nonfinite_kernel(const float *x, float *site1, float *site2, float *lg, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const float v = x[i];
+        site1[i] = ns_vad_energy_expr<false, true>(v);
+        site2[i] = ns_aversnr_expr<false, true>(v);
+        lg[i] = ns_logf<true>(v);
+    }
+}
+
 /* EVERY float argument a site can see -- site 1: every finite float frameSum >= 64 (the int16 batch path stays below
  * 64 + 80 * 32768^2 = 2^36.3; the float streaming entry points, sea_ns_stream_push / sea_ns_streams_push, can present
  * any float); site 2: every finite float above 1e-5 -- through the site's fast form AND its slow form (double-double log, the

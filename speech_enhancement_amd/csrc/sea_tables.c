@@ -370,7 +370,10 @@ static void cc_mel_lanes(const band_t *B, sea_cc_tables *t)
         lane = 32 * g + fill[g]++;
         t->melLaneBase[lane] = it[i].base + SEA_CC_PWROW * it[i].h;
         t->melLaneFb[lane] = 24 * it[i].h + it[i].b;
-        for (j = 0; j < b->len; j++) t->melLaneW[lead + j][lane] = b->w[j];
+        for (j = 0; j < b->len; j++) {
+            if (b->w[j] == 0.0f) abort(); /* zero = outside the band: compceps_frames_kernel skips such taps (cc_tile<.., NF>) */
+            t->melLaneW[lead + j][lane] = b->w[j];
+        }
     }
     for (g = 0; g < 2; g++) { /* no two lanes of a group on one pair of banks */
         memset(seen, 0, sizeof seen);

@@ -815,7 +815,8 @@ def test_ns_stream_float_amplitude_extremes(oracle):
     the PSD is 0 or within [2^-40, 2^48] and the noise estimate within [2^-15, 2^28]; everything else takes
     the plain-division path.  Streams scaled from 1e-21 (PSD in the denormals) to 1e18, streams sitting on
     the domain's edges, and streams that jump between scales mid-way (the one-frame hand-over between the
-    two paths) must all be bit-identical to the oracle."""
+    two paths) must all be bit-identical to the oracle.  ("Any magnitude" here means finite floats whose frame energy stays
+    finite; samples whose square overflows, Inf and NaN are tests/test_gpu_nonfinite.py's.)"""
     import speech_enhancement_amd as sea
     torch = _torch()
     base = _float_stream_case(11)
