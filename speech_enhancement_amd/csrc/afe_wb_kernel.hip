@@ -3,7 +3,8 @@
  *
  * A unit of its own: whatever joins cc_kernel.hip's unit moves the register allocation of the 8 kHz kernels there (afe_ceps_kernel
  * came out with 233 or 251 instead of 255 VGPRs), and those are to stay as measured.  The tile and WaveProc are shared with them
- * through cc_tile.h / cc_waveproc.h; the PostProc + VAD pass of the chain is afe_wb_vad_kernel in cc_kernel.hip.
+ * through cc_tile.h / cc_waveproc.h; the PostProc + VAD pass of the chain is afe_wb_vad_kernel in cc_kernel.hip (its registers and
+ * decision: afe_vad.h).  The time-slice forms of both passes, for both rates, are one text in afe_slice_kernel.hip.
  */
 #undef SEA_CC_TIMING /* the tile's timing diagnostic is compceps_kernel's (cc_kernel.hip) */
 #include "cc_tile.h"

@@ -348,6 +348,30 @@ int sea_ns_denoise_batch_fd(const short *d_in, short *d_out, float *d_out_f32,
     return 0;
 }
 
+/* the arguments the four feature-chain entry points have in common (sea_kernels.h, AfeArgs) */
+static void afe_args(sea::AfeArgs *a, const DeviceCtx *c, const float *d_den_f32, const unsigned char *d_flags,
+                     const long long *d_offsets, const long long *d_lengths, const int *d_first_out, const int *d_onset,
+                     const long long *d_ceps_cum, float *d_feat_cc, float *d_feat_pp, const long long *d_feat_cum, float *d_feat15,
+                     int *d_n_feat, int *d_n_ceps, int n_utt)
+{
+    *a = {};
+    a->den_f32 = d_den_f32;
+    a->flags = d_flags;
+    a->offsets = d_offsets;
+    a->lengths = d_lengths;
+    a->first_out = d_first_out;
+    a->onset = d_onset;
+    a->ceps_cum = d_ceps_cum;
+    a->feat_cc = d_feat_cc;
+    a->feat_pp = d_feat_pp;
+    a->feat_cum = d_feat_cum;
+    a->feat15 = d_feat15;
+    a->n_feat = d_n_feat;
+    a->n_ceps = d_n_ceps;
+    a->tables = c->cc;
+    a->n_utt = n_utt;
+}
+
 int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags, const long long *d_offsets,
                            const long long *d_lengths, const int *d_first_out, const int *d_onset,
                            const long long *d_ceps_cum, long long total_ceps, float *d_feat_cc, float *d_feat_pp,
@@ -357,22 +381,9 @@ int sea_afe_features_batch(const float *d_den_f32, const unsigned char *d_flags,
     if (n_utt <= 0) return 0;
     DeviceCtx *c;
     if (ctx(&c)) return 1;
-    sea::AfeArgs a = {};
-    a.den_f32 = d_den_f32;
-    a.flags = d_flags;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.first_out = d_first_out;
-    a.onset = d_onset;
-    a.ceps_cum = d_ceps_cum;
-    a.feat_cc = d_feat_cc;
-    a.feat_pp = d_feat_pp;
-    a.feat_cum = d_feat_cum;
-    a.feat15 = d_feat15;
-    a.n_feat = d_n_feat;
-    a.n_ceps = d_n_ceps;
-    a.tables = c->cc;
-    a.n_utt = n_utt;
+    sea::AfeArgs a;
+    afe_args(&a, c, d_den_f32, d_flags, d_offsets, d_lengths, d_first_out, d_onset, d_ceps_cum, d_feat_cc, d_feat_pp, d_feat_cum,
+             d_feat15, d_n_feat, d_n_ceps, n_utt);
     if (total_ceps > 0) {
         const long long nslot = total_ceps / 8 + n_utt; /* tile slots of 8 frames (cc_kernel.hip, kAfeT) */
         constexpr long long kAfeGrid = 8192; /* waves of the launch */
@@ -446,21 +457,8 @@ int sea_afe_features_batch_slice(const float *d_den_f32, const unsigned char *d_
     if (ctx(&c)) return 1;
     sea::AfeSliceArgs s = {};
     sea::AfeArgs &a = s.a;
-    a.den_f32 = d_den_f32;
-    a.flags = d_flags;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.first_out = d_first_out;
-    a.onset = d_onset;
-    a.ceps_cum = d_ceps_cum;
-    a.feat_cc = d_feat_cc;
-    a.feat_pp = d_feat_pp;
-    a.feat_cum = d_feat_cum;
-    a.feat15 = d_feat15;
-    a.n_feat = d_n_feat;
-    a.n_ceps = d_n_ceps;
-    a.tables = c->cc;
-    a.n_utt = n_utt;
+    afe_args(&a, c, d_den_f32, d_flags, d_offsets, d_lengths, d_first_out, d_onset, d_ceps_cum, d_feat_cc, d_feat_pp, d_feat_cum,
+             d_feat15, d_n_feat, d_n_ceps, n_utt);
     s.final = d_final;
     s.state = d_afe_state;
     s.frame_base = frame_base;
@@ -686,7 +684,7 @@ int sea_wb_slice_state_floats(void) { return sea::kWbSliceStateFloats; }
 int sea_wb_afe_slice_state_floats(void) { return sea::kWbAfeStateFloats; }
 
 /* The feature chain over one TIME SLICE: see include/sea_mi355x.h.  Two launches as in sea_wb_afe_features_batch, each the slice
- * form of its kernel (afe_wb_slice_kernel.hip); the second one also stores what the next slice starts from. */
+ * form of its kernel (afe_slice_kernel.hip); the second one also stores what the next slice starts from. */
 int sea_wb_afe_features_batch_slice(const float *d_out_f32, const unsigned char *d_flag_rows, const float *d_hp_rows,
                                     const float *d_code_rows, const long long *d_offsets, const long long *d_lengths,
                                     const int *d_first_out, const int *d_onset, const unsigned char *d_final,
@@ -707,21 +705,8 @@ int sea_wb_afe_features_batch_slice(const float *d_out_f32, const unsigned char 
     if (ctx(&c)) return 1;
     sea::WbAfeSliceArgs s = {};
     sea::AfeArgs &a = s.w.a;
-    a.den_f32 = d_out_f32;
-    a.flags = d_flag_rows;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.first_out = d_first_out;
-    a.onset = d_onset;
-    a.ceps_cum = d_ceps_cum;
-    a.feat_cc = d_feat_cc;
-    a.feat_pp = d_feat_pp;
-    a.feat_cum = d_feat_cum;
-    a.feat15 = d_feat15;
-    a.n_feat = d_n_feat;
-    a.n_ceps = d_n_ceps;
-    a.tables = c->cc;
-    a.n_utt = n_utt;
+    afe_args(&a, c, d_out_f32, d_flag_rows, d_offsets, d_lengths, d_first_out, d_onset, d_ceps_cum, d_feat_cc, d_feat_pp, d_feat_cum,
+             d_feat15, d_n_feat, d_n_ceps, n_utt);
     s.w.hp_rows = d_hp_rows;
     s.w.code_rows = d_code_rows;
     s.w.wb = c->wb;
@@ -757,21 +742,8 @@ int sea_wb_afe_features_batch(const float *d_out_f32, const unsigned char *d_fla
     if (ctx(&c)) return 1;
     sea::WbAfeArgs w = {};
     sea::AfeArgs &a = w.a;
-    a.den_f32 = d_out_f32;
-    a.flags = d_flag_rows;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.first_out = d_first_out;
-    a.onset = d_onset;
-    a.ceps_cum = d_ceps_cum;
-    a.feat_cc = d_feat_cc;
-    a.feat_pp = d_feat_pp;
-    a.feat_cum = d_feat_cum;
-    a.feat15 = d_feat15;
-    a.n_feat = d_n_feat;
-    a.n_ceps = d_n_ceps;
-    a.tables = c->cc;
-    a.n_utt = n_utt;
+    afe_args(&a, c, d_out_f32, d_flag_rows, d_offsets, d_lengths, d_first_out, d_onset, d_ceps_cum, d_feat_cc, d_feat_pp, d_feat_cum,
+             d_feat15, d_n_feat, d_n_ceps, n_utt);
     w.hp_rows = d_hp_rows;
     w.code_rows = d_code_rows;
     w.wb = c->wb;

@@ -13,6 +13,7 @@
  */
 #include "cc_tile.h"
 #include "cc_waveproc.h"
+#include "afe_vad.h"
 
 namespace sea {
 
@@ -419,7 +420,9 @@ __global__ __launch_bounds__(64, 1) void afe_ceps_kernel(AfeArgs a)
 namespace {
 /* WB: frames of 160 input samples, the speech flags one byte per per-frame row (ns_denoise_pipe_wb_fd_kernel); the null vectors
  * follow the wideband gate, which works on the 160 raw samples (ParmInterface.c:244-251): a.onset is that gate's.  The
- * arithmetic is the same: PostProc.c and VAD.c read no wideband state. */
+ * arithmetic is the same: PostProc.c and VAD.c read no wideband state.  The registers, PostProc's table and the decision are
+ * afe_vad.h's, shared with the slice form (afe_slice_kernel.hip); the row loop and the flush loop are written out here and there:
+ * why, afe_vad.h says. */
 template <bool WB>
 __device__ __forceinline__ void afe_vad_body(const AfeArgs &a, float (&ring)[7][16])
 {
@@ -447,42 +450,11 @@ __device__ __forceinline__ void afe_vad_body(const AfeArgs &a, float (&ring)[7][
         for (int r = 0; r < 7; ++r) ring[r][lane] = 0.0f;
     wave_sync();
 
-    static const float target[12] = {(float)-6.618909, (float)0.198269, (float)-0.740308, (float)0.055132,
-                                     (float)-0.227086, (float)0.144280, (float)-0.112451, (float)-0.146940,
-                                     (float)-0.327466, (float)0.134571, (float)0.027884,  (float)-0.114905};
-    const float tgt = (lane < 12) ? target[lane] : 0.0f;
-    const float lambda = (float)0.0087890625;
-    float wLMS = 0.0f;   /* weightLMS[lane] */
-    float feat = 0.0f;   /* FeatureBuffer[lane]: persists between calls like the reference's buffer */
-    int focus = 0, hangOver = 23, hCount = 0, vCount = 0, frameCounter = 0;
+    const float tgt = afe_postproc_target(lane);
+    const float lambda = kPostProcLambda;
+    AfeVad v;
 
-    /* trigger = longest run of speech-flagged frames in the ring, scanned from focus+1 round to focus */
-    auto decide = [&](int fc) {
-        int sum = 0, trigger = 0;
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            int r = focus + i + 1;
-            r = r > 6 ? r - 7 : r;
-            if (ring[r][14] != 0.0f)
-                sum++;
-            else {
-                trigger = sum > trigger ? sum : trigger;
-                sum = 0;
-            }
-        }
-        trigger = sum > trigger ? sum : trigger;
-        if (trigger >= 4) {
-            hCount = hangOver;
-            if (fc <= 35) hangOver = 50;
-        }
-        if (hCount && trigger < 3) hCount--;
-        if (trigger >= 3) vCount = 5;
-        if (vCount && trigger < 3) vCount--;
-        int r = focus + 1;
-        r = r > 6 ? r - 7 : r;
-        feat = (lane < 15) ? ring[r][lane] : 0.0f;
-        if (lane == 14) feat = (vCount || hCount || trigger >= 3) ? 1.0f : 0.0f;
-    };
+    auto decide = [&](int fc) { afe_vad_decide(v, ring, fc, lane); };
 
     /* rows and flag bytes are requested kAhead frames before use: the loop body is a few dozen
      * instructions, an HBM round trip a few thousand clocks */
@@ -508,23 +480,23 @@ __device__ __forceinline__ void afe_vad_body(const AfeArgs &a, float (&ring)[7][
         const float logE = __shfl(c, 13, 64);
         float wp = (logE * (float)64 - (float)211) / (float)64;
         wp = (wp < 0) ? 0.0f : ((wp > 1) ? lambda : wp * lambda);
-        float v = c;
+        float x = c;
         if (lane < 12) {
-            const float dif = ((c - wLMS) - tgt);
-            v = c - wLMS;
-            wLMS += dif * wp;
+            const float dif = ((c - v.wLMS) - tgt);
+            x = c - v.wLMS;
+            v.wLMS += dif * wp;
         }
-        if (pp && lane < 14) pp[j * SEA_CC_NCEP + lane] = v;
-        if (lane < 14) feat = v;
+        if (pp && lane < 14) pp[j * SEA_CC_NCEP + lane] = x;
+        if (lane < 14) v.feat = x;
         /* DoVADProc */
-        frameCounter = (int)j + 5; /* nbFrame[0] when NoiseSup output j+3 appears */
-        focus = (focus + 1 == 7) ? 0 : focus + 1;
-        if (lane < 14) ring[focus][lane] = feat;
-        if (lane == 14) ring[focus][14] = bits ? 1.0f : 0.0f;
+        v.frameCounter = (int)j + 5; /* nbFrame[0] when NoiseSup output j+3 appears */
+        v.focus = (v.focus + 1 == 7) ? 0 : v.focus + 1;
+        if (lane < 14) ring[v.focus][lane] = v.feat;
+        if (lane == 14) ring[v.focus][14] = bits ? 1.0f : 0.0f;
         wave_sync();
-        if (frameCounter > 10) {
-            decide(frameCounter);
-            if (lane < 15) out[nemit * 15 + lane] = feat;
+        if (v.frameCounter > 10) {
+            decide(v.frameCounter);
+            if (lane < 15) out[nemit * 15 + lane] = v.feat;
             nemit++;
         }
         wave_sync();
@@ -532,15 +504,15 @@ __device__ __forceinline__ void afe_vad_body(const AfeArgs &a, float (&ring)[7][
     }
     /* FlushAdvProcess until DoVADFlush returns FALSE */
     {
-        const int flushFocus = focus;
+        const int flushFocus = v.focus;
         for (;;) {
-            int nf = focus + 1;
+            int nf = v.focus + 1;
             nf = (nf == 7) ? 0 : nf;
             if (nf == flushFocus) break;
-            focus = nf;
-            frameCounter++;
-            if (frameCounter > 10) decide(frameCounter);
-            if (lane < 15) out[nemit * 15 + lane] = feat;
+            v.focus = nf;
+            v.frameCounter++;
+            if (v.frameCounter > 10) decide(v.frameCounter);
+            if (lane < 15) out[nemit * 15 + lane] = v.feat;
             nemit++;
         }
     }

@@ -201,7 +201,7 @@ struct WbAfeArgs {
 __global__ void afe_wb_ceps_kernel(WbAfeArgs a); /* WaveProc + the 26-band CompCeps */
 __global__ void afe_wb_vad_kernel(AfeArgs a);    /* PostProc + frame-dropping VAD + flush on frames of 160 samples */
 
-/* The wideband feature chain over one TIME SLICE (afe_wb_slice_kernel.hip; include/sea_mi355x.h,
+/* The wideband feature chain over one TIME SLICE (afe_slice_kernel.hip, AfeSliceRate<true>; include/sea_mi355x.h,
  * sea_wb_afe_features_batch_slice).  Every buffer of w describes the slice as sea_wb_denoise_batch_slice_fd leaves it; first_out
  * and onset are absolute.  Cepstral frame j of an utterance with first output f0 completes with output frame f0 + j + 2, so the
  * frames that complete in a slice [fb, fb + n) are j in [max(0, fb - f0 - 2), fb + n - f0 - 2).  What one utterance carries,
@@ -236,9 +236,9 @@ struct WbAfeSliceArgs {
 __global__ void afe_wb_ceps_slice_kernel(WbAfeSliceArgs s); /* WaveProc + the 26-band CompCeps of the frames completing in the slice */
 __global__ void afe_wb_vad_slice_kernel(WbAfeSliceArgs s);  /* nulls, PostProc + VAD, flush where final; then the state */
 
-/* The 8 kHz feature chain over one TIME SLICE (afe_slice_kernel.hip; include/sea_mi355x.h, sea_afe_features_batch_slice): the
- * wideband slice form above without the high-band and code rows.  Every buffer of a describes the slice as
- * sea_ns_denoise_batch_slice_fd leaves it (den_f32 at offsets[u], the flag byte of the slice's frame f at offsets[u]/8 + 10 f);
+/* The 8 kHz feature chain over one TIME SLICE (afe_slice_kernel.hip, AfeSliceRate<false>; include/sea_mi355x.h,
+ * sea_afe_features_batch_slice): the same kernel text as the wideband slice form above, without the high-band and code rows.
+ * Every buffer of a describes the slice as sea_ns_denoise_batch_slice_fd leaves it (den_f32 at offsets[u], the flag byte of the slice's frame f at offsets[u]/8 + 10 f);
  * first_out and onset are absolute.  What one utterance carries, kAfeStateFloats floats at state + u * that, integers as their
  * bit patterns:
  *   kAf8StF32   240 floats  the last three frames of the float stream, SHIFTED by the slice's frames (kAfStKeep of them)

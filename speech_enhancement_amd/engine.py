@@ -373,39 +373,7 @@ def wb_afe_features_batch_slice(batch, den, afe_state, frame_base, resume, final
     complete in it; feat_pp None without want_pp), ceps_cum / feat_cum (host prefix sums of the capacities: the slice's frames
     and the slice's frames + 6), feat15 (the device tensor behind feats); rows behind the counts are zero.
     Concatenated over the slices of an utterance, everything is bit for bit wb_afe_features_batch's."""
-    torch = _torch()
-    lib = _lib.load()
-    n = batch.n_utt
-    if afe_state is None or afe_state.dtype != torch.float32 or not afe_state.is_contiguous() \
-            or afe_state.numel() < n * int(lib.sea_wb_afe_slice_state_floats()):
-        raise ValueError("afe_state must be a contiguous float32 tensor of sea_wb_afe_slice_state_floats() floats per utterance")
-    dev = batch.data.device
-    nfr = np.asarray(batch.host_lengths, dtype=np.int64) // 160
-    ccum = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
-    fcum = np.concatenate(([0], np.cumsum(nfr + 6))).astype(np.int64)
-    tc, tf = int(ccum[-1]), int(fcum[-1])
-    feat_cc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
-    feat_pp = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev) if want_pp else None
-    feat15 = torch.zeros((max(tf, 1), 15), dtype=torch.float32, device=dev)
-    n_feat = torch.zeros(n, dtype=torch.int32, device=dev)
-    n_ceps = torch.zeros(n, dtype=torch.int32, device=dev)
-    d_ccum, d_fcum = torch.from_numpy(ccum).to(dev), torch.from_numpy(fcum).to(dev)
-    d_final = None
-    if final is not None:
-        d_final = torch.from_numpy(np.asarray(final, dtype=bool).astype(np.uint8)).to(dev)
-        if d_final.numel() != n:
-            raise ValueError("final must hold one entry per utterance of the slice")
-    rc = lib.sea_wb_afe_features_batch_slice(_dptr(den["f32"]), _dptr(den["flag_rows"]), _dptr(den["hp_rows"]),
-                                             _dptr(den["code_rows"]), _dptr(batch.offsets), _dptr(batch.lengths),
-                                             _dptr(den["first_out"]), _dptr(den["onset"]), _dptr(d_final), _dptr(d_ccum), tc,
-                                             _dptr(feat_cc), _dptr(feat_pp), _dptr(d_fcum), _dptr(feat15), _dptr(n_feat),
-                                             _dptr(n_ceps), _dptr(afe_state), n, int(frame_base), 1 if resume else 0,
-                                             _stream_ptr())
-    _lib.check(rc, "sea_wb_afe_features_batch_slice")
-    torch.cuda.synchronize()
-    host15, nf, nc = feat15.cpu().numpy(), n_feat.cpu().numpy(), n_ceps.cpu().numpy()
-    return dict(feats=[host15[fcum[u]:fcum[u] + int(nf[u])] for u in range(n)], n_feat=nf, n_ceps=nc, feat_cc=feat_cc,
-                feat_pp=feat_pp, feat15=feat15, ceps_cum=ccum, feat_cum=fcum, afe_state=afe_state)
+    return _afe_slice(batch, den, afe_state, frame_base, resume, final, want_pp, True)
 
 
 def wb_features_utterances(utterances, want_lp=False):
@@ -675,24 +643,16 @@ def ns_denoise_batch_slice(batch, state, frame_base, resume, want_f32=False, wan
     return dict(out=out, f32=f32, first_out=first_out, onset=None, flags=None, state=state)
 
 
-def afe_features_batch_slice(batch, den, afe_state, frame_base, resume, final=None, want_pp=False):
-    """The 8 kHz feature chain over one TIME SLICE (sea_afe_features_batch_slice): ``batch`` and ``den`` are the slice's batch
-    and the dict ``ns_denoise_batch_slice(.., want_flags=True)`` returned for it, ``afe_state`` an ``afe_slice_state`` tensor
-    with a row per utterance, ``frame_base`` / ``resume`` as there.  ``final``: per utterance, true where the utterance ends
-    with this slice -- DoVADFlush runs after it (a slice may be empty: a stream whose end is learnt late); None flushes nothing.
-    Returns a dict for THIS slice: feats (list of float32 [n_u, 15] host arrays, the frames emitted during the slice), n_feat /
-    n_ceps (int32 host arrays), feat_cc / feat_pp (device tensors [frames of the slice, 14], the cepstral frames that complete
-    in it; feat_pp None without want_pp), ceps_cum / feat_cum (host prefix sums of the capacities: the slice's frames and the
-    slice's frames + 6), feat15 (the device tensor behind feats); rows behind the counts are zero.
-    Concatenated over the slices of an utterance, everything is bit for bit afe_features_batch's."""
+def _afe_slice(batch, den, afe_state, frame_base, resume, final, want_pp, wb):
     torch = _torch()
     lib = _lib.load()
     n = batch.n_utt
+    name = "sea_wb_afe_slice_state_floats" if wb else "sea_afe_slice_state_floats"
     if afe_state is None or afe_state.dtype != torch.float32 or not afe_state.is_contiguous() \
-            or afe_state.numel() < n * int(lib.sea_afe_slice_state_floats()):
-        raise ValueError("afe_state must be a contiguous float32 tensor of sea_afe_slice_state_floats() floats per utterance")
+            or afe_state.numel() < n * int(getattr(lib, name)()):
+        raise ValueError(f"afe_state must be a contiguous float32 tensor of {name}() floats per utterance")
     dev = batch.data.device
-    nfr = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+    nfr = np.asarray(batch.host_lengths, dtype=np.int64) // (160 if wb else 80)
     ccum = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
     fcum = np.concatenate(([0], np.cumsum(nfr + 6))).astype(np.int64)
     tc, tf = int(ccum[-1]), int(fcum[-1])
@@ -707,16 +667,32 @@ def afe_features_batch_slice(batch, den, afe_state, frame_base, resume, final=No
         d_final = torch.from_numpy(np.asarray(final, dtype=bool).astype(np.uint8)).to(dev)
         if d_final.numel() != n:
             raise ValueError("final must hold one entry per utterance of the slice")
-    rc = lib.sea_afe_features_batch_slice(_dptr(den["f32"]), _dptr(den["flags"]), _dptr(batch.offsets), _dptr(batch.lengths),
-                                          _dptr(den["first_out"]), _dptr(den["onset"]), _dptr(d_final), _dptr(d_ccum), tc,
-                                          _dptr(feat_cc), _dptr(feat_pp), _dptr(d_fcum), _dptr(feat15), _dptr(n_feat),
-                                          _dptr(n_ceps), _dptr(afe_state), n, int(frame_base), 1 if resume else 0,
-                                          _stream_ptr())
-    _lib.check(rc, "sea_afe_features_batch_slice")
+    if wb:
+        call, stream = "sea_wb_afe_features_batch_slice", (den["f32"], den["flag_rows"], den["hp_rows"], den["code_rows"])
+    else:
+        call, stream = "sea_afe_features_batch_slice", (den["f32"], den["flags"])
+    rc = getattr(lib, call)(*[_dptr(t) for t in stream], _dptr(batch.offsets), _dptr(batch.lengths), _dptr(den["first_out"]),
+                            _dptr(den["onset"]), _dptr(d_final), _dptr(d_ccum), tc, _dptr(feat_cc), _dptr(feat_pp), _dptr(d_fcum),
+                            _dptr(feat15), _dptr(n_feat), _dptr(n_ceps), _dptr(afe_state), n, int(frame_base), 1 if resume else 0,
+                            _stream_ptr())
+    _lib.check(rc, call)
     torch.cuda.synchronize()
     host15, nf, nc = feat15.cpu().numpy(), n_feat.cpu().numpy(), n_ceps.cpu().numpy()
     return dict(feats=[host15[fcum[u]:fcum[u] + int(nf[u])] for u in range(n)], n_feat=nf, n_ceps=nc, feat_cc=feat_cc,
                 feat_pp=feat_pp, feat15=feat15, ceps_cum=ccum, feat_cum=fcum, afe_state=afe_state)
+
+
+def afe_features_batch_slice(batch, den, afe_state, frame_base, resume, final=None, want_pp=False):
+    """The 8 kHz feature chain over one TIME SLICE (sea_afe_features_batch_slice): ``batch`` and ``den`` are the slice's batch
+    and the dict ``ns_denoise_batch_slice(.., want_flags=True)`` returned for it, ``afe_state`` an ``afe_slice_state`` tensor
+    with a row per utterance, ``frame_base`` / ``resume`` as there.  ``final``: per utterance, true where the utterance ends
+    with this slice -- DoVADFlush runs after it (a slice may be empty: a stream whose end is learnt late); None flushes nothing.
+    Returns a dict for THIS slice: feats (list of float32 [n_u, 15] host arrays, the frames emitted during the slice), n_feat /
+    n_ceps (int32 host arrays), feat_cc / feat_pp (device tensors [frames of the slice, 14], the cepstral frames that complete
+    in it; feat_pp None without want_pp), ceps_cum / feat_cum (host prefix sums of the capacities: the slice's frames and the
+    slice's frames + 6), feat15 (the device tensor behind feats); rows behind the counts are zero.
+    Concatenated over the slices of an utterance, everything is bit for bit afe_features_batch's."""
+    return _afe_slice(batch, den, afe_state, frame_base, resume, final, want_pp, False)
 
 
 def features_utterances(utterances, want_out=False):

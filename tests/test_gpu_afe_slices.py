@@ -111,10 +111,11 @@ def _cuts(utts, bounds, final=True):
     return slices
 
 
-def _in_slices(n_utt, slices, features=True):
+def _in_slices(n_utt, slices, features=True, states=None):
     """One launch group per slice into sentinel-filled buffers: sea_ns_denoise_batch_slice_fd + sea_afe_features_batch_slice
     (features) or the plain sea_ns_denoise_batch_slice.  Both states start as NaN: resume = 0 must not read them.  Returns per
-    utterance the concatenated pieces and the summed counts."""
+    utterance the concatenated pieces and the summed counts; `states`, a list, receives the feature chain's state after
+    the last slice, one row per utterance."""
     import speech_enhancement_amd as sea
     torch = _torch()
     lib = sea.load()
@@ -175,6 +176,8 @@ def _in_slices(n_utt, slices, features=True):
                     and _is_sent(h15[fcum[u] + e:fcum[u + 1]]), f"slice {k}, utterance {u}: rows behind the slice's counts were written"
                 n_feat[u] += e
                 n_ceps[u] += a
+    if states is not None:
+        states.append(afe.cpu().numpy())
     first, onset = first.cpu().numpy(), onset.cpu().numpy()
     res = []
     for u, g in enumerate(got):
@@ -403,6 +406,39 @@ def test_engine_wrappers_in_two_slices():
             assert np.array_equal(_u32(g[k]), _u32(w[k])), f"{what}: {k} differs in bits from the one launch"
         assert np.array_equal(g["out"], w["out"]), f"{what}: int16 audio differs from the one launch"
         assert np.array_equal(g["flags"], w["flags"]), f"{what}: flag bytes differ from the one launch"
+
+
+def _assert_final_state(st, want, x, what):
+    """st: one utterance's feature-chain state after its last slice, d_final set there (sea_kernels.h, kAfeStateFloats: history
+    at 0, ring at 240, lanes at 352, scalars at 384); want: its entry of _one_launch; x: its samples.  Every expected word comes
+    from the one launch and the length.  The history is copied from the slice's float stream, so frames before the first
+    output hold what that buffer held before the launch: the sentinel."""
+    assert st.shape == (392,)
+    assert not np.isnan(st).any(), f"{what}: {int(np.isnan(st).sum())} words of the state are still NaN"
+    nfr = len(x) // 80
+    quiet = want["first_out"] if want["first_out"] >= 0 else nfr
+    stream = want["f32"][:nfr].copy()
+    stream[:quiet] = SENT_F32
+    hist = np.concatenate([np.zeros(240, np.float32), stream.reshape(-1)])[-240:]
+    assert np.array_equal(_u32(st[:240]), _u32(hist)), f"{what}: the history is not the float stream's last 240 words"
+    scal = st[384:392].view(np.int32)
+    assert (int(scal[5]), int(scal[6]), int(scal[7])) == (want["n_ceps"], min(want["onset"], nfr), 1), \
+        f"{what}: cepstral frames / null vectors / flushed {scal[5:8]}, expected {want['n_ceps']} / {min(want['onset'], nfr)} / 1"
+
+
+def test_final_state_words():
+    """The words of the state that no later slice reads back: after the last slice (d_final set) the 240 history floats are the
+    tail of the one launch's float stream, zeros in front where the utterance is shorter, the three diagnostic integers are the
+    one launch's n_ceps, min(onset, frames) and 1, and no word is still the NaN it started as.  Six utterances cut at frame 41
+    (test_engine_wrappers_in_two_slices' list) and the short batch cut at every frame."""
+    fixtures, _ = _fixture_one_launch()
+    six = list(fixtures[:5]) + [np.concatenate([fixtures[5][:80 * 30], fixtures[5][80 * 50:]])]
+    for name, utts, bounds in (("six cut at 41", six, (0, 41, 400)), ("short batch", _sorted(_short_batch())[1], tuple(range(46)))):
+        want = _one_launch(utts)
+        states = []
+        _in_slices(len(utts), _cuts(utts, bounds), states=states)
+        for j, x in enumerate(utts):
+            _assert_final_state(states[0][j], want[j], x, f"{name}, utterance {j} ({len(x)} samples)")
 
 
 def test_slice_arguments_are_checked():

@@ -113,10 +113,11 @@ def _cuts(utts, bounds, final=True):
     return slices
 
 
-def _in_slices(n_utt, slices, features=True):
+def _in_slices(n_utt, slices, features=True, states=None):
     """One launch group per slice into sentinel-filled buffers: sea_wb_denoise_batch_slice_fd + sea_wb_afe_features_batch_slice
     (features) or the plain sea_wb_denoise_batch_slice.  Both states start as NaN: resume = 0 must not read them.  Returns per
-    utterance the concatenated pieces and the summed counts."""
+    utterance the concatenated pieces and the summed counts; `states`, a list, receives the feature chain's state after
+    the last slice, one row per utterance."""
     import speech_enhancement_amd as sea
     torch = _torch()
     lib = sea.load()
@@ -183,6 +184,8 @@ def _in_slices(n_utt, slices, features=True):
                     and _is_sent(h15[fcum[u] + e:fcum[u + 1]]), f"slice {k}, utterance {u}: rows behind the slice's counts were written"
                 n_feat[u] += e
                 n_ceps[u] += a
+    if states is not None:
+        states.append(afe.cpu().numpy())
     first, onset = first.cpu().numpy(), onset.cpu().numpy()
     res = []
     for u, g in enumerate(got):
@@ -384,6 +387,44 @@ def test_engine_wrappers_in_two_slices():
             assert np.array_equal(_u32(g[k]), _u32(w[k])), f"{what}: {k} differs in bits from the one launch"
         assert np.array_equal(g["out"], w["out"]), f"{what}: low band differs from the one launch"
         assert np.array_equal(g["flags"], w["flags"]), f"{what}: flag bytes differ from the one launch"
+
+
+def _assert_final_state(st, want, x, what):
+    """st: one utterance's feature-chain state after its last slice, d_final set there (sea_kernels.h, kWbAfeStateFloats:
+    history at 0, high-band rows at 240, code rows at 248, ring at 272, lanes at 384, scalars at 416); want: its entry of
+    _one_launch; x: its samples.  Every expected word comes from the one launch and the length.  History and rows are copied
+    from the slice's buffers, so frames before the first output hold what those held before the launch: the sentinel."""
+    assert st.shape == (424,)
+    assert not np.isnan(st).any(), f"{what}: {int(np.isnan(st).sum())} words of the state are still NaN"
+    nfr = len(x) // 160
+    quiet = want["first_out"] if want["first_out"] >= 0 else nfr
+    for key, at, keep, pad in (("f32", 0, 240, 0), ("hp", 240, 6, 2), ("code", 248, 18, 6)):
+        rows = want[key][:nfr].copy()
+        rows[:quiet] = SENT_F32
+        tail = np.concatenate([np.zeros(keep, np.float32), rows.reshape(-1)])[-keep:]
+        assert np.array_equal(_u32(st[at:at + keep]), _u32(tail)), f"{what}: {key} words of the state are not the one launch's last"
+        assert not _u32(st[at + keep:at + keep + pad]).any(), f"{what}: the padding behind the {key} rows is not zero"
+    scal = st[416:424].view(np.int32)
+    assert (int(scal[5]), int(scal[6]), int(scal[7])) == (want["n_ceps"], min(want["onset"], nfr), 1), \
+        f"{what}: cepstral frames / null vectors / flushed {scal[5:8]}, expected {want['n_ceps']} / {min(want['onset'], nfr)} / 1"
+
+
+def test_final_state_words():
+    """The words of the state that no later slice reads back: after the last slice (d_final set) the 240 history floats are the
+    tail of the one launch's low-band float stream and the 2 x 3 / 2 x 9 rows the last two frames' rows, zeros in front where
+    the utterance is shorter and in words 6-7 / 18-23 of the row blocks; the three diagnostic integers are the one launch's
+    n_ceps, min(onset, frames) and 1, and no word is still the NaN it started as.  The seven fixtures cut at frame 41 and the
+    short batch cut at every frame."""
+    from tests.test_gpu_wb_afe import _edge_batch
+    _, fixtures, fixture_want = _fixture_one_launch()
+    short = _sorted(_edge_batch()[0][:12])[1]
+    for name, utts, want, bounds in (("fixtures cut at 41", fixtures, fixture_want, (0, 41, 303)),
+                                     ("short batch", short, None, tuple(range(44)))):
+        want = want if want is not None else _one_launch(utts)
+        states = []
+        _in_slices(len(utts), _cuts(utts, bounds), states=states)
+        for j, x in enumerate(utts):
+            _assert_final_state(states[0][j], want[j], x, f"{name}, utterance {j} ({len(x)} samples)")
 
 
 def test_slice_arguments_are_checked():
