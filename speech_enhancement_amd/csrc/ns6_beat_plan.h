@@ -33,8 +33,12 @@ enum Role { FA = 0, FB = 1, B0 = 2, N1 = 3, G1 = 4, S = 5, kRoles = 6 };
 
 /* the compile-time variants of the body: a flag of the table belongs to all of them (kAlways) or to those with one of these */
 constexpr unsigned kAlways = 0u, kFd = 1u, kLight = 2u, kDifg1 = 4u;
-/* the three kernels */
+/* kRedeal (round 8, the dense kernel): feed-forward work dealt to the waves that wait -- N1 takes the VAD log-energy of frame i-2 off S,
+ * FA runs the stage-0 17-tap filter of frame i-3 (off B0) in the beat in which it windows that frame's stage-1 input */
+constexpr unsigned kRedeal = 8u;
+/* the three kernels; kVariantDense is the dense body without the re-deal, which no kernel takes since round 8 */
 constexpr unsigned kVariantPlain = kLight | kDifg1, kVariantDense = 0u, kVariantFd = kFd | kLight | kDifg1;
+constexpr unsigned kVariantDenseRedeal = kRedeal;
 
 struct Flag {
     int d;         /* the flag is about frame i - d ... */
@@ -51,14 +55,15 @@ struct RolePlan {
 };
 
 constexpr RolePlan kPlan[kRoles] = {
-    /* FA: frame i itself enters stage 0 from tick 3; stage 1 of frame i-3 from tick 5; LIGHT: the VAD log-energy of frame i-2 */
-    {3, {{0, 3, kAlways}, {3, 5, kAlways}, {2, 1, kLight}, {0, 0, 0}, {0, 0, 0}}, 1, 0},
+    /* FA: frame i itself enters stage 0 from tick 3; stage 1 of frame i-3 from tick 5; LIGHT: the VAD log-energy of frame i-2;
+     * kRedeal: the stage-0 filter of frame i-3, from tick 3 (ticks 3 and 4 leave output that the first stage-1 window needs) */
+    {4, {{0, 3, kAlways}, {3, 5, kAlways}, {2, 1, kLight}, {3, 3, kRedeal}, {0, 0, 0}}, 1, 0},
     /* FB: one beat behind FA on both transforms */
     {2, {{1, 3, kAlways}, {4, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
     /* B0: stage-0 back half of frame i-2 */
     {1, {{2, 3, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
-    /* N1: noise tracking of frame i-5, gain-factor scalars of frame i-7 */
-    {2, {{5, 5, kAlways}, {7, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* N1: noise tracking of frame i-5, gain-factor scalars of frame i-7; kRedeal: the VAD log-energy of frame i-2 */
+    {3, {{5, 5, kAlways}, {7, 5, kAlways}, {2, 1, kRedeal}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
     /* G1: gains of frame i-8 */
     {1, {{8, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
     /* S: VAD sum of frame i-1, denSigSE1 sum of i-3, noise sum of i-6, output of i-9; FD: the speech flags of frame i-9 */

@@ -1437,6 +1437,18 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
     wave_sync();
 }
 
+/* The stage-0 filter in the wave that consumes its output (the dense six-wave form since round 8).  The producer ran
+ * ns_back<0, .., IDCT_HEAD = SEA_NMEL>: ns_idct_head then adds ALL the terms of the nine IDCT sums and leaves them in rec[28..36];
+ * here the Hanning weight (irWin of lane k = 0..8), the lane reads and the 17-tap sums follow exactly as ns_back's
+ * ns_fir_regs(fir_taps_rl(ns_idct_tap_rl(..))) has them -- the same operations in the same order, the cut falls between the last
+ * addition of the sum and its one multiplication. */
+constexpr int kIdctRecFloats = 40; /* ns_idct_head's record: [0..24] mel gains, [28..36] the sums of rows 0..8 */
+__device__ __forceinline__ void ns_fir_from_idct_rec(const float *rec, float irWin, const float *buf, int lane, float &y0, float &y1)
+{
+    const int l = (lane <= 8) ? lane : 8;
+    ns_fir_regs(fir_taps_rl(rec[28 + l] * irWin), buf, lane, y0, y1);
+}
+
 /* One whole stage on the single-wave form: stage 0 deposits its 80 output samples in
  * ring[1][240..319], stage 1 in outb[0..79].  Only the streaming kernels (ns_tick) run it, on the caller's floats: NF. */
 template <int ST, bool FD = false>

@@ -29,6 +29,15 @@
  * the general copy (template parameter STEADY_LOOP).  configs[1]: 1.76 -> 1.71 ms = 479 M frames/s, 489 -> 356 scalar instructions per
  * frame (profiles/ns6_steady_loop.txt).
  *
+ * Round 8, the dense kernel only (REDEAL of ns_pipe6_body): two pieces of feed-forward work leave the two longest roles for waves that
+ * waited at the barrier, the instruction stream and the results unchanged --
+ *   wave N1  also: the VAD log-energy of the frame pushed at i-2, from the sum S left in frameEn one beat before -> frameEnLog (read by B0)
+ *   wave B0  stops at the nine IDCT sums of frame i-2 -> tap[]
+ *   wave FA  also: Hanning weight and the 17-tap filter of frame i-3 over the stage-0 buffer -> stage-1 buffer, before it windows that frame
+ *   wave S   leaves 64 + the frame's sum of squares, not its logarithm
+ * and that kernel has a wave -> role map of its own (kRedealPerm).  The plain and the _fd kernel run what is described above.
+ * configs[1]: 1.71 -> 1.66 ms (profiles/ns6_redeal.txt).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -91,6 +100,10 @@ constexpr int kPrioLevels = 32;
 /* wave -> role (octal digits, wave 0 rightmost; roles 0 FA, 1 FB, 2 B0, 3 N1, 4 G1, 5 S): B0 and S on the two oldest waves.
  * NsBatchArgs::perm6 != 0 replaces it (sea_debug_ns6_perm, which accepts permutations of 0..5 only). */
 constexpr int kDefaultPerm = 0014352;
+/* The re-dealt dense kernel (round 8): B0, FB, G1, N1, S, FA on waves 0..5, which keeps G1 and N1 on waves 2 and 3 and B0 on wave 0
+ * or 1 -- the best four of that kernel's 720 maps do (tools/ns6_perm_sweep.py; kDefaultPerm is not among its best forty, and this map
+ * is 1 % behind kDefaultPerm in the kernel before the re-deal) */
+constexpr int kRedealPerm = 0053412;
 
 /* Frame bookkeeping (valid / tick / produced of every frame) is a pure function of the frame index: the zero-frame gate
  * (ParmInterface.c:244-251) has one degree of freedom per utterance, the index `onset` of the first non-zero frame.  From it on every
@@ -183,9 +196,18 @@ __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, 
  *   stage-1 buffer    B0 writes the slot of tick t+6 (frame f+6, at iteration f+8) while G1 reads the window of tick t, slots
  *                     t-3 .. t, and FA that of tick t+5 (frame f+5 at f+8), slots t+2 .. t+5: ten live slots, eight collide
  *                     (t+6 = t-2 mod 8), so kSlots1 = 16, with the same three mirrored slots behind the last one
+ *   REDEAL            FA itself writes the stage-1 slot, one iteration later: at iteration f+8 the slot of tick t+5 (frame f+5), which
+ *                     its own window of that beat reads right after (same wave, wave_sync between), while G1 reads slots t-3 .. t:
+ *                     nine live slots, eight still collide (t+5 = t-3 mod 8), sixteen do not; the slot's previous content, tick t-11,
+ *                     was last read by G1 at iteration f.  The filter reads the stage-0 slots of ticks t+2 .. t+4 (buf[72..167] of the
+ *                     window of tick t+5) while FA's own push of that beat writes the slot of tick t+8 = t (mod 8) and S reads that of
+ *                     tick t+7: no other wave writes the stage-0 buffer, and FA's write is to none of the three.  kDepth stays 9.
+ *   tap               B0 writes the nine IDCT sums of frame f at f+2, FA reads them at f+3: D > 1, by frame parity
+ *   frameEnLog        REDEAL: N1 writes the slot (tick + 2) & 7 of the frame pushed at i-2 at iteration i, B0 reads it two iterations
+ *                     later -- LIGHT's timing, where FA writes it
  * nbFrame of the gain-factor job: N1's counter has by then counted the two frames tracked since; the job takes the frame's own
  * count, tick - 4 (the first second-stage frame has tick 5).
- * LDS: 24 624 B per workgroup (was 19 904); four workgroups per CU take 98.5 KB of the 160. */
+ * LDS: 24 944 B per workgroup (24 624 + the two tap records); four workgroups per CU take 99.8 KB of the 160. */
 constexpr int kP1Ring = 8;
 constexpr int kRnRing = 4;
 struct __attribute__((aligned(16))) RecPsd { /* FB -> B0 (stage 0) / N1, G1 (stage 1) */
@@ -201,6 +223,10 @@ struct __attribute__((aligned(16))) RecOut { /* G1 -> S */
     float out[80]; /* second-stage filter output before the DC-offset filter */
 };
 
+struct __attribute__((aligned(16))) RecTap { /* B0 -> FA: ns_idct_head's record, of which [28..36] are written and read */
+    float rec[kIdctRecFloats];
+};
+
 struct __attribute__((aligned(16))) Pipe6Lds {
     float circ0[kCirc + kMirror];   /* stage-0 buffer: kSlots slots and three mirrored ones */
     float circ1[kCirc1 + kMirror];  /* stage-1 buffer: kSlots1 slots and three mirrored ones */
@@ -209,7 +235,7 @@ struct __attribute__((aligned(16))) Pipe6Lds {
     float ssq[80], sdif[80], sout[80], szero[4]; /* scratch of S */
     float frameEn[kSlots], denSum[kSlots];
     int onset;                      /* index of the first non-zero frame, kNoOnset until FA has met it */
-    float frameEnLog[kSlots];       /* LIGHT: frameEn = 64 + sum of squares (S), frameEnLog = its log-energy (FA, one beat later) */
+    float frameEnLog[kSlots];       /* LIGHT, REDEAL: frameEn = 64 + sum of squares (S), frameEnLog = its log-energy (FA / N1, one beat later) */
     int fdFlags[kSlots];
     float idctT[SEA_NMEL * 16];
     RecPsd p0[2], p1[kP1Ring];
@@ -217,6 +243,7 @@ struct __attribute__((aligned(16))) Pipe6Lds {
     RecN rn[kRnRing];
     RecOut ro[2];
     float nzSum[2], alfa[2];        /* S -> N1: in-order sum of rn[f].noise; N1 -> G1: alfaGF of frame f; both by frame parity */
+    RecTap tap[2];                  /* B0 -> FA (dense form): the stage-0 filter's taps before their window, by frame parity */
 };
 /* The helper wave reads its four sources with one ds_read_b128 per quad; lanes of different chains share a lane group
  * ({ssq, den} in two of the four groups, {dif, noise} in the other two; past term 68 the sums read szero), so two sources that sit a
@@ -239,7 +266,7 @@ static_assert(lds_slots_differ(NS6_OFF(ro[0].out[68]), NS6_OFF(szero)) && lds_sl
               lds_slots_differ(NS6_OFF(ro[0].out[76]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[1].out[68]), NS6_OFF(szero)) &&
               lds_slots_differ(NS6_OFF(ro[1].out[72]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[1].out[76]), NS6_OFF(szero)), "ro tail | szero");
 #undef NS6_OFF
-static_assert(sizeof(Pipe6Lds) == 24624, "the figure in the comment at kP1Ring");
+static_assert(sizeof(Pipe6Lds) == 24944, "the figure in the comment at kP1Ring");
 
 /* SLOTS: kSlots for the stage-0 buffer, kSlots1 for the stage-1 buffer */
 template <int SLOTS>
@@ -272,10 +299,19 @@ __device__ __forceinline__ void load_back_const(NsConst &C, const sea_ns_tables 
 }
 
 template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands over the DC differences */,
-          bool STEADY_LOOP /* the flag-free copy of every role's beat on its steady range (run_beats) */>
+          bool STEADY_LOOP /* the flag-free copy of every role's beat on its steady range (run_beats) */,
+          bool REDEAL = false /* round 8, the dense kernel: feed-forward work of S and B0 in the waves that wait, and the map that goes with it */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 {
-    constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u);
+    static_assert(!REDEAL || (!LIGHT && !DIFG1), "the re-deal is a variant of the dense body");
+    constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u);
+    /* REDEAL moves two pieces whose inputs do not depend on the recursive state (profiles/ns6_redeal.txt):
+     *   LOG_N1  the VAD log-energy: N1, which holds no transform tables and waited 1300 clk per beat, takes it one beat after S left the
+     *           sum (LIGHT's timing, with N1 for FA: FA is the register-bound role of the 72-VGPR kernel)
+     *   FIR_FA  the stage-0 17-tap filter: B0 stops at the nine IDCT sums, FA windows them and filters in the beat in which it reads the output
+     * Same operations in the same order.  With them the roles are near 2400-2950 clk each instead of 1770-3110, and the wave -> role map
+     * that was best before is no longer: kRedealPerm. */
+    constexpr bool LOG_N1 = REDEAL, FIR_FA = REDEAL;
     const int lane = threadIdx.x & 63;
     /* LIGHT / DIFG1 (the forms for up to two utterances per CU, where the run time is one utterance's chain of frames): the helper
      * wave S was this form's longest role (3397 clk per frame alone, B0 3089, G1 2985, N1 2623, FB 2608, FA 2268): (LIGHT) the VAD's
@@ -286,7 +322,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
      * limit and the same change costs 2 % there (1.99 against 1.95 ms).
      * The placement of the roles on the SIMDs decides at four utterances per CU (round 3, before the dense form: identity
      * 3.19 ms, 0104352 (B0, S, N1, G1, FA, FB) 2.78 ms, the ten even / odd splits in wave order 2.97-3.26 ms). */
-    const int role = ((a.perm6 ? a.perm6 : kDefaultPerm) >> (3 * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6))) & 7;
+    const int role = ((a.perm6 ? a.perm6 : (REDEAL ? kRedealPerm : kDefaultPerm)) >> (3 * __builtin_amdgcn_readfirstlane(threadIdx.x >> 6))) & 7;
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
     const long long off = a.offsets[u];
     /* frame counts and counters are 32-bit and scalar: 2^31 frames would be 172 G samples, in and out 687 GB, more than the device's
@@ -346,6 +382,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         float win8[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) win8[k] = a.tables->win8[k][lane];
+        const float irWin = FIR_FA ? a.tables->irWin[lane] : 0.0f; /* lane k = 0..8: the Hanning weight of tap 8 +- k */
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
         uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
         int onset = kNoOnset; /* index of the first non-zero frame */
@@ -380,6 +417,16 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             /* stage 1, frame i-3 (B0 finished it at the previous iteration): NoiseSup.c:1178 <=> tick >= 5 */
             const int t1 = tick_of(i - 3, onset);
             const bool actB = beat_flag<V, ns6plan::FA, 3, 5, STEADY>(i, onset, nfr);
+            if constexpr (FIR_FA) {
+                /* stage-0 filter of frame i-3 from the IDCT sums B0 left at the previous iteration; from tick 3, not 5: ticks 3 and 4
+                 * leave output that the first stage-1 window reads.  Also in the drain, where FA has no frame of its own. */
+                if (beat_flag<V, ns6plan::FA, 3, 3, STEADY>(i, onset, nfr)) {
+                    float y0, y1;
+                    ns_fir_from_idct_rec(L.tap[(i - 3) & 1].rec, irWin, L.circ0 + window_base<kSlots>(t1), lane, y0, y1);
+                    if (lane < 40) slot_store<kSlots1>(L.circ1, t1, lane, y0, y1);
+                    wave_sync();
+                }
+            }
             if (actA || actB) {
                 wave_sync();
                 float e[8];
@@ -444,12 +491,18 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 int bits = 0;
                 /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
                  * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
-                float y01[2] = {0.0f, 0.0f};
-                ns_back<0, true, FD, true>(r.psd, L.circ0 + window_base<kSlots>(t), L.back[0], s, C, nullptr, lane,
-                                     (LIGHT ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)], o.den, L.idctT, &fd, &bits, nullptr,
-                                     y01);
-                if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
-                if (lane < 40) slot_store<kSlots1>(L.circ1, t, lane, y01[0], y01[1]);
+                const float frameEn = ((LIGHT || LOG_N1) ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)];
+                if constexpr (FIR_FA) { /* stop at the nine IDCT sums; FA windows them and filters at the next iteration */
+                    ns_back<0, true, FD, true, SEA_NMEL>(r.psd, nullptr, L.back[0], s, C, L.tap[f & 1].rec, lane, frameEn, o.den, L.idctT,
+                                                         &fd, &bits);
+                    if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
+                } else {
+                    float y01[2] = {0.0f, 0.0f};
+                    ns_back<0, true, FD, true>(r.psd, L.circ0 + window_base<kSlots>(t), L.back[0], s, C, nullptr, lane, frameEn, o.den,
+                                               L.idctT, &fd, &bits, nullptr, y01);
+                    if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
+                    if (lane < 40) slot_store<kSlots1>(L.circ1, t, lane, y01[0], y01[1]);
+                }
             }
             NS6_T_MID;
             block_sync();
@@ -469,6 +522,13 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
             const int f = i - 5, fg = i - 7;
+            if constexpr (LOG_N1) { /* the log-energy of the sum S left one beat ago, as FA takes it with LIGHT; B0 reads it two beats on */
+                if (beat_flag<V, ns6plan::N1, 2, 1, STEADY>(i, onset, nfr)) {
+                    const int e = (tick_of(i - 2, onset) + 2) & (kSlots - 1);
+                    const float en = vad_frame_energy(L.frameEn[e]);
+                    if (lane == 0) L.frameEnLog[e] = en;
+                }
+            }
             if (beat_flag<V, ns6plan::N1, 7, 5, STEADY>(i, onset, nfr)) {
                 const int t = tick_of(fg, onset);
                 /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
@@ -570,7 +630,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 helper_chains<kSChunks, false, true>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane, nullptr, nullptr,
                                                      nullptr, nzSrc, &nzTotal);
                 if (doVad) {
-                    const float en = LIGHT ? vadSum : vad_frame_energy(vadSum); /* LIGHT: FA takes the log one beat later */
+                    const float en = (LIGHT || LOG_N1) ? vadSum : vad_frame_energy(vadSum); /* FA (LIGHT) or N1 takes the log one beat later */
                     if (lane == 0) L.frameEn[(tp + 2) & (kSlots - 1)] = en;
                 }
                 if (doDen && lane == 0) L.denSum[td & (kSlots - 1)] = denTotal;
@@ -619,8 +679,8 @@ __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
     __shared__ p6::Pipe6Lds L;
     p6::ns_pipe6_body<false, true, true, false>(a, L);
 }
-/* The same body compiled for SEVEN waves per SIMD (71 VGPRs, thirty SGPRs spilled to lanes, no scratch): the form for three or four utterances per CU
- * (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
+/* The same body compiled for SEVEN waves per SIMD (72 VGPRs, five SGPRs spilled to lanes, no scratch; since round 8 with REDEAL and its own
+ * wave -> role map): the form for three or four utterances per CU (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
  * dispatcher, which deals the six waves of a workgroup 2 / 2 / 1 / 1 over the SIMDs, does not find room for the fourth: it
  * waited for one of the first three to end (configs[1]: 3.20 ms, which rounds 1-3 read as "the six-wave form loses at four
  * per CU").  One wave slot of slack per SIMD lets all four co-reside: 2.14 ms without priorities, **2.00-2.05 ms** with the
@@ -639,7 +699,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false, true>(a, L);
+    p6::ns_pipe6_body<false, false, false, true, true>(a, L);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
