@@ -874,6 +874,61 @@ __device__ __forceinline__ float ns_mel_fb(const BackLds &B, const NsConst &C, i
     return melOut;
 }
 
+/* The 25 values of the IDCT basis in LDS ([f][16]) that row l multiplies, as ONE batch of reads ahead of the in-order sum (the
+ * latency-bound six-wave forms).  The sum is a chain of 25 dependent additions; with the reads written into it the compiler
+ * requests them two at a time, three to four instructions ahead of their use, and the nine row lanes sit through the LDS latency
+ * six to seven times per frame for values that never change.  ns_idct_basis_request issues the reads; ns_idct_basis_take, placed
+ * after the 25 lane reads of the mel gains (which cover the latency), makes the values opaque so that no read sinks back to its
+ * use.  They are live only over the sum (the basis does not become resident). */
+__device__ __forceinline__ void ns_idct_basis_request(const float *idctLds, int l, float (&b)[SEA_NMEL])
+{
+#pragma unroll
+    for (int f = 0; f < SEA_NMEL; ++f) b[f] = idctLds[f * 16 + l];
+    __builtin_amdgcn_sched_barrier(0); /* issued here: the compiler neither sinks the reads to the sum nor lifts the take over the lane reads */
+}
+__device__ __forceinline__ void ns_idct_basis_take(float (&b)[SEA_NMEL])
+{
+    static_assert(SEA_NMEL == 25, "the operand list below");
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]), "+v"(b[8]),
+                      "+v"(b[9]), "+v"(b[10]), "+v"(b[11]), "+v"(b[12]), "+v"(b[13]), "+v"(b[14]), "+v"(b[15]), "+v"(b[16]),
+                      "+v"(b[17]), "+v"(b[18]), "+v"(b[19]), "+v"(b[20]), "+v"(b[21]), "+v"(b[22]), "+v"(b[23]), "+v"(b[24]));
+}
+
+/* The in-order sum of ns_idct_taps<true, true> with the basis in TWO batches of reads (ns_idct_basis_request has the why): the
+ * first is issued ahead of the 25 lane reads, which cover its latency; the second once kLate terms of the first are added, and
+ * arrives behind the rest of them.  One batch of 25 costs the dense six-wave kernel, whose G1 holds 68 of the 72 VGPRs here, a
+ * spilled register; this keeps 21 values in flight at the most.  The scheduling barriers keep the compiler from sinking a batch
+ * to its first use.  Every lane computes (no divergence); lanes above 8 repeat row 8. */
+__device__ __forceinline__ float ns_idct_sum_two_batches(float melOut, int lane, const float *idctLds)
+{
+    constexpr int kA = 13, kLate = 4;
+    int l = (lane <= 8) ? lane : 8;
+    float mf[SEA_NMEL], ba[kA], bb[SEA_NMEL - kA];
+#pragma unroll
+    for (int f = 0; f < kA; ++f) ba[f] = idctLds[f * 16 + l];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int f = 0; f < SEA_NMEL; ++f) mf[f] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(melOut), f));
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+v"(ba[0]), "+v"(ba[1]), "+v"(ba[2]), "+v"(ba[3]), "+v"(ba[4]), "+v"(ba[5]), "+v"(ba[6]), "+v"(ba[7]),
+                      "+v"(ba[8]), "+v"(ba[9]), "+v"(ba[10]), "+v"(ba[11]), "+v"(ba[12]));
+    float h = 0.0f;
+#pragma unroll
+    for (int f = 0; f < kLate; ++f) h += mf[f] * ba[f];
+    asm("" : "+v"(l) : "v"(h)); /* the second batch not before these terms */
+#pragma unroll
+    for (int f = kA; f < SEA_NMEL; ++f) bb[f - kA] = idctLds[f * 16 + l];
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int f = kLate; f < kA; ++f) h += mf[f] * ba[f];
+    asm volatile("" : "+v"(bb[0]), "+v"(bb[1]), "+v"(bb[2]), "+v"(bb[3]), "+v"(bb[4]), "+v"(bb[5]), "+v"(bb[6]), "+v"(bb[7]),
+                      "+v"(bb[8]), "+v"(bb[9]), "+v"(bb[10]), "+v"(bb[11]) : "v"(h)); /* behind the first batch's sum */
+#pragma unroll
+    for (int f = kA; f < SEA_NMEL; ++f) h += mf[f] * bb[f - kA];
+    return h;
+}
+
 /* DoMelIDCT rows 0..8 (MelProc.c:357-378), mirror + Hanning(17) (NoiseSup.c:660-669), then ApplyWF:
  * the 17-tap FIR over buf[80..159] with 8 samples of context either side (NoiseSup.c:324-340);
  * lanes 0..39 produce two outputs each into dst.  Ends with wave_sync().
@@ -884,6 +939,15 @@ __device__ __forceinline__ void ns_idct_taps(float melOut, BackLds &B, const NsC
     /* RL (the latency-bound kernel forms): band f's gain sits in lane f and reaches the nine row lanes through
      * v_readlane (a scalar operand of the multiply) instead of an LDS store, a fence and seven broadcast reads.
      * The issue-bound forms keep the LDS route: 25 lane reads are 25 more vector instructions. */
+    if constexpr (RL && LDSBASIS) { /* the six-wave forms' G1 */
+        const float tap = ns_idct_sum_two_batches(melOut, lane, idctLds) * C.irWin;
+        if (lane <= 8) {
+            B.fir[8 + lane] = tap;
+            B.fir[8 - lane] = tap;
+        }
+        wave_sync();
+        return;
+    }
     float mf[SEA_NMEL];
     if (RL) {
 #pragma unroll
@@ -920,14 +984,26 @@ __device__ __forceinline__ void ns_idct_taps(float melOut, BackLds &B, const NsC
  * remaining gains; the consumer continues with terms K .. 24 in the same order, then windows and mirrors the taps.
  * rec layout: [0..24] mel gains (only K.. are read), [28..36] partial sums of rows 0..8. */
 /* bregs (optional): the lane's basis column in registers (bregs[f] = basis[f][min(lane, 8)]) instead of 25 LDS reads per frame */
-template <int K>
+/* BATCH (K = SEA_NMEL, no bregs: the dense six-wave form's B0): the basis from LDS as one batch of reads (ns_idct_basis_request) */
+template <int K, bool BATCH = false>
 __device__ __forceinline__ void ns_idct_head(float melOut, float *rec, int lane, const float *idctLds, const float *bregs = nullptr)
 {
     float h = 0.0f;
     const int l = (lane <= 8) ? lane : 8;
+    if constexpr (BATCH) {
+        static_assert(K == SEA_NMEL, "the batch is the whole column");
+        float mf[SEA_NMEL], b[SEA_NMEL];
+        ns_idct_basis_request(idctLds, l, b);
 #pragma unroll
-    for (int f = 0; f < K; ++f)
-        h += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(melOut), f)) * (bregs ? bregs[f] : idctLds[f * 16 + l]);
+        for (int f = 0; f < K; ++f) mf[f] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(melOut), f));
+        ns_idct_basis_take(b);
+#pragma unroll
+        for (int f = 0; f < K; ++f) h += mf[f] * b[f];
+    } else {
+#pragma unroll
+        for (int f = 0; f < K; ++f)
+            h += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(melOut), f)) * (bregs ? bregs[f] : idctLds[f * 16 + l]);
+    }
     if (lane <= 8) rec[28 + lane] = h;
     if (lane >= K && lane < SEA_NMEL) rec[lane] = melOut;
     wave_sync();
@@ -1072,6 +1148,20 @@ __device__ __forceinline__ float ns_idct_tap_rl(float melOut, float irWin, int l
         h += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(melOut), f)) * (bregs ? bregs[f] : idctLds[f * 16 + l]);
     return h * irWin;
 }
+/* ns_idct_tap_rl on the basis in LDS, fetched as one batch of reads (ns_idct_basis_request): the same sum */
+__device__ __forceinline__ float ns_idct_tap_rl_batch(float melOut, float irWin, int lane, const float *idctLds)
+{
+    const int l = (lane <= 8) ? lane : 8;
+    float mf[SEA_NMEL], b[SEA_NMEL];
+    ns_idct_basis_request(idctLds, l, b);
+#pragma unroll
+    for (int f = 0; f < SEA_NMEL; ++f) mf[f] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(melOut), f));
+    ns_idct_basis_take(b);
+    float h = 0.0f;
+#pragma unroll
+    for (int f = 0; f < SEA_NMEL; ++f) h += mf[f] * b[f];
+    return h * irWin;
+}
 /* ns_idct_tail with the tap left in lane k instead of the 17 taps in LDS */
 template <int K>
 __device__ __forceinline__ float ns_idct_tail_rl(const float *rec, const float *idctLds, float irWin, int lane)
@@ -1161,7 +1251,8 @@ __device__ unsigned long long g_back_ck[16];
  * IDCT_HEAD = K >= 0: stop inside the IDCT -- add only the first K terms of its sums and deposit the partial sums and the
  *   remaining mel gains in dst (ns_idct_head); the consumer wave, which has cycles to spare, finishes them into the taps
  *   (ns_idct_tail, ns_idct_tail_rl) and runs the FIR itself. */
-template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1, bool NF = false /* see ns_ln */>
+template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1, bool NF = false /* see ns_ln */,
+          bool LDSB = false /* the six-wave forms: the IDCT basis from LDS as one batch of reads (ns_idct_basis_request), no bregs */>
 __device__ __forceinline__ void ns_back(const float *psd, const float *buf, BackLds &B, NsRegs &s,
                                         const NsConst &C, float *dst, int lane, float frameEnExt = 0.0f,
                                         float *spectOut = nullptr, const float *idctLds = nullptr,
@@ -1314,9 +1405,12 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
     }
     NS_BACK_CK(3); /* in-order sum, gain factor */
     if constexpr (IDCT_HEAD >= 0) {
-        ns_idct_head<IDCT_HEAD>(melOut, dst, lane, idctLds, bregs);
+        ns_idct_head<IDCT_HEAD, LDSB>(melOut, dst, lane, idctLds, bregs);
     } else if (RL && PIPE && yRegs) {
-        ns_fir_regs(fir_taps_rl(ns_idct_tap_rl(melOut, C.irWin, lane, idctLds, bregs)), buf, lane, yRegs[0], yRegs[1]);
+        if constexpr (LDSB)
+            ns_fir_regs(fir_taps_rl(ns_idct_tap_rl_batch(melOut, C.irWin, lane, idctLds)), buf, lane, yRegs[0], yRegs[1]);
+        else
+            ns_fir_regs(fir_taps_rl(ns_idct_tap_rl(melOut, C.irWin, lane, idctLds, bregs)), buf, lane, yRegs[0], yRegs[1]);
     } else {
         ns_idct_fir<PIPE, RL>(melOut, B, C, buf, dst, lane, idctLds);
     }
@@ -1373,6 +1467,10 @@ __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const
     /* the fast-division domain as in ns_back: this wave sees every frame's PSD too and owns den; the noise
      * magnitudes arrive from the N1 wave (>= eps by its clamp) */
     const float nSigLo = psd[lane], nSigHi = psd[64], nzLo = noise[lane], nzHi = noise[64];
+    /* the mean PSD with the same batch of reads, ahead of the ballots and the branch: both branches start from it (opaque, or the
+     * reads sink behind the branch and cost a round trip of their own) */
+    float PLo = P[lane], PHi = P[64];
+    asm volatile("" : "+v"(PLo), "+v"(PHi));
     const bool psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
     const bool noiseOk = __ballot(!(nzLo <= 0x1p29f && nzHi <= 0x1p29f)) == 0ull;
     const bool fast = psdOk && noiseOk && (s.psdOk[1] != 0);
@@ -1380,7 +1478,7 @@ __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const
     float WLo, WHi;
     if (fast) { /* as filter_bins_fast: the lean square root (valid on the domain), the pair (lane, 64) through the packed form */
         const ns_v2f nSig = {SEA_SQRT(nSigLo), SEA_SQRT(nSigHi)};
-        const ns_v2f Pq = {SEA_SQRT(P[lane]), SEA_SQRT(P[64])};
+        const ns_v2f Pq = {SEA_SQRT(PLo), SEA_SQRT(PHi)};
         ns_v2f den = {s.denLo[1], s.denHi[1]};
         const ns_v2f W = gain_bin2(Pq, nSig, ns_v2f{nzLo, nzHi}, den);
         s.denLo[1] = den.x;
@@ -1388,8 +1486,8 @@ __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const
         WLo = W.x;
         WHi = W.y;
     } else {
-        WLo = gain_bin<false>(sqrtf(P[lane]), sqrtf(nSigLo), nzLo, s.denLo[1]);
-        WHi = gain_bin<false>(sqrtf(P[64]), sqrtf(nSigHi), nzHi, s.denHi[1]);
+        WLo = gain_bin<false>(sqrtf(PLo), sqrtf(nSigLo), nzLo, s.denLo[1]);
+        WHi = gain_bin<false>(sqrtf(PHi), sqrtf(nSigHi), nzHi, s.denHi[1]);
     }
     B.wbuf[lane] = WLo;
     if (lane == 0) B.wbuf[64] = WHi;
@@ -1408,6 +1506,10 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
                                              int lane, const float *idctLds, float &lastIn)
 {
     const float nSigLo = psd[lane], nSigHi = psd[64], nzLo = noise[lane], nzHi = noise[64];
+    /* the mean PSD with the same batch of reads, ahead of the ballots and the branch: both branches start from it (opaque, or the
+     * reads sink behind the branch and cost a round trip of their own) */
+    float PLo = P[lane], PHi = P[64];
+    asm volatile("" : "+v"(PLo), "+v"(PHi));
     const bool psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
     const bool noiseOk = __ballot(!(nzLo <= 0x1p29f && nzHi <= 0x1p29f)) == 0ull;
     const bool fast = psdOk && noiseOk && (s.psdOk[1] != 0);
@@ -1415,7 +1517,7 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
     float WLo, WHi;
     if (fast) { /* as filter_bins_fast: the lean square root (valid on the domain), the pair (lane, 64) through the packed form */
         const ns_v2f nSig = {SEA_SQRT(nSigLo), SEA_SQRT(nSigHi)};
-        const ns_v2f Pq = {SEA_SQRT(P[lane]), SEA_SQRT(P[64])};
+        const ns_v2f Pq = {SEA_SQRT(PLo), SEA_SQRT(PHi)};
         ns_v2f den = {s.denLo[1], s.denHi[1]};
         const ns_v2f W = gain_bin2(Pq, nSig, ns_v2f{nzLo, nzHi}, den);
         s.denLo[1] = den.x;
@@ -1423,8 +1525,8 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
         WLo = W.x;
         WHi = W.y;
     } else {
-        WLo = gain_bin<false>(sqrtf(P[lane]), sqrtf(nSigLo), nzLo, s.denLo[1]);
-        WHi = gain_bin<false>(sqrtf(P[64]), sqrtf(nSigHi), nzHi, s.denHi[1]);
+        WLo = gain_bin<false>(sqrtf(PLo), sqrtf(nSigLo), nzLo, s.denLo[1]);
+        WHi = gain_bin<false>(sqrtf(PHi), sqrtf(nSigHi), nzHi, s.denHi[1]);
     }
     B.wbuf[lane] = WLo;
     if (lane == 0) B.wbuf[64] = WHi;
@@ -1432,7 +1534,7 @@ __device__ __forceinline__ void ns_gain1_dif(const float *psd, const float *P, c
     float melOut = ns_mel_fb(B, C, lane);
     melOut = (float)((double)(alfaGF * melOut) + (1.0 - (double)alfaGF) * 1.0);
     float d0, d1;
-    lastIn = ns_fir_dif_rl(fir_taps_rl(ns_idct_tap_rl(melOut, C.irWin, lane, idctLds)), buf, lane, lastIn, d0, d1);
+    lastIn = ns_fir_dif_rl(fir_taps_rl(ns_idct_tap_rl_batch(melOut, C.irWin, lane, idctLds)), buf, lane, lastIn, d0, d1);
     if (lane < 40) *reinterpret_cast<float2 *>(dif + 2 * lane) = make_float2(d0, d1);
     wave_sync();
 }

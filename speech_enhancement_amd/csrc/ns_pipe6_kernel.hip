@@ -38,6 +38,16 @@
  * and that kernel has a wave -> role map of its own (kRedealPerm).  The plain and the _fd kernel run what is described above.
  * configs[1]: 1.71 -> 1.66 ms (profiles/ns6_redeal.txt).
  *
+ * Round 9, all three kernels, scheduling only: what S, G1 and B0 waited for in turn is fetched as batches of LDS reads --
+ *   wave S   the prep of its chains (squares of the frame, differences of G1's output) from ONE batch in lanes 0..39, where four
+ *            round trips over 64 + 16 lanes were
+ *   wave B0  the 25 IDCT basis values ahead of the lane reads of the mel gains, then the unchanged in-order sum (ns_core.h,
+ *            ns_idct_basis_request); G1 of the plain and the _fd kernel likewise
+ *   wave G1  of the dense kernel: the same in two batches, 13 + 12 (one of 25 spills a register there); the mean PSD with its first reads
+ * S 2935 -> 2700, G1 2920 -> 2720, B0 2640 -> 2365 clk per frame.  256 utterances 1.541 -> 1.412 ms, 768 1.609 -> 1.544, the _fd
+ * kernel on 512 2.669 -> 2.433 (B0 sets those kernels' period); configs[1] 1.66 -> 1.64 ms, the same 0.020 ms in three alternations,
+ * which is over three times the spread in one of them only (profiles/ns6_lds_batches.txt).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -493,12 +503,12 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                  * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
                 const float frameEn = ((LIGHT || LOG_N1) ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)];
                 if constexpr (FIR_FA) { /* stop at the nine IDCT sums; FA windows them and filters at the next iteration */
-                    ns_back<0, true, FD, true, SEA_NMEL>(r.psd, nullptr, L.back[0], s, C, L.tap[f & 1].rec, lane, frameEn, o.den, L.idctT,
+                    ns_back<0, true, FD, true, SEA_NMEL, false, true>(r.psd, nullptr, L.back[0], s, C, L.tap[f & 1].rec, lane, frameEn, o.den, L.idctT,
                                                          &fd, &bits);
                     if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
                 } else {
                     float y01[2] = {0.0f, 0.0f};
-                    ns_back<0, true, FD, true>(r.psd, L.circ0 + window_base<kSlots>(t), L.back[0], s, C, nullptr, lane, frameEn, o.den,
+                    ns_back<0, true, FD, true, -1, false, true>(r.psd, L.circ0 + window_base<kSlots>(t), L.back[0], s, C, nullptr, lane, frameEn, o.den,
                                                L.idctT, &fd, &bits, nullptr, y01);
                     if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
                     if (lane < 40) slot_store<kSlots1>(L.circ1, t, lane, y01[0], y01[1]);
@@ -607,23 +617,28 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             const float *nzSrc = L.rn[fn & (kRnRing - 1)].noise;
             const bool haveOut = STEADY || (fo >= 0 && fo < nfr);
             float2 vOut = make_float2(0.0f, 0.0f);
-            if (doVad) {
-                const float *frame = L.circ0 + (tp & (kSlots - 1)) * kSlotLen;
-                const float x = frame[lane];
-                L.ssq[lane] = x * x;
-                if (lane < 16) {
-                    const float yv = frame[64 + lane];
-                    L.ssq[64 + lane] = yv * yv;
+            /* The prep of the chains, round 9: lanes 0..39 take samples 2l and 2l + 1 (lanes >= 40 repeat lane 39, stores included:
+             * the same values to the same words), and every operand -- the frame's pair for the squares, G1's pair, its predecessor
+             * and y2[79] for the differences and the next dcX -- is fetched in ONE batch of LDS reads before the first use.  It
+             * used to be four round trips in sequence (64 + 16 lanes, twice).  The reads are unconditional: the slot indices are
+             * masked, a record nobody has written yet holds garbage, and what is computed from it is stored under the flags only. */
+            const int l2 = (lane < 40) ? lane : 39;
+            float2 sqIn = *reinterpret_cast<const float2 *>(L.circ0 + (tp & (kSlots - 1)) * kSlotLen + 2 * l2);
+            const float *difS = DIFG1 ? L.ro[fo & 1].out : L.sdif; /* DIFG1: G1 left the differences themselves */
+            if constexpr (DIFG1) { /* no difference pass: the square half alone */
+                asm volatile("" : "+v"(sqIn.x), "+v"(sqIn.y));
+            } else {
+                const float *y2 = L.ro[fo & 1].out;
+                float2 yIn = *reinterpret_cast<const float2 *>(y2 + 2 * l2);
+                float below = y2[(l2 > 0) ? 2 * l2 - 1 : 0], last = y2[79];
+                asm volatile("" : "+v"(sqIn.x), "+v"(sqIn.y), "+v"(yIn.x), "+v"(yIn.y), "+v"(below), "+v"(last));
+                if (produced) {
+                    const float xm1 = (lane == 0) ? dcX : below; /* lane 0's predecessor: prevSamples */
+                    *reinterpret_cast<float2 *>(L.sdif + 2 * l2) = make_float2(yIn.x - xm1, yIn.y - yIn.x);
+                    dcX = last;
                 }
             }
-            const float *difS = DIFG1 ? L.ro[fo & 1].out : L.sdif; /* DIFG1: G1 left the differences themselves */
-            if (produced && !DIFG1) {
-                const float *y2 = L.ro[fo & 1].out;
-                const float xm1 = (lane == 0) ? dcX : y2[lane - 1];
-                L.sdif[lane] = y2[lane] - xm1;
-                if (lane < 16) L.sdif[64 + lane] = y2[64 + lane] - y2[63 + lane];
-                dcX = y2[79];
-            }
+            if (doVad) *reinterpret_cast<float2 *>(L.ssq + 2 * l2) = make_float2(sqIn.x * sqIn.x, sqIn.y * sqIn.y);
             if (doVad || doDen || doNz || produced) {
                 wave_sync();
                 float vadSum, denTotal, nzTotal, y = dcY;
@@ -671,7 +686,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 /* launched for at most two utterances per CU (capi.hip::ns_pick_form): twelve waves per CU, three per SIMD, so the
  * register allocation could use up to 168 VGPRs.  The plain form stays compiled for 80 (measured: 1644 against 1679 ns
  * per frame with the looser bound, which only changes the schedule); the _fd form takes the looser bound, which
- * removes its 7 spilled registers (91 VGPRs).  Today the plain form takes 68 VGPRs and the _fd form 82, nothing spilled.
+ * removes its 7 spilled registers (91 VGPRs).  Today the plain form takes 68 VGPRs, nothing spilled, and the _fd form 93 with 6 SGPRs
+ * spilled to lanes (82 and none before round 9's batches), no scratch.
  * STEADY_LOOP: off here -- with the steady copies this form ran 2.1 % (256 utterances) and 2.6 % (768) slower, its period is B0's beat,
  * the one role they did not shorten; on in the dense form (-2.9 %) and in the _fd form (-1.9 %).  profiles/ns6_steady_loop.txt */
 __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
@@ -679,7 +695,7 @@ __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
     __shared__ p6::Pipe6Lds L;
     p6::ns_pipe6_body<false, true, true, false>(a, L);
 }
-/* The same body compiled for SEVEN waves per SIMD (72 VGPRs, five SGPRs spilled to lanes, no scratch; since round 8 with REDEAL and its own
+/* The same body compiled for SEVEN waves per SIMD (72 VGPRs, two SGPRs spilled to lanes, no scratch; since round 8 with REDEAL and its own
  * wave -> role map): the form for three or four utterances per CU (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
  * dispatcher, which deals the six waves of a workgroup 2 / 2 / 1 / 1 over the SIMDs, does not find room for the fourth: it
  * waited for one of the first three to end (configs[1]: 3.20 ms, which rounds 1-3 read as "the six-wave form loses at four
