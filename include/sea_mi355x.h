@@ -490,8 +490,8 @@ int sea_trainset_last_chunks(void);
  * HuWang.cpp:41-76) on its 25-channel 8 kHz gammatone bank: AudiPeriph (gammatone + Meddis hair cell, hOut in float), lowPass
  * (hEv), computeACF, crossCorr, globalPitch, timeCrn (corrHc) and the initial labelling of Grp (csrc/hw25_kernel.hip,
  * DESIGN.md section 5.11).  Parity: bit for bit against the reference's own functions compiled on a CPU
- * (tests/golden/hw25_golden.npz).  initGroup and pitchDtm follow below (sea_hw25_pitch_*); computeAM, finalSeg and resynthesis
- * are not built.
+ * (tests/golden/hw25_golden.npz).  initGroup and pitchDtm follow below (sea_hw25_pitch_*), then computeAM, finalSeg and the
+ * whole estimator (sea_hw25_am_batch, sea_hw25_finalseg_batch, sea_hw25_ibm*); resynthesis is not built.
  * Samples are floats on the int16 scale, as createIBM takes them.  Batch forms (device pointers): d_in_f32 holds the packed
  * batch, utterance u at d_offsets[u] (multiples of 8; the stretch up to the next multiple of 8 past its length must be
  * readable); d_hout / d_hev hold 25x the packed size, utterance u's [25][pitch] block at d_offsets[u] * 25, pitch =
@@ -560,6 +560,68 @@ int sea_hw25_pitch_batch(const float *d_acf_hc, const float *d_cross_hc, const f
                          const long long *d_lengths, const long long *d_row_offsets, int *d_pitch, float *d_grp, float *d_pratio,
                          int *d_status, void *d_stages, void *d_scratch, const int *d_order, int n_utt, void *stream);
 int sea_hw25_pitch(const float *x, long L, int *pitch, float *grp, float *pratio, int *status);
+/* The rest of createIBM() on the same bank: computeAM (HuWang.cpp:1146-1317: amPatt, hilbert, computeAMRate, sinModel, with
+ * kaiserPara / kaiserBandPass / bessi0 / fft:1553-1677), finalSeg (:1321-1494: reSegmentation, develope) and the binarisation
+ * :99-106 (csrc/hw25_am_kernel.hip).  After it sea_hw25_ibm (x) is createIBM (x).
+ * Parity (tests/golden/hw25_am_golden.npz, the reference's own functions compiled on a CPU): gOut, the AM pattern before and
+ * after its normalisation and sEng bit for bit.  sinModel calls cosf, sinf and atanf on data; the C library's are not correctly
+ * rounded and cannot be reproduced, so each is evaluated in double and rounded to float: ratio = error / sEng agrees to the
+ * fixture's ratio_tol, and the label, every stage of finalSeg and the mask are equal wherever no ratio lies within that band of
+ * THETAE = 0.20 (the fixture has no such unit).
+ * sea_hw25_periphery_gout_batch is sea_hw25_periphery_batch with one more output: d_gout, gammaToneFilter's output before the
+ * hair cell, in d_hout's layout (null: not written, exactly sea_hw25_periphery_batch).
+ * sea_hw25_am_batch: inputs d_gout and d_pitch [rows] (sea_hw25_pitch_batch's; 0 = unvoiced, else 16..100), not modified.
+ * Outputs d_amcrn [rows][25] floats 0 / 1, AmCrn; optional (null: not written) d_ratio and d_seng [rows][25] (error / sEng, 0
+ * where sinModel does not run; sEng) and d_ampatt, d_am in d_gout's layout (amPatt's output; the same over its envelope).
+ * d_status [n_utt]: flags only.  d_scratch must hold sea_hw25_am_scratch_bytes (total_padded_samples, n_utt) bytes, the same
+ * total_padded_samples (the extent of the packed sample space: the largest d_offsets[u] + lengths[u] rounded up to 8) being
+ * passed to the call: it decides whether the FFT (two complex buffers of 2 x the padded length per channel) runs over all 25
+ * channels at once or in five groups of five channels.
+ * sea_hw25_finalseg_batch: inputs d_grp and d_pratio (sea_hw25_pitch_batch's outputs), d_amcrn, d_cross_ev [rows][25], not
+ * modified.  Outputs d_mask [rows][25] floats 0 / 1; d_status [n_utt] flags; optional d_grp_final [rows][25] in {-1, 0, 1}, Grp
+ * before the binarisation, and d_stages: utterance u's [SEA_HW25_FINAL_STAGES][rows_u][25] floats at float d_row_offsets[u] *
+ * SEA_HW25_FINAL_STAGES * 25, Grp after the relabelling that follows each reSegmentation (three), after develope (m, -1) with
+ * its relabelling, and after develope (m, 1).  d_scratch: sea_hw25_finalseg_scratch_bytes (total_rows, n_utt).
+ * sea_hw25_ibm_batch: the whole chain from packed float audio, one launch group on `stream`: d_mask [rows][25], d_pitch [rows],
+ * d_status [n_utt] (sea_hw25_pitch_batch's status with the flags of the two later stages), d_stages optional as above;
+ * d_scratch: sea_hw25_ibm_scratch_bytes (total_padded_samples, total_rows, n_utt), with the same totals passed to the call.
+ * sea_hw25_ibm: one utterance from host memory; mask [L / 80][25], pitch [L / 80] (either may be null), status [1].  L = 0 is
+ * an utterance without a frame: nothing is written but status = 0 (the batch forms take such an utterance too); L < 0 fails.
+ * The lengths stay on the device, nothing synchronises with the host, every launch is on `stream`; no output may be an input
+ * or another output (equal pointers are rejected).
+ * Where the reference is undefined, or this differs, it is defined:
+ *  - more than 150000 samples (MAX_SIG_LENGTH; the reference's Input[] overflows): SEA_HW25_AM_TOO_LONG, the AM outputs all 0,
+ *    and in sea_hw25_ibm_batch the mask all 0.  No FFT runs;
+ *  - a pitch above 100 (sea_hw25_pitch_batch never writes one): SEA_HW25_AM_BAD_PITCH, treated the same way;
+ *  - reSegmentation finds more than 400 segments (segMark[MAX_NUMBER_SEGMENT] overflows, as in initGroup):
+ *    SEA_HW25_FINAL_TOO_MANY_SEGMENTS, the mask (grp_final, the stages) all 0;
+ *  - fewer than 3 rows: the mask (grp_final, the stages) is all 0 and no flag is set; with no segment upstream grp is all 0,
+ *    no frame is voiced, and the mask is all 0 by the reference's own logic.
+ * resynthesis (:1498), which writes one waveform as a text file, is not built. */
+enum {
+    SEA_HW25_FINAL_STAGES = 5,
+    SEA_HW25_FINAL_TOO_MANY_SEGMENTS = 1 << 18,
+    SEA_HW25_AM_TOO_LONG = 1 << 19,
+    SEA_HW25_AM_BAD_PITCH = 1 << 20
+};
+int sea_hw25_periphery_gout_batch(const float *d_in_f32, float *d_hout, float *d_hev, float *d_gout, const long long *d_offsets,
+                                  const long long *d_lengths, const int *d_order, int n_utt, void *stream);
+/* a = -20 log10 (delta) and beta of kaiserPara (0.01, ..), N of computeAM:1156 at L = 2^7 .. 2^17, and fft's twiddles u of every
+ * stage (n_twiddles = 2^18 - 1 (re, im) pairs, period p's p values from entry p - 1); every pointer may be null */
+int sea_hw25_am_tables_host(float *a_beta2, int *n_at_pow2_11, float *twiddles, int n_twiddles);
+long long sea_hw25_am_scratch_bytes(long long total_padded_samples, int n_utt);
+int sea_hw25_am_batch(const float *d_gout, const int *d_pitch, const long long *d_offsets, const long long *d_lengths,
+                      const long long *d_row_offsets, float *d_amcrn, float *d_ratio, float *d_seng, float *d_ampatt, float *d_am,
+                      int *d_status, void *d_scratch, long long total_padded_samples, const int *d_order, int n_utt, void *stream);
+long long sea_hw25_finalseg_scratch_bytes(long long total_rows, int n_utt);
+int sea_hw25_finalseg_batch(const float *d_grp, const float *d_amcrn, const float *d_cross_ev, const float *d_pratio,
+                            const long long *d_lengths, const long long *d_row_offsets, float *d_mask, float *d_grp_final,
+                            int *d_status, float *d_stages, void *d_scratch, const int *d_order, int n_utt, void *stream);
+long long sea_hw25_ibm_scratch_bytes(long long total_padded_samples, long long total_rows, int n_utt);
+int sea_hw25_ibm_batch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
+                       float *d_mask, int *d_pitch, int *d_status, float *d_stages, void *d_scratch, long long total_padded_samples,
+                       long long total_rows, const int *d_order, int n_utt, void *stream);
+int sea_hw25_ibm(const float *x, long L, float *mask, int *pitch, int *status);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

@@ -23,4 +23,5 @@ from .engine import (DoCompCeps, MaskBatch, NoiseSup, PackedBatch, afe_features_
                      wb_compceps_batch_slice, denoise_ceps_utterances, wb_denoise_ceps_utterances, addnoise, addnoise_batch,
                      make_trainset, snr_lin, trainset_batch, Hw25Result, hw25_correlogram_batch, hw25_frontend,
                      hw25_frontend_batch, hw25_periphery_batch, hw25_split, hw25_tables, Hw25PitchResult, hw25_pitch,
-                     hw25_pitch_batch)
+                     hw25_pitch_batch, Hw25AmResult, Hw25MaskResult, hw25_am_batch, hw25_am_tables, hw25_finalseg_batch,
+                     hw25_ibm, hw25_ibm_batch, hw25_periphery_gout_batch)

@@ -95,6 +95,15 @@ PROTOTYPES = {
     "sea_hw25_pitch_scratch_bytes": (_ll, [_ll, _i]),
     "sea_hw25_pitch_batch": (_i, [_vp] * 13 + [_i, _vp]),
     "sea_hw25_pitch": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
+    "sea_hw25_periphery_gout_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sea_hw25_am_tables_host": (_i, [_vp, _vp, _vp, _i]),
+    "sea_hw25_am_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw25_am_batch": (_i, [_vp] * 12 + [_ll, _vp, _i, _vp]),
+    "sea_hw25_finalseg_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw25_finalseg_batch": (_i, [_vp] * 12 + [_i, _vp]),
+    "sea_hw25_ibm_scratch_bytes": (_ll, [_ll, _ll, _i]),
+    "sea_hw25_ibm_batch": (_i, [_vp] * 9 + [_ll, _ll, _vp, _i, _vp]),
+    "sea_hw25_ibm": (_i, [_vp, _l, _vp, _vp, _vp]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

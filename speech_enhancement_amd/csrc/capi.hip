@@ -42,6 +42,8 @@ sea_gt_tables g_gt_host;
 sea_ns16k_tables g_ns16_host;
 sea_wb_tables g_wb_host;
 sea_hw25_tables g_hw25_host;
+std::vector<float> g_hw25_tw; /* the forward FFT's twiddles; the inverse's are checked to be their conjugates */
+bool g_hw25_tw_conjugate = false;
 bool g_host_ready = false;
 
 void host_tables()
@@ -53,6 +55,15 @@ void host_tables()
     sea_build_ns16k_tables(&g_ns16_host);
     sea_build_wb_tables(&g_wb_host);
     sea_build_hw25_tables(&g_hw25_host);
+    {
+        std::vector<float> inv(2 * (size_t)SEA_HW25_TWIDDLES);
+        g_hw25_tw.resize(2 * (size_t)SEA_HW25_TWIDDLES);
+        sea_build_hw25_twiddles(g_hw25_tw.data(), 1);
+        sea_build_hw25_twiddles(inv.data(), -1);
+        g_hw25_tw_conjugate = true;
+        for (size_t i = 0; i < (size_t)SEA_HW25_TWIDDLES; ++i)
+            if (inv[2 * i] != g_hw25_tw[2 * i] || inv[2 * i + 1] != -g_hw25_tw[2 * i + 1]) g_hw25_tw_conjugate = false;
+    }
     g_host_ready = true;
 }
 } // namespace
@@ -83,6 +94,9 @@ int ctx(DeviceCtx **out)
         HIP_TRY(hipMemcpy(c.ns16, &g_ns16_host, sizeof g_ns16_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.wb, &g_wb_host, sizeof g_wb_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.hw25, &g_hw25_host, sizeof g_hw25_host, hipMemcpyHostToDevice));
+        if (!g_hw25_tw_conjugate) return fail("hw25: the inverse FFT's twiddles are not the conjugates of the forward ones");
+        HIP_TRY(hipMalloc(&c.hw25_tw, g_hw25_tw.size() * sizeof(float)));
+        HIP_TRY(hipMemcpy(c.hw25_tw, g_hw25_tw.data(), g_hw25_tw.size() * sizeof(float), hipMemcpyHostToDevice));
         c.ready = true;
     }
     *out = &c;
@@ -1214,13 +1228,22 @@ static int hw25_args(sea::Hw25Args &a, int n_utt)
 int sea_hw25_periphery_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
                              const long long *d_lengths, const int *d_order, int n_utt, void *stream)
 {
+    return sea_hw25_periphery_gout_batch(d_in_f32, d_hout, d_hev, nullptr, d_offsets, d_lengths, d_order, n_utt, stream);
+}
+
+int sea_hw25_periphery_gout_batch(const float *d_in_f32, float *d_hout, float *d_hev, float *d_gout, const long long *d_offsets,
+                                  const long long *d_lengths, const int *d_order, int n_utt, void *stream)
+{
     if (n_utt <= 0) return 0;
     if (!d_in_f32 || !d_hout || !d_hev || !d_offsets || !d_lengths) return fail("hw25_periphery: null pointer");
+    if (d_gout && (d_gout == d_in_f32 || d_gout == d_hout || d_gout == d_hev))
+        return fail("hw25_periphery: d_gout must be a buffer of its own");
     sea::Hw25Args a;
     if (hw25_args(a, n_utt)) return 1;
     a.in = d_in_f32;
     a.hout = d_hout;
     a.hev = d_hev;
+    a.gout = d_gout;
     a.offsets = d_offsets;
     a.lengths = d_lengths;
     a.order = d_order;

@@ -1,0 +1,505 @@
+/*
+ * hw25_am_kernel.hip -- the Hu-Wang estimator's AM labels and final grouping on the 25-channel 8 kHz bank, gfx950:
+ * computeAM:1146-1317 (amPatt, hilbert, computeAMRate, sinModel, with kaiserPara / kaiserBandPass / bessi0 / fft:1553-1677),
+ * finalSeg:1321-1494 (reSegmentation, develope) and the binarisation :99-106 of
+ * function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp.  A first form, not tuned.  DESIGN.md section 5.13.
+ *
+ *   hw25_am_prepare_kernel    per utterance: N of the FFT, whether the stage runs at all, the status flags; the outputs of an
+ *                             utterance that skips the stage are zeroed here
+ *   hw25_am_patt_kernel       amPatt: per block of five frames the Kaiser band-pass for the block's mean pitch (taps computed
+ *                             in the workgroup, lane = tap), then the FIR over max (gOut, 0), lane = sample
+ *   hw25_am_fft_head_kernel   fft's bit reversal and its stages 1..12 on 4096 points in LDS; the inverse form applies hilbert's
+ *                             doubling and zeroing to what it loads
+ *   hw25_am_fft_stage_kernel  one of the stages 13..18 over global memory; utterances with a smaller N leave
+ *   hw25_am_norm_kernel       the pattern over its envelope, computeAM:1177-1178
+ *   hw25_am_rate_kernel       computeAMRate + sinModel, lane = (frame, channel), the 200-sample loops inside the lane
+ *   hw25_finalseg_kernel      finalSeg and the binarisation, one wave per utterance
+ *
+ * Every expression keeps the type the reference's C++ gives it (a float argument selects the float overload, an expression
+ * with the double literal PI is double; -ffp-contract=off).  The one exception is sinModel's cosf / sinf / atanf: glibc's are
+ * not correctly rounded and cannot be reproduced, so each is the double function rounded to float;
+ * ratio is therefore compared with a tolerance, everything before it bit for bit.
+ */
+#include "../../include/sea_mi355x.h"
+#include "hw25_segment.h"
+#include "sea_device.h"
+#include "sea_kernels.h"
+
+namespace sea {
+
+namespace {
+
+constexpr int kCh = SEA_HW25_NCHAN, kHop = SEA_HW25_HOP, kWin = SEA_HW25_WINDOW;
+constexpr int kBlock = 5 * kHop; /* amPatt's blocks of five frames */
+constexpr int kMaxTaps = SEA_HW25_AM_MAXTAPS;
+constexpr int kLdsLog2 = SEA_HW25_AM_LDS_LOG2;
+constexpr double kPi = 3.1415926535897932384626433832795; /* HuWang.h:7 */
+constexpr unsigned kChanBits = (1u << kCh) - 1u;
+constexpr int kNone = kHw25None;
+
+__device__ __forceinline__ void lanes_fence() { __threadfence(); }
+
+/* computeAM:1156 for lengths 240 .. 150000: the integer ceil (log2 (L)), and at a power of two the constant that the
+ * reference's double expression gave on a CPU (SEA_HW25_N_AT_POW2) */
+__device__ __forceinline__ int fft_log2(long long L)
+{
+    constexpr int at_pow2[11] = SEA_HW25_N_AT_POW2;
+    const int up = 64 - __clzll(L - 1);
+    if ((L & (L - 1)) == 0 && up >= 7 && up <= 17) return at_pow2[up - 7];
+    return up;
+}
+
+struct AmUtt {
+    int u, nfr, N;
+    long long off, L, pitch, row0;
+};
+__device__ __forceinline__ AmUtt am_utterance(const Hw25AmArgs &a)
+{
+    AmUtt t;
+    t.u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    t.off = a.offsets[t.u];
+    t.L = a.lengths[t.u];
+    t.pitch = (t.L + 7) & ~7LL;
+    t.nfr = t.L > 0 ? (int)(t.L / kHop) : 0;
+    t.row0 = a.row_offsets[t.u];
+    t.N = a.info[t.u];
+    return t;
+}
+
+/* bessi0:1603-1614, its polynomial branch (|x| < 3.75 always: beta < 3.75 and the square root is at most 1) */
+__device__ __forceinline__ float bessi0_small(float x)
+{
+    float y = (float)((double)x / 3.75);
+    y *= y;
+    const double d = y;
+    return (float)(1.0 + d * (3.5156229 + d * (3.0899424 + d * (1.2067492 + d * (0.2659732 + d * (0.360768e-1 + d * 0.45813e-2))))));
+}
+
+} // namespace
+
+__global__ __launch_bounds__(64) void hw25_am_prepare_kernel(Hw25AmArgs a)
+{
+    const int lane = threadIdx.x;
+    const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    const long long off = a.offsets[u], L = a.lengths[u], row0 = a.row_offsets[u];
+    const long long pitch = (L + 7) & ~7LL;
+    const int nfr = L > 0 ? (int)(L / kHop) : 0;
+    int flags = 0;
+    bool voiced = false, bad = false;
+    if (L > SEA_HW25_MAXLEN) {
+        flags |= SEA_HW25_AM_TOO_LONG;
+    } else {
+        for (int f = lane; f < nfr; f += 64) {
+            const int p = a.pitch[row0 + f];
+            voiced = voiced || p > 0;
+            bad = bad || p >= SEA_HW25_DELAYS;
+        }
+        voiced = __any(voiced);
+        bad = __any(bad);
+        if (bad) flags |= SEA_HW25_AM_BAD_PITCH;
+    }
+    /* amPatt's first block is centred on frame 2: fewer than three frames leave the pattern at zero */
+    const bool run = flags == 0 && voiced && nfr >= 3;
+    if (lane == 0) {
+        a.info[u] = run ? fft_log2(L) : -1;
+        if (a.status_or)
+            a.status[u] |= flags;
+        else
+            a.status[u] = flags;
+    }
+    if (run) return;
+    const long long cells = (long long)nfr * kCh;
+    for (long long i = lane; i < cells; i += 64) {
+        a.amcrn[row0 * kCh + i] = 0.0f;
+        if (a.ratio) a.ratio[row0 * kCh + i] = 0.0f;
+        if (a.seng) a.seng[row0 * kCh + i] = 0.0f;
+    }
+    if (L > 0)
+        for (int c = 0; c < kCh; ++c)
+            for (long long n = lane; n < L; n += 64) {
+                a.ampatt[off * kCh + c * pitch + n] = 0.0f;
+                a.am[off * kCh + c * pitch + n] = 0.0f;
+            }
+}
+
+/* grid (n_utt, PATT_GRID, 25): workgroup (u, g, c) takes the blocks g, g + PATT_GRID, ... of channel c.  A block is the 400
+ * samples of five frames centred on frame 5 b + 2; one without that frame, or without a voiced frame, is zeros. */
+__global__ __launch_bounds__(256) void hw25_am_patt_kernel(Hw25AmArgs a)
+{
+    __shared__ float taps[kMaxTaps];
+    __shared__ float win[kBlock + kMaxTaps];
+    const int tid = threadIdx.x, c = blockIdx.z;
+    const AmUtt t = am_utterance(a);
+    if (t.N < 0) return;
+    const long long L = t.L;
+    const float *in = a.gout + t.off * kCh + c * t.pitch;
+    float *out = a.ampatt + t.off * kCh + c * t.pitch;
+    const int nblocks = (int)((L + kBlock - 1) / kBlock);
+    const float b0 = bessi0_small(a.tables->am_beta);
+    for (int b = blockIdx.y; b < nblocks; b += gridDim.y) {
+        const int frame = 5 * b + 2;
+        const long long n0 = (long long)b * kBlock;
+        /* amPatt:1199-1211: the float mean of the block's positive pitches */
+        float mp = 0.0f;
+        int count = 0;
+        if (frame < t.nfr)
+            for (int f = frame - 2; f <= frame + 2; ++f)
+                if (f < t.nfr) {
+                    const int p = a.pitch[t.row0 + f];
+                    if (p > 0) {
+                        mp += (float)p;
+                        count++;
+                    }
+                }
+        if (count == 0) {
+            for (int i = tid; i < kBlock; i += 256)
+                if (n0 + i < L) out[n0 + i] = 0.0f;
+            continue;
+        }
+        mp /= (float)count;
+        /* kaiserPara (0.01, 0.4 / mp, ..):1553-1569 with a and beta from the tables */
+        const float transBw = (float)(0.4 / (double)mp);
+        const float len = (float)(((double)a.tables->am_a - 7.95) / 14.36 / (double)transBw);
+        int fLength = (int)len;
+        if ((double)(len - (float)fLength) < 0.5)
+            fLength++;
+        else
+            fLength += 2;
+        if (fLength % 2 != 0) fLength++;
+        if (fLength + 1 > kMaxTaps) fLength = kMaxTaps - 2; /* unreachable with pitches up to 100: keeps LDS in bounds */
+        const int half = fLength / 2;
+        /* kaiserBandPass (filter, fLength, beta, 2.1 / mp, 0.7 / mp):1571-1601 */
+        const float wc = (float)(2.1 / (double)mp), wn = (float)(0.7 / (double)mp);
+        __syncthreads(); /* the last block's readers are done */
+        for (int tim = tid; tim <= fLength; tim += 256) {
+            const float k = (float)(2 * tim) / (float)fLength - 1.0f;
+            float f = bessi0_small(a.tables->am_beta * sqrtf(1.0f - k * k)) / b0;
+            const int step = tim - half;
+            if (step != 0)
+                f = (float)((double)f * (sin((double)wn * kPi * (double)step) / kPi / (double)step));
+            else
+                f *= wn;
+            taps[tim] = (float)((double)f * (2.0 * cos((double)((float)step * wc) * kPi)));
+        }
+        /* win[j] holds max (gOut, 0) at sample n0 - half + j, zero outside [0, L): a skipped term and an added zero give the
+         * same sum (it starts at +0) */
+        for (int j = tid; j < kBlock + fLength; j += 256) {
+            const long long tim = n0 - half + j;
+            float v = 0.0f;
+            if (tim >= 0 && tim < L) {
+                v = in[tim];
+                v = v > 0.0f ? v : 0.0f;
+            }
+            win[j] = v;
+        }
+        __syncthreads();
+        for (int i = tid; i < kBlock; i += 256) {
+            if (n0 + i >= L) break;
+            float sum = 0.0f;
+#pragma unroll 4
+            for (int m = 0; m <= fLength; ++m) sum += win[i + fLength - m] * taps[m]; /* tim = n + fLength / 2 - m */
+            out[n0 + i] = sum;
+        }
+    }
+}
+
+/* grid (n_utt, FFT_GRID, chunk): workgroup (u, g, z) takes the 4096-point pieces g, g + FFT_GRID, ... of channel chan0 + z.
+ * Piece k of the bit-reversed array is loaded from the reversed indices, and the stages 1 .. min (N, 12) never leave it. */
+__global__ __launch_bounds__(256) void hw25_am_fft_head_kernel(Hw25AmArgs a)
+{
+    __shared__ float2 x[1 << kLdsLog2];
+    const int tid = threadIdx.x, z = blockIdx.z, c = a.chan0 + z;
+    const AmUtt t = am_utterance(a);
+    if (t.N < 0 || c >= kCh) return;
+    const int N = t.N, K = N < kLdsLog2 ? N : kLdsLog2;
+    const long long sigL = 1LL << N, L = t.L;
+    const int points = 1 << K, pieces = (int)(sigL >> K);
+    const long long base = t.off * a.chunk * 2 + (long long)z * 2 * t.pitch;
+    const float *pat = a.ampatt + t.off * kCh + c * t.pitch;
+    const float2 *src = a.fa + base;
+    float2 *dst = (a.inverse ? a.fb : a.fa) + base;
+    const float sign = a.inverse ? -1.0f : 1.0f; /* the inverse's twiddles are the conjugates */
+    for (int piece = blockIdx.y; piece < pieces; piece += gridDim.y) {
+        __syncthreads();
+        for (int i = tid; i < points; i += 256) {
+            const unsigned gi = (unsigned)piece * (unsigned)points + (unsigned)i;
+            const long long s = (long long)(__brev(gi) >> (32 - N));
+            float2 v = make_float2(0.0f, 0.0f);
+            if (!a.inverse) {
+                if (s < L) v.x = pat[s]; /* computeAM:1170-1174 */
+            } else if (s <= sigL / 2) {  /* hilbert:1244-1254: bins 0 and sigL / 2 as they are, the ones between doubled */
+                v = src[s];
+                if (s != 0 && s != sigL / 2) {
+                    v.x *= 2.0f;
+                    v.y *= 2.0f;
+                }
+            }
+            x[i] = v;
+        }
+        __syncthreads();
+        for (int n = 1; n <= K; ++n) {
+            const int period = 1 << (n - 1);
+            const float2 *tw = a.tw + (period - 1);
+            for (int b = tid; b < points / 2; b += 256) {
+                const int j = b & (period - 1);
+                const int i = ((b >> (n - 1)) << n) + j;
+                const float uR = tw[j].x, uI = sign * tw[j].y;
+                const float2 lo = x[i], hi = x[i + period];
+                const float tmpR = hi.x * uR - hi.y * uI; /* fft:1663-1669 */
+                const float tmpI = hi.x * uI + hi.y * uR;
+                x[i + period] = make_float2(lo.x - tmpR, lo.y - tmpI);
+                x[i] = make_float2(lo.x + tmpR, lo.y + tmpI);
+            }
+            __syncthreads();
+        }
+        for (int i = tid; i < points; i += 256) dst[(long long)piece * points + i] = x[i];
+    }
+}
+
+/* stage a.stage (13 .. 18) in place over global memory: the butterflies of one stage touch disjoint pairs */
+__global__ __launch_bounds__(256) void hw25_am_fft_stage_kernel(Hw25AmArgs a)
+{
+    const int z = blockIdx.z, c = a.chan0 + z, n = a.stage;
+    const AmUtt t = am_utterance(a);
+    if (t.N < n || c >= kCh) return;
+    const long long half = 1LL << (t.N - 1);
+    const long long period = 1LL << (n - 1);
+    float2 *x = (a.inverse ? a.fb : a.fa) + t.off * a.chunk * 2 + (long long)z * 2 * t.pitch;
+    const float2 *tw = a.tw + (period - 1);
+    const float sign = a.inverse ? -1.0f : 1.0f;
+    for (long long b = (long long)blockIdx.y * 256 + threadIdx.x; b < half; b += (long long)gridDim.y * 256) {
+        const long long j = b & (period - 1);
+        const long long i = ((b >> (n - 1)) << n) + j;
+        const float uR = tw[j].x, uI = sign * tw[j].y;
+        const float2 lo = x[i], hi = x[i + period];
+        const float tmpR = hi.x * uR - hi.y * uI;
+        const float tmpI = hi.x * uI + hi.y * uR;
+        x[i + period] = make_float2(lo.x - tmpR, lo.y - tmpI);
+        x[i] = make_float2(lo.x + tmpR, lo.y + tmpI);
+    }
+}
+
+/* computeAM:1177-1178: sqrtf of a float, a float over (float) sigL, then a double sum and a double quotient rounded to float */
+__global__ __launch_bounds__(256) void hw25_am_norm_kernel(Hw25AmArgs a)
+{
+    const int z = blockIdx.z, c = a.chan0 + z;
+    const AmUtt t = am_utterance(a);
+    if (t.N < 0 || c >= kCh) return;
+    const float sigL = (float)(1LL << t.N);
+    const float2 *x = a.fb + t.off * a.chunk * 2 + (long long)z * 2 * t.pitch;
+    const float *pat = a.ampatt + t.off * kCh + c * t.pitch;
+    float *am = a.am + t.off * kCh + c * t.pitch;
+    for (long long n = (long long)blockIdx.y * 256 + threadIdx.x; n < t.L; n += (long long)gridDim.y * 256) {
+        const float2 v = x[n];
+        const float env = sqrtf(v.x * v.x + v.y * v.y) / sigL;
+        am[n] = (float)((double)pat[n] / ((double)env + 1e-30));
+    }
+}
+
+/* grid (n_utt, RATE_GRID): computeAMRate:1259-1287 and sinModel:1289-1317, lane = (frame, channel).  cosf, sinf and atanf
+ * are the double functions rounded to float. */
+__global__ __launch_bounds__(64) void hw25_am_rate_kernel(Hw25AmArgs a)
+{
+    const AmUtt t = am_utterance(a);
+    if (t.N < 0) return;
+    const int cells = t.nfr * kCh;
+    for (int i = blockIdx.y * 64 + threadIdx.x; i < cells; i += gridDim.y * 64) {
+        const int frame = i / kCh, c = i % kCh;
+        const long long shift = (long long)(frame - 1) * kHop;
+        const float *sig = a.am + t.off * kCh + c * t.pitch + shift;
+        float sEng = 0.0f;
+        if (frame < t.nfr - 1 && frame > 0)
+            for (int tim = 0; tim < kWin; ++tim) sEng += sig[tim] * sig[tim];
+        const int p = a.pitch[t.row0 + frame];
+        float ratio = 0.0f, label = 0.0f;
+        if (p > 0 && sEng > 0.0f) {
+            float freq = 8000.0f / (float)p;
+            freq = (float)((double)freq * (2 * kPi / 8000));
+            float pa = 0.0f, pb = 0.0f;
+            for (int tim = 0; tim < kWin; ++tim) {
+                const double arg = (double)(freq * (float)tim);
+                pa += (float)cos(arg) * sig[tim];
+                pb += (float)sin(arg) * sig[tim];
+            }
+            const float phase = (pa == 0.0f) ? (float)(kPi / 2) : (float)(double)(float)atan((double)(-pb / pa));
+            float error1 = 0.0f, error2 = 0.0f;
+            for (int tim = 0; tim < kWin; ++tim) {
+                const float s = 1.0f * (float)cos((double)(freq * (float)tim + phase));
+                error1 += (sig[tim] - s) * (sig[tim] - s);
+                error2 += (sig[tim] + s) * (sig[tim] + s);
+            }
+            const float error = error1 < error2 ? error1 : error2;
+            ratio = error / sEng;
+            label = ((double)ratio > 0.20) ? 0.0f : 1.0f; /* THETAE */
+        }
+        a.amcrn[t.row0 * kCh + i] = label;
+        if (a.ratio) a.ratio[t.row0 * kCh + i] = ratio;
+        if (a.seng) a.seng[t.row0 * kCh + i] = sEng;
+    }
+}
+
+/* ---- finalSeg ------------------------------------------------------------------------------------------------------------- */
+namespace {
+
+struct FinalScr {
+    int *lab, *key, *lo, *hi, *m, *g; /* [F][25] each */
+};
+
+/* reSegmentation:1390-1440 on m: the components that hold a unit whose two time neighbours are marked (the reference's
+ * segments) and span at least MIN_SEG_LENGTH frames stay, everything else is cleared.  Returns the number of segments. */
+__device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lane)
+{
+    const int ncell = F * kCh;
+    int *m = s.m;
+    for (int i = lane; i < ncell; i += 64) {
+        s.lab[i] = m[i] ? i : kNone;
+        s.key[i] = kNone;
+        s.lo[i] = F;
+        s.hi[i] = 0;
+    }
+    lanes_fence();
+    hw25_label_components(s.lab, F, lane);
+    lanes_fence();
+    for (int i = lane; i < ncell; i += 64) {
+        const int f = i / kCh;
+        if (!m[i]) continue;
+        const int root = s.lab[i];
+        atomicMin(&s.lo[root], f);
+        atomicMax(&s.hi[root], f);
+        if (f >= 1 && f <= F - 2 && m[i - kCh] && m[i + kCh]) atomicMin(&s.key[root], i);
+    }
+    lanes_fence();
+    int count = 0;
+    for (int base = 0; base < ncell; base += 64) {
+        const int i = base + lane;
+        const bool seg = i < ncell && s.lab[i] == i && s.key[i] != kNone;
+        count += __popcll(__ballot(seg));
+    }
+    for (int i = lane; i < ncell; i += 64) {
+        int keep = 0;
+        if (m[i]) {
+            const int root = s.lab[i];
+            keep = (s.key[root] != kNone && s.hi[root] - s.lo[root] + 1 >= 5) ? 1 : 0;
+        }
+        m[i] = keep;
+    }
+    lanes_fence();
+    return count;
+}
+
+/* develope:1442-1494: the reference sweeps in place until nothing changes; the fixpoint is the closure of {g == v} over
+ * 4-neighbours with m set, whatever the sweep order.  Lane = channel: a frame takes v from the frame before it in sweep
+ * direction, then v spreads along the frame's marked channels. */
+__device__ __forceinline__ void develope(const FinalScr &s, int F, int v, int lane)
+{
+    bool again = true;
+    while (again) {
+        bool changed = false;
+        for (int dir = 0; dir < 2; ++dir) {
+            unsigned carry = 0;
+            for (int k = 0; k < F; ++k) {
+                const int f = dir ? F - 1 - k : k;
+                const bool isv = lane < kCh && s.g[f * kCh + lane] == v;
+                const bool mm = lane < kCh && s.m[f * kCh + lane] != 0;
+                const unsigned V0 = (unsigned)__ballot(isv) & kChanBits, M = (unsigned)__ballot(mm) & kChanBits;
+                unsigned V = V0 | (carry & M), prev;
+                do {
+                    prev = V;
+                    V |= ((V << 1) | (V >> 1)) & M;
+                } while (V != prev);
+                if (lane < kCh && ((V >> lane) & 1u) && !isv) {
+                    s.g[f * kCh + lane] = v;
+                    changed = true;
+                }
+                carry = V;
+            }
+        }
+        again = __any(changed);
+    }
+    lanes_fence();
+}
+
+} // namespace
+
+__global__ __launch_bounds__(64) void hw25_finalseg_kernel(Hw25FinalArgs a)
+{
+    const int lane = threadIdx.x;
+    const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    const long long L = a.lengths[u], row0 = a.row_offsets[u];
+    const int F = L > 0 ? (int)(L / kHop) : 0, ncell = F * kCh;
+    int *block = a.rowscr + row0 * SEA_HW25_FINAL_SCRATCH_WORDS;
+    const FinalScr s = {block, block + ncell, block + 2 * ncell, block + 3 * ncell, block + 4 * ncell, block + 5 * ncell};
+    const float *grp = a.grp + row0 * kCh, *am = a.amcrn + row0 * kCh, *cross = a.cross_ev + row0 * kCh, *pr = a.pratio + row0 * kCh;
+    float *stages = a.stages ? a.stages + row0 * (SEA_HW25_FINAL_STAGES * kCh) : nullptr;
+    auto put_stage = [&](int k) {
+        if (stages)
+            for (int i = lane; i < ncell; i += 64) stages[(long long)k * ncell + i] = (float)s.g[i];
+    };
+    bool too_many = false;
+    /* in the whole estimator: an utterance whose AM stage was refused (too long, a pitch out of range) gets a zero mask */
+    const bool refused = a.status_or && (a.status[u] & (SEA_HW25_AM_TOO_LONG | SEA_HW25_AM_BAD_PITCH)) != 0;
+    if (F >= 3 && !refused) {
+        /* finalSeg:1330-1338: segments for unresolved harmonics */
+        for (int i = lane; i < ncell; i += 64) {
+            s.g[i] = (int)grp[i];
+            s.m[i] = (grp[i] == 0.0f && am[i] != 0.0f && (double)cross[i] > 0.985) ? 1 : 0;
+        }
+        lanes_fence();
+        too_many = re_segmentation(s, F, lane) > SEA_HW25_MAX_SEGMENTS;
+        for (int i = lane; i < ncell; i += 64) s.g[i] += s.m[i] * 2;
+        lanes_fence();
+        put_stage(0);
+        /* :1341-1352 */
+        for (int i = lane; i < ncell; i += 64) s.m[i] = (s.g[i] == 1 && (double)pr[i] > 0.85) ? 1 : 0;
+        lanes_fence();
+        too_many = re_segmentation(s, F, lane) > SEA_HW25_MAX_SEGMENTS || too_many;
+        for (int i = lane; i < ncell; i += 64)
+            if (s.g[i] == 1 && (double)pr[i] > 0.85) s.g[i] = s.m[i] == 1 ? 1 : -2;
+        lanes_fence();
+        put_stage(1);
+        /* :1355-1366 */
+        for (int i = lane; i < ncell; i += 64) s.m[i] = (s.g[i] == 1 && (double)pr[i] <= 0.85) ? 1 : 0;
+        lanes_fence();
+        too_many = re_segmentation(s, F, lane) > SEA_HW25_MAX_SEGMENTS || too_many;
+        for (int i = lane; i < ncell; i += 64)
+            if (s.g[i] == 1 && (double)pr[i] <= 0.85) s.g[i] = s.m[i] == 1 ? -1 : -2;
+        lanes_fence();
+        put_stage(2);
+        /* :1368-1379 */
+        for (int i = lane; i < ncell; i += 64) s.m[i] = s.g[i] == -2 ? 1 : 0;
+        lanes_fence();
+        develope(s, F, -1, lane);
+        for (int i = lane; i < ncell; i += 64)
+            if (s.g[i] == -2 || s.g[i] == 2) s.g[i] = 1;
+        lanes_fence();
+        put_stage(3);
+        /* :1381-1385 */
+        for (int i = lane; i < ncell; i += 64) s.m[i] = (am[i] == 1.0f && s.g[i] == 0) ? 1 : 0;
+        lanes_fence();
+        develope(s, F, 1, lane);
+        put_stage(4);
+    }
+    if (F < 3 || refused || too_many) {
+        /* no segment can exist, or more than the reference's list holds: every output of the utterance is zero */
+        for (int i = lane; i < ncell; i += 64) {
+            a.mask[row0 * kCh + i] = 0.0f;
+            if (a.grp_final) a.grp_final[row0 * kCh + i] = 0.0f;
+        }
+        if (stages)
+            for (int i = lane; i < SEA_HW25_FINAL_STAGES * ncell; i += 64) stages[i] = 0.0f;
+    } else {
+        for (int i = lane; i < ncell; i += 64) {
+            a.mask[row0 * kCh + i] = s.g[i] > 0 ? 1.0f : 0.0f; /* createIBM:103 */
+            if (a.grp_final) a.grp_final[row0 * kCh + i] = (float)s.g[i];
+        }
+    }
+    if (lane == 0) {
+        const int flags = too_many ? SEA_HW25_FINAL_TOO_MANY_SEGMENTS : 0;
+        if (a.status_or)
+            a.status[u] |= flags;
+        else
+            a.status[u] = flags;
+    }
+}
+
+} // namespace sea

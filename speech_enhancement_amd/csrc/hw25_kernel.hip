@@ -3,7 +3,7 @@
  * (function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp:41-76; constants HuWang.h).  A first form, not tuned.
  *
  *   hw25_periphery_kernel    AudiPeriph: gammaToneFilter:225-251 + hairCell:277-298, one lane per (utterance, channel),
- *                            float in, hOut in float
+ *                            float in, hOut in float; gOut (the filter's output before the hair cell) on request
  *   hw25_lowpass_kernel      lowPass:318-328: hEv, the 91-tap FIR of hOut, one lane per sample
  *   hw25_correlogram_kernel  computeACF:341-369, crossCorr:377-437, globalPitch:445-461, timeCrn:771-790 and the initial
  *                            labelling :74-76, one workgroup per frame with the frame's 2 x 25 x 101 ACF values held in LDS
@@ -86,6 +86,7 @@ __global__ __launch_bounds__(64) void hw25_periphery_kernel(Hw25Args a)
     const float f1 = t.f1[c], f2 = t.f2[c], gain = t.gain[c];
     const float *in = a.in + off;
     float *out = a.hout + off * kCh + c * pitch;
+    float *gout = a.gout ? a.gout + off * kCh + c * pitch : nullptr; /* gOut, the gammatone output computeAM reads (optional) */
     Gt25 g = {};
     Hair25 h = {t.q0, t.c0, t.w0};
     /* in[] holds `pitch` floats: the reads of the last group stay inside the utterance's padded stretch */
@@ -96,16 +97,26 @@ __global__ __launch_bounds__(64) void hw25_periphery_kernel(Hw25Args a)
             n0 = *reinterpret_cast<const float4 *>(in + n + kPerTile);
             n1 = *reinterpret_cast<const float4 *>(in + n + kPerTile + 4);
         }
-        float o[kPerTile];
+        float o[kPerTile], go[kPerTile];
 #pragma unroll
-        for (int k = 0; k < kPerTile; ++k) o[k] = hair25_step(h, gt25_step(g, x[k], f1, f2, gain), t);
+        for (int k = 0; k < kPerTile; ++k) {
+            go[k] = gt25_step(g, x[k], f1, f2, gain);
+            o[k] = hair25_step(h, go[k], t);
+        }
         if (n + kPerTile <= L) {
             *reinterpret_cast<float4 *>(out + n) = make_float4(o[0], o[1], o[2], o[3]);
             *reinterpret_cast<float4 *>(out + n + 4) = make_float4(o[4], o[5], o[6], o[7]);
+            if (gout) {
+                *reinterpret_cast<float4 *>(gout + n) = make_float4(go[0], go[1], go[2], go[3]);
+                *reinterpret_cast<float4 *>(gout + n + 4) = make_float4(go[4], go[5], go[6], go[7]);
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < kPerTile; ++k)
-                if (n + k < L) out[n + k] = o[k];
+                if (n + k < L) {
+                    out[n + k] = o[k];
+                    if (gout) gout[n + k] = go[k];
+                }
         }
     }
 }

@@ -27,6 +27,7 @@
  * the carried values stay in registers.
  */
 #include "../../include/sea_mi355x.h"
+#include "hw25_segment.h"
 #include "sea_device.h"
 #include "sea_kernels.h"
 
@@ -37,7 +38,7 @@ namespace {
 constexpr int kCh = SEA_HW25_NCHAN, kDel = SEA_HW25_DELAYS, kHop = SEA_HW25_HOP, kMinDel = SEA_HW25_MINDELAY;
 constexpr int kRow = kCh * kDel;
 constexpr int kMaxSeg = SEA_HW25_MAX_SEGMENTS;
-constexpr int kNone = 0x7fffffff;
+constexpr int kNone = kHw25None;
 constexpr unsigned kChanBits = (1u << kCh) - 1u;
 constexpr double kThetaP = 0.95;
 
@@ -220,45 +221,8 @@ __global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
             key[i] = kNone;
         }
         lanes_fence();
-        /* ---- components: every marked unit ends with the smallest unit index of its component.  Lane = channel; a frame
-         * takes the label of the frame before it in sweep direction (carried in registers), then every run of marked
-         * channels takes its minimum.  Forward and backward sweeps until neither changes anything. ---- */
-        bool again = true;
-        while (again) {
-            bool changed = false;
-            for (int dir = 0; dir < 2; ++dir) {
-                int carry = kNone;
-                for (int k = 0; k < F; ++k) {
-                    const int f = dir ? F - 1 - k : k;
-                    const int old = lane < kCh ? lab[f * kCh + lane] : kNone;
-                    int v = old;
-                    if (v != kNone && carry < v) v = carry;
-                    const unsigned m = (unsigned)__ballot(v != kNone) & kChanBits;
-                    /* the run [start, end] of marked channels around this lane */
-                    const unsigned below = ~m & ((1u << (lane & 31)) - 1u);
-                    const int start = below ? 32 - __clz((int)below) : 0;
-                    const unsigned above = lane < 31 ? (~m >> (lane + 1)) : 1u;
-                    const int end = lane + (__ffs((int)above) - 1);
-#pragma unroll
-                    for (int d = 1; d < 32; d <<= 1) {
-                        const int o = __shfl_up(v, d);
-                        if (lane - d >= start && o < v) v = o;
-                    }
-                    const int r = __shfl(v, end & 63);
-                    if (old != kNone) {
-                        v = r;
-                        if (v != old) {
-                            lab[f * kCh + lane] = v;
-                            changed = true;
-                        }
-                    } else {
-                        v = kNone;
-                    }
-                    carry = v;
-                }
-            }
-            again = __any(changed);
-        }
+        /* ---- components: every marked unit ends with the smallest unit index of its component (hw25_segment.h) ---- */
+        hw25_label_components(lab, F, lane);
         lanes_fence();
         /* ---- per component its first seed in scan order ---- */
         for (int i = lane; i < ncell; i += 64) {

@@ -339,6 +339,7 @@ __global__ void irm_target_kernel(IrmArgs a); /* per-lane codelet, lane = (polyp
 struct Hw25Args {
     const float *in;
     float *hout, *hev;
+    float *gout; /* the periphery kernel: gOut in hout's layout, or null: not written */
     const long long *offsets;
     const long long *lengths;
     const long long *row_offsets;
@@ -382,6 +383,60 @@ __global__ void hw25_pitch_segment_kernel(Hw25PitchArgs a); /* grid n_utt x 64 *
 __global__ void hw25_pitch_frame_kernel(Hw25PitchArgs a);   /* grid (n_utt, G) x 64 */
 __global__ void hw25_pitch_regroup_kernel(Hw25PitchArgs a); /* grid n_utt x 64 */
 __global__ void hw25_pitch_track_kernel(Hw25PitchArgs a);   /* grid n_utt x 64 */
+
+/* The Hu-Wang estimator's AM labels (hw25_am_kernel.hip): computeAM:1146-1317.  gout, ampatt, am: hout's layout; pitch [rows]
+ * ints; amcrn, ratio, seng [rows][25] (ratio, seng or null).  ampatt and am are never null here: the caller's buffers or
+ * scratch.  fa / fb: the FFT's two complex buffers, utterance u's [chunk][2 * pitch] block at offsets[u] * chunk * 2 (2^N is at
+ * most twice the length); one launch group handles the channels chan0 .. chan0 + chunk - 1.  info [n_utt]: N, or -1 when the
+ * utterance skips the stage (all outputs zero: fewer than 3 rows, no voiced frame, too long, a pitch above 100). */
+struct Hw25AmArgs {
+    const float *gout;
+    const int *pitch;
+    const long long *offsets;
+    const long long *lengths;
+    const long long *row_offsets;
+    float *amcrn, *ratio, *seng;
+    float *ampatt, *am;
+    float2 *fa, *fb;
+    int *info;
+    int *status;
+    const int *order;
+    const sea_hw25_tables *tables;
+    const float2 *tw;
+    int n_utt;
+    int status_or; /* status[u] |= flags instead of = flags */
+    int chan0, chunk;
+    int stage;   /* hw25_am_fft_stage_kernel: the stage n (twoPeriod = 2^n) of the launch */
+    int inverse; /* the FFT kernels: 0 forward (from ampatt into fa), 1 inverse (from fa, hilbert's doubling and zeroing
+                  * applied on the way, into fb) */
+};
+#define SEA_HW25_AM_LDS_LOG2 12 /* the stages 1..12 run on 4096 points in LDS, the rest over global memory */
+#define SEA_HW25_AM_PATT_GRID 8  /* workgroups per (utterance, channel) that walk its blocks of five frames */
+#define SEA_HW25_AM_FFT_GRID 8   /* workgroups per (utterance, channel) in the FFT and normalisation kernels */
+#define SEA_HW25_AM_RATE_GRID 8  /* workgroups per utterance that walk its (frame, channel) units */
+__global__ void hw25_am_prepare_kernel(Hw25AmArgs a);   /* grid n_utt x 64 */
+__global__ void hw25_am_patt_kernel(Hw25AmArgs a);      /* grid (n_utt, PATT_GRID, 25) x 256 */
+__global__ void hw25_am_fft_head_kernel(Hw25AmArgs a);  /* grid (n_utt, FFT_GRID, chunk) x 256 */
+__global__ void hw25_am_fft_stage_kernel(Hw25AmArgs a); /* grid (n_utt, FFT_GRID, chunk) x 256 */
+__global__ void hw25_am_norm_kernel(Hw25AmArgs a);      /* grid (n_utt, FFT_GRID, chunk) x 256 */
+__global__ void hw25_am_rate_kernel(Hw25AmArgs a);      /* grid (n_utt, RATE_GRID) x 64 */
+
+/* finalSeg:1321-1494 and the binarisation :99-106 (hw25_am_kernel.hip).  grp, amcrn, cross_ev, pratio [rows][25] are only
+ * read; mask [rows][25] 0 / 1; grp_final (or null) [rows][25] in {-1, 0, 1}; stages (or null): utterance u's [5][F][25] floats
+ * at row_offsets[u] * 125; rowscr: SEA_HW25_FINAL_SCRATCH_WORDS ints per row. */
+struct Hw25FinalArgs {
+    const float *grp, *amcrn, *cross_ev, *pratio;
+    const long long *lengths;
+    const long long *row_offsets;
+    float *mask, *grp_final, *stages;
+    int *status;
+    int *rowscr;
+    const int *order;
+    int n_utt;
+    int status_or;
+};
+#define SEA_HW25_FINAL_SCRATCH_WORDS 150 /* per row: lab, key, lo, hi, m, g [25] */
+__global__ void hw25_finalseg_kernel(Hw25FinalArgs a); /* grid n_utt x 64 */
 
 __global__ void subband_kernel(SubbandArgs a);
 __global__ void ns_denoise_pipe_kernel(NsBatchArgs a);

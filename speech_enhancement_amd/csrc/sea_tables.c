@@ -649,6 +649,9 @@ void sea_build_hw25_tables(sea_hw25_tables *t)
         else fLength += 2;
         if (fLength % 2 != 0) fLength++;
         if (fLength != SEA_HW25_TAPS - 1) abort();
+        if (!(beta < 3.75f)) abort(); /* bessi0 then only ever takes its polynomial branch */
+        t->am_a = a; /* amPatt:1215 calls kaiserPara with the same delta */
+        t->am_beta = beta;
         for (tim = 0; tim <= fLength; tim++) { /* kaiserLowPass, :1576-1590 */
             float k = 2 * tim / (float)fLength - 1;
             float f = hw_bessi0(beta * sqrtf(1 - k * k)) / hw_bessi0(beta);
@@ -670,6 +673,27 @@ void sea_build_hw25_tables(sea_hw25_tables *t)
         t->c0 = (float)(M * Y * kt / (Lc * kt + Y * (Lc + R)));
         t->q0 = (float)(t->c0 * (Lc + R) / kt);
         t->w0 = (float)(t->c0 * R / X);
+    }
+}
+
+void sea_build_hw25_twiddles(float *tw, int direct)
+{ /* fft:1650-1675 */
+    const double kPiHW = 3.1415926535897932384626433832795;
+    const float dir = (float)direct;
+    long period, j;
+    for (period = 1; period <= (1L << (SEA_HW25_MAXLOG2 - 1)); period *= 2) {
+        float uR = 1.0, uI = 0.0, tmpR, tmpI;
+        const float wR = (float)cos(kPiHW / period);
+        const float wI = (float)(-1.0 * sin(kPiHW / period * dir));
+        float *out = tw + 2 * (period - 1);
+        for (j = 0; j < period; j++) {
+            out[2 * j] = uR;
+            out[2 * j + 1] = uI;
+            tmpR = uR * wR - uI * wI;
+            tmpI = uR * wI + uI * wR;
+            uR = tmpR;
+            uI = tmpI;
+        }
     }
 }
 

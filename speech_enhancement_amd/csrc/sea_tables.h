@@ -238,8 +238,16 @@ enum {
     SEA_HW25_WINDOW = 200, /* WINDOW = 8000 / 40 */
     SEA_HW25_HOP = 80,     /* OFFSET = 8000 / 100 */
     SEA_HW25_TAPS = 91,    /* fLength + 1, fLength = 90 from kaiserPara (0.01, 200 / 8000.) */
-    SEA_HW25_MAXWIN = 400  /* the widest window: channel 0, int (4 * 8000 / cf) */
+    SEA_HW25_MAXWIN = 400, /* the widest window: channel 0, int (4 * 8000 / cf) */
+    SEA_HW25_MAXLEN = 150000,               /* MAX_SIG_LENGTH: computeAM's FFT is 2^N points, N <= 18 */
+    SEA_HW25_MAXLOG2 = 18,
+    SEA_HW25_TWIDDLES = (1 << 18) - 1,      /* fft:1650-1676, every stage's u values: period p's p entries start at p - 1 */
+    SEA_HW25_AM_MAXTAPS = 576               /* amPatt's fLength + 1 is at most 564 (mp = 100) */
 };
+/* computeAM:1156, N = int (ceil (log (L * 1.0) / log (2 * 1.0))) in double, evaluated with the C library on a CPU at L = 2^k,
+ * k = 7..17: the quotient is the exact integer at every one of them, so N = k (one ulp above it would have made N = k + 1 and
+ * doubled the zero padding).  Entry k - 7.  Every other L lies far from an integer quotient. */
+#define SEA_HW25_N_AT_POW2 {7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17}
 typedef struct {
     float cf[32], bw[32], midEar[32];             /* entries 0..24 */
     float gain[32], f1[32], f2[32];
@@ -247,9 +255,12 @@ typedef struct {
     float lp[96];                                 /* the 91 taps of kaiserLowPass */
     float ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt; /* hairCell:261-268 */
     float q0, c0, w0;                             /* its initial state, :271-274 */
-    float pad[2];
+    float am_a, am_beta;                          /* kaiserPara (0.01, ..): a = -20 log10 (delta) and beta, amPatt:1215 */
 } sea_hw25_tables;
 void sea_build_hw25_tables(sea_hw25_tables *t);
+/* fft:1654-1674 for every period 1, 2, .., 2^17: u starts at (1, 0) and is multiplied by w once per j, in float; tw holds
+ * SEA_HW25_TWIDDLES (re, im) pairs.  direct = 1 forward, -1 inverse. */
+void sea_build_hw25_twiddles(float *tw, int direct);
 /* plain tables for host-side checks; hair10 = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0 */
 void sea_hw25_plain_tables(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
                            float *lp91, float *hair10);

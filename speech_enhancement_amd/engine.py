@@ -1129,6 +1129,161 @@ def hw25_pitch(x):
 
 
 # ------------------------------------------------------------------------------------------------
+# the Hu-Wang estimator's AM labels, final grouping and the whole of createIBM (HuWang.cpp:89-106: computeAM, finalSeg, the
+# binarisation; csrc/hw25_am_kernel.hip)
+# ------------------------------------------------------------------------------------------------
+HW25_FINAL_STAGES = ("final_reseg1", "final_reseg2", "final_reseg3", "final_dev_minus", "final_dev_plus")
+HW25_FINAL_TOO_MANY_SEGMENTS, HW25_AM_TOO_LONG, HW25_AM_BAD_PITCH = 1 << 18, 1 << 19, 1 << 20
+
+
+def hw25_am_tables():
+    """The AM stage's host constants: a, beta (kaiserPara (0.01, ..)), n_at_pow2 int32 [11] (computeAM's N at L = 2^7 .. 2^17)
+    and twiddles float32 [2^18 - 1][2] (fft's u values, period p's p entries from entry p - 1)."""
+    lib = _lib.load()
+    ab, n, tw = np.zeros(2, np.float32), np.zeros(11, np.int32), np.zeros(((1 << 18) - 1, 2), np.float32)
+    _lib.check(lib.sea_hw25_am_tables_host(_np_ptr(ab), _np_ptr(n), _np_ptr(tw), tw.shape[0]), "sea_hw25_am_tables_host")
+    return dict(a=ab[0], beta=ab[1], n_at_pow2=n, twiddles=tw)
+
+
+def hw25_periphery_gout_batch(batch, use_order=True):
+    """hw25_periphery_batch() with gOut, the gammatone output before the hair cell: (hOut, hEv, gOut), the same layout."""
+    torch = _torch()
+    lib = _lib.load()
+    x = _hw25_input(batch)
+    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=x.device)
+    hev, gout = torch.zeros_like(hout), torch.zeros_like(hout)
+    rc = lib.sea_hw25_periphery_gout_batch(_dptr(x), _dptr(hout), _dptr(hev), _dptr(gout), _dptr(batch.offsets), _dptr(batch.lengths),
+                                           _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_periphery_gout_batch")
+    return hout, hev, gout
+
+
+class Hw25AmResult:
+    """What hw25_am_batch() computed, device tensors: amcrn [rows][25] 0 / 1, status int32 [n_utt] (HW25_AM_TOO_LONG,
+    HW25_AM_BAD_PITCH) and, when asked for, ratio and seng [rows][25], ampatt and am (gOut's layout).  utterance(u): numpy."""
+
+    def __init__(self, batch, **kw):
+        self.batch = batch
+        self.__dict__.update(kw)
+
+    def utterance(self, u):
+        r0, n = int(self.host_row_offsets[u]), int(self.host_rows[u])
+        out = dict(amcrn=self.amcrn[r0:r0 + n].cpu().numpy(), status=int(self.status[u]))
+        for k in ("ratio", "seng"):
+            if getattr(self, k) is not None:
+                out[k] = getattr(self, k)[r0:r0 + n].cpu().numpy()
+        for k in ("ampatt", "am"):
+            if getattr(self, k) is not None:
+                out[k] = hw25_split(self.batch, getattr(self, k))[u]
+        return out
+
+
+def hw25_am_batch(batch, gout, pitch, row_offsets=None, want_details=False, use_order=True):
+    """computeAM for every utterance of the batch from hw25_periphery_gout_batch()'s gOut and hw25_pitch_batch()'s pitch (int32
+    [rows] on the device; row_offsets: the int64 device tensor that goes with it) -> Hw25AmResult.  want_details: also ratio,
+    seng, ampatt and am."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = gout.device
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
+    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
+    d_offs = row_offsets if row_offsets is not None else torch.from_numpy(offs).to(dev)
+    n = max(int(rows.sum()), 1)
+    amcrn = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
+    ratio, seng = (torch.zeros_like(amcrn) for _ in range(2)) if want_details else (None, None)
+    ampatt, am = (torch.zeros_like(gout) for _ in range(2)) if want_details else (None, None)
+    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
+    total = max(int(batch.total), 8)
+    scratch = torch.empty(int(lib.sea_hw25_am_scratch_bytes(total, int(batch.n_utt))), dtype=torch.uint8, device=dev)
+    rc = lib.sea_hw25_am_batch(_dptr(gout), _dptr(pitch), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs), _dptr(amcrn),
+                               _dptr(ratio), _dptr(seng), _dptr(ampatt), _dptr(am), _dptr(status), _dptr(scratch), total,
+                               _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_am_batch")
+    return Hw25AmResult(batch, amcrn=amcrn, ratio=ratio, seng=seng, ampatt=ampatt, am=am, status=status, row_offsets=d_offs,
+                        host_row_offsets=offs, host_rows=rows)
+
+
+class Hw25MaskResult:
+    """What hw25_finalseg_batch() / hw25_ibm_batch() computed, device tensors: mask [rows][25] 0 / 1, status int32 [n_utt],
+    grp_final [rows][25] or None, pitch int32 [rows] or None, stages (floats, or None).  utterance(u): numpy arrays, the stage
+    arrays under HW25_FINAL_STAGES when they were asked for."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def utterance(self, u):
+        r0, n = int(self.host_row_offsets[u]), int(self.host_rows[u])
+        out = dict(mask=self.mask[r0:r0 + n].cpu().numpy(), status=int(self.status[u]))
+        for k in ("grp_final", "pitch"):
+            if getattr(self, k, None) is not None:
+                out[k] = getattr(self, k)[r0:r0 + n].cpu().numpy()
+        if self.stages is not None:
+            w = len(HW25_FINAL_STAGES) * HW25_NCHAN
+            block = self.stages[r0 * w:(r0 + n) * w].cpu().numpy().reshape(len(HW25_FINAL_STAGES), n, HW25_NCHAN)
+            for k, name in enumerate(HW25_FINAL_STAGES):
+                out[name] = block[k].copy()
+        return out
+
+
+def hw25_finalseg_batch(grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages=False, use_order=None):
+    """finalSeg and the binarisation on device tensors [rows][25] (hw25_pitch_batch()'s grp and pratio, hw25_am_batch()'s amcrn,
+    the front half's cross_ev), lengths / row_offsets int64 [n_utt] on the device, host_rows the row counts -> Hw25MaskResult.
+    use_order: an int32 device tensor (launch order) or None."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = grp.device
+    host_rows = np.asarray(host_rows, dtype=np.int64)
+    offs = (np.concatenate(([0], np.cumsum(host_rows)[:-1])) if len(host_rows) else np.zeros(0)).astype(np.int64)
+    n_utt, n = len(host_rows), max(int(host_rows.sum()), 1)
+    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
+    grp_final = torch.zeros_like(mask)
+    status = torch.zeros(max(n_utt, 1), dtype=torch.int32, device=dev)
+    st = torch.zeros(n * len(HW25_FINAL_STAGES) * HW25_NCHAN, dtype=torch.float32, device=dev) if stages else None
+    scratch = torch.empty(int(lib.sea_hw25_finalseg_scratch_bytes(n, n_utt)), dtype=torch.uint8, device=dev)
+    rc = lib.sea_hw25_finalseg_batch(_dptr(grp), _dptr(amcrn), _dptr(cross_ev), _dptr(pratio), _dptr(lengths), _dptr(row_offsets),
+                                     _dptr(mask), _dptr(grp_final), _dptr(status), _dptr(st), _dptr(scratch), _dptr(use_order), n_utt,
+                                     _stream_ptr())
+    _lib.check(rc, "sea_hw25_finalseg_batch")
+    return Hw25MaskResult(mask=mask, grp_final=grp_final, status=status, stages=st, pitch=None, host_row_offsets=offs, host_rows=host_rows)
+
+
+def hw25_ibm_batch(batch, stages=False, use_order=True):
+    """createIBM() for every utterance of the batch, one launch group on the current stream -> Hw25MaskResult with the binary
+    mask [rows][25], pitchDtm's pitch [rows] and the status (hw25_pitch_batch()'s with HW25_FINAL_TOO_MANY_SEGMENTS,
+    HW25_AM_TOO_LONG).  stages: also keep Grp after each of finalSeg's five steps."""
+    torch = _torch()
+    lib = _lib.load()
+    x = _hw25_input(batch)
+    dev = x.device
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
+    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
+    n, total = max(int(rows.sum()), 1), max(int(batch.total), 8)
+    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
+    pitch = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
+    st = torch.zeros(n * len(HW25_FINAL_STAGES) * HW25_NCHAN, dtype=torch.float32, device=dev) if stages else None
+    scratch = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, n, int(batch.n_utt))), dtype=torch.uint8, device=dev)
+    rc = lib.sea_hw25_ibm_batch(_dptr(x), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(torch.from_numpy(offs).to(dev)), _dptr(mask),
+                                _dptr(pitch), _dptr(status), _dptr(st), _dptr(scratch), total, n,
+                                _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_ibm_batch")
+    return Hw25MaskResult(mask=mask, grp_final=None, status=status, stages=st, pitch=pitch, host_row_offsets=offs, host_rows=rows)
+
+
+def hw25_ibm(x):
+    """createIBM (x) for one utterance from host memory (float32 or int16 samples on the int16 scale) -> dict: mask [F][25]
+    floats 0 / 1, pitch int32 [F], status."""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    F = x.size // HW25_HOP
+    r = dict(mask=np.zeros((F, HW25_NCHAN), np.float32), pitch=np.zeros(F, np.int32))
+    status = np.zeros(1, np.int32)
+    _lib.check(lib.sea_hw25_ibm(_np_ptr(x), x.size, _np_ptr(r["mask"]), _np_ptr(r["pitch"]), _np_ptr(status)), "sea_hw25_ibm")
+    r["status"] = int(status[0])
+    return r
+
+
+# ------------------------------------------------------------------------------------------------
 # the training-set builder (enhancement_extract_subband_linux/cpp/main.cpp:91-274): mix at an SNR, subbands, IRM target
 # ------------------------------------------------------------------------------------------------
 def snr_lin(db):

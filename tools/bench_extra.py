@@ -13,6 +13,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what trainset --steps 7  # the training-set builder: mix, subbands, IRM, pipeline and host entry point, opt-in
     python tools/bench_extra.py --what hw25 --steps 5  # the Hu-Wang front half on the 25-channel bank: periphery, correlogram, launch group, opt-in
     python tools/bench_extra.py --what hw25pitch --steps 3  # its initial grouping and pitch tracking beside the correlogram, opt-in
+    python tools/bench_extra.py --what hw25ibm --steps 3  # its AM stage, final grouping and the whole estimator beside the other stages, opt-in
 """
 import argparse
 import json
@@ -1165,6 +1166,80 @@ def main():
                           "utterances_flagged": {"too_many_segments": int((s_host >> 16 & 1).sum()), "chanmark_unset": int((s_host >> 17 & 1).sum())},
                           "voiced_frames": int((p_host > 0).sum())}), flush=True)
         del hout, hev, acf_hc, stages, scratch
+
+    if "hw25ibm" in what:
+        # The rest of the Hu-Wang estimator (computeAM, finalSeg) and the whole of createIBM on the --utts corpus batch taken as
+        # float samples, beside the stages that feed them, in one process: the periphery with gOut, the correlogram with the
+        # corrHc ACF output, initGroup + pitchDtm, the AM stage, the final grouping, and sea_hw25_ibm_batch.  Device events
+        # around every step, one warm-up discarded, median.
+        lib = sea.load()
+        n = batch.n_utt
+        x = batch.data.to(torch.float32)
+        rows = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames, total = int(rows.sum()), int(batch.total)
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev, gout = z(total * 25), z(total * 25), z(total * 25)
+        cross_hc, cross_ev, pratio_in, mark, gpitch = z((frames, 25)), z((frames, 25)), z((frames, 25)), z((frames, 25)), z(frames, torch.int32)
+        acf_hc = z((frames, 25, 101))
+        pitch, grp, pratio, status = z(frames, torch.int32), z((frames, 25)), z((frames, 25)), z(n, torch.int32)
+        amcrn, mask, st_am, st_fin, st_ibm, pitch2, mask2 = z((frames, 25)), z((frames, 25)), z(n, torch.int32), z(n, torch.int32), z(n, torch.int32), z(frames, torch.int32), z((frames, 25))
+        scr_pitch = torch.empty(int(lib.sea_hw25_pitch_scratch_bytes(frames, n)), dtype=torch.uint8, device=dev)
+        scr_am = torch.empty(int(lib.sea_hw25_am_scratch_bytes(total, n)), dtype=torch.uint8, device=dev)
+        scr_fin = torch.empty(int(lib.sea_hw25_finalseg_scratch_bytes(frames, n)), dtype=torch.uint8, device=dev)
+        scr_ibm = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, frames, n)), dtype=torch.uint8, device=dev)
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def periphery():
+            assert lib.sea_hw25_periphery_gout_batch(P(x), P(hout), P(hev), P(gout), P(batch.offsets), P(batch.lengths), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def correlogram():
+            assert lib.sea_hw25_correlogram_batch(P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(acf_hc), None, P(cross_hc),
+                                                  P(cross_ev), P(gpitch), P(pratio_in), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def pitch_stage():
+            assert lib.sea_hw25_pitch_batch(P(acf_hc), P(cross_hc), P(pratio_in), P(mark), P(batch.lengths), P(d_offs), P(pitch), P(grp), P(pratio),
+                                            P(status), None, P(scr_pitch), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def am_stage():
+            assert lib.sea_hw25_am_batch(P(gout), P(pitch), P(batch.offsets), P(batch.lengths), P(d_offs), P(amcrn), None, None, None, None,
+                                         P(st_am), P(scr_am), total, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def final_stage():
+            assert lib.sea_hw25_finalseg_batch(P(grp), P(amcrn), P(cross_ev), P(pratio), P(batch.lengths), P(d_offs), P(mask), None, P(st_fin),
+                                               None, P(scr_fin), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def whole():
+            assert lib.sea_hw25_ibm_batch(P(x), P(batch.offsets), P(batch.lengths), P(d_offs), P(mask2), P(pitch2), P(st_ibm), None, P(scr_ibm),
+                                          total, frames, P(batch.order), n, st) == 0, lib.sea_last_error()
+        samples = int(np.sum(batch.host_lengths))
+        workload = f"the {args.utts}-utterance corpus as 8 kHz float samples: {samples} samples, {frames} frames of 80; median of {args.steps} steps after one warm-up"
+        results = {}
+        for key, name, fn, kernels in (
+                ("periphery", "periphery with gOut", periphery, "sea::hw25_periphery_kernel + sea::hw25_lowpass_kernel"),
+                ("correlogram", "correlogram with the corrHc ACF output", correlogram, "sea::hw25_correlogram_kernel"),
+                ("pitch", "initial grouping and pitch tracking", pitch_stage, "the eight launches of sea_hw25_pitch_batch"),
+                ("am", "AM stage (amPatt, hilbert, computeAMRate)", am_stage,
+                 "sea::hw25_am_prepare_kernel + _patt_kernel + per channel group (_fft_head_kernel + 6 x _fft_stage_kernel) x 2 + _norm_kernel; _rate_kernel"),
+                ("final", "final grouping (finalSeg)", final_stage, "sea::hw25_finalseg_kernel"),
+                ("whole", "the whole estimator, sea_hw25_ibm_batch", whole, "all of the above")):
+            med, t = median_ms(fn, args.steps)
+            results[key] = med
+            print(json.dumps({"metric": f"Hu-Wang estimator, 25-channel 8 kHz bank: {name} (frames of 80 samples/sec); a first form, not tuned",
+                              "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
+                              "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}), flush=True)
+        assert torch.equal(mask, mask2) and torch.equal(pitch, pitch2), "the launch group and the single stages differ"
+        s_host = (st_ibm.cpu().numpy() | st_am.cpu().numpy() | st_fin.cpu().numpy())
+        print(json.dumps({"metric": "Hu-Wang estimator: each stage relative to the correlogram of the same run",
+                          "value": results["whole"] / results["correlogram"], "unit": "ratio (the whole estimator)",
+                          "stage_over_correlogram": {k: v / results["correlogram"] for k, v in results.items()},
+                          "config": {"workload": workload, "fft_channels_per_launch_group": 25 if total * 2 * 25 * 16 <= (256 << 20) else 5},
+                          "utterances_flagged": {"final_too_many_segments": int((s_host >> 18 & 1).sum()), "am_too_long": int((s_host >> 19 & 1).sum())},
+                          "voiced_frames": int((pitch.cpu().numpy() > 0).sum()), "am_labels": int(amcrn.sum().item()),
+                          "mask_units": int(mask.sum().item())}), flush=True)
+        del hout, hev, gout, acf_hc, scr_am, scr_ibm
 
     if "rfft" in what:
         n = 1 << 18
