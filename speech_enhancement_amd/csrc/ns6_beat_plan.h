@@ -39,6 +39,11 @@ constexpr unsigned kRedeal = 8u;
 /* the three kernels; kVariantDense is the dense body without the re-deal, which no kernel takes since round 8 */
 constexpr unsigned kVariantPlain = kLight | kDifg1, kVariantDense = 0u, kVariantFd = kFd | kLight | kDifg1;
 constexpr unsigned kVariantDenseRedeal = kRedeal;
+/* kBin64 (round 10, the dense kernel): the stage-1 Wiener gain of bin 64 rides in B0's stage-0 filter pass -- lane 1 of the component
+ * that carries bin 64 takes stage-1 frame i-6 (N1 left its mean PSD and noise at i-5), G1 computes bins 0..63 only.  The dense kernel is
+ * kVariantDenseBin64; kVariantDenseRedeal is the body it grew from, which no kernel takes any more */
+constexpr unsigned kBin64 = 16u;
+constexpr unsigned kVariantDenseBin64 = kRedeal | kBin64;
 
 struct Flag {
     int d;         /* the flag is about frame i - d ... */
@@ -60,8 +65,8 @@ constexpr RolePlan kPlan[kRoles] = {
     {4, {{0, 3, kAlways}, {3, 5, kAlways}, {2, 1, kLight}, {3, 3, kRedeal}, {0, 0, 0}}, 1, 0},
     /* FB: one beat behind FA on both transforms */
     {2, {{1, 3, kAlways}, {4, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
-    /* B0: stage-0 back half of frame i-2 */
-    {1, {{2, 3, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* B0: stage-0 back half of frame i-2; kBin64: stage-1 bin 64 of frame i-6 */
+    {2, {{2, 3, kAlways}, {6, 5, kBin64}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
     /* N1: noise tracking of frame i-5, gain-factor scalars of frame i-7; kRedeal: the VAD log-energy of frame i-2 */
     {3, {{5, 5, kAlways}, {7, 5, kAlways}, {2, 1, kRedeal}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
     /* G1: gains of frame i-8 */

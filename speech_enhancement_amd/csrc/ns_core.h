@@ -534,6 +534,47 @@ __device__ __forceinline__ void filter_bins_fast(float PLo, float PHi, float nSi
     WHi = W.y;
 }
 
+/* ---- a guest in the second component (round 10, the dense six-wave form) ---------------------------------------
+ * The second component of filter_bins_fast<0> is ONE useful value, stage-0 bin 64, computed in 64 identical lanes, and the wave G1
+ * paid a second such component for stage-1 bin 64.  B0 now carries both in one pass: lane 0 (and every lane but 1) has stage-0 bin 64
+ * as before, lane 1 has stage-1 bin 64 of the frame N1 tracked one beat before -- its PSD from FB's record, its mean PSD and its
+ * ALREADY updated noise from N1's, its recursive den in a register of B0's own (NsBin64::den).  From then on lane 1 of every "Hi"
+ * register of B0 (prevHi, noiseHi, denHi of stage 0) is a don't-care: stage-0 bin 64 is taken from lane 0 (wbuf[64], spectOut[64]) and
+ * the domain ballots leave lane 1's second component out.  The guest's operations are gain_bin<true>'s in its order, so its bits are
+ * what G1 computed. */
+constexpr int kNsFastWord = 65; /* RecN::P[65] (spare: P has 65 bins in 68 floats), as an int: N1's fast-division decision of the frame */
+struct NsBin64 {
+    const float *psd1;  /* in: the stage-1 PSD record of frame g */
+    const float *P1;    /* in: N1's record of frame g -- mean PSD ([kNsFastWord]: its domain flag) ... */
+    const float *noise1; /* ... and noise */
+    bool live;          /* in: frame g exists with tick >= 5 (wave-uniform) */
+    float den;          /* state: denSigSE2[64], meaningful in lane 1 */
+    float W;            /* out: the gain, meaningful in lane 1 when done */
+    bool done;          /* out: the mixed pass ran (both frames inside the fast-division domain); otherwise the caller computes the guest */
+};
+/* filter_bins_fast<0> with the guest: `guest` is true in lane 1 while the guest is live; PHi and nSigHi arrive mixed.  The VAD-gated
+ * noise update of stage 0 runs on noiseHi as before and leaves junk in lane 1 of it (a don't-care); the guest's noise, which arrives
+ * updated, is selected into the gain computation's operand behind it. */
+__device__ __forceinline__ void filter_bins_fast_guest(float PLo, float PHi, float nSigLo, float nSigHi, float &noiseLo, float &noiseHi,
+                                                       float &denLo, float &denHi, int nb, int flagVAD, float eps, float &WLo,
+                                                       float &WHi, bool guest, float nz1, float den1)
+{
+    const ns_v2f nSig = {SEA_SQRT(nSigLo), SEA_SQRT(nSigHi)};
+    const ns_v2f P = {SEA_SQRT(PLo), SEA_SQRT(PHi)};
+    const float lambda = (nb < 100) ? 1 - 1 / (float)nb : (float)0.99; /* VAD-gated noise tracking in magnitude, :531-546 */
+    if (flagVAD == 0) {
+        const float nl = lambda * noiseLo + (1 - lambda) * P.x, nh = lambda * noiseHi + (1 - lambda) * P.y;
+        noiseLo = (nl < eps) ? eps : nl;
+        noiseHi = (nh < eps) ? eps : nh;
+    }
+    ns_v2f den = {denLo, guest ? den1 : denHi};
+    const ns_v2f W = gain_bin2(P, nSig, ns_v2f{noiseLo, guest ? nz1 : noiseHi}, den);
+    denLo = den.x;
+    denHi = den.y;
+    WLo = W.x;
+    WHi = W.y;
+}
+
 template <int ST, bool FAST = false>
 __device__ __forceinline__ float filter_bin(float P, float nSig, float &noise, float &den, int nb,
                                             int flagVAD, float eps)
@@ -1252,21 +1293,39 @@ __device__ unsigned long long g_back_ck[16];
  *   remaining mel gains in dst (ns_idct_head); the consumer wave, which has cycles to spare, finishes them into the taps
  *   (ns_idct_tail, ns_idct_tail_rl) and runs the FIR itself. */
 template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1, bool NF = false /* see ns_ln */,
-          bool LDSB = false /* the six-wave forms: the IDCT basis from LDS as one batch of reads (ns_idct_basis_request), no bregs */>
+          bool LDSB = false /* the six-wave forms: the IDCT basis from LDS as one batch of reads (ns_idct_basis_request), no bregs */,
+          bool B64 = false /* the dense six-wave form: stage-1 bin 64 rides in lane 1 of the second component (NsBin64) */>
 __device__ __forceinline__ void ns_back(const float *psd, const float *buf, BackLds &B, NsRegs &s,
                                         const NsConst &C, float *dst, int lane, float frameEnExt = 0.0f,
                                         float *spectOut = nullptr, const float *idctLds = nullptr,
                                         NsFd *fd = nullptr, int *fdFlags = nullptr, float *fdRec = nullptr,
                                         float *yRegs = nullptr /* RL, IDCT_HEAD < 0: the filter's two outputs of this lane stay in
                                                                 * yRegs[0..1] (ns_fir_regs), dst is not written */,
-                                        const float *bregs = nullptr /* RL: the IDCT basis column in registers (ns_idct_head) */)
+                                        const float *bregs = nullptr /* RL: the IDCT basis column in registers (ns_idct_head) */,
+                                        NsBin64 *x = nullptr /* B64 */)
 {
+    static_assert(!B64 || (ST == 0 && PIPE && RL && !FD), "the guest rides in filter_bins_fast<0> of the pipelined forms");
     NS_BACK_CK_START;
-    const float nSigLo = psd[lane], nSigHi = psd[64];
+    /* B64: lane 1 fetches the guest's PSD with the read every lane makes of bin 64; its mean PSD, its noise and its domain flag come
+     * with the same batch (unconditional: the slots are masked, a record nobody has written yet holds garbage, used under `live` only) */
+    const bool guest = B64 && x->live && lane == 1;
+    const float nSigLo = psd[lane], nSigHi = B64 ? *(guest ? x->psd1 + 64 : psd + 64) : psd[64];
+    float P1 = 0.0f, nz1 = 0.0f;
+    int fastWord1 = 0;
+    if constexpr (B64) { /* opaque: or the reads sink into a lane-1 branch of their own and cost a round trip each */
+        P1 = x->P1[64];
+        nz1 = x->noise1[64];
+        fastWord1 = reinterpret_cast<const int *>(x->P1)[kNsFastWord];
+        asm volatile("" : "+v"(P1), "+v"(nz1), "+v"(fastWord1));
+    }
 
     /* --- PSDMean over two frames (NoiseSup.c:289-303) --- */
     const float PLo = (s.prevLo[ST] + nSigLo) * 0.5f;
-    const float PHi = (s.prevHi[ST] + nSigHi) * 0.5f;
+    float PHi = (s.prevHi[ST] + nSigHi) * 0.5f;
+    if constexpr (B64) {
+        asm volatile("" : "+v"(PHi));
+        PHi = guest ? P1 : PHi;
+    }
     s.prevLo[ST] = nSigLo;
     s.prevHi[ST] = nSigHi;
 
@@ -1289,14 +1348,22 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
      * (so P is 0 or in [2^-41, 2^48], and den, left by the previous frame, 0 or in [2^-24, 2^24]) and the
      * noise magnitude in [2^-15, 2^28] (>= eps = 2^-14.4 by construction; each update keeps it below
      * max(noise, 1.05 sqrt(P))).  Wave-uniform; always true for int16 audio ((200 * 32768)^2 = 2^45.3). */
-    const bool psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
-    /* The noise range is an invariant of the fast path: a frame inside the domain has P <= 2^48, and its update leaves the noise in
+    bool psdOk;
+    if constexpr (B64) psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && (ns_psd_in_domain(nSigHi) || lane == 1))) == 0ull;
+    else psdOk = __ballot(!(ns_psd_in_domain(nSigLo) && ns_psd_in_domain(nSigHi))) == 0ull;
+    /* (B64: lane 1's second component is not this stage's, here and in the noise test below; the other 63 lanes test bin 64)
+     * The noise range is an invariant of the fast path: a frame inside the domain has P <= 2^48, and its update leaves the noise in
      * [eps, max(noise, 1.05 sqrt(P))] (stage 0: a convex combination with sqrt(P), :531-546; stage 1: n2 * upd with upd <= 1 when
      * n2 >= P and n2 * upd < 1.1 P otherwise, :492-508), so after a fast frame the test is skipped (~10 vector instructions per stage
      * and frame); after anything else -- initial state, a reloaded state, a frame outside the domain -- it is made. */
     bool noiseOk = true;
-    if (!s.noiseSafe[ST])
-        noiseOk = __ballot(!(s.noiseLo[ST] <= 0x1p28f && s.noiseHi[ST] <= 0x1p28f && s.noiseLo[ST] >= 0x1p-15f && s.noiseHi[ST] >= 0x1p-15f)) == 0ull;
+    if (!s.noiseSafe[ST]) {
+        if constexpr (B64)
+            noiseOk = __ballot(!(s.noiseLo[ST] <= 0x1p28f && s.noiseLo[ST] >= 0x1p-15f &&
+                                 ((s.noiseHi[ST] <= 0x1p28f && s.noiseHi[ST] >= 0x1p-15f) || lane == 1))) == 0ull;
+        else
+            noiseOk = __ballot(!(s.noiseLo[ST] <= 0x1p28f && s.noiseHi[ST] <= 0x1p28f && s.noiseLo[ST] >= 0x1p-15f && s.noiseHi[ST] >= 0x1p-15f)) == 0ull;
+    }
     const bool fast = psdOk && noiseOk && (s.psdOk[ST] != 0);
     s.noiseSafe[ST] = fast ? 1 : 0;
     s.psdOk[ST] = psdOk ? 1 : 0;
@@ -1335,7 +1402,17 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
         }
     }
     if (fast) {
-        if (RL) { /* not in the 80-VGPR form: the pairs cost registers there (9 spills, -4 %) */
+        if constexpr (B64) {
+            /* the guest's frame is inside the domain when N1 said so: its PSD and the frame's before it by N1's own test, its noise
+             * <= 2^29 (N1 tested <= 2^28 before the update) and >= eps, its den left by a frame inside the domain */
+            filter_bins_fast_guest(PLo, PHi, nSigLo, nSigHi, s.noiseLo[ST], s.noiseHi[ST], s.denLo[ST], s.denHi[ST], nb16, s.flagVAD,
+                                   C.eps, WLo, WHi, guest, nz1, x->den);
+            x->done = x->live && __builtin_amdgcn_readfirstlane(fastWord1) != 0;
+            if (x->done) {
+                x->den = s.denHi[ST];
+                x->W = WHi;
+            }
+        } else if (RL) { /* not in the 80-VGPR form: the pairs cost registers there (9 spills, -4 %) */
             filter_bins_fast<ST>(PLo, PHi, nSigLo, nSigHi, s.noiseLo[ST], s.noiseHi[ST], s.denLo[ST], s.denHi[ST],
                                  nb16, s.flagVAD, C.eps, WLo, WHi);
         } else if (ST == 0 || nb16 >= 11) { /* the two chains in one basic block (filter_steady) */
@@ -1425,6 +1502,7 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
  *   (gain_fact_update; ns_pipe6_kernel.hip has the schedule).
  * ns_gain1 (wave G1): the gains of all bins from (P, PSD, noise), mel filter bank, gain
  *   factorisation of the 25 mel gains, IDCT, FIR (:522-560, MelProc.c, :639-640, :324-340). */
+template <bool PUBLISH = false /* the dense six-wave form: leave the frame's fast-division decision in Pout[kNsFastWord] for G1 and B0 */>
 __device__ __forceinline__ void ns_noise1(const float *psd, float *Pout, float *noiseOut, NsRegs &s, float eps,
                                           int lane)
 {
@@ -1456,14 +1534,47 @@ __device__ __forceinline__ void ns_noise1(const float *psd, float *Pout, float *
     if (lane == 0) {
         Pout[64] = PHi;
         noiseOut[64] = s.noiseHi[1];
+        /* `fast` implies the domain of the gain computation (gain_bin): this frame's and the previous frame's PSD inside the domain, and
+         * the noise, <= 2^28 before this frame's update, <= 2^29 after it (the invariant stated in ns_back) and >= eps by the clamp */
+        if (PUBLISH) reinterpret_cast<int *>(Pout)[kNsFastWord] = fast ? 1 : 0;
     }
     wave_sync();
 }
 
+/* The gains of ns_gain1 in the dense six-wave form since round 10: bins 0..63 through the single-component gain_bin, the domain decision
+ * from N1's flag (P[kNsFastWord]; not-fast takes the IEEE path) and W[64] from the word B0 left two beats before (*w64).  All operands
+ * in one batch of reads.  Leaves wbuf[0..64] staged, as the head of ns_gain1 does. */
+__device__ __forceinline__ void ns_gain1_bins63(const float *psd, const float *P, const float *noise, const float *w64, BackLds &B, NsRegs &s,
+                                                int lane)
+{
+    const float nSigLo = psd[lane], nzLo = noise[lane], WHi = *w64;
+    const int fastWord = reinterpret_cast<const int *>(P)[kNsFastWord];
+    float PLo = P[lane];
+    asm volatile("" : "+v"(PLo));
+    float WLo;
+    if (__builtin_amdgcn_readfirstlane(fastWord) != 0) {
+        const float nSig = SEA_SQRT(nSigLo), Pq = SEA_SQRT(PLo);
+        WLo = gain_bin<true>(Pq, nSig, nzLo, s.denLo[1]);
+    } else {
+        WLo = gain_bin<false>(sqrtf(PLo), sqrtf(nSigLo), nzLo, s.denLo[1]);
+    }
+    B.wbuf[lane] = WLo;
+    if (lane == 0) B.wbuf[64] = WHi;
+    wave_sync();
+}
+
+template <bool B64 = false>
 __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const float *noise, float alfaGF,
                                          const float *buf, BackLds &B, NsRegs &s, const NsConst &C, float *dst,
-                                         int lane, const float *idctLds)
+                                         int lane, const float *idctLds, const float *w64 = nullptr)
 {
+    if constexpr (B64) {
+        ns_gain1_bins63(psd, P, noise, w64, B, s, lane);
+        float melOut = ns_mel_fb(B, C, lane);
+        melOut = (float)((double)(alfaGF * melOut) + (1.0 - (double)alfaGF) * 1.0);
+        ns_idct_fir<true, true>(melOut, B, C, buf, dst, lane, idctLds);
+        return;
+    }
     /* the fast-division domain as in ns_back: this wave sees every frame's PSD too and owns den; the noise
      * magnitudes arrive from the N1 wave (>= eps by its clamp) */
     const float nSigLo = psd[lane], nSigHi = psd[64], nzLo = noise[lane], nzHi = noise[64];

@@ -48,6 +48,15 @@
  * kernel on 512 2.669 -> 2.433 (B0 sets those kernels' period); configs[1] 1.66 -> 1.64 ms, the same 0.020 ms in three alternations,
  * which is over three times the spread in one of them only (profiles/ns6_lds_batches.txt).
  *
+ * Round 10, the dense kernel only (BIN64 of ns_pipe6_body): the Wiener-gain chain ran on the pair (bin lane, bin 64) in B0 and in G1, and
+ * the second component is one useful value in 64 identical lanes --
+ *   wave B0  also: stage-1 bin 64 of frame i-6 in lane 1 of that second component (PSD, mean PSD and updated noise from FB's and N1's
+ *            records, the recursive den in a register of its own) -> w1hi (read by G1 two beats later)
+ *   wave G1  bins 0..63 through the single-component chain, W[64] from w1hi
+ *   wave N1  also: its fast-division decision of the frame -> rn[].P[65]; G1 and B0 read it instead of testing the PSD again
+ * and the wave -> role map was swept again (kRedealPerm).  G1 2720 -> 2120 clk per frame, B0 2365 -> 2575, the beat 3065 -> 2975;
+ * the step moved with the new map, not before it: the figures are in profiles/ns6_bin64_in_b0.txt.
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -110,10 +119,11 @@ constexpr int kPrioLevels = 32;
 /* wave -> role (octal digits, wave 0 rightmost; roles 0 FA, 1 FB, 2 B0, 3 N1, 4 G1, 5 S): B0 and S on the two oldest waves.
  * NsBatchArgs::perm6 != 0 replaces it (sea_debug_ns6_perm, which accepts permutations of 0..5 only). */
 constexpr int kDefaultPerm = 0014352;
-/* The re-dealt dense kernel (round 8): B0, FB, G1, N1, S, FA on waves 0..5, which keeps G1 and N1 on waves 2 and 3 and B0 on wave 0
- * or 1 -- the best four of that kernel's 720 maps do (tools/ns6_perm_sweep.py; kDefaultPerm is not among its best forty, and this map
- * is 1 % behind kDefaultPerm in the kernel before the re-deal) */
-constexpr int kRedealPerm = 0053412;
+/* The re-dealt dense kernel: a map of its own, re-swept whenever the roles' lengths move (tools/ns6_perm_sweep.py, all 720 maps).
+ * Round 8: 0053412 (B0, FB, G1, N1, S, FA on waves 0..5).  Round 10, with G1 the shortest role instead of the longest: FA, N1, B0, G1, S,
+ * FB on waves 0..5 -- the best ten maps of that sweep all keep G1 on wave 3 and B0 or N1 on wave 2; 0053412 is 76th there, 2.8 %
+ * behind (profiles/ns6_bin64_in_b0.txt) */
+constexpr int kRedealPerm = 0154230;
 
 /* Frame bookkeeping (valid / tick / produced of every frame) is a pure function of the frame index: the zero-frame gate
  * (ParmInterface.c:244-251) has one degree of freedom per utterance, the index `onset` of the first non-zero frame.  From it on every
@@ -215,11 +225,16 @@ __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, 
  *   tap               B0 writes the nine IDCT sums of frame f at f+2, FA reads them at f+3: D > 1, by frame parity
  *   frameEnLog        REDEAL: N1 writes the slot (tick + 2) & 7 of the frame pushed at i-2 at iteration i, B0 reads it two iterations
  *                     later -- LIGHT's timing, where FA writes it
+ *   BIN64 (round 10)  B0 takes stage-1 bin 64 of frame f at f+6: it reads p1[f] (written at f+4, last read by G1 at f+8) and rn[f]
+ *                     (written at f+5, last read at f+8) inside their lifetimes, so neither ring grows.  It leaves the gain in
+ *                     w1hi[f], written at f+6, read by G1 at f+8: D > 2, three would do; four makes the slot a mask (kW1Ring).
+ *                     N1's domain flag of frame f sits in rn[f].P[kNsFastWord] and lives as rn does.
  * nbFrame of the gain-factor job: N1's counter has by then counted the two frames tracked since; the job takes the frame's own
  * count, tick - 4 (the first second-stage frame has tick 5).
- * LDS: 24 944 B per workgroup (24 624 + the two tap records); four workgroups per CU take 99.8 KB of the 160. */
+ * LDS: 24 960 B per workgroup (24 624 + the two tap records + the ring of W1[64]); four workgroups per CU take 99.8 KB of the 160. */
 constexpr int kP1Ring = 8;
 constexpr int kRnRing = 4;
+constexpr int kW1Ring = 4;
 struct __attribute__((aligned(16))) RecPsd { /* FB -> B0 (stage 0) / N1, G1 (stage 1) */
     float psd[68];
 };
@@ -254,6 +269,7 @@ struct __attribute__((aligned(16))) Pipe6Lds {
     RecOut ro[2];
     float nzSum[2], alfa[2];        /* S -> N1: in-order sum of rn[f].noise; N1 -> G1: alfaGF of frame f; both by frame parity */
     RecTap tap[2];                  /* B0 -> FA (dense form): the stage-0 filter's taps before their window, by frame parity */
+    float w1hi[kW1Ring];            /* B0 -> G1 (dense form, BIN64): the stage-1 gain of bin 64 */
 };
 /* The helper wave reads its four sources with one ds_read_b128 per quad; lanes of different chains share a lane group
  * ({ssq, den} in two of the four groups, {dif, noise} in the other two; past term 68 the sums read szero), so two sources that sit a
@@ -276,7 +292,8 @@ static_assert(lds_slots_differ(NS6_OFF(ro[0].out[68]), NS6_OFF(szero)) && lds_sl
               lds_slots_differ(NS6_OFF(ro[0].out[76]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[1].out[68]), NS6_OFF(szero)) &&
               lds_slots_differ(NS6_OFF(ro[1].out[72]), NS6_OFF(szero)) && lds_slots_differ(NS6_OFF(ro[1].out[76]), NS6_OFF(szero)), "ro tail | szero");
 #undef NS6_OFF
-static_assert(sizeof(Pipe6Lds) == 24944, "the figure in the comment at kP1Ring");
+static_assert(sizeof(Pipe6Lds) == 24960 && 4 * sizeof(Pipe6Lds) <= 160 * 1024 && sizeof(Pipe6Lds) < 40 * 1024,
+              "the figure in the comment at kP1Ring; four workgroups fit a CU");
 
 /* SLOTS: kSlots for the stage-0 buffer, kSlots1 for the stage-1 buffer */
 template <int SLOTS>
@@ -310,11 +327,22 @@ __device__ __forceinline__ void load_back_const(NsConst &C, const sea_ns_tables 
 
 template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands over the DC differences */,
           bool STEADY_LOOP /* the flag-free copy of every role's beat on its steady range (run_beats) */,
-          bool REDEAL = false /* round 8, the dense kernel: feed-forward work of S and B0 in the waves that wait, and the map that goes with it */>
+          bool REDEAL = false /* round 8, the dense kernel: feed-forward work of S and B0 in the waves that wait, and the map that goes with it */,
+          bool BIN64 = false /* round 10, the dense kernel: stage-1 bin 64 rides in B0's second component, one domain flag per stage-1 frame */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
 {
     static_assert(!REDEAL || (!LIGHT && !DIFG1), "the re-deal is a variant of the dense body");
-    constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u);
+    static_assert(!BIN64 || (REDEAL && !FD), "the guest of B0's second component is a variant of the re-dealt dense body");
+    constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u) |
+                           (BIN64 ? ns6plan::kBin64 : 0u);
+    static_assert(!BIN64 || V == ns6plan::kVariantDenseBin64, "the variant tests/test_ns6_bin64_plan_cpu.py sweeps");
+    /* BIN64 (profiles/ns6_bin64_in_b0.txt): the Wiener-gain chain ran on the pair (bin lane, bin 64) in B0 and in G1, and the second
+     * component is one useful value in 64 identical lanes.  B0, at beat i, takes stage-1 bin 64 of frame g = i-6 into lane 1 of its
+     * second component (ns_core.h, NsBin64) and leaves W1[64] in w1hi[g & 3]; G1 computes bins 0..63 with the single-component chain.
+     * N1 publishes its fast-division decision of the frame, which G1 and B0 read instead of testing the PSD again.  The mixed pass
+     * needs both frames inside the domain; otherwise, and on the four drain beats on which B0 has no stage-0 frame left, the guest
+     * goes through plain IEEE division, which gives the same bits inside the domain (sea_selftest_nsdiv).  With int16 input every PSD
+     * is inside the domain. */
     /* REDEAL moves two pieces whose inputs do not depend on the recursive state (profiles/ns6_redeal.txt):
      *   LOG_N1  the VAD log-energy: N1, which holds no transform tables and waited 1300 clk per beat, takes it one beat after S left the
      *           sum (LIGHT's timing, with N1 for FA: FA is the register-bound role of the 72-VGPR kernel)
@@ -487,13 +515,23 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         regs_init(s, C.eps);
         NsFd fd;
         fd_init(fd);
+        NsBin64 x; /* BIN64: the guest, stage-1 bin 64 */
+        x.den = 0.0f; /* denSigSE2[64] as DoNoiseSupInit leaves it */
+        x.W = 0.0f;
         int onset = kNoOnset;
         auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
             constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
-            const int f = i - 2;
+            const int f = i - 2, g = i - 6;
+            if constexpr (BIN64) {
+                x.psd1 = L.p1[g & (kP1Ring - 1)].psd;
+                x.P1 = L.rn[g & (kRnRing - 1)].P;
+                x.noise1 = L.rn[g & (kRnRing - 1)].noise;
+                x.live = beat_flag<V, ns6plan::B0, 6, 5, STEADY>(i, onset, nfr);
+                x.done = false;
+            }
             if (beat_flag<V, ns6plan::B0, 2, 3, STEADY>(i, onset, nfr)) {
                 const RecPsd &r = L.p0[f & 1];
                 RecDen &o = L.rd[f & 1];
@@ -502,7 +540,10 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
                  * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
                 const float frameEn = ((LIGHT || LOG_N1) ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)];
-                if constexpr (FIR_FA) { /* stop at the nine IDCT sums; FA windows them and filters at the next iteration */
+                if constexpr (BIN64) { /* as FIR_FA below, with the guest in lane 1 of the second component */
+                    ns_back<0, true, FD, true, SEA_NMEL, false, true, true>(r.psd, nullptr, L.back[0], s, C, L.tap[f & 1].rec, lane, frameEn, o.den,
+                                                                            L.idctT, &fd, &bits, nullptr, nullptr, nullptr, &x);
+                } else if constexpr (FIR_FA) { /* stop at the nine IDCT sums; FA windows them and filters at the next iteration */
                     ns_back<0, true, FD, true, SEA_NMEL, false, true>(r.psd, nullptr, L.back[0], s, C, L.tap[f & 1].rec, lane, frameEn, o.den, L.idctT,
                                                          &fd, &bits);
                     if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
@@ -512,6 +553,15 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                                                L.idctT, &fd, &bits, nullptr, y01);
                     if (FD && lane == 0) L.fdFlags[t & (kSlots - 1)] = bits;
                     if (lane < 40) slot_store<kSlots1>(L.circ1, t, lane, y01[0], y01[1]);
+                }
+            }
+            if constexpr (BIN64) {
+                if (x.live) {
+                    if (!x.done) { /* no stage-0 frame beside it (the drain), or one of the two frames outside the domain: IEEE division */
+                        const float W = gain_bin<false>(sqrtf(x.P1[64]), sqrtf(x.psd1[64]), x.noise1[64], x.den);
+                        x.W = W;
+                    }
+                    if (lane == 1) L.w1hi[g & (kW1Ring - 1)] = x.W;
                 }
             }
             NS6_T_MID;
@@ -554,7 +604,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             if (beat_flag<V, ns6plan::N1, 5, 5, STEADY>(i, onset, nfr)) {
                 const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place three beats later (kP1Ring) */
                 RecN &o = L.rn[f & (kRnRing - 1)];
-                ns_noise1(r.psd, o.P, o.noise, s, eps, lane);
+                ns_noise1<BIN64>(r.psd, o.P, o.noise, s, eps, lane);
             }
             NS6_T_MID;
             block_sync();
@@ -582,10 +632,11 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 RecOut &o = L.ro[f & 1];
                 const int t = tick_of(f, onset);
                 const float alfa = L.alfa[f & 1];
+                const float *w64 = BIN64 ? &L.w1hi[f & (kW1Ring - 1)] : nullptr; /* B0 left it two beats ago */
                 if (DIFG1)
                     ns_gain1_dif(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT, lastIn);
                 else
-                    ns_gain1(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT);
+                    ns_gain1<BIN64>(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT, w64);
             }
             NS6_T_MID;
             block_sync();
@@ -715,7 +766,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false, true, true>(a, L);
+    p6::ns_pipe6_body<false, false, false, true, true, true>(a, L);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif

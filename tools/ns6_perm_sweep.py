@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""tools/ns6_perm_sweep.py [rounds] [steps] -- (GPU box) configs[1] step of the dense six-wave form for EVERY wave -> role map
+"""tools/ns6_perm_sweep.py [rounds] [steps] [map ...] -- (GPU box) configs[1] step of the dense six-wave form for EVERY wave -> role map
 (720 permutations of roles 0 FA, 1 FB, 2 B0, 3 N1, 4 G1, 5 S over waves 0..5), `rounds` passes over all of them in a fresh random
-order each, `steps` launches per measurement; prints the maps sorted by their median step.  One process: the map is a launch
+order each, `steps` launches per measurement; prints the maps sorted by their median step, the best forty and the last five, and
+after them the maps named on the command line (octal, as kRedealPerm is written) with their rank.  One process: the map is a launch
 argument (sea_debug_ns6_perm)."""
 import ctypes, itertools, os, random, sys, time
 import numpy as np
@@ -53,3 +54,7 @@ names = ["FA", "FB", "B0", "N1", "G1", "S"]
 for med, mn, o in res[:40] + res[-5:]:
     w = [int(c) for c in o[1:]][::-1]
     print(o, f"median {med:.3f} ms  min {mn:.3f}", " ".join(names[x] for x in w))
+for want in sys.argv[3:]:
+    for rank, (med, mn, o) in enumerate(res):
+        if o == want:
+            print(f"named {o}: rank {rank + 1} of {len(res)}, median {med:.4f} ms  min {mn:.4f}; best {res[0][2]} median {res[0][0]:.4f}")
