@@ -491,7 +491,8 @@ int sea_trainset_last_chunks(void);
  * (hEv), computeACF, crossCorr, globalPitch, timeCrn (corrHc) and the initial labelling of Grp (csrc/hw25_kernel.hip,
  * DESIGN.md section 5.11).  Parity: bit for bit against the reference's own functions compiled on a CPU
  * (tests/golden/hw25_golden.npz).  initGroup and pitchDtm follow below (sea_hw25_pitch_*), then computeAM, finalSeg and the
- * whole estimator (sea_hw25_am_batch, sea_hw25_finalseg_batch, sea_hw25_ibm*); resynthesis is not built.
+ * whole estimator (sea_hw25_am_batch, sea_hw25_finalseg_batch, sea_hw25_ibm*), and last resynthesis (sea_hw25_resynth*,
+ * sea_hw25_enhance*): audio in, enhanced audio out.
  * Samples are floats on the int16 scale, as createIBM takes them.  Batch forms (device pointers): d_in_f32 holds the packed
  * batch, utterance u at d_offsets[u] (multiples of 8; the stretch up to the next multiple of 8 past its length must be
  * readable); d_hout / d_hev hold 25x the packed size, utterance u's [25][pitch] block at d_offsets[u] * 25, pitch =
@@ -597,7 +598,7 @@ int sea_hw25_pitch(const float *x, long L, int *pitch, float *grp, float *pratio
  *    SEA_HW25_FINAL_TOO_MANY_SEGMENTS, the mask (grp_final, the stages) all 0;
  *  - fewer than 3 rows: the mask (grp_final, the stages) is all 0 and no flag is set; with no segment upstream grp is all 0,
  *    no frame is voiced, and the mask is all 0 by the reference's own logic.
- * resynthesis (:1498), which writes one waveform as a text file, is not built. */
+ * resynthesis (:1498) follows below (sea_hw25_resynth_*, sea_hw25_enhance_*). */
 enum {
     SEA_HW25_FINAL_STAGES = 5,
     SEA_HW25_FINAL_TOO_MANY_SEGMENTS = 1 << 18,
@@ -622,6 +623,45 @@ int sea_hw25_ibm_batch(const float *d_in_f32, const long long *d_offsets, const 
                        float *d_mask, int *d_pitch, int *d_status, float *d_stages, void *d_scratch, long long total_padded_samples,
                        long long total_rows, const int *d_order, int n_utt, void *stream);
 int sea_hw25_ibm(const float *x, long L, float *mask, int *pitch, int *status);
+/* resynthesis() on the same bank (HuWang.cpp:1498-1549; csrc/hw25_resynth_kernel.hip): the mask applied
+ * to gOut, enhanced audio out.  The same loop is the body of resynth (`mark > 0`, (short) cast to a WAV) and resynth_test
+ * (`mark > 0.5`) in function_2/20141106_speech_enhancement/wav_extract/extractwav.cpp, hence the threshold and the int16 output.
+ * Per channel c = 0..24 in order: gOut[c] / midEarCoeff[c] reversed in time, gammaToneFilter again, / midEarCoeff[c], reversed
+ * back; times the overlap-add weight of the frames whose unit is set (mask > threshold; NaN and -0.0 > 0 are not set); the 25
+ * products added in channel order from +0.0f, every channel multiplied and added whatever its weight (an Inf or NaN sample
+ * under a weight of 0 gives NaN, as in the reference).  The window is not a raised cosine: WINDOW = 200 and OFFSET = 80, so a
+ * set frame f adds up80[o] on [80 (f - 1), 80 f) -- not for f = 0 -- and down120[j], j = 0..119, on [80 f, 80 f + 120), whose
+ * last 40 values rise again.  sea_hw25_resynth_tables_host: up80, down120 in double, and w640[o * 8 + bits], the float weight at
+ * position o = 0..79 of a hop, bit 0 / 1 / 2 of `bits`: frame k - 1 / k / k + 1 (k = the sample's index / 80) exists and is set;
+ * the terms are added in that order, each a double sum rounded to float, as the reference's `weight[..] +=`.  Every pointer
+ * may be null.
+ * Where the reference is undefined, this is defined: the reference's frame loop writes weight[] up to index 80 F + 39 of L
+ * (F = L / 80), past the array when L % 80 < 40 and the last row has a unit set, onto the heap.  Here contributions at indices
+ * >= L are dropped.  Parity: bit for bit against the reference's own resynthesis() compiled on a CPU
+ * (tests/golden/hw25_resynth_golden.npz) on inputs where every channel's largest set frame f has 80 f + 119 < L; elsewhere
+ * against the numpy model that is pinned to that fixture (tests/hw25_resynth_model.py).
+ * sea_hw25_resynth_batch: d_gout as sea_hw25_periphery_gout_batch writes it and d_mask [rows][25] (utterance u's lengths[u] / 80
+ * rows from d_row_offsets[u]) are not modified.  Outputs are packed as the input audio is: utterance u's lengths[u] samples at
+ * d_offsets[u], the padding up to the next multiple of 8 not written; d_out_f32 floats, d_out_i16 their (short) conversion as
+ * the x86-64 build performs it (truncation toward zero to int32, low 16 bits; NaN or a magnitude of 2^31 and more give 0).
+ * Either output may be null, not both.  No scratch.  An utterance shorter than 80 samples has no frame and yields zeros.
+ * sea_hw25_enhance_batch: sea_hw25_ibm_batch followed by the resynthesis (threshold 0) of its own mask from the gOut it keeps
+ * in its scratch, one launch group on `stream`: d_mask, d_pitch, d_status as sea_hw25_ibm_batch writes them, d_scratch of
+ * sea_hw25_ibm_scratch_bytes (total_padded_samples, total_rows, n_utt).  An utterance whose status zeroes the mask yields zeros.
+ * n_utt <= 0 returns 0; null or equal pointers return non-zero before anything is launched.
+ * sea_hw25_resynth / sea_hw25_enhance: one utterance from host memory (up to 150000 samples as sea_hw25_ibm); mask [F][25] with
+ * F = L / 80 (anything else fails); out_f32 [L]; sea_hw25_enhance's mask and pitch may be null.  L = 0 is no work.
+ * sea_hw25_resynth_text_write: one "%f\n" line per sample, byte for byte the file that resynthesis() writes (:1543-1544). */
+int sea_hw25_resynth_tables_host(float *w640, double *up80, double *down120);
+int sea_hw25_resynth_batch(const float *d_gout, const float *d_mask, const long long *d_offsets, const long long *d_lengths,
+                           const long long *d_row_offsets, float threshold, float *d_out_f32, short *d_out_i16, const int *d_order,
+                           int n_utt, void *stream);
+int sea_hw25_enhance_batch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
+                           float *d_out_f32, short *d_out_i16, float *d_mask, int *d_pitch, int *d_status, void *d_scratch,
+                           long long total_padded_samples, long long total_rows, const int *d_order, int n_utt, void *stream);
+int sea_hw25_resynth(const float *x, long L, const float *mask, long F, float threshold, float *out_f32);
+int sea_hw25_enhance(const float *x, long L, float *out_f32, float *mask, int *pitch, int *status);
+int sea_hw25_resynth_text_write(const char *path, const float *out, long L);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

@@ -24,4 +24,5 @@ from .engine import (DoCompCeps, MaskBatch, NoiseSup, PackedBatch, afe_features_
                      make_trainset, snr_lin, trainset_batch, Hw25Result, hw25_correlogram_batch, hw25_frontend,
                      hw25_frontend_batch, hw25_periphery_batch, hw25_split, hw25_tables, Hw25PitchResult, hw25_pitch,
                      hw25_pitch_batch, Hw25AmResult, Hw25MaskResult, hw25_am_batch, hw25_am_tables, hw25_finalseg_batch,
-                     hw25_ibm, hw25_ibm_batch, hw25_periphery_gout_batch)
+                     hw25_ibm, hw25_ibm_batch, hw25_periphery_gout_batch, Hw25EnhanceResult, hw25_enhance, hw25_enhance_batch,
+                     hw25_resynth, hw25_resynth_batch, hw25_resynth_tables)

@@ -104,6 +104,12 @@ PROTOTYPES = {
     "sea_hw25_ibm_scratch_bytes": (_ll, [_ll, _ll, _i]),
     "sea_hw25_ibm_batch": (_i, [_vp] * 9 + [_ll, _ll, _vp, _i, _vp]),
     "sea_hw25_ibm": (_i, [_vp, _l, _vp, _vp, _vp]),
+    "sea_hw25_resynth_tables_host": (_i, [_vp, _vp, _vp]),
+    "sea_hw25_resynth_batch": (_i, [_vp] * 5 + [_c.c_float, _vp, _vp, _vp, _i, _vp]),
+    "sea_hw25_enhance_batch": (_i, [_vp] * 10 + [_ll, _ll, _vp, _i, _vp]),
+    "sea_hw25_resynth": (_i, [_vp, _l, _vp, _l, _c.c_float, _vp]),
+    "sea_hw25_enhance": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
+    "sea_hw25_resynth_text_write": (_i, [_c.c_char_p, _vp, _l]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

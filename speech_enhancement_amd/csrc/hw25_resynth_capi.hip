@@ -1,0 +1,146 @@
+/*
+ * hw25_resynth_capi.hip -- the C ABI of the Hu-Wang 25-channel resynthesis (hw25_resynth_kernel.hip):
+ * sea_hw25_resynth_tables_host, sea_hw25_resynth_batch, sea_hw25_enhance_batch (the whole estimator followed by the
+ * resynthesis of its own mask), the single-utterance forms sea_hw25_resynth and sea_hw25_enhance, and the text writer.  The
+ * batch calls are launches on one stream and nothing else: the lengths stay on the device.
+ */
+#include <cstdio>
+
+#include "capi_internal.h"
+
+using namespace sea_capi;
+
+int sea_hw25_resynth_tables_host(float *w640, double *up80, double *down120)
+{
+    sea_hw25_ola_tables(w640, up80, down120);
+    return 0;
+}
+
+int sea_hw25_resynth_batch(const float *d_gout, const float *d_mask, const long long *d_offsets, const long long *d_lengths,
+                           const long long *d_row_offsets, float threshold, float *d_out_f32, short *d_out_i16, const int *d_order,
+                           int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_gout || !d_mask || !d_offsets || !d_lengths || !d_row_offsets) return fail("hw25_resynth: null pointer (only d_order and one output may be null)");
+    if (!d_out_f32 && !d_out_i16) return fail("hw25_resynth: no output (d_out_f32 and d_out_i16 are both null)");
+    const void *f32 = d_out_f32, *i16 = d_out_i16;
+    if (f32 == i16 || f32 == d_gout || f32 == d_mask || i16 == d_gout || i16 == d_mask)
+        return fail("hw25_resynth: an output must not be an input or the other output");
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::Hw25ResynthArgs a{};
+    a.gout = d_gout;
+    a.mask = d_mask;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.row_offsets = d_row_offsets;
+    a.out_f32 = d_out_f32;
+    a.out_i16 = d_out_i16;
+    a.order = d_order;
+    a.tables = c->hw25;
+    a.threshold = threshold;
+    a.n_utt = n_utt;
+    hipLaunchKernelGGL(sea::hw25_resynth_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_hw25_enhance_batch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
+                           float *d_out_f32, short *d_out_i16, float *d_mask, int *d_pitch, int *d_status, void *d_scratch,
+                           long long total_padded_samples, long long total_rows, const int *d_order, int n_utt, void *stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_out_f32 && !d_out_i16) return fail("hw25_enhance: no output (d_out_f32 and d_out_i16 are both null)");
+    const void *outs[] = {d_out_f32, d_out_i16};
+    for (const void *o : outs)
+        if (o && (o == d_in_f32 || o == d_mask || o == d_pitch || o == d_status || o == d_scratch))
+            return fail("hw25_enhance: an output must not be the input or another output");
+    if (d_out_f32 && (const void *)d_out_f32 == (const void *)d_out_i16) return fail("hw25_enhance: an output must not be the input or another output");
+    /* the mask of createIBM :99-106 is 0 / 1: the reference's `mark > 0` */
+    if (sea_hw25_ibm_batch(d_in_f32, d_offsets, d_lengths, d_row_offsets, d_mask, d_pitch, d_status, nullptr, d_scratch,
+                           total_padded_samples, total_rows, d_order, n_utt, stream))
+        return 1;
+    const float *gout = reinterpret_cast<const float *>(static_cast<const char *>(d_scratch) +
+                                                        hw25_ibm_gout_offset(total_padded_samples, total_rows, n_utt));
+    return sea_hw25_resynth_batch(gout, d_mask, d_offsets, d_lengths, d_row_offsets, 0.0f, d_out_f32, d_out_i16, d_order, n_utt, stream);
+}
+
+int sea_hw25_resynth(const float *x, long L, const float *mask, long F, float threshold, float *out_f32)
+{
+    if (L < 0) return fail("hw25_resynth: L=%ld", L);
+    if (L == 0) return 0;
+    if (!x || !out_f32) return fail("hw25_resynth: null pointer");
+    if (F != (long)sea_hw25_frames(L)) return fail("hw25_resynth: F=%ld, not L / 80 = %lld", F, sea_hw25_frames(L));
+    if (F > 0 && !mask) return fail("hw25_resynth: null pointer");
+    const long long Lp = align8(L), rows = F > 0 ? F : 1;
+    DevBuf<float> din, dstreams, dmask, dout;
+    DevBuf<long long> dmeta;
+    HIP_TRY(din.alloc((size_t)Lp));
+    HIP_TRY(dstreams.alloc((size_t)Lp * SEA_HW25_NCHAN * 3)); /* hout | hev | gout */
+    HIP_TRY(dmask.alloc((size_t)rows * SEA_HW25_NCHAN));
+    HIP_TRY(dout.alloc((size_t)Lp));
+    HIP_TRY(dmeta.alloc(3));
+    const long long meta[3] = {0, L, 0};
+    const size_t plane = (size_t)Lp * SEA_HW25_NCHAN;
+    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
+    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(dmask.p, 0, (size_t)rows * SEA_HW25_NCHAN * sizeof(float)));
+    if (F > 0) HIP_TRY(hipMemcpy(dmask.p, mask, (size_t)F * SEA_HW25_NCHAN * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
+    if (sea_hw25_periphery_gout_batch(din.p, dstreams.p, dstreams.p + plane, dstreams.p + 2 * plane, dmeta.p, dmeta.p + 1, nullptr, 1,
+                                      nullptr))
+        return 1;
+    if (sea_hw25_resynth_batch(dstreams.p + 2 * plane, dmask.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, threshold, dout.p, nullptr, nullptr, 1,
+                               nullptr))
+        return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out_f32, dout.p, (size_t)L * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int sea_hw25_enhance(const float *x, long L, float *out_f32, float *mask, int *pitch, int *status)
+{
+    if (L < 0) return fail("hw25_enhance: L=%ld", L);
+    if (!status || (L > 0 && (!x || !out_f32))) return fail("hw25_enhance: null pointer");
+    if (L == 0) { /* no sample: nothing to compute */
+        *status = 0;
+        return 0;
+    }
+    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
+    DevBuf<float> din, dmask, dout;
+    DevBuf<int> dint;
+    DevBuf<long long> dmeta;
+    DevBuf<char> dscr;
+    HIP_TRY(din.alloc((size_t)Lp));
+    HIP_TRY(dout.alloc((size_t)Lp));
+    HIP_TRY(dmask.alloc((size_t)rows * SEA_HW25_NCHAN));
+    HIP_TRY(dint.alloc((size_t)rows + 1)); /* pitch | status */
+    HIP_TRY(dmeta.alloc(3));
+    HIP_TRY(dscr.alloc((size_t)sea_hw25_ibm_scratch_bytes(Lp, rows, 1)));
+    const long long meta[3] = {0, L, 0};
+    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
+    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
+    if (sea_hw25_enhance_batch(din.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dout.p, nullptr, dmask.p, dint.p, dint.p + rows, dscr.p, Lp, rows,
+                               nullptr, 1, nullptr))
+        return 1;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(status, dint.p + rows, sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_f32, dout.p, (size_t)L * sizeof(float), hipMemcpyDeviceToHost));
+    if (F > 0) {
+        if (mask) HIP_TRY(hipMemcpy(mask, dmask.p, (size_t)F * SEA_HW25_NCHAN * sizeof(float), hipMemcpyDeviceToHost));
+        if (pitch) HIP_TRY(hipMemcpy(pitch, dint.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
+
+int sea_hw25_resynth_text_write(const char *path, const float *out, long L)
+{
+    if (!path || L < 0 || (L > 0 && !out)) return fail("hw25_resynth_text_write: bad argument");
+    FILE *fp = fopen(path, "w");
+    if (!fp) return fail("hw25_resynth_text_write: cannot open %s", path);
+    bool ok = true;
+    for (long n = 0; n < L; n++) ok = fprintf(fp, "%f\n", out[n]) > 0 && ok; /* resynthesis:1543-1544 */
+    ok = fclose(fp) == 0 && ok;
+    return ok ? 0 : fail("hw25_resynth_text_write: writing %s failed", path);
+}

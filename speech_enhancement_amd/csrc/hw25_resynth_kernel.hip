@@ -1,0 +1,160 @@
+/*
+ * hw25_resynth_kernel.hip -- resynthesis() of the Hu-Wang estimator on its 25-channel 8 kHz gammatone bank, gfx950
+ * (function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp:1498-1549; the same loop is the body of resynth and
+ * resynth_test in function_2/20141106_speech_enhancement/wav_extract/extractwav.cpp).  A first form, not tuned.
+ *
+ * Per channel the reference divides gOut by midEarCoeff, filters it backwards in time with the analysis filter, divides
+ * again, weights the result with the overlap-add window of the frames whose unit is set, and adds the 25 channels in order.
+ * Here one wave takes one utterance, in tiles of 64 samples from the last tile to the first:
+ *
+ *   lanes 0..24 = channel   divide -> gammaToneFilter step -> divide for the tile's samples, latest first, gOut read in groups
+ *                           of 8 samples as two 16-byte loads with the next group requested ahead; `reverse` goes to an LDS
+ *                           tile [25][64] with a row stride of 65 words (no bank conflict on either side)
+ *   lanes 0..63 = sample    sum over the channels 0..24 in order from +0.0f of weight * reverse, every channel multiplied and
+ *                           added whatever its weight; coalesced float store and, on request, the x86-64 (short) conversion
+ *
+ * The weight of a channel at sample 80 k + o depends on o and on whether the frames k - 1, k and k + 1 exist and are set: one
+ * of the 640 floats of sea_hw25_ola_tables (sea_tables.c), held in LDS.  A tile touches at most two values of k, so four mask
+ * rows: lanes 0..24 load them before the recurrence, and a ballot per row leaves each row as 25 bits in a scalar register.
+ * Only samples below the length are produced, so what the reference's frame loop writes past its arrays (indices >= L) has
+ * no counterpart here.  Every product and sum is rounded on its own (-ffp-contract=off); the divisions are the compiler's
+ * correctly rounded ones.  No intermediate goes to global memory.
+ */
+#include "sea_device.h"
+#include "sea_kernels.h"
+
+namespace sea {
+
+namespace {
+
+constexpr int kCh = SEA_HW25_NCHAN, kHop = SEA_HW25_HOP;
+constexpr int kTile = 64;            /* samples per tile: one per lane in the summing half */
+constexpr int kGroup = 8;            /* samples per fetch of the recurrence */
+constexpr int kStride = kTile + 1;   /* words per channel row of the LDS tile */
+
+/* gammaToneFilter:231-251 for one sample: returns p[3] * gain taken BEFORE the update */
+struct Gt25 {
+    float p[4], q[4];
+};
+__device__ __forceinline__ float gt25_step(Gt25 &s, float in, float f1, float f2, float gain)
+{
+    const float out = s.p[3] * gain;
+    float x[4], y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[i] = f1 * s.p[i] - f2 * s.q[i];
+        y[i] = f2 * s.p[i] + f1 * s.q[i];
+    }
+    s.p[0] = in * f1 + x[0];
+    s.q[0] = in * f2 + y[0];
+    s.p[1] = s.p[0] + x[1];
+    s.q[1] = s.q[0] + y[1];
+    s.p[2] = s.p[1] + x[1] + x[2];
+    s.q[2] = s.q[1] + y[1] + y[2];
+    s.p[3] = s.p[2] + x[1] + 2 * x[2] + x[3];
+    s.q[3] = s.q[2] + y[1] + 2 * y[2] + y[3];
+    return out;
+}
+
+/* :1513-1519 for the eight samples tg .. tg + 7 of one channel, the latest first; kPartial: the group that holds the
+ * utterance's last sample, whose samples at or past L are skipped */
+template <bool kPartial>
+__device__ __forceinline__ void resynth_group(Gt25 &s, const float (&x)[kGroup], long long tg, long long L, float f1, float f2, float gain,
+                                              float ear, float *row)
+{
+    const int j = (int)(tg & (kTile - 1));
+#pragma unroll
+    for (int k = kGroup - 1; k >= 0; --k) {
+        if (kPartial && tg + k >= L) continue;
+        const float g2 = gt25_step(s, x[k] / ear, f1, f2, gain);
+        row[j + k] = g2 / ear;
+    }
+}
+
+/* (short) of a float as the x86-64 build converts it (cvttss2si + low half): truncation toward zero to int32, the low 16 bits
+ * kept; NaN or a magnitude of 2^31 and more give 0 */
+__device__ __forceinline__ short resynth_to_short(float v)
+{
+    const int i = fabsf(v) < 2147483648.0f ? (int)v : 0;
+    return (short)(unsigned short)((unsigned)i & 0xffffu);
+}
+
+} // namespace
+
+__global__ __launch_bounds__(64) void hw25_resynth_kernel(Hw25ResynthArgs a)
+{
+    __shared__ float rev[kCh * kStride];
+    __shared__ float wtab[SEA_HW25_OLA_WEIGHTS];
+    const int lane = threadIdx.x;
+    const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    const long long off = a.offsets[u], L = a.lengths[u];
+    if (L <= 0) return;
+    const long long pitch = (L + 7) & ~7LL, nfr = L / kHop, row0 = a.row_offsets[u];
+    const sea_hw25_tables &t = *a.tables;
+    for (int i = lane; i < SEA_HW25_OLA_WEIGHTS; i += kTile) wtab[i] = t.olaW[i];
+    const bool chan = lane < kCh; /* the lanes that run a channel's recurrence */
+    const int c = chan ? lane : 0;
+    const float f1 = t.f1[c], f2 = t.f2[c], gain = t.gain[c], ear = t.midEar[c];
+    const float *src = a.gout + off * kCh + c * pitch;
+    const float *mask = a.mask + row0 * kCh + c;
+    const float thr = a.threshold;
+    float *row = rev + c * kStride;
+    Gt25 s = {};
+    /* gout holds `pitch` floats per channel: the reads of the last group stay inside the channel's padded stretch */
+    float4 n0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n1 = n0;
+    if (chan) {
+        const long long tg = (L - 1) & ~(long long)(kGroup - 1);
+        n0 = *reinterpret_cast<const float4 *>(src + tg);
+        n1 = *reinterpret_cast<const float4 *>(src + tg + 4);
+    }
+    for (long long tile = (L - 1) / kTile; tile >= 0; --tile) {
+        const long long t0 = tile * kTile;
+        const long long k0 = t0 / kHop; /* the frame of the tile's first sample; its last one lies in k0 or k0 + 1 */
+        /* the units of the frames k0 - 1 .. k0 + 2; a frame that does not exist is not set */
+        float mv[4];
+        bool have[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const long long f = k0 - 1 + r;
+            have[r] = chan && f >= 0 && f < nfr;
+            mv[r] = have[r] ? mask[f * kCh] : 0.0f;
+        }
+        if (chan) {
+#pragma unroll 1
+            for (int gi = kTile / kGroup - 1; gi >= 0; --gi) {
+                const long long tg = t0 + gi * kGroup;
+                if (tg >= L) continue;
+                const float x[kGroup] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w};
+                if (tg >= kGroup) {
+                    n0 = *reinterpret_cast<const float4 *>(src + tg - kGroup);
+                    n1 = *reinterpret_cast<const float4 *>(src + tg - kGroup + 4);
+                }
+                if (tg + kGroup <= L) resynth_group<false>(s, x, tg, L, f1, f2, gain, ear, row);
+                else resynth_group<true>(s, x, tg, L, f1, f2, gain, ear, row);
+            }
+        }
+        unsigned set[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) set[r] = (unsigned)__ballot(have[r] && mv[r] > thr); /* NaN and -0.0 > 0 are false */
+        __syncthreads();
+        const long long tt = t0 + lane;
+        if (tt < L) {
+            const long long k = tt / kHop;
+            const int o = (int)(tt - k * kHop);
+            const bool next = k != k0;
+            const unsigned b0 = next ? set[1] : set[0], b1 = next ? set[2] : set[1], b2 = next ? set[3] : set[2];
+            const float *w = wtab + o * 8;
+            float sum = 0.0f;
+#pragma unroll
+            for (int ch = 0; ch < kCh; ++ch) {
+                const unsigned bits = ((b0 >> ch) & 1u) | (((b1 >> ch) & 1u) << 1) | (((b2 >> ch) & 1u) << 2);
+                sum += w[bits] * rev[ch * kStride + lane];
+            }
+            if (a.out_f32) a.out_f32[off + tt] = sum;
+            if (a.out_i16) a.out_i16[off + tt] = resynth_to_short(sum);
+        }
+        __syncthreads();
+    }
+}
+
+} // namespace sea

@@ -438,6 +438,24 @@ struct Hw25FinalArgs {
 #define SEA_HW25_FINAL_SCRATCH_WORDS 150 /* per row: lab, key, lo, hi, m, g [25] */
 __global__ void hw25_finalseg_kernel(Hw25FinalArgs a); /* grid n_utt x 64 */
 
+/* resynthesis:1498-1549 on the same bank (hw25_resynth_kernel.hip).  gout: hout's layout, only read; mask [rows][25], utterance
+ * u's lengths[u] / 80 rows from row_offsets[u], a unit set where mask > threshold; out_f32 / out_i16 (either may be null):
+ * the packed sample space of the input audio, utterance u's lengths[u] samples at offsets[u]. */
+struct Hw25ResynthArgs {
+    const float *gout;
+    const float *mask;
+    const long long *offsets;
+    const long long *lengths;
+    const long long *row_offsets;
+    float *out_f32;
+    short *out_i16;
+    const int *order;
+    const sea_hw25_tables *tables;
+    float threshold;
+    int n_utt;
+};
+__global__ void hw25_resynth_kernel(Hw25ResynthArgs a); /* grid n_utt x 64 */
+
 __global__ void subband_kernel(SubbandArgs a);
 __global__ void ns_denoise_pipe_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_big_kernel(NsBatchArgs a); /* lower-register form for > 4 utterances per CU */

@@ -674,6 +674,28 @@ void sea_build_hw25_tables(sea_hw25_tables *t)
         t->q0 = (float)(t->c0 * (Lc + R) / kt);
         t->w0 = (float)(t->c0 * R / X);
     }
+    sea_hw25_ola_tables(t->olaW, NULL, NULL);
+}
+
+void sea_hw25_ola_tables(float *w640, double *up80, double *down120)
+{ /* resynthesis:1521-1536 */
+    const double kPiHW = 3.1415926535897932384626433832795;
+    double up[SEA_HW25_HOP], down[SEA_HW25_WINDOW - SEA_HW25_HOP];
+    long n;
+    int o, bits;
+    for (n = 0; n < SEA_HW25_HOP; n++) up[n] = 0.5 * (1.0 + cos(n * kPiHW / (SEA_HW25_HOP) + kPiHW));
+    for (n = SEA_HW25_HOP; n < SEA_HW25_WINDOW; n++) down[n - SEA_HW25_HOP] = 0.5 * (1.0 + cos((n - SEA_HW25_HOP) * kPiHW / (SEA_HW25_HOP)));
+    if (up80) memcpy(up80, up, sizeof up);
+    if (down120) memcpy(down120, down, sizeof down);
+    if (!w640) return;
+    for (o = 0; o < SEA_HW25_HOP; o++)
+        for (bits = 0; bits < 8; bits++) { /* the frames in ascending order, each `weight[..] += double` rounded to float */
+            float w = 0.0;
+            if ((bits & 1) && o < SEA_HW25_WINDOW - 2 * SEA_HW25_HOP) w += down[SEA_HW25_HOP + o];
+            if (bits & 2) w += down[o];
+            if (bits & 4) w += up[o];
+            w640[o * 8 + bits] = w;
+        }
 }
 
 void sea_build_hw25_twiddles(float *tw, int direct)

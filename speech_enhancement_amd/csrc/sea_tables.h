@@ -242,7 +242,8 @@ enum {
     SEA_HW25_MAXLEN = 150000,               /* MAX_SIG_LENGTH: computeAM's FFT is 2^N points, N <= 18 */
     SEA_HW25_MAXLOG2 = 18,
     SEA_HW25_TWIDDLES = (1 << 18) - 1,      /* fft:1650-1676, every stage's u values: period p's p entries start at p - 1 */
-    SEA_HW25_AM_MAXTAPS = 576               /* amPatt's fLength + 1 is at most 564 (mp = 100) */
+    SEA_HW25_AM_MAXTAPS = 576,              /* amPatt's fLength + 1 is at most 564 (mp = 100) */
+    SEA_HW25_OLA_WEIGHTS = 640              /* resynthesis: 80 positions in a hop x 8 states of the three frames that reach it */
 };
 /* computeAM:1156, N = int (ceil (log (L * 1.0) / log (2 * 1.0))) in double, evaluated with the C library on a CPU at L = 2^k,
  * k = 7..17: the quotient is the exact integer at every one of them, so N = k (one ulp above it would have made N = k + 1 and
@@ -256,8 +257,16 @@ typedef struct {
     float ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt; /* hairCell:261-268 */
     float q0, c0, w0;                             /* its initial state, :271-274 */
     float am_a, am_beta;                          /* kaiserPara (0.01, ..): a = -20 log10 (delta) and beta, amPatt:1215 */
+    float olaW[SEA_HW25_OLA_WEIGHTS];             /* resynthesis:1521-1536, sea_hw25_ola_tables's w640 */
 } sea_hw25_tables;
 void sea_build_hw25_tables(sea_hw25_tables *t);
+/* resynthesis:1521-1536, the overlap-add weight of one channel at a sample 80 k + o.  up80[n] = 0.5 (1 + cos (n pi / 80 + pi)),
+ * n = 0..79, is the rising half of a set frame (:1530, on the 80 samples before the frame's own); down120[j] = 0.5 (1 + cos (j
+ * pi / 80)), j = 0..119, what follows it (:1534; WINDOW - OFFSET = 120 samples, of which the last 40 rise again).  The sample
+ * receives, in the order of the frame loop, down120[80 + o] from frame k - 1 (only where o < 40), down120[o] from frame k and
+ * up80[o] from frame k + 1, each a double added to the float weight and rounded to float.  w640[o * 8 + bits] is the result,
+ * bit 0 / 1 / 2 of `bits`: frame k - 1 / k / k + 1 exists and is set.  Every pointer may be null. */
+void sea_hw25_ola_tables(float *w640, double *up80, double *down120);
 /* fft:1654-1674 for every period 1, 2, .., 2^17: u starts at (1, 0) and is multiplied by w once per j, in float; tw holds
  * SEA_HW25_TWIDDLES (re, im) pairs.  direct = 1 forward, -1 inverse. */
 void sea_build_hw25_twiddles(float *tw, int direct);

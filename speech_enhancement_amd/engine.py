@@ -1284,6 +1284,102 @@ def hw25_ibm(x):
 
 
 # ------------------------------------------------------------------------------------------------
+# the Hu-Wang estimator's resynthesis (HuWang.cpp:1498-1549; csrc/hw25_resynth_kernel.hip): the mask applied, audio out
+# ------------------------------------------------------------------------------------------------
+def hw25_resynth_tables():
+    """The overlap-add tables of resynthesis(): up float64 [80], down float64 [120] and w float32 [80][8], the weight at
+    position o of a hop for the eight states (bit 0 / 1 / 2: frame k - 1 / k / k + 1 exists and is set)."""
+    lib = _lib.load()
+    w, up, down = np.zeros((80, 8), np.float32), np.zeros(80, np.float64), np.zeros(120, np.float64)
+    _lib.check(lib.sea_hw25_resynth_tables_host(_np_ptr(w), _np_ptr(up), _np_ptr(down)), "sea_hw25_resynth_tables_host")
+    return dict(w=w, up=up, down=down)
+
+
+def _hw25_rows(batch):
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
+    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
+    return rows, offs
+
+
+def hw25_resynth_batch(batch, gout, mask, row_offsets=None, threshold=0.0, int16=False, use_order=True):
+    """resynthesis() for every utterance of the batch from hw25_periphery_gout_batch()'s gOut and a mask [rows][25] on the
+    device (a unit is set where mask > threshold; row_offsets: the int64 device tensor that goes with it, else length // 80 rows
+    per utterance one after the other) -> float32 audio packed like batch.data (batch.split cuts it); int16=True: (audio, the
+    int16 conversion of it)."""
+    torch = _torch()
+    lib = _lib.load()
+    dev = gout.device
+    d_offs = row_offsets if row_offsets is not None else torch.from_numpy(_hw25_rows(batch)[1]).to(dev)
+    mask = mask.to(torch.float32).contiguous()
+    out = torch.zeros(batch.total, dtype=torch.float32, device=dev)
+    out16 = torch.zeros(batch.total, dtype=torch.int16, device=dev) if int16 else None
+    rc = lib.sea_hw25_resynth_batch(_dptr(gout), _dptr(mask), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs),
+                                    float(threshold), _dptr(out), _dptr(out16), _dptr(batch.order) if use_order else None,
+                                    batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_resynth_batch")
+    return (out, out16) if int16 else out
+
+
+def hw25_resynth(x, mask, threshold=0.0):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale) and its mask [len(x) // 80][25] -> the
+    resynthesised float32 audio [len(x)]."""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    mask = np.ascontiguousarray(mask, dtype=np.float32).reshape(-1, HW25_NCHAN)
+    out = np.zeros(x.size, np.float32)
+    rc = lib.sea_hw25_resynth(_np_ptr(x), x.size, _np_ptr(mask), mask.shape[0], float(threshold), _np_ptr(out))
+    _lib.check(rc, "sea_hw25_resynth")
+    return out
+
+
+class Hw25EnhanceResult(Hw25MaskResult):
+    """What hw25_enhance_batch() computed, device tensors: audio float32, packed like the batch's data (batch.split cuts it),
+    with mask [rows][25], pitch int32 [rows] and status int32 [n_utt] as hw25_ibm_batch() gives them.  utterance(u): numpy."""
+
+    def utterance(self, u):
+        out = super().utterance(u)
+        off, L = int(self.batch.host_offsets[u]), int(self.batch.host_lengths[u])
+        out["audio"] = self.audio[off:off + L].cpu().numpy()
+        return out
+
+
+def hw25_enhance_batch(batch, use_order=True):
+    """createIBM() followed by resynthesis() of its own mask for every utterance of the batch, one launch group on the
+    current stream -> Hw25EnhanceResult."""
+    torch = _torch()
+    lib = _lib.load()
+    x = _hw25_input(batch)
+    dev = x.device
+    rows, offs = _hw25_rows(batch)
+    n, total = max(int(rows.sum()), 1), max(int(batch.total), 8)
+    audio = torch.zeros(total, dtype=torch.float32, device=dev)
+    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
+    pitch = torch.zeros(n, dtype=torch.int32, device=dev)
+    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
+    scratch = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, n, int(batch.n_utt))), dtype=torch.uint8, device=dev)
+    rc = lib.sea_hw25_enhance_batch(_dptr(x), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(torch.from_numpy(offs).to(dev)),
+                                    _dptr(audio), None, _dptr(mask), _dptr(pitch), _dptr(status), _dptr(scratch), total, n,
+                                    _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
+    _lib.check(rc, "sea_hw25_enhance_batch")
+    return Hw25EnhanceResult(batch=batch, audio=audio, mask=mask, grp_final=None, status=status, stages=None, pitch=pitch,
+                             host_row_offsets=offs, host_rows=rows)
+
+
+def hw25_enhance(x):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict: audio float32 [L], the enhanced
+    signal; mask [F][25] floats 0 / 1, pitch int32 [F], status, as hw25_ibm() gives them."""
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    F = x.size // HW25_HOP
+    r = dict(audio=np.zeros(x.size, np.float32), mask=np.zeros((F, HW25_NCHAN), np.float32), pitch=np.zeros(F, np.int32))
+    status = np.zeros(1, np.int32)
+    rc = lib.sea_hw25_enhance(_np_ptr(x), x.size, _np_ptr(r["audio"]), _np_ptr(r["mask"]), _np_ptr(r["pitch"]), _np_ptr(status))
+    _lib.check(rc, "sea_hw25_enhance")
+    r["status"] = int(status[0])
+    return r
+
+
+# ------------------------------------------------------------------------------------------------
 # the training-set builder (enhancement_extract_subband_linux/cpp/main.cpp:91-274): mix at an SNR, subbands, IRM target
 # ------------------------------------------------------------------------------------------------
 def snr_lin(db):

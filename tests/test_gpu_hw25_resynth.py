@@ -1,0 +1,329 @@
+"""The Hu-Wang 25-channel resynthesis on the GPU (csrc/hw25_resynth_kernel.hip) against what the reference's own resynthesis()
+produced (tests/golden/hw25_resynth_golden.npz) and, where the reference writes out of bounds or the fixture holds nothing,
+against the numpy model that the CPU tests pin to that fixture (tests/hw25_resynth_model.py).  Every comparison is on the bits.
+
+The fixture batch holds the six in-bounds audio inputs and the two hand inputs (eight utterances, the longest 12000 samples);
+every other batch holds at most eight utterances of at most 4048 samples.  Output buffers are filled with a sentinel and carry
+slack past their end; the padding between an utterance's length and its pitch must keep the sentinel."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import hw25_am_model as AM
+from tests import hw25_model as M
+from tests import hw25_resynth_model as RM
+
+pytestmark = pytest.mark.gpu
+
+NCH = 25
+SENT, SENT16 = -7777.25, -7777
+SLACK = 64
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _lib():
+    from speech_enhancement_amd import _lib
+    return _lib, _lib.load()
+
+
+def _stream():
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _pack(utts):
+    import speech_enhancement_amd as sea
+    return sea.PackedBatch.from_arrays([np.ascontiguousarray(x, np.float32) for x in utts], device="cuda:0", dtype=np.float32)
+
+
+def _rows(batch):
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+    return rows, np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+
+
+def _gout(batch):
+    import speech_enhancement_amd as sea
+    return sea.hw25_periphery_gout_batch(batch)[2]
+
+
+def launch(batch, gout, masks, threshold=0.0, order=None, f32=True, i16=False):
+    """sea_hw25_resynth_batch on sentinel-filled outputs with slack -> per utterance (floats, shorts); asserts that the padding
+    and the slack keep the sentinel, that every sample was written and that the inputs are unchanged"""
+    import torch
+    lib_mod, lib = _lib()
+    rows, offs = _rows(batch)
+    assert [m.shape for m in masks] == [(int(r), NCH) for r in rows]
+    flat = np.concatenate([np.asarray(m, np.float32).reshape(-1, NCH) for m in masks] + [np.full((1, NCH), 1.0, np.float32)])
+    d_mask = torch.from_numpy(flat).to("cuda:0")
+    d_offs = torch.from_numpy(offs).to("cuda:0")
+    out = torch.full((batch.total + SLACK,), SENT, dtype=torch.float32, device="cuda:0") if f32 else None
+    out16 = torch.full((batch.total + SLACK,), SENT16, dtype=torch.int16, device="cuda:0") if i16 else None
+    before = gout.clone(), d_mask.clone()
+    rc = lib.sea_hw25_resynth_batch(_ptr(gout), _ptr(d_mask), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(d_offs),
+                                    ctypes.c_float(threshold), _ptr(out), _ptr(out16), _ptr(order), batch.n_utt, _stream())
+    lib_mod.check(rc, "sea_hw25_resynth_batch")
+    torch.cuda.synchronize()
+    assert torch.equal(gout.view(torch.int32), before[0].view(torch.int32)), "gout changed"
+    assert torch.equal(d_mask.view(torch.int32), before[1].view(torch.int32)), "the mask changed"
+    res = []
+    for name, t, sent in (("f32", out, np.float32(SENT)), ("i16", out16, np.int16(SENT16))):
+        if t is None:
+            res.append([None] * batch.n_utt)
+            continue
+        host = t.cpu().numpy()
+        written = np.zeros(len(host), bool)
+        per = []
+        for off, L in zip(batch.host_offsets, batch.host_lengths):
+            written[int(off):int(off) + int(L)] = True
+            per.append(host[int(off):int(off) + int(L)].copy())
+        assert (host[~written] == sent).all(), f"{name}: the padding or the slack past the output was written"
+        if name == "f32":
+            assert not (host[written] == sent).any(), "a sample was not written"
+        res.append(per)
+    return res[0], res[1]
+
+
+# ---- the fixture's cases -----------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def fix():
+    """the six audio inputs and the two hand inputs as one batch, its gOut on the GPU (computed once, never changed)"""
+    g, am = RM.load_golden(), AM.load_golden()
+    names = list(RM.AUDIO_CASES) + list(RM.HAND_INPUTS)
+    xs = AM.audio_inputs()
+    utts = [xs[k] for k in RM.AUDIO_CASES] + [RM.hand_input(i) for i in RM.HAND_INPUTS]
+    assert [len(x) for x in utts] == [4000, 4000, 4000, 1600, 2048, 12000, 2048, 1640]
+    batch = _pack(utts)
+    return dict(g=g, am=am, names=names, utts=utts, batch=batch, gout=_gout(batch))
+
+
+def test_fixture_cases_equal_the_references_floats(fix):
+    g, batch = fix["g"], fix["batch"]
+    n_audio = len(RM.AUDIO_CASES)
+    seen = set()
+    for r, hand in enumerate(RM.HAND_MASKS):
+        keys = [f"a_{k}" for k in RM.AUDIO_CASES] + [f"h_{i}_{hand}" for i in RM.HAND_INPUTS]
+        masks = [g[f"mask_{k}"].astype(np.float32) for k in keys]
+        got, _ = launch(batch, fix["gout"], masks)
+        for u, k in enumerate(keys):
+            if u < n_audio and r:
+                continue  # the audio cases once
+            assert M.same_bits(got[u], g[f"out_{k}"]), f"{k}: not the reference's resynthesis"
+            seen.add(k)
+    assert len(seen) == 18 == len([k for k in g if k.startswith("out_")])
+
+
+def test_enhance_equals_the_reference_end_to_end(fix):
+    import torch
+    import speech_enhancement_amd as sea
+    g, am = fix["g"], fix["am"]
+    batch = _pack(fix["utts"][:len(RM.AUDIO_CASES)])
+    data = batch.data.clone()
+    res = sea.hw25_enhance_batch(batch)
+    ibm = sea.hw25_ibm_batch(batch)
+    plain = sea.hw25_enhance_batch(batch, use_order=False)
+    torch.cuda.synchronize()
+    assert torch.equal(res.mask.view(torch.int32), ibm.mask.view(torch.int32)) and torch.equal(res.pitch, ibm.pitch)
+    assert torch.equal(res.status, ibm.status)
+    assert torch.equal(res.audio.view(torch.int32), plain.audio.view(torch.int32)), "the result depends on the launch order"
+    assert torch.equal(batch.data.view(torch.int32), data.view(torch.int32)), "the input changed"
+    for u, k in enumerate(RM.AUDIO_CASES):
+        got = res.utterance(u)
+        assert np.array_equal(got["mask"], am[f"mask_{k}"].astype(np.float32)), f"{k}: the mask is not createIBM's"
+        assert M.same_bits(got["audio"], g[f"out_a_{k}"]), f"{k}: audio in, enhanced audio out is not the reference's"
+        assert got["status"] >> 16 == 0
+
+
+def test_out_of_the_references_bounds_against_the_model(fix):
+    """m9 and r: createIBM sets units in frame 49 of 50 at L = 4000, where the reference writes past weight[]"""
+    import speech_enhancement_amd as sea
+    am = fix["am"]
+    xs = AM.audio_inputs()
+    batch = _pack([xs[k] for k in RM.MODEL_ONLY_CASES])
+    res = sea.hw25_enhance_batch(batch)
+    for u, k in enumerate(RM.MODEL_ONLY_CASES):
+        got = res.utterance(u)
+        mask = am[f"mask_{k}"].astype(np.float32)
+        assert mask[49].any() and np.array_equal(got["mask"], mask), k
+        assert M.same_bits(got["audio"], RM.resynth_input(k, mask)), f"{k}: not the model's resynthesis"
+
+
+# ---- mixed lengths, launch order, sentinels ------------------------------------------------------------------------------------
+def _mixed(lengths, seed):
+    """slices of p with random 0 / 1 masks whose last rows have units set (the drop rule), the model's result for each"""
+    rng = np.random.default_rng(seed)
+    p = AM.audio_inputs()["p12000"]
+    t = M.tables()
+    utts = [np.ascontiguousarray(p[1000 + 37 * i:1000 + 37 * i + L]) for i, L in enumerate(lengths)]
+    masks = [(rng.random((L // 80, NCH)) < 0.5).astype(np.float32) for L in lengths]
+    for m in masks:
+        if len(m):
+            m[-1, ::2] = 1
+    want = [RM.resynth(AM.gout(x, t), m, 0.0, t) for x, m in zip(utts, masks)]
+    return utts, masks, want
+
+
+@pytest.mark.parametrize("lengths,seed", [((0, 79, 80, 119, 120, 1603, 1640, 2048), 1), ((1, 63, 64, 65, 127, 128, 129, 7), 2)])
+def test_mixed_batch_against_the_model(lengths, seed):
+    import torch
+    utts, masks, want = _mixed(lengths, seed)
+    batch = _pack(utts)
+    gout = _gout(batch)
+    assert not np.array_equal(batch.order.cpu().numpy(), np.arange(batch.n_utt)), "the batch's launch order is no permutation"
+    perm = torch.tensor([3, 7, 0, 5, 1, 6, 2, 4], dtype=torch.int32, device="cuda:0")
+    for run, order in (("batch order", batch.order), ("no order", None), ("permuted", perm)):
+        got, got16 = launch(batch, gout, masks, order=order, i16=True)
+        for u, L in enumerate(lengths):
+            assert got[u].shape == (L,) and M.same_bits(got[u], want[u]), f"{run}, L = {L}: not the model's resynthesis"
+            assert np.array_equal(got16[u], RM.to_short(want[u])), f"{run}, L = {L}: int16"
+            if L < 80:
+                assert not got[u].any(), f"L = {L}: an utterance without a frame must give zeros"
+    only16 = launch(batch, gout, masks, f32=False, i16=True)[1]
+    assert all(np.array_equal(a, RM.to_short(w)) for a, w in zip(only16, want))
+    assert any(len(w) and np.abs(w).max() > 40 for w in want), "the case carries no signal"
+
+
+# ---- thresholds and mask values ------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def hand(fix):
+    batch = _pack([RM.hand_input(i) for i in RM.HAND_INPUTS])
+    return dict(batch=batch, gout=_gout(batch), g=fix["g"])
+
+
+def test_thresholds_on_soft_masks(hand):
+    masks = [RM.hand_mask("soft", len(RM.hand_input(i)) // 80) for i in RM.HAND_INPUTS]
+    at0, _ = launch(hand["batch"], hand["gout"], masks, threshold=0.0)
+    at05, _ = launch(hand["batch"], hand["gout"], masks, threshold=0.5)
+    for u, i in enumerate(RM.HAND_INPUTS):
+        assert M.same_bits(at0[u], hand["g"][f"out_h_{i}_soft"]), f"{i}: threshold 0 is the reference's mark > 0"
+        assert M.same_bits(at05[u], RM.resynth_input(i, masks[u], 0.5)), f"{i}: threshold 0.5"
+        assert M.same_bits(at05[u], RM.resynth_input(i, (masks[u] == np.float32(0.7)).astype(np.float32))), i
+        assert not M.same_bits(at0[u], at05[u])
+
+
+def test_nan_and_negative_zero_count_as_not_set(hand):
+    rng = np.random.default_rng(5)
+    masks, cleaned = [], []
+    for i in RM.HAND_INPUTS:
+        nfr = len(RM.hand_input(i)) // 80
+        m = (rng.random((nfr, NCH)) < 0.4).astype(np.float32)
+        odd = rng.integers(0, 4, m.shape)
+        m[odd == 1] = np.nan
+        m[odd == 2] = -0.0
+        m[(odd == 3) & (m == 0)] = -1.0
+        masks.append(m)
+        with np.errstate(invalid="ignore"):
+            cleaned.append((m > 0).astype(np.float32))
+    got, _ = launch(hand["batch"], hand["gout"], masks)
+    for u, i in enumerate(RM.HAND_INPUTS):
+        assert np.isnan(masks[u]).sum() > 50 and (np.signbit(masks[u]) & (masks[u] == 0)).sum() > 50
+        assert M.same_bits(got[u], RM.resynth_input(i, masks[u])), f"{i}: NaN / -0.0 / negative marks"
+        assert M.same_bits(got[u], RM.resynth_input(i, cleaned[u])), i
+        assert np.isfinite(got[u]).all()
+
+
+def test_a_single_inf_sample_against_the_model():
+    """Inf enters the filter state for good: every later gOut is NaN, and so is all of the second pass but the sample it starts
+    from; a weight of zero does not hide it (0 * NaN), as in the reference's literal arithmetic"""
+    x = RM.hand_input("w2048").copy()
+    x[1500] = np.inf
+    t = M.tables()
+    mask = RM.hand_mask("checker", len(x) // 80)
+    with np.errstate(all="ignore"):
+        want = RM.resynth(AM.gout(x, t), mask, 0.0, t)
+    batch = _pack([x, RM.hand_input("t1640")])
+    got, got16 = launch(batch, _gout(batch), [mask, RM.hand_mask("checker", 20)], i16=True)
+    assert np.isnan(want).sum() >= len(x) - 1 and M.same_bits(got[0], want)
+    assert np.array_equal(got16[0], RM.to_short(want)) and not got16[0].any()
+    assert M.same_bits(got[1], RM.load_golden()["out_h_t1640_checker"]), "the neighbour of the utterance with the Inf"
+
+
+def test_int16_output_is_the_x86_conversion():
+    """t scaled by four: samples beyond +-32767 wrap as the x86-64 (short) cast does"""
+    xs = [RM.hand_input("t1640") * np.float32(4), AM.audio_inputs()["w1600"]]
+    t = M.tables()
+    masks = [RM.hand_mask("ones", len(x) // 80) for x in xs]
+    want = [RM.resynth(AM.gout(x, t), m, 0.0, t) for x, m in zip(xs, masks)]
+    batch = _pack(xs)
+    got, got16 = launch(batch, _gout(batch), masks, i16=True)
+    for u in range(2):
+        assert M.same_bits(got[u], want[u]) and got16[u].dtype == np.int16
+        assert np.array_equal(got16[u], RM.to_short(want[u])), "int16 is not the x86 conversion of the float output"
+    assert (np.abs(want[0]) > 32768).sum() > 100 and np.abs(want[1]).max() < 32767
+    wrapped = np.abs(want[0]) > 32768
+    assert not np.array_equal(got16[0][wrapped], np.clip(np.trunc(want[0][wrapped]), -32768, 32767).astype(np.int16)), "saturated"
+
+
+# ---- the Python layer, the single-utterance forms, refusals -------------------------------------------------------------------------
+def test_single_utterance_forms_equal_the_batch_forms(fix):
+    import speech_enhancement_amd as sea
+    g, am = fix["g"], fix["am"]
+    x = fix["utts"][3]  # w1600
+    mask = am["mask_w1600"].astype(np.float32)
+    assert M.same_bits(sea.hw25_resynth(x, mask), g["out_a_w1600"])
+    soft = RM.hand_mask("soft", 20)
+    x2 = RM.hand_input("t1640")
+    assert M.same_bits(sea.hw25_resynth(x2, soft, threshold=0.5), RM.resynth_input("t1640", soft, 0.5))
+    one = sea.hw25_enhance(x)
+    assert M.same_bits(one["audio"], g["out_a_w1600"]) and np.array_equal(one["mask"], mask) and one["status"] >> 16 == 0
+    assert np.array_equal(one["pitch"], am["pitch_w1600"])
+    res = sea.hw25_enhance_batch(_pack([x, x2[:79]]))
+    assert M.same_bits(res.utterance(0)["audio"], one["audio"]) and not res.utterance(1)["audio"].any()
+    # the Python batch form with the int16 output, on the fixture's batch
+    masks = [g[f"mask_a_{k}"] for k in RM.AUDIO_CASES] + [g[f"mask_h_{i}_ones"] for i in RM.HAND_INPUTS]
+    import torch
+    d_mask = torch.from_numpy(np.concatenate(masks).astype(np.float32)).to("cuda:0")
+    audio, shorts = sea.hw25_resynth_batch(fix["batch"], fix["gout"], d_mask, int16=True)
+    got, got16 = fix["batch"].split(audio), fix["batch"].split(shorts)
+    assert M.same_bits(np.asarray(got[7], np.float32), g["out_h_t1640_ones"]) and M.same_bits(np.asarray(got[0], np.float32), g["out_a_p"])
+    assert np.array_equal(np.asarray(got16[7]), RM.to_short(g["out_h_t1640_ones"]))
+    # short and empty inputs
+    short = sea.hw25_enhance(x[:79])
+    assert short["audio"].shape == (79,) and not short["audio"].any() and short["mask"].shape == (0, 25)
+    assert not sea.hw25_resynth(x[:79], np.zeros((0, 25), np.float32)).any()
+    empty = sea.hw25_enhance(np.zeros(0, np.float32))
+    assert empty["audio"].shape == (0,) and empty["status"] == 0
+    assert sea.hw25_resynth(np.zeros(0, np.float32), np.zeros((0, 25), np.float32)).shape == (0,)
+    with pytest.raises(sea.SeaError):
+        sea.hw25_resynth(x, mask[:19])
+
+
+def test_null_and_shared_buffers_are_refused(hand):
+    import torch
+    _, lib = _lib()
+    batch, gout = hand["batch"], hand["gout"]
+    rows, offs = _rows(batch)
+    d_mask = torch.zeros((int(rows.sum()), NCH), dtype=torch.float32, device="cuda:0")
+    d_offs = torch.from_numpy(offs).to("cuda:0")
+    out = torch.zeros(batch.total, dtype=torch.float32, device="cuda:0")
+    out16 = torch.zeros(batch.total, dtype=torch.int16, device="cuda:0")
+
+    def call(gout_, mask_, f32, i16, n=batch.n_utt):
+        return lib.sea_hw25_resynth_batch(_ptr(gout_), _ptr(mask_), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(d_offs),
+                                          ctypes.c_float(0.0), _ptr(f32), _ptr(i16), None, n, _stream())
+
+    assert call(gout, d_mask, None, None) != 0, "no output at all must be refused"
+    assert call(None, d_mask, out, None) != 0 and call(gout, None, out, None) != 0
+    assert call(gout, d_mask, gout, None) != 0 and call(gout, d_mask, d_mask, None) != 0 and call(gout, d_mask, out, out) != 0
+    assert call(None, None, None, None, n=0) == 0, "n_utt <= 0 is no work"
+    assert call(gout, d_mask, out, out16) == 0 and call(gout, d_mask, None, out16) == 0
+    # the whole chain: no output, and an output that is the input
+    total, n = int(batch.total), int(rows.sum())
+    o = dict(mask=d_mask, pitch=torch.zeros(n, dtype=torch.int32, device="cuda:0"), status=torch.zeros(2, dtype=torch.int32, device="cuda:0"))
+    scratch = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, n, 2)), dtype=torch.uint8, device="cuda:0")
+
+    def enhance(f32, i16, mask_=d_mask):
+        return lib.sea_hw25_enhance_batch(_ptr(batch.data), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(d_offs), _ptr(f32), _ptr(i16),
+                                          _ptr(mask_), _ptr(o["pitch"]), _ptr(o["status"]), _ptr(scratch), total, n, None, 2, _stream())
+
+    assert enhance(None, None) != 0 and enhance(batch.data, None) != 0 and enhance(d_mask, None) != 0 and enhance(out, None, None) != 0
+    assert enhance(out, out16) == 0
+    torch.cuda.synchronize()
+    for u, i in enumerate(RM.HAND_INPUTS):
+        off, L = int(batch.host_offsets[u]), int(batch.host_lengths[u])
+        a, s = out[off:off + L].cpu().numpy(), out16[off:off + L].cpu().numpy()
+        m = d_mask[int(offs[u]):int(offs[u]) + int(rows[u])].cpu().numpy()
+        assert M.same_bits(a, RM.resynth_input(i, m)) and np.array_equal(s, RM.to_short(a)), i

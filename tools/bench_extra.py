@@ -14,6 +14,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw25 --steps 5  # the Hu-Wang front half on the 25-channel bank: periphery, correlogram, launch group, opt-in
     python tools/bench_extra.py --what hw25pitch --steps 3  # its initial grouping and pitch tracking beside the correlogram, opt-in
     python tools/bench_extra.py --what hw25ibm --steps 3  # its AM stage, final grouping and the whole estimator beside the other stages, opt-in
+    python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
 """
 import argparse
 import json
@@ -1240,6 +1241,63 @@ def main():
                           "voiced_frames": int((pitch.cpu().numpy() > 0).sum()), "am_labels": int(amcrn.sum().item()),
                           "mask_units": int(mask.sum().item())}), flush=True)
         del hout, hev, gout, acf_hc, scr_am, scr_ibm
+
+    if "hw25resynth" in what:
+        # The Hu-Wang resynthesis on the --utts corpus batch taken as float samples, in one process: sea_hw25_resynth_batch alone
+        # (float output, on the gOut and the mask of the same run), sea_hw25_enhance_batch (audio in, enhanced audio out), and
+        # beside them sea_hw25_ibm_batch and the periphery with gOut, whose kernel runs the same recurrence.  Device events around
+        # every step, one warm-up discarded, median.
+        lib = sea.load()
+        n = batch.n_utt
+        x = batch.data.to(torch.float32)
+        rows = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames, total = int(rows.sum()), int(batch.total)
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev, gout = z(total * 25), z(total * 25), z(total * 25)
+        mask, pitch, status = z((frames, 25)), z(frames, torch.int32), z(n, torch.int32)
+        mask2, pitch2, status2 = z((frames, 25)), z(frames, torch.int32), z(n, torch.int32)
+        audio, audio2, shorts = z(total), z(total), z(total, torch.int16)
+        scr_ibm = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, frames, n)), dtype=torch.uint8, device=dev)
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def periphery():
+            assert lib.sea_hw25_periphery_gout_batch(P(x), P(hout), P(hev), P(gout), P(batch.offsets), P(batch.lengths), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def ibm():
+            assert lib.sea_hw25_ibm_batch(P(x), P(batch.offsets), P(batch.lengths), P(d_offs), P(mask), P(pitch), P(status), None, P(scr_ibm),
+                                          total, frames, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def resynth(i16=None):
+            assert lib.sea_hw25_resynth_batch(P(gout), P(mask), P(batch.offsets), P(batch.lengths), P(d_offs), 0.0, P(audio), P(i16),
+                                              P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def enhance():
+            assert lib.sea_hw25_enhance_batch(P(x), P(batch.offsets), P(batch.lengths), P(d_offs), P(audio2), None, P(mask2), P(pitch2),
+                                              P(status2), P(scr_ibm), total, frames, P(batch.order), n, st) == 0, lib.sea_last_error()
+        samples = int(np.sum(batch.host_lengths))
+        workload = f"the {args.utts}-utterance corpus as 8 kHz float samples: {samples} samples, {frames} frames of 80; median of {args.steps} steps after one warm-up"
+        results = {}
+        for key, name, fn, kernels in (
+                ("periphery", "periphery with gOut", periphery, "sea::hw25_periphery_kernel + sea::hw25_lowpass_kernel"),
+                ("ibm", "the whole estimator, sea_hw25_ibm_batch", ibm, "every kernel of the estimator"),
+                ("resynth", "resynthesis alone, float output", resynth, "sea::hw25_resynth_kernel"),
+                ("resynth_i16", "resynthesis alone, float and int16 outputs", lambda: resynth(shorts), "sea::hw25_resynth_kernel"),
+                ("enhance", "audio in, enhanced audio out, sea_hw25_enhance_batch", enhance, "every kernel of the estimator + sea::hw25_resynth_kernel")):
+            med, t = median_ms(fn, args.steps)
+            results[key] = med
+            print(json.dumps({"metric": f"Hu-Wang 25-channel resynthesis: {name} (samples/sec); a first form, not tuned",
+                              "value": samples / (med / 1e3), "unit": "samples/s", "ms_per_step": med, "x_realtime_8k": samples / 8000.0 / (med / 1e3),
+                              "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}), flush=True)
+        assert torch.equal(mask, mask2) and torch.equal(audio.view(torch.int32), audio2.view(torch.int32)), "the launch group and the single stages differ"
+        print(json.dumps({"metric": "Hu-Wang 25-channel resynthesis relative to the periphery and to the estimator of the same run",
+                          "value": results["resynth"] / results["periphery"], "unit": "ratio (resynthesis / periphery with gOut)",
+                          "resynth_over_ibm": results["resynth"] / results["ibm"], "enhance_over_ibm": results["enhance"] / results["ibm"],
+                          "config": {"workload": workload}, "mask_units": int(mask.sum().item()),
+                          "nonzero_output_samples": int((audio != 0).sum().item())}), flush=True)
+        del hout, hev, gout, scr_ibm
 
     if "rfft" in what:
         n = 1 << 18
