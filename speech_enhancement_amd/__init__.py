@@ -6,6 +6,7 @@ reference's own C entry points (include/sea_mi355x.h).
 Only what that path needs lives here:
   csrc/       HIP kernels, host table builder, the C ABI (libsea_mi355x.so, built in-tree)
   engine.py   host-side mirror of the reference interface + batched HBM-resident forms
+  hw25.py     the same for the Hu-Wang mask estimator and its resynthesis on the 25-channel bank
   corpus.py   the deterministic synthetic corpus the measurements run on
   shard.py    utterance sharding over the GPUs of a node (LPT / blocks) and the two-scalar job reduction
   host/       plain-C drivers with the reference's command lines (cfg -> list -> WAV in / WAV out) and the
@@ -21,8 +22,8 @@ from .engine import (DoCompCeps, MaskBatch, NoiseSup, PackedBatch, afe_features_
                      wb_denoise, wb_denoise_batch, wb_denoise_batch_slice, wb_denoise_utterances, wb_features_utterances,
                      wb_rows, wb_slice_state, wb_split, wb_tables, cc_slice_state, wb_cc_slice_state, compceps_batch_slice,
                      wb_compceps_batch_slice, denoise_ceps_utterances, wb_denoise_ceps_utterances, addnoise, addnoise_batch,
-                     make_trainset, snr_lin, trainset_batch, Hw25Result, hw25_correlogram_batch, hw25_frontend,
-                     hw25_frontend_batch, hw25_periphery_batch, hw25_split, hw25_tables, Hw25PitchResult, hw25_pitch,
-                     hw25_pitch_batch, Hw25AmResult, Hw25MaskResult, hw25_am_batch, hw25_am_tables, hw25_finalseg_batch,
-                     hw25_ibm, hw25_ibm_batch, hw25_periphery_gout_batch, Hw25EnhanceResult, hw25_enhance, hw25_enhance_batch,
-                     hw25_resynth, hw25_resynth_batch, hw25_resynth_tables)
+                     make_trainset, snr_lin, trainset_batch)
+from .hw25 import (Hw25Result, hw25_correlogram_batch, hw25_frontend, hw25_frontend_batch, hw25_periphery_batch,  # noqa: F401
+                   hw25_split, hw25_tables, Hw25PitchResult, hw25_pitch, hw25_pitch_batch, Hw25AmResult, Hw25MaskResult,
+                   hw25_am_batch, hw25_am_tables, hw25_finalseg_batch, hw25_ibm, hw25_ibm_batch, hw25_periphery_gout_batch,
+                   Hw25EnhanceResult, hw25_enhance, hw25_enhance_batch, hw25_resynth, hw25_resynth_batch, hw25_resynth_tables)

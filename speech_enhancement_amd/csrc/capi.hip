@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "capi_internal.h"
+#include "hw25_capi.h"
 
 namespace sea_capi {
 
@@ -1303,41 +1304,27 @@ int sea_hw25_frontend(const float *in, long L, float *hout, float *hev, float *a
                       float *cross_ev, int *pitch, float *pratio, float *mark)
 {
     if (L <= 0) return fail("hw25_frontend: L=%ld", L);
-    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
-    DevBuf<float> din, dho, dhe, dah, dae, dfr;
+    Hw25Single u;
+    if (u.load(in, L)) return 1;
+    const size_t Lp = (size_t)u.Lp, fr = (size_t)u.rows * SEA_HW25_NCHAN, acf = (size_t)SEA_HW25_NCHAN * SEA_HW25_DELAYS;
+    DevBuf<float> dho, dhe, dah, dae, dfr;
     DevBuf<int> dp;
-    DevBuf<long long> dmeta;
-    HIP_TRY(din.alloc((size_t)Lp));
-    HIP_TRY(dho.alloc((size_t)Lp * SEA_HW25_NCHAN));
-    HIP_TRY(dhe.alloc((size_t)Lp * SEA_HW25_NCHAN));
-    if (acf_hc) HIP_TRY(dah.alloc((size_t)rows * SEA_HW25_NCHAN * SEA_HW25_DELAYS));
-    if (acf_ev) HIP_TRY(dae.alloc((size_t)rows * SEA_HW25_NCHAN * SEA_HW25_DELAYS));
-    HIP_TRY(dfr.alloc((size_t)rows * SEA_HW25_NCHAN * 4)); /* cross_hc | cross_ev | pratio | mark */
-    HIP_TRY(dp.alloc((size_t)rows));
-    HIP_TRY(dmeta.alloc(3));
-    const long long meta[3] = {0, L, 0};
-    const size_t fr = (size_t)rows * SEA_HW25_NCHAN;
-    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
-    HIP_TRY(hipMemcpy(din.p, in, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
-    if (sea_hw25_frontend_batch(din.p, dho.p, dhe.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dah.p, dae.p, dfr.p, dfr.p + fr, dp.p,
-                                dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
+    HIP_TRY(dho.alloc(Lp * SEA_HW25_NCHAN));
+    HIP_TRY(dhe.alloc(Lp * SEA_HW25_NCHAN));
+    if (acf_hc) HIP_TRY(dah.alloc(fr * SEA_HW25_DELAYS));
+    if (acf_ev) HIP_TRY(dae.alloc(fr * SEA_HW25_DELAYS));
+    HIP_TRY(dfr.alloc(fr * 4)); /* cross_hc | cross_ev | pratio | mark */
+    HIP_TRY(dp.alloc((size_t)u.rows));
+    if (sea_hw25_frontend_batch(u.d_in, dho.p, dhe.p, u.d_offsets, u.d_lengths, u.d_row_offsets, dah.p, dae.p, dfr.p, dfr.p + fr,
+                                dp.p, dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
         return 1;
     HIP_TRY(hipDeviceSynchronize());
     const size_t rowb = (size_t)L * sizeof(float);
-    if (hout) HIP_TRY(hipMemcpy2D(hout, rowb, dho.p, (size_t)Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
-    if (hev) HIP_TRY(hipMemcpy2D(hev, rowb, dhe.p, (size_t)Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
-    if (F > 0) {
-        const size_t nf = (size_t)F * SEA_HW25_NCHAN * sizeof(float);
-        if (acf_hc) HIP_TRY(hipMemcpy(acf_hc, dah.p, nf * SEA_HW25_DELAYS, hipMemcpyDeviceToHost));
-        if (acf_ev) HIP_TRY(hipMemcpy(acf_ev, dae.p, nf * SEA_HW25_DELAYS, hipMemcpyDeviceToHost));
-        if (cross_hc) HIP_TRY(hipMemcpy(cross_hc, dfr.p, nf, hipMemcpyDeviceToHost));
-        if (cross_ev) HIP_TRY(hipMemcpy(cross_ev, dfr.p + fr, nf, hipMemcpyDeviceToHost));
-        if (pratio) HIP_TRY(hipMemcpy(pratio, dfr.p + 2 * fr, nf, hipMemcpyDeviceToHost));
-        if (mark) HIP_TRY(hipMemcpy(mark, dfr.p + 3 * fr, nf, hipMemcpyDeviceToHost));
-        if (pitch) HIP_TRY(hipMemcpy(pitch, dp.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    return 0;
+    if (hout) HIP_TRY(hipMemcpy2D(hout, rowb, dho.p, Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
+    if (hev) HIP_TRY(hipMemcpy2D(hev, rowb, dhe.p, Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
+    return u.rows_back(acf_hc, dah.p, acf) || u.rows_back(acf_ev, dae.p, acf) || u.rows_back(cross_hc, dfr.p, SEA_HW25_NCHAN) ||
+           u.rows_back(cross_ev, dfr.p + fr, SEA_HW25_NCHAN) || u.rows_back(pratio, dfr.p + 2 * fr, SEA_HW25_NCHAN) ||
+           u.rows_back(mark, dfr.p + 3 * fr, SEA_HW25_NCHAN) || u.rows_back(pitch, dp.p, 1);
 }
 
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength)

@@ -46,10 +46,6 @@ inline long long align8(long long v) { return (v + 7) & ~7LL; }
 /* launch order of the utterance-per-workgroup kernels: longest first, every other row of n_cu reversed */
 void launch_order(const long long *lens, int n, int n_cu, int *order);
 
-/* where sea_hw25_ibm_batch keeps gOut ([25][pitch] per utterance, hout's layout) in its scratch, in bytes from its start, for
- * the same three arguments as sea_hw25_ibm_scratch_bytes (hw25_am_capi.hip); sea_hw25_enhance_batch resynthesises from it */
-long long hw25_ibm_gout_offset(long long total_padded_samples, long long total_rows, int n_utt);
-
 /* NoiseSup kernel form for a batch of n_inflight utterances sharing the device (capi.hip::sea_ns_denoise_batch):
  * 3 six-wave, 6 dense six-wave, 4 four-wave / tables in LDS, 2 four-wave; honours sea_ns_kernel_form / SEA_NS_KERNEL */
 int ns_pick_form(int n_inflight, int n_cu);

@@ -4,9 +4,7 @@
  * estimator, sea_hw25_ibm_scratch_bytes, sea_hw25_ibm_batch, sea_hw25_ibm.  The batch calls are launches on one stream and
  * nothing else: the lengths stay on the device.
  */
-#include <initializer_list>
-
-#include "capi_internal.h"
+#include "hw25_capi.h"
 
 using namespace sea_capi;
 
@@ -14,18 +12,6 @@ namespace {
 
 long long pos(long long v) { return v > 0 ? v : 0; }
 
-/* nonzero when one of the n outputs (null: not given) is one of the inputs or another output */
-int shared_buffer(const void *const *outs, int n, std::initializer_list<const void *> ins)
-{
-    for (int i = 0; i < n; ++i) {
-        if (!outs[i]) continue;
-        for (const void *in : ins)
-            if (outs[i] == in) return 1;
-        for (int j = 0; j < i; ++j)
-            if (outs[i] == outs[j]) return 1;
-    }
-    return 0;
-}
 long long up256(long long v) { return (v + 255) & ~255LL; }
 
 /* The FFT works on `chunk` channels at a time, two complex buffers of 2 x the padded length each: all 25 channels while that
@@ -268,28 +254,19 @@ int sea_hw25_ibm(const float *x, long L, float *mask, int *pitch, int *status)
         *status = 0;
         return 0;
     }
-    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
-    DevBuf<float> din, dmask;
+    Hw25Single u;
+    if (u.load(x, L)) return 1;
+    const long long rows = u.rows;
+    DevBuf<float> dmask;
     DevBuf<int> dint;
-    DevBuf<long long> dmeta;
     DevBuf<char> dscr;
-    HIP_TRY(din.alloc((size_t)Lp));
     HIP_TRY(dmask.alloc((size_t)rows * SEA_HW25_NCHAN));
     HIP_TRY(dint.alloc((size_t)rows + 1)); /* pitch | status */
-    HIP_TRY(dmeta.alloc(3));
-    HIP_TRY(dscr.alloc((size_t)sea_hw25_ibm_scratch_bytes(Lp, rows, 1)));
-    const long long meta[3] = {0, L, 0};
-    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
-    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
-    if (sea_hw25_ibm_batch(din.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dmask.p, dint.p, dint.p + rows, nullptr, dscr.p, Lp, rows, nullptr, 1,
-                           nullptr))
+    HIP_TRY(dscr.alloc((size_t)sea_hw25_ibm_scratch_bytes(u.Lp, rows, 1)));
+    if (sea_hw25_ibm_batch(u.d_in, u.d_offsets, u.d_lengths, u.d_row_offsets, dmask.p, dint.p, dint.p + rows, nullptr, dscr.p, u.Lp,
+                           rows, nullptr, 1, nullptr))
         return 1;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(status, dint.p + rows, sizeof(int), hipMemcpyDeviceToHost));
-    if (F > 0) {
-        if (mask) HIP_TRY(hipMemcpy(mask, dmask.p, (size_t)F * SEA_HW25_NCHAN * sizeof(float), hipMemcpyDeviceToHost));
-        if (pitch) HIP_TRY(hipMemcpy(pitch, dint.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return u.rows_back(mask, dmask.p, SEA_HW25_NCHAN) || u.rows_back(pitch, dint.p, 1);
 }

@@ -21,7 +21,7 @@
  * ratio is therefore compared with a tolerance, everything before it bit for bit.
  */
 #include "../../include/sea_mi355x.h"
-#include "hw25_segment.h"
+#include "hw25_device.h"
 #include "sea_device.h"
 #include "sea_kernels.h"
 
@@ -34,10 +34,6 @@ constexpr int kBlock = 5 * kHop; /* amPatt's blocks of five frames */
 constexpr int kMaxTaps = SEA_HW25_AM_MAXTAPS;
 constexpr int kLdsLog2 = SEA_HW25_AM_LDS_LOG2;
 constexpr double kPi = 3.1415926535897932384626433832795; /* HuWang.h:7 */
-constexpr unsigned kChanBits = (1u << kCh) - 1u;
-constexpr int kNone = kHw25None;
-
-__device__ __forceinline__ void lanes_fence() { __threadfence(); }
 
 /* computeAM:1156 for lengths 240 .. 150000: the integer ceil (log2 (L)), and at a power of two the constant that the
  * reference's double expression gave on a CPU (SEA_HW25_N_AT_POW2) */
@@ -352,8 +348,8 @@ __device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lan
     const int ncell = F * kCh;
     int *m = s.m;
     for (int i = lane; i < ncell; i += 64) {
-        s.lab[i] = m[i] ? i : kNone;
-        s.key[i] = kNone;
+        s.lab[i] = m[i] ? i : kHw25None;
+        s.key[i] = kHw25None;
         s.lo[i] = F;
         s.hi[i] = 0;
     }
@@ -372,14 +368,14 @@ __device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lan
     int count = 0;
     for (int base = 0; base < ncell; base += 64) {
         const int i = base + lane;
-        const bool seg = i < ncell && s.lab[i] == i && s.key[i] != kNone;
+        const bool seg = i < ncell && s.lab[i] == i && s.key[i] != kHw25None;
         count += __popcll(__ballot(seg));
     }
     for (int i = lane; i < ncell; i += 64) {
         int keep = 0;
         if (m[i]) {
             const int root = s.lab[i];
-            keep = (s.key[root] != kNone && s.hi[root] - s.lo[root] + 1 >= 5) ? 1 : 0;
+            keep = (s.key[root] != kHw25None && s.hi[root] - s.lo[root] + 1 >= 5) ? 1 : 0;
         }
         m[i] = keep;
     }
@@ -401,7 +397,7 @@ __device__ __forceinline__ void develope(const FinalScr &s, int F, int v, int la
                 const int f = dir ? F - 1 - k : k;
                 const bool isv = lane < kCh && s.g[f * kCh + lane] == v;
                 const bool mm = lane < kCh && s.m[f * kCh + lane] != 0;
-                const unsigned V0 = (unsigned)__ballot(isv) & kChanBits, M = (unsigned)__ballot(mm) & kChanBits;
+                const unsigned V0 = (unsigned)__ballot(isv) & kHw25ChanBits, M = (unsigned)__ballot(mm) & kHw25ChanBits;
                 unsigned V = V0 | (carry & M), prev;
                 do {
                     prev = V;

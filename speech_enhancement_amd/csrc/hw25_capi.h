@@ -1,0 +1,69 @@
+/*
+ * hw25_capi.h -- what the translation units behind the Hu-Wang C ABI share (capi.hip, hw25_pitch_capi.hip, hw25_am_capi.hip,
+ * hw25_resynth_capi.hip): the single-utterance forms' batch of one, the refusal of outputs that are inputs, and where the
+ * whole estimator keeps gOut.
+ */
+#pragma once
+#include <initializer_list>
+
+#include "capi_internal.h"
+
+namespace sea_capi {
+
+/* nonzero when one of the n outputs (null: not given) is one of the inputs or another output */
+inline int shared_buffer(const void *const *outs, int n, std::initializer_list<const void *> ins)
+{
+    for (int i = 0; i < n; ++i) {
+        if (!outs[i]) continue;
+        for (const void *in : ins)
+            if (outs[i] == in) return 1;
+        for (int j = 0; j < i; ++j)
+            if (outs[i] == outs[j]) return 1;
+    }
+    return 0;
+}
+
+/* where sea_hw25_ibm_batch keeps gOut ([25][pitch] per utterance, hout's layout) in its scratch, in bytes from its start, for
+ * the same three arguments as sea_hw25_ibm_scratch_bytes (hw25_am_capi.hip); sea_hw25_enhance_batch resynthesises from it */
+long long hw25_ibm_gout_offset(long long total_padded_samples, long long total_rows, int n_utt);
+
+/* One utterance from host memory as a batch of one: the samples zero-padded to Lp = L rounded up to 8 on the device, and
+ * the three words a batch call takes as offsets, lengths and row_offsets (0, L, 0).  F = L / 80 frames; rows = F, but at
+ * least 1, is what the frame outputs are allocated for. */
+struct Hw25Single {
+    long long Lp = 0, F = 0, rows = 1;
+    const float *d_in = nullptr;
+    const long long *d_offsets = nullptr, *d_lengths = nullptr, *d_row_offsets = nullptr;
+
+    int load(const float *x, long L) /* L > 0; 0 or fail() */
+    {
+        Lp = align8(L);
+        F = sea_hw25_frames(L);
+        rows = F > 0 ? F : 1;
+        HIP_TRY(in_.alloc((size_t)Lp));
+        HIP_TRY(meta_.alloc(3));
+        const long long meta[3] = {0, L, 0};
+        HIP_TRY(hipMemset(in_.p, 0, (size_t)Lp * sizeof(float)));
+        HIP_TRY(hipMemcpy(in_.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(meta_.p, meta, sizeof meta, hipMemcpyHostToDevice));
+        d_in = in_.p;
+        d_offsets = meta_.p;
+        d_lengths = meta_.p + 1;
+        d_row_offsets = meta_.p + 2;
+        return 0;
+    }
+
+    /* the F rows of `width` elements at d_src to host memory, where the caller asked for them and there is a frame */
+    template <typename T>
+    int rows_back(T *dst, const T *d_src, size_t width) const
+    {
+        if (dst && F > 0) HIP_TRY(hipMemcpy(dst, d_src, (size_t)F * width * sizeof(T), hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+private:
+    DevBuf<float> in_;
+    DevBuf<long long> meta_;
+};
+
+} // namespace sea_capi

@@ -1,0 +1,89 @@
+/*
+ * hw25_device.h -- what the Hu-Wang kernel files share on the device: the gammatone recurrence of the analysis
+ * (hw25_kernel.hip) and of the resynthesis that inverts it (hw25_resynth_kernel.hip), and the constants, the lane fence and
+ * the label propagation of the estimator's two segmentations, initGroup's (hw25_pitch_kernel.hip) and finalSeg's
+ * reSegmentation (hw25_am_kernel.hip).
+ */
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "sea_tables.h"
+
+namespace sea {
+
+/* gammaToneFilter:231-251 for one sample: returns p[3] * gain taken BEFORE the update */
+struct Gt25 {
+    float p[4], q[4];
+};
+__device__ __forceinline__ float gt25_step(Gt25 &s, float in, float f1, float f2, float gain)
+{
+    const float out = s.p[3] * gain;
+    float x[4], y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        x[i] = f1 * s.p[i] - f2 * s.q[i];
+        y[i] = f2 * s.p[i] + f1 * s.q[i];
+    }
+    s.p[0] = in * f1 + x[0];
+    s.q[0] = in * f2 + y[0];
+    s.p[1] = s.p[0] + x[1];
+    s.q[1] = s.q[0] + y[1];
+    s.p[2] = s.p[1] + x[1] + x[2];
+    s.q[2] = s.q[1] + y[1] + y[2];
+    s.p[3] = s.p[2] + x[1] + 2 * x[2] + x[3];
+    s.q[3] = s.q[2] + y[1] + 2 * y[2] + y[3];
+    return out;
+}
+
+constexpr int kHw25None = 0x7fffffff;                              /* no label, no key */
+constexpr unsigned kHw25ChanBits = (1u << SEA_HW25_NCHAN) - 1u;    /* the channel lanes of a ballot */
+
+/* between a write by one lane and a later read by another lane of the same wave */
+__device__ __forceinline__ void lanes_fence() { __threadfence(); }
+
+/* One wave per utterance.  lab [F][25]: the unit's own index where it is marked, kHw25None elsewhere.  On return every marked
+ * unit holds the smallest unit index of its 4-connected component.  Lane = channel; a frame takes the label of the frame
+ * before it in sweep direction (carried in registers), then every run of marked channels takes its minimum.  Forward and
+ * backward sweeps until neither changes anything.  The caller fences before and after. */
+__device__ __forceinline__ void hw25_label_components(int *lab, int F, int lane)
+{
+    constexpr int kCh = SEA_HW25_NCHAN;
+    bool again = true;
+    while (again) {
+        bool changed = false;
+        for (int dir = 0; dir < 2; ++dir) {
+            int carry = kHw25None;
+            for (int k = 0; k < F; ++k) {
+                const int f = dir ? F - 1 - k : k;
+                const int old = lane < kCh ? lab[f * kCh + lane] : kHw25None;
+                int v = old;
+                if (v != kHw25None && carry < v) v = carry;
+                const unsigned m = (unsigned)__ballot(v != kHw25None) & kHw25ChanBits;
+                /* the run [start, end] of marked channels around this lane */
+                const unsigned below = ~m & ((1u << (lane & 31)) - 1u);
+                const int start = below ? 32 - __clz((int)below) : 0;
+                const unsigned above = lane < 31 ? (~m >> (lane + 1)) : 1u;
+                const int end = lane + (__ffs((int)above) - 1);
+#pragma unroll
+                for (int d = 1; d < 32; d <<= 1) {
+                    const int o = __shfl_up(v, d);
+                    if (lane - d >= start && o < v) v = o;
+                }
+                const int r = __shfl(v, end & 63);
+                if (old != kHw25None) {
+                    v = r;
+                    if (v != old) {
+                        lab[f * kCh + lane] = v;
+                        changed = true;
+                    }
+                } else {
+                    v = kHw25None;
+                }
+                carry = v;
+            }
+        }
+        again = __any(changed);
+    }
+}
+
+} // namespace sea

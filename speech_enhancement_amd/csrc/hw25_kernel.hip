@@ -12,6 +12,7 @@
  * the square root are the compiler's correctly rounded ones.  Layout: utterance u's 25 streams form a [25][pitch] float block
  * at offsets[u] * 25, pitch = lengths[u] rounded up to 8; the frame outputs are rows, utterance u's first at row_offsets[u].
  */
+#include "hw25_device.h"
 #include "sea_device.h"
 #include "sea_kernels.h"
 
@@ -22,30 +23,6 @@ namespace {
 constexpr int kCh = SEA_HW25_NCHAN, kDel = SEA_HW25_DELAYS, kHop = SEA_HW25_HOP, kTaps = SEA_HW25_TAPS;
 constexpr int kPerTile = 8;                          /* samples per step of the periphery loop */
 constexpr int kWinStage = SEA_HW25_MAXWIN + kDel - 1; /* samples one (channel, frame) reads: the window and 100 before it */
-
-/* gammaToneFilter:231-251 for one sample: returns p[3] * gain taken BEFORE the update */
-struct Gt25 {
-    float p[4], q[4];
-};
-__device__ __forceinline__ float gt25_step(Gt25 &s, float in, float f1, float f2, float gain)
-{
-    const float out = s.p[3] * gain;
-    float x[4], y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        x[i] = f1 * s.p[i] - f2 * s.q[i];
-        y[i] = f2 * s.p[i] + f1 * s.q[i];
-    }
-    s.p[0] = in * f1 + x[0];
-    s.q[0] = in * f2 + y[0];
-    s.p[1] = s.p[0] + x[1];
-    s.q[1] = s.q[0] + y[1];
-    s.p[2] = s.p[1] + x[1] + x[2];
-    s.q[2] = s.q[1] + y[1] + y[2];
-    s.p[3] = s.p[2] + x[1] + 2 * x[2] + x[3];
-    s.q[3] = s.q[2] + y[1] + 2 * y[2] + y[3];
-    return out;
-}
 
 /* hairCell:279-297 for one sample.  kt is a double expression of the input (float + double literal), rounded once; the rest
  * is float arithmetic; comparisons against the double literals 0.0 and 1.0 are exact in float. */

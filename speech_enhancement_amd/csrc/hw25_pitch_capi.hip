@@ -3,9 +3,7 @@
  * sea_hw25_pitch_scratch_bytes, sea_hw25_pitch_batch, sea_hw25_pitch.  The batch call is eight launches on one stream and
  * nothing else: the lengths stay on the device.
  */
-#include <initializer_list>
-
-#include "capi_internal.h"
+#include "hw25_capi.h"
 
 using namespace sea_capi;
 
@@ -63,9 +61,9 @@ int sea_hw25_pitch_batch(const float *d_acf_hc, const float *d_cross_hc, const f
         !d_pratio || !d_status || !d_scratch)
         return fail("hw25_pitch: null pointer (only d_stages and d_order may be null)");
     /* the kernels read the inputs after they have begun to write the outputs: no output may be an input */
-    for (const float *out : {(const float *)d_grp, (const float *)d_pratio})
-        for (const float *in : {d_acf_hc, d_cross_hc, d_pratio_in, d_mark_in})
-            if (out == in) return fail("hw25_pitch: an output (d_grp, d_pratio) must not be one of the inputs");
+    for (const void *out : {(const void *)d_grp, (const void *)d_pratio})
+        if (shared_buffer(&out, 1, {d_acf_hc, d_cross_hc, d_pratio_in, d_mark_in}))
+            return fail("hw25_pitch: an output (d_grp, d_pratio) must not be one of the inputs");
     if (d_grp == d_pratio) return fail("hw25_pitch: d_grp and d_pratio must be different buffers");
     sea::Hw25PitchArgs a{};
     a.acf = d_acf_hc;
@@ -90,38 +88,28 @@ int sea_hw25_pitch(const float *x, long L, int *pitch, float *grp, float *pratio
 {
     if (L <= 0) return fail("hw25_pitch: L=%ld", L);
     if (!x || !status) return fail("hw25_pitch: null pointer");
-    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
+    Hw25Single u;
+    if (u.load(x, L)) return 1;
+    const long long rows = u.rows;
     const size_t fr = (size_t)rows * SEA_HW25_NCHAN;
-    DevBuf<float> din, dho, dhe, dah, dfr;
+    DevBuf<float> dho, dhe, dah, dfr;
     DevBuf<int> dp, dint;
-    DevBuf<long long> dmeta;
     DevBuf<char> dscr;
-    HIP_TRY(din.alloc((size_t)Lp));
-    HIP_TRY(dho.alloc((size_t)Lp * SEA_HW25_NCHAN));
-    HIP_TRY(dhe.alloc((size_t)Lp * SEA_HW25_NCHAN));
+    HIP_TRY(dho.alloc((size_t)u.Lp * SEA_HW25_NCHAN));
+    HIP_TRY(dhe.alloc((size_t)u.Lp * SEA_HW25_NCHAN));
     HIP_TRY(dah.alloc(fr * SEA_HW25_DELAYS));
     HIP_TRY(dfr.alloc(fr * 6)); /* cross_hc | cross_ev | pratio_in | mark | grp | pratio */
     HIP_TRY(dp.alloc((size_t)rows));
     HIP_TRY(dint.alloc((size_t)rows + 1)); /* pitch | status */
-    HIP_TRY(dmeta.alloc(3));
     HIP_TRY(dscr.alloc((size_t)sea_hw25_pitch_scratch_bytes(rows, 1)));
-    const long long meta[3] = {0, L, 0};
-    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
-    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
-    if (sea_hw25_frontend_batch(din.p, dho.p, dhe.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dah.p, nullptr, dfr.p, dfr.p + fr, dp.p,
-                                dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
+    if (sea_hw25_frontend_batch(u.d_in, dho.p, dhe.p, u.d_offsets, u.d_lengths, u.d_row_offsets, dah.p, nullptr, dfr.p, dfr.p + fr,
+                                dp.p, dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
         return 1;
-    if (sea_hw25_pitch_batch(dah.p, dfr.p, dfr.p + 2 * fr, dfr.p + 3 * fr, dmeta.p + 1, dmeta.p + 2, dint.p, dfr.p + 4 * fr,
+    if (sea_hw25_pitch_batch(dah.p, dfr.p, dfr.p + 2 * fr, dfr.p + 3 * fr, u.d_lengths, u.d_row_offsets, dint.p, dfr.p + 4 * fr,
                              dfr.p + 5 * fr, dint.p + rows, nullptr, dscr.p, nullptr, 1, nullptr))
         return 1;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(status, dint.p + rows, sizeof(int), hipMemcpyDeviceToHost));
-    if (F > 0) {
-        const size_t nf = (size_t)F * SEA_HW25_NCHAN * sizeof(float);
-        if (pitch) HIP_TRY(hipMemcpy(pitch, dint.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-        if (grp) HIP_TRY(hipMemcpy(grp, dfr.p + 4 * fr, nf, hipMemcpyDeviceToHost));
-        if (pratio) HIP_TRY(hipMemcpy(pratio, dfr.p + 5 * fr, nf, hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return u.rows_back(pitch, dint.p, 1) || u.rows_back(grp, dfr.p + 4 * fr, SEA_HW25_NCHAN) ||
+           u.rows_back(pratio, dfr.p + 5 * fr, SEA_HW25_NCHAN);
 }

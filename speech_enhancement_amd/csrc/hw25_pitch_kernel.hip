@@ -27,7 +27,7 @@
  * the carried values stay in registers.
  */
 #include "../../include/sea_mi355x.h"
-#include "hw25_segment.h"
+#include "hw25_device.h"
 #include "sea_device.h"
 #include "sea_kernels.h"
 
@@ -38,11 +38,7 @@ namespace {
 constexpr int kCh = SEA_HW25_NCHAN, kDel = SEA_HW25_DELAYS, kHop = SEA_HW25_HOP, kMinDel = SEA_HW25_MINDELAY;
 constexpr int kRow = kCh * kDel;
 constexpr int kMaxSeg = SEA_HW25_MAX_SEGMENTS;
-constexpr int kNone = kHw25None;
-constexpr unsigned kChanBits = (1u << kCh) - 1u;
 constexpr double kThetaP = 0.95;
-
-__device__ __forceinline__ void lanes_fence() { __threadfence(); }
 
 __device__ __forceinline__ int popc64(unsigned long long m) { return __popcll(m); }
 
@@ -99,7 +95,7 @@ __device__ __forceinline__ unsigned ratio_mask(const float *acf, const float *mr
         const float q = acf[lane * kDel + delay] / mvalue_of(mraw[lane]);
         ok = grp[lane] > 0.0f && (double)q > kThetaP;
     }
-    return (unsigned)__ballot(ok) & kChanBits;
+    return (unsigned)__ballot(ok) & kHw25ChanBits;
 }
 
 /* count[0] / count[1] of segment `id` in one frame: its units with pRatio above / not above the threshold */
@@ -217,11 +213,11 @@ __global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
 
     if (F >= 3) {
         for (int i = lane; i < ncell; i += 64) {
-            lab[i] = mark[i] != 0.0f ? i : kNone;
-            key[i] = kNone;
+            lab[i] = mark[i] != 0.0f ? i : kHw25None;
+            key[i] = kHw25None;
         }
         lanes_fence();
-        /* ---- components: every marked unit ends with the smallest unit index of its component (hw25_segment.h) ---- */
+        /* ---- components: every marked unit ends with the smallest unit index of its component (hw25_device.h) ---- */
         hw25_label_components(lab, F, lane);
         lanes_fence();
         /* ---- per component its first seed in scan order ---- */
@@ -351,7 +347,7 @@ __global__ __launch_bounds__(64) void hw25_pitch_frame_kernel(Hw25PitchArgs a)
         if (find) {
             /* findPitch:836-858; with Pitch = 0 the reference divides acf[chan][0], and zeroes a zero */
             const float *grp = a.grp + row * kCh;
-            const unsigned gm = (unsigned)__ballot(lane < kCh && grp[lane] > 0.0f) & kChanBits;
+            const unsigned gm = (unsigned)__ballot(lane < kCh && grp[lane] > 0.0f) & kHw25ChanBits;
             P = sum_auto(acf, gm, kMinDel, kDel, lane);
             const int n1 = __popc(gm), n2 = __popc(ratio_mask(acf, mraw, grp, P, lane));
             /* lFrame / rFrame (:838-839) come from sumAuto's result BEFORE the vote zeroes it: kept for the track kernel */
@@ -437,7 +433,7 @@ __device__ __forceinline__ bool develope(const Hw25PitchArgs &a, const Utt &t, i
         } else {
             unset = unset || !computed;
             const float g = lane < kCh ? grp0[frame * kCh + lane] : 0.0f;
-            const unsigned own = (unsigned)__ballot(left ? g > 0.0f : g != 0.0f) & kChanBits;
+            const unsigned own = (unsigned)__ballot(left ? g > 0.0f : g != 0.0f) & kHw25ChanBits;
             const unsigned mark2 = own & chan_mark;
             const int number = __popc(mark2);
             if (number) {

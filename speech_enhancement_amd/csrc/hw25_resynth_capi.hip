@@ -6,7 +6,7 @@
  */
 #include <cstdio>
 
-#include "capi_internal.h"
+#include "hw25_capi.h"
 
 using namespace sea_capi;
 
@@ -23,8 +23,8 @@ int sea_hw25_resynth_batch(const float *d_gout, const float *d_mask, const long 
     if (n_utt <= 0) return 0;
     if (!d_gout || !d_mask || !d_offsets || !d_lengths || !d_row_offsets) return fail("hw25_resynth: null pointer (only d_order and one output may be null)");
     if (!d_out_f32 && !d_out_i16) return fail("hw25_resynth: no output (d_out_f32 and d_out_i16 are both null)");
-    const void *f32 = d_out_f32, *i16 = d_out_i16;
-    if (f32 == i16 || f32 == d_gout || f32 == d_mask || i16 == d_gout || i16 == d_mask)
+    const void *outs[] = {d_out_f32, d_out_i16};
+    if (shared_buffer(outs, 2, {d_gout, d_mask}))
         return fail("hw25_resynth: an output must not be an input or the other output");
     DeviceCtx *c;
     if (ctx(&c)) return 1;
@@ -52,10 +52,8 @@ int sea_hw25_enhance_batch(const float *d_in_f32, const long long *d_offsets, co
     if (n_utt <= 0) return 0;
     if (!d_out_f32 && !d_out_i16) return fail("hw25_enhance: no output (d_out_f32 and d_out_i16 are both null)");
     const void *outs[] = {d_out_f32, d_out_i16};
-    for (const void *o : outs)
-        if (o && (o == d_in_f32 || o == d_mask || o == d_pitch || o == d_status || o == d_scratch))
-            return fail("hw25_enhance: an output must not be the input or another output");
-    if (d_out_f32 && (const void *)d_out_f32 == (const void *)d_out_i16) return fail("hw25_enhance: an output must not be the input or another output");
+    if (shared_buffer(outs, 2, {d_in_f32, d_mask, d_pitch, d_status, d_scratch}))
+        return fail("hw25_enhance: an output must not be the input or another output");
     /* the mask of createIBM :99-106 is 0 / 1: the reference's `mark > 0` */
     if (sea_hw25_ibm_batch(d_in_f32, d_offsets, d_lengths, d_row_offsets, d_mask, d_pitch, d_status, nullptr, d_scratch,
                            total_padded_samples, total_rows, d_order, n_utt, stream))
@@ -72,26 +70,20 @@ int sea_hw25_resynth(const float *x, long L, const float *mask, long F, float th
     if (!x || !out_f32) return fail("hw25_resynth: null pointer");
     if (F != (long)sea_hw25_frames(L)) return fail("hw25_resynth: F=%ld, not L / 80 = %lld", F, sea_hw25_frames(L));
     if (F > 0 && !mask) return fail("hw25_resynth: null pointer");
-    const long long Lp = align8(L), rows = F > 0 ? F : 1;
-    DevBuf<float> din, dstreams, dmask, dout;
-    DevBuf<long long> dmeta;
-    HIP_TRY(din.alloc((size_t)Lp));
-    HIP_TRY(dstreams.alloc((size_t)Lp * SEA_HW25_NCHAN * 3)); /* hout | hev | gout */
-    HIP_TRY(dmask.alloc((size_t)rows * SEA_HW25_NCHAN));
-    HIP_TRY(dout.alloc((size_t)Lp));
-    HIP_TRY(dmeta.alloc(3));
-    const long long meta[3] = {0, L, 0};
-    const size_t plane = (size_t)Lp * SEA_HW25_NCHAN;
-    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
-    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(dmask.p, 0, (size_t)rows * SEA_HW25_NCHAN * sizeof(float)));
+    Hw25Single u;
+    if (u.load(x, L)) return 1;
+    const size_t plane = (size_t)u.Lp * SEA_HW25_NCHAN, units = (size_t)u.rows * SEA_HW25_NCHAN;
+    DevBuf<float> dstreams, dmask, dout;
+    HIP_TRY(dstreams.alloc(plane * 3)); /* hout | hev | gout */
+    HIP_TRY(dmask.alloc(units));
+    HIP_TRY(dout.alloc((size_t)u.Lp));
+    HIP_TRY(hipMemset(dmask.p, 0, units * sizeof(float)));
     if (F > 0) HIP_TRY(hipMemcpy(dmask.p, mask, (size_t)F * SEA_HW25_NCHAN * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
-    if (sea_hw25_periphery_gout_batch(din.p, dstreams.p, dstreams.p + plane, dstreams.p + 2 * plane, dmeta.p, dmeta.p + 1, nullptr, 1,
-                                      nullptr))
+    if (sea_hw25_periphery_gout_batch(u.d_in, dstreams.p, dstreams.p + plane, dstreams.p + 2 * plane, u.d_offsets, u.d_lengths, nullptr,
+                                      1, nullptr))
         return 1;
-    if (sea_hw25_resynth_batch(dstreams.p + 2 * plane, dmask.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, threshold, dout.p, nullptr, nullptr, 1,
-                               nullptr))
+    if (sea_hw25_resynth_batch(dstreams.p + 2 * plane, dmask.p, u.d_offsets, u.d_lengths, u.d_row_offsets, threshold, dout.p, nullptr,
+                               nullptr, 1, nullptr))
         return 1;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out_f32, dout.p, (size_t)L * sizeof(float), hipMemcpyDeviceToHost));
@@ -106,32 +98,23 @@ int sea_hw25_enhance(const float *x, long L, float *out_f32, float *mask, int *p
         *status = 0;
         return 0;
     }
-    const long long Lp = align8(L), F = sea_hw25_frames(L), rows = F > 0 ? F : 1;
-    DevBuf<float> din, dmask, dout;
+    Hw25Single u;
+    if (u.load(x, L)) return 1;
+    const long long rows = u.rows;
+    DevBuf<float> dmask, dout;
     DevBuf<int> dint;
-    DevBuf<long long> dmeta;
     DevBuf<char> dscr;
-    HIP_TRY(din.alloc((size_t)Lp));
-    HIP_TRY(dout.alloc((size_t)Lp));
+    HIP_TRY(dout.alloc((size_t)u.Lp));
     HIP_TRY(dmask.alloc((size_t)rows * SEA_HW25_NCHAN));
     HIP_TRY(dint.alloc((size_t)rows + 1)); /* pitch | status */
-    HIP_TRY(dmeta.alloc(3));
-    HIP_TRY(dscr.alloc((size_t)sea_hw25_ibm_scratch_bytes(Lp, rows, 1)));
-    const long long meta[3] = {0, L, 0};
-    HIP_TRY(hipMemset(din.p, 0, (size_t)Lp * sizeof(float)));
-    HIP_TRY(hipMemcpy(din.p, x, (size_t)L * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dmeta.p, meta, sizeof meta, hipMemcpyHostToDevice));
-    if (sea_hw25_enhance_batch(din.p, dmeta.p, dmeta.p + 1, dmeta.p + 2, dout.p, nullptr, dmask.p, dint.p, dint.p + rows, dscr.p, Lp, rows,
-                               nullptr, 1, nullptr))
+    HIP_TRY(dscr.alloc((size_t)sea_hw25_ibm_scratch_bytes(u.Lp, rows, 1)));
+    if (sea_hw25_enhance_batch(u.d_in, u.d_offsets, u.d_lengths, u.d_row_offsets, dout.p, nullptr, dmask.p, dint.p, dint.p + rows, dscr.p,
+                               u.Lp, rows, nullptr, 1, nullptr))
         return 1;
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(status, dint.p + rows, sizeof(int), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(out_f32, dout.p, (size_t)L * sizeof(float), hipMemcpyDeviceToHost));
-    if (F > 0) {
-        if (mask) HIP_TRY(hipMemcpy(mask, dmask.p, (size_t)F * SEA_HW25_NCHAN * sizeof(float), hipMemcpyDeviceToHost));
-        if (pitch) HIP_TRY(hipMemcpy(pitch, dint.p, (size_t)F * sizeof(int), hipMemcpyDeviceToHost));
-    }
-    return 0;
+    return u.rows_back(mask, dmask.p, SEA_HW25_NCHAN) || u.rows_back(pitch, dint.p, 1);
 }
 
 int sea_hw25_resynth_text_write(const char *path, const float *out, long L)

@@ -20,6 +20,7 @@
  * no counterpart here.  Every product and sum is rounded on its own (-ffp-contract=off); the divisions are the compiler's
  * correctly rounded ones.  No intermediate goes to global memory.
  */
+#include "hw25_device.h"
 #include "sea_device.h"
 #include "sea_kernels.h"
 
@@ -31,30 +32,6 @@ constexpr int kCh = SEA_HW25_NCHAN, kHop = SEA_HW25_HOP;
 constexpr int kTile = 64;            /* samples per tile: one per lane in the summing half */
 constexpr int kGroup = 8;            /* samples per fetch of the recurrence */
 constexpr int kStride = kTile + 1;   /* words per channel row of the LDS tile */
-
-/* gammaToneFilter:231-251 for one sample: returns p[3] * gain taken BEFORE the update */
-struct Gt25 {
-    float p[4], q[4];
-};
-__device__ __forceinline__ float gt25_step(Gt25 &s, float in, float f1, float f2, float gain)
-{
-    const float out = s.p[3] * gain;
-    float x[4], y[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        x[i] = f1 * s.p[i] - f2 * s.q[i];
-        y[i] = f2 * s.p[i] + f1 * s.q[i];
-    }
-    s.p[0] = in * f1 + x[0];
-    s.q[0] = in * f2 + y[0];
-    s.p[1] = s.p[0] + x[1];
-    s.q[1] = s.q[0] + y[1];
-    s.p[2] = s.p[1] + x[1] + x[2];
-    s.q[2] = s.q[1] + y[1] + y[2];
-    s.p[3] = s.p[2] + x[1] + 2 * x[2] + x[3];
-    s.q[3] = s.q[2] + y[1] + 2 * y[2] + y[3];
-    return out;
-}
 
 /* :1513-1519 for the eight samples tg .. tg + 7 of one channel, the latest first; kPartial: the group that holds the
  * utterance's last sample, whose samples at or past L are skipped */

@@ -176,6 +176,13 @@ def _dptr(t):
 MAX_FRAMES_PER_UTTERANCE = 2 ** 31 - 17
 
 
+def _row_offsets(rows, total=False):
+    """Row counts per utterance -> the int64 host array of where each one's rows begin when they lie one after the other (the
+    exclusive prefix sum; nothing in, nothing out).  total=True: one more entry, the sum."""
+    starts = np.concatenate((np.zeros(1, np.int64), np.cumsum(np.asarray(rows, dtype=np.int64))))
+    return starts if total else starts[:-1]
+
+
 def launch_order(lengths, n_cu=256):
     """Launch order of the utterance-per-workgroup kernels: longest first (the dispatcher serves the
     oldest waves first, so the critical path -- the longest utterance -- starts at once and keeps
@@ -215,7 +222,13 @@ class PackedBatch:
     @property
     def n_frames(self):
         """NoiseSup frames (80 samples) in the batch."""
-        return int(sum(int(l) // 80 for l in self.host_lengths))
+        return int(self.frame_rows()[0].sum())
+
+    def frame_rows(self, hop=80):
+        """(rows, offsets), host int64 arrays: every utterance's whole frames of ``hop`` samples, and its first row where
+        the rows of the batch lie one after the other."""
+        rows = np.asarray(self.host_lengths, dtype=np.int64) // hop
+        return rows, _row_offsets(rows)
 
     @staticmethod
     def layout(lengths):
@@ -224,7 +237,7 @@ class PackedBatch:
             raise ValueError(f"an utterance of {int(lengths.max())} samples has {MAX_FRAMES_PER_UTTERANCE} frames or more: "
                              "the NoiseSup kernels count frames in 32 bits")
         padded = (lengths + 7) // 8 * 8
-        offsets = np.concatenate(([0], np.cumsum(padded)[:-1])).astype(np.int64) if len(lengths) else np.zeros(0, np.int64)
+        offsets = _row_offsets(padded)
         total = int(padded.sum())
         return offsets, total, launch_order(lengths)
 
@@ -424,7 +437,7 @@ def wb_compceps_batch(batch, res):
     torch = _torch()
     lib = _lib.load()
     cap = np.maximum(np.asarray(batch.host_lengths) // 160 - 6, 0).astype(np.int64)
-    cum = np.concatenate(([0], np.cumsum(cap))).astype(np.int64)
+    cum = _row_offsets(cap, total=True)
     total = int(cum[-1])
     dev = batch.data.device
     ceps = torch.zeros((max(total, 1), 14), dtype=torch.float32, device=dev)
@@ -466,9 +479,9 @@ def wb_afe_features_batch(batch, want_intermediates=False, use_order=True):
                                            _stream_ptr()), "sea_wb_denoise_batch_fd")
     nfr = np.asarray(batch.host_lengths) // 160
     ccap = np.maximum(nfr - 6, 0).astype(np.int64)
-    ccum = np.concatenate(([0], np.cumsum(ccap))).astype(np.int64)
+    ccum = _row_offsets(ccap, total=True)
     fcap = (nfr + 6).astype(np.int64)
-    fcum = np.concatenate(([0], np.cumsum(fcap))).astype(np.int64)
+    fcum = _row_offsets(fcap, total=True)
     tc, tf = int(ccum[-1]), int(fcum[-1])
     feat_cc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
     feat_pp = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev) if want_intermediates else None
@@ -528,7 +541,7 @@ def compceps_batch(batch, den_f32, first_out):
     torch = _torch()
     lib = _lib.load()
     cap = np.maximum(np.asarray(batch.host_lengths) // 80 - 6, 0).astype(np.int64)
-    cum = np.concatenate(([0], np.cumsum(cap))).astype(np.int64)
+    cum = _row_offsets(cap, total=True)
     total = int(cum[-1])
     dev = batch.data.device
     ceps = torch.zeros((max(total, 1), 14), dtype=torch.float32, device=dev)
@@ -563,9 +576,9 @@ def afe_features_batch(batch, want_intermediates=False):
                                            _dptr(onset), n, _stream_ptr()), "sea_ns_denoise_batch_fd")
     nfr = np.asarray(batch.host_lengths) // 80
     ccap = np.maximum(nfr - 6, 0).astype(np.int64)
-    ccum = np.concatenate(([0], np.cumsum(ccap))).astype(np.int64)
+    ccum = _row_offsets(ccap, total=True)
     fcap = (nfr + 6).astype(np.int64)
-    fcum = np.concatenate(([0], np.cumsum(fcap))).astype(np.int64)
+    fcum = _row_offsets(fcap, total=True)
     tc, tf = int(ccum[-1]), int(fcum[-1])
     feat_cc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
     feat_pp = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev) if want_intermediates else None
@@ -653,8 +666,8 @@ def _afe_slice(batch, den, afe_state, frame_base, resume, final, want_pp, wb):
         raise ValueError(f"afe_state must be a contiguous float32 tensor of {name}() floats per utterance")
     dev = batch.data.device
     nfr = np.asarray(batch.host_lengths, dtype=np.int64) // (160 if wb else 80)
-    ccum = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
-    fcum = np.concatenate(([0], np.cumsum(nfr + 6))).astype(np.int64)
+    ccum = _row_offsets(nfr, total=True)
+    fcum = _row_offsets(nfr + 6, total=True)
     tc, tf = int(ccum[-1]), int(fcum[-1])
     feat_cc = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev)
     feat_pp = torch.zeros((max(tc, 1), 14), dtype=torch.float32, device=dev) if want_pp else None
@@ -737,7 +750,7 @@ def _cc_slice(batch, den, cc_state, frame_base, resume, wb):
         raise ValueError(f"cc_state must be a contiguous float32 tensor of {name}() floats per utterance")
     dev = batch.data.device
     nfr = np.asarray(batch.host_lengths, dtype=np.int64) // (160 if wb else 80)
-    cum = np.concatenate(([0], np.cumsum(nfr))).astype(np.int64)
+    cum = _row_offsets(nfr, total=True)
     total = int(cum[-1])
     ceps = torch.zeros((max(total, 1), 14), dtype=torch.float32, device=dev)
     n_ceps = torch.zeros(n, dtype=torch.int32, device=dev)
@@ -856,7 +869,7 @@ class MaskBatch:
     def from_arrays(cls, masks, device="cuda"):
         torch = _torch()
         rows = np.array([m.shape[0] for m in masks], dtype=np.int64)
-        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        offs = _row_offsets(rows)
         host = np.concatenate([np.ascontiguousarray(m, dtype=np.float32) for m in masks], axis=0)
         return cls(torch.from_numpy(host).to(device), torch.from_numpy(offs).to(device), offs, rows)
 
@@ -907,7 +920,7 @@ def irm_target_batch(batch, pure_sub, noise_sub, window=1):
     if np.any(np.asarray(batch.host_lengths) < 320):
         raise ValueError("irm_target needs utterances of at least one 320-sample frame")
     rows = (np.asarray(batch.host_lengths) - 320) // 160 + 1
-    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    offs = _row_offsets(rows)
     dev = batch.data.device
     irm = torch.zeros((int(rows.sum()), 64), dtype=torch.float32, device=dev)
     d_offs = torch.from_numpy(offs).to(dev)
@@ -915,468 +928,6 @@ def irm_target_batch(batch, pure_sub, noise_sub, window=1):
                                         _dptr(d_offs), _dptr(irm), int(window), batch.n_utt, _stream_ptr()),
                "sea_irm_target_batch")
     return MaskBatch(irm, d_offs, offs, rows)
-
-
-# ------------------------------------------------------------------------------------------------
-# the Hu-Wang estimator's front half on the 25-channel 8 kHz bank (aurora_etsi_test/HuWang.cpp:41-76; csrc/hw25_kernel.hip)
-# ------------------------------------------------------------------------------------------------
-HW25_NCHAN, HW25_DELAYS, HW25_HOP = 25, 101, 80
-
-
-def hw25_tables():
-    """The bank's host tables: cf, bw, midEarCoeff, gain, f1, f2 [25], winsize int32 [25], lp [91] (lowPass's Kaiser taps) and
-    hair [10] = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0."""
-    lib = _lib.load()
-    t = {k: np.zeros(HW25_NCHAN, np.float32) for k in ("cf", "bw", "midEarCoeff", "gain", "f1", "f2")}
-    t.update(winsize=np.zeros(HW25_NCHAN, np.int32), lp=np.zeros(91, np.float32), hair=np.zeros(10, np.float32))
-    keys = ("cf", "bw", "midEarCoeff", "gain", "f1", "f2", "winsize", "lp", "hair")
-    _lib.check(lib.sea_hw25_tables_host(*[_np_ptr(t[k]) for k in keys]), "sea_hw25_tables_host")
-    return t
-
-
-def _hw25_input(batch):
-    """createIBM takes float samples on the int16 scale: an int16 batch converts exactly, a float32 one is used as it is"""
-    torch = _torch()
-    if batch.data.dtype == torch.float32:
-        return batch.data
-    if batch.data.dtype != torch.int16:
-        raise ValueError("hw25: the batch must hold int16 or float32 samples")
-    return batch.data.to(torch.float32)
-
-
-def hw25_periphery_batch(batch, use_order=True):
-    """AudiPeriph + lowPass for every utterance of the batch: (hOut, hEv), two float32 tensors of 25x the packed size;
-    utterance u's [25][pitch] block starts at offsets[u]*25, pitch = length rounded up to 8 (hw25_split cuts them)."""
-    torch = _torch()
-    lib = _lib.load()
-    x = _hw25_input(batch)
-    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=x.device)
-    hev = torch.zeros_like(hout)
-    rc = lib.sea_hw25_periphery_batch(_dptr(x), _dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths),
-                                      _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_periphery_batch")
-    return hout, hev
-
-
-def hw25_split(batch, tensor):
-    """A hw25_periphery_batch() tensor -> per-utterance numpy arrays [25][L]."""
-    host = tensor.detach().cpu().numpy()
-    out = []
-    for off, L in zip(batch.host_offsets, batch.host_lengths):
-        pitch = (int(L) + 7) // 8 * 8
-        out.append(host[off * HW25_NCHAN:off * HW25_NCHAN + HW25_NCHAN * pitch].reshape(HW25_NCHAN, pitch)[:, :int(L)].copy())
-    return out
-
-
-class Hw25Result:
-    """What hw25_frontend_batch() computed, device tensors: hout, hev (25x the packed size), cross_hc, cross_ev, pratio, mark
-    [rows][25], pitch int32 [rows], acf_hc, acf_ev [rows][25][101] or None; row_offsets / host_row_offsets / host_rows say
-    where utterance u's length // 80 rows are.  utterance(u) returns numpy views of one utterance under the reference's names."""
-
-    def __init__(self, batch, **kw):
-        self.batch = batch
-        self.__dict__.update(kw)
-
-    def utterance(self, u):
-        r0, n = int(self.host_row_offsets[u]), int(self.host_rows[u])
-        off, L = int(self.batch.host_offsets[u]), int(self.batch.host_lengths[u])
-        pitch = (L + 7) // 8 * 8
-
-        def rows(t):
-            return None if t is None else t[r0:r0 + n].cpu().numpy()
-
-        def block(t):
-            return t[off * HW25_NCHAN:off * HW25_NCHAN + HW25_NCHAN * pitch].cpu().numpy().reshape(HW25_NCHAN, pitch)[:, :L]
-
-        return dict(hOut=block(self.hout), hEv=block(self.hev), acf_hc=rows(self.acf_hc), acf_ev=rows(self.acf_ev),
-                    cross_hc=rows(self.cross_hc), cross_ev=rows(self.cross_ev), pitch=rows(self.pitch), pRatio=rows(self.pratio),
-                    mark=rows(self.mark))
-
-
-def _hw25_outputs(batch, dev, want_acf):
-    """the frame outputs of a batch (at least one row, so that no tensor is empty), the row offsets and the scratch"""
-    torch = _torch()
-    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
-    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
-    n = max(int(rows.sum()), 1)
-    fr = {k: torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev) for k in ("cross_hc", "cross_ev", "pratio", "mark")}
-    acf = [torch.zeros((n, HW25_NCHAN, HW25_DELAYS), dtype=torch.float32, device=dev) if want_acf else None for _ in range(2)]
-    nbytes = int(_lib.load().sea_hw25_scratch_bytes(int(batch.total), int(batch.n_utt)))
-    return dict(rows=rows, offs=offs, d_offs=torch.from_numpy(offs).to(dev), fr=fr, acf=acf,
-                pitch=torch.zeros(n, dtype=torch.int32, device=dev),
-                scratch=torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None)
-
-
-def hw25_correlogram_batch(batch, hout, hev, want_acf=False, use_order=True):
-    """computeACF, crossCorr, globalPitch, timeCrn and the initial labelling from hw25_periphery_batch()'s tensors."""
-    lib = _lib.load()
-    o = _hw25_outputs(batch, hout.device, want_acf)
-    fr, acf, pitch, d_offs, scratch = o["fr"], o["acf"], o["pitch"], o["d_offs"], o["scratch"]
-    rc = lib.sea_hw25_correlogram_batch(_dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs),
-                                        _dptr(acf[0]), _dptr(acf[1]), _dptr(fr["cross_hc"]), _dptr(fr["cross_ev"]), _dptr(pitch),
-                                        _dptr(fr["pratio"]), _dptr(fr["mark"]), _dptr(scratch),
-                                        _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_correlogram_batch")
-    return Hw25Result(batch, hout=hout, hev=hev, acf_hc=acf[0], acf_ev=acf[1], pitch=pitch, row_offsets=d_offs,
-                      host_row_offsets=o["offs"], host_rows=o["rows"], **fr)
-
-
-def hw25_frontend_batch(batch, want_acf=False, use_order=True):
-    """The front half of createIBM() for every utterance of the batch, one launch group on the current stream -> Hw25Result.
-    The ACFs are [rows][25][101] floats per stream (about 8 MB per 4 s utterance): computed always, written only on request."""
-    torch = _torch()
-    lib = _lib.load()
-    x = _hw25_input(batch)
-    dev = x.device
-    o = _hw25_outputs(batch, dev, want_acf)
-    fr, acf, pitch, d_offs, scratch = o["fr"], o["acf"], o["pitch"], o["d_offs"], o["scratch"]
-    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=dev)
-    hev = torch.zeros_like(hout)
-    rc = lib.sea_hw25_frontend_batch(_dptr(x), _dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs),
-                                     _dptr(acf[0]), _dptr(acf[1]), _dptr(fr["cross_hc"]), _dptr(fr["cross_ev"]), _dptr(pitch),
-                                     _dptr(fr["pratio"]), _dptr(fr["mark"]), _dptr(scratch),
-                                     _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_frontend_batch")
-    return Hw25Result(batch, hout=hout, hev=hev, acf_hc=acf[0], acf_ev=acf[1], pitch=pitch, row_offsets=d_offs,
-                      host_row_offsets=o["offs"], host_rows=o["rows"], **fr)
-
-
-def hw25_frontend(x, want_acf=True):
-    """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict under the reference's names:
-    hOut, hEv [25][L]; acf_hc, acf_ev [F][25][101] (None without want_acf); cross_hc, cross_ev, pRatio, mark [F][25]; pitch [F]."""
-    lib = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    L, F = x.size, x.size // HW25_HOP
-    r = dict(hOut=np.zeros((HW25_NCHAN, L), np.float32), hEv=np.zeros((HW25_NCHAN, L), np.float32),
-             acf_hc=np.zeros((F, HW25_NCHAN, HW25_DELAYS), np.float32) if want_acf else None,
-             acf_ev=np.zeros((F, HW25_NCHAN, HW25_DELAYS), np.float32) if want_acf else None,
-             cross_hc=np.zeros((F, HW25_NCHAN), np.float32), cross_ev=np.zeros((F, HW25_NCHAN), np.float32),
-             pitch=np.zeros(F, np.int32), pRatio=np.zeros((F, HW25_NCHAN), np.float32), mark=np.zeros((F, HW25_NCHAN), np.float32))
-    keys = ("hOut", "hEv", "acf_hc", "acf_ev", "cross_hc", "cross_ev", "pitch", "pRatio", "mark")
-    rc = lib.sea_hw25_frontend(_np_ptr(x), L, *[_np_ptr(r[k]) if r[k] is not None else None for k in keys])
-    _lib.check(rc, "sea_hw25_frontend")
-    return r
-
-
-# ------------------------------------------------------------------------------------------------
-# the Hu-Wang estimator's initial grouping and pitch tracking (HuWang.cpp:79-87: initGroup, pitchDtm; csrc/hw25_pitch_kernel.hip)
-# ------------------------------------------------------------------------------------------------
-HW25_STAGE_WORDS, HW25_TOO_MANY_SEGMENTS, HW25_CHANMARK_UNSET = 55, 1 << 16, 1 << 17
-HW25_PITCH_STAGES = ("pitch_find1", "pitch_find2", "pitch_check", "pitch_left", "pitch_right")
-HW25_GRP_STAGES = ("grp_init", "grp_thetap")
-
-
-class Hw25PitchResult:
-    """What hw25_pitch_batch() computed, device tensors: pitch int32 [rows] (0 = unvoiced, else the delay 16..100 in samples
-    at 8 kHz), grp [rows][25] in {-1, 0, +1} (+1: grouped with the dominant voiced source), pratio [rows][25], status int32
-    [n_utt] (bits 0..15 the segment count, HW25_TOO_MANY_SEGMENTS, HW25_CHANMARK_UNSET), stages (int32 words, or None) and
-    front, the Hw25Result they were computed from.  utterance(u) returns numpy arrays of one utterance, the stage arrays
-    under HW25_PITCH_STAGES / HW25_GRP_STAGES when they were asked for."""
-
-    def __init__(self, front, **kw):
-        self.front = front
-        self.__dict__.update(kw)
-
-    def utterance(self, u):
-        r0, n = int(self.front.host_row_offsets[u]), int(self.front.host_rows[u])
-        out = dict(pitch=self.pitch[r0:r0 + n].cpu().numpy(), grp=self.grp[r0:r0 + n].cpu().numpy(),
-                   pratio=self.pratio[r0:r0 + n].cpu().numpy(), status=int(self.status[u]))
-        if self.stages is not None:
-            block = self.stages[r0 * HW25_STAGE_WORDS:(r0 + n) * HW25_STAGE_WORDS].cpu().numpy()
-            for k, name in enumerate(HW25_PITCH_STAGES):
-                out[name] = block[k * n:(k + 1) * n].copy()
-            grp = block[5 * n:].view(np.float32).reshape(2, n, HW25_NCHAN)
-            for k, name in enumerate(HW25_GRP_STAGES):
-                out[name] = grp[k].copy()
-        return out
-
-
-def hw25_pitch_batch(batch, stages=False, use_order=True):
-    """createIBM():41-87 for every utterance of the batch: the front half with its ACF output, then initGroup and pitchDtm, one
-    launch group on the current stream -> Hw25PitchResult.  stages: also keep Pitch / Grp after every step of pitchDtm."""
-    torch = _torch()
-    lib = _lib.load()
-    front = hw25_frontend_batch(batch, want_acf=True, use_order=use_order)
-    dev = front.pitch.device
-    n = front.pitch.shape[0]
-    pitch = torch.zeros(n, dtype=torch.int32, device=dev)
-    grp = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
-    pratio = torch.zeros_like(grp)
-    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
-    st = torch.zeros(n * HW25_STAGE_WORDS, dtype=torch.int32, device=dev) if stages else None
-    nbytes = int(lib.sea_hw25_pitch_scratch_bytes(n, int(batch.n_utt)))
-    scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_pitch_batch(_dptr(front.acf_hc), _dptr(front.cross_hc), _dptr(front.pratio), _dptr(front.mark),
-                                  _dptr(batch.lengths), _dptr(front.row_offsets), _dptr(pitch), _dptr(grp), _dptr(pratio),
-                                  _dptr(status), _dptr(st), _dptr(scratch), _dptr(batch.order) if use_order else None,
-                                  batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_pitch_batch")
-    return Hw25PitchResult(front, pitch=pitch, grp=grp, pratio=pratio, status=status, stages=st)
-
-
-def hw25_pitch(x):
-    """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict: pitch int32 [F], grp and pratio
-    [F][25], status."""
-    lib = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    F = x.size // HW25_HOP
-    r = dict(pitch=np.zeros(F, np.int32), grp=np.zeros((F, HW25_NCHAN), np.float32), pratio=np.zeros((F, HW25_NCHAN), np.float32))
-    status = np.zeros(1, np.int32)
-    rc = lib.sea_hw25_pitch(_np_ptr(x), x.size, _np_ptr(r["pitch"]), _np_ptr(r["grp"]), _np_ptr(r["pratio"]), _np_ptr(status))
-    _lib.check(rc, "sea_hw25_pitch")
-    r["status"] = int(status[0])
-    return r
-
-
-# ------------------------------------------------------------------------------------------------
-# the Hu-Wang estimator's AM labels, final grouping and the whole of createIBM (HuWang.cpp:89-106: computeAM, finalSeg, the
-# binarisation; csrc/hw25_am_kernel.hip)
-# ------------------------------------------------------------------------------------------------
-HW25_FINAL_STAGES = ("final_reseg1", "final_reseg2", "final_reseg3", "final_dev_minus", "final_dev_plus")
-HW25_FINAL_TOO_MANY_SEGMENTS, HW25_AM_TOO_LONG, HW25_AM_BAD_PITCH = 1 << 18, 1 << 19, 1 << 20
-
-
-def hw25_am_tables():
-    """The AM stage's host constants: a, beta (kaiserPara (0.01, ..)), n_at_pow2 int32 [11] (computeAM's N at L = 2^7 .. 2^17)
-    and twiddles float32 [2^18 - 1][2] (fft's u values, period p's p entries from entry p - 1)."""
-    lib = _lib.load()
-    ab, n, tw = np.zeros(2, np.float32), np.zeros(11, np.int32), np.zeros(((1 << 18) - 1, 2), np.float32)
-    _lib.check(lib.sea_hw25_am_tables_host(_np_ptr(ab), _np_ptr(n), _np_ptr(tw), tw.shape[0]), "sea_hw25_am_tables_host")
-    return dict(a=ab[0], beta=ab[1], n_at_pow2=n, twiddles=tw)
-
-
-def hw25_periphery_gout_batch(batch, use_order=True):
-    """hw25_periphery_batch() with gOut, the gammatone output before the hair cell: (hOut, hEv, gOut), the same layout."""
-    torch = _torch()
-    lib = _lib.load()
-    x = _hw25_input(batch)
-    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=x.device)
-    hev, gout = torch.zeros_like(hout), torch.zeros_like(hout)
-    rc = lib.sea_hw25_periphery_gout_batch(_dptr(x), _dptr(hout), _dptr(hev), _dptr(gout), _dptr(batch.offsets), _dptr(batch.lengths),
-                                           _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_periphery_gout_batch")
-    return hout, hev, gout
-
-
-class Hw25AmResult:
-    """What hw25_am_batch() computed, device tensors: amcrn [rows][25] 0 / 1, status int32 [n_utt] (HW25_AM_TOO_LONG,
-    HW25_AM_BAD_PITCH) and, when asked for, ratio and seng [rows][25], ampatt and am (gOut's layout).  utterance(u): numpy."""
-
-    def __init__(self, batch, **kw):
-        self.batch = batch
-        self.__dict__.update(kw)
-
-    def utterance(self, u):
-        r0, n = int(self.host_row_offsets[u]), int(self.host_rows[u])
-        out = dict(amcrn=self.amcrn[r0:r0 + n].cpu().numpy(), status=int(self.status[u]))
-        for k in ("ratio", "seng"):
-            if getattr(self, k) is not None:
-                out[k] = getattr(self, k)[r0:r0 + n].cpu().numpy()
-        for k in ("ampatt", "am"):
-            if getattr(self, k) is not None:
-                out[k] = hw25_split(self.batch, getattr(self, k))[u]
-        return out
-
-
-def hw25_am_batch(batch, gout, pitch, row_offsets=None, want_details=False, use_order=True):
-    """computeAM for every utterance of the batch from hw25_periphery_gout_batch()'s gOut and hw25_pitch_batch()'s pitch (int32
-    [rows] on the device; row_offsets: the int64 device tensor that goes with it) -> Hw25AmResult.  want_details: also ratio,
-    seng, ampatt and am."""
-    torch = _torch()
-    lib = _lib.load()
-    dev = gout.device
-    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
-    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
-    d_offs = row_offsets if row_offsets is not None else torch.from_numpy(offs).to(dev)
-    n = max(int(rows.sum()), 1)
-    amcrn = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
-    ratio, seng = (torch.zeros_like(amcrn) for _ in range(2)) if want_details else (None, None)
-    ampatt, am = (torch.zeros_like(gout) for _ in range(2)) if want_details else (None, None)
-    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
-    total = max(int(batch.total), 8)
-    scratch = torch.empty(int(lib.sea_hw25_am_scratch_bytes(total, int(batch.n_utt))), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_am_batch(_dptr(gout), _dptr(pitch), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs), _dptr(amcrn),
-                               _dptr(ratio), _dptr(seng), _dptr(ampatt), _dptr(am), _dptr(status), _dptr(scratch), total,
-                               _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_am_batch")
-    return Hw25AmResult(batch, amcrn=amcrn, ratio=ratio, seng=seng, ampatt=ampatt, am=am, status=status, row_offsets=d_offs,
-                        host_row_offsets=offs, host_rows=rows)
-
-
-class Hw25MaskResult:
-    """What hw25_finalseg_batch() / hw25_ibm_batch() computed, device tensors: mask [rows][25] 0 / 1, status int32 [n_utt],
-    grp_final [rows][25] or None, pitch int32 [rows] or None, stages (floats, or None).  utterance(u): numpy arrays, the stage
-    arrays under HW25_FINAL_STAGES when they were asked for."""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-    def utterance(self, u):
-        r0, n = int(self.host_row_offsets[u]), int(self.host_rows[u])
-        out = dict(mask=self.mask[r0:r0 + n].cpu().numpy(), status=int(self.status[u]))
-        for k in ("grp_final", "pitch"):
-            if getattr(self, k, None) is not None:
-                out[k] = getattr(self, k)[r0:r0 + n].cpu().numpy()
-        if self.stages is not None:
-            w = len(HW25_FINAL_STAGES) * HW25_NCHAN
-            block = self.stages[r0 * w:(r0 + n) * w].cpu().numpy().reshape(len(HW25_FINAL_STAGES), n, HW25_NCHAN)
-            for k, name in enumerate(HW25_FINAL_STAGES):
-                out[name] = block[k].copy()
-        return out
-
-
-def hw25_finalseg_batch(grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages=False, use_order=None):
-    """finalSeg and the binarisation on device tensors [rows][25] (hw25_pitch_batch()'s grp and pratio, hw25_am_batch()'s amcrn,
-    the front half's cross_ev), lengths / row_offsets int64 [n_utt] on the device, host_rows the row counts -> Hw25MaskResult.
-    use_order: an int32 device tensor (launch order) or None."""
-    torch = _torch()
-    lib = _lib.load()
-    dev = grp.device
-    host_rows = np.asarray(host_rows, dtype=np.int64)
-    offs = (np.concatenate(([0], np.cumsum(host_rows)[:-1])) if len(host_rows) else np.zeros(0)).astype(np.int64)
-    n_utt, n = len(host_rows), max(int(host_rows.sum()), 1)
-    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
-    grp_final = torch.zeros_like(mask)
-    status = torch.zeros(max(n_utt, 1), dtype=torch.int32, device=dev)
-    st = torch.zeros(n * len(HW25_FINAL_STAGES) * HW25_NCHAN, dtype=torch.float32, device=dev) if stages else None
-    scratch = torch.empty(int(lib.sea_hw25_finalseg_scratch_bytes(n, n_utt)), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_finalseg_batch(_dptr(grp), _dptr(amcrn), _dptr(cross_ev), _dptr(pratio), _dptr(lengths), _dptr(row_offsets),
-                                     _dptr(mask), _dptr(grp_final), _dptr(status), _dptr(st), _dptr(scratch), _dptr(use_order), n_utt,
-                                     _stream_ptr())
-    _lib.check(rc, "sea_hw25_finalseg_batch")
-    return Hw25MaskResult(mask=mask, grp_final=grp_final, status=status, stages=st, pitch=None, host_row_offsets=offs, host_rows=host_rows)
-
-
-def hw25_ibm_batch(batch, stages=False, use_order=True):
-    """createIBM() for every utterance of the batch, one launch group on the current stream -> Hw25MaskResult with the binary
-    mask [rows][25], pitchDtm's pitch [rows] and the status (hw25_pitch_batch()'s with HW25_FINAL_TOO_MANY_SEGMENTS,
-    HW25_AM_TOO_LONG).  stages: also keep Grp after each of finalSeg's five steps."""
-    torch = _torch()
-    lib = _lib.load()
-    x = _hw25_input(batch)
-    dev = x.device
-    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
-    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
-    n, total = max(int(rows.sum()), 1), max(int(batch.total), 8)
-    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
-    pitch = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
-    st = torch.zeros(n * len(HW25_FINAL_STAGES) * HW25_NCHAN, dtype=torch.float32, device=dev) if stages else None
-    scratch = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, n, int(batch.n_utt))), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_ibm_batch(_dptr(x), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(torch.from_numpy(offs).to(dev)), _dptr(mask),
-                                _dptr(pitch), _dptr(status), _dptr(st), _dptr(scratch), total, n,
-                                _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_ibm_batch")
-    return Hw25MaskResult(mask=mask, grp_final=None, status=status, stages=st, pitch=pitch, host_row_offsets=offs, host_rows=rows)
-
-
-def hw25_ibm(x):
-    """createIBM (x) for one utterance from host memory (float32 or int16 samples on the int16 scale) -> dict: mask [F][25]
-    floats 0 / 1, pitch int32 [F], status."""
-    lib = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    F = x.size // HW25_HOP
-    r = dict(mask=np.zeros((F, HW25_NCHAN), np.float32), pitch=np.zeros(F, np.int32))
-    status = np.zeros(1, np.int32)
-    _lib.check(lib.sea_hw25_ibm(_np_ptr(x), x.size, _np_ptr(r["mask"]), _np_ptr(r["pitch"]), _np_ptr(status)), "sea_hw25_ibm")
-    r["status"] = int(status[0])
-    return r
-
-
-# ------------------------------------------------------------------------------------------------
-# the Hu-Wang estimator's resynthesis (HuWang.cpp:1498-1549; csrc/hw25_resynth_kernel.hip): the mask applied, audio out
-# ------------------------------------------------------------------------------------------------
-def hw25_resynth_tables():
-    """The overlap-add tables of resynthesis(): up float64 [80], down float64 [120] and w float32 [80][8], the weight at
-    position o of a hop for the eight states (bit 0 / 1 / 2: frame k - 1 / k / k + 1 exists and is set)."""
-    lib = _lib.load()
-    w, up, down = np.zeros((80, 8), np.float32), np.zeros(80, np.float64), np.zeros(120, np.float64)
-    _lib.check(lib.sea_hw25_resynth_tables_host(_np_ptr(w), _np_ptr(up), _np_ptr(down)), "sea_hw25_resynth_tables_host")
-    return dict(w=w, up=up, down=down)
-
-
-def _hw25_rows(batch):
-    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HW25_HOP
-    offs = (np.concatenate(([0], np.cumsum(rows)[:-1])) if len(rows) else np.zeros(0)).astype(np.int64)
-    return rows, offs
-
-
-def hw25_resynth_batch(batch, gout, mask, row_offsets=None, threshold=0.0, int16=False, use_order=True):
-    """resynthesis() for every utterance of the batch from hw25_periphery_gout_batch()'s gOut and a mask [rows][25] on the
-    device (a unit is set where mask > threshold; row_offsets: the int64 device tensor that goes with it, else length // 80 rows
-    per utterance one after the other) -> float32 audio packed like batch.data (batch.split cuts it); int16=True: (audio, the
-    int16 conversion of it)."""
-    torch = _torch()
-    lib = _lib.load()
-    dev = gout.device
-    d_offs = row_offsets if row_offsets is not None else torch.from_numpy(_hw25_rows(batch)[1]).to(dev)
-    mask = mask.to(torch.float32).contiguous()
-    out = torch.zeros(batch.total, dtype=torch.float32, device=dev)
-    out16 = torch.zeros(batch.total, dtype=torch.int16, device=dev) if int16 else None
-    rc = lib.sea_hw25_resynth_batch(_dptr(gout), _dptr(mask), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(d_offs),
-                                    float(threshold), _dptr(out), _dptr(out16), _dptr(batch.order) if use_order else None,
-                                    batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_resynth_batch")
-    return (out, out16) if int16 else out
-
-
-def hw25_resynth(x, mask, threshold=0.0):
-    """One utterance from host memory (float32 or int16 samples on the int16 scale) and its mask [len(x) // 80][25] -> the
-    resynthesised float32 audio [len(x)]."""
-    lib = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    mask = np.ascontiguousarray(mask, dtype=np.float32).reshape(-1, HW25_NCHAN)
-    out = np.zeros(x.size, np.float32)
-    rc = lib.sea_hw25_resynth(_np_ptr(x), x.size, _np_ptr(mask), mask.shape[0], float(threshold), _np_ptr(out))
-    _lib.check(rc, "sea_hw25_resynth")
-    return out
-
-
-class Hw25EnhanceResult(Hw25MaskResult):
-    """What hw25_enhance_batch() computed, device tensors: audio float32, packed like the batch's data (batch.split cuts it),
-    with mask [rows][25], pitch int32 [rows] and status int32 [n_utt] as hw25_ibm_batch() gives them.  utterance(u): numpy."""
-
-    def utterance(self, u):
-        out = super().utterance(u)
-        off, L = int(self.batch.host_offsets[u]), int(self.batch.host_lengths[u])
-        out["audio"] = self.audio[off:off + L].cpu().numpy()
-        return out
-
-
-def hw25_enhance_batch(batch, use_order=True):
-    """createIBM() followed by resynthesis() of its own mask for every utterance of the batch, one launch group on the
-    current stream -> Hw25EnhanceResult."""
-    torch = _torch()
-    lib = _lib.load()
-    x = _hw25_input(batch)
-    dev = x.device
-    rows, offs = _hw25_rows(batch)
-    n, total = max(int(rows.sum()), 1), max(int(batch.total), 8)
-    audio = torch.zeros(total, dtype=torch.float32, device=dev)
-    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
-    pitch = torch.zeros(n, dtype=torch.int32, device=dev)
-    status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
-    scratch = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(total, n, int(batch.n_utt))), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_enhance_batch(_dptr(x), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(torch.from_numpy(offs).to(dev)),
-                                    _dptr(audio), None, _dptr(mask), _dptr(pitch), _dptr(status), _dptr(scratch), total, n,
-                                    _dptr(batch.order) if use_order else None, batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_enhance_batch")
-    return Hw25EnhanceResult(batch=batch, audio=audio, mask=mask, grp_final=None, status=status, stages=None, pitch=pitch,
-                             host_row_offsets=offs, host_rows=rows)
-
-
-def hw25_enhance(x):
-    """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict: audio float32 [L], the enhanced
-    signal; mask [F][25] floats 0 / 1, pitch int32 [F], status, as hw25_ibm() gives them."""
-    lib = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    F = x.size // HW25_HOP
-    r = dict(audio=np.zeros(x.size, np.float32), mask=np.zeros((F, HW25_NCHAN), np.float32), pitch=np.zeros(F, np.int32))
-    status = np.zeros(1, np.int32)
-    rc = lib.sea_hw25_enhance(_np_ptr(x), x.size, _np_ptr(r["audio"]), _np_ptr(r["mask"]), _np_ptr(r["pitch"]), _np_ptr(status))
-    _lib.check(rc, "sea_hw25_enhance")
-    r["status"] = int(status[0])
-    return r
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1455,7 +1006,7 @@ def trainset_batch(batch, noise_src, noise_start, db, window=1, noisy_subband=Fa
     gain = torch.zeros(batch.n_utt, dtype=torch.float32, device=dev)
     subs = [torch.zeros(batch.total * 64, dtype=torch.int16, device=dev) for _ in range(3 if noisy_subband else 2)]
     rows = (np.asarray(batch.host_lengths) - 320) // 160 + 1
-    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    offs = _row_offsets(rows)
     irm = torch.zeros((int(rows.sum()), 64), dtype=torch.float32, device=dev)
     d_offs = torch.from_numpy(offs).to(dev)
     _lib.check(lib.sea_trainset_batch(_dptr(batch.data), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(noise_src),

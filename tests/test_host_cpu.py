@@ -231,6 +231,23 @@ def test_packed_batch_layout():
     assert [len(p) for p in b.split(b.data, full_frames_only=True)] == [960, 0, 0, 4000, 0]
 
 
+def test_frame_rows_and_row_offsets():
+    """rows per utterance and their exclusive prefix sum, the one place every batch wrapper takes them from"""
+    import speech_enhancement_amd as sea
+    b = sea.PackedBatch.from_arrays([np.arange(n, dtype=np.int16) for n in [1000, 0, 79, 4001, 8]], device="cpu")
+    for hop, want_rows, want_offs in ((None, [12, 0, 0, 50, 0], [0, 12, 12, 12, 62]), (160, [6, 0, 0, 25, 0], [0, 6, 6, 6, 31])):
+        rows, offs = b.frame_rows() if hop is None else b.frame_rows(hop=hop)
+        assert isinstance(rows, np.ndarray) and isinstance(offs, np.ndarray)
+        assert rows.dtype == np.int64 and offs.dtype == np.int64
+        assert list(rows) == want_rows and list(offs) == want_offs
+    assert b.n_frames == 62
+    rows, offs = sea.PackedBatch.from_arrays([], device="cpu").frame_rows()
+    assert rows.shape == (0,) and offs.shape == (0,) and rows.dtype == np.int64 and offs.dtype == np.int64
+    m = sea.MaskBatch.from_arrays([np.zeros((r, 64), np.float32) for r in (3, 1, 2)], device="cpu")
+    assert m.host_row_offsets.dtype == np.int64 and list(m.host_row_offsets) == [0, 3, 4]
+    assert list(m.host_rows) == [3, 1, 2] and m.row_offsets.tolist() == [0, 3, 4] and tuple(m.data.shape) == (6, 64)
+
+
 def test_corpus_is_deterministic_and_matches_scalar_lcg():
     from speech_enhancement_amd import corpus
     s, ref = 12345, []
