@@ -662,6 +662,36 @@ int sea_hw25_enhance_batch(const float *d_in_f32, const long long *d_offsets, co
 int sea_hw25_resynth(const float *x, long L, const float *mask, long F, float threshold, float *out_f32);
 int sea_hw25_enhance(const float *x, long L, float *out_f32, float *mask, int *pitch, int *status);
 int sea_hw25_resynth_text_write(const char *path, const float *out, long L);
+/* The front half of createIBM() at 16 kHz on 64 channels: the same HuWang.cpp:41-76 at the constants of resyth_64sub_IBM/cpp/
+ * HuWang.h (SAMPLING_FREQUENCY 16000, NUMBER_CHANNEL 64, MINCF 50, MAXCF 8000, WINDOW 320, OFFSET 160, MAX_DELAY 201, MIN_DELAY
+ * 32), the bank of sea_subband64_batch / sea_resynth64_batch / sea_irm_target_batch (csrc/hw64_kernel.hip, DESIGN.md section
+ * 5.16).  Parity: bit for bit against the reference's own functions compiled on a CPU against that header
+ * (tests/golden/hw64_*.npz).  initGroup onwards (pitchDtm, computeAM, finalSeg, resynthesis) is NOT built at 16 kHz.
+ * The calls mirror the sea_hw25_* front-half calls argument for argument, with 64 / 201 / 160 for 25 / 101 / 80: d_hout / d_hev
+ * (and d_gout, the gammatone output before the hair cell; null: not written) hold 64x the packed size, utterance u's
+ * [64][pitch] block at d_offsets[u] * 64; utterance u has sea_hw64_frames (lengths[u]) = lengths[u] / 160 rows from
+ * d_row_offsets[u]: d_cross_hc / d_cross_ev / d_pratio / d_mark [rows][64], d_pitch [rows] (32..200), d_acf_hc / d_acf_ev
+ * [rows][64][201] -- 51 456 B per row and stream, optional: a null pointer is not written.  d_scratch is not read and may be
+ * null.  Null pointers and an output that is an input or another output are refused before anything is launched; n_utt <= 0
+ * returns 0; the lengths stay on the device and nothing synchronises with the host.  sea_hw64_workgroups_per_utterance: how
+ * many workgroups the correlogram launch gives every utterance of a batch of n_utt on the current device (workgroup g takes
+ * the frames g, g + G, ..); 0 on error. */
+int sea_hw64_tables_host(float *cf64, float *bw64, float *midEar64, float *gain64, float *f1_64, float *f2_64, int *winsize64,
+                         float *lp181, float *hair10 /* ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0 */);
+long long sea_hw64_frames(long long length);
+int sea_hw64_workgroups_per_utterance(int n_utt);
+int sea_hw64_periphery_batch(const float *d_in_f32, float *d_hout, float *d_hev, float *d_gout, const long long *d_offsets,
+                             const long long *d_lengths, const int *d_order, int n_utt, void *stream);
+int sea_hw64_correlogram_batch(const float *d_hout, const float *d_hev, const long long *d_offsets, const long long *d_lengths,
+                               const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev, float *d_cross_hc,
+                               float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
+                               const int *d_order, int n_utt, void *stream);
+int sea_hw64_frontend_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
+                            const long long *d_lengths, const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev,
+                            float *d_cross_hc, float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
+                            const int *d_order, int n_utt, void *stream);
+int sea_hw64_frontend(const float *in, long L, float *hout, float *hev, float *acf_hc, float *acf_ev, float *cross_hc,
+                      float *cross_ev, int *pitch, float *pratio, float *mark);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

@@ -110,6 +110,13 @@ PROTOTYPES = {
     "sea_hw25_resynth": (_i, [_vp, _l, _vp, _l, _c.c_float, _vp]),
     "sea_hw25_enhance": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
     "sea_hw25_resynth_text_write": (_i, [_c.c_char_p, _vp, _l]),
+    "sea_hw64_tables_host": (_i, [_vp] * 9),
+    "sea_hw64_frames": (_ll, [_ll]),
+    "sea_hw64_workgroups_per_utterance": (_i, [_i]),
+    "sea_hw64_periphery_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "sea_hw64_correlogram_batch": (_i, [_vp] * 14 + [_i, _vp]),
+    "sea_hw64_frontend_batch": (_i, [_vp] * 15 + [_i, _vp]),
+    "sea_hw64_frontend": (_i, [_vp, _l] + [_vp] * 9),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -43,6 +43,7 @@ sea_gt_tables g_gt_host;
 sea_ns16k_tables g_ns16_host;
 sea_wb_tables g_wb_host;
 sea_hw25_tables g_hw25_host;
+sea_hw64_tables g_hw64_host;
 std::vector<float> g_hw25_tw; /* the forward FFT's twiddles; the inverse's are checked to be their conjugates */
 bool g_hw25_tw_conjugate = false;
 bool g_host_ready = false;
@@ -56,6 +57,7 @@ void host_tables()
     sea_build_ns16k_tables(&g_ns16_host);
     sea_build_wb_tables(&g_wb_host);
     sea_build_hw25_tables(&g_hw25_host);
+    sea_build_hw64_tables(&g_hw64_host);
     {
         std::vector<float> inv(2 * (size_t)SEA_HW25_TWIDDLES);
         g_hw25_tw.resize(2 * (size_t)SEA_HW25_TWIDDLES);
@@ -89,12 +91,14 @@ int ctx(DeviceCtx **out)
         HIP_TRY(hipMalloc(&c.ns16, sizeof(sea_ns16k_tables)));
         HIP_TRY(hipMalloc(&c.wb, sizeof(sea_wb_tables)));
         HIP_TRY(hipMalloc(&c.hw25, sizeof(sea_hw25_tables)));
+        HIP_TRY(hipMalloc(&c.hw64, sizeof(sea_hw64_tables)));
         HIP_TRY(hipMemcpy(c.ns, &g_ns_host, sizeof g_ns_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.cc, &g_cc_host, sizeof g_cc_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.gt, &g_gt_host, sizeof g_gt_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.ns16, &g_ns16_host, sizeof g_ns16_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.wb, &g_wb_host, sizeof g_wb_host, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(c.hw25, &g_hw25_host, sizeof g_hw25_host, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(c.hw64, &g_hw64_host, sizeof g_hw64_host, hipMemcpyHostToDevice));
         if (!g_hw25_tw_conjugate) return fail("hw25: the inverse FFT's twiddles are not the conjugates of the forward ones");
         HIP_TRY(hipMalloc(&c.hw25_tw, g_hw25_tw.size() * sizeof(float)));
         HIP_TRY(hipMemcpy(c.hw25_tw, g_hw25_tw.data(), g_hw25_tw.size() * sizeof(float), hipMemcpyHostToDevice));

@@ -27,6 +27,7 @@ struct DeviceCtx {
     sea_ns16k_tables *ns16 = nullptr;
     sea_wb_tables *wb = nullptr;
     sea_hw25_tables *hw25 = nullptr;
+    sea_hw64_tables *hw64 = nullptr;
     float *hw25_tw = nullptr; /* SEA_HW25_TWIDDLES (re, im) pairs: sea_build_hw25_twiddles (.., 1) */
     int n_cu = 256;
 };

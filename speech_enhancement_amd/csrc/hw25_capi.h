@@ -1,6 +1,6 @@
 /*
  * hw25_capi.h -- what the translation units behind the Hu-Wang C ABI share (capi.hip, hw25_pitch_capi.hip, hw25_am_capi.hip,
- * hw25_resynth_capi.hip): the single-utterance forms' batch of one, the refusal of outputs that are inputs, and where the
+ * hw25_resynth_capi.hip, hw64_capi.hip): the single-utterance forms' batch of one, the refusal of outputs that are inputs, and where the
  * whole estimator keeps gOut.
  */
 #pragma once
@@ -28,17 +28,17 @@ inline int shared_buffer(const void *const *outs, int n, std::initializer_list<c
 long long hw25_ibm_gout_offset(long long total_padded_samples, long long total_rows, int n_utt);
 
 /* One utterance from host memory as a batch of one: the samples zero-padded to Lp = L rounded up to 8 on the device, and
- * the three words a batch call takes as offsets, lengths and row_offsets (0, L, 0).  F = L / 80 frames; rows = F, but at
- * least 1, is what the frame outputs are allocated for. */
+ * the three words a batch call takes as offsets, lengths and row_offsets (0, L, 0).  F = L / hop frames (80 samples on the
+ * 25-channel bank, 160 on the 64-channel one); rows = F, but at least 1, is what the frame outputs are allocated for. */
 struct Hw25Single {
     long long Lp = 0, F = 0, rows = 1;
     const float *d_in = nullptr;
     const long long *d_offsets = nullptr, *d_lengths = nullptr, *d_row_offsets = nullptr;
 
-    int load(const float *x, long L) /* L > 0; 0 or fail() */
+    int load(const float *x, long L, int hop = SEA_HW25_HOP) /* L > 0; 0 or fail() */
     {
         Lp = align8(L);
-        F = sea_hw25_frames(L);
+        F = L / hop;
         rows = F > 0 ? F : 1;
         HIP_TRY(in_.alloc((size_t)Lp));
         HIP_TRY(meta_.alloc(3));

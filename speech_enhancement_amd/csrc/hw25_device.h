@@ -1,6 +1,7 @@
 /*
  * hw25_device.h -- what the Hu-Wang kernel files share on the device: the gammatone recurrence of the analysis
- * (hw25_kernel.hip) and of the resynthesis that inverts it (hw25_resynth_kernel.hip), and the constants, the lane fence and
+ * (hw25_kernel.hip, hw64_kernel.hip) and of the resynthesis that inverts it (hw25_resynth_kernel.hip), the hair cell's step of
+ * both banks' analysis, and the constants, the lane fence and
  * the label propagation of the estimator's two segmentations, initGroup's (hw25_pitch_kernel.hip) and finalSeg's
  * reSegmentation (hw25_am_kernel.hip).
  */
@@ -35,7 +36,32 @@ __device__ __forceinline__ float gt25_step(Gt25 &s, float in, float f1, float f2
     return out;
 }
 
-constexpr int kHw25None = 0x7fffffff;                              /* no label, no key */
+/* hairCell:279-297 for one sample.  kt is a double expression of the input (float + double literal), rounded once; the rest
+ * is float arithmetic; comparisons against the double literals 0.0 and 1.0 are exact in float.  Every constant comes from the
+ * bank's tables (sea_hw25_tables or sea_hw64_tables). */
+struct Hair25 {
+    float q, c, w;
+};
+template <class Tables>
+__device__ __forceinline__ float hair25_step(Hair25 &h, float in, const Tables &t)
+{
+    const double s = (double)in + 3.0;
+    const float kt = (s > 0.0) ? (float)((double)t.gdt * s / (s + 300.0)) : 0.0f;
+    const float replenish = (h.q < 1.0f) ? (t.ymdt - t.ydt * h.q) : 0.0f;
+    const float eject = kt * h.q;
+    const float reuptakeandloss = t.lplusrdt * h.c;
+    const float reuptake = t.rdt * h.c;
+    const float reprocess = t.xdt * h.w;
+    h.q = h.q + replenish - eject + reprocess;
+    if (h.q < 0.0f) h.q = 0.0f;
+    h.c = h.c + eject - reuptakeandloss;
+    if (h.c < 0.0f) h.c = 0.0f;
+    h.w = h.w + reuptake - reprocess;
+    if (h.w < 0.0f) h.w = 0.0f;
+    return t.hdt * h.c;
+}
+
+constexpr int kHw25None = 0x7fffffff;                             /* no label, no key */
 constexpr unsigned kHw25ChanBits = (1u << SEA_HW25_NCHAN) - 1u;    /* the channel lanes of a ballot */
 
 /* between a write by one lane and a later read by another lane of the same wave */

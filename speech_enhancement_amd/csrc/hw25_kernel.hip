@@ -24,29 +24,6 @@ constexpr int kCh = SEA_HW25_NCHAN, kDel = SEA_HW25_DELAYS, kHop = SEA_HW25_HOP,
 constexpr int kPerTile = 8;                          /* samples per step of the periphery loop */
 constexpr int kWinStage = SEA_HW25_MAXWIN + kDel - 1; /* samples one (channel, frame) reads: the window and 100 before it */
 
-/* hairCell:279-297 for one sample.  kt is a double expression of the input (float + double literal), rounded once; the rest
- * is float arithmetic; comparisons against the double literals 0.0 and 1.0 are exact in float. */
-struct Hair25 {
-    float q, c, w;
-};
-__device__ __forceinline__ float hair25_step(Hair25 &h, float in, const sea_hw25_tables &t)
-{
-    const double s = (double)in + 3.0;
-    const float kt = (s > 0.0) ? (float)((double)t.gdt * s / (s + 300.0)) : 0.0f;
-    const float replenish = (h.q < 1.0f) ? (t.ymdt - t.ydt * h.q) : 0.0f;
-    const float eject = kt * h.q;
-    const float reuptakeandloss = t.lplusrdt * h.c;
-    const float reuptake = t.rdt * h.c;
-    const float reprocess = t.xdt * h.w;
-    h.q = h.q + replenish - eject + reprocess;
-    if (h.q < 0.0f) h.q = 0.0f;
-    h.c = h.c + eject - reuptakeandloss;
-    if (h.c < 0.0f) h.c = 0.0f;
-    h.w = h.w + reuptake - reprocess;
-    if (h.w < 0.0f) h.w = 0.0f;
-    return t.hdt * h.c;
-}
-
 } // namespace
 
 /* One wave per utterance, lane = channel (25 of 64 lanes).  The input sample is the same word for every lane; the next

@@ -355,6 +355,29 @@ __global__ void hw25_periphery_kernel(Hw25Args a);   /* grid n_utt x 64 threads 
 __global__ void hw25_lowpass_kernel(Hw25Args a);     /* grid (n_utt, 25) x 256 */
 __global__ void hw25_correlogram_kernel(Hw25Args a); /* grid (n_utt, G) x 256: workgroup (u, g) takes frames g, g + G, ... */
 
+/* The same front half at 16 kHz on the 64-channel bank (hw64_kernel.hip).  Hw25Args's layout at 64 channels: hout / hev / gout
+ * hold utterance u's [64][pitch] block at offsets[u] * 64; utterance u has lengths[u] / 160 rows from row_offsets[u]: acf_*
+ * [rows][64][201] (either may be null: not written), cross_*, pratio, mark [rows][64], pitch [rows]. */
+struct Hw64Args {
+    const float *in;
+    float *hout, *hev;
+    float *gout; /* the periphery kernel: gOut in hout's layout, or null: not written */
+    const long long *offsets;
+    const long long *lengths;
+    const long long *row_offsets;
+    float *acf_hc, *acf_ev;
+    float *cross_hc, *cross_ev;
+    int *pitch;
+    float *pratio, *mark;
+    const int *order;
+    const sea_hw64_tables *tables;
+    int n_utt;
+};
+constexpr int kHw64CorrThreads = 512;                 /* seven waves of (stream, delay) lanes and one that follows them */
+__global__ void hw64_periphery_kernel(Hw64Args a);   /* grid n_utt x 64 threads */
+__global__ void hw64_lowpass_kernel(Hw64Args a);     /* grid (n_utt, 64) x 256 */
+__global__ void hw64_correlogram_kernel(Hw64Args a); /* grid (n_utt, G) x 512: workgroup (u, g) takes frames g, g + G, ... */
+
 /* The Hu-Wang estimator's initial grouping and pitch tracking (hw25_pitch_kernel.hip).  Rows as Hw25Args has them: acf
  * [rows][25][101], cross, pratio_in, mark_in [rows][25] are the front half's and only read; pitch [rows], grp and pratio
  * [rows][25], status [n_utt] are written.  stages (or null): utterance u's block of SEA_HW25_STAGE_WORDS words per row at

@@ -7,6 +7,7 @@
  * arithmetic it reproduces; the layouts (lane-major, padded, bit-reversed) are this engine's own.
  */
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -608,36 +609,39 @@ static float hw_bessi0(float x)
     return ans;
 }
 
-void sea_build_hw25_tables(sea_hw25_tables *t)
+/* One bank of the estimator at the constants of its HuWang.h: AudiPeriph:121-140, gammaToneFilter:216-223, computeACF:345-346,
+ * lowPass's filter and hairCell:261-274.  fs = SAMPLING_FREQUENCY, window = WINDOW; the per-channel arrays hold nch entries,
+ * lp taps, hair10 = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0; am2 (null: not wanted) = kaiserPara's a and beta. */
+static void hw_build_bank(int fs, int mincf, int maxcf, int nch, int window, int maxwin, int taps, float *cfs, float *bws,
+                          float *midEar, float *gain, float *f1, float *f2, int *winsize, float *lp, float *hair10, float *am2)
 {
     const double kPiHW = 3.1415926535897932384626433832795; /* HuWang.h:7 */
     const double Y = 5.05, G = 2000.0, Lc = 2500.0, R = 6580.0, X = 66.31, A = 3.0, B = 300.0, H = 48000.0, M = 1.0; /* HuWang.h:36-44 */
-    float erbLo = (float)(21.4 * log10(80 * 0.00437 + 1.0));
-    float erbHi = (float)(21.4 * log10(4000 * 0.00437 + 1.0));
-    float erbStep = (erbHi - erbLo) / (SEA_HW25_NCHAN - 1);
-    float dt = 1 / (float)8000;
+    float erbLo = (float)(21.4 * log10(mincf * 0.00437 + 1.0));
+    float erbHi = (float)(21.4 * log10(maxcf * 0.00437 + 1.0));
+    float erbStep = (erbHi - erbLo) / (nch - 1);
+    float dt = 1 / (float)fs;
     float twoPiT = (float)(2 * kPiHW * dt);
     int c;
-    memset(t, 0, sizeof *t);
-    for (c = 0; c < SEA_HW25_NCHAN; c++) { /* AudiPeriph:132-140, gammaToneFilter:216-223, computeACF:345-346 */
+    for (c = 0; c < nch; c++) { /* AudiPeriph:132-140, gammaToneFilter:216-223, computeACF:345-346 */
         float cf = (float)((pow(10, (erbLo + c * erbStep) / 21.4) - 1) / 0.00437);
         float bw = (float)(24.7 * (cf * 0.00437 + 1.0) * 1.019);
         float phon = (float)(phons_at(cf) - 60.0);
         float ear = (float)pow(10, (double)(phon / 20));
         float z = expf(-twoPiT * bw);
-        int win = (int)(4 * 8000 / cf);
-        t->cf[c] = cf;
-        t->bw[c] = bw;
-        t->midEar[c] = ear;
-        t->gain[c] = (float)(ear * pow((double)(twoPiT * bw), 4.0) / 3.0);
-        t->f1[c] = cosf(cf * twoPiT) * z;
-        t->f2[c] = sinf(cf * twoPiT) * z;
-        t->winsize[c] = win < SEA_HW25_WINDOW ? SEA_HW25_WINDOW : win;
-        if (t->winsize[c] > SEA_HW25_MAXWIN) abort();
+        int win = (int)(4 * fs / cf);
+        cfs[c] = cf;
+        bws[c] = bw;
+        midEar[c] = ear;
+        gain[c] = (float)(ear * pow((double)(twoPiT * bw), 4.0) / 3.0);
+        f1[c] = cosf(cf * twoPiT) * z;
+        f2[c] = sinf(cf * twoPiT) * z;
+        winsize[c] = win < window ? window : win;
+        if (winsize[c] > maxwin) abort();
     }
     { /* kaiserPara (RIPPLE, float (STOPBAND - PASSBAND) / SAMPLING_FREQUENCY, ..), :1553-1569 */
-        const float delta = (float)0.01, transBw = (float)((float)(1200 - 1000) / 8000);
-        const float wn = (float)(1000 + 1200) / 8000; /* :311 */
+        const float delta = (float)0.01, transBw = (float)((float)(1200 - 1000) / fs);
+        const float wn = (float)(1000 + 1200) / fs; /* :311 */
         float a = -20 * log10f(delta), beta, len;
         int fLength, tim;
         if (a <= 21) beta = 0;
@@ -648,32 +652,46 @@ void sea_build_hw25_tables(sea_hw25_tables *t)
         if ((len - fLength) < 0.5) fLength++;
         else fLength += 2;
         if (fLength % 2 != 0) fLength++;
-        if (fLength != SEA_HW25_TAPS - 1) abort();
+        if (fLength != taps - 1) abort();
         if (!(beta < 3.75f)) abort(); /* bessi0 then only ever takes its polynomial branch */
-        t->am_a = a; /* amPatt:1215 calls kaiserPara with the same delta */
-        t->am_beta = beta;
+        if (am2) { /* amPatt:1215 calls kaiserPara with the same delta */
+            am2[0] = a;
+            am2[1] = beta;
+        }
         for (tim = 0; tim <= fLength; tim++) { /* kaiserLowPass, :1576-1590 */
             float k = 2 * tim / (float)fLength - 1;
             float f = hw_bessi0(beta * sqrtf(1 - k * k)) / hw_bessi0(beta);
             int step = tim - fLength / 2;
             if (step != 0) f = (float)(f * (sin(wn * kPiHW * step) / kPiHW / step));
             else f *= wn;
-            t->lp[tim] = f;
+            lp[tim] = f;
         }
     }
     { /* hairCell:261-274 */
         float kt = (float)(G * A / (A + B));
-        t->ymdt = (float)(Y * M * dt);
-        t->xdt = (float)(X * dt);
-        t->ydt = (float)(Y * dt);
-        t->lplusrdt = (float)((Lc + R) * dt);
-        t->rdt = (float)(R * dt);
-        t->gdt = (float)(G * dt);
-        t->hdt = (float)H;
-        t->c0 = (float)(M * Y * kt / (Lc * kt + Y * (Lc + R)));
-        t->q0 = (float)(t->c0 * (Lc + R) / kt);
-        t->w0 = (float)(t->c0 * R / X);
+        float c0 = (float)(M * Y * kt / (Lc * kt + Y * (Lc + R)));
+        hair10[0] = (float)(Y * M * dt);
+        hair10[1] = (float)(X * dt);
+        hair10[2] = (float)(Y * dt);
+        hair10[3] = (float)((Lc + R) * dt);
+        hair10[4] = (float)(R * dt);
+        hair10[5] = (float)(G * dt);
+        hair10[6] = (float)H;
+        hair10[7] = (float)(c0 * (Lc + R) / kt);
+        hair10[8] = c0;
+        hair10[9] = (float)(c0 * R / X);
     }
+}
+
+/* the ten hair-cell words of both banks' tables are consecutive floats from ymdt on */
+typedef char hw25_hair_words_are_consecutive[offsetof(sea_hw25_tables, w0) - offsetof(sea_hw25_tables, ymdt) == 9 * sizeof(float) ? 1 : -1];
+typedef char hw64_hair_words_are_consecutive[offsetof(sea_hw64_tables, w0) - offsetof(sea_hw64_tables, ymdt) == 9 * sizeof(float) ? 1 : -1];
+
+void sea_build_hw25_tables(sea_hw25_tables *t)
+{
+    memset(t, 0, sizeof *t);
+    hw_build_bank(8000, 80, 4000, SEA_HW25_NCHAN, SEA_HW25_WINDOW, SEA_HW25_MAXWIN, SEA_HW25_TAPS, t->cf, t->bw, t->midEar, t->gain,
+                  t->f1, t->f2, t->winsize, t->lp, &t->ymdt, &t->am_a);
     sea_hw25_ola_tables(t->olaW, NULL, NULL);
 }
 
@@ -732,6 +750,30 @@ void sea_hw25_plain_tables(float *cf25, float *bw25, float *midEar25, float *gai
     memcpy(f2_25, t.f2, SEA_HW25_NCHAN * sizeof(float));
     memcpy(winsize25, t.winsize, SEA_HW25_NCHAN * sizeof(int));
     memcpy(lp91, t.lp, SEA_HW25_TAPS * sizeof(float));
+    memcpy(hair10, &t.ymdt, 10 * sizeof(float));
+}
+
+/* the same bank at the constants of resyth_64sub_IBM/cpp/HuWang.h: 16 kHz, 64 channels from 50 Hz to 8 kHz */
+void sea_build_hw64_tables(sea_hw64_tables *t)
+{
+    memset(t, 0, sizeof *t);
+    hw_build_bank(16000, 50, 8000, SEA_HW64_NCHAN, SEA_HW64_WINDOW, SEA_HW64_MAXWIN, SEA_HW64_TAPS, t->cf, t->bw, t->midEar, t->gain,
+                  t->f1, t->f2, t->winsize, t->lp, &t->ymdt, NULL);
+}
+
+void sea_hw64_plain_tables(float *cf64, float *bw64, float *midEar64, float *gain64, float *f1_64, float *f2_64, int *winsize64,
+                           float *lp181, float *hair10)
+{
+    sea_hw64_tables t;
+    sea_build_hw64_tables(&t);
+    memcpy(cf64, t.cf, sizeof t.cf);
+    memcpy(bw64, t.bw, sizeof t.bw);
+    memcpy(midEar64, t.midEar, sizeof t.midEar);
+    memcpy(gain64, t.gain, sizeof t.gain);
+    memcpy(f1_64, t.f1, sizeof t.f1);
+    memcpy(f2_64, t.f2, sizeof t.f2);
+    memcpy(winsize64, t.winsize, sizeof t.winsize);
+    memcpy(lp181, t.lp, SEA_HW64_TAPS * sizeof(float));
     memcpy(hair10, &t.ymdt, 10 * sizeof(float));
 }
 

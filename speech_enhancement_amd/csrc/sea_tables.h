@@ -274,6 +274,31 @@ void sea_build_hw25_twiddles(float *tw, int direct);
 void sea_hw25_plain_tables(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
                            float *lp91, float *hair10);
 
+/* ---- the same front end at 16 kHz on 64 channels: HuWang.cpp compiled against resyth_64sub_IBM/cpp/HuWang.h (SAMPLING_FREQUENCY
+ * 16000, NUMBER_CHANNEL 64, MINCF 50, MAXCF 8000).  The expressions and their roundings are those of the 25-channel tables; only
+ * the constants differ. */
+enum {
+    SEA_HW64_NCHAN = 64,    /* NUMBER_CHANNEL */
+    SEA_HW64_DELAYS = 201,  /* MAX_DELAY = 16000 / 80 + 1 */
+    SEA_HW64_MINDELAY = 32, /* MIN_DELAY = 16000 / 500 */
+    SEA_HW64_WINDOW = 320,  /* WINDOW = 16000 / 50 */
+    SEA_HW64_HOP = 160,     /* OFFSET = 16000 / 100 */
+    SEA_HW64_TAPS = 181,    /* fLength + 1, fLength = 180 from kaiserPara (0.01, 200 / 16000.) */
+    SEA_HW64_MAXWIN = 1280  /* the widest window: channel 0, int (4 * 16000 / cf), cf = 50 */
+};
+typedef struct {
+    float cf[SEA_HW64_NCHAN], bw[SEA_HW64_NCHAN], midEar[SEA_HW64_NCHAN];
+    float gain[SEA_HW64_NCHAN], f1[SEA_HW64_NCHAN], f2[SEA_HW64_NCHAN];
+    int winsize[SEA_HW64_NCHAN];                   /* 1280, 978, 784, 647, 547, 470, 410, 360, then 320: 23 396 in all */
+    float lp[184];                                 /* the 181 taps of kaiserLowPass */
+    float ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt; /* hairCell:261-268 at dt = 1 / 16000 */
+    float q0, c0, w0;                              /* its initial state, :271-274 */
+} sea_hw64_tables;
+void sea_build_hw64_tables(sea_hw64_tables *t);
+/* plain tables for host-side checks; hair10 as in sea_hw25_plain_tables */
+void sea_hw64_plain_tables(float *cf64, float *bw64, float *midEar64, float *gain64, float *f1_64, float *f2_64, int *winsize64,
+                           float *lp181, float *hair10);
+
 void sea_build_ns_tables(sea_ns_tables *t);
 void sea_build_cc_tables(sea_cc_tables *t);
 void sea_build_gt_tables(sea_gt_tables *t);

@@ -12,6 +12,10 @@ from . import _lib
 from .engine import _dptr, _np_ptr, _row_offsets, _stream_ptr, _torch
 
 HW25_NCHAN, HW25_DELAYS, HW25_HOP = 25, 101, 80
+# what the front half's wrappers need to know of a bank (hw64.py has the 64-channel one): its sizes and its calls' names;
+# gout_fn: the periphery call that also returns gOut, where the bank has one of its own (None: periphery_fn takes a null)
+_BANK25 = SimpleNamespace(name="hw25", nchan=HW25_NCHAN, delays=HW25_DELAYS, hop=HW25_HOP, taps=91,
+                          gout_fn="sea_hw25_periphery_gout_batch", scratch_fn="sea_hw25_scratch_bytes")
 
 
 # ------------------------------------------------------------------------------------------------
@@ -27,9 +31,9 @@ def _hw25_input(batch):
     return batch.data.to(torch.float32)
 
 
-def _hw25_start(batch, dev=None, row_offsets=None, zeros=()):
+def _hw25_start(batch, dev=None, row_offsets=None, zeros=(), bank=_BANK25):
     """What a batch wrapper starts with: x, the float input (only without dev: the wrappers that are given device tensors pass
-    their device); rows and offs, length // 80 rows per utterance and where they begin (host); d_offs, row_offsets or the
+    their device); rows and offs, length // 80 (the bank's hop) rows per utterance and where they begin (host); d_offs, row_offsets or the
     device copy of offs; n, the rows of the batch, and total, its packed samples (at least 1 and 8, so that no tensor is
     empty); and the zeroed outputs named in zeros: mask [n][25], pitch int32 [n], status int32 [n_utt]."""
     torch = _torch()
@@ -37,10 +41,10 @@ def _hw25_start(batch, dev=None, row_offsets=None, zeros=()):
     if dev is None:
         s.x = _hw25_input(batch)
         s.dev = s.x.device
-    s.rows, s.offs = batch.frame_rows(HW25_HOP)
+    s.rows, s.offs = batch.frame_rows(bank.hop)
     s.d_offs = row_offsets if row_offsets is not None else torch.from_numpy(s.offs).to(s.dev)
     s.n, s.total = max(int(s.rows.sum()), 1), max(int(batch.total), 8)
-    shapes = dict(mask=((s.n, HW25_NCHAN), torch.float32), pitch=(s.n, torch.int32), status=(max(batch.n_utt, 1), torch.int32))
+    shapes = dict(mask=((s.n, bank.nchan), torch.float32), pitch=(s.n, torch.int32), status=(max(batch.n_utt, 1), torch.int32))
     for k in zeros:
         setattr(s, k, torch.zeros(shapes[k][0], dtype=shapes[k][1], device=s.dev))
     return s
@@ -53,6 +57,7 @@ def _hw25_order(batch, use_order):
 class _Hw25Rows:
     """The results' common part: the keyword attributes, and utterance u's share of a device tensor as numpy.  host_row_offsets
     and host_rows say where its rows are (Hw25PitchResult: its front's), batch where its samples are."""
+    NCHAN = HW25_NCHAN
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -67,9 +72,9 @@ class _Hw25Rows:
 
     def _block(self, u, t):
         """utterance u's [25][L] block of a tensor of 25x the packed size (a view into its padded [25][pitch] copy)"""
-        off, L = int(self.batch.host_offsets[u]), int(self.batch.host_lengths[u])
+        off, L, nch = int(self.batch.host_offsets[u]), int(self.batch.host_lengths[u]), self.NCHAN
         pitch = (L + 7) // 8 * 8
-        return t[off * HW25_NCHAN:off * HW25_NCHAN + HW25_NCHAN * pitch].cpu().numpy().reshape(HW25_NCHAN, pitch)[:, :L]
+        return t[off * nch:off * nch + nch * pitch].cpu().numpy().reshape(nch, pitch)[:, :L]
 
 
 def _hw25_host(fn, x, keys, *args, status=True):
@@ -91,28 +96,42 @@ def _hw25_host(fn, x, keys, *args, status=True):
 # ------------------------------------------------------------------------------------------------
 # the estimator's front half (HuWang.cpp:41-76; csrc/hw25_kernel.hip)
 # ------------------------------------------------------------------------------------------------
-def hw25_tables():
-    """The bank's host tables: cf, bw, midEarCoeff, gain, f1, f2 [25], winsize int32 [25], lp [91] (lowPass's Kaiser taps) and
-    hair [10] = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0."""
+def _bank_tables(bank):
     lib = _lib.load()
-    t = {k: np.zeros(HW25_NCHAN, np.float32) for k in ("cf", "bw", "midEarCoeff", "gain", "f1", "f2")}
-    t.update(winsize=np.zeros(HW25_NCHAN, np.int32), lp=np.zeros(91, np.float32), hair=np.zeros(10, np.float32))
+    t = {k: np.zeros(bank.nchan, np.float32) for k in ("cf", "bw", "midEarCoeff", "gain", "f1", "f2")}
+    t.update(winsize=np.zeros(bank.nchan, np.int32), lp=np.zeros(bank.taps, np.float32), hair=np.zeros(10, np.float32))
     keys = ("cf", "bw", "midEarCoeff", "gain", "f1", "f2", "winsize", "lp", "hair")
-    _lib.check(lib.sea_hw25_tables_host(*[_np_ptr(t[k]) for k in keys]), "sea_hw25_tables_host")
+    fn = f"sea_{bank.name}_tables_host"
+    _lib.check(getattr(lib, fn)(*[_np_ptr(t[k]) for k in keys]), fn)
     return t
 
 
-def _hw25_periphery(batch, use_order, want_gout):
+def hw25_tables():
+    """The bank's host tables: cf, bw, midEarCoeff, gain, f1, f2 [25], winsize int32 [25], lp [91] (lowPass's Kaiser taps) and
+    hair [10] = ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0."""
+    return _bank_tables(_BANK25)
+
+
+def _bank_periphery(bank, batch, use_order, want_gout):
     torch = _torch()
     lib = _lib.load()
     x = _hw25_input(batch)
-    hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=x.device)
+    hout = torch.zeros(batch.total * bank.nchan, dtype=torch.float32, device=x.device)
     outs = [hout] + [torch.zeros_like(hout) for _ in range(2 if want_gout else 1)]
-    fn = "sea_hw25_periphery_gout_batch" if want_gout else "sea_hw25_periphery_batch"
-    rc = getattr(lib, fn)(_dptr(x), *[_dptr(t) for t in outs], _dptr(batch.offsets), _dptr(batch.lengths),
-                          _hw25_order(batch, use_order), batch.n_utt, _stream_ptr())
+    ptrs = [_dptr(t) for t in outs]
+    fn = f"sea_{bank.name}_periphery_batch"
+    if bank.gout_fn and want_gout:
+        fn = bank.gout_fn
+    elif not bank.gout_fn and not want_gout:
+        ptrs.append(None)
+    rc = getattr(lib, fn)(_dptr(x), *ptrs, _dptr(batch.offsets), _dptr(batch.lengths), _hw25_order(batch, use_order),
+                          batch.n_utt, _stream_ptr())
     _lib.check(rc, fn)
     return tuple(outs)
+
+
+def _hw25_periphery(batch, use_order, want_gout):
+    return _bank_periphery(_BANK25, batch, use_order, want_gout)
 
 
 def hw25_periphery_batch(batch, use_order=True):
@@ -121,14 +140,18 @@ def hw25_periphery_batch(batch, use_order=True):
     return _hw25_periphery(batch, use_order, False)
 
 
-def hw25_split(batch, tensor):
-    """A hw25_periphery_batch() tensor -> per-utterance numpy arrays [25][L]."""
+def _bank_split(bank, batch, tensor):
     host = tensor.detach().cpu().numpy()
-    out = []
+    out, nch = [], bank.nchan
     for off, L in zip(batch.host_offsets, batch.host_lengths):
         pitch = (int(L) + 7) // 8 * 8
-        out.append(host[off * HW25_NCHAN:off * HW25_NCHAN + HW25_NCHAN * pitch].reshape(HW25_NCHAN, pitch)[:, :int(L)].copy())
+        out.append(host[off * nch:off * nch + nch * pitch].reshape(nch, pitch)[:, :int(L)].copy())
     return out
+
+
+def hw25_split(batch, tensor):
+    """A hw25_periphery_batch() tensor -> per-utterance numpy arrays [25][L]."""
+    return _bank_split(_BANK25, batch, tensor)
 
 
 class Hw25Result(_Hw25Rows):
@@ -148,56 +171,62 @@ class Hw25Result(_Hw25Rows):
                     mark=rows(self.mark))
 
 
-def _hw25_front(batch, want_acf, use_order, hout=None, hev=None):
-    """the one body of hw25_correlogram_batch (hout and hev given) and hw25_frontend_batch (computed here, in the same launch
-    group); the frame outputs have at least one row, so that no tensor is empty"""
+def _bank_front(bank, result, batch, want_acf, use_order, hout=None, hev=None):
+    """the one body of the correlogram wrappers (hout and hev given) and the front-half wrappers (computed here, in the same
+    launch group) of both banks; the frame outputs have at least one row, so that no tensor is empty"""
     torch = _torch()
     lib = _lib.load()
     whole = hout is None
-    s = _hw25_start(batch, dev=None if whole else hout.device, zeros=("pitch",))
-    fr = {k: torch.zeros((s.n, HW25_NCHAN), dtype=torch.float32, device=s.dev) for k in ("cross_hc", "cross_ev", "pratio", "mark")}
-    acf = [torch.zeros((s.n, HW25_NCHAN, HW25_DELAYS), dtype=torch.float32, device=s.dev) if want_acf else None for _ in range(2)]
-    nbytes = int(lib.sea_hw25_scratch_bytes(int(batch.total), int(batch.n_utt)))
+    nch = bank.nchan
+    s = _hw25_start(batch, dev=None if whole else hout.device, zeros=("pitch",), bank=bank)
+    fr = {k: torch.zeros((s.n, nch), dtype=torch.float32, device=s.dev) for k in ("cross_hc", "cross_ev", "pratio", "mark")}
+    acf = [torch.zeros((s.n, nch, bank.delays), dtype=torch.float32, device=s.dev) if want_acf else None for _ in range(2)]
+    nbytes = int(getattr(lib, bank.scratch_fn)(int(batch.total), int(batch.n_utt))) if bank.scratch_fn else 0
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=s.dev) if nbytes else None
     if whole:
-        hout = torch.zeros(batch.total * HW25_NCHAN, dtype=torch.float32, device=s.dev)
+        hout = torch.zeros(batch.total * nch, dtype=torch.float32, device=s.dev)
         hev = torch.zeros_like(hout)
-    fn = "sea_hw25_frontend_batch" if whole else "sea_hw25_correlogram_batch"
+    fn = f"sea_{bank.name}_frontend_batch" if whole else f"sea_{bank.name}_correlogram_batch"
     rc = getattr(lib, fn)(*([_dptr(s.x)] if whole else []), _dptr(hout), _dptr(hev), _dptr(batch.offsets), _dptr(batch.lengths),
                           _dptr(s.d_offs), _dptr(acf[0]), _dptr(acf[1]), _dptr(fr["cross_hc"]), _dptr(fr["cross_ev"]), _dptr(s.pitch),
                           _dptr(fr["pratio"]), _dptr(fr["mark"]), _dptr(scratch), _hw25_order(batch, use_order), batch.n_utt,
                           _stream_ptr())
     _lib.check(rc, fn)
-    return Hw25Result(batch, hout=hout, hev=hev, acf_hc=acf[0], acf_ev=acf[1], pitch=s.pitch, row_offsets=s.d_offs,
-                      host_row_offsets=s.offs, host_rows=s.rows, **fr)
+    return result(batch, hout=hout, hev=hev, acf_hc=acf[0], acf_ev=acf[1], pitch=s.pitch, row_offsets=s.d_offs,
+                  host_row_offsets=s.offs, host_rows=s.rows, **fr)
 
 
 def hw25_correlogram_batch(batch, hout, hev, want_acf=False, use_order=True):
     """computeACF, crossCorr, globalPitch, timeCrn and the initial labelling from hw25_periphery_batch()'s tensors."""
-    return _hw25_front(batch, want_acf, use_order, hout, hev)
+    return _bank_front(_BANK25, Hw25Result, batch, want_acf, use_order, hout, hev)
 
 
 def hw25_frontend_batch(batch, want_acf=False, use_order=True):
     """The front half of createIBM() for every utterance of the batch, one launch group on the current stream -> Hw25Result.
     The ACFs are [rows][25][101] floats per stream (about 8 MB per 4 s utterance): computed always, written only on request."""
-    return _hw25_front(batch, want_acf, use_order)
+    return _bank_front(_BANK25, Hw25Result, batch, want_acf, use_order)
+
+
+def _bank_frontend_host(bank, x, want_acf):
+    lib = _lib.load()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    L, F, nch = x.size, x.size // bank.hop, bank.nchan
+    r = dict(hOut=np.zeros((nch, L), np.float32), hEv=np.zeros((nch, L), np.float32),
+             acf_hc=np.zeros((F, nch, bank.delays), np.float32) if want_acf else None,
+             acf_ev=np.zeros((F, nch, bank.delays), np.float32) if want_acf else None,
+             cross_hc=np.zeros((F, nch), np.float32), cross_ev=np.zeros((F, nch), np.float32),
+             pitch=np.zeros(F, np.int32), pRatio=np.zeros((F, nch), np.float32), mark=np.zeros((F, nch), np.float32))
+    keys = ("hOut", "hEv", "acf_hc", "acf_ev", "cross_hc", "cross_ev", "pitch", "pRatio", "mark")
+    fn = f"sea_{bank.name}_frontend"
+    rc = getattr(lib, fn)(_np_ptr(x), L, *[_np_ptr(r[k]) if r[k] is not None else None for k in keys])
+    _lib.check(rc, fn)
+    return r
 
 
 def hw25_frontend(x, want_acf=True):
     """One utterance from host memory (float32 or int16 samples on the int16 scale) -> dict under the reference's names:
     hOut, hEv [25][L]; acf_hc, acf_ev [F][25][101] (None without want_acf); cross_hc, cross_ev, pRatio, mark [F][25]; pitch [F]."""
-    lib = _lib.load()
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    L, F = x.size, x.size // HW25_HOP
-    r = dict(hOut=np.zeros((HW25_NCHAN, L), np.float32), hEv=np.zeros((HW25_NCHAN, L), np.float32),
-             acf_hc=np.zeros((F, HW25_NCHAN, HW25_DELAYS), np.float32) if want_acf else None,
-             acf_ev=np.zeros((F, HW25_NCHAN, HW25_DELAYS), np.float32) if want_acf else None,
-             cross_hc=np.zeros((F, HW25_NCHAN), np.float32), cross_ev=np.zeros((F, HW25_NCHAN), np.float32),
-             pitch=np.zeros(F, np.int32), pRatio=np.zeros((F, HW25_NCHAN), np.float32), mark=np.zeros((F, HW25_NCHAN), np.float32))
-    keys = ("hOut", "hEv", "acf_hc", "acf_ev", "cross_hc", "cross_ev", "pitch", "pRatio", "mark")
-    rc = lib.sea_hw25_frontend(_np_ptr(x), L, *[_np_ptr(r[k]) if r[k] is not None else None for k in keys])
-    _lib.check(rc, "sea_hw25_frontend")
-    return r
+    return _bank_frontend_host(_BANK25, x, want_acf)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what cepsslices --steps 7  # NoiseSup + the plain CompCeps in time slices and from host buffers, both rates, opt-in
     python tools/bench_extra.py --what trainset --steps 7  # the training-set builder: mix, subbands, IRM, pipeline and host entry point, opt-in
     python tools/bench_extra.py --what hw25 --steps 5  # the Hu-Wang front half on the 25-channel bank: periphery, correlogram, launch group, opt-in
+    python tools/bench_extra.py --what hw64 --steps 3  # the same front half at 16 kHz on the 64-channel bank, opt-in
     python tools/bench_extra.py --what hw25pitch --steps 3  # its initial grouping and pitch tracking beside the correlogram, opt-in
     python tools/bench_extra.py --what hw25ibm --steps 3  # its AM stage, final grouping and the whole estimator beside the other stages, opt-in
     python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
@@ -1102,6 +1103,55 @@ def main():
                                    "sea::hw25_periphery_kernel + sea::hw25_lowpass_kernel + sea::hw25_correlogram_kernel")):
             med, t = median_ms(fn, args.steps)
             line = {"metric": f"Hu-Wang front half, 25-channel 8 kHz bank: {name} (frames of 80 samples/sec); a first form, not tuned",
+                    "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
+                    "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}
+            if "correlogram" in name:
+                line["multiply_adds_per_step"] = macs
+                line["multiply_adds_per_sec"] = macs / (med / 1e3)
+            else:
+                line["samples_per_sec"] = samples / (med / 1e3)
+            print(json.dumps(line), flush=True)
+        del hout, hev, acf_hc, acf_ev
+
+    if "hw64" in what:
+        # The Hu-Wang estimator's front half at 16 kHz on the 64-channel bank, on the --utts corpus batch taken as 16 kHz float
+        # samples: the steps and the scheme of --what hw25.  The correlogram's arithmetic is 2 x 201 x 23396 multiply-adds per
+        # frame (the window sizes sum to 23396), 8.8 times the 25-channel bank's.
+        lib = sea.load()
+        n = batch.n_utt
+        x = batch.data.to(torch.float32)
+        rows = np.asarray(batch.host_lengths, dtype=np.int64) // 160
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames = int(rows.sum())
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev = z(batch.total * 64), z(batch.total * 64)
+        cross_hc, cross_ev, pratio, mark, pitch = z((frames, 64)), z((frames, 64)), z((frames, 64)), z((frames, 64)), z(frames, torch.int32)
+        acf_hc, acf_ev = z((frames, 64, 201)), z((frames, 64, 201))
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def periphery():
+            assert lib.sea_hw64_periphery_batch(P(x), P(hout), P(hev), None, P(batch.offsets), P(batch.lengths), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def correlogram(a0=None, a1=None):
+            assert lib.sea_hw64_correlogram_batch(P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(a0), P(a1), P(cross_hc),
+                                                  P(cross_ev), P(pitch), P(pratio), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def group():
+            assert lib.sea_hw64_frontend_batch(P(x), P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), None, None, P(cross_hc),
+                                               P(cross_ev), P(pitch), P(pratio), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+        macs = frames * 2 * 201 * 23396
+        samples = int(np.sum(batch.host_lengths))
+        workload = (f"the {args.utts}-utterance corpus as 16 kHz float samples: {samples} samples, {frames} frames of 160, "
+                    f"{lib.sea_hw64_workgroups_per_utterance(n)} workgroup(s) per utterance; median of {args.steps} steps after one warm-up")
+        for name, fn, kernels in (("periphery (64-channel gammatone + hair cell + 181-tap low-pass)", periphery, "sea::hw64_periphery_kernel + sea::hw64_lowpass_kernel"),
+                                  ("correlogram without ACF outputs", correlogram, "sea::hw64_correlogram_kernel"),
+                                  ("correlogram with both ACF outputs", lambda: correlogram(acf_hc, acf_ev), "sea::hw64_correlogram_kernel"),
+                                  ("launch group: periphery + correlogram without ACF outputs", group,
+                                   "sea::hw64_periphery_kernel + sea::hw64_lowpass_kernel + sea::hw64_correlogram_kernel")):
+            med, t = median_ms(fn, args.steps)
+            line = {"metric": f"Hu-Wang front half, 64-channel 16 kHz bank: {name} (frames of 160 samples/sec); a first form, not tuned",
                     "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
                     "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}
             if "correlogram" in name:
