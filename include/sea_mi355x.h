@@ -666,7 +666,8 @@ int sea_hw25_resynth_text_write(const char *path, const float *out, long L);
  * HuWang.h (SAMPLING_FREQUENCY 16000, NUMBER_CHANNEL 64, MINCF 50, MAXCF 8000, WINDOW 320, OFFSET 160, MAX_DELAY 201, MIN_DELAY
  * 32), the bank of sea_subband64_batch / sea_resynth64_batch / sea_irm_target_batch (csrc/hw64_kernel.hip, DESIGN.md section
  * 5.16).  Parity: bit for bit against the reference's own functions compiled on a CPU against that header
- * (tests/golden/hw64_*.npz).  initGroup onwards (pitchDtm, computeAM, finalSeg, resynthesis) is NOT built at 16 kHz.
+ * (tests/golden/hw64_*.npz).  initGroup and pitchDtm follow below (sea_hw64_pitch_*); computeAM onwards (finalSeg, resynthesis)
+ * is NOT built at 16 kHz.
  * The calls mirror the sea_hw25_* front-half calls argument for argument, with 64 / 201 / 160 for 25 / 101 / 80: d_hout / d_hev
  * (and d_gout, the gammatone output before the hair cell; null: not written) hold 64x the packed size, utterance u's
  * [64][pitch] block at d_offsets[u] * 64; utterance u has sea_hw64_frames (lengths[u]) = lengths[u] / 160 rows from
@@ -692,6 +693,38 @@ int sea_hw64_frontend_batch(const float *d_in_f32, float *d_hout, float *d_hev, 
                             const int *d_order, int n_utt, void *stream);
 int sea_hw64_frontend(const float *in, long L, float *hout, float *hev, float *acf_hc, float *acf_ev, float *cross_hc,
                       float *cross_ev, int *pitch, float *pratio, float *mark);
+/* createIBM():79-87 on the same bank: initGroup and pitchDtm as sea_hw25_pitch_* has them (see there for the functions, the
+ * outputs' meaning, d_stages' layout, d_scratch, d_order and the status word), at 64 channels, 201 delays and a hop of 160
+ * (csrc/hw64_pitch_kernel.hip).  Parity: bit for bit, every stage, against the reference's own functions
+ * compiled on a CPU against resyth_64sub_IBM/cpp/HuWang.h (tests/golden/hw64_pitch_golden.npz).
+ * Inputs are the rows sea_hw64_correlogram_batch wrote and are not modified: d_acf_hc [rows][64][201], d_pratio_in, d_mark_in
+ * [rows][64]; utterance u has lengths[u] / 160 rows from d_row_offsets[u].  There is NO d_cross_hc argument: the 25-band call
+ * reads it only because leftDevelope / rightDevelope bound their chan_mark test and their number2 loop by the literal 40, which
+ * on a bank of 25 reaches fifteen ghost channels in the arrays behind the frame's acf.  On this bank of 64 the same literal
+ * stays inside the frame: channels 40..63 never enter chan_mark (so never chan_mark2, number or the Developes' sumAuto) and are
+ * not counted in number2.  That is reproduced; a port with 64 in place of 40 computes other pitches.
+ * Outputs: d_pitch [rows] ints (0 = unvoiced, else 32..200), d_grp and d_pratio [rows][64] floats, d_status [n_utt] ints with
+ * the segment count in bits 0..15, SEA_HW25_TOO_MANY_SEGMENTS and SEA_HW25_CHANMARK_UNSET.  d_stages (optional): utterance u's
+ * block of SEA_HW64_STAGE_WORDS words per row at word d_row_offsets[u] * SEA_HW64_STAGE_WORDS, [5][rows_u] ints then
+ * [2][rows_u][64] floats, laid out as SEA_HW25_STAGE_WORDS.  d_scratch must hold sea_hw64_pitch_scratch_bytes (total_rows,
+ * n_utt) bytes.  Null pointers (other than d_stages and d_order) and an output that is an input or another output are refused
+ * before anything is launched; n_utt <= 0 returns 0; the lengths stay on the device, nothing synchronises with the host, every
+ * launch is on `stream`.
+ * The reference's undefined cases are defined as for sea_hw25_pitch_batch: no segment (always so with fewer than 3 rows):
+ * segment count 0 and all outputs 0; more than 400 segments: SEA_HW25_TOO_MANY_SEGMENTS, the count, all outputs 0; chan_mark
+ * read before it is set: it starts at zeros and SEA_HW25_CHANMARK_UNSET is set.  The fourth case there (ghost channels past
+ * the arrays on an utterance's last frame) does not exist on this bank.
+ * sea_hw64_pitch_waves_per_utterance: how many waves the two frame-walking kernels (the maximum and the findPitch / timeCrn
+ * kernel) give every utterance of a batch of n_utt on the current device (wave g takes the frames g, g + G, ..); 0 on error.
+ * sea_hw64_pitch: one utterance from host memory; runs the front half itself; pitch [L / 160], grp and pratio [L / 160][64],
+ * status [1]; pitch, grp and pratio may be null. */
+enum { SEA_HW64_STAGE_WORDS = 133 /* per row: 5 ints and 2 x 64 floats */ };
+long long sea_hw64_pitch_scratch_bytes(long long total_rows, int n_utt);
+int sea_hw64_pitch_waves_per_utterance(int n_utt);
+int sea_hw64_pitch_batch(const float *d_acf_hc, const float *d_pratio_in, const float *d_mark_in, const long long *d_lengths,
+                         const long long *d_row_offsets, int *d_pitch, float *d_grp, float *d_pratio, int *d_status, void *d_stages,
+                         void *d_scratch, const int *d_order, int n_utt, void *stream);
+int sea_hw64_pitch(const float *x, long L, int *pitch, float *grp, float *pratio, int *status);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

@@ -117,6 +117,10 @@ PROTOTYPES = {
     "sea_hw64_correlogram_batch": (_i, [_vp] * 14 + [_i, _vp]),
     "sea_hw64_frontend_batch": (_i, [_vp] * 15 + [_i, _vp]),
     "sea_hw64_frontend": (_i, [_vp, _l] + [_vp] * 9),
+    "sea_hw64_pitch_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw64_pitch_waves_per_utterance": (_i, [_i]),
+    "sea_hw64_pitch_batch": (_i, [_vp] * 12 + [_i, _vp]),
+    "sea_hw64_pitch": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -67,6 +67,22 @@ constexpr unsigned kHw25ChanBits = (1u << SEA_HW25_NCHAN) - 1u;    /* the channe
 /* between a write by one lane and a later read by another lane of the same wave */
 __device__ __forceinline__ void lanes_fence() { __threadfence(); }
 
+/* what the pitch tracking of both banks shares (hw25_pitch_kernel.hip, hw64_pitch_kernel.hip): the maximum from mvalue = 0
+ * (findPitch, the Developes) out of the stored maximum from -inf */
+__device__ __forceinline__ float mvalue_of(float mraw) { return mraw > 0.0f ? mraw : 0.0f; }
+
+/* pitchCrn:887-899 */
+__device__ __forceinline__ bool pitch_crn(int d1, int d2)
+{
+    float lowerP = (float)(0.8 * (double)(float)d1);
+    float upperP = (float)(1.2 * (double)(float)d1);
+    if (d1 > d2)
+        upperP = (float)(1.2 * (double)(float)d2);
+    else
+        lowerP = (float)(0.8 * (double)(float)d2);
+    return ((float)d1 > lowerP) && ((float)d1 < upperP) && ((float)d2 > lowerP) && ((float)d2 < upperP);
+}
+
 /* One wave per utterance.  lab [F][25]: the unit's own index where it is marked, kHw25None elsewhere.  On return every marked
  * unit holds the smallest unit index of its 4-connected component.  Lane = channel; a frame takes the label of the frame
  * before it in sweep direction (carried in registers), then every run of marked channels takes its minimum.  Forward and

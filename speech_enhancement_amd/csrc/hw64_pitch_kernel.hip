@@ -1,30 +1,34 @@
 /*
- * hw25_pitch_kernel.hip -- the Hu-Wang estimator's initial grouping and pitch tracking on the 25-channel 8 kHz bank, gfx950:
- * createIBM():79-87 of function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp, that is initGroup:639-702 (with
- * segmentation / search / relationship:466-637) and pitchDtm:795-824 (findPitch, sumAuto, pitchCrn, checkPitch, leftDevelope,
- * rightDevelope, linearEstimate, timeCrn, reGroup, relationship2).  A first form, not tuned.  DESIGN.md section 5.12.
+ * hw64_pitch_kernel.hip -- the Hu-Wang estimator's initial grouping and pitch tracking at 16 kHz on the 64-channel bank, gfx950:
+ * createIBM():79-87 of function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp at the constants of resyth_64sub_IBM/cpp/
+ * HuWang.h (NUMBER_CHANNEL 64, MAX_DELAY 201, MIN_DELAY 32, OFFSET 160), that is initGroup:639-702 (with segmentation / search /
+ * relationship:466-637) and pitchDtm:795-824.  The mapping is hw25_pitch_kernel.hip's; what the channel count changes is
+ * restated, not templated: a channel is a lane of the WHOLE wave, so ballots are 64-bit and nothing is masked to the channel
+ * lanes, the segmented minimum runs over 64 lanes, sumAuto deals its 169 delays in three passes.  A first form, not tuned.
+ * DESIGN.md section 5.17.
  *
- *   hw25_pitch_max_kernel      per (frame, channel) the maximum of acf[c][16..100]: findPitch, timeCrn and both Developes
- *                              recompute it, it never changes.  One wave per frame, lane = delay.
- *   hw25_pitch_segment_kernel  segmentation + initGroup, one wave per utterance.  A segment is a 4-connected component of
- *                              the marks that holds a unit whose two time neighbours are marked; the reference lists them in
- *                              the scan order of their first such unit.  Components: minimum-label propagation, lane =
- *                              channel, forward and backward over the frames until nothing changes.
- *   hw25_pitch_frame_kernel    findPitch and / or timeCrn, one wave per frame: lane = delay in sumAuto, lane = channel after
- *   hw25_pitch_regroup_kernel  reGroup (theta), one wave per utterance, lane = frame in relationship2
- *   hw25_pitch_track_kernel    checkPitch, leftDevelope, rightDevelope, linearEstimate: serial over frames, one wave per
+ *   hw64_pitch_max_kernel      per (frame, channel) the maximum of acf[c][32..200].  One wave per frame, lane = delay.
+ *   hw64_pitch_segment_kernel  segmentation + initGroup, one wave per utterance, lane = channel in the label propagation
+ *   hw64_pitch_frame_kernel    findPitch and / or timeCrn, one wave per frame: lane = delay in sumAuto, lane = channel after
+ *   hw64_pitch_regroup_kernel  reGroup (theta), one wave per utterance, lane = frame in relationship2
+ *   hw64_pitch_track_kernel    checkPitch, leftDevelope, rightDevelope, linearEstimate: serial over frames, one wave per
  *                              utterance, lane = delay inside sumAuto, lane = channel in the unit tests
  *
- * Every expression keeps the type the reference's C++ gives it: pRatio > THETAP in initGroup and acf / mvalue > THETAP are
- * float values against the double 0.95; reGroup's theta is a float; pitchCrn's bounds and the Developes' k1 / k2 are double
- * expressions stored in float variables; x / 0 is IEEE.  Sums run over the marked channels in the order 0..24, maxima are first
- * strict maxima.  No kernel modifies acf, cross, pratio_in or mark_in.
+ * FORTY CHANNELS.  leftDevelope and rightDevelope say `if (chan<40)` where they compute chan_mark and `for(chan=0; chan<40;
+ * chan++)` where they count number2 (HuWang.cpp:969, 1009, 1047, 1087).  On this bank these are real channels: 40..63 never
+ * enter chan_mark, hence never chan_mark2, number or the sumAuto inside a Develope, and are not counted in number2.  kDevelope
+ * is that bound; it is applied at those four places (two in develope(), which is both functions) and nowhere else.  There are
+ * no ghost channels here, so nothing reads the cross array.
  *
- * Scratch: utterance u's block of SEA_HW25_SCRATCH_WORDS words per row at a.rowscr + row_offsets[u] * SEA_HW25_SCRATCH_WORDS
- * (lab, key: [F][25] ints; mraw: [F][25] floats; buf: [F] ints, sumAuto's result per frame from findPitch, then checkPitch's
- * buffer), and a.segse: [n_utt][2][400] ints.
- * Memory that one lane writes and another lane of the same wave reads later is separated by a fence; inside a serial loop
- * the carried values stay in registers.
+ * Every expression keeps the type the reference's C++ gives it, as in hw25_pitch_kernel.hip: pRatio > THETAP in initGroup and
+ * acf / mvalue > THETAP are float values against the double 0.95; reGroup's theta is a float; pitchCrn's bounds and the
+ * Developes' k1 / k2 are double expressions stored in float variables, clamped at 32 and 200; x / 0 is IEEE.  Sums run over the
+ * marked channels in the order 0..63, maxima are first strict maxima.  No kernel modifies acf, pratio_in or mark_in.
+ *
+ * Scratch: utterance u's block of SEA_HW64_SCRATCH_WORDS words per row at a.rowscr + row_offsets[u] * SEA_HW64_SCRATCH_WORDS
+ * (lab, key: [F][64] ints; mraw: [F][64] floats; buf: [F] ints), and a.segse: [n_utt][2][400] ints.  Memory that one lane
+ * writes and another lane of the same wave reads later is separated by a fence; inside a serial loop the carried values stay
+ * in registers.
  */
 #include "../../include/sea_mi355x.h"
 #include "hw25_device.h"
@@ -35,16 +39,20 @@ namespace sea {
 
 namespace {
 
-constexpr int kCh = SEA_HW25_NCHAN, kDel = SEA_HW25_DELAYS, kHop = SEA_HW25_HOP, kMinDel = SEA_HW25_MINDELAY;
+constexpr int kCh = SEA_HW64_NCHAN, kDel = SEA_HW64_DELAYS, kHop = SEA_HW64_HOP, kMinDel = SEA_HW64_MINDELAY;
 constexpr int kRow = kCh * kDel;
 constexpr int kMaxSeg = SEA_HW25_MAX_SEGMENTS;
 constexpr double kThetaP = 0.95;
+constexpr unsigned long long kDevelope = (1ull << 40) - 1ull; /* the Developes' `chan<40` */
+static_assert(kCh == 64, "a channel is a lane of the whole wave");
 
-__device__ __forceinline__ int popc64(unsigned long long m) { return __popcll(m); }
+using ChanSet = unsigned long long; /* channel c is bit c */
 
-/* sumAuto:862-885 on one frame's acf [25][101]: the channels of `mask` in order per delay (lane = delay), the first strict
- * maximum over [lo, hi) from mvalue = 0; every lane returns it */
-__device__ __forceinline__ int sum_auto(const float *acf, unsigned mask, int lo, int hi, int lane)
+__device__ __forceinline__ int popc64(ChanSet m) { return __popcll(m); }
+
+/* sumAuto:862-885 on one frame's acf [64][201]: the channels of `mask` in order per delay (lane = delay), the first strict
+ * maximum over [lo, hi) from mvalue = 0; every lane returns it.  mask is the same in every lane. */
+__device__ __forceinline__ int sum_auto(const float *acf, ChanSet mask, int lo, int hi, int lane)
 {
     float bv = 0.0f;
     int bd = 0;
@@ -52,8 +60,7 @@ __device__ __forceinline__ int sum_auto(const float *acf, unsigned mask, int lo,
         const int d = d0 + lane;
         if (d < hi) {
             float sum = 0.0f;
-            for (int c = 0; c < kCh; ++c)
-                if ((mask >> c) & 1u) sum += acf[c * kDel + d];
+            for (ChanSet m = mask; m; m &= m - 1ull) sum += acf[(__ffsll((long long)m) - 1) * kDel + d];
             if (sum > bv) {
                 bv = sum;
                 bd = d;
@@ -73,14 +80,10 @@ __device__ __forceinline__ int sum_auto(const float *acf, unsigned mask, int lo,
 }
 
 /* the channels with Grp > 0 and (acf[c][delay] / mvalue) > THETAP: the float quotient against the double constant */
-__device__ __forceinline__ unsigned ratio_mask(const float *acf, const float *mraw, const float *grp, int delay, int lane)
+__device__ __forceinline__ ChanSet ratio_mask(const float *acf, const float *mraw, const float *grp, int delay, int lane)
 {
-    bool ok = false;
-    if (lane < kCh) {
-        const float q = acf[lane * kDel + delay] / mvalue_of(mraw[lane]);
-        ok = grp[lane] > 0.0f && (double)q > kThetaP;
-    }
-    return (unsigned)__ballot(ok) & kHw25ChanBits;
+    const float q = acf[lane * kDel + delay] / mvalue_of(mraw[lane]);
+    return __ballot(grp[lane] > 0.0f && (double)q > kThetaP);
 }
 
 /* count[0] / count[1] of segment `id` in one frame: its units with pRatio above / not above the threshold */
@@ -100,17 +103,17 @@ __device__ __forceinline__ void seg_votes(const int *lab, const float *pr, int i
 struct Utt {
     int u, nfr;
     long long row0;
-    int *lab, *key, *buf; /* the utterance's scratch block: lab | key | mraw [F][25], buf [F] */
+    int *lab, *key, *buf; /* the utterance's scratch block: lab | key | mraw [F][64], buf [F] */
     float *mraw;
 };
-__device__ __forceinline__ Utt utterance(const Hw25PitchArgs &a)
+__device__ __forceinline__ Utt utterance(const Hw64PitchArgs &a)
 {
     Utt t;
     t.u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
     const long long L = a.lengths[t.u];
     t.nfr = L > 0 ? (int)(L / kHop) : 0;
     t.row0 = a.row_offsets[t.u];
-    int *block = a.rowscr + t.row0 * SEA_HW25_SCRATCH_WORDS;
+    int *block = a.rowscr + t.row0 * SEA_HW64_SCRATCH_WORDS;
     const long long plane = (long long)t.nfr * kCh;
     t.lab = block;
     t.key = block + plane;
@@ -119,47 +122,67 @@ __device__ __forceinline__ Utt utterance(const Hw25PitchArgs &a)
     return t;
 }
 
-/* The number2 loops of both Developes (:1009, :1087) run over FORTY channels on this bank of 25.  The reference's arrays are
- * contiguous, so its channel 25 + j of frame f is the flat element (25 + j) * 101 + delay of [acf | cross | pRatio | acf of
- * frame f + 1] with the mark of channel j of frame f + 1; that is reproduced.  On the last frame the fifteen lie past the
- * arrays and are not counted.  Lane = j; returns how many of them pass the test. */
-__device__ __forceinline__ int ghost_count(const Hw25PitchArgs &a, const Utt &t, int frame, int delay, int lane)
+/* utterance u's stage block: [5][F] ints (Pitch), then [2][F][64] floats (Grp) */
+__device__ __forceinline__ int *stage_pitch(const Hw64PitchArgs &a, const Utt &t, int k)
 {
-    if (frame + 1 >= t.nfr) return 0;
-    const long long row = t.row0 + frame;
-    const float *cross = a.cross + row * kCh, *pr = a.pratio + row * kCh, *next = a.acf + (row + 1) * kRow;
-    auto flat = [&](int idx) { /* idx >= 25 * 101 */
-        return idx < kRow + kCh ? cross[idx - kRow] : (idx < kRow + 2 * kCh ? pr[idx - kRow - kCh] : next[idx - kRow - 2 * kCh]);
-    };
-    bool ok = false;
-    if (lane < 40 - kCh && a.grp[(row + 1) * kCh + lane] > 0.0f) {
-        const int base = (kCh + lane) * kDel;
-        float mvalue = 0.0f;
-        for (int d = kMinDel; d < kDel; ++d) {
-            const float v = flat(base + d);
-            if (v > mvalue) mvalue = v;
-        }
-        ok = (double)(flat(base + delay) / mvalue) > kThetaP;
-    }
-    return popc64(__ballot(ok));
+    return a.stages + t.row0 * SEA_HW64_STAGE_WORDS + (long long)k * t.nfr;
 }
-
-/* utterance u's stage block: [5][F] ints (Pitch), then [2][F][25] floats (Grp) */
-__device__ __forceinline__ int *stage_pitch(const Hw25PitchArgs &a, const Utt &t, int k)
+__device__ __forceinline__ float *stage_grp(const Hw64PitchArgs &a, const Utt &t, int k)
 {
-    return a.stages + t.row0 * SEA_HW25_STAGE_WORDS + (long long)k * t.nfr;
-}
-__device__ __forceinline__ float *stage_grp(const Hw25PitchArgs &a, const Utt &t, int k)
-{
-    return reinterpret_cast<float *>(a.stages + t.row0 * SEA_HW25_STAGE_WORDS + 5LL * t.nfr) + (long long)k * t.nfr * kCh;
+    return reinterpret_cast<float *>(a.stages + t.row0 * SEA_HW64_STAGE_WORDS + 5LL * t.nfr) + (long long)k * t.nfr * kCh;
 }
 
 /* segment count 0 or a set TOO_MANY bit: the segment kernel wrote zeros, the later kernels leave the utterance alone */
 __device__ __forceinline__ bool inactive(int status) { return (status & 0xffff) == 0 || (status & SEA_HW25_TOO_MANY_SEGMENTS); }
 
+/* hw25_label_components (hw25_device.h) with a channel in every lane.  lab [F][64]: the unit's own index where it is marked,
+ * kHw25None elsewhere.  On return every marked unit holds the smallest unit index of its 4-connected component.  A frame
+ * takes the label of the frame before it in sweep direction (carried in registers), then every run of marked channels takes
+ * its minimum: a prefix minimum over the 64 lanes that stops at the run's start, read back from the run's end.  Forward and
+ * backward sweeps until neither changes anything.  The caller fences before and after. */
+__device__ __forceinline__ void label_components(int *lab, int F, int lane)
+{
+    bool again = true;
+    while (again) {
+        bool changed = false;
+        for (int dir = 0; dir < 2; ++dir) {
+            int carry = kHw25None;
+            for (int k = 0; k < F; ++k) {
+                const int f = dir ? F - 1 - k : k;
+                const int old = lab[f * kCh + lane];
+                int v = old;
+                if (v != kHw25None && carry < v) v = carry;
+                const ChanSet m = __ballot(v != kHw25None);
+                /* the run [start, end] of marked channels around this lane */
+                const ChanSet below = ~m & ((1ull << lane) - 1ull);
+                const int start = below ? 64 - __clzll((long long)below) : 0;
+                const ChanSet above = lane < 63 ? (~m >> (lane + 1)) : 0ull;
+                const int end = above ? lane + (__ffsll((long long)above) - 1) : 63;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int o = __shfl_up(v, d);
+                    if (lane - d >= start && o < v) v = o;
+                }
+                const int r = __shfl(v, end);
+                if (old != kHw25None) {
+                    v = r;
+                    if (v != old) {
+                        lab[f * kCh + lane] = v;
+                        changed = true;
+                    }
+                } else {
+                    v = kHw25None;
+                }
+                carry = v;
+            }
+        }
+        again = __any(changed);
+    }
+}
+
 } // namespace
 
-__global__ __launch_bounds__(64) void hw25_pitch_max_kernel(Hw25PitchArgs a)
+__global__ __launch_bounds__(64) void hw64_pitch_max_kernel(Hw64PitchArgs a)
 {
     const int lane = threadIdx.x;
     const Utt t = utterance(a);
@@ -168,12 +191,14 @@ __global__ __launch_bounds__(64) void hw25_pitch_max_kernel(Hw25PitchArgs a)
         const float *acf = a.acf + row * kRow;
         float keep = 0.0f;
         for (int c = 0; c < kCh; ++c) {
+            const float *p = acf + c * kDel + kMinDel + lane;
             float m = -INFINITY;
-            const float v0 = acf[c * kDel + kMinDel + lane]; /* delays 16..79 */
+            const float v0 = p[0], v1 = p[64]; /* delays 32..95, 96..159 */
             if (v0 > m) m = v0;
-            if (kMinDel + 64 + lane < kDel) { /* delays 80..100 */
-                const float v1 = acf[c * kDel + kMinDel + 64 + lane];
-                if (v1 > m) m = v1;
+            if (v1 > m) m = v1;
+            if (kMinDel + 128 + lane < kDel) { /* delays 160..200 */
+                const float v2 = p[128];
+                if (v2 > m) m = v2;
             }
 #pragma unroll
             for (int off = 32; off >= 1; off >>= 1) {
@@ -182,11 +207,11 @@ __global__ __launch_bounds__(64) void hw25_pitch_max_kernel(Hw25PitchArgs a)
             }
             if (lane == c) keep = m;
         }
-        if (lane < kCh) t.mraw[frame * kCh + lane] = keep;
+        t.mraw[frame * kCh + lane] = keep;
     }
 }
 
-__global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
+__global__ __launch_bounds__(64) void hw64_pitch_segment_kernel(Hw64PitchArgs a)
 {
     __shared__ int sS[kMaxSeg], sE[kMaxSeg], sRel[kMaxSeg];
     const int lane = threadIdx.x;
@@ -202,8 +227,8 @@ __global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
             key[i] = kHw25None;
         }
         lanes_fence();
-        /* ---- components: every marked unit ends with the smallest unit index of its component (hw25_device.h) ---- */
-        hw25_label_components(lab, F, lane);
+        /* ---- components: every marked unit ends with the smallest unit index of its component ---- */
+        label_components(lab, F, lane);
         lanes_fence();
         /* ---- per component its first seed in scan order ---- */
         for (int i = lane; i < ncell; i += 64) {
@@ -214,17 +239,14 @@ __global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
         /* ---- the segment list: components in the order of their first seeds; key[root] becomes -(index + 1) ---- */
         int count = 0;
         for (int base = 0; base < ncell; base += 64) {
-            const int i = base + lane;
+            const int i = base + lane, f = i / kCh; /* ncell is a multiple of 64: i < ncell */
             bool first = false;
             int root = 0;
-            if (i < ncell) {
-                const int f = i / kCh;
-                if (f >= 1 && f <= F - 2 && mark[i] != 0.0f && mark[i - kCh] != 0.0f && mark[i + kCh] != 0.0f) {
-                    root = lab[i];
-                    first = key[root] == i;
-                }
+            if (f >= 1 && f <= F - 2 && mark[i] != 0.0f && mark[i - kCh] != 0.0f && mark[i + kCh] != 0.0f) {
+                root = lab[i];
+                first = key[root] == i;
             }
-            const unsigned long long bal = __ballot(first);
+            const ChanSet bal = __ballot(first);
             const int idx = count + popc64(bal & ((1ull << lane) - 1ull));
             if (first && idx < kMaxSeg) {
                 key[root] = -(idx + 1);
@@ -252,7 +274,7 @@ __global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
         }
         for (int f = lane; f < F; f += 64) a.pitch[t.row0 + f] = 0;
         if (a.stages)
-            for (int i = lane; i < F * SEA_HW25_STAGE_WORDS; i += 64) a.stages[t.row0 * SEA_HW25_STAGE_WORDS + i] = 0;
+            for (int i = lane; i < F * SEA_HW64_STAGE_WORDS; i += 64) a.stages[t.row0 * SEA_HW64_STAGE_WORDS + i] = 0;
         if (lane == 0) a.status[t.u] = nseg | flags;
         return;
     }
@@ -319,7 +341,7 @@ __global__ __launch_bounds__(64) void hw25_pitch_segment_kernel(Hw25PitchArgs a)
     if (lane == 0) a.status[t.u] = nseg;
 }
 
-__global__ __launch_bounds__(64) void hw25_pitch_frame_kernel(Hw25PitchArgs a)
+__global__ __launch_bounds__(64) void hw64_pitch_frame_kernel(Hw64PitchArgs a)
 {
     const int lane = threadIdx.x;
     const Utt t = utterance(a);
@@ -332,9 +354,9 @@ __global__ __launch_bounds__(64) void hw25_pitch_frame_kernel(Hw25PitchArgs a)
         if (find) {
             /* findPitch:836-858; with Pitch = 0 the reference divides acf[chan][0], and zeroes a zero */
             const float *grp = a.grp + row * kCh;
-            const unsigned gm = (unsigned)__ballot(lane < kCh && grp[lane] > 0.0f) & kHw25ChanBits;
+            const ChanSet gm = __ballot(grp[lane] > 0.0f);
             P = sum_auto(acf, gm, kMinDel, kDel, lane);
-            const int n1 = __popc(gm), n2 = __popc(ratio_mask(acf, mraw, grp, P, lane));
+            const int n1 = popc64(gm), n2 = popc64(ratio_mask(acf, mraw, grp, P, lane));
             /* lFrame / rFrame (:838-839) come from sumAuto's result BEFORE the vote zeroes it: kept for the track kernel */
             if (lane == 0) t.buf[frame] = P;
             if (n2 * 2 <= n1) P = 0;
@@ -345,7 +367,7 @@ __global__ __launch_bounds__(64) void hw25_pitch_frame_kernel(Hw25PitchArgs a)
         } else {
             P = a.pitch[row];
         }
-        if (crn && lane < kCh) {
+        if (crn) {
             /* timeCrn:771-790: mp starts at acf[chan][Pitch] */
             float out = 0.0f;
             if (P > 0) {
@@ -358,7 +380,7 @@ __global__ __launch_bounds__(64) void hw25_pitch_frame_kernel(Hw25PitchArgs a)
     }
 }
 
-__global__ __launch_bounds__(64) void hw25_pitch_regroup_kernel(Hw25PitchArgs a)
+__global__ __launch_bounds__(64) void hw64_pitch_regroup_kernel(Hw64PitchArgs a)
 {
     __shared__ int sRel[kMaxSeg];
     const int lane = threadIdx.x;
@@ -395,21 +417,22 @@ __global__ __launch_bounds__(64) void hw25_pitch_regroup_kernel(Hw25PitchArgs a)
 namespace {
 
 /* leftDevelope:954-1030 (step -1) / rightDevelope:1032-1108 (step +1) from `frame` to `last`.  chan_mark lives in a register
- * as channel bits; it starts at zeros, and reading it before it was computed is reported.  The pitch and buffer of the frame
- * just handled are carried to the next step in registers. */
-__device__ __forceinline__ bool develope(const Hw25PitchArgs &a, const Utt &t, int frame, int last, int step, int lane)
+ * pair as a channel set; it starts at zeros, and reading it before it was computed is reported.  The pitch and buffer of the
+ * frame just handled are carried to the next step in registers. */
+__device__ __forceinline__ bool develope(const Hw64PitchArgs &a, const Utt &t, int frame, int last, int step, int lane)
 {
     const bool left = step < 0;
     if (left ? frame < last : frame > last) return false;
     int *pitch = a.pitch + t.row0, *buf = t.buf;
     const float *grp0 = a.grp + t.row0 * kCh, *acf0 = a.acf + t.row0 * kRow, *mraw0 = t.mraw;
-    unsigned chan_mark = 0;
+    ChanSet chan_mark = 0;
     bool computed = false, unset = false;
     int pn = pitch[frame - step], bn = buf[frame - step];
     for (; left ? frame >= last : frame <= last; frame += step) {
         const int nb = frame - step;
         if (pn) {
-            chan_mark = ratio_mask(acf0 + (long long)nb * kRow, mraw0 + nb * kCh, grp0 + nb * kCh, pn, lane);
+            /* :966-979 / :1044-1057: chan_mark[chan] = 0 for every channel, the test only `if (chan<40)` */
+            chan_mark = ratio_mask(acf0 + (long long)nb * kRow, mraw0 + nb * kCh, grp0 + nb * kCh, pn, lane) & kDevelope;
             computed = true;
         }
         int pf = pitch[frame], bf = buf[frame];
@@ -417,10 +440,10 @@ __device__ __forceinline__ bool develope(const Hw25PitchArgs &a, const Utt &t, i
             pf = bf;
         } else {
             unset = unset || !computed;
-            const float g = lane < kCh ? grp0[frame * kCh + lane] : 0.0f;
-            const unsigned own = (unsigned)__ballot(left ? g > 0.0f : g != 0.0f) & kHw25ChanBits;
-            const unsigned mark2 = own & chan_mark;
-            const int number = __popc(mark2);
+            const float g = grp0[frame * kCh + lane];
+            const ChanSet own = __ballot(left ? g > 0.0f : g != 0.0f); /* :986 / :1064: all 64 channels */
+            const ChanSet mark2 = own & chan_mark;
+            const int number = popc64(mark2);
             if (number) {
                 float k1 = (float)(0.65 * (double)(float)(bn + 1) - 1);
                 if (k1 < (float)kMinDel) k1 = (float)kMinDel;
@@ -430,8 +453,8 @@ __device__ __forceinline__ bool develope(const Hw25PitchArgs &a, const Utt &t, i
                 pf = sum_auto(acf, mark2, (int)k1, (int)k2, lane);
                 bool keep = false;
                 if (pitch_crn(pf, bn)) {
-                    const int number2 = __popc(ratio_mask(acf, mraw0 + frame * kCh, grp0 + frame * kCh, pf, lane)) +
-                                        ghost_count(a, t, frame, pf, lane);
+                    /* :1009 / :1087: `for(chan=0; chan<40; chan++)` */
+                    const int number2 = popc64(ratio_mask(acf, mraw0 + frame * kCh, grp0 + frame * kCh, pf, lane) & kDevelope);
                     keep = number2 * 2 > number;
                 }
                 if (keep) {
@@ -456,7 +479,7 @@ __device__ __forceinline__ bool develope(const Hw25PitchArgs &a, const Utt &t, i
 
 } // namespace
 
-__global__ __launch_bounds__(64) void hw25_pitch_track_kernel(Hw25PitchArgs a)
+__global__ __launch_bounds__(64) void hw64_pitch_track_kernel(Hw64PitchArgs a)
 {
     const int lane = threadIdx.x;
     const Utt t = utterance(a);

@@ -407,6 +407,33 @@ __global__ void hw25_pitch_frame_kernel(Hw25PitchArgs a);   /* grid (n_utt, G) x
 __global__ void hw25_pitch_regroup_kernel(Hw25PitchArgs a); /* grid n_utt x 64 */
 __global__ void hw25_pitch_track_kernel(Hw25PitchArgs a);   /* grid n_utt x 64 */
 
+/* The same stage at 16 kHz on the 64-channel bank (hw64_pitch_kernel.hip).  Hw25PitchArgs's layout at 64 channels and 201
+ * delays, without cross, which nothing reads on this bank: acf [rows][64][201], pratio_in, mark_in [rows][64] only read; pitch
+ * [rows], grp and pratio [rows][64], status [n_utt] written; utterance u has lengths[u] / 160 rows from row_offsets[u].  stages
+ * (or null): SEA_HW64_STAGE_WORDS words per row, [5][F] ints then [2][F][64] floats.  Scratch: rowscr, SEA_HW64_SCRATCH_WORDS
+ * words per row; segse [n_utt][2][400] ints. */
+struct Hw64PitchArgs {
+    const float *acf, *pratio_in, *mark_in;
+    const long long *lengths;
+    const long long *row_offsets;
+    int *pitch;
+    float *grp, *pratio;
+    int *status;
+    int *stages;
+    int *rowscr, *segse;
+    const int *order;
+    int n_utt;
+    int mode;    /* frame kernel: SEA_HW25_FRAME_FIND | SEA_HW25_FRAME_TIMECRN */
+    int stage;   /* as Hw25PitchArgs */
+    float theta; /* regroup kernel */
+};
+#define SEA_HW64_SCRATCH_WORDS 193 /* per row: lab, key, mraw [64] and buf */
+__global__ void hw64_pitch_max_kernel(Hw64PitchArgs a);     /* grid (n_utt, G) x 64: wave (u, g) takes frames g, g + G, ... */
+__global__ void hw64_pitch_segment_kernel(Hw64PitchArgs a); /* grid n_utt x 64 */
+__global__ void hw64_pitch_frame_kernel(Hw64PitchArgs a);   /* grid (n_utt, G) x 64 */
+__global__ void hw64_pitch_regroup_kernel(Hw64PitchArgs a); /* grid n_utt x 64 */
+__global__ void hw64_pitch_track_kernel(Hw64PitchArgs a);   /* grid n_utt x 64 */
+
 /* The Hu-Wang estimator's AM labels (hw25_am_kernel.hip): computeAM:1146-1317.  gout, ampatt, am: hout's layout; pitch [rows]
  * ints; amcrn, ratio, seng [rows][25] (ratio, seng or null).  ampatt and am are never null here: the caller's buffers or
  * scratch.  fa / fb: the FFT's two complex buffers, utterance u's [chunk][2 * pitch] block at offsets[u] * chunk * 2 (2^N is at

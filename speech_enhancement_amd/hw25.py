@@ -13,9 +13,10 @@ from .engine import _dptr, _np_ptr, _row_offsets, _stream_ptr, _torch
 
 HW25_NCHAN, HW25_DELAYS, HW25_HOP = 25, 101, 80
 # what the front half's wrappers need to know of a bank (hw64.py has the 64-channel one): its sizes and its calls' names;
-# gout_fn: the periphery call that also returns gOut, where the bank has one of its own (None: periphery_fn takes a null)
+# gout_fn: the periphery call that also returns gOut, where the bank has one of its own (None: periphery_fn takes a null);
+# pitch_reads_cross: whether the bank's pitch call takes the front half's cross_hc (hw64.py says why the 64-channel one does not)
 _BANK25 = SimpleNamespace(name="hw25", nchan=HW25_NCHAN, delays=HW25_DELAYS, hop=HW25_HOP, taps=91,
-                          gout_fn="sea_hw25_periphery_gout_batch", scratch_fn="sea_hw25_scratch_bytes")
+                          gout_fn="sea_hw25_periphery_gout_batch", scratch_fn="sea_hw25_scratch_bytes", pitch_reads_cross=True)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -77,14 +78,14 @@ class _Hw25Rows:
         return t[off * nch:off * nch + nch * pitch].cpu().numpy().reshape(nch, pitch)[:, :L]
 
 
-def _hw25_host(fn, x, keys, *args, status=True):
+def _hw25_host(fn, x, keys, *args, status=True, bank=_BANK25):
     """The one body of the forms that take one utterance from host memory: x as contiguous float32, the zeroed outputs named
-    in keys (audio [L], pitch int32 [F], every other [F][25]), the call fn (x, L, *args, *outputs[, status]) -> the outputs
-    as a dict, with the status word where the call has one."""
+    in keys (audio [L], pitch int32 [F], every other [F][25], the bank's channels), the call fn (x, L, *args, *outputs[, status])
+    -> the outputs as a dict, with the status word where the call has one."""
     x = np.ascontiguousarray(x, dtype=np.float32)
-    L, F = x.size, x.size // HW25_HOP
+    L, F = x.size, x.size // bank.hop
     shape = dict(audio=L, pitch=F)
-    r = {k: np.zeros(shape.get(k, (F, HW25_NCHAN)), np.int32 if k == "pitch" else np.float32) for k in keys}
+    r = {k: np.zeros(shape.get(k, (F, bank.nchan)), np.int32 if k == "pitch" else np.float32) for k in keys}
     word = np.zeros(1, np.int32)
     rc = getattr(_lib.load(), fn)(_np_ptr(x), L, *args, *[_np_ptr(r[k]) for k in keys], *([_np_ptr(word)] if status else []))
     _lib.check(rc, fn)
@@ -243,6 +244,7 @@ class Hw25PitchResult(_Hw25Rows):
     [n_utt] (bits 0..15 the segment count, HW25_TOO_MANY_SEGMENTS, HW25_CHANMARK_UNSET), stages (int32 words, or None) and
     front, the Hw25Result they were computed from.  utterance(u) returns numpy arrays of one utterance, the stage arrays
     under HW25_PITCH_STAGES / HW25_GRP_STAGES when they were asked for."""
+    STAGE_WORDS = HW25_STAGE_WORDS
 
     def __init__(self, front, **kw):
         super().__init__(front=front, **kw)
@@ -251,36 +253,42 @@ class Hw25PitchResult(_Hw25Rows):
         out = dict(pitch=self._rows(u, self.pitch), grp=self._rows(u, self.grp), pratio=self._rows(u, self.pratio),
                    status=int(self.status[u]))
         if self.stages is not None:
-            block = self._rows(u, self.stages, HW25_STAGE_WORDS)
+            block = self._rows(u, self.stages, self.STAGE_WORDS)
             n = len(out["pitch"])
             for k, name in enumerate(HW25_PITCH_STAGES):
                 out[name] = block[k * n:(k + 1) * n].copy()
-            grp = block[5 * n:].view(np.float32).reshape(2, n, HW25_NCHAN)
+            grp = block[5 * n:].view(np.float32).reshape(2, n, self.NCHAN)
             for k, name in enumerate(HW25_GRP_STAGES):
                 out[name] = grp[k].copy()
         return out
 
 
-def hw25_pitch_batch(batch, stages=False, use_order=True):
-    """createIBM():41-87 for every utterance of the batch: the front half with its ACF output, then initGroup and pitchDtm, one
-    launch group on the current stream -> Hw25PitchResult.  stages: also keep Pitch / Grp after every step of pitchDtm."""
+def _bank_pitch(bank, front_result, result, batch, stages, use_order):
+    """the one body of the pitch wrappers of both banks: the front half with its ACF, then the bank's pitch call"""
     torch = _torch()
     lib = _lib.load()
-    front = hw25_frontend_batch(batch, want_acf=True, use_order=use_order)
+    front = _bank_front(bank, front_result, batch, True, use_order)
     dev = front.pitch.device
     n = front.pitch.shape[0]
     pitch = torch.zeros(n, dtype=torch.int32, device=dev)
-    grp = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
+    grp = torch.zeros((n, bank.nchan), dtype=torch.float32, device=dev)
     pratio = torch.zeros_like(grp)
     status = torch.zeros(max(batch.n_utt, 1), dtype=torch.int32, device=dev)
-    st = torch.zeros(n * HW25_STAGE_WORDS, dtype=torch.int32, device=dev) if stages else None
-    nbytes = int(lib.sea_hw25_pitch_scratch_bytes(n, int(batch.n_utt)))
+    st = torch.zeros(n * result.STAGE_WORDS, dtype=torch.int32, device=dev) if stages else None
+    nbytes = int(getattr(lib, f"sea_{bank.name}_pitch_scratch_bytes")(n, int(batch.n_utt)))
     scratch = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_pitch_batch(_dptr(front.acf_hc), _dptr(front.cross_hc), _dptr(front.pratio), _dptr(front.mark),
-                                  _dptr(batch.lengths), _dptr(front.row_offsets), _dptr(pitch), _dptr(grp), _dptr(pratio),
-                                  _dptr(status), _dptr(st), _dptr(scratch), _hw25_order(batch, use_order), batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_pitch_batch")
-    return Hw25PitchResult(front, pitch=pitch, grp=grp, pratio=pratio, status=status, stages=st)
+    fn = f"sea_{bank.name}_pitch_batch"
+    rc = getattr(lib, fn)(_dptr(front.acf_hc), *([_dptr(front.cross_hc)] if bank.pitch_reads_cross else []), _dptr(front.pratio),
+                          _dptr(front.mark), _dptr(batch.lengths), _dptr(front.row_offsets), _dptr(pitch), _dptr(grp), _dptr(pratio),
+                          _dptr(status), _dptr(st), _dptr(scratch), _hw25_order(batch, use_order), batch.n_utt, _stream_ptr())
+    _lib.check(rc, fn)
+    return result(front, pitch=pitch, grp=grp, pratio=pratio, status=status, stages=st)
+
+
+def hw25_pitch_batch(batch, stages=False, use_order=True):
+    """createIBM():41-87 for every utterance of the batch: the front half with its ACF output, then initGroup and pitchDtm, one
+    launch group on the current stream -> Hw25PitchResult.  stages: also keep Pitch / Grp after every step of pitchDtm."""
+    return _bank_pitch(_BANK25, Hw25Result, Hw25PitchResult, batch, stages, use_order)
 
 
 def hw25_pitch(x):

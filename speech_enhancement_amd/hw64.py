@@ -1,18 +1,25 @@
 """The front half of the Hu-Wang mask estimator createIBM() at 16 kHz on the 64-channel gammatone bank (HuWang.cpp:41-76 at the
 constants of resyth_64sub_IBM/cpp/HuWang.h; csrc/hw64_kernel.hip), over libsea_mi355x.so: AudiPeriph, lowPass, computeACF,
 crossCorr, globalPitch, timeCrn and the initial labelling.  The functions have the shapes and the result class of their
-hw25_* namesakes at 64 channels, 201 delays and a hop of 160 samples, and share their bodies (hw25.py).  initGroup onwards is
-not built at 16 kHz.
+hw25_* namesakes at 64 channels, 201 delays and a hop of 160 samples, and share their bodies (hw25.py).
+
+Then createIBM():79-87, initGroup and pitchDtm (csrc/hw64_pitch_kernel.hip): the pitch contour of the dominant voiced source and
+the units grouped with it or against it, hw64_pitch_batch / hw64_pitch.  The reference's leftDevelope and rightDevelope bound
+two loops by the literal 40; on this bank that keeps channels 40..63 out of their votes (the 25-band bank reads the cross
+array there instead, which is why only its call takes one).  computeAM onwards is not built at 16 kHz.
 
 torch is used for device memory and streams only (plumbing); all compute is in the HIP library.
 """
 from types import SimpleNamespace
 
 from . import _lib
-from .hw25 import Hw25Result, _bank_front, _bank_frontend_host, _bank_periphery, _bank_split, _bank_tables
+from .hw25 import (Hw25PitchResult, Hw25Result, _bank_front, _bank_frontend_host, _bank_periphery, _bank_pitch, _bank_split,
+                   _bank_tables, _hw25_host)
 
 HW64_NCHAN, HW64_DELAYS, HW64_HOP = 64, 201, 160
-_BANK64 = SimpleNamespace(name="hw64", nchan=HW64_NCHAN, delays=HW64_DELAYS, hop=HW64_HOP, taps=181, gout_fn=None, scratch_fn=None)
+HW64_STAGE_WORDS = 5 + 2 * HW64_NCHAN
+_BANK64 = SimpleNamespace(name="hw64", nchan=HW64_NCHAN, delays=HW64_DELAYS, hop=HW64_HOP, taps=181, gout_fn=None, scratch_fn=None,
+                          pitch_reads_cross=False)
 
 
 class Hw64Result(Hw25Result):
@@ -61,3 +68,31 @@ def hw64_frontend(x, want_acf=True):
 def hw64_workgroups_per_utterance(n_utt):
     """How many workgroups the correlogram launch gives every utterance of a batch of n_utt on the current device."""
     return int(_lib.load().sea_hw64_workgroups_per_utterance(int(n_utt)))
+
+
+class Hw64PitchResult(Hw25PitchResult):
+    """What hw64_pitch_batch() computed: Hw25PitchResult's tensors at 64 channels -- pitch int32 [rows] (0 = unvoiced, else the
+    delay 32..200 in samples at 16 kHz), grp [rows][64] in {-1, 0, +1}, pratio [rows][64], status int32 [n_utt] (bits 0..15 the
+    segment count, HW25_TOO_MANY_SEGMENTS, HW25_CHANMARK_UNSET), stages (HW64_STAGE_WORDS int32 words per row, or None) and
+    front, the Hw64Result they were computed from.  utterance(u): numpy arrays, the stage arrays under HW25_PITCH_STAGES /
+    HW25_GRP_STAGES when they were asked for."""
+    NCHAN = HW64_NCHAN
+    STAGE_WORDS = HW64_STAGE_WORDS
+
+
+def hw64_pitch_batch(batch, stages=False, use_order=True):
+    """createIBM():41-87 at 16 kHz for every utterance of the batch: the front half with its ACF output (51 456 B per row), then
+    initGroup and pitchDtm, one launch group on the current stream -> Hw64PitchResult.  stages: also keep Pitch / Grp after
+    every step of pitchDtm."""
+    return _bank_pitch(_BANK64, Hw64Result, Hw64PitchResult, batch, stages, use_order)
+
+
+def hw64_pitch(x):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale, 16 kHz) -> dict: pitch int32 [F], grp and
+    pratio [F][64], status; F = len(x) // 160."""
+    return _hw25_host("sea_hw64_pitch", x, ("pitch", "grp", "pratio"), bank=_BANK64)
+
+
+def hw64_pitch_waves_per_utterance(n_utt):
+    """How many waves the pitch stage's two frame-walking kernels give every utterance of a batch of n_utt on the current device."""
+    return int(_lib.load().sea_hw64_pitch_waves_per_utterance(int(n_utt)))

@@ -14,6 +14,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw25 --steps 5  # the Hu-Wang front half on the 25-channel bank: periphery, correlogram, launch group, opt-in
     python tools/bench_extra.py --what hw64 --steps 3  # the same front half at 16 kHz on the 64-channel bank, opt-in
     python tools/bench_extra.py --what hw25pitch --steps 3  # its initial grouping and pitch tracking beside the correlogram, opt-in
+    python tools/bench_extra.py --what hw64pitch --steps 3  # the same stage at 16 kHz on the 64-channel bank, opt-in
     python tools/bench_extra.py --what hw25ibm --steps 3  # its AM stage, final grouping and the whole estimator beside the other stages, opt-in
     python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
 """
@@ -1216,6 +1217,68 @@ def main():
                                                      "max": int((s_host & 0xFFFF).max())},
                           "utterances_flagged": {"too_many_segments": int((s_host >> 16 & 1).sum()), "chanmark_unset": int((s_host >> 17 & 1).sum())},
                           "voiced_frames": int((p_host > 0).sum())}), flush=True)
+        del hout, hev, acf_hc, stages, scratch
+
+    if "hw64pitch" in what:
+        # The same stage at 16 kHz on the 64-channel bank (sea_hw64_pitch_batch) on the --utts corpus batch taken as 16 kHz float
+        # samples, beside the front half that feeds it, in one process and with the scheme of --what hw25pitch.  The corpus runs
+        # WHOLE: its corrHc ACF is 51 456 B per row (about 21 GB at 1024 utterances) and hOut / hEv are 256 B per sample each; the
+        # total is checked against the free device memory first, and the run stops there if it does not fit.
+        lib = sea.load()
+        n = batch.n_utt
+        rows = np.asarray(batch.host_lengths, dtype=np.int64) // 160
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames = int(rows.sum())
+        scratch_bytes = int(lib.sea_hw64_pitch_scratch_bytes(frames, n))
+        need = 4 * (frames * (64 * 201 + 6 * 64 + 2 + 133) + 2 * int(batch.total) * 64 + int(batch.total)) + scratch_bytes
+        free, total = torch.cuda.mem_get_info()
+        assert need < 0.9 * free, f"hw64pitch: the corpus whole needs {need / 1e9:.1f} GB, {free / 1e9:.1f} GB of device memory are free"
+        x = batch.data.to(torch.float32)
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev = z(batch.total * 64), z(batch.total * 64)
+        cross_hc, cross_ev, pratio_in, mark, gpitch = z((frames, 64)), z((frames, 64)), z((frames, 64)), z((frames, 64)), z(frames, torch.int32)
+        acf_hc = z((frames, 64, 201))
+        pitch, grp, pratio, status = z(frames, torch.int32), z((frames, 64)), z((frames, 64)), z(n, torch.int32)
+        stages = z(frames * 133, torch.int32)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def front():
+            assert lib.sea_hw64_frontend_batch(P(x), P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(acf_hc), None, P(cross_hc),
+                                               P(cross_ev), P(gpitch), P(pratio_in), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def correlogram():
+            assert lib.sea_hw64_correlogram_batch(P(hout), P(hev), P(batch.offsets), P(batch.lengths), P(d_offs), P(acf_hc), None, P(cross_hc),
+                                                  P(cross_ev), P(gpitch), P(pratio_in), P(mark), None, P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def stage(with_stages=False):
+            assert lib.sea_hw64_pitch_batch(P(acf_hc), P(pratio_in), P(mark), P(batch.lengths), P(d_offs), P(pitch), P(grp), P(pratio),
+                                            P(status), P(stages) if with_stages else None, P(scratch), P(batch.order), n, st) == 0, lib.sea_last_error()
+        samples = int(np.sum(batch.host_lengths))
+        workload = (f"the {args.utts}-utterance corpus WHOLE as 16 kHz float samples: {samples} samples, {frames} frames of 160, "
+                    f"{frames * 64 * 201 * 4 / 1e9:.1f} GB of corrHc ACF, {need / 1e9:.1f} GB of device memory in all ({free / 1e9:.0f} GB were free), "
+                    f"{lib.sea_hw64_pitch_waves_per_utterance(n)} wave(s) per utterance in the frame kernels; median of {args.steps} steps after one warm-up")
+        results = []
+        for name, fn, kernels in (("front half with the corrHc ACF output", front, "sea::hw64_periphery_kernel + sea::hw64_lowpass_kernel + sea::hw64_correlogram_kernel"),
+                                  ("correlogram with the corrHc ACF output", correlogram, "sea::hw64_correlogram_kernel"),
+                                  ("initial grouping and pitch tracking", stage,
+                                   "sea::hw64_pitch_max_kernel + _segment_kernel + _frame_kernel x3 + _regroup_kernel x2 + _track_kernel"),
+                                  ("initial grouping and pitch tracking with the stage block", lambda: stage(True), "the same")):
+            med, t = median_ms(fn, args.steps)
+            results.append(med)
+            print(json.dumps({"metric": f"Hu-Wang estimator, 64-channel 16 kHz bank: {name} (frames of 160 samples/sec); a first form, not tuned",
+                              "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
+                              "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels}), flush=True)
+        s_host = status.cpu().numpy()
+        p_host = pitch.cpu().numpy()
+        print(json.dumps({"metric": "Hu-Wang estimator, 64-channel 16 kHz bank: initial grouping and pitch tracking relative to the correlogram of the same run",
+                          "value": results[2] / results[1], "unit": "ratio", "config": {"workload": workload},
+                          "segments_per_utterance": {"min": int((s_host & 0xFFFF).min()), "median": float(np.median(s_host & 0xFFFF)),
+                                                     "max": int((s_host & 0xFFFF).max())},
+                          "utterances_flagged": {"too_many_segments": int((s_host >> 16 & 1).sum()), "chanmark_unset": int((s_host >> 17 & 1).sum())},
+                          "voiced_frames": int((p_host > 0).sum()), "plus_units_in_channels_40_to_63": int((grp[:, 40:] > 0).sum().item())}), flush=True)
         del hout, hev, acf_hc, stages, scratch
 
     if "hw25ibm" in what:
