@@ -1,7 +1,7 @@
 /*
  * ns6_beat_plan.h -- which beats of a six-wave NoiseSup role need no frame bookkeeping (ns_pipe6_kernel.hip).
  *
- * Every role of the six-wave form runs niter = nfr + kDepth beats; at beat i it handles a few frames i - d, and what it does with
+ * Every role of the six-wave form runs niter = nfr + kDepth beats (nfr + depth_of(variant): the variant with kIdctS is deeper); at beat i it handles a few frames i - d, and what it does with
  * each hangs on one flag, "frame i - d exists and has tick >= k":
  *
  *      flag(i; d, k)  =  i - d < nfr  &&  i - d - (k - 1) >= onset          (tick_ge of the kernel; onset = first non-zero frame)
@@ -44,6 +44,14 @@ constexpr unsigned kVariantDenseRedeal = kRedeal;
  * kVariantDenseBin64; kVariantDenseRedeal is the body it grew from, which no kernel takes any more */
 constexpr unsigned kBin64 = 16u;
 constexpr unsigned kVariantDenseBin64 = kRedeal | kBin64;
+/* kIdctS (round 11, the dense kernel): the two in-order IDCT sums (DoMelIDCT, nine rows of 25 terms per stage) ride in idle lanes of the
+ * helper wave's stream.  B0 and G1 leave the 9 x 25 rounded products, S adds them up one beat later, and the 17-tap filters follow one
+ * beat after that: FA filters stage-0 frame i-4 (was i-3), so every stage-1 job moves by one beat, and G1 filters frame i-11 in the
+ * beat in which it takes the gains of frame i-9.  The variant has a table of its own (kPlanIdct) and a depth of its own (depth_of);
+ * the dense kernel is kVariantDenseIdct, kVariantDenseBin64 is the body it grew from, which no kernel takes any more */
+constexpr unsigned kIdctS = 32u;
+constexpr unsigned kVariantDenseIdct = kRedeal | kBin64 | kIdctS;
+constexpr int kDepthIdct = 12;       /* a role of that variant runs nfr + 12 beats; S stores frame i - 12 */
 
 struct Flag {
     int d;         /* the flag is about frame i - d ... */
@@ -75,35 +83,58 @@ constexpr RolePlan kPlan[kRoles] = {
     {5, {{1, 1, kAlways}, {3, 3, kAlways}, {6, 5, kAlways}, {kDepth, 5, kAlways}, {kDepth, 5, kFd}}, 0, 1},
 };
 
+/* the table of the variants with kIdctS: every flag belongs to the one kernel that takes it */
+constexpr RolePlan kPlanIdct[kRoles] = {
+    /* FA: frame i itself enters stage 0 from tick 3; the stage-0 filter of frame i-4 from tick 3, from the sums S left at i-1; stage 1
+     * of frame i-4 from tick 5 */
+    {3, {{0, 3, kAlways}, {4, 5, kAlways}, {4, 3, kAlways}, {0, 0, 0}, {0, 0, 0}}, 1, 0},
+    /* FB: one beat behind FA on both transforms */
+    {2, {{1, 3, kAlways}, {5, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* B0: stage-0 back half of frame i-2 (up to the IDCT products); stage-1 bin 64 of frame i-7 */
+    {2, {{2, 3, kAlways}, {7, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* N1: the VAD log-energy of frame i-2, noise tracking of frame i-6, gain-factor scalars of frame i-8 */
+    {3, {{2, 1, kAlways}, {6, 5, kAlways}, {8, 5, kAlways}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* G1: gains, mel and IDCT products of frame i-9; Hanning weight and 17-tap filter of frame i-11, from the sums S left at i-1 */
+    {2, {{9, 5, kAlways}, {11, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* S: VAD sum of frame i-1, denSigSE1 sum and stage-0 IDCT sums of i-3, noise sum of i-7, stage-1 IDCT sums of i-10, output of i-12 */
+    {5, {{1, 1, kAlways}, {3, 3, kAlways}, {7, 5, kAlways}, {10, 5, kAlways}, {kDepthIdct, 5, kAlways}}, 0, 1},
+};
+SEA_NS6_HD constexpr const RolePlan &plan_of(unsigned variant, int role) { return (variant & kIdctS) ? kPlanIdct[role] : kPlan[role]; }
+/* beats a role runs past the last frame; S stores frame i - depth_of */
+SEA_NS6_HD constexpr int depth_of(unsigned variant) { return (variant & kIdctS) ? kDepthIdct : kDepth; }
+
 SEA_NS6_HD constexpr bool flag_applies(const Flag &f, unsigned variant) { return f.when == kAlways || (f.when & variant) != 0u; }
 
 /* (d, k) is a flag of the role in that variant: what the kernel asserts of every flag it evaluates */
 SEA_NS6_HD constexpr bool has_flag(unsigned variant, int role, int d, int k)
 {
-    for (int j = 0; j < kPlan[role].n; ++j)
-        if (kPlan[role].f[j].d == d && kPlan[role].f[j].k == k && flag_applies(kPlan[role].f[j], variant)) return true;
+    const RolePlan &p = plan_of(variant, role);
+    for (int j = 0; j < p.n; ++j)
+        if (p.f[j].d == d && p.f[j].k == k && flag_applies(p.f[j], variant)) return true;
     return false;
 }
 
 /* beats after the onset from which all flags hold: max over the flags of d + k - 1, plus the settle beats */
 SEA_NS6_HD constexpr int steady_lead(unsigned variant, int role)
 {
+    const RolePlan &p = plan_of(variant, role);
     int lead = 0;
-    for (int j = 0; j < kPlan[role].n; ++j) {
-        const Flag &f = kPlan[role].f[j];
+    for (int j = 0; j < p.n; ++j) {
+        const Flag &f = p.f[j];
         if (flag_applies(f, variant) && f.d + f.k - 1 > lead) lead = f.d + f.k - 1;
     }
-    return lead + kPlan[role].settle;
+    return lead + p.settle;
 }
 /* beats past nfr at which the first flag falls: min over the flags of d, less the frames a steady beat touches ahead (may be < 0) */
 SEA_NS6_HD constexpr int steady_tail(unsigned variant, int role)
 {
-    int tail = kDepth;
-    for (int j = 0; j < kPlan[role].n; ++j) {
-        const Flag &f = kPlan[role].f[j];
+    const RolePlan &p = plan_of(variant, role);
+    int tail = depth_of(variant);
+    for (int j = 0; j < p.n; ++j) {
+        const Flag &f = p.f[j];
         if (flag_applies(f, variant) && f.d < tail) tail = f.d;
     }
-    return tail - kPlan[role].ahead;
+    return tail - p.ahead;
 }
 
 /* first beat at which every flag of the role is true; kNoOnset while there is no onset (no beat is >= it: frame counts stay below) */
@@ -111,7 +142,7 @@ SEA_NS6_HD constexpr int steady_begin(unsigned variant, int role, int onset)
 {
     return onset == kNoOnset ? kNoOnset : onset + steady_lead(variant, role);
 }
-/* first beat from steady_begin on at which one of them is false again (never above nfr + kDepth - 1; the range is empty when this
+/* first beat from steady_begin on at which one of them is false again (never above nfr + depth_of(variant) - 1; the range is empty when this
  * is not above steady_begin) */
 SEA_NS6_HD constexpr int steady_end(unsigned variant, int role, int nfr)
 {

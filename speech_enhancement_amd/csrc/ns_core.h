@@ -1049,6 +1049,36 @@ __device__ __forceinline__ void ns_idct_head(float melOut, float *rec, int lane,
     if (lane >= K && lane < SEA_NMEL) rec[lane] = melOut;
     wave_sync();
 }
+/* DoMelIDCT with its sums in another wave (the dense six-wave form since round 11): the wave that holds the mel gains leaves the
+ * 9 x 25 ROUNDED PRODUCTS melOut[f] * basis[f][t] -- the library is built with -ffp-contract=off, so the reference's
+ * h[t] += W[f] * idct[t][f] is RN(h + RN(W * b)) -- and the helper wave adds each row up in order in one of its idle lanes
+ * (helper_chains<.., IDS>), where the 25 lane reads, the 25 basis reads and the chain of 25 dependent additions cost no instruction.
+ * Row t of prod starts at [t * kIdctStride] (the stride is the helper wave's bank rule: ns_pipe6_kernel.hip, Pipe6Idct), row t of
+ * basisQ at [t * kIdctRow]; in both, terms f = 0..24 and [25..27] zero (basisQ's are written once, mel[25..27] are zero, so the record's
+ * come out as +0 * +0).  Lane = (row, quad): lane L < 63 has quad L % 7 of row L / 7; the mel gains reach it through the LDS copy
+ * mel[0..27].  Executed: one 32-bit store, two 128-bit reads, four
+ * multiplications, one 128-bit store.  (Lane = band, no cross-lane traffic: three reads of the band's basis column, nine
+ * multiplications, nine 32-bit stores.)  Lane 63 repeats lane 62.  Ends with wave_sync(). */
+constexpr int kIdctRow = 28;
+constexpr int kIdctStride = 44;      /* 11 slots of 16 B from row to row */
+constexpr int kIdctProdFloats = 384; /* eight strides and a row, rounded up to a multiple of 256 B */
+constexpr int kIdctBasisFloats = 256;
+constexpr int kIdsTapStride = 2;     /* the helper wave's record of windowed taps (helper_chains<.., IDS>): tap t at [kIdsTapStride * t], */
+constexpr int kIdsTapFloats = 32;    /* and a reader may fetch [kIdsTapStride * lane] in any lane: kIdsTapReach floats must exist behind it */
+constexpr int kIdsTapReach = kIdsTapStride * 63 + 1;
+__device__ __forceinline__ void ns_idct_products(float melOut, float *mel, const float *basisQ, float *prod, int lane)
+{
+    static_assert(9 * kIdctRow == 4 * 63 && kIdctRow >= SEA_NMEL && kIdctStride >= kIdctRow && 8 * kIdctStride + kIdctRow <= kIdctProdFloats &&
+                      9 * kIdctRow <= kIdctBasisFloats, "63 lanes of one quad each");
+    if (lane < SEA_NMEL) mel[lane] = melOut;
+    wave_sync();
+    const int L = (lane < 63) ? lane : 62;
+    const float4 m = *reinterpret_cast<const float4 *>(mel + 4 * (L % 7));
+    const float4 b = *reinterpret_cast<const float4 *>(basisQ + 4 * L);
+    *reinterpret_cast<float4 *>(prod + (L / 7) * kIdctStride + 4 * (L % 7)) = make_float4(m.x * b.x, m.y * b.y, m.z * b.z, m.w * b.w);
+    wave_sync();
+}
+
 template <int K>
 __device__ __forceinline__ void ns_idct_tail(const float *rec, const float *idctLds, float irWin, float *fir, int lane)
 {
@@ -1294,7 +1324,9 @@ __device__ unsigned long long g_back_ck[16];
  *   (ns_idct_tail, ns_idct_tail_rl) and runs the FIR itself. */
 template <int ST, bool PIPE, bool FD = false, bool RL = false, int IDCT_HEAD = -1, bool NF = false /* see ns_ln */,
           bool LDSB = false /* the six-wave forms: the IDCT basis from LDS as one batch of reads (ns_idct_basis_request), no bregs */,
-          bool B64 = false /* the dense six-wave form: stage-1 bin 64 rides in lane 1 of the second component (NsBin64) */>
+          bool B64 = false /* the dense six-wave form: stage-1 bin 64 rides in lane 1 of the second component (NsBin64) */,
+          bool IPROD = false /* the dense six-wave form: stop at the IDCT's products (ns_idct_products: dst the record, idctLds the
+                              * basis in the record's layout); the helper wave adds them up */>
 __device__ __forceinline__ void ns_back(const float *psd, const float *buf, BackLds &B, NsRegs &s,
                                         const NsConst &C, float *dst, int lane, float frameEnExt = 0.0f,
                                         float *spectOut = nullptr, const float *idctLds = nullptr,
@@ -1481,7 +1513,10 @@ __device__ __forceinline__ void ns_back(const float *psd, const float *buf, Back
         }
     }
     NS_BACK_CK(3); /* in-order sum, gain factor */
-    if constexpr (IDCT_HEAD >= 0) {
+    if constexpr (IPROD) {
+        static_assert(!IPROD || (ST == 0 && PIPE && !FD && IDCT_HEAD == SEA_NMEL), "in place of ns_idct_head's whole sums");
+        ns_idct_products(melOut, B.mel, idctLds, dst, lane);
+    } else if constexpr (IDCT_HEAD >= 0) {
         ns_idct_head<IDCT_HEAD, LDSB>(melOut, dst, lane, idctLds, bregs);
     } else if (RL && PIPE && yRegs) {
         if constexpr (LDSB)
@@ -1608,6 +1643,28 @@ __device__ __forceinline__ void ns_gain1(const float *psd, const float *P, const
     ns_idct_fir<true, true>(melOut, B, C, buf, dst, lane, idctLds);
 }
 
+/* ns_gain1<true> cut behind the gain factorisation (the dense six-wave form since round 11): ns_gain1_products leaves the IDCT's
+ * products of the frame (ns_idct_products), the helper wave adds them up and windows the sums, and two beats later ns_fir_from_taps
+ * mirrors the nine taps into the 17 and filters, exactly as ns_idct_taps<true, true> and ns_fir_apply do behind the tap. */
+__device__ __forceinline__ void ns_gain1_products(const float *psd, const float *P, const float *noise, float alfaGF, BackLds &B, NsRegs &s,
+                                                  const NsConst &C, float *prod, int lane, const float *basisQ, const float *w64)
+{
+    ns_gain1_bins63(psd, P, noise, w64, B, s, lane);
+    float melOut = ns_mel_fb(B, C, lane);
+    melOut = (float)((double)(alfaGF * melOut) + (1.0 - (double)alfaGF) * 1.0);
+    ns_idct_products(melOut, B.mel, basisQ, prod, lane);
+}
+__device__ __forceinline__ void ns_fir_from_taps(const float *taps, float *fir, const float *buf, float *dst, int lane)
+{
+    const float tap = taps[kIdsTapStride * ((lane <= 8) ? lane : 8)];
+    if (lane <= 8) {
+        fir[8 + lane] = tap;
+        fir[8 - lane] = tap;
+    }
+    wave_sync();
+    ns_fir_apply(fir, buf, dst, lane);
+}
+
 /* ns_gain1 for the six-wave forms since round 4: the taps as scalar operands, the filter's outputs in registers, and what
  * leaves the wave is the DC-offset filter's input differences d[n] = y[n] - y[n-1] (ns_fir_dif_rl) instead of y itself: the helper
  * wave's chain starts from them without a pass of its own over the frame.  lastIn = y[79] of the previous filtered frame (this
@@ -1660,6 +1717,45 @@ __device__ __forceinline__ void ns_fir_from_idct_rec(const float *rec, float irW
 {
     const int l = (lane <= 8) ? lane : 8;
     ns_fir_regs(fir_taps_rl(rec[28 + l] * irWin), buf, lane, y0, y1);
+}
+/* the same from the nine windowed taps themselves (taps[kIdsTapStride * k], left by the helper wave: helper_chains<.., IDS>), read
+ * at [kIdsTapStride * lane] by every lane: lanes 0..8 matter.  The window's 18 samples
+ * arrive in two batches of reads, x[8..17] ahead of taps 0..4 and x[0..7] behind them, where ns_fir_regs has them in one: FA is the
+ * register-bound role of the 72-VGPR kernel, and with one batch of 18 its general copy takes 74.  Same sums in the same order. */
+__device__ __forceinline__ void ns_fir_from_idct_taps(const float *taps, const float *buf, int lane, float &y0, float &y1)
+{
+    const FirTaps T = fir_taps_rl(taps[kIdsTapStride * lane]);
+    constexpr int kFirst = 5; /* taps 0..4 read x[12..17] */
+    float x[18];
+    int o = 72 + 2 * ((lane < 40) ? lane : 39); /* x[m] = buf[72 + 2l + m] */
+#pragma unroll
+    for (int m = 8; m < 18; m += 2) {
+        const float2 v = *reinterpret_cast<const float2 *>(buf + o + m);
+        x[m] = v.x;
+        x[m + 1] = v.y;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    y0 = 0.0f, y1 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < kFirst; ++k) {
+        const float c = T.t[8 - k];
+        y0 += c * x[16 - k];
+        y1 += c * x[17 - k];
+    }
+    asm("" : "+v"(o) : "v"(y0)); /* the second batch not before these terms */
+#pragma unroll
+    for (int m = 0; m < 8; m += 2) {
+        const float2 v = *reinterpret_cast<const float2 *>(buf + o + m);
+        x[m] = v.x;
+        x[m + 1] = v.y;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int k = kFirst; k < SEA_NTAP; ++k) {
+        const float c = T.t[k < 8 ? 8 - k : k - 8];
+        y0 += c * x[16 - k];
+        y1 += c * x[17 - k];
+    }
 }
 
 /* One whole stage on the single-wave form: stage 0 deposits its 80 output samples in
@@ -1761,13 +1857,43 @@ __device__ __forceinline__ bool dc_step_ok(float d, float yPrev)
  * nz[65..67] must be zero, x = 0 from n = 68 on; returned in *nzSum.  Its zero tail is folded into the
  * per-lane offsets before the stream as the den chain's is, so the stream keeps its instruction count (113 instructions between
  * the 80 FMAs of the dense six-wave kernel's listing, with and without NZ). */
-template <int CHUNKS, bool FDCH = false, bool NZ = false>
+/* IDS (the dense six-wave form since round 11, with NZ): eighteen more in-order sums, the nine rows of DoMelIDCT of each stage
+ * (MelProc.c:357-378: h[t] += W[f] * idct[t][f] from h = 0), in lanes 1..9 (stage 0, which otherwise repeat the VAD sum) and 17..25
+ * (stage 1, which repeat the den sum).  Lane 1 + t / 17 + t reads row t of the products ns_idct_products left (ids->prod0 / prod1, rows
+ * kIdctStride floats apart, kIdctRow of them read, [25..27] zero) with m = 1 from acc = 0: RN(1 * acc + x) == RN(acc + x), and acc, which starts at +0, never becomes
+ * -0, so the zero terms behind the row add nothing.  Those zeros come from ids->zeros through per-lane bases set before the stream,
+ * one for each of the three ranges of n -- n < 28, 28 <= n < 68, 68 <= n -- so that every read of the stream is `base + n` with n in
+ * the instruction's offset and no select between two FMAs: the row lanes read zeros[n - 28] from n = 28 on, the den and the noise
+ * lanes zeros[n - 68] from n = 68 on (zero4 is not used); kIdsZeros floats.  After the stream each of the eighteen lanes multiplies its
+ * own acc by its row's Hanning weight (NoiseSup.c:660-669; ids->hann, per lane) and stores the tap into ids->tap0 / tap1
+ * [kIdsTapStride * t]: one multiplication and one store through a per-lane address, no lane read.  (The stride is FA's: it reads
+ * tap[2 * lane] through the address it has for its sample pairs; FA is the register-bound role of the 72-VGPR kernel.) */
+constexpr int kIdsZeros = SEA_HOP - kIdctRow; /* 52 */
+/* Which record a lane reads changes from beat to beat with two scalars only -- p, the frame parity of the den record and of both
+ * product and tap records (stage 1's are the other parity's), and q, the slot of the noise ring -- so the lane's part of every
+ * address is set ONCE before the frame loop (byte offsets from `lds`, the start of the workgroup's LDS record), and a beat costs two
+ * multiply-adds for src, one select for the middle base and one multiply-add for the store address; no lane-class mask but the row
+ * lanes' stays alive over the loop (the masks were what the SGPR budget of the 72-VGPR kernel did not have). */
+struct HelperIdct {
+    char *lds;
+    int src0, srcP, srcQ; /* n < 28 (rows) / n < 68 (the others): lds + src0 + srcP * p + srcQ * q */
+    int end;              /* n >= 68: the row, den and noise lanes' zeros, the VAD and DC lanes' own source */
+    int rowZeros;         /* 28 <= n < 68, row lanes: zeros - kIdctRow; the others go on with src */
+    int tap0, tapP;       /* row lanes: the tap goes to lds + tap0 + tapP * p */
+    float hann;           /* row lanes: the Hanning weight of taps 8 +- t */
+    float m, acc0;        /* the lane's multiplier, and its start value unless it is on the DC chain */
+    int p, q;             /* this beat's scalars */
+};
+template <int CHUNKS, bool FDCH = false, bool NZ = false, bool IDS = false>
 __device__ __forceinline__ void helper_chains(const float *sq, const float *den, const float *dif, float *out,
                                               const float *zero4, float &vadSum, float &denSum,
                                               float &y, int lane, bool *unsafe = nullptr, const float *fdRec = nullptr,
-                                              float *fdSums = nullptr, const float *nz = nullptr, float *nzSum = nullptr)
+                                              float *fdSums = nullptr, const float *nz = nullptr, float *nzSum = nullptr,
+                                              const HelperIdct *ids = nullptr)
 {
     static_assert(!(FDCH && NZ), "lanes 48..63 carry either the fd sums or the noise sum");
+    static_assert(!IDS || NZ, "the IDCT rows ride beside the noise sum");
+    const bool rowLane = IDS && ((lane >= 1 && lane <= 9) || (lane >= 17 && lane <= 25));
     const int g = lane >> 4;
     const bool fdLane = FDCH && lane >= 48 && lane <= 50;
     const float *src = (g == 0) ? sq : ((g == 1) ? den : dif);
@@ -1782,6 +1908,17 @@ __device__ __forceinline__ void helper_chains(const float *sq, const float *den,
         m = 1.0f;
         acc = 0.0f;
     }
+    /* IDS: the three per-lane bases, each used as base + n */
+    const float *mid = src, *end = src;
+    float *sumDst = nullptr;
+    if constexpr (IDS) {
+        src = reinterpret_cast<const float *>(ids->lds + (ids->src0 + ids->srcP * ids->p + ids->srcQ * ids->q));
+        mid = rowLane ? reinterpret_cast<const float *>(ids->lds + ids->rowZeros) : src;
+        end = reinterpret_cast<const float *>(ids->lds + ids->end);
+        m = ids->m;
+        acc = (g == 2) ? y : ids->acc0;
+        sumDst = reinterpret_cast<float *>(ids->lds + (ids->tap0 + ids->tapP * ids->p));
+    }
     /* the 20 quads are requested in CHUNKS chunks (4: 2 x 20 VGPRs in flight; 10: 2 x 8, for the 80-VGPR kernel
      * forms), chunk c + 1 before the chain of chunk c starts (an LDS round trip is ~60 clk) */
     constexpr int kQ = SEA_HOP / 4 / CHUNKS;
@@ -1793,6 +1930,7 @@ __device__ __forceinline__ void helper_chains(const float *sq, const float *den,
             const int n = 4 * (c * kQ + k);
             const float *p = (n >= 68) ? tail + (NZ ? ((g == 1 || g == 3) ? 0 : n) : ((g == 1) ? 0 : n)) : src + n;
             if (FDCH && n >= 28) p = (n >= fdLim) ? zero4 : p;
+            if (IDS) p = ((n >= 68) ? end : ((n >= kIdctRow) ? mid : src)) + n;
             dstq[k] = *reinterpret_cast<const float4 *>(p);
         }
     };
@@ -1850,6 +1988,9 @@ __device__ __forceinline__ void helper_chains(const float *sq, const float *den,
         fdSums[2] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 50));
     }
     if (NZ) *nzSum = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(acc), 48));
+    if constexpr (IDS) {
+        if (rowLane) *sumDst = acc * ids->hann;
+    }
     wave_sync();
 }
 

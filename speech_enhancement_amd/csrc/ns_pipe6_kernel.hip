@@ -17,6 +17,7 @@
  *   wave S   the lane-grouped scalar chains: VAD log-energy of the frame pushed at i-1, in-order sum of
  *            denSigSE1 of frame i-3, in-order sum of the noise spectrum of frame i-6, DC-offset recurrence
  *            + cast + store of frame i-9 (kDepth)
+ * (the dense kernel's schedule since round 11 is three beats deeper: the Round 11 paragraph below)
  *
  * Round 6: the in-order sum of the 65 second-stage noise magnitudes (64 v_readlane + v_add in N1, ~129 vector instructions
  * for one scalar) rides the helper wave's serial stream in lanes 48..63, which only repeated the DC chain: no instruction
@@ -56,6 +57,20 @@
  *   wave N1  also: its fast-division decision of the frame -> rn[].P[65]; G1 and B0 read it instead of testing the PSD again
  * and the wave -> role map was swept again (kRedealPerm).  G1 2720 -> 2120 clk per frame, B0 2365 -> 2575, the beat 3065 -> 2975;
  * the step moved with the new map, not before it: the figures are in profiles/ns6_bin64_in_b0.txt.
+ *
+ * Round 11, the dense kernel only (IDCTS of ns_pipe6_body): DoMelIDCT's nine in-order sums of 25 terms cost B0 and G1, for nine useful
+ * lanes each, 25 lane reads, 25 basis reads, 25 multiplications and a chain of 25 dependent additions per frame.  Now --
+ *   wave B0  frame i-2 as before, up to the 9 x 25 rounded products of the mel gains and the basis (lane = (row, quad): four
+ *            multiplications and one 128-bit store) -> prod[0]
+ *   wave G1  frame i-9: gains, mel, gain factorisation, the same products -> prod[1]; frame i-11: the 17-tap filter from S's taps
+ *   wave S   also: the nine rows of stage-0 frame i-3 in lanes 1..9 and of stage-1 frame i-10 in lanes 17..25 of its serial stream
+ *            (they only repeated the VAD and the den chain), `acc = fma(1, acc, x)` from +0, which is the reference's
+ *            h += W * idct term by term; then the Hanning weight, one multiplication -> tap[]; noise sum of i-7, output of i-12
+ *   wave FA  the stage-0 filter of frame i-4 from S's taps, and with it every stage-1 job one beat later: FB i-5, N1 i-6 / i-8, B0's
+ *            guest i-7
+ * The pipeline is twelve beats deep instead of nine (ns6plan::depth_of), the stream keeps its length (110 instructions between the
+ * 80 FMAs of the listing, 113 before: the three bases are set before it), and the map was swept again (kRedealPerm).  configs[1]:
+ * 1.61 -> 1.47 ms = 555 M frames/s (profiles/ns6_idct_in_helper.txt).
  *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
@@ -110,7 +125,7 @@ constexpr int kCirc = kSlots * kSlotLen;
 constexpr int kCirc1 = kSlots1 * kSlotLen;
 constexpr int kMirror = 3 * kSlotLen;
 constexpr int kWaves = 6;
-constexpr int kDepth = ns6plan::kDepth; /* 9: S stores frame i - kDepth */
+constexpr int kDepth = ns6plan::kDepth; /* 9: S stores frame i - kDepth (IDCTS: ns6plan::depth_of, 12) */
 constexpr int kSChunks = 10; /* helper_chains: the helper wave's 20 quads are requested in ten chunks (2 x 8 VGPRs in flight) */
 /* issue priority by remaining frames: evaluated every kPrioStep frames, kPrioLevels levels dithered into the four hardware ones
  * (the rule and its measurements: ns_pipe_kernel.hip) */
@@ -122,8 +137,10 @@ constexpr int kDefaultPerm = 0014352;
 /* The re-dealt dense kernel: a map of its own, re-swept whenever the roles' lengths move (tools/ns6_perm_sweep.py, all 720 maps).
  * Round 8: 0053412 (B0, FB, G1, N1, S, FA on waves 0..5).  Round 10, with G1 the shortest role instead of the longest: FA, N1, B0, G1, S,
  * FB on waves 0..5 -- the best ten maps of that sweep all keep G1 on wave 3 and B0 or N1 on wave 2; 0053412 is 76th there, 2.8 %
- * behind (profiles/ns6_bin64_in_b0.txt) */
-constexpr int kRedealPerm = 0154230;
+ * behind (profiles/ns6_bin64_in_b0.txt).  Round 11, with the IDCT sums in S: S, B0, N1, FA, G1, FB on waves 0..5 -- six of the best
+ * ten maps of that sweep keep N1 on wave 2 and G1 on wave 4, seven have S on wave 0 or 1; 0154230 is 122nd there, 3.9 % behind
+ * (profiles/ns6_idct_in_helper.txt) */
+constexpr int kRedealPerm = 0140325;
 
 /* Frame bookkeeping (valid / tick / produced of every frame) is a pure function of the frame index: the zero-frame gate
  * (ParmInterface.c:244-251) has one degree of freedom per utterance, the index `onset` of the first non-zero frame.  From it on every
@@ -229,6 +246,26 @@ __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, 
  *                     (written at f+5, last read at f+8) inside their lifetimes, so neither ring grows.  It leaves the gain in
  *                     w1hi[f], written at f+6, read by G1 at f+8: D > 2, three would do; four makes the slot a mask (kW1Ring).
  *                     N1's domain flag of frame f sits in rn[f].P[kNsFastWord] and lives as rn does.
+ *   IDCTS (round 11)  every stage-1 job one beat later, the filter two beats behind the gains:
+ *                     frame f is transformed (stage 1) by FA at f+4, FB at f+5; noise-tracked at f+6 (B0's guest: f+7); noise-summed at
+ *                     f+7; gain-factored at f+8; G1 takes its gains and leaves the products at f+9; S adds them up at f+10; G1 filters
+ *                     at f+11 -> ro[f]; S stores at f+12 = f+DEPTH.  Stage 0: B0's products at f+2, S's sums at f+3, FA's filter at f+4.
+ *   p1                written at f+5, read by N1 at f+6, B0 at f+7, G1 at f+9: D > 4, as before
+ *   rn                written at f+6, read by S and B0 at f+7, by G1 at f+9: D > 3, as before
+ *   w1hi              written at f+7, read at f+9: D > 2, as before
+ *   nzSum, alfa, ro   f+7 -> f+8, f+8 -> f+9, f+11 -> f+12: by frame parity, as before
+ *   prod, tap         written at one iteration, read at the next (B0 f+2 -> S f+3 -> FA f+4; G1 f+9 -> S f+10 -> G1 f+11): by frame
+ *                     parity; at one beat S reads stage 0's record of parity (i-3) & 1 and stage 1's of the other, (i-10) & 1
+ *   denSum[tick & 7]  tick t written by S at f+3; N1 reads ticks t-2 .. t for the frames f .. f+2, the last at f+2+8: D > 7 -- eight
+ *                     still hold, by one
+ *   fdFlags           not this variant's (no FD)
+ *   stage-1 buffer    FA writes the slot of frame i-4 at iteration i (tick t+7, where t is the tick of frame i-11), and its own
+ *                     window of that beat reads slots t+4 .. t+7; G1's filter of frame i-11 reads slots t-3 .. t: eleven live slots,
+ *                     sixteen do not collide (t+7 = t-9 mod 16); the slot's previous content, tick t-9, was last read by G1 at
+ *                     iteration i-6.  The three mirrored slots are written with their slots and live as they do.
+ *   stage-0 buffer    FA's filter of frame i-4 reads the slots of frames i-7 .. i-5 (buf[72..167] of that frame's window) while its push
+ *                     of that beat writes the slot of frame i = i-8 (mod 8), and its own window reads i-3 .. i: no collision, by one
+ *   LDS               31 856 B per workgroup; five fit a CU's 160 KB, which is what the compiler's occupancy of 7 counts
  * nbFrame of the gain-factor job: N1's counter has by then counted the two frames tracked since; the job takes the frame's own
  * count, tick - 4 (the first second-stage frame has tick 5).
  * LDS: 24 960 B per workgroup (24 624 + the two tap records + the ring of W1[64]); four workgroups per CU take 99.8 KB of the 160. */
@@ -295,6 +332,68 @@ static_assert(lds_slots_differ(NS6_OFF(ro[0].out[68]), NS6_OFF(szero)) && lds_sl
 static_assert(sizeof(Pipe6Lds) == 24960 && 4 * sizeof(Pipe6Lds) <= 160 * 1024 && sizeof(Pipe6Lds) < 40 * 1024,
               "the figure in the comment at kP1Ring; four workgroups fit a CU");
 
+/* IDCTS (round 11, the dense kernel): what the IDCT sums in the helper wave need, behind the record every six-wave kernel has -- whose
+ * layout, and with it the other two kernels' listings and LDS size, stays as it was (tap[] is the one member the dense kernel no longer
+ * touches).  prod: the products B0 ([0]) and G1 ([1]) leave, by frame parity, read by S one beat later; tap: S's nine sums per stage
+ * times their Hanning weights, by frame parity, read by FA / G1 one beat later; zeros: what S's row lanes
+ * read behind their 28 terms, and its den and noise lanes behind their 68.
+ * Bank rule of S's ds_read_b128 (as above: a 16-lane group serves 256 B per clock, so two DIFFERENT addresses of a group must differ
+ * mod 256 B; equal addresses are one access).  The groups are {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (and two more in lanes
+ * 32-63, which carry no row): each holds the VAD lanes' ssq + n, the den lanes' den + n, three rows of one stage and six of the other.
+ * Every product record is a multiple of 256 B long, so all four put their row t into the same slot, and S's two records of a beat
+ * have opposite frame parities.  ssq sits in slot 12 of 16, den in slots 0 and 1 by parity: with rows 28 floats = 7 slots apart no
+ * offset of the records keeps both groups free of a collision (nor with 9, 13: searched over all offsets), with 11 slots = 44 floats
+ * (kIdctStride) three offsets do, with 15 two; 44 is the shorter record.  From n = 28 on the row lanes read zeros + n - 28 (one address), from n = 68 on the
+ * den and noise lanes zeros + n - 68: both must miss ssq + n, the first den + n as well, the second sdif + n.  All of it asserted
+ * below; as above it is the rule applied, what was measured is SQ_LDS_BANK_CONFLICT as a whole (profiles/ns6_idct_in_helper.txt). */
+struct __attribute__((aligned(16))) Pipe6Idct {
+    float tap[2][2][kIdsTapFloats];    /* [stage][frame parity]: the nine windowed taps, kIdsTapStride apart */
+    float pad0[4];                     /* puts zeros, */
+    float zeros[kIdsZeros];
+    float pad[4];                      /* and the rows' slots, where ssq, sdif and den are not */
+    float prod[2][2][kIdctProdFloats]; /* [stage][frame parity] */
+};
+/* basisQ takes the place of idctT, which this variant does not read: four workgroups need 4 x 40 KB at the most, but the compiler's
+ * occupancy figure counts whole workgroups against the CU's 160 KB, and seven waves per SIMD are five of these, 32 KB each */
+constexpr int kIdctBasisAt = 3; /* floats into idctT: the first 16-byte boundary */
+struct __attribute__((aligned(16))) Pipe6LdsIdct {
+    Pipe6Lds base;
+    Pipe6Idct x;
+};
+constexpr size_t lds_slot(size_t off) { return (off / 16) % 16; }
+/* the slots of one 16-lane group at n < 28: ssq, den, rows r0 .. r1-1 of one record and the other rows of the other, all different */
+constexpr bool lds_group_ok(size_t ssq, size_t den, size_t recA, size_t recB, int r0, int r1)
+{
+    size_t sl[11] = {lds_slot(ssq), lds_slot(den)};
+    int n = 2;
+    for (int r = 0; r < 9; ++r) sl[n++] = lds_slot(((r >= r0 && r < r1) ? recA : recB) + r * kIdctStride * sizeof(float));
+    for (int i = 0; i < n; ++i)
+        for (int j = i + 1; j < n; ++j)
+            if (sl[i] == sl[j]) return false;
+    return true;
+}
+#define NS6_OFF(m) offsetof(Pipe6LdsIdct, m)
+static_assert(NS6_OFF(base) == 0 && NS6_OFF(x.prod) % 256 == NS6_OFF(x.prod[0][1]) % 256 && NS6_OFF(x.prod) % 256 == NS6_OFF(x.prod[1][0]) % 256 &&
+                  NS6_OFF(x.prod) % 256 == NS6_OFF(x.prod[1][1]) % 256 && NS6_OFF(x.prod) % 16 == 0 && (kIdctRow * sizeof(float)) % 16 == 0 &&
+                  (NS6_OFF(base.idctT) + kIdctBasisAt * sizeof(float)) % 16 == 0 && kIdctBasisAt + kIdctBasisFloats <= SEA_NMEL * 16 &&
+                  NS6_OFF(x.tap[0][1]) % 16 == 0 && NS6_OFF(x.tap[1][1]) + kIdsTapReach * sizeof(float) <= sizeof(Pipe6LdsIdct),
+              "the four product records share their slots");
+/* lanes 1-3 | 4-9 have stage-0 rows 0-2 | 3-8 (record of den's parity), lanes 20-25 | 17-19 stage-1 rows 3-8 | 0-2 (the other parity) */
+static_assert(lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[0].den), NS6_OFF(x.prod[0][0]), NS6_OFF(x.prod[1][1]), 0, 3) &&
+                  lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[0].den), NS6_OFF(x.prod[0][0]), NS6_OFF(x.prod[1][1]), 3, 9) &&
+                  lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[1].den), NS6_OFF(x.prod[0][1]), NS6_OFF(x.prod[1][0]), 0, 3) &&
+                  lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[1].den), NS6_OFF(x.prod[0][1]), NS6_OFF(x.prod[1][0]), 3, 9) &&
+                  (kIdctStride * sizeof(float)) % 16 == 0, "n < 28: ssq, den | the rows, in both groups and both parities");
+static_assert(NS6_OFF(x.zeros) % 16 == 0 && lds_slots_differ(NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float), NS6_OFF(base.ssq)) &&
+                  lds_slots_differ(NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float), NS6_OFF(base.rd[0].den)) &&
+                  lds_slots_differ(NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float), NS6_OFF(base.rd[1].den)), "28 <= n: the rows' zeros | ssq, den");
+static_assert(lds_slots_differ(NS6_OFF(x.zeros) + 512 - 68 * sizeof(float), NS6_OFF(base.ssq)) &&
+                  lds_slots_differ(NS6_OFF(x.zeros) + 512 - 68 * sizeof(float), NS6_OFF(base.sdif)) &&
+                  lds_slots_differ(NS6_OFF(x.zeros) + 512 - 68 * sizeof(float), NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float)),
+              "68 <= n: the den and noise lanes' zeros | ssq, sdif, the rows' zeros");
+#undef NS6_OFF
+static_assert(4 * sizeof(Pipe6LdsIdct) <= 160 * 1024 && 5 * sizeof(Pipe6LdsIdct) <= 160 * 1024, "four workgroups fit a CU; five, for the compiler's occupancy of 7");
+
 /* SLOTS: kSlots for the stage-0 buffer, kSlots1 for the stage-1 buffer */
 template <int SLOTS>
 __device__ __forceinline__ int window_base(int tick) { return ((tick - 3) & (SLOTS - 1)) * kSlotLen; }
@@ -328,14 +427,26 @@ __device__ __forceinline__ void load_back_const(NsConst &C, const sea_ns_tables 
 template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands over the DC differences */,
           bool STEADY_LOOP /* the flag-free copy of every role's beat on its steady range (run_beats) */,
           bool REDEAL = false /* round 8, the dense kernel: feed-forward work of S and B0 in the waves that wait, and the map that goes with it */,
-          bool BIN64 = false /* round 10, the dense kernel: stage-1 bin 64 rides in B0's second component, one domain flag per stage-1 frame */>
-__device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
+          bool BIN64 = false /* round 10, the dense kernel: stage-1 bin 64 rides in B0's second component, one domain flag per stage-1 frame */,
+          bool IDCTS = false /* round 11, the dense kernel: both stages' IDCT sums ride in the helper wave's idle lanes; X is its LDS */>
+__device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L, Pipe6Idct *X = nullptr)
 {
     static_assert(!REDEAL || (!LIGHT && !DIFG1), "the re-deal is a variant of the dense body");
     static_assert(!BIN64 || (REDEAL && !FD), "the guest of B0's second component is a variant of the re-dealt dense body");
+    static_assert(!IDCTS || BIN64, "the IDCT sums in the helper wave are a variant of that body in turn");
     constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u) |
-                           (BIN64 ? ns6plan::kBin64 : 0u);
-    static_assert(!BIN64 || V == ns6plan::kVariantDenseBin64, "the variant tests/test_ns6_bin64_plan_cpu.py sweeps");
+                           (BIN64 ? ns6plan::kBin64 : 0u) | (IDCTS ? ns6plan::kIdctS : 0u);
+    static_assert(!BIN64 || V == (IDCTS ? ns6plan::kVariantDenseIdct : ns6plan::kVariantDenseBin64),
+                  "the variants tests/test_ns6_idct_plan_cpu.py and tests/test_ns6_bin64_plan_cpu.py sweep");
+    /* IDCTS (profiles/ns6_idct_in_helper.txt): DoMelIDCT's nine in-order sums of 25 terms, twice per frame, cost B0 and G1 25 lane reads,
+     * 25 basis reads, 25 multiplications and a chain of 25 dependent additions each, for nine useful lanes.  Here B0 (frame i-2) and G1
+     * (frame i-9) stop at the rounded products (ns_idct_products), S adds the rows up one beat later in lanes that only repeated another
+     * chain (helper_chains<.., IDS>: the same additions in the same order), and the filters follow one beat after that: FA filters
+     * stage-0 frame i-4, so every stage-1 job sits one beat later than the table at kP1Ring has it (kS1), and G1 filters frame i-11 in
+     * the beat in which it takes the gains of frame i-9.  The pipeline is three beats deeper (DEPTH). */
+    constexpr int kS1 = IDCTS ? 1 : 0;             /* beats by which stage 1 starts later */
+    constexpr int DEPTH = ns6plan::depth_of(V);    /* S stores frame i - DEPTH */
+    static_assert(DEPTH == (IDCTS ? 12 : kDepth), "the depth the ring depths at kP1Ring are derived for");
     /* BIN64 (profiles/ns6_bin64_in_b0.txt): the Wiener-gain chain ran on the pair (bin lane, bin 64) in B0 and in G1, and the second
      * component is one useful value in 64 identical lanes.  B0, at beat i, takes stage-1 bin 64 of frame g = i-6 into lane 1 of its
      * second component (ns_core.h, NsBin64) and leaves W1[64] in w1hi[g & 3]; G1 computes bins 0..63 with the single-component chain.
@@ -370,7 +481,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
      * formed in 64 bits (a single utterance may exceed 2^31 samples). */
     const long long nfr64 = a.lengths[u] / SEA_HOP;
     const int nfr = __builtin_amdgcn_readfirstlane((int)(nfr64 < kMaxFrames ? nfr64 : kMaxFrames));
-    const int niter = nfr + kDepth;
+    const int niter = nfr + DEPTH;
     /* issue priority by remaining frames, the rule of the four-wave form (ns_pipe_kernel.hip): on whenever the
      * launch has more utterances than CUs to put them on and an order whose first entry is the longest */
     const bool lrpt = a.prio_row > 0 && a.order;
@@ -393,7 +504,9 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         float *z = reinterpret_cast<float *>(&L);
         for (int i = threadIdx.x; i < kCirc + kCirc1 + 2 * kMirror; i += 64 * kWaves) z[i] = 0.0f;
     }
-    for (int i = threadIdx.x; i < SEA_NMEL * 16; i += 64 * kWaves) L.idctT[i] = a.tables->idct[i >> 4][i & 15];
+    if constexpr (!IDCTS)
+        for (int i = threadIdx.x; i < SEA_NMEL * 16; i += 64 * kWaves) L.idctT[i] = a.tables->idct[i >> 4][i & 15];
+    float *const basisQ = L.idctT + kIdctBasisAt; /* IDCTS: the basis in the product record's layout (ns_idct_products) */
     if (threadIdx.x < 4) L.szero[threadIdx.x] = 0.0f;
     if (threadIdx.x < kSlots) {
         L.frameEn[threadIdx.x] = 0.0f;
@@ -410,6 +523,14 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         L.rn[k].noise[65] = L.rn[k].noise[66] = L.rn[k].noise[67] = 0.0f; /* likewise */
     }
     if (threadIdx.x == 0) L.onset = kNoOnset;
+    if constexpr (IDCTS) { /* the basis in the product record's layout, the rows' zero pads, the zero region, the pads of the two mel copies */
+        for (int i = threadIdx.x; i < kIdctBasisFloats; i += 64 * kWaves) {
+            const int t = i / kIdctRow, f = i % kIdctRow;
+            basisQ[i] = (t < 9 && f < SEA_NMEL) ? a.tables->idct[f][t] : 0.0f;
+        }
+        if (threadIdx.x < kIdsZeros) X->zeros[threadIdx.x] = 0.0f;
+        if (threadIdx.x < 6) L.back[threadIdx.x / 3].mel[SEA_NMEL + threadIdx.x % 3] = 0.0f;
+    }
     block_sync();
     NS6_T_DECL;
 
@@ -420,7 +541,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         float win8[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) win8[k] = a.tables->win8[k][lane];
-        const float irWin = FIR_FA ? a.tables->irWin[lane] : 0.0f; /* lane k = 0..8: the Hanning weight of tap 8 +- k */
+        const float irWin = (FIR_FA && !IDCTS) ? a.tables->irWin[lane] : 0.0f; /* lane k = 0..8: the Hanning weight of tap 8 +- k (IDCTS: S has it) */
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
         uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
         int onset = kNoOnset; /* index of the first non-zero frame */
@@ -452,15 +573,18 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                     actA = STEADY || tick >= 3; /* NoiseSup.c:1152 */
                 }
             }
-            /* stage 1, frame i-3 (B0 finished it at the previous iteration): NoiseSup.c:1178 <=> tick >= 5 */
-            const int t1 = tick_of(i - 3, onset);
-            const bool actB = beat_flag<V, ns6plan::FA, 3, 5, STEADY>(i, onset, nfr);
+            /* stage 1, frame i-3 (B0 finished it at the previous iteration; IDCTS: frame i-4, S did): NoiseSup.c:1178 <=> tick >= 5 */
+            const int t1 = tick_of(i - 3 - kS1, onset);
+            const bool actB = beat_flag<V, ns6plan::FA, 3 + kS1, 5, STEADY>(i, onset, nfr);
             if constexpr (FIR_FA) {
                 /* stage-0 filter of frame i-3 from the IDCT sums B0 left at the previous iteration; from tick 3, not 5: ticks 3 and 4
                  * leave output that the first stage-1 window reads.  Also in the drain, where FA has no frame of its own. */
-                if (beat_flag<V, ns6plan::FA, 3, 3, STEADY>(i, onset, nfr)) {
+                if (beat_flag<V, ns6plan::FA, 3 + kS1, 3, STEADY>(i, onset, nfr)) {
                     float y0, y1;
-                    ns_fir_from_idct_rec(L.tap[(i - 3) & 1].rec, irWin, L.circ0 + window_base<kSlots>(t1), lane, y0, y1);
+                    if constexpr (IDCTS) /* the taps S left at the previous iteration */
+                        ns_fir_from_idct_taps(X->tap[0][(i - 4) & 1], L.circ0 + window_base<kSlots>(t1), lane, y0, y1);
+                    else
+                        ns_fir_from_idct_rec(L.tap[(i - 3) & 1].rec, irWin, L.circ0 + window_base<kSlots>(t1), lane, y0, y1);
                     if (lane < 40) slot_store<kSlots1>(L.circ1, t1, lane, y0, y1);
                     wave_sync();
                 }
@@ -490,9 +614,9 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             if (!STEADY) onset_poll(onset, &L.onset);
             const int g = i - 1; /* FA's iteration */
             if (STEADY || g >= 0) {
-                const int f0 = g, f1 = g - 3;
+                const int f0 = g, f1 = g - 3 - kS1;
                 const bool actA = beat_flag<V, ns6plan::FB, 1, 3, STEADY>(i, onset, nfr);
-                const bool actB = beat_flag<V, ns6plan::FB, 4, 5, STEADY>(i, onset, nfr);
+                const bool actB = beat_flag<V, ns6plan::FB, 4 + kS1, 5, STEADY>(i, onset, nfr);
                 float *work = L.work[g & 1];
                 if (actA || actB) {
                     float o[8]; /* the last level stays in registers and feeds both PSDs (ns_core.h, psd_from_last_level) */
@@ -524,12 +648,12 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_BEGIN;
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
-            const int f = i - 2, g = i - 6;
+            const int f = i - 2, g = i - 6 - kS1;
             if constexpr (BIN64) {
                 x.psd1 = L.p1[g & (kP1Ring - 1)].psd;
                 x.P1 = L.rn[g & (kRnRing - 1)].P;
                 x.noise1 = L.rn[g & (kRnRing - 1)].noise;
-                x.live = beat_flag<V, ns6plan::B0, 6, 5, STEADY>(i, onset, nfr);
+                x.live = beat_flag<V, ns6plan::B0, 6 + kS1, 5, STEADY>(i, onset, nfr);
                 x.done = false;
             }
             if (beat_flag<V, ns6plan::B0, 2, 3, STEADY>(i, onset, nfr)) {
@@ -540,7 +664,10 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 /* the filter taps as scalar operands (v_readlane), the filter's outputs in registers straight
                  * into the stage-1 buffer -- two LDS round trips less on this role's chain (ns_core.h, fir_taps_rl) */
                 const float frameEn = ((LIGHT || LOG_N1) ? L.frameEnLog : L.frameEn)[t & (kSlots - 1)];
-                if constexpr (BIN64) { /* as FIR_FA below, with the guest in lane 1 of the second component */
+                if constexpr (IDCTS) { /* as BIN64 below, up to the IDCT's products; S adds them up at the next iteration */
+                    ns_back<0, true, FD, true, SEA_NMEL, false, true, true, true>(r.psd, nullptr, L.back[0], s, C, X->prod[0][f & 1], lane, frameEn, o.den,
+                                                                                  basisQ, &fd, &bits, nullptr, nullptr, nullptr, &x);
+                } else if constexpr (BIN64) { /* as FIR_FA below, with the guest in lane 1 of the second component */
                     ns_back<0, true, FD, true, SEA_NMEL, false, true, true>(r.psd, nullptr, L.back[0], s, C, L.tap[f & 1].rec, lane, frameEn, o.den,
                                                                             L.idctT, &fd, &bits, nullptr, nullptr, nullptr, &x);
                 } else if constexpr (FIR_FA) { /* stop at the nine IDCT sums; FA windows them and filters at the next iteration */
@@ -581,7 +708,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_BEGIN;
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
-            const int f = i - 5, fg = i - 7;
+            const int f = i - 5 - kS1, fg = i - 7 - kS1;
             if constexpr (LOG_N1) { /* the log-energy of the sum S left one beat ago, as FA takes it with LIGHT; B0 reads it two beats on */
                 if (beat_flag<V, ns6plan::N1, 2, 1, STEADY>(i, onset, nfr)) {
                     const int e = (tick_of(i - 2, onset) + 2) & (kSlots - 1);
@@ -589,7 +716,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                     if (lane == 0) L.frameEnLog[e] = en;
                 }
             }
-            if (beat_flag<V, ns6plan::N1, 7, 5, STEADY>(i, onset, nfr)) {
+            if (beat_flag<V, ns6plan::N1, 7 + kS1, 5, STEADY>(i, onset, nfr)) {
                 const int t = tick_of(fg, onset);
                 /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
                 s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
@@ -601,7 +728,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 s.nbFrame[1] = nbNow;
                 if (lane == 0) L.alfa[fg & 1] = s.alfaGF;
             }
-            if (beat_flag<V, ns6plan::N1, 5, 5, STEADY>(i, onset, nfr)) {
+            if (beat_flag<V, ns6plan::N1, 5 + kS1, 5, STEADY>(i, onset, nfr)) {
                 const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place three beats later (kP1Ring) */
                 RecN &o = L.rn[f & (kRnRing - 1)];
                 ns_noise1<BIN64>(r.psd, o.P, o.noise, s, eps, lane);
@@ -625,15 +752,24 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
             NS6_T_BEGIN;
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
-            const int f = i - 8;
-            if (beat_flag<V, ns6plan::G1, 8, 5, STEADY>(i, onset, nfr)) {
+            const int f = i - 8 - kS1;
+            if constexpr (IDCTS) {
+                /* the 17-tap filter of frame i-11, whose windowed taps S left at the previous iteration, ahead of the
+                 * gains of frame i-9: the two do not depend on each other.  Also in the drain, where no gains are left. */
+                const int ff = i - 11;
+                if (beat_flag<V, ns6plan::G1, 11, 5, STEADY>(i, onset, nfr))
+                    ns_fir_from_taps(X->tap[1][ff & 1], L.back[1].fir, L.circ1 + window_base<kSlots1>(tick_of(ff, onset)), L.ro[ff & 1].out, lane);
+            }
+            if (beat_flag<V, ns6plan::G1, 8 + kS1, 5, STEADY>(i, onset, nfr)) {
                 const float *psd = L.p1[f & (kP1Ring - 1)].psd;
                 const RecN &r = L.rn[f & (kRnRing - 1)];
                 RecOut &o = L.ro[f & 1];
                 const int t = tick_of(f, onset);
                 const float alfa = L.alfa[f & 1];
                 const float *w64 = BIN64 ? &L.w1hi[f & (kW1Ring - 1)] : nullptr; /* B0 left it two beats ago */
-                if (DIFG1)
+                if constexpr (IDCTS)
+                    ns_gain1_products(psd, r.P, r.noise, alfa, L.back[1], s, C, X->prod[1][f & 1], lane, basisQ, w64);
+                else if (DIFG1)
                     ns_gain1_dif(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT, lastIn);
                 else
                     ns_gain1<BIN64>(psd, r.P, r.noise, alfa, L.circ1 + window_base<kSlots1>(t), L.back[1], s, C, o.out, lane, L.idctT, w64);
@@ -651,6 +787,32 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
         float dcX = 0.0f, dcY = 0.0f; /* prevSamples, NoiseSup.c:908-909 */
         int firstOut = -1;
         int onset = kNoOnset;
+        HelperIdct ids = {}; /* IDCTS: the lane's constants of helper_chains<.., IDS> */
+        if constexpr (IDCTS) {
+            static_assert(!IDCTS || !DIFG1, "the DC lanes read sdif");
+            char *const lds = reinterpret_cast<char *>(&L);
+            auto at = [&](const void *q) { return (int)(reinterpret_cast<const char *>(q) - lds); };
+            const int g = lane >> 4, t = (lane - 1) & 15; /* lanes 1 + t and 17 + t, t = 0..8, have row t */
+            const bool row = t <= 8 && g <= 1;
+            constexpr int kProd = sizeof(X->prod[0][0]), kTap = sizeof(X->tap[0][0]), kRowB = kIdctStride * sizeof(float), kTapB = kIdsTapStride * sizeof(float);
+            ids.lds = lds;
+            ids.rowZeros = at(X->zeros) - kIdctRow * (int)sizeof(float);
+            if (row) { /* stage 0: the records of parity p; stage 1: those of the other parity */
+                ids.src0 = (g == 0 ? at(X->prod[0][0]) : at(X->prod[1][1])) + kRowB * t;
+                ids.srcP = g == 0 ? kProd : -kProd;
+                ids.end = ids.rowZeros;
+                ids.tap0 = (g == 0 ? at(X->tap[0][0]) : at(X->tap[1][1])) + kTapB * t;
+                ids.tapP = g == 0 ? kTap : -kTap;
+            } else {
+                ids.src0 = g == 0 ? at(L.ssq) : (g == 1 ? at(L.rd[0].den) : (g == 2 ? at(L.sdif) : at(L.rn[0].noise)));
+                ids.srcP = g == 1 ? (int)sizeof(RecDen) : 0;
+                ids.srcQ = g == 3 ? (int)sizeof(RecN) : 0;
+                ids.end = (g == 1 || g == 3) ? at(X->zeros) - 68 * (int)sizeof(float) : ids.src0;
+            }
+            ids.hann = a.tables->irWin[t];
+            ids.m = g == 2 ? 0.9990234375f : 1.0f;
+            ids.acc0 = (g == 0 && !row) ? 64.0f : 0.0f;
+        }
         auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
             constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
@@ -660,9 +822,11 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
              *     tick tp+2); (2) in-order sum of denSigSE1 of the frame B0 finished at i-1; (3) DC-offset
              *     filter, int16 cast, store of the frame G1 finished at i-1; (4) in-order sum of the noise
              *     spectrum N1 left at i-1 */
-            const int fp = i - 1, fd = i - 3, fn = i - 6, fo = i - kDepth;
+            const int fp = i - 1, fd = i - 3, fn = i - 6 - kS1, fo = i - DEPTH;
             const bool doVad = beat_flag<V, ns6plan::S, 1, 1, STEADY>(i, onset, nfr), doDen = beat_flag<V, ns6plan::S, 3, 3, STEADY>(i, onset, nfr),
-                       doNz = beat_flag<V, ns6plan::S, 6, 5, STEADY>(i, onset, nfr), produced = beat_flag<V, ns6plan::S, kDepth, 5, STEADY>(i, onset, nfr);
+                       doNz = beat_flag<V, ns6plan::S, 6 + kS1, 5, STEADY>(i, onset, nfr), produced = beat_flag<V, ns6plan::S, DEPTH, 5, STEADY>(i, onset, nfr);
+            bool doIdct1 = false; /* IDCTS: the stage-1 IDCT sums of the frame G1 left its products of at i-1; the stage-0 sums go with doDen */
+            if constexpr (IDCTS) doIdct1 = beat_flag<V, ns6plan::S, 10, 5, STEADY>(i, onset, nfr);
             const int tp = tick_of(fp, onset), td = tick_of(fd, onset);
             const float *denSrc = L.rd[(STEADY || (fd >= 0 && fd < nfr)) ? (fd & 1) : 0].den;
             const float *nzSrc = L.rn[fn & (kRnRing - 1)].noise;
@@ -690,11 +854,20 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                 }
             }
             if (doVad) *reinterpret_cast<float2 *>(L.ssq + 2 * l2) = make_float2(sqIn.x * sqIn.x, sqIn.y * sqIn.y);
-            if (doVad || doDen || doNz || produced) {
+            if (doVad || doDen || doNz || doIdct1 || produced) {
                 wave_sync();
                 float vadSum, denTotal, nzTotal, y = dcY;
-                helper_chains<kSChunks, false, true>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane, nullptr, nullptr,
-                                                     nullptr, nzSrc, &nzTotal);
+                if constexpr (IDCTS) {
+                    /* the taps are stored whatever the flags say: a record whose frame does not exist is read by nobody (FA's and
+                     * G1's flags are these flags one beat on), and its slot's previous content was read at the previous iteration */
+                    static_assert(((10 - 3) & 1) == 1, "S's two product records of a beat have opposite frame parities");
+                    ids.p = fd & 1;
+                    ids.q = fn & (kRnRing - 1);
+                    helper_chains<kSChunks, false, true, true>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane, nullptr, nullptr,
+                                                               nullptr, nzSrc, &nzTotal, &ids);
+                } else
+                    helper_chains<kSChunks, false, true>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane, nullptr, nullptr,
+                                                         nullptr, nzSrc, &nzTotal);
                 if (doVad) {
                     const float en = (LIGHT || LOG_N1) ? vadSum : vad_frame_energy(vadSum); /* FA (LIGHT) or N1 takes the log one beat later */
                     if (lane == 0) L.frameEn[(tp + 2) & (kSlots - 1)] = en;
@@ -717,7 +890,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L)
                     (out32 + (long long)fo * 40)[lane] = packed;
                 }
                 if constexpr (FD) { /* the speech flags B0 left for this frame seven beats ago: the plan's fifth flag of S */
-                    if (beat_flag<V, ns6plan::S, kDepth, 5, STEADY>(i, onset, nfr) && lane == 0 && a.flags_out)
+                    if (beat_flag<V, ns6plan::S, DEPTH, 5, STEADY>(i, onset, nfr) && lane == 0 && a.flags_out)
                         a.flags_out[off / 8 + 10 * (long long)fo] = (unsigned char)L.fdFlags[tick_of(fo, onset) & (kSlots - 1)];
                 }
                 wave_sync();
@@ -758,7 +931,7 @@ __device__ unsigned g_ns6_wg[16384 * 4]; /* dense form, per workgroup: start, en
 #endif
 __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchArgs a)
 {
-    __shared__ p6::Pipe6Lds L;
+    __shared__ p6::Pipe6LdsIdct L;
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) {
         g_ns6_wg[4 * blockIdx.x] = (unsigned)wall_clock64();
@@ -766,7 +939,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false, true, true, true>(a, L);
+    p6::ns_pipe6_body<false, false, false, true, true, true, true>(a, L.base, &L.x);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
