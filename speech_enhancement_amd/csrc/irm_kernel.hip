@@ -10,7 +10,8 @@
  * PARITY UNPINNED: asdk::SpecInfo (the reference's spectrum routine) is absent third-party code; its analysis
  * window is a parameter here (0 rectangular, 1 Hamming, 2 Hanning).  The oracle (oracle/resynth_oracle.c,
  * ora_irm_target) evaluates the same definition as a direct double-precision DFT; the float transform here agrees
- * with it to ~1e-6 relative (tests/test_gpu_parity.py::test_irm_target_vs_oracle, tolerance 1e-4).
+ * with it and with the float64 model of tests/irm_model.py to a few 1e-7 (tests/test_gpu_irm.py, tests/test_gpu_parity.py::
+ * test_irm_target_vs_oracle; the tolerance is IRM_TOL of tests/irm_cases.py, derived in tests/test_irm_cpu.py).
  */
 #include "sea_device.h"
 #include "sea_kernels.h"
@@ -28,7 +29,8 @@ namespace sea {
  * v_permlane32_swap (gfx950) so that each row ends with a quarter of the bins; powers, the 64-bin sum, the ratio.
  * The samples of a 16-frame tile (17 half-frames = 2720 int16, one coalesced read) are staged in LDS as four polyphase planes:
  * lane (r, f) reads 160 contiguous bytes of plane r -- ten ds_read_b128, conflict-free within each row (80 f bytes apart: sixteen
- * different 16-byte slots of the 256-byte bank row).  The float operation order is the codelet's (parity unpinned, 1e-4). */
+ * different 16-byte slots of the 256-byte bank row).  The float operation order is the codelet's (parity unpinned, within IRM_TOL of
+ * tests/irm_cases.py; tests/irm_kernel_driver.cpp restates it on the host). */
 namespace {
 constexpr int kTileF = 16;                           /* frames per tile */
 constexpr int kTileS = 160 * (kTileF + 1);           /* samples per tile: 2720 */

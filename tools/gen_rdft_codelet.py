@@ -11,7 +11,9 @@ sub-transforms (only k = 0 .. n/2 of each is ever built; X[n/2 - k] = conj(E[k] 
 X[k] = E[k] + w^k O[k]); signs are carried beside the nodes (negation is an operand modifier on the device), constants fold,
 x + 0 / x * 0 / x * 1 vanish -- so the zero padding and the trivial twiddles cost nothing -- dead code is dropped, and a
 product with a single use is fused into its consumer as an FMA.  The float arithmetic order is this script's, not any
-reference's: the IRM target's parity is unpinned with a 1e-4 tolerance, which is what makes the freedom legal.
+reference's: the IRM target's parity is unpinned and held to IRM_TOL of tests/irm_cases.py, which tests/test_irm_cpu.py
+derives from this codelet's own float error; that is what makes the freedom legal.  The same test runs this script and compares its
+output with the committed csrc/irm_rdft128.inc byte for byte.
 """
 import math
 import sys
