@@ -72,6 +72,17 @@
  * 80 FMAs of the listing, 113 before: the three bases are set before it), and the map was swept again (kRedealPerm).  configs[1]:
  * 1.61 -> 1.47 ms = 555 M frames/s (profiles/ns6_idct_in_helper.txt).
  *
+ * Round 12, all three kernels (PAIRED of ns_pipe6_body, run_beats): the steady beats run two by two, an even beat and the odd one
+ * after it, so the frame parity is a constant of each copy.  Every record that is double-buffered by parity gets its address as an
+ * instruction offset, and FB (FA but for its register-resident start) keeps the transform's operand addresses unpacked in registers: the
+ * eight `base + packed half-word` additions in front of every level's LDS reads are gone.  Same operations, same order.  Dense kernel:
+ * 1169 -> 1088 vector and 349 -> 314 scalar instructions per frame, configs[1] 1.49 -> 1.41 ms (1.456 -> 1.377 over 200 steps) =
+ * 594 M frames/s; the plain kernel takes the steady copies with it.  What that issue set out to do -- FA and FB on the latency form of
+ * the transform (the four-wave F wave's since round 3) and N1's two logarithms in one lane-split pass -- was built, measured and
+ * dropped: FB's role 2490 -> 2350 clk but the step 1.479 -> 1.501 ms, FA 1.479 -> 1.496, both 1.479 -> 1.520, the logarithm pair
+ * 1.479 -> 1.486 with N1 2440 -> 2585 clk, none better under its own best wave -> role map; the step follows the instruction count, not
+ * the longest role: all four launch rows end together (profiles/ns6_transform_chain.txt).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -187,7 +198,16 @@ __device__ __forceinline__ bool tick_ge(int f, int k, int onset, int nfr) { retu
  *   FA: steady_end(FA) = nfr - 1 (RolePlan::ahead), so a steady beat's prefetch of frame i + 1 stays inside the utterance -- for the
  *     last utterance of the batch that is the end of the packed buffer.
  *   S: steady_begin(S) = onset + 14 (RolePlan::settle): the first produced frame is onset + 4 at beat onset + 13, in the general
- *     copy, which sets firstOut; the steady copy never touches it. */
+ *     copy, which sets firstOut; the steady copy never touches it.
+ *   PAIRED (round 12): the steady beats run two by two, an even beat and the odd one after it, written as beat(2h), beat(2h + 1).  The
+ *     frame parity -- by which the records between the roles and the two transform work areas are double-buffered -- is then a
+ *     constant of each of the two copies: every `(i - k) & 1` folds, record addresses become instruction offsets, and the compiler
+ *     keeps the transform's operand addresses unpacked in registers instead of forming base + packed half-word before every LDS
+ *     access.  The general copy is valid on every beat, so a steady range that begins on an odd beat gives its first beat to the
+ *     general copy (the test `(i & 1) == 0` fails once, the statement behind it runs beat<false>(i) and ++i, and the range is entered
+ *     on the next pass), and one that ends behind an even beat its last (h stops at e >> 1, i = 2h = e - 1 < e).  Each call still
+ *     executes one barrier and i goes up by one per call, so the barrier count above holds; the steady copies only ever see
+ *     steady_begin <= i < steady_end, as before. */
 template <bool B>
 struct BoolC {
     static constexpr bool value = B;
@@ -199,14 +219,24 @@ __device__ __forceinline__ bool beat_flag(int i, int onset, int nfr)
     static_assert(ns6plan::has_flag(VARIANT, ROLE, D, K), "a flag the beat plan of ns6_beat_plan.h does not know");
     return STEADY || tick_ge(i - D, K, onset, nfr);
 }
-template <bool STEADY_LOOP, unsigned VARIANT, int ROLE, class Beat>
+template <bool STEADY_LOOP, unsigned VARIANT, int ROLE, bool PAIRED = false, class Beat>
 __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, Beat &&beat)
 {
     int i = 0;
     while (i < niter) {
         if (STEADY_LOOP && i >= ns6plan::steady_begin(VARIANT, ROLE, onset)) {
             const int e0 = ns6plan::steady_end(VARIANT, ROLE, nfr), e = e0 < niter ? e0 : niter;
-            for (; i < e; ++i) beat(BoolC<true>{}, i);
+            if constexpr (PAIRED) {
+                if ((i & 1) == 0) { /* an odd beat in front goes through the general copy below, and so does one left over behind */
+                    int h = i >> 1;
+                    for (const int he = e >> 1; h < he; ++h) {
+                        beat(BoolC<true>{}, 2 * h);
+                        beat(BoolC<true>{}, 2 * h + 1);
+                    }
+                    i = 2 * h;
+                }
+            } else
+                for (; i < e; ++i) beat(BoolC<true>{}, i);
         }
         if (i < niter) {
             beat(BoolC<false>{}, i);
@@ -428,12 +458,14 @@ template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands
           bool STEADY_LOOP /* the flag-free copy of every role's beat on its steady range (run_beats) */,
           bool REDEAL = false /* round 8, the dense kernel: feed-forward work of S and B0 in the waves that wait, and the map that goes with it */,
           bool BIN64 = false /* round 10, the dense kernel: stage-1 bin 64 rides in B0's second component, one domain flag per stage-1 frame */,
-          bool IDCTS = false /* round 11, the dense kernel: both stages' IDCT sums ride in the helper wave's idle lanes; X is its LDS */>
+          bool IDCTS = false /* round 11, the dense kernel: both stages' IDCT sums ride in the helper wave's idle lanes; X is its LDS */,
+          bool PAIRED = false /* round 12, all three kernels: the steady beats two by two, the frame parity a constant of each copy (run_beats) */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L, Pipe6Idct *X = nullptr)
 {
     static_assert(!REDEAL || (!LIGHT && !DIFG1), "the re-deal is a variant of the dense body");
     static_assert(!BIN64 || (REDEAL && !FD), "the guest of B0's second component is a variant of the re-dealt dense body");
     static_assert(!IDCTS || BIN64, "the IDCT sums in the helper wave are a variant of that body in turn");
+    static_assert(!PAIRED || STEADY_LOOP, "the paired beats are the steady copies'");
     constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u) |
                            (BIN64 ? ns6plan::kBin64 : 0u) | (IDCTS ? ns6plan::kIdctS : 0u);
     static_assert(!BIN64 || V == (IDCTS ? ns6plan::kVariantDenseIdct : ns6plan::kVariantDenseBin64),
@@ -593,13 +625,21 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
                 wave_sync();
                 float e[8];
                 ns_window8(L.circ0 + window_base<kSlots>(tick), actA, L.circ1 + window_base<kSlots1>(t1), actB, win8, lane, e);
+                if constexpr (STEADY && PAIRED && !FD) {
+                    /* FA is the register-bound role of the 72-VGPR dense and of the 80-VGPR plain kernel: with all twelve address words
+                     * of its transform half unpacked (run_beats, PAIRED) it spills five and four VGPRs there.  The four words of the
+                     * register-resident start stay packed -- an empty statement that "changes" them every beat, so their halves cannot
+                     * be taken out of the loop.  The _fd kernel has the registers (launch bound of two waves per SIMD). */
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) asm volatile("" : "+v"(fft.head8[q]));
+                }
                 rfft256_dual_lo<false>(e, L.work[i & 1], fft);
             }
             NS6_T_MID;
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::FA>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::FA, PAIRED>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
         if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset == kNoOnset ? nfr : onset;
     } else if (role == 1) {
@@ -629,7 +669,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::FB>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::FB, PAIRED>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else if (role == 2) {
         /* ---- B0: BACK of stage 0; its 80 outputs enter the stage-1 buffer ---- */
@@ -695,7 +735,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::B0>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::B0, PAIRED>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else if (role == 3) {
         /* ---- N1: stage-1 noise tracking of frame i-5; gain-factor scalars of frame i-7, whose noise sum S took in between ---- */
@@ -737,7 +777,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::N1>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::N1, PAIRED>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else if (role == 4) {
         /* ---- G1: stage-1 Wiener gains, mel, gain factorisation, IDCT, FIR ---- */
@@ -778,7 +818,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::G1>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::G1, PAIRED>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
     } else {
         /* ---- S: the lane-grouped scalar chains (helper_chains) ---- */
@@ -899,7 +939,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::S>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::S, PAIRED>(niter, nfr, onset, beat);
         NS6_T_FLUSH(role, niter);
         if (a.first_out && lane == 0) a.first_out[u] = firstOut;
     }
@@ -912,12 +952,15 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
  * per frame with the looser bound, which only changes the schedule); the _fd form takes the looser bound, which
  * removes its 7 spilled registers (91 VGPRs).  Today the plain form takes 68 VGPRs, nothing spilled, and the _fd form 93 with 6 SGPRs
  * spilled to lanes (82 and none before round 9's batches), no scratch.
- * STEADY_LOOP: off here -- with the steady copies this form ran 2.1 % (256 utterances) and 2.6 % (768) slower, its period is B0's beat,
- * the one role they did not shorten; on in the dense form (-2.9 %) and in the _fd form (-1.9 %).  profiles/ns6_steady_loop.txt */
+ * STEADY_LOOP: round 7 left it off here -- with the steady copies alone this form ran 2.1 % (256 utterances) and 2.6 % (768) slower, its
+ * period is B0's beat, the one role they did not shorten; on in the dense form (-2.9 %) and in the _fd form (-1.9 %),
+ * profiles/ns6_steady_loop.txt.  Round 12: on, with the beats paired (PAIRED), in all three: 256 utterances 1.416 -> 1.321 ms, 768
+ * 1.566 -> 1.434, the _fd kernel on 512 2.488 -> 2.403 (profiles/ns6_transform_chain.txt).  The plain form now takes its whole bound
+ * of 80 VGPRs and the _fd form 95 with 14 SGPRs spilled to lanes; nothing in scratch. */
 __global__ __launch_bounds__(384, 6) void ns_denoise_pipe6_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
-    p6::ns_pipe6_body<false, true, true, false>(a, L);
+    p6::ns_pipe6_body<false, true, true, true, false, false, false, true>(a, L);
 }
 /* The same body compiled for SEVEN waves per SIMD (72 VGPRs, two SGPRs spilled to lanes, no scratch; since round 8 with REDEAL and its own
  * wave -> role map): the form for three or four utterances per CU (round 4).  With 80 VGPRs a SIMD holds six waves, four six-wave workgroups are exactly the 24 a CU then holds -- and the
@@ -939,7 +982,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false, true, true, true, true>(a, L.base, &L.x);
+    p6::ns_pipe6_body<false, false, false, true, true, true, true, true>(a, L.base, &L.x);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
@@ -947,7 +990,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
 __global__ __launch_bounds__(384, 2) void ns_denoise_pipe6_fd_kernel(NsBatchArgs a)
 {
     __shared__ p6::Pipe6Lds L;
-    p6::ns_pipe6_body<true, true, true, true>(a, L);
+    p6::ns_pipe6_body<true, true, true, true, false, false, false, true>(a, L);
 }
 
 } // namespace sea
