@@ -666,8 +666,8 @@ int sea_hw25_resynth_text_write(const char *path, const float *out, long L);
  * HuWang.h (SAMPLING_FREQUENCY 16000, NUMBER_CHANNEL 64, MINCF 50, MAXCF 8000, WINDOW 320, OFFSET 160, MAX_DELAY 201, MIN_DELAY
  * 32), the bank of sea_subband64_batch / sea_resynth64_batch / sea_irm_target_batch (csrc/hw64_kernel.hip, DESIGN.md section
  * 5.16).  Parity: bit for bit against the reference's own functions compiled on a CPU against that header
- * (tests/golden/hw64_*.npz).  initGroup and pitchDtm follow below (sea_hw64_pitch_*); computeAM onwards (finalSeg, resynthesis)
- * is NOT built at 16 kHz.
+ * (tests/golden/hw64_*.npz).  initGroup and pitchDtm follow below (sea_hw64_pitch_*), then computeAM, finalSeg and the whole
+ * estimator (sea_hw64_am_batch, sea_hw64_finalseg_batch, sea_hw64_ibm*); only resynthesis() is NOT built at 16 kHz.
  * The calls mirror the sea_hw25_* front-half calls argument for argument, with 64 / 201 / 160 for 25 / 101 / 80: d_hout / d_hev
  * (and d_gout, the gammatone output before the hair cell; null: not written) hold 64x the packed size, utterance u's
  * [64][pitch] block at d_offsets[u] * 64; utterance u has sea_hw64_frames (lengths[u]) = lengths[u] / 160 rows from
@@ -725,6 +725,37 @@ int sea_hw64_pitch_batch(const float *d_acf_hc, const float *d_pratio_in, const 
                          const long long *d_row_offsets, int *d_pitch, float *d_grp, float *d_pratio, int *d_status, void *d_stages,
                          void *d_scratch, const int *d_order, int n_utt, void *stream);
 int sea_hw64_pitch(const float *x, long L, int *pitch, float *grp, float *pratio, int *status);
+/* createIBM():89-106 on the same bank: computeAM, finalSeg and the binarisation as sea_hw25_am_batch, sea_hw25_finalseg_batch and
+ * sea_hw25_ibm* have them (see there for the functions, the outputs' meaning, the optional outputs, d_scratch, the status bits
+ * and the parity of ratio), at 64 channels and a hop of 160 (csrc/hw64_am_kernel.hip).  After it
+ * sea_hw64_ibm (x) is createIBM (x) compiled against resyth_64sub_IBM/cpp/HuWang.h.  Each call mirrors its sea_hw25_* namesake
+ * argument for argument, with 64 / 160 for 25 / 80: d_gout, d_ampatt and d_am in sea_hw64_periphery_batch's layout, the frame
+ * arrays [rows][64], utterance u's lengths[u] / 160 rows from d_row_offsets[u], d_stages utterance u's [SEA_HW25_FINAL_STAGES]
+ * [rows_u][64] floats at float d_row_offsets[u] * SEA_HW25_FINAL_STAGES * 64.  What the constants change: WINDOW is 320, exactly
+ * two hops, so frame f's window is [160 (f - 1), 160 (f + 1)); sinModel's frequency is 16000 / pitch; d_pitch holds 0 or
+ * 32..200, and a pitch of 201 or more is SEA_HW25_AM_BAD_PITCH; amPatt's filter has up to 1119 taps.  The FFT's two complex
+ * buffers take 2048 bytes per padded sample for 64 channels: all channels at once while that stays under 256 MiB (up to 131 072
+ * padded samples), else eight groups of eight channels; total_padded_samples alone decides, and
+ * sea_hw64_am_scratch_bytes shows which.  The status bits and the cases where the reference is undefined (more than
+ * 150000 samples, no voiced frame, fewer than three rows, a length of 0, more than 400 segments) are those of the 25-band calls;
+ * the refusals too: null pointers, and an output that is an input or another output, the status array included.  Nothing
+ * synchronises with the host and every launch is on `stream`.
+ * Parity (tests/golden/hw64_am_golden.npz, the reference's own functions compiled on a CPU against the 64-band header): gOut,
+ * the AM pattern before and after its normalisation, sEng, AmCrn, every stage of finalSeg and the mask bit for bit; ratio to the
+ * fixture's ratio_tol, and no unit of the fixture within that band of THETAE. */
+long long sea_hw64_am_scratch_bytes(long long total_padded_samples, int n_utt);
+int sea_hw64_am_batch(const float *d_gout, const int *d_pitch, const long long *d_offsets, const long long *d_lengths,
+                      const long long *d_row_offsets, float *d_amcrn, float *d_ratio, float *d_seng, float *d_ampatt, float *d_am,
+                      int *d_status, void *d_scratch, long long total_padded_samples, const int *d_order, int n_utt, void *stream);
+long long sea_hw64_finalseg_scratch_bytes(long long total_rows, int n_utt);
+int sea_hw64_finalseg_batch(const float *d_grp, const float *d_amcrn, const float *d_cross_ev, const float *d_pratio,
+                            const long long *d_lengths, const long long *d_row_offsets, float *d_mask, float *d_grp_final,
+                            int *d_status, float *d_stages, void *d_scratch, const int *d_order, int n_utt, void *stream);
+long long sea_hw64_ibm_scratch_bytes(long long total_padded_samples, long long total_rows, int n_utt);
+int sea_hw64_ibm_batch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
+                       float *d_mask, int *d_pitch, int *d_status, float *d_stages, void *d_scratch, long long total_padded_samples,
+                       long long total_rows, const int *d_order, int n_utt, void *stream);
+int sea_hw64_ibm(const float *x, long L, float *mask, int *pitch, int *status);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

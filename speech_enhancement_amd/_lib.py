@@ -121,6 +121,13 @@ PROTOTYPES = {
     "sea_hw64_pitch_waves_per_utterance": (_i, [_i]),
     "sea_hw64_pitch_batch": (_i, [_vp] * 12 + [_i, _vp]),
     "sea_hw64_pitch": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
+    "sea_hw64_am_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw64_am_batch": (_i, [_vp] * 12 + [_ll, _vp, _i, _vp]),
+    "sea_hw64_finalseg_scratch_bytes": (_ll, [_ll, _i]),
+    "sea_hw64_finalseg_batch": (_i, [_vp] * 12 + [_i, _vp]),
+    "sea_hw64_ibm_scratch_bytes": (_ll, [_ll, _ll, _i]),
+    "sea_hw64_ibm_batch": (_i, [_vp] * 9 + [_ll, _ll, _vp, _i, _vp]),
+    "sea_hw64_ibm": (_i, [_vp, _l, _vp, _vp, _vp]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -1,6 +1,6 @@
 /*
  * hw25_capi.h -- what the translation units behind the Hu-Wang C ABI share (capi.hip, hw25_pitch_capi.hip, hw25_am_capi.hip,
- * hw25_resynth_capi.hip, hw64_capi.hip): the single-utterance forms' batch of one, the refusal of outputs that are inputs, and where the
+ * hw25_resynth_capi.hip, hw64_capi.hip, hw64_pitch_capi.hip, hw64_am_capi.hip): the single-utterance forms' batch of one, the refusal of outputs that are inputs, and where the
  * whole estimator keeps gOut.
  */
 #pragma once

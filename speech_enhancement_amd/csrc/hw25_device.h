@@ -2,8 +2,9 @@
  * hw25_device.h -- what the Hu-Wang kernel files share on the device: the gammatone recurrence of the analysis
  * (hw25_kernel.hip, hw64_kernel.hip) and of the resynthesis that inverts it (hw25_resynth_kernel.hip), the hair cell's step of
  * both banks' analysis, and the constants, the lane fence and
- * the label propagation of the estimator's two segmentations, initGroup's (hw25_pitch_kernel.hip) and finalSeg's
- * reSegmentation (hw25_am_kernel.hip).
+ * the label propagation of the estimator's two segmentations, initGroup's (hw25_pitch_kernel.hip, hw64_pitch_kernel.hip) and
+ * finalSeg's reSegmentation (hw25_am_kernel.hip, hw64_am_kernel.hip), over 25 and over 64 lanes, and what both banks' AM stage
+ * shares: the utterance decode, N of the FFT, bessi0, and the bodies of the FFT's global stages and of the normalisation.
  */
 #pragma once
 #include <hip/hip_runtime.h>
@@ -127,5 +128,139 @@ __device__ __forceinline__ void hw25_label_components(int *lab, int F, int lane)
         again = __any(changed);
     }
 }
+
+/* hw25_label_components with a channel in every lane, for the 64-channel bank's two segmentations (hw64_pitch_kernel.hip,
+ * hw64_am_kernel.hip).  lab [F][64]: the unit's own index where it is marked, kHw25None elsewhere.  On return every marked
+ * unit holds the smallest unit index of its 4-connected component.  A frame takes the label of the frame before it in sweep
+ * direction (carried in registers), then every run of marked channels takes its minimum: a prefix minimum over the 64 lanes
+ * that stops at the run's start, read back from the run's end.  Forward and backward sweeps until neither changes anything.
+ * The caller fences before and after. */
+__device__ __forceinline__ void hw64_label_components(int *lab, int F, int lane)
+{
+    constexpr int kCh = SEA_HW64_NCHAN;
+    bool again = true;
+    while (again) {
+        bool changed = false;
+        for (int dir = 0; dir < 2; ++dir) {
+            int carry = kHw25None;
+            for (int k = 0; k < F; ++k) {
+                const int f = dir ? F - 1 - k : k;
+                const int old = lab[f * kCh + lane];
+                int v = old;
+                if (v != kHw25None && carry < v) v = carry;
+                const unsigned long long m = __ballot(v != kHw25None);
+                /* the run [start, end] of marked channels around this lane */
+                const unsigned long long below = ~m & ((1ull << lane) - 1ull);
+                const int start = below ? 64 - __clzll((long long)below) : 0;
+                const unsigned long long above = lane < 63 ? (~m >> (lane + 1)) : 0ull;
+                const int end = above ? lane + (__ffsll((long long)above) - 1) : 63;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int o = __shfl_up(v, d);
+                    if (lane - d >= start && o < v) v = o;
+                }
+                const int r = __shfl(v, end);
+                if (old != kHw25None) {
+                    v = r;
+                    if (v != old) {
+                        lab[f * kCh + lane] = v;
+                        changed = true;
+                    }
+                } else {
+                    v = kHw25None;
+                }
+                carry = v;
+            }
+        }
+        again = __any(changed);
+    }
+}
+
+/* ---- what the AM stage of both banks shares (hw25_am_kernel.hip, hw64_am_kernel.hip): the utterance a workgroup works on, N
+ * of the FFT, bessi0, and the bodies of the FFT's global stages and of the normalisation kernel, which know of the bank only its channel count (in
+ * two address expressions) and its hop.  Args is Hw25AmArgs (sea_kernels.h).  Internal to each unit, as they were in
+ * hw25_am_kernel.hip. ---- */
+namespace {
+
+/* computeAM:1156 for lengths 240 .. 150000: the integer ceil (log2 (L)), and at a power of two the constant that the
+ * reference's double expression gave on a CPU (SEA_HW25_N_AT_POW2) */
+__device__ __forceinline__ int fft_log2(long long L)
+{
+    constexpr int at_pow2[11] = SEA_HW25_N_AT_POW2;
+    const int up = 64 - __clzll(L - 1);
+    if ((L & (L - 1)) == 0 && up >= 7 && up <= 17) return at_pow2[up - 7];
+    return up;
+}
+
+struct AmUtt {
+    int u, nfr, N;
+    long long off, L, pitch, row0;
+};
+template <int kHop, class Args>
+__device__ __forceinline__ AmUtt am_utterance(const Args &a)
+{
+    AmUtt t;
+    t.u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
+    t.off = a.offsets[t.u];
+    t.L = a.lengths[t.u];
+    t.pitch = (t.L + 7) & ~7LL;
+    t.nfr = t.L > 0 ? (int)(t.L / kHop) : 0;
+    t.row0 = a.row_offsets[t.u];
+    t.N = a.info[t.u];
+    return t;
+}
+
+/* bessi0:1603-1614, its polynomial branch (|x| < 3.75 always: beta < 3.75 and the square root is at most 1) */
+__device__ __forceinline__ float bessi0_small(float x)
+{
+    float y = (float)((double)x / 3.75);
+    y *= y;
+    const double d = y;
+    return (float)(1.0 + d * (3.5156229 + d * (3.0899424 + d * (1.2067492 + d * (0.2659732 + d * (0.360768e-1 + d * 0.45813e-2))))));
+}
+
+/* stage a.stage (above kLdsLog2) in place over global memory: the butterflies of one stage touch disjoint pairs */
+template <int kCh, int kHop, class Args>
+__device__ __forceinline__ void am_fft_stage(const Args &a)
+{
+    const int z = blockIdx.z, c = a.chan0 + z, n = a.stage;
+    const AmUtt t = am_utterance<kHop>(a);
+    if (t.N < n || c >= kCh) return;
+    const long long half = 1LL << (t.N - 1);
+    const long long period = 1LL << (n - 1);
+    float2 *x = (a.inverse ? a.fb : a.fa) + t.off * a.chunk * 2 + (long long)z * 2 * t.pitch;
+    const float2 *tw = a.tw + (period - 1);
+    const float sign = a.inverse ? -1.0f : 1.0f;
+    for (long long b = (long long)blockIdx.y * 256 + threadIdx.x; b < half; b += (long long)gridDim.y * 256) {
+        const long long j = b & (period - 1);
+        const long long i = ((b >> (n - 1)) << n) + j;
+        const float uR = tw[j].x, uI = sign * tw[j].y;
+        const float2 lo = x[i], hi = x[i + period];
+        const float tmpR = hi.x * uR - hi.y * uI;
+        const float tmpI = hi.x * uI + hi.y * uR;
+        x[i + period] = make_float2(lo.x - tmpR, lo.y - tmpI);
+        x[i] = make_float2(lo.x + tmpR, lo.y + tmpI);
+    }
+}
+
+/* computeAM:1177-1178: sqrtf of a float, a float over (float) sigL, then a double sum and a double quotient rounded to float */
+template <int kCh, int kHop, class Args>
+__device__ __forceinline__ void am_norm(const Args &a)
+{
+    const int z = blockIdx.z, c = a.chan0 + z;
+    const AmUtt t = am_utterance<kHop>(a);
+    if (t.N < 0 || c >= kCh) return;
+    const float sigL = (float)(1LL << t.N);
+    const float2 *x = a.fb + t.off * a.chunk * 2 + (long long)z * 2 * t.pitch;
+    const float *pat = a.ampatt + t.off * kCh + c * t.pitch;
+    float *am = a.am + t.off * kCh + c * t.pitch;
+    for (long long n = (long long)blockIdx.y * 256 + threadIdx.x; n < t.L; n += (long long)gridDim.y * 256) {
+        const float2 v = x[n];
+        const float env = sqrtf(v.x * v.x + v.y * v.y) / sigL;
+        am[n] = (float)((double)pat[n] / ((double)env + 1e-30));
+    }
+}
+
+} // namespace
 
 } // namespace sea

@@ -1,24 +1,28 @@
 /*
- * hw25_am_kernel.hip -- the Hu-Wang estimator's AM labels and final grouping on the 25-channel 8 kHz bank, gfx950:
- * computeAM:1146-1317 (amPatt, hilbert, computeAMRate, sinModel, with kaiserPara / kaiserBandPass / bessi0 / fft:1553-1677),
- * finalSeg:1321-1494 (reSegmentation, develope) and the binarisation :99-106 of
- * function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp.  A first form, not tuned.  DESIGN.md section 5.13.
+ * hw64_am_kernel.hip -- the Hu-Wang estimator's AM labels and final grouping at 16 kHz on the 64-channel bank, gfx950:
+ * createIBM():89-106 of function/20141106_speech_enhancement/aurora_etsi_test/HuWang.cpp at the constants of resyth_64sub_IBM/cpp/
+ * HuWang.h (NUMBER_CHANNEL 64, OFFSET 160, WINDOW 320, SAMPLING_FREQUENCY 16000), that is computeAM:1146-1317 (amPatt, hilbert,
+ * computeAMRate, sinModel, with kaiserPara / kaiserBandPass / bessi0 / fft:1553-1677), finalSeg:1321-1494 (reSegmentation,
+ * develope) and the binarisation.  The mapping is hw25_am_kernel.hip's.  Those functions hold no literal channel count or
+ * rate, so what the constants change is restated, not templated: the pattern, rate and final-grouping kernels, and the FFT's
+ * head; the FFT's global stages and the normalisation share their bodies with the 25-band unit (hw25_device.h).  A first form,
+ * not tuned.  DESIGN.md section 5.18.
  *
- *   hw25_am_prepare_kernel    per utterance: N of the FFT, whether the stage runs at all, the status flags; the outputs of an
+ *   hw64_am_prepare_kernel    per utterance: N of the FFT, whether the stage runs at all, the status flags; the outputs of an
  *                             utterance that skips the stage are zeroed here
- *   hw25_am_patt_kernel       amPatt: per block of five frames the Kaiser band-pass for the block's mean pitch (taps computed
- *                             in the workgroup, lane = tap), then the FIR over max (gOut, 0), lane = sample
- *   hw25_am_fft_head_kernel   fft's bit reversal and its stages 1..12 on 4096 points in LDS; the inverse form applies hilbert's
- *                             doubling and zeroing to what it loads
- *   hw25_am_fft_stage_kernel  one of the stages 13..18 over global memory; utterances with a smaller N leave
- *   hw25_am_norm_kernel       the pattern over its envelope, computeAM:1177-1178
- *   hw25_am_rate_kernel       computeAMRate + sinModel, lane = (frame, channel), the 200-sample loops inside the lane
- *   hw25_finalseg_kernel      finalSeg and the binarisation, one wave per utterance
+ *   hw64_am_patt_kernel       amPatt: per block of five frames (800 samples) the Kaiser band-pass for the block's mean pitch,
+ *                             up to 1119 taps computed in the workgroup (lane = tap), then the FIR over max (gOut, 0)
+ *   hw64_am_fft_head_kernel   fft's bit reversal and its stages 1..12 on 4096 points in LDS
+ *   hw64_am_fft_stage_kernel  one of the stages 13..18 over global memory
+ *   hw64_am_norm_kernel       the pattern over its envelope, computeAM:1177-1178
+ *   hw64_am_rate_kernel       computeAMRate + sinModel, lane = (frame, channel), the 320-sample loops inside the lane: the
+ *                             window of frame f is [160 (f - 1), 160 (f + 1)), exactly two hops
+ *   hw64_finalseg_kernel      finalSeg and the binarisation, one wave per utterance; a channel is a lane of the WHOLE wave:
+ *                             64-bit ballots, nothing masked to the channel count
  *
- * Every expression keeps the type the reference's C++ gives it (a float argument selects the float overload, an expression
- * with the double literal PI is double; -ffp-contract=off).  The one exception is sinModel's cosf / sinf / atanf: glibc's are
- * not correctly rounded and cannot be reproduced, so each is the double function rounded to float;
- * ratio is therefore compared with a tolerance, everything before it bit for bit.
+ * Types as in hw25_am_kernel.hip: every expression keeps the type the reference's C++ gives it (-ffp-contract=off); sinModel's
+ * cosf / sinf / atanf are the double functions rounded to float, so ratio is compared with a tolerance, everything before it
+ * bit for bit.
  */
 #include "../../include/sea_mi355x.h"
 #include "hw25_device.h"
@@ -29,15 +33,20 @@ namespace sea {
 
 namespace {
 
-constexpr int kCh = SEA_HW25_NCHAN, kHop = SEA_HW25_HOP, kWin = SEA_HW25_WINDOW;
+constexpr int kCh = SEA_HW64_NCHAN, kHop = SEA_HW64_HOP, kWin = SEA_HW64_WINDOW;
 constexpr int kBlock = 5 * kHop; /* amPatt's blocks of five frames */
-constexpr int kMaxTaps = SEA_HW25_AM_MAXTAPS;
+constexpr int kMaxTaps = SEA_HW64_AM_MAXTAPS;
 constexpr int kLdsLog2 = SEA_HW25_AM_LDS_LOG2;
+constexpr int kFs = 16000;                                 /* SAMPLING_FREQUENCY */
 constexpr double kPi = 3.1415926535897932384626433832795; /* HuWang.h:7 */
+static_assert(kCh == 64, "a channel is a lane of the whole wave");
+static_assert(kWin == 2 * kHop, "computeAMRate's window is two hops");
+
+using ChanSet = unsigned long long; /* channel c is bit c */
 
 } // namespace
 
-__global__ __launch_bounds__(64) void hw25_am_prepare_kernel(Hw25AmArgs a)
+__global__ __launch_bounds__(64) void hw64_am_prepare_kernel(Hw25AmArgs a)
 {
     const int lane = threadIdx.x;
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
@@ -52,7 +61,7 @@ __global__ __launch_bounds__(64) void hw25_am_prepare_kernel(Hw25AmArgs a)
         for (int f = lane; f < nfr; f += 64) {
             const int p = a.pitch[row0 + f];
             voiced = voiced || p > 0;
-            bad = bad || p >= SEA_HW25_DELAYS;
+            bad = bad || p >= SEA_HW64_DELAYS;
         }
         voiced = __any(voiced);
         bad = __any(bad);
@@ -82,9 +91,10 @@ __global__ __launch_bounds__(64) void hw25_am_prepare_kernel(Hw25AmArgs a)
             }
 }
 
-/* grid (n_utt, PATT_GRID, 25): workgroup (u, g, c) takes the blocks g, g + PATT_GRID, ... of channel c.  A block is the 400
- * samples of five frames centred on frame 5 b + 2; one without that frame, or without a voiced frame, is zeros. */
-__global__ __launch_bounds__(256) void hw25_am_patt_kernel(Hw25AmArgs a)
+/* grid (n_utt, PATT_GRID, 64): workgroup (u, g, c) takes the blocks g, g + PATT_GRID, ... of channel c.  A block is the 800
+ * samples of five frames centred on frame 5 b + 2; one without that frame, or without a voiced frame, is zeros.  12 160 bytes
+ * of LDS: 1120 taps and the 800 + 1120 samples they reach. */
+__global__ __launch_bounds__(256) void hw64_am_patt_kernel(Hw25AmArgs a)
 {
     __shared__ float taps[kMaxTaps];
     __shared__ float win[kBlock + kMaxTaps];
@@ -126,7 +136,7 @@ __global__ __launch_bounds__(256) void hw25_am_patt_kernel(Hw25AmArgs a)
         else
             fLength += 2;
         if (fLength % 2 != 0) fLength++;
-        if (fLength + 1 > kMaxTaps) fLength = kMaxTaps - 2; /* unreachable with pitches up to 100: keeps LDS in bounds */
+        if (fLength + 1 > kMaxTaps) fLength = kMaxTaps - 2; /* unreachable with pitches up to 200: keeps LDS in bounds */
         const int half = fLength / 2;
         /* kaiserBandPass (filter, fLength, beta, 2.1 / mp, 0.7 / mp):1571-1601 */
         const float wc = (float)(2.1 / (double)mp), wn = (float)(0.7 / (double)mp);
@@ -164,8 +174,10 @@ __global__ __launch_bounds__(256) void hw25_am_patt_kernel(Hw25AmArgs a)
 }
 
 /* grid (n_utt, FFT_GRID, chunk): workgroup (u, g, z) takes the 4096-point pieces g, g + FFT_GRID, ... of channel chan0 + z.
- * Piece k of the bit-reversed array is loaded from the reversed indices, and the stages 1 .. min (N, 12) never leave it. */
-__global__ __launch_bounds__(256) void hw25_am_fft_head_kernel(Hw25AmArgs a)
+ * Piece k of the bit-reversed array is loaded from the reversed indices, and the stages 1 .. min (N, 12) never leave it.
+ * hw25_am_fft_head_kernel's text with this bank's channel count in `pat` and in the channel bound: shared as a body, that
+ * kernel's instructions came out in another order. */
+__global__ __launch_bounds__(256) void hw64_am_fft_head_kernel(Hw25AmArgs a)
 {
     __shared__ float2 x[1 << kLdsLog2];
     const int tid = threadIdx.x, z = blockIdx.z, c = a.chan0 + z;
@@ -217,14 +229,14 @@ __global__ __launch_bounds__(256) void hw25_am_fft_head_kernel(Hw25AmArgs a)
 }
 
 /* stage a.stage (13 .. 18) in place over global memory; this body and the next are the two banks' (hw25_device.h) */
-__global__ __launch_bounds__(256) void hw25_am_fft_stage_kernel(Hw25AmArgs a) { am_fft_stage<kCh, kHop>(a); }
+__global__ __launch_bounds__(256) void hw64_am_fft_stage_kernel(Hw25AmArgs a) { am_fft_stage<kCh, kHop>(a); }
 
 /* computeAM:1177-1178 */
-__global__ __launch_bounds__(256) void hw25_am_norm_kernel(Hw25AmArgs a) { am_norm<kCh, kHop>(a); }
+__global__ __launch_bounds__(256) void hw64_am_norm_kernel(Hw25AmArgs a) { am_norm<kCh, kHop>(a); }
 
 /* grid (n_utt, RATE_GRID): computeAMRate:1259-1287 and sinModel:1289-1317, lane = (frame, channel).  cosf, sinf and atanf
  * are the double functions rounded to float. */
-__global__ __launch_bounds__(64) void hw25_am_rate_kernel(Hw25AmArgs a)
+__global__ __launch_bounds__(64) void hw64_am_rate_kernel(Hw25AmArgs a)
 {
     const AmUtt t = am_utterance<kHop>(a);
     if (t.N < 0) return;
@@ -239,8 +251,8 @@ __global__ __launch_bounds__(64) void hw25_am_rate_kernel(Hw25AmArgs a)
         const int p = a.pitch[t.row0 + frame];
         float ratio = 0.0f, label = 0.0f;
         if (p > 0 && sEng > 0.0f) {
-            float freq = 8000.0f / (float)p;
-            freq = (float)((double)freq * (2 * kPi / 8000));
+            float freq = (float)kFs / (float)p;
+            freq = (float)((double)freq * (2 * kPi / kFs));
             float pa = 0.0f, pb = 0.0f;
             for (int tim = 0; tim < kWin; ++tim) {
                 const double arg = (double)(freq * (float)tim);
@@ -268,11 +280,12 @@ __global__ __launch_bounds__(64) void hw25_am_rate_kernel(Hw25AmArgs a)
 namespace {
 
 struct FinalScr {
-    int *lab, *key, *lo, *hi, *m, *g; /* [F][25] each */
+    int *lab, *key, *lo, *hi, *m, *g; /* [F][64] each */
 };
 
 /* reSegmentation:1390-1440 on m: the components that hold a unit whose two time neighbours are marked (the reference's
- * segments) and span at least MIN_SEG_LENGTH frames stay, everything else is cleared.  Returns the number of segments. */
+ * segments) and span at least MIN_SEG_LENGTH frames stay, everything else is cleared.  Returns the number of segments.
+ * F * 64 is a multiple of the wave: every lane holds a unit in every pass. */
 __device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lane)
 {
     const int ncell = F * kCh;
@@ -284,7 +297,7 @@ __device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lan
         s.hi[i] = 0;
     }
     lanes_fence();
-    hw25_label_components(s.lab, F, lane);
+    hw64_label_components(s.lab, F, lane);
     lanes_fence();
     for (int i = lane; i < ncell; i += 64) {
         const int f = i / kCh;
@@ -296,11 +309,7 @@ __device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lan
     }
     lanes_fence();
     int count = 0;
-    for (int base = 0; base < ncell; base += 64) {
-        const int i = base + lane;
-        const bool seg = i < ncell && s.lab[i] == i && s.key[i] != kHw25None;
-        count += __popcll(__ballot(seg));
-    }
+    for (int i = lane; i < ncell; i += 64) count += __popcll(__ballot(s.lab[i] == i && s.key[i] != kHw25None));
     for (int i = lane; i < ncell; i += 64) {
         int keep = 0;
         if (m[i]) {
@@ -315,25 +324,24 @@ __device__ __forceinline__ int re_segmentation(const FinalScr &s, int F, int lan
 
 /* develope:1442-1494: the reference sweeps in place until nothing changes; the fixpoint is the closure of {g == v} over
  * 4-neighbours with m set, whatever the sweep order.  Lane = channel: a frame takes v from the frame before it in sweep
- * direction, then v spreads along the frame's marked channels. */
+ * direction, then v spreads along the frame's marked channels, over all 64 lanes. */
 __device__ __forceinline__ void develope(const FinalScr &s, int F, int v, int lane)
 {
     bool again = true;
     while (again) {
         bool changed = false;
         for (int dir = 0; dir < 2; ++dir) {
-            unsigned carry = 0;
+            ChanSet carry = 0;
             for (int k = 0; k < F; ++k) {
                 const int f = dir ? F - 1 - k : k;
-                const bool isv = lane < kCh && s.g[f * kCh + lane] == v;
-                const bool mm = lane < kCh && s.m[f * kCh + lane] != 0;
-                const unsigned V0 = (unsigned)__ballot(isv) & kHw25ChanBits, M = (unsigned)__ballot(mm) & kHw25ChanBits;
-                unsigned V = V0 | (carry & M), prev;
+                const bool isv = s.g[f * kCh + lane] == v;
+                const ChanSet V0 = __ballot(isv), M = __ballot(s.m[f * kCh + lane] != 0);
+                ChanSet V = V0 | (carry & M), prev;
                 do {
                     prev = V;
                     V |= ((V << 1) | (V >> 1)) & M;
                 } while (V != prev);
-                if (lane < kCh && ((V >> lane) & 1u) && !isv) {
+                if (((V >> lane) & 1ull) && !isv) {
                     s.g[f * kCh + lane] = v;
                     changed = true;
                 }
@@ -347,13 +355,13 @@ __device__ __forceinline__ void develope(const FinalScr &s, int F, int v, int la
 
 } // namespace
 
-__global__ __launch_bounds__(64) void hw25_finalseg_kernel(Hw25FinalArgs a)
+__global__ __launch_bounds__(64) void hw64_finalseg_kernel(Hw25FinalArgs a)
 {
     const int lane = threadIdx.x;
     const int u = a.order ? a.order[blockIdx.x] : (int)blockIdx.x;
     const long long L = a.lengths[u], row0 = a.row_offsets[u];
     const int F = L > 0 ? (int)(L / kHop) : 0, ncell = F * kCh;
-    int *block = a.rowscr + row0 * SEA_HW25_FINAL_SCRATCH_WORDS;
+    int *block = a.rowscr + row0 * SEA_HW64_FINAL_SCRATCH_WORDS;
     const FinalScr s = {block, block + ncell, block + 2 * ncell, block + 3 * ncell, block + 4 * ncell, block + 5 * ncell};
     const float *grp = a.grp + row0 * kCh, *am = a.amcrn + row0 * kCh, *cross = a.cross_ev + row0 * kCh, *pr = a.pratio + row0 * kCh;
     float *stages = a.stages ? a.stages + row0 * (SEA_HW25_FINAL_STAGES * kCh) : nullptr;

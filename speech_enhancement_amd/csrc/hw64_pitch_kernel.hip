@@ -135,51 +135,6 @@ __device__ __forceinline__ float *stage_grp(const Hw64PitchArgs &a, const Utt &t
 /* segment count 0 or a set TOO_MANY bit: the segment kernel wrote zeros, the later kernels leave the utterance alone */
 __device__ __forceinline__ bool inactive(int status) { return (status & 0xffff) == 0 || (status & SEA_HW25_TOO_MANY_SEGMENTS); }
 
-/* hw25_label_components (hw25_device.h) with a channel in every lane.  lab [F][64]: the unit's own index where it is marked,
- * kHw25None elsewhere.  On return every marked unit holds the smallest unit index of its 4-connected component.  A frame
- * takes the label of the frame before it in sweep direction (carried in registers), then every run of marked channels takes
- * its minimum: a prefix minimum over the 64 lanes that stops at the run's start, read back from the run's end.  Forward and
- * backward sweeps until neither changes anything.  The caller fences before and after. */
-__device__ __forceinline__ void label_components(int *lab, int F, int lane)
-{
-    bool again = true;
-    while (again) {
-        bool changed = false;
-        for (int dir = 0; dir < 2; ++dir) {
-            int carry = kHw25None;
-            for (int k = 0; k < F; ++k) {
-                const int f = dir ? F - 1 - k : k;
-                const int old = lab[f * kCh + lane];
-                int v = old;
-                if (v != kHw25None && carry < v) v = carry;
-                const ChanSet m = __ballot(v != kHw25None);
-                /* the run [start, end] of marked channels around this lane */
-                const ChanSet below = ~m & ((1ull << lane) - 1ull);
-                const int start = below ? 64 - __clzll((long long)below) : 0;
-                const ChanSet above = lane < 63 ? (~m >> (lane + 1)) : 0ull;
-                const int end = above ? lane + (__ffsll((long long)above) - 1) : 63;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1) {
-                    const int o = __shfl_up(v, d);
-                    if (lane - d >= start && o < v) v = o;
-                }
-                const int r = __shfl(v, end);
-                if (old != kHw25None) {
-                    v = r;
-                    if (v != old) {
-                        lab[f * kCh + lane] = v;
-                        changed = true;
-                    }
-                } else {
-                    v = kHw25None;
-                }
-                carry = v;
-            }
-        }
-        again = __any(changed);
-    }
-}
-
 } // namespace
 
 __global__ __launch_bounds__(64) void hw64_pitch_max_kernel(Hw64PitchArgs a)
@@ -228,7 +183,7 @@ __global__ __launch_bounds__(64) void hw64_pitch_segment_kernel(Hw64PitchArgs a)
         }
         lanes_fence();
         /* ---- components: every marked unit ends with the smallest unit index of its component ---- */
-        label_components(lab, F, lane);
+        hw64_label_components(lab, F, lane);
         lanes_fence();
         /* ---- per component its first seed in scan order ---- */
         for (int i = lane; i < ncell; i += 64) {

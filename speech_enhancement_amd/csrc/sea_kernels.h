@@ -488,6 +488,19 @@ struct Hw25FinalArgs {
 #define SEA_HW25_FINAL_SCRATCH_WORDS 150 /* per row: lab, key, lo, hi, m, g [25] */
 __global__ void hw25_finalseg_kernel(Hw25FinalArgs a); /* grid n_utt x 64 */
 
+/* The same two stages at 16 kHz on the 64-channel bank (hw64_am_kernel.hip).  Hw25AmArgs and Hw25FinalArgs as they are, at 64
+ * channels, a hop of 160 and a pitch of at most 200: gout, ampatt, am in hw64_periphery_kernel's layout; amcrn, ratio, seng,
+ * grp, cross_ev, pratio, mask, grp_final [rows][64]; stages [5][F][64] floats at row_offsets[u] * 320; tables: the 25-band
+ * tables, of which only am_a and am_beta are read (kaiserPara (0.01, ..) knows neither rate nor bank); tw: the same twiddles. */
+__global__ void hw64_am_prepare_kernel(Hw25AmArgs a);   /* grid n_utt x 64 */
+__global__ void hw64_am_patt_kernel(Hw25AmArgs a);      /* grid (n_utt, PATT_GRID, 64) x 256 */
+__global__ void hw64_am_fft_head_kernel(Hw25AmArgs a);  /* grid (n_utt, FFT_GRID, chunk) x 256 */
+__global__ void hw64_am_fft_stage_kernel(Hw25AmArgs a); /* grid (n_utt, FFT_GRID, chunk) x 256 */
+__global__ void hw64_am_norm_kernel(Hw25AmArgs a);      /* grid (n_utt, FFT_GRID, chunk) x 256 */
+__global__ void hw64_am_rate_kernel(Hw25AmArgs a);      /* grid (n_utt, RATE_GRID) x 64 */
+#define SEA_HW64_FINAL_SCRATCH_WORDS 384 /* per row: lab, key, lo, hi, m, g [64] */
+__global__ void hw64_finalseg_kernel(Hw25FinalArgs a);  /* grid n_utt x 64 */
+
 /* resynthesis:1498-1549 on the same bank (hw25_resynth_kernel.hip).  gout: hout's layout, only read; mask [rows][25], utterance
  * u's lengths[u] / 80 rows from row_offsets[u], a unit set where mask > threshold; out_f32 / out_i16 (either may be null):
  * the packed sample space of the input audio, utterance u's lengths[u] samples at offsets[u]. */

@@ -284,7 +284,9 @@ enum {
     SEA_HW64_WINDOW = 320,  /* WINDOW = 16000 / 50 */
     SEA_HW64_HOP = 160,     /* OFFSET = 16000 / 100 */
     SEA_HW64_TAPS = 181,    /* fLength + 1, fLength = 180 from kaiserPara (0.01, 200 / 16000.) */
-    SEA_HW64_MAXWIN = 1280  /* the widest window: channel 0, int (4 * 16000 / cf), cf = 50 */
+    SEA_HW64_MAXWIN = 1280, /* the widest window: channel 0, int (4 * 16000 / cf), cf = 50 */
+    SEA_HW64_AM_MAXTAPS = 1120 /* amPatt's fLength + 1 is at most 1119 (mp = 200; 5.59 mp): kaiserPara's float arithmetic at the
+                                * largest mean of five pitches in 32..200 */
 };
 typedef struct {
     float cf[SEA_HW64_NCHAN], bw[SEA_HW64_NCHAN], midEar[SEA_HW64_NCHAN];

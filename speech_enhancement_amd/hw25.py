@@ -337,23 +337,30 @@ class Hw25AmResult(_Hw25Rows):
         return out
 
 
+def _bank_am(bank, result, batch, gout, pitch, row_offsets, want_details, use_order):
+    """the one body of the AM wrappers of both banks"""
+    torch = _torch()
+    lib = _lib.load()
+    s = _hw25_start(batch, dev=gout.device, row_offsets=row_offsets, zeros=("status",), bank=bank)
+    amcrn = torch.zeros((s.n, bank.nchan), dtype=torch.float32, device=s.dev)
+    ratio, seng = (torch.zeros_like(amcrn) for _ in range(2)) if want_details else (None, None)
+    ampatt, am = (torch.zeros_like(gout) for _ in range(2)) if want_details else (None, None)
+    nbytes = int(getattr(lib, f"sea_{bank.name}_am_scratch_bytes")(s.total, int(batch.n_utt)))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=s.dev)
+    fn = f"sea_{bank.name}_am_batch"
+    rc = getattr(lib, fn)(_dptr(gout), _dptr(pitch), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(s.d_offs), _dptr(amcrn),
+                          _dptr(ratio), _dptr(seng), _dptr(ampatt), _dptr(am), _dptr(s.status), _dptr(scratch), s.total,
+                          _hw25_order(batch, use_order), batch.n_utt, _stream_ptr())
+    _lib.check(rc, fn)
+    return result(batch, amcrn=amcrn, ratio=ratio, seng=seng, ampatt=ampatt, am=am, status=s.status, row_offsets=s.d_offs,
+                  host_row_offsets=s.offs, host_rows=s.rows)
+
+
 def hw25_am_batch(batch, gout, pitch, row_offsets=None, want_details=False, use_order=True):
     """computeAM for every utterance of the batch from hw25_periphery_gout_batch()'s gOut and hw25_pitch_batch()'s pitch (int32
     [rows] on the device; row_offsets: the int64 device tensor that goes with it) -> Hw25AmResult.  want_details: also ratio,
     seng, ampatt and am."""
-    torch = _torch()
-    lib = _lib.load()
-    s = _hw25_start(batch, dev=gout.device, row_offsets=row_offsets, zeros=("status",))
-    amcrn = torch.zeros((s.n, HW25_NCHAN), dtype=torch.float32, device=s.dev)
-    ratio, seng = (torch.zeros_like(amcrn) for _ in range(2)) if want_details else (None, None)
-    ampatt, am = (torch.zeros_like(gout) for _ in range(2)) if want_details else (None, None)
-    scratch = torch.empty(int(lib.sea_hw25_am_scratch_bytes(s.total, int(batch.n_utt))), dtype=torch.uint8, device=s.dev)
-    rc = lib.sea_hw25_am_batch(_dptr(gout), _dptr(pitch), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(s.d_offs), _dptr(amcrn),
-                               _dptr(ratio), _dptr(seng), _dptr(ampatt), _dptr(am), _dptr(s.status), _dptr(scratch), s.total,
-                               _hw25_order(batch, use_order), batch.n_utt, _stream_ptr())
-    _lib.check(rc, "sea_hw25_am_batch")
-    return Hw25AmResult(batch, amcrn=amcrn, ratio=ratio, seng=seng, ampatt=ampatt, am=am, status=s.status, row_offsets=s.d_offs,
-                        host_row_offsets=s.offs, host_rows=s.rows)
+    return _bank_am(_BANK25, Hw25AmResult, batch, gout, pitch, row_offsets, want_details, use_order)
 
 
 class Hw25MaskResult(_Hw25Rows):
@@ -367,33 +374,39 @@ class Hw25MaskResult(_Hw25Rows):
             if getattr(self, k, None) is not None:
                 out[k] = self._rows(u, getattr(self, k))
         if self.stages is not None:
-            w = len(HW25_FINAL_STAGES) * HW25_NCHAN
-            block = self._rows(u, self.stages, w).reshape(len(HW25_FINAL_STAGES), len(out["mask"]), HW25_NCHAN)
+            w = len(HW25_FINAL_STAGES) * self.NCHAN
+            block = self._rows(u, self.stages, w).reshape(len(HW25_FINAL_STAGES), len(out["mask"]), self.NCHAN)
             for k, name in enumerate(HW25_FINAL_STAGES):
                 out[name] = block[k].copy()
         return out
+
+
+def _bank_finalseg(bank, result, grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages, use_order):
+    """the one body of the final-grouping wrappers of both banks"""
+    torch = _torch()
+    lib = _lib.load()
+    dev = grp.device
+    host_rows = np.asarray(host_rows, dtype=np.int64)
+    n_utt, n = len(host_rows), max(int(host_rows.sum()), 1)
+    mask = torch.zeros((n, bank.nchan), dtype=torch.float32, device=dev)
+    grp_final = torch.zeros_like(mask)
+    status = torch.zeros(max(n_utt, 1), dtype=torch.int32, device=dev)
+    st = torch.zeros(n * len(HW25_FINAL_STAGES) * bank.nchan, dtype=torch.float32, device=dev) if stages else None
+    nbytes = int(getattr(lib, f"sea_{bank.name}_finalseg_scratch_bytes")(n, n_utt))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    fn = f"sea_{bank.name}_finalseg_batch"
+    rc = getattr(lib, fn)(_dptr(grp), _dptr(amcrn), _dptr(cross_ev), _dptr(pratio), _dptr(lengths), _dptr(row_offsets), _dptr(mask),
+                          _dptr(grp_final), _dptr(status), _dptr(st), _dptr(scratch), _dptr(use_order), n_utt, _stream_ptr())
+    _lib.check(rc, fn)
+    return result(mask=mask, grp_final=grp_final, status=status, stages=st, pitch=None, host_row_offsets=_row_offsets(host_rows),
+                  host_rows=host_rows)
 
 
 def hw25_finalseg_batch(grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages=False, use_order=None):
     """finalSeg and the binarisation on device tensors [rows][25] (hw25_pitch_batch()'s grp and pratio, hw25_am_batch()'s amcrn,
     the front half's cross_ev), lengths / row_offsets int64 [n_utt] on the device, host_rows the row counts -> Hw25MaskResult.
     use_order: an int32 device tensor (launch order) or None."""
-    torch = _torch()
-    lib = _lib.load()
-    dev = grp.device
-    host_rows = np.asarray(host_rows, dtype=np.int64)
-    n_utt, n = len(host_rows), max(int(host_rows.sum()), 1)
-    mask = torch.zeros((n, HW25_NCHAN), dtype=torch.float32, device=dev)
-    grp_final = torch.zeros_like(mask)
-    status = torch.zeros(max(n_utt, 1), dtype=torch.int32, device=dev)
-    st = torch.zeros(n * len(HW25_FINAL_STAGES) * HW25_NCHAN, dtype=torch.float32, device=dev) if stages else None
-    scratch = torch.empty(int(lib.sea_hw25_finalseg_scratch_bytes(n, n_utt)), dtype=torch.uint8, device=dev)
-    rc = lib.sea_hw25_finalseg_batch(_dptr(grp), _dptr(amcrn), _dptr(cross_ev), _dptr(pratio), _dptr(lengths), _dptr(row_offsets),
-                                     _dptr(mask), _dptr(grp_final), _dptr(status), _dptr(st), _dptr(scratch), _dptr(use_order), n_utt,
-                                     _stream_ptr())
-    _lib.check(rc, "sea_hw25_finalseg_batch")
-    return Hw25MaskResult(mask=mask, grp_final=grp_final, status=status, stages=st, pitch=None,
-                          host_row_offsets=_row_offsets(host_rows), host_rows=host_rows)
+    return _bank_finalseg(_BANK25, Hw25MaskResult, grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages, use_order)
 
 
 class Hw25EnhanceResult(Hw25MaskResult):
@@ -407,20 +420,23 @@ class Hw25EnhanceResult(Hw25MaskResult):
         return out
 
 
-def _hw25_ibm(batch, stages, use_order, enhance):
-    """the one body of hw25_ibm_batch and of hw25_enhance_batch, which resynthesises the mask in the same launch group"""
+def _bank_ibm(bank, result, batch, stages, use_order, enhance=False):
+    """the one body of the whole-estimator wrappers of both banks and of hw25_enhance_batch, which resynthesises the mask in
+    the same launch group"""
     torch = _torch()
     lib = _lib.load()
-    s = _hw25_start(batch, zeros=("mask", "pitch", "status"))
-    st = torch.zeros(s.n * len(HW25_FINAL_STAGES) * HW25_NCHAN, dtype=torch.float32, device=s.dev) if stages else None
-    scratch = torch.empty(int(lib.sea_hw25_ibm_scratch_bytes(s.total, s.n, int(batch.n_utt))), dtype=torch.uint8, device=s.dev)
+    s = _hw25_start(batch, zeros=("mask", "pitch", "status"), bank=bank)
+    st = torch.zeros(s.n * len(HW25_FINAL_STAGES) * bank.nchan, dtype=torch.float32, device=s.dev) if stages else None
+    nbytes = int(getattr(lib, f"sea_{bank.name}_ibm_scratch_bytes")(s.total, s.n, int(batch.n_utt)))
+    scratch = torch.empty(nbytes, dtype=torch.uint8, device=s.dev)
     head = (_dptr(s.x), _dptr(batch.offsets), _dptr(batch.lengths), _dptr(s.d_offs))
     outs = (_dptr(s.mask), _dptr(s.pitch), _dptr(s.status))
     tail = (_dptr(scratch), s.total, s.n, _hw25_order(batch, use_order), batch.n_utt, _stream_ptr())
     res = dict(mask=s.mask, grp_final=None, status=s.status, stages=st, pitch=s.pitch, host_row_offsets=s.offs, host_rows=s.rows)
     if not enhance:
-        _lib.check(lib.sea_hw25_ibm_batch(*head, *outs, _dptr(st), *tail), "sea_hw25_ibm_batch")
-        return Hw25MaskResult(**res)
+        fn = f"sea_{bank.name}_ibm_batch"
+        _lib.check(getattr(lib, fn)(*head, *outs, _dptr(st), *tail), fn)
+        return result(**res)
     audio = torch.zeros(s.total, dtype=torch.float32, device=s.dev)
     _lib.check(lib.sea_hw25_enhance_batch(*head, _dptr(audio), None, *outs, *tail), "sea_hw25_enhance_batch")
     return Hw25EnhanceResult(batch=batch, audio=audio, **res)
@@ -430,7 +446,7 @@ def hw25_ibm_batch(batch, stages=False, use_order=True):
     """createIBM() for every utterance of the batch, one launch group on the current stream -> Hw25MaskResult with the binary
     mask [rows][25], pitchDtm's pitch [rows] and the status (hw25_pitch_batch()'s with HW25_FINAL_TOO_MANY_SEGMENTS,
     HW25_AM_TOO_LONG).  stages: also keep Grp after each of finalSeg's five steps."""
-    return _hw25_ibm(batch, stages, use_order, False)
+    return _bank_ibm(_BANK25, Hw25MaskResult, batch, stages, use_order)
 
 
 def hw25_ibm(x):
@@ -479,7 +495,7 @@ def hw25_resynth(x, mask, threshold=0.0):
 def hw25_enhance_batch(batch, use_order=True):
     """createIBM() followed by resynthesis() of its own mask for every utterance of the batch, one launch group on the
     current stream -> Hw25EnhanceResult."""
-    return _hw25_ibm(batch, False, use_order, True)
+    return _bank_ibm(_BANK25, Hw25MaskResult, batch, False, use_order, enhance=True)
 
 
 def hw25_enhance(x):

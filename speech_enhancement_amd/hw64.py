@@ -6,15 +6,19 @@ hw25_* namesakes at 64 channels, 201 delays and a hop of 160 samples, and share 
 Then createIBM():79-87, initGroup and pitchDtm (csrc/hw64_pitch_kernel.hip): the pitch contour of the dominant voiced source and
 the units grouped with it or against it, hw64_pitch_batch / hw64_pitch.  The reference's leftDevelope and rightDevelope bound
 two loops by the literal 40; on this bank that keeps channels 40..63 out of their votes (the 25-band bank reads the cross
-array there instead, which is why only its call takes one).  computeAM onwards is not built at 16 kHz.
+array there instead, which is why only its call takes one).
+
+Then createIBM():89-106, computeAM, finalSeg and the binarisation (csrc/hw64_am_kernel.hip): hw64_am_batch, hw64_finalseg_batch
+and the whole estimator, hw64_ibm_batch / hw64_ibm, the binary mask [frames][64] from 16 kHz audio.  Of the reference's chain
+only resynthesis() is not built at 16 kHz.
 
 torch is used for device memory and streams only (plumbing); all compute is in the HIP library.
 """
 from types import SimpleNamespace
 
 from . import _lib
-from .hw25 import (Hw25PitchResult, Hw25Result, _bank_front, _bank_frontend_host, _bank_periphery, _bank_pitch, _bank_split,
-                   _bank_tables, _hw25_host)
+from .hw25 import (Hw25AmResult, Hw25MaskResult, Hw25PitchResult, Hw25Result, _bank_am, _bank_finalseg, _bank_front,
+                   _bank_frontend_host, _bank_ibm, _bank_periphery, _bank_pitch, _bank_split, _bank_tables, _hw25_host)
 
 HW64_NCHAN, HW64_DELAYS, HW64_HOP = 64, 201, 160
 HW64_STAGE_WORDS = 5 + 2 * HW64_NCHAN
@@ -96,3 +100,43 @@ def hw64_pitch(x):
 def hw64_pitch_waves_per_utterance(n_utt):
     """How many waves the pitch stage's two frame-walking kernels give every utterance of a batch of n_utt on the current device."""
     return int(_lib.load().sea_hw64_pitch_waves_per_utterance(int(n_utt)))
+
+
+class Hw64AmResult(Hw25AmResult):
+    """What hw64_am_batch() computed: Hw25AmResult's tensors at 64 channels -- amcrn [rows][64] 0 / 1, status int32 [n_utt]
+    (HW25_AM_TOO_LONG, HW25_AM_BAD_PITCH) and, when asked for, ratio and seng [rows][64], ampatt and am (gOut's layout)."""
+    NCHAN = HW64_NCHAN
+
+
+class Hw64MaskResult(Hw25MaskResult):
+    """What hw64_finalseg_batch() / hw64_ibm_batch() computed: Hw25MaskResult's tensors at 64 channels -- mask [rows][64] 0 / 1,
+    status int32 [n_utt], grp_final [rows][64] or None, pitch int32 [rows] or None, stages (floats, [5][rows_u][64] per
+    utterance, or None).  utterance(u): numpy arrays, the stage arrays under HW25_FINAL_STAGES when they were asked for."""
+    NCHAN = HW64_NCHAN
+
+
+def hw64_am_batch(batch, gout, pitch, row_offsets=None, want_details=False, use_order=True):
+    """computeAM at 16 kHz for every utterance of the batch from hw64_periphery_batch(gout=True)'s gOut and hw64_pitch_batch()'s
+    pitch (int32 [rows] on the device, 0 or 32..200; row_offsets: the int64 device tensor that goes with it) -> Hw64AmResult.
+    want_details: also ratio, seng, ampatt and am."""
+    return _bank_am(_BANK64, Hw64AmResult, batch, gout, pitch, row_offsets, want_details, use_order)
+
+
+def hw64_finalseg_batch(grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages=False, use_order=None):
+    """finalSeg and the binarisation on device tensors [rows][64] (hw64_pitch_batch()'s grp and pratio, hw64_am_batch()'s amcrn,
+    the front half's cross_ev), lengths / row_offsets int64 [n_utt] on the device, host_rows the row counts -> Hw64MaskResult.
+    use_order: an int32 device tensor (launch order) or None."""
+    return _bank_finalseg(_BANK64, Hw64MaskResult, grp, amcrn, cross_ev, pratio, lengths, row_offsets, host_rows, stages, use_order)
+
+
+def hw64_ibm_batch(batch, stages=False, use_order=True):
+    """createIBM() at 16 kHz for every utterance of the batch, one launch group on the current stream -> Hw64MaskResult with the
+    binary mask [rows][64], pitchDtm's pitch [rows] and the status (hw64_pitch_batch()'s with HW25_FINAL_TOO_MANY_SEGMENTS,
+    HW25_AM_TOO_LONG).  stages: also keep Grp after each of finalSeg's five steps."""
+    return _bank_ibm(_BANK64, Hw64MaskResult, batch, stages, use_order)
+
+
+def hw64_ibm(x):
+    """createIBM (x) for one utterance from host memory (float32 or int16 samples on the int16 scale, 16 kHz) -> dict: mask
+    [F][64] floats 0 / 1, pitch int32 [F], status; F = len(x) // 160."""
+    return _hw25_host("sea_hw64_ibm", x, ("mask", "pitch"), bank=_BANK64)

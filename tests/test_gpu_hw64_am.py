@@ -1,0 +1,579 @@
+"""The Hu-Wang AM labels, final grouping and the whole estimator at 16 kHz on the 64-channel bank on the GPU
+(csrc/hw64_am_kernel.hip) against what the reference's own computeAM / finalSeg / createIBM produced when compiled against the
+64-band header (tests/golden/hw64_am_golden.npz) and, where the fixture holds nothing, the numpy model that the CPU tests pin to
+that fixture (tests/hw64_am_model.py).  gOut, the AM pattern before and after its normalisation and sEng are compared bit for
+bit, ratio = error / sEng within the fixture's ratio_tol (sinModel's cosf / sinf / atanf are the double functions rounded to
+float: DESIGN.md section 5.18), the labels, every stage of finalSeg and the mask exactly.
+
+The audio batch: the fixture's five inputs (p11900 has N = 14: four LDS pieces and two stages over global memory, and fifteen
+blocks of five frames, so the pattern kernel's walk makes a second trip); then 0, 159, 160, 480 and 800 samples against the
+model; then 150001 samples of zeros, one more than the FFT is built for.  Its padded extent is past 131 072 samples, so the FFT
+runs in eight groups of eight channels; a second batch of the same five inputs is small enough for all 64 channels at once and
+is compared with the same CRCs.  Every output buffer is filled with a sentinel and carries guard rows; every call also runs in a
+permuted launch order and without its optional outputs.  A third batch feeds arrays straight to sea_hw64_finalseg_batch; a
+fourth one takes the FFT to its largest size, N = 18."""
+import ctypes
+
+import numpy as np
+import pytest
+
+from tests import hw64_am_model as AM
+from tests import hw64_model as M
+from tests import hw64_pitch_model as PM
+
+pytestmark = pytest.mark.gpu
+
+NCH, HOP = 64, 160
+SENT, SENT_I = -7777.25, -77
+GUARD = 3
+FW = len(AM.FINAL_STAGES) * NCH
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _lib():
+    from speech_enhancement_amd import _lib
+    return _lib, _lib.load()
+
+
+def _stream():
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _full(shape, value, dtype):
+    import torch
+    return torch.full(shape, value, dtype=dtype, device="cuda:0")
+
+
+def _blocks(batch, t):
+    """a tensor in gOut's layout -> per utterance (the [64][L] array, its padding columns)"""
+    host = t.cpu().numpy()
+    out = []
+    for off, L in zip(batch.host_offsets, batch.host_lengths):
+        pitch = (int(L) + 7) // 8 * 8
+        b = host[off * NCH:off * NCH + NCH * pitch].reshape(NCH, pitch)
+        out.append((b[:, :int(L)], b[:, int(L):]))
+    return out
+
+
+def _against_crcs(got, g, name, k):
+    idx = AM.sample_index(got.shape[1])
+    bad = np.flatnonzero(np.ascontiguousarray(got).ravel()[idx].view(np.uint32) != g[f"{name}_s_{k}"].view(np.uint32))
+    assert not len(bad), f"{k}: {name} differs first at flat index {idx[bad[0]]}"
+    assert np.array_equal(AM.channel_crcs(got), g[f"{name}_crc_{k}"]), f"{k}: {name} CRCs"
+
+
+def _am_scratch_size(total, n_utt, chunk):
+    """sea_hw64_am_scratch_bytes when the FFT runs on `chunk` channels at a time"""
+    up = lambda v: (v + 255) // 256 * 256  # noqa: E731
+    return up(4 * n_utt) + 2 * up(total * NCH * 4 + 64) + 2 * up(total * 2 * chunk * 8 + 64)
+
+
+# ---- the audio batch -----------------------------------------------------------------------------------------------------------
+N_FIX = len(AM.AUDIO_CASES)
+PERM = [10, 4, 8, 0, 6, 2, 9, 7, 1, 5, 3]
+
+
+def am_launch(a, order=None, details=True):
+    """sea_hw64_am_batch on sentinel-filled outputs with guard rows -> numpy arrays"""
+    import torch
+    lib_mod, lib = _lib()
+    batch, total, n_utt = a["batch"], int(a["rows"].sum()), len(a["utts"])
+    o = dict(amcrn=_full((total + GUARD, NCH), SENT, torch.float32), status=_full((n_utt + GUARD,), SENT_I, torch.int32))
+    for k in ("ratio", "seng"):
+        o[k] = _full((total + GUARD, NCH), SENT, torch.float32) if details else None
+    for k in ("ampatt", "am"):
+        o[k] = _full((batch.total * NCH + 64,), SENT, torch.float32) if details else None
+    nbytes = int(lib.sea_hw64_am_scratch_bytes(batch.total, n_utt))
+    scratch = torch.empty(nbytes + 64, dtype=torch.uint8, device="cuda:0")
+    rc = lib.sea_hw64_am_batch(_ptr(a["gout"]), _ptr(a["pitch"]), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(a["row_offsets"]),
+                               _ptr(o["amcrn"]), _ptr(o["ratio"]), _ptr(o["seng"]), _ptr(o["ampatt"]), _ptr(o["am"]), _ptr(o["status"]),
+                               _ptr(scratch), batch.total, _ptr(order), n_utt, _stream())
+    lib_mod.check(rc, "sea_hw64_am_batch")
+    torch.cuda.synchronize()
+    return {k: (v.cpu().numpy() if v is not None else None) for k, v in o.items()}, o
+
+
+@pytest.fixture(scope="module")
+def audio():
+    """the batch, its periphery on the GPU (computed once, never changed) and what every utterance must give"""
+    import torch
+    import speech_enhancement_amd as sea
+    g = AM.load_golden()
+    t = M.tables()
+    utts = [g[f"x_{k}"] for k in AM.AUDIO_CASES]
+    n = np.arange(800)
+    xs = PM.audio_inputs()
+    extra = [np.zeros(0, np.float32), (40 * np.sin(2 * np.pi * 200 * n[:159] / 16000)).astype(np.float32),
+             (900 * np.sin(2 * np.pi * 300 * n[:160] / 16000)).astype(np.float32),
+             (3000 * np.sin(2 * np.pi * 125 * n[:480] / 16000) + 1500 * np.sin(2 * np.pi * 250 * n[:480] / 16000)).astype(np.float32),
+             xs["p"][2000:2800].copy()]
+    model = []
+    for x in extra:  # the whole chain from the models
+        nfr = len(x) // HOP
+        fr = M.frontend(x, t) if nfr else None
+        ps = PM.pitch_stage(fr["acf_hc"], fr["pRatio"], fr["mark"]) if nfr else dict(pitch=np.zeros(0, np.int32), status=0)
+        am = AM.am_stage(AM.gout(x, t), ps["pitch"])
+        fin = AM.final_seg(ps["grp"], am["amcrn"], fr["cross_ev"], ps["pratio"]) if nfr else dict(mask=np.zeros((0, NCH), np.float32), status=0)
+        model.append(dict(pitch=ps["pitch"], am=am, mask=fin["mask"], status=ps["status"] | am["status"] | fin["status"]))
+    assert model[-1]["mask"].any() and model[-1]["am"]["amcrn"].any(), "the 800-sample input must reach the AM stage with a voiced frame"
+    utts = utts + extra + [np.zeros(150001, np.float32)]
+    assert [len(x) // HOP for x in utts] == [74, 25, 18, 18, 25, 0, 0, 1, 3, 5, 937] and sorted(PERM) == list(range(len(utts)))
+    batch = sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32)
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HOP
+    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    # the size rule: past 131 072 padded samples the FFT runs in eight groups of eight channels
+    lib_mod, lib = _lib()
+    total, n_utt = int(batch.total), len(utts)
+    assert total > 131072 and total * 2 * NCH * 16 > 256 << 20
+    assert int(lib.sea_hw64_am_scratch_bytes(total, n_utt)) == _am_scratch_size(total, n_utt, 8) != _am_scratch_size(total, n_utt, NCH), \
+        "the size rule did not select eight groups of eight channels"
+    # the periphery with gOut on a sentinel-filled buffer, in the batch's launch order and in index order
+    hout, hev, gout = (_full((batch.total * NCH + 64,), SENT, torch.float32) for _ in range(3))
+    lib_mod.check(lib.sea_hw64_periphery_batch(_ptr(batch.data), _ptr(hout), _ptr(hev), _ptr(gout), _ptr(batch.offsets),
+                                               _ptr(batch.lengths), _ptr(batch.order), batch.n_utt, _stream()), "periphery")
+    hout1, hev1, gout1 = (_full((batch.total * NCH + 64,), SENT, torch.float32) for _ in range(3))  # in index order
+    lib_mod.check(lib.sea_hw64_periphery_batch(_ptr(batch.data), _ptr(hout1), _ptr(hev1), _ptr(gout1), _ptr(batch.offsets),
+                                               _ptr(batch.lengths), None, batch.n_utt, _stream()), "periphery")
+    torch.cuda.synchronize()
+    assert not np.array_equal(batch.order.cpu().numpy(), np.arange(batch.n_utt)), "the batch's launch order is no permutation"
+    assert torch.equal(gout.view(torch.int32), gout1.view(torch.int32)), "gOut depends on the launch order"
+    del hout, hev, hout1, hev1, gout1
+    # the reference-equal pitch: the fixture's, the model's for the short inputs, none for the over-long one
+    pitch = np.concatenate([g[f"pitch_{k}"] for k in AM.AUDIO_CASES] + [m["pitch"] for m in model] + [np.zeros(937, np.int32)])
+    a = dict(g=g, utts=utts, model=model, batch=batch, rows=rows, offs=offs, gout=gout,
+             pitch=torch.from_numpy(pitch.astype(np.int32)).to("cuda:0"), row_offsets=torch.from_numpy(offs).to("cuda:0"))
+    a["before"] = {k: a[k].clone() for k in ("gout", "pitch")}
+    a["runs"] = {"plain": am_launch(a)[0], "nodetails": am_launch(a, details=False)[0],
+                 "permuted": am_launch(a, order=torch.tensor(PERM, dtype=torch.int32, device="cuda:0"))[0]}
+    return a
+
+
+def test_gout_is_the_references(audio):
+    t = M.tables()
+    blocks = _blocks(audio["batch"], audio["gout"])
+    for u, k in enumerate(AM.AUDIO_CASES):
+        _against_crcs(blocks[u][0], audio["g"], "gout", k)
+    for u in range(N_FIX, N_FIX + 5):
+        assert M.same_bits(np.ascontiguousarray(blocks[u][0]), AM.gout(audio["utts"][u], t)), f"utterance {u}: gOut"
+    for u, (body, pad) in enumerate(blocks):
+        assert not (body == SENT).any() and (pad == SENT).all(), f"utterance {u}: gOut's padding was written, or a sample was not"
+    assert (audio["gout"][audio["batch"].total * NCH:] == SENT).all()
+
+
+def _check_fixture_rows(out, g, u, k, r0, n, tol, run, details=True):
+    assert out["status"][u] == 0
+    assert np.array_equal(out["amcrn"][r0:r0 + n], g[f"amcrn_{k}"].astype(np.float32)), f"{run}, {k}: AmCrn"
+    if details:
+        assert M.same_bits(np.ascontiguousarray(out["seng"][r0:r0 + n]), g[f"seng_{k}"]), f"{run}, {k}: sEng"
+        ref, got = g[f"ratio_{k}"], out["ratio"][r0:r0 + n]
+        on = ref != 0
+        assert np.array_equal(got != 0, on), f"{run}, {k}: the units where sinModel runs"
+        rel = np.abs(got[on].astype(np.float64) - ref[on]) / ref[on]
+        print(f"{run}, {k}: ratio's largest relative difference {rel.max():.3g} (tolerance {tol:.3g})")
+        assert rel.max() <= tol, f"{run}, {k}: ratio"
+
+
+def _check_am(audio, out, run, details=True):
+    g, tol = audio["g"], float(audio["g"]["ratio_tol"])
+    total, n_utt = int(audio["rows"].sum()), len(audio["utts"])
+
+    def rows(name, u):
+        return out[name][int(audio["offs"][u]):int(audio["offs"][u]) + int(audio["rows"][u])]
+
+    for u, k in enumerate(AM.AUDIO_CASES):
+        _check_fixture_rows(out, g, u, k, int(audio["offs"][u]), int(audio["rows"][u]), tol, run, details)
+    for i, m in enumerate(audio["model"]):
+        u = N_FIX + i
+        assert out["status"][u] == m["am"]["status"] == 0
+        assert np.array_equal(rows("amcrn", u), m["am"]["amcrn"]), f"{run}, utterance {u}: AmCrn"
+        if details:
+            assert M.same_bits(np.ascontiguousarray(rows("seng", u)), m["am"]["seng"]), f"{run}, utterance {u}: sEng"
+            ref, got = m["am"]["ratio"], rows("ratio", u)
+            on = ref != 0
+            assert np.array_equal(got != 0, on)
+            assert not on.any() or (np.abs(got[on].astype(np.float64) - ref[on]) / ref[on]).max() <= tol, f"{run}, utterance {u}: ratio"
+    u = n_utt - 1
+    assert out["status"][u] == AM.AM_TOO_LONG and not rows("amcrn", u).any()
+    assert (out["amcrn"][total:] == SENT).all() and not (out["amcrn"][:total] == SENT).any()
+    assert (out["status"][n_utt:] == SENT_I).all()
+    if details:
+        assert not rows("ratio", u).any() and not rows("seng", u).any()
+        for name in ("ratio", "seng"):
+            assert (out[name][total:] == SENT).all() and not (out[name][:total] == SENT).any()
+        for name in ("ampatt", "am"):
+            host = out[name]
+            for v, (off, L) in enumerate(zip(audio["batch"].host_offsets, audio["batch"].host_lengths)):
+                pitch = (int(L) + 7) // 8 * 8
+                b = host[off * NCH:off * NCH + NCH * pitch].reshape(NCH, pitch)
+                assert not (b[:, :int(L)] == SENT).any() and (b[:, int(L):] == SENT).all(), f"{run}, utterance {v}: {name}"
+                if v < N_FIX:
+                    _against_crcs(b[:, :int(L)], g, name, AM.AUDIO_CASES[v])
+                elif v < n_utt - 1:
+                    assert M.same_bits(np.ascontiguousarray(b[:, :int(L)]), audio["model"][v - N_FIX]["am"][name]), f"utterance {v}: {name}"
+                else:
+                    assert not b[:, :int(L)].any()
+            assert (host[audio["batch"].total * NCH:] == SENT).all()
+
+
+@pytest.mark.parametrize("run", ["plain", "permuted"])
+def test_am_stage_equals_the_reference_or_the_model(audio, run):
+    _check_am(audio, audio["runs"][run], run)
+
+
+def test_am_stage_without_its_optional_outputs(audio):
+    out = audio["runs"]["nodetails"]
+    assert out["ratio"] is None and out["ampatt"] is None
+    _check_am(audio, out, "nodetails", details=False)
+    assert M.same_bits(out["amcrn"], audio["runs"]["plain"]["amcrn"]) and np.array_equal(out["status"], audio["runs"]["plain"]["status"])
+
+
+def test_am_inputs_are_unchanged(audio):
+    import torch
+    for k, v in audio["before"].items():
+        assert torch.equal(audio[k].view(torch.int32), v.view(torch.int32)), k
+
+
+def test_fixture_labels_reach_the_upper_channels(audio):
+    """what a 32-bit ballot or a channel bound of 40 would lose"""
+    g = audio["g"]
+    assert sum(int(g[f"amcrn_{k}"][:, 40:].sum()) for k in AM.AUDIO_CASES) > 500
+    late = sum(int(((g[f"final_dev_plus_{k}"][:, 40:] == 1) & (g[f"final_dev_minus_{k}"][:, 40:] == 0)).sum()) for k in AM.AUDIO_CASES)
+    assert late > 0, "no mask unit in channels 40..63 that only develope adds"
+
+
+def test_all_64_channels_at_once_and_a_pitch_out_of_range(audio):
+    """The fixture's five inputs in a batch small enough (under 131 072 padded samples) for the FFT to run over all 64 channels
+    in one launch group, on buffers laid out for 64: the same CRCs, sEng, ratio and AmCrn as the grouped run of the audio
+    batch.  With them a copy of `hi` whose pitch holds 201 at one frame (AM_BAD_PITCH, every output zero), one whose pitches
+    are all 200 and one whose pitches are all 0 (no voiced frame: it skips the stage)."""
+    import torch
+    import speech_enhancement_amd as sea
+    _, lib = _lib()
+    g = audio["g"]
+    tol = float(g["ratio_tol"])
+    utts = [g[f"x_{k}"] for k in AM.AUDIO_CASES] + [g["x_hi"]] * 3
+    batch = sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32)
+    n_utt, total = len(utts), int(batch.total)
+    assert total <= 131072
+    assert int(lib.sea_hw64_am_scratch_bytes(total, n_utt)) == _am_scratch_size(total, n_utt, NCH) != _am_scratch_size(total, n_utt, 8), \
+        "the size rule did not select all 64 channels at once"
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // HOP
+    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    bad = g["pitch_hi"].copy()
+    bad[3] = 201
+    top = np.full_like(bad, 200)
+    pitch = np.concatenate([g[f"pitch_{k}"] for k in AM.AUDIO_CASES] + [bad, top, np.zeros_like(bad)]).astype(np.int32)
+    _, _, gout = sea.hw64_periphery_batch(batch, gout=True)
+    a = dict(batch=batch, rows=rows, utts=utts, gout=gout, pitch=torch.from_numpy(pitch).to("cuda:0"),
+             row_offsets=torch.from_numpy(offs).to("cuda:0"))
+    out, _ = am_launch(a)
+    rows_total = int(rows.sum())
+    for name in ("amcrn", "ratio", "seng"):
+        assert (out[name][rows_total:] == SENT).all() and not (out[name][:rows_total] == SENT).any(), name
+    assert (out["status"][n_utt:] == SENT_I).all()
+    want_top = AM.am_stage(AM.gout(g["x_hi"], M.tables()), top)
+    for u in range(n_utt):
+        r0, n = int(offs[u]), int(rows[u])
+        off, L = int(batch.host_offsets[u]), len(utts[u])
+        pitch_u = (L + 7) // 8 * 8
+        blocks = {name: out[name][off * NCH:off * NCH + NCH * pitch_u].reshape(NCH, pitch_u) for name in ("ampatt", "am")}
+        for name, b in blocks.items():
+            assert not (b[:, :L] == SENT).any() and (b[:, L:] == SENT).all(), f"utterance {u}: {name}"
+        if u < N_FIX:
+            k = AM.AUDIO_CASES[u]
+            for name, b in blocks.items():
+                _against_crcs(b[:, :L], g, name, k)
+            _check_fixture_rows(out, g, u, k, r0, n, tol, "all 64 at once")
+        elif u == N_FIX + 1:  # every block at the largest pitch: the 1119-tap filter throughout, against the model
+            assert out["status"][u] == 0
+            for name, b in blocks.items():
+                assert M.same_bits(np.ascontiguousarray(b[:, :L]), want_top[name]), f"pitch 200 throughout: {name}"
+            assert M.same_bits(np.ascontiguousarray(out["seng"][r0:r0 + n]), want_top["seng"])
+        else:
+            assert out["status"][u] == (AM.AM_BAD_PITCH if u == N_FIX else 0), f"utterance {u}: status {int(out['status'][u]):#x}"
+            assert not any(out[name][r0:r0 + n].any() for name in ("amcrn", "ratio", "seng")), f"utterance {u}"
+            assert not blocks["ampatt"][:, :L].any() and not blocks["am"][:, :L].any(), f"utterance {u}"
+
+
+def test_an_output_that_is_an_input_is_refused(audio):
+    import torch
+    _, lib = _lib()
+    batch, n_utt = audio["batch"], len(audio["utts"])
+    amcrn = torch.zeros((int(audio["rows"].sum()) + 1, NCH), dtype=torch.float32, device="cuda:0")
+    status = torch.zeros(n_utt, dtype=torch.int32, device="cuda:0")
+    scratch = torch.empty(64, dtype=torch.uint8, device="cuda:0")  # a refused call launches nothing
+    head = (_ptr(audio["gout"]), _ptr(audio["pitch"]), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(audio["row_offsets"]))
+    for am_out, ratio, ampatt in ((audio["gout"], None, None), (amcrn, amcrn, None), (amcrn, None, audio["gout"])):
+        rc = lib.sea_hw64_am_batch(*head, _ptr(am_out), _ptr(ratio), None, _ptr(ampatt), None, _ptr(status), _ptr(scratch), batch.total,
+                                   None, n_utt, _stream())
+        assert rc != 0
+    rc = lib.sea_hw64_am_batch(*head, _ptr(amcrn), None, None, None, None, _ptr(amcrn), _ptr(scratch), batch.total, None, n_utt, _stream())
+    assert rc != 0, "d_status == d_amcrn must be refused"
+    for missing in range(5):  # a null input
+        args = list(head)
+        args[missing] = None
+        assert lib.sea_hw64_am_batch(*args, _ptr(amcrn), None, None, None, None, _ptr(status), _ptr(scratch), batch.total, None, n_utt,
+                                     _stream()) != 0
+    assert lib.sea_hw64_am_batch(*head, None, None, None, None, None, _ptr(status), _ptr(scratch), batch.total, None, n_utt, _stream()) != 0
+    assert lib.sea_hw64_am_batch(*head, _ptr(amcrn), None, None, None, None, None, _ptr(scratch), batch.total, None, n_utt, _stream()) != 0
+    assert lib.sea_hw64_am_batch(*head, _ptr(amcrn), None, None, None, None, _ptr(status), None, batch.total, None, n_utt, _stream()) != 0
+    assert lib.sea_hw64_am_batch(*head, _ptr(amcrn), None, None, None, None, _ptr(status), _ptr(scratch), 0, None, n_utt, _stream()) != 0
+    # the whole estimator: the input as an output, every pair of outputs, a null pointer
+    total = int(audio["rows"].sum())
+    o = dict(mask=amcrn, pitch=torch.zeros(total + 1, dtype=torch.int32, device="cuda:0"), status=status,
+             stages=torch.zeros(64, dtype=torch.float32, device="cuda:0"))
+    pairs = [("mask", batch.data)] + [(a, o[b]) for i, a in enumerate(o) for b in list(o)[:i]] + [(a, None) for a in ("mask", "pitch", "status")]
+    assert len(pairs) == 10
+    for name, other in pairs:
+        p = dict(o, **{name: other})
+        rc = lib.sea_hw64_ibm_batch(_ptr(batch.data), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(audio["row_offsets"]), _ptr(p["mask"]),
+                                    _ptr(p["pitch"]), _ptr(p["status"]), _ptr(p["stages"]), _ptr(scratch), batch.total, total, None, n_utt,
+                                    _stream())
+        assert rc != 0, f"sea_hw64_ibm_batch: {name} shared with another buffer, or null, must be refused"
+    torch.cuda.synchronize()
+
+
+# ---- the whole estimator ---------------------------------------------------------------------------------------------------------
+def ibm_launch(audio, order=None, stages=True):
+    import torch
+    lib_mod, lib = _lib()
+    batch, total, n_utt = audio["batch"], int(audio["rows"].sum()), len(audio["utts"])
+    o = dict(mask=_full((total + GUARD, NCH), SENT, torch.float32), pitch=_full((total + GUARD,), SENT_I, torch.int32),
+             status=_full((n_utt + GUARD,), SENT_I, torch.int32), stages=_full(((total + GUARD) * FW,), SENT, torch.float32) if stages else None)
+    scratch = torch.empty(int(lib.sea_hw64_ibm_scratch_bytes(batch.total, total, n_utt)) + 64, dtype=torch.uint8, device="cuda:0")
+    rc = lib.sea_hw64_ibm_batch(_ptr(batch.data), _ptr(batch.offsets), _ptr(batch.lengths), _ptr(audio["row_offsets"]), _ptr(o["mask"]),
+                                _ptr(o["pitch"]), _ptr(o["status"]), _ptr(o["stages"]), _ptr(scratch), batch.total, total, _ptr(order), n_utt,
+                                _stream())
+    lib_mod.check(rc, "sea_hw64_ibm_batch")
+    torch.cuda.synchronize()
+    return {k: (v.cpu().numpy() if v is not None else None) for k, v in o.items()}
+
+
+def _check_ibm(audio, out, run):
+    g = audio["g"]
+    total, n_utt = int(audio["rows"].sum()), len(audio["utts"])
+    for u in range(n_utt):
+        r0, n = int(audio["offs"][u]), int(audio["rows"][u])
+        mask, pitch, status = out["mask"][r0:r0 + n], out["pitch"][r0:r0 + n], int(out["status"][u])
+        if u < N_FIX:
+            k = AM.AUDIO_CASES[u]
+            assert np.array_equal(mask, g[f"mask_{k}"].astype(np.float32)), f"{run}, {k}: the mask is not createIBM's"
+            assert np.array_equal(pitch, g[f"pitch_{k}"]) and status >> 18 == 0 and status & 0xffff > 0, f"{run}, {k}: pitch / status {status:#x}"
+            if out["stages"] is not None:
+                st = out["stages"][r0 * FW:(r0 + n) * FW].reshape(len(AM.FINAL_STAGES), n, NCH)
+                for i, name in enumerate(AM.FINAL_STAGES):
+                    assert np.array_equal(st[i], g[f"{name}_{k}"].astype(np.float32)), f"{run}, {k}: {name}"
+        elif u < n_utt - 1:
+            m = audio["model"][u - N_FIX]
+            assert np.array_equal(mask, m["mask"]) and np.array_equal(pitch, m["pitch"]) and status == m["status"], f"{run}, utterance {u}"
+        else:
+            assert status & AM.AM_TOO_LONG and not mask.any(), f"{run}: the over-long utterance, status {status:#x}"
+    assert (out["mask"][total:] == SENT).all() and not (out["mask"][:total] == SENT).any()
+    assert (out["pitch"][total:] == SENT_I).all() and not (out["pitch"][:total] == SENT_I).any()
+    assert (out["status"][n_utt:] == SENT_I).all() and not (out["status"][:n_utt] == SENT_I).any()
+    if out["stages"] is not None:
+        assert (out["stages"][total * FW:] == SENT).all() and not (out["stages"][:total * FW] == SENT).any()
+
+
+def test_whole_estimator_gives_createibms_mask(audio):
+    import torch
+    data = audio["batch"].data.clone()
+    plain = ibm_launch(audio)
+    _check_ibm(audio, plain, "plain")
+    nost = ibm_launch(audio, stages=False)
+    _check_ibm(audio, nost, "no stages")
+    assert M.same_bits(plain["mask"], nost["mask"])
+    _check_ibm(audio, ibm_launch(audio, order=torch.tensor(PERM, dtype=torch.int32, device="cuda:0")), "permuted")
+    assert torch.equal(audio["batch"].data.view(torch.int32), data.view(torch.int32)), "the input changed"
+    assert sum(int(audio["g"][f"mask_{k}"].sum()) for k in AM.AUDIO_CASES) > 2000
+
+
+def test_python_layer_and_single_utterance_form(audio):
+    import speech_enhancement_amd as sea
+    g = audio["g"]
+    res = sea.hw64_ibm_batch(audio["batch"], stages=True)
+    for u, k in enumerate(AM.AUDIO_CASES):
+        got = res.utterance(u)
+        assert got["mask"].shape == (len(g[f"x_{k}"]) // HOP, NCH)
+        assert np.array_equal(got["mask"], g[f"mask_{k}"].astype(np.float32)) and np.array_equal(got["pitch"], g[f"pitch_{k}"]), k
+        assert np.array_equal(got["final_reseg2"], g[f"final_reseg2_{k}"].astype(np.float32)), k
+        assert np.array_equal(got["final_dev_plus"], g[f"final_dev_plus_{k}"].astype(np.float32)), k
+    assert sea.hw64_ibm_batch(audio["batch"], use_order=False).stages is None
+    for u in (1, 2, 3):
+        k = AM.AUDIO_CASES[u]
+        got = sea.hw64_ibm(audio["utts"][u])
+        assert np.array_equal(got["mask"], g[f"mask_{k}"].astype(np.float32)) and np.array_equal(got["pitch"], g[f"pitch_{k}"]), k
+        assert got["status"] >> 18 == 0
+    for u in (6, 8, 9):
+        got, m = sea.hw64_ibm(audio["utts"][u]), audio["model"][u - N_FIX]
+        assert np.array_equal(got["mask"], m["mask"]) and got["status"] == m["status"], u
+    assert sea.hw64_ibm(np.zeros(1600, np.float32))["mask"].shape == (10, 64)
+    empty = sea.hw64_ibm(np.zeros(0, np.float32))
+    assert empty["mask"].shape == (0, 64) and empty["pitch"].shape == (0,) and empty["status"] == 0
+    hout, hev, gout = sea.hw64_periphery_batch(audio["batch"], gout=True)
+    am = sea.hw64_am_batch(audio["batch"], gout, audio["pitch"], want_details=True)
+    assert np.array_equal(am.utterance(3)["amcrn"], g["amcrn_hi"].astype(np.float32))
+    _against_crcs(am.utterance(3)["am"], g, "am", "hi")
+    assert am.utterance(10)["status"] == AM.AM_TOO_LONG
+    _, lib = _lib()
+    assert lib.sea_hw64_ibm(None, -1, None, None, None) != 0 and lib.sea_hw64_ibm(None, 160, None, None, None) != 0
+
+
+# ---- arrays straight into sea_hw64_finalseg_batch ---------------------------------------------------------------------------------
+def final_launch(cases, order=None, stages=True, grp_final=True):
+    import torch
+    lib_mod, lib = _lib()
+    rows = np.array([c["grp"].shape[0] for c in cases], np.int64)
+    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    total, n_utt = int(rows.sum()), len(cases)
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+    inp = {k: dev(np.concatenate([np.asarray(c[k], np.float32) for c in cases])) for k in ("grp", "amcrn", "cross_ev", "pratio")}
+    before = {k: v.clone() for k, v in inp.items()}
+    o = dict(mask=_full((total + GUARD, NCH), SENT, torch.float32), status=_full((n_utt + GUARD,), SENT_I, torch.int32),
+             grp_final=_full((total + GUARD, NCH), SENT, torch.float32) if grp_final else None,
+             stages=_full(((total + GUARD) * FW,), SENT, torch.float32) if stages else None)
+    scratch = torch.empty(int(lib.sea_hw64_finalseg_scratch_bytes(total, n_utt)) + 64, dtype=torch.uint8, device="cuda:0")
+    d_lengths, d_offs = dev(rows * HOP + 7), dev(offs)
+    rc = lib.sea_hw64_finalseg_batch(_ptr(inp["grp"]), _ptr(inp["amcrn"]), _ptr(inp["cross_ev"]), _ptr(inp["pratio"]), _ptr(d_lengths),
+                                     _ptr(d_offs), _ptr(o["mask"]), _ptr(o["grp_final"]), _ptr(o["status"]), _ptr(o["stages"]),
+                                     _ptr(scratch), _ptr(order), n_utt, _stream())
+    lib_mod.check(rc, "sea_hw64_finalseg_batch")
+    torch.cuda.synchronize()
+    for k, v in before.items():
+        assert torch.equal(inp[k].view(torch.int32), v.view(torch.int32)), f"input {k} changed"
+    out = {k: (v.cpu().numpy() if v is not None else None) for k, v in o.items()}
+    assert (out["mask"][total:] == SENT).all() and not (out["mask"][:total] == SENT).any()
+    assert (out["status"][n_utt:] == SENT_I).all() and not (out["status"][:n_utt] == SENT_I).any()
+    if grp_final:
+        assert (out["grp_final"][total:] == SENT).all() and not (out["grp_final"][:total] == SENT).any()
+    if stages:
+        assert (out["stages"][total * FW:] == SENT).all() and not (out["stages"][:total * FW] == SENT).any()
+    return out, rows, offs
+
+
+def test_final_grouping_on_handmade_and_audio_arrays():
+    """The fixture's hand-made cases at [F][64] (a pruned and a kept component in each reSegmentation; growth that needs
+    several sweeps in both directions; units that turn -2 and then 1; no unit; growth across channel 31 / 32 up to channel 63)
+    and the audio cases' stage inputs against the reference's arrays; then more than 400 segments and two rows against the
+    model."""
+    import torch
+    g = AM.load_golden()
+    names = tuple(AM.HAND_CASES) + AM.AUDIO_CASES
+    cases = [AM.HAND_CASES[k]() for k in AM.HAND_CASES] + [{n: g[f"{n}_{k}"].astype(np.float32) for n in ("grp", "amcrn", "cross_ev", "pratio")}
+                                                          for k in AM.AUDIO_CASES]
+    want = [{n: g[f"{n}_{k}"].astype(np.float32) for n in AM.FINAL_STAGES + ("grp_final", "mask")} | {"status": 0} for k in names]
+    more = [AM.many_final_segments_case(), {k: v[:2] for k, v in AM.hand_minus2().items()}]
+    cases += more
+    want += [AM.final_seg(**c) for c in more]
+    assert want[-2]["status"] == AM.FINAL_TOO_MANY_SEGMENTS and want[-1]["status"] == 0
+    perm = torch.tensor(list(reversed(range(len(cases)))), dtype=torch.int32, device="cuda:0")
+    base = None
+    for run, kw in (("plain", {}), ("permuted", dict(order=perm)), ("bare", dict(stages=False, grp_final=False))):
+        out, rows, offs = final_launch(cases, **kw)
+        for u, w in enumerate(want):
+            r0, n = int(offs[u]), int(rows[u])
+            assert int(out["status"][u]) == w["status"], f"{run}, case {u}: status {int(out['status'][u]):#x}"
+            assert np.array_equal(out["mask"][r0:r0 + n], w["mask"]), f"{run}, case {u}: mask"
+            if out["grp_final"] is not None:
+                assert np.array_equal(out["grp_final"][r0:r0 + n], w["grp_final"]), f"{run}, case {u}: grp_final"
+            if out["stages"] is not None:
+                st = out["stages"][r0 * FW:(r0 + n) * FW].reshape(len(AM.FINAL_STAGES), n, NCH)
+                for i, name in enumerate(AM.FINAL_STAGES):
+                    assert np.array_equal(st[i], w[name]), f"{run}, case {u}: {name}"
+        base = base if base is not None else out["mask"]
+        assert M.same_bits(out["mask"], base)
+    _, lib = _lib()
+    t = torch.zeros((16, NCH), dtype=torch.float32, device="cuda:0")
+    meta = torch.tensor([16 * HOP + 7, 0], dtype=torch.int64, device="cuda:0")
+    st = torch.zeros(4, dtype=torch.int32, device="cuda:0")
+    scratch = torch.empty(int(lib.sea_hw64_finalseg_scratch_bytes(16, 1)), dtype=torch.uint8, device="cuda:0")
+    ins = [t.clone() for _ in range(3)]
+    rc = lib.sea_hw64_finalseg_batch(_ptr(t), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(meta), _ptr(meta[1:]), _ptr(t), None,
+                                     _ptr(st), None, _ptr(scratch), None, 1, _stream())
+    assert rc != 0, "mask == grp must be refused"
+    out = t.clone()
+    rc = lib.sea_hw64_finalseg_batch(_ptr(t), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(meta), _ptr(meta[1:]), _ptr(out), None,
+                                     _ptr(out), None, _ptr(scratch), None, 1, _stream())
+    assert rc != 0, "status == mask must be refused"
+    rc = lib.sea_hw64_finalseg_batch(_ptr(t), _ptr(ins[0]), _ptr(ins[1]), _ptr(ins[2]), _ptr(meta), _ptr(meta[1:]), None, None,
+                                     _ptr(st), None, _ptr(scratch), None, 1, _stream())
+    assert rc != 0, "a null mask must be refused"
+    rc = lib.sea_hw64_finalseg_batch(_ptr(t), None, _ptr(ins[1]), _ptr(ins[2]), _ptr(meta), _ptr(meta[1:]), _ptr(out), None,
+                                     _ptr(st), None, _ptr(scratch), None, 1, _stream())
+    assert rc != 0, "a null input must be refused"
+    torch.cuda.synchronize()
+
+
+# ---- the largest FFT ---------------------------------------------------------------------------------------------------------------
+NAMED = (0, 31, 32, 63)
+
+
+def test_longest_supported_utterance_against_the_model():
+    """150000 samples, N = 18: 64 LDS pieces per channel (eight trips of the piece loop) and all six stages over global memory,
+    on a made-up gOut (noise with a slow envelope in all 64 channels).  Its pitch is made by hand: the first block at 200, so
+    that the longest filter's window starts before the utterance; a block of five frames without a voiced frame between voiced
+    ones; a block at 32; voiced frames up to the end, so that the last block's window ends past the utterance.  Beside it 4097
+    samples (N = 13: two pieces, one global stage) and 480 samples, so that workgroups of utterances with a smaller N leave the
+    later stages.  The long utterance alone is past the size rule: eight groups of eight channels.  Expected values from the
+    model on the channels NAMED (the first and the last of the wave and the two either side of its 32-lane halves), which keeps
+    the CPU side short; ratio within the fixture's tolerance, labels compared where no ratio lies in the band.  Every channel
+    is compared between the plain and the permuted run."""
+    import torch
+    import speech_enhancement_amd as sea
+    rng = np.random.default_rng(18)
+    g = AM.load_golden()
+    tol = float(g["ratio_tol"])
+    lens = [4097, 150000, 480]
+    gouts, pitches, want = [], [], []
+    for L in lens:
+        env = 1 + 0.8 * np.sin(2 * np.pi * 100 * np.arange(L) / 16000)
+        a = (rng.normal(0, 300, (NCH, L)) * env).astype(np.float32)
+        gouts.append(a)
+        nfr = L // HOP
+        p = AM.gap_pitch(nfr) if nfr >= 25 else np.array([0, 80, 0], np.int32)
+        if L > 100000:
+            p[15:nfr - 8] = 0  # 180 of the 187 blocks have no voiced frame: the model skips them
+            p[nfr - 8:] = 150
+        pitches.append(p)
+        # the model on the named channels: the pattern and its normalisation per channel, the rate on an array of 64
+        patt = AM.am_patt(a[list(NAMED)], p)
+        am = np.zeros((NCH, L), np.float32)
+        am[list(NAMED)] = AM.normalised(patt)
+        seng, ratio, label = AM.am_rate(am, p)
+        want.append(dict(ampatt=patt, am=am[list(NAMED)], seng=seng[:, NAMED], ratio=ratio[:, NAMED], amcrn=label[:, NAMED]))
+    blocks = [AM.block_mean_pitch(pitches[1], f) for f in range(2, lens[1] // HOP, 5)]
+    assert blocks[0] == 200 and blocks[1] is None and blocks[2] == 32 and blocks[-1] == 150 and len(blocks) == 187
+    batch = sea.PackedBatch.from_arrays([np.zeros(L, np.float32) for L in lens], device="cuda:0", dtype=np.float32)
+    _, lib = _lib()
+    assert int(lib.sea_hw64_am_scratch_bytes(int(batch.total), 3)) == _am_scratch_size(int(batch.total), 3, 8)
+    packed = np.zeros(batch.total * NCH, np.float32)
+    for a, off, L in zip(gouts, batch.host_offsets, lens):
+        pitch = (L + 7) // 8 * 8
+        packed[off * NCH:off * NCH + NCH * pitch].reshape(NCH, pitch)[:, :L] = a
+    d_gout, d_pitch = torch.from_numpy(packed).to("cuda:0"), torch.from_numpy(np.concatenate(pitches)).to("cuda:0")
+    res = sea.hw64_am_batch(batch, d_gout, d_pitch, want_details=True)
+    other = sea.hw64_am_batch(batch, d_gout, d_pitch, want_details=True, use_order=False)
+    torch.cuda.synchronize()
+    assert not np.array_equal(batch.order.cpu().numpy(), np.arange(3)), "the batch's launch order is no permutation"
+    for name in ("amcrn", "ratio", "seng", "ampatt", "am", "status"):
+        assert torch.equal(getattr(res, name).view(torch.int32), getattr(other, name).view(torch.int32)), f"{name} depends on the launch order"
+    for u, w in enumerate(want):
+        got = res.utterance(u)
+        assert got["status"] == 0
+        for name in ("ampatt", "am"):
+            assert M.same_bits(np.ascontiguousarray(got[name][list(NAMED)]), w[name]), f"L = {lens[u]}: {name}"
+        assert M.same_bits(np.ascontiguousarray(got["seng"][:, NAMED]), w["seng"]), f"L = {lens[u]}: sEng"
+        on = w["ratio"] != 0
+        assert np.array_equal(got["ratio"][:, NAMED] != 0, on) and on.sum() >= (60, 60, 4)[u]
+        rel = np.abs(got["ratio"][:, NAMED][on].astype(np.float64) - w["ratio"][on]) / w["ratio"][on]
+        assert rel.max() <= tol, f"L = {lens[u]}: ratio differs by {rel.max():.3g}"
+        clear = ~(np.abs(w["ratio"].astype(np.float64) - AM.THETAE) <= tol * AM.THETAE)
+        assert np.array_equal(got["amcrn"][:, NAMED][clear], w["amcrn"][clear]), f"L = {lens[u]}: AmCrn"
+        assert np.abs(got["ampatt"]).max(axis=1).min() > 0, "a channel's pattern is all zeros"

@@ -16,6 +16,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw25pitch --steps 3  # its initial grouping and pitch tracking beside the correlogram, opt-in
     python tools/bench_extra.py --what hw64pitch --steps 3  # the same stage at 16 kHz on the 64-channel bank, opt-in
     python tools/bench_extra.py --what hw25ibm --steps 3  # its AM stage, final grouping and the whole estimator beside the other stages, opt-in
+    python tools/bench_extra.py --what hw64ibm --steps 3  # the same at 16 kHz on the 64-channel bank; also writes profiles/hw64ibm_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
 """
 import argparse
@@ -1354,6 +1355,121 @@ def main():
                           "voiced_frames": int((pitch.cpu().numpy() > 0).sum()), "am_labels": int(amcrn.sum().item()),
                           "mask_units": int(mask.sum().item())}), flush=True)
         del hout, hev, gout, acf_hc, scr_am, scr_ibm
+
+    if "hw64ibm" in what:
+        # The rest of the Hu-Wang estimator at 16 kHz on the 64-channel bank (computeAM, finalSeg) and the whole of createIBM on
+        # the --utts corpus batch taken as 16 kHz float samples, beside the stages that exist, in one process and with the scheme
+        # of --what hw25ibm: the periphery with the gOut store, the correlogram with the corrHc ACF output, initGroup + pitchDtm,
+        # the AM stage, the final grouping, and sea_hw64_ibm_batch.  Device events around every step, one warm-up discarded,
+        # median.  The single stages need three sample streams of 256 B per sample, the ACF of 51 456 B per row and the AM
+        # scratch (two more streams and the FFT's buffers); the launch group keeps all of that in its own scratch, so the stages'
+        # buffers are freed before it is allocated.  The larger of the two is checked against the free device memory BEFORE
+        # anything is allocated; if the corpus whole does not fit, its first half, quarter, ... runs, and the lines say so.
+        # The lines also go to profiles/hw64ibm_bench_extra.jsonl.
+        lib = sea.load()
+
+        def plan(k):
+            lengths = np.array([corpus.utterance_length(u) for u in range(k)], dtype=np.int64)
+            _, tot, _ = sea.PackedBatch.layout(lengths)
+            fr = int((lengths // 160).sum())
+            stage_bytes = (4 * (3 * tot * 64 + fr * 64 * 201 + 13 * fr * 64 + 3 * fr) + int(lib.sea_hw64_pitch_scratch_bytes(fr, k))
+                           + int(lib.sea_hw64_am_scratch_bytes(tot, k)) + int(lib.sea_hw64_finalseg_scratch_bytes(fr, k)))
+            group_bytes = int(lib.sea_hw64_ibm_scratch_bytes(tot, fr, k)) + 4 * (2 * fr * 64 + 2 * fr)
+            return max(stage_bytes, group_bytes) + 4 * int(tot)
+
+        free, _ = torch.cuda.mem_get_info()
+        n = args.utts
+        while n > 1 and plan(n) >= 0.9 * free:
+            n //= 2
+        need = plan(n)
+        assert need < 0.9 * free, f"hw64ibm: one utterance needs {need / 1e9:.1f} GB, {free / 1e9:.1f} GB of device memory are free"
+        shard = batch if n == args.utts else bench.build_shard(n, 0, dev)
+        x = shard.data.to(torch.float32)
+        rows = np.asarray(shard.host_lengths, dtype=np.int64) // 160
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames, total = int(rows.sum()), int(shard.total)
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev, gout = z(total * 64), z(total * 64), z(total * 64)
+        cross_hc, cross_ev, pratio_in, mark, gpitch = z((frames, 64)), z((frames, 64)), z((frames, 64)), z((frames, 64)), z(frames, torch.int32)
+        acf_hc = z((frames, 64, 201))
+        pitch, grp, pratio, status = z(frames, torch.int32), z((frames, 64)), z((frames, 64)), z(n, torch.int32)
+        amcrn, mask, st_am, st_fin, st_ibm, pitch2, mask2 = z((frames, 64)), z((frames, 64)), z(n, torch.int32), z(n, torch.int32), z(n, torch.int32), z(frames, torch.int32), z((frames, 64))
+        scr_pitch = torch.empty(int(lib.sea_hw64_pitch_scratch_bytes(frames, n)), dtype=torch.uint8, device=dev)
+        scr_am = torch.empty(int(lib.sea_hw64_am_scratch_bytes(total, n)), dtype=torch.uint8, device=dev)
+        scr_fin = torch.empty(int(lib.sea_hw64_finalseg_scratch_bytes(frames, n)), dtype=torch.uint8, device=dev)
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+        order = shard.order
+
+        def periphery(with_gout=True):
+            assert lib.sea_hw64_periphery_batch(P(x), P(hout), P(hev), P(gout) if with_gout else None, P(shard.offsets), P(shard.lengths), P(order), n, st) == 0, lib.sea_last_error()
+
+        def correlogram():
+            assert lib.sea_hw64_correlogram_batch(P(hout), P(hev), P(shard.offsets), P(shard.lengths), P(d_offs), P(acf_hc), None, P(cross_hc),
+                                                  P(cross_ev), P(gpitch), P(pratio_in), P(mark), None, P(order), n, st) == 0, lib.sea_last_error()
+
+        def pitch_stage():
+            assert lib.sea_hw64_pitch_batch(P(acf_hc), P(pratio_in), P(mark), P(shard.lengths), P(d_offs), P(pitch), P(grp), P(pratio),
+                                            P(status), None, P(scr_pitch), P(order), n, st) == 0, lib.sea_last_error()
+
+        def am_stage():
+            assert lib.sea_hw64_am_batch(P(gout), P(pitch), P(shard.offsets), P(shard.lengths), P(d_offs), P(amcrn), None, None, None, None,
+                                         P(st_am), P(scr_am), total, P(order), n, st) == 0, lib.sea_last_error()
+
+        def final_stage():
+            assert lib.sea_hw64_finalseg_batch(P(grp), P(amcrn), P(cross_ev), P(pratio), P(shard.lengths), P(d_offs), P(mask), None, P(st_fin),
+                                               None, P(scr_fin), P(order), n, st) == 0, lib.sea_last_error()
+        samples = int(np.sum(shard.host_lengths))
+        chunk = 64 if total * 2 * 64 * 16 <= (256 << 20) else 8
+        part = "WHOLE" if n == args.utts else f"FIRST {n} UTTERANCES ONLY (the whole does not fit)"
+        workload = (f"the {args.utts}-utterance corpus, {part}, as 16 kHz float samples: {samples} samples, {frames} frames of 160, "
+                    f"{need / 1e9:.1f} GB of device memory at the most ({free / 1e9:.0f} GB were free), the FFT over {chunk} channels per launch "
+                    f"group; median of {args.steps} steps after one warm-up")
+        out_path = os.path.join(ROOT, "profiles", "hw64ibm_bench_extra.jsonl")
+        lines = []
+
+        def emit(record):
+            lines.append(json.dumps(record))
+            print(lines[-1], flush=True)
+
+        results = {}
+
+        def measure(key, name, fn, kernels):
+            med, t = median_ms(fn, args.steps)
+            results[key] = med
+            emit({"metric": f"Hu-Wang estimator, 64-channel 16 kHz bank: {name} (frames of 160 samples/sec); a first form, not tuned",
+                  "value": frames / (med / 1e3), "unit": "frames/s", "ms_per_step": med,
+                  "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels})
+
+        measure("periphery_plain", "periphery without gOut", lambda: periphery(False), "sea::hw64_periphery_kernel + sea::hw64_lowpass_kernel")
+        measure("periphery", "periphery with the gOut store", periphery, "sea::hw64_periphery_kernel + sea::hw64_lowpass_kernel")
+        measure("correlogram", "correlogram with the corrHc ACF output", correlogram, "sea::hw64_correlogram_kernel")
+        measure("pitch", "initial grouping and pitch tracking", pitch_stage, "the eight launches of sea_hw64_pitch_batch")
+        measure("am", "AM stage (amPatt, hilbert, computeAMRate)", am_stage,
+                "sea::hw64_am_prepare_kernel + _patt_kernel + per channel group (_fft_head_kernel + 6 x _fft_stage_kernel) x 2 + _norm_kernel; _rate_kernel")
+        measure("final", "final grouping (finalSeg)", final_stage, "sea::hw64_finalseg_kernel")
+        del hout, hev, gout, acf_hc, scr_am, scr_pitch, scr_fin
+        torch.cuda.empty_cache()
+        scr_ibm = torch.empty(int(lib.sea_hw64_ibm_scratch_bytes(total, frames, n)), dtype=torch.uint8, device=dev)
+
+        def whole():
+            assert lib.sea_hw64_ibm_batch(P(x), P(shard.offsets), P(shard.lengths), P(d_offs), P(mask2), P(pitch2), P(st_ibm), None, P(scr_ibm),
+                                          total, frames, P(order), n, st) == 0, lib.sea_last_error()
+        measure("whole", "the whole estimator, sea_hw64_ibm_batch", whole, "all of the above")
+        assert torch.equal(mask, mask2) and torch.equal(pitch, pitch2), "the launch group and the single stages differ"
+        s_host = (st_ibm.cpu().numpy() | st_am.cpu().numpy() | st_fin.cpu().numpy())
+        emit({"metric": "Hu-Wang estimator, 64-channel 16 kHz bank: each stage relative to the correlogram of the same run",
+              "value": results["whole"] / results["correlogram"], "unit": "ratio (the whole estimator)",
+              "stage_over_correlogram": {k: v / results["correlogram"] for k, v in results.items()},
+              "config": {"workload": workload, "fft_channels_per_launch_group": chunk},
+              "utterances_flagged": {"final_too_many_segments": int((s_host >> 18 & 1).sum()), "am_too_long": int((s_host >> 19 & 1).sum()),
+                                     "am_bad_pitch": int((s_host >> 20 & 1).sum())},
+              "voiced_frames": int((pitch.cpu().numpy() > 0).sum()), "am_labels": int(amcrn.sum().item()),
+              "am_labels_in_channels_40_to_63": int(amcrn[:, 40:].sum().item()), "mask_units": int(mask.sum().item())})
+        with open(out_path, "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+        del scr_ibm
 
     if "hw25resynth" in what:
         # The Hu-Wang resynthesis on the --utts corpus batch taken as float samples, in one process: sea_hw25_resynth_batch alone
