@@ -468,7 +468,8 @@ int sea_addnoise(const short *clean, const short *noise, long L, int db, short *
  * then sea_irm_target_batch (clean, scaled noise), all on `stream`.  The subband buffers are the caller's, 64x the packed size
  * each; with d_sums given nothing is allocated inside (without it: the per-thread buffer and its rule above).  Every utterance
  * needs 320 samples: the lengths are read back first (one stream synchronisation) and a shorter one makes the call return
- * non-zero before anything is launched. */
+ * non-zero before anything is launched.  This is the one device-pointer call that waits for its stream; on a stream that is
+ * being captured into a graph it returns non-zero at once, before the read-back, and leaves the capture valid. */
 int sea_trainset_batch(const short *d_clean, const long long *d_offsets, const long long *d_lengths, const short *d_noise_src,
                        const long long *d_noise_start, const float *d_snr_lin, short *d_noise_scaled, short *d_noisy,
                        float *d_sums, float *d_gain, short *d_sub_clean, short *d_sub_noise, short *d_sub_noisy,

@@ -308,7 +308,16 @@ int sea_trainset_batch(const short *d_clean, const long long *d_offsets, const l
     if (window < 0 || window > 2) return fail("trainset: window %d (0 rectangular, 1 Hamming, 2 Hanning)", window);
     if (!d_sub_clean || !d_sub_noise || !d_row_offsets || !d_irm || !d_lengths)
         return fail("trainset: a required pointer is NULL");
-    /* make_single_IBM's frame count (L - 320) / 160 + 1 needs one frame: the lengths come back before anything is launched */
+    /* make_single_IBM's frame count (L - 320) / 160 + 1 needs one frame: the lengths come back before anything is launched.
+     * A capturing stream cannot be synchronised, and trying to would invalidate the caller's capture: refuse first, with the
+     * capture left intact (the query is legal during capture) */
+    if (stream) {
+        hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+        HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &capturing));
+        if (capturing != hipStreamCaptureStatusNone)
+            return fail("trainset: the call reads the lengths back before it launches and cannot be captured in a graph "
+                        "(capture sea_addnoise_batch, sea_subband64_batch and sea_irm_target_batch instead)");
+    }
     std::vector<long long> lens((size_t)n_utt);
     HIP_TRY(hipMemcpyAsync(lens.data(), d_lengths, (size_t)n_utt * sizeof(long long), hipMemcpyDeviceToHost, (hipStream_t)stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));

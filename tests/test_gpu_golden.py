@@ -48,14 +48,15 @@ def test_golden_etsi_denoise_drop_in():
         assert np.array_equal(got, want), f"{name}: {np.count_nonzero(got != want)} of {len(x)} samples differ from the reference"
 
 
-def test_golden_noisesup_batch_int16_float_stream_and_cepstra():
+def test_golden_noisesup_batch_int16_float_stream_and_cepstra(names=NAMES):
     """The batch entry points on the six golden utterances at once: int16 output, the float NoiseSup stream and
     the cepstra computed from it, against the reference's ns_trace (NoiseSup driven explicitly, CompCeps through
-    BufInGetLast, oracle/ref_driver.c)."""
+    BufInGetLast, oracle/ref_driver.c).  names: the utterances of the batch, in order
+    (tests/test_gpu_streams.py runs them in another order as well)."""
     import speech_enhancement_amd as sea
     torch = _torch()
     g = np.load(os.path.join(GOLD, "ns_golden.npz"))
-    utts = [g[f"{n}/in"] for n in NAMES]
+    utts = [g[f"{n}/in"] for n in names]
     batch = sea.PackedBatch.from_arrays(utts)
     out, f32, first = sea.ns_denoise_batch(batch, want_f32=True)
     ceps, cum, n_ceps = sea.compceps_batch(batch, f32, first)
@@ -63,7 +64,7 @@ def test_golden_noisesup_batch_int16_float_stream_and_cepstra():
     got16 = batch.split(out, full_frames_only=True)
     f32h, firsth, cepsh, nc = f32.cpu().numpy(), first.cpu().numpy(), ceps.cpu().numpy(), n_ceps.cpu().numpy()
     worst = 0.0
-    for u, name in enumerate(NAMES):
+    for u, name in enumerate(names):
         full = len(utts[u]) // 80 * 80
         want16 = g[f"{name}/etsi_denoise"][:full]
         assert np.array_equal(got16[u], want16), f"{name}: int16 output differs from the reference"
@@ -134,22 +135,22 @@ def test_golden_compceps_frames():
     assert _bits_differ(one, g["coef"][3]) == 0
 
 
-def test_golden_afe_feature_chain():
+def test_golden_afe_feature_chain(names=NAMES):
     """Speech flags per NoiseSup output frame, features after CompCeps and after PostProc, and the emitted frames
     with their VAD decisions, against what the reference's own DoWaveProc / DoCompCeps / DoPostProc / DoVADProc /
-    FlushAdvProcess produced on the golden utterances."""
+    FlushAdvProcess produced on the golden utterances (names: which, in the order of the batch)."""
     import speech_enhancement_amd as sea
     _torch()
     gi = np.load(os.path.join(GOLD, "ns_golden.npz"))
     g = np.load(os.path.join(GOLD, "afe_golden.npz"))
-    utts = [gi[f"{n}/in"] for n in NAMES]
+    utts = [gi[f"{n}/in"] for n in names]
     batch = sea.PackedBatch.from_arrays(utts)
     res = sea.afe_features_batch(batch, want_intermediates=True)
     flags = res["flags"].cpu().numpy()
     fcc, fpp = res["feat_cc"].cpu().numpy(), res["feat_pp"].cpu().numpy()
     n_ceps, first = res["n_ceps"].cpu().numpy(), res["first_out"].cpu().numpy()
     worst = 0.0
-    for u, name in enumerate(NAMES):
+    for u, name in enumerate(names):
         nfr = len(utts[u]) // 80
         wf = g[f"{name}/flags"]
         assert wf.shape[0] == nfr

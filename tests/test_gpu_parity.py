@@ -128,10 +128,11 @@ def test_etsi_denoise_tail_untouched(oracle):
     _assert_int16_close(got, want, "etsi_denoise ragged")
 
 
-def test_ns_batch_vs_oracle(oracle):
+def test_ns_batch_vs_oracle(oracle, utts=None):
+    """utts: another list than _mixed_corpus() (tests/test_gpu_streams.py: some of it, in two orders)"""
     import speech_enhancement_amd as sea
     _torch()
-    utts = _mixed_corpus()
+    utts = _mixed_corpus() if utts is None else utts
     batch = sea.PackedBatch.from_arrays(utts)
     out, f32, first = sea.ns_denoise_batch(batch, want_f32=True)
     outs = batch.split(out, full_frames_only=True)
