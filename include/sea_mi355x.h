@@ -668,7 +668,8 @@ int sea_hw25_resynth_text_write(const char *path, const float *out, long L);
  * 32), the bank of sea_subband64_batch / sea_resynth64_batch / sea_irm_target_batch (csrc/hw64_kernel.hip, DESIGN.md section
  * 5.16).  Parity: bit for bit against the reference's own functions compiled on a CPU against that header
  * (tests/golden/hw64_*.npz).  initGroup and pitchDtm follow below (sea_hw64_pitch_*), then computeAM, finalSeg and the whole
- * estimator (sea_hw64_am_batch, sea_hw64_finalseg_batch, sea_hw64_ibm*); only resynthesis() is NOT built at 16 kHz.
+ * estimator (sea_hw64_am_batch, sea_hw64_finalseg_batch, sea_hw64_ibm*), then resynthesis() from host memory (sea_hw64_resynth*,
+ * sea_hw64_enhance*): of the reference's chain only resynthesis() is NOT built at 16 kHz as a call on device pointers.
  * The calls mirror the sea_hw25_* front-half calls argument for argument, with 64 / 201 / 160 for 25 / 101 / 80: d_hout / d_hev
  * (and d_gout, the gammatone output before the hair cell; null: not written) hold 64x the packed size, utterance u's
  * [64][pitch] block at d_offsets[u] * 64; utterance u has sea_hw64_frames (lengths[u]) = lengths[u] / 160 rows from
@@ -757,6 +758,54 @@ int sea_hw64_ibm_batch(const float *d_in_f32, const long long *d_offsets, const 
                        float *d_mask, int *d_pitch, int *d_status, float *d_stages, void *d_scratch, long long total_padded_samples,
                        long long total_rows, const int *d_order, int n_utt, void *stream);
 int sea_hw64_ibm(const float *x, long L, float *mask, int *pitch, int *status);
+/* resynthesis() on the same bank (HuWang.cpp:1498-1549 against resyth_64sub_IBM/cpp/HuWang.h; csrc/hw64_resynth_kernel.hip,
+ * DESIGN.md section 5.19): the mask applied to gOut, enhanced 16 kHz audio out, which closes the chain at this bank.  Per channel
+ * c = 0..63 in order, as sea_hw25_resynth* describes it: gOut[c] / midEarCoeff[c] reversed in time, gammaToneFilter again, /
+ * midEarCoeff[c], reversed back; times the overlap-add weight of the frames whose unit is set (mask > threshold; NaN and -0.0 > 0
+ * are not set); the 64 products added in channel order from +0.0f, every channel multiplied and added whatever its weight.
+ * What the constants change: WINDOW = 320 is exactly two hops of 160, so the window IS a raised cosine: a set frame f adds
+ * up160[o] on [160 (f - 1), 160 f) -- not for f = 0 -- and down160[o] on [160 f, 160 f + 160), and nothing after that.  The
+ * largest index frame F - 1 writes is 160 F - 1 <= L - 1 (F = L / 160): the reference never leaves its arrays, no contribution
+ * is dropped, and the reference pins every case.  The samples [160 F, L) have weight 0.
+ * sea_hw64_resynth_tables_host: up160[n] = 0.5 (1 + cos (n pi / 160 + pi)) and down160[n] = 0.5 (1 + cos (n pi / 160)) in double,
+ * and w640[o * 4 + bits], the float weight at position o = 0..159 of a hop, bit 0 / 1 of `bits`: frame k / k + 1 (k = the
+ * sample's index / 160) exists and is set; the terms are added in that order, each a double sum rounded to float, as the
+ * reference's `weight[..] +=`.  Every pointer may be null.
+ * Every call here takes HOST pointers.  The batch launches on device pointers and a stream exist inside the library only; their
+ * exported forms (sea_hw64_resynth_batch, sea_hw64_enhance_batch) are left to a change that also gives them their rows in the
+ * table of caller's-stream tests.
+ * sea_hw64_resynth / sea_hw64_enhance: one utterance, the prototypes of their sea_hw25_* namesakes: mask [F][64] with F = L / 160
+ * (anything else fails); out_f32 [L]; sea_hw64_enhance's mask and pitch may be null, its status word is sea_hw64_ibm's.  L = 0 is
+ * no work (status 0); L < 160 has no frame and gives zeros; more than 150000 samples: the status zeroes the mask, as in
+ * sea_hw64_ibm, and the audio is zeros.  Each is the list form below on a list of one.
+ * sea_hw64_resynth_utterances: n_utt utterances in[u] of lengths[u] float samples (on the int16 scale) with masks[u]
+ * [lengths[u] / 160][64] (may be null where that is no row) -> out_f32[u] floats and out_i16[u], their (short) conversion as the
+ * x86-64 build performs it (see sea_hw25_resynth_batch); either output array may be null as a whole, not both.  Runs the
+ * periphery with gOut and then the resynthesis.
+ * sea_hw64_enhance_utterances: createIBM followed by the resynthesis (threshold 0) of its own mask, from the gOut that
+ * sea_hw64_ibm_batch keeps in its scratch: out_f32 / out_i16 as above; optional (null as a whole, or per utterance) masks[u]
+ * [lengths[u] / 160][64] and pitch[u] [lengths[u] / 160]; status [n_utt], sea_hw64_ibm's words.
+ * Both cut the list, in order and greedily, into chunks that fit HBM; every chunk is one launch group with an LPT launch order
+ * of its own, and the device buffers are sized once for the largest chunk.  A chunk of n utterances with s samples (each
+ * length rounded up to 8) and r rows grows while W + 10 s + 260 r + 32 n stays within the budget, W = sea_hw64_ibm_scratch_bytes
+ * (s, r, n), for the resynthesis alone 768 s (the three [64][pitch] planes); an utterance that exceeds the budget alone gets a
+ * chunk to itself.  The budget is 60 % of the HBM that is free at the call; SEA_HW64_ENHANCE_SCRATCH_MB (MiB) overrides it.
+ * The results do not depend on the cut.  sea_hw64_enhance_plan: that cut for a given budget, without touching a device: returns
+ * the number of chunks (0 for n_utt <= 0, -1 for a null or negative length) and, where cuts is not null, writes that many + 1
+ * ints: the first utterance of every chunk, then n_utt.  sea_hw64_enhance_last_chunks: how many chunks the calling thread's
+ * last list call completed.  sea_hw64_enhance_last_resynth_ms: the device time of that call's resynthesis launches alone, in ms,
+ * summed over its chunks (a pair of device events around each launch): the launch is internal, so it cannot be timed from outside.
+ * sea_hw25_resynth_text_write writes the reference's text file for either bank. */
+int sea_hw64_resynth_tables_host(float *w640, double *up160, double *down160);
+int sea_hw64_resynth(const float *x, long L, const float *mask, long F, float threshold, float *out_f32);
+int sea_hw64_enhance(const float *x, long L, float *out_f32, float *mask, int *pitch, int *status);
+int sea_hw64_resynth_utterances(const float *const *in, const long *lengths, const float *const *masks, float threshold,
+                                float *const *out_f32, short *const *out_i16, int n_utt);
+int sea_hw64_enhance_utterances(const float *const *in, const long *lengths, int n_utt, float *const *out_f32, short *const *out_i16,
+                                float *const *masks, int *const *pitch, int *status);
+int sea_hw64_enhance_plan(const long *lengths, int n_utt, long long budget_bytes, int resynth_only, int *cuts);
+int sea_hw64_enhance_last_chunks(void);
+double sea_hw64_enhance_last_resynth_ms(void);
 /* gammaToneFilter(input, output, fChan, sigLength) for channel `chan` of the 64-band bank */
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength);
 

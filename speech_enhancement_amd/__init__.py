@@ -30,4 +30,5 @@ from .hw25 import (Hw25Result, hw25_correlogram_batch, hw25_frontend, hw25_front
 from .hw64 import (Hw64Result, hw64_correlogram_batch, hw64_frontend, hw64_frontend_batch, hw64_periphery_batch,  # noqa: F401
                    hw64_split, hw64_tables, hw64_workgroups_per_utterance, HW64_STAGE_WORDS, Hw64PitchResult, hw64_pitch,
                    hw64_pitch_batch, hw64_pitch_waves_per_utterance, Hw64AmResult, Hw64MaskResult, hw64_am_batch,
-                   hw64_finalseg_batch, hw64_ibm, hw64_ibm_batch)
+                   hw64_finalseg_batch, hw64_ibm, hw64_ibm_batch, hw64_enhance, hw64_enhance_plan, hw64_enhance_utterances,
+                   hw64_resynth, hw64_resynth_tables, hw64_resynth_utterances)

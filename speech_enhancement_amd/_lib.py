@@ -128,6 +128,14 @@ PROTOTYPES = {
     "sea_hw64_ibm_scratch_bytes": (_ll, [_ll, _ll, _i]),
     "sea_hw64_ibm_batch": (_i, [_vp] * 9 + [_ll, _ll, _vp, _i, _vp]),
     "sea_hw64_ibm": (_i, [_vp, _l, _vp, _vp, _vp]),
+    "sea_hw64_resynth_tables_host": (_i, [_vp, _vp, _vp]),
+    "sea_hw64_resynth": (_i, [_vp, _l, _vp, _l, _c.c_float, _vp]),
+    "sea_hw64_enhance": (_i, [_vp, _l, _vp, _vp, _vp, _vp]),
+    "sea_hw64_resynth_utterances": (_i, [_vp, _vp, _vp, _c.c_float, _vp, _vp, _i]),
+    "sea_hw64_enhance_utterances": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "sea_hw64_enhance_plan": (_i, [_vp, _i, _ll, _i, _vp]),
+    "sea_hw64_enhance_last_chunks": (_i, []),
+    "sea_hw64_enhance_last_resynth_ms": (_c.c_double, []),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

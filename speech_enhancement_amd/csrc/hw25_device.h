@@ -1,6 +1,7 @@
 /*
  * hw25_device.h -- what the Hu-Wang kernel files share on the device: the gammatone recurrence of the analysis
- * (hw25_kernel.hip, hw64_kernel.hip) and of the resynthesis that inverts it (hw25_resynth_kernel.hip), the hair cell's step of
+ * (hw25_kernel.hip, hw64_kernel.hip) and of the resynthesis that inverts it (hw25_resynth_kernel.hip, hw64_resynth_kernel.hip:
+ * the tile's constants, a group of the second pass and the (short) conversion), the hair cell's step of
  * both banks' analysis, and the constants, the lane fence and
  * the label propagation of the estimator's two segmentations, initGroup's (hw25_pitch_kernel.hip, hw64_pitch_kernel.hip) and
  * finalSeg's reSegmentation (hw25_am_kernel.hip, hw64_am_kernel.hip), over 25 and over 64 lanes, and what both banks' AM stage
@@ -35,6 +36,35 @@ __device__ __forceinline__ float gt25_step(Gt25 &s, float in, float f1, float f2
     s.p[3] = s.p[2] + x[1] + 2 * x[2] + x[3];
     s.q[3] = s.q[2] + y[1] + 2 * y[2] + y[3];
     return out;
+}
+
+/* ---- what the resynthesis kernels of both banks share (hw25_resynth_kernel.hip, hw64_resynth_kernel.hip): one wave per
+ * utterance walks it in tiles of kResynthTile samples, the channel lanes fetching kResynthGroup samples at a time ---- */
+constexpr int kResynthTile = 64;                   /* samples per tile: one per lane in the summing half */
+constexpr int kResynthGroup = 8;                   /* samples per fetch of the recurrence */
+constexpr int kResynthStride = kResynthTile + 1;   /* words per channel row of the LDS tile */
+
+/* resynthesis:1513-1519 for the eight samples tg .. tg + 7 of one channel, the latest first; kPartial: the group that holds
+ * the utterance's last sample, whose samples at or past L are skipped */
+template <bool kPartial>
+__device__ __forceinline__ void resynth_group(Gt25 &s, const float (&x)[kResynthGroup], long long tg, long long L, float f1, float f2,
+                                              float gain, float ear, float *row)
+{
+    const int j = (int)(tg & (kResynthTile - 1));
+#pragma unroll
+    for (int k = kResynthGroup - 1; k >= 0; --k) {
+        if (kPartial && tg + k >= L) continue;
+        const float g2 = gt25_step(s, x[k] / ear, f1, f2, gain);
+        row[j + k] = g2 / ear;
+    }
+}
+
+/* (short) of a float as the x86-64 build converts it (cvttss2si + low half): truncation toward zero to int32, the low 16 bits
+ * kept; NaN or a magnitude of 2^31 and more give 0 */
+__device__ __forceinline__ short resynth_to_short(float v)
+{
+    const int i = fabsf(v) < 2147483648.0f ? (int)v : 0;
+    return (short)(unsigned short)((unsigned)i & 0xffffu);
 }
 
 /* hairCell:279-297 for one sample.  kt is a double expression of the input (float + double literal), rounded once; the rest

@@ -29,32 +29,7 @@ namespace sea {
 namespace {
 
 constexpr int kCh = SEA_HW25_NCHAN, kHop = SEA_HW25_HOP;
-constexpr int kTile = 64;            /* samples per tile: one per lane in the summing half */
-constexpr int kGroup = 8;            /* samples per fetch of the recurrence */
-constexpr int kStride = kTile + 1;   /* words per channel row of the LDS tile */
-
-/* :1513-1519 for the eight samples tg .. tg + 7 of one channel, the latest first; kPartial: the group that holds the
- * utterance's last sample, whose samples at or past L are skipped */
-template <bool kPartial>
-__device__ __forceinline__ void resynth_group(Gt25 &s, const float (&x)[kGroup], long long tg, long long L, float f1, float f2, float gain,
-                                              float ear, float *row)
-{
-    const int j = (int)(tg & (kTile - 1));
-#pragma unroll
-    for (int k = kGroup - 1; k >= 0; --k) {
-        if (kPartial && tg + k >= L) continue;
-        const float g2 = gt25_step(s, x[k] / ear, f1, f2, gain);
-        row[j + k] = g2 / ear;
-    }
-}
-
-/* (short) of a float as the x86-64 build converts it (cvttss2si + low half): truncation toward zero to int32, the low 16 bits
- * kept; NaN or a magnitude of 2^31 and more give 0 */
-__device__ __forceinline__ short resynth_to_short(float v)
-{
-    const int i = fabsf(v) < 2147483648.0f ? (int)v : 0;
-    return (short)(unsigned short)((unsigned)i & 0xffffu);
-}
+constexpr int kTile = kResynthTile, kGroup = kResynthGroup, kStride = kResynthStride; /* hw25_device.h, with resynth_group */
 
 } // namespace
 

@@ -193,6 +193,11 @@ long long sea_hw64_ibm_scratch_bytes(long long total_padded_samples, long long t
     return ibm_layout(total_padded_samples, total_rows, n_utt).end;
 }
 
+long long sea_capi::hw64_ibm_gout_offset(long long total_padded_samples, long long total_rows, int n_utt)
+{
+    return ibm_layout(total_padded_samples, total_rows, n_utt).gout;
+}
+
 int sea_hw64_ibm_batch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
                        float *d_mask, int *d_pitch, int *d_status, float *d_stages, void *d_scratch, long long total_padded_samples,
                        long long total_rows, const int *d_order, int n_utt, void *stream)

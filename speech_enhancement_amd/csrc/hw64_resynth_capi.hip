@@ -1,0 +1,406 @@
+/*
+ * hw64_resynth_capi.hip -- the C ABI of the Hu-Wang resynthesis at 16 kHz on the 64-channel bank (hw64_resynth_kernel.hip):
+ * sea_hw64_resynth_tables_host, the single-utterance forms sea_hw64_resynth and sea_hw64_enhance, the forms that take lists of
+ * utterances in host memory, sea_hw64_resynth_utterances and sea_hw64_enhance_utterances, with the plan that cuts a list into
+ * chunks that fit HBM (sea_hw64_enhance_plan, sea_hw64_enhance_last_chunks, sea_hw64_enhance_last_resynth_ms).  Every exported
+ * call takes host pointers.  The
+ * batch launches on device pointers and a stream, hw64_resynth_launch and hw64_enhance_launch (hw25_capi.h), are internal:
+ * each chunk of a list is one launch group of them, and a single utterance is a list of one.
+ */
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "hw25_capi.h"
+
+using namespace sea_capi;
+
+namespace {
+
+constexpr int kCh = SEA_HW64_NCHAN;
+
+thread_local int t_last_chunks = 0;
+thread_local double t_last_resynth_ms = 0.0;
+
+/* a pair of device events around the resynthesis launch of every chunk, so that the kernel can be timed although its launch is
+ * not exported (sea_hw64_enhance_last_resynth_ms): add_ms() after the chunk's synchronisation */
+struct LaunchTimer {
+    hipEvent_t before = nullptr, after = nullptr;
+    ~LaunchTimer()
+    {
+        if (before) (void)hipEventDestroy(before);
+        if (after) (void)hipEventDestroy(after);
+    }
+    int create()
+    {
+        HIP_TRY(hipEventCreate(&before));
+        HIP_TRY(hipEventCreate(&after));
+        return 0;
+    }
+    int add_ms(double *sum) const
+    {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, before, after));
+        *sum += ms;
+        return 0;
+    }
+};
+
+long long rows_of(long L) { return L > 0 ? L / SEA_HW64_HOP : 0; }
+
+/* Device footprint of a chunk of n utterances with s padded samples and r mask rows in all: what the launch group works in --
+ * the estimator's scratch, or for the resynthesis alone the three [64][pitch] planes hOut, hEv and gOut -- and its I/O buffers:
+ * 10 B per padded sample (float in, float out, int16 out), 260 B per row (mask, pitch), 32 B per utterance (offsets, lengths,
+ * row offsets, launch order, status). */
+long long chunk_bytes(long long s, long long r, int n, int resynth_only)
+{
+    const long long work = resynth_only ? 3 * s * kCh * 4 : sea_hw64_ibm_scratch_bytes(s, r, n);
+    return work + 10 * s + 260 * r + 32LL * n;
+}
+
+/* the list in order, greedily: a chunk grows while its footprint stays within the budget; an utterance that exceeds the
+ * budget alone forms a chunk of its own.  cuts: the first utterance of every chunk, then n_utt. */
+std::vector<int> plan(const long *lengths, int n_utt, long long budget, int resynth_only)
+{
+    std::vector<int> cuts(1, 0);
+    long long s = 0, r = 0;
+    for (int u = 0; u < n_utt; ++u) {
+        const long long su = align8(lengths[u]), ru = rows_of(lengths[u]);
+        if (u > cuts.back() && chunk_bytes(s + su, r + ru, u - cuts.back() + 1, resynth_only) > budget) {
+            cuts.push_back(u);
+            s = r = 0;
+        }
+        s += su;
+        r += ru;
+    }
+    cuts.push_back(n_utt);
+    return cuts;
+}
+
+/* 60 % of the HBM that is free now, as sea_trainset_utterances; SEA_HW64_ENHANCE_SCRATCH_MB overrides it */
+int budget_bytes(long long *budget)
+{
+    if (const char *e = getenv("SEA_HW64_ENHANCE_SCRATCH_MB")) {
+        *budget = atoll(e) * (1LL << 20);
+        return 0;
+    }
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    *budget = (long long)(free_b / 10 * 6);
+    return 0;
+}
+
+/* What both list forms share: the cut, the device and host buffers sized once for the largest chunk, and a chunk's way up
+ * (samples zero-padded to a multiple of 8, offsets | lengths | row offsets, the LPT launch order) and down (float and int16
+ * audio scattered to the callers' buffers). */
+struct List {
+    const float *const *in;
+    const long *lengths;
+    int n_utt, n_cu = 256;
+    std::vector<int> cuts;
+    long long max_s = 0, max_r = 0, max_work = 0;
+    int max_n = 0;
+    DevBuf<float> d_in, d_out, d_mask;
+    DevBuf<short> d_out16;
+    DevBuf<long long> d_meta;
+    DevBuf<int> d_order;
+    std::vector<float> h_f32, h_mask;
+    std::vector<short> h_i16;
+    std::vector<long long> h_meta;
+    std::vector<int> h_order;
+    /* the chunk in hand */
+    int u0 = 0, n = 0;
+    long long s = 0, r = 0;
+    const long long *offs = nullptr, *lens = nullptr, *roff = nullptr;
+
+    int setup(const char *what, const float *const *in_, const long *lengths_, int n_utt_, float *const *out_f32, short *const *out_i16,
+              int resynth_only)
+    {
+        in = in_;
+        lengths = lengths_;
+        n_utt = n_utt_;
+        if (!in || !lengths) return fail("%s: null pointer", what);
+        if (!out_f32 && !out_i16) return fail("%s: no output (out_f32 and out_i16 are both null)", what);
+        for (int u = 0; u < n_utt; ++u) {
+            if (lengths[u] < 0) return fail("%s: utterance %d has length %ld", what, u, lengths[u]);
+            if (lengths[u] > 0 && (!in[u] || (out_f32 && !out_f32[u]) || (out_i16 && !out_i16[u])))
+                return fail("%s: utterance %d has a null buffer", what, u);
+        }
+        DeviceCtx *dc;
+        if (ctx(&dc)) return 1;
+        n_cu = dc->n_cu;
+        long long budget = 0;
+        if (budget_bytes(&budget)) return 1;
+        cuts = plan(lengths, n_utt, budget, resynth_only);
+        for (size_t k = 0; k + 1 < cuts.size(); ++k) {
+            long long cs = 0, cr = 0;
+            for (int u = cuts[k]; u < cuts[k + 1]; ++u) cs += align8(lengths[u]), cr += rows_of(lengths[u]);
+            const int cn = cuts[k + 1] - cuts[k];
+            max_s = std::max(max_s, cs);
+            max_r = std::max(max_r, cr);
+            max_n = std::max(max_n, cn);
+            max_work = std::max(max_work, chunk_bytes(cs, cr, cn, resynth_only) - (10 * cs + 260 * cr + 32LL * cn));
+        }
+        HIP_TRY(d_in.alloc((size_t)max_s));
+        if (out_f32) HIP_TRY(d_out.alloc((size_t)max_s));
+        if (out_i16) HIP_TRY(d_out16.alloc((size_t)max_s));
+        HIP_TRY(d_mask.alloc((size_t)(max_r + 1) * kCh));
+        HIP_TRY(d_meta.alloc(3 * (size_t)max_n));
+        HIP_TRY(d_order.alloc((size_t)max_n));
+        h_f32.resize((size_t)max_s);
+        if (out_i16) h_i16.resize((size_t)max_s);
+        h_mask.resize((size_t)(max_r + 1) * kCh);
+        h_meta.resize(3 * (size_t)max_n);
+        h_order.resize((size_t)max_n);
+        return 0;
+    }
+
+    int chunks() const { return (int)cuts.size() - 1; }
+
+    int upload(int k)
+    {
+        u0 = cuts[k];
+        n = cuts[k + 1] - u0;
+        long long *o = h_meta.data(), *l = o + n, *ro = l + n;
+        s = r = 0;
+        for (int j = 0; j < n; ++j) {
+            const long L = lengths[u0 + j];
+            o[j] = s;
+            l[j] = L;
+            ro[j] = r;
+            if (L > 0) memcpy(h_f32.data() + s, in[u0 + j], (size_t)L * sizeof(float));
+            std::fill(h_f32.begin() + s + L, h_f32.begin() + s + align8(L), 0.0f);
+            s += align8(L);
+            r += rows_of(L);
+        }
+        launch_order(l, n, n_cu, h_order.data());
+        if (s > 0) HIP_TRY(hipMemcpy(d_in.p, h_f32.data(), (size_t)s * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_meta.p, h_meta.data(), 3 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_order.p, h_order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        offs = d_meta.p;
+        lens = d_meta.p + n;
+        roff = d_meta.p + 2 * n;
+        return 0;
+    }
+
+    int audio_back(float *const *out_f32, short *const *out_i16)
+    {
+        const long long *o = h_meta.data(), *l = o + n;
+        if (out_f32 && s > 0) {
+            HIP_TRY(hipMemcpy(h_f32.data(), d_out.p, (size_t)s * sizeof(float), hipMemcpyDeviceToHost));
+            for (int j = 0; j < n; ++j)
+                if (l[j] > 0) memcpy(out_f32[u0 + j], h_f32.data() + o[j], (size_t)l[j] * sizeof(float));
+        }
+        if (out_i16 && s > 0) {
+            HIP_TRY(hipMemcpy(h_i16.data(), d_out16.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost));
+            for (int j = 0; j < n; ++j)
+                if (l[j] > 0) memcpy(out_i16[u0 + j], h_i16.data() + o[j], (size_t)l[j] * sizeof(short));
+        }
+        return 0;
+    }
+};
+
+/* periphery with gOut, then the resynthesis of the callers' masks: one launch group per chunk */
+int resynth_list(const float *const *in, const long *lengths, const float *const *masks, float threshold, float *const *out_f32,
+                 short *const *out_i16, int n_utt, int *chunks)
+{
+    const char *what = "hw64_resynth_utterances";
+    List q;
+    if (q.setup(what, in, lengths, n_utt, out_f32, out_i16, 1)) return 1;
+    for (int u = 0; u < n_utt; ++u)
+        if (rows_of(lengths[u]) > 0 && (!masks || !masks[u])) return fail("%s: utterance %d has no mask", what, u);
+    const size_t plane = (size_t)q.max_s * kCh;
+    DevBuf<float> d_planes; /* hout | hev | gout */
+    HIP_TRY(d_planes.alloc(3 * plane));
+    LaunchTimer timer;
+    if (timer.create()) return 1;
+    for (int k = 0; k < q.chunks(); ++k) {
+        if (q.upload(k)) return 1;
+        if (q.s > 0) {
+            const long long *ro = q.h_meta.data() + 2 * q.n;
+            for (int j = 0; j < q.n; ++j) {
+                const size_t units = (size_t)rows_of(lengths[q.u0 + j]) * kCh;
+                if (units) memcpy(q.h_mask.data() + ro[j] * kCh, masks[q.u0 + j], units * sizeof(float));
+            }
+            if (q.r > 0) HIP_TRY(hipMemcpy(q.d_mask.p, q.h_mask.data(), (size_t)q.r * kCh * sizeof(float), hipMemcpyHostToDevice));
+            float *gout = d_planes.p + 2 * plane;
+            if (sea_hw64_periphery_batch(q.d_in.p, d_planes.p, d_planes.p + plane, gout, q.offs, q.lens, q.d_order.p, q.n, nullptr))
+                return 1;
+            HIP_TRY(hipEventRecord(timer.before, nullptr));
+            if (hw64_resynth_launch(gout, q.d_mask.p, q.offs, q.lens, q.roff, threshold, q.d_out.p, q.d_out16.p, q.d_order.p, q.n, nullptr))
+                return 1;
+            HIP_TRY(hipEventRecord(timer.after, nullptr));
+            HIP_TRY(hipDeviceSynchronize());
+            if (timer.add_ms(&t_last_resynth_ms)) return 1;
+            if (q.audio_back(out_f32, out_i16)) return 1;
+        }
+        *chunks = k + 1;
+    }
+    return 0;
+}
+
+/* sea_hw64_ibm_batch, then the resynthesis of its own mask from the gOut it keeps in its scratch: one launch group per chunk */
+int enhance_list(const float *const *in, const long *lengths, int n_utt, float *const *out_f32, short *const *out_i16,
+                 float *const *masks, int *const *pitch, int *status, int *chunks)
+{
+    const char *what = "hw64_enhance_utterances";
+    if (!status) return fail("%s: null pointer", what);
+    List q;
+    if (q.setup(what, in, lengths, n_utt, out_f32, out_i16, 0)) return 1;
+    DevBuf<int> d_int; /* pitch | status */
+    DevBuf<char> d_scr;
+    HIP_TRY(d_int.alloc((size_t)(q.max_r + 1) + (size_t)q.max_n));
+    HIP_TRY(d_scr.alloc((size_t)q.max_work));
+    std::vector<int> h_int((size_t)(q.max_r + 1) + (size_t)q.max_n);
+    int *d_pitch = d_int.p, *d_status = d_int.p + q.max_r + 1;
+    LaunchTimer timer;
+    if (timer.create()) return 1;
+    for (int k = 0; k < q.chunks(); ++k) {
+        if (q.upload(k)) return 1;
+        if (q.s == 0) { /* no sample in the whole chunk: nothing to compute */
+            for (int j = 0; j < q.n; ++j) status[q.u0 + j] = 0;
+            *chunks = k + 1;
+            continue;
+        }
+        if (hw64_enhance_launch(q.d_in.p, q.offs, q.lens, q.roff, q.d_out.p, q.d_out16.p, q.d_mask.p, d_pitch, d_status, d_scr.p, q.s, q.r,
+                                q.d_order.p, q.n, nullptr, timer.before, timer.after))
+            return 1;
+        HIP_TRY(hipDeviceSynchronize());
+        if (timer.add_ms(&t_last_resynth_ms)) return 1;
+        HIP_TRY(hipMemcpy(status + q.u0, d_status, (size_t)q.n * sizeof(int), hipMemcpyDeviceToHost));
+        if (q.audio_back(out_f32, out_i16)) return 1;
+        const long long *ro = q.h_meta.data() + 2 * q.n;
+        if (masks && q.r > 0) {
+            HIP_TRY(hipMemcpy(q.h_mask.data(), q.d_mask.p, (size_t)q.r * kCh * sizeof(float), hipMemcpyDeviceToHost));
+            for (int j = 0; j < q.n; ++j) {
+                const size_t units = (size_t)rows_of(lengths[q.u0 + j]) * kCh;
+                if (units && masks[q.u0 + j]) memcpy(masks[q.u0 + j], q.h_mask.data() + ro[j] * kCh, units * sizeof(float));
+            }
+        }
+        if (pitch && q.r > 0) {
+            HIP_TRY(hipMemcpy(h_int.data(), d_pitch, (size_t)q.r * sizeof(int), hipMemcpyDeviceToHost));
+            for (int j = 0; j < q.n; ++j) {
+                const size_t rows = (size_t)rows_of(lengths[q.u0 + j]);
+                if (rows && pitch[q.u0 + j]) memcpy(pitch[q.u0 + j], h_int.data() + ro[j], rows * sizeof(int));
+            }
+        }
+        *chunks = k + 1;
+    }
+    return 0;
+}
+
+} // namespace
+
+int sea_capi::hw64_resynth_launch(const float *d_gout, const float *d_mask, const long long *d_offsets, const long long *d_lengths,
+                                  const long long *d_row_offsets, float threshold, float *d_out_f32, short *d_out_i16,
+                                  const int *d_order, int n_utt, hipStream_t stream)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_gout || !d_mask || !d_offsets || !d_lengths || !d_row_offsets) return fail("hw64_resynth: null pointer (only d_order and one output may be null)");
+    if (!d_out_f32 && !d_out_i16) return fail("hw64_resynth: no output (d_out_f32 and d_out_i16 are both null)");
+    const void *outs[] = {d_out_f32, d_out_i16};
+    if (shared_buffer(outs, 2, {d_gout, d_mask}))
+        return fail("hw64_resynth: an output must not be an input or the other output");
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    sea::Hw64ResynthArgs a{};
+    a.gout = d_gout;
+    a.mask = d_mask;
+    a.offsets = d_offsets;
+    a.lengths = d_lengths;
+    a.row_offsets = d_row_offsets;
+    a.out_f32 = d_out_f32;
+    a.out_i16 = d_out_i16;
+    a.order = d_order;
+    a.tables = c->hw64;
+    a.threshold = threshold;
+    a.n_utt = n_utt;
+    hipLaunchKernelGGL(sea::hw64_resynth_kernel, dim3(n_utt), dim3(64), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int sea_capi::hw64_enhance_launch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths,
+                                  const long long *d_row_offsets, float *d_out_f32, short *d_out_i16, float *d_mask, int *d_pitch,
+                                  int *d_status, void *d_scratch, long long total_padded_samples, long long total_rows,
+                                  const int *d_order, int n_utt, hipStream_t stream, hipEvent_t before_resynth, hipEvent_t after_resynth)
+{
+    if (n_utt <= 0) return 0;
+    if (!d_out_f32 && !d_out_i16) return fail("hw64_enhance: no output (d_out_f32 and d_out_i16 are both null)");
+    const void *outs[] = {d_out_f32, d_out_i16};
+    if (shared_buffer(outs, 2, {d_in_f32, d_mask, d_pitch, d_status, d_scratch}))
+        return fail("hw64_enhance: an output must not be the input or another output");
+    /* the mask of createIBM :99-106 is 0 / 1: the reference's `mark > 0` */
+    if (sea_hw64_ibm_batch(d_in_f32, d_offsets, d_lengths, d_row_offsets, d_mask, d_pitch, d_status, nullptr, d_scratch,
+                           total_padded_samples, total_rows, d_order, n_utt, stream))
+        return 1;
+    const float *gout = reinterpret_cast<const float *>(static_cast<const char *>(d_scratch) +
+                                                        hw64_ibm_gout_offset(total_padded_samples, total_rows, n_utt));
+    if (before_resynth) HIP_TRY(hipEventRecord(before_resynth, stream));
+    if (hw64_resynth_launch(gout, d_mask, d_offsets, d_lengths, d_row_offsets, 0.0f, d_out_f32, d_out_i16, d_order, n_utt, stream)) return 1;
+    if (after_resynth) HIP_TRY(hipEventRecord(after_resynth, stream));
+    return 0;
+}
+
+int sea_hw64_resynth_tables_host(float *w640, double *up160, double *down160)
+{
+    sea_hw64_ola_tables(w640, up160, down160);
+    return 0;
+}
+
+int sea_hw64_enhance_plan(const long *lengths, int n_utt, long long budget_bytes, int resynth_only, int *cuts)
+{
+    if (n_utt <= 0) return 0;
+    if (!lengths) return fail("hw64_enhance_plan: null pointer"), -1;
+    for (int u = 0; u < n_utt; ++u)
+        if (lengths[u] < 0) return fail("hw64_enhance_plan: utterance %d has length %ld", u, lengths[u]), -1;
+    const std::vector<int> c = plan(lengths, n_utt, budget_bytes, resynth_only);
+    if (cuts) std::copy(c.begin(), c.end(), cuts);
+    return (int)c.size() - 1;
+}
+
+int sea_hw64_enhance_last_chunks(void) { return t_last_chunks; }
+
+double sea_hw64_enhance_last_resynth_ms(void) { return t_last_resynth_ms; }
+
+int sea_hw64_resynth_utterances(const float *const *in, const long *lengths, const float *const *masks, float threshold,
+                                float *const *out_f32, short *const *out_i16, int n_utt)
+{
+    t_last_chunks = 0;
+    t_last_resynth_ms = 0.0;
+    if (n_utt <= 0) return 0;
+    return resynth_list(in, lengths, masks, threshold, out_f32, out_i16, n_utt, &t_last_chunks);
+}
+
+int sea_hw64_enhance_utterances(const float *const *in, const long *lengths, int n_utt, float *const *out_f32, short *const *out_i16,
+                                float *const *masks, int *const *pitch, int *status)
+{
+    t_last_chunks = 0;
+    t_last_resynth_ms = 0.0;
+    if (n_utt <= 0) return 0;
+    return enhance_list(in, lengths, n_utt, out_f32, out_i16, masks, pitch, status, &t_last_chunks);
+}
+
+int sea_hw64_resynth(const float *x, long L, const float *mask, long F, float threshold, float *out_f32)
+{
+    if (L < 0) return fail("hw64_resynth: L=%ld", L);
+    if (L == 0) return 0;
+    if (!x || !out_f32) return fail("hw64_resynth: null pointer");
+    if (F != (long)sea_hw64_frames(L)) return fail("hw64_resynth: F=%ld, not L / 160 = %lld", F, sea_hw64_frames(L));
+    if (F > 0 && !mask) return fail("hw64_resynth: null pointer");
+    int chunks = 0;
+    return resynth_list(&x, &L, &mask, threshold, &out_f32, nullptr, 1, &chunks);
+}
+
+int sea_hw64_enhance(const float *x, long L, float *out_f32, float *mask, int *pitch, int *status)
+{
+    if (L < 0) return fail("hw64_enhance: L=%ld", L);
+    if (!status || (L > 0 && (!x || !out_f32))) return fail("hw64_enhance: null pointer");
+    if (L == 0) { /* no sample: nothing to compute */
+        *status = 0;
+        return 0;
+    }
+    int chunks = 0;
+    return enhance_list(&x, &L, 1, &out_f32, nullptr, mask ? &mask : nullptr, pitch ? &pitch : nullptr, status, &chunks);
+}

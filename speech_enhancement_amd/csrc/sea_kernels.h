@@ -519,6 +519,23 @@ struct Hw25ResynthArgs {
 };
 __global__ void hw25_resynth_kernel(Hw25ResynthArgs a); /* grid n_utt x 64 */
 
+/* The same at 16 kHz on the 64-channel bank (hw64_resynth_kernel.hip).  Hw25ResynthArgs's fields with the 64-band tables: gout
+ * in hw64_periphery_kernel's layout, only read; mask [rows][64], utterance u's lengths[u] / 160 rows from row_offsets[u]. */
+struct Hw64ResynthArgs {
+    const float *gout;
+    const float *mask;
+    const long long *offsets;
+    const long long *lengths;
+    const long long *row_offsets;
+    float *out_f32;
+    short *out_i16;
+    const int *order;
+    const sea_hw64_tables *tables;
+    float threshold;
+    int n_utt;
+};
+__global__ void hw64_resynth_kernel(Hw64ResynthArgs a); /* grid n_utt x 64 */
+
 __global__ void subband_kernel(SubbandArgs a);
 __global__ void ns_denoise_pipe_kernel(NsBatchArgs a);
 __global__ void ns_denoise_pipe_big_kernel(NsBatchArgs a); /* lower-register form for > 4 utterances per CU */

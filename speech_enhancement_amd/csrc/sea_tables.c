@@ -759,6 +759,27 @@ void sea_build_hw64_tables(sea_hw64_tables *t)
     memset(t, 0, sizeof *t);
     hw_build_bank(16000, 50, 8000, SEA_HW64_NCHAN, SEA_HW64_WINDOW, SEA_HW64_MAXWIN, SEA_HW64_TAPS, t->cf, t->bw, t->midEar, t->gain,
                   t->f1, t->f2, t->winsize, t->lp, &t->ymdt, NULL);
+    sea_hw64_ola_tables(t->olaW, NULL, NULL);
+}
+
+void sea_hw64_ola_tables(float *w640, double *up160, double *down160)
+{ /* resynthesis:1521-1536 at OFFSET 160, WINDOW 320 */
+    const double kPiHW = 3.1415926535897932384626433832795;
+    double up[SEA_HW64_HOP], down[SEA_HW64_WINDOW - SEA_HW64_HOP];
+    long n;
+    int o, bits;
+    for (n = 0; n < SEA_HW64_HOP; n++) up[n] = 0.5 * (1.0 + cos(n * kPiHW / (SEA_HW64_HOP) + kPiHW));
+    for (n = SEA_HW64_HOP; n < SEA_HW64_WINDOW; n++) down[n - SEA_HW64_HOP] = 0.5 * (1.0 + cos((n - SEA_HW64_HOP) * kPiHW / (SEA_HW64_HOP)));
+    if (up160) memcpy(up160, up, sizeof up);
+    if (down160) memcpy(down160, down, sizeof down);
+    if (!w640) return;
+    for (o = 0; o < SEA_HW64_HOP; o++)
+        for (bits = 0; bits < 4; bits++) { /* the frames in ascending order, each `weight[..] += double` rounded to float */
+            float w = 0.0;
+            if (bits & 1) w += down[o];
+            if (bits & 2) w += up[o];
+            w640[o * 4 + bits] = w;
+        }
 }
 
 void sea_hw64_plain_tables(float *cf64, float *bw64, float *midEar64, float *gain64, float *f1_64, float *f2_64, int *winsize64,

@@ -285,8 +285,9 @@ enum {
     SEA_HW64_HOP = 160,     /* OFFSET = 16000 / 100 */
     SEA_HW64_TAPS = 181,    /* fLength + 1, fLength = 180 from kaiserPara (0.01, 200 / 16000.) */
     SEA_HW64_MAXWIN = 1280, /* the widest window: channel 0, int (4 * 16000 / cf), cf = 50 */
-    SEA_HW64_AM_MAXTAPS = 1120 /* amPatt's fLength + 1 is at most 1119 (mp = 200; 5.59 mp): kaiserPara's float arithmetic at the
-                                * largest mean of five pitches in 32..200 */
+    SEA_HW64_AM_MAXTAPS = 1120, /* amPatt's fLength + 1 is at most 1119 (mp = 200; 5.59 mp): kaiserPara's float arithmetic at the
+                                 * largest mean of five pitches in 32..200 */
+    SEA_HW64_OLA_WEIGHTS = 640  /* resynthesis: 160 positions in a hop x 4 states of the two frames that reach it */
 };
 typedef struct {
     float cf[SEA_HW64_NCHAN], bw[SEA_HW64_NCHAN], midEar[SEA_HW64_NCHAN];
@@ -295,8 +296,17 @@ typedef struct {
     float lp[184];                                 /* the 181 taps of kaiserLowPass */
     float ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt; /* hairCell:261-268 at dt = 1 / 16000 */
     float q0, c0, w0;                              /* its initial state, :271-274 */
+    float olaW[SEA_HW64_OLA_WEIGHTS];              /* resynthesis:1521-1536, sea_hw64_ola_tables's w640 */
 } sea_hw64_tables;
 void sea_build_hw64_tables(sea_hw64_tables *t);
+/* resynthesis:1521-1536 at WINDOW = 320 = 2 OFFSET, the overlap-add weight of one channel at a sample 160 k + o.  up160[n] =
+ * 0.5 (1 + cos (n pi / 160 + pi)) is the rising half of a set frame (:1530, on the 160 samples before the frame's own, not for
+ * frame 0), down160[n] = 0.5 (1 + cos (n pi / 160)) its falling half (:1534, on the frame's own 160 samples): the window ends
+ * where the next hop begins, so, unlike sea_hw25_ola_tables, nothing rises again and nothing reaches a third hop.  The sample
+ * receives, in the order of the frame loop, down160[o] from frame k and up160[o] from frame k + 1, each a double added to the
+ * float weight and rounded to float.  w640[o * 4 + bits] is the result, bit 0 / 1 of `bits`: frame k / k + 1 exists and is
+ * set.  Every pointer may be null. */
+void sea_hw64_ola_tables(float *w640, double *up160, double *down160);
 /* plain tables for host-side checks; hair10 as in sea_hw25_plain_tables */
 void sea_hw64_plain_tables(float *cf64, float *bw64, float *midEar64, float *gain64, float *f1_64, float *f2_64, int *winsize64,
                            float *lp181, float *hair10);

@@ -9,14 +9,22 @@ two loops by the literal 40; on this bank that keeps channels 40..63 out of thei
 array there instead, which is why only its call takes one).
 
 Then createIBM():89-106, computeAM, finalSeg and the binarisation (csrc/hw64_am_kernel.hip): hw64_am_batch, hw64_finalseg_batch
-and the whole estimator, hw64_ibm_batch / hw64_ibm, the binary mask [frames][64] from 16 kHz audio.  Of the reference's chain
-only resynthesis() is not built at 16 kHz.
+and the whole estimator, hw64_ibm_batch / hw64_ibm, the binary mask [frames][64] from 16 kHz audio.
+
+Then resynthesis() (HuWang.cpp:1498-1549; csrc/hw64_resynth_kernel.hip), which closes the chain at this bank: hw64_resynth and
+hw64_enhance for one utterance from host memory, hw64_resynth_utterances and hw64_enhance_utterances for lists of utterances,
+cut into chunks that fit HBM (hw64_enhance_plan shows the cut).  These take host arrays only: the forms on a PackedBatch
+(hw64_resynth_batch, hw64_enhance_batch) wait for the exported device-pointer calls they would bind.
 
 torch is used for device memory and streams only (plumbing); all compute is in the HIP library.
 """
+import ctypes
 from types import SimpleNamespace
 
+import numpy as np
+
 from . import _lib
+from .engine import _np_ptr
 from .hw25 import (Hw25AmResult, Hw25MaskResult, Hw25PitchResult, Hw25Result, _bank_am, _bank_finalseg, _bank_front,
                    _bank_frontend_host, _bank_ibm, _bank_periphery, _bank_pitch, _bank_split, _bank_tables, _hw25_host)
 
@@ -140,3 +148,93 @@ def hw64_ibm(x):
     """createIBM (x) for one utterance from host memory (float32 or int16 samples on the int16 scale, 16 kHz) -> dict: mask
     [F][64] floats 0 / 1, pitch int32 [F], status; F = len(x) // 160."""
     return _hw25_host("sea_hw64_ibm", x, ("mask", "pitch"), bank=_BANK64)
+
+
+# ------------------------------------------------------------------------------------------------
+# the estimator's resynthesis at 16 kHz (HuWang.cpp:1498-1549; csrc/hw64_resynth_kernel.hip): the mask applied, audio out
+# ------------------------------------------------------------------------------------------------
+def hw64_resynth_tables():
+    """The overlap-add tables of resynthesis() at WINDOW = 320 = 2 x 160: up float64 [160], down float64 [160] and w float32
+    [160][4], the weight at position o of a hop for the four states (bit 0 / 1: frame k / k + 1 exists and is set)."""
+    lib = _lib.load()
+    w, up, down = np.zeros((160, 4), np.float32), np.zeros(160, np.float64), np.zeros(160, np.float64)
+    _lib.check(lib.sea_hw64_resynth_tables_host(_np_ptr(w), _np_ptr(up), _np_ptr(down)), "sea_hw64_resynth_tables_host")
+    return dict(w=w, up=up, down=down)
+
+
+def hw64_resynth(x, mask, threshold=0.0):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale, 16 kHz) and its mask [len(x) // 160][64]
+    (a unit is set where mask > threshold) -> the resynthesised float32 audio [len(x)]."""
+    mask = np.ascontiguousarray(mask, dtype=np.float32).reshape(-1, HW64_NCHAN)
+    return _hw25_host("sea_hw64_resynth", x, ("audio",), _np_ptr(mask), mask.shape[0], float(threshold), status=False,
+                      bank=_BANK64)["audio"]
+
+
+def hw64_enhance(x):
+    """One utterance from host memory (float32 or int16 samples on the int16 scale, 16 kHz) -> dict: audio float32 [L], the
+    enhanced signal; mask [F][64] floats 0 / 1, pitch int32 [F], status, as hw64_ibm() gives them; F = len(x) // 160."""
+    return _hw25_host("sea_hw64_enhance", x, ("audio", "mask", "pitch"), bank=_BANK64)
+
+
+def _ptr_array(arrays):
+    return (ctypes.c_void_p * max(len(arrays), 1))(*[a.ctypes.data for a in arrays]) if arrays is not None else None
+
+
+def _host_list(xs):
+    xs = [np.ascontiguousarray(x, dtype=np.float32).reshape(-1) for x in xs]
+    return xs, (ctypes.c_long * max(len(xs), 1))(*[x.size for x in xs])
+
+
+def hw64_resynth_utterances(xs, masks, threshold=0.0, int16=False):
+    """resynthesis() for a list of utterances in host memory (float32 or int16 samples on the int16 scale, 16 kHz) with their
+    masks [len(x) // 160][64] -> dict: audio, the list of float32 arrays; int16=True: also shorts, their int16 conversion as
+    the x86-64 build performs it; chunks, how many launch groups the list was cut into to fit HBM."""
+    lib = _lib.load()
+    xs, lens = _host_list(xs)
+    masks = [np.ascontiguousarray(m, dtype=np.float32).reshape(-1, HW64_NCHAN) for m in masks]
+    if len(masks) != len(xs) or any(m.shape[0] != x.size // HW64_HOP for x, m in zip(xs, masks)):
+        raise ValueError("hw64_resynth_utterances: one mask [len(x) // 160][64] per utterance")
+    audio = [np.zeros(x.size, np.float32) for x in xs]
+    shorts = [np.zeros(x.size, np.int16) for x in xs] if int16 else None
+    rc = lib.sea_hw64_resynth_utterances(_ptr_array(xs), lens, _ptr_array(masks), float(threshold), _ptr_array(audio),
+                                         _ptr_array(shorts), len(xs))
+    _lib.check(rc, "sea_hw64_resynth_utterances")
+    out = dict(audio=audio, chunks=int(lib.sea_hw64_enhance_last_chunks()))
+    if int16:
+        out["shorts"] = shorts
+    return out
+
+
+def hw64_enhance_utterances(xs, int16=False):
+    """createIBM() followed by resynthesis() of its own mask for a list of utterances in host memory (float32 or int16 samples
+    on the int16 scale, 16 kHz) -> dict of lists: audio float32 [L], mask [F][64] floats 0 / 1, pitch int32 [F] (F = L // 160),
+    status, as hw64_ibm() gives them; int16=True: also shorts; and chunks, how many launch groups the list was cut into to fit
+    HBM (the estimator's scratch is about 200 MB per four-second utterance)."""
+    lib = _lib.load()
+    xs, lens = _host_list(xs)
+    n = len(xs)
+    audio = [np.zeros(x.size, np.float32) for x in xs]
+    shorts = [np.zeros(x.size, np.int16) for x in xs] if int16 else None
+    masks = [np.zeros((x.size // HW64_HOP, HW64_NCHAN), np.float32) for x in xs]
+    pitch = [np.zeros(x.size // HW64_HOP, np.int32) for x in xs]
+    status = np.zeros(max(n, 1), np.int32)
+    rc = lib.sea_hw64_enhance_utterances(_ptr_array(xs), lens, n, _ptr_array(audio), _ptr_array(shorts), _ptr_array(masks),
+                                         _ptr_array(pitch), _np_ptr(status))
+    _lib.check(rc, "sea_hw64_enhance_utterances")
+    out = dict(audio=audio, mask=masks, pitch=pitch, status=[int(v) for v in status[:n]], chunks=int(lib.sea_hw64_enhance_last_chunks()))
+    if int16:
+        out["shorts"] = shorts
+    return out
+
+
+def hw64_enhance_plan(lengths, budget_bytes, resynth_only=False):
+    """How hw64_enhance_utterances (resynth_only: hw64_resynth_utterances) cuts a list of these lengths for a budget in bytes:
+    the first utterance of every chunk, then len(lengths) -- int32 [chunks + 1].  Touches no device."""
+    lib = _lib.load()
+    n = len(lengths)
+    lens = (ctypes.c_long * max(n, 1))(*[int(v) for v in lengths])
+    cuts = np.zeros(n + 1, np.int32)
+    k = int(lib.sea_hw64_enhance_plan(lens, n, int(budget_bytes), int(bool(resynth_only)), _np_ptr(cuts)))
+    if k < 0:
+        _lib.check(1, "sea_hw64_enhance_plan")
+    return cuts[:k + 1].copy()

@@ -18,6 +18,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw25ibm --steps 3  # its AM stage, final grouping and the whole estimator beside the other stages, opt-in
     python tools/bench_extra.py --what hw64ibm --steps 3  # the same at 16 kHz on the 64-channel bank; also writes profiles/hw64ibm_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
+    python tools/bench_extra.py --what hw64resynth --steps 3  # the same at 16 kHz on the 64-channel bank, through the host-list forms; also writes profiles/hw64resynth_bench_extra.jsonl, opt-in
 """
 import argparse
 import json
@@ -1527,6 +1528,107 @@ def main():
                           "config": {"workload": workload}, "mask_units": int(mask.sum().item()),
                           "nonzero_output_samples": int((audio != 0).sum().item())}), flush=True)
         del hout, hev, gout, scr_ibm
+
+    if "hw64resynth" in what:
+        # The Hu-Wang resynthesis at 16 kHz on the 64-channel bank, on the --utts corpus batch taken as 16 kHz float samples, in
+        # one process.  Through the exported device-pointer calls, device events around every step: the periphery with gOut and
+        # sea_hw64_ibm_batch.  The resynthesis has no exported device-pointer call: it is reached through the host-list forms,
+        # which time their own resynthesis launches with a pair of device events (sea_hw64_enhance_last_resynth_ms): that is
+        # "the resynthesis alone"; the host calls' wall time (upload, launch group, download) is given beside it.  One warm-up
+        # discarded, median of --steps.  The launch group's audio and mask are checked against the single stages, bit for bit.
+        # The lines also go to profiles/hw64resynth_bench_extra.jsonl.
+        import ctypes
+        lib = sea.load()
+        n = batch.n_utt
+        x = batch.data.to(torch.float32)
+        lengths = np.asarray(batch.host_lengths, dtype=np.int64)
+        rows = lengths // 160
+        offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+        frames, total, samples = int(rows.sum()), int(batch.total), int(lengths.sum())
+        d_offs = torch.from_numpy(offs).to(dev)
+        z = lambda shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
+        hout, hev, gout = z(total * 64), z(total * 64), z(total * 64)
+        mask, pitch, status = z((frames, 64)), z(frames, torch.int32), z(n, torch.int32)
+        scr_ibm = torch.empty(int(lib.sea_hw64_ibm_scratch_bytes(total, frames, n)), dtype=torch.uint8, device=dev)
+        P = lambda t: t.data_ptr() if t is not None else None
+        st = torch.cuda.current_stream().cuda_stream
+
+        def periphery():
+            assert lib.sea_hw64_periphery_batch(P(x), P(hout), P(hev), P(gout), P(batch.offsets), P(batch.lengths), P(batch.order), n, st) == 0, lib.sea_last_error()
+
+        def ibm():
+            assert lib.sea_hw64_ibm_batch(P(x), P(batch.offsets), P(batch.lengths), P(d_offs), P(mask), P(pitch), P(status), None, P(scr_ibm),
+                                          total, frames, P(batch.order), n, st) == 0, lib.sea_last_error()
+        workload = (f"the {args.utts}-utterance corpus as 16 kHz float samples: {samples} samples, {frames} frames of 160; median of "
+                    f"{args.steps} steps after one warm-up")
+        lines, results = [], {}
+
+        def emit(record):
+            lines.append(json.dumps(record))
+            print(lines[-1], flush=True)
+
+        def line(key, name, med, t, kernels, **more):
+            results[key] = med
+            emit({"metric": f"Hu-Wang 64-channel 16 kHz resynthesis: {name} (samples/sec); a first form, not tuned",
+                  "value": samples / (med / 1e3), "unit": "samples/s", "ms_per_step": med, "x_realtime_16k": samples / 16000.0 / (med / 1e3),
+                  "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "kernels": kernels, **more})
+
+        for key, name, fn, kernels in (("periphery", "periphery with gOut, device events", periphery, "sea::hw64_periphery_kernel + sea::hw64_lowpass_kernel"),
+                                       ("ibm", "the whole estimator, sea_hw64_ibm_batch, device events", ibm, "every kernel of the estimator")):
+            med, t = median_ms(fn, args.steps)
+            line(key, name, med, t, kernels)
+        torch.cuda.synchronize()
+        host = x.cpu().numpy()
+        xs = [np.ascontiguousarray(host[int(o):int(o) + int(L)]) for o, L in zip(batch.host_offsets, lengths)]
+        mask_h, pitch_h = mask.cpu().numpy(), pitch.cpu().numpy()
+        masks = [np.ascontiguousarray(mask_h[int(o):int(o) + int(r)]) for o, r in zip(offs, rows)]
+        del hout, hev, gout, scr_ibm
+        torch.cuda.empty_cache()
+        ptrs = lambda arrs: (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs]) if arrs is not None else None
+        lens = (ctypes.c_long * n)(*[int(L) for L in lengths])
+        audio = [np.zeros(int(L), np.float32) for L in lengths]
+        audio2 = [np.zeros(int(L), np.float32) for L in lengths]
+        shorts = [np.zeros(int(L), np.int16) for L in lengths]
+        masks2 = [np.zeros((int(r), 64), np.float32) for r in rows]
+        pitch2 = [np.zeros(int(r), np.int32) for r in rows]
+        status2 = np.zeros(n, np.int32)
+
+        def host_call(fn):
+            """one warm-up, then --steps calls -> (the launches' device time, the calls' wall time, chunks), medians in ms"""
+            dev_ms, wall_ms = [], []
+            for i in range(args.steps + 1):
+                t0 = time.perf_counter()
+                assert fn() == 0, lib.sea_last_error()
+                if i:
+                    wall_ms.append((time.perf_counter() - t0) * 1e3)
+                    dev_ms.append(float(lib.sea_hw64_enhance_last_resynth_ms()))
+            return sorted(dev_ms), sorted(wall_ms), int(lib.sea_hw64_enhance_last_chunks())
+
+        def resynth_call(i16):
+            return lambda: lib.sea_hw64_resynth_utterances(ptrs(xs), lens, ptrs(masks), 0.0, ptrs(audio), ptrs(shorts) if i16 else None, n)
+
+        def enhance_call():
+            return lib.sea_hw64_enhance_utterances(ptrs(xs), lens, n, ptrs(audio2), None, ptrs(masks2), ptrs(pitch2),
+                                                   status2.ctypes.data_as(ctypes.c_void_p))
+        for key, name, fn in (("resynth", "resynthesis alone, float output", resynth_call(False)),
+                              ("resynth_i16", "resynthesis alone, float and int16 outputs", resynth_call(True))):
+            d, w, chunks = host_call(fn)
+            line(key, name + ": the launches inside sea_hw64_resynth_utterances, device events", d[len(d) // 2], d, "sea::hw64_resynth_kernel",
+                 host_call_wall_ms=w[len(w) // 2], host_call_wall_ms_sorted=[round(v, 1) for v in w], chunks=chunks)
+        d, w, chunks = host_call(enhance_call)
+        line("enhance", "audio in, enhanced audio out, sea_hw64_enhance_utterances end to end from host memory, wall time", w[len(w) // 2], w,
+             "every kernel of the estimator + sea::hw64_resynth_kernel, with the upload and the download", chunks=chunks,
+             resynth_launch_ms=d[len(d) // 2])
+        same_audio = all(a.tobytes() == b.tobytes() for a, b in zip(audio, audio2))
+        same_mask = all(np.array_equal(a, b) for a, b in zip(masks, masks2)) and np.array_equal(np.concatenate(pitch2), pitch_h)
+        assert same_audio and same_mask, "the launch group and the single stages differ"
+        emit({"metric": "Hu-Wang 64-channel 16 kHz resynthesis relative to the periphery and to the estimator of the same run",
+              "value": results["resynth"] / results["periphery"], "unit": "ratio (resynthesis / periphery with gOut)",
+              "resynth_over_ibm": results["resynth"] / results["ibm"], "enhance_host_call_over_ibm": results["enhance"] / results["ibm"],
+              "config": {"workload": workload}, "chunks": chunks, "audio_and_mask_equal_the_single_stages": True,
+              "mask_units": int(mask_h.sum()), "nonzero_output_samples": int(sum(int((a != 0).sum()) for a in audio))})
+        with open(os.path.join(ROOT, "profiles", "hw64resynth_bench_extra.jsonl"), "w") as fh:
+            fh.write("\n".join(lines) + "\n")
 
     if "rfft" in what:
         n = 1 << 18
