@@ -824,14 +824,17 @@ __device__ __forceinline__ void psd_from_last_level(const float (&o)[8], const F
     const float Pc = o[4] * o[4] + ic * ic; /* bin 63 - s | 32 */
     const float Pd = o[5] * o[5] + id * id; /* bin 127 - s | 96 */
     const float Pe = o[2] * o[2];           /* slot 31: bin 128 */
+    /* Both moves write every lane (row and bank masks full) and take a lane without a source -- lane 0 of wave_shr:1 only -- as
+     * zero (bound_ctrl), so neither needs a previous value in its destination; the two wrap lanes are then written with the
+     * values read from lanes 31 and 63 (v_writelane), which is what the two selects on the lane index gave. */
     auto below = [&](float v) { /* the same value of slot s - 1, slot 0: of slot 31 */
-        const float sh = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, false));
-        const float l31 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 31));
-        const float l63 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-        return lane == 0 ? l31 : (lane == 32 ? l63 : sh);
+        int sh = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138 /* wave_shr:1 */, 0xf, 0xf, true);
+        const int l31 = __builtin_amdgcn_readlane(__float_as_int(v), 31), l63 = __builtin_amdgcn_readlane(__float_as_int(v), 63);
+        asm("v_writelane_b32 %0, %1, 0\n\tv_writelane_b32 %0, %2, 32" : "+v"(sh) : "s"(l31), "s"(l63));
+        return __int_as_float(sh);
     };
     auto above = [&](float v) { /* of slot s + 1 (even s: the same quad) */
-        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xF5 /* quad_perm:[1,1,3,3] */, 0xf, 0xf, false));
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xF5 /* quad_perm:[1,1,3,3] */, 0xf, 0xf, true));
     };
     const float qa = (below(Pa) + Pa) * 0.5f, qb = (below(Pb) + Pb) * 0.5f;
     const float qc = (above(Pc) + Pc) * 0.5f, qd = (above(Pd) + Pd) * 0.5f;

@@ -83,6 +83,21 @@
  * 1.479 -> 1.486 with N1 2440 -> 2585 clk, none better under its own best wave -> role map; the step follows the instruction count, not
  * the longest role: all four launch rows end together (profiles/ns6_transform_chain.txt).
  *
+ * Round 13, all three kernels: address and operand set-up off the steady beats of the two transform waves, no operation, beat, barrier, ring
+ * slot or LDS instruction added --
+ *   wave FA  the steady copies take the onset and their pair counter through v_readfirstlane at the switch into the range (FA writes its
+ *            onset under the gate's ballot and the compiler took it, and everything derived from it, for lane-dependent): ticks, ring
+ *            slots and window bases are scalar, the next frame's address is an SGPR pair counted on by one frame per beat and its load
+ *            sits under the store's lane branch
+ *   FA, FB   the twiddled butterfly's four output additions read the halves of their operand pairs through op_sel / neg_lo / neg_hi
+ *            (sea_device.h, fft2_bf_out) instead of operands built with a packed negation, an exclusive-or and three moves
+ *   wave FB  the PSD's neighbour fetches need no zero in their destination (bound_ctrl) and repair the two wrap lanes with v_writelane
+ *            (ns_core.h, psd_from_last_level)
+ *   all      the test "is this a beat on which the priority is set" is one scalar compare and branch (prio_by_remaining; not the _fd kernel)
+ * Dense kernel: FA 251.5 -> 217.5, FB 150.5 -> 130.5 vector instructions per beat on the listing; counted, 1088 -> 1036 vector, 314 -> 322
+ * scalar and 205 -> 204 LDS instructions per frame; configs[1] 1.365-1.370 -> 1.332-1.336 ms over 200 steps, 2.5 % and over five times the
+ * spread in two alternations of the final code (profiles/ns6_offstream.txt).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -219,8 +234,11 @@ __device__ __forceinline__ bool beat_flag(int i, int onset, int nfr)
     static_assert(ns6plan::has_flag(VARIANT, ROLE, D, K), "a flag the beat plan of ns6_beat_plan.h does not know");
     return STEADY || tick_ge(i - D, K, onset, nfr);
 }
-template <bool STEADY_LOOP, unsigned VARIANT, int ROLE, bool PAIRED = false, class Beat>
-__device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, Beat &&beat)
+struct NoEnter {
+    __device__ __forceinline__ int operator()(int h) const { return h; }
+};
+template <bool STEADY_LOOP, unsigned VARIANT, int ROLE, bool PAIRED = false, class Beat, class Enter = NoEnter>
+__device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, Beat &&beat, Enter &&enter = Enter{})
 {
     int i = 0;
     while (i < niter) {
@@ -228,7 +246,9 @@ __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, 
             const int e0 = ns6plan::steady_end(VARIANT, ROLE, nfr), e = e0 < niter ? e0 : niter;
             if constexpr (PAIRED) {
                 if ((i & 1) == 0) { /* an odd beat in front goes through the general copy below, and so does one left over behind */
-                    int h = i >> 1;
+                    /* enter: the role's hook at the switch into a steady range; it gets the pair counter's first value and returns
+                     * the one to count from (FA: the same number, stated to be wave-uniform) */
+                    int h = enter(i >> 1);
                     for (const int he = e >> 1; h < he; ++h) {
                         beat(BoolC<true>{}, 2 * h);
                         beat(BoolC<true>{}, 2 * h + 1);
@@ -521,7 +541,14 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
     const float lrptScale = (float)kPrioLevels / (float)(longestFr > 0 ? longestFr : 1);
     const int lrptBias = lrpt ? (int)blockIdx.x / a.prio_row : 0; /* equal levels: the hardware prefers the oldest wave */
     auto prio_by_remaining = [&](int i) {
-        if (lrpt && (i & (kPrioStep - 1)) == 0) {
+        if ((FD ? lrpt : true) && (i & (kPrioStep - 1)) == 0) {
+            /* round 13: the beat's own test first and alone, one scalar compare and branch; the empty statement keeps the compiler from
+             * merging it with the launch's flag into a lane-mask expression of six instructions per beat.  Not in the _fd kernel, whose
+             * G1 gains four moves per pair of beats with it (its period is B0's beat: nothing to win there). */
+            if constexpr (!FD) {
+                asm volatile("");
+                if (!lrpt) return;
+            }
             const int L = __builtin_amdgcn_readfirstlane((int)((float)(nfr - i) * lrptScale)) + lrptBias;
             const int pr = (L + (int)(((unsigned)i / kPrioStep) & (kPrioLevels / 4 - 1))) / (kPrioLevels / 4);
             if (pr >= 3) __builtin_amdgcn_s_setprio(3);
@@ -576,9 +603,20 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
         const float irWin = (FIR_FA && !IDCTS) ? a.tables->irWin[lane] : 0.0f; /* lane k = 0..8: the Hanning weight of tap 8 +- k (IDCTS: S has it) */
         const uint32_t *in32 = reinterpret_cast<const uint32_t *>(a.in + off);
         uint32_t nextw = (lane < 40 && nfr > 0) ? in32[lane] : 0u;
-        int onset = kNoOnset; /* index of the first non-zero frame */
+        int onsetG = kNoOnset; /* index of the first non-zero frame */
+        /* Round 13: FA is the one role that WRITES its onset, under the gate's ballot, and the compiler takes the value -- and with
+         * it the switch into the steady range, the beat counter, every tick and ring slot -- for lane-dependent: the slot and
+         * address arithmetic of its steady copies ran on the vector unit.  The steady copies never change the onset (run_beats),
+         * so at the switch they get it, and their pair counter, through v_readfirstlane (every lane holds the same number); from
+         * there on counter, ticks, ring slots and the next frame's address are scalar, and the lane's part of an address is
+         * formed once in front of the loop.  The general copy keeps onsetG and publishes it exactly as before. */
+        int onsetS = kNoOnset;
+        typedef const __attribute__((address_space(1))) uint32_t *FramePtr;
+        unsigned long long nextFr = 0; /* steady copies: the address of frame i + 1 of the utterance, set at the switch, one frame on per beat */
         auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
             constexpr bool STEADY = decltype(steady)::value;
+            int &onset = *(STEADY && PAIRED ? &onsetS : &onsetG);
+            constexpr bool NEXT_S = STEADY && PAIRED; /* the next frame's address as a running scalar */
             NS6_T_BEGIN;
             prio_by_remaining(i);
             if constexpr (LIGHT) { /* the log-energy of the sum S left one beat ago (the frame pushed at i-2 is its tick + 2's "current frame") */
@@ -592,7 +630,8 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             bool actA = false;
             if (STEADY || i < nfr) {
                 const uint32_t w = nextw;
-                if ((STEADY || i + 1 < nfr) && lane < 40) nextw = (in32 + (long long)(i + 1) * 40)[lane];
+                if constexpr (!NEXT_S)
+                    if ((STEADY || i + 1 < nfr) && lane < 40) nextw = (in32 + (long long)(i + 1) * 40)[lane];
                 if (!STEADY && onset == kNoOnset && __ballot(w != 0u) != 0ull) {
                     onset = i;
                     if (lane == 0) __hip_atomic_store(&L.onset, i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -600,7 +639,16 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
                 if (STEADY || i >= onset) {
                     tick = tick_of(i, onset);
                     const float x0 = (float)(short)(w & 0xFFFFu), x1 = (float)(short)(w >> 16);
-                    if (lane < 40) slot_store<kSlots>(L.circ0, tick, lane, x0, x1);
+                    if (lane < 40) {
+                        /* steady copies (round 13): the next frame's load under the same lanes' branch as the store, its address in
+                         * SGPRs -- counted on from the switch into the range -- and the lane as the load's offset */
+                        if constexpr (NEXT_S) nextw = reinterpret_cast<FramePtr>(nextFr)[lane];
+                        slot_store<kSlots>(L.circ0, tick, lane, x0, x1);
+                    }
+                    if constexpr (NEXT_S) { /* outside the lanes' branch, and opaque: or it becomes a pointer per lane, two VGPRs */
+                        nextFr += SEA_HOP * 2u;
+                        asm("" : "+s"(nextFr));
+                    }
                     static_assert(ns6plan::has_flag(V, ns6plan::FA, 0, 3), "frame i exists here: its flag is the tick alone");
                     actA = STEADY || tick >= 3; /* NoiseSup.c:1152 */
                 }
@@ -639,9 +687,16 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             block_sync();
             NS6_T_END;
         };
-        run_beats<STEADY_LOOP, V, ns6plan::FA, PAIRED>(niter, nfr, onset, beat);
+        run_beats<STEADY_LOOP, V, ns6plan::FA, PAIRED>(niter, nfr, onsetG, beat, [&](int h) {
+            onsetS = __builtin_amdgcn_readfirstlane(onsetG);
+            const int hs = __builtin_amdgcn_readfirstlane(h);
+            unsigned long long fr = reinterpret_cast<unsigned long long>(in32 + (unsigned long long)(unsigned)(2 * hs + 1) * 40u);
+            asm("" : "+s"(fr));
+            nextFr = fr;
+            return hs;
+        });
         NS6_T_FLUSH(role, niter);
-        if (FD && a.onset_out && lane == 0) a.onset_out[u] = onset == kNoOnset ? nfr : onset;
+        if (FD && a.onset_out && lane == 0) a.onset_out[u] = onsetG == kNoOnset ? nfr : onsetG;
     } else if (role == 1) {
         /* ---- FB: second half of both transforms, FFTtoPSD ---- */
         Fft2Regs fft;

@@ -406,6 +406,25 @@ __device__ __forceinline__ void fft2_keep(const float (&v)[8])
     asm volatile("" ::"v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]), "v"(v[4]), "v"(v[5]), "v"(v[6]), "v"(v[7]) : "memory");
 }
 
+/* The output stage of the twiddled butterfly (rfft.c:163-174): eight additions on four register pairs,
+ *   o16 = (x1 + t5, x1 - t5)   o25 = (x5 + t4, x5 - t4)   o83 = (t6 + x6, t6 - x6)   o47 = (x2 - t3, -x2 - t3)
+ * with T56 = (t5, t6), D34 = (t3, t4).  Each is one v_pk_add_f32 whose op_sel / op_sel_hi fields pick the half of a pair that
+ * feeds the low / the high result and whose neg_lo / neg_hi fields flip an operand's sign on its way in; x1 and x5 travel as
+ * the halves of one pair, x2 and x6 of another, so no (x, x), (t, -t) or (x, -x) operand is ever built in registers (the
+ * compiler built them: a packed negation, an exclusive-or of the sign bit and three moves per butterfly).  a - b is
+ * a + (-b) in IEEE arithmetic, and a neg modifier is the same flip of bit 31 the exclusive-or made, before the addition
+ * and on every kind of value alike, so -0, Inf and NaN come out as before: same additions, same operands, same bits. */
+typedef float fft2_v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void fft2_bf_out(float x1, float x5, float x2, float x6, fft2_v2f T56, fft2_v2f D34, fft2_v2f &o16,
+                                            fft2_v2f &o25, fft2_v2f &o83, fft2_v2f &o47)
+{
+    const fft2_v2f x15 = {x1, x5}, x26 = {x2, x6};
+    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[0,0] neg_hi:[0,1]" : "=v"(o16) : "v"(x15), "v"(T56));
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]" : "=v"(o25) : "v"(x15), "v"(D34));
+    asm("v_pk_add_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[1,1] neg_hi:[0,1]" : "=v"(o83) : "v"(T56), "v"(x26));
+    asm("v_pk_add_f32 %0, %1, %2 op_sel_hi:[0,0] neg_lo:[0,1] neg_hi:[1,1]" : "=v"(o47) : "v"(x26), "v"(D34));
+}
+
 /* Both butterfly kinds are evaluated by every lane and the lane's own kind selects the results: a wave executes both
  * sides of a divergent branch anyway, and without the branch the two independent dependency chains interleave and the
  * compiler sees that the operand loads have been consumed (with the branch it had to protect the next level's loads
@@ -432,10 +451,8 @@ __device__ __forceinline__ void fft2_butterfly(const Fft2Regs &R, const Fft2Ops 
         asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(q3) : "v"(a48), "v"(w3));
         const v2f T12 = p1 + q1, T34 = p3 + q3;
         const v2f T56 = T12 + T34, D34 = T12 - T34; /* (t5,t6), new (t3,t4) */
-        const v2f o16 = v2f{x1, x1} + v2f{T56.x, -T56.x}; /* x1 + t5, x1 - t5 */
-        const v2f o25 = v2f{x5, x5} + v2f{D34.y, -D34.y}; /* x5 + t4, x5 - t4 */
-        const v2f o83 = v2f{T56.y, T56.y} + v2f{x6, -x6}; /* x6 + t6, t6 - x6 */
-        const v2f o47 = v2f{x2, -x2} - v2f{D34.x, D34.x}; /* x2 - t3, -x2 - t3 */
+        v2f o16, o25, o83, o47;
+        fft2_bf_out(x1, x5, x2, x6, T56, D34, o16, o25, o83, o47);
         o1 = o16.x, o6 = o16.y, o2 = o25.x, o5 = o25.y, o8 = o83.x, o3 = o83.y, o4 = o47.x, o7 = o47.y;
     }
     float p1, p3, p4, p5, p6, p7, p8;
@@ -474,10 +491,8 @@ __device__ __forceinline__ void fft2_bf_kind(const unsigned kind, const float (&
         asm("v_pk_mul_f32 %0, %1, %2 op_sel:[1,1] op_sel_hi:[0,1] neg_hi:[0,1]" : "=v"(q3) : "v"(a48), "v"(w3));
         const v2f T12 = p1 + q1, T34 = p3 + q3;
         const v2f T56 = T12 + T34, D34 = T12 - T34;
-        const v2f o16 = v2f{x1, x1} + v2f{T56.x, -T56.x};
-        const v2f o25 = v2f{x5, x5} + v2f{D34.y, -D34.y};
-        const v2f o83 = v2f{T56.y, T56.y} + v2f{x6, -x6};
-        const v2f o47 = v2f{x2, -x2} - v2f{D34.x, D34.x};
+        v2f o16, o25, o83, o47;
+        fft2_bf_out(x1, x5, x2, x6, T56, D34, o16, o25, o83, o47);
         o1 = o16.x, o6 = o16.y, o2 = o25.x, o5 = o25.y, o8 = o83.x, o3 = o83.y, o4 = o47.x, o7 = o47.y;
     } else { /* SEA_BF_PAIR (rfft.c:110-113, :120-125) */
         const float t1 = x4 + x3;
