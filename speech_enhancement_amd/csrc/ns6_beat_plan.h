@@ -52,6 +52,14 @@ constexpr unsigned kVariantDenseBin64 = kRedeal | kBin64;
 constexpr unsigned kIdctS = 32u;
 constexpr unsigned kVariantDenseIdct = kRedeal | kBin64 | kIdctS;
 constexpr int kDepthIdct = 12;       /* a role of that variant runs nfr + 12 beats; S stores frame i - 12 */
+/* kFirPair (round 14, the dense kernel): both 17-tap filters run as ONE pass on the two lane halves of G1 -- stage-0 frame i-4 (off FA)
+ * and stage-1 frame i-12, whose taps S leaves at the same beat i-1.  The filtered stage-0 frame crosses a frame barrier before FA windows
+ * it (FA: stage 1 of frame i-5, was i-4), so every stage-1 job moves by one more beat.  The variant has a table of its own
+ * (kPlanFirPair) and a depth of its own; the dense kernel is kVariantDenseFirPair, kVariantDenseIdct is the body it grew from, which no
+ * kernel takes any more */
+constexpr unsigned kFirPair = 64u;
+constexpr unsigned kVariantDenseFirPair = kRedeal | kBin64 | kIdctS | kFirPair;
+constexpr int kDepthFirPair = 13;    /* a role of that variant runs nfr + 13 beats; S stores frame i - 13 */
 
 struct Flag {
     int d;         /* the flag is about frame i - d ... */
@@ -99,9 +107,30 @@ constexpr RolePlan kPlanIdct[kRoles] = {
     /* S: VAD sum of frame i-1, denSigSE1 sum and stage-0 IDCT sums of i-3, noise sum of i-7, stage-1 IDCT sums of i-10, output of i-12 */
     {5, {{1, 1, kAlways}, {3, 3, kAlways}, {7, 5, kAlways}, {10, 5, kAlways}, {kDepthIdct, 5, kAlways}}, 0, 1},
 };
-SEA_NS6_HD constexpr const RolePlan &plan_of(unsigned variant, int role) { return (variant & kIdctS) ? kPlanIdct[role] : kPlan[role]; }
+/* the table of the variants with kFirPair, likewise.  Derivation, from the stage-0 chain (FA i, FB i-1, B0 i-2, S i-3, whose offsets do
+ * not move): S leaves the stage-0 taps of frame f at f+3, G1 filters at f+4 (from tick 3: ticks 3 and 4 leave output that the first
+ * stage-1 window reads), FA windows the stage-1 input at f+5, FB f+6, N1 tracks at f+7, S sums the noise and B0 takes bin 64 at f+8, N1's
+ * gain-factor scalars at f+9, G1's gains and products at f+10, S's stage-1 sums at f+11, G1 filters at f+12, S stores at f+13 */
+constexpr RolePlan kPlanFirPair[kRoles] = {
+    /* FA: frame i itself enters stage 0 from tick 3; stage 1 of frame i-5 from tick 5 */
+    {2, {{0, 3, kAlways}, {5, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 1, 0},
+    /* FB: one beat behind FA on both transforms */
+    {2, {{1, 3, kAlways}, {6, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* B0: stage-0 back half of frame i-2 (up to the IDCT products); stage-1 bin 64 of frame i-8 */
+    {2, {{2, 3, kAlways}, {8, 5, kAlways}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* N1: the VAD log-energy of frame i-2, noise tracking of frame i-7, gain-factor scalars of frame i-9 */
+    {3, {{2, 1, kAlways}, {7, 5, kAlways}, {9, 5, kAlways}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* G1: the merged filter pass over stage-0 frame i-4 and stage-1 frame i-12; gains, mel and IDCT products of frame i-10 */
+    {3, {{4, 3, kAlways}, {10, 5, kAlways}, {12, 5, kAlways}, {0, 0, 0}, {0, 0, 0}}, 0, 0},
+    /* S: VAD sum of frame i-1, denSigSE1 sum and stage-0 IDCT sums of i-3, noise sum of i-8, stage-1 IDCT sums of i-11, output of i-13 */
+    {5, {{1, 1, kAlways}, {3, 3, kAlways}, {8, 5, kAlways}, {11, 5, kAlways}, {kDepthFirPair, 5, kAlways}}, 0, 1},
+};
+SEA_NS6_HD constexpr const RolePlan &plan_of(unsigned variant, int role)
+{
+    return (variant & kFirPair) ? kPlanFirPair[role] : ((variant & kIdctS) ? kPlanIdct[role] : kPlan[role]);
+}
 /* beats a role runs past the last frame; S stores frame i - depth_of */
-SEA_NS6_HD constexpr int depth_of(unsigned variant) { return (variant & kIdctS) ? kDepthIdct : kDepth; }
+SEA_NS6_HD constexpr int depth_of(unsigned variant) { return (variant & kFirPair) ? kDepthFirPair : ((variant & kIdctS) ? kDepthIdct : kDepth); }
 
 SEA_NS6_HD constexpr bool flag_applies(const Flag &f, unsigned variant) { return f.when == kAlways || (f.when & variant) != 0u; }
 

@@ -1761,6 +1761,69 @@ __device__ __forceinline__ void ns_fir_from_idct_taps(const float *taps, const f
     }
 }
 
+/* Both 17-tap filters of a beat as ONE pass on the two halves of a wave (the dense six-wave form since round 14).  ns_fir_from_idct_taps
+ * and ns_fir_apply each give 80 outputs as 40 lanes x 2: 68 multiplications and additions on 40 of 64 lanes, twice per frame, each
+ * with its own taps and samples.  Here lane 32 h + j computes outputs 3j, 3j + 1 and 3j + 2 of half h's filter (h = 0: stage 0,
+ * h = 1: stage 1): 160 outputs over 2 x 27 lanes, 17 x 3 multiplications and as many additions for both.  Every output is the same
+ * sum as in ns_fir_regs -- y = 0, then y += c[k] * x[16 + o - k] for k = 0..16 in that order, c[k] the tap |k - 8|, x[m] =
+ * buf[72 + 3j + m] -- so the results are the same bits.
+ *   lanes    j = 26 has outputs 78, 79 and 80: the third is computed (from buf[152..168], inside the window) and never stored.  Lanes
+ *            j = 27..31 repeat lane 26, stores included (the same values to the same words, as lanes >= 40 do in the two-output
+ *            forms): one lane mask per beat, that of the third output, and none for the first two.
+ *   samples  19 per lane at a stride of three words: a lane's address is 8-byte aligned for even j only, so the reads are 32-bit
+ *            (pairs of them: ds_read2_b32)
+ *   taps     the nine distinct ones sit in per-lane registers, read from the half's record of windowed taps (helper_chains<.., IDS>,
+ *            kIdsTapStride apart): scalar operands (fir_taps_rl) cannot differ between the halves, and no mirrored copy of the 17
+ *            is stored or waited for
+ *   address  the lane's part of every address is formed once in front of the frame loop (FirPair3, byte offsets into the workgroup's
+ *            LDS); a beat adds scalars, selected by half: the window bases, the frame parity of the tap and output records, the
+ *            stage-1 buffer's slot
+ *   stores   half 0 into the stage-1 buffer's slot and, for slots 0..2, into the mirrored slot behind the ring (mirror > 0: its
+ *            distance in bytes), half 1 into the output record; live0 / live1: whether the half's frame exists (both literal `true`
+ *            in the steady copy).  A dead half computes on whatever its addresses hold, all inside the record, and stores nothing.
+ * Nothing the wave itself reads afterwards is written here, so it ends without a wave_sync(): the frame barrier publishes the stores. */
+struct FirPair3 {
+    char *lds;
+    int x;   /* samples: the half's buffer + (72 + 3j) floats; the beat adds the half's window base */
+    int tap; /* the half's tap record of parity 0; the beat adds the parity's */
+    int dst; /* half 0: the stage-1 buffer, half 1: the output record of parity 0, + 3j floats; the beat adds slot or parity */
+};
+__device__ __forceinline__ void ns_fir_pair3(const FirPair3 &F, int win0, int win1 /* bytes: window bases */, int tapPar /* bytes */,
+                                             int dst0, int dst1 /* bytes: slot of the stage-1 buffer, output record's parity */,
+                                             int mirror, bool live0, bool live1, int lane)
+{
+    const bool hi = lane >= 32;
+    const bool third = (lane & 31) < 26;
+    const float *taps = reinterpret_cast<const float *>(F.lds + (F.tap + tapPar));
+    const float *src = reinterpret_cast<const float *>(F.lds + (F.x + (hi ? win1 : win0)));
+    float *dst = reinterpret_cast<float *>(F.lds + (F.dst + (hi ? dst1 : dst0)));
+    float t[9], x[19];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) t[k] = taps[kIdsTapStride * k];
+#pragma unroll
+    for (int m = 0; m < 19; ++m) x[m] = src[m];
+    float y0 = 0.0f, y1 = 0.0f, y2 = 0.0f;
+#pragma unroll
+    for (int k = 0; k < SEA_NTAP; ++k) {
+        const float c = t[k < 8 ? 8 - k : k - 8];
+        y0 += c * x[16 - k];
+        y1 += c * x[17 - k];
+        y2 += c * x[18 - k];
+    }
+    const bool live = hi ? live1 : live0;
+    if (live) {
+        dst[0] = y0;
+        dst[1] = y1;
+        if (third) dst[2] = y2;
+    }
+    if (mirror > 0 && live0 && !hi) {
+        float *m = reinterpret_cast<float *>(reinterpret_cast<char *>(dst) + mirror);
+        m[0] = y0;
+        m[1] = y1;
+        if (third) m[2] = y2;
+    }
+}
+
 /* One whole stage on the single-wave form: stage 0 deposits its 80 output samples in
  * ring[1][240..319], stage 1 in outb[0..79].  Only the streaming kernels (ns_tick) run it, on the caller's floats: NF. */
 template <int ST, bool FD = false>

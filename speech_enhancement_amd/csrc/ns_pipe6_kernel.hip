@@ -17,7 +17,7 @@
  *   wave S   the lane-grouped scalar chains: VAD log-energy of the frame pushed at i-1, in-order sum of
  *            denSigSE1 of frame i-3, in-order sum of the noise spectrum of frame i-6, DC-offset recurrence
  *            + cast + store of frame i-9 (kDepth)
- * (the dense kernel's schedule since round 11 is three beats deeper: the Round 11 paragraph below)
+ * (the dense kernel's schedule since round 11 is three beats deeper, since round 14 four: the Round 11 and Round 14 paragraphs below)
  *
  * Round 6: the in-order sum of the 65 second-stage noise magnitudes (64 v_readlane + v_add in N1, ~129 vector instructions
  * for one scalar) rides the helper wave's serial stream in lanes 48..63, which only repeated the DC chain: no instruction
@@ -98,6 +98,19 @@
  * scalar and 205 -> 204 LDS instructions per frame; configs[1] 1.365-1.370 -> 1.332-1.336 ms over 200 steps, 2.5 % and over five times the
  * spread in two alternations of the final code (profiles/ns6_offstream.txt).
  *
+ * Round 14, the dense kernel only (FIRP of ns_pipe6_body): the time-domain filter ApplyWF ran twice per frame in two waves, each time 80
+ * outputs as 40 lanes x 2, 68 multiplications and additions on 40 of 64 lanes with its own taps and samples; both become ready at the same
+ * beat, S leaves both stages' taps at i-1.  Now --
+ *   wave G1  also: ONE pass on its two lane halves (ns_core.h, ns_fir_pair3), lane 32 h + j computing outputs 3j .. 3j + 2 of stage h from
+ *            per-lane taps: stage-0 frame i-4 -> the stage-1 buffer, stage-1 frame i-12 -> ro[]; 102 multiplications and additions for both
+ *            where 136 were, one set of reads, no mirrored taps; then the gains of frame i-10
+ *   wave FA  filters no more; it windows stage-1 frame i-5, which G1 left one beat before, behind a frame barrier
+ *   all      every stage-1 job one more beat later: FB i-6, N1 i-7 / i-9, B0's guest i-8, S's noise sum i-8, stage-1 sums i-11, output i-13
+ * The pipeline is thirteen beats deep (ns6plan::depth_of), S's ring of den sums sixteen (kDenRing16), and the map was swept again
+ * (kRedealPerm).  Every output is the same in-order 17-term sum of the same rounded products.  Listing, steady beats: FA 81 vector and 8
+ * LDS instructions fewer per frame, G1 34 and 5 more; configs[1] over 200 steps 1.344 -> 1.295 ms with the parent's map (8 x the larger spread), 1.334 ->
+ * 1.267 ms = 646 M frames/s with the swept one (-5.0 %, 7 x; profiles/ns6_fir_merged.txt).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -165,8 +178,10 @@ constexpr int kDefaultPerm = 0014352;
  * FB on waves 0..5 -- the best ten maps of that sweep all keep G1 on wave 3 and B0 or N1 on wave 2; 0053412 is 76th there, 2.8 %
  * behind (profiles/ns6_bin64_in_b0.txt).  Round 11, with the IDCT sums in S: S, B0, N1, FA, G1, FB on waves 0..5 -- six of the best
  * ten maps of that sweep keep N1 on wave 2 and G1 on wave 4, seven have S on wave 0 or 1; 0154230 is 122nd there, 3.9 % behind
- * (profiles/ns6_idct_in_helper.txt) */
-constexpr int kRedealPerm = 0140325;
+ * (profiles/ns6_idct_in_helper.txt).  Round 14, with both filters in G1 and FA the lighter for it: S, B0, N1, G1, FA, FB on waves 0..5
+ * -- G1 and FA change places; eight of the best ten maps of that sweep keep G1 on wave 3, seven N1 on wave 2, all ten S on wave 0 or 1; 0140325 is 18th there,
+ * 1.2 % behind (profiles/ns6_fir_merged.txt) */
+constexpr int kRedealPerm = 0104325;
 
 /* Frame bookkeeping (valid / tick / produced of every frame) is a pure function of the frame index: the zero-frame gate
  * (ParmInterface.c:244-251) has one degree of freedom per utterance, the index `onset` of the first non-zero frame.  From it on every
@@ -316,12 +331,41 @@ __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, 
  *   stage-0 buffer    FA's filter of frame i-4 reads the slots of frames i-7 .. i-5 (buf[72..167] of that frame's window) while its push
  *                     of that beat writes the slot of frame i = i-8 (mod 8), and its own window reads i-3 .. i: no collision, by one
  *   LDS               31 856 B per workgroup; five fit a CU's 160 KB, which is what the compiler's occupancy of 7 counts
+ *   FIRP (round 14)   both filters in G1, FA's stage-1 window behind a frame barrier, every stage-1 job one more beat later:
+ *                     stage 0: B0's products at f+2, S's sums at f+3, G1's filter (low half) at f+4 -> the stage-1 buffer.  Frame f is
+ *                     transformed (stage 1) by FA at f+5, FB at f+6; noise-tracked at f+7 (B0's guest: f+8); noise-summed at f+8;
+ *                     gain-factored at f+9; G1 takes its gains and leaves the products at f+10; S adds them up at f+11; G1 filters
+ *                     (high half) at f+12 -> ro[f]; S stores at f+13 = f+DEPTH.
+ *   p1                written at f+6, read by N1 at f+7, B0 at f+8, G1 at f+10: D > 4, as before
+ *   rn                written at f+7, read by S and B0 at f+8, by G1 at f+10: D > 3, as before
+ *   w1hi              written at f+8, read at f+10: D > 2, as before
+ *   nzSum, alfa, ro   f+8 -> f+9, f+9 -> f+10, f+12 -> f+13: by frame parity, as before
+ *   prod, tap         B0 f+2 -> S f+3 -> G1 f+4; G1 f+10 -> S f+11 -> G1 f+12: by frame parity; at one beat S reads stage 0's record of
+ *                     parity (i-3) & 1 and stage 1's of the SAME parity, (i-11) & 1 -- all four product records sit in the same bank
+ *                     slots (asserted below), so which two meet does not matter -- and G1's two halves read the tap records of one
+ *                     parity, (i-4) & 1 = (i-12) & 1
+ *   denSum            tick t written by S at f+3; N1 reads ticks t-2 .. t for the frames f .. f+2, the last at f+2+9: D > 8.  Eight
+ *                     no longer hold (at iteration f+11 S writes tick t+8 while N1 reads tick t): the variant has a ring of its own,
+ *                     Pipe6Idct::denSum16, sixteen deep (kDenRing16); Pipe6Lds::denSum stays for the other kernels
+ *   stage-1 buffer    G1 writes the slot of frame i-4 at iteration i (tick T) and its three mirrored words' slot with it; FA's window
+ *                     of frame i-5 reads slots T-4 .. T-1 (written at iterations i-4 .. i-1, each behind a barrier), G1's high half
+ *                     reads buf[72..168] of the window of frame i-12, slots T-11 .. T-9: twelve live slots T-11 .. T, sixteen do not
+ *                     collide (the slot's previous content, tick T-16 = frame i-20, was last read by G1 at iteration i-7, as the last slot
+ *                     of frame i-19's filter).  A mirrored slot is written only with its slot and read only as that slot's tick: it lives as the slot does.
+ *   stage-0 buffer    its reader is now G1, concurrently with FA's push of that beat (until now both were FA): G1's low half reads
+ *                     buf[72..168] of the window of frame i-4, i.e. the slots of frames i-7 (8 words), i-6 and i-5 (9 words; the
+ *                     ninth, buf[168], only feeds lane 26's unused third output), FA writes the slot of frame i = i-8 (mod 8) and,
+ *                     for slots 0..2, its mirrored copy: a different tick mod 8 from all three, so neither the slot nor its mirror is
+ *                     one G1 reads -- by one, as before; S reads the slot of frame i-1.  The slots G1 reads were written at iterations
+ *                     i-7 .. i-5.
+ *   LDS               31 920 B per workgroup (+ 64 for denSum16): five still fit a CU's 160 KB
  * nbFrame of the gain-factor job: N1's counter has by then counted the two frames tracked since; the job takes the frame's own
  * count, tick - 4 (the first second-stage frame has tick 5).
  * LDS: 24 960 B per workgroup (24 624 + the two tap records + the ring of W1[64]); four workgroups per CU take 99.8 KB of the 160. */
 constexpr int kP1Ring = 8;
 constexpr int kRnRing = 4;
 constexpr int kW1Ring = 4;
+constexpr int kDenRing16 = 16;
 struct __attribute__((aligned(16))) RecPsd { /* FB -> B0 (stage 0) / N1, G1 (stage 1) */
     float psd[68];
 };
@@ -402,6 +446,7 @@ struct __attribute__((aligned(16))) Pipe6Idct {
     float zeros[kIdsZeros];
     float pad[4];                      /* and the rows' slots, where ssq, sdif and den are not */
     float prod[2][2][kIdctProdFloats]; /* [stage][frame parity] */
+    float denSum16[kDenRing16];        /* FIRP: S's denSigSE1 sums by tick & 15, in place of Pipe6Lds::denSum (derivation at kP1Ring) */
 };
 /* basisQ takes the place of idctT, which this variant does not read: four workgroups need 4 x 40 KB at the most, but the compiler's
  * occupancy figure counts whole workgroups against the CU's 160 KB, and seven waves per SIMD are five of these, 32 KB each */
@@ -434,6 +479,12 @@ static_assert(lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[0].den), NS6_OFF(x
                   lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[1].den), NS6_OFF(x.prod[0][1]), NS6_OFF(x.prod[1][0]), 0, 3) &&
                   lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[1].den), NS6_OFF(x.prod[0][1]), NS6_OFF(x.prod[1][0]), 3, 9) &&
                   (kIdctStride * sizeof(float)) % 16 == 0, "n < 28: ssq, den | the rows, in both groups and both parities");
+/* FIRP: stage 1's record has the parity of stage 0's */
+static_assert(lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[0].den), NS6_OFF(x.prod[0][0]), NS6_OFF(x.prod[1][0]), 0, 3) &&
+                  lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[0].den), NS6_OFF(x.prod[0][0]), NS6_OFF(x.prod[1][0]), 3, 9) &&
+                  lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[1].den), NS6_OFF(x.prod[0][1]), NS6_OFF(x.prod[1][1]), 0, 3) &&
+                  lds_group_ok(NS6_OFF(base.ssq), NS6_OFF(base.rd[1].den), NS6_OFF(x.prod[0][1]), NS6_OFF(x.prod[1][1]), 3, 9),
+              "the same with both stages' records of one parity");
 static_assert(NS6_OFF(x.zeros) % 16 == 0 && lds_slots_differ(NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float), NS6_OFF(base.ssq)) &&
                   lds_slots_differ(NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float), NS6_OFF(base.rd[0].den)) &&
                   lds_slots_differ(NS6_OFF(x.zeros) + 256 - kIdctRow * sizeof(float), NS6_OFF(base.rd[1].den)), "28 <= n: the rows' zeros | ssq, den");
@@ -479,26 +530,36 @@ template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands
           bool REDEAL = false /* round 8, the dense kernel: feed-forward work of S and B0 in the waves that wait, and the map that goes with it */,
           bool BIN64 = false /* round 10, the dense kernel: stage-1 bin 64 rides in B0's second component, one domain flag per stage-1 frame */,
           bool IDCTS = false /* round 11, the dense kernel: both stages' IDCT sums ride in the helper wave's idle lanes; X is its LDS */,
-          bool PAIRED = false /* round 12, all three kernels: the steady beats two by two, the frame parity a constant of each copy (run_beats) */>
+          bool PAIRED = false /* round 12, all three kernels: the steady beats two by two, the frame parity a constant of each copy (run_beats) */,
+          bool FIRP = false /* round 14, the dense kernel: both 17-tap filters as one pass on G1's two lane halves, off FA (ns_core.h, ns_fir_pair3) */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L, Pipe6Idct *X = nullptr)
 {
     static_assert(!REDEAL || (!LIGHT && !DIFG1), "the re-deal is a variant of the dense body");
     static_assert(!BIN64 || (REDEAL && !FD), "the guest of B0's second component is a variant of the re-dealt dense body");
     static_assert(!IDCTS || BIN64, "the IDCT sums in the helper wave are a variant of that body in turn");
     static_assert(!PAIRED || STEADY_LOOP, "the paired beats are the steady copies'");
+    static_assert(!FIRP || IDCTS, "the merged filter pass takes both stages' taps from the helper wave");
     constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u) |
-                           (BIN64 ? ns6plan::kBin64 : 0u) | (IDCTS ? ns6plan::kIdctS : 0u);
-    static_assert(!BIN64 || V == (IDCTS ? ns6plan::kVariantDenseIdct : ns6plan::kVariantDenseBin64),
-                  "the variants tests/test_ns6_idct_plan_cpu.py and tests/test_ns6_bin64_plan_cpu.py sweep");
+                           (BIN64 ? ns6plan::kBin64 : 0u) | (IDCTS ? ns6plan::kIdctS : 0u) | (FIRP ? ns6plan::kFirPair : 0u);
+    static_assert(!BIN64 || V == (FIRP ? ns6plan::kVariantDenseFirPair : (IDCTS ? ns6plan::kVariantDenseIdct : ns6plan::kVariantDenseBin64)),
+                  "the variants tests/test_ns6_fir_plan_cpu.py, tests/test_ns6_idct_plan_cpu.py and tests/test_ns6_bin64_plan_cpu.py sweep");
     /* IDCTS (profiles/ns6_idct_in_helper.txt): DoMelIDCT's nine in-order sums of 25 terms, twice per frame, cost B0 and G1 25 lane reads,
      * 25 basis reads, 25 multiplications and a chain of 25 dependent additions each, for nine useful lanes.  Here B0 (frame i-2) and G1
      * (frame i-9) stop at the rounded products (ns_idct_products), S adds the rows up one beat later in lanes that only repeated another
      * chain (helper_chains<.., IDS>: the same additions in the same order), and the filters follow one beat after that: FA filters
      * stage-0 frame i-4, so every stage-1 job sits one beat later than the table at kP1Ring has it (kS1), and G1 filters frame i-11 in
      * the beat in which it takes the gains of frame i-9.  The pipeline is three beats deeper (DEPTH). */
-    constexpr int kS1 = IDCTS ? 1 : 0;             /* beats by which stage 1 starts later */
+    /* FIRP (profiles/ns6_fir_merged.txt): the two filters -- stage-0 frame i-4 in FA, stage-1 frame i-11 in G1 -- were 2 x 68 vector
+     * instructions on 40 of 64 lanes, and both become ready at the same beat: S leaves both stages' taps at i-1.  G1, the role with the
+     * most slack, runs them as one pass on its two lane halves (ns_fir_pair3: 102 for both, one set of reads, no mirrored taps); FA,
+     * workgroup 0's longest role, filters no more.  The filtered stage-0 frame now crosses a frame barrier before FA windows it, so
+     * every stage-1 job sits one more beat later (kS1 = 2) and the pipeline is thirteen beats deep. */
+    constexpr int kS1 = FIRP ? 2 : (IDCTS ? 1 : 0); /* beats by which stage 1 starts later */
     constexpr int DEPTH = ns6plan::depth_of(V);    /* S stores frame i - DEPTH */
-    static_assert(DEPTH == (IDCTS ? 12 : kDepth), "the depth the ring depths at kP1Ring are derived for");
+    static_assert(DEPTH == (FIRP ? 13 : (IDCTS ? 12 : kDepth)) && DEPTH == 9 + 2 * (IDCTS ? 1 : 0) + kS1, "the depth the ring depths at kP1Ring are derived for");
+    /* the ring of S's denSigSE1 sums, one per tick: FIRP reads it one beat later still and has sixteen (derivation at kP1Ring) */
+    constexpr int kDenRing = FIRP ? kDenRing16 : kSlots;
+    float *const denRing = FIRP ? X->denSum16 : L.denSum;
     /* BIN64 (profiles/ns6_bin64_in_b0.txt): the Wiener-gain chain ran on the pair (bin lane, bin 64) in B0 and in G1, and the second
      * component is one useful value in 64 identical lanes.  B0, at beat i, takes stage-1 bin 64 of frame g = i-6 into lane 1 of its
      * second component (ns_core.h, NsBin64) and leaves W1[64] in w1hi[g & 3]; G1 computes bins 0..63 with the single-component chain.
@@ -588,6 +649,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             basisQ[i] = (t < 9 && f < SEA_NMEL) ? a.tables->idct[f][t] : 0.0f;
         }
         if (threadIdx.x < kIdsZeros) X->zeros[threadIdx.x] = 0.0f;
+        if (FIRP && threadIdx.x < kDenRing16) X->denSum16[threadIdx.x] = 0.0f;
         if (threadIdx.x < 6) L.back[threadIdx.x / 3].mel[SEA_NMEL + threadIdx.x % 3] = 0.0f;
     }
     block_sync();
@@ -653,10 +715,10 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
                     actA = STEADY || tick >= 3; /* NoiseSup.c:1152 */
                 }
             }
-            /* stage 1, frame i-3 (B0 finished it at the previous iteration; IDCTS: frame i-4, S did): NoiseSup.c:1178 <=> tick >= 5 */
+            /* stage 1, frame i-3 (B0 finished it at the previous iteration; IDCTS: frame i-4, S did; FIRP: frame i-5, G1 did): NoiseSup.c:1178 <=> tick >= 5 */
             const int t1 = tick_of(i - 3 - kS1, onset);
             const bool actB = beat_flag<V, ns6plan::FA, 3 + kS1, 5, STEADY>(i, onset, nfr);
-            if constexpr (FIR_FA) {
+            if constexpr (FIR_FA && !FIRP) { /* FIRP: G1 filtered frame i-5 at the previous iteration, behind a frame barrier */
                 /* stage-0 filter of frame i-3 from the IDCT sums B0 left at the previous iteration; from tick 3, not 5: ticks 3 and 4
                  * leave output that the first stage-1 window reads.  Also in the drain, where FA has no frame of its own. */
                 if (beat_flag<V, ns6plan::FA, 3 + kS1, 3, STEADY>(i, onset, nfr)) {
@@ -814,9 +876,9 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             if (beat_flag<V, ns6plan::N1, 7 + kS1, 5, STEADY>(i, onset, nfr)) {
                 const int t = tick_of(fg, onset);
                 /* denEn1[0..2] (NoiseSup.c:595-598) = sums of denSigSE1 of ticks t-2, t-1, t */
-                s.denEn0 = L.denSum[(t - 2) & (kSlots - 1)];
-                s.denEn1 = L.denSum[(t - 1) & (kSlots - 1)];
-                s.denEn2 = L.denSum[t & (kSlots - 1)];
+                s.denEn0 = denRing[(t - 2) & (kDenRing - 1)];
+                s.denEn1 = denRing[(t - 1) & (kDenRing - 1)];
+                s.denEn2 = denRing[t & (kDenRing - 1)];
                 const int nbNow = s.nbFrame[1]; /* has counted the frames tracked since; this frame's count is t - 4 */
                 s.nbFrame[1] = t - 4;
                 gain_fact_update(s, L.nzSum[fg & 1]);
@@ -842,13 +904,37 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
         regs_init(s, C.eps);
         float lastIn = 0.0f; /* LIGHT: y[79] of the previous filtered frame (prevSamples, NoiseSup.c:908) */
         int onset = kNoOnset;
+        FirPair3 fp = {}; /* FIRP: the lane's part of the merged filter pass's addresses (ns_core.h) */
+        if constexpr (FIRP) {
+            char *const lds = reinterpret_cast<char *>(&L);
+            auto at = [&](const void *q) { return (int)(reinterpret_cast<const char *>(q) - lds); };
+            const int j = (lane & 31) < 27 ? (lane & 31) : 26; /* lanes 27..31 of a half repeat lane 26 */
+            fp.lds = lds;
+            fp.x = (lane < 32 ? at(L.circ0) : at(L.circ1)) + (72 + 3 * j) * (int)sizeof(float);
+            fp.tap = lane < 32 ? at(X->tap[0][0]) : at(X->tap[1][0]);
+            fp.dst = (lane < 32 ? at(L.circ1) : at(L.ro[0].out)) + 3 * j * (int)sizeof(float);
+        }
         auto beat = [&](auto steady, int i) __attribute__((always_inline)) {
             constexpr bool STEADY = decltype(steady)::value;
             NS6_T_BEGIN;
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
             const int f = i - 8 - kS1;
-            if constexpr (IDCTS) {
+            if constexpr (FIRP) {
+                /* both 17-tap filters, from the windowed taps S left at the previous iteration: stage-0 frame i-4 (from tick 3, not 5:
+                 * ticks 3 and 4 leave output that the first stage-1 window reads) in lanes 0..31 -> the stage-1 buffer's slot of its
+                 * tick, which FA windows from the next iteration on; stage-1 frame i-12 in lanes 32..63 -> ro[].  Both frames have
+                 * the same parity, so both tap records are that parity's.  Ahead of the gains of frame i-10, which depend on neither;
+                 * in the fill only the low half is live, in the drain only the high half. */
+                const int f0 = i - 4, f1 = i - 12;
+                const bool live0 = beat_flag<V, ns6plan::G1, 4, 3, STEADY>(i, onset, nfr), live1 = beat_flag<V, ns6plan::G1, 12, 5, STEADY>(i, onset, nfr);
+                if (live0 || live1) {
+                    const int t0 = tick_of(f0, onset), slot = t0 & (kSlots1 - 1);
+                    constexpr int kF = sizeof(float);
+                    ns_fir_pair3(fp, window_base<kSlots>(t0) * kF, window_base<kSlots1>(tick_of(f1, onset)) * kF, (f0 & 1) * (int)sizeof(X->tap[0][0]),
+                                 slot * kSlotLen * kF, (f1 & 1) * (int)sizeof(RecOut), slot < 3 ? kCirc1 * kF : 0, live0, live1, lane);
+                }
+            } else if constexpr (IDCTS) {
                 /* the 17-tap filter of frame i-11, whose windowed taps S left at the previous iteration, ahead of the
                  * gains of frame i-9: the two do not depend on each other.  Also in the drain, where no gains are left. */
                 const int ff = i - 11;
@@ -892,12 +978,12 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             constexpr int kProd = sizeof(X->prod[0][0]), kTap = sizeof(X->tap[0][0]), kRowB = kIdctStride * sizeof(float), kTapB = kIdsTapStride * sizeof(float);
             ids.lds = lds;
             ids.rowZeros = at(X->zeros) - kIdctRow * (int)sizeof(float);
-            if (row) { /* stage 0: the records of parity p; stage 1: those of the other parity */
-                ids.src0 = (g == 0 ? at(X->prod[0][0]) : at(X->prod[1][1])) + kRowB * t;
-                ids.srcP = g == 0 ? kProd : -kProd;
+            if (row) { /* stage 0: the records of parity p; stage 1: those of the other parity (FIRP: frame i-11, the same parity as i-3) */
+                ids.src0 = (g == 0 ? at(X->prod[0][0]) : at(X->prod[1][FIRP ? 0 : 1])) + kRowB * t;
+                ids.srcP = (g == 0 || FIRP) ? kProd : -kProd;
                 ids.end = ids.rowZeros;
-                ids.tap0 = (g == 0 ? at(X->tap[0][0]) : at(X->tap[1][1])) + kTapB * t;
-                ids.tapP = g == 0 ? kTap : -kTap;
+                ids.tap0 = (g == 0 ? at(X->tap[0][0]) : at(X->tap[1][FIRP ? 0 : 1])) + kTapB * t;
+                ids.tapP = (g == 0 || FIRP) ? kTap : -kTap;
             } else {
                 ids.src0 = g == 0 ? at(L.ssq) : (g == 1 ? at(L.rd[0].den) : (g == 2 ? at(L.sdif) : at(L.rn[0].noise)));
                 ids.srcP = g == 1 ? (int)sizeof(RecDen) : 0;
@@ -921,7 +1007,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             const bool doVad = beat_flag<V, ns6plan::S, 1, 1, STEADY>(i, onset, nfr), doDen = beat_flag<V, ns6plan::S, 3, 3, STEADY>(i, onset, nfr),
                        doNz = beat_flag<V, ns6plan::S, 6 + kS1, 5, STEADY>(i, onset, nfr), produced = beat_flag<V, ns6plan::S, DEPTH, 5, STEADY>(i, onset, nfr);
             bool doIdct1 = false; /* IDCTS: the stage-1 IDCT sums of the frame G1 left its products of at i-1; the stage-0 sums go with doDen */
-            if constexpr (IDCTS) doIdct1 = beat_flag<V, ns6plan::S, 10, 5, STEADY>(i, onset, nfr);
+            if constexpr (IDCTS) doIdct1 = beat_flag<V, ns6plan::S, FIRP ? 11 : 10, 5, STEADY>(i, onset, nfr);
             const int tp = tick_of(fp, onset), td = tick_of(fd, onset);
             const float *denSrc = L.rd[(STEADY || (fd >= 0 && fd < nfr)) ? (fd & 1) : 0].den;
             const float *nzSrc = L.rn[fn & (kRnRing - 1)].noise;
@@ -955,7 +1041,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
                 if constexpr (IDCTS) {
                     /* the taps are stored whatever the flags say: a record whose frame does not exist is read by nobody (FA's and
                      * G1's flags are these flags one beat on), and its slot's previous content was read at the previous iteration */
-                    static_assert(((10 - 3) & 1) == 1, "S's two product records of a beat have opposite frame parities");
+                    static_assert((((FIRP ? 11 : 10) - 3) & 1) == (FIRP ? 0 : 1), "S's two product records of a beat have opposite frame parities; FIRP: the same");
                     ids.p = fd & 1;
                     ids.q = fn & (kRnRing - 1);
                     helper_chains<kSChunks, false, true, true>(L.ssq, denSrc, difS, L.sout, L.szero, vadSum, denTotal, y, lane, nullptr, nullptr,
@@ -967,7 +1053,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
                     const float en = (LIGHT || LOG_N1) ? vadSum : vad_frame_energy(vadSum); /* FA (LIGHT) or N1 takes the log one beat later */
                     if (lane == 0) L.frameEn[(tp + 2) & (kSlots - 1)] = en;
                 }
-                if (doDen && lane == 0) L.denSum[td & (kSlots - 1)] = denTotal;
+                if (doDen && lane == 0) denRing[td & (kDenRing - 1)] = denTotal;
                 if (doNz && lane == 0) L.nzSum[fn & 1] = nzTotal;
                 if (produced) {
                     vOut = dc_verify_take(difS, L.sout, dcY, y, lane); /* check + output in one batch of reads */
@@ -1037,7 +1123,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false, true, true, true, true, true>(a, L.base, &L.x);
+    p6::ns_pipe6_body<false, false, false, true, true, true, true, true, true>(a, L.base, &L.x);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif
