@@ -487,6 +487,24 @@ int sea_trainset_utterances(const short *const *clean, const long *lengths, int 
                             short *const *noisy, float *const *irm, short *const *noise_scaled, short *const *sub_clean,
                             short *const *sub_noise, short *const *sub_noisy);
 int sea_trainset_last_chunks(void);
+/* RECORDINGS, not utterances: how the reference's batch tool cuts a long recording for NoiseSup (BufferDenoise,
+ * function/20141106_speech_enhancement/aurora_speech_enhancement/aurora_speech_enhancement.cpp:25-80) and where the stitched
+ * result lies in the chunks' outputs (csrc/recording_plan.h).  Host arithmetic, no device needed.  The chunks
+ * are independent NoiseSup chains, each from a fresh state -- so their stitched result is NOT etsi_denoise's on the whole
+ * recording -- and can run as the utterances of one sea_denoise_utterances / sea_ns_denoise_batch call.
+ * chunk = B is a multiple of 80 and at least 320 (the tool's is 1 440 000, 3 minutes at 8 kHz); with T = S / B and R = S % B the
+ * chunks are x[0:S] when T = 0, else x[0:B], x[iB-320 : iB+B] for i = 1..T-1 and x[TB-320 : TB+R] (it exists when R = 0 too).
+ * sea_recording_plan returns their number (0 for a recording shorter than 320 samples, which the tool skips; -1 and
+ * sea_last_error () for a bad chunk) and fills, for the first max_chunks of them and where the pointer is given, chunk_src
+ * (first sample in the recording), chunk_len and chunk_off: the chunk's offset, a multiple of 8, in a LAYOUT that holds the
+ * chunks one after the other, each padded to 8 samples -- sea_recording_layout_samples () samples = S + 320 T and the pad. */
+long long sea_recording_plan(long samples, long chunk, long long *chunk_src, long long *chunk_len, long long *chunk_off,
+                             long long max_chunks);
+long long sea_recording_layout_samples(long samples, long chunk);
+/* The stitch: index[k], for t = first + k, is where des[t] lies in the chunks' etsi_denoise outputs laid out as above (zeroed
+ * first: etsi_denoise never writes a chunk's trailing len % 80 samples), or -1 where des[t] is 0 -- the last 320 samples.
+ * des[t] = out[chunk_off[i] + t + 320 + (i > 0 ? 320 : 0) - i B] with i = (t + 320) / B. */
+int sea_recording_stitch_map(long samples, long chunk, long first, long count, long long *index);
 /* The front half of the Hu-Wang mask estimator createIBM() (function/20141106_speech_enhancement/aurora_etsi_test/
  * HuWang.cpp:41-76) on its 25-channel 8 kHz gammatone bank: AudiPeriph (gammatone + Meddis hair cell, hOut in float), lowPass
  * (hEv), computeACF, crossCorr, globalPitch, timeCrn (corrHc) and the initial labelling of Grp (csrc/hw25_kernel.hip,

@@ -32,3 +32,4 @@ from .hw64 import (Hw64Result, hw64_correlogram_batch, hw64_frontend, hw64_front
                    hw64_pitch_batch, hw64_pitch_waves_per_utterance, Hw64AmResult, Hw64MaskResult, hw64_am_batch,
                    hw64_finalseg_batch, hw64_ibm, hw64_ibm_batch, hw64_enhance, hw64_enhance_plan, hw64_enhance_utterances,
                    hw64_resynth, hw64_resynth_tables, hw64_resynth_utterances)
+from .recordings import buffer_denoise, buffer_denoise_recordings, recording_plan, recording_stitch_map  # noqa: F401

@@ -85,6 +85,9 @@ PROTOTYPES = {
     "sea_trainset_batch": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "sea_trainset_utterances": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "sea_trainset_last_chunks": (_i, []),
+    "sea_recording_plan": (_ll, [_l, _l, _vp, _vp, _vp, _ll]),
+    "sea_recording_layout_samples": (_ll, [_l, _l]),
+    "sea_recording_stitch_map": (_i, [_l, _l, _l, _l, _vp]),
     "sea_hw25_tables_host": (_i, [_vp] * 9),
     "sea_hw25_frames": (_ll, [_ll]),
     "sea_hw25_scratch_bytes": (_ll, [_ll, _i]),
