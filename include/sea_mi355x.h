@@ -887,6 +887,63 @@ void etsi_denoise_mapping_thread_release(void **sm_thd_pins);
 void etsi_denoise_mapping_global_release(void **sm_glb_pins);
 
 /* ----------------------------------------------------------------------------------------------
+ * The DNN mask estimator: noisy audio -> 64 subband streams -> cochleagram -> feed-forward network -> mask rows ->
+ * resynthesis (csrc/dnn_kernel.hip, csrc/dnn_capi.hip).  Host pointers only.  Every operation is
+ * stated, and the plain-C model tests/dnn_model_driver.c reproduces every result bit for bit as values (-0 equals +0):
+ *
+ * Cochleagram: 20 ms frames every 10 ms on the int16 streams sea_subband64 writes.  For f < F = (L - 320) / 160 + 1 and c < 64:
+ * E = the sum of s_c[160 f + n]^2 over n < 320 as an exact integer, y = (float)(E + 1) (one round-to-nearest conversion),
+ * feats[f][c] = sea_lnf (y) of csrc/dnn_math.h (within 1 ulp of ln y; silence gives 0).  The rows are the mask rows of
+ * sea_resynth64 with binary bit 1 clear.
+ *
+ * Network: context C = 0..15, K0 = 64 (2 C + 1), 1..8 layers, every dimension 1..4096, dims[0] == K0.  Input row f of an
+ * utterance, for d = -C..C: x0[(d + C) 64 + c] = (feats[clamp (f + d, 0, F - 1)][c] + shift[k]) * scale[k], a float add, then a
+ * float multiply (Kaldi's Splice, AddShift, Rescale); the splice never crosses an utterance.  Layer l: acc = b[j], then for k
+ * ascending acc = fmaf (x[k], W[j][k], acc), W[l] row-major [out][in] as torch.nn.Linear.weight; then act[l]: 0 identity,
+ * 1 the sigmoid 1.0f / (1.0f + sea_expf (-z)) (sea_expf clamps its argument to +-88), 2 z > 0 ? z : 0.
+ *
+ * sea_dnn_create: copies the weights to the current device once; NULL (sea_last_error says why) for a context outside 0..15,
+ * dims[0] != K0, a dimension outside 1..4096, an unknown activation or a value of shift, scale, W or b that is not finite.
+ * The model is used on the device it was created on.
+ * sea_cochleagram64: sub64 [64][L] as sea_subband64 writes it -> feats [F][64]; L < 320 fails.
+ * sea_cochleagram_utterances: sea_subband64 and the cochleagram of every utterance of a list; feats[u] [F_u][64].
+ * sea_dnn_forward: feats[u] [n_rows[u]][64] -> out[u] [n_rows[u]][dims[n_layers]]; an utterance may have no row.
+ * sea_dnn_enhance_utterances: the whole chain for a list of 16 kHz int16 utterances, on the device on one stream: subbands,
+ * cochleagram, the layers, the fused resynthesis kernel with the network's output as its mask (so dims[n_layers] must be 64),
+ * int16 audio out [lengths[u]]; masks (NULL as a whole or per utterance: not wanted) receives the network's output
+ * [F_u][64].  binary: bit 0 as in sea_resynth64 (a unit is kept where its mask value passes the reference's threshold);
+ * bit 1 is refused, the cochleagram has (L - 320) / 160 + 1 rows.  Any utterance shorter than 320 samples makes the call
+ * return non-zero before the device is touched; no output is written.
+ * The three list calls run in chunks of whole utterances in list order, a chunk's device footprint held to 60 % of the HBM
+ * that is free (SEA_DNN_SCRATCH_MB overrides the budget; per padded sample 4 B of audio, 128 B of subbands and the
+ * resynthesis scratch, per row 256 B of features, 256 B of mask and two activation rows); sea_dnn_last_chunks: how many chunks
+ * the last such call of this thread ran.  Results do not depend on the cut.  There is no CPU fallback.
+ * sea_dnn_last_stage_ms: the device time in ms of a stage (SEA_DNN_STAGE_*) of this thread's last
+ * sea_dnn_enhance_utterances, between events on its stream, summed over the chunks; 0 for a layer the network does not have,
+ * -1 for an unknown stage.  For measurement (tools/bench_extra.py --what dnn).
+ * -------------------------------------------------------------------------------------------- */
+typedef struct sea_dnn sea_dnn;
+sea_dnn *sea_dnn_create(int context, const float *shift, const float *scale, int n_layers, const int *dims,
+                        const float *const *W, const float *const *b, const int *act);
+void sea_dnn_destroy(sea_dnn *m);
+int sea_cochleagram64(const short *sub64, long L, float *feats);
+int sea_cochleagram_utterances(const short *const *in, const long *lengths, int n_utt, float *const *feats);
+int sea_dnn_forward(const sea_dnn *m, const float *const *feats, const int *n_rows, int n_utt, float *const *out);
+int sea_dnn_enhance_utterances(const sea_dnn *m, const short *const *in, const long *lengths, int n_utt, int binary,
+                               short *const *out, float *const *masks);
+int sea_dnn_last_chunks(void);
+enum {
+    SEA_DNN_STAGE_SUBBAND = 0,
+    SEA_DNN_STAGE_COCHLEAGRAM = 1,
+    SEA_DNN_STAGE_SPLICE = 2,
+    SEA_DNN_STAGE_LAYER0 = 3, /* layer l is SEA_DNN_STAGE_LAYER0 + l, l < 8 */
+    SEA_DNN_STAGE_RESYNTH = 11,
+    SEA_DNN_STAGE_ALL = 12, /* from before the subbands to after the resynthesis */
+    SEA_DNN_STAGE_COUNT = 13
+};
+double sea_dnn_last_stage_ms(int stage);
+
+/* ----------------------------------------------------------------------------------------------
  * device self-tests of the places where a kernel takes a cheaper route than the reference's
  * literal arithmetic (each proven or guarded, see csrc/sea_device.h, csrc/ns_core.h and DESIGN.md section 3)
  * -------------------------------------------------------------------------------------------- */

@@ -139,6 +139,14 @@ PROTOTYPES = {
     "sea_hw64_enhance_plan": (_i, [_vp, _i, _ll, _i, _vp]),
     "sea_hw64_enhance_last_chunks": (_i, []),
     "sea_hw64_enhance_last_resynth_ms": (_c.c_double, []),
+    "sea_dnn_create": (_vp, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "sea_dnn_destroy": (None, [_vp]),
+    "sea_cochleagram64": (_i, [_vp, _l, _vp]),
+    "sea_cochleagram_utterances": (_i, [_vp, _vp, _i, _vp]),
+    "sea_dnn_forward": (_i, [_vp, _vp, _vp, _i, _vp]),
+    "sea_dnn_enhance_utterances": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "sea_dnn_last_chunks": (_i, []),
+    "sea_dnn_last_stage_ms": (_c.c_double, [_i]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -19,6 +19,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw64ibm --steps 3  # the same at 16 kHz on the 64-channel bank; also writes profiles/hw64ibm_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
     python tools/bench_extra.py --what hw64resynth --steps 3  # the same at 16 kHz on the 64-channel bank, through the host-list forms; also writes profiles/hw64resynth_bench_extra.jsonl, opt-in
+    python tools/bench_extra.py --what dnn --steps 5  # the DNN mask estimator: cochleagram, every layer (TFLOP/s), the chain, beside the resynthesis alone and hw64_enhance_utterances; also writes profiles/dnn_bench_extra.jsonl, opt-in
 """
 import argparse
 import json
@@ -1628,6 +1629,97 @@ def main():
               "config": {"workload": workload}, "chunks": chunks, "audio_and_mask_equal_the_single_stages": True,
               "mask_units": int(mask_h.sum()), "nonzero_output_samples": int(sum(int((a != 0).sum()) for a in audio))})
         with open(os.path.join(ROOT, "profiles", "hw64resynth_bench_extra.jsonl"), "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    if "dnn" in what:
+        # The DNN mask estimator on the --utts corpus batch taken as 16 kHz int16 utterances, with a seeded 704-1024-1024-1024-64
+        # sigmoid network (context 5), in one process.  The chain has no exported device-pointer call: it is reached through
+        # sea_dnn_enhance_utterances, which times its own stages with device events on its stream (sea_dnn_last_stage_ms):
+        # the cochleagram, the splice, every layer (2 M K N FLOP each -> TFLOP/s) and the chain from before the subbands to
+        # after the resynthesis; the host call's wall time (upload, launches, download) is given beside them.  On the same
+        # list: sea_resynth_utterances alone (with the chain's masks) and sea_hw64_enhance_utterances, wall time.  One warm-up
+        # discarded, median of --steps.  The yardstick for a layer is the 122 TFLOP/s of an untuned LDS-tiled GEMM on
+        # v_mfma_f32_32x32x2_f32 at 4096^3; this is a first form and there is no target.  The lines also go to
+        # profiles/dnn_bench_extra.jsonl.
+        import ctypes
+        lib = sea.load()
+        n = batch.n_utt
+        host = batch.data.cpu().numpy()
+        lengths = np.asarray(batch.host_lengths, dtype=np.int64)
+        xs = [np.ascontiguousarray(host[int(o):int(o) + int(L)]) for o, L in zip(batch.host_offsets, lengths)]
+        rows = (lengths - 320) // 160 + 1
+        n_rows, samples = int(rows.sum()), int(lengths.sum())
+        dims, context = [704, 1024, 1024, 1024, 64], 5
+        rng = np.random.default_rng(2025)
+        weights = [(rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])).astype(np.float32) for l in range(4)]
+        biases = [rng.uniform(-0.5, 0.5, size=dims[l + 1]).astype(np.float32) for l in range(4)]
+        model = sea.DnnMask(context, np.full(704, -10.0, np.float32), np.full(704, 0.1, np.float32), weights, biases, [1, 1, 1, 1])
+        ptrs = lambda arrs: (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs]) if arrs is not None else None
+        lens = (ctypes.c_long * n)(*[int(L) for L in lengths])
+        out = [np.zeros(int(L), np.int16) for L in lengths]
+        out2 = [np.zeros(int(L), np.int16) for L in lengths]
+        masks = [np.zeros((int(r), 64), np.float32) for r in rows]
+        workload = (f"the {args.utts}-utterance corpus as 16 kHz int16 utterances: {samples} samples, {n_rows} rows; network "
+                    f"{'-'.join(map(str, dims))}, sigmoid, context {context}; median of {args.steps} calls after one warm-up")
+        lines = []
+
+        def emit(record):
+            lines.append(json.dumps(record))
+            print(lines[-1], flush=True)
+
+        STAGES = {"subbands": 0, "cochleagram": 1, "splice": 2, "layer 0": 3, "layer 1": 4, "layer 2": 5, "layer 3": 6, "resynthesis": 11,
+                  "chain": 12}
+        stage_ms = {k: [] for k in STAGES}
+        wall_ms = []
+        for i in range(args.steps + 1):
+            t0 = time.perf_counter()
+            assert lib.sea_dnn_enhance_utterances(model._handle, ptrs(xs), lens, n, 0, ptrs(out), ptrs(masks)) == 0, lib.sea_last_error()
+            if i:
+                wall_ms.append((time.perf_counter() - t0) * 1e3)
+                for k, st in STAGES.items():
+                    stage_ms[k].append(float(lib.sea_dnn_last_stage_ms(st)))
+        chunks = int(lib.sea_dnn_last_chunks())
+        med = lambda t: sorted(t)[len(t) // 2]
+        for k in STAGES:
+            t = sorted(stage_ms[k])
+            rec = {"metric": f"DNN mask estimator: {k}, device events inside sea_dnn_enhance_utterances (ms); a first form, not tuned",
+                   "value": med(t), "unit": "ms", "config": {"workload": workload, "ms_sorted": [round(v, 3) for v in t]}, "chunks": chunks}
+            if k.startswith("layer"):
+                l = int(k.split()[1])
+                flop = 2.0 * n_rows * dims[l] * dims[l + 1]
+                rec.update(tflops=flop / (med(t) / 1e3) / 1e12, flop=flop, yardstick_tflops=122.0, kernels="sea::dnn_layer_kernel",
+                           shape=f"M={n_rows} K={dims[l]} N={dims[l + 1]}")
+            if k == "chain":
+                rec.update(x_realtime_16k=samples / 16000.0 / (med(t) / 1e3),
+                           layers_tflops=sum(2.0 * n_rows * dims[l] * dims[l + 1] for l in range(4)) / (sum(med(stage_ms[f"layer {l}"]) for l in range(4)) / 1e3) / 1e12)
+            emit(rec)
+        emit({"metric": "DNN mask estimator: sea_dnn_enhance_utterances end to end from host memory, wall time (ms)", "value": med(wall_ms),
+              "unit": "ms", "x_realtime_16k": samples / 16000.0 / (med(wall_ms) / 1e3),
+              "config": {"workload": workload, "ms_sorted": [round(v, 1) for v in sorted(wall_ms)]}, "chunks": chunks})
+
+        def host_wall(fn):
+            t = []
+            for i in range(args.steps + 1):
+                t0 = time.perf_counter()
+                assert fn() == 0, lib.sea_last_error()
+                if i:
+                    t.append((time.perf_counter() - t0) * 1e3)
+            return sorted(t)
+        t = host_wall(lambda: lib.sea_resynth_utterances(ptrs(xs), lens, ptrs(masks), 0, ptrs(out2), n))
+        assert all(np.array_equal(a, b) for a, b in zip(out, out2)), "the chain's audio is not the resynthesis of its masks"
+        emit({"metric": "sea_resynth_utterances alone on the same list with the chain's masks, wall time (ms)", "value": med(t), "unit": "ms",
+              "config": {"workload": workload, "ms_sorted": [round(v, 1) for v in t]}, "audio_equals_the_chain": True})
+        xf = [x.astype(np.float32) for x in xs]
+        audio = [np.zeros(int(L), np.float32) for L in lengths]
+        m2 = [np.zeros((int(L) // 160, 64), np.float32) for L in lengths]
+        p2 = [np.zeros(int(L) // 160, np.int32) for L in lengths]
+        status2 = np.zeros(n, np.int32)
+        t = host_wall(lambda: lib.sea_hw64_enhance_utterances(ptrs(xf), lens, n, ptrs(audio), None, ptrs(m2), ptrs(p2),
+                                                              status2.ctypes.data_as(ctypes.c_void_p)))
+        emit({"metric": "sea_hw64_enhance_utterances (the Hu-Wang estimator and its resynthesis) on the same list, wall time (ms)",
+              "value": med(t), "unit": "ms", "config": {"workload": workload, "ms_sorted": [round(v, 1) for v in t]},
+              "chunks": int(lib.sea_hw64_enhance_last_chunks())})
+        with open(os.path.join(ROOT, "profiles", "dnn_bench_extra.jsonl"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
 
     if "rfft" in what:
