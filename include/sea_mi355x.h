@@ -944,6 +944,64 @@ enum {
 double sea_dnn_last_stage_ms(int stage);
 
 /* ----------------------------------------------------------------------------------------------
+ * Training that network: minibatch SGD with momentum on Kaldi nnet1's MSE, 1/2 sum e^2 (csrc/dnn_train_kernel.hip,
+ * csrc/dnn_train_capi.hip).  Host pointers only, one internal stream.  The plain-C model
+ * tests/dnn_train_model_driver.c reproduces every value bit for bit (-0 equals +0).  All operations are float, individually
+ * rounded, never contracted; every chain starts from +0.  One step on the rows idx[0 .. B - 1] of the training set, 1 <= B <= 4096:
+ *   x0[m] = the network's input row of global row idx[m] (the splice is clamped to that row's utterance); a_0 = x0 and
+ *   a_l = layer l of the inference contract above, every a_l kept
+ *   e = a_n - t[idx[m]];  r[m]: acc = fmaf (e[m][j], e[m][j], acc), j ascending;  p[l] = sum over i ascending of (double) r[64 i + l],
+ *   loss = 0.5 * sum over l = 0..63 ascending of p[l], in double
+ *   delta_n = e d(a_n);  d: sigmoid a * (1 - a) (a subtract, a multiply) and delta = e * d (one more multiply); ReLU
+ *   delta = a > 0 ? e : 0; identity delta = e
+ *   G_l[j][k]: acc = fmaf (delta_l[m][j], a_(l-1)[m][k], acc), m ascending 0 .. B - 1, one chain
+ *   g_l[j]: acc = acc + delta_l[m][j], m ascending
+ *   for l = n .. 2: E[m][k]: acc = fmaf (delta_l[m][j], W_l[j][k], acc), j ascending, W as before this step's update;
+ *   delta_(l-1) = E d(a_(l-1)) by the rules above
+ *   every weight and bias: v = mu * v + g (a multiply, an add), w = w - eta * v (a multiply, a subtract)
+ * eta multiplies the gradient SUMMED over the minibatch, as in nnet1: a rate lr meant for the mean gradient is eta = lr / B.
+ * The update is in place in the sea_dnn's device storage (its tile padding is never written), so the handle serves
+ * sea_dnn_forward and sea_dnn_enhance_utterances at once.  What happens once a value stops being finite is not pinned.
+ *
+ * sea_dnn_trainer_create: uploads the training set once (feats[u] [n_rows[u]][64], targets[u] [n_rows[u]][dims[n_layers]]),
+ * allocates the step's buffers for minibatches of at most max_batch rows and zeroes the momentum.  NULL (sea_last_error says
+ * why) for a null argument, max_batch outside 1..4096, n_utt < 1, a negative n_rows[u] or no row at all -- all before the
+ * device is touched -- and for a set that does not fit 60 % of the free device memory.  The model must outlive the trainer.
+ * sea_dnn_trainer_run: cuts order[0 .. n_order - 1] (global rows, any length, repeats allowed) into consecutive minibatches of
+ * `batch` rows, the last one shorter, runs the steps back to back and writes losses[ceil (n_order / batch)].  update = 0 is
+ * evaluation: forward and loss only, no state touched.  Returns 0; 2 if any step's loss is not finite; 1, before the device is
+ * touched, for a null argument, batch outside 1..4096 or above max_batch, n_order < 1, an index outside the set, eta not finite
+ * or mu not in [0, 1) (the checks that need only the arguments come before any use of the trainer).
+ * sea_dnn_trainer_read: the last step's values, what = SEA_DNN_TRAIN_*: ACT a_layer [B][dims[layer]], layer 0..n (B the last
+ * step's rows); DELTA delta_layer [B][dims[layer]], WGRAD G_layer [dims[layer]][dims[layer - 1]], BGRAD g_layer, WMOM / BMOM the
+ * momentum of W_layer / b_layer, layer 1..n.  After an evaluation only ACT is of that step.  An unknown what or layer is refused.
+ * sea_dnn_get_params: the model's weights as dense [out][in] arrays and its biases, from the device.
+ * sea_dnn_trainer_stage_ms: the device time in ms of a stage (SEA_DNN_TRAIN_STAGE_*) of the last step of the last run, between
+ * events on the trainer's stream; 0 for a stage that step did not have, -1 for an unknown stage.  For measurement.
+ * -------------------------------------------------------------------------------------------- */
+typedef struct sea_dnn_trainer sea_dnn_trainer;
+enum { SEA_DNN_TRAIN_ACT = 0, SEA_DNN_TRAIN_DELTA = 1, SEA_DNN_TRAIN_WGRAD = 2, SEA_DNN_TRAIN_BGRAD = 3, SEA_DNN_TRAIN_WMOM = 4,
+       SEA_DNN_TRAIN_BMOM = 5 };
+enum {
+    SEA_DNN_TRAIN_STAGE_GATHER = 0,
+    SEA_DNN_TRAIN_STAGE_FORWARD0 = 1, /* layer l (1..n) is SEA_DNN_TRAIN_STAGE_FORWARD0 + l - 1 */
+    SEA_DNN_TRAIN_STAGE_DELTA = 9,    /* the output delta and the loss */
+    SEA_DNN_TRAIN_STAGE_DGRAD0 = 10,  /* delta_l -> delta_(l-1), l = 2..n, is SEA_DNN_TRAIN_STAGE_DGRAD0 + l - 1 */
+    SEA_DNN_TRAIN_STAGE_WGRAD0 = 18,  /* G_l and g_l, l = 1..n, is SEA_DNN_TRAIN_STAGE_WGRAD0 + l - 1 */
+    SEA_DNN_TRAIN_STAGE_UPDATE = 26,
+    SEA_DNN_TRAIN_STAGE_ALL = 27,
+    SEA_DNN_TRAIN_STAGE_COUNT = 28
+};
+sea_dnn_trainer *sea_dnn_trainer_create(sea_dnn *m, const float *const *feats, const float *const *targets, const int *n_rows,
+                                        int n_utt, int max_batch);
+void sea_dnn_trainer_destroy(sea_dnn_trainer *t);
+int sea_dnn_trainer_run(sea_dnn_trainer *t, const long long *order, long long n_order, int batch, float eta, float mu, int update,
+                        double *losses);
+int sea_dnn_trainer_read(const sea_dnn_trainer *t, int what, int layer, float *out);
+int sea_dnn_get_params(const sea_dnn *m, float *const *weights, float *const *biases);
+double sea_dnn_trainer_stage_ms(const sea_dnn_trainer *t, int stage);
+
+/* ----------------------------------------------------------------------------------------------
  * device self-tests of the places where a kernel takes a cheaper route than the reference's
  * literal arithmetic (each proven or guarded, see csrc/sea_device.h, csrc/ns_core.h and DESIGN.md section 3)
  * -------------------------------------------------------------------------------------------- */

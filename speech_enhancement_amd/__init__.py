@@ -7,7 +7,7 @@ Only what that path needs lives here:
   csrc/       HIP kernels, host table builder, the C ABI (libsea_mi355x.so, built in-tree)
   engine.py   host-side mirror of the reference interface + batched HBM-resident forms
   hw25.py     the same for the Hu-Wang mask estimator and its resynthesis on the 25-channel bank
-  dnn.py      the DNN mask estimator: cochleagram, feed-forward network, the chain from noisy to enhanced audio
+  dnn.py      the DNN mask estimator: cochleagram, feed-forward network, its trainer, the chain from noisy to enhanced audio
   corpus.py   the deterministic synthetic corpus the measurements run on
   shard.py    utterance sharding over the GPUs of a node (LPT / blocks) and the two-scalar job reduction
   host/       plain-C drivers with the reference's command lines (cfg -> list -> WAV in / WAV out) and the
@@ -33,6 +33,6 @@ from .hw64 import (Hw64Result, hw64_correlogram_batch, hw64_frontend, hw64_front
                    hw64_pitch_batch, hw64_pitch_waves_per_utterance, Hw64AmResult, Hw64MaskResult, hw64_am_batch,
                    hw64_finalseg_batch, hw64_ibm, hw64_ibm_batch, hw64_enhance, hw64_enhance_plan, hw64_enhance_utterances,
                    hw64_resynth, hw64_resynth_tables, hw64_resynth_utterances)
-from .dnn import (DnnMask, cochleagram, cochleagram_utterances, dnn_enhance_utterances, dnn_forward, dnn_last_chunks,  # noqa: F401
-                  dnn_rows)
+from .dnn import (DnnMask, DnnTrainer, cochleagram, cochleagram_utterances, dnn_enhance_utterances, dnn_forward,  # noqa: F401
+                  dnn_last_chunks, dnn_rows)
 from .recordings import buffer_denoise, buffer_denoise_recordings, recording_plan, recording_stitch_map  # noqa: F401

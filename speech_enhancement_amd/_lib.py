@@ -147,6 +147,12 @@ PROTOTYPES = {
     "sea_dnn_enhance_utterances": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "sea_dnn_last_chunks": (_i, []),
     "sea_dnn_last_stage_ms": (_c.c_double, [_i]),
+    "sea_dnn_trainer_create": (_vp, [_vp, _vp, _vp, _vp, _i, _i]),
+    "sea_dnn_trainer_destroy": (None, [_vp]),
+    "sea_dnn_trainer_run": (_i, [_vp, _vp, _ll, _i, _c.c_float, _c.c_float, _i, _vp]),
+    "sea_dnn_trainer_read": (_i, [_vp, _i, _i, _vp]),
+    "sea_dnn_get_params": (_i, [_vp, _vp, _vp]),
+    "sea_dnn_trainer_stage_ms": (_c.c_double, [_vp, _i]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -2,7 +2,9 @@
 16 kHz audio -> 64 subband streams -> cochleagram -> feed-forward network -> mask rows -> resynthesis, the reference's headline
 workflow with its network and features on the GPU.
 
-  DnnMask                  the network: context, shift, scale, weights, biases, activations; from_torch, load, save
+  DnnMask                  the network: context, shift, scale, weights, biases, activations; from_torch, load, save; normaliser
+                           (shift and scale from training features), pull (the trained weights back from the device)
+  DnnTrainer               minibatch SGD with momentum on the device, in place in a DnnMask's weights
   cochleagram(sub64)       one utterance's [64][L] subband streams -> [F][64] features, F = (L - 320) // 160 + 1
   cochleagram_utterances   subbands + cochleagram for a list of int16 utterances (with make_trainset's `noisy` outputs these
                            are the training set's inputs; its `irm` outputs are the targets, row for row)
@@ -109,6 +111,28 @@ class DnnMask:
                 raise TypeError(f"DnnMask.from_torch: {type(layer).__name__} is not Linear, Sigmoid or ReLU")
         return cls(context, shift, scale, weights, biases, acts)
 
+    def pull(self):
+        """Refresh weights and biases from the device (a DnnTrainer updates them there), so that save() writes the trained
+        network.  The arrays are new ones: the constructor may have kept the caller's own."""
+        weights, biases = [np.zeros_like(w) for w in self.weights], [np.zeros_like(b) for b in self.biases]
+        _lib.check(_lib.load().sea_dnn_get_params(self._handle, _ptr_array(weights), _ptr_array(biases)), "sea_dnn_get_params")
+        self.weights, self.biases = weights, biases
+        return self
+
+    @staticmethod
+    def normaliser(feats_list, context):
+        """(shift, scale) for the constructor from training features [F_u][64]: per channel c the mean and the standard
+        deviation over all rows in float64, shift[k] = -mean[k & 63], scale[k] = 1 / std[k & 63], rounded to float32 once.  A
+        channel that does not vary is refused."""
+        rows = np.concatenate([np.asarray(f, dtype=np.float64).reshape(-1, DNN_NCHAN) for f in feats_list], axis=0)
+        if rows.shape[0] == 0:
+            raise ValueError("DnnMask.normaliser: no feature row")
+        mean, std = rows.mean(axis=0), rows.std(axis=0)
+        if not np.all(np.isfinite(mean)) or not np.all(std > 0):
+            raise ValueError(f"DnnMask.normaliser: channel {int(np.argmin(std > 0))} does not vary (or a feature is not finite)")
+        reps = 2 * int(context) + 1
+        return np.tile(-mean, reps).astype(np.float32), np.tile(1.0 / std, reps).astype(np.float32)
+
     def save(self, path):
         arrays = dict(context=np.int32(self.context), shift=self.shift, scale=self.scale, acts=np.asarray(self.acts, np.int32))
         for l, (w, b) in enumerate(zip(self.weights, self.biases)):
@@ -122,6 +146,84 @@ class DnnMask:
             n = len(z["acts"])
             return cls(int(z["context"]), z["shift"], z["scale"], [z[f"W{l}"] for l in range(n)], [z[f"b{l}"] for l in range(n)],
                        [int(a) for a in z["acts"]])
+
+
+class DnnTrainer:
+    """Minibatch SGD with momentum on 1/2 sum (y - t)^2 (Kaldi nnet1's MSE), on the device, in place in `model`'s weights: the
+    model serves dnn_forward and dnn_enhance_utterances between and after runs, and model.pull() fetches the weights.
+    feats_list[u] [F_u][64] (cochleagram_utterances of make_trainset's `noisy`), targets_list[u] [F_u][model.n_out] (its `irm`).
+    The whole set is uploaded once.  lr multiplies the gradient SUMMED over the minibatch, as in nnet1: a rate meant for the mean
+    gradient is lr / batch.  Every value is pinned bit for bit by tests/dnn_train_model_driver.c."""
+
+    WHAT = {"act": 0, "delta": 1, "wgrad": 2, "bgrad": 3, "wmom": 4, "bmom": 5}
+
+    def __init__(self, model, feats_list, targets_list, max_batch=1024):
+        self._handle = None
+        self.model = model
+        feats = [np.ascontiguousarray(f, dtype=np.float32).reshape(-1, DNN_NCHAN) for f in feats_list]
+        targets = [np.ascontiguousarray(t, dtype=np.float32).reshape(-1, model.n_out) for t in targets_list]
+        if len(feats) != len(targets) or any(f.shape[0] != t.shape[0] for f, t in zip(feats, targets)):
+            raise ValueError("DnnTrainer: one target row per feature row, utterance by utterance")
+        self.total_rows = int(sum(f.shape[0] for f in feats))
+        self.max_batch = int(max_batch)
+        self.last_batch = 0
+        n_rows = (ctypes.c_int * max(len(feats), 1))(*[f.shape[0] for f in feats])
+        handle = _lib.load().sea_dnn_trainer_create(model._handle, _ptr_array(feats), _ptr_array(targets), n_rows, len(feats),
+                                                    self.max_batch)
+        if not handle:
+            _lib.check(1, "sea_dnn_trainer_create")
+        self._handle = handle
+
+    def close(self):
+        if self._handle:
+            _lib.load().sea_dnn_trainer_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run(self, order, batch, lr, momentum=0.0, update=True):
+        """Steps over consecutive minibatches of `batch` rows of `order` (global rows; the last minibatch may be shorter) ->
+        the loss of every step, float64.  update=False: forward and loss only.  A loss that is not finite raises."""
+        order = np.ascontiguousarray(order, dtype=np.int64).reshape(-1)
+        batch = int(batch)
+        losses = np.zeros((order.size + batch - 1) // batch if batch > 0 else 0, np.float64)
+        rc = _lib.load().sea_dnn_trainer_run(self._handle, _np_ptr(order), order.size, batch, float(lr), float(momentum),
+                                             int(bool(update)), _np_ptr(losses))
+        _lib.check(rc, "sea_dnn_trainer_run")
+        self.last_batch = order.size - (losses.size - 1) * batch
+        return losses
+
+    def epoch(self, seed, batch, lr, momentum=0.0):
+        """One pass over the set in the order np.random.default_rng(seed).permutation(total_rows)."""
+        return self.run(np.random.default_rng(seed).permutation(self.total_rows), batch, lr, momentum)
+
+    def evaluate(self, batch=None):
+        """The summed loss over all rows in natural order, nothing updated (a cross-validation pass)."""
+        batch = self.max_batch if batch is None else batch
+        return float(self.run(np.arange(self.total_rows), batch, 0.0, 0.0, update=False).sum())
+
+    def read(self, what, layer):
+        """The last step's values: "act" a_layer [B][dims[layer]] (layer 0..n), "delta" [B][dims[layer]], "wgrad"
+        [dims[layer]][dims[layer - 1]], "bgrad", "wmom", "bmom" (layer 1..n)."""
+        code = self.WHAT[what] if isinstance(what, str) else int(what)
+        lib = _lib.load()
+        dims, layer = self.model.dims, int(layer)
+        if not (0 <= code <= 5) or not ((0 if code == 0 else 1) <= layer < len(dims)):
+            _lib.check(lib.sea_dnn_trainer_read(self._handle, code, layer, _np_ptr(np.zeros(1, np.float32))), "sea_dnn_trainer_read")
+            raise ValueError(f"DnnTrainer.read: what {what!r}, layer {layer}")
+        last = self.last_batch
+        shape = (last, dims[layer]) if code < 2 else (dims[layer], dims[layer - 1]) if code in (2, 4) else (dims[layer],)
+        out = np.zeros(shape, np.float32)
+        _lib.check(lib.sea_dnn_trainer_read(self._handle, code, layer, _np_ptr(out)), "sea_dnn_trainer_read")
+        return out
+
+    def stage_ms(self, stage):
+        """device time in ms of a stage (SEA_DNN_TRAIN_STAGE_* of the header) of the last step of the last run"""
+        return float(_lib.load().sea_dnn_trainer_stage_ms(self._handle, int(stage)))
 
 
 def cochleagram(sub64):

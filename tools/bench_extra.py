@@ -20,6 +20,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw25resynth --steps 3  # its resynthesis alone and audio in / enhanced audio out, beside the estimator and the periphery, opt-in
     python tools/bench_extra.py --what hw64resynth --steps 3  # the same at 16 kHz on the 64-channel bank, through the host-list forms; also writes profiles/hw64resynth_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what dnn --steps 5  # the DNN mask estimator: cochleagram, every layer (TFLOP/s), the chain, beside the resynthesis alone and hw64_enhance_utterances; also writes profiles/dnn_bench_extra.jsonl, opt-in
+    python tools/bench_extra.py --what dnntrain  # its trainer: 200 SGD steps at minibatch 256, 1024 and 4096, every stage (TFLOP/s per GEMM beside the forward layer at the same M), steps/s, an epoch's time; also writes profiles/dnntrain_bench_extra.jsonl, opt-in
 """
 import argparse
 import json
@@ -1720,6 +1721,72 @@ def main():
               "value": med(t), "unit": "ms", "config": {"workload": workload, "ms_sorted": [round(v, 1) for v in t]},
               "chunks": int(lib.sea_hw64_enhance_last_chunks())})
         with open(os.path.join(ROOT, "profiles", "dnn_bench_extra.jsonl"), "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    if "dnntrain" in what:
+        # The DNN mask estimator's trainer: the seeded 704-1024-1024-1024-64 sigmoid network (context 5)
+        # on synthetic feature and target rows of the --utts corpus's row count, resident on the device.  Per minibatch size
+        # (256, 1024, 4096): one warm-up run, then 5 runs of 200 steps over a seeded order; a run's wall time (the call
+        # synchronises its stream) gives steps/s, rows/s and the time of an epoch over the rows; the device time of every stage
+        # of a run's last step comes from events on the trainer's stream (sea_dnn_trainer_stage_ms).  Median of the 5 runs, the
+        # sorted values beside it.  There is no target: the yardstick written beside each gradient GEMM is the unchanged forward
+        # dnn_layer_kernel of the same layer at the same M in the same process (same FLOP count).  The lines also go to
+        # profiles/dnntrain_bench_extra.jsonl.
+        lengths = np.asarray(batch.host_lengths, dtype=np.int64)
+        rows = (lengths - 320) // 160 + 1
+        n_rows = int(rows.sum())
+        dims, context, n_steps, runs = [704, 1024, 1024, 1024, 64], 5, 200, 5
+        rng = np.random.default_rng(2025)
+        weights = [(rng.standard_normal((dims[l + 1], dims[l])) / np.sqrt(dims[l])).astype(np.float32) for l in range(4)]
+        biases = [rng.uniform(-0.5, 0.5, size=dims[l + 1]).astype(np.float32) for l in range(4)]
+        feats = [rng.uniform(0, 27, size=(int(r), 64)).astype(np.float32) for r in rows]
+        targets = [rng.uniform(0, 1, size=(int(r), 64)).astype(np.float32) for r in rows]
+        shift, scale = sea.DnnMask.normaliser(feats, context)
+        model = sea.DnnMask(context, shift, scale, weights, biases, [1, 1, 1, 1])
+        trainer = sea.DnnTrainer(model, feats, targets, max_batch=4096)
+        med = lambda t: sorted(t)[len(t) // 2]
+        lines = []
+
+        def emit(record):
+            lines.append(json.dumps(record))
+            print(lines[-1], flush=True)
+
+        STAGES = [("gather", 0)] + [(f"forward layer {l}", l) for l in (1, 2, 3, 4)] + [("delta and loss", 9)]
+        STAGES += [(f"dgrad layer {l}", 10 + l - 1) for l in (4, 3, 2)] + [(f"wgrad layer {l}", 18 + l - 1) for l in (4, 3, 2, 1)]
+        STAGES += [("update", 26), ("step", 27)]
+        for B in (256, 1024, 4096):
+            workload = (f"{n_rows} synthetic rows ({args.utts} utterances), network {'-'.join(map(str, dims))}, sigmoid, context {context}; "
+                        f"minibatch {B}, {n_steps} steps per run, mu 0.9; median of {runs} runs after one warm-up run")
+            order = np.random.default_rng(B).integers(0, n_rows, size=n_steps * B)
+            stage_ms, wall_s = {k: [] for k, _ in STAGES}, []
+            for i in range(runs + 1):
+                t0 = time.perf_counter()
+                losses = trainer.run(order, B, 1e-3 / B, 0.9)
+                if i:
+                    wall_s.append(time.perf_counter() - t0)
+                    for k, st in STAGES:
+                        stage_ms[k].append(trainer.stage_ms(st))
+            assert np.all(np.isfinite(losses))
+            fwd = {l: 2.0 * B * dims[l - 1] * dims[l] / (med(stage_ms[f"forward layer {l}"]) / 1e3) / 1e12 for l in (1, 2, 3, 4)}
+            for k, _ in STAGES:
+                t = sorted(stage_ms[k])
+                rec = {"metric": f"DNN trainer, minibatch {B}: {k}, device events on the last step of a run (ms); a first form, not tuned",
+                       "value": med(t), "unit": "ms", "config": {"workload": workload, "ms_sorted": [round(v, 4) for v in t]}}
+                if "layer" in k:
+                    l = int(k.split()[-1])
+                    flop = 2.0 * B * dims[l - 1] * dims[l]
+                    rec.update(tflops=flop / (med(t) / 1e3) / 1e12, flop=flop, shape=f"B={B} K={dims[l - 1]} N={dims[l]}",
+                               yardstick_forward_dnn_layer_kernel_same_M_tflops=fwd[l],
+                               kernels="sea::dnn_layer_kernel" if k.startswith("forward") else
+                               "sea::dnn_dgrad_kernel" if k.startswith("dgrad") else "sea::dnn_wgrad_kernel (with the bias gradient)")
+                emit(rec)
+            w = sorted(wall_s)
+            emit({"metric": f"DNN trainer, minibatch {B}: steps/s over a run of {n_steps} steps, wall time of sea_dnn_trainer_run",
+                  "value": n_steps / med(w), "unit": "steps/s", "rows_per_s": n_steps * B / med(w),
+                  "epoch_s": n_rows / (n_steps * B / med(w)), "epoch_rows": n_rows, "loss_first": float(losses[0]), "loss_last": float(losses[-1]),
+                  "config": {"workload": workload, "run_s_sorted": [round(v, 4) for v in w]}})
+        trainer.close()
+        with open(os.path.join(ROOT, "profiles", "dnntrain_bench_extra.jsonl"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
 
     if "rfft" in what:
