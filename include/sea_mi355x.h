@@ -907,7 +907,11 @@ void etsi_denoise_mapping_global_release(void **sm_glb_pins);
  * The model is used on the device it was created on.
  * sea_cochleagram64: sub64 [64][L] as sea_subband64 writes it -> feats [F][64]; L < 320 fails.
  * sea_cochleagram_utterances: sea_subband64 and the cochleagram of every utterance of a list; feats[u] [F_u][64].
- * sea_dnn_forward: feats[u] [n_rows[u]][64] -> out[u] [n_rows[u]][dims[n_layers]]; an utterance may have no row.
+ * sea_dnn_forward: feats[u] [n_rows[u]][64] -> out[u] [n_rows[u]][dims[n_layers]]; an utterance may have no row (its
+ * pointers may be NULL, its output is not touched).  Features that are not finite are accepted: the operations above are
+ * IEEE's on them too (a NaN through the rectifier is 0, through the sigmoid a NaN), such a value reaches the 2 C + 1 rows
+ * around it within its utterance and no other row, and the C model gives the same class value for value (a NaN where a NaN
+ * is, payload and sign free; otherwise the same value).
  * sea_dnn_enhance_utterances: the whole chain for a list of 16 kHz int16 utterances, on the device on one stream: subbands,
  * cochleagram, the layers, the fused resynthesis kernel with the network's output as its mask (so dims[n_layers] must be 64),
  * int16 audio out [lengths[u]]; masks (NULL as a whole or per utterance: not wanted) receives the network's output

@@ -1,5 +1,6 @@
-"""Test infrastructure: the launch caps of the grid-stride kernels, read from speech_enhancement_amd/csrc/capi.hip, and the
-arithmetic that says how many trips of its loop a workgroup takes on a given input.
+"""Test infrastructure: the launch caps of the grid-stride kernels, read from speech_enhancement_amd/csrc/capi.hip (and, for
+the trainer's dnn_sgd_kernel, from dnn_train_capi.hip), and the arithmetic that says how many trips of its loop a workgroup
+takes on a given input.
 
 Most kernels outside the NoiseSup frame loop are launched with a capped grid and walk their work in a grid-stride loop; a
 test only reaches a loop's second trip when its input is larger than the cap.  The caps are constants of the launch code, so
@@ -13,6 +14,8 @@ tests take their sizes from the helpers below with the device's CU count.
     sea_wb_compceps_batch, sea_*compceps_batch_slice   the same                            min (nslot, 16384)
     sea_*afe_features_batch and their _slice forms     nslot = total / 8 + n_utt           min (nslot, kAfeGrid)
     sea_hw25_correlogram_batch                    the frames of one utterance              per_utt = ceil (8 n_cu / n_utt), 1..1024
+    sea_dnn_trainer_run (dnn_sgd_kernel, one      npiece = ceil ((N K + N) / 256)          min (npiece, 4096)
+      launch per layer; dnn_train_capi.hip)       (256 entries of W, then b, per piece)
 
 Workgroup b of a grid of G takes the items b, b + G, ...: ceil ((work - b) / G) trips.  In the slot kernels utterance u owns
 the slots [cum[u] / T + u, cum[u + 1] / T + u + 1) and slot k of an utterance holds its rows kT .. kT + T - 1; a slot past
@@ -77,6 +80,58 @@ def trips(items, grid):
     items = np.arange(int(items), dtype=np.int64) if np.isscalar(items) else np.asarray(items, dtype=np.int64)
     per = np.bincount(items % grid, minlength=1) if items.size else np.zeros(1, np.int64)
     return Trips(int(grid), int(items.size), int(per.max()), int((per >= 2).sum()), int((per >= 3).sum()))
+
+
+# ---- dnn_sgd_kernel (dnn_train_capi.hip, dnn_train_kernel.hip) ----
+DNN_TRAIN_CAPI = os.path.join(os.path.dirname(CAPI), "dnn_train_capi.hip")
+DNN_TRAIN_KERNEL = os.path.join(os.path.dirname(CAPI), "dnn_train_kernel.hip")
+
+SgdCap = collections.namedtuple("SgdCap", "threads grid")
+
+
+def parse_sgd(capi_text=None, kernel_text=None):
+    """the cap of dnn_sgd_kernel's launch -- std::min<long long>((total + 255) / 256, 4096) workgroups of 256 over
+    total = N K + N entries -- from dnn_train_capi.hip's text, and the kernel's own stride from dnn_train_kernel.hip's;
+    LookupError names what is not where it was"""
+    if capi_text is None:
+        with open(DNN_TRAIN_CAPI) as f:
+            capi_text = f.read()
+    if kernel_text is None:
+        with open(DNN_TRAIN_KERNEL) as f:
+            kernel_text = f.read()
+
+    def one(pattern, text, what, where):
+        found = re.findall(pattern, text)
+        if len(found) != 1:
+            raise LookupError(f"{what}: expected 1 match of /{pattern}/ in {where}, found {len(found)}")
+        return found[0]
+
+    one(r"const long long total = \(long long\)sa\.N \* sa\.K \+ sa\.N;", capi_text, "the entry count `total` of dnn_sgd_kernel's launch",
+        "dnn_train_capi.hip")
+    round_up, per, grid, threads = one(r"hipLaunchKernelGGL\(sea::dnn_sgd_kernel, dim3\(\(unsigned\)std::min<long long>\(\(total \+ (\d+)\) / (\d+), (\d+)\)\), "
+                                       r"dim3\((\d+)\)", capi_text, "the launch cap of dnn_sgd_kernel (std::min<long long>((total + 255) / 256, 4096))",
+                                       "dnn_train_capi.hip")
+    first, stride = one(r"for \(long long i = \(long long\)blockIdx\.x \* (\d+) \+ threadIdx\.x; i < total; i \+= \(long long\)gridDim\.x \* (\d+)\)",
+                        kernel_text, "the grid-stride loop of dnn_sgd_kernel", "dnn_train_kernel.hip")
+    if not int(round_up) + 1 == int(per) == int(threads) == int(first) == int(stride):
+        raise LookupError(f"dnn_sgd_kernel: the piece size disagrees: (total + {round_up}) / {per}, dim3({threads}), "
+                          f"blockIdx.x * {first}, gridDim.x * {stride}")
+    return SgdCap(int(threads), int(grid))
+
+
+def sgd_pieces(N, K, cap):
+    return (N * K + N + cap.threads - 1) // cap.threads
+
+
+def sgd_trips(N, K, cap):
+    """a layer [N][K] with its N biases: workgroup b takes the 256-entry pieces b, b + grid, ... of the N K + N entries"""
+    npiece = sgd_pieces(N, K, cap)
+    return trips(npiece, min(npiece, cap.grid))
+
+
+def sgd_second_trip_entry(cap):
+    """the flat index (over W row-major, then b) of the first entry that a workgroup reaches on its second trip"""
+    return cap.threads * cap.grid
 
 
 # ---- sea_rfft256_batch ----
