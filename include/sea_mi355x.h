@@ -521,7 +521,9 @@ int sea_recording_stitch_map(long samples, long chunk, long first, long count, l
  * a null pointer is not written.  d_order (launch order, optional) as elsewhere.  sea_hw25_scratch_bytes is what d_scratch
  * must hold; the present form keeps a frame's ACFs in LDS and needs none (0 bytes, d_scratch may be null).
  * sea_hw25_frontend_batch is the two batch calls as one launch group on `stream`.  sea_hw25_frontend: one utterance from
- * host memory; hout / hev [25][L], the frame outputs as above with rows = L / 80; every output pointer may be null. */
+ * host memory; hout / hev [25][L], the frame outputs as above with rows = L / 80; every output pointer may be null.
+ * Every sea_hw25_*_batch call refuses what its sea_hw64_* namesake refuses, before anything is launched: a null required
+ * pointer, and an output that is an input (d_offsets, d_lengths, d_row_offsets and d_order included) or another output. */
 int sea_hw25_tables_host(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
                          float *lp91, float *hair10 /* ymdt, xdt, ydt, lplusrdt, rdt, gdt, hdt, q0, c0, w0 */);
 long long sea_hw25_frames(long long length);

@@ -15,7 +15,6 @@
 #include <vector>
 
 #include "capi_internal.h"
-#include "hw25_capi.h"
 
 namespace sea_capi {
 
@@ -120,6 +119,18 @@ void launch_order(const long long *lens, int n, int n_cu, int *order)
         if (row & 1) std::reverse(idx.begin() + start, idx.begin() + end);
     }
     for (int i = 0; i < n; ++i) order[i] = idx[i];
+}
+
+/* Grid y of the Hu-Wang frame kernels (hw_bank_capi.hip): a fixed number of workgroups (or waves) per utterance walks its
+ * frames, about eight per CU over the batch and at most 1024; the utterances go on grid x (y ends at 65535).  The lengths stay
+ * on the device, so the number is the same for every utterance.  0: no utterance, or fail(). */
+int per_utterance(int n_utt)
+{
+    DeviceCtx *c;
+    if (n_utt <= 0 || ctx(&c)) return 0;
+    int per_utt = (8 * c->n_cu + n_utt - 1) / n_utt;
+    per_utt = per_utt < 1 ? 1 : (per_utt > 1024 ? 1024 : per_utt);
+    return per_utt;
 }
 
 void gammatone_host_tables(float *cf64, float *bw64, float *midEar64)
@@ -1200,135 +1211,6 @@ int sea_irm_target(const short *pure64, const short *noise64, long L, int window
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(irm, dirm.p, (size_t)F * 64 * sizeof(float), hipMemcpyDeviceToHost));
     return 0;
-}
-
-/* ---- the Hu-Wang estimator's front half on the 25-channel 8 kHz bank (hw25_kernel.hip) ------------------------------ */
-int sea_hw25_tables_host(float *cf25, float *bw25, float *midEar25, float *gain25, float *f1_25, float *f2_25, int *winsize25,
-                         float *lp91, float *hair10)
-{
-    sea_hw25_plain_tables(cf25, bw25, midEar25, gain25, f1_25, f2_25, winsize25, lp91, hair10);
-    return 0;
-}
-
-long long sea_hw25_frames(long long length) { return length > 0 ? length / SEA_HW25_HOP : 0; }
-
-/* the correlogram keeps a frame's ACFs in LDS: this form needs no scratch */
-long long sea_hw25_scratch_bytes(long long total_padded_samples, int n_utt)
-{
-    (void)total_padded_samples;
-    (void)n_utt;
-    return 0;
-}
-
-static int hw25_args(sea::Hw25Args &a, int n_utt)
-{
-    DeviceCtx *c;
-    if (ctx(&c)) return 1;
-    a = sea::Hw25Args{};
-    a.tables = c->hw25;
-    a.n_utt = n_utt;
-    return 0;
-}
-
-int sea_hw25_periphery_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
-                             const long long *d_lengths, const int *d_order, int n_utt, void *stream)
-{
-    return sea_hw25_periphery_gout_batch(d_in_f32, d_hout, d_hev, nullptr, d_offsets, d_lengths, d_order, n_utt, stream);
-}
-
-int sea_hw25_periphery_gout_batch(const float *d_in_f32, float *d_hout, float *d_hev, float *d_gout, const long long *d_offsets,
-                                  const long long *d_lengths, const int *d_order, int n_utt, void *stream)
-{
-    if (n_utt <= 0) return 0;
-    if (!d_in_f32 || !d_hout || !d_hev || !d_offsets || !d_lengths) return fail("hw25_periphery: null pointer");
-    if (d_gout && (d_gout == d_in_f32 || d_gout == d_hout || d_gout == d_hev))
-        return fail("hw25_periphery: d_gout must be a buffer of its own");
-    sea::Hw25Args a;
-    if (hw25_args(a, n_utt)) return 1;
-    a.in = d_in_f32;
-    a.hout = d_hout;
-    a.hev = d_hev;
-    a.gout = d_gout;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.order = d_order;
-    hipLaunchKernelGGL(sea::hw25_periphery_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(sea::hw25_lowpass_kernel, dim3(n_utt, SEA_HW25_NCHAN), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int sea_hw25_correlogram_batch(const float *d_hout, const float *d_hev, const long long *d_offsets, const long long *d_lengths,
-                               const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev, float *d_cross_hc,
-                               float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
-                               const int *d_order, int n_utt, void *stream)
-{
-    (void)d_scratch; /* sea_hw25_scratch_bytes is 0 for this form */
-    if (n_utt <= 0) return 0;
-    if (!d_hout || !d_hev || !d_offsets || !d_lengths || !d_row_offsets || !d_cross_hc || !d_cross_ev || !d_pitch || !d_pratio ||
-        !d_mark)
-        return fail("hw25_correlogram: null pointer (only d_acf_hc, d_acf_ev, d_scratch and d_order may be null)");
-    DeviceCtx *c;
-    sea::Hw25Args a;
-    if (ctx(&c) || hw25_args(a, n_utt)) return 1;
-    a.hout = const_cast<float *>(d_hout);
-    a.hev = const_cast<float *>(d_hev);
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.row_offsets = d_row_offsets;
-    a.acf_hc = d_acf_hc;
-    a.acf_ev = d_acf_ev;
-    a.cross_hc = d_cross_hc;
-    a.cross_ev = d_cross_ev;
-    a.pitch = d_pitch;
-    a.pratio = d_pratio;
-    a.mark = d_mark;
-    a.order = d_order;
-    /* the lengths stay on the device: a fixed number of workgroups per utterance walks its frames, about eight workgroups
-     * per CU over the batch; the utterances go on grid x (y ends at 65535) */
-    int per_utt = (8 * c->n_cu + n_utt - 1) / n_utt;
-    per_utt = per_utt < 1 ? 1 : (per_utt > 1024 ? 1024 : per_utt);
-    hipLaunchKernelGGL(sea::hw25_correlogram_kernel, dim3(n_utt, per_utt), dim3(256), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int sea_hw25_frontend_batch(const float *d_in_f32, float *d_hout, float *d_hev, const long long *d_offsets,
-                            const long long *d_lengths, const long long *d_row_offsets, float *d_acf_hc, float *d_acf_ev,
-                            float *d_cross_hc, float *d_cross_ev, int *d_pitch, float *d_pratio, float *d_mark, void *d_scratch,
-                            const int *d_order, int n_utt, void *stream)
-{
-    if (sea_hw25_periphery_batch(d_in_f32, d_hout, d_hev, d_offsets, d_lengths, d_order, n_utt, stream)) return 1;
-    return sea_hw25_correlogram_batch(d_hout, d_hev, d_offsets, d_lengths, d_row_offsets, d_acf_hc, d_acf_ev, d_cross_hc,
-                                      d_cross_ev, d_pitch, d_pratio, d_mark, d_scratch, d_order, n_utt, stream);
-}
-
-int sea_hw25_frontend(const float *in, long L, float *hout, float *hev, float *acf_hc, float *acf_ev, float *cross_hc,
-                      float *cross_ev, int *pitch, float *pratio, float *mark)
-{
-    if (L <= 0) return fail("hw25_frontend: L=%ld", L);
-    Hw25Single u;
-    if (u.load(in, L)) return 1;
-    const size_t Lp = (size_t)u.Lp, fr = (size_t)u.rows * SEA_HW25_NCHAN, acf = (size_t)SEA_HW25_NCHAN * SEA_HW25_DELAYS;
-    DevBuf<float> dho, dhe, dah, dae, dfr;
-    DevBuf<int> dp;
-    HIP_TRY(dho.alloc(Lp * SEA_HW25_NCHAN));
-    HIP_TRY(dhe.alloc(Lp * SEA_HW25_NCHAN));
-    if (acf_hc) HIP_TRY(dah.alloc(fr * SEA_HW25_DELAYS));
-    if (acf_ev) HIP_TRY(dae.alloc(fr * SEA_HW25_DELAYS));
-    HIP_TRY(dfr.alloc(fr * 4)); /* cross_hc | cross_ev | pratio | mark */
-    HIP_TRY(dp.alloc((size_t)u.rows));
-    if (sea_hw25_frontend_batch(u.d_in, dho.p, dhe.p, u.d_offsets, u.d_lengths, u.d_row_offsets, dah.p, dae.p, dfr.p, dfr.p + fr,
-                                dp.p, dfr.p + 2 * fr, dfr.p + 3 * fr, nullptr, nullptr, 1, nullptr))
-        return 1;
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t rowb = (size_t)L * sizeof(float);
-    if (hout) HIP_TRY(hipMemcpy2D(hout, rowb, dho.p, Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
-    if (hev) HIP_TRY(hipMemcpy2D(hev, rowb, dhe.p, Lp * sizeof(float), rowb, SEA_HW25_NCHAN, hipMemcpyDeviceToHost));
-    return u.rows_back(acf_hc, dah.p, acf) || u.rows_back(acf_ev, dae.p, acf) || u.rows_back(cross_hc, dfr.p, SEA_HW25_NCHAN) ||
-           u.rows_back(cross_ev, dfr.p + fr, SEA_HW25_NCHAN) || u.rows_back(pratio, dfr.p + 2 * fr, SEA_HW25_NCHAN) ||
-           u.rows_back(mark, dfr.p + 3 * fr, SEA_HW25_NCHAN) || u.rows_back(pitch, dp.p, 1);
 }
 
 int sea_gammatone_filter(const float *input, float *output, int chan, long sigLength)

@@ -46,6 +46,8 @@ inline long long align8(long long v) { return (v + 7) & ~7LL; }
 
 /* launch order of the utterance-per-workgroup kernels: longest first, every other row of n_cu reversed */
 void launch_order(const long long *lens, int n, int n_cu, int *order);
+/* grid y of the Hu-Wang frame kernels: eight workgroups per CU over the batch, 1..1024; 0: no utterance, or fail() */
+int per_utterance(int n_utt);
 
 /* NoiseSup kernel form for a batch of n_inflight utterances sharing the device (capi.hip::sea_ns_denoise_batch):
  * 3 six-wave, 6 dense six-wave, 4 four-wave / tables in LDS, 2 four-wave; honours sea_ns_kernel_form / SEA_NS_KERNEL */

@@ -1,7 +1,7 @@
 /*
- * hw25_capi.h -- what the translation units behind the Hu-Wang C ABI share (capi.hip, hw25_pitch_capi.hip, hw25_am_capi.hip,
- * hw25_resynth_capi.hip, hw64_capi.hip, hw64_pitch_capi.hip, hw64_am_capi.hip, hw64_resynth_capi.hip): the single-utterance forms' batch of one, the refusal of outputs that are inputs,
- * where the whole estimator keeps gOut, and the 64-band resynthesis's internal batch launches.
+ * hw25_capi.h -- what the translation units behind the Hu-Wang C ABI share (hw_bank_capi.hip, hw25_resynth_capi.hip,
+ * hw64_resynth_capi.hip): the refusal of outputs that are inputs and the single-utterance forms' batch of one.  What differs
+ * between the two banks is in hw_bank.h.
  */
 #pragma once
 #include <initializer_list>
@@ -22,23 +22,6 @@ inline int shared_buffer(const void *const *outs, int n, std::initializer_list<c
     }
     return 0;
 }
-
-/* where sea_hw25_ibm_batch keeps gOut ([25][pitch] per utterance, hout's layout) in its scratch, in bytes from its start, for
- * the same three arguments as sea_hw25_ibm_scratch_bytes (hw25_am_capi.hip); sea_hw25_enhance_batch resynthesises from it */
-long long hw25_ibm_gout_offset(long long total_padded_samples, long long total_rows, int n_utt);
-/* the same for sea_hw64_ibm_batch and sea_hw64_ibm_scratch_bytes ([64][pitch] per utterance; hw64_am_capi.hip) */
-long long hw64_ibm_gout_offset(long long total_padded_samples, long long total_rows, int n_utt);
-
-/* The batch launches of the 64-band resynthesis (hw64_resynth_capi.hip), on device pointers and one stream, argument for
- * argument sea_hw25_resynth_batch and sea_hw25_enhance_batch at 64 channels and a hop of 160.  Internal: the exported calls are
- * the host-pointer forms built on them (sea_hw64_resynth, sea_hw64_enhance, sea_hw64_*_utterances). */
-int hw64_resynth_launch(const float *d_gout, const float *d_mask, const long long *d_offsets, const long long *d_lengths,
-                        const long long *d_row_offsets, float threshold, float *d_out_f32, short *d_out_i16, const int *d_order,
-                        int n_utt, hipStream_t stream);
-int hw64_enhance_launch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
-                        float *d_out_f32, short *d_out_i16, float *d_mask, int *d_pitch, int *d_status, void *d_scratch,
-                        long long total_padded_samples, long long total_rows, const int *d_order, int n_utt, hipStream_t stream,
-                        hipEvent_t before_resynth = nullptr, hipEvent_t after_resynth = nullptr); /* recorded around the resynthesis */
 
 /* One utterance from host memory as a batch of one: the samples zero-padded to Lp = L rounded up to 8 on the device, and
  * the three words a batch call takes as offsets, lengths and row_offsets (0, L, 0).  F = L / hop frames (80 samples on the

@@ -2,11 +2,11 @@
  * hw25_resynth_capi.hip -- the C ABI of the Hu-Wang 25-channel resynthesis (hw25_resynth_kernel.hip):
  * sea_hw25_resynth_tables_host, sea_hw25_resynth_batch, sea_hw25_enhance_batch (the whole estimator followed by the
  * resynthesis of its own mask), the single-utterance forms sea_hw25_resynth and sea_hw25_enhance, and the text writer.  The
- * batch calls are launches on one stream and nothing else: the lengths stay on the device.
+ * batch calls are the shared launches of hw_bank.h on this bank: launches on one stream, the lengths stay on the device.
  */
 #include <cstdio>
 
-#include "hw25_capi.h"
+#include "hw_bank.h"
 
 using namespace sea_capi;
 
@@ -20,47 +20,16 @@ int sea_hw25_resynth_batch(const float *d_gout, const float *d_mask, const long 
                            const long long *d_row_offsets, float threshold, float *d_out_f32, short *d_out_i16, const int *d_order,
                            int n_utt, void *stream)
 {
-    if (n_utt <= 0) return 0;
-    if (!d_gout || !d_mask || !d_offsets || !d_lengths || !d_row_offsets) return fail("hw25_resynth: null pointer (only d_order and one output may be null)");
-    if (!d_out_f32 && !d_out_i16) return fail("hw25_resynth: no output (d_out_f32 and d_out_i16 are both null)");
-    const void *outs[] = {d_out_f32, d_out_i16};
-    if (shared_buffer(outs, 2, {d_gout, d_mask}))
-        return fail("hw25_resynth: an output must not be an input or the other output");
-    DeviceCtx *c;
-    if (ctx(&c)) return 1;
-    sea::Hw25ResynthArgs a{};
-    a.gout = d_gout;
-    a.mask = d_mask;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.row_offsets = d_row_offsets;
-    a.out_f32 = d_out_f32;
-    a.out_i16 = d_out_i16;
-    a.order = d_order;
-    a.tables = c->hw25;
-    a.threshold = threshold;
-    a.n_utt = n_utt;
-    hipLaunchKernelGGL(sea::hw25_resynth_kernel, dim3(n_utt), dim3(64), 0, (hipStream_t)stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return resynth_launch<Bank25>(d_gout, d_mask, d_offsets, d_lengths, d_row_offsets, threshold, d_out_f32, d_out_i16, d_order, n_utt,
+                                  (hipStream_t)stream);
 }
 
 int sea_hw25_enhance_batch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths, const long long *d_row_offsets,
                            float *d_out_f32, short *d_out_i16, float *d_mask, int *d_pitch, int *d_status, void *d_scratch,
                            long long total_padded_samples, long long total_rows, const int *d_order, int n_utt, void *stream)
 {
-    if (n_utt <= 0) return 0;
-    if (!d_out_f32 && !d_out_i16) return fail("hw25_enhance: no output (d_out_f32 and d_out_i16 are both null)");
-    const void *outs[] = {d_out_f32, d_out_i16};
-    if (shared_buffer(outs, 2, {d_in_f32, d_mask, d_pitch, d_status, d_scratch}))
-        return fail("hw25_enhance: an output must not be the input or another output");
-    /* the mask of createIBM :99-106 is 0 / 1: the reference's `mark > 0` */
-    if (sea_hw25_ibm_batch(d_in_f32, d_offsets, d_lengths, d_row_offsets, d_mask, d_pitch, d_status, nullptr, d_scratch,
-                           total_padded_samples, total_rows, d_order, n_utt, stream))
-        return 1;
-    const float *gout = reinterpret_cast<const float *>(static_cast<const char *>(d_scratch) +
-                                                        hw25_ibm_gout_offset(total_padded_samples, total_rows, n_utt));
-    return sea_hw25_resynth_batch(gout, d_mask, d_offsets, d_lengths, d_row_offsets, 0.0f, d_out_f32, d_out_i16, d_order, n_utt, stream);
+    return enhance_launch<Bank25>(d_in_f32, d_offsets, d_lengths, d_row_offsets, d_out_f32, d_out_i16, d_mask, d_pitch, d_status,
+                                  d_scratch, total_padded_samples, total_rows, d_order, n_utt, (hipStream_t)stream);
 }
 
 int sea_hw25_resynth(const float *x, long L, const float *mask, long F, float threshold, float *out_f32)

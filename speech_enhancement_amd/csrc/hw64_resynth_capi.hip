@@ -3,16 +3,16 @@
  * sea_hw64_resynth_tables_host, the single-utterance forms sea_hw64_resynth and sea_hw64_enhance, the forms that take lists of
  * utterances in host memory, sea_hw64_resynth_utterances and sea_hw64_enhance_utterances, with the plan that cuts a list into
  * chunks that fit HBM (sea_hw64_enhance_plan, sea_hw64_enhance_last_chunks, sea_hw64_enhance_last_resynth_ms).  Every exported
- * call takes host pointers.  The
- * batch launches on device pointers and a stream, hw64_resynth_launch and hw64_enhance_launch (hw25_capi.h), are internal:
- * each chunk of a list is one launch group of them, and a single utterance is a list of one.
+ * call takes host pointers.  The batch launches on device pointers and a stream are the shared ones of hw_bank.h on the
+ * 64-channel bank, resynth_launch and enhance_launch: each chunk of a list is one launch group of them, and a single utterance
+ * is a list of one.
  */
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "hw25_capi.h"
+#include "hw_bank.h"
 
 using namespace sea_capi;
 
@@ -228,7 +228,7 @@ int resynth_list(const float *const *in, const long *lengths, const float *const
             if (sea_hw64_periphery_batch(q.d_in.p, d_planes.p, d_planes.p + plane, gout, q.offs, q.lens, q.d_order.p, q.n, nullptr))
                 return 1;
             HIP_TRY(hipEventRecord(timer.before, nullptr));
-            if (hw64_resynth_launch(gout, q.d_mask.p, q.offs, q.lens, q.roff, threshold, q.d_out.p, q.d_out16.p, q.d_order.p, q.n, nullptr))
+            if (resynth_launch<Bank64>(gout, q.d_mask.p, q.offs, q.lens, q.roff, threshold, q.d_out.p, q.d_out16.p, q.d_order.p, q.n, nullptr))
                 return 1;
             HIP_TRY(hipEventRecord(timer.after, nullptr));
             HIP_TRY(hipDeviceSynchronize());
@@ -263,7 +263,7 @@ int enhance_list(const float *const *in, const long *lengths, int n_utt, float *
             *chunks = k + 1;
             continue;
         }
-        if (hw64_enhance_launch(q.d_in.p, q.offs, q.lens, q.roff, q.d_out.p, q.d_out16.p, q.d_mask.p, d_pitch, d_status, d_scr.p, q.s, q.r,
+        if (enhance_launch<Bank64>(q.d_in.p, q.offs, q.lens, q.roff, q.d_out.p, q.d_out16.p, q.d_mask.p, d_pitch, d_status, d_scr.p, q.s, q.r,
                                 q.d_order.p, q.n, nullptr, timer.before, timer.after))
             return 1;
         HIP_TRY(hipDeviceSynchronize());
@@ -291,57 +291,6 @@ int enhance_list(const float *const *in, const long *lengths, int n_utt, float *
 }
 
 } // namespace
-
-int sea_capi::hw64_resynth_launch(const float *d_gout, const float *d_mask, const long long *d_offsets, const long long *d_lengths,
-                                  const long long *d_row_offsets, float threshold, float *d_out_f32, short *d_out_i16,
-                                  const int *d_order, int n_utt, hipStream_t stream)
-{
-    if (n_utt <= 0) return 0;
-    if (!d_gout || !d_mask || !d_offsets || !d_lengths || !d_row_offsets) return fail("hw64_resynth: null pointer (only d_order and one output may be null)");
-    if (!d_out_f32 && !d_out_i16) return fail("hw64_resynth: no output (d_out_f32 and d_out_i16 are both null)");
-    const void *outs[] = {d_out_f32, d_out_i16};
-    if (shared_buffer(outs, 2, {d_gout, d_mask}))
-        return fail("hw64_resynth: an output must not be an input or the other output");
-    DeviceCtx *c;
-    if (ctx(&c)) return 1;
-    sea::Hw64ResynthArgs a{};
-    a.gout = d_gout;
-    a.mask = d_mask;
-    a.offsets = d_offsets;
-    a.lengths = d_lengths;
-    a.row_offsets = d_row_offsets;
-    a.out_f32 = d_out_f32;
-    a.out_i16 = d_out_i16;
-    a.order = d_order;
-    a.tables = c->hw64;
-    a.threshold = threshold;
-    a.n_utt = n_utt;
-    hipLaunchKernelGGL(sea::hw64_resynth_kernel, dim3(n_utt), dim3(64), 0, stream, a);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int sea_capi::hw64_enhance_launch(const float *d_in_f32, const long long *d_offsets, const long long *d_lengths,
-                                  const long long *d_row_offsets, float *d_out_f32, short *d_out_i16, float *d_mask, int *d_pitch,
-                                  int *d_status, void *d_scratch, long long total_padded_samples, long long total_rows,
-                                  const int *d_order, int n_utt, hipStream_t stream, hipEvent_t before_resynth, hipEvent_t after_resynth)
-{
-    if (n_utt <= 0) return 0;
-    if (!d_out_f32 && !d_out_i16) return fail("hw64_enhance: no output (d_out_f32 and d_out_i16 are both null)");
-    const void *outs[] = {d_out_f32, d_out_i16};
-    if (shared_buffer(outs, 2, {d_in_f32, d_mask, d_pitch, d_status, d_scratch}))
-        return fail("hw64_enhance: an output must not be the input or another output");
-    /* the mask of createIBM :99-106 is 0 / 1: the reference's `mark > 0` */
-    if (sea_hw64_ibm_batch(d_in_f32, d_offsets, d_lengths, d_row_offsets, d_mask, d_pitch, d_status, nullptr, d_scratch,
-                           total_padded_samples, total_rows, d_order, n_utt, stream))
-        return 1;
-    const float *gout = reinterpret_cast<const float *>(static_cast<const char *>(d_scratch) +
-                                                        hw64_ibm_gout_offset(total_padded_samples, total_rows, n_utt));
-    if (before_resynth) HIP_TRY(hipEventRecord(before_resynth, stream));
-    if (hw64_resynth_launch(gout, d_mask, d_offsets, d_lengths, d_row_offsets, 0.0f, d_out_f32, d_out_i16, d_order, n_utt, stream)) return 1;
-    if (after_resynth) HIP_TRY(hipEventRecord(after_resynth, stream));
-    return 0;
-}
 
 int sea_hw64_resynth_tables_host(float *w640, double *up160, double *down160)
 {
