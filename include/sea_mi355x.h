@@ -1043,6 +1043,13 @@ int sea_selftest_log(const float *x, double *ln_out, int n);
 int sea_selftest_log_dd(const double *x, double *hi, double *lo, int n);
 int sea_selftest_log_sites(const float *x, float *site1, float *site2, int n);
 int sea_selftest_log_guard(int site, unsigned long long *stats8, float *hits3, int cap);
+/* the lane form of both sites (csrc/ns_core.h, ns_log_lanes_request / ns_log_lanes_take: one logarithm per lane, the site chosen per
+ * lane, one ballot for the guard), which the dense six-wave kernel runs on the VAD sums of two beats at once, against the two
+ * complete sites above, bit for bit, on EVERY float argument either site can see.  A wave takes two neighbouring arguments per pass;
+ * all_vad = 0: as site 1 in lanes 0, 1 and as site 2 in lanes 2, 3 (four different logarithms per pass), all_vad != 0: as site 1 alone.
+ * stats8 = {arguments of site 1, of site 2, guard hits of site 1, of site 2, results or guard flags that differ from the complete
+ * site's for site 1, for site 2 (both must be 0), passes that went through the slow branch, 0} */
+int sea_selftest_log_lanes(int all_vad, unsigned long long *stats8);
 /* the same three logarithm forms as the kernels that take the caller's floats instantiate them (sea_ns_stream_push, sea_ns_streams_push,
  * sea_ns_streams_push_fd, sea_ns16k_streams_push, sea_compceps_frames): the exponent field is tested first, +Inf gives +Inf, a NaN
  * (and -Inf) gives NaN, as libm's log does; every other argument goes the way of sea_selftest_log_sites.  n floats of any bit

@@ -1566,4 +1566,21 @@ int sea_selftest_log_guard(int site, unsigned long long *stats8, float *hits3, i
     return 0;
 }
 
+int sea_selftest_log_lanes(int all_vad, unsigned long long *stats8)
+{
+    DeviceCtx *c;
+    if (ctx(&c)) return 1;
+    DevBuf<unsigned long long> ds;
+    HIP_TRY(ds.alloc(8));
+    HIP_TRY(hipMemset(ds.p, 0, 8 * sizeof(unsigned long long)));
+    if (all_vad)
+        hipLaunchKernelGGL(sea::selftest_log_lanes_kernel<true>, dim3(4096), dim3(256), 0, nullptr, ds.p);
+    else
+        hipLaunchKernelGGL(sea::selftest_log_lanes_kernel<false>, dim3(4096), dim3(256), 0, nullptr, ds.p);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(stats8, ds.p, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return 0;
+}
+
 } // extern "C"

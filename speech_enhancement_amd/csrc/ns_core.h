@@ -157,6 +157,35 @@ __device__ __forceinline__ double ns_ln(double x)
     const double small = __fma_rn(r2, p, r) + __fma_rn(de, ln2_lo, tl);
     return __fma_rn(de, ln2_hi, th) + small;
 }
+/* ns_ln once more, in its two halves, for a caller that fetches the table row between them (ns_log_lanes_request below): the integer
+ * prelude -- exponent e, the pattern mb of m, the row's index as the return value -- and the series on the row (c, th, tl), statement
+ * by statement what ns_ln has.  ns_ln is NOT written in terms of them: built that way it computes the same, but the register
+ * allocation of nine other units that inline it moves, and their listings are compared from round to round. */
+__device__ __forceinline__ unsigned ns_ln_reduce(float x, int &e, unsigned &mb)
+{
+    const unsigned fb = __float_as_uint(x);
+    e = (int)(fb >> 23) - 127;
+    mb = (fb & 0x007fffffu) | 0x3f800000u;
+    const bool big = mb > 0x3FB504F2u;
+    mb = big ? mb - 0x00800000u : mb;
+    e = big ? e + 1 : e;
+    return (mb - 0x3F3504F3u) >> 15;
+}
+__device__ __forceinline__ double ns_ln_series(int e, unsigned mb, double c, double th, double tl)
+{
+    const double m = (double)__uint_as_float(mb);
+    const double r = __fma_rn(m, c, -1.0);
+    const double r2 = r * r;
+    double p = -1.0 / 6.0;
+    p = __fma_rn(p, r, 1.0 / 5.0);
+    p = __fma_rn(p, r, -1.0 / 4.0);
+    p = __fma_rn(p, r, 1.0 / 3.0);
+    p = __fma_rn(p, r, -0.5);
+    const double de = (double)e;
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+    const double small = __fma_rn(r2, p, r) + __fma_rn(de, ln2_lo, tl);
+    return __fma_rn(de, ln2_hi, th) + small;
+}
 
 /* ---- the guard of the lean log --------------------------------------------------------------------------
  * Both call sites round a short double expression of the log to float (NoiseSup.c:391, :607).  ns_ln is within
@@ -343,6 +372,52 @@ __device__ __forceinline__ float ns_aversnr_expr(float averSNR, bool *hit = null
     }
     if (__builtin_expect(near, 0)) return ns_aversnr_slow(averSNR);
     return (float)v;
+}
+
+/* ---- both sites, one logarithm per LANE, in two halves (round 15: N1 of the dense six-wave kernel) -----------------------
+ * A wave-uniform site pays the whole instruction stream of ns_ln, most of it double precision, for one useful lane.  Here every
+ * lane carries an argument of its own and says which site it is (vad: NoiseSup.c:391, otherwise :607), so one pass serves as
+ * many sites as there are arguments at hand.  Per lane the operations are those of ns_vad_energy_expr<false> and
+ * ns_aversnr_expr<false>, one by one:
+ *   the pre-scale        x 0.015625 (vad) or x 1.0 in double, both exact
+ *   ns_ln                the same prelude and series (ns_ln_reduce, ns_ln_series), the table row through a per-lane load
+ *   the expression       fma(L, k, a) with (k, a) = (16 / ln 2, 0.5) or (20 log10 e / 3, +0.0).  fma(L, k, +0.0) rounds L k + 0 = L k
+ *                        once, which is what L * k rounds: the same double for every L, except that an exact product of -0 would
+ *                        come out as +0.  The product is a zero only for L = 0 (|k| > 1 and a non-zero L is a log of a float,
+ *                        |L| > 2^-25: no underflow), and L = 0 comes out of ns_ln_series as +0 (x = 1: e = 0, r = 0, th = tl = 0,
+ *                        sums of +0), whose product with k > 0 is +0 in both forms.
+ *   the guard            ns_near_float_boundary with the lane's own window (10 / 20), all lanes under ONE ballot: a hit (1e-7 per
+ *                        lane) sends the wave into the branch, where the lanes that hit take their site's slow form and the others
+ *                        keep what they have.
+ * request() ends with the row's loads in flight and take() begins by waiting for them: the caller puts work that neither needs
+ * them nor feeds them in between, and the scheduling barriers and the opaque statement keep the compiler from sinking the loads to
+ * their use (the pattern of ns_idct_basis_request).  sea_selftest_log_lanes compares the pair with the two <false> forms, bit for
+ * bit, on every float argument either site can see. */
+struct NsLogLanes {
+    int e;
+    unsigned mb;
+    double c, th, tl;
+};
+__device__ __forceinline__ void ns_log_lanes_request(NsLogLanes &q, float arg, bool vad)
+{
+    const double x = (double)arg * (vad ? 0.015625 : 1.0);
+    const double *t = kNsLogTab[ns_ln_reduce((float)x /* exact: x is a float */, q.e, q.mb)];
+    q.c = t[0], q.th = t[1], q.tl = t[2];
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ float ns_log_lanes_take(NsLogLanes &q, float arg, bool vad, bool *hit = nullptr)
+{
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile("" : "+v"(q.c), "+v"(q.th), "+v"(q.tl));
+    const double l = ns_ln_series(q.e, q.mb, q.c, q.th, q.tl);
+    const double v = __fma_rn(l, vad ? 23.083120654223414 /* 16 / ln 2 */ : 2.8952965460216789 /* 20 log10(e) / 3 */, vad ? 0.5 : 0.0);
+    const bool near = ns_near_float_boundary(v, vad ? 10 : 20);
+    if (hit) *hit = near;
+    float r = (float)v;
+    if (__builtin_expect(__ballot(near) != 0ull, 0)) {
+        if (near) r = vad ? ns_vad_energy_slow(arg) : ns_aversnr_slow(arg);
+    }
+    return r;
 }
 
 /* FilterCalc (NoiseSup.c:449-563) for one PSD bin, in two pieces so that the pipelined kernel can

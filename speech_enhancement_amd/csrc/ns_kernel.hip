@@ -189,6 +189,51 @@ __global__ __launch_bounds__(256) void selftest_log_guard_kernel(int site, unsig
     if (nmiss) atomicAdd(stats + 4, nmiss);
 }
 
+/* The lane form of both sites (ns_core.h, ns_log_lanes_request / ns_log_lanes_take) against ns_vad_energy_expr<false> and
+ * ns_aversnr_expr<false>, bit for bit, on EVERY float argument either site can see (the ranges of selftest_log_guard_kernel), as the
+ * dense six-wave kernel's N1 runs it: a few distinct arguments per wave, repeated over its lanes.  A wave takes two neighbouring
+ * float patterns per pass, lane & 1 choosing between them; ALLVAD: every lane is site 1; otherwise lanes with lane & 2 clear are
+ * site 1 and the others site 2 on the same two patterns, four different logarithms per pass.  A lane whose pattern is outside its
+ * site's range computes on a harmless argument and is not counted.  Lanes 0 .. 3 (ALLVAD: 0, 1) count:
+ * stats[0], [1] = arguments of site 1, 2; [2], [3] = guard hits; [4], [5] = results that differ from the <false> form's (must be
+ * 0) or guard flags that differ from its; [6] = passes in which the ballot sent the wave through the slow branch. */
+template <bool ALLVAD>
+__global__ __launch_bounds__(256) void selftest_log_lanes_kernel(unsigned long long *stats)
+{
+    const unsigned lo = ALLVAD ? 0x42800000u /* 64 */ : 0x3727C5ADu /* first float above 1e-5 (double compare) */;
+    const unsigned hi = 0x7F7FFFFFu;
+    const int lane = threadIdx.x & 63;
+    const bool vad = ALLVAD || !(lane & 2), counts = lane < (ALLVAD ? 2 : 4);
+    unsigned long long ntest = 0, nhit = 0, nbad = 0, nslow = 0;
+    const unsigned long long wave = ((unsigned long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const unsigned long long stride = 2ull * (((unsigned long long)gridDim.x * blockDim.x) >> 6);
+    for (unsigned long long p = (unsigned long long)lo + 2ull * wave; p <= hi; p += stride) {
+        const unsigned long long b = p + (lane & 1);
+        float x = __uint_as_float((unsigned)b);
+        const bool valid = b <= hi && (vad ? x >= 64.0f : (double)x > 0.00001);
+        if (!valid) x = vad ? 64.0f : 1.0f;
+        NsLogLanes q;
+        bool hit = false, hitWant = false;
+        ns_log_lanes_request(q, x, vad);
+        const float got = ns_log_lanes_take(q, x, vad, &hit);
+        const float want = vad ? ns_vad_energy_expr<false>(x, &hitWant) : ns_aversnr_expr<false>(x, &hitWant);
+        const bool slow = __ballot(hit) != 0ull; /* all lanes of the wave are here: p is the wave's */
+        nslow += (lane == 0 && slow) ? 1 : 0;
+        if (valid && counts) {
+            ntest++;
+            nhit += hit ? 1 : 0;
+            nbad += (__float_as_uint(got) != __float_as_uint(want) || hit != hitWant) ? 1 : 0;
+        }
+    }
+    const int site = vad ? 0 : 1;
+    if (ntest) atomicAdd(stats + 0 + site, ntest);
+    if (nhit) atomicAdd(stats + 2 + site, nhit);
+    if (nbad) atomicAdd(stats + 4 + site, nbad);
+    if (nslow) atomicAdd(stats + 6, nslow);
+}
+template __global__ void selftest_log_lanes_kernel<false>(unsigned long long *);
+template __global__ void selftest_log_lanes_kernel<true>(unsigned long long *);
+
 /* sea_selftest_nsdiv: ns_div / ns_inv64 (ns_core.h) against the compiler's IEEE division, bit for bit, on
  * pseudo-random and edge-mantissa operands spanning the whole domain ns_back() admits: denominators
  * 2^-30 .. 2^59, numerators 0 or 2^-76 .. 2^49 with an exponent difference within [-106, 80]; the double

@@ -111,6 +111,18 @@
  * LDS instructions fewer per frame, G1 34 and 5 more; configs[1] over 200 steps 1.344 -> 1.295 ms with the parent's map (8 x the larger spread), 1.334 ->
  * 1.267 ms = 646 M frames/s with the swept one (-5.0 %, 7 x; profiles/ns6_fir_merged.txt).
  *
+ * Round 15, the dense kernel only (LOGP of ns_pipe6_body): N1's VAD logarithm was a full wave64 instruction stream, most of it double
+ * precision, for one wave-uniform value per beat.  Its argument is feed-forward (S's sum of squares) and its result is read two beats
+ * later, so there is a spare beat: in a steady pair of beats (2h, 2h+1) --
+ *   wave N1  nothing for the VAD in the even beat; in the odd beat the sums of both beats in its even and odd lanes through ONE pass
+ *            (ns_core.h, ns_log_lanes_request / ns_log_lanes_take: per lane the operations of ns_vad_energy_expr<false>, the guard of
+ *            all lanes under one ballot), the table rows by per-lane loads requested at the top of the beat and taken behind the
+ *            noise tracking -> both slots of frameEnLog, one barrier ahead of B0's read of the first
+ * The general copy keeps one logarithm per beat; no flag, ring, beat or barrier changed.  N1's steady pair on the listing: 928 -> 888
+ * vector (349 -> 316 of them f64), 331 -> 278 scalar instructions; configs[1] over 200 steps 1.278 -> 1.243 ms = 658 M frames/s (-2.7 %,
+ * 7 x the larger spread; profiles/ns6_log_pairs.txt, which also says what of that issue was not built: the averSNR pair and the
+ * fourteen-beat schedule it needs).
+ *
  * All records between neighbouring stages are double-buffered by frame parity (written at one
  * iteration, read at the next), those that are read in place over several beats sit in rings (kP1Ring, kRnRing); the two
  * transform work areas alternate between FA and FB.  The records carry data only: which frames are valid, their ticks
@@ -359,6 +371,10 @@ __device__ __forceinline__ void run_beats(int niter, int nfr, const int &onset, 
  *                     one G1 reads -- by one, as before; S reads the slot of frame i-1.  The slots G1 reads were written at iterations
  *                     i-7 .. i-5.
  *   LDS               31 920 B per workgroup (+ 64 for denSum16): five still fit a CU's 160 KB
+ *   LOGP (round 15)   frameEn, frameEnLog in a steady pair (2h, 2h+1): the slot of tick(2h) is written by S at 2h-1, read by N1 at 2h+1
+ *                     (was 2h) and rewritten by S at 2h+7; its logarithm is written by N1 at 2h+1 (was 2h), read by B0 at 2h+2 and
+ *                     rewritten at the earliest at 2h+8.  The slot of tick(2h+1) keeps its beats (S 2h, N1 2h+1, B0 2h+3).  At beat
+ *                     2h+1 S writes the slot of tick(2h+2), which is neither.  Rings of eight hold both with room; no schedule moved.
  * nbFrame of the gain-factor job: N1's counter has by then counted the two frames tracked since; the job takes the frame's own
  * count, tick - 4 (the first second-stage frame has tick 5).
  * LDS: 24 960 B per workgroup (24 624 + the two tap records + the ring of W1[64]); four workgroups per CU take 99.8 KB of the 160. */
@@ -531,7 +547,8 @@ template <bool FD, bool LIGHT /* the VAD log leaves S */, bool DIFG1 /* G1 hands
           bool BIN64 = false /* round 10, the dense kernel: stage-1 bin 64 rides in B0's second component, one domain flag per stage-1 frame */,
           bool IDCTS = false /* round 11, the dense kernel: both stages' IDCT sums ride in the helper wave's idle lanes; X is its LDS */,
           bool PAIRED = false /* round 12, all three kernels: the steady beats two by two, the frame parity a constant of each copy (run_beats) */,
-          bool FIRP = false /* round 14, the dense kernel: both 17-tap filters as one pass on G1's two lane halves, off FA (ns_core.h, ns_fir_pair3) */>
+          bool FIRP = false /* round 14, the dense kernel: both 17-tap filters as one pass on G1's two lane halves, off FA (ns_core.h, ns_fir_pair3) */,
+          bool LOGP = false /* round 15, the dense kernel: the two VAD logarithms of a steady pair of beats as one pass on N1's lanes (ns_core.h, ns_log_lanes_request) */>
 __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L, Pipe6Idct *X = nullptr)
 {
     static_assert(!REDEAL || (!LIGHT && !DIFG1), "the re-deal is a variant of the dense body");
@@ -539,6 +556,7 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
     static_assert(!IDCTS || BIN64, "the IDCT sums in the helper wave are a variant of that body in turn");
     static_assert(!PAIRED || STEADY_LOOP, "the paired beats are the steady copies'");
     static_assert(!FIRP || IDCTS, "the merged filter pass takes both stages' taps from the helper wave");
+    static_assert(!LOGP || (REDEAL && PAIRED), "the paired logarithms are N1's (LOG_N1), in the odd copy of its steady pair");
     constexpr unsigned V = (FD ? ns6plan::kFd : 0u) | (LIGHT ? ns6plan::kLight : 0u) | (DIFG1 ? ns6plan::kDifg1 : 0u) | (REDEAL ? ns6plan::kRedeal : 0u) |
                            (BIN64 ? ns6plan::kBin64 : 0u) | (IDCTS ? ns6plan::kIdctS : 0u) | (FIRP ? ns6plan::kFirPair : 0u);
     static_assert(!BIN64 || V == (FIRP ? ns6plan::kVariantDenseFirPair : (IDCTS ? ns6plan::kVariantDenseIdct : ns6plan::kVariantDenseBin64)),
@@ -866,7 +884,22 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
             prio_by_remaining(i);
             if (!STEADY) onset_poll(onset, &L.onset);
             const int f = i - 5 - kS1, fg = i - 7 - kS1;
-            if constexpr (LOG_N1) { /* the log-energy of the sum S left one beat ago, as FA takes it with LIGHT; B0 reads it two beats on */
+            /* LOGP, the steady pair (2h, 2h+1): nothing for the VAD in the even beat; the odd beat i takes both sums -- slot tick(i-1)
+             * in the even lanes (S left it at i-2, B0 reads its log at i+1), slot tick(i) in the odd ones (S: i-1, B0: i+2) -- and
+             * requests their table rows here; the pass itself runs behind the noise tracking, which covers the loads.  Both beats of
+             * a pair lie in the steady range, so the even beat's flag (2, 1) is this beat's (3, 1): no flag the plan does not have. */
+            constexpr bool LOG_PAIR = LOGP && STEADY;
+            const bool logNow = LOG_PAIR && (i & 1); /* a constant of each steady copy */
+            NsLogLanes lq = {};
+            int lqSlot = 0;
+            float lqSum = 0.0f;
+            if constexpr (LOG_PAIR) {
+                if (logNow) {
+                    lqSlot = (tick_of(i - 3, onset) + 2 + (lane & 1)) & (kSlots - 1);
+                    lqSum = L.frameEn[lqSlot];
+                    ns_log_lanes_request(lq, lqSum, true);
+                }
+            } else if constexpr (LOG_N1) { /* the log-energy of the sum S left one beat ago, as FA takes it with LIGHT; B0 reads it two beats on */
                 if (beat_flag<V, ns6plan::N1, 2, 1, STEADY>(i, onset, nfr)) {
                     const int e = (tick_of(i - 2, onset) + 2) & (kSlots - 1);
                     const float en = vad_frame_energy(L.frameEn[e]);
@@ -889,6 +922,12 @@ __device__ __forceinline__ void ns_pipe6_body(const NsBatchArgs &a, Pipe6Lds &L,
                 const RecPsd &r = L.p1[f & (kP1Ring - 1)]; /* G1 reads it in place three beats later (kP1Ring) */
                 RecN &o = L.rn[f & (kRnRing - 1)];
                 ns_noise1<BIN64>(r.psd, o.P, o.noise, s, eps, lane);
+            }
+            if constexpr (LOG_PAIR) {
+                if (logNow) {
+                    const float en = ns_log_lanes_take(lq, lqSum, true);
+                    if (lane < 2) L.frameEnLog[lqSlot] = en;
+                }
             }
             NS6_T_MID;
             block_sync();
@@ -1123,7 +1162,7 @@ __global__ __launch_bounds__(384, 7) void ns_denoise_pipe6_dense_kernel(NsBatchA
         g_ns6_wg[4 * blockIdx.x + 3] = __builtin_amdgcn_s_getreg((31 << 11) | (0 << 6) | 20);
     }
 #endif
-    p6::ns_pipe6_body<false, false, false, true, true, true, true, true, true>(a, L.base, &L.x);
+    p6::ns_pipe6_body<false, false, false, true, true, true, true, true, true, true>(a, L.base, &L.x);
 #ifdef SEA_NS6_TIMING
     if (threadIdx.x == 0 && blockIdx.x < 16384) g_ns6_wg[4 * blockIdx.x + 1] = (unsigned)wall_clock64();
 #endif

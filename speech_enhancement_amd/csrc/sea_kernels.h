@@ -561,6 +561,8 @@ __global__ void selftest_log_dd_kernel(const double *x, double *hi, double *lo, 
 __global__ void selftest_log_sites_kernel(const float *x, float *site1, float *site2, int n);
 __global__ void selftest_log_nonfinite_kernel(const float *x, float *site1, float *site2, float *lg, int n);
 __global__ void selftest_log_guard_kernel(int site, unsigned long long *stats, float *hits, int cap);
+template <bool ALLVAD>
+__global__ void selftest_log_lanes_kernel(unsigned long long *stats);
 __global__ void selftest_nsdiv_kernel(unsigned long long *out, int iters);
 __global__ void selftest_div_kernel(const sea_gt_tables *t, unsigned long long *mismatches);
 __global__ void rfft256_kernel(const float *in, float *out, long long nframes, const sea_fft_tables *t);
