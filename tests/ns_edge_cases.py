@@ -6,7 +6,11 @@ oracle/ns_oracle.c and oracle/ns16k_oracle.c they take (tools/oracle_coverage.py
 restatement to the reference on them, tests/test_gpu_edge_inputs.py runs the kernels on them.
 
 Every length is the shortest (in the steps that were searched, see each line) at which the signal still takes the
-branches it is there for; the whole 8 kHz set is below 400 000 samples."""
+branches it is there for; the whole 8 kHz set is below 400 000 samples.
+
+signals_wb() is the wideband (16 kHz) set: four signals carried over from the 8 kHz recipes and the wideband edge set, whose
+branches are those of the reference's own wideband code (tools/wb_oracle_coverage.py, tests/test_wb_edge_coverage_cpu.py);
+below 800 000 samples.  tests/wb_edge_cuts.py records where the time-slice tests cut it."""
 import collections
 
 import numpy as np
@@ -185,10 +189,16 @@ def streams_16k():
 
 
 # ---- wideband (16 kHz int16) mode: the quiet, onset, loud-then-zero and fade signals at 16 kHz -----------------------------
+WB_CARRIED = ("uniform_pm2", "onset_tone", "loud_then_zeros", "exp_fade")   # the four carried over from the 8 kHz recipes
+
+
 def signals_wb():
-    """name -> int16 signal at 16 kHz: the same recipes with twice the samples per unit of time"""
-    return collections.OrderedDict([("uniform_pm2", uniform_pm2(160 * 20)), ("onset_tone", _onset_tone_wb()),
-                                    ("loud_then_zeros", _loud_then_zeros_wb()), ("exp_fade", exp_fade(160 * 150))])
+    """name -> int16 signal at 16 kHz: the same recipes with twice the samples per unit of time, then the wideband edge set"""
+    s = collections.OrderedDict([("uniform_pm2", uniform_pm2(160 * 20)), ("onset_tone", _onset_tone_wb()),
+                                 ("loud_then_zeros", _loud_then_zeros_wb()), ("exp_fade", exp_fade(160 * 150))])
+    for f in _SIGNALS_WB:
+        s[f.__name__] = f()
+    return s
 
 
 def _onset_tone_wb(n=160 * 100):
@@ -202,3 +212,64 @@ def _loud_then_zeros_wb():
     from speech_enhancement_amd import corpus
     loud = np.clip(corpus.synth_wideband(6, 160 * 60).astype(np.int32) * 8, -32768, 32767).astype(np.int16)
     return np.concatenate([loud, np.zeros(24000, np.int16)])
+
+
+# ---- the wideband edge set --------------------------------------------------------------------------------------------------
+# What the REFERENCE's own wideband code needs beyond the four above and the other inputs of the wideband GPU tests: branches
+# are named by the reference's file, function and line, as tools/wb_oracle_coverage.py reports them.  The lengths and first
+# frames were found with that tool's --only NAME and --first FILE:LINE (a bisection over prefixes of the signal).
+WB_HOP = 160
+
+
+def ones_then_zeros_wb(n_noise=WB_HOP * 10, n_zero=WB_HOP * 1500):
+    """ten frames of +-1 noise, 1500 all-zero frames, ten frames of +-1 noise again: FilterCalc's two noise-estimate floors on
+    the QMF low band (NoiseSup.c:515 first taken at frame 114, :543 at frame 450) and the high band's noise estimate clamped
+    at its floor in DoSpecSub16k (16kHzProcessing.c:461, first at frame 1373: the estimate loses 1 % per frame from the level
+    the ten noise frames left).  1020 zero frames do not reach the high band's clamp, 1500 do; bisected to 1374 frames in all.
+    An all-zero frame gives high-band rows of 0 whatever the estimate holds, so the clamp shows only in what follows: the
+    zeros go on to frame 1510, where the estimate without its clamp would stand at 0.25 of the floor, and the closing noise
+    (WB_TAIL_START) subtracts 1.5 times the estimate from band energies of about a hundred."""
+    rng = _rng(6)
+    head, tail = rng.integers(-1, 2, n_noise).astype(np.int16), rng.integers(-1, 2, n_noise).astype(np.int16)
+    return np.concatenate([head, np.zeros(n_zero, np.int16), tail])
+
+
+WB_TAIL_START = 1510       # the frame at which ones_then_zeros_wb's closing noise begins
+
+
+def square8_burst_wb(n=WB_HOP * 40, start=1680):
+    """noise of sigma 15 with a full-scale square wave of period 8 (period 4 in the QMF low band) from sample 1680 to 4880:
+    GetMaximaPositions' search that finds no neighbouring maximum, to the right and to the left (WaveProc.c:145 / :155 first
+    at frame 16, :130 / :140 at frame 34), and speech found by SpeechFoundVADNS alone (VAD.c:249, first at frame 17).  Periods
+    4 / 8 / 16, starts 1680 / 1700 / 1720 / 1760 and both phases tried: only period 8 at 1680 or 1760 gives frames with the
+    last measure alone, 1680 kept; 35 frames are needed, 40 kept."""
+    x = _rng(8).standard_normal(n) * 15.0
+    k = np.arange(start, start + 3200)
+    x[start:start + 3200] += np.where((k // 4) % 2 == 0, 32767.0, -32767.0)
+    return _i16(x)
+
+
+def low_tone_after_burst_wb(n=WB_HOP * 56):
+    """noise of sigma 300, a Hann-shaped 1500 Hz tone of amplitude 300 on frames 2..11 and a 120 Hz tone of amplitude 300 on
+    frames 30..49: speech found by SpeechFoundMel alone (VAD.c:249, first at frame 34).  The 8 kHz recipe without the early
+    tone never gives it at 16 kHz (80 / 120 / 200 / 300 Hz at 0.12 .. 4 times sigma tried: the three measures fire together or
+    not at all): the early tone, while the frame counter is below 15, lifts the running maxima of the spectral and the
+    variance measure but not that of mel bands 1..3, so the later low tone passes the mel measure only.  Early tone at 1000 /
+    1500 Hz with amplitude 300 / 1000 / 3000 and the low tone at 0.25 / 0.5 / 1 times sigma tried: 1500 Hz at 300 with 1 gives
+    nine such frames, the louder early tones none."""
+    x = _rng(9).standard_normal(n) * 300.0
+    x[WB_HOP * 2:WB_HOP * 12] += np.hanning(WB_HOP * 10) * _tone(WB_HOP * 10, 1500.0, 300.0, 16000.0)
+    x[WB_HOP * 30:WB_HOP * 50] += _tone(WB_HOP * 20, 120.0, 300.0, 16000.0)
+    return _i16(x)
+
+
+def short_onset_wb(n=WB_HOP * 12):
+    """noise of sigma 15 and a 20 000-amplitude 1000 Hz tone from sample 960 to the end of a 12-frame utterance: the ring of
+    seven still holds four speech frames in a row when DoVADFlush runs with the frame counter at 35 or less, so the flush
+    raises the hang-over (VAD.c:394).  20 frames tried first; bisected to 11, 12 kept."""
+    x = _rng(3).standard_normal(n) * 15.0
+    x[960:] += _tone(n - 960, 1000.0, 20000.0, 16000.0)
+    return _i16(x)
+
+
+_SIGNALS_WB = (ones_then_zeros_wb, square8_burst_wb, low_tone_after_burst_wb, short_onset_wb)

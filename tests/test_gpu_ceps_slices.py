@@ -437,3 +437,53 @@ def test_host_pipeline_equals_one_launch(wb):
         for k, v in saved.items():
             if v is not None:
                 os.environ[k] = v
+
+
+def _wb_edge_set():
+    """the wideband edge set (tests/ns_edge_cases.signals_wb()), longest first, and the bounds tests/wb_edge_cuts.py derives
+    from the reference: -> (names, utterances, bounds)"""
+    from tests import ns_edge_cases
+    from tests import wb_edge_cuts
+    from tests.test_gpu_wb import _reference
+    _reference()                         # the cuts come from the reference run live: a missing library is a failure
+    sig = ns_edge_cases.signals_wb()
+    names = list(sig)
+    ids, utts = _sorted([sig[k] for k in names], 160)
+    return [names[u] for u in ids], utts, wb_edge_cuts.bounds()
+
+
+def test_wb_edge_signals_in_slices():
+    """The eight signals of the wideband edge set, longest first, cut at tests/wb_edge_cuts.bounds(): one-frame slices across
+    the frames at which the reference first reaches the three noise floors (the high band's and code rows carried in the
+    cepstrum's state are then the floored ones), inside the first thirteen frames and inside the stretches on the floors.
+    Rows, counts and audio are the one launch's bits, behind the plain and behind the _fd slice call."""
+    names, utts, bounds = _wb_edge_set()
+    want = _one_launch(utts, True)
+    slices = _cuts(utts, bounds, 160)
+    got, got_fd = _in_slices(len(utts), slices, True), _in_slices(len(utts), slices, True, fd=True)
+    words = 0
+    for j, name in enumerate(names):
+        _assert_equal(got[j], want[j], f"edge signal {name}")
+        _assert_equal(got_fd[j], want[j], f"edge signal {name} behind the _fd slice call")
+        words += 2 * (got[j]["ceps"].size + got[j]["out"].size + 2)
+    assert want[names.index("ones_then_zeros_wb")]["n_ceps"] > 1510
+    print(f"\n{len(slices)} slices, {words} words compared with the one launch, 0 differ")
+
+
+def test_wb_edge_signals_through_the_host_pipeline():
+    """The edge set four times over (32 utterances, enough bytes for sea_wb_denoise_ceps_utterances to cut the list) against
+    wb_denoise_batch + wb_compceps_batch: rows, counts and audio bit for bit."""
+    import speech_enhancement_amd as sea
+    names, utts, _ = _wb_edge_set()
+    lst = utts * 4
+    want = _one_launch(lst, True)
+    got = sea.wb_denoise_ceps_utterances(lst, want_lp=True)
+    assert got["slices"] > 1, f"run as {got['slices']} launch(es)"
+    words = 0
+    for u, w in enumerate(want):
+        what = f"edge signal {names[u % len(names)]} (copy {u // len(names)})"
+        assert int(got["n_ceps"][u]) == w["n_ceps"] == len(got["ceps"][u]), f"{what}: {int(got['n_ceps'][u])} rows, one launch {w['n_ceps']}"
+        assert np.array_equal(_u32(got["ceps"][u]), _u32(w["ceps"])), f"{what}: rows differ in bits from the one launch"
+        assert np.array_equal(got["out"][u][:len(w["out"])], w["out"]), f"{what}: audio differs from the one launch"
+        words += w["ceps"].size + w["out"].size + 1
+    print(f"\n{len(lst)} utterances, {got['slices']} launches, {words} words compared with the one launch, 0 differ")

@@ -360,8 +360,10 @@ def test_e_ns16k_native(oracle):
 
 
 def test_f_wideband():
-    """(f) the quiet, onset, loud-then-zero and fade signals at 16 kHz through the wideband mode and its feature chain,
-    against the reference's own code (tests/wb_reference.py, tests/wb_afe_reference.py); every value bit for bit"""
+    """(f) the quiet, onset, loud-then-zero and fade signals at 16 kHz and the wideband edge set (the noise floors of both
+    bands, WaveProc without a neighbouring maximum, speech found by one measure alone, the flush's raised hang-over:
+    tests/test_wb_edge_coverage_cpu.py) through the wideband mode and its feature chain, against the reference's own code
+    (tests/wb_reference.py, tests/wb_afe_reference.py); every value bit for bit"""
     from tests import ns_edge_cases as E
     from tests import test_gpu_wb as WB
     from tests import test_gpu_wb_afe as WA

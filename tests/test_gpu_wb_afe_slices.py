@@ -524,3 +524,55 @@ def test_host_pipeline_equals_one_launch():
                 assert np.array_equal(_u32(r["feats"][u]), _u32(w["feats"])), f"{what}: rows differ in bits from the one launch"
             assert np.array_equal(got["out"][u], lp[u]) and np.array_equal(lp[u], w["out"]), f"{what}: low band"
         print(f"\n{name}: {len(lst)} utterance(s), {got['slices']} launch(es), {sum(len(w['feats']) for w in want)} rows equal to the one launch bit for bit")
+
+
+def _edge_set():
+    """the wideband edge set (tests/ns_edge_cases.signals_wb()), longest first, and the bounds tests/wb_edge_cuts.py derives
+    from the reference: -> (names, utterances, bounds)"""
+    from tests import ns_edge_cases as E
+    from tests import wb_edge_cuts as K
+    from tests.test_gpu_wb_afe import _reference
+    _reference()                         # the cuts come from the reference run live: a missing library is a failure
+    sig = E.signals_wb()
+    names = list(sig)
+    ids, utts = _sorted([sig[k] for k in names])
+    return [names[u] for u in ids], utts, K.bounds()
+
+
+def test_edge_set_in_slices():
+    """The eight signals of the wideband edge set, longest first, cut where the reference says their branches are taken:
+    every frame of the first thirteen (the first ten frames' rules, the 12-frame utterance whose flush raises the hang-over),
+    one-frame slices across the frames at which WaveProc first finds no neighbouring maximum (16, 34), at which speech is
+    first found by VADNS alone (17) and by the mel measure alone (34), across the first frame at which a countdown alone
+    holds the VAD flag, across the three noise floors, and inside the stretches on the floors.  Everything equals the one
+    launch bit for bit, the raised hang-over included: it shows in the emitted flags behind the cut."""
+    names, utts, bounds = _edge_set()
+    assert {16, 17, 34, 35, 1373, 1374} <= set(bounds) and bounds[-1] == len(utts[0]) // 160
+    want = _one_launch(utts)
+    got = _in_slices(len(utts), _cuts(utts, bounds))
+    words = 0
+    for j, name in enumerate(names):
+        _assert_features_equal(got[j], want[j], f"edge signal {name}")
+        words += sum(got[j][k].size for k in ("feat_cc", "feat_pp", "feats", "flags", "out", "f32", "hp", "code")) + 4
+    short = want[names.index("short_onset_wb")]
+    assert len(short["feats"]) and short["feats"][:, 14].all(), "short_onset_wb: the flush no longer keeps the VAD flag up"
+    print(f"\n{len(bounds) - 1} slices, {words} words compared with the one launch, 0 differ")
+
+
+def test_edge_set_through_the_host_pipeline():
+    """The edge set four times over (32 utterances, enough bytes for sea_wb_features_utterances to cut the list) against
+    wb_afe_features_batch: emitted rows bit for bit, the low band too."""
+    import speech_enhancement_amd as sea
+    names, utts, _ = _edge_set()
+    lst = utts * 4
+    want = _one_launch(lst)
+    got = sea.wb_features_utterances(lst, want_lp=True)
+    assert got["slices"] > 1, f"run as {got['slices']} launch(es)"
+    words = 0
+    for u, w in enumerate(want):
+        what = f"edge signal {names[u % len(names)]} (copy {u // len(names)})"
+        assert got["feats"][u].shape == w["feats"].shape, f"{what}: {len(got['feats'][u])} rows, one launch {len(w['feats'])}"
+        assert np.array_equal(_u32(got["feats"][u]), _u32(w["feats"])), f"{what}: rows differ in bits from the one launch"
+        assert np.array_equal(got["out"][u], w["out"]), f"{what}: low band"
+        words += w["feats"].size + w["out"].size
+    print(f"\n{len(lst)} utterances, {got['slices']} launches, {words} words compared with the one launch, 0 differ")

@@ -305,3 +305,56 @@ def test_host_pipeline_equals_one_launch(gold):
                 assert np.array_equal(again["out"][u], got["out"][u]) and np.array_equal(_u32(again["hp_rows"][u]), _u32(got["hp_rows"][u])) \
                     and np.array_equal(_u32(again["code_rows"][u]), _u32(got["code_rows"][u])), f"{what}: two runs differ"
         print(f"\n{name}: {len(lst)} utterance(s), {got['slices']} launch(es), equal to the one launch bit for bit")
+
+
+def _edge_set():
+    """the wideband edge set (tests/ns_edge_cases.signals_wb()), longest first, and the bounds tests/wb_edge_cuts.py derives
+    from the reference: -> (names, utterances, bounds)"""
+    from tests import ns_edge_cases as E
+    from tests import test_gpu_wb as WB
+    from tests import wb_edge_cuts as K
+    WB._reference()                      # the cuts come from the reference run live: a missing library is a failure
+    sig = E.signals_wb()
+    names = sorted(sig, key=lambda k: -(len(sig[k]) // 160))
+    return names, [sig[k] for k in names], K.bounds()
+
+
+def test_edge_set_in_slices():
+    """The eight signals of the wideband edge set, longest first, cut where the reference says their branches are taken:
+    every frame of the first thirteen, one-frame slices across the frames at which the low band's two noise-estimate floors
+    (114, 450) and the high band's (1373) are first reached, across the first frame of a hang-over of the high band's VAD,
+    two cuts while the estimates sit on their floors and one-frame slices
+    across the start of the closing noise, whose rows are the first to show what the high band's estimate holds.  A state that drops the word one of these rules reads changes the
+    bits behind the cut: everything equals the one launch bit for bit."""
+    import speech_enhancement_amd as sea
+    names, utts, bounds = _edge_set()
+    assert {1373, 1374, 114, 115, 450, 451, 1510, 1511} <= set(bounds) and bounds[-1] == len(utts[0]) // 160
+    want = _one_launch(sea, utts)
+    got = _in_slices(sea, utts, bounds)
+    words = 0
+    for j, name in enumerate(names):
+        _assert_same_bits(got[j], want[j], f"edge signal {name}")
+        words += sum(got[j][k].size for k in ("out", "f32", "hp", "code")) + 2
+    hp = want[names.index("ones_then_zeros_wb")]["hp"]     # the rows that read the floored estimate: the closing noise's
+    assert not hp[1400:1500].any() and (hp[1512:1520] > 0).all() and (hp[1512:1520] < SENT_F32).all()
+    print(f"\n{len(bounds) - 1} slices, {words} words compared with the one launch, 0 differ")
+
+
+def test_edge_set_through_the_host_pipeline():
+    """The edge set four times over (32 utterances, enough bytes for sea_wb_denoise_utterances to cut the list) against
+    sea_wb_denoise_batch: low band and rows bit for bit."""
+    import speech_enhancement_amd as sea
+    _torch()
+    names, utts, _ = _edge_set()
+    lst = utts * 4
+    want = _batch_rows(sea, lst)
+    got = sea.wb_denoise_utterances(lst, want_hb=True)
+    assert got["slices"] > 1, f"run as {got['slices']} launch(es)"
+    words = 0
+    for u, (o, h, c) in enumerate(want):
+        what = f"edge signal {names[u % len(names)]} (copy {u // len(names)})"
+        assert got["out"][u].shape == o.shape and np.array_equal(got["out"][u], o), f"{what}: low band != one launch"
+        assert np.array_equal(_u32(got["hp_rows"][u]), _u32(h)), f"{what}: high-band rows != one launch"
+        assert np.array_equal(_u32(got["code_rows"][u]), _u32(c)), f"{what}: code rows != one launch"
+        words += o.size + h.size + c.size
+    print(f"\n{len(lst)} utterances, {got['slices']} launches, {words} words compared with the one launch, 0 differ")
