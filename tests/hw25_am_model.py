@@ -119,6 +119,22 @@ def hand_empty():
 HAND_CASES = {"prune": hand_prune, "sweeps": hand_sweeps, "minus2": hand_minus2, "empty": hand_empty}
 
 
+def edge_frame0():
+    """Edge set: finalSeg's develope with a unit of the growing value at frame 0 (HuWang.cpp:1456, the outcome `no earlier
+    frame`), and at the last frame.  A + segment of six frames from frame 0 in channel 5 with a labelled unit beside it at
+    frame 0, which develope (m, 1) adds; a segment below THETAT that ends at the last frame in the top channel, with a single
+    + unit beside it at the last frame, which develope (m, -1) turns to -1."""
+    c = _blank(12)
+    c["grp"][0:6, 5], c["pratio"][0:6, 5] = 1, 0.9
+    c["amcrn"][0, 6], c["cross_ev"][0, 6] = 1, 0.5
+    c["grp"][6:12, NCH - 1], c["pratio"][6:12, NCH - 1] = 1, 0.5
+    c["grp"][11, NCH - 2], c["pratio"][11, NCH - 2] = 1, 0.9
+    return c
+
+
+EDGE_HAND_CASES = {"eframe0": edge_frame0}
+
+
 def many_final_segments_case():
     """more than 400 segments in the first reSegmentation: 442 isolated columns of three frames (model only)"""
     nfr = 34 * 4 + 1

@@ -42,6 +42,44 @@ def frames(length):
     return max(int(length), 0) // HOP
 
 
+# ---- the edge inputs ------------------------------------------------------------------------------------------------------
+def edge_dc():
+    """One frame of silence, then a step to -10000 held to the end (21 frames and 10 samples): very loud and very abrupt.  The
+    gammatone's response to the constant settles below -MED_A in the low channels, so the hair cell's permeability is 0
+    there, its cleft contents fall to exactly 0 (through the clamp at 8 kHz, by underflow at 16 kHz) and hOut and hEv are
+    exactly 0 over whole ACF windows: both normalising sums of crossCorr are 0 (HuWang.cpp:408 and :413, the outcome `not
+    divided`), pRatio is 0 / 0 there.  createIBM finds no segment in it: the front half alone judges it."""
+    x = np.zeros(21 * HOP + 10, np.float32)
+    x[HOP:] = -10000.0
+    return x
+
+
+def edge_whole():
+    """A voice with vibrato from the first sample to the last (seed 1203), voiced up to the last frame: the last block of five
+    frames is voiced and three frames long, so that amPatt's window runs past the signal's end (HuWang.cpp:1221, the outcome
+    `no such sample`), and the last frame holds units for the searches and developes.
+
+    33 frames and HOP // 2 + 17 samples: with a unit set in the last frame f the reference's resynthesis stays inside its
+    weight array only if HOP f + (WINDOW - HOP - 1) < L (80 f + 119 < L at 25 bands; hw25_resynth_model.in_bounds), which
+    asks for at least half a hop after the last whole frame."""
+    L = 33 * HOP + HOP // 2 + 17
+    n = np.arange(L, dtype=np.float64)
+    f0 = 150.0 + 10.0 * np.sin(2 * np.pi * 2.5 * n / FS)
+    ph = 2 * np.pi * np.cumsum(f0) / FS
+    x = np.zeros(L)
+    for h in range(1, 40):
+        x += (2500.0 / h ** 0.6) * np.sin(h * ph) * (f0 * h < 0.475 * FS)
+    return (x + np.random.default_rng(1203).normal(0, 40, L)).astype(np.float32)
+
+
+EDGE_INPUTS = {"edc": edge_dc, "ewhole": edge_whole}
+
+
+def edge_inputs():
+    """the audio inputs of the edge set (tools/hw_oracle_coverage.py --set edge), by name"""
+    return {k: make() for k, make in EDGE_INPUTS.items()}
+
+
 # ---- step 1: the tables --------------------------------------------------------------------------------------------------
 def _phons(freq):
     """loudnessLevelInPhons:184-204: float table rows, float interpolation, the closing expression in double"""

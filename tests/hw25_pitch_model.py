@@ -136,9 +136,47 @@ def cross_case():
 HAND_CASES = {"h": handmade_case, "v": vote_case, "x": cross_case}
 
 
+def edge_grid_case():
+    """Edge set: a segment that lies against three edges of the grid at once -- frame 0, the last frame and the top channel
+    (channels NCH - 3 .. NCH - 1 over all 12 frames) -- and a second one inside.  The segment search meets a unit at frame 0
+    (HuWang.cpp:590, the outcome `no earlier frame`), at the last frame (:602) and in the top channel (:626)."""
+    return rect_case(12, [(0, 11, NCH - 3, NCH - 1, MIN_DELAY + 24, 0.99), (2, 9, 3, 5, MIN_DELAY + 24, 0.99)])
+
+
+def edge_crn_case():
+    """Edge set: pitchCrn decided by its last test (HuWang.cpp:897).  One segment whose peak delay is 41 over frames 2..7 and
+    50 over frames 8..13 (twice that on the 64-channel bank): 41 lies within 20 % of 50 counted from 50 (above 40), 50 does
+    not lie within 20 % of 41 (49.2), so `d1 > lowerP, d1 < upperP, d2 > lowerP` hold and `d2 < upperP` fails."""
+    k = MIN_DELAY // 16
+    return rect_case(16, [(2, 7, 4, 6, 41 * k, 0.99), (8, 13, 4, 6, 50 * k, 0.99)])
+
+
+def edge_rclamp_case():
+    """Edge set: rightDevelope's lower search bound clamped at MIN_DELAY (HuWang.cpp:1077): the mirror image of cross_case
+    without its cross.  Channels 0-1 are marked over frames 3..12 and peak at delay MIN_DELAY + 1 up to frame 11, at three
+    times that in frame 12, where the earlier delay keeps 600 of 1100.  rightDevelope at frame 12 finds the two delays
+    inconsistent and searches from 0.65 (MIN_DELAY + 2) - 1, which lies below MIN_DELAY.  In frame 12 the delay MIN_DELAY - 1,
+    which only a search without the clamp reaches and which is consistent with the earlier delay, holds 2000: with the clamp
+    Pitch[12] is 0, without it MIN_DELAY - 1."""
+    d = MIN_DELAY + 1
+    acf, pratio, mark = rect_case(16, [(3, 12, 0, 1, d, 0.99)])
+    acf[12, 0:2, d], acf[12, 0:2, 3 * d], acf[12, 0:2, MIN_DELAY - 1] = 600, 1100, 2000
+    return acf, pratio, mark
+
+
+def edge_lclamp_case():
+    """Edge set: edge_rclamp_case with the frames in reverse order, for leftDevelope's clamp (HuWang.cpp:999; the older
+    inputs take the outcome, but none of them changes when the clamp is removed): with the clamp Pitch[3] is 0, without
+    it MIN_DELAY - 1."""
+    return tuple(np.ascontiguousarray(a[::-1]) for a in edge_rclamp_case())
+
+
+EDGE_HAND_CASES = {"egrid": edge_grid_case, "ecrn": edge_crn_case, "erclamp": edge_rclamp_case, "elclamp": edge_lclamp_case}
+
+
 def hand_inputs(k):
     """acf, pratio, mark, cross of a hand-made case (cross zero where the case has none)"""
-    c = HAND_CASES[k]()
+    c = {**HAND_CASES, **EDGE_HAND_CASES}[k]()
     return c if len(c) == 4 else c + (np.zeros_like(c[1]),)
 
 

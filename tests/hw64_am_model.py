@@ -177,3 +177,5 @@ def hand_wide():
 
 
 HAND_CASES = {"prune": hand_prune, "sweeps": hand_sweeps, "minus2": hand_minus2, "empty": hand_empty, "wide": hand_wide}
+# the edge case of tests/hw25_am_model.py at this bank's channels (the same docstring holds)
+EDGE_HAND_CASES = _B.EDGE_HAND_CASES

@@ -54,6 +54,8 @@ def _second_instance():
 _B = _second_instance()
 frames, periphery, lowpass, acf, cross_corr, global_pitch, p_ratio, initial_mark, same_bits = (
     _B.frames, _B.periphery, _B.lowpass, _B.acf, _B.cross_corr, _B.global_pitch, _B.p_ratio, _B.initial_mark, _B.same_bits)
+# the edge inputs of tests/hw25_model.py at this bank's rate and hop: the same docstrings hold, at 16 kHz
+EDGE_INPUTS, edge_inputs = _B.EDGE_INPUTS, _B.edge_inputs
 
 
 def load_golden():

@@ -189,6 +189,10 @@ SEPARATES = {"left_mark": ("ml", 3, 80, 0), "left_number2": ("nl", 3, 0, 70), "r
              "right_number2": ("nr", 12, 0, 70)}
 
 
+# the edge cases of tests/hw25_pitch_model.py at this bank's channels and delays (the same docstrings hold)
+EDGE_HAND_CASES = _B.EDGE_HAND_CASES
+
+
 def hand_inputs(k):
     """acf [F][64][201], pratio, mark [F][64] of a hand-made case"""
-    return HAND_CASES[k]()
+    return {**HAND_CASES, **EDGE_HAND_CASES}[k]()

@@ -228,3 +228,52 @@ def test_more_utterances_than_a_grid_dimension_y_holds(case):
         got = res.utterance(u)
         assert M.same_bits(np.ascontiguousarray(got["hOut"]), hout8) and M.same_bits(np.ascontiguousarray(got["hEv"]), hev8), u
         assert got["pitch"].size == 0
+
+
+# ---- the edge set ------------------------------------------------------------------------------------------------------------
+EDGE_PERM = [2, 0, 3, 1]
+
+
+def test_edge_inputs_in_one_batch_with_present_ones(case):
+    """The edge set's audio (tests/hw25_model.EDGE_INPUTS) between the fixture's (b) and the white noise of the batch above:
+    edc, whose hair-cell output is exactly 0 over whole ACF windows (both normalising sums 0 and not divided by, pRatio 0 / 0),
+    and ewhole, voiced from the first sample to the last.  Every array against tests/golden/hw25_edge_golden.npz, bit for bit
+    (the large ones through their CRC32), in plain and permuted launch order, as one launch group and as two calls, with and
+    without the ACF outputs; guard rows and padding untouched."""
+    import torch
+    import speech_enhancement_amd as sea
+    from tests import hw_edge as E
+    e = E.load("hw25")
+    names = [None, "edc", "ewhole", None]
+    utts = [case["utts"][1], e["x_edc"], e["x_ewhole"], case["utts"][6]]
+    rows = np.array([len(x) // 80 for x in utts], np.int64)
+    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    c = dict(utts=utts, batch=sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32), rows=rows, offs=offs,
+             d_offs=torch.from_numpy(offs).to("cuda:0"), d_perm=torch.tensor(EDGE_PERM, dtype=torch.int32, device="cuda:0"))
+    assert int(np.isnan(e["front_pRatio_edc"]).sum()) > 100 and (e["front_cross_hc_edc"] == 0).sum() > 100
+    assert e["front_mark_ewhole"].sum() > 100 and e["front_mark_ewhole"][-1].sum() > 0
+    runs = {"group_plain": _launch(c, "group", False, True), "two_permuted": _launch(c, "two", True, True),
+            "group_permuted_noacf": _launch(c, "group", True, False)}
+    nrows = int(rows.sum())
+    for run in ("group_plain", "two_permuted"):
+        tally = E.Tally(f"hw25 front half, edge set, {run}")
+        for u, k in enumerate(names):
+            got = _utterance(c, runs[run], u)
+            if k:
+                E.add_front(tally, got, e, k, k)
+            else:
+                for name in ARRAYS:
+                    tally.add(got[name], case["want"][1 if u == 0 else 6][name], f"utterance {u} {name}")
+        tally.done()
+    for name in ("hout", "hev", "cross_hc", "cross_ev", "pitch", "pratio", "mark"):
+        assert M.same_bits(runs["two_permuted"][name], runs["group_permuted_noacf"][name]), name
+    for run, out in runs.items():
+        for name in ("hout", "hev"):
+            assert (out[name][c["batch"].total * NCH:] == SENT).all(), f"{run}: {name} guard"
+        for name in ("acf_hc", "acf_ev", "cross_hc", "cross_ev", "pratio", "mark"):
+            if out[name] is not None:
+                assert (out[name][nrows:] == SENT).all() and not (out[name][:nrows] == SENT).any(), f"{run}: {name} rows"
+        assert (out["pitch"][nrows:] == SENT_I).all()
+        for u in range(4):
+            got = _utterance(c, out, u)
+            assert (got["pad_hOut"] == SENT).all() and (got["pad_hEv"] == SENT).all(), f"{run}: padding of utterance {u}"

@@ -69,6 +69,17 @@ N_FIX = len(AM.AUDIO_CASES)
 PERM = [13, 4, 8, 0, 11, 6, 2, 9, 7, 12, 1, 5, 10, 3]
 
 
+def extra_inputs():
+    """the short inputs of the audio batch that the fixture does not hold (the models judge them): no sample, no frame, one
+    frame, three frames, five frames; also what tools/hw_oracle_coverage.py feeds the reference as part of `hw-tests`"""
+    n = np.arange(400)
+    xs = PM.audio_inputs()
+    return [np.zeros(0, np.float32), (40 * np.sin(2 * np.pi * 200 * n[:79] / 8000)).astype(np.float32),
+            (900 * np.sin(2 * np.pi * 300 * n[:80] / 8000)).astype(np.float32),
+            (3000 * np.sin(2 * np.pi * 125 * n[:240] / 8000) + 1500 * np.sin(2 * np.pi * 250 * n[:240] / 8000)).astype(np.float32),
+            xs["p"][2000:2400].copy()]
+
+
 def am_launch(a, order=None, details=True):
     """sea_hw25_am_batch on sentinel-filled outputs with guard rows -> numpy arrays"""
     import torch
@@ -97,12 +108,7 @@ def audio():
     g = AM.load_golden()
     t = M.tables()
     utts = [g[f"x_{k}"] for k in AM.AUDIO_CASES]
-    n = np.arange(400)
-    xs = PM.audio_inputs()
-    extra = [np.zeros(0, np.float32), (40 * np.sin(2 * np.pi * 200 * n[:79] / 8000)).astype(np.float32),
-             (900 * np.sin(2 * np.pi * 300 * n[:80] / 8000)).astype(np.float32),
-             (3000 * np.sin(2 * np.pi * 125 * n[:240] / 8000) + 1500 * np.sin(2 * np.pi * 250 * n[:240] / 8000)).astype(np.float32),
-             xs["p"][2000:2400].copy()]
+    extra = extra_inputs()
     model = []
     for x in extra:  # the whole chain from the models
         fr = M.frontend(x, t) if len(x) >= 80 else None
@@ -526,3 +532,114 @@ def test_fft_in_five_channel_groups_and_a_pitch_out_of_range(audio):
             assert out["status"][u] == (AM.AM_BAD_PITCH if u == N_FIX else 0), f"utterance {u}: status {int(out['status'][u]):#x}"
             assert not any(out[name][r0:r0 + n].any() for name in ("amcrn", "ratio", "seng")), f"utterance {u}"
             assert not blocks["ampatt"][:, :L].any() and not blocks["am"][:, :L].any(), f"utterance {u}"
+
+
+# ---- the edge set ------------------------------------------------------------------------------------------------------------
+def test_edge_set_through_the_am_stage_the_whole_estimator_and_final_grouping():
+    """The edge set (tests/test_hw_edge_coverage_cpu.py) against tests/golden/hw25_edge_golden.npz.
+
+    Audio, in one batch after the fixture's w1600: edc (a step whose ACF rows are exactly 0 and whose pRatio is 0 / 0) and
+    ewhole (voiced up to the last frame, its last block of five frames three frames long, so that the pattern filter's window
+    runs past the signal's end).  Where the reference finds no segment in edc (at 25 bands) the fixture holds its front half
+    alone and the expected arrays are the models' (tests/hw_edge.model_chain): no voiced frame, no label, an empty mask,
+    status 0.  The AM stage runs from the expected pitch (AmCrn exact, sEng and the patterns bit for bit, ratio within the
+    fixture's ratio_tol), then the whole estimator (mask, pitch, status, finalSeg's stages), each in plain and permuted order
+    and without the optional outputs.
+
+    finalSeg: eframe0 (units of the growing value at frame 0 and at the last frame, in the top channel) and the edge audio's
+    stage inputs, after the fixture's prune.
+
+    Units of both signs come from eframe0 alone, which is asserted.  The edge audio is not meant to give a -1 unit and gives
+    none at either bank: it is there for the ends of the signal and for the zero rows.  The -1 units from audio are those of
+    the fixture's own cases, among them w1600, the neighbour in this batch."""
+    import torch
+    import speech_enhancement_amd as sea
+    from tests import hw_edge as E
+    e, g = E.load("hw25"), AM.load_golden()
+    keys = ["w1600"] + list(E.AUDIO)
+    src = [g] + [E.source("hw25", k) for k in E.AUDIO]
+    modelled = [False] + [f"status_{k}" in s for s, k in zip(src[1:], keys[1:])]
+    assert keys[1:] == ["edc", "ewhole"] and not modelled[2] and modelled[1] == True
+    utts = [s[f"x_{k}"] for s, k in zip(src, keys)]
+    batch = sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32)
+    rows = np.asarray(batch.host_lengths, dtype=np.int64) // 80
+    offs = np.concatenate(([0], np.cumsum(rows)[:-1])).astype(np.int64)
+    gout = sea.hw25_periphery_gout_batch(batch)[2]
+    pitch = np.concatenate([s[f"pitch_{k}"] for s, k in zip(src, keys)]).astype(np.int32)
+    a = dict(utts=utts, batch=batch, rows=rows, offs=offs, gout=gout, pitch=torch.from_numpy(pitch).to("cuda:0"),
+             row_offsets=torch.from_numpy(offs).to("cuda:0"))
+    tol = float(e["ratio_tol"])
+    assert tol == float(g["ratio_tol"])
+    assert (e["pitch_ewhole"] > 0).sum() >= 25 and e["pitch_ewhole"][-1] > 0 and e["amcrn_ewhole"].sum() > 100 and e["mask_ewhole"].sum() > 100
+    assert not (e["grp_final_ewhole"] < 0).any() and (g["grp_final_w1600"] < 0).any()    # see the docstring
+    order = torch.tensor(list(reversed(range(len(keys)))), dtype=torch.int32, device="cuda:0")
+    for run, kw in (("plain", {}), ("permuted", dict(order=order)), ("no details", dict(details=False))):
+        out = am_launch(a, **kw)[0]
+        tally = E.Tally(f"hw25 AM stage, edge audio, {run}")
+        for u, (s, k) in enumerate(zip(src, keys)):
+            r0, n, L = int(offs[u]), int(rows[u]), len(utts[u])
+            assert out["status"][u] == 0
+            tally.add(out["amcrn"][r0:r0 + n], s[f"amcrn_{k}"].astype(np.float32), f"{k} amcrn")
+            if out["seng"] is None:
+                continue
+            tally.add(out["seng"][r0:r0 + n], s[f"seng_{k}"], f"{k} seng")
+            ref, got = s[f"ratio_{k}"], out["ratio"][r0:r0 + n]
+            on = ref != 0
+            assert np.array_equal(got != 0, on), f"{run}, {k}: the units where sinModel runs"
+            if on.any():
+                rel = np.abs(got[on].astype(np.float64) - ref[on]) / ref[on]
+                print(f"{run}, {k}: ratio's largest relative difference {rel.max():.3g} (tolerance {tol:.3g}) over {int(on.sum())} units")
+                assert rel.max() <= tol, f"{run}, {k}: ratio"
+            else:
+                assert modelled[u], f"{k}: sinModel runs on no unit"
+            for name in ("ampatt", "am"):
+                off, pitch_ = int(batch.host_offsets[u]), (L + 7) // 8 * 8
+                b = out[name][off * NCH:off * NCH + NCH * pitch_].reshape(NCH, pitch_)
+                assert (b[:, L:] == SENT).all(), f"{run}, {k}: {name}'s padding"
+                if modelled[u]:
+                    tally.add(b[:, :L], s[f"{name}_{k}"], f"{k} {name}")
+                else:
+                    _against_crcs(b[:, :L], s, name, k)
+                    tally.words += NCH * L
+        tally.done()
+        assert (out["amcrn"][int(rows.sum()):] == SENT).all()
+    for run, kw in (("plain", {}), ("permuted", dict(order=order)), ("no stages", dict(stages=False))):
+        out = ibm_launch(a, **kw)
+        tally = E.Tally(f"hw25 whole estimator, edge audio, {run}")
+        for u, (s, k) in enumerate(zip(src, keys)):
+            r0, n = int(offs[u]), int(rows[u])
+            status = int(out["status"][u])
+            if modelled[u]:
+                assert status == s[f"status_{k}"] == 0, f"{run}, {k}: status {status:#x}, expected no segment (0)"
+            else:
+                assert status >> 16 == 0 and status > 0, f"{run}, {k}: status {status:#x}"
+            tally.add(out["mask"][r0:r0 + n], s[f"mask_{k}"].astype(np.float32), f"{k} mask")
+            tally.add(out["pitch"][r0:r0 + n], s[f"pitch_{k}"], f"{k} pitch")
+            if out["stages"] is not None:
+                st = out["stages"][r0 * FW:(r0 + n) * FW].reshape(len(AM.FINAL_STAGES), n, NCH)
+                for i, name in enumerate(AM.FINAL_STAGES):
+                    tally.add(st[i], s[f"{name}_{k}"].astype(np.float32), f"{k} {name}")
+        tally.done()
+        total = int(rows.sum())
+        assert (out["mask"][total:] == SENT).all() and (out["pitch"][total:] == SENT_I).all() and (out["status"][len(keys):] == SENT_I).all()
+    # finalSeg
+    names = [("prune", g), ("eframe0", e)] + list(zip(keys[1:], src[1:]))
+    cases = [AM.HAND_CASES["prune"](), AM.EDGE_HAND_CASES["eframe0"]()]
+    cases += [{n: np.asarray(s[f"{n}_{k}"]).astype(np.float32) for n in ("grp", "amcrn", "cross_ev", "pratio")} for k, s in names[2:]]
+    w0 = e["grp_final_eframe0"]
+    assert (w0 < 0).sum() > 0 and e["mask_eframe0"].sum() > 0 and e["mask_eframe0"][0].any() and w0[-1, NCH - 1] < 0 and w0[-1, NCH - 2] < 0
+    perm = torch.tensor(list(reversed(range(len(cases)))), dtype=torch.int32, device="cuda:0")
+    for run, kw in (("plain", {}), ("permuted", dict(order=perm)), ("bare", dict(stages=False, grp_final=False))):
+        out, frows, foffs = final_launch(cases, **kw)
+        tally = E.Tally(f"hw25 finalSeg, edge set, {run}")
+        for u, (k, s) in enumerate(names):
+            r0, n = int(foffs[u]), int(frows[u])
+            assert int(out["status"][u]) == 0
+            tally.add(out["mask"][r0:r0 + n], s[f"mask_{k}"].astype(np.float32), f"{k} mask")
+            if out["grp_final"] is not None:
+                tally.add(out["grp_final"][r0:r0 + n], s[f"grp_final_{k}"].astype(np.float32), f"{k} grp_final")
+            if out["stages"] is not None:
+                st = out["stages"][r0 * FW:(r0 + n) * FW].reshape(len(AM.FINAL_STAGES), n, NCH)
+                for i, name in enumerate(AM.FINAL_STAGES):
+                    tally.add(st[i], s[f"{name}_{k}"].astype(np.float32), f"{k} {name}")
+        tally.done()

@@ -327,3 +327,41 @@ def test_null_and_shared_buffers_are_refused(hand):
         a, s = out[off:off + L].cpu().numpy(), out16[off:off + L].cpu().numpy()
         m = d_mask[int(offs[u]):int(offs[u]) + int(rows[u])].cpu().numpy()
         assert M.same_bits(a, RM.resynth_input(i, m)) and np.array_equal(s, RM.to_short(a)), i
+
+
+# ---- the edge set ------------------------------------------------------------------------------------------------------------
+def test_edge_set_through_resynthesis_and_the_host_forms():
+    """The edge set's audio (tests/test_hw_edge_coverage_cpu.py: edc, and ewhole with units in its last frame) against
+    tests/golden/hw25_edge_golden.npz, bit for bit: resynthesis of the expected mask in one batch after a fixture input, then
+    once end to end through the host forms (sea_hw25_ibm, sea_hw25_enhance), whose mask and pitch are createIBM's and whose audio is the
+    resynthesis of that mask.  Where the reference finds no segment in edc (at 25 bands) the fixture holds its front half alone
+    and the expected mask (empty), pitch (unvoiced), status (0) and audio are the models' (tests/hw_edge.model_chain)."""
+    import speech_enhancement_amd as sea
+    from tests import hw_edge as E
+    e, am = E.load("hw25"), AM.load_golden()
+    keys = list(E.AUDIO)
+    src = [E.source("hw25", k) for k in keys]
+    assert keys == ["edc", "ewhole"] and ("status_edc" in src[0]) == True and "status_ewhole" not in src[1]
+    assert e["mask_ewhole"][-1].any() and np.abs(e["out_ewhole"]).max() > 1000
+    xs = [am["x_w1600"]] + [s[f"x_{k}"] for s, k in zip(src, keys)]
+    masks = [am["mask_w1600"].astype(np.float32)] + [s[f"mask_{k}"].astype(np.float32) for s, k in zip(src, keys)]
+    want = [RM.load_golden()["out_a_w1600"]] + [s[f"out_{k}"] for s, k in zip(src, keys)]
+    batch = _pack(xs)
+    got, _ = launch(batch, _gout(batch), masks)
+    tally = E.Tally("hw25 resynthesis, edge audio in one batch")
+    for u, w in enumerate(want):
+        tally.add(got[u], w, f"utterance {u}")
+    tally.done()
+    tally = E.Tally("hw25 host forms, edge audio end to end")
+    enhs = [sea.hw25_enhance(x) for x in xs[1:]]
+    for k, s, x, enh in zip(keys, src, xs[1:], enhs):
+        ibm = sea.hw25_ibm(x)
+        for name, r in (("ibm", ibm), ("enhance", enh)):
+            if f"status_{k}" in s:
+                assert r["status"] == s[f"status_{k}"] == 0, f"{k} {name}: status {r['status']:#x}, expected no segment (0)"
+            else:
+                assert r["status"] >> 16 == 0 and r["status"] > 0, f"{k} {name}: status {r['status']:#x}"
+            tally.add(r["mask"], s[f"mask_{k}"].astype(np.float32), f"{k} {name} mask")
+            tally.add(r["pitch"], s[f"pitch_{k}"], f"{k} {name} pitch")
+        tally.add(enh["audio"], s[f"out_{k}"], f"{k} enhanced audio")
+    tally.done()

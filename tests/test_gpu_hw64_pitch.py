@@ -108,6 +108,15 @@ PERM = [4, 8, 0, 6, 2, 9, 7, 1, 5, 3]
 NGOLD = len(PM.AUDIO_CASES)
 
 
+def extra_inputs():
+    """the inputs of the audio batch that the fixture does not hold (the model judges them): s, no frame, two, three and five
+    frames; also what tools/hw_oracle_coverage.py feeds the reference as part of `hw-tests`"""
+    xs = PM.audio_inputs()
+    n = np.arange(480)
+    tone = (3000 * np.sin(2 * np.pi * 125 * n / 16000) + 1500 * np.sin(2 * np.pi * 250 * n / 16000)).astype(np.float32)
+    return [xs["s"], tone[:159].copy(), tone[:320].copy(), tone, xs["p"][4000:4800].copy()]
+
+
 @pytest.fixture(scope="module")
 def audio():
     """the batch, its front half on the GPU (computed once, never changed) and what every utterance must give"""
@@ -116,9 +125,7 @@ def audio():
     g = PM.load_golden()
     xs = PM.audio_inputs()
     utts = [g[f"x_{k}"] for k in PM.AUDIO_CASES]
-    n = np.arange(480)
-    tone = (3000 * np.sin(2 * np.pi * 125 * n / 16000) + 1500 * np.sin(2 * np.pi * 250 * n / 16000)).astype(np.float32)
-    utts += [xs["s"], tone[:159].copy(), tone[:320].copy(), tone, xs["p"][4000:4800].copy()]
+    utts += extra_inputs()
     assert [len(x) // HOP for x in utts] == [75, 75, 87, 62, 62, 50, 0, 2, 3, 5]
     batch = sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32)
     front = sea.hw64_frontend_batch(batch, want_acf=True)
@@ -292,3 +299,59 @@ def test_grid_stride_loops_reach_their_third_trip(audio):
     assert_guards(out, 5 * n_utt, n_utt)
     for u in range(n_utt):
         assert_equal(utterance(out, offs, rows, u), wants[pick[u]], f"utterance {u} (rows from {pick[u]})")
+
+
+# ---- the edge set ------------------------------------------------------------------------------------------------------------
+def test_edge_set_audio_and_handmade_arrays():
+    """The edge set (tests/test_hw_edge_coverage_cpu.py) against tests/golden/hw64_edge_golden.npz, every output and stage bit
+    for bit.  Audio: ewhole (voiced up to the last frame) and edc (whole ACF rows exactly 0, pRatio 0 / 0; where the reference
+    finds no segment in it the fixture holds nothing and the model judges) in one batch after the fixture's m9, through the
+    front half on the GPU, in plain and permuted order and with null d_stages.  Hand-made: egrid (a segment against frame 0,
+    the last frame and the top channel), ecrn (pitchCrn decided by its last test) and erclamp / elclamp (the Developes' search bound
+    clamped at MIN_DELAY, where it decides Pitch) in one batch after the fixture's v."""
+    import torch
+    import speech_enhancement_amd as sea
+    from tests import hw_edge as E
+    e, g = E.load("hw64"), PM.load_golden()
+    utts = [g["x_m9"], e["x_ewhole"], e["x_edc"]]
+    batch = sea.PackedBatch.from_arrays(utts, device="cuda:0", dtype=np.float32)
+    front = sea.hw64_frontend_batch(batch, want_acf=True)
+    torch.cuda.synchronize()
+    rows, offs = np.asarray(front.host_rows), np.asarray(front.host_row_offsets)
+    inp = dict(acf=front.acf_hc, cross=front.cross_hc, pratio=front.pratio, mark=front.mark, lengths=batch.lengths,
+               row_offsets=front.row_offsets)
+    for u, k in ((1, "ewhole"), (2, "edc")):
+        assert PM.crc32(front.utterance(u)["acf_hc"]) == int(e[f"front_acf_hc_crc_{k}"]), f"{k}: the FRONT half's ACF differs"
+    want = [_from_golden(g, "m9"), E.pitch_want(e, "ewhole", PM.PITCH_STAGES, PM.GRP_STAGES)]
+    if "nseg_edc" in e:
+        want.append(E.pitch_want(e, "edc", PM.PITCH_STAGES, PM.GRP_STAGES))
+    else:
+        fr = {k: inp[k].cpu().numpy()[int(offs[2]):int(offs[2] + rows[2])] for k in ("acf", "pratio", "mark", "cross")}
+        want.append(PM.pitch_stage(fr["acf"], fr["pratio"], fr["mark"]))
+        assert want[2]["status"] == 0
+    assert (want[1]["pitch"] > 0).sum() >= 25 and want[1]["pitch"][-1] > 0 and (want[1]["grp"] > 0).sum() > 100
+    runs = {"plain": pitch_launch(inp, rows), "nostages": pitch_launch(inp, rows, stages=False),
+            "permuted": pitch_launch(inp, rows, order=torch.tensor([1, 2, 0], dtype=torch.int32, device="cuda:0"))}
+    for run, out in runs.items():
+        tally = E.Tally(f"hw64 pitch stage, edge audio, {run}")
+        for u, w in enumerate(want):
+            E.add_pitch(tally, utterance(out, offs, rows, u), w, NAMES if out["stages"] is not None else ("pitch", "grp", "pratio"),
+                        f"utterance {u}")
+        tally.done()
+        assert_guards(out, int(rows.sum()), len(utts))
+    hand = ("egrid", "ecrn", "erclamp", "elclamp")
+    cases = [PM.hand_inputs("v")] + [PM.hand_inputs(k) for k in hand]
+    want = [_from_golden(g, "v")] + [E.pitch_want(e, k, PM.PITCH_STAGES, PM.GRP_STAGES) for k in hand]
+    assert want[1]["grp"][0].any() and want[1]["grp"][-1].any() and want[1]["grp"][:, NCH - 1].any()
+    assert (want[2]["pitch"] > 0).any() and (want[3]["pitch"] > 0).any() and want[3]["pitch"][12] == 0 and want[4]["pitch"][3] == 0
+    assert all((w["grp"] > 0).any() for w in want[1:])    # no - unit: none of these inputs is meant to give one
+    inp, rows, offs = _device_inputs(cases)
+    for run, kw in (("plain", {}), ("permuted", dict(order=torch.tensor([3, 1, 4, 0, 2], dtype=torch.int32, device="cuda:0"))),
+                    ("nostages", dict(stages=False))):
+        out = pitch_launch(inp, rows, **kw)
+        tally = E.Tally(f"hw64 pitch stage, edge hand-made arrays, {run}")
+        for u, w in enumerate(want):
+            E.add_pitch(tally, utterance(out, offs, rows, u), w, NAMES if out["stages"] is not None else ("pitch", "grp", "pratio"),
+                        f"hand-made {u}")
+        tally.done()
+        assert_guards(out, int(rows.sum()), len(cases))

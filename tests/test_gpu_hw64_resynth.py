@@ -318,3 +318,41 @@ def test_null_buffers_are_refused():
     import speech_enhancement_amd as sea
     whole = sea.hw64_enhance(x)
     assert M.same_bits(out, whole["audio"]) and status[0] == whole["status"]
+
+
+# ---- the edge set ------------------------------------------------------------------------------------------------------------
+def test_edge_set_through_resynthesis_and_the_host_forms():
+    """The edge set's audio (tests/test_hw_edge_coverage_cpu.py: edc, and ewhole with units in its last frame) against
+    tests/golden/hw64_edge_golden.npz, bit for bit: resynthesis of the expected mask in one batch after a fixture input, then
+    once end to end through the host forms (sea_hw64_ibm, sea_hw64_enhance_utterances), whose mask and pitch are createIBM's
+    and whose audio is the resynthesis of that mask.  At this bank the reference finds a segment in edc and the fixture holds
+    all of its arrays; tests/hw_edge.source would take the models' where it did not, as at 25 bands."""
+    import speech_enhancement_amd as sea
+    from tests import hw_edge as E
+    e, am = E.load("hw64"), AM.load_golden()
+    keys = list(E.AUDIO)
+    src = [E.source("hw64", k) for k in keys]
+    assert keys == ["edc", "ewhole"] and ("status_edc" in src[0]) == False and "status_ewhole" not in src[1]
+    assert e["mask_ewhole"][-1].any() and np.abs(e["out_ewhole"]).max() > 1000
+    xs = [am["x_w4096"]] + [s[f"x_{k}"] for s, k in zip(src, keys)]
+    masks = [am["mask_w4096"].astype(np.float32)] + [s[f"mask_{k}"].astype(np.float32) for s, k in zip(src, keys)]
+    want = [RM.load_golden()["out_a_w4096"]] + [s[f"out_{k}"] for s, k in zip(src, keys)]
+    got = resynth_list(xs, masks)[0]
+    tally = E.Tally("hw64 resynthesis, edge audio in one batch")
+    for u, w in enumerate(want):
+        tally.add(got[u], w, f"utterance {u}")
+    tally.done()
+    tally = E.Tally("hw64 host forms, edge audio end to end")
+    res = enhance_list(xs[1:])
+    enhs = [{n: res[n][i] for n in ("audio", "mask", "pitch", "status")} for i in range(len(keys))]
+    for k, s, x, enh in zip(keys, src, xs[1:], enhs):
+        ibm = sea.hw64_ibm(x)
+        for name, r in (("ibm", ibm), ("enhance", enh)):
+            if f"status_{k}" in s:
+                assert r["status"] == s[f"status_{k}"] == 0, f"{k} {name}: status {r['status']:#x}, expected no segment (0)"
+            else:
+                assert r["status"] >> 16 == 0 and r["status"] > 0, f"{k} {name}: status {r['status']:#x}"
+            tally.add(r["mask"], s[f"mask_{k}"].astype(np.float32), f"{k} {name} mask")
+            tally.add(r["pitch"], s[f"pitch_{k}"], f"{k} {name} pitch")
+        tally.add(enh["audio"], s[f"out_{k}"], f"{k} enhanced audio")
+    tally.done()

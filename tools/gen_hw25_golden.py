@@ -20,6 +20,10 @@ mark_k [F][25], pitch_k [F]; the tables cf, bw, midEarCoeff, winsize [25] and lp
 The large float arrays (hOut, hEv, both ACFs) are stored as their four byte planes, uint8 [4][shape], least significant byte
 first: zlib packs the sign / exponent planes far tighter than interleaved floats (1.09 MB -> 0.87 MB), which keeps the file
 under 1 MiB.  tests/hw25_model.py::load_golden() puts them together again.
+
+Before the file is written the tool asserts, on the instrumented build that `make -C oracle hwcov` leaves under
+oracle/_ref/hwcov (tools/hw_oracle_coverage.py), that its inputs execute every executable line of HuWang.cpp:117-465 but the
+two of UNREACHABLE below.
 """
 import os
 import subprocess
@@ -185,6 +189,20 @@ def outcomes(r):
     return np.array([(cross & energy).sum(), (~cross & energy).sum(), (cross & ~energy).sum(), (~cross & ~energy).sum()])
 
 
+# loudnessLevelInPhons's refusal of a frequency outside its table (:191-192): the centre frequencies are constants inside it
+UNREACHABLE = {191: "loudnessLevelInPhons: every centre frequency lies inside 20..12500 Hz", 192: "the same refusal's exit"}
+
+
+def assert_lines_executed(bank, signals):
+    """every executable line of the front half's functions (HuWang.cpp:117-465; createIBM above them is not called by the
+    driver) but UNREACHABLE ran on the fixture's inputs, on the instrumented build of `make -C oracle hwcov`"""
+    sys.path.insert(0, ROOT)
+    from tools import hw_oracle_coverage as C
+    executable, missed = C.front_lines_missed(bank, signals, 117, 465)
+    print(f"HuWang.cpp:117-465: {executable} executable lines, never executed: " + ", ".join(f"{n} ({UNREACHABLE.get(n, '?')})" for n in missed))
+    assert executable > 150 and set(missed) == set(UNREACHABLE), f"expected exactly the unreachable lines {sorted(UNREACHABLE)}, got {missed}"
+
+
 def main():
     ref_root = sys.argv[1] if len(sys.argv) > 1 else "/root/reference"
     data, total = {}, np.zeros(4, np.int64)
@@ -206,6 +224,7 @@ def main():
             if k in "abc":
                 total += o
     assert len(data["lp"]) == 91 and (data["winsize"][:3] > 200).all()
+    assert_lines_executed("hw25", inputs().values())
     assert (total >= 5).all(), f"the labelling's four outcomes over (a)-(c) are {total.tolist()}: each needs 5 cells"
     np.savez_compressed(PATH, **data)
     assert os.path.getsize(PATH) < 1 << 20, "the fixture must stay under 1 MiB"

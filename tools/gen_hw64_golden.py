@@ -25,6 +25,9 @@ Files (every one under 1 MiB):
     hw64_acf_k.npz         acf_hc_k, acf_ev_k [F][64][201], k = a, b, c
 The large float arrays are stored as their four byte planes, uint8 [4][shape], least significant byte first, as in
 hw25_golden.npz.  tests/hw64_model.py::load_golden() puts everything together again.
+
+Before hw64_golden.npz is written the tool asserts what tools/gen_hw25_golden.py asserts: on the instrumented 64-band build
+under oracle/_ref/hwcov its inputs execute every executable line of HuWang.cpp:117-465 but that tool's UNREACHABLE.
 """
 import hashlib
 import os
@@ -36,7 +39,7 @@ import tempfile
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from gen_hw25_golden import DRIVER, outcomes, planes  # noqa: E402
+from gen_hw25_golden import DRIVER, assert_lines_executed, outcomes, planes  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -155,6 +158,7 @@ def main():
     assert (data["winsize"][8:] == 320).all() and int(data["winsize"].sum()) == 23396
     assert (total >= 5).all(), f"the labelling's four outcomes over (a)-(c) are {total.tolist()}: each needs 5 cells"
     print(f"outcomes over (a)-(c): {total.tolist()}, pitches {min(pitches)}..{max(pitches)}")
+    assert_lines_executed("hw64", inputs().values())
     save("hw64_golden.npz", **data)
 
 
