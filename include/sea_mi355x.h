@@ -950,6 +950,46 @@ enum {
 double sea_dnn_last_stage_ms(int stage);
 
 /* ----------------------------------------------------------------------------------------------
+ * Objective scores: enhanced audio against clean audio, an estimated mask against the ideal one (csrc/score_kernel.hip,
+ * csrc/score_capi.hip).  Host pointers only.  With int16 audio every energy is an exact integer and
+ * the logarithm is sea_lnf of csrc/dnn_math.h, so the plain-C model tests/score_model_driver.c reproduces every result bit
+ * for bit.
+ *
+ * sea_score_utterances: ref[u] and est[u] hold lengths[u] samples (0 .. 2^31 - 1), hop is 80 (8 kHz) or 160 (16 kHz), a frame
+ * is 2 hop samples every hop: F = L < 2 hop ? 0 : (L - 2 hop) / hop + 1 (at hop 160 the rows of the cochleagram and the
+ * masks).  sums[u] = {Srr, See, Sre}: the sums of ref^2, est^2 and ref est (signed) over ALL L samples.  Per frame f < F, over
+ * samples hop f .. hop f + 2 hop - 1: srr, see, sre likewise and n = srr - 2 sre + see; a frame with srr == 0 is skipped,
+ * otherwise d = (sea_lnf ((float)(srr + 1)) - sea_lnf ((float)(n + 1))) * 0x1.15f2cep+2f (one conversion each, a float
+ * subtract, a float multiply by the float nearest 10 / ln 10), clamped to [-10, 35].  seg_frames[u]: the frames used.
+ * seg_sum[u]: p[l] = the sum over i ascending of (double) d[64 i + l] (a skipped frame adds nothing), then the sum of p[l] over
+ * l = 0..63 ascending.  frame_db: NULL, or per utterance NULL or [F] floats that receive d, a skipped frame the bit pattern
+ * 0x7fc00000.  SNR, SI-SDR and the segmental SNR follow from these on the host (speech_enhancement_amd/scores.py).
+ * sea_mask_score_utterances: est[u] and ideal[u] [n_rows[u]][64]; a unit is on iff value > threshold, strictly (a NaN is off);
+ * counts[u] = {n11, n10, n01, n00}, the units with est on / ideal on, est on / ideal off, est off / ideal on, both off.
+ * Both return non-zero, with a sea_last_error message and before any device call, for n_utt < 0, a hop other than 80 or 160, a
+ * threshold that is not finite, a NULL argument (frame_db excepted), a negative length or row count, a length above
+ * 2^31 - 1, or a NULL buffer of an utterance that has samples or rows; the scalars are looked at first, then n_utt == 0
+ * returns 0 whatever the pointers.  An utterance without samples or rows may have NULL buffers; its outputs are zeros.
+ * Lists run in chunks of whole utterances in list order, a chunk's device footprint held to 60 % of the HBM that is free
+ * (SEA_SCORE_SCRATCH_MB overrides the budget); sea_score_last_chunks: how many chunks the last such call of this thread ran.
+ * Results do not depend on the cut.  There is no CPU fallback.
+ * sea_score_last_stage_ms: the device time in ms of a kernel (SEA_SCORE_STAGE_*) in this thread's last call that ran it,
+ * between events, summed over the chunks; -1 for an unknown stage.  For measurement (tools/bench_extra.py --what score).
+ * -------------------------------------------------------------------------------------------- */
+int sea_score_utterances(const short *const *ref, const short *const *est, const long *lengths, int n_utt, int hop,
+                         long long *sums, double *seg_sum, int *seg_frames, float *const *frame_db);
+int sea_mask_score_utterances(const float *const *est, const float *const *ideal, const int *n_rows, int n_utt, float t_est,
+                              float t_ideal, long long *counts);
+int sea_score_last_chunks(void);
+enum {
+    SEA_SCORE_STAGE_FRAMES = 0, /* score_frames_kernel */
+    SEA_SCORE_STAGE_FINISH = 1, /* score_finish_kernel */
+    SEA_SCORE_STAGE_MASK = 2,   /* mask_score_kernel */
+    SEA_SCORE_STAGE_COUNT = 3
+};
+double sea_score_last_stage_ms(int stage);
+
+/* ----------------------------------------------------------------------------------------------
  * Training that network: minibatch SGD with momentum on Kaldi nnet1's MSE, 1/2 sum e^2 (csrc/dnn_train_kernel.hip,
  * csrc/dnn_train_capi.hip).  Host pointers only, one internal stream.  The plain-C model
  * tests/dnn_train_model_driver.c reproduces every value bit for bit (-0 equals +0).  All operations are float, individually

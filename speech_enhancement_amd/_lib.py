@@ -153,6 +153,10 @@ PROTOTYPES = {
     "sea_dnn_trainer_read": (_i, [_vp, _i, _i, _vp]),
     "sea_dnn_get_params": (_i, [_vp, _vp, _vp]),
     "sea_dnn_trainer_stage_ms": (_c.c_double, [_vp, _i]),
+    "sea_score_utterances": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sea_mask_score_utterances": (_i, [_vp, _vp, _vp, _i, _c.c_float, _c.c_float, _vp]),
+    "sea_score_last_chunks": (_i, []),
+    "sea_score_last_stage_ms": (_c.c_double, [_i]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

@@ -12,7 +12,8 @@
  *
  * Both kernels are fdlibm's float forms (e_logf.c, e_expf.c: the argument reductions and the minimax coefficients are
  * published there).  Measured over every argument that can occur (tests/test_dnn_cpu.py): sea_lnf within 1 ulp of the
- * double log on every float of [1, 2^39]; sea_expf within 2^-23 relative wherever the result is a normal float.
+ * double log on every float of [1, 2^39] (and of (2^39, 2^41], which only the scores of score_kernel.hip reach:
+ * tests/test_scores_cpu.py); sea_expf within 2^-23 relative wherever the result is a normal float.
  */
 #ifndef SEA_DNN_MATH_H
 #define SEA_DNN_MATH_H

@@ -21,6 +21,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what hw64resynth --steps 3  # the same at 16 kHz on the 64-channel bank, through the host-list forms; also writes profiles/hw64resynth_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what dnn --steps 5  # the DNN mask estimator: cochleagram, every layer (TFLOP/s), the chain, beside the resynthesis alone and hw64_enhance_utterances; also writes profiles/dnn_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what dnntrain  # its trainer: 200 SGD steps at minibatch 256, 1024 and 4096, every stage (TFLOP/s per GEMM beside the forward layer at the same M), steps/s, an epoch's time; also writes profiles/dnntrain_bench_extra.jsonl, opt-in
+    python tools/bench_extra.py --what score --steps 5  # the objective scores: each kernel between device events beside the bytes it reads, the host calls' wall time; also writes profiles/score_bench_extra.jsonl, opt-in
 """
 import argparse
 import json
@@ -1787,6 +1788,68 @@ def main():
                   "config": {"workload": workload, "run_s_sorted": [round(v, 4) for v in w]}})
         trainer.close()
         with open(os.path.join(ROOT, "profiles", "dnntrain_bench_extra.jsonl"), "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    if "score" in what:
+        # The objective scores on the --utts corpus batch taken as 16 kHz int16 utterances: the clean
+        # audio against itself plus a quarter of the next utterance's samples, hop 160, and two seeded masks of the corpus's row
+        # count.  The calls take host memory only and time their own kernels with device events (sea_score_last_stage_ms); the
+        # host call's wall time (staging, upload, launches, download) is given beside them.  Bytes read by the frame kernel:
+        # 4 per sample (ref and est, int16), by the mask kernel 8 per unit; the share of the HBM peak is written beside each.
+        # One warm-up discarded, median of --steps.  A first form; there is no target.  The lines also go to
+        # profiles/score_bench_extra.jsonl.
+        import ctypes
+        lib = sea.load()
+        n = batch.n_utt
+        host = batch.data.cpu().numpy()
+        lengths = np.asarray(batch.host_lengths, dtype=np.int64)
+        refs = [np.ascontiguousarray(host[int(o):int(o) + int(L)]) for o, L in zip(batch.host_offsets, lengths)]
+        ests = [np.clip(r.astype(np.int32) + np.resize(refs[(u + 1) % n], r.size) // 4, -32768, 32767).astype(np.int16)
+                for u, r in enumerate(refs)]
+        rows = np.maximum((lengths - 320) // 160 + 1, 0)
+        n_rows, samples = int(rows.sum()), int(lengths.sum())
+        rng = np.random.default_rng(2026)
+        m_est = [rng.uniform(0, 1, size=(int(r), 64)).astype(np.float32) for r in rows]
+        m_ideal = [rng.uniform(0, 1, size=(int(r), 64)).astype(np.float32) for r in rows]
+        ptrs = lambda arrs: (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        lens = (ctypes.c_long * n)(*[int(L) for L in lengths])
+        nr = (ctypes.c_int * n)(*[int(r) for r in rows])
+        sums, seg, used, counts = np.zeros((n, 3), np.int64), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros((n, 4), np.int64)
+        workload = (f"the {args.utts}-utterance corpus as 16 kHz int16 utterances: {samples} samples, {n_rows} frames and mask rows; "
+                    f"median of {args.steps} calls after one warm-up")
+        med = lambda t: sorted(t)[len(t) // 2]
+        lines = []
+
+        def emit(record):
+            lines.append(json.dumps(record))
+            print(lines[-1], flush=True)
+
+        calls = (("sea_score_utterances", lambda: lib.sea_score_utterances(ptrs(refs), ptrs(ests), lens, n, 160, vp(sums), vp(seg), vp(used), None),
+                  (("sea::score_frames_kernel<160>", 0, 4 * samples), ("sea::score_finish_kernel", 1, 4 * n_rows + 96 * (samples // 40320 + n)))),
+                 ("sea_mask_score_utterances", lambda: lib.sea_mask_score_utterances(ptrs(m_est), ptrs(m_ideal), nr, n, 0.5, 0.5, vp(counts)),
+                  (("sea::mask_score_kernel", 2, 512 * n_rows),)))
+        for name, fn, kernels in calls:
+            wall, stage = [], {k: [] for k, _, _ in kernels}
+            for i in range(args.steps + 1):
+                t0 = time.perf_counter()
+                assert fn() == 0, lib.sea_last_error()
+                if i:
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                    for k, st, _ in kernels:
+                        stage[k].append(float(lib.sea_score_last_stage_ms(st)))
+            chunks = int(lib.sea_score_last_chunks())
+            for k, _, nbytes in kernels:
+                t = sorted(stage[k])
+                gbps = nbytes / (med(t) / 1e3) / 1e9
+                emit({"metric": f"objective scores: {k}, device events inside {name} (ms); a first form, not tuned", "value": med(t),
+                      "unit": "ms", "bytes_read": nbytes, "GBps": gbps, "hbm_peak_GBps": HBM_PEAK_GBPS, "frac_of_hbm_peak": gbps / HBM_PEAK_GBPS,
+                      "config": {"workload": workload, "ms_sorted": [round(v, 4) for v in t]}, "chunks": chunks})
+            emit({"metric": f"objective scores: {name} from host memory, wall time, PCIe inclusive (ms)", "value": med(wall), "unit": "ms",
+                  "bytes_uploaded": sum(b for _, st, b in kernels if st != 1), "x_realtime_16k": samples / 16000.0 / (med(wall) / 1e3),
+                  "config": {"workload": workload, "ms_sorted": [round(v, 2) for v in sorted(wall)]}, "chunks": chunks})
+        assert int(used.sum()) > 0 and int(counts.sum()) == 64 * n_rows
+        with open(os.path.join(ROOT, "profiles", "score_bench_extra.jsonl"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
 
     if "rfft" in what:
