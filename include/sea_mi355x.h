@@ -990,6 +990,42 @@ enum {
 double sea_score_last_stage_ms(int stage);
 
 /* ----------------------------------------------------------------------------------------------
+ * STOI, the short-time objective intelligibility measure of Taal, Hendriks, Heusdens and Jensen (2011), of enhanced against
+ * clean int16 audio (csrc/stoi_kernel.hip, csrc/stoi_capi.hip; the contract, operation by operation, is DESIGN.md section
+ * 5.24, and the plain-C model tests/stoi_model_driver.c reproduces every result bit for bit).  Host pointers only.
+ *
+ * sea_stoi_utterances: ref[u] and est[u] hold lengths[u] samples (0 .. 2^31 - 1) at `rate` 16000 or 8000.  Both are resampled
+ * to 10 kHz (L10 = ceil (5 L / q) samples, q = 8 or 4); frames are 256 samples every 128, F = L10 < 256 ? 0 :
+ * (L10 - 256) / 128 + 1; the frames of the reference more than 40 dB below its loudest are removed from both signals, M are
+ * kept; the kept frames are overlap-added and cut into M frames again, each gives 15 third-octave magnitudes; every run of 30
+ * frames is a segment, S = max (M - 29, 0), and every (segment, band) a term d in [-1, 1].
+ * frames_kept[u] = {F, M}; stoi_terms[u] = 15 S; stoi_sum[u]: p[l] = the sum over i ascending of (double) d[64 i + l] over the
+ * flat index i = 15 s + j, then the sum of p[l] over l = 0..63 ascending.  d_out: NULL, or per utterance NULL or [S][15] floats
+ * that receive d.  The figure is stoi_sum / stoi_terms, on the host (speech_enhancement_amd/scores.py).
+ * Returns non-zero, with a sea_last_error message and before any device call, for n_utt < 0, a rate other than 16000 or
+ * 8000, a NULL argument (d_out excepted), a negative length, a length above 2^31 - 1, or a NULL buffer of an utterance that
+ * has samples; the scalars are looked at first, then n_utt == 0 returns 0 whatever the pointers.  An utterance without
+ * samples may have NULL buffers; its outputs are zeros.  Lists run in chunks of whole utterances in list order, a chunk's
+ * device footprint held to 60 % of the HBM that is free (SEA_SCORE_SCRATCH_MB overrides the budget); sea_stoi_last_chunks:
+ * how many chunks the last call of this thread ran.  Results do not depend on the cut.  There is no CPU fallback.
+ * sea_stoi_last_stage_ms: the device time in ms of a kernel (SEA_STOI_STAGE_*) in this thread's last call, between events,
+ * summed over the chunks; -1 for an unknown stage.  For measurement (tools/bench_extra.py --what stoi).
+ * -------------------------------------------------------------------------------------------- */
+int sea_stoi_utterances(const short *const *ref, const short *const *est, const long *lengths, int n_utt, int rate,
+                        double *stoi_sum, long long *stoi_terms, int *frames_kept, float *const *d_out);
+int sea_stoi_last_chunks(void);
+enum {
+    SEA_STOI_STAGE_RESAMPLE = 0, /* stoi_resample_kernel */
+    SEA_STOI_STAGE_ENERGY = 1,   /* stoi_energy_kernel */
+    SEA_STOI_STAGE_COMPACT = 2,  /* stoi_compact_kernel */
+    SEA_STOI_STAGE_BAND = 3,     /* stoi_band_kernel */
+    SEA_STOI_STAGE_SEGMENT = 4,  /* stoi_segment_kernel */
+    SEA_STOI_STAGE_FINISH = 5,   /* stoi_finish_kernel */
+    SEA_STOI_STAGE_COUNT = 6
+};
+double sea_stoi_last_stage_ms(int stage);
+
+/* ----------------------------------------------------------------------------------------------
  * Training that network: minibatch SGD with momentum on Kaldi nnet1's MSE, 1/2 sum e^2 (csrc/dnn_train_kernel.hip,
  * csrc/dnn_train_capi.hip).  Host pointers only, one internal stream.  The plain-C model
  * tests/dnn_train_model_driver.c reproduces every value bit for bit (-0 equals +0).  All operations are float, individually

@@ -8,7 +8,7 @@ Only what that path needs lives here:
   engine.py   host-side mirror of the reference interface + batched HBM-resident forms
   hw25.py     the same for the Hu-Wang mask estimator and its resynthesis on the 25-channel bank
   dnn.py      the DNN mask estimator: cochleagram, feed-forward network, its trainer, the chain from noisy to enhanced audio
-  scores.py   objective scores: SNR, SI-SDR, segmental SNR of enhanced audio; HIT - FA of an estimated mask
+  scores.py   objective scores: SNR, SI-SDR, segmental SNR and STOI of enhanced audio; HIT - FA of an estimated mask
   corpus.py   the deterministic synthetic corpus the measurements run on
   shard.py    utterance sharding over the GPUs of a node (LPT / blocks) and the two-scalar job reduction
   host/       plain-C drivers with the reference's command lines (cfg -> list -> WAV in / WAV out) and the
@@ -36,5 +36,6 @@ from .hw64 import (Hw64Result, hw64_correlogram_batch, hw64_frontend, hw64_front
                    hw64_resynth, hw64_resynth_tables, hw64_resynth_utterances)
 from .dnn import (DnnMask, DnnTrainer, cochleagram, cochleagram_utterances, dnn_enhance_utterances, dnn_forward,  # noqa: F401
                   dnn_last_chunks, dnn_rows)
-from .scores import (dnn_score_utterances, mask_scores, score_frames, score_last_chunks, score_utterances)  # noqa: F401
+from .scores import (dnn_score_utterances, mask_scores, score_frames, score_last_chunks, score_utterances,  # noqa: F401
+                     stoi_frames, stoi_last_chunks, stoi_utterances)
 from .recordings import buffer_denoise, buffer_denoise_recordings, recording_plan, recording_stitch_map  # noqa: F401

@@ -157,6 +157,9 @@ PROTOTYPES = {
     "sea_mask_score_utterances": (_i, [_vp, _vp, _vp, _i, _c.c_float, _c.c_float, _vp]),
     "sea_score_last_chunks": (_i, []),
     "sea_score_last_stage_ms": (_c.c_double, [_i]),
+    "sea_stoi_utterances": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "sea_stoi_last_chunks": (_i, []),
+    "sea_stoi_last_stage_ms": (_c.c_double, [_i]),
     "sea_gammatone_filter": (_i, [_vp, _vp, _i, _l]),
     "sea_ns_stream_alloc": (_vp, []),
     "sea_ns_stream_init": (None, [_vp]),

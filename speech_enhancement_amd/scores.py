@@ -4,6 +4,7 @@ enhancement made the audio better, and how close an estimated mask is to the ide
   score_utterances       clean and enhanced int16 audio -> the exact energies Srr, See, Sre, and SNR, SI-SDR, segmental SNR
   mask_scores            estimated and ideal masks [F][64] -> the 2 x 2 counts, HIT, FA and HIT - FA, per utterance and pooled
   dnn_score_utterances   dnn_enhance_utterances followed by the scores of its output and of its input against the clean audio
+  stoi_utterances        clean and enhanced int16 audio -> STOI, the short-time objective intelligibility measure (section 5.24)
 
 The library returns exact integers (and the segmental sum as a double formed in a stated order); the derived figures are host
 arithmetic here, in float64 from exact Python ints.  Where a denominator is zero:
@@ -11,6 +12,7 @@ arithmetic here, in float64 from exact Python ints.  Where a denominator is zero
   snr_db      N = Srr - 2 Sre + See:  Srr > 0, N = 0 -> +inf;  Srr = 0, N > 0 -> -inf;  both 0 -> nan
   si_sdr_db   T = Sre^2, D = Srr See - T (>= 0 by Cauchy-Schwarz):  T > 0, D = 0 -> +inf;  T = 0, D > 0 -> -inf;  both 0 -> nan
   segsnr_db   no frame used -> nan
+  stoi        no term (fewer than 30 kept frames) -> nan
   hit, fa     no ideal unit on (off) -> nan; hit_fa is nan if either is
 
 All arguments are host arrays; there is no CPU fallback.
@@ -116,6 +118,41 @@ def dnn_score_utterances(model, noisy, clean):
     before = score_utterances(clean, noisy)
     return dict(enhanced=enhanced, noisy=before,
                 gain_db={k: enhanced[k] - before[k] for k in ("snr_db", "si_sdr_db", "segsnr_db")})
+
+
+def stoi_frames(length, rate=16000):
+    """frames of 256 samples every 128 in an utterance of `length` samples once it is resampled to 10 kHz"""
+    q = {16000: 8, 8000: 4}[int(rate)]
+    l10 = (5 * int(length) + q - 1) // q
+    return (l10 - 256) // 128 + 1 if l10 >= 256 else 0
+
+
+def stoi_utterances(refs, ests, rate=16000, terms=False):
+    """Clean (refs) and enhanced (ests) int16 utterances of equal lengths at 16000 or 8000 Hz -> dict of arrays over the list:
+    stoi (float64; stoi_sum / stoi_terms, nan without a term), stoi_sum (float64), stoi_terms (int64), frames and kept (int32:
+    the frames at 10 kHz, and those within 40 dB of the reference's loudest); terms=True adds d, the list of float32 [S_u][15]
+    arrays of the intermediate measure per 30-frame segment and third-octave band."""
+    lib = _lib.load()
+    refs, lens = _i16_list(refs)
+    ests, elens = _i16_list(ests)
+    if len(refs) != len(ests) or any(r.size != e.size for r, e in zip(refs, ests)):
+        raise ValueError("stoi_utterances: one estimate per reference, of the same length")
+    n = len(refs)
+    stoi_sum, stoi_terms, fk = np.zeros(n, np.float64), np.zeros(n, np.int64), np.zeros((n, 2), np.int32)
+    d = [np.zeros((max(stoi_frames(r.size, rate) - 29, 0), 15), np.float32) for r in refs] if terms else None
+    rc = lib.sea_stoi_utterances(_ptr_array(refs), _ptr_array(ests), lens, n, int(rate), _np_ptr(stoi_sum), _np_ptr(stoi_terms),
+                                 _np_ptr(fk), _ptr_array(d) if terms else None)
+    _lib.check(rc, "sea_stoi_utterances")
+    out = dict(stoi=np.array([_div(float(s), int(k)) for s, k in zip(stoi_sum, stoi_terms)], np.float64), stoi_sum=stoi_sum,
+               stoi_terms=stoi_terms, frames=fk[:, 0].copy(), kept=fk[:, 1].copy())
+    if terms:
+        out["d"] = [a[:int(k) // 15] for a, k in zip(d, stoi_terms)]
+    return out
+
+
+def stoi_last_chunks():
+    """How many chunks the last stoi_utterances call of this thread was cut into (SEA_SCORE_SCRATCH_MB sets the budget)."""
+    return int(_lib.load().sea_stoi_last_chunks())
 
 
 def score_last_chunks():

@@ -22,6 +22,7 @@ script prints one JSON line per workload with the same roofline convention.
     python tools/bench_extra.py --what dnn --steps 5  # the DNN mask estimator: cochleagram, every layer (TFLOP/s), the chain, beside the resynthesis alone and hw64_enhance_utterances; also writes profiles/dnn_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what dnntrain  # its trainer: 200 SGD steps at minibatch 256, 1024 and 4096, every stage (TFLOP/s per GEMM beside the forward layer at the same M), steps/s, an epoch's time; also writes profiles/dnntrain_bench_extra.jsonl, opt-in
     python tools/bench_extra.py --what score --steps 5  # the objective scores: each kernel between device events beside the bytes it reads, the host calls' wall time; also writes profiles/score_bench_extra.jsonl, opt-in
+    python tools/bench_extra.py --what stoi --steps 5  # STOI: each kernel between device events, the band kernel's TFLOP/s beside the DNN forward layer's, the host call's wall time; also writes profiles/stoi_bench_extra.jsonl, opt-in
 """
 import argparse
 import json
@@ -1850,6 +1851,65 @@ def main():
                   "config": {"workload": workload, "ms_sorted": [round(v, 2) for v in sorted(wall)]}, "chunks": chunks})
         assert int(used.sum()) > 0 and int(counts.sum()) == 64 * n_rows
         with open(os.path.join(ROOT, "profiles", "score_bench_extra.jsonl"), "w") as fh:
+            fh.write("\n".join(lines) + "\n")
+
+    if "stoi" in what:
+        # STOI on the --utts corpus batch taken as 16 kHz int16 utterances: the clean audio against
+        # itself plus a quarter of the next utterance's samples.  The call takes host memory only and times its own kernels with
+        # device events (sea_stoi_last_stage_ms); the host call's wall time (staging, upload, launches, download) is given beside
+        # them.  The band kernel multiplies the kept frames of both signals [rows][256] by the basis [256][424] on the f32 MFMA:
+        # 2 * rows * 256 * 424 flop, beside the DNN forward layer's rate on the same corpus (section 5.21: 60 TFLOP/s at
+        # 1024 x 1024, M = 407 816).  One warm-up discarded, median of --steps.  A first form; there is no target.  The lines
+        # also go to profiles/stoi_bench_extra.jsonl.
+        import ctypes
+        lib = sea.load()
+        n = batch.n_utt
+        host = batch.data.cpu().numpy()
+        lengths = np.asarray(batch.host_lengths, dtype=np.int64)
+        refs = [np.ascontiguousarray(host[int(o):int(o) + int(L)]) for o, L in zip(batch.host_offsets, lengths)]
+        ests = [np.clip(r.astype(np.int32) + np.resize(refs[(u + 1) % n], r.size) // 4, -32768, 32767).astype(np.int16)
+                for u, r in enumerate(refs)]
+        ptrs = lambda arrs: (ctypes.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        lens = (ctypes.c_long * n)(*[int(L) for L in lengths])
+        ssum, terms, fk = np.zeros(n, np.float64), np.zeros(n, np.int64), np.zeros((n, 2), np.int32)
+        samples = int(lengths.sum())
+        med = lambda t: sorted(t)[len(t) // 2]
+        names = ("sea::stoi_resample_kernel", "sea::stoi_energy_kernel", "sea::stoi_compact_kernel", "sea::stoi_band_kernel",
+                 "sea::stoi_segment_kernel", "sea::stoi_finish_kernel")
+        wall, stage = [], [[] for _ in names]
+        for i in range(args.steps + 1):
+            t0 = time.perf_counter()
+            assert lib.sea_stoi_utterances(ptrs(refs), ptrs(ests), lens, n, 16000, vp(ssum), vp(terms), vp(fk), None) == 0, lib.sea_last_error()
+            if i:
+                wall.append((time.perf_counter() - t0) * 1e3)
+                for st in range(len(names)):
+                    stage[st].append(float(lib.sea_stoi_last_stage_ms(st)))
+        chunks = int(lib.sea_stoi_last_chunks())
+        frames, kept, n_terms = int(fk[:, 0].sum()), int(fk[:, 1].sum()), int(terms.sum())
+        workload = (f"the {args.utts}-utterance corpus as 16 kHz int16 utterances: {samples} samples, {frames} frames at 10 kHz of which "
+                    f"{kept} are kept, {n_terms} terms; median of {args.steps} calls after one warm-up")
+        lines = []
+
+        def emit(record):
+            lines.append(json.dumps(record))
+            print(lines[-1], flush=True)
+
+        for st, k in enumerate(names):
+            t = sorted(stage[st])
+            rec = {"metric": f"STOI: {k}, device events inside sea_stoi_utterances (ms); a first form, not tuned", "value": med(t), "unit": "ms",
+                   "config": {"workload": workload, "ms_sorted": [round(v, 4) for v in t]}, "chunks": chunks}
+            if k.endswith("band_kernel"):
+                flop = 2.0 * (2 * kept) * 256 * 424
+                rec.update(flop=flop, TFLOPs=flop / (med(t) / 1e3) / 1e12, dnn_forward_layer_TFLOPs_same_corpus=60.0)
+            emit(rec)
+        with np.errstate(invalid="ignore"):
+            mean_stoi = float(np.nanmean(ssum / terms))
+        emit({"metric": "STOI: sea_stoi_utterances from host memory, wall time, PCIe inclusive (ms)", "value": med(wall), "unit": "ms",
+              "bytes_uploaded": 4 * samples, "x_realtime_16k": samples / 16000.0 / (med(wall) / 1e3), "mean_stoi": mean_stoi,
+              "config": {"workload": workload, "ms_sorted": [round(v, 2) for v in sorted(wall)]}, "chunks": chunks})
+        assert n_terms > 0 and 0.0 < mean_stoi < 1.0
+        with open(os.path.join(ROOT, "profiles", "stoi_bench_extra.jsonl"), "w") as fh:
             fh.write("\n".join(lines) + "\n")
 
     if "rfft" in what:
