@@ -1,11 +1,16 @@
 /*
- * capi_internal.h -- what the translation units behind the C ABI share (capi.hip, hostpipe.hip): the
- * per-thread error string, the per-device context with the constant tables, small RAII helpers.
+ * capi_internal.h -- what the translation units behind the C ABI share: the per-thread error string and HIP_TRY, the
+ * per-device context with the constant tables, the launch order and the NoiseSup form, and the HIP half of the chunked host
+ * lists (chunk_plan.h holds the integer half): DevBuf, the chunk budget (scratch_budget), an RAII set of timing events
+ * (EventSet) and a device buffer with its host staging (Staged).
  */
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "../../include/sea_mi355x.h"
+#include "chunk_plan.h"
 #include "sea_kernels.h"
 
 namespace sea_capi {
@@ -42,7 +47,52 @@ struct DevBuf {
     hipError_t alloc(size_t n) { return hipMalloc(&p, n * sizeof(T) + 16); }
 };
 
-inline long long align8(long long v) { return (v + 7) & ~7LL; }
+/* the budget of a chunk of a host list: the MiB that the variable env_name gives, else 60 % of the
+ * HBM that is free now plus the held bytes the caller will reuse; env_name == nullptr: no override */
+inline int scratch_budget(const char *env_name, long long *budget, size_t held = 0)
+{
+    const char *e = env_name ? getenv(env_name) : nullptr;
+    size_t free_b = 0, total_b = 0;
+    if (!e) HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    *budget = budget_of(free_b, held, e);
+    return 0;
+}
+
+/* N device events; add_ms() after the synchronisation that follows the later one */
+template <int N>
+struct EventSet {
+    hipEvent_t e[N] = {};
+    ~EventSet()
+    {
+        for (hipEvent_t ev : e)
+            if (ev) (void)hipEventDestroy(ev);
+    }
+    int create()
+    {
+        for (hipEvent_t &ev : e) HIP_TRY(hipEventCreate(&ev));
+        return 0;
+    }
+    int add_ms(int from, int to, double *sum) const
+    {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, e[from], e[to]));
+        *sum += ms;
+        return 0;
+    }
+};
+
+/* a device buffer and the host staging of the same n elements (none with host = false); the copies stay with the callers */
+template <class T>
+struct Staged {
+    DevBuf<T> d;
+    std::vector<T> h;
+    hipError_t alloc(size_t n, bool host = true)
+    {
+        const hipError_t e = d.alloc(n);
+        if (e == hipSuccess && host) h.resize(n);
+        return e;
+    }
+};
 
 /* launch order of the utterance-per-workgroup kernels: longest first, every other row of n_cu reversed */
 void launch_order(const long long *lens, int n, int n_cu, int *order);

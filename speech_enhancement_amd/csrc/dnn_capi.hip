@@ -85,50 +85,9 @@ thread_local int t_last_chunks = 0;
 constexpr int kStages = SEA_DNN_STAGE_COUNT;
 thread_local double t_stage_ms[kStages] = {};
 
-struct Events {
-    hipEvent_t e[kStages + 1] = {};
-    ~Events()
-    {
-        for (hipEvent_t ev : e)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    int create()
-    {
-        for (hipEvent_t &ev : e) HIP_TRY(hipEventCreate(&ev));
-        return 0;
-    }
-};
-
 long long rows_of(long L) { return (L - 320) / 160 + 1; }
 
-/* 60 % of the HBM that is free now, as sea_trainset_utterances; SEA_DNN_SCRATCH_MB overrides it */
-int dnn_budget(long long *budget)
-{
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    *budget = (long long)(free_b / 10 * 6);
-    if (const char *e = getenv("SEA_DNN_SCRATCH_MB")) *budget = atoll(e) * (1LL << 20);
-    return 0;
-}
-
-/* whole utterances in list order, cut where the next one would pass the budget; an utterance larger than the budget forms a
- * chunk of its own and hipMalloc reports what does not fit */
-template <typename Bytes>
-std::vector<int> cut_list(int n_utt, long long budget, Bytes bytes_of)
-{
-    std::vector<int> cuts(1, 0);
-    long long run = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        const long long b = bytes_of(u);
-        if (u > cuts.back() && run + b > budget) {
-            cuts.push_back(u);
-            run = 0;
-        }
-        run += b;
-    }
-    cuts.push_back(n_utt);
-    return cuts;
-}
+enum { S, R }; /* of an utterance of audio: padded samples, rows, bytes */
 
 int on_models_device(const sea_dnn *m, const char *who)
 {
@@ -261,52 +220,42 @@ int sea_cochleagram_utterances(const short *const *in, const long *lengths, int 
     DeviceCtx *dc;
     if (ctx(&dc)) return 1;
     long long budget;
-    if (dnn_budget(&budget)) return 1;
-    const std::vector<int> cuts =
-        cut_list(n_utt, budget, [&](int u) -> long long { return align8(lengths[u]) * 130 + rows_of(lengths[u]) * 256 + 64; });
-    const int nchunk = (int)cuts.size() - 1;
-    long long max_s = 0, max_r = 0;
-    int max_n = 0;
-    for (int k = 0; k < nchunk; ++k) {
-        long long s = 0, r = 0;
-        for (int u = cuts[k]; u < cuts[k + 1]; ++u) s += align8(lengths[u]), r += rows_of(lengths[u]);
-        max_s = std::max(max_s, s), max_r = std::max(max_r, r), max_n = std::max(max_n, cuts[k + 1] - cuts[k]);
-    }
-    DevBuf<short> d_in, d_sub;
-    DevBuf<float> d_feats;
-    DevBuf<long long> d_meta; /* offsets, lengths, row offsets */
-    DevBuf<int> d_order;
-    HIP_TRY(d_in.alloc((size_t)max_s));
-    HIP_TRY(d_sub.alloc((size_t)max_s * 64));
-    HIP_TRY(d_feats.alloc((size_t)max_r * 64));
-    HIP_TRY(d_meta.alloc(3 * (size_t)max_n));
-    HIP_TRY(d_order.alloc((size_t)max_n));
-    std::vector<short> h_in((size_t)max_s);
-    std::vector<float> h_feats((size_t)max_r * 64);
-    std::vector<long long> h_meta(3 * (size_t)max_n);
-    std::vector<int> h_order((size_t)max_n);
-    for (int k = 0; k < nchunk; ++k) {
-        const int u0 = cuts[k], n = cuts[k + 1] - u0;
-        long long *offs = h_meta.data(), *lens = offs + n, *roff = lens + n;
+    if (scratch_budget("SEA_DNN_SCRATCH_MB", &budget)) return 1;
+    auto of = [&](int u) -> Totals<3> {
+        const long long s = align8(lengths[u]), r = rows_of(lengths[u]);
+        return {s, r, s * 130 + r * 256 + 64};
+    };
+    const ChunkPlan<3> plan = plan_chunks<3>(n_utt, budget, of);
+    Staged<short> b_in;
+    DevBuf<short> d_sub;
+    Staged<float> b_feats;
+    Staged<long long> b_meta; /* offsets, lengths, row offsets */
+    Staged<int> b_order;
+    HIP_TRY(b_in.alloc((size_t)plan.max[S]));
+    HIP_TRY(d_sub.alloc((size_t)plan.max[S] * 64));
+    HIP_TRY(b_feats.alloc((size_t)plan.max[R] * 64));
+    HIP_TRY(b_meta.alloc(3 * (size_t)plan.max_n));
+    HIP_TRY(b_order.alloc((size_t)plan.max_n));
+    const long long *d_meta = b_meta.d.p;
+    for (int k = 0; k < plan.chunks(); ++k) {
+        const int u0 = plan.cuts[k], n = plan.cuts[k + 1] - u0;
+        long long *offs = b_meta.h.data(), *lens = offs + n, *roff = lens + n;
         long long s = 0, r = 0;
         for (int j = 0; j < n; ++j) {
-            const long L = lengths[u0 + j];
-            offs[j] = s, lens[j] = L, roff[j] = r;
-            memcpy(h_in.data() + s, in[u0 + j], (size_t)L * sizeof(short));
-            memset(h_in.data() + s + L, 0, (size_t)(align8(L) - L) * sizeof(short));
-            s += align8(L);
-            r += rows_of(L);
+            offs[j] = s, lens[j] = lengths[u0 + j], roff[j] = r;
+            s += pack_padded(b_in.h.data() + s, in[u0 + j], lens[j]);
+            r += rows_of(lengths[u0 + j]);
         }
-        launch_order(lens, n, dc->n_cu, h_order.data());
-        HIP_TRY(hipMemcpy(d_in.p, h_in.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_meta.p, h_meta.data(), 3 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_order.p, h_order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-        if (sea_subband64_batch(d_in.p, d_sub.p, d_meta.p, d_meta.p + n, d_order.p, n, nullptr)) return 1;
-        if (cochleagram64_launch(d_sub.p, d_meta.p, d_meta.p + n, d_meta.p + 2 * n, d_feats.p, n, nullptr)) return 1;
+        launch_order(lens, n, dc->n_cu, b_order.h.data());
+        HIP_TRY(hipMemcpy(b_in.d.p, b_in.h.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b_meta.d.p, b_meta.h.data(), 3 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b_order.d.p, b_order.h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        if (sea_subband64_batch(b_in.d.p, d_sub.p, d_meta, d_meta + n, b_order.d.p, n, nullptr)) return 1;
+        if (cochleagram64_launch(d_sub.p, d_meta, d_meta + n, d_meta + 2 * n, b_feats.d.p, n, nullptr)) return 1;
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(h_feats.data(), d_feats.p, (size_t)r * 64 * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b_feats.h.data(), b_feats.d.p, (size_t)r * 64 * sizeof(float), hipMemcpyDeviceToHost));
         for (int j = 0; j < n; ++j)
-            memcpy(feats[u0 + j], h_feats.data() + roff[j] * 64, (size_t)rows_of((long)lens[j]) * 64 * sizeof(float));
+            memcpy(feats[u0 + j], b_feats.h.data() + roff[j] * 64, (size_t)rows_of((long)lens[j]) * 64 * sizeof(float));
         t_last_chunks = k + 1;
     }
     return 0;
@@ -325,45 +274,38 @@ int sea_dnn_forward(const sea_dnn *m, const float *const *feats, const int *n_ro
     }
     const int n_out = m->dims[m->n_layers];
     long long budget;
-    if (dnn_budget(&budget)) return 1;
+    if (scratch_budget("SEA_DNN_SCRATCH_MB", &budget)) return 1;
     const long long row_bytes = 256 + 4LL * n_out + 8LL * m->ld;
-    const std::vector<int> cuts = cut_list(n_utt, budget, [&](int u) -> long long { return n_rows[u] * row_bytes + 8; });
-    const int nchunk = (int)cuts.size() - 1;
-    long long max_r = 0;
-    int max_n = 0;
-    for (int k = 0; k < nchunk; ++k) {
-        long long r = 0;
-        for (int u = cuts[k]; u < cuts[k + 1]; ++u) r += n_rows[u];
-        max_r = std::max(max_r, r), max_n = std::max(max_n, cuts[k + 1] - cuts[k]);
-    }
+    const ChunkPlan<2> plan =
+        plan_chunks<2>(n_utt, budget, [&](int u) -> Totals<2> { return {n_rows[u], n_rows[u] * row_bytes + 8}; }); /* rows, bytes */
+    const size_t max_r = (size_t)plan.max[0];
     if (max_r == 0) return 0;
-    DevBuf<float> d_feats, d_act[2], d_out;
-    DevBuf<long long> d_roff;
-    HIP_TRY(d_feats.alloc((size_t)max_r * 64));
-    HIP_TRY(d_act[0].alloc((size_t)max_r * m->ld));
-    HIP_TRY(d_act[1].alloc((size_t)max_r * m->ld));
-    HIP_TRY(d_out.alloc((size_t)max_r * n_out));
-    HIP_TRY(d_roff.alloc((size_t)max_n + 1));
-    std::vector<float> h_feats((size_t)max_r * 64), h_out((size_t)max_r * n_out);
-    std::vector<long long> h_roff((size_t)max_n + 1);
-    for (int k = 0; k < nchunk; ++k) {
-        const int u0 = cuts[k], n = cuts[k + 1] - u0;
+    Staged<float> b_feats, b_out;
+    DevBuf<float> d_act[2];
+    Staged<long long> b_roff;
+    HIP_TRY(b_feats.alloc(max_r * 64));
+    HIP_TRY(d_act[0].alloc(max_r * m->ld));
+    HIP_TRY(d_act[1].alloc(max_r * m->ld));
+    HIP_TRY(b_out.alloc(max_r * n_out));
+    HIP_TRY(b_roff.alloc((size_t)plan.max_n + 1));
+    for (int k = 0; k < plan.chunks(); ++k) {
+        const int u0 = plan.cuts[k], n = plan.cuts[k + 1] - u0;
         long long r = 0;
         for (int j = 0; j < n; ++j) {
-            h_roff[j] = r;
-            if (n_rows[u0 + j]) memcpy(h_feats.data() + r * 64, feats[u0 + j], (size_t)n_rows[u0 + j] * 64 * sizeof(float));
+            b_roff.h[j] = r;
+            if (n_rows[u0 + j]) memcpy(b_feats.h.data() + r * 64, feats[u0 + j], (size_t)n_rows[u0 + j] * 64 * sizeof(float));
             r += n_rows[u0 + j];
         }
-        h_roff[n] = r;
+        b_roff.h[n] = r;
         if (r > 0) {
-            HIP_TRY(hipMemcpy(d_feats.p, h_feats.data(), (size_t)r * 64 * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(d_roff.p, h_roff.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice));
-            if (dnn_forward_launch(m, d_feats.p, d_roff.p, n, r, d_act[0].p, d_act[1].p, d_out.p, nullptr)) return 1;
+            HIP_TRY(hipMemcpy(b_feats.d.p, b_feats.h.data(), (size_t)r * 64 * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(b_roff.d.p, b_roff.h.data(), ((size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice));
+            if (dnn_forward_launch(m, b_feats.d.p, b_roff.d.p, n, r, d_act[0].p, d_act[1].p, b_out.d.p, nullptr)) return 1;
             HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipMemcpy(h_out.data(), d_out.p, (size_t)r * n_out * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(b_out.h.data(), b_out.d.p, (size_t)r * n_out * sizeof(float), hipMemcpyDeviceToHost));
             for (int j = 0; j < n; ++j)
                 if (n_rows[u0 + j])
-                    memcpy(out[u0 + j], h_out.data() + h_roff[j] * n_out, (size_t)n_rows[u0 + j] * n_out * sizeof(float));
+                    memcpy(out[u0 + j], b_out.h.data() + b_roff.h[j] * n_out, (size_t)n_rows[u0 + j] * n_out * sizeof(float));
         }
         t_last_chunks = k + 1;
     }
@@ -392,89 +334,77 @@ int sea_dnn_enhance_utterances(const sea_dnn *m, const short *const *in, const l
     DeviceCtx *dc;
     if (ctx(&dc)) return 1;
     long long budget;
-    if (dnn_budget(&budget)) return 1;
+    if (scratch_budget("SEA_DNN_SCRATCH_MB", &budget)) return 1;
     const long long row_bytes = 512 + 8LL * m->ld;
-    const std::vector<int> cuts = cut_list(n_utt, budget, [&](int u) -> long long {
-        return align8(lengths[u]) * 132 + sea_resynth_scratch_bytes(align8(lengths[u]), 1) + rows_of(lengths[u]) * row_bytes + 64;
-    });
-    const int nchunk = (int)cuts.size() - 1;
-    long long max_s = 0, max_r = 0;
-    int max_n = 0;
-    for (int k = 0; k < nchunk; ++k) {
-        long long s = 0, r = 0;
-        for (int u = cuts[k]; u < cuts[k + 1]; ++u) s += align8(lengths[u]), r += rows_of(lengths[u]);
-        max_s = std::max(max_s, s), max_r = std::max(max_r, r), max_n = std::max(max_n, cuts[k + 1] - cuts[k]);
-    }
-    DevBuf<short> d_in, d_out, d_sub;
-    DevBuf<float> d_feats, d_act[2], d_mask, d_inter;
-    DevBuf<long long> d_meta; /* offsets, lengths, row offsets [n + 1] */
-    DevBuf<int> d_order;
-    HIP_TRY(d_in.alloc((size_t)max_s));
-    HIP_TRY(d_out.alloc((size_t)max_s));
-    HIP_TRY(d_sub.alloc((size_t)max_s * 64));
-    HIP_TRY(d_inter.alloc((size_t)sea_resynth_scratch_bytes(max_s, max_n) / sizeof(float)));
-    HIP_TRY(d_feats.alloc((size_t)max_r * 64));
-    HIP_TRY(d_mask.alloc((size_t)max_r * 64));
-    HIP_TRY(d_act[0].alloc((size_t)max_r * m->ld));
-    HIP_TRY(d_act[1].alloc((size_t)max_r * m->ld));
-    HIP_TRY(d_meta.alloc(3 * (size_t)max_n + 1));
-    HIP_TRY(d_order.alloc((size_t)max_n));
-    std::vector<short> h_audio((size_t)max_s);
-    std::vector<float> h_mask(masks ? (size_t)max_r * 64 : 0);
-    std::vector<long long> h_meta(3 * (size_t)max_n + 1);
-    std::vector<int> h_order((size_t)max_n);
+    auto of = [&](int u) -> Totals<3> {
+        const long long s = align8(lengths[u]), r = rows_of(lengths[u]);
+        return {s, r, s * 132 + sea_resynth_scratch_bytes(s, 1) + r * row_bytes + 64};
+    };
+    const ChunkPlan<3> plan = plan_chunks<3>(n_utt, budget, of);
+    const size_t max_s = (size_t)plan.max[S], max_r = (size_t)plan.max[R], max_n = (size_t)plan.max_n;
+    Staged<short> b_audio; /* in on the way up, out on the way down */
+    DevBuf<short> d_out, d_sub;
+    DevBuf<float> d_feats, d_act[2], d_inter;
+    Staged<float> b_mask;
+    Staged<long long> b_meta; /* offsets, lengths, row offsets [n + 1] */
+    Staged<int> b_order;
+    HIP_TRY(b_audio.alloc(max_s));
+    HIP_TRY(d_out.alloc(max_s));
+    HIP_TRY(d_sub.alloc(max_s * 64));
+    HIP_TRY(d_inter.alloc((size_t)sea_resynth_scratch_bytes(plan.max[S], plan.max_n) / sizeof(float)));
+    HIP_TRY(d_feats.alloc(max_r * 64));
+    HIP_TRY(b_mask.alloc(max_r * 64, masks != nullptr));
+    HIP_TRY(d_act[0].alloc(max_r * m->ld));
+    HIP_TRY(d_act[1].alloc(max_r * m->ld));
+    HIP_TRY(b_meta.alloc(3 * max_n + 1));
+    HIP_TRY(b_order.alloc(max_n));
+    short *d_in = b_audio.d.p;
+    float *d_mask = b_mask.d.p;
     hipStream_t stream = nullptr;
-    Events ev; /* e[0] before the subbands, e[1 + s] after stage s */
+    EventSet<kStages + 1> ev; /* e[0] before the subbands, e[1 + s] after stage s */
     if (ev.create()) return 1;
     for (double &t : t_stage_ms) t = 0.0;
     const int nl = m->n_layers;
-    for (int k = 0; k < nchunk; ++k) {
-        const int u0 = cuts[k], n = cuts[k + 1] - u0;
-        long long *offs = h_meta.data(), *lens = offs + n, *roff = lens + n;
+    for (int k = 0; k < plan.chunks(); ++k) {
+        const int u0 = plan.cuts[k], n = plan.cuts[k + 1] - u0;
+        long long *offs = b_meta.h.data(), *lens = offs + n, *roff = lens + n;
         long long s = 0, r = 0;
         for (int j = 0; j < n; ++j) {
-            const long L = lengths[u0 + j];
-            offs[j] = s, lens[j] = L, roff[j] = r;
-            memcpy(h_audio.data() + s, in[u0 + j], (size_t)L * sizeof(short));
-            memset(h_audio.data() + s + L, 0, (size_t)(align8(L) - L) * sizeof(short));
-            s += align8(L);
-            r += rows_of(L);
+            offs[j] = s, lens[j] = lengths[u0 + j], roff[j] = r;
+            s += pack_padded(b_audio.h.data() + s, in[u0 + j], lens[j]);
+            r += rows_of(lengths[u0 + j]);
         }
         roff[n] = r;
-        launch_order(lens, n, dc->n_cu, h_order.data());
-        HIP_TRY(hipMemcpyAsync(d_in.p, h_audio.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_meta.p, h_meta.data(), (3 * (size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(d_order.p, h_order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
-        const long long *d_offs = d_meta.p, *d_lens = d_meta.p + n, *d_roff = d_meta.p + 2 * n;
+        launch_order(lens, n, dc->n_cu, b_order.h.data());
+        HIP_TRY(hipMemcpyAsync(d_in, b_audio.h.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(b_meta.d.p, b_meta.h.data(), (3 * (size_t)n + 1) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(b_order.d.p, b_order.h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream));
+        const long long *d_offs = b_meta.d.p, *d_lens = d_offs + n, *d_roff = d_offs + 2 * n;
         HIP_TRY(hipEventRecord(ev.e[0], stream));
-        if (sea_subband64_batch(d_in.p, d_sub.p, d_offs, d_lens, d_order.p, n, stream)) return 1;
+        if (sea_subband64_batch(d_in, d_sub.p, d_offs, d_lens, b_order.d.p, n, stream)) return 1;
         HIP_TRY(hipEventRecord(ev.e[1 + SEA_DNN_STAGE_SUBBAND], stream));
         if (cochleagram64_launch(d_sub.p, d_offs, d_lens, d_roff, d_feats.p, n, stream)) return 1;
         HIP_TRY(hipEventRecord(ev.e[1 + SEA_DNN_STAGE_COCHLEAGRAM], stream));
-        if (dnn_forward_launch(m, d_feats.p, d_roff, n, r, d_act[0].p, d_act[1].p, d_mask.p, stream, &ev.e[1 + SEA_DNN_STAGE_SPLICE]))
+        if (dnn_forward_launch(m, d_feats.p, d_roff, n, r, d_act[0].p, d_act[1].p, d_mask, stream, &ev.e[1 + SEA_DNN_STAGE_SPLICE]))
             return 1;
-        if (sea_resynth64_batch(d_in.p, d_out.p, d_offs, d_lens, d_mask.p, d_roff, d_inter.p, d_order.p, n, binary, stream)) return 1;
+        if (sea_resynth64_batch(d_in, d_out.p, d_offs, d_lens, d_mask, d_roff, d_inter.p, b_order.d.p, n, binary, stream)) return 1;
         HIP_TRY(hipEventRecord(ev.e[1 + SEA_DNN_STAGE_RESYNTH], stream));
-        HIP_TRY(hipMemcpyAsync(h_audio.data(), d_out.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost, stream));
-        if (masks) HIP_TRY(hipMemcpyAsync(h_mask.data(), d_mask.p, (size_t)r * 64 * sizeof(float), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(b_audio.h.data(), d_out.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost, stream));
+        if (masks) HIP_TRY(hipMemcpyAsync(b_mask.h.data(), d_mask, (size_t)r * 64 * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         {   /* stage s lasts from the event before it to its own; the stages 3 + n_layers .. 10 do not exist */
             int before = 0;
             for (int st = 0; st <= SEA_DNN_STAGE_RESYNTH; ++st) {
                 if (st >= SEA_DNN_STAGE_LAYER0 + nl && st < SEA_DNN_STAGE_RESYNTH) continue;
-                float ms = 0.0f;
-                HIP_TRY(hipEventElapsedTime(&ms, ev.e[before], ev.e[1 + st]));
-                t_stage_ms[st] += ms;
+                if (ev.add_ms(before, 1 + st, &t_stage_ms[st])) return 1;
                 before = 1 + st;
             }
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1 + SEA_DNN_STAGE_RESYNTH]));
-            t_stage_ms[SEA_DNN_STAGE_ALL] += ms;
+            if (ev.add_ms(0, 1 + SEA_DNN_STAGE_RESYNTH, &t_stage_ms[SEA_DNN_STAGE_ALL])) return 1;
         }
         for (int j = 0; j < n; ++j) {
-            memcpy(out[u0 + j], h_audio.data() + offs[j], (size_t)lens[j] * sizeof(short));
+            memcpy(out[u0 + j], b_audio.h.data() + offs[j], (size_t)lens[j] * sizeof(short));
             if (masks && masks[u0 + j])
-                memcpy(masks[u0 + j], h_mask.data() + roff[j] * 64, (size_t)(roff[j + 1] - roff[j]) * 64 * sizeof(float));
+                memcpy(masks[u0 + j], b_mask.h.data() + roff[j] * 64, (size_t)(roff[j + 1] - roff[j]) * 64 * sizeof(float));
         }
         t_last_chunks = k + 1;
     }

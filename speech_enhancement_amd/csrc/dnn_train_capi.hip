@@ -58,11 +58,11 @@ int trainer_fill(sea_dnn_trainer *t, const float *const *feats, const float *con
     const size_t mb = (size_t)t->max_batch, ld = (size_t)m->ld;
     size_t bytes = (size_t)t->rows * (64 + (size_t)n_out) * 4 + ((size_t)t->n_utt + 1) * 8 + (2 * (size_t)n + 1) * mb * ld * 4;
     for (int l = 0; l < n; ++l) bytes += 2 * ((size_t)m->dims[l] + 1) * (size_t)m->dims[l + 1] * 4;
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    if (bytes > free_b / 10 * 6)
+    long long limit;
+    if (scratch_budget(nullptr, &limit)) return 1;
+    if (bytes > (size_t)limit)
         return fail("dnn_trainer_create: the training set and the step's buffers take %zu bytes, 60 %% of the free device memory is "
-                    "%zu (a set larger than the device is out of scope)", bytes, free_b / 10 * 6);
+                    "%zu (a set larger than the device is out of scope)", bytes, (size_t)limit);
     HIP_TRY(hipStreamCreate(&t->stream));
     for (hipEvent_t &e : t->ev) HIP_TRY(hipEventCreate(&e));
     if (dev_alloc(&t->d_feats, (size_t)t->rows * 64) || dev_alloc(&t->d_targets, (size_t)t->rows * n_out) ||

@@ -1406,10 +1406,8 @@ int sea_resynth_utterances(const short *const *in, const long *lengths, const fl
     PipeWs &w = t_ws;
     HIP_TRY(w.bind());
     Pool &pool = Pool::get(w.device);
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    long long budget = (long long)((free_b + w.inter.dcap) / 10 * 6);
-    if (const char *e = getenv("SEA_RESYNTH_SCRATCH_MB")) budget = atoll(e) * (1LL << 20);
+    long long budget;
+    if (scratch_budget("SEA_RESYNTH_SCRATCH_MB", &budget, w.inter.dcap)) return 1;
     /* regions: as many streams as there will be chunks, each at least one utterance */
     long long region = std::max(largest, budget / kStreams);
     /* chunk = at most a region's worth of scratch and about SEA_HOST_CHUNK_MB of (int16 + mask) input */

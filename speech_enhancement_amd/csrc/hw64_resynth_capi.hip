@@ -23,72 +23,29 @@ constexpr int kCh = SEA_HW64_NCHAN;
 thread_local int t_last_chunks = 0;
 thread_local double t_last_resynth_ms = 0.0;
 
-/* a pair of device events around the resynthesis launch of every chunk, so that the kernel can be timed although its launch is
- * not exported (sea_hw64_enhance_last_resynth_ms): add_ms() after the chunk's synchronisation */
-struct LaunchTimer {
-    hipEvent_t before = nullptr, after = nullptr;
-    ~LaunchTimer()
-    {
-        if (before) (void)hipEventDestroy(before);
-        if (after) (void)hipEventDestroy(after);
-    }
-    int create()
-    {
-        HIP_TRY(hipEventCreate(&before));
-        HIP_TRY(hipEventCreate(&after));
-        return 0;
-    }
-    int add_ms(double *sum) const
-    {
-        float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, before, after));
-        *sum += ms;
-        return 0;
-    }
-};
-
 long long rows_of(long L) { return L > 0 ? L / SEA_HW64_HOP : 0; }
 
 /* Device footprint of a chunk of n utterances with s padded samples and r mask rows in all: what the launch group works in --
  * the estimator's scratch, or for the resynthesis alone the three [64][pitch] planes hOut, hEv and gOut -- and its I/O buffers:
  * 10 B per padded sample (float in, float out, int16 out), 260 B per row (mask, pitch), 32 B per utterance (offsets, lengths,
  * row offsets, launch order, status). */
+long long work_bytes(long long s, long long r, int n, int resynth_only)
+{
+    return resynth_only ? 3 * s * kCh * 4 : sea_hw64_ibm_scratch_bytes(s, r, n);
+}
 long long chunk_bytes(long long s, long long r, int n, int resynth_only)
 {
-    const long long work = resynth_only ? 3 * s * kCh * 4 : sea_hw64_ibm_scratch_bytes(s, r, n);
-    return work + 10 * s + 260 * r + 32LL * n;
+    return work_bytes(s, r, n, resynth_only) + 10 * s + 260 * r + 32LL * n;
 }
 
-/* the list in order, greedily: a chunk grows while its footprint stays within the budget; an utterance that exceeds the
- * budget alone forms a chunk of its own.  cuts: the first utterance of every chunk, then n_utt. */
-std::vector<int> plan(const long *lengths, int n_utt, long long budget, int resynth_only)
-{
-    std::vector<int> cuts(1, 0);
-    long long s = 0, r = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        const long long su = align8(lengths[u]), ru = rows_of(lengths[u]);
-        if (u > cuts.back() && chunk_bytes(s + su, r + ru, u - cuts.back() + 1, resynth_only) > budget) {
-            cuts.push_back(u);
-            s = r = 0;
-        }
-        s += su;
-        r += ru;
-    }
-    cuts.push_back(n_utt);
-    return cuts;
-}
+enum { S, R }; /* of an utterance: padded samples, mask rows */
 
-/* 60 % of the HBM that is free now, as sea_trainset_utterances; SEA_HW64_ENHANCE_SCRATCH_MB overrides it */
-int budget_bytes(long long *budget)
+/* the cut of chunk_plan.h over a footprint that is a function of the chunk's totals, not a sum over its utterances */
+ChunkPlan<2> plan(const long *lengths, int n_utt, long long budget, int resynth_only)
 {
-    if (const char *e = getenv("SEA_HW64_ENHANCE_SCRATCH_MB")) {
-        *budget = atoll(e) * (1LL << 20);
-        return 0;
-    }
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    *budget = (long long)(free_b / 10 * 6);
-    return 0;
+    return plan_chunks<2>(
+        n_utt, budget, [&](int u) -> Totals<2> { return {align8(lengths[u]), rows_of(lengths[u])}; },
+        [&](const Totals<2> &c, int n) { return chunk_bytes(c[S], c[R], n, resynth_only); });
 }
 
 /* What both list forms share: the cut, the device and host buffers sized once for the largest chunk, and a chunk's way up
@@ -98,17 +55,14 @@ struct List {
     const float *const *in;
     const long *lengths;
     int n_utt, n_cu = 256;
-    std::vector<int> cuts;
+    ChunkPlan<2> p;
     long long max_s = 0, max_r = 0, max_work = 0;
     int max_n = 0;
-    DevBuf<float> d_in, d_out, d_mask;
-    DevBuf<short> d_out16;
-    DevBuf<long long> d_meta;
-    DevBuf<int> d_order;
-    std::vector<float> h_f32, h_mask;
-    std::vector<short> h_i16;
-    std::vector<long long> h_meta;
-    std::vector<int> h_order;
+    Staged<float> f32, mask; /* f32: the input on the way up, the float output on the way down */
+    DevBuf<float> d_out;
+    Staged<short> i16;
+    Staged<long long> meta;
+    Staged<int> order;
     /* the chunk in hand */
     int u0 = 0, n = 0;
     long long s = 0, r = 0;
@@ -131,71 +85,58 @@ struct List {
         if (ctx(&dc)) return 1;
         n_cu = dc->n_cu;
         long long budget = 0;
-        if (budget_bytes(&budget)) return 1;
-        cuts = plan(lengths, n_utt, budget, resynth_only);
-        for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-            long long cs = 0, cr = 0;
-            for (int u = cuts[k]; u < cuts[k + 1]; ++u) cs += align8(lengths[u]), cr += rows_of(lengths[u]);
-            const int cn = cuts[k + 1] - cuts[k];
-            max_s = std::max(max_s, cs);
-            max_r = std::max(max_r, cr);
-            max_n = std::max(max_n, cn);
-            max_work = std::max(max_work, chunk_bytes(cs, cr, cn, resynth_only) - (10 * cs + 260 * cr + 32LL * cn));
-        }
-        HIP_TRY(d_in.alloc((size_t)max_s));
+        if (scratch_budget("SEA_HW64_ENHANCE_SCRATCH_MB", &budget)) return 1;
+        p = plan(lengths, n_utt, budget, resynth_only);
+        max_s = p.max[S], max_r = p.max[R], max_n = p.max_n;
+        for (int k = 0; k < p.chunks(); ++k)
+            max_work = std::max(max_work, work_bytes(p.sum[k][S], p.sum[k][R], p.cuts[k + 1] - p.cuts[k], resynth_only));
+        HIP_TRY(f32.alloc((size_t)max_s));
         if (out_f32) HIP_TRY(d_out.alloc((size_t)max_s));
-        if (out_i16) HIP_TRY(d_out16.alloc((size_t)max_s));
-        HIP_TRY(d_mask.alloc((size_t)(max_r + 1) * kCh));
-        HIP_TRY(d_meta.alloc(3 * (size_t)max_n));
-        HIP_TRY(d_order.alloc((size_t)max_n));
-        h_f32.resize((size_t)max_s);
-        if (out_i16) h_i16.resize((size_t)max_s);
-        h_mask.resize((size_t)(max_r + 1) * kCh);
-        h_meta.resize(3 * (size_t)max_n);
-        h_order.resize((size_t)max_n);
+        if (out_i16) HIP_TRY(i16.alloc((size_t)max_s));
+        HIP_TRY(mask.alloc((size_t)(max_r + 1) * kCh));
+        HIP_TRY(meta.alloc(3 * (size_t)max_n));
+        HIP_TRY(order.alloc((size_t)max_n));
         return 0;
     }
 
-    int chunks() const { return (int)cuts.size() - 1; }
+    int chunks() const { return p.chunks(); }
 
     int upload(int k)
     {
-        u0 = cuts[k];
-        n = cuts[k + 1] - u0;
-        long long *o = h_meta.data(), *l = o + n, *ro = l + n;
+        u0 = p.cuts[k];
+        n = p.cuts[k + 1] - u0;
+        long long *o = meta.h.data(), *l = o + n, *ro = l + n;
         s = r = 0;
         for (int j = 0; j < n; ++j) {
             const long L = lengths[u0 + j];
             o[j] = s;
             l[j] = L;
             ro[j] = r;
-            if (L > 0) memcpy(h_f32.data() + s, in[u0 + j], (size_t)L * sizeof(float));
-            std::fill(h_f32.begin() + s + L, h_f32.begin() + s + align8(L), 0.0f);
-            s += align8(L);
+            s += pack_padded(f32.h.data() + s, in[u0 + j], L);
             r += rows_of(L);
         }
-        launch_order(l, n, n_cu, h_order.data());
-        if (s > 0) HIP_TRY(hipMemcpy(d_in.p, h_f32.data(), (size_t)s * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_meta.p, h_meta.data(), 3 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_order.p, h_order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-        offs = d_meta.p;
-        lens = d_meta.p + n;
-        roff = d_meta.p + 2 * n;
+        launch_order(l, n, n_cu, order.h.data());
+        if (s > 0) HIP_TRY(hipMemcpy(f32.d.p, f32.h.data(), (size_t)s * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(meta.d.p, meta.h.data(), 3 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(order.d.p, order.h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        offs = meta.d.p;
+        lens = offs + n;
+        roff = offs + 2 * n;
         return 0;
     }
 
     int audio_back(float *const *out_f32, short *const *out_i16)
     {
-        const long long *o = h_meta.data(), *l = o + n;
+        const long long *o = meta.h.data(), *l = o + n;
         if (out_f32 && s > 0) {
-            HIP_TRY(hipMemcpy(h_f32.data(), d_out.p, (size_t)s * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(f32.h.data(), d_out.p, (size_t)s * sizeof(float), hipMemcpyDeviceToHost));
             for (int j = 0; j < n; ++j)
-                if (l[j] > 0) memcpy(out_f32[u0 + j], h_f32.data() + o[j], (size_t)l[j] * sizeof(float));
+                if (l[j] > 0) memcpy(out_f32[u0 + j], f32.h.data() + o[j], (size_t)l[j] * sizeof(float));
         }
         if (out_i16 && s > 0) {
-            HIP_TRY(hipMemcpy(h_i16.data(), d_out16.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(i16.h.data(), i16.d.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost));
             for (int j = 0; j < n; ++j)
-                if (l[j] > 0) memcpy(out_i16[u0 + j], h_i16.data() + o[j], (size_t)l[j] * sizeof(short));
+                if (l[j] > 0) memcpy(out_i16[u0 + j], i16.h.data() + o[j], (size_t)l[j] * sizeof(short));
         }
         return 0;
     }
@@ -213,26 +154,26 @@ int resynth_list(const float *const *in, const long *lengths, const float *const
     const size_t plane = (size_t)q.max_s * kCh;
     DevBuf<float> d_planes; /* hout | hev | gout */
     HIP_TRY(d_planes.alloc(3 * plane));
-    LaunchTimer timer;
+    EventSet<2> timer; /* around the resynthesis launch, which is not exported: sea_hw64_enhance_last_resynth_ms */
     if (timer.create()) return 1;
     for (int k = 0; k < q.chunks(); ++k) {
         if (q.upload(k)) return 1;
         if (q.s > 0) {
-            const long long *ro = q.h_meta.data() + 2 * q.n;
+            const long long *ro = q.meta.h.data() + 2 * q.n;
             for (int j = 0; j < q.n; ++j) {
                 const size_t units = (size_t)rows_of(lengths[q.u0 + j]) * kCh;
-                if (units) memcpy(q.h_mask.data() + ro[j] * kCh, masks[q.u0 + j], units * sizeof(float));
+                if (units) memcpy(q.mask.h.data() + ro[j] * kCh, masks[q.u0 + j], units * sizeof(float));
             }
-            if (q.r > 0) HIP_TRY(hipMemcpy(q.d_mask.p, q.h_mask.data(), (size_t)q.r * kCh * sizeof(float), hipMemcpyHostToDevice));
+            if (q.r > 0) HIP_TRY(hipMemcpy(q.mask.d.p, q.mask.h.data(), (size_t)q.r * kCh * sizeof(float), hipMemcpyHostToDevice));
             float *gout = d_planes.p + 2 * plane;
-            if (sea_hw64_periphery_batch(q.d_in.p, d_planes.p, d_planes.p + plane, gout, q.offs, q.lens, q.d_order.p, q.n, nullptr))
+            if (sea_hw64_periphery_batch(q.f32.d.p, d_planes.p, d_planes.p + plane, gout, q.offs, q.lens, q.order.d.p, q.n, nullptr))
                 return 1;
-            HIP_TRY(hipEventRecord(timer.before, nullptr));
-            if (resynth_launch<Bank64>(gout, q.d_mask.p, q.offs, q.lens, q.roff, threshold, q.d_out.p, q.d_out16.p, q.d_order.p, q.n, nullptr))
+            HIP_TRY(hipEventRecord(timer.e[0], nullptr));
+            if (resynth_launch<Bank64>(gout, q.mask.d.p, q.offs, q.lens, q.roff, threshold, q.d_out.p, q.i16.d.p, q.order.d.p, q.n, nullptr))
                 return 1;
-            HIP_TRY(hipEventRecord(timer.after, nullptr));
+            HIP_TRY(hipEventRecord(timer.e[1], nullptr));
             HIP_TRY(hipDeviceSynchronize());
-            if (timer.add_ms(&t_last_resynth_ms)) return 1;
+            if (timer.add_ms(0, 1, &t_last_resynth_ms)) return 1;
             if (q.audio_back(out_f32, out_i16)) return 1;
         }
         *chunks = k + 1;
@@ -254,7 +195,7 @@ int enhance_list(const float *const *in, const long *lengths, int n_utt, float *
     HIP_TRY(d_scr.alloc((size_t)q.max_work));
     std::vector<int> h_int((size_t)(q.max_r + 1) + (size_t)q.max_n);
     int *d_pitch = d_int.p, *d_status = d_int.p + q.max_r + 1;
-    LaunchTimer timer;
+    EventSet<2> timer; /* around the resynthesis launch, which is not exported: sea_hw64_enhance_last_resynth_ms */
     if (timer.create()) return 1;
     for (int k = 0; k < q.chunks(); ++k) {
         if (q.upload(k)) return 1;
@@ -263,19 +204,19 @@ int enhance_list(const float *const *in, const long *lengths, int n_utt, float *
             *chunks = k + 1;
             continue;
         }
-        if (enhance_launch<Bank64>(q.d_in.p, q.offs, q.lens, q.roff, q.d_out.p, q.d_out16.p, q.d_mask.p, d_pitch, d_status, d_scr.p, q.s, q.r,
-                                q.d_order.p, q.n, nullptr, timer.before, timer.after))
+        if (enhance_launch<Bank64>(q.f32.d.p, q.offs, q.lens, q.roff, q.d_out.p, q.i16.d.p, q.mask.d.p, d_pitch, d_status, d_scr.p, q.s, q.r,
+                                q.order.d.p, q.n, nullptr, timer.e[0], timer.e[1]))
             return 1;
         HIP_TRY(hipDeviceSynchronize());
-        if (timer.add_ms(&t_last_resynth_ms)) return 1;
+        if (timer.add_ms(0, 1, &t_last_resynth_ms)) return 1;
         HIP_TRY(hipMemcpy(status + q.u0, d_status, (size_t)q.n * sizeof(int), hipMemcpyDeviceToHost));
         if (q.audio_back(out_f32, out_i16)) return 1;
-        const long long *ro = q.h_meta.data() + 2 * q.n;
+        const long long *ro = q.meta.h.data() + 2 * q.n;
         if (masks && q.r > 0) {
-            HIP_TRY(hipMemcpy(q.h_mask.data(), q.d_mask.p, (size_t)q.r * kCh * sizeof(float), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(q.mask.h.data(), q.mask.d.p, (size_t)q.r * kCh * sizeof(float), hipMemcpyDeviceToHost));
             for (int j = 0; j < q.n; ++j) {
                 const size_t units = (size_t)rows_of(lengths[q.u0 + j]) * kCh;
-                if (units && masks[q.u0 + j]) memcpy(masks[q.u0 + j], q.h_mask.data() + ro[j] * kCh, units * sizeof(float));
+                if (units && masks[q.u0 + j]) memcpy(masks[q.u0 + j], q.mask.h.data() + ro[j] * kCh, units * sizeof(float));
             }
         }
         if (pitch && q.r > 0) {
@@ -304,9 +245,9 @@ int sea_hw64_enhance_plan(const long *lengths, int n_utt, long long budget_bytes
     if (!lengths) return fail("hw64_enhance_plan: null pointer"), -1;
     for (int u = 0; u < n_utt; ++u)
         if (lengths[u] < 0) return fail("hw64_enhance_plan: utterance %d has length %ld", u, lengths[u]), -1;
-    const std::vector<int> c = plan(lengths, n_utt, budget_bytes, resynth_only);
-    if (cuts) std::copy(c.begin(), c.end(), cuts);
-    return (int)c.size() - 1;
+    const ChunkPlan<2> p = plan(lengths, n_utt, budget_bytes, resynth_only);
+    if (cuts) std::copy(p.cuts.begin(), p.cuts.end(), cuts);
+    return p.chunks();
 }
 
 int sea_hw64_enhance_last_chunks(void) { return t_last_chunks; }

@@ -330,10 +330,8 @@ int sea_trainset_batch(const short *d_clean, const long long *d_offsets, const l
 int sea_trainset_last_chunks(void) { return t_last_chunks; }
 
 /* Device footprint of a chunk: per padded sample 2 B each of clean, scaled noise and noisy plus 128 B per subband set
- * (two or three), per mask row 256 B, per utterance its metadata.  The chunks are whole utterances in list order, cut
- * where the next one would pass 60 % of the HBM that is free after the noise recordings went up (SEA_TRAINSET_SCRATCH_MB
- * overrides the budget); an utterance larger than that forms a chunk of its own and hipMalloc reports what does not fit.
- * The reference handles one utterance at a time; results do not depend on the cut. */
+ * (two or three), per mask row 256 B, per utterance its metadata.  The budget (SEA_TRAINSET_SCRATCH_MB) is read after the
+ * noise recordings went up.  The reference handles one utterance at a time; results do not depend on the cut. */
 int sea_trainset_utterances(const short *const *clean, const long *lengths, int n_utt, const short *const *noises,
                             const long *noise_lengths, int n_noise, const int *rec, const long *off, const int *db, int window,
                             short *const *noisy, float *const *irm, short *const *noise_scaled, short *const *sub_clean,
@@ -366,82 +364,63 @@ int sea_trainset_utterances(const short *const *clean, const long *lengths, int 
         if (noise_lengths[r])
             HIP_TRY(hipMemcpy(d_noise.p + nbase[r], noises[r], (size_t)noise_lengths[r] * sizeof(short), hipMemcpyHostToDevice));
 
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    long long budget = (long long)(free_b / 10 * 6);
-    if (const char *e = getenv("SEA_TRAINSET_SCRATCH_MB")) budget = atoll(e) * (1LL << 20);
+    long long budget;
+    if (scratch_budget("SEA_TRAINSET_SCRATCH_MB", &budget)) return 1;
     auto rows_of = [](long L) -> long long { return (L - 320) / 160 + 1; };
-    auto bytes_of = [&](long L) -> long long { return align8(L) * (6 + 128LL * nsets) + rows_of(L) * 256 + 64; };
-    std::vector<int> cuts(1, 0);
-    long long run = 0, max_s = 0, max_r = 0;
-    int max_n = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        const long long b = bytes_of(lengths[u]);
-        if (u > cuts.back() && run + b > budget) {
-            cuts.push_back(u);
-            run = 0;
-        }
-        run += b;
-    }
-    cuts.push_back(n_utt);
-    const int nchunk = (int)cuts.size() - 1;
-    for (int k = 0; k < nchunk; ++k) {
-        long long s = 0, r = 0;
-        for (int u = cuts[k]; u < cuts[k + 1]; ++u) s += align8(lengths[u]), r += rows_of(lengths[u]);
-        max_s = std::max(max_s, s);
-        max_r = std::max(max_r, r);
-        max_n = std::max(max_n, cuts[k + 1] - cuts[k]);
-    }
-    DevBuf<short> d_clean, d_scaled, d_noisy, d_sub[3];
-    DevBuf<float> d_irm, d_snr, d_sums;
-    DevBuf<long long> d_meta; /* offsets, lengths, noise starts, row offsets */
-    DevBuf<int> d_order;
-    HIP_TRY(d_clean.alloc((size_t)max_s));
-    HIP_TRY(d_scaled.alloc((size_t)max_s));
-    HIP_TRY(d_noisy.alloc((size_t)max_s));
-    for (int s = 0; s < nsets; ++s) HIP_TRY(d_sub[s].alloc((size_t)max_s * 64));
-    HIP_TRY(d_irm.alloc((size_t)max_r * 64));
-    HIP_TRY(d_snr.alloc((size_t)max_n));
-    HIP_TRY(d_sums.alloc(2 * (size_t)max_n));
-    HIP_TRY(d_meta.alloc(4 * (size_t)max_n));
-    HIP_TRY(d_order.alloc((size_t)max_n));
-    std::vector<short> h_clean((size_t)max_s), h_out((size_t)max_s);
-    std::vector<float> h_irm((size_t)max_r * 64), h_snr((size_t)max_n);
-    std::vector<long long> h_meta(4 * (size_t)max_n);
-    std::vector<int> h_order((size_t)max_n);
+    enum { S, R }; /* of an utterance: padded samples, rows, bytes */
+    auto of = [&](int u) -> Totals<3> {
+        const long long s = align8(lengths[u]), r = rows_of(lengths[u]);
+        return {s, r, s * (6 + 128LL * nsets) + r * 256 + 64};
+    };
+    const ChunkPlan<3> plan = plan_chunks<3>(n_utt, budget, of);
+    const size_t max_s = (size_t)plan.max[S], max_n = (size_t)plan.max_n;
+    Staged<short> b_clean, b_noisy; /* b_noisy.h brings the scaled noise back as well */
+    DevBuf<short> d_scaled, d_sub[3];
+    Staged<float> b_irm, b_snr;
+    DevBuf<float> d_sums;
+    Staged<long long> b_meta; /* offsets, lengths, noise starts, row offsets */
+    Staged<int> b_order;
+    HIP_TRY(b_clean.alloc(max_s));
+    HIP_TRY(d_scaled.alloc(max_s));
+    HIP_TRY(b_noisy.alloc(max_s));
+    for (int s = 0; s < nsets; ++s) HIP_TRY(d_sub[s].alloc(max_s * 64));
+    HIP_TRY(b_irm.alloc((size_t)plan.max[R] * 64));
+    HIP_TRY(b_snr.alloc(max_n));
+    HIP_TRY(d_sums.alloc(2 * max_n));
+    HIP_TRY(b_meta.alloc(4 * max_n));
+    HIP_TRY(b_order.alloc(max_n));
+    const long long *d_meta = b_meta.d.p;
+    std::vector<short> &h_out = b_noisy.h;
 
-    for (int k = 0; k < nchunk; ++k) {
-        const int u0 = cuts[k], n = cuts[k + 1] - u0;
-        long long *offs = h_meta.data(), *lens = offs + n, *nst = lens + n, *roff = nst + n;
+    for (int k = 0; k < plan.chunks(); ++k) {
+        const int u0 = plan.cuts[k], n = plan.cuts[k + 1] - u0;
+        long long *offs = b_meta.h.data(), *lens = offs + n, *nst = lens + n, *roff = nst + n;
         long long s = 0, r = 0;
         for (int j = 0; j < n; ++j) {
             const int u = u0 + j;
-            const long L = lengths[u];
             offs[j] = s;
-            lens[j] = L;
+            lens[j] = lengths[u];
             nst[j] = nbase[rec[u]] + off[u];
             roff[j] = r;
-            h_snr[j] = snr_lin_of(db[u]);
-            memcpy(h_clean.data() + s, clean[u], (size_t)L * sizeof(short));
-            memset(h_clean.data() + s + L, 0, (size_t)(align8(L) - L) * sizeof(short));
-            s += align8(L);
-            r += rows_of(L);
+            b_snr.h[j] = snr_lin_of(db[u]);
+            s += pack_padded(b_clean.h.data() + s, clean[u], lens[j]);
+            r += rows_of(lengths[u]);
         }
-        launch_order(lens, n, dc->n_cu, h_order.data());
-        HIP_TRY(hipMemcpy(d_clean.p, h_clean.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_meta.p, h_meta.data(), 4 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_snr.p, h_snr.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d_order.p, h_order.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
-        if (trainset_launch(d_clean.p, d_meta.p, d_meta.p + n, d_noise.p, d_meta.p + 2 * n, d_snr.p, d_scaled.p, d_noisy.p, d_sums.p,
-                            nullptr, d_sub[0].p, d_sub[1].p, sub_noisy ? d_sub[2].p : nullptr, d_meta.p + 3 * n, d_irm.p, window,
-                            d_order.p, n, nullptr))
+        launch_order(lens, n, dc->n_cu, b_order.h.data());
+        HIP_TRY(hipMemcpy(b_clean.d.p, b_clean.h.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b_meta.d.p, b_meta.h.data(), 4 * (size_t)n * sizeof(long long), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b_snr.d.p, b_snr.h.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(b_order.d.p, b_order.h.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        if (trainset_launch(b_clean.d.p, d_meta, d_meta + n, d_noise.p, d_meta + 2 * n, b_snr.d.p, d_scaled.p, b_noisy.d.p, d_sums.p,
+                            nullptr, d_sub[0].p, d_sub[1].p, sub_noisy ? d_sub[2].p : nullptr, d_meta + 3 * n, b_irm.d.p, window,
+                            b_order.d.p, n, nullptr))
             return 1;
         HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipMemcpy(h_out.data(), d_noisy.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_out.data(), b_noisy.d.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost));
         for (int j = 0; j < n; ++j) memcpy(noisy[u0 + j], h_out.data() + offs[j], (size_t)lens[j] * sizeof(short));
-        HIP_TRY(hipMemcpy(h_irm.data(), d_irm.p, (size_t)r * 64 * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(b_irm.h.data(), b_irm.d.p, (size_t)r * 64 * sizeof(float), hipMemcpyDeviceToHost));
         for (int j = 0; j < n; ++j)
-            memcpy(irm[u0 + j], h_irm.data() + roff[j] * 64, (size_t)rows_of((long)lens[j]) * 64 * sizeof(float));
+            memcpy(irm[u0 + j], b_irm.h.data() + roff[j] * 64, (size_t)rows_of((long)lens[j]) * 64 * sizeof(float));
         if (noise_scaled) {
             HIP_TRY(hipMemcpy(h_out.data(), d_scaled.p, (size_t)s * sizeof(short), hipMemcpyDeviceToHost));
             for (int j = 0; j < n; ++j)

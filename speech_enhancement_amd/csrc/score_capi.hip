@@ -20,52 +20,8 @@ thread_local int t_last_chunks = 0;
 constexpr int kStages = SEA_SCORE_STAGE_COUNT;
 thread_local double t_stage_ms[kStages] = {};
 
-struct Events {
-    hipEvent_t e[3] = {};
-    ~Events()
-    {
-        for (hipEvent_t ev : e)
-            if (ev) (void)hipEventDestroy(ev);
-    }
-    int create()
-    {
-        for (hipEvent_t &ev : e) HIP_TRY(hipEventCreate(&ev));
-        return 0;
-    }
-};
-
-/* 60 % of the HBM that is free now, as sea_dnn_enhance_utterances; SEA_SCORE_SCRATCH_MB overrides it */
-int score_budget(long long *budget)
-{
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    *budget = (long long)(free_b / 10 * 6);
-    if (const char *e = getenv("SEA_SCORE_SCRATCH_MB")) *budget = atoll(e) * (1LL << 20);
-    return 0;
-}
-
-/* whole utterances in list order, cut where the next one would pass the budget; an utterance larger than the budget forms a
- * chunk of its own and hipMalloc reports what does not fit */
-template <typename Bytes>
-std::vector<int> cut_list(int n_utt, long long budget, Bytes bytes_of)
-{
-    std::vector<int> cuts(1, 0);
-    long long run = 0;
-    for (int u = 0; u < n_utt; ++u) {
-        const long long b = bytes_of(u);
-        if (u > cuts.back() && run + b > budget) {
-            cuts.push_back(u);
-            run = 0;
-        }
-        run += b;
-    }
-    cuts.push_back(n_utt);
-    return cuts;
-}
-
 long long halves_of(long long L, int hop) { return L / hop; }
 long long frames_of(long long L, int hop) { return L < 2 * hop ? 0 : (L - 2 * hop) / hop + 1; }
-long long tiles_of(long long n, int per) { return (n + per - 1) / per; }
 
 } // namespace
 
@@ -92,71 +48,55 @@ int sea_score_utterances(const short *const *ref, const short *const *est, const
     DeviceCtx *dc;
     if (ctx(&dc)) return 1;
     long long budget;
-    if (score_budget(&budget)) return 1;
-    const std::vector<int> cuts = cut_list(n_utt, budget, [&](int u) -> long long {
-        const long long L = lengths[u];
-        return align8(L) * 4 + frames_of(L, hop) * 4 + tiles_of(halves_of(L, hop), sea::kScoreTileHalves) * sea::kScoreWaves * 24 + 96;
-    });
-    const int nchunk = (int)cuts.size() - 1;
-    long long max_s = 0, max_f = 0, max_t = 0;
-    int max_n = 0;
-    for (int k = 0; k < nchunk; ++k) {
-        long long s = 0, f = 0, t = 0;
-        for (int u = cuts[k]; u < cuts[k + 1]; ++u) {
-            s += align8(lengths[u]), f += frames_of(lengths[u], hop);
-            t += tiles_of(halves_of(lengths[u], hop), sea::kScoreTileHalves);
-        }
-        max_s = std::max(max_s, s), max_f = std::max(max_f, f), max_t = std::max(max_t, t);
-        max_n = std::max(max_n, cuts[k + 1] - cuts[k]);
-    }
-    if (max_t > 0x7fffffffLL) return fail("score: %lld tiles in one launch", max_t);
-    DevBuf<short> d_ref, d_est;
-    DevBuf<float> d_db;
-    DevBuf<long long> d_meta, d_part, d_sums; /* meta: offsets [n], lengths [n], frame offsets [n + 1], tile prefix [n + 1] */
+    if (scratch_budget("SEA_SCORE_SCRATCH_MB", &budget)) return 1;
+    enum { S, F, T }; /* of an utterance: padded samples, frames, tiles, bytes */
+    auto of = [&](int u) -> Totals<4> {
+        const long long L = lengths[u], s = align8(L), f = frames_of(L, hop), t = tiles_of(halves_of(L, hop), sea::kScoreTileHalves);
+        return {s, f, t, s * 4 + f * 4 + t * sea::kScoreWaves * 24 + 96};
+    };
+    const ChunkPlan<4> plan = plan_chunks<4>(n_utt, budget, of);
+    const size_t max_n = (size_t)plan.max_n;
+    if (plan.max[T] > 0x7fffffffLL) return fail("score: %lld tiles in one launch", plan.max[T]);
+    Staged<short> b_ref, b_est;
+    Staged<float> b_db;
+    Staged<long long> b_meta; /* offsets [n], lengths [n], frame offsets [n + 1], tile prefix [n + 1] */
+    DevBuf<long long> d_part, d_sums;
     DevBuf<double> d_seg;
     DevBuf<int> d_used;
-    HIP_TRY(d_ref.alloc((size_t)max_s));
-    HIP_TRY(d_est.alloc((size_t)max_s));
-    HIP_TRY(d_db.alloc((size_t)max_f));
-    HIP_TRY(d_part.alloc((size_t)max_t * sea::kScoreWaves * 3));
-    HIP_TRY(d_meta.alloc(4 * (size_t)max_n + 2));
-    HIP_TRY(d_sums.alloc(3 * (size_t)max_n));
-    HIP_TRY(d_seg.alloc((size_t)max_n));
-    HIP_TRY(d_used.alloc((size_t)max_n));
-    std::vector<short> h_ref((size_t)max_s), h_est((size_t)max_s);
-    std::vector<float> h_db(frame_db ? (size_t)max_f : 0);
-    std::vector<long long> h_meta(4 * (size_t)max_n + 2);
+    HIP_TRY(b_ref.alloc((size_t)plan.max[S]));
+    HIP_TRY(b_est.alloc((size_t)plan.max[S]));
+    HIP_TRY(b_db.alloc((size_t)plan.max[F], frame_db != nullptr));
+    HIP_TRY(d_part.alloc((size_t)plan.max[T] * sea::kScoreWaves * 3));
+    HIP_TRY(b_meta.alloc(4 * max_n + 2));
+    HIP_TRY(d_sums.alloc(3 * max_n));
+    HIP_TRY(d_seg.alloc(max_n));
+    HIP_TRY(d_used.alloc(max_n));
+    const long long *d_meta = b_meta.d.p;
     hipStream_t stream = nullptr;
-    Events ev;
+    EventSet<3> ev;
     if (ev.create()) return 1;
     t_stage_ms[SEA_SCORE_STAGE_FRAMES] = t_stage_ms[SEA_SCORE_STAGE_FINISH] = 0.0;
-    for (int k = 0; k < nchunk; ++k) {
-        const int u0 = cuts[k], n = cuts[k + 1] - u0;
-        long long *offs = h_meta.data(), *lens = offs + n, *foff = lens + n, *tcum = foff + n + 1;
+    for (int k = 0; k < plan.chunks(); ++k) {
+        const int u0 = plan.cuts[k], n = plan.cuts[k + 1] - u0;
+        long long *offs = b_meta.h.data(), *lens = offs + n, *foff = lens + n, *tcum = foff + n + 1;
         long long s = 0, f = 0, t = 0;
         for (int j = 0; j < n; ++j) {
-            const long long L = lengths[u0 + j], Lp = align8(L);
-            offs[j] = s, lens[j] = L, foff[j] = f, tcum[j] = t;
-            if (L > 0) {
-                memcpy(h_ref.data() + s, ref[u0 + j], (size_t)L * sizeof(short));
-                memcpy(h_est.data() + s, est[u0 + j], (size_t)L * sizeof(short));
-            }
-            if (Lp > L) {
-                memset(h_ref.data() + s + L, 0, (size_t)(Lp - L) * sizeof(short));
-                memset(h_est.data() + s + L, 0, (size_t)(Lp - L) * sizeof(short));
-            }
-            s += Lp, f += frames_of(L, hop), t += tiles_of(halves_of(L, hop), sea::kScoreTileHalves);
+            const Totals<4> q = of(u0 + j);
+            offs[j] = s, lens[j] = lengths[u0 + j], foff[j] = f, tcum[j] = t;
+            pack_padded(b_ref.h.data() + s, ref[u0 + j], lens[j]);
+            pack_padded(b_est.h.data() + s, est[u0 + j], lens[j]);
+            s += q[S], f += q[F], t += q[T];
         }
         foff[n] = f, tcum[n] = t;
         if (s > 0) {
-            HIP_TRY(hipMemcpyAsync(d_ref.p, h_ref.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_est.p, h_est.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(b_ref.d.p, b_ref.h.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(b_est.d.p, b_est.h.data(), (size_t)s * sizeof(short), hipMemcpyHostToDevice, stream));
         }
-        HIP_TRY(hipMemcpyAsync(d_meta.p, h_meta.data(), (4 * (size_t)n + 2) * sizeof(long long), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(b_meta.d.p, b_meta.h.data(), (4 * (size_t)n + 2) * sizeof(long long), hipMemcpyHostToDevice, stream));
         sea::ScoreArgs a;
-        a.ref = d_ref.p, a.est = d_est.p;
-        a.offsets = d_meta.p, a.lengths = d_meta.p + n, a.frame_offsets = d_meta.p + 2 * n, a.tile_cum = d_meta.p + 3 * n + 1;
-        a.frame_db = d_db.p, a.partials = d_part.p;
+        a.ref = b_ref.d.p, a.est = b_est.d.p;
+        a.offsets = d_meta, a.lengths = d_meta + n, a.frame_offsets = d_meta + 2 * n, a.tile_cum = d_meta + 3 * n + 1;
+        a.frame_db = b_db.d.p, a.partials = d_part.p;
         a.sums = d_sums.p, a.seg_sum = d_seg.p, a.seg_frames = d_used.p;
         a.n_utt = n, a.hop = hop;
         HIP_TRY(hipEventRecord(ev.e[0], stream));
@@ -172,17 +112,14 @@ int sea_score_utterances(const short *const *ref, const short *const *est, const
         HIP_TRY(hipMemcpyAsync(sums + 3 * (size_t)u0, d_sums.p, 3 * (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(seg_sum + u0, d_seg.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipMemcpyAsync(seg_frames + u0, d_used.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, stream));
-        if (frame_db && f > 0) HIP_TRY(hipMemcpyAsync(h_db.data(), d_db.p, (size_t)f * sizeof(float), hipMemcpyDeviceToHost, stream));
+        if (frame_db && f > 0) HIP_TRY(hipMemcpyAsync(b_db.h.data(), b_db.d.p, (size_t)f * sizeof(float), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        for (int st = 0; st < 2; ++st) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.e[st], ev.e[st + 1]));
-            t_stage_ms[st] += ms;
-        }
+        for (int st = 0; st < 2; ++st)
+            if (ev.add_ms(st, st + 1, &t_stage_ms[st])) return 1;
         if (frame_db)
             for (int j = 0; j < n; ++j)
                 if (frame_db[u0 + j] && foff[j + 1] > foff[j])
-                    memcpy(frame_db[u0 + j], h_db.data() + foff[j], (size_t)(foff[j + 1] - foff[j]) * sizeof(float));
+                    memcpy(frame_db[u0 + j], b_db.h.data() + foff[j], (size_t)(foff[j + 1] - foff[j]) * sizeof(float));
         t_last_chunks = k + 1;
     }
     return 0;
@@ -204,52 +141,44 @@ int sea_mask_score_utterances(const float *const *est, const float *const *ideal
     DeviceCtx *dc;
     if (ctx(&dc)) return 1;
     long long budget;
-    if (score_budget(&budget)) return 1;
-    const std::vector<int> cuts = cut_list(n_utt, budget, [&](int u) -> long long { return n_rows[u] * 512LL + 48; });
-    const int nchunk = (int)cuts.size() - 1;
-    long long max_r = 0, max_t = 0;
-    int max_n = 0;
-    for (int k = 0; k < nchunk; ++k) {
-        long long r = 0, t = 0;
-        for (int u = cuts[k]; u < cuts[k + 1]; ++u) r += n_rows[u], t += tiles_of(n_rows[u], sea::kMaskTileRows);
-        max_r = std::max(max_r, r), max_t = std::max(max_t, t), max_n = std::max(max_n, cuts[k + 1] - cuts[k]);
-    }
-    if (max_t > 0x7fffffffLL) return fail("mask_score: %lld tiles in one launch", max_t);
-    DevBuf<float> d_est, d_ideal;
-    DevBuf<long long> d_meta; /* row offsets [n + 1], tile prefix [n + 1] */
+    if (scratch_budget("SEA_SCORE_SCRATCH_MB", &budget)) return 1;
+    enum { R, T }; /* of an utterance: rows, tiles, bytes */
+    auto of = [&](int u) -> Totals<3> { return {n_rows[u], tiles_of(n_rows[u], sea::kMaskTileRows), n_rows[u] * 512LL + 48}; };
+    const ChunkPlan<3> plan = plan_chunks<3>(n_utt, budget, of);
+    if (plan.max[T] > 0x7fffffffLL) return fail("mask_score: %lld tiles in one launch", plan.max[T]);
+    Staged<float> b_est, b_ideal;
+    Staged<long long> b_meta; /* row offsets [n + 1], tile prefix [n + 1] */
     DevBuf<unsigned long long> d_counts;
-    HIP_TRY(d_est.alloc((size_t)max_r * 64));
-    HIP_TRY(d_ideal.alloc((size_t)max_r * 64));
-    HIP_TRY(d_meta.alloc(2 * (size_t)max_n + 2));
-    HIP_TRY(d_counts.alloc(4 * (size_t)max_n));
-    std::vector<float> h_est((size_t)max_r * 64), h_ideal((size_t)max_r * 64);
-    std::vector<long long> h_meta(2 * (size_t)max_n + 2);
+    HIP_TRY(b_est.alloc((size_t)plan.max[R] * 64));
+    HIP_TRY(b_ideal.alloc((size_t)plan.max[R] * 64));
+    HIP_TRY(b_meta.alloc(2 * (size_t)plan.max_n + 2));
+    HIP_TRY(d_counts.alloc(4 * (size_t)plan.max_n));
     hipStream_t stream = nullptr;
-    Events ev;
+    EventSet<2> ev;
     if (ev.create()) return 1;
     t_stage_ms[SEA_SCORE_STAGE_MASK] = 0.0;
-    for (int k = 0; k < nchunk; ++k) {
-        const int u0 = cuts[k], n = cuts[k + 1] - u0;
-        long long *roff = h_meta.data(), *tcum = roff + n + 1;
+    for (int k = 0; k < plan.chunks(); ++k) {
+        const int u0 = plan.cuts[k], n = plan.cuts[k + 1] - u0;
+        long long *roff = b_meta.h.data(), *tcum = roff + n + 1;
         long long r = 0, t = 0;
         for (int j = 0; j < n; ++j) {
-            const long long rows = n_rows[u0 + j];
+            const Totals<3> q = of(u0 + j);
             roff[j] = r, tcum[j] = t;
-            if (rows > 0) {
-                memcpy(h_est.data() + r * 64, est[u0 + j], (size_t)rows * 64 * sizeof(float));
-                memcpy(h_ideal.data() + r * 64, ideal[u0 + j], (size_t)rows * 64 * sizeof(float));
+            if (q[R] > 0) {
+                memcpy(b_est.h.data() + r * 64, est[u0 + j], (size_t)q[R] * 64 * sizeof(float));
+                memcpy(b_ideal.h.data() + r * 64, ideal[u0 + j], (size_t)q[R] * 64 * sizeof(float));
             }
-            r += rows, t += tiles_of(rows, sea::kMaskTileRows);
+            r += q[R], t += q[T];
         }
         roff[n] = r, tcum[n] = t;
         HIP_TRY(hipMemsetAsync(d_counts.p, 0, 4 * (size_t)n * sizeof(unsigned long long), stream));
         if (t > 0) {
-            HIP_TRY(hipMemcpyAsync(d_est.p, h_est.data(), (size_t)r * 64 * sizeof(float), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_ideal.p, h_ideal.data(), (size_t)r * 64 * sizeof(float), hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(d_meta.p, h_meta.data(), (2 * (size_t)n + 2) * sizeof(long long), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(b_est.d.p, b_est.h.data(), (size_t)r * 64 * sizeof(float), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(b_ideal.d.p, b_ideal.h.data(), (size_t)r * 64 * sizeof(float), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(b_meta.d.p, b_meta.h.data(), (2 * (size_t)n + 2) * sizeof(long long), hipMemcpyHostToDevice, stream));
             sea::MaskScoreArgs a;
-            a.est = d_est.p, a.ideal = d_ideal.p;
-            a.row_offsets = d_meta.p, a.tile_cum = d_meta.p + n + 1;
+            a.est = b_est.d.p, a.ideal = b_ideal.d.p;
+            a.row_offsets = b_meta.d.p, a.tile_cum = b_meta.d.p + n + 1;
             a.counts = d_counts.p;
             a.t_est = t_est, a.t_ideal = t_ideal;
             a.n_utt = n;
@@ -261,11 +190,7 @@ int sea_mask_score_utterances(const float *const *est, const float *const *ideal
         static_assert(sizeof(long long) == sizeof(unsigned long long), "counts are copied as they are");
         HIP_TRY(hipMemcpyAsync(counts + 4 * (size_t)u0, d_counts.p, 4 * (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        if (t > 0) {
-            float ms = 0.0f;
-            HIP_TRY(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]));
-            t_stage_ms[SEA_SCORE_STAGE_MASK] += ms;
-        }
+        if (t > 0 && ev.add_ms(0, 1, &t_stage_ms[SEA_SCORE_STAGE_MASK])) return 1;
         t_last_chunks = k + 1;
     }
     return 0;
